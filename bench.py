@@ -39,6 +39,9 @@ The JSON line also carries
                   baseline sample: mean per-channel PSNR of |x_gpu| against |x_oracle| (peak 1, main_recon_tsmis_FFT.m:362-367),
                   fraction of pixels whose matched atom (T1/T2) is identical, PD relative error
 `--workload slices` instead times whole slices (100 ADMM iterations + dictionary match) over a per-GPU batch.
+`--dump-outputs DIR` writes, after the timed steps, what the timed call returned (rank 0) as DIR/<name>.npy: x after the last timed ADMM
+iteration and the LSQR counts (workload admm), or a seeded sample of the last launch's x and the maps of its last slice (workload slices).
+The line is printed with compact separators: prose about what a field means lives here and beside the code that computes it.
 """
 import argparse
 import json
@@ -87,6 +90,7 @@ HBM_PEAK_GBS = 8000.0                 # MI355X_MICROARCH.md: HBM3E peak (6.3 TB/
 SPLIT_PRODUCTS = 6 if BF16X6 else 3   # MFMA products per fp32-equivalent product (conv6_kernels.hip: bf16 x 6 / f16 x 3)
 SCHEME_TEXT = ("v_mfma_f32_32x32x16_bf16, operands split 3-way into bf16, 6 products, f32 accumulate" if BF16X6 else
                "v_mfma_f32_32x32x16_f16, operands split into f16 (hi, scaled residual), 3 products, f32 accumulate")
+SCHEME_SHORT = "bf16 x 6" if BF16X6 else "f16 x 3"   # (in the roofline objects' kernel names; SCHEME_TEXT is on the line once, in config)
 CONV3X3_FLOP = 2 * 64 * 64 * 9 * 224 * 224      # 3 699 376 128: identical at all four UNetRes levels
 DENOISER_FLOP = 213_253_619_712                 # SURVEY.md section 8d (10-channel UNetRes at 224 x 224)
 TRAFFIC_FILE = os.path.join(ROOT, "profiles", "conv_traffic.json")   # written by tools/pmc_traffic.py from rocprofv3 --pmc passes
@@ -126,7 +130,32 @@ def parse_args():
     ap.add_argument("--one-device", action="store_true", help="every rank uses device 0 (rehearsal only)")
     ap.add_argument("--plumbing-only", action="store_true", help="rank start-up, rendezvous, barrier and max-over-ranks only: no engine, no GPU "
                     "(CPU test of the --gpus N path; the line carries value null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed call returned (rank 0) as DIR/<name>.npy, "
+                    "float32 / float64, at most 64 MB in all; the inputs are seeded, so two builds can be compared output for output")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays) -> list:
+    """--dump-outputs: every array of `arrays` (name -> array) as path/<name>.npy.  Complex arrays get a trailing [real, imag] axis; anything that is not
+    float32 / float64 (counts) is written as float64.  Returns the names written."""
+    out = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if np.iscomplexobj(a):
+            a = np.stack([a.real, a.imag], axis=-1)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        out[name] = np.ascontiguousarray(a)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(out)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -183,7 +212,8 @@ def psnr_peak1(a, b) -> float:
 
 
 def parity_numbers(x_gpu, x_cpu, maps_gpu, maps_cpu, iters, dic=None) -> dict:
-    """SURVEY.md section 8(d) metric 3: GPU output against the CPU restatement's output of the same reconstruction."""
+    """SURVEY.md section 8(d) metric 3: GPU output against the CPU restatement's output of the same reconstruction.  Tolerance: LSQR tol 1e-4
+    leaves a stop-rule ambiguity of ~2e-4 per x-update, so tsmi_rel_l2 <= 1e-3 is parity."""
     s = x_gpu.shape[-1]
     ps = [psnr_peak1(np.abs(x_gpu[..., c]), np.abs(x_cpu[..., c])) for c in range(s)]
     same = maps_gpu["dm"] == maps_cpu["dm"]
@@ -210,15 +240,16 @@ def parity_numbers(x_gpu, x_cpu, maps_gpu, maps_cpu, iters, dic=None) -> dict:
             "atom_index_identical_frac": round(float(same.mean()), 6),
             "t1_mae_on_differing_px_s": round(float(np.abs(t1g[diff] - t1c[diff]).mean()), 6) if diff.any() else 0.0,
             "t2_mae_on_differing_px_s": round(float(np.abs(t2g[diff] - t2c[diff]).mean()), 6) if diff.any() else 0.0,
-            "pd_rel_err": float(np.linalg.norm(pg - pc) / max(np.linalg.norm(pc), 1e-300)),
-            "tolerance": "LSQR tol 1e-4 leaves a stop-rule ambiguity of ~2e-4 per x-update (SURVEY 8 a7): tsmi_rel_l2 <= 1e-3 is parity"}
+            "pd_rel_err": float(np.linalg.norm(pg - pc) / max(np.linalg.norm(pc), 1e-300))}
 
 
 def load_traffic(B: int):
     """HBM-side bytes per launch of the dominant kernel from the committed PMC passes.  The passes are taken per kernel and batch size
     (recorded in the file): profiles/conv_traffic.json = k_conv6<0, 2> at one slice per launch, profiles/conv_traffic_batch<B>.json = the
-    persistent k_conv6p of slice batches.  A run whose dominant kernel / batch has no pass reports null, not another grid's bytes."""
+    persistent k_conv6p of slice batches.  A run whose dominant kernel / batch has no pass reports null, not another grid's bytes.
+    The source named on the line is the file: it records the kernel, the passes and the corrections behind the figure."""
     path = TRAFFIC_FILE if B == 1 else os.path.join(ROOT, "profiles", f"conv_traffic_batch{B}.json")
+    rel = os.path.relpath(path, ROOT)
     try:
         with open(path) as f:
             t = json.load(f)
@@ -226,10 +257,16 @@ def load_traffic(B: int):
             return None, f"no PMC pass for batch {B}"
         fam = t.get("family_per_forward")
         if fam:                                                    # round 5: the whole 3x3 family of a forward pass, the set of launches the roofline times
-            return int(fam["corrected_bytes"]), ("per FORWARD PASS (all units of the roofline together): " + fam.get("what", "") + "; " + t.get("source", ""))
-        return int(t["corrected_bytes_per_launch_per_slice"] * B), (t.get("kernel", "") + ": " + t.get("source", ""))
+            return int(fam["corrected_bytes"]), rel + ": per forward pass, all timed units"
+        return int(t["corrected_bytes_per_launch_per_slice"] * B), rel + ": per launch"
     except (OSError, KeyError, ValueError):
-        return None, (None if B == 1 else f"no PMC pass for batch {B} (profiles/conv_traffic_batch{B}.json)")
+        return None, (None if B == 1 else f"no PMC pass for batch {B} ({rel})")
+
+
+def health_fields(h: dict) -> dict:
+    """Engine.health() for the line: the set-up split belongs to the cold start, and the per-call stage marks are zero outside profile level 3
+    (the slices phase reports them per launch)."""
+    return {k_: v for k_, v in h.items() if k_ not in ("set_denoiser_ms", "last_call_stage_ms")}
 
 
 def atom_tolerance(K: int) -> float:
@@ -242,7 +279,10 @@ def atom_tolerance(K: int) -> float:
 
 
 def conv_roofline(pr, B, kernel_text, traffic=None, traffic_source=None):
-    """`roofline` of the 3x3 convolution family from a level-2 profile (qmri_profile): executed MFMA flop of the timed units / their summed durations."""
+    """`roofline` of the 3x3 convolution family from a level-2 profile (qmri_profile): executed MFMA flop of the timed units / their summed durations.
+    Every launch of the family is ONE unit, timed from its own dispatch timestamps (hipExtLaunchKernelGGL events): a split-K layer from the convolution's
+    start to its reduce kernel's end, a resident-tile launch whole.  `traffic` = HBM-side bytes (2 x FETCH_SIZE + WRITE_SIZE) of all timed units of one
+    forward pass where the committed PMC file carries them, else per launch of the kernel that file names (`traffic_source`)."""
     if pr["n_conv3x3"] <= 0 or pr["ms_conv3x3"] <= 0:
         return None
     t3 = pr["ms_conv3x3"] * 1e-3
@@ -251,10 +291,6 @@ def conv_roofline(pr, B, kernel_text, traffic=None, traffic_source=None):
     nf = max(pr["n_net_forward"], 1)
     roof = {"kernel": kernel_text, "bound": "mfma", "achieved": round(ach, 3), "peak": BF16_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
             "frac": round(ach / BF16_MFMA_PEAK_TFLOPS, 4), "traffic": traffic, "traffic_source": traffic_source,
-            "traffic_unit": "HBM-side bytes (2 x FETCH_SIZE + WRITE_SIZE) of ALL timed units of one forward pass, when the committed PMC file carries them; "
-                            "else per launch of the kernel named in traffic_source",
-            "timing": "every launch of the family is ONE unit, timed from its own dispatch timestamps (hipExtLaunchKernelGGL events): a split-K layer from the "
-                      "convolution's start to its reduce kernel's end, a resident-tile launch whole; achieved = executed flop of the units / sum of their durations",
             "units_timed": int(pr["n_conv3x3"]), "units_per_forward": round(pr["n_conv3x3"] / nf, 2), "ms_timed_per_forward": round(pr["ms_conv3x3"] / nf, 4),
             "executed_flop_per_forward": SPLIT_PRODUCTS * pr["flop_conv3x3"] / nf, "fp32_equivalent_flop_per_forward": pr["flop_conv3x3"] / nf,
             "layer_equivalents_per_forward": round(leq / nf, 3), "us_per_layer_equivalent": round(t3 / leq * 1e6, 3),
@@ -265,17 +301,17 @@ def conv_roofline(pr, B, kernel_text, traffic=None, traffic_source=None):
             "sustained_mfma_tflops_measured": SUSTAINED_MFMA_TFLOPS, "frac_of_sustained": round(ach / SUSTAINED_MFMA_TFLOPS, 4),
             "sustained_mfma_tflops_bare_mfma_loop": SUSTAINED_MFMA_TFLOPS_BARE, "frac_of_sustained_bare_mfma_loop": round(ach / SUSTAINED_MFMA_TFLOPS_BARE, 4)}
     if pr["n_conv2x2"] > 0 and pr["ms_conv2x2"] > 0:
+        # the same ratio over every convolution launch of the forward pass (3x3 family + the 2x2 / stride-2 layers launched alone)
         tall, fall = t3 + pr["ms_conv2x2"] * 1e-3, pr["flop_conv3x3"] + pr["flop_conv2x2"]
-        roof["all_conv_launches"] = {"what": "the same ratio over every convolution launch of the forward pass (3x3 family + the 2x2 / stride-2 layers launched alone)",
-                                     "ms_per_forward": round(tall * 1e3 / nf, 4), "achieved": round(SPLIT_PRODUCTS * fall / tall / 1e12, 3),
+        roof["all_conv_launches"] = {"ms_per_forward": round(tall * 1e3 / nf, 4), "achieved": round(SPLIT_PRODUCTS * fall / tall / 1e12, 3),
                                      "frac": round(SPLIT_PRODUCTS * fall / tall / 1e12 / BF16_MFMA_PEAK_TFLOPS, 4)}
     if pr["n_net_forward"] > 0 and pr["ms_net_forward"] > 0:
+        # the whole forward pass between two stream events (all 64 layers, the |output| report, every launch gap): 3 x 213.25 GFLOP per slice / its
+        # duration -- UNDER THE PER-LAUNCH PROFILE, whose event bookkeeping makes the pass 20 - 25 % longer than inside the ADMM loop: `frac` above
+        # comes from the units' own dispatch timestamps, `whole_denoiser_in_admm_loop` from the loop's own stage
         tf = pr["ms_net_forward"] / pr["n_net_forward"] * 1e-3
         ex = SPLIT_PRODUCTS * DENOISER_FLOP * B
-        roof["whole_denoiser"] = {"what": "the whole forward pass between two stream events (all 64 layers, the |output| report, every launch gap): 3 x 213.25 GFLOP "
-                                          "per slice / its duration -- UNDER THE PER-LAUNCH PROFILE, whose event bookkeeping makes the pass 20 - 25 % longer than inside "
-                                          "the ADMM loop: `frac` above comes from the units' own dispatch timestamps, `whole_denoiser_in_admm_loop` from the loop's own stage",
-                                  "ms_per_forward": round(tf * 1e3, 4), "executed_flop": ex,
+        roof["whole_denoiser"] = {"ms_per_forward": round(tf * 1e3, 4), "executed_flop": ex,
                                   "achieved": round(ex / tf / 1e12, 3), "frac": round(ex / tf / 1e12 / BF16_MFMA_PEAK_TFLOPS, 4)}
     return roof
 
@@ -292,26 +328,32 @@ XUPDATE_TRAFFIC_FILE = os.path.join(ROOT, "profiles", "xupdate_traffic.json")   
 
 def load_xupdate_traffic(key):
     """HBM-side bytes of the LSQR iteration kernels per LSQR iteration (all slices of the launch sequence) from the committed PMC passes, by configuration
-    key ("spiral_T200_B1", "epi_T200_B15", ...).  None when no pass exists for this configuration."""
+    key ("spiral_T200_B1", "epi_T200_B15", ...).  None when no pass exists for this configuration.  Also returns the in-kernel stamps of the
+    one-launch iteration recorded beside the passes (taken on the headline configuration: spiral cut3, one slice)."""
+    rel = os.path.relpath(XUPDATE_TRAFFIC_FILE, ROOT)
     try:
         with open(XUPDATE_TRAFFIC_FILE) as f:
             t = json.load(f)
         e = t["configs"][key]
-        return int(e["bytes_per_lsqr_iteration"]), e.get("kernels", "") + "; " + t.get("source", ""), t.get("one_launch_iteration_phases_us")
+        phases = t.get("one_launch_iteration_phases_us")
+        if phases:
+            phases = {k_: v for k_, v in phases.items() if k_ != "source"}      # (the file says where the stamps come from)
+        return int(e["bytes_per_lsqr_iteration"]), f"{rel}: {e.get('kernels', '').strip()}", phases
     except (OSError, KeyError, ValueError):
-        return None, f"no PMC pass for {key} in profiles/xupdate_traffic.json (tools/pmc_xupdate.sh)", None
+        return None, f"no PMC pass for {key} in {rel} (tools/pmc_xupdate.sh)", None
 
 
-def xupdate_roofline(pr, ns, s, m, B, one_launch, traffic_key=None):
-    """`xupdate` object from a level-1 + level-2 profile of an ADMM run: stage time, LSQR iterations, and the iteration kernels alone against HBM."""
+def xupdate_roofline(pr, ns, s, m, B, one_launch, traffic_key=None, with_stamps=True):
+    """`xupdate` object from a level-1 + level-2 profile of an ADMM run: stage time, LSQR iterations, and the iteration kernels alone against HBM.
+    `form`: the one-launch iteration (k_ks_persist: all iterations of a solve in one launch, the state on chip; the slices of a batch go through it as
+    many per launch as are resident together -- EPI: one, the spiral: two) or two launches per LSQR iteration (k_ks_a, k_ks_b: the state streams through
+    HBM / Infinity Cache).  `with_stamps`: attach the committed in-kernel stamps of the one-launch iteration (they were taken on the headline
+    configuration only)."""
     it = max(pr["admm_iters"], 1)
     li = max(pr["lsqr_iters"], 1)                                   # summed over slices
     byt = xupdate_bytes_per_lsqr_iteration(ns, s, m)
     out = {"lsqr_iters_per_xupdate": round(pr["lsqr_iters"] / it / B, 2), "bytes_per_lsqr_iteration_per_slice": byt,
-           "form": ("k_ks_persist: all iterations of a solve in one launch, the iteration's state on chip" +
-                    ("; the slices of a batch go through it as many per launch as are resident together (EPI: one, the spiral: two)" if B > 1 else ""))
-                   if one_launch else
-                   "two launches per LSQR iteration (k_ks_a, k_ks_b), the state streams through HBM / Infinity Cache"}
+           "form": "one launch per solve (k_ks_persist)" if one_launch else "two launches per LSQR iteration (k_ks_a, k_ks_b)"}
     if pr["n_lsqr_launches"] > 0 and pr["ms_lsqr_kernels"] > 0:
         # per LSQR iteration of the whole batch: the iteration kernels' own dispatch timestamps; iterations = the slowest slice's count summed over
         # the x-updates ~ lsqr_iters / B (slices of a batch iterate together)
@@ -321,7 +363,8 @@ def xupdate_roofline(pr, ns, s, m, B, one_launch, traffic_key=None):
         # What bounds this stage is LATENCY, not bandwidth: the one-launch form keeps the iteration's state in registers and LDS and an iteration is two
         # grid-wide all-reduces of tagged granules.  `achieved` is therefore the ALGORITHMIC rate (the contract's definition: algorithmic bytes / duration)
         # and is labelled as an effective rate; `traffic` is what the PMC counters saw leave / enter the L2s per iteration, and `traffic_gbs` that over the
-        # same duration -- the figure an HBM roofline would bind on, far below the peak.
+        # same duration -- the figure an HBM roofline would bind on, far below the peak.  achieved = algorithmic bytes of an iteration (all slices of the
+        # batch) / duration of the iteration's kernels from their own dispatch timestamps: an EFFECTIVE rate.
         out.update({"us_per_lsqr_iteration": round(us, 2), "us_per_lsqr_iteration_per_slice": round(us / B, 2),
                     "roofline": {"bound": "hbm", "unit": "GB/s", "peak": HBM_PEAK_GBS, "achieved": round(gbs, 1), "frac": round(gbs / HBM_PEAK_GBS, 4),
                                  "effective_gbs": round(gbs, 1), "bytes_per_launch_pair": byt * B, "algorithmic_bytes_per_lsqr_iteration": byt * B,
@@ -330,9 +373,7 @@ def xupdate_roofline(pr, ns, s, m, B, one_launch, traffic_key=None):
                                  "traffic_over_algorithmic": round(traffic / (byt * B), 4) if traffic else None,
                                  "binding_limit": "latency: " + ("two grid-wide all-reduces per LSQR iteration inside one launch" if one_launch else
                                                                   "two dependent launches per LSQR iteration") + f" = {us:.2f} us per iteration",
-                                 "one_launch_iteration_phases_us": phases if one_launch else None,
-                                 "note": "achieved = algorithmic bytes of an iteration (all slices of the batch) / duration of the iteration's kernels from their own "
-                                         "dispatch timestamps: an EFFECTIVE rate" + (" (the one-launch form keeps the state on chip; traffic = PMC bytes per iteration)" if one_launch else "")}})
+                                 "one_launch_iteration_phases_us": phases if one_launch and with_stamps else None}})
     return out
 
 
@@ -392,15 +433,17 @@ def _secondary_config(args, torch, dev, eng, name, T, mask, B, multi, steps, dic
     ns = int(np.unique(k).size)
     m = int(fp[-1])
     one_launch = p2["n_lsqr_launches"] > 0 and p2["n_lsqr_launches"] <= p2["admm_iters"]      # (one k_ks_persist launch per x-update)
-    out = {"workload": name, "value": round(steps * B / dt, 3), "unit": "slice-iterations/s (ADMM iterations x slices advanced together)",
+    # value: ADMM iterations x slices advanced together, per second; the reference's switches for these configurations are
+    # main_recon_tsmis_FFT.m:41-49 (cut, subsampling_pattern) and :75-83 (denoiser_type)
+    out = {"workload": name, "value": round(steps * B / dt, 3), "unit": "slice-iterations/s",
            "ms_per_admm_iteration": round(dt / steps * 1e3, 4), "ms_per_slice_iteration": round(dt / steps / B * 1e3, 4), "steps": steps, "slices_per_launch": B,
            "T": T, "m": m, "sampled_k_locations": ns, "mask": mask, "denoiser": "11-channel multi-level UNetRes (noise-map channel)" if multi else "10-channel UNetRes",
            "stage_ms_per_iter": {"xupdate": round(p1["ms_xupdate"] / it, 4), "denoiser": round(p1["ms_denoiser"] / it, 4),
                                  "elementwise": round(p1["ms_elementwise"] / it, 4)},
            "xupdate_share_of_iteration": round(p1["ms_xupdate"] / max(p1["ms_xupdate"] + p1["ms_denoiser"] + p1["ms_elementwise"], 1e-9), 3),
-           "xupdate": xupdate_roofline({**p2, "admm_iters": p2["admm_iters"], "lsqr_iters": p2["lsqr_iters"]}, ns, s, m, B, one_launch, f"{mask}_T{T}_B{B}"),
-           "health": health,
-           "reference_switches": "main_recon_tsmis_FFT.m:41-49 (cut, subsampling_pattern), :75-83 (denoiser_type)"}
+           "xupdate": xupdate_roofline({**p2, "admm_iters": p2["admm_iters"], "lsqr_iters": p2["lsqr_iters"]}, ns, s, m, B, one_launch, f"{mask}_T{T}_B{B}",
+                                       with_stamps=False),
+           "health": health_fields(health)}
     out["xupdate"]["us_per_lsqr_iteration_incl_fixed_launches"] = round(p1["ms_xupdate"] / it / max(p1["lsqr_iters"] / it / B, 1e-9) * 1e3, 2)
     return out
 
@@ -428,11 +471,11 @@ def multicoil_config(torch, local_rank, steps, ncoil=8):
         t0 = time.perf_counter()
         x, li = eng.pnp_admm_mc(y_mc, iters=steps)
         dt = time.perf_counter() - t0
-        return {"workload": f"EXTENSION (no reference counterpart, parity unpinned): cut0 (T = 1000, m = {eng.m} per coil) x {ncoil} coils, PnP-ADMM over the multi-coil "
-                            "operator (image-domain LSQR) + 10-channel UNetRes, one slice, host arrays in and out",
+        return {"workload": f"EXTENSION (no reference counterpart): cut0 x {ncoil} coils, multi-coil PnP-ADMM + 10-channel UNetRes, host arrays", "m_per_coil": int(eng.m),
                 "value": round(steps / dt, 3), "unit": "ADMM iters/s", "steps": steps, "ms_per_admm_iteration": round(dt / steps * 1e3, 2),
                 "lsqr_iters_mean": round(float(np.mean(li)), 2), "ms_per_lsqr_iteration": round(dt / max(float(np.sum(li)), 1.0) * 1e3, 3),
-                "rel_err_to_ground_truth": round(float(np.linalg.norm((x - X0).ravel()) / np.linalg.norm(X0.ravel())), 4), "health": eng.health()}
+                "rel_err_to_ground_truth": round(float(np.linalg.norm((x - X0).ravel()) / np.linalg.norm(X0.ravel())), 4),
+                "health": health_fields(eng.health())}
     finally:
         eng.close()
 
@@ -551,6 +594,10 @@ def slices_phase(args, rank, local_rank, world, dev, torch, dist, total, batch, 
         per_rank = [g.cpu().tolist() for g in gathered]
     out = None
     if rank == 0:
+        # sharding: a fixed total in contiguous blocks (batch.shard_slices), no collective in the data path.  Results: x (8 MB) and the T1 / T2 / PD
+        # maps of every slice are copied to pinned host memory inside the timed region (copy stream, overlapped).  `health` is qmri_get_health after
+        # the timed launches: every fast path that can give up and repeat its work on the slower path counts it there (zero on a clean run); a slow
+        # launch with zero counters was slow for a reason outside the library.
         K = int(dic["K"])
         out = {"metric": f"slices/sec ({total}-slice synthetic batch: {iters} ADMM iterations + dictionary match per slice)", "value": round(total / dt, 4),
                "unit": "slices/s", "n_gpus": world, "scaling": "strong", "seconds": round(dt, 3), "ms_per_slice": round(dt / max(nsl, 1) * 1e3, 3),
@@ -562,14 +609,12 @@ def slices_phase(args, rank, local_rank, world, dev, torch, dist, total, batch, 
                                 "slices_per_rank": [int(r[6]) for r in per_rank]},
                "health": {**{k_: v for k_, v in h_end.items() if not k_.startswith("last_call") and k_ != "set_denoiser_ms"},
                           "all_ranks": {"denoiser_fallbacks": int(sum(r[1] for r in per_rank)), "resident_tile_timeouts": int(sum(r[2] for r in per_rank)),
-                                        "lsqr_one_launch_timeouts": int(sum(r[3] for r in per_rank)), "repeated_calls": int(sum(r[4] for r in per_rank))},
-                          "what": "qmri_get_health after the timed launches: every fast path that can give up and repeat its work on the slower path counts it here "
-                                  "(zero on a clean run); a slow launch with zero counters was slow for a reason outside the library"},
-               "sharding": "fixed total, contiguous blocks (batch.shard_slices), no collective in the data path",
-               "results": "x (8 MB) and the T1 / T2 / PD maps of every slice copied to pinned host memory inside the timed region (copy stream, overlapped)",
+                                        "lsqr_one_launch_timeouts": int(sum(r[3] for r in per_rank)), "repeated_calls": int(sum(r[4] for r in per_rank))}},
                "workload": f"cut3 {total}-slice batch over {world} GPU(s), {B} slices advanced together, spiral mask, PnP-ADMM + UNetRes + dictionary match K={K}"}
         if launch_health:
-            # the slowest launch of rank 0, stage by stage (device time between the stage marks) beside its host wall clock
+            # the slowest launch of rank 0, stage by stage (device time between the stage marks: profile level 3 on every timed launch) beside its host
+            # wall clock: a launch that is slow INSIDE a stage names the stage, one that is slow outside them (host, queue, another process on the
+            # device) shows in outside_the_stages_ms
             worst = int(np.argmax(batch_s))
             lh = launch_health[worst]
             st_sum = sum(lh["last_call_stage_ms"].values())
@@ -577,9 +622,7 @@ def slices_phase(args, rank, local_rank, world, dev, torch, dist, total, batch, 
                                            "stage_ms": lh["last_call_stage_ms"], "stages_sum_ms": round(st_sum, 3),
                                            "outside_the_stages_ms": round(lh["last_call_wall_ms"] - st_sum, 3),
                                            "median_launch_stage_ms": {k_: round(float(np.median([h["last_call_stage_ms"][k_] for h in launch_health])), 3)
-                                                                      for k_ in lh["last_call_stage_ms"]},
-                                           "what": "stage marks (profile level 3) of every timed launch; a launch that is slow INSIDE a stage names the stage, one that "
-                                                   "is slow outside them (host, queue, another process on the device) shows in outside_the_stages_ms"}
+                                                                      for k_ in lh["last_call_stage_ms"]}}
         if not args.no_roofline and nsl:
             # the batched conv kernel (k_conv6p): live dispatch durations of three forwards of B slices
             eng.profile_get(reset=True)
@@ -593,8 +636,8 @@ def slices_phase(args, rank, local_rank, world, dev, torch, dist, total, batch, 
             pr = eng.profile_get(reset=True)
             eng.profile_enable(0)
             traffic, tsrc = load_traffic(B)
-            out["roofline"] = conv_roofline(pr, B, f"3x3 convolution launches of a {B}-slice forward pass: k_conv6p (persistent implicit GEMM, every 64 -> 64 ... 512 -> 512 "
-                                                   f"layer) + the head and tail on k_conv6, on {SCHEME_TEXT}", traffic, tsrc)
+            # the 3x3 launches of a B-slice forward pass: k_conv6p (persistent implicit GEMM, every 64 -> 64 ... 512 -> 512 layer) + the head and tail on k_conv6
+            out["roofline"] = conv_roofline(pr, B, f"k_conv6p + head / tail on k_conv6, {B} slices, {SCHEME_SHORT}", traffic, tsrc)
             # the dictionary match of one reconstructed slice (d_x[0][0]: the first slice of an earlier launch), HIP events on the engine's stream
             with torch.cuda.stream(stream):
                 for _ in range(3):
@@ -609,11 +652,11 @@ def slices_phase(args, rank, local_rank, world, dev, torch, dist, total, batch, 
             pairs = ((K + 31) // 32) * ((N * N + 31) // 32)
             exec_f16 = pairs * 6 * 32 * 32 * 16 * 2               # filter: 6 x v_mfma_f32_32x32x16_f16 per (32-atom, 32-pixel) tile pair
             alg = 2 * 2 * N * N * K * s
+            # against the pipe it uses: executed f16-MFMA flops of the filter (K-padding 10 -> 16 included; the exact f32 products of the ~1 % listed
+            # tiles not counted) / time; the maps are bit-identical to the oracle's
             out["dict_match"] = {"ms_per_slice": round(ms, 4), "K": K,
                                  "roofline": {"bound": "mfma", "unit": "TFLOP/s", "peak": BF16_MFMA_PEAK_TFLOPS, "achieved": round(exec_f16 / (ms * 1e-3) / 1e12, 1),
                                               "frac": round(exec_f16 / (ms * 1e-3) / 1e12 / BF16_MFMA_PEAK_TFLOPS, 4), "executed_flop": exec_f16, "traffic": None,
-                                              "note": "against the pipe it uses: executed f16-MFMA flops of the filter (K-padding 10 -> 16 included; the exact f32 products "
-                                                      "of the ~1 % listed tiles not counted) / time; maps bit-identical to the oracle's",
                                               "algorithmic_f32_tflops": round(alg / (ms * 1e-3) / 1e12, 1),
                                               "algorithmic_over_f32_mfma_peak": round(alg / (ms * 1e-3) / 1e12 / F32_MFMA_PEAK_TFLOPS, 3)}}
     eng.close()
@@ -654,10 +697,7 @@ def cold_start(torch, local_rank):
         eng.pnp_admm(y, iters=100)
         eng.dict_match(x)
         warm_s = time.perf_counter() - t2
-        return {"what": "one slice from nothing on rank 0, host wall clock, first use of the library in the process: create + plans, then y on the host -> 100 PnP-ADMM "
-                        "iterations -> dictionary match (K = 98 304) -> x and T1 / T2 / PD maps on the host (the reference's unit of work: main_recon_tsmis_FFT.m:37-38, "
-                        "138-152, 285-317)",
-                "setup_ms": {"qmri_create": round((t[1] - t[0]) * 1e3, 2), "qmri_set_operator": round((t[2] - t[1]) * 1e3, 2),
+        return {"setup_ms": {"qmri_create": round((t[1] - t[0]) * 1e3, 2), "qmri_set_operator": round((t[2] - t[1]) * 1e3, 2),
                              "qmri_set_denoiser": round((t[3] - t[2]) * 1e3, 2), "qmri_set_denoiser_split": split,
                              "qmri_set_dictionary": round((t[4] - t[3]) * 1e3, 2), "total": round(setup_s * 1e3, 2)},
                 "first_reconstruction_s": round(recon_s, 4), "of_which_admm_s": round(t_rec - t_in, 4), "of_which_match_and_maps_s": round(t_out - t_rec, 4),
@@ -762,6 +802,7 @@ def worker(args):
         return t.cpu().numpy().view(np.complex128).reshape((N, N, s), order="F")
 
     n = N * N * s
+    dumped = None                                                # (names written by --dump-outputs)
     if args.workload == "admm":
         y, X_gt = make_y(rank, want_gt=True)
         y_parity = y
@@ -790,6 +831,10 @@ def worker(args):
         run(args.steps)
         barrier()
         dt = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0:
+            # what the timed call hands its caller, before the runs below reuse d_x and li: x after the last of the --steps ADMM iterations
+            # (N x N x s complex, PnP_ADMM's return value; 8 MB) and the LSQR iteration count of every x-update
+            dumped = dump_outputs(args.dump_outputs, {"x": x_from_device(d_x), "lsqr_iters": li[: args.steps]})
         lsqr_mean = float(li[: args.steps].mean()) if args.steps else 0.0
         unit_count = args.steps                                  # ADMM iterations per rank
         total_units = args.steps * world
@@ -803,7 +848,7 @@ def worker(args):
             dist.all_gather(gathered, mine_t)
             per_rank = [g.cpu().tolist() for g in gathered]
         result_extra = {"lsqr_iters_mean": lsqr_mean,
-                        "health": {**{k_: v for k_, v in h0.items() if k_ != "set_denoiser_ms"},
+                        "health": {**health_fields(h0),
                                    "all_ranks": {"denoiser_fallbacks": int(sum(r[1] for r in per_rank)), "resident_tile_timeouts": int(sum(r[2] for r in per_rank)),
                                                  "lsqr_one_launch_timeouts": int(sum(r[3] for r in per_rank)), "repeated_calls": int(sum(r[4] for r in per_rank))},
                                    "rank_seconds": [round(r[0], 4) for r in per_rank]}}
@@ -821,7 +866,6 @@ def worker(args):
             dt_diag = float(t.item())
         result_extra["with_diagnostics"] = {"value": round(args.steps * world / dt_diag, 4), "unit": "ADMM iters/s",
                                             "ms_per_step": round(dt_diag / max(args.steps, 1) * 1e3, 4),
-                                            "what": "same steps with want_diag = 1 (PnP_ADMM.m:106-109: data-fidelity and ground-truth errors per iteration)",
                                             "last_data_fidelity_rel": float(diag[max(args.steps, 1) - 1, 0]), "last_gt_rel_err": float(diag[max(args.steps, 1) - 1, 1])}
     else:
         from qmri_pnp_recon_poc_amd.batch import shard_slices
@@ -864,6 +908,17 @@ def worker(args):
         run_slices(nsl, args.steps)
         barrier()
         dt = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0 and nsl:
+            # the last launch's x (up to B slices; a fixed seeded sample of at most 6 of them = 48 MB) and the maps of the last slice matched
+            s_last = (nsl - 1) // B * B
+            cnt = nsl - s_last
+            pick = np.sort(np.random.default_rng(0).choice(cnt, min(cnt, 6), replace=False))
+            xs = d_x[:cnt].cpu().numpy()
+            dumped = dump_outputs(args.dump_outputs, {
+                "x": np.stack([xs[i].view(np.complex128).reshape((N, N, s), order="F") for i in pick]),
+                "x_slice_ids": np.asarray([mine[s_last + i] for i in pick], np.float64),
+                "t1t2": d_q.cpu().numpy().reshape((N, N, 2), order="F"),
+                "pd": d_pd.cpu().numpy().view(np.complex64).reshape((N, N), order="F")})
         unit_count = nsl
         result_extra = {"admm_iters_per_slice": args.steps, "dict_K": int(dic["K"]), "slices_on_rank0": nsl, "batch": B,
                         "total_slices": int(total_units), "sharding": "fixed total, contiguous blocks" if args.total_slices > 0 else "fixed per GPU"}
@@ -899,10 +954,10 @@ def worker(args):
             else:
                 traffic, tsrc = load_traffic(B)
                 resident = debug_knob("conv_resident", 1) != 0 and B == 1
-                roof = conv_roofline(pr, B, (f"3x3 convolution launches of a forward pass on {SCHEME_TEXT}: k_conv6 (one launch per layer; the 28 x 28 level's split-K "
-                                             "layers with their reduce kernel) + k_conv6r (the 16 full-resolution ResBlock layers with the head, the tail and the level's "
-                                             "down-sampling convolution as TWO resident-tile launches)") if resident else
-                                     f"3x3 convolution launches of a forward pass (k_conv6 / k_conv6p, split-K layers with their reduce kernel) on {SCHEME_TEXT}", traffic, tsrc)
+                # the 3x3 launches of a forward pass: k_conv6 (one launch per layer; the 28 x 28 level's split-K layers with their reduce kernel) + k_conv6r
+                # (the 16 full-resolution ResBlock layers with the head, the tail and the level's down-sampling convolution as TWO resident-tile launches)
+                roof = conv_roofline(pr, B, (f"k_conv6 + k_conv6r (resident tiles), {SCHEME_SHORT}" if resident else
+                                             f"k_conv6 / k_conv6p (split-K with reduce), {SCHEME_SHORT}"), traffic, tsrc)
         # stage split of one more run of the SAME workload (profile level 1 synchronises per stage; not part of the timed region): all
         # args.steps iterations, because the x-update is not uniform over a reconstruction -- LSQR needs 16 iterations in the first
         # x-updates and 5-8 in the later ones (lsqr_iters_mean)
@@ -967,8 +1022,8 @@ def worker(args):
             del dic_big
         if args.workload == "admm":
             cpu = {"value": round(n_cpu / tc, 4), "unit": "ADMM iters/s",
-                   "sample": f"first {n_cpu} PnP-ADMM iterations of the same slice (LSQR tol 1e-4 fp64 + UNetRes fp32, diagnostics on), {tc:.1f} s; "
-                             f"one thread: 1 iteration, {t1:.1f} s", **common}
+                   # the sample: the first n_cpu PnP-ADMM iterations of the same slice (LSQR tol 1e-4 fp64 + UNetRes fp32, diagnostics on)
+                   "sample": f"first {n_cpu} iterations, {tc:.1f} s; one thread: 1 iteration, {t1:.1f} s", **common}
             cpu["one_thread_value"] = round(1.0 / t1, 4)
         else:
             per_slice = tc / n_cpu * args.steps + t_match
@@ -1014,11 +1069,11 @@ def worker(args):
             ms_s, roof_s, per_s = forward_ms(eng)
             ms_r, roof_r, per_r = forward_ms(e2)
             ms_step = dt / max(args.steps, 1) * 1e3
+            # one 224 x 224 forward pass, same input, same call path (qmri_net_forward_dev, profile level 2), with the bench network (structured_weights(eps=0.02):
+            # ADMM-stable, interior layers at 1.5e-4 of the output) and with random_weights(seed=1, gain=0.7), under which every layer's activations are of
+            # order one -- what a trained DRUNet resembles
             result_extra["denoiser_weights_timing"] = {
-                "what": "one 224 x 224 forward pass, same input, same call path (qmri_net_forward_dev, profile level 2), with the bench network "
-                        "(structured_weights(eps=0.02): ADMM-stable, interior layers at 1.5e-4 of the output) and with random_weights(seed=1, gain=0.7), under "
-                        "which every layer's activations are of order one -- what a trained DRUNet resembles",
-                "denoiser_ms_structured_weights": round(ms_s, 4), "denoiser_ms_random_weights": round(ms_r, 4), "statistic": "median of 10 passes",
+                "denoiser_ms_structured_weights": round(ms_s, 4), "denoiser_ms_random_weights": round(ms_r, 4),      # (medians of the 10 passes)
                 "passes_ms_structured_weights": per_s, "passes_ms_random_weights": per_r,
                 "conv3x3_frac_structured_weights": roof_s["frac"] if roof_s else None, "conv3x3_frac_random_weights": roof_r["frac"] if roof_r else None,
                 "random_over_structured": round(ms_r / max(ms_s, 1e-9), 4),
@@ -1038,10 +1093,9 @@ def worker(args):
     if args.workload == "admm" and not args.no_secondary and rank == 0:
         # (rank 0 only, no collective inside: a failure here -- say, no memory left on a shared box -- is reported in the object instead of costing
         #  the line its headline metric)
-        for key, cfg_args in (("epi_batch15", ("BASELINE configs[2]: cut3, EPI mask (m = 134 400), 15 slices advanced together, "
-                                               "PnP-ADMM + 11-channel multi-level UNetRes", 200, "epi", 15, True)),
-                              ("cut0", ("BASELINE configs[4] as far as the reference goes: cut0 (T = 1000, m = 618 000), spiral mask, one "
-                                        "slice, PnP-ADMM + 10-channel UNetRes", 1000, "spiral", 1, False))):
+        # (cut0: BASELINE configs[4] as far as the reference goes -- one coil)
+        for key, cfg_args in (("epi_batch15", ("BASELINE configs[2]: cut3, EPI mask, 15 slices per launch, 11-channel multi-level UNetRes", 200, "epi", 15, True)),
+                              ("cut0", ("BASELINE configs[4]: cut0, spiral mask, one slice, 10-channel UNetRes", 1000, "spiral", 1, False))):
             try:
                 secondary[key] = secondary_config(args, torch, dev, local_rank, *cfg_args, args.secondary_steps)
             except Exception as exc:                                # noqa: BLE001
@@ -1078,7 +1132,10 @@ def worker(args):
         if slices_obj is not None:
             out["slices"] = slices_obj
         out.update(secondary)
-        print(json.dumps(out), flush=True)
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
+        # compact separators: the line carries many objects, and a reader that keeps only the end of a long output must still find all of it
+        print(json.dumps(out, separators=(",", ":")), flush=True)
     eng.close()
     if world > 1:
         dist.destroy_process_group()

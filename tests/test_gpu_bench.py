@@ -4,10 +4,13 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# The result line must survive a reader that keeps only the end of a long output: a 21 KB line was lost that way, 11 KB lines were not.
+LINE_LIMIT = 12 * 1024
 
 
 def _run(args, timeout=900):
@@ -16,6 +19,7 @@ def _run(args, timeout=900):
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
+    assert len(lines[0]) < LINE_LIMIT, f"result line of {len(lines[0])} bytes"
     return json.loads(lines[0])
 
 
@@ -110,3 +114,38 @@ def test_bench_slices_fixed_total_sharding():
     out = _run(["--workload", "slices", "--total-slices", "4", "--batch", "3", "--steps", "2", "--warmup", "1", "--dict-k", "64", "32",
                 "--no-roofline", "--no-cpu-baseline"])
     assert out["scaling"] == "strong" and out["total_slices"] == 4 and out["slices_on_rank0"] == 4 and out["value"] > 0 and out["unit"] == "slices/s"
+
+
+def _rel(a, b):
+    return float(np.linalg.norm((a - b).ravel()) / np.linalg.norm(b.ravel()))
+
+
+def test_bench_dump_outputs_of_the_timed_call(tmp_path):
+    """--dump-outputs DIR: what the headline's timed call returned -- x after the last of the --steps ADMM iterations (224 x 224 x 10 complex as a
+    trailing [real, imag] axis, float64) and one LSQR count per timed iteration.  Same arguments, same inputs: a second run reconstructs the same x
+    (up to the LSQR stop-rule ambiguity, ~2e-4 per x-update), and a longer run is a different x."""
+    common = ["--warmup", "1", "--no-roofline", "--no-cpu-baseline", "--no-secondary", "--no-slices", "--no-cold-start"]
+    runs = {}
+    for tag, steps in (("a", 3), ("b", 3), ("c", 5)):
+        out = _run(["--steps", str(steps), "--dump-outputs", str(tmp_path / tag)] + common)
+        assert out["steps"] == steps and out["dumped_outputs"] == ["lsqr_iters", "x"] and out["value"] > 0
+        assert sum(f.stat().st_size for f in (tmp_path / tag).iterdir()) <= 64 << 20
+        x, li = np.load(tmp_path / tag / "x.npy"), np.load(tmp_path / tag / "lsqr_iters.npy")
+        assert x.shape == (224, 224, 10, 2) and x.dtype == np.float64 and np.isfinite(x).all() and np.abs(x).max() > 0
+        assert li.shape == (steps,) and li.dtype == np.float64 and (li >= 1).all() and (li <= 100).all()
+        runs[tag] = (x, li)
+    assert _rel(runs["b"][0], runs["a"][0]) < 1e-3
+    assert _rel(runs["c"][0], runs["a"][0]) > 1e-3 and np.array_equal(runs["c"][1][:3], runs["a"][1])
+
+
+def test_bench_slices_dump_outputs(tmp_path):
+    """--workload slices --dump-outputs: the last launch's x (a fixed sample of at most 6 of its slices, with their ids) and the T1 / T2 / PD maps of
+    the last slice matched; the maps are those the library computes from that slice's x."""
+    out = _run(["--workload", "slices", "--total-slices", "4", "--batch", "3", "--steps", "2", "--warmup", "1", "--dict-k", "64", "32",
+                "--no-roofline", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)])
+    assert out["dumped_outputs"] == ["pd", "t1t2", "x", "x_slice_ids"]
+    x, ids = np.load(tmp_path / "x.npy"), np.load(tmp_path / "x_slice_ids.npy")
+    t1t2, pd = np.load(tmp_path / "t1t2.npy"), np.load(tmp_path / "pd.npy")
+    assert x.shape == (1, 224, 224, 10, 2) and x.dtype == np.float64 and ids.tolist() == [3.0]      # 4 slices, 3 per launch: the last launch holds slice 3
+    assert t1t2.shape == (224, 224, 2) and pd.shape == (224, 224, 2) and t1t2.dtype == pd.dtype == np.float32
+    assert np.isfinite(x).all() and np.isfinite(t1t2).all() and (t1t2 > 0).all() and np.isfinite(pd).all()

@@ -15,7 +15,8 @@ GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
 
 def test_file_written_by_matlab():
-    """scipy's own test datum testhdf5_7.4_GLNX86.mat (MATLAB 7.4, `testdouble = 0:pi/4:2*pi`, cf. testdouble_7.4_GLNX86.mat)"""
+    """scipy's own test datum testhdf5_7.4_GLNX86.mat (MATLAB 7.4, `testdouble = 0:pi/4:2*pi`), against its v5 twin testdouble_7.4_GLNX86.mat
+    (both from scipy's test data, stored under tests/golden/)"""
     path = os.path.join(GOLD, "testhdf5_7.4_GLNX86.mat")
     assert mat73.is_mat73(path)
     with pytest.raises(NotImplementedError):
@@ -24,7 +25,7 @@ def test_file_written_by_matlab():
     assert list(d) == ["testdouble"]
     assert d["testdouble"].shape == (1, 9) and d["testdouble"].dtype == np.float64
     np.testing.assert_array_equal(d["testdouble"][0], np.arange(9) * (np.pi / 4))
-    v5 = scipy.io.loadmat(os.path.join(os.path.dirname(scipy.io.__file__), "matlab", "tests", "data", "testdouble_7.4_GLNX86.mat"))
+    v5 = scipy.io.loadmat(os.path.join(GOLD, "testdouble_7.4_GLNX86.mat"))
     np.testing.assert_array_equal(d["testdouble"], v5["testdouble"])
     assert H.load_mat(path)["testdouble"].shape == (9,)
 
