@@ -69,6 +69,8 @@ int qmri_build_spiral(qmri_ctx* ctx, int N, int S, int T, int32_t* frame_ptr, in
 int qmri_build_epi(qmri_ctx* ctx, int N, int M, double percentage, int T, int32_t* frame_ptr, int32_t* kidx,
                    int cap, int* m_out);
 /* Defines P (setup_subsampling_*.m:36-42): V is T x s column-major real (main_recon_tsmis_FFT.m:129).
+ * Grid: N, M in {32, 64, 96, 112, 128, 160, 192, 224, 256}, chosen independently (N: first, contiguous index; M: second); any other
+ * side returns QMRI_ERR_UNSUPPORTED.  The spiral builder makes square masks only (setup_subsampling_spiralgrided.m:28-31).
  * max_batch = number of slices the context can hold at once (>= 1). */
 int qmri_set_operator(qmri_ctx* ctx, int N, int M, int s, int T, const double* V, const int32_t* frame_ptr,
                       const int32_t* kidx, int max_batch);

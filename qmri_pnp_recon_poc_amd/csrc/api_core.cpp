@@ -3,6 +3,7 @@
 // Replaces (reference file:line): struct F main_recon_tsmis_FFT.m:228-229; setup_subsampling_spiralgrided.m:1-43;
 // setup_subsampling_epi.m:1-36; the lsqr x-update call site PnP_ADMM.m:102 with afun PnP_ADMM.m:153-171.
 #include "qmri_internal.h"
+#include "fft_codelets.h"
 
 #include <algorithm>
 #include <atomic>
@@ -257,7 +258,7 @@ OpDev qmri_opdev(const qmri_ctx* ctx) {
     const OpHost& o = ctx->op;
     OpDev d;
     d.N = o.N; d.M = o.M; d.s = o.s; d.T = o.T; d.m = o.m;
-    d.Vt = o.d_Vt; d.ent = o.d_ent; d.perm = o.d_perm; d.kptr = o.d_kptr; d.tw = o.d_tw;
+    d.Vt = o.d_Vt; d.ent = o.d_ent; d.perm = o.d_perm; d.kptr = o.d_kptr; d.tw_h = o.d_tw; d.tw_w = o.d_tw + o.N;
     d.kslot = o.d_kslot; d.ginv = o.d_ginv;
     return d;
 }
@@ -275,9 +276,8 @@ extern "C" int qmri_set_operator(qmri_ctx* ctx, int N, int M, int s, int T, cons
     QMRI_HIP(ctx, hipSetDevice(ctx->device));
     QMRI_CHECK_ARG(ctx, V && frame_ptr && kidx, "V / frame_ptr / kidx must not be NULL");
     QMRI_CHECK_ARG(ctx, N > 0 && M > 0 && s > 0 && T > 0 && max_batch > 0, "N, M, s, T, max_batch must be positive");
-    if (N != M || !dc_size_supported(N)) {
-        qmri_set_error(ctx, "grid %d x %d unsupported: the FFT kernels implement square grids of 32, 64, 128, 224 "
-                            "(the reference's spiral mask assumes N == M, setup_subsampling_spiralgrided.m:28-31)", N, M);
+    if (!dc_size_supported(N) || !dc_size_supported(M)) {
+        qmri_set_error(ctx, "grid %d x %d unsupported: the FFT kernels implement N, M in {" QFFT_SIDES_TEXT "}, chosen independently", N, M);
         return QMRI_ERR_UNSUPPORTED;
     }
     if (s > 10 || T > 65535 || M > 65535) { qmri_set_error(ctx, "s <= 10 and T, M <= 65535 required (got s=%d T=%d)", s, T); return QMRI_ERR_UNSUPPORTED; }
@@ -321,23 +321,24 @@ extern "C" int qmri_set_operator(qmri_ctx* ctx, int N, int M, int s, int T, cons
     std::vector<double> Vt((size_t)T * s);
     for (int t = 0; t < T; ++t)
         for (int c = 0; c < s; ++c) Vt[(size_t)t * s + c] = V[t + (size_t)T * c];
-    std::vector<double2> tw(N);
+    std::vector<double2> tw((size_t)N + M);           // the h plan's twiddles, then the w plan's (OpDev::tw_h, tw_w)
     const double pi = 3.14159265358979323846;
     for (int j = 0; j < N; ++j) { const double a = 2.0 * pi * j / N; tw[j] = make_double2(std::cos(a), -std::sin(a)); }
+    for (int j = 0; j < M; ++j) { const double a = 2.0 * pi * j / M; tw[(size_t)N + j] = make_double2(std::cos(a), -std::sin(a)); }
 
     const size_t n = (size_t)N * M * s, B = (size_t)max_batch;
     QMRI_TRY(dev_alloc(ctx, &o.d_Vt, Vt.size()));
     QMRI_TRY(dev_alloc(ctx, &o.d_ent, (size_t)m));
     QMRI_TRY(dev_alloc(ctx, &o.d_perm, (size_t)m));
     QMRI_TRY(dev_alloc(ctx, &o.d_kptr, (size_t)NM + 1));
-    QMRI_TRY(dev_alloc(ctx, &o.d_tw, (size_t)N));
+    QMRI_TRY(dev_alloc(ctx, &o.d_tw, tw.size()));
     QMRI_TRY(dev_alloc(ctx, &o.d_kslot, (size_t)NM));
     QMRI_TRY(dev_alloc(ctx, &o.d_ginv, (size_t)o.nsampled * s * s));
     QMRI_HIP(ctx, hipMemcpy(o.d_Vt, Vt.data(), Vt.size() * sizeof(double), hipMemcpyHostToDevice));
     QMRI_HIP(ctx, hipMemcpy(o.d_ent, o.ent_h.data(), (size_t)m * sizeof(KEntry), hipMemcpyHostToDevice));
     QMRI_HIP(ctx, hipMemcpy(o.d_perm, o.perm_h.data(), (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice));
     QMRI_HIP(ctx, hipMemcpy(o.d_kptr, o.kptr_h.data(), ((size_t)NM + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
-    QMRI_HIP(ctx, hipMemcpy(o.d_tw, tw.data(), (size_t)N * sizeof(double2), hipMemcpyHostToDevice));
+    QMRI_HIP(ctx, hipMemcpy(o.d_tw, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice));
     QMRI_HIP(ctx, hipMemcpy(o.d_kslot, kslot.data(), (size_t)NM * sizeof(int32_t), hipMemcpyHostToDevice));
 
     LsqrDev& ls = o.ls;
@@ -447,12 +448,17 @@ extern "C" int qmri_set_operator(qmri_ctx* ctx, int N, int M, int s, int T, cons
         ctx->ks_lds_attr[0] = ctx->ks_lds_attr[1] = false;
     }
     ls.nblk_z = 256;
+    // per-slice partial sums of |z|^2 (ls.pz) and partial min / max (d_mm): nblk_z from the stand-alone kernels, or one per h-pass workgroup
+    // when k_dual_fwd_h / k_adj_h produce them (dc_hpass_blocks: s*M/L, 320 at 256 x 256 where the h-pass takes 8 lines per workgroup)
+    OpDev dims{};
+    dims.N = N; dims.M = M; dims.s = s;
+    const size_t npart = (size_t)std::max(ls.nblk_z, dc_hpass_blocks(dims));
     QMRI_TRY(dev_alloc(ctx, &o.d_tmp, B * n));
     QMRI_TRY(dev_alloc(ctx, &o.d_xa, B * n));
     QMRI_TRY(dev_alloc(ctx, &o.d_xb, B * n));
     QMRI_TRY(dev_alloc(ctx, &o.d_ya, B * (size_t)m));
     QMRI_TRY(dev_alloc(ctx, &ls.st, B));
-    QMRI_TRY(dev_alloc(ctx, &ls.pz, B * ls.nblk_z));
+    QMRI_TRY(dev_alloc(ctx, &ls.pz, B * npart));
     QMRI_TRY(dev_alloc(ctx, &ls.py, B * (size_t)DC_SORT_BLOCKS));
     for (int par = 0; par < 2; ++par) {
         QMRI_TRY(dev_alloc(ctx, &ks.pu[par], B * 2 * ks.G));
@@ -476,7 +482,7 @@ extern "C" int qmri_set_operator(qmri_ctx* ctx, int N, int M, int s, int T, cons
     QMRI_TRY(dev_alloc(ctx, &o.d_vv, B * n));
     QMRI_TRY(dev_alloc(ctx, &o.d_z, B * n));
     QMRI_TRY(dev_alloc(ctx, &o.d_chat, B * n));
-    QMRI_TRY(dev_alloc(ctx, &o.d_mm, B * ls.nblk_z * 2));
+    QMRI_TRY(dev_alloc(ctx, &o.d_mm, B * npart * 2));
     QMRI_TRY(dev_alloc(ctx, &o.d_norm, B * 2));
     QMRI_TRY(dev_alloc(ctx, &o.d_pd, B * ((size_t)N + 2 * ls.nblk_z)));
     QMRI_HIP(ctx, hipMemset(ls.st, 0, B * sizeof(LsqrState)));

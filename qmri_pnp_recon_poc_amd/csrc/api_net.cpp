@@ -414,7 +414,7 @@ static int run_conv(qmri_ctx* ctx, ConvLayer& L, int B, const PTensor& in, const
 static int run_resblocks(qmri_ctx* ctx, size_t& li, int nb, int B, const PTensor& src, const PTensor& cur, const PTensor& tmp,
                          const PTensor* skip) {
     NetPlan& p = ctx->net;
-    if (p.d_res_xbuf && src.H == p.H && !p.force_f32) {            // the full-resolution level: one launch with resident tiles where it applies
+    if (p.d_res_xbuf && src.H == p.H && src.W == p.W && !p.force_f32) {            // the full-resolution level: one launch with resident tiles where it applies
         bool done = false;
         Conv6rRun r;
         r.res = &p.layers[li]; r.nres = 2 * nb; r.src = &src; r.cur = &cur; r.skip = skip;

@@ -820,14 +820,14 @@ int conv6_launch(qmri_ctx* ctx, const ConvLayer& L, int B, const PTensor& in, co
         // then, on another box: 64-pixel x 2 (and 64-pixel unsplit at 56 x 56) 743 | configuration 3 at both levels, K over 2: 751.6 | over 4: 756
         const int deep_cfg = deep_cfg_g;
         const int deep_ks = qmri_knob(K_CONV_DEEPKS);
-        const bool deep = in.H <= 32;
+        const bool deep = (long)in.H * in.W <= 32 * 32;          // (by pixel count: the same choice at square levels, one rule for H != W)
         const int cfg = deep ? deep_cfg : mid_cfg;
         const long nt = (cfg == 0) ? ntiles(16, 16) : (cfg == 1) ? ntiles(16, 8) : (cfg == 2) ? ntiles(8, 8) : 2 * ntiles(16, 8);
         int ksplit = 1;
         while ((deep || cfg < 2) && cfg >= 0 && ksplit * 2 * nt <= 256 && ksplit * 2 <= (deep ? deep_ks : 8) && L.nchunk6 % (ksplit * 2) == 0 &&
                L.nchunk6 / (ksplit * 2) >= 4)
             ksplit *= 2;
-        if (ksplit > 1 && in.H <= 64) {
+        if (ksplit > 1 && (long)in.H * in.W <= 64 * 64) {
             const long out_ks = (long)B * out.Cal * out.plane();
             const size_t need = (size_t)ksplit * out_ks + 8192;
             NetPlan& net = ctx->net;
@@ -870,6 +870,6 @@ int conv6_launch(qmri_ctx* ctx, const ConvLayer& L, int B, const PTensor& in, co
             return QMRI_OK;
         }
     }
-    if (L.nchunk6 >= 16 && L.Cout % 64 == 0 && ((in.H <= 32) ? deep_cfg_g : mid_cfg) == 3) return launch6<3>(ctx, L, B, in, out, add1, add2, relu_out);
+    if (L.nchunk6 >= 16 && L.Cout % 64 == 0 && (((long)in.H * in.W <= 32 * 32) ? deep_cfg_g : mid_cfg) == 3) return launch6<3>(ctx, L, B, in, out, add1, add2, relu_out);
     return launch6<2>(ctx, L, B, in, out, add1, add2, relu_out);
 }

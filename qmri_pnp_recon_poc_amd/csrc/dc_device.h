@@ -113,6 +113,26 @@ template <int R1, int R2> struct Cfg {
     static constexpr int L = (16 * P::LINE * 16 <= 65536 && 16 * (R1 > R2 ? R1 : R2) <= NT) ? 16 : 8;   // lines per h-pass block
 };
 
+// Run f(Plan<R1, R2>{}) with the plan of an axis of side n (QFFT_PLANS).  qmri_set_operator admits only the sides of that table.
+template <class F> int with_plan(qmri_ctx* ctx, int n, F&& f) {
+    switch (n) {
+#define DC_PLAN_CASE_(n_, a_, b_) case n_: return f(Plan<a_, b_>{});
+        QFFT_PLANS(DC_PLAN_CASE_)
+#undef DC_PLAN_CASE_
+        default:
+            qmri_set_error(ctx, "unsupported FFT length %d (supported: " QFFT_SIDES_TEXT ")", n);
+            return QMRI_ERR_UNSUPPORTED;
+    }
+}
+
+// Workgroups of an h-pass kernel on the h plan (R1, R2) per slice: s*M/L.  A workgroup's L lines must lie in one channel (k_adj_h).
+template <int R1, int R2> int hpass_grid(qmri_ctx* ctx, const OpDev& op, int* gx) {
+    constexpr int L = Cfg<R1, R2>::L;
+    if (op.M % L != 0) { qmri_set_error(ctx, "h-pass: M=%d is not a multiple of %d lines per workgroup", op.M, L); return QMRI_ERR_STATE; }
+    *gx = op.s * op.M / L;
+    return QMRI_OK;
+}
+
 
 // two sums at once (one pair of barriers)
 __device__ __forceinline__ void block_sum2(double& a, double& b, double* sh) {

@@ -27,7 +27,7 @@ namespace {
 // ---------------------------------------------------------------------------------------------------
 // forward, pass 1: FFT along h (contiguous) of L lines; transposed store tmp[c][kh][w]
 // ---------------------------------------------------------------------------------------------------
-template <int R1, int R2>
+template <int R1, int R2>   // the h plan
 __global__ __launch_bounds__(NT) void k_fwd_h(OpDev op, const double2* __restrict__ src, double2* __restrict__ tmp) {
     typedef Plan<R1, R2> P;
     constexpr int N = P::N, L = Cfg<R1, R2>::L;
@@ -41,7 +41,7 @@ __global__ __launch_bounds__(NT) void k_fwd_h(OpDev op, const double2* __restric
     }
     cd out[R2];
     int line2, k1;
-    if (fft_lds<R1, R2, true>(lds, L, op.tw, out, line2, k1)) {
+    if (fft_lds<R1, R2, true>(lds, L, op.tw_h, out, line2, k1)) {
         const int l = blockIdx.x * L + line2;
         const int c = l / op.M, w = l - c * op.M;
         double2* dst = tmp + (size_t)b * n + (size_t)c * N * op.M + w;
@@ -107,7 +107,7 @@ __global__ __launch_bounds__(NT) void k_dual_fwd_h(OpDev op, DualArgs d, ActChec
     if (tid == 0) d.pz[(size_t)b * gridDim.x + blockIdx.x] = tot;
     cd out[R2];
     int line2, k1;
-    if (fft_lds<R1, R2, true>(lds, L, op.tw, out, line2, k1)) {
+    if (fft_lds<R1, R2, true>(lds, L, op.tw_h, out, line2, k1)) {
         const int l = blockIdx.x * L + line2;
         const int c = l / M, w = l - c * M;
         double2* dst = tmp + (size_t)b * n + (size_t)c * N * M + w;
@@ -124,12 +124,12 @@ template <int R1, int R2, int MODE>
 __global__ __launch_bounds__(NT) void k_fwd_w(OpDev op, LsqrDev ls, const double2* tmp,
                                                double2* y_out, double* __restrict__ pdiag,
                                                const double2* __restrict__ chat, double rr) {
-    typedef Plan<R1, R2> P;
-    constexpr int N = P::N;
+    typedef Plan<R1, R2> P;                              // the w plan
+    constexpr int M = P::N;
     __shared__ cd lds[DC_MAXS * P::LINE];
     __shared__ double vlds[DC_VCAP];
     __shared__ double red[NT / 64];
-    const int tid = threadIdx.x, b = blockIdx.y, kh = blockIdx.x, s = op.s, M = op.M;
+    const int tid = threadIdx.x, b = blockIdx.y, kh = blockIdx.x, s = op.s, N = op.N;
     const size_t n = (size_t)s * N * M;
     const bool v_in_lds = op.T * s <= DC_VCAP;           // V(t,:) rows are read once per sample: keep them on chip
     if (v_in_lds) for (int i = tid; i < op.T * s; i += NT) vlds[i] = op.Vt[i];
@@ -139,7 +139,7 @@ __global__ __launch_bounds__(NT) void k_fwd_w(OpDev op, LsqrDev ls, const double
     }
     cd out[R2];
     int line2, k1;
-    const bool act = fft_lds<R1, R2, false>(lds, s, op.tw, out, line2, k1);
+    const bool act = fft_lds<R1, R2, false>(lds, s, op.tw_w, out, line2, k1);
     __syncthreads();
     if (act) {
 #pragma unroll
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(NT) void k_fwd_w(OpDev op, LsqrDev ls, const double
                 for (int c = 0; c < s; ++c) lds[c * P::LINE + kw] = mk(rx[c] * ir, -ry[c] * ir);
             }
         }
-        const bool act2 = fft_lds<R1, R2, false>(lds, s, op.tw, out, line2, k1);
+        const bool act2 = fft_lds<R1, R2, false>(lds, s, op.tw_w, out, line2, k1);
         if (act2) {
             double2* dst = y_out + (size_t)b * n + ((size_t)line2 * N + kh) * M;   // y_out doubles as tmp here
 #pragma unroll
@@ -224,13 +224,13 @@ __global__ __launch_bounds__(NT) void k_fwd_w(OpDev op, LsqrDev ls, const double
 template <int R1, int R2>
 __global__ __launch_bounds__(NT) void k_adj_w(OpDev op, const double2* __restrict__ y_in,
                                                double2* __restrict__ tmp) {
-    typedef Plan<R1, R2> P;
-    constexpr int N = P::N;
+    typedef Plan<R1, R2> P;                              // the w plan
+    constexpr int M = P::N;
     __shared__ cd lds[DC_MAXS * P::LINE];
     __shared__ double vlds[DC_VCAP];
     __shared__ double2 ulds[DC_CH];
     __shared__ unsigned short tlds[DC_CH];
-    const int tid = threadIdx.x, b = blockIdx.y, kh = blockIdx.x, s = op.s, M = op.M;
+    const int tid = threadIdx.x, b = blockIdx.y, kh = blockIdx.x, s = op.s, N = op.N;
     const size_t n = (size_t)s * N * M;
     const bool v_in_lds = op.T * s <= DC_VCAP;
     if (v_in_lds) for (int i = tid; i < op.T * s; i += NT) vlds[i] = op.Vt[i];
@@ -239,7 +239,7 @@ __global__ __launch_bounds__(NT) void k_adj_w(OpDev op, const double2* __restric
     // coalesced loads, DC_CH at a time, so the serial walk of a heavily sampled k (200 frames at DC) runs at LDS latency,
     // four independent loads at a time, instead of one dependent global round trip per sample.
     const size_t mb = (size_t)b * op.m;
-    constexpr int NQ = (N * DC_MAXS + NT - 1) / NT;
+    constexpr int NQ = (M * DC_MAXS + NT - 1) / NT;
     double ar[NQ], ai[NQ];
     int e0[NQ], e1[NQ];
 #pragma unroll
@@ -298,7 +298,7 @@ __global__ __launch_bounds__(NT) void k_adj_w(OpDev op, const double2* __restric
     }
     cd out[R2];
     int line2, k1;
-    if (fft_lds<R1, R2, false>(lds, s, op.tw, out, line2, k1)) {
+    if (fft_lds<R1, R2, false>(lds, s, op.tw_w, out, line2, k1)) {
         double2* dst = tmp + (size_t)b * n + ((size_t)line2 * N + kh) * M;
 #pragma unroll
         for (int k2 = 0; k2 < R2; ++k2) st_wt(dst + k1 + R1 * k2, out[k2]);
@@ -330,7 +330,7 @@ __global__ __launch_bounds__(NT) void k_adj_h(OpDev op, const double2* __restric
     cd out[R2];
     int line2, k1;
     double lo = INFINITY, hi = -INFINITY;
-    if (fft_lds<R1, R2, false>(lds, L, op.tw, out, line2, k1)) {
+    if (fft_lds<R1, R2, false>(lds, L, op.tw_h, out, line2, k1)) {
         const double sc = 1.0 / sqrt((double)N * (double)M);
         const size_t g0 = (size_t)b * n + (size_t)(l0 + line2) * N;
         double ur[R2];
@@ -404,13 +404,20 @@ __global__ __launch_bounds__(NT) void k_prepare_z(LsqrDev ls, size_t n, const do
     if (threadIdx.x == 0) ls.pz[(size_t)b * ls.nblk_z + blockIdx.x] = tot;
 }
 
-template <int R1, int R2>
-int launch_fwd_t(qmri_ctx* ctx, const OpDev& op, const LsqrDev& ls, int mode, int B, const double2* src,
-                 double2* tmp, double2* y_out, double* pdiag, const double2* chat, double rr) {
-    constexpr int L = Cfg<R1, R2>::L;
-    dim3 gh(op.s * op.M / L, B), gw(op.N, B), blk(NT);
+template <int R1, int R2>   // the h plan
+int launch_fwd_h_t(qmri_ctx* ctx, const OpDev& op, int B, const double2* src, double2* tmp) {
+    int gx = 0;
+    QMRI_TRY((hpass_grid<R1, R2>(ctx, op, &gx)));
+    k_fwd_h<R1, R2><<<dim3(gx, B), dim3(NT), 0, ctx->stream>>>(op, src, tmp);
+    QMRI_HIP(ctx, hipGetLastError());
+    return QMRI_OK;
+}
+
+template <int R1, int R2>   // the w plan
+int launch_fwd_w_t(qmri_ctx* ctx, const OpDev& op, const LsqrDev& ls, int mode, int B, const double2* tmp, double2* y_out, double* pdiag,
+                   const double2* chat, double rr) {
+    dim3 gw(op.N, B), blk(NT);
     hipStream_t st = ctx->stream;
-    k_fwd_h<R1, R2><<<gh, blk, 0, st>>>(op, src, tmp);
     switch (mode) {
         case DC_FWD_H_ONLY: break;
         case DC_DIAG: k_fwd_w<R1, R2, DC_DIAG><<<gw, blk, 0, st>>>(op, ls, tmp, nullptr, pdiag, nullptr, 0.0); break;
@@ -422,86 +429,85 @@ int launch_fwd_t(qmri_ctx* ctx, const OpDev& op, const LsqrDev& ls, int mode, in
     return QMRI_OK;
 }
 
-template <int R1, int R2>
-int launch_adj_t(qmri_ctx* ctx, const OpDev& op, int B, const double2* y_in, double2* tmp, double2* dst, bool skip_w,
-                 const double2* u = nullptr, double* mm = nullptr) {
-    constexpr int L = Cfg<R1, R2>::L;
-    dim3 gh(op.s * op.M / L, B), gw(op.N, B), blk(NT);
-    hipStream_t st = ctx->stream;
-    if (!skip_w) k_adj_w<R1, R2><<<gw, blk, 0, st>>>(op, y_in, tmp);
-    k_adj_h<R1, R2><<<gh, blk, 0, st>>>(op, tmp, dst, u, mm);
+template <int R1, int R2>   // the w plan
+int launch_adj_w_t(qmri_ctx* ctx, const OpDev& op, int B, const double2* y_in, double2* tmp) {
+    k_adj_w<R1, R2><<<dim3(op.N, B), dim3(NT), 0, ctx->stream>>>(op, y_in, tmp);
     QMRI_HIP(ctx, hipGetLastError());
     return QMRI_OK;
 }
 
+template <int R1, int R2>   // the h plan
+int launch_adj_h_t(qmri_ctx* ctx, const OpDev& op, int B, const double2* tmp, double2* dst, const double2* u, double* mm) {
+    int gx = 0;
+    QMRI_TRY((hpass_grid<R1, R2>(ctx, op, &gx)));
+    k_adj_h<R1, R2><<<dim3(gx, B), dim3(NT), 0, ctx->stream>>>(op, tmp, dst, u, mm);
+    QMRI_HIP(ctx, hipGetLastError());
+    return QMRI_OK;
+}
+
+// the two passes of one transform, each on its own axis's plan
+int launch_fwd(qmri_ctx* ctx, const OpDev& op, const LsqrDev& ls, int mode, int B, const double2* src, double2* tmp, double2* y_out,
+               double* pdiag, const double2* chat, double rr) {
+    QMRI_TRY(with_plan(ctx, op.N, [&](auto p) { return launch_fwd_h_t<decltype(p)::R1, decltype(p)::R2>(ctx, op, B, src, tmp); }));
+    if (mode == DC_FWD_H_ONLY) return QMRI_OK;
+    return with_plan(ctx, op.M, [&](auto p) {
+        return launch_fwd_w_t<decltype(p)::R1, decltype(p)::R2>(ctx, op, ls, mode, B, tmp, y_out, pdiag, chat, rr);
+    });
+}
+
+int launch_adj(qmri_ctx* ctx, const OpDev& op, int B, const double2* y_in, double2* tmp, double2* dst, bool skip_w,
+               const double2* u = nullptr, double* mm = nullptr) {
+    if (!skip_w) QMRI_TRY(with_plan(ctx, op.M, [&](auto p) { return launch_adj_w_t<decltype(p)::R1, decltype(p)::R2>(ctx, op, B, y_in, tmp); }));
+    return with_plan(ctx, op.N, [&](auto p) { return launch_adj_h_t<decltype(p)::R1, decltype(p)::R2>(ctx, op, B, tmp, dst, u, mm); });
+}
+
 }  // namespace
 
-bool dc_size_supported(int N) { return N == 224 || N == 128 || N == 64 || N == 32; }
-
-#define DC_DISPATCH(N_, CALL)                                  \
-    switch (N_) {                                              \
-        case 224: return CALL(16, 14);                         \
-        case 128: return CALL(16, 8);                          \
-        case 64: return CALL(8, 8);                            \
-        case 32: return CALL(8, 4);                            \
-        default:                                               \
-            qmri_set_error(ctx, "unsupported grid size N=%d (supported: 32, 64, 128, 224)", N_); \
-            return QMRI_ERR_UNSUPPORTED;                       \
-    }
+bool dc_size_supported(int n) { return qfft::side_supported(n); }
 
 int dc_launch_fwd(qmri_ctx* ctx, const OpDev& op, const LsqrDev& ls, int mode, int B, const double2* src, double2* tmp,
                   double2* y_out, double* pdiag) {
-#define CALL_F(a, b) launch_fwd_t<a, b>(ctx, op, ls, mode, B, src, tmp, y_out, pdiag, nullptr, 0.0)
-    DC_DISPATCH(op.N, CALL_F)
-#undef CALL_F
+    return launch_fwd(ctx, op, ls, mode, B, src, tmp, y_out, pdiag, nullptr, 0.0);
 }
 
 int dc_launch_adj(qmri_ctx* ctx, const OpDev& op, int B, const double2* y_in, double2* tmp, double2* dst) {
-#define CALL_A(a, b) launch_adj_t<a, b>(ctx, op, B, y_in, tmp, dst, false)
-    DC_DISPATCH(op.N, CALL_A)
-#undef CALL_A
+    return launch_adj(ctx, op, B, y_in, tmp, dst, false);
 }
 
 int dc_launch_adj_h(qmri_ctx* ctx, const OpDev& op, int B, const double2* tmp, double2* dst, const double2* u, double* mm) {
-#define CALL_H(a, b) launch_adj_t<a, b>(ctx, op, B, nullptr, const_cast<double2*>(tmp), dst, true, u, mm)
-    DC_DISPATCH(op.N, CALL_H)
-#undef CALL_H
+    return launch_adj(ctx, op, B, nullptr, const_cast<double2*>(tmp), dst, true, u, mm);
 }
 
-// workgroups of the h-pass kernels per slice (= partial sums of |z|^2 of k_dual_fwd_h, partial min / max of k_adj_h)
+// workgroups of the h-pass kernels per slice (= partial sums of |z|^2 of k_dual_fwd_h, partial min / max of k_adj_h); 0 for an unsupported N
 int dc_hpass_blocks(const OpDev& op) {
     switch (op.N) {
-        case 224: return op.s * op.M / Cfg<16, 14>::L;
-        case 128: return op.s * op.M / Cfg<16, 8>::L;
-        case 64: return op.s * op.M / Cfg<8, 8>::L;
-        default: return op.s * op.M / Cfg<8, 4>::L;
+#define DC_HPASS_CASE_(n_, a_, b_) case n_: return op.s * op.M / Cfg<a_, b_>::L;
+        QFFT_PLANS(DC_HPASS_CASE_)
+#undef DC_HPASS_CASE_
+        default: return 0;
     }
 }
 
-template <int R1, int R2>
+template <int R1, int R2>   // the h plan
 static int launch_dual_t(qmri_ctx* ctx, const OpDev& op, int B, const DualArgs& d, const ActCheckArgs& ac, double2* tmp) {
-    constexpr int L = Cfg<R1, R2>::L;
-    k_dual_fwd_h<R1, R2><<<dim3(op.s * op.M / L, B), dim3(NT), 0, ctx->stream>>>(op, d, ac, tmp);
+    int gx = 0;
+    QMRI_TRY((hpass_grid<R1, R2>(ctx, op, &gx)));
+    k_dual_fwd_h<R1, R2><<<dim3(gx, B), dim3(NT), 0, ctx->stream>>>(op, d, ac, tmp);
     QMRI_HIP(ctx, hipGetLastError());
     return QMRI_OK;
 }
 
 // unnormalise + dual update + z = v - u + h-pass of z's transform into tmp (+ the forward pass's |output| report): see k_dual_fwd_h
 int dc_launch_dual_fwd_h(qmri_ctx* ctx, const OpDev& op, int B, const DualArgs& d, const ActCheckArgs& ac, double2* tmp) {
-#define CALL_U(a, b) launch_dual_t<a, b>(ctx, op, B, d, ac, tmp)
-    DC_DISPATCH(op.N, CALL_U)
-#undef CALL_U
+    return with_plan(ctx, op.N, [&](auto p) { return launch_dual_t<decltype(p)::R1, decltype(p)::R2>(ctx, op, B, d, ac, tmp); });
 }
 
 int dc_launch_direct(qmri_ctx* ctx, const OpDev& op, int B, const double2* z, const double2* chat, double r,
                      double2* tmp, double2* x_out) {
     LsqrDev ls{};
     // tmp holds the h-pass output, then (in place, row by row) the conjugate-domain w-pass output of k_fwd_w
-#define CALL_D(a, b) (launch_fwd_t<a, b>(ctx, op, ls, DC_DIRECT, B, z, tmp, tmp, nullptr, chat, r) != QMRI_OK \
-                          ? (int)QMRI_ERR_HIP                                                                   \
-                          : launch_adj_t<a, b>(ctx, op, B, nullptr, tmp, x_out, true))
-    DC_DISPATCH(op.N, CALL_D)
-#undef CALL_D
+    QMRI_TRY(launch_fwd(ctx, op, ls, DC_DIRECT, B, z, tmp, tmp, nullptr, chat, r));
+    return launch_adj(ctx, op, B, nullptr, tmp, x_out, true);
 }
 
 int dc_launch_sort_y(qmri_ctx* ctx, const OpDev& op, const LsqrDev& ls, int B, const double2* y) {

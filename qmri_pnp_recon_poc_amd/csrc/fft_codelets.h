@@ -1,7 +1,8 @@
 // fft_codelets.h -- in-register forward DFT codelets (double precision) for the data-consistency kernels.
 //
 // These implement the per-channel fft2/ifft2 of the reference's forward operator
-// (main_recon_tsmis_FFT.m:228-229) for N = R1*R2 with R1, R2 in {2,4,7,8,14,16}; 224 = 16 * 14.
+// (main_recon_tsmis_FFT.m:228-229) for N = R1*R2 with R1, R2 in {2,3,4,5,6,7,8,10,12,14,16}; every side the operator supports
+// has one plan (QFFT_PLANS below), e.g. 224 = 16 * 14, 256 = 16 * 16, 96 = 8 * 12.
 // Sign convention: X[k] = sum_n x[n] exp(-2*pi*i*n*k/R).  The inverse is obtained by conjugating on
 // the way in and out.  The header compiles for host and device (QMRI_HD) so that tests/ can check the
 // codelets against a naive DFT with g++ on a machine without a GPU.
@@ -126,14 +127,98 @@ template <> struct Dft<14> {
     }
 };
 
+template <> struct Dft<3> {
+    static QMRI_HD void run(cd* a) {
+        const double S = 0.8660254037844386;                  // sin(2 pi / 3); cos(2 pi / 3) = -1/2
+        const cd p = add(a[1], a[2]), q = sub(a[1], a[2]), a0 = a[0];
+        const cd r = mk(a0.x - 0.5 * p.x, a0.y - 0.5 * p.y);
+        a[0] = add(a0, p);
+        // X_1 = r - i S q ; X_2 = r + i S q    with -i*(x+iy) = (y, -x)
+        a[1] = mk(r.x + S * q.y, r.y - S * q.x);
+        a[2] = mk(r.x - S * q.y, r.y + S * q.x);
+    }
+};
+
+template <> struct Dft<5> {
+    // as Dft<7>: X_k = a0 + sum_j p_j cos(2 pi j k/5) - i sum_j q_j sin(2 pi j k/5),  p_j = a_j + a_{5-j}, q_j = a_j - a_{5-j}
+    static QMRI_HD void run(cd* a) {
+        const double C1 = 0.30901699437494745, C2 = -0.8090169943749475;
+        const double S1 = 0.9510565162951535, S2 = 0.5877852522924731;
+        cd p1 = add(a[1], a[4]), p2 = add(a[2], a[3]);
+        cd q1 = sub(a[1], a[4]), q2 = sub(a[2], a[3]);
+        cd a0 = a[0];
+        cd r1 = mk(a0.x + C1 * p1.x + C2 * p2.x, a0.y + C1 * p1.y + C2 * p2.y);
+        cd r2 = mk(a0.x + C2 * p1.x + C1 * p2.x, a0.y + C2 * p1.y + C1 * p2.y);
+        cd i1 = mk(S1 * q1.x + S2 * q2.x, S1 * q1.y + S2 * q2.y);
+        cd i2 = mk(S2 * q1.x - S1 * q2.x, S2 * q1.y - S1 * q2.y);
+        a[0] = mk(a0.x + p1.x + p2.x, a0.y + p1.y + p2.y);
+        a[1] = mk(r1.x + i1.y, r1.y - i1.x); a[4] = mk(r1.x - i1.y, r1.y + i1.x);
+        a[2] = mk(r2.x + i2.y, r2.y - i2.x); a[3] = mk(r2.x - i2.y, r2.y + i2.x);
+    }
+};
+
+// Dft<2R> from two Dft<R> of the even and odd samples (as Dft<14>); c[k], s[k] = cos, sin(2 pi k / 2R)
+template <int R> QMRI_HD void dft_even_odd(cd* a, const double* c, const double* s) {
+    cd e[R], o[R];
+#pragma unroll
+    for (int k = 0; k < R; ++k) { e[k] = a[2 * k]; o[k] = a[2 * k + 1]; }
+    Dft<R>::run(e);
+    Dft<R>::run(o);
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+        cd t = (k == 0) ? o[0] : mulw(o[k], c[k], s[k]);
+        a[k] = add(e[k], t);
+        a[k + R] = sub(e[k], t);
+    }
+}
+
+template <> struct Dft<6> {
+    static QMRI_HD void run(cd* a) {
+        const double c[3] = { 1.0, 0.5, -0.5 };
+        const double s[3] = { 0.0, 0.8660254037844386, 0.8660254037844386 };
+        dft_even_odd<3>(a, c, s);
+    }
+};
+
+template <> struct Dft<10> {
+    static QMRI_HD void run(cd* a) {
+        const double c[5] = { 1.0, 0.8090169943749475, 0.30901699437494745, -0.30901699437494745, -0.8090169943749475 };
+        const double s[5] = { 0.0, 0.5877852522924731, 0.9510565162951535, 0.9510565162951535, 0.5877852522924731 };
+        dft_even_odd<5>(a, c, s);
+    }
+};
+
+template <> struct Dft<12> {
+    static QMRI_HD void run(cd* a) {
+        const double c[6] = { 1.0, 0.8660254037844386, 0.5, 0.0, -0.5, -0.8660254037844386 };
+        const double s[6] = { 0.0, 0.5, 0.8660254037844386, 1.0, 0.8660254037844386, 0.5 };
+        dft_even_odd<6>(a, c, s);
+    }
+};
+
 // Index maps of the two-step (R1 x R2) transform, N = R1*R2, input index n = R2*n1 + n2, output k = k1 + R1*k2:
 //   step 1 (thread n2): a[n1] = x[R2*n1 + n2]; DFT_R1; a[k1] *= W_N^(n2*k1); store S[n2][k1]
 //   step 2 (thread k1): b[n2] = S[n2][k1];     DFT_R2; X[k1 + R1*k2] = b[k2]
 // S is kept at pitch R1+1 so that both the strided writes and the row reads are bank-conflict free.
-template <int R1, int R2> struct Plan {
+template <int R1_, int R2_> struct Plan {
+    static constexpr int R1 = R1_, R2 = R2_;
     static constexpr int N = R1 * R2;
     static constexpr int SP = R1 + 1;                 // pitch of the intermediate S[n2][.]
     static constexpr int LINE = ((R2 * SP > N ? R2 * SP : N) | 1);   // LDS complex elements reserved per line (odd)
 };
+
+// The sides an axis of the operator may have and the plan of each: X(side, R1, R2).  Each kernel transforms along one axis and is
+// instantiated on that axis's plan (h: length N, w: length M, chosen independently).  32, 64, 128 and 224 keep the factorisation they
+// had when the operator was square-only, so their results are unchanged bit for bit.  Every side is a multiple of 16, the most lines an
+// h-pass workgroup takes (dc_device.h Cfg::L), so the h-pass grid s*M/L divides exactly.
+#define QFFT_PLANS(X) X(32, 8, 4) X(64, 8, 8) X(96, 8, 12) X(112, 16, 7) X(128, 16, 8) X(160, 16, 10) X(192, 16, 12) X(224, 16, 14) X(256, 16, 16)
+#define QFFT_SIDES_TEXT "32, 64, 96, 112, 128, 160, 192, 224, 256"
+
+QMRI_HD bool side_supported(int n) {
+#define QFFT_SIDE_(n_, a_, b_) if (n == n_) return true;
+    QFFT_PLANS(QFFT_SIDE_)
+#undef QFFT_SIDE_
+    return false;
+}
 
 }  // namespace qfft

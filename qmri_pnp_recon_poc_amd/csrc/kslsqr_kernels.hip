@@ -85,18 +85,17 @@ __device__ __forceinline__ void store_v(const OpDev& op, const double* rv, doubl
 // ---------------------------------------------------------------------------------------------------------------
 template <int R1, int R2, bool FWDW>
 __global__ __launch_bounds__(KT) void k_ks_init_a(OpDev op, KsDev ks, const double2* __restrict__ tmp) {
-    typedef Plan<R1, R2> P;
-    constexpr int N = P::N;
+    typedef Plan<R1, R2> P;                                // the w plan
+    constexpr int M = P::N;
     extern __shared__ __align__(16) unsigned char smem[];
-    constexpr int M = N;                                   // square grids only (checked by qmri_set_operator)
-    const int tid = threadIdx.x, kh = blockIdx.x, b = blockIdx.y, s = op.s, sM = s * M;
+    const int tid = threadIdx.x, kh = blockIdx.x, b = blockIdx.y, s = op.s, sM = s * M, N = op.N;
     cd* lines = (cd*)smem;                                 // [c][kw] xhat0 of the row  (FWDW: first the FFT buffer, [c][P::LINE])
     double* vlds = (double*)(lines + (FWDW ? DC_MAXS * P::LINE : sM));
     __shared__ double red[3 * KT / 64];
     const size_t n = (size_t)s * N * M;
     const double sr = ks.sr;
     // ---- request everything (clamped, not predicated): one memory latency for the whole row
-    constexpr int NQ = (DC_MAXS * N + KT - 1) / KT, NE = 10;   // (NE: samples per thread requested up front -- the busiest k-rows of the spiral hold 2 400 samples against a mean of 550, and every further round of the loop below is another dependent memory latency for the whole launch: 4 -> 10, 15.9 -> 12.2 us per launch)
+    constexpr int NQ = (DC_MAXS * M + KT - 1) / KT, NE = 10;   // (NE: samples per thread requested up front -- the busiest k-rows of the spiral hold 2 400 samples against a mean of 550, and every further round of the loop below is another dependent memory latency for the whole launch: 4 -> 10, 15.9 -> 12.2 us per launch)
     double2 xv[NQ], zv[NQ];
     int slot[NQ];
 #pragma unroll
@@ -128,7 +127,7 @@ __global__ __launch_bounds__(KT) void k_ks_init_a(OpDev op, KsDev ks, const doub
         }
         cd out[R2];
         int line2, k1;
-        const bool act = fft_lds<R1, R2, false>(lines, s, op.tw, out, line2, k1);
+        const bool act = fft_lds<R1, R2, false>(lines, s, op.tw_w, out, line2, k1);
         lds_barrier();
         if (act) {
 #pragma unroll
@@ -890,13 +889,13 @@ __global__ __launch_bounds__(KT, CP::MINW) void k_ks_persist(OpDev op, KsDev ks,
 // ---------------------------------------------------------------------------------------------------------------
 template <int R1, int R2>
 __global__ __launch_bounds__(KT) void k_ks_final_w(OpDev op, KsDev ks, double2* __restrict__ tmp) {
-    typedef Plan<R1, R2> P;
-    constexpr int N = P::N, M = N;
+    typedef Plan<R1, R2> P;                                // the w plan
+    constexpr int M = P::N;
     __shared__ cd lds[DC_MAXS * P::LINE];
     __shared__ double red[KT / 64];
     extern __shared__ __align__(16) unsigned char smem[];
     double* vlds = (double*)smem;
-    const int tid = threadIdx.x, kh = blockIdx.x, b = blockIdx.y, s = op.s, sM = s * M;
+    const int tid = threadIdx.x, kh = blockIdx.x, b = blockIdx.y, s = op.s, sM = s * M, N = op.N;
     const size_t n = (size_t)s * N * M;
     const double ue = ks.st[b].ue_final;
     // a workgroup of the one-launch iteration gave up on this solve (k_ks_persist, `aborted`): the host must not believe any "done"
@@ -904,7 +903,7 @@ __global__ __launch_bounds__(KT) void k_ks_final_w(OpDev op, KsDev ks, double2* 
     double rv[NVQ];
     load_v(op, rv);
     // ---- request everything (clamped, not predicated): the slots first, then the compact x / the two spectra
-    constexpr int NQ = (DC_MAXS * N + KT - 1) / KT;
+    constexpr int NQ = (DC_MAXS * M + KT - 1) / KT;
     int slot[NQ];
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
@@ -960,7 +959,7 @@ __global__ __launch_bounds__(KT) void k_ks_final_w(OpDev op, KsDev ks, double2* 
     }
     cd out[R2];
     int line2, k1;
-    if (fft_lds<R1, R2, false>(lds, s, op.tw, out, line2, k1)) {
+    if (fft_lds<R1, R2, false>(lds, s, op.tw_w, out, line2, k1)) {
         double2* dst = tmp + (size_t)b * n + ((size_t)line2 * N + kh) * M;
 #pragma unroll
         for (int k2 = 0; k2 < R2; ++k2) st_wt(dst + k1 + R1 * k2, out[k2]);
@@ -980,7 +979,7 @@ int allow_big_lds(qmri_ctx* ctx, const void* fn, size_t* max_dyn = nullptr) {
     return QMRI_OK;
 }
 
-template <int R1, int R2>
+template <int R1, int R2>   // the w plan
 int launch_final_t(qmri_ctx* ctx, const OpDev& op, const KsDev& ks, int B, double2* tmp) {
     if (!ctx->ks_lds_attr[1]) { QMRI_TRY(allow_big_lds(ctx, (const void*)k_ks_final_w<R1, R2>)); ctx->ks_lds_attr[1] = true; }
     k_ks_final_w<R1, R2><<<dim3(op.N, B), dim3(KT), (size_t)ks.vcap * 8, ctx->stream>>>(op, ks, tmp);
@@ -988,7 +987,7 @@ int launch_final_t(qmri_ctx* ctx, const OpDev& op, const KsDev& ks, int B, doubl
     return QMRI_OK;
 }
 
-template <int N, int R1, int R2, class CP>
+template <int R1, int R2, class CP>   // the w plan
 int lds_fits_t(qmri_ctx* ctx, int s, int M, int vcap, bool* ok) {
     const size_t vb = (size_t)vcap * 8;
     const void* fns[6] = {(const void*)k_ks_init_a<R1, R2, false>, (const void*)k_ks_a<CP>, (const void*)k_ks_b<CP, true>, (const void*)k_ks_b<CP, false>,
@@ -1003,24 +1002,21 @@ int lds_fits_t(qmri_ctx* ctx, int s, int M, int vcap, bool* ok) {
     return QMRI_OK;
 }
 template <class CP>
-int lds_fits_c(qmri_ctx* ctx, int N, int s, int M, int vcap, bool* ok) {
-    switch (N) {
-        case 224: return lds_fits_t<224, 16, 14, CP>(ctx, s, M, vcap, ok);
-        case 128: return lds_fits_t<128, 16, 8, CP>(ctx, s, M, vcap, ok);
-        case 64: return lds_fits_t<64, 8, 8, CP>(ctx, s, M, vcap, ok);
-        default: return lds_fits_t<32, 8, 4, CP>(ctx, s, M, vcap, ok);
-    }
+int lds_fits_c(qmri_ctx* ctx, int s, int M, int vcap, bool* ok) {
+    return with_plan(ctx, M, [&](auto p) { return lds_fits_t<decltype(p)::R1, decltype(p)::R2, CP>(ctx, s, M, vcap, ok); });
 }
 
 }  // namespace
 
 // Does V (vcap doubles) fit next to the other LDS arrays of every k-space LSQR kernel for this grid, with the unit capacities `caps` (KS_CAPS)?
+// (The row kernels run on the w plan; N, the number of rows, does not enter their LDS.)
 int ks_lds_fits(qmri_ctx* ctx, int N, int s, int M, int vcap, int caps, bool* ok) {
+    (void)N;
     switch (caps) {
-        case 1: return lds_fits_c<Caps1>(ctx, N, s, M, vcap, ok);
-        case 2: return lds_fits_c<Caps2>(ctx, N, s, M, vcap, ok);
-        case 3: return lds_fits_c<Caps3>(ctx, N, s, M, vcap, ok);
-        default: return lds_fits_c<Caps0>(ctx, N, s, M, vcap, ok);
+        case 1: return lds_fits_c<Caps1>(ctx, s, M, vcap, ok);
+        case 2: return lds_fits_c<Caps2>(ctx, s, M, vcap, ok);
+        case 3: return lds_fits_c<Caps3>(ctx, s, M, vcap, ok);
+        default: return lds_fits_c<Caps0>(ctx, s, M, vcap, ok);
     }
 }
 
@@ -1030,12 +1026,15 @@ template <class CP> static int ks_attrs_c(qmri_ctx* ctx) {
     QMRI_TRY(allow_big_lds(ctx, (const void*)k_ks_b<CP, false>));
     return QMRI_OK;
 }
-static int ks_attrs(qmri_ctx* ctx, int caps) {
+template <int R1, int R2> static int ks_attrs_p(qmri_ctx* ctx) {   // the w plan
+    QMRI_TRY(allow_big_lds(ctx, (const void*)k_ks_init_a<R1, R2, false>));
+    QMRI_TRY(allow_big_lds(ctx, (const void*)k_ks_init_a<R1, R2, true>));
+    return QMRI_OK;
+}
+// large dynamic LDS for the kernels this operator launches: the row kernels of its w plan and those of its unit shape (reset by qmri_set_operator)
+static int ks_attrs(qmri_ctx* ctx, const OpDev& op, int caps) {
     if (ctx->ks_lds_attr[0]) return QMRI_OK;
-    QMRI_TRY(allow_big_lds(ctx, (const void*)k_ks_init_a<16, 14, false>)); QMRI_TRY(allow_big_lds(ctx, (const void*)k_ks_init_a<16, 14, true>));
-    QMRI_TRY(allow_big_lds(ctx, (const void*)k_ks_init_a<16, 8, false>)); QMRI_TRY(allow_big_lds(ctx, (const void*)k_ks_init_a<16, 8, true>));
-    QMRI_TRY(allow_big_lds(ctx, (const void*)k_ks_init_a<8, 8, false>)); QMRI_TRY(allow_big_lds(ctx, (const void*)k_ks_init_a<8, 8, true>));
-    QMRI_TRY(allow_big_lds(ctx, (const void*)k_ks_init_a<8, 4, false>)); QMRI_TRY(allow_big_lds(ctx, (const void*)k_ks_init_a<8, 4, true>));
+    QMRI_TRY(with_plan(ctx, op.M, [&](auto p) { return ks_attrs_p<decltype(p)::R1, decltype(p)::R2>(ctx); }));
     if (caps == 1) QMRI_TRY(ks_attrs_c<Caps1>(ctx));
     else if (caps == 2) QMRI_TRY(ks_attrs_c<Caps2>(ctx));
     else if (caps == 3) QMRI_TRY(ks_attrs_c<Caps3>(ctx));
@@ -1055,20 +1054,14 @@ static int ks_attrs(qmri_ctx* ctx, int caps) {
 // residual + first Golub-Kahan vectors; ks.xhat / ks.zhat hold the unitary spectra of x0 and z
 // hpass_tmp (nullable): the h-pass output of z's transform; the launch then also runs the w-pass and writes ks.zhat (k_ks_init_a<FWDW>)
 int ks_launch_init(qmri_ctx* ctx, const OpDev& op, const KsDev& ks, int B, const double2* hpass_tmp, bool first_step) {
-    QMRI_TRY(ks_attrs(ctx, ks.caps));
+    QMRI_TRY(ks_attrs(ctx, op, ks.caps));
     const size_t vb = (size_t)ks.vcap * 8;
-#define KS_INIT(R1_, R2_)                                                                                                       \
-    do {                                                                                                                        \
-        if (hpass_tmp) k_ks_init_a<R1_, R2_, true><<<dim3(op.N, B), dim3(KT), (size_t)DC_MAXS * Plan<R1_, R2_>::LINE * 16 + vb, ctx->stream>>>(op, ks, hpass_tmp); \
-        else k_ks_init_a<R1_, R2_, false><<<dim3(op.N, B), dim3(KT), (size_t)op.s * op.M * 16 + vb, ctx->stream>>>(op, ks, nullptr);                              \
-    } while (0)
-    switch (op.N) {
-        case 224: KS_INIT(16, 14); break;
-        case 128: KS_INIT(16, 8); break;
-        case 64: KS_INIT(8, 8); break;
-        default: KS_INIT(8, 4); break;
-    }
-#undef KS_INIT
+    QMRI_TRY(with_plan(ctx, op.M, [&](auto p) {
+        typedef decltype(p) P;                                   // the w plan
+        if (hpass_tmp) k_ks_init_a<P::R1, P::R2, true><<<dim3(op.N, B), dim3(KT), (size_t)DC_MAXS * P::LINE * 16 + vb, ctx->stream>>>(op, ks, hpass_tmp);
+        else k_ks_init_a<P::R1, P::R2, false><<<dim3(op.N, B), dim3(KT), (size_t)op.s * op.M * 16 + vb, ctx->stream>>>(op, ks, nullptr);
+        return (int)QMRI_OK;
+    }));
     // (first_step = false: k_ks_persist takes the first Golub-Kahan step itself, ks_launch_persist(..., init_here = true))
     if (first_step) KS_BY_CAPS(ks.caps, (k_ks_b<CP, true><<<dim3(ks.G, B), dim3(KT), vb, ctx->stream>>>(op, ks)));
     QMRI_HIP(ctx, hipGetLastError());
@@ -1149,13 +1142,5 @@ int ks_launch_persist(qmri_ctx* ctx, const OpDev& op, const KsDev& ks_in, int B,
 size_t ks_gran_bytes(int G, int B) { return (size_t)B * 6 * G * sizeof(KsGran) + 64; }     // + the sticky time-out word
 
 int ks_launch_final(qmri_ctx* ctx, const OpDev& op, const KsDev& ks, int B, double2* tmp) {
-    switch (op.N) {
-        case 224: return launch_final_t<16, 14>(ctx, op, ks, B, tmp);
-        case 128: return launch_final_t<16, 8>(ctx, op, ks, B, tmp);
-        case 64: return launch_final_t<8, 8>(ctx, op, ks, B, tmp);
-        case 32: return launch_final_t<8, 4>(ctx, op, ks, B, tmp);
-        default:
-            qmri_set_error(ctx, "unsupported grid size N=%d (supported: 32, 64, 128, 224)", op.N);
-            return QMRI_ERR_UNSUPPORTED;
-    }
+    return with_plan(ctx, op.M, [&](auto p) { return launch_final_t<decltype(p)::R1, decltype(p)::R2>(ctx, op, ks, B, tmp); });
 }

@@ -82,7 +82,8 @@ struct OpDev {
     const KEntry* ent;       // [m]     k-sorted: (kh, kw, t) ascending
     const int32_t* perm;     // [m]     k-sorted position -> frame-major measurement index (ABI order)
     const int32_t* kptr;     // [N*M+1] CSR over k' = kh*M + kw into ent
-    const double2* tw;       // [N]     exp(-2*pi*i*j/N)
+    const double2* tw_h;     // [N]     exp(-2*pi*i*j/N): twiddles of the h plan
+    const double2* tw_w;     // [M]     exp(-2*pi*i*j/M): twiddles of the w plan
     const int32_t* kslot;    // [N*M]   DIRECT solver: slot of k' among sampled locations or -1
     const double* ginv;      // [nsampled][s*s] (G_k + r I)^-1, symmetric, row-major
 };

@@ -259,7 +259,8 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
     elif recon_method == "LRTV":                                                     # :273-282
         param = {"K": 4e-5, "iter": 200 if lrtv_iters is None else int(lrtv_iters), "step": X0.size / np.asarray(Y).size, "tol": 1e-4,
                  "backtrack": 1, "usegpu": 0}
-        X = R.FISTA_deep({"N": M, "M": M, "L": s, "y": np.asarray(Y, dtype=np.complex128), "F": F, "D": []}, param)
+        X = R.FISTA_deep({"N": N, "M": M, "L": s,   # (the script sets data.N = M, :281: the same on its square grid)
+                          "y": np.asarray(Y, dtype=np.complex128), "F": F, "D": []}, param)
     else:
         raise ValueError(f"unknown reconstruction method {recon_method}")
     par = {"f": {"qout": 1, "pdout": 1, "mtout": 0, "Xout": 0, "dmout": 0, "Yout": 0, "verbose": 0}, "fp": {"blockSize": 1e9}}   # :302-309

@@ -5,9 +5,12 @@ function F = qmri_make_F(pattern, N, M, rate, V)
 %       F.forward = @(x) P.for(reshape(fft2(x),[],1))/sqrt(N*M);
 %       F.adjoint = @(x) (ifft2(reshape(P.adj(x),N,M,[]))*sqrt(N*M));
 %   by   F = qmri_make_F('Spiral', N, M, spiral_sampling_curve, V);          (or 'EPI', ..., epi_sampling_rate, V)
+%   N, M in {32 64 96 112 128 160 192 224 256}, chosen independently (EPI); the spiral is square, N == M.
 T = size(V, 1);  s = size(V, 2);
 switch pattern
-    case 'Spiral', [fp, k] = qmri_mex('build_spiral', N, rate, T);
+    case 'Spiral'
+        if N ~= M, error('qmri:pattern', 'the spiral mask is square (setup_subsampling_spiralgrided.m:28-31): N must equal M'); end
+        [fp, k] = qmri_mex('build_spiral', N, rate, T);
     case 'EPI',    [fp, k] = qmri_mex('build_epi', N, M, rate, T);
     otherwise, error('qmri:pattern', 'unknown subsampling pattern %s', pattern);
 end

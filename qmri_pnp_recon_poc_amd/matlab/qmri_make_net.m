@@ -8,6 +8,7 @@ function net = qmri_make_net(weights, denoiser_type, residual_noise, imsize, arc
 %   UNetRes state_dict order (Conv2d OIHW, ConvTranspose2d IOHW): 32 648 448 values for the 10-channel and 32 649 024 for
 %   the 11-channel DRUNet (main_test.py:245-252).
 %   imsize (optional, default [224 224], the script's cropped TSMI, :189,:212): [H W] of the images the handle will see.
+%          [H W] = the operator's [N M] (qmri_make_F); H, W multiples of 8, H ~= W allowed.
 %   arch   (optional, only with a weight vector): struct('out_nc', 10, 'nc', [64 128 256 512], 'nb', 4) = UNetRes as trained
 %          (network_unet.py:68); the input has out_nc channels ('single_level') or out_nc + 1 ('multi_level': the noise map).
 if nargin < 4 || isempty(imsize), imsize = [224 224]; end

@@ -36,6 +36,8 @@ def release():
 def setup_subsampling_spiralgrided(N, M, S, V):
     """Gridded spiral masks (setup_subsampling_spiralgrided.m:7-34).  The reference returns closures over the sparse
     matrix P; here P is its defining data (masks + V) and the products happen inside F."""
+    if int(N) != int(M):
+        raise ValueError(f"the spiral mask is square (setup_subsampling_spiralgrided.m:28-31): N = {N} != M = {M}")
     V = np.real(np.asarray(V, dtype=np.complex128)).astype(np.float64)        # V = real(dict.V), main_recon_tsmis_FFT.m:129
     fp, k = E.build_spiral(int(N), int(S), V.shape[0])
     return SimpleNamespace(N=int(N), M=int(M), V=V, frame_ptr=fp, kidx=k, pattern="Spiral")
