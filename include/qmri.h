@@ -171,6 +171,17 @@ int qmri_pnp_admm_batch(qmri_ctx* ctx, int nslices, int slices_per_launch, const
                         const void* gt, void* x_out, double* diag_out, int32_t* lsqr_iters_out);
 /* Multi-coil extension of the loop (see qmri_xupdate_mc above: no reference counterpart, parity unpinned). */
 int qmri_pnp_admm_mc(qmri_ctx* ctx, const void* y_mc, const qmri_admm_params* prm, const void* x0, void* x_out, int32_t* lsqr_iters_out);
+/* Slice stacks of the multi-coil extension, each slice with its own maps (no reference counterpart, parity unpinned).  Slice-major layouts:
+ * maps nslices x ncoil x N*M, y_mc nslices x ncoil x m, z / x0 / x_out nslices x N*M*s (complex doubles).  The LSQR keeps every scalar on the device
+ * and its reductions in one fixed order per slice: a slice's result does not depend on the batch it is solved in or on max_batch.  These calls
+ * neither read nor change the maps of qmri_set_coils.  iters_out / flags_out: nslices entries (nullable); lsqr_iters_out: nslices x prm->iters. */
+int qmri_xupdate_mc_batch(qmri_ctx* ctx, int nslices, int ncoil, const void* maps, const void* y_mc, const void* z, double r, double tol, int maxit,
+                          const void* x0, void* x_out, int32_t* iters_out, int32_t* flags_out);
+int qmri_pnp_admm_mc_batch(qmri_ctx* ctx, int nslices, int slices_per_launch, int ncoil, const void* maps, const void* y_mc,
+                           const qmri_admm_params* prm, const void* x0, void* x_out, int32_t* lsqr_iters_out);
+/* the same with device arrays, nslices <= max_batch of the operator and the denoiser; d_x_out must not alias d_x0 */
+int qmri_pnp_admm_mc_dev(qmri_ctx* ctx, int nslices, int ncoil, const void* d_maps, const void* d_y, const qmri_admm_params* prm,
+                         const void* d_x0, void* d_x_out, int32_t* lsqr_iters_out);
 
 /* ---- LRTV option: x = FISTA_deep(data, param), main_recon_tsmis_FFT.m:273-282 -------------------------- */
 /* FISTA with backtracking on 0.5 |y - F.forward(x)|^2 + K |x|_TV (FISTA_deep.m:31-104); the TV prox is unlocbox's
@@ -250,6 +261,11 @@ typedef struct {
  * pd_out: nslices x Npix complex single or NULL.  One host thread + one context per device in devs[]. */
 int qmri_recon_batch(int ndev, const int* devs, int nslices, const qmri_problem* prob, const void* Y,
                      void* X_out, float* qmap_out, float* pd_out, char* errbuf, size_t errbuf_len);
+/* Multi-coil extension of qmri_recon_batch (no reference counterpart, parity unpinned): maps nslices x ncoil x N*M, Y_mc nslices x ncoil x m
+ * complex doubles, each slice with its own maps; the same workers, pipelining and shared-device rules, each launch one qmri_pnp_admm_mc_dev call
+ * (LSQR solver only).  X_out / qmap_out / pd_out as qmri_recon_batch. */
+int qmri_recon_batch_mc(int ndev, const int* devs, int nslices, const qmri_problem* prob, int ncoil, const void* maps, const void* Y_mc,
+                        void* X_out, float* qmap_out, float* pd_out, char* errbuf, size_t errbuf_len);
 
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------------ */
 typedef struct {

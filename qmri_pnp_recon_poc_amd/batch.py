@@ -26,11 +26,26 @@ def shard_slices(nslices: int, world: int, rank: int) -> list:
 
 def recon_batch(devices, Y, N, M, V, frame_ptr, kidx, weights, in_nc=10, out_nc=10, nc=(64, 128, 256, 512), nb=4,
                 dictionary=None, gamma=0.05, iters=100, cg_tol=1e-4, cg_maxit=100, solver="lsqr", multi_level=False,
-                noise_std=0.01, slices_per_launch=1):
-    """Reconstruct Y[nslices, m] on the given devices; returns dict(X [nslices,N,M,s], qmap, pd)."""
+                noise_std=0.01, slices_per_launch=1, coil_maps=None):
+    """Reconstruct Y[nslices, m] on the given devices; returns dict(X [nslices,N,M,s], qmap, pd).
+
+    coil_maps [nslices, N, M, ncoil] (multi-coil extension, no reference counterpart): Y is then [nslices, m, ncoil], every slice is reconstructed
+    with its own maps through qmri_recon_batch_mc (LSQR solver only).  Without coil_maps nothing changes."""
     L = _lib.lib()
+    ncoil, Mb = 0, None
+    if coil_maps is not None:
+        from .engine import _cbuf
+        cm, Yc = np.asarray(coil_maps), np.asarray(Y)
+        if cm.ndim != 4 or cm.shape[1:3] != (N, M) or Yc.ndim != 3 or Yc.shape[0] != cm.shape[0] or Yc.shape[2] != cm.shape[3]:
+            raise ValueError("coil_maps must be [nslices, N, M, ncoil] and Y [nslices, m, ncoil]")
+        if solver != "lsqr":
+            raise ValueError("the multi-coil reconstruction uses the LSQR solver")
+        ncoil = int(cm.shape[3])
+        Mb = np.ascontiguousarray(np.concatenate([_cbuf(cm[b]) for b in range(cm.shape[0])]))
+        Y = np.stack([_cbuf(Yc[b]) for b in range(Yc.shape[0])])
     Y = np.ascontiguousarray(Y, dtype=np.complex128)
     nsl, m = Y.shape
+    m //= max(ncoil, 1)
     from .engine import real_dictionary_array
     V = real_dictionary_array(V, "V", np.float64)
     T, s = V.shape
@@ -67,9 +82,12 @@ def recon_batch(devices, Y, N, M, V, frame_ptr, kidx, weights, in_nc=10, out_nc=
     pd = np.empty((nsl, N * M), np.complex64) if dictionary is not None else None
     devs = (C.c_int * len(devices))(*[int(v) for v in devices])
     err = C.create_string_buffer(1024)
-    st = L.qmri_recon_batch(len(devices), devs, nsl, C.byref(pb), Y.ctypes.data_as(C.c_void_p), X.ctypes.data_as(C.c_void_p),
-                            qmap.ctypes.data_as(f) if qmap is not None else None,
-                            pd.ctypes.data_as(f) if pd is not None else None, err, len(err))
+    outs = (X.ctypes.data_as(C.c_void_p), qmap.ctypes.data_as(f) if qmap is not None else None, pd.ctypes.data_as(f) if pd is not None else None,
+            err, len(err))
+    if ncoil:
+        st = L.qmri_recon_batch_mc(len(devices), devs, nsl, C.byref(pb), ncoil, Mb.ctypes.data_as(C.c_void_p), Y.ctypes.data_as(C.c_void_p), *outs)
+    else:
+        st = L.qmri_recon_batch(len(devices), devs, nsl, C.byref(pb), Y.ctypes.data_as(C.c_void_p), *outs)
     if st != 0:
         from .engine import QmriError
         raise QmriError(st, err.value.decode())

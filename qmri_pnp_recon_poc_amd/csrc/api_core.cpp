@@ -141,6 +141,7 @@ void qmri_free_operator(qmri_ctx* ctx) {
     if (o.h_state) (void)hipHostFree(o.h_state);
     if (o.h_ring) (void)hipHostFree(o.h_ring);
     free_dev(ctx->d_ks_gran); ctx->d_ks_gran = nullptr; ctx->ks_persist_cap = -1;    // (sized for this operator's work units)
+    mc_free_work(o.mc);
     o = OpHost();
 }
 

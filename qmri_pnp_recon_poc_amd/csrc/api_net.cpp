@@ -893,14 +893,126 @@ static int pnp_admm_dev_impl(qmri_ctx* ctx, int nslices, const void* d_y, const 
 
 // ---------------------------------------------------------------------------------------------------
 // Multi-coil extension (no reference counterpart: README.md:63 -- parity unpinned; mc_kernels.hip): the x-update and the PnP-ADMM loop of
-// PnP_ADMM.m:76-146 with A replaced by the SENSE operator of qmri_set_coils.  One slice; host arrays in, host arrays out.
+// PnP_ADMM.m:76-146 with A replaced by the SENSE operator.  B slices, each with its own maps ([B][ncoil][N*M]), y ([B][ncoil][m]) and x ([B][n]);
+// the single-slice entry points are B = 1 calls on the maps of qmri_set_coils.  The batched calls neither read nor change those maps.
 // ---------------------------------------------------------------------------------------------------
-int qmri_lsqr_mc_dev(qmri_ctx* ctx, const double2* d_y, const double2* d_z, double r, double tol, int maxit, double2* d_x, int32_t* iters_out, int32_t* flag_out);
+static int mc_require(qmri_ctx* ctx, int nslices, int ncoil, const void* maps, const void* y) {
+    const OpHost& o = ctx->op;
+    if (!o.ready) { qmri_set_error(ctx, "operator not set: call qmri_set_operator first"); return QMRI_ERR_STATE; }
+    QMRI_CHECK_ARG(ctx, nslices >= 1 && ncoil >= 1 && ncoil <= 1024, "nslices >= 1 and 1 <= ncoil <= 1024");
+    QMRI_CHECK_ARG(ctx, maps && y, "maps / y_mc must not be NULL");
+    return QMRI_OK;
+}
+static int mc_admm_check(qmri_ctx* ctx, const qmri_admm_params* prm) {
+    const OpHost& o = ctx->op;
+    const NetPlan& net = ctx->net;
+    if (!net.ready) { qmri_set_error(ctx, "denoiser not set: call qmri_set_denoiser first"); return QMRI_ERR_STATE; }
+    QMRI_CHECK_ARG(ctx, prm, "params must not be NULL");
+    QMRI_CHECK_ARG(ctx, prm->iters >= 0 && prm->gamma > 0 && prm->cg_maxit >= 0 && prm->solver == QMRI_SOLVER_LSQR, "iters >= 0, gamma > 0, cg_maxit >= 0, LSQR solver required");
+    const int multi = prm->denoiser_type == QMRI_DENOISER_MULTI_LEVEL;
+    if (net.H != o.N || net.W != o.M || net.desc.in_nc != o.s + (multi ? 1 : 0) || net.desc.out_nc != o.s) {
+        qmri_set_error(ctx, "denoiser (%d x %d, %d -> %d channels) does not fit the operator (%d x %d x %d)", net.H, net.W, net.desc.in_nc, net.desc.out_nc, o.N, o.M, o.s);
+        return QMRI_ERR_INVALID_ARG;
+    }
+    return QMRI_OK;
+}
 
-struct McStage {                                   // device copies of one multi-coil problem
-    double2 *y = nullptr, *z = nullptr, *x = nullptr;
-    ~McStage() { if (y) (void)hipFree(y); if (z) (void)hipFree(z); if (x) (void)hipFree(x); }
-};
+// PnP_ADMM.m:76-146 for B <= max_batch slices, all on the device (d_x0 NULL: x = A_mc' y as :84; returns x as :148).  When the network's range guard
+// trips, the loop starts again from the inputs (d_x_out must not alias d_x0) with no second allocation.
+static int mc_admm_group(qmri_ctx* ctx, int B, int ncoil, const double2* d_maps, const double2* d_y, const qmri_admm_params* prm, const double2* d_x0,
+                         double2* d_x, int32_t* li_out, int li_stride) {
+    OpHost& o = ctx->op;
+    NetPlan& net = ctx->net;
+    const int multi = prm->denoiser_type == QMRI_DENOISER_MULTI_LEVEL;
+    const size_t plane = (size_t)o.N * o.M, n = plane * o.s;
+    std::vector<int32_t> li((size_t)B);
+    for (int attempt = 0;; ++attempt) {
+        if (d_x0) QMRI_HIP(ctx, hipMemcpyAsync(d_x, d_x0, (size_t)B * n * sizeof(double2), hipMemcpyDeviceToDevice, ctx->stream));
+        else QMRI_TRY(mc_adjoint_batch_dev(ctx, B, ncoil, d_maps, d_y, d_x));
+        QMRI_HIP(ctx, hipMemcpyAsync(o.d_vv, d_x, (size_t)B * n * sizeof(double2), hipMemcpyDeviceToDevice, ctx->stream));       // v = x
+        QMRI_HIP(ctx, hipMemsetAsync(o.d_u, 0, (size_t)B * n * sizeof(double2), ctx->stream));                                  // uold = 0
+        QMRI_TRY(dc_launch_prepare_z(ctx, qmri_opdev(ctx), o.ls, B, o.d_vv, o.d_u, o.d_z));                                      // z = v - uold
+        bool again = false;
+        for (int it = 0; it < prm->iters; ++it) {
+            QMRI_TRY(qmri_lsqr_mc_batch_dev(ctx, B, ncoil, d_maps, d_y, o.d_z, prm->gamma, prm->cg_tol, prm->cg_maxit, d_x, li.data(), nullptr));   // :102
+            if (li_out) for (int b = 0; b < B; ++b) li_out[(size_t)b * li_stride + it] = li[b];
+            QMRI_TRY(ew_launch_minmax_normalise(ctx, B, n, (int)plane, o.N, o.s, multi, prm->noise_std, d_x, o.d_u, o.d_mm, o.d_norm, o.ls.nblk_z, net.in32, false));
+            QMRI_TRY(net_forward(ctx, B));
+            QMRI_TRY(ew_launch_unnormalise_dual(ctx, B, n, (int)plane, o.N, net.out32, net.in32, net.desc.residual_noise, o.d_norm, d_x, o.d_u, nullptr, o.d_z,
+                                                o.ls.pz, o.ls.nblk_z));
+            QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            QMRI_TRY(net_range_tripped(ctx, again));              // (f16 range / hand-off guards: the network is re-packed or the form switched; start again)
+            if (again) break;
+        }
+        if (!again) break;
+        ctx->admm_repeats += 1;
+        if (attempt >= 2) { qmri_set_error(ctx, "the denoiser's range guard tripped three times in a row in the multi-coil PnP-ADMM loop"); return QMRI_ERR_HIP; }
+    }
+    o.xhat_valid = false;
+    return QMRI_OK;
+}
+
+extern "C" int qmri_xupdate_mc_batch(qmri_ctx* ctx, int nslices, int ncoil, const void* maps, const void* y_mc, const void* z, double r, double tol, int maxit,
+                                     const void* x0, void* x_out, int32_t* iters_out, int32_t* flags_out) {
+    if (!ctx) return QMRI_ERR_INVALID_ARG;
+    QMRI_HIP(ctx, hipSetDevice(ctx->device));
+    QMRI_TRY(mc_require(ctx, nslices, ncoil, maps, y_mc));
+    QMRI_CHECK_ARG(ctx, z && x_out && r > 0 && maxit >= 0, "z / x_out must not be NULL, r > 0, maxit >= 0");
+    OpHost& o = ctx->op;
+    const size_t plane = (size_t)o.N * o.M, n = plane * o.s, img = (size_t)nslices * ncoil;
+    QMRI_TRY(mc_ensure_staging(ctx, nslices, ncoil));
+    McWork& w = o.mc;
+    QMRI_HIP(ctx, hipMemcpyAsync(w.sm, maps, img * plane * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
+    QMRI_HIP(ctx, hipMemcpyAsync(w.sy, y_mc, img * o.m * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
+    QMRI_HIP(ctx, hipMemcpyAsync(w.sz, z, nslices * n * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
+    if (x0) QMRI_HIP(ctx, hipMemcpyAsync(w.sx, x0, nslices * n * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
+    else QMRI_HIP(ctx, hipMemsetAsync(w.sx, 0, nslices * n * sizeof(double2), ctx->stream));
+    QMRI_TRY(qmri_lsqr_mc_batch_dev(ctx, nslices, ncoil, w.sm, w.sy, w.sz, r, tol, maxit, w.sx, iters_out, flags_out));
+    QMRI_HIP(ctx, hipMemcpyAsync(x_out, w.sx, nslices * n * sizeof(double2), hipMemcpyDeviceToHost, ctx->stream));
+    QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return QMRI_OK;
+}
+
+extern "C" int qmri_pnp_admm_mc_dev(qmri_ctx* ctx, int nslices, int ncoil, const void* d_maps, const void* d_y, const qmri_admm_params* prm,
+                                    const void* d_x0, void* d_x_out, int32_t* lsqr_iters_out) {
+    if (!ctx) return QMRI_ERR_INVALID_ARG;
+    QMRI_HIP(ctx, hipSetDevice(ctx->device));
+    QMRI_TRY(mc_require(ctx, nslices, ncoil, d_maps, d_y));
+    QMRI_TRY(mc_admm_check(ctx, prm));
+    QMRI_CHECK_ARG(ctx, d_x_out && d_x_out != d_x0, "x_out must not be NULL and must not alias x0");
+    QMRI_CHECK_ARG(ctx, nslices <= ctx->op.maxB && nslices <= ctx->net.maxB, "nslices exceeds max_batch of the operator or the denoiser");
+    QMRI_TRY(mc_admm_group(ctx, nslices, ncoil, (const double2*)d_maps, (const double2*)d_y, prm, (const double2*)d_x0, (double2*)d_x_out,
+                           lsqr_iters_out, prm->iters));
+    QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return QMRI_OK;
+}
+
+extern "C" int qmri_pnp_admm_mc_batch(qmri_ctx* ctx, int nslices, int slices_per_launch, int ncoil, const void* maps, const void* y_mc,
+                                      const qmri_admm_params* prm, const void* x0, void* x_out, int32_t* lsqr_iters_out) {
+    if (!ctx) return QMRI_ERR_INVALID_ARG;
+    QMRI_HIP(ctx, hipSetDevice(ctx->device));
+    QMRI_TRY(mc_require(ctx, nslices, ncoil, maps, y_mc));
+    QMRI_TRY(mc_admm_check(ctx, prm));
+    QMRI_CHECK_ARG(ctx, x_out && slices_per_launch >= 1, "x_out must not be NULL, slices_per_launch >= 1");
+    OpHost& o = ctx->op;
+    const int spl = std::min(slices_per_launch, nslices);
+    QMRI_CHECK_ARG(ctx, spl <= o.maxB && spl <= ctx->net.maxB, "slices_per_launch exceeds max_batch of the operator or the denoiser");
+    const size_t plane = (size_t)o.N * o.M, n = plane * o.s;
+    QMRI_TRY(mc_ensure_staging(ctx, spl, ncoil));
+    McWork& w = o.mc;
+    for (int b0 = 0; b0 < nslices; b0 += spl) {
+        const int B = std::min(spl, nslices - b0);
+        const size_t img0 = (size_t)b0 * ncoil, img = (size_t)B * ncoil;
+        QMRI_HIP(ctx, hipMemcpyAsync(w.sm, (const double2*)maps + img0 * plane, img * plane * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
+        QMRI_HIP(ctx, hipMemcpyAsync(w.sy, (const double2*)y_mc + img0 * o.m, img * o.m * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
+        if (x0) QMRI_HIP(ctx, hipMemcpyAsync(w.sz, (const double2*)x0 + (size_t)b0 * n, B * n * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
+        QMRI_TRY(mc_admm_group(ctx, B, ncoil, w.sm, w.sy, prm, x0 ? w.sz : nullptr, w.sx,
+                               lsqr_iters_out ? lsqr_iters_out + (size_t)b0 * prm->iters : nullptr, prm->iters));
+        QMRI_HIP(ctx, hipMemcpyAsync((double2*)x_out + (size_t)b0 * n, w.sx, B * n * sizeof(double2), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return QMRI_OK;
+}
 
 extern "C" int qmri_xupdate_mc(qmri_ctx* ctx, const void* y_mc, const void* z, double r, double tol, int maxit, const void* x0, void* x_out,
                                int32_t* iters_out, int32_t* flag_out) {
@@ -911,16 +1023,14 @@ extern "C" int qmri_xupdate_mc(qmri_ctx* ctx, const void* y_mc, const void* z, d
     if (!o.ncoil) { qmri_set_error(ctx, "no coil maps set: call qmri_set_coils first"); return QMRI_ERR_STATE; }
     QMRI_CHECK_ARG(ctx, y_mc && z && x_out && r > 0 && maxit >= 0, "y / z / x_out must not be NULL, r > 0, maxit >= 0");
     const size_t n = (size_t)o.N * o.M * o.s, mtot = (size_t)o.ncoil * o.m;
-    McStage st;
-    QMRI_HIP(ctx, hipMalloc((void**)&st.y, mtot * sizeof(double2)));
-    QMRI_HIP(ctx, hipMalloc((void**)&st.z, n * sizeof(double2)));
-    QMRI_HIP(ctx, hipMalloc((void**)&st.x, n * sizeof(double2)));
-    QMRI_HIP(ctx, hipMemcpyAsync(st.y, y_mc, mtot * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
-    QMRI_HIP(ctx, hipMemcpyAsync(st.z, z, n * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
-    if (x0) QMRI_HIP(ctx, hipMemcpyAsync(st.x, x0, n * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
-    else QMRI_HIP(ctx, hipMemsetAsync(st.x, 0, n * sizeof(double2), ctx->stream));
-    QMRI_TRY(qmri_lsqr_mc_dev(ctx, st.y, st.z, r, tol, maxit, st.x, iters_out, flag_out));
-    QMRI_HIP(ctx, hipMemcpyAsync(x_out, st.x, n * sizeof(double2), hipMemcpyDeviceToHost, ctx->stream));
+    QMRI_TRY(mc_ensure_staging(ctx, 1, o.ncoil));
+    McWork& w = o.mc;
+    QMRI_HIP(ctx, hipMemcpyAsync(w.sy, y_mc, mtot * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
+    QMRI_HIP(ctx, hipMemcpyAsync(w.sz, z, n * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
+    if (x0) QMRI_HIP(ctx, hipMemcpyAsync(w.sx, x0, n * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
+    else QMRI_HIP(ctx, hipMemsetAsync(w.sx, 0, n * sizeof(double2), ctx->stream));
+    QMRI_TRY(qmri_lsqr_mc_batch_dev(ctx, 1, o.ncoil, o.d_coils, w.sy, w.sz, r, tol, maxit, w.sx, iters_out, flag_out));
+    QMRI_HIP(ctx, hipMemcpyAsync(x_out, w.sx, n * sizeof(double2), hipMemcpyDeviceToHost, ctx->stream));
     QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return QMRI_OK;
 }
@@ -929,53 +1039,18 @@ extern "C" int qmri_pnp_admm_mc(qmri_ctx* ctx, const void* y_mc, const qmri_admm
     if (!ctx) return QMRI_ERR_INVALID_ARG;
     QMRI_HIP(ctx, hipSetDevice(ctx->device));
     OpHost& o = ctx->op;
-    NetPlan& net = ctx->net;
     if (!o.ready) { qmri_set_error(ctx, "operator not set: call qmri_set_operator first"); return QMRI_ERR_STATE; }
     if (!o.ncoil) { qmri_set_error(ctx, "no coil maps set: call qmri_set_coils first"); return QMRI_ERR_STATE; }
-    if (!net.ready) { qmri_set_error(ctx, "denoiser not set: call qmri_set_denoiser first"); return QMRI_ERR_STATE; }
-    QMRI_CHECK_ARG(ctx, y_mc && prm && x_out, "y / params / x_out must not be NULL");
-    QMRI_CHECK_ARG(ctx, prm->iters >= 0 && prm->gamma > 0 && prm->cg_maxit >= 0 && prm->solver == QMRI_SOLVER_LSQR, "iters >= 0, gamma > 0, cg_maxit >= 0, LSQR solver required");
-    const int multi = prm->denoiser_type == QMRI_DENOISER_MULTI_LEVEL;
-    if (net.H != o.N || net.W != o.M || net.desc.in_nc != o.s + (multi ? 1 : 0) || net.desc.out_nc != o.s) {
-        qmri_set_error(ctx, "denoiser (%d x %d, %d -> %d channels) does not fit the operator (%d x %d x %d)", net.H, net.W, net.desc.in_nc, net.desc.out_nc, o.N, o.M, o.s);
-        return QMRI_ERR_INVALID_ARG;
-    }
-    const size_t plane = (size_t)o.N * o.M, n = plane * o.s, mtot = (size_t)o.ncoil * o.m;
-    McStage st;
-    QMRI_HIP(ctx, hipMalloc((void**)&st.y, mtot * sizeof(double2)));
-    QMRI_HIP(ctx, hipMalloc((void**)&st.x, n * sizeof(double2)));
-    QMRI_HIP(ctx, hipMemcpyAsync(st.y, y_mc, mtot * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
-    double2* scr = nullptr;                                        // [max_batch][n] coil images of the initial adjoint
-    QMRI_HIP(ctx, hipMalloc((void**)&scr, (size_t)o.maxB * n * sizeof(double2)));
-    struct Scr { double2* p; ~Scr() { if (p) (void)hipFree(p); } } scr_guard{scr};
-    if (x0) QMRI_HIP(ctx, hipMemcpyAsync(st.x, x0, n * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
-    else {                                                         // x = F.adjoint(Y)  (PnP_ADMM.m:84)
-        for (int j0 = 0; j0 < o.ncoil; j0 += o.maxB) {
-            const int cnt = std::min(o.maxB, o.ncoil - j0);
-            QMRI_TRY(dc_launch_adj(ctx, qmri_opdev(ctx), cnt, st.y + (size_t)j0 * o.m, o.d_tmp, scr));
-            QMRI_TRY(ew_launch_coil_sum(ctx, n, plane, cnt, scr, o.d_coils + (size_t)j0 * plane, st.x, j0 > 0));
-        }
-    }
-    QMRI_HIP(ctx, hipMemcpyAsync(o.d_vv, st.x, n * sizeof(double2), hipMemcpyDeviceToDevice, ctx->stream));          // v = x
-    QMRI_HIP(ctx, hipMemsetAsync(o.d_u, 0, n * sizeof(double2), ctx->stream));                                          // uold = 0
-    QMRI_TRY(dc_launch_prepare_z(ctx, qmri_opdev(ctx), o.ls, 1, o.d_vv, o.d_u, o.d_z));                                 // z = v - uold
-    bool again = false;
-    for (int it = 0; it < prm->iters; ++it) {
-        int32_t li = 0;
-        QMRI_TRY(qmri_lsqr_mc_dev(ctx, st.y, o.d_z, prm->gamma, prm->cg_tol, prm->cg_maxit, st.x, &li, nullptr));      // PnP_ADMM.m:102
-        if (lsqr_iters_out) lsqr_iters_out[it] = li;
-        QMRI_TRY(ew_launch_minmax_normalise(ctx, 1, n, (int)plane, o.N, o.s, multi, prm->noise_std, st.x, o.d_u, o.d_mm, o.d_norm, o.ls.nblk_z, net.in32, false));
-        QMRI_TRY(net_forward(ctx, 1));
-        QMRI_TRY(ew_launch_unnormalise_dual(ctx, 1, n, (int)plane, o.N, net.out32, net.in32, net.desc.residual_noise, o.d_norm, st.x, o.d_u, nullptr, o.d_z,
-                                            o.ls.pz, o.ls.nblk_z));
-        QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        QMRI_TRY(net_range_tripped(ctx, again));                   // (f16 range / hand-off guards: the network is re-packed or the form switched; repeat from the start)
-        if (again) break;
-    }
-    if (again) { ctx->admm_repeats += 1; return qmri_pnp_admm_mc(ctx, y_mc, prm, x0, x_out, lsqr_iters_out); }
-    QMRI_HIP(ctx, hipMemcpyAsync(x_out, st.x, n * sizeof(double2), hipMemcpyDeviceToHost, ctx->stream));                // returns x, not v
+    QMRI_TRY(mc_admm_check(ctx, prm));
+    QMRI_CHECK_ARG(ctx, y_mc && x_out, "y / params / x_out must not be NULL");
+    const size_t n = (size_t)o.N * o.M * o.s, mtot = (size_t)o.ncoil * o.m;
+    QMRI_TRY(mc_ensure_staging(ctx, 1, o.ncoil));
+    McWork& w = o.mc;
+    QMRI_HIP(ctx, hipMemcpyAsync(w.sy, y_mc, mtot * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
+    if (x0) QMRI_HIP(ctx, hipMemcpyAsync(w.sz, x0, n * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
+    QMRI_TRY(mc_admm_group(ctx, 1, o.ncoil, o.d_coils, w.sy, prm, x0 ? w.sz : nullptr, w.sx, lsqr_iters_out, prm->iters));
+    QMRI_HIP(ctx, hipMemcpyAsync(x_out, w.sx, n * sizeof(double2), hipMemcpyDeviceToHost, ctx->stream));      // returns x, not v
     QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    o.xhat_valid = false;
     return QMRI_OK;
 }
 
@@ -1214,19 +1289,23 @@ extern "C" int qmri_dict_match(qmri_ctx* ctx, const void* X, int Npix, float* qm
 // iteration (one workgroup per CU, every unit resident at once) and the resident-tile convolution launch -- would then be partially resident
 // side by side, both would wait to their time-outs and the reconstruction would be repeated: such a worker starts on the two-launch iteration
 // and one launch per layer (same bits, tested).
+// ncoil > 0 (multi-coil extension, qmri_recon_batch_mc): Y holds ncoil x m samples per slice and `cmaps` ncoil x N*M maps per slice; each launch is
+// one qmri_pnp_admm_mc_dev call.  ncoil = 0 is the single-coil path, unchanged.
 static int recon_worker(int device, bool shared_device, int widx, int nworkers, int nslices, const qmri_problem* pb, const char* Y, char* X_out,
-                        float* qmap_out, float* pd_out, std::string* err) {
+                        float* qmap_out, float* pd_out, std::string* err, int ncoil = 0, const char* cmaps = nullptr) {
     qmri_ctx* ctx = nullptr;
     int st = qmri_create(device, &ctx);
     if (st != QMRI_OK) { *err = qmri_last_error(nullptr); return st; }
     const int spl = std::max(1, pb->slices_per_launch);
     const size_t n = (size_t)pb->N * pb->M * pb->s, npix = (size_t)pb->N * pb->M;
-    const int m = pb->frame_ptr[pb->T];
+    const int m = pb->frame_ptr[pb->T] * std::max(ncoil, 1);       // samples per slice (all coils)
     const int Q = std::max(pb->Q, 1);
     const bool maps = pb->K > 0 && (qmap_out || pd_out);
     const size_t by = (size_t)spl * m * sizeof(double2), bx = (size_t)spl * n * sizeof(double2);
     const size_t bq = (size_t)spl * npix * Q * sizeof(float), bp = (size_t)spl * npix * 2 * sizeof(float);
-    struct Set { double2 *dY = nullptr, *dX = nullptr; float *dq = nullptr, *dp = nullptr; char *hY = nullptr, *hX = nullptr; float *hq = nullptr, *hp = nullptr;
+    const size_t bm = (size_t)spl * ncoil * npix * sizeof(double2);
+    struct Set { double2 *dY = nullptr, *dX = nullptr, *dM = nullptr; float *dq = nullptr, *dp = nullptr; char *hY = nullptr, *hX = nullptr, *hM = nullptr;
+                 float *hq = nullptr, *hp = nullptr;
                  hipEvent_t matched = nullptr, copied = nullptr; int s0 = -1, cnt = 0; } set[2];
     hipStream_t cs = nullptr;
     auto bail = [&](int code) { *err = qmri_last_error(ctx); return code; };
@@ -1254,6 +1333,7 @@ static int recon_worker(int device, bool shared_device, int widx, int nworkers, 
             ok = hipMalloc((void**)&S.dY, by) == hipSuccess && hipMalloc((void**)&S.dX, bx) == hipSuccess && hipHostMalloc((void**)&S.hY, by, hipHostMallocDefault) == hipSuccess &&
                  hipHostMalloc((void**)&S.hX, bx, hipHostMallocDefault) == hipSuccess && hipEventCreateWithFlags(&S.matched, hipEventDisableTiming) == hipSuccess &&
                  hipEventCreateWithFlags(&S.copied, hipEventDisableTiming) == hipSuccess;
+            if (ok && ncoil) ok = hipMalloc((void**)&S.dM, bm) == hipSuccess && hipHostMalloc((void**)&S.hM, bm, hipHostMallocDefault) == hipSuccess;
             if (ok && maps) ok = hipMalloc((void**)&S.dq, bq) == hipSuccess && hipMalloc((void**)&S.dp, bp) == hipSuccess &&
                                  hipHostMalloc((void**)&S.hq, bq, hipHostMallocDefault) == hipSuccess && hipHostMalloc((void**)&S.hp, bp, hipHostMallocDefault) == hipSuccess;
         }
@@ -1267,7 +1347,12 @@ static int recon_worker(int device, bool shared_device, int widx, int nworkers, 
             const int s0 = l * spl, cnt = std::min(spl, nslices - s0);
             std::memcpy(S.hY, Y + (size_t)s0 * m * sizeof(double2), (size_t)cnt * m * sizeof(double2));
             if (hipMemcpyAsync(S.dY, S.hY, (size_t)cnt * m * sizeof(double2), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) { hipfail("H2D copy"); break; }
-            if ((st = qmri_pnp_admm_dev(ctx, cnt, S.dY, &pb->admm, nullptr, nullptr, S.dX, nullptr, nullptr)) != QMRI_OK) { bail(st); break; }
+            if (ncoil) {
+                const size_t mb = (size_t)ncoil * npix * sizeof(double2);
+                std::memcpy(S.hM, cmaps + (size_t)s0 * mb, (size_t)cnt * mb);
+                if (hipMemcpyAsync(S.dM, S.hM, (size_t)cnt * mb, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) { hipfail("H2D copy"); break; }
+                if ((st = qmri_pnp_admm_mc_dev(ctx, cnt, ncoil, S.dM, S.dY, &pb->admm, nullptr, S.dX, nullptr)) != QMRI_OK) { bail(st); break; }
+            } else if ((st = qmri_pnp_admm_dev(ctx, cnt, S.dY, &pb->admm, nullptr, nullptr, S.dX, nullptr, nullptr)) != QMRI_OK) { bail(st); break; }
             if (maps) {
                 for (int i = 0; i < cnt && st == QMRI_OK; ++i)
                     if ((st = qmri_dict_match_dev(ctx, S.dX + (size_t)i * n, (int)npix, qmap_out ? S.dq + (size_t)i * npix * Q : nullptr,
@@ -1286,9 +1371,9 @@ static int recon_worker(int device, bool shared_device, int widx, int nworkers, 
     } while (0);
     (void)hipDeviceSynchronize();
     for (Set& S : set) {
-        void* dptr[] = { S.dY, S.dX, S.dq, S.dp };
+        void* dptr[] = { S.dY, S.dX, S.dM, S.dq, S.dp };
         for (void* p : dptr) if (p) (void)hipFree(p);
-        void* hptr[] = { S.hY, S.hX, S.hq, S.hp };
+        void* hptr[] = { S.hY, S.hX, S.hM, S.hq, S.hp };
         for (void* p : hptr) if (p) (void)hipHostFree(p);
         if (S.matched) (void)hipEventDestroy(S.matched);
         if (S.copied) (void)hipEventDestroy(S.copied);
@@ -1298,12 +1383,12 @@ static int recon_worker(int device, bool shared_device, int widx, int nworkers, 
     return st;
 }
 
-extern "C" int qmri_recon_batch(int ndev, const int* devs, int nslices, const qmri_problem* prob, const void* Y, void* X_out,
-                                float* qmap_out, float* pd_out, char* errbuf, size_t errbuf_len) {
+static int recon_batch_impl(const char* name, int ndev, const int* devs, int nslices, const qmri_problem* prob, int ncoil, const void* maps, const void* Y,
+                            void* X_out, float* qmap_out, float* pd_out, char* errbuf, size_t errbuf_len) {
     auto report = [&](const std::string& s) { if (errbuf && errbuf_len) { snprintf(errbuf, errbuf_len, "%s", s.c_str()); } };
     if (ndev <= 0 || !devs || nslices <= 0 || !prob || !Y || !X_out || !prob->V || !prob->frame_ptr || !prob->kidx || !prob->net ||
-        !prob->weights) {
-        report("qmri_recon_batch: invalid arguments");
+        !prob->weights || (ncoil && (ncoil < 0 || ncoil > 1024 || !maps))) {
+        report(std::string(name) + ": invalid arguments");
         return QMRI_ERR_INVALID_ARG;
     }
     std::vector<std::thread> th;
@@ -1313,13 +1398,28 @@ extern "C" int qmri_recon_batch(int ndev, const int* devs, int nslices, const qm
         bool shared = false;
         for (int v = 0; v < ndev; ++v) shared = shared || (v != w && devs[v] == devs[w]);
         th.emplace_back([&, w, shared]() {
-            status[w] = recon_worker(devs[w], shared, w, ndev, nslices, prob, (const char*)Y, (char*)X_out, qmap_out, pd_out, &errs[w]);
+            status[w] = recon_worker(devs[w], shared, w, ndev, nslices, prob, (const char*)Y, (char*)X_out, qmap_out, pd_out, &errs[w], ncoil,
+                                     (const char*)maps);
         });
     }
     for (auto& t : th) t.join();
     for (int w = 0; w < ndev; ++w)
         if (status[w] != QMRI_OK) { report("device " + std::to_string(devs[w]) + ": " + errs[w]); return status[w]; }
     return QMRI_OK;
+}
+
+extern "C" int qmri_recon_batch(int ndev, const int* devs, int nslices, const qmri_problem* prob, const void* Y, void* X_out,
+                                float* qmap_out, float* pd_out, char* errbuf, size_t errbuf_len) {
+    return recon_batch_impl("qmri_recon_batch", ndev, devs, nslices, prob, 0, nullptr, Y, X_out, qmap_out, pd_out, errbuf, errbuf_len);
+}
+
+extern "C" int qmri_recon_batch_mc(int ndev, const int* devs, int nslices, const qmri_problem* prob, int ncoil, const void* maps, const void* Y_mc,
+                                   void* X_out, float* qmap_out, float* pd_out, char* errbuf, size_t errbuf_len) {
+    if (ncoil < 1) {
+        if (errbuf && errbuf_len) snprintf(errbuf, errbuf_len, "qmri_recon_batch_mc: invalid arguments (ncoil >= 1)");
+        return QMRI_ERR_INVALID_ARG;
+    }
+    return recon_batch_impl("qmri_recon_batch_mc", ndev, devs, nslices, prob, ncoil, maps, Y_mc, X_out, qmap_out, pd_out, errbuf, errbuf_len);
 }
 
 // diagnostic: copy the per-workgroup stamps of the most recent conv launch (see conv_kernels.hip) to the host

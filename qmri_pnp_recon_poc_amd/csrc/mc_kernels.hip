@@ -5,220 +5,438 @@
 //     x = lsqr(@afun, [y; sqrt(r) z], cg_tol, cg_iter, [], [], x0),   afun: B = [A; sqrt(r) I]  (PnP_ADMM.m:153-171)
 // with A replaced by the SENSE operator of api_core.cpp (qmri_forward_mc / qmri_adjoint_mc):  A_mc x = [A (C_j . x)]_j,  A_mc' y = sum_j conj(C_j) . A' y_j.
 // Coil maps act in image space, so A_mc'A_mc is no longer block-diagonal in k-space and the k-space iteration of kslsqr_kernels.hip does not apply:
-// this is the image-domain LSQR (the recurrences, stop rules and their order exactly as oracle/orc_lsqr.c restates MATLAB's lsqr), two batched
-// transforms per coil chunk and iteration, the scalars on the host (three small device -> host copies per iteration: an extension, not a tuned path).
-// Sums are 256 block partials added on the host in block order: run-to-run reproducible.
+// this is the image-domain LSQR, the recurrences, stop rules and their order exactly as oracle/orc_lsqr.c restates MATLAB's lsqr.
+//
+// B slices per call, each with its own maps ([B][ncoil][N*M]).  The "coil images" of all slices (g = b * ncoil + j) go through the batched transforms
+// of dc_kernels.hip max_batch at a time; a chunk may span slices.  Every LSQR scalar lives on the device, in one LsqrState per slice (sc[0] only):
+//     sc[0].c, s, phibar, normr, norma, thet, rho, phi, alpha, beta   the recurrences
+//     sc[0].factor = normar,  sc[0].ua = 1 / alpha,  sc[0].ub = 1 / beta,  pad = stagnation counter,  iter / done / flag as the k-space solver's
+// u and v are kept UNSCALED: the 1 / beta and 1 / alpha of lsqr's normalisations are multiplied in by the next kernel that reads them.  The small
+// k_mcl_scalar launches (one wave per slice) do the recurrences and the stop tests and mirror iter / done / flag to pinned host memory; the host
+// enqueues a predicted number of iterations, waits on ONE event and reads the flags (qmri_lsqr_mc_batch_dev).  A slice that has stopped is frozen: every
+// kernel tests its slice's done flag (uniform per workgroup) and leaves x, u, v, d alone.
+//
+// Reductions: every norm is summed from fixed per-vector partials -- PS workgroups per slice vector, PC per coil image, whatever B or the chunking --
+// added in one fixed order by k_mcl_scalar.  No floating-point atomics.  So a slice's x-update is bit-identical alone or at any position in any batch,
+// with any max_batch.  (The conjugate coil sum accumulates coil j after coil j - 1 in fp64 whichever chunk holds them: the same bits too.)
 #include <cfloat>
 #include <cmath>
 #include <vector>
 #include "qmri_internal.h"
 
 namespace {
-constexpr int MT = 256, MB = 256;     // threads per block, blocks per reduction
+constexpr int NT = 256;          // threads per workgroup of the streaming kernels
+constexpr int PS = 256;          // partial sums per slice vector (n complex)
+constexpr int PC = 64;           // partial sums per coil image (m complex)
+enum { MCL_INIT = 0, MCL_ITER = 1 };
+enum { SC_BETA0 = 0, SC_BETA = 1, SC_STOP = 2, SC_ALPHA = 3 };
 
-__device__ __forceinline__ double mc_block_sum(double v, double* sh) {
+// partial-sum slots of one solve (McWork::part): [img][PC] |u_j|^2, [img][PC] |y_j|^2, then [B][PS] each of |u2|^2, |z|^2, |d|^2, |x|^2, |v|^2
+struct McParts {
+    double *pu, *py, *pb, *pz, *pd, *px, *pv;
+};
+McParts mc_parts(double* base, int B, int ncoil) {
+    McParts p;
+    const size_t img = (size_t)B * ncoil * PC, sl = (size_t)B * PS;
+    p.pu = base; p.py = p.pu + img; p.pb = p.py + img; p.pz = p.pb + sl; p.pd = p.pz + sl; p.px = p.pd + sl; p.pv = p.px + sl;
+    return p;
+}
+
+__device__ __forceinline__ double block_sum(double v, double* sh) {          // fixed order: lanes by shuffle tree, waves in index order
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
     __syncthreads();
     double t = 0.0;
-    if (threadIdx.x == 0) for (int w = 0; w < MT / 64; ++w) t += sh[w];
+    if (threadIdx.x == 0) for (int w = 0; w < NT / 64; ++w) t += sh[w];
     __syncthreads();
     return t;
 }
-// u = a - alpha * u   (a nullable: u = -alpha * u), partial |u|^2 -> part[blockIdx.x]      (doubles: a complex vector as 2n reals)
-__global__ __launch_bounds__(MT) void k_mc_lin(size_t n, const double* __restrict__ a, double sa, double alpha, double* __restrict__ u, double* __restrict__ part) {
-    __shared__ double sh[MT / 64];
-    double acc = 0.0;
-    for (size_t i = (size_t)blockIdx.x * MT + threadIdx.x; i < n; i += (size_t)MB * MT) {
-        const double v = (a ? a[i] * sa : 0.0) - alpha * u[i];
-        u[i] = v;
-        acc += v * v;
+__device__ __forceinline__ double wave_sum(const double* p, int cnt) {        // one wave: lane l adds p[l], p[l + 64], ..., then a shuffle tree
+    double v = 0.0;
+    for (int i = threadIdx.x; i < cnt; i += 64) v += p[i];
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    return __shfl(v, 0, 64);
+}
+__device__ __forceinline__ bool frozen(const LsqrState* st, int b) { return st && st[b].done; }
+__device__ __forceinline__ double2 cmul(double2 c, double2 v) { return make_double2(c.x * v.x - c.y * v.y, c.x * v.y + c.y * v.x); }
+
+// out[j][i] = maps[g0 + j][i % plane] * x[b][i],  b = (g0 + j) / ncoil    (grid: n / NT x cnt)
+__global__ __launch_bounds__(NT) void k_mcl_coil_mul(size_t n, size_t plane, int ncoil, int g0, const double2* __restrict__ x,
+                                                     const double2* __restrict__ maps, const LsqrState* __restrict__ st, double2* __restrict__ out) {
+    const int g = g0 + blockIdx.y, b = g / ncoil;
+    if (frozen(st, b)) return;
+    const size_t i = (size_t)blockIdx.x * NT + threadIdx.x;
+    if (i >= n) return;
+    out[(size_t)blockIdx.y * n + i] = cmul(maps[(size_t)g * plane + i % plane], x[(size_t)b * n + i]);
+}
+// t[b][i] (+)= sum over the chunk's coils j of slice b, ascending, of conj(maps[g][px]) * xj[g - g0][i]   (grid: n / NT x slices the chunk touches)
+__global__ __launch_bounds__(NT) void k_mcl_coil_sum(size_t n, size_t plane, int ncoil, int g0, int cnt, const double2* __restrict__ xj,
+                                                     const double2* __restrict__ maps, const LsqrState* __restrict__ st, double2* __restrict__ t) {
+    const int b = g0 / ncoil + blockIdx.y;
+    if (frozen(st, b)) return;
+    const size_t i = (size_t)blockIdx.x * NT + threadIdx.x;
+    if (i >= n) return;
+    const int lo = max(g0, b * ncoil), hi = min(g0 + cnt, (b + 1) * ncoil);
+    const size_t px = i % plane;
+    double2 a = lo > b * ncoil ? t[(size_t)b * n + i] : make_double2(0.0, 0.0);
+    for (int g = lo; g < hi; ++g) {
+        const double2 c = maps[(size_t)g * plane + px], v = xj[(size_t)(g - g0) * n + i];
+        a.x += c.x * v.x + c.y * v.y;                              // conj(c) * v
+        a.y += c.x * v.y - c.y * v.x;
     }
-    const double t = mc_block_sum(acc, sh);
-    if (threadIdx.x == 0) part[blockIdx.x] = t;
+    t[(size_t)b * n + i] = a;
 }
-// v = (t + ub * sr) - beta * v, partial |v|^2
-__global__ __launch_bounds__(MT) void k_mc_vupd(size_t n, const double* __restrict__ t, const double* __restrict__ ub, double sr, double beta, double* __restrict__ v,
-                                                double* __restrict__ part) {
-    __shared__ double sh[MT / 64];
-    double acc = 0.0;
-    for (size_t i = (size_t)blockIdx.x * MT + threadIdx.x; i < n; i += (size_t)MB * MT) {
-        const double w = (t[i] + ub[i] * sr) - beta * v[i];
-        v[i] = w;
-        acc += w * w;
+// measurement half of u, one coil image per blockIdx.y (grid: PC x cnt), m complex each:
+//   INIT  u_j = y_j - (A C_j x0),  partials |u_j|^2 and |y_j|^2
+//   ITER  u_j = (A C_j v) - (alpha / beta) u_j
+__global__ __launch_bounds__(NT) void k_mcl_ulin(int mode, size_t m, int ncoil, int g0, const double2* __restrict__ ya, const double2* __restrict__ y,
+                                                 const LsqrState* __restrict__ st, double2* __restrict__ ut, double* __restrict__ pu, double* __restrict__ py) {
+    __shared__ double sh[NT / 64];
+    const int g = g0 + blockIdx.y, b = g / ncoil;
+    if (frozen(st, b)) return;
+    const double coef = mode == MCL_ITER ? st[b].sc[0].alpha * st[b].sc[0].ub : 0.0;
+    const double2* a = ya + (size_t)blockIdx.y * m;
+    double2* u = ut + (size_t)g * m;
+    double su = 0.0, sy = 0.0;
+    for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < m; i += (size_t)PC * NT) {
+        const double2 av = a[i];
+        double2 w;
+        if (mode == MCL_INIT) {
+            const double2 yv = y[(size_t)g * m + i];
+            w = make_double2(yv.x - av.x, yv.y - av.y);
+            sy += yv.x * yv.x + yv.y * yv.y;
+        } else {
+            const double2 uv = u[i];
+            w = make_double2(av.x - coef * uv.x, av.y - coef * uv.y);
+        }
+        u[i] = w;
+        su += w.x * w.x + w.y * w.y;
     }
-    const double tt = mc_block_sum(acc, sh);
-    if (threadIdx.x == 0) part[blockIdx.x] = tt;
-}
-__global__ __launch_bounds__(MT) void k_mc_scale(size_t n, double s, double* __restrict__ u) {
-    for (size_t i = (size_t)blockIdx.x * MT + threadIdx.x; i < n; i += (size_t)gridDim.x * MT) u[i] *= s;
-}
-// d = (v - thet d) / rho ; partials |d|^2 and |x|^2
-__global__ __launch_bounds__(MT) void k_mc_dupd(size_t n, const double* __restrict__ v, double thet, double rho, double* __restrict__ d, const double* __restrict__ x,
-                                                double* __restrict__ part) {
-    __shared__ double sh[MT / 64];
-    double a = 0.0, b = 0.0;
-    for (size_t i = (size_t)blockIdx.x * MT + threadIdx.x; i < n; i += (size_t)MB * MT) {
-        const double w = (v[i] - thet * d[i]) / rho;
-        d[i] = w;
-        a += w * w; b += x[i] * x[i];
+    su = block_sum(su, sh);
+    if (mode == MCL_INIT) sy = block_sum(sy, sh);
+    if (threadIdx.x == 0) {
+        pu[(size_t)g * PC + blockIdx.x] = su;
+        if (mode == MCL_INIT) py[(size_t)g * PC + blockIdx.x] = sy;
     }
-    const double ta = mc_block_sum(a, sh);
-    const double tb = mc_block_sum(b, sh);
-    if (threadIdx.x == 0) { part[blockIdx.x] = ta; part[MB + blockIdx.x] = tb; }
 }
-__global__ __launch_bounds__(MT) void k_mc_axpy(size_t n, double phi, const double* __restrict__ d, double* __restrict__ x) {
-    for (size_t i = (size_t)blockIdx.x * MT + threadIdx.x; i < n; i += (size_t)gridDim.x * MT) x[i] += phi * d[i];
+// image half of u, per slice (grid: PS x B):
+//   INIT  u2 = sr z - sr x0,  d = 0,  partials |u2|^2 and |z|^2
+//   ITER  v = v / alpha (stored scaled from here on),  u2 = sr v - (alpha / beta) u2,  partial |u2|^2
+__global__ __launch_bounds__(NT) void k_mcl_ub(int mode, size_t n, double sr, const double2* __restrict__ z, const double2* __restrict__ x,
+                                               const LsqrState* __restrict__ st, double2* __restrict__ ub, double2* __restrict__ v, double2* __restrict__ d,
+                                               double* __restrict__ pb, double* __restrict__ pz) {
+    __shared__ double sh[NT / 64];
+    const int b = blockIdx.y;
+    if (mode == MCL_ITER && frozen(st, b)) return;
+    const size_t o = (size_t)b * n;
+    double ia = 0.0, coef = 0.0;
+    if (mode == MCL_ITER) { ia = st[b].sc[0].ua; coef = st[b].sc[0].alpha * st[b].sc[0].ub; }
+    double sb = 0.0, szz = 0.0;
+    for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < n; i += (size_t)PS * NT) {
+        double2 w;
+        if (mode == MCL_INIT) {
+            const double2 zv = z[o + i], xv = x[o + i];
+            w = make_double2(zv.x * sr - xv.x * sr, zv.y * sr - xv.y * sr);
+            d[o + i] = make_double2(0.0, 0.0);
+            szz += zv.x * zv.x + zv.y * zv.y;
+        } else {
+            double2 vv = v[o + i];
+            vv = make_double2(vv.x * ia, vv.y * ia);
+            v[o + i] = vv;
+            const double2 uv = ub[o + i];
+            w = make_double2(vv.x * sr - coef * uv.x, vv.y * sr - coef * uv.y);
+        }
+        ub[o + i] = w;
+        sb += w.x * w.x + w.y * w.y;
+    }
+    sb = block_sum(sb, sh);
+    if (mode == MCL_INIT) szz = block_sum(szz, sh);
+    if (threadIdx.x == 0) {
+        pb[(size_t)b * PS + blockIdx.x] = sb;
+        if (mode == MCL_INIT) pz[(size_t)b * PS + blockIdx.x] = szz;
+    }
 }
-__global__ __launch_bounds__(MT) void k_mc_sq(size_t n, const double* __restrict__ a, double* __restrict__ part) {
-    __shared__ double sh[MT / 64];
-    double acc = 0.0;
-    for (size_t i = (size_t)blockIdx.x * MT + threadIdx.x; i < n; i += (size_t)MB * MT) acc += a[i] * a[i];
-    const double t = mc_block_sum(acc, sh);
-    if (threadIdx.x == 0) part[blockIdx.x] = t;
+// d = (v - thet d) / rho, partials |d|^2 and |x|^2 (x before this iteration's update: the stagnation test)   (grid: PS x B)
+__global__ __launch_bounds__(NT) void k_mcl_dupd(size_t n, const double2* __restrict__ v, const double2* __restrict__ x, const LsqrState* __restrict__ st,
+                                                 double2* __restrict__ d, double* __restrict__ pd, double* __restrict__ px) {
+    __shared__ double sh[NT / 64];
+    const int b = blockIdx.y;
+    if (frozen(st, b)) return;
+    const size_t o = (size_t)b * n;
+    const double thet = st[b].sc[0].thet, rho = st[b].sc[0].rho;
+    double a = 0.0, c = 0.0;
+    for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < n; i += (size_t)PS * NT) {
+        const double2 vv = v[o + i], dv = d[o + i], xv = x[o + i];
+        const double2 w = make_double2((vv.x - thet * dv.x) / rho, (vv.y - thet * dv.y) / rho);
+        d[o + i] = w;
+        a += w.x * w.x + w.y * w.y;
+        c += xv.x * xv.x + xv.y * xv.y;
+    }
+    a = block_sum(a, sh);
+    c = block_sum(c, sh);
+    if (threadIdx.x == 0) { pd[(size_t)b * PS + blockIdx.x] = a; px[(size_t)b * PS + blockIdx.x] = c; }
+}
+// the x update of the iteration that passed its stop tests, fused with the next v (grid: PS x B):
+//   INIT  v = t / beta + sr u2 / beta
+//   ITER  x += phi d,  v = t / beta + sr u2 / beta - beta v
+// partial |v|^2 (v unscaled: the next k_mcl_ub divides by alpha)
+__global__ __launch_bounds__(NT) void k_mcl_vupd(int mode, size_t n, double sr, const double2* __restrict__ t, const double2* __restrict__ ub,
+                                                 const double2* __restrict__ d, const LsqrState* __restrict__ st, double2* __restrict__ x,
+                                                 double2* __restrict__ v, double* __restrict__ pv) {
+    __shared__ double sh[NT / 64];
+    const int b = blockIdx.y;
+    if (frozen(st, b)) return;
+    const size_t o = (size_t)b * n;
+    const double ib = st[b].sc[0].ub, beta = st[b].sc[0].beta, phi = st[b].sc[0].phi;
+    double a = 0.0;
+    for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < n; i += (size_t)PS * NT) {
+        const double2 tv = t[o + i], uv = ub[o + i];
+        double2 w = make_double2(tv.x * ib + uv.x * ib * sr, tv.y * ib + uv.y * ib * sr);
+        if (mode == MCL_ITER) {
+            const double2 dv = d[o + i], xv = x[o + i], vv = v[o + i];
+            x[o + i] = make_double2(xv.x + phi * dv.x, xv.y + phi * dv.y);
+            w = make_double2(w.x - beta * vv.x, w.y - beta * vv.y);
+        }
+        v[o + i] = w;
+        a += w.x * w.x + w.y * w.y;
+    }
+    a = block_sum(a, sh);
+    if (threadIdx.x == 0) pv[(size_t)b * PS + blockIdx.x] = a;
 }
 
-struct McBuf { double2 *ut = nullptr, *ub = nullptr, *v = nullptr, *d = nullptr, *t = nullptr, *scr = nullptr; double* part = nullptr; };
-
-int mc_sum(qmri_ctx* ctx, const double* d_part, int cnt, double* out) {          // block partials -> host, added in block order
-    std::vector<double> h((size_t)cnt);
-    QMRI_HIP(ctx, hipMemcpyAsync(h.data(), d_part, (size_t)cnt * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    double s = 0.0;
-    for (double v : h) s += v;
-    *out = s;
-    return QMRI_OK;
+struct ScalarArgs { LsqrState* st; LsqrState* hst; McParts p; int ncoil, ii, maxit; double tol, r; };
+__device__ void mcl_tell(const ScalarArgs& a, int b, const LsqrState& s) {
+    if (threadIdx.x == 0 && a.hst) { LsqrState* h = a.hst + b; h->iter = s.iter; h->flag = s.flag; h->done = s.done; }
 }
-// tm[j] = A (C_j . x) for all coils, in chunks of the operator's max_batch (qmri_forward_mc's device half); then u1 = tm * st - alpha * u1 chunk by chunk
-int mc_forward_lin(qmri_ctx* ctx, const McBuf& b, const double2* x, double st, double alpha, double2* u1, double* sumsq) {
+// the recurrences of orc_lsqr.c between the vector kernels, one wave per slice (grid: B x 64)
+__global__ __launch_bounds__(64) void k_mcl_scalar(int stage, ScalarArgs a) {
+    const int b = blockIdx.x;
+    LsqrState& S = a.st[b];
+    LsqrScalars& q = S.sc[0];
+    if (stage != SC_BETA0 && S.done) return;
+    double su = 0.0;
+    if (stage == SC_BETA0 || stage == SC_BETA)
+        for (int j = 0; j < a.ncoil; ++j) su += wave_sum(a.p.pu + ((size_t)b * a.ncoil + j) * PC, PC);
+    if (stage == SC_BETA0) {
+        double sy = 0.0;
+        for (int j = 0; j < a.ncoil; ++j) sy += wave_sum(a.p.py + ((size_t)b * a.ncoil + j) * PC, PC);
+        const double sz = wave_sum(a.p.pz + (size_t)b * PS, PS), sb = wave_sum(a.p.pb + (size_t)b * PS, PS);
+        if (threadIdx.x) return;
+        S.n2b = sqrt(sy + a.r * sz);
+        S.tolb = a.tol * S.n2b;
+        S.ny2 = sy;
+        q.beta = sqrt(su + sb);
+        q.normr = q.beta;
+        q.ub = q.beta != 0.0 ? 1.0 / q.beta : 1.0;
+        q.c = 1.0; q.s = 0.0; q.phibar = q.beta; q.norma = 0.0; q.phi = 0.0; q.thet = 0.0; q.rho = 1.0; q.alpha = 0.0;
+        S.pad = 0; S.iter = a.maxit; S.flag = 1; S.done = 0;
+        mcl_tell(a, b, S);
+    } else if (stage == SC_BETA) {
+        const double sb = wave_sum(a.p.pb + (size_t)b * PS, PS);
+        if (threadIdx.x) return;
+        const double beta = sqrt(su + sb), alpha = q.alpha;
+        q.beta = beta;
+        q.ub = 1.0 / beta;
+        q.norma = sqrt(q.norma * q.norma + alpha * alpha + beta * beta);
+        const double thet = -q.s * alpha, rhot = q.c * alpha, rho = sqrt(rhot * rhot + beta * beta);
+        q.thet = thet; q.rho = rho;
+        q.c = rhot / rho;
+        q.s = -beta / rho;
+        q.phi = q.c * q.phibar;
+        if (q.phi == 0.0) S.pad = 1;
+        q.phibar = q.s * q.phibar;
+    } else if (stage == SC_STOP) {
+        const double sd = wave_sum(a.p.pd + (size_t)b * PS, PS), sx = wave_sum(a.p.px + (size_t)b * PS, PS);
+        if (threadIdx.x) return;
+        if (fabs(q.phi) * sqrt(sd) < DBL_EPSILON * sqrt(sx)) S.pad++; else S.pad = 0;
+        if (q.factor / (q.norma * q.normr) <= a.tol || q.normr <= S.tolb) { S.done = 1; S.iter = a.ii - 1; S.flag = 0; }
+        else if (S.pad >= 3) { S.done = 1; S.iter = a.ii - 1; S.flag = 3; }
+        else q.normr = fabs(q.s) * q.normr;
+        if (S.done) mcl_tell(a, b, S);
+    } else {   // SC_ALPHA
+        const double sv = wave_sum(a.p.pv + (size_t)b * PS, PS);
+        if (threadIdx.x) return;
+        const double alpha = sqrt(sv);
+        q.alpha = alpha;
+        if (a.ii == 0) {
+            q.ua = alpha != 0.0 ? 1.0 / alpha : 1.0;
+            q.factor = alpha * q.beta;
+            if (q.factor == 0.0 || S.n2b == 0.0) { S.done = 1; S.iter = 0; S.flag = 0; }
+            else if (a.maxit == 0) { S.done = 1; S.iter = 0; S.flag = 1; }
+        } else {
+            q.ua = 1.0 / alpha;
+            q.factor = alpha * fabs(q.s * q.phi);
+            if (a.ii == a.maxit) { S.done = 1; S.iter = a.maxit; S.flag = 1; }
+        }
+        if (S.done) mcl_tell(a, b, S);
+    }
+}
+
+inline unsigned blocks_of(size_t n) { return (unsigned)((n + NT - 1) / NT); }
+
+// A_mc' (one coil image per row of u) into t, chunk by chunk
+int mc_adjoint_chunks(qmri_ctx* ctx, int B, int ncoil, const double2* maps, const double2* ut, const LsqrState* st, double2* t) {
     OpHost& o = ctx->op;
+    McWork& w = o.mc;
     const size_t n = (size_t)o.N * o.M * o.s, plane = (size_t)o.N * o.M;
-    double tot = 0.0;
-    for (int j0 = 0; j0 < o.ncoil; j0 += o.maxB) {
-        const int cnt = std::min(o.maxB, o.ncoil - j0);
-        QMRI_TRY(ew_launch_coil_mul(ctx, n, plane, cnt, x, o.d_coils + (size_t)j0 * plane, b.scr));
-        QMRI_TRY(dc_launch_fwd(ctx, qmri_opdev(ctx), o.ls, DC_PLAIN, cnt, b.scr, o.d_tmp, o.d_ya, nullptr));
-        const size_t len = (size_t)2 * cnt * o.m;
-        k_mc_lin<<<dim3(MB), dim3(MT), 0, ctx->stream>>>(len, (const double*)o.d_ya, st, alpha, (double*)(u1 + (size_t)j0 * o.m), b.part);
+    for (int g0 = 0; g0 < B * ncoil; g0 += o.maxB) {
+        const int cnt = std::min(o.maxB, B * ncoil - g0), nb = (g0 + cnt - 1) / ncoil - g0 / ncoil + 1;
+        QMRI_TRY(dc_launch_adj(ctx, qmri_opdev(ctx), cnt, ut + (size_t)g0 * o.m, o.d_tmp, w.scr));
+        k_mcl_coil_sum<<<dim3(blocks_of(n), nb), dim3(NT), 0, ctx->stream>>>(n, plane, ncoil, g0, cnt, w.scr, maps, st, t);
         QMRI_HIP(ctx, hipGetLastError());
-        double s = 0.0;
-        QMRI_TRY(mc_sum(ctx, b.part, MB, &s));
-        tot += s;
     }
-    *sumsq = tot;
     return QMRI_OK;
 }
-// t = A_mc' u1
-int mc_adjoint(qmri_ctx* ctx, const McBuf& b, const double2* u1, double2* t) {
+// A_mc x chunk by chunk, each chunk's measurements straight into k_mcl_ulin
+int mc_forward_chunks(qmri_ctx* ctx, int mode, int B, int ncoil, const double2* maps, const double2* x, const double2* y, const LsqrState* st, const McParts& p) {
     OpHost& o = ctx->op;
+    McWork& w = o.mc;
     const size_t n = (size_t)o.N * o.M * o.s, plane = (size_t)o.N * o.M;
-    for (int j0 = 0; j0 < o.ncoil; j0 += o.maxB) {
-        const int cnt = std::min(o.maxB, o.ncoil - j0);
-        QMRI_TRY(dc_launch_adj(ctx, qmri_opdev(ctx), cnt, u1 + (size_t)j0 * o.m, o.d_tmp, b.scr));
-        QMRI_TRY(ew_launch_coil_sum(ctx, n, plane, cnt, b.scr, o.d_coils + (size_t)j0 * plane, t, j0 > 0));
+    for (int g0 = 0; g0 < B * ncoil; g0 += o.maxB) {
+        const int cnt = std::min(o.maxB, B * ncoil - g0);
+        k_mcl_coil_mul<<<dim3(blocks_of(n), cnt), dim3(NT), 0, ctx->stream>>>(n, plane, ncoil, g0, x, maps, st, w.scr);
+        QMRI_HIP(ctx, hipGetLastError());
+        QMRI_TRY(dc_launch_fwd(ctx, qmri_opdev(ctx), o.ls, DC_PLAIN, cnt, w.scr, o.d_tmp, o.d_ya, nullptr));
+        k_mcl_ulin<<<dim3(PC, cnt), dim3(NT), 0, ctx->stream>>>(mode, (size_t)o.m, ncoil, g0, o.d_ya, y, st, w.ut, p.pu, p.py);
+        QMRI_HIP(ctx, hipGetLastError());
     }
+    return QMRI_OK;
+}
+int mc_scalar(qmri_ctx* ctx, int stage, int B, const ScalarArgs& a) {
+    k_mcl_scalar<<<dim3(B), dim3(64), 0, ctx->stream>>>(stage, a);
+    QMRI_HIP(ctx, hipGetLastError());
     return QMRI_OK;
 }
 }  // namespace
 
-// LSQR on [A_mc; sqrt(r) I] x = [y; sqrt(r) z] from x0 = d_x (device, overwritten with the solution).  d_y: [ncoil][m] in the ABI's frame-major order.
-// Recurrences and stop rules in the order of oracle/orc_lsqr.c (MATLAB's lsqr as documented; flags 0 converged, 1 maxit, 3 stagnation).
-int qmri_lsqr_mc_dev(qmri_ctx* ctx, const double2* d_y, const double2* d_z, double r, double tol, int maxit, double2* d_x, int32_t* iters_out, int32_t* flag_out) {
+void mc_free_work(McWork& w) {
+    void* ptrs[] = {w.ut, w.ub, w.v, w.d, w.t, w.scr, w.part, w.st, w.sy, w.sm, w.sx, w.sz};
+    for (void* p : ptrs) if (p) (void)hipFree(p);
+    if (w.hst) (void)hipHostFree(w.hst);
+    w = McWork();
+}
+
+// work buffers of a B-slice, ncoil-coil solve: allocated on first use, grown only when B or B x ncoil grows (qmri_free_operator frees them)
+int mc_ensure_work(qmri_ctx* ctx, int B, int ncoil) {
     OpHost& o = ctx->op;
-    if (!o.ncoil) { qmri_set_error(ctx, "no coil maps set: call qmri_set_coils first"); return QMRI_ERR_STATE; }
-    const size_t n = (size_t)o.N * o.M * o.s, n2 = 2 * n, mtot = (size_t)o.ncoil * o.m;
-    McBuf b;
-    void* owned[7] = {};
-    auto alloc = [&](void** p, size_t bytes, int slot) { if (hipMalloc(p, bytes) != hipSuccess) return false; owned[slot] = *p; return true; };
-    int rc = QMRI_OK;
-    if (!alloc((void**)&b.ut, mtot * sizeof(double2), 0) || !alloc((void**)&b.ub, n * sizeof(double2), 1) || !alloc((void**)&b.v, n * sizeof(double2), 2) ||
-        !alloc((void**)&b.d, n * sizeof(double2), 3) || !alloc((void**)&b.t, n * sizeof(double2), 4) || !alloc((void**)&b.scr, (size_t)o.maxB * n * sizeof(double2), 5) ||
-        !alloc((void**)&b.part, (size_t)2 * MB * sizeof(double), 6)) {
-        qmri_set_error(ctx, "hipMalloc failed in the multi-coil x-update");
-        rc = QMRI_ERR_NOMEM;
+    McWork& w = o.mc;
+    const size_t img = (size_t)B * ncoil;
+    if (w.ut && (size_t)B <= w.cap_sl && img <= w.cap_img) return QMRI_OK;
+    QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const size_t cap_sl = std::max((size_t)B, w.cap_sl), cap_img = std::max(img, w.cap_img);
+    auto drop = [&]() {                                        // the solve's buffers only (the staging grows on its own: mc_ensure_staging)
+        void* ptrs[] = {w.ut, w.ub, w.v, w.d, w.t, w.scr, w.part, w.st};
+        for (void* p : ptrs) if (p) (void)hipFree(p);
+        if (w.hst) (void)hipHostFree(w.hst);
+        w.ut = w.ub = w.v = w.d = w.t = w.scr = nullptr; w.part = nullptr; w.st = w.hst = nullptr;
+        w.cap_sl = w.cap_img = 0;
+    };
+    drop();
+    const size_t n = (size_t)o.N * o.M * o.s;
+    const size_t parts = 2 * cap_img * PC + 5 * cap_sl * PS;
+    if (hipMalloc((void**)&w.ut, cap_img * o.m * sizeof(double2)) != hipSuccess || hipMalloc((void**)&w.ub, cap_sl * n * sizeof(double2)) != hipSuccess ||
+        hipMalloc((void**)&w.v, cap_sl * n * sizeof(double2)) != hipSuccess || hipMalloc((void**)&w.d, cap_sl * n * sizeof(double2)) != hipSuccess ||
+        hipMalloc((void**)&w.t, cap_sl * n * sizeof(double2)) != hipSuccess || hipMalloc((void**)&w.scr, (size_t)o.maxB * n * sizeof(double2)) != hipSuccess ||
+        hipMalloc((void**)&w.part, parts * sizeof(double)) != hipSuccess || hipMalloc((void**)&w.st, cap_sl * sizeof(LsqrState)) != hipSuccess ||
+        hipHostMalloc((void**)&w.hst, cap_sl * sizeof(LsqrState), hipHostMallocDefault) != hipSuccess) {
+        drop();
+        qmri_set_error(ctx, "out of device memory for the multi-coil LSQR of %d slices x %d coils", B, ncoil);
+        return QMRI_ERR_NOMEM;
     }
-    int iter = maxit, flag = 1;
-    do {
-        if (rc != QMRI_OK) break;
-        const double sr = std::sqrt(r);
-        double sy = 0.0, sz = 0.0, s1 = 0.0, s2 = 0.0;
-#define MC_TRY(x) { rc = (x); if (rc != QMRI_OK) break; }
-#define MC_LAUNCH(...) { __VA_ARGS__; if (hipGetLastError() != hipSuccess) { qmri_set_error(ctx, "kernel launch failed in the multi-coil x-update"); rc = QMRI_ERR_HIP; break; } }
-        // n2b = norm([y; sqrt(r) z])
-        MC_LAUNCH((k_mc_sq<<<dim3(MB), dim3(MT), 0, ctx->stream>>>(2 * mtot, (const double*)d_y, b.part)));
-        MC_TRY(mc_sum(ctx, b.part, MB, &sy));
-        MC_LAUNCH((k_mc_sq<<<dim3(MB), dim3(MT), 0, ctx->stream>>>(n2, (const double*)d_z, b.part)));
-        MC_TRY(mc_sum(ctx, b.part, MB, &sz));
-        const double n2b = std::sqrt(sy + r * sz), tolb = tol * n2b;
-        // u = b - B x0:  u1 = y - A_mc x0  (k_mc_lin with u1 := y first),  u2 = sqrt(r) z - sqrt(r) x0
-        if (hipMemcpyAsync(b.ut, d_y, mtot * sizeof(double2), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess ||
-            hipMemcpyAsync(b.ub, d_x, n * sizeof(double2), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess ||
-            hipMemsetAsync(b.d, 0, n * sizeof(double2), ctx->stream) != hipSuccess) { rc = QMRI_ERR_HIP; break; }
-        MC_TRY(mc_forward_lin(ctx, b, d_x, -1.0, -1.0, b.ut, &s1));                      // u1 = -(A x0) + y
-        MC_LAUNCH((k_mc_lin<<<dim3(MB), dim3(MT), 0, ctx->stream>>>(n2, (const double*)d_z, sr, sr, (double*)b.ub, b.part)));   // u2 = z sr - sr x0
-        MC_TRY(mc_sum(ctx, b.part, MB, &s2));
-        double beta = std::sqrt(s1 + s2), normr = beta;
-        if (beta != 0.0) {
-            MC_LAUNCH((k_mc_scale<<<dim3(MB), dim3(MT), 0, ctx->stream>>>(2 * mtot, 1.0 / beta, (double*)b.ut)));
-            MC_LAUNCH((k_mc_scale<<<dim3(MB), dim3(MT), 0, ctx->stream>>>(n2, 1.0 / beta, (double*)b.ub)));
+    w.cap_sl = cap_sl; w.cap_img = cap_img;
+    return QMRI_OK;
+}
+
+// staging of host-array calls: maps, y, x, z (or x0) for B slices of ncoil coils, grown only when B or B x ncoil grows
+int mc_ensure_staging(qmri_ctx* ctx, int B, int ncoil) {
+    OpHost& o = ctx->op;
+    McWork& w = o.mc;
+    const size_t img = (size_t)B * ncoil;
+    if (w.sy && (size_t)B <= w.stage_sl && img <= w.stage_img) return QMRI_OK;
+    QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const size_t sl = std::max((size_t)B, w.stage_sl), im = std::max(img, w.stage_img);
+    void* old[] = {w.sy, w.sm, w.sx, w.sz};
+    for (void* p : old) if (p) (void)hipFree(p);
+    w.sy = w.sm = w.sx = w.sz = nullptr;
+    w.stage_sl = w.stage_img = 0;
+    const size_t n = (size_t)o.N * o.M * o.s, plane = (size_t)o.N * o.M;
+    if (hipMalloc((void**)&w.sy, im * o.m * sizeof(double2)) != hipSuccess || hipMalloc((void**)&w.sm, im * plane * sizeof(double2)) != hipSuccess ||
+        hipMalloc((void**)&w.sx, sl * n * sizeof(double2)) != hipSuccess || hipMalloc((void**)&w.sz, sl * n * sizeof(double2)) != hipSuccess) {
+        void* got[] = {w.sy, w.sm, w.sx, w.sz};
+        for (void* p : got) if (p) (void)hipFree(p);
+        w.sy = w.sm = w.sx = w.sz = nullptr;
+        qmri_set_error(ctx, "out of device memory for the staging of %d slices x %d coils", B, ncoil);
+        return QMRI_ERR_NOMEM;
+    }
+    w.stage_sl = sl; w.stage_img = im;
+    return QMRI_OK;
+}
+
+// x = A_mc' y for B slices (the ADMM loop's start, PnP_ADMM.m:84)
+int mc_adjoint_batch_dev(qmri_ctx* ctx, int B, int ncoil, const double2* d_maps, const double2* d_y, double2* d_x) {
+    QMRI_TRY(mc_ensure_work(ctx, B, ncoil));                   // (the chunks' coil images go through McWork::scr)
+    return mc_adjoint_chunks(ctx, B, ncoil, d_maps, d_y, nullptr, d_x);
+}
+
+// LSQR on [A_mc; sqrt(r) I] x = [y; sqrt(r) z] for B slices from x0 = d_x (device, overwritten with the solutions).  d_maps: [B][ncoil][N*M],
+// d_y: [B][ncoil][m] (the ABI's frame-major order), d_z / d_x: [B][n].  iters_out / flags_out: [B] (nullable).
+int qmri_lsqr_mc_batch_dev(qmri_ctx* ctx, int B, int ncoil, const double2* d_maps, const double2* d_y, const double2* d_z, double r, double tol, int maxit,
+                           double2* d_x, int32_t* iters_out, int32_t* flags_out) {
+    OpHost& o = ctx->op;
+    QMRI_TRY(mc_ensure_work(ctx, B, ncoil));
+    McWork& w = o.mc;
+    const size_t n = (size_t)o.N * o.M * o.s;
+    const double sr = std::sqrt(r);
+    const McParts p = mc_parts(w.part, B, ncoil);
+    ScalarArgs a{w.st, w.hst, p, ncoil, 0, maxit, tol, r};
+    const dim3 gs(PS, B);
+    // u = b - B x0, v = B' u
+    k_mcl_ub<<<gs, dim3(NT), 0, ctx->stream>>>(MCL_INIT, n, sr, d_z, d_x, w.st, w.ub, w.v, w.d, p.pb, p.pz);
+    QMRI_HIP(ctx, hipGetLastError());
+    QMRI_TRY(mc_forward_chunks(ctx, MCL_INIT, B, ncoil, d_maps, d_x, d_y, nullptr, p));
+    QMRI_TRY(mc_scalar(ctx, SC_BETA0, B, a));
+    QMRI_TRY(mc_adjoint_chunks(ctx, B, ncoil, d_maps, w.ut, w.st, w.t));
+    k_mcl_vupd<<<gs, dim3(NT), 0, ctx->stream>>>(MCL_INIT, n, sr, w.t, w.ub, w.d, w.st, d_x, w.v, p.pv);
+    QMRI_HIP(ctx, hipGetLastError());
+    QMRI_TRY(mc_scalar(ctx, SC_ALPHA, B, a));
+    // iterations in chunks: the first as many as the last solve needed, then a quarter of that (>= 2) at a time; one event wait per chunk.  The
+    // transforms run on every coil image of a chunk whether or not its slice is still active, so the host first waits for the initial step: a
+    // batch that stops at iteration 0 (y = 0, or z = x0 with A x0 = y) queues no iteration at all.
+    if (!ctx->ev_state) QMRI_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_state, hipEventDisableTiming));
+    QMRI_HIP(ctx, hipEventRecord(ctx->ev_state, ctx->stream));
+    QMRI_HIP(ctx, hipEventSynchronize(ctx->ev_state));
+    bool any = false;
+    for (int b = 0; b < B; ++b) any |= !w.hst[b].done;
+    int ii = 1, chunk = std::max(1, std::min(maxit, w.pred));
+    for (; any;) {
+        const int last = std::min(maxit, ii + chunk - 1);
+        for (; ii <= last; ++ii) {
+            a.ii = ii;
+            k_mcl_ub<<<gs, dim3(NT), 0, ctx->stream>>>(MCL_ITER, n, sr, nullptr, nullptr, w.st, w.ub, w.v, nullptr, p.pb, nullptr);
+            QMRI_HIP(ctx, hipGetLastError());
+            QMRI_TRY(mc_forward_chunks(ctx, MCL_ITER, B, ncoil, d_maps, w.v, nullptr, w.st, p));
+            QMRI_TRY(mc_scalar(ctx, SC_BETA, B, a));
+            k_mcl_dupd<<<gs, dim3(NT), 0, ctx->stream>>>(n, w.v, d_x, w.st, w.d, p.pd, p.px);
+            QMRI_HIP(ctx, hipGetLastError());
+            QMRI_TRY(mc_scalar(ctx, SC_STOP, B, a));
+            QMRI_TRY(mc_adjoint_chunks(ctx, B, ncoil, d_maps, w.ut, w.st, w.t));
+            k_mcl_vupd<<<gs, dim3(NT), 0, ctx->stream>>>(MCL_ITER, n, sr, w.t, w.ub, w.d, w.st, d_x, w.v, p.pv);
+            QMRI_HIP(ctx, hipGetLastError());
+            QMRI_TRY(mc_scalar(ctx, SC_ALPHA, B, a));
         }
-        double c = 1.0, s = 0.0, phibar = beta;
-        // v = B' u
-        MC_TRY(mc_adjoint(ctx, b, b.ut, b.t));
-        if (hipMemsetAsync(b.v, 0, n * sizeof(double2), ctx->stream) != hipSuccess) { rc = QMRI_ERR_HIP; break; }
-        MC_LAUNCH((k_mc_vupd<<<dim3(MB), dim3(MT), 0, ctx->stream>>>(n2, (const double*)b.t, (const double*)b.ub, sr, 0.0, (double*)b.v, b.part)));
-        MC_TRY(mc_sum(ctx, b.part, MB, &s1));
-        double alpha = std::sqrt(s1);
-        if (alpha != 0.0) MC_LAUNCH((k_mc_scale<<<dim3(MB), dim3(MT), 0, ctx->stream>>>(n2, 1.0 / alpha, (double*)b.v)));
-        double normar = alpha * beta;
-        if (normar == 0.0 || n2b == 0.0) { flag = 0; iter = 0; break; }
-        double norma = 0.0;
-        int stag = 0;
-        for (int ii = 1; ii <= maxit; ++ii) {
-            // u = B v - alpha u
-            MC_TRY(mc_forward_lin(ctx, b, b.v, 1.0, alpha, b.ut, &s1));
-            MC_LAUNCH((k_mc_lin<<<dim3(MB), dim3(MT), 0, ctx->stream>>>(n2, (const double*)b.v, sr, alpha, (double*)b.ub, b.part)));
-            MC_TRY(mc_sum(ctx, b.part, MB, &s2));
-            beta = std::sqrt(s1 + s2);
-            MC_LAUNCH((k_mc_scale<<<dim3(MB), dim3(MT), 0, ctx->stream>>>(2 * mtot, 1.0 / beta, (double*)b.ut)));
-            MC_LAUNCH((k_mc_scale<<<dim3(MB), dim3(MT), 0, ctx->stream>>>(n2, 1.0 / beta, (double*)b.ub)));
-            norma = std::sqrt(norma * norma + alpha * alpha + beta * beta);
-            const double thet = -s * alpha, rhot = c * alpha, rho = std::sqrt(rhot * rhot + beta * beta);
-            c = rhot / rho;
-            s = -beta / rho;
-            const double phi = c * phibar;
-            if (phi == 0.0) stag = 1;
-            phibar = s * phibar;
-            MC_LAUNCH((k_mc_dupd<<<dim3(MB), dim3(MT), 0, ctx->stream>>>(n2, (const double*)b.v, thet, rho, (double*)b.d, (const double*)d_x, b.part)));
-            double sd = 0.0, sx = 0.0;
-            {
-                std::vector<double> h((size_t)2 * MB);
-                if (hipMemcpyAsync(h.data(), b.part, h.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-                    hipStreamSynchronize(ctx->stream) != hipSuccess) { rc = QMRI_ERR_HIP; break; }
-                for (int k = 0; k < MB; ++k) { sd += h[k]; sx += h[MB + k]; }
-            }
-            if (std::fabs(phi) * std::sqrt(sd) < DBL_EPSILON * std::sqrt(sx)) stag++; else stag = 0;
-            if (normar / (norma * normr) <= tol) { flag = 0; iter = ii - 1; break; }
-            if (normr <= tolb) { flag = 0; iter = ii - 1; break; }
-            if (stag >= 3) { flag = 3; iter = ii - 1; break; }
-            MC_LAUNCH((k_mc_axpy<<<dim3(MB), dim3(MT), 0, ctx->stream>>>(n2, phi, (const double*)b.d, (double*)d_x)));
-            normr = std::fabs(s) * normr;
-            // v = B' u - beta v
-            MC_TRY(mc_adjoint(ctx, b, b.ut, b.t));
-            MC_LAUNCH((k_mc_vupd<<<dim3(MB), dim3(MT), 0, ctx->stream>>>(n2, (const double*)b.t, (const double*)b.ub, sr, beta, (double*)b.v, b.part)));
-            MC_TRY(mc_sum(ctx, b.part, MB, &s1));
-            alpha = std::sqrt(s1);
-            MC_LAUNCH((k_mc_scale<<<dim3(MB), dim3(MT), 0, ctx->stream>>>(n2, 1.0 / alpha, (double*)b.v)));
-            normar = alpha * std::fabs(s * phi);
-        }
-#undef MC_TRY
-#undef MC_LAUNCH
-    } while (0);
-    (void)hipStreamSynchronize(ctx->stream);
-    for (void* p : owned) if (p) (void)hipFree(p);
-    if (rc == QMRI_ERR_HIP && ctx->err.empty()) qmri_set_error(ctx, "HIP failure in the multi-coil x-update");
-    if (rc != QMRI_OK) return rc;
-    if (iters_out) *iters_out = iter;
-    if (flag_out) *flag_out = flag;
+        QMRI_HIP(ctx, hipEventRecord(ctx->ev_state, ctx->stream));
+        QMRI_HIP(ctx, hipEventSynchronize(ctx->ev_state));
+        bool active = false;
+        for (int b = 0; b < B; ++b) active |= !w.hst[b].done;
+        if (!active || ii > maxit) break;
+        chunk = std::max(2, w.pred / 4);
+    }
+    int most = 0;
+    for (int b = 0; b < B; ++b) {
+        if (iters_out) iters_out[b] = w.hst[b].iter;
+        if (flags_out) flags_out[b] = w.hst[b].flag;
+        most = std::max(most, (int)w.hst[b].iter);
+    }
+    w.pred = std::max(1, most + 1);
     return QMRI_OK;
 }

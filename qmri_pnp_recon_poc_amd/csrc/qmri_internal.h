@@ -250,6 +250,26 @@ struct NetPlan {
     bool ready = false;
 };
 
+// multi-coil LSQR of B slices (mc_kernels.hip): work buffers owned by the context, grown only when B or B x ncoil grows
+struct McWork {
+    double2 *ut = nullptr;              // [B][ncoil][m]  u(1:m) of every coil image, unscaled
+    double2 *ub = nullptr, *v = nullptr, *d = nullptr, *t = nullptr;   // [B][n]  u(m+1:end) unscaled, v, d, A_mc' u
+    double2 *scr = nullptr;             // [max_batch][n] coil images of one transform chunk
+    double* part = nullptr;             // fixed partial sums (mc_kernels.hip McParts)
+    LsqrState* st = nullptr;            // [B] device state; sc[0] only
+    LsqrState* hst = nullptr;           // [B] pinned: iter / done / flag written by the kernel that changes them
+    size_t cap_sl = 0, cap_img = 0;
+    int pred = 8;                       // iterations enqueued before the first event wait after the initial step (the last solve's count + 1)
+    // staging of the host-array entry points: maps [B][ncoil][N*M], y [B][ncoil][m], x and z (or x0) [B][n]
+    double2 *sm = nullptr, *sy = nullptr, *sx = nullptr, *sz = nullptr;
+    size_t stage_sl = 0, stage_img = 0;
+};
+void mc_free_work(McWork& w);
+int mc_ensure_staging(qmri_ctx* ctx, int B, int ncoil);
+int mc_adjoint_batch_dev(qmri_ctx* ctx, int B, int ncoil, const double2* d_maps, const double2* d_y, double2* d_x);
+int qmri_lsqr_mc_batch_dev(qmri_ctx* ctx, int B, int ncoil, const double2* d_maps, const double2* d_y, const double2* d_z, double r, double tol, int maxit,
+                           double2* d_x, int32_t* iters_out, int32_t* flags_out);
+
 // ---------------------------------------------------------------------------------------------------
 // context
 // ---------------------------------------------------------------------------------------------------
@@ -259,6 +279,7 @@ struct OpHost {
     double* d_Vt = nullptr; KEntry* d_ent = nullptr; int32_t* d_perm = nullptr; int32_t* d_kptr = nullptr;
     double2* d_tw = nullptr; int32_t* d_kslot = nullptr; double* d_ginv = nullptr;
     double2* d_coils = nullptr; int ncoil = 0;   // multi-coil extension: [ncoil][N*M] sensitivity maps (qmri_set_coils)
+    McWork mc;                          // ... and the work buffers of its LSQR
     KsDev ks{};                         // k-space LSQR plan + state (device pointers owned here)
     bool xhat_valid = false;            // ks.xhat holds the spectrum of d_x
     double ginv_r = -1.0;

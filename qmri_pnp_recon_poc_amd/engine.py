@@ -235,6 +235,53 @@ class Engine:
         self._check(self.L.qmri_pnp_admm_mc(self.h, _vp(yb), C.byref(p), _vp(x0b), _vp(x), li.ctypes.data_as(C.POINTER(C.c_int32))))
         return x.reshape((self.N, self.M, self.s), order="F"), li[:iters]
 
+    def _mc_stack(self, maps, y_mc):
+        """maps [S, N, M, ncoil], y_mc [S, m, ncoil] -> slice-major column-major buffers (S, ncoil, maps, y)."""
+        maps, y_mc = np.asarray(maps), np.asarray(y_mc)
+        if maps.ndim != 4 or maps.shape[1:3] != (self.N, self.M):
+            raise ValueError(f"maps must be [slices, {self.N}, {self.M}, ncoil]")
+        S, nc = maps.shape[0], maps.shape[3]
+        if y_mc.shape != (S, self.m, nc):
+            raise ValueError(f"y_mc must be [{S}, {self.m}, {nc}]")
+        mb = np.concatenate([_cbuf(maps[b]) for b in range(S)])
+        yb = np.concatenate([_cbuf(y_mc[b]) for b in range(S)])
+        return S, nc, mb, yb
+
+    def _image_stack(self, a, S):
+        if a is None:
+            return None
+        a = np.asarray(a)
+        if a.shape != (S, self.N, self.M, self.s):
+            raise ValueError(f"image stack must be [{S}, {self.N}, {self.M}, {self.s}]")
+        return np.concatenate([_cbuf(a[b]) for b in range(S)])
+
+    def xupdate_mc_batch(self, maps, y_mc, z, r, tol=1e-4, maxit=100, x0=None):
+        """Multi-coil x-update of a slice stack, each slice with its own maps (extension, no reference counterpart): maps [S, N, M, ncoil],
+        y_mc [S, m, ncoil], z / x0 [S, N, M, s].  Does not use or change the maps of set_coils.  Returns (x [S, N, M, s], iters [S], flags [S])."""
+        S, nc, mb, yb = self._mc_stack(maps, y_mc)
+        zb, x0b = self._image_stack(z, S), self._image_stack(x0, S)
+        n = self.N * self.M * self.s
+        x = np.empty(S * n, np.complex128)
+        it, fl = np.zeros(S, np.int32), np.zeros(S, np.int32)
+        ip = C.POINTER(C.c_int32)
+        self._check(self.L.qmri_xupdate_mc_batch(self.h, S, nc, _vp(mb), _vp(yb), _vp(zb), float(r), float(tol), int(maxit), _vp(x0b), _vp(x),
+                                                 it.ctypes.data_as(ip), fl.ctypes.data_as(ip)))
+        return np.stack([x[b * n:(b + 1) * n].reshape((self.N, self.M, self.s), order="F") for b in range(S)]), it, fl
+
+    def pnp_admm_mc_batch(self, maps, y_mc, slices_per_launch=1, gamma=0.05, iters=100, cg_tol=1e-4, cg_maxit=100, multi_level=False, noise_std=0.01,
+                          x0=None):
+        """Multi-coil PnP-ADMM of a slice stack, slices_per_launch at a time, each slice with its own maps (extension): maps [S, N, M, ncoil],
+        y_mc [S, m, ncoil].  Returns (X [S, N, M, s], lsqr_iters [S, iters])."""
+        S, nc, mb, yb = self._mc_stack(maps, y_mc)
+        x0b = self._image_stack(x0, S)
+        p = AdmmParams(float(gamma), int(iters), float(cg_tol), int(cg_maxit), SOLVER_LSQR, int(bool(multi_level)), float(noise_std), 0)
+        n = self.N * self.M * self.s
+        x = np.empty(S * n, np.complex128)
+        li = np.zeros((S, max(iters, 1)), np.int32)
+        self._check(self.L.qmri_pnp_admm_mc_batch(self.h, S, int(slices_per_launch), nc, _vp(mb), _vp(yb), C.byref(p), _vp(x0b), _vp(x),
+                                                  li.ctypes.data_as(C.POINTER(C.c_int32))))
+        return np.stack([x[b * n:(b + 1) * n].reshape((self.N, self.M, self.s), order="F") for b in range(S)]), li.reshape(-1)[: S * iters].reshape(S, iters)
+
     def xupdate(self, y, z, r, tol=1e-4, maxit=100, x0=None, solver="lsqr"):
         """The x-update of PnP_ADMM.m:102 alone.  Returns (x, iters, flag)."""
         yb, zb = _cbuf(y), _cbuf(z)

@@ -13,6 +13,8 @@ function [X, qmap, pd] = qmri_recon_batch(Y, param, devs, slices_per_launch)
 %   out.qmap / out.pd of every slice; empty when no dictionary is set or they are not asked for).
 %   devs (default 0): device ids, an id may repeat (two workers sharing one GPU); slices_per_launch (default 15).
 %   param: the reference's fields iter, gamma, cg_tol, denoiser_type, noise_map (PnP_ADMM.m:62-76); param.F from qmri_make_F.
+%   param.coils (optional, multi-coil extension with no reference counterpart): N x M x ncoil x S coil maps, one set per slice; Y is then
+%   m x ncoil x S, column (:, j, k) = F.forward(param.coils(:, :, j, k) .* X0_k) + noise.
 if nargin < 3 || isempty(devs), devs = 0; end
 if nargin < 4 || isempty(slices_per_launch), slices_per_launch = 15; end
 if ~isfield(param.F, 'qmri'), error('qmri:F', 'param.F must be created by qmri_make_F'); end
@@ -20,9 +22,15 @@ p.gamma = param.gamma;  p.iter = param.iter;  p.cg_tol = param.cg_tol;
 p.multi_level = double(strcmp(param.denoiser_type, 'multi_level'));
 if p.multi_level, p.noise_std = param.noise_map(1); else, p.noise_std = 0.01; end
 g = param.F.qmri;
-if nargout > 1
-    [X, qmap, pd] = qmri_mex('recon_batch', complex(double(Y)), p, double(devs(:)), double(slices_per_launch), [g.N g.M g.s]);
+if isfield(param, 'coils') && ~isempty(param.coils)
+    % multi-coil EXTENSION (no reference counterpart): param.coils N x M x ncoil x S (every slice its own maps), Y m x ncoil x S
+    a = {'recon_batch_mc', complex(double(Y)), complex(double(param.coils))};
 else
-    X = qmri_mex('recon_batch', complex(double(Y)), p, double(devs(:)), double(slices_per_launch), [g.N g.M g.s]);
+    a = {'recon_batch', complex(double(Y))};
+end
+if nargout > 1
+    [X, qmap, pd] = qmri_mex(a{:}, p, double(devs(:)), double(slices_per_launch), [g.N g.M g.s]);
+else
+    X = qmri_mex(a{:}, p, double(devs(:)), double(slices_per_launch), [g.N g.M g.s]);
 end
 end

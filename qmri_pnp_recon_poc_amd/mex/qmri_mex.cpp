@@ -15,6 +15,8 @@
 //   * 'device' selects the GPU of the single-context commands;
 //   * 'recon_batch' hands a whole slice stack to qmri_recon_batch: one worker (host thread + context) per entry of `devs`, slices_per_launch
 //     slices advanced together on each (k_conv6p, batched LSQR), x and the T1 / T2 / PD maps of every slice back.
+//   * 'recon_batch_mc' is the same for multi-coil stacks, every slice with its own coil maps (qmri_recon_batch_mc; an extension, no reference
+//     counterpart).
 // tests/cpp/mex_mock.cpp is a small stand-in for the MATLAB runtime's C API under which this file is compiled, LINKED against libqmri.so and
 // driven command by command on the GPU box (tests/test_gpu_mex.py); with MATLAB's own mex.h nothing here changes.
 #include "mex.h"
@@ -299,20 +301,38 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         }
         if (nlhs > 1) plhs[1] = diag; else mxDestroyArray(diag);
         if (nlhs > 2) plhs[2] = li; else mxDestroyArray(li);
-    } else if (c == "recon_batch") {                 // [X, qmap, pd] = qmri_mex('recon_batch', Y(m x S), param_struct, devs, slices_per_launch, [N M s])
+    } else if (c == "recon_batch" || c == "recon_batch_mc") {   // [X, qmap, pd] = qmri_mex('recon_batch', Y(m x S), param_struct, devs, slices_per_launch, [N M s])
         // north_star's batch path: S independent slices sharded over the GPUs in `devs` (one worker = host thread + context per entry; an id may
         // repeat), slices_per_launch advanced together on each; 100 PnP-ADMM iterations + dictionary match per slice (the match only when a dictionary
         // is set and maps are asked for).  Uses the operator / denoiser / dictionary given to 'set_operator' / 'set_denoiser' / 'set_dictionary'.
-        need(nrhs, 6, "[X, qmap, pd] = qmri_mex('recon_batch', Y, param, devs, slices_per_launch, [N M s])");
+        // 'recon_batch_mc' (multi-coil extension, no reference counterpart): qmri_mex('recon_batch_mc', Y(m x ncoil x S), maps(N x M x ncoil x S),
+        // param_struct, devs, slices_per_launch, [N M s]) -- every slice with its own coil maps (qmri_recon_batch_mc).
+        const bool mc = c == "recon_batch_mc";
+        const int o = mc ? 1 : 0;                                  // (arguments after Y move one place right)
+        if (mc) need(nrhs, 7, "[X, qmap, pd] = qmri_mex('recon_batch_mc', Y, maps, param, devs, slices_per_launch, [N M s])");
+        else need(nrhs, 6, "[X, qmap, pd] = qmri_mex('recon_batch', Y, param, devs, slices_per_launch, [N M s])");
         if (!g_op.V || !g_net.w) mexErrMsgIdAndTxt("qmri:recon_batch:state", "set_operator and set_denoiser (or load_onnx) must come first");
-        const size_t S = mxGetN(prhs[1]);
-        (void)dims_numel(prhs[5]);
-        want(mxIsStruct(prhs[2]), "qmri:recon_batch:type", "param must be a struct");
-        want(is_cdouble(prhs[1]) && S >= 1 && mxGetM(prhs[1]) == operator_m(), "qmri:recon_batch:size", "Y must be complex double, one column of m samples per slice");
-        want(mxIsDouble(prhs[3]) && !mxIsComplex(prhs[3]), "qmri:recon_batch:devs", "devs must be a double vector of device ids");
-        const double* d = mxGetDoubles(prhs[5]);
-        std::vector<int> devs(mxGetNumberOfElements(prhs[3]));
-        for (size_t i = 0; i < devs.size(); ++i) devs[i] = (int)mxGetDoubles(prhs[3])[i];
+        size_t S = mxGetN(prhs[1]), ncoil = 0;
+        if (mc) {
+            const mwSize nd = mxGetNumberOfDimensions(prhs[1]);
+            const mwSize* yd = mxGetDimensions(prhs[1]);
+            ncoil = nd >= 2 ? yd[1] : 1;
+            S = nd >= 3 ? yd[2] : 1;
+            want(nd <= 3 && is_cdouble(prhs[1]) && ncoil >= 1 && S >= 1 && yd[0] == operator_m(), "qmri:recon_batch_mc:size",
+                 "Y must be complex double, m x ncoil x S");
+            const mwSize md = mxGetNumberOfDimensions(prhs[2]);
+            const mwSize* cd = mxGetDimensions(prhs[2]);
+            want(is_cdouble(prhs[2]) && md >= 2 && md <= 4 && (mwSize)cd[0] == (mwSize)g_op.N && (mwSize)cd[1] == (mwSize)g_op.M &&
+                 mxGetNumberOfElements(prhs[2]) == (size_t)g_op.N * g_op.M * ncoil * S, "qmri:recon_batch_mc:maps",
+                 "maps must be complex double, N x M x ncoil x S");
+        }
+        (void)dims_numel(prhs[5 + o]);
+        want(mxIsStruct(prhs[2 + o]), "qmri:recon_batch:type", "param must be a struct");
+        if (!mc) want(is_cdouble(prhs[1]) && S >= 1 && mxGetM(prhs[1]) == operator_m(), "qmri:recon_batch:size", "Y must be complex double, one column of m samples per slice");
+        want(mxIsDouble(prhs[3 + o]) && !mxIsComplex(prhs[3 + o]), "qmri:recon_batch:devs", "devs must be a double vector of device ids");
+        const double* d = mxGetDoubles(prhs[5 + o]);
+        std::vector<int> devs(mxGetNumberOfElements(prhs[3 + o]));
+        for (size_t i = 0; i < devs.size(); ++i) devs[i] = (int)mxGetDoubles(prhs[3 + o])[i];
         if (devs.empty()) mexErrMsgIdAndTxt("qmri:recon_batch:devs", "devs must name at least one device");
         const bool maps = nlhs > 1 && g_dict.D;
         qmri_problem pb;
@@ -324,8 +344,8 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
             pb.K = (int)mxGetM(g_dict.D); pb.Q = (int)mxGetN(g_dict.lut);
             pb.D = (const float*)mxGetData(g_dict.D); pb.normD = (const float*)mxGetData(g_dict.normD); pb.lut = (const float*)mxGetData(g_dict.lut);
         }
-        pb.admm = admm_params(prhs[2], false);
-        pb.slices_per_launch = std::max(1, (int)mxGetScalar(prhs[4]));
+        pb.admm = admm_params(prhs[2 + o], false);
+        pb.slices_per_launch = std::max(1, (int)mxGetScalar(prhs[4 + o]));
         const mwSize xd[4] = {(mwSize)d[0], (mwSize)d[1], (mwSize)d[2], (mwSize)S};
         plhs[0] = mxCreateNumericArray(4, xd, mxDOUBLE_CLASS, mxCOMPLEX);
         mxArray *qm = nullptr, *pd = nullptr;
@@ -336,8 +356,10 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
             pd = mxCreateNumericArray(3, pdd, mxSINGLE_CLASS, mxCOMPLEX);
         }
         char err[1024] = "";
-        const int st = qmri_recon_batch((int)devs.size(), devs.data(), (int)S, &pb, mxGetComplexDoubles(prhs[1]), mxGetComplexDoubles(plhs[0]),
-                                        qm ? (float*)mxGetData(qm) : nullptr, pd ? (float*)mxGetData(pd) : nullptr, err, sizeof err);
+        const int st = mc ? qmri_recon_batch_mc((int)devs.size(), devs.data(), (int)S, &pb, (int)ncoil, mxGetComplexDoubles(prhs[2]), mxGetComplexDoubles(prhs[1]),
+                                                mxGetComplexDoubles(plhs[0]), qm ? (float*)mxGetData(qm) : nullptr, pd ? (float*)mxGetData(pd) : nullptr, err, sizeof err)
+                          : qmri_recon_batch((int)devs.size(), devs.data(), (int)S, &pb, mxGetComplexDoubles(prhs[1]), mxGetComplexDoubles(plhs[0]),
+                                             qm ? (float*)mxGetData(qm) : nullptr, pd ? (float*)mxGetData(pd) : nullptr, err, sizeof err);
         if (st != QMRI_OK) {
             char id[32];
             snprintf(id, sizeof id, "qmri:err%d", -st);
