@@ -267,6 +267,36 @@ int qmri_recon_batch(int ndev, const int* devs, int nslices, const qmri_problem*
 int qmri_recon_batch_mc(int ndev, const int* devs, int nslices, const qmri_problem* prob, int ncoil, const void* maps, const void* Y_mc,
                         void* X_out, float* qmap_out, float* pd_out, char* errbuf, size_t errbuf_len);
 
+/* ---- coil compression (multi-coil extension, no reference counterpart, parity unpinned) -------------------------- */
+/* One linear map on the coil index turns ncoil coils into nv virtual coils, applied alike to the data and to the maps (Buehrer et al. 2007,
+ * Huang et al. 2008), optionally after pre-whitening with a noise covariance Psi = L L^H (Cholesky, lower triangle of Psi read):
+ *   K = sum_i L^-1 y_i (L^-1 y_i)^H over the m samples of a slice (or of the stack: shared),  K = U diag(lambda) U^H, lambda descending, every
+ *   column of U scaled so that its entry of largest magnitude (lowest index on ties) is real and positive;  W = L^-H U(:, 1:nv)  (U(:, 1:nv)
+ *   without Psi);  y' = W^H y,  maps' = W^H maps.  nv: p->nv, or (nv == 0) the smallest nv with sum_{l<nv} lambda_l >= energy sum lambda,
+ *   the largest over the slices of a stack.  ncoil <= 128 (QMRI_ERR_UNSUPPORTED above).  Layouts as the _mc_batch calls: y_mc nslices x ncoil x m,
+ *   maps nslices x ncoil x N*M (m, N, M of qmri_set_operator); Psi ncoil x ncoil column-major. */
+typedef struct {
+    int32_t nv;          /* > 0: keep nv virtual coils; 0: choose by energy */
+    double  energy;      /* (0, 1], used when nv == 0 */
+    int32_t shared;      /* 0: one W per slice; 1: one W for the stack */
+} qmri_cc_params;
+/* Outputs are written compactly with the chosen nv: y_out nslices x nv x m, maps_out nslices x nv x N*M, W_out nmat x ncoil x nv (column-major per
+ * matrix), eig_out nmat x ncoil (nmat = 1 when shared, else nslices).  A caller who lets energy choose sizes them for nv = ncoil.  maps_out is
+ * nullable iff maps is; W_out and eig_out are nullable. */
+int qmri_coil_compress(qmri_ctx* ctx, int nslices, int ncoil, const void* y_mc, const void* maps, const void* noise_cov, const qmri_cc_params* p,
+                       int* nv_out, void* y_out, void* maps_out, void* W_out, double* eig_out);
+/* The same on device arrays of ctx's device (y_mc, maps, noise_cov, y_out, maps_out, W_out); eig_out stays a host array (the eigensolve runs on
+ * the host).  Returns after its kernels have finished. */
+int qmri_coil_compress_dev(qmri_ctx* ctx, int nslices, int ncoil, const void* d_y_mc, const void* d_maps, const void* d_noise_cov, const qmri_cc_params* p,
+                           int* nv_out, void* d_y_out, void* d_maps_out, void* d_W_out, double* eig_out);
+/* Host only, no context: the eigensolver of the coil compression (cyclic Jacobi) on the Hermitian n x n matrix whose upper triangle `herm` holds
+ * (column-major complex doubles), 1 <= n <= 128.  evals: n, descending; evecs: n x n column-major, phase rule as above. */
+int qmri_coil_eig(int n, const void* herm, double* evals, void* evecs);
+/* qmri_recon_batch_mc with every launch's slices compressed on the device (qmri_coil_compress_dev) before qmri_pnp_admm_mc_dev: cc->nv > 0 coils per
+ * slice, one W per slice (energy and shared are refused: a stack is split over workers and launches).  noise_cov: host ncoil x ncoil or NULL. */
+int qmri_recon_batch_mc_cc(int ndev, const int* devs, int nslices, const qmri_problem* prob, int ncoil, const void* maps, const void* Y_mc,
+                           void* X_out, float* qmap_out, float* pd_out, char* errbuf, size_t errbuf_len, const void* noise_cov, const qmri_cc_params* cc);
+
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------------ */
 typedef struct {
     double ms_xupdate, ms_denoiser, ms_elementwise, ms_diag, ms_match;   /* hipEvent time per stage */

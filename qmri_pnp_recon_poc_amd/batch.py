@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import AdmmParams, NetDesc, Problem
+from ._lib import AdmmParams, CcParams, NetDesc, Problem
 
 
 def shard_slices(nslices: int, world: int, rank: int) -> list:
@@ -26,13 +26,27 @@ def shard_slices(nslices: int, world: int, rank: int) -> list:
 
 def recon_batch(devices, Y, N, M, V, frame_ptr, kidx, weights, in_nc=10, out_nc=10, nc=(64, 128, 256, 512), nb=4,
                 dictionary=None, gamma=0.05, iters=100, cg_tol=1e-4, cg_maxit=100, solver="lsqr", multi_level=False,
-                noise_std=0.01, slices_per_launch=1, coil_maps=None):
+                noise_std=0.01, slices_per_launch=1, coil_maps=None, coil_compress=None, noise_cov=None):
     """Reconstruct Y[nslices, m] on the given devices; returns dict(X [nslices,N,M,s], qmap, pd).
 
     coil_maps [nslices, N, M, ncoil] (multi-coil extension, no reference counterpart): Y is then [nslices, m, ncoil], every slice is reconstructed
-    with its own maps through qmri_recon_batch_mc (LSQR solver only).  Without coil_maps nothing changes."""
+    with its own maps through qmri_recon_batch_mc (LSQR solver only).  Without coil_maps nothing changes.
+
+    coil_compress (with coil_maps): an int nv, or a dict of qmri_cc_params fields (nv, energy, shared), and noise_cov [ncoil, ncoil] (or None):
+    every launch compresses its slices to nv virtual coils on the device, one W per slice (whitened by noise_cov), before the reconstruction
+    (qmri_recon_batch_mc_cc; the library refuses energy and shared there).  Without coil_compress nothing changes."""
     L = _lib.lib()
     ncoil, Mb = 0, None
+    cc = None
+    if coil_compress is not None or noise_cov is not None:
+        if coil_maps is None:
+            raise ValueError("coil_compress / noise_cov need coil_maps (multi-coil stacks)")
+        if coil_compress is None:
+            raise ValueError("noise_cov is used by the coil compression: give coil_compress too")
+        d = {"nv": int(coil_compress)} if np.isscalar(coil_compress) else dict(coil_compress)
+        if set(d) - {"nv", "energy", "shared"}:
+            raise ValueError("coil_compress takes the fields nv, energy, shared")
+        cc = CcParams(int(d.get("nv", 0)), float(d.get("energy", 0.0)), int(bool(d.get("shared", False))))
     if coil_maps is not None:
         from .engine import _cbuf
         cm, Yc = np.asarray(coil_maps), np.asarray(Y)
@@ -43,6 +57,11 @@ def recon_batch(devices, Y, N, M, V, frame_ptr, kidx, weights, in_nc=10, out_nc=
         ncoil = int(cm.shape[3])
         Mb = np.ascontiguousarray(np.concatenate([_cbuf(cm[b]) for b in range(cm.shape[0])]))
         Y = np.stack([_cbuf(Yc[b]) for b in range(Yc.shape[0])])
+        if noise_cov is not None:
+            noise_cov = np.asarray(noise_cov)
+            if noise_cov.shape != (ncoil, ncoil):
+                raise ValueError(f"noise_cov must be [{ncoil}, {ncoil}]")
+            noise_cov = _cbuf(noise_cov)
     Y = np.ascontiguousarray(Y, dtype=np.complex128)
     nsl, m = Y.shape
     m //= max(ncoil, 1)
@@ -84,7 +103,10 @@ def recon_batch(devices, Y, N, M, V, frame_ptr, kidx, weights, in_nc=10, out_nc=
     err = C.create_string_buffer(1024)
     outs = (X.ctypes.data_as(C.c_void_p), qmap.ctypes.data_as(f) if qmap is not None else None, pd.ctypes.data_as(f) if pd is not None else None,
             err, len(err))
-    if ncoil:
+    if cc is not None:
+        st = L.qmri_recon_batch_mc_cc(len(devices), devs, nsl, C.byref(pb), ncoil, Mb.ctypes.data_as(C.c_void_p), Y.ctypes.data_as(C.c_void_p), *outs,
+                                      noise_cov.ctypes.data_as(C.c_void_p) if noise_cov is not None else None, C.byref(cc))
+    elif ncoil:
         st = L.qmri_recon_batch_mc(len(devices), devs, nsl, C.byref(pb), ncoil, Mb.ctypes.data_as(C.c_void_p), Y.ctypes.data_as(C.c_void_p), *outs)
     else:
         st = L.qmri_recon_batch(len(devices), devs, nsl, C.byref(pb), Y.ctypes.data_as(C.c_void_p), *outs)

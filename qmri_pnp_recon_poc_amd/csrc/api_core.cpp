@@ -155,6 +155,7 @@ extern "C" int qmri_destroy(qmri_ctx* ctx) {
     qmri_free_operator(ctx);
     qmri_free_net(ctx);
     qmri_free_dict(ctx);
+    cc_free_work(ctx->cc);
     for (auto& ev : ctx->ev) if (ev) (void)hipEventDestroy(ev);
     if (ctx->ev_state) (void)hipEventDestroy(ctx->ev_state);
     for (hipEvent_t e : ctx->chain) if (e) (void)hipEventDestroy(e);

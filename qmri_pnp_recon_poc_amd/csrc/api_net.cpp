@@ -1291,8 +1291,11 @@ extern "C" int qmri_dict_match(qmri_ctx* ctx, const void* X, int Npix, float* qm
 // and one launch per layer (same bits, tested).
 // ncoil > 0 (multi-coil extension, qmri_recon_batch_mc): Y holds ncoil x m samples per slice and `cmaps` ncoil x N*M maps per slice; each launch is
 // one qmri_pnp_admm_mc_dev call.  ncoil = 0 is the single-coil path, unchanged.
+// cc (qmri_recon_batch_mc_cc; nullptr on every other path): each launch's uploaded slices are first compressed on the device to cc->nv virtual coils
+// (qmri_coil_compress_dev, one W per slice, whitened with `psi` when given) and the reconstruction runs on the compressed stack.
 static int recon_worker(int device, bool shared_device, int widx, int nworkers, int nslices, const qmri_problem* pb, const char* Y, char* X_out,
-                        float* qmap_out, float* pd_out, std::string* err, int ncoil = 0, const char* cmaps = nullptr) {
+                        float* qmap_out, float* pd_out, std::string* err, int ncoil = 0, const char* cmaps = nullptr,
+                        const qmri_cc_params* cc = nullptr, const void* psi = nullptr) {
     qmri_ctx* ctx = nullptr;
     int st = qmri_create(device, &ctx);
     if (st != QMRI_OK) { *err = qmri_last_error(nullptr); return st; }
@@ -1304,7 +1307,11 @@ static int recon_worker(int device, bool shared_device, int widx, int nworkers, 
     const size_t by = (size_t)spl * m * sizeof(double2), bx = (size_t)spl * n * sizeof(double2);
     const size_t bq = (size_t)spl * npix * Q * sizeof(float), bp = (size_t)spl * npix * 2 * sizeof(float);
     const size_t bm = (size_t)spl * ncoil * npix * sizeof(double2);
-    struct Set { double2 *dY = nullptr, *dX = nullptr, *dM = nullptr; float *dq = nullptr, *dp = nullptr; char *hY = nullptr, *hX = nullptr, *hM = nullptr;
+    const int nv = cc ? cc->nv : ncoil;                             // coils the reconstruction sees
+    const size_t byc = (size_t)spl * pb->frame_ptr[pb->T] * nv * sizeof(double2), bmc = (size_t)spl * nv * npix * sizeof(double2);
+    double2* d_psi = nullptr;
+    struct Set { double2 *dY = nullptr, *dX = nullptr, *dM = nullptr, *dYc = nullptr, *dMc = nullptr; float *dq = nullptr, *dp = nullptr;
+                 char *hY = nullptr, *hX = nullptr, *hM = nullptr;
                  float *hq = nullptr, *hp = nullptr;
                  hipEvent_t matched = nullptr, copied = nullptr; int s0 = -1, cnt = 0; } set[2];
     hipStream_t cs = nullptr;
@@ -1334,10 +1341,13 @@ static int recon_worker(int device, bool shared_device, int widx, int nworkers, 
                  hipHostMalloc((void**)&S.hX, bx, hipHostMallocDefault) == hipSuccess && hipEventCreateWithFlags(&S.matched, hipEventDisableTiming) == hipSuccess &&
                  hipEventCreateWithFlags(&S.copied, hipEventDisableTiming) == hipSuccess;
             if (ok && ncoil) ok = hipMalloc((void**)&S.dM, bm) == hipSuccess && hipHostMalloc((void**)&S.hM, bm, hipHostMallocDefault) == hipSuccess;
+            if (ok && cc) ok = hipMalloc((void**)&S.dYc, byc) == hipSuccess && hipMalloc((void**)&S.dMc, bmc) == hipSuccess;
             if (ok && maps) ok = hipMalloc((void**)&S.dq, bq) == hipSuccess && hipMalloc((void**)&S.dp, bp) == hipSuccess &&
                                  hipHostMalloc((void**)&S.hq, bq, hipHostMallocDefault) == hipSuccess && hipHostMalloc((void**)&S.hp, bp, hipHostMallocDefault) == hipSuccess;
         }
+        if (ok && cc && psi) ok = hipMalloc((void**)&d_psi, (size_t)ncoil * ncoil * sizeof(double2)) == hipSuccess;
         if (!ok) { *err = "allocation failed in qmri_recon_batch"; st = QMRI_ERR_NOMEM; break; }
+        if (d_psi && hipMemcpy(d_psi, psi, (size_t)ncoil * ncoil * sizeof(double2), hipMemcpyHostToDevice) != hipSuccess) { hipfail("H2D copy"); break; }
         const int nlaunch = (nslices + spl - 1) / spl;
         int k = 0;
         for (int l = widx; l < nlaunch && st == QMRI_OK; l += nworkers, ++k) {
@@ -1351,7 +1361,11 @@ static int recon_worker(int device, bool shared_device, int widx, int nworkers, 
                 const size_t mb = (size_t)ncoil * npix * sizeof(double2);
                 std::memcpy(S.hM, cmaps + (size_t)s0 * mb, (size_t)cnt * mb);
                 if (hipMemcpyAsync(S.dM, S.hM, (size_t)cnt * mb, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) { hipfail("H2D copy"); break; }
-                if ((st = qmri_pnp_admm_mc_dev(ctx, cnt, ncoil, S.dM, S.dY, &pb->admm, nullptr, S.dX, nullptr)) != QMRI_OK) { bail(st); break; }
+                if (cc) {
+                    int got = 0;
+                    if ((st = qmri_coil_compress_dev(ctx, cnt, ncoil, S.dY, S.dM, d_psi, cc, &got, S.dYc, S.dMc, nullptr, nullptr)) != QMRI_OK) { bail(st); break; }
+                    if ((st = qmri_pnp_admm_mc_dev(ctx, cnt, nv, S.dMc, S.dYc, &pb->admm, nullptr, S.dX, nullptr)) != QMRI_OK) { bail(st); break; }
+                } else if ((st = qmri_pnp_admm_mc_dev(ctx, cnt, ncoil, S.dM, S.dY, &pb->admm, nullptr, S.dX, nullptr)) != QMRI_OK) { bail(st); break; }
             } else if ((st = qmri_pnp_admm_dev(ctx, cnt, S.dY, &pb->admm, nullptr, nullptr, S.dX, nullptr, nullptr)) != QMRI_OK) { bail(st); break; }
             if (maps) {
                 for (int i = 0; i < cnt && st == QMRI_OK; ++i)
@@ -1371,7 +1385,7 @@ static int recon_worker(int device, bool shared_device, int widx, int nworkers, 
     } while (0);
     (void)hipDeviceSynchronize();
     for (Set& S : set) {
-        void* dptr[] = { S.dY, S.dX, S.dM, S.dq, S.dp };
+        void* dptr[] = { S.dY, S.dX, S.dM, S.dYc, S.dMc, S.dq, S.dp };
         for (void* p : dptr) if (p) (void)hipFree(p);
         void* hptr[] = { S.hY, S.hX, S.hM, S.hq, S.hp };
         for (void* p : hptr) if (p) (void)hipHostFree(p);
@@ -1379,12 +1393,14 @@ static int recon_worker(int device, bool shared_device, int widx, int nworkers, 
         if (S.copied) (void)hipEventDestroy(S.copied);
     }
     if (cs) (void)hipStreamDestroy(cs);
+    if (d_psi) (void)hipFree(d_psi);
     qmri_destroy(ctx);
     return st;
 }
 
 static int recon_batch_impl(const char* name, int ndev, const int* devs, int nslices, const qmri_problem* prob, int ncoil, const void* maps, const void* Y,
-                            void* X_out, float* qmap_out, float* pd_out, char* errbuf, size_t errbuf_len) {
+                            void* X_out, float* qmap_out, float* pd_out, char* errbuf, size_t errbuf_len, const qmri_cc_params* cc = nullptr,
+                            const void* psi = nullptr) {
     auto report = [&](const std::string& s) { if (errbuf && errbuf_len) { snprintf(errbuf, errbuf_len, "%s", s.c_str()); } };
     if (ndev <= 0 || !devs || nslices <= 0 || !prob || !Y || !X_out || !prob->V || !prob->frame_ptr || !prob->kidx || !prob->net ||
         !prob->weights || (ncoil && (ncoil < 0 || ncoil > 1024 || !maps))) {
@@ -1399,7 +1415,7 @@ static int recon_batch_impl(const char* name, int ndev, const int* devs, int nsl
         for (int v = 0; v < ndev; ++v) shared = shared || (v != w && devs[v] == devs[w]);
         th.emplace_back([&, w, shared]() {
             status[w] = recon_worker(devs[w], shared, w, ndev, nslices, prob, (const char*)Y, (char*)X_out, qmap_out, pd_out, &errs[w], ncoil,
-                                     (const char*)maps);
+                                     (const char*)maps, cc, psi);
         });
     }
     for (auto& t : th) t.join();
@@ -1433,4 +1449,16 @@ extern "C" int qmri_debug_conv_stamps(qmri_ctx* ctx, unsigned long long* out, in
     QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     QMRI_HIP(ctx, hipMemcpy(out, ctx->net.d_stamps, (size_t)4096 * 11 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return QMRI_OK;
+}
+
+extern "C" int qmri_recon_batch_mc_cc(int ndev, const int* devs, int nslices, const qmri_problem* prob, int ncoil, const void* maps, const void* Y_mc,
+                                      void* X_out, float* qmap_out, float* pd_out, char* errbuf, size_t errbuf_len, const void* noise_cov,
+                                      const qmri_cc_params* cc) {
+    std::string msg = "invalid arguments (ncoil >= 1)";
+    const int code = ncoil < 1 ? QMRI_ERR_INVALID_ARG : cc_batch_param_error(ncoil, cc, &msg);
+    if (code != QMRI_OK) {
+        if (errbuf && errbuf_len) snprintf(errbuf, errbuf_len, "qmri_recon_batch_mc_cc: %s", msg.c_str());
+        return code;
+    }
+    return recon_batch_impl("qmri_recon_batch_mc_cc", ndev, devs, nslices, prob, ncoil, maps, Y_mc, X_out, qmap_out, pd_out, errbuf, errbuf_len, cc, noise_cov);
 }

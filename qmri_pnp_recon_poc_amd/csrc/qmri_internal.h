@@ -270,6 +270,27 @@ int mc_adjoint_batch_dev(qmri_ctx* ctx, int B, int ncoil, const double2* d_maps,
 int qmri_lsqr_mc_batch_dev(qmri_ctx* ctx, int B, int ncoil, const double2* d_maps, const double2* d_y, const double2* d_z, double r, double tol, int maxit,
                            double2* d_x, int32_t* iters_out, int32_t* flags_out);
 
+// coil compression of multi-coil stacks (cc_kernels.hip, api_cc.cpp): work buffers owned by the context, grown only when a call needs more
+struct CcWork {
+    double2 *part = nullptr, *R = nullptr, *X = nullptr, *L = nullptr, *U = nullptr, *W = nullptr;   // partials, R / K, scratch, chol(Psi), U_nv, W
+    size_t part_cap = 0, R_cap = 0, X_cap = 0, L_cap = 0, U_cap = 0, W_cap = 0;
+    double2* hK = nullptr; size_t hK_cap = 0;   // pinned: K to the host eigensolve, then U_nv back
+    int* hbad = nullptr;                        // pinned: Cholesky of Psi failed
+    bool lds_attr = false;                      // > 64 KB dynamic LDS allowed for the 128-coil covariance kernel
+    // staging of the host-array entry point and of Psi: y / maps in, y / maps out
+    double2 *psi = nullptr, *sy = nullptr, *sm = nullptr, *oy = nullptr, *om = nullptr;
+    size_t psi_cap = 0, sy_cap = 0, sm_cap = 0, oy_cap = 0, om_cap = 0;
+};
+void cc_free_work(CcWork& w);
+int cc_ensure_staging(qmri_ctx* ctx, size_t ny, size_t nm, size_t nyo, size_t nmo);
+int cc_compress_dev(qmri_ctx* ctx, int B, int ncoil, const double2* d_y, const double2* d_maps, const double2* d_psi, const qmri_cc_params& prm,
+                    int* nv_out, double2* d_yout, double2* d_mout, double2* d_Wout, double* eig_out);
+// host (api_cc.cpp): eigen-decomposition of the Hermitian n x n matrix whose upper triangle is A (column-major), lambda descending, the phase rule
+// applied (cyclic Jacobi); and the smallest nv whose leading eigenvalues hold `energy` of the sum
+int cc_eig_host(qmri_ctx* ctx, int n, const double2* A, double* lam, double2* U);
+int cc_choose_nv(int n, const double* lam, double energy);
+int cc_batch_param_error(int ncoil, const qmri_cc_params* p, std::string* msg);   // qmri_recon_batch_mc_cc's rules: QMRI_OK or the code + *msg
+
 // ---------------------------------------------------------------------------------------------------
 // context
 // ---------------------------------------------------------------------------------------------------
@@ -333,6 +354,7 @@ struct qmri_ctx {
     OpHost op;
     NetPlan net;
     DictHost dict;
+    CcWork cc;                          // coil compression (cc_kernels.hip)
     int prof_level = 0;
     qmri_profile prof{};
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};

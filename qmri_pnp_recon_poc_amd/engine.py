@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import AdmmParams, LrtvInfo, LrtvParams, NetDesc, Profile
+from ._lib import AdmmParams, CcParams, LrtvInfo, LrtvParams, NetDesc, Profile
 
 ARCH_UNETRES, ARCH_SEQ_CONV = 0, 1
 SOLVER_LSQR, SOLVER_DIRECT = 0, 1
@@ -281,6 +281,48 @@ class Engine:
         self._check(self.L.qmri_pnp_admm_mc_batch(self.h, S, int(slices_per_launch), nc, _vp(mb), _vp(yb), C.byref(p), _vp(x0b), _vp(x),
                                                   li.ctypes.data_as(C.POINTER(C.c_int32))))
         return np.stack([x[b * n:(b + 1) * n].reshape((self.N, self.M, self.s), order="F") for b in range(S)]), li.reshape(-1)[: S * iters].reshape(S, iters)
+
+    def coil_compress(self, y_mc, maps=None, noise_cov=None, nv=0, energy=0.99, shared=False):
+        """Coil compression of a stack (extension, no reference counterpart; include/qmri.h qmri_coil_compress): y_mc [S, m, ncoil], maps
+        [S, N, M, ncoil] or None, noise_cov [ncoil, ncoil] Hermitian positive definite or None (pre-whitening); nv > 0 keeps nv virtual coils,
+        nv = 0 takes the smallest nv holding `energy` of the eigenvalue sum (the largest over the slices); shared: one W for the whole stack.
+        Returns dict(y [S, m, nv], maps [S, N, M, nv] or None, W [S or 1, ncoil, nv], eig [S or 1, ncoil], nv)."""
+        y_mc = np.asarray(y_mc)
+        if y_mc.ndim != 3 or y_mc.shape[1] != self.m or y_mc.shape[0] < 1:
+            raise ValueError(f"y_mc must be [slices, {self.m}, ncoil]")
+        S, nc = y_mc.shape[0], y_mc.shape[2]
+        if maps is not None:
+            maps = np.asarray(maps)
+            if maps.shape != (S, self.N, self.M, nc):
+                raise ValueError(f"maps must be [{S}, {self.N}, {self.M}, {nc}]")
+        if noise_cov is not None:
+            noise_cov = np.asarray(noise_cov)
+            if noise_cov.shape != (nc, nc):
+                raise ValueError(f"noise_cov must be [{nc}, {nc}]")
+        if not (0 <= int(nv) <= nc):
+            raise ValueError(f"nv must satisfy 0 <= nv <= ncoil = {nc}")
+        yb = np.concatenate([_cbuf(y_mc[b]) for b in range(S)])
+        mb = np.concatenate([_cbuf(maps[b]) for b in range(S)]) if maps is not None else None
+        pb = _cbuf(noise_cov) if noise_cov is not None else None
+        p = CcParams(int(nv), float(energy), int(bool(shared)))
+        nmat = 1 if shared else S
+        plane = self.N * self.M
+        yo = np.empty(S * nc * self.m, np.complex128)
+        mo = np.empty(S * nc * plane, np.complex128) if maps is not None else None
+        W = np.empty(nmat * nc * nc, np.complex128)
+        eig = np.empty(nmat * nc, np.float64)
+        got = C.c_int(0)
+        self._check(self.L.qmri_coil_compress(self.h, S, nc, _vp(yb), _vp(mb), _vp(pb), C.byref(p), C.byref(got), _vp(yo), _vp(mo), _vp(W),
+                                              eig.ctypes.data_as(C.POINTER(C.c_double))))
+        k = got.value
+        m = self.m
+        out = {"nv": k, "eig": eig.reshape(nmat, nc),
+               "y": np.stack([yo[b * k * m:(b + 1) * k * m].reshape((m, k), order="F") for b in range(S)]),
+               "W": np.stack([W[j * nc * k:(j + 1) * nc * k].reshape((nc, k), order="F") for j in range(nmat)]),
+               "maps": None}
+        if maps is not None:
+            out["maps"] = np.stack([mo[b * k * plane:(b + 1) * k * plane].reshape((self.N, self.M, k), order="F") for b in range(S)])
+        return out
 
     def xupdate(self, y, z, r, tol=1e-4, maxit=100, x0=None, solver="lsqr"):
         """The x-update of PnP_ADMM.m:102 alone.  Returns (x, iters, flag)."""

@@ -15,6 +15,8 @@ function [X, qmap, pd] = qmri_recon_batch(Y, param, devs, slices_per_launch)
 %   param: the reference's fields iter, gamma, cg_tol, denoiser_type, noise_map (PnP_ADMM.m:62-76); param.F from qmri_make_F.
 %   param.coils (optional, multi-coil extension with no reference counterpart): N x M x ncoil x S coil maps, one set per slice; Y is then
 %   m x ncoil x S, column (:, j, k) = F.forward(param.coils(:, :, j, k) .* X0_k) + noise.
+%   param.coil_compress (optional, with param.coils): nv, or a struct with field nv -- every launch compresses its slices to nv virtual coils on
+%   the GPU first, one transform per slice (qmri_coil_compress); param.noise_cov (optional): ncoil x ncoil noise covariance, whitened first.
 if nargin < 3 || isempty(devs), devs = 0; end
 if nargin < 4 || isempty(slices_per_launch), slices_per_launch = 15; end
 if ~isfield(param.F, 'qmri'), error('qmri:F', 'param.F must be created by qmri_make_F'); end
@@ -22,15 +24,23 @@ p.gamma = param.gamma;  p.iter = param.iter;  p.cg_tol = param.cg_tol;
 p.multi_level = double(strcmp(param.denoiser_type, 'multi_level'));
 if p.multi_level, p.noise_std = param.noise_map(1); else, p.noise_std = 0.01; end
 g = param.F.qmri;
+tail = {};
 if isfield(param, 'coils') && ~isempty(param.coils)
     % multi-coil EXTENSION (no reference counterpart): param.coils N x M x ncoil x S (every slice its own maps), Y m x ncoil x S
     a = {'recon_batch_mc', complex(double(Y)), complex(double(param.coils))};
+    if isfield(param, 'coil_compress') && ~isempty(param.coil_compress)
+        cc = param.coil_compress;
+        if ~isstruct(cc), cc = struct('nv', double(cc)); end
+        psi = [];
+        if isfield(param, 'noise_cov') && ~isempty(param.noise_cov), psi = complex(double(param.noise_cov)); end
+        tail = {cc, psi};
+    end
 else
     a = {'recon_batch', complex(double(Y))};
 end
 if nargout > 1
-    [X, qmap, pd] = qmri_mex(a{:}, p, double(devs(:)), double(slices_per_launch), [g.N g.M g.s]);
+    [X, qmap, pd] = qmri_mex(a{:}, p, double(devs(:)), double(slices_per_launch), [g.N g.M g.s], tail{:});
 else
-    X = qmri_mex(a{:}, p, double(devs(:)), double(slices_per_launch), [g.N g.M g.s]);
+    X = qmri_mex(a{:}, p, double(devs(:)), double(slices_per_launch), [g.N g.M g.s], tail{:});
 end
 end

@@ -16,7 +16,8 @@
 //   * 'recon_batch' hands a whole slice stack to qmri_recon_batch: one worker (host thread + context) per entry of `devs`, slices_per_launch
 //     slices advanced together on each (k_conv6p, batched LSQR), x and the T1 / T2 / PD maps of every slice back.
 //   * 'recon_batch_mc' is the same for multi-coil stacks, every slice with its own coil maps (qmri_recon_batch_mc; an extension, no reference
-//     counterpart).
+//     counterpart); with a coil-compression argument every launch compresses its slices on the device first (qmri_recon_batch_mc_cc).
+//   * 'coil_compress' compresses a multi-coil stack to virtual coils (qmri_coil_compress; extension).
 // tests/cpp/mex_mock.cpp is a small stand-in for the MATLAB runtime's C API under which this file is compiled, LINKED against libqmri.so and
 // driven command by command on the GPU box (tests/test_gpu_mex.py); with MATLAB's own mex.h nothing here changes.
 #include "mex.h"
@@ -139,6 +140,28 @@ static qmri_admm_params admm_params(const mxArray* P, bool want_diag) {
     p.noise_std = scalar_field(P, "noise_std", 0.01);
     p.want_diag = want_diag ? 1 : 0;
     return p;
+}
+
+// coil compression options: a scalar nv, or a struct with the fields nv (default 0: choose by energy), energy (default 0.99), shared (default 0)
+static qmri_cc_params cc_params(const mxArray* a, const char* id) {
+    qmri_cc_params p;
+    p.nv = 0; p.energy = 0.99; p.shared = 0;
+    if (mxIsStruct(a)) {
+        const mxArray* f = mxGetField(a, 0, "nv");
+        if (f) p.nv = int_arg(f, 0, 1024, id, "cc.nv must be an integer in [0, ncoil]");
+        p.energy = scalar_field(a, "energy", 0.99);
+        f = mxGetField(a, 0, "shared");
+        if (f) p.shared = int_arg(f, 0, 1, id, "cc.shared must be 0 or 1");
+    } else {
+        p.nv = int_arg(a, 0, 1024, id, "cc must be a scalar nv or a struct with fields nv, energy, shared");
+    }
+    return p;
+}
+// a noise covariance argument: [] or a complex double ncoil x ncoil matrix
+static const void* noise_cov_arg(const mxArray* a, size_t ncoil, const char* id) {
+    if (mxIsEmpty(a)) return nullptr;
+    want(is_cdouble(a) && mxGetM(a) == ncoil && mxGetN(a) == ncoil, id, "noise_cov must be [] or complex double, ncoil x ncoil");
+    return mxGetComplexDoubles(a);
 }
 
 static void set_denoiser_from(const mxArray* w, const qmri_net_desc& d, int H, int W, int max_batch) {
@@ -309,7 +332,9 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         // param_struct, devs, slices_per_launch, [N M s]) -- every slice with its own coil maps (qmri_recon_batch_mc).
         const bool mc = c == "recon_batch_mc";
         const int o = mc ? 1 : 0;                                  // (arguments after Y move one place right)
-        if (mc) need(nrhs, 7, "[X, qmap, pd] = qmri_mex('recon_batch_mc', Y, maps, param, devs, slices_per_launch, [N M s])");
+        // Optional 8th / 9th arguments of 'recon_batch_mc': cc (scalar nv or struct, 'coil_compress') and noise_cov ([] or ncoil x ncoil): every launch
+        // compresses its slices on the device before the reconstruction (qmri_recon_batch_mc_cc).
+        if (mc) need(nrhs, 7, "[X, qmap, pd] = qmri_mex('recon_batch_mc', Y, maps, param, devs, slices_per_launch, [N M s] [, cc, noise_cov])");
         else need(nrhs, 6, "[X, qmap, pd] = qmri_mex('recon_batch', Y, param, devs, slices_per_launch, [N M s])");
         if (!g_op.V || !g_net.w) mexErrMsgIdAndTxt("qmri:recon_batch:state", "set_operator and set_denoiser (or load_onnx) must come first");
         size_t S = mxGetN(prhs[1]), ncoil = 0;
@@ -355,8 +380,18 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
             qm = mxCreateNumericArray(4, qd, mxSINGLE_CLASS, mxREAL);
             pd = mxCreateNumericArray(3, pdd, mxSINGLE_CLASS, mxCOMPLEX);
         }
+        const bool use_cc = mc && nrhs > 7 && !mxIsEmpty(prhs[7]);
+        qmri_cc_params ccp{};
+        const void* psi = nullptr;
+        if (use_cc) {
+            ccp = cc_params(prhs[7], "qmri:recon_batch_mc:cc");
+            if (nrhs > 8) psi = noise_cov_arg(prhs[8], ncoil, "qmri:recon_batch_mc:noise_cov");
+        }
         char err[1024] = "";
-        const int st = mc ? qmri_recon_batch_mc((int)devs.size(), devs.data(), (int)S, &pb, (int)ncoil, mxGetComplexDoubles(prhs[2]), mxGetComplexDoubles(prhs[1]),
+        const int st = use_cc ? qmri_recon_batch_mc_cc((int)devs.size(), devs.data(), (int)S, &pb, (int)ncoil, mxGetComplexDoubles(prhs[2]), mxGetComplexDoubles(prhs[1]),
+                                                       mxGetComplexDoubles(plhs[0]), qm ? (float*)mxGetData(qm) : nullptr, pd ? (float*)mxGetData(pd) : nullptr,
+                                                       err, sizeof err, psi, &ccp)
+                     : mc ? qmri_recon_batch_mc((int)devs.size(), devs.data(), (int)S, &pb, (int)ncoil, mxGetComplexDoubles(prhs[2]), mxGetComplexDoubles(prhs[1]),
                                                 mxGetComplexDoubles(plhs[0]), qm ? (float*)mxGetData(qm) : nullptr, pd ? (float*)mxGetData(pd) : nullptr, err, sizeof err)
                           : qmri_recon_batch((int)devs.size(), devs.data(), (int)S, &pb, mxGetComplexDoubles(prhs[1]), mxGetComplexDoubles(plhs[0]),
                                              qm ? (float*)mxGetData(qm) : nullptr, pd ? (float*)mxGetData(pd) : nullptr, err, sizeof err);
@@ -367,6 +402,45 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         }
         if (nlhs > 1) plhs[1] = qm ? qm : mxCreateNumericMatrix(0, 0, mxSINGLE_CLASS, mxREAL);
         if (nlhs > 2) plhs[2] = pd ? pd : mxCreateNumericMatrix(0, 0, mxSINGLE_CLASS, mxCOMPLEX); else if (pd) mxDestroyArray(pd);
+    } else if (c == "coil_compress") {               // [yc, mapsc, W, eig] = qmri_mex('coil_compress', Y(m x ncoil x S), maps, noise_cov, cc)
+        // multi-coil extension (no reference counterpart): maps [] or N x M x ncoil x S, noise_cov [] or ncoil x ncoil, cc a scalar nv or a struct
+        // (nv, energy, shared).  yc m x nv x S, mapsc N x M x nv x S (or []), W ncoil x nv x S (1 when shared), eig ncoil x S (1 when shared).
+        need(nrhs, 5, "[yc, mapsc, W, eig] = qmri_mex('coil_compress', Y, maps, noise_cov, cc)");
+        want(g_op.V != nullptr, "qmri:state", "no operator: call qmri_mex('set_operator', ...) (qmri_make_F) first");
+        const mwSize nd = mxGetNumberOfDimensions(prhs[1]);
+        const mwSize* yd = mxGetDimensions(prhs[1]);
+        const size_t m = operator_m(), ncoil = nd >= 2 ? yd[1] : 1, S = nd >= 3 ? yd[2] : 1, plane = (size_t)g_op.N * g_op.M;
+        want(nd <= 3 && is_cdouble(prhs[1]) && yd[0] == m && ncoil >= 1 && S >= 1, "qmri:coil_compress:size", "Y must be complex double, m x ncoil x S");
+        const bool has_maps = !mxIsEmpty(prhs[2]);
+        if (has_maps) {
+            const mwSize* cd = mxGetDimensions(prhs[2]);
+            want(is_cdouble(prhs[2]) && mxGetNumberOfDimensions(prhs[2]) >= 2 && cd[0] == (mwSize)g_op.N && cd[1] == (mwSize)g_op.M &&
+                 mxGetNumberOfElements(prhs[2]) == plane * ncoil * S, "qmri:coil_compress:maps", "maps must be [] or complex double, N x M x ncoil x S");
+        }
+        const void* psi = noise_cov_arg(prhs[3], ncoil, "qmri:coil_compress:noise_cov");
+        const qmri_cc_params p = cc_params(prhs[4], "qmri:coil_compress:cc");
+        const size_t nmat = p.shared ? 1 : S;
+        std::vector<double> yo(2 * S * ncoil * m), mo(has_maps ? 2 * S * ncoil * plane : 0), Wo(2 * nmat * ncoil * ncoil), eo(nmat * ncoil);
+        int nv = 0;
+        check(qmri_coil_compress(ctx(), (int)S, (int)ncoil, mxGetComplexDoubles(prhs[1]), has_maps ? mxGetComplexDoubles(prhs[2]) : nullptr, psi, &p, &nv,
+                                 yo.data(), has_maps ? mo.data() : nullptr, Wo.data(), eo.data()));
+        const mwSize yc[3] = {(mwSize)m, (mwSize)nv, (mwSize)S};
+        plhs[0] = mxCreateNumericArray(3, yc, mxDOUBLE_CLASS, mxCOMPLEX);
+        std::memcpy(mxGetComplexDoubles(plhs[0]), yo.data(), S * nv * m * 2 * sizeof(double));
+        if (nlhs > 1) {
+            const mwSize mc4[4] = {(mwSize)g_op.N, (mwSize)g_op.M, (mwSize)nv, (mwSize)S};
+            plhs[1] = has_maps ? mxCreateNumericArray(4, mc4, mxDOUBLE_CLASS, mxCOMPLEX) : mxCreateDoubleMatrix(0, 0, mxCOMPLEX);
+            if (has_maps) std::memcpy(mxGetComplexDoubles(plhs[1]), mo.data(), S * nv * plane * 2 * sizeof(double));
+        }
+        if (nlhs > 2) {
+            const mwSize wd[3] = {(mwSize)ncoil, (mwSize)nv, (mwSize)nmat};
+            plhs[2] = mxCreateNumericArray(3, wd, mxDOUBLE_CLASS, mxCOMPLEX);
+            std::memcpy(mxGetComplexDoubles(plhs[2]), Wo.data(), nmat * ncoil * nv * 2 * sizeof(double));
+        }
+        if (nlhs > 3) {
+            plhs[3] = mxCreateDoubleMatrix(ncoil, nmat, mxREAL);
+            std::memcpy(mxGetDoubles(plhs[3]), eo.data(), nmat * ncoil * sizeof(double));
+        }
     } else if (c == "lrtv") {                        // [x, info] = qmri_mex('lrtv', y, param_struct, [N M s])   (FISTA_deep, main_recon_tsmis_FFT.m:273-282)
         need(nrhs, 4, "[x, info] = qmri_mex('lrtv', y, param, [N M s])");
         const mxArray* P = prhs[2];
