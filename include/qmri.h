@@ -105,6 +105,30 @@ int qmri_xupdate_mc(qmri_ctx* ctx, const void* y_mc, const void* z, double r, do
 int qmri_xupdate(qmri_ctx* ctx, const void* y, const void* z, double r, double tol, int maxit, int solver,
                  void* x, int32_t* iters_out, int32_t* flag_out);
 
+/* ---- non-Cartesian trajectories (NUFFT operator) ------------------------------ */
+/* The exact spiral of setup_subsampling_spiralgrided.m:7-27 BEFORE it is rounded onto the grid: all S points of every frame, m = S * T, frame-major.
+ * Point j of frame f: omega = (pi r_j cos(theta_j + f delta), pi r_j sin(theta_j + f delta)) in radians per pixel, (omega1, omega2) interleaved.
+ * frame_ptr: T+1 entries; omega: cap pairs (2 * cap doubles).  Capacity rules and ctx == NULL as qmri_build_spiral. */
+int qmri_build_spiral_traj(qmri_ctx* ctx, int N, int S, int T, int32_t* frame_ptr, double* omega, int cap, int* m_out);
+/* A trajectory operator.  Sample i (frame t(i) by frame_ptr, frame-major as the ABI's y) lies at omega_i = (omega1, omega2) radians per pixel,
+ * omega1 along N (first index), omega2 along M; every omega finite and in [-pi, pi]:
+ *   y_i = (1 / sqrt(N M)) sum_{n1 < N, n2 < M} (sum_c V(t(i), c) x_c[n1, n2]) exp(-i (omega1 n1 + omega2 n2))
+ * and the adjoint is its exact Hermitian transpose.  On-grid points (omega = 2 pi k / N wrapped into [-pi, pi)) give qmri_forward of the mask of
+ * those k.  Computed by a 2x oversampled NUFFT with an "exponential of semicircle" kernel of width w (relative error about 10^(1-w); DESIGN.md
+ * section 14).  Replaces the context's operator (qmri_set_operator makes it gridded again).  N, M, s, T, max_batch as qmri_set_operator.  The
+ * arguments are checked before the context is used (ctx == NULL: QMRI_ERR_INVALID_ARG, the message of the first failing check in qmri_last_error(NULL)). */
+typedef struct {
+    int32_t width;           /* kernel width w in oversampled grid points, 2..16; 0 = default (12: error about 3e-11) */
+    int32_t reserved[7];     /* must be zero */
+} qmri_nufft_params;
+int qmri_set_operator_nufft(qmri_ctx* ctx, int N, int M, int s, int T, const double* V, const int32_t* frame_ptr, const double* omega,
+                            int max_batch, const qmri_nufft_params* p);
+/* On a trajectory operator these work unchanged: qmri_forward / _adjoint (and _f32, _dev), qmri_operator_m, qmri_set_coils, qmri_forward_mc /
+ * _adjoint_mc, qmri_xupdate_mc(_batch), qmri_pnp_admm_mc(_batch, _dev), qmri_coil_compress*, and qmri_xupdate / qmri_pnp_admm (one slice, LSQR,
+ * no diagnostics) as the image-domain LSQR with one unit coil -- bit for bit the qmri_*_mc call with that coil.  Everything else that needs the
+ * operator (the DIRECT solver, the per-iteration diagnostics, qmri_pnp_admm_dev with several slices, qmri_pnp_admm_batch with several slices per
+ * launch, qmri_lrtv) returns QMRI_ERR_UNSUPPORTED. */
+
 /* ---- denoiser plugin: param.net, main_recon_tsmis_FFT.m:138-171 ----------------------------------- */
 enum { QMRI_ARCH_UNETRES = 0, QMRI_ARCH_SEQ_CONV = 1 };
 typedef struct {

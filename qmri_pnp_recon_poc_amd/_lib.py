@@ -17,7 +17,7 @@ CSRC = os.path.join(_PKG, "csrc")
 # every symbol include/qmri.h declares (checked at load time and by tests/test_abi.py)
 SYMBOLS = [
     "qmri_abi_version", "qmri_create", "qmri_destroy", "qmri_last_error", "qmri_set_stream", "qmri_synchronize",
-    "qmri_build_spiral", "qmri_build_epi", "qmri_set_operator", "qmri_operator_m", "qmri_forward", "qmri_adjoint",
+    "qmri_build_spiral", "qmri_build_epi", "qmri_build_spiral_traj", "qmri_set_operator", "qmri_set_operator_nufft", "qmri_operator_m", "qmri_forward", "qmri_adjoint",
     "qmri_forward_f32", "qmri_adjoint_f32", "qmri_forward_dev", "qmri_adjoint_dev", "qmri_set_coils", "qmri_forward_mc", "qmri_adjoint_mc", "qmri_xupdate_mc", "qmri_pnp_admm_mc", "qmri_xupdate_mc_batch", "qmri_pnp_admm_mc_batch", "qmri_pnp_admm_mc_dev", "qmri_xupdate", "qmri_net_nparams", "qmri_set_denoiser", "qmri_denoise",
     "qmri_net_forward_dev", "qmri_denoiser_scheme", "qmri_pnp_admm", "qmri_pnp_admm_dev", "qmri_pnp_admm_batch", "qmri_set_dictionary", "qmri_dict_match",
     "qmri_dict_match_dev", "qmri_dict_match_xfit", "qmri_dict_match_xfit_dev", "qmri_recon_batch", "qmri_recon_batch_mc",
@@ -48,6 +48,10 @@ class Problem(C.Structure):
 
 class CcParams(C.Structure):
     _fields_ = [("nv", C.c_int32), ("energy", C.c_double), ("shared", C.c_int32)]
+
+
+class NufftParams(C.Structure):
+    _fields_ = [("width", C.c_int32), ("reserved", C.c_int32 * 7)]
 
 
 class LrtvParams(C.Structure):
@@ -114,6 +118,8 @@ def lib() -> C.CDLL:
     L.qmri_build_spiral.argtypes = [vp, i, i, i, ip, ip, i, C.POINTER(i)]
     L.qmri_build_epi.argtypes = [vp, i, i, C.c_double, i, ip, ip, i, C.POINTER(i)]
     L.qmri_set_operator.argtypes = [vp, i, i, i, i, dp, ip, ip, i]
+    L.qmri_build_spiral_traj.argtypes = [vp, i, i, i, ip, dp, i, C.POINTER(i)]
+    L.qmri_set_operator_nufft.argtypes = [vp, i, i, i, i, dp, ip, dp, i, C.POINTER(NufftParams)]
     L.qmri_operator_m.argtypes = [vp, C.POINTER(i)]
     L.qmri_forward.argtypes = [vp, vp, i, vp]
     L.qmri_adjoint.argtypes = [vp, vp, vp]

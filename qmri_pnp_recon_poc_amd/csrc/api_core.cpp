@@ -27,7 +27,7 @@ const KnobDef g_knob_defs[K_COUNT] = {
     {"res_stamps", 0}, {"conv_stamps", 0}, {"conv_stamp_launch", -1}, {"lsqr_stamps", 0},
     {"conv_mt2", 1024}, {"conv_occ", 2},
     {"fuse_ew", 1}, {"lsqr_persist", 1}, {"lsqr_fold", 1}, {"dictw_lsp", 2}, {"verbose", 0},
-    {"pack_gpu", 1},
+    {"pack_gpu", 1}, {"nufft_seg", NU_SEG},
 };
 std::atomic<int> g_knob_val[K_COUNT];
 std::once_flag g_knob_once;
@@ -142,6 +142,7 @@ void qmri_free_operator(qmri_ctx* ctx) {
     if (o.h_ring) (void)hipHostFree(o.h_ring);
     free_dev(ctx->d_ks_gran); ctx->d_ks_gran = nullptr; ctx->ks_persist_cap = -1;    // (sized for this operator's work units)
     mc_free_work(o.mc);
+    nufft_free(o.nu);
     o = OpHost();
 }
 
@@ -181,14 +182,9 @@ extern "C" int qmri_synchronize(qmri_ctx* ctx) {
 // ---------------------------------------------------------------------------------------------------
 // mask builders (host, integer index math)
 // ---------------------------------------------------------------------------------------------------
-extern "C" int qmri_build_spiral(qmri_ctx* ctx, int N, int S, int T, int32_t* frame_ptr, int32_t* kidx, int cap, int* m_out) {
-    QMRI_CHECK_ARG(ctx, N > 0 && S > 1 && T > 0 && frame_ptr && (kidx || cap == 0) && m_out, "qmri_build_spiral arguments");
-    // setup_subsampling_spiralgrided.m:7-34.  8-turn exponential spiral sampled at S points, rotated 7.5 deg per
-    // frame, rounded onto the N x N grid (MATLAB round = half away from zero), clamped, fftshift-ed; the sample
-    // order inside a frame is find()'s ascending column-major order.
+void spiral_points(int S, std::vector<double>& theta, std::vector<double>& rad) {
     const double pi = 3.14159265358979323846;
-    const double delta = pi / 180.0 * 7.5;
-    std::vector<double> theta(S), rad(S);
+    theta.assign(S, 0.0); rad.assign(S, 0.0);
     double lo = HUGE_VAL, hi = -HUGE_VAL;
     for (int j = 0; j < S; ++j) {
         const double t = (j == S - 1) ? 2.0 * pi : (double)j * (2.0 * pi) / (double)(S - 1);   // linspace(0,2*pi,S)
@@ -198,6 +194,16 @@ extern "C" int qmri_build_spiral(qmri_ctx* ctx, int N, int S, int T, int32_t* fr
         hi = std::max(hi, rad[j]);
     }
     for (double& r : rad) r = (r - lo) / (hi - lo);
+}
+
+extern "C" int qmri_build_spiral(qmri_ctx* ctx, int N, int S, int T, int32_t* frame_ptr, int32_t* kidx, int cap, int* m_out) {
+    QMRI_CHECK_ARG(ctx, N > 0 && S > 1 && T > 0 && frame_ptr && (kidx || cap == 0) && m_out, "qmri_build_spiral arguments");
+    // setup_subsampling_spiralgrided.m:7-34.  8-turn exponential spiral sampled at S points, rotated 7.5 deg per
+    // frame, rounded onto the N x N grid (MATLAB round = half away from zero), clamped, fftshift-ed; the sample
+    // order inside a frame is find()'s ascending column-major order.
+    const double delta = SPIRAL_DELTA;
+    std::vector<double> theta, rad;
+    spiral_points(S, theta, rad);
     std::vector<uint8_t> grid((size_t)N * N);
     const int half = N / 2;
     long m = 0;
@@ -518,6 +524,7 @@ extern "C" int qmri_operator_m(const qmri_ctx* ctx, int* m_out) {
 extern "C" int qmri_forward_dev(qmri_ctx* ctx, const void* d_x, void* d_y, int batch) {
     REQUIRE_OP(ctx);
     QMRI_CHECK_ARG(ctx, d_x && d_y && batch >= 1 && batch <= ctx->op.maxB, "qmri_forward_dev arguments / batch > max_batch");
+    if (ctx->op.kind == OP_NUFFT) return nufft_launch_fwd(ctx, batch, (const double2*)d_x, (double2*)d_y);
     return dc_launch_fwd(ctx, qmri_opdev(ctx), ctx->op.ls, DC_PLAIN, batch, (const double2*)d_x, ctx->op.d_tmp,
                          (double2*)d_y, nullptr);
 }
@@ -525,6 +532,7 @@ extern "C" int qmri_forward_dev(qmri_ctx* ctx, const void* d_x, void* d_y, int b
 extern "C" int qmri_adjoint_dev(qmri_ctx* ctx, const void* d_y, void* d_x, int batch) {
     REQUIRE_OP(ctx);
     QMRI_CHECK_ARG(ctx, d_x && d_y && batch >= 1 && batch <= ctx->op.maxB, "qmri_adjoint_dev arguments / batch > max_batch");
+    if (ctx->op.kind == OP_NUFFT) return nufft_launch_adj(ctx, batch, (const double2*)d_y, (double2*)d_x);
     return dc_launch_adj(ctx, qmri_opdev(ctx), batch, (const double2*)d_y, ctx->op.d_tmp, (double2*)d_x);
 }
 
@@ -595,7 +603,8 @@ extern "C" int qmri_forward_mc(qmri_ctx* ctx, const void* x, int x_is_complex, v
     for (int j0 = 0; j0 < o.ncoil; j0 += o.maxB) {
         const int cnt = std::min(o.maxB, o.ncoil - j0);
         QMRI_TRY(ew_launch_coil_mul(ctx, n, plane, cnt, o.d_xa, o.d_coils + (size_t)j0 * plane, o.d_x));          // (o.d_x: [max_batch][n], free outside a reconstruction)
-        QMRI_TRY(dc_launch_fwd(ctx, qmri_opdev(ctx), o.ls, DC_PLAIN, cnt, o.d_x, o.d_tmp, o.d_ya, nullptr));
+        if (o.kind == OP_NUFFT) QMRI_TRY(nufft_launch_fwd(ctx, cnt, o.d_x, o.d_ya));
+        else QMRI_TRY(dc_launch_fwd(ctx, qmri_opdev(ctx), o.ls, DC_PLAIN, cnt, o.d_x, o.d_tmp, o.d_ya, nullptr));
         QMRI_HIP(ctx, hipMemcpyAsync((double2*)y + (size_t)j0 * o.m, o.d_ya, (size_t)cnt * o.m * sizeof(double2), hipMemcpyDeviceToHost, ctx->stream));
     }
     QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -611,7 +620,8 @@ extern "C" int qmri_adjoint_mc(qmri_ctx* ctx, const void* y, void* x) {
     for (int j0 = 0; j0 < o.ncoil; j0 += o.maxB) {
         const int cnt = std::min(o.maxB, o.ncoil - j0);
         QMRI_HIP(ctx, hipMemcpyAsync(o.d_ya, (const double2*)y + (size_t)j0 * o.m, (size_t)cnt * o.m * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
-        QMRI_TRY(dc_launch_adj(ctx, qmri_opdev(ctx), cnt, o.d_ya, o.d_tmp, o.d_x));
+        if (o.kind == OP_NUFFT) QMRI_TRY(nufft_launch_adj(ctx, cnt, o.d_ya, o.d_x));
+        else QMRI_TRY(dc_launch_adj(ctx, qmri_opdev(ctx), cnt, o.d_ya, o.d_tmp, o.d_x));
         QMRI_TRY(ew_launch_coil_sum(ctx, n, plane, cnt, o.d_x, o.d_coils + (size_t)j0 * plane, o.d_xa, j0 > 0));
     }
     QMRI_HIP(ctx, hipMemcpyAsync(x, o.d_xa, n * sizeof(double2), hipMemcpyDeviceToHost, ctx->stream));
@@ -711,6 +721,7 @@ int qmri_prepare_direct(qmri_ctx* ctx, double r) {
 int qmri_lsqr_run(qmri_ctx* ctx, int B, const double2* d_z, double r, double tol, int maxit, double2* d_x,
                   int32_t* iters_out, int32_t* flag_out, double* pdiag, LsqrState* hslot, bool* deferred, const LsqrFuse* fuse) {
     OpHost& o = ctx->op;
+    QMRI_TRY(nufft_check_gridded(ctx, "the k-space LSQR", "the image-domain LSQR of the qmri_*_mc calls applies (internal)"));
     const OpDev op = qmri_opdev(ctx);
     KsDev ks = o.ks;
     ks.sr = std::sqrt(r); ks.tol = tol; ks.maxit = maxit; ks.ii = 0; ks.pdiag = pdiag;
@@ -821,6 +832,25 @@ extern "C" int qmri_xupdate(qmri_ctx* ctx, const void* y, const void* z, double 
     REQUIRE_OP(ctx);
     QMRI_CHECK_ARG(ctx, y && z && x && r > 0 && maxit >= 0, "qmri_xupdate arguments");
     OpHost& o = ctx->op;
+    if (o.kind == OP_NUFFT) {
+        // a trajectory: A^H A is not block-diagonal in k-space, so the k-space LSQR does not apply -- the image-domain LSQR with one unit coil,
+        // staged as qmri_xupdate_mc stages it (the same bits as that call with the unit map)
+        if (solver != QMRI_SOLVER_LSQR) {
+            qmri_set_error(ctx, "the DIRECT solver is not available on a trajectory operator (qmri_set_operator_nufft): its closed form needs a gridded "
+                                "mask; use QMRI_SOLVER_LSQR");
+            return QMRI_ERR_UNSUPPORTED;
+        }
+        const size_t n = (size_t)o.N * o.M * o.s;
+        QMRI_TRY(mc_ensure_staging(ctx, 1, 1));
+        McWork& w = o.mc;
+        QMRI_HIP(ctx, hipMemcpyAsync(w.sy, y, (size_t)o.m * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
+        QMRI_HIP(ctx, hipMemcpyAsync(w.sz, z, n * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
+        QMRI_HIP(ctx, hipMemcpyAsync(w.sx, x, n * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
+        QMRI_TRY(qmri_lsqr_mc_batch_dev(ctx, 1, 1, o.nu.d_ones, w.sy, w.sz, r, tol, maxit, w.sx, iters_out, flag_out));
+        QMRI_HIP(ctx, hipMemcpyAsync(x, w.sx, n * sizeof(double2), hipMemcpyDeviceToHost, ctx->stream));
+        QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return QMRI_OK;
+    }
     const OpDev op = qmri_opdev(ctx);
     const size_t n = (size_t)o.N * o.M * o.s;
     QMRI_HIP(ctx, hipMemcpyAsync(o.d_ya, y, (size_t)o.m * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));

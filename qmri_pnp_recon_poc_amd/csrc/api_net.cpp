@@ -731,9 +731,48 @@ extern "C" int qmri_pnp_admm_dev(qmri_ctx* ctx, int nslices, const void* d_y, co
     return st;
 }
 
+static int mc_admm_group(qmri_ctx* ctx, int B, int ncoil, const double2* d_maps, const double2* d_y, const qmri_admm_params* prm, const double2* d_x0,
+                         double2* d_x, int32_t* li_out, int li_stride);
+static int mc_admm_check(qmri_ctx* ctx, const qmri_admm_params* prm);
+
+// A trajectory operator (qmri_set_operator_nufft): one slice through the multi-coil loop with one unit coil -- the k-space LSQR and the fused
+// launches around it need a gridded mask.  The same bits as qmri_pnp_admm_mc with that coil.
+static int pnp_admm_nufft(qmri_ctx* ctx, int nslices, const void* d_y, const qmri_admm_params* prm, const void* d_x0, void* d_x_out,
+                          double* diag_out, int32_t* lsqr_iters_out) {
+    if (nslices != 1) {
+        qmri_set_error(ctx, "PnP-ADMM of %d slices in one call is not available on a trajectory operator (qmri_set_operator_nufft): reconstruct them "
+                            "one at a time, or as a stack with qmri_pnp_admm_mc_batch and one unit coil per slice", nslices);
+        return QMRI_ERR_UNSUPPORTED;
+    }
+    if (prm && prm->solver != QMRI_SOLVER_LSQR) {
+        qmri_set_error(ctx, "the DIRECT solver is not available on a trajectory operator (qmri_set_operator_nufft): its closed form needs a gridded "
+                            "mask; use QMRI_SOLVER_LSQR");
+        return QMRI_ERR_UNSUPPORTED;
+    }
+    if (prm && prm->want_diag && diag_out) {
+        qmri_set_error(ctx, "the per-iteration diagnostics are not available on a trajectory operator (qmri_set_operator_nufft): set want_diag = 0 "
+                            "and evaluate the result with qmri_forward");
+        return QMRI_ERR_UNSUPPORTED;
+    }
+    QMRI_TRY(mc_admm_check(ctx, prm));
+    QMRI_CHECK_ARG(ctx, d_y && d_x_out && d_x_out != d_x0, "y / x_out must not be NULL, x_out must not alias x0");
+    // staged as qmri_pnp_admm_mc stages it (the caller's y may be o.d_ya, which the multi-coil transforms use as their scratch)
+    OpHost& o = ctx->op;
+    const size_t n = (size_t)o.N * o.M * o.s;
+    QMRI_TRY(mc_ensure_staging(ctx, 1, 1));
+    McWork& w = o.mc;
+    QMRI_HIP(ctx, hipMemcpyAsync(w.sy, d_y, (size_t)o.m * sizeof(double2), hipMemcpyDeviceToDevice, ctx->stream));
+    if (d_x0) QMRI_HIP(ctx, hipMemcpyAsync(w.sz, d_x0, n * sizeof(double2), hipMemcpyDeviceToDevice, ctx->stream));
+    QMRI_TRY(mc_admm_group(ctx, 1, 1, o.nu.d_ones, w.sy, prm, d_x0 ? w.sz : nullptr, w.sx, lsqr_iters_out, prm->iters));
+    QMRI_HIP(ctx, hipMemcpyAsync(d_x_out, w.sx, n * sizeof(double2), hipMemcpyDeviceToDevice, ctx->stream));
+    QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return QMRI_OK;
+}
+
 static int pnp_admm_dev_impl(qmri_ctx* ctx, int nslices, const void* d_y, const qmri_admm_params* prm, const void* d_x0,
                              const void* d_gt, void* d_x_out, double* diag_out, int32_t* lsqr_iters_out) {
     QMRI_HIP(ctx, hipSetDevice(ctx->device));
+    if (ctx->op.ready && ctx->op.kind == OP_NUFFT) return pnp_admm_nufft(ctx, nslices, d_y, prm, d_x0, d_x_out, diag_out, lsqr_iters_out);
     OpHost& o = ctx->op;
     NetPlan& net = ctx->net;
     if (!o.ready) { qmri_set_error(ctx, "operator not set: call qmri_set_operator first"); return QMRI_ERR_STATE; }
@@ -1097,6 +1136,9 @@ extern "C" int qmri_pnp_admm_batch(qmri_ctx* ctx, int nslices, int slices_per_la
     if (!o.ready) { qmri_set_error(ctx, "operator not set: call qmri_set_operator first"); return QMRI_ERR_STATE; }
     if (!ctx->net.ready) { qmri_set_error(ctx, "denoiser not set: call qmri_set_denoiser first"); return QMRI_ERR_STATE; }
     QMRI_CHECK_ARG(ctx, y && p && x_out && nslices >= 1 && slices_per_launch >= 1, "y / params / x_out must not be NULL, nslices and slices_per_launch >= 1");
+    if (std::min(slices_per_launch, nslices) > 1)
+        QMRI_TRY(nufft_check_gridded(ctx, "qmri_pnp_admm_batch with more than one slice per launch",
+                                     "use slices_per_launch = 1, or qmri_pnp_admm_mc_batch with one unit coil per slice"));
     const int spl = std::min(slices_per_launch, nslices);
     QMRI_CHECK_ARG(ctx, spl <= o.maxB && spl <= ctx->net.maxB, "slices_per_launch exceeds max_batch of the operator or the denoiser");
     const size_t n = (size_t)o.N * o.M * o.s, m = (size_t)o.m, it = (size_t)std::max(p->iters, 0);

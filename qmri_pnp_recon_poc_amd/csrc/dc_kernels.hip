@@ -467,10 +467,15 @@ bool dc_size_supported(int n) { return qfft::side_supported(n); }
 
 int dc_launch_fwd(qmri_ctx* ctx, const OpDev& op, const LsqrDev& ls, int mode, int B, const double2* src, double2* tmp,
                   double2* y_out, double* pdiag) {
+    if (mode != DC_SPECTRUM && mode != DC_FWD_H_ONLY && !op.kptr) {
+        qmri_set_error(ctx, "dc_launch_fwd: the operator has no gridded mask (a trajectory operator reached a gridded path; internal)");
+        return QMRI_ERR_UNSUPPORTED;
+    }
     return launch_fwd(ctx, op, ls, mode, B, src, tmp, y_out, pdiag, nullptr, 0.0);
 }
 
 int dc_launch_adj(qmri_ctx* ctx, const OpDev& op, int B, const double2* y_in, double2* tmp, double2* dst) {
+    if (!op.kptr) { qmri_set_error(ctx, "dc_launch_adj: the operator has no gridded mask (a trajectory operator reached a gridded path; internal)"); return QMRI_ERR_UNSUPPORTED; }
     return launch_adj(ctx, op, B, y_in, tmp, dst, false);
 }
 
@@ -504,6 +509,7 @@ int dc_launch_dual_fwd_h(qmri_ctx* ctx, const OpDev& op, int B, const DualArgs& 
 
 int dc_launch_direct(qmri_ctx* ctx, const OpDev& op, int B, const double2* z, const double2* chat, double r,
                      double2* tmp, double2* x_out) {
+    if (!op.kslot) { qmri_set_error(ctx, "dc_launch_direct: the operator has no gridded mask (a trajectory operator reached a gridded path; internal)"); return QMRI_ERR_UNSUPPORTED; }
     LsqrDev ls{};
     // tmp holds the h-pass output, then (in place, row by row) the conjugate-domain w-pass output of k_fwd_w
     QMRI_TRY(launch_fwd(ctx, op, ls, DC_DIRECT, B, z, tmp, tmp, nullptr, chat, r));
@@ -511,6 +517,7 @@ int dc_launch_direct(qmri_ctx* ctx, const OpDev& op, int B, const double2* z, co
 }
 
 int dc_launch_sort_y(qmri_ctx* ctx, const OpDev& op, const LsqrDev& ls, int B, const double2* y) {
+    if (!op.perm) { qmri_set_error(ctx, "dc_launch_sort_y: the operator has no gridded mask (a trajectory operator reached a gridded path; internal)"); return QMRI_ERR_UNSUPPORTED; }
     k_sort_y<<<dim3(DC_SORT_BLOCKS, B), dim3(NT), 0, ctx->stream>>>(op, ls, y);
     k_sort_y_sum<<<dim3(B), dim3(64), 0, ctx->stream>>>(ls);
     QMRI_HIP(ctx, hipGetLastError());

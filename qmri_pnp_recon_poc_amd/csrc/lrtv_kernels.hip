@@ -336,6 +336,7 @@ extern "C" int qmri_lrtv(qmri_ctx* ctx, const void* y, const qmri_lrtv_params* p
     QMRI_HIP(ctx, hipSetDevice(ctx->device));
     OpHost& o = ctx->op;
     if (!o.ready) { qmri_set_error(ctx, "operator not set: call qmri_set_operator first"); return QMRI_ERR_STATE; }
+    QMRI_TRY(nufft_check_gridded(ctx, "qmri_lrtv", "the LRTV option is implemented for gridded masks only; use qmri_pnp_admm"));
     QMRI_CHECK_ARG(ctx, y && prm && x_out, "qmri_lrtv: y / params / x_out must not be NULL");
     QMRI_CHECK_ARG(ctx, prm->K >= 0.0 && prm->iters >= 1 && prm->tol > 0.0, "qmri_lrtv: K >= 0, iters >= 1, tol > 0");
     const int N = o.N, R = 2 * o.N, C = o.M * o.s;

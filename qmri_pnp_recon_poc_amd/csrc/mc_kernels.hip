@@ -281,7 +281,8 @@ int mc_adjoint_chunks(qmri_ctx* ctx, int B, int ncoil, const double2* maps, cons
     const size_t n = (size_t)o.N * o.M * o.s, plane = (size_t)o.N * o.M;
     for (int g0 = 0; g0 < B * ncoil; g0 += o.maxB) {
         const int cnt = std::min(o.maxB, B * ncoil - g0), nb = (g0 + cnt - 1) / ncoil - g0 / ncoil + 1;
-        QMRI_TRY(dc_launch_adj(ctx, qmri_opdev(ctx), cnt, ut + (size_t)g0 * o.m, o.d_tmp, w.scr));
+        if (o.kind == OP_NUFFT) QMRI_TRY(nufft_launch_adj(ctx, cnt, ut + (size_t)g0 * o.m, w.scr));
+        else QMRI_TRY(dc_launch_adj(ctx, qmri_opdev(ctx), cnt, ut + (size_t)g0 * o.m, o.d_tmp, w.scr));
         k_mcl_coil_sum<<<dim3(blocks_of(n), nb), dim3(NT), 0, ctx->stream>>>(n, plane, ncoil, g0, cnt, w.scr, maps, st, t);
         QMRI_HIP(ctx, hipGetLastError());
     }
@@ -296,7 +297,8 @@ int mc_forward_chunks(qmri_ctx* ctx, int mode, int B, int ncoil, const double2* 
         const int cnt = std::min(o.maxB, B * ncoil - g0);
         k_mcl_coil_mul<<<dim3(blocks_of(n), cnt), dim3(NT), 0, ctx->stream>>>(n, plane, ncoil, g0, x, maps, st, w.scr);
         QMRI_HIP(ctx, hipGetLastError());
-        QMRI_TRY(dc_launch_fwd(ctx, qmri_opdev(ctx), o.ls, DC_PLAIN, cnt, w.scr, o.d_tmp, o.d_ya, nullptr));
+        if (o.kind == OP_NUFFT) QMRI_TRY(nufft_launch_fwd(ctx, cnt, w.scr, o.d_ya));
+        else QMRI_TRY(dc_launch_fwd(ctx, qmri_opdev(ctx), o.ls, DC_PLAIN, cnt, w.scr, o.d_tmp, o.d_ya, nullptr));
         k_mcl_ulin<<<dim3(PC, cnt), dim3(NT), 0, ctx->stream>>>(mode, (size_t)o.m, ncoil, g0, o.d_ya, y, st, w.ut, p.pu, p.py);
         QMRI_HIP(ctx, hipGetLastError());
     }

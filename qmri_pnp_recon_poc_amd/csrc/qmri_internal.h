@@ -63,6 +63,7 @@ enum QmriKnob {
     K_DICTW_LSP,
     K_VERBOSE,            // calibration / guard decisions on stderr
     K_PACK_GPU,           // qmri_set_denoiser: weights split and ordered on the device (1, default) or on the host (0: the round-1 packers, same bits)
+    K_NUFFT_SEG,          // qmri_set_operator_nufft: samples per spreading segment (default NU_SEG = 512, at least 32); results change only in rounding
     K_COUNT
 };
 int qmri_knob(QmriKnob k);
@@ -292,9 +293,55 @@ int cc_choose_nv(int n, const double* lam, double energy);
 int cc_batch_param_error(int ncoil, const qmri_cc_params* p, std::string* msg);   // qmri_recon_batch_mc_cc's rules: QMRI_OK or the code + *msg
 
 // ---------------------------------------------------------------------------------------------------
+// trajectory (NUFFT) operator (nufft_kernels.hip, api_nufft.cpp).  Planned once on the host per qmri_set_operator_nufft:
+// samples sorted by the 16 x 16 tile of the 2N x 2M oversampled grid that holds their position ("bins"), and for the output-driven spreading the
+// list of samples each tile's kernel windows reach, cut into segments of <= NU_SEG samples (knob nufft_seg).
+// ---------------------------------------------------------------------------------------------------
+constexpr int NU_TB = 16;        // tile side (oversampled grid points) of the spreading; 2N and 2M are multiples of it for every supported side
+constexpr int NU_SEG = 512;      // samples per spreading segment by default (a heavier tile is split; its partial tiles are summed in segment order)
+constexpr int NU_WMAX = 16;      // widest kernel
+struct NuSeg { int32_t tile, b, e, slot; };      // tile index (t1 * ntile2 + t2), list range, partial slot (-1: the segment writes the grid itself)
+struct NuRed { int32_t tile, slot0, nslot, pad; };
+struct NufftDev {
+    int N, M, s, T, m, w;
+    double beta, hw;                             // kernel exp(beta (sqrt(1 - (d / hw)^2) - 1)), hw = w / 2
+    int ntile2, nseg, nred, nslot;
+    const double* Vt;                            // [T][s]
+    const double2* u;                            // [m] sorted: oversampled grid coordinates (omega1 N / pi, omega2 M / pi)
+    const double2* ph;                           // [m] sorted: exp(-i (omega1 N / 2 + omega2 M / 2))
+    const int32_t* t;                            // [m] sorted: frame
+    const int32_t* perm;                         // [m] sorted position -> ABI index
+    const int32_t* list;                         // spreading lists of the segments (sorted positions)
+    const NuSeg* seg;                            // [nseg]
+    const NuRed* red;                            // [nred]
+    const double* dp1; const double* dp2;        // [N], [M] deapodisation 1 / Phi at n - N/2
+    const double2* r1; const double2* r2;        // [N], [M] exp(-i pi (n - N/2) / N): the half-bin ramps
+};
+struct NufftHost {
+    double* d_u = nullptr; double* d_ph = nullptr; int32_t* d_t = nullptr; int32_t* d_perm = nullptr; int32_t* d_list = nullptr;
+    NuSeg* d_seg = nullptr; NuRed* d_red = nullptr; double* d_dp = nullptr; double2* d_r = nullptr;
+    double2* d_g = nullptr; double2* d_grid = nullptr; double2* d_part = nullptr;   // [4 maxB][n] x2, [maxB][nslot][s][256]
+    double2* d_ones = nullptr;                   // [N*M] the unit coil of qmri_xupdate / qmri_pnp_admm on a trajectory
+    int w = 0, nseg = 0, nred = 0, nslot = 0;
+    double beta = 0.0;
+};
+// the exponential spiral of setup_subsampling_spiralgrided.m:7-27 before rounding (shared by qmri_build_spiral and qmri_build_spiral_traj): S angles
+// theta_j and radii r_j normalised to [0, 1]; frame f is rotated by f * SPIRAL_DELTA
+void spiral_points(int S, std::vector<double>& theta, std::vector<double>& rad);
+constexpr double SPIRAL_DELTA = 3.14159265358979323846 / 180.0 * 7.5;
+int nufft_launch_fwd(qmri_ctx* ctx, int B, const double2* x, double2* y);    // x [B][n] -> y [B][m] (ABI order)
+int nufft_launch_adj(qmri_ctx* ctx, int B, const double2* y, double2* x);    // y [B][m] -> x [B][n]
+int nufft_check_gridded(qmri_ctx* ctx, const char* what, const char* instead);   // QMRI_ERR_UNSUPPORTED on a trajectory operator, else QMRI_OK
+void nufft_free(NufftHost& h);
+bool nufft_kernel_ok(int w);
+
+// ---------------------------------------------------------------------------------------------------
 // context
 // ---------------------------------------------------------------------------------------------------
+enum { OP_GRIDDED = 0, OP_NUFFT = 1 };
 struct OpHost {
+    int kind = OP_GRIDDED;              // OP_NUFFT: qmri_set_operator_nufft (nu below; the k-space tables are not allocated)
+    NufftHost nu;
     bool ready = false;
     int N = 0, M = 0, s = 0, T = 0, m = 0, maxB = 0, nsampled = 0;
     double* d_Vt = nullptr; KEntry* d_ent = nullptr; int32_t* d_perm = nullptr; int32_t* d_kptr = nullptr;

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import AdmmParams, CcParams, LrtvInfo, LrtvParams, NetDesc, Profile
+from ._lib import AdmmParams, CcParams, LrtvInfo, LrtvParams, NetDesc, NufftParams, Profile
 
 ARCH_UNETRES, ARCH_SEQ_CONV = 0, 1
 SOLVER_LSQR, SOLVER_DIRECT = 0, 1
@@ -70,6 +70,20 @@ def build_epi(N: int, M: int, percentage: float, T: int):
     if st != 0:
         raise QmriError(st, L.qmri_last_error(None).decode())
     return fp, k[: m.value].copy()
+
+
+def build_spiral_traj(N: int, S: int, T: int):
+    """The spiral of setup_subsampling_spiralgrided.m:7-27 before rounding -> (frame_ptr[T+1] int32, omega[m, 2] float64 radians per pixel),
+    m = S * T, frame-major; omega[:, 0] runs along N (the first index), omega[:, 1] along M."""
+    L = _lib.lib()
+    fp = np.zeros(T + 1, np.int32)
+    om = np.zeros((S * T, 2), np.float64)
+    m = C.c_int(0)
+    st = L.qmri_build_spiral_traj(None, int(N), int(S), int(T), fp.ctypes.data_as(C.POINTER(C.c_int32)), om.ctypes.data_as(C.POINTER(C.c_double)),
+                                  om.shape[0], C.byref(m))
+    if st != 0:
+        raise QmriError(st, L.qmri_last_error(None).decode())
+    return fp, om[: m.value].copy()
 
 
 def read_onnx_unetres(path):
@@ -135,6 +149,26 @@ class Engine:
         k = np.ascontiguousarray(kidx, dtype=np.int32)
         self._check(self.L.qmri_set_operator(self.h, int(N), int(M), int(s), int(T), Vf.ctypes.data_as(C.POINTER(C.c_double)),
                                              fp.ctypes.data_as(C.POINTER(C.c_int32)), k.ctypes.data_as(C.POINTER(C.c_int32)), int(max_batch)))
+        self.N, self.M, self.s, self.T, self.m = int(N), int(M), int(s), int(T), int(fp[-1])
+
+    def set_trajectory(self, N, M, V, frame_ptr, omega, max_batch=1, width=0):
+        """A non-Cartesian operator (qmri_set_operator_nufft): omega is m x 2 radians per pixel in [-pi, pi] (column 0 along N, column 1 along M),
+        frame-major as y; width = NUFFT kernel width (0: the default).  forward / adjoint / pnp_admm / the _mc methods then run on it."""
+        V = real_dictionary_array(V, "V", np.float64)
+        if V.ndim != 2:
+            raise ValueError("V must be T x s")
+        T, s = V.shape
+        Vf = np.ascontiguousarray(V.ravel(order="F"))
+        fp = np.ascontiguousarray(frame_ptr, dtype=np.int32)
+        om = np.ascontiguousarray(omega, dtype=np.float64)
+        if fp.ndim != 1 or fp.size != T + 1:
+            raise ValueError(f"frame_ptr must have T + 1 = {T + 1} entries")
+        if om.ndim != 2 or om.shape[1] != 2 or om.shape[0] != int(fp[-1]):
+            raise ValueError(f"omega must be m x 2 with m = frame_ptr[-1] = {int(fp[-1])}")
+        p = NufftParams(int(width))
+        self._check(self.L.qmri_set_operator_nufft(self.h, int(N), int(M), int(s), int(T), Vf.ctypes.data_as(C.POINTER(C.c_double)),
+                                                   fp.ctypes.data_as(C.POINTER(C.c_int32)), om.ctypes.data_as(C.POINTER(C.c_double)), int(max_batch),
+                                                   C.byref(p)))
         self.N, self.M, self.s, self.T, self.m = int(N), int(M), int(s), int(T), int(fp[-1])
 
     def forward(self, x):

@@ -230,6 +230,10 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
         P = R.setup_subsampling_spiralgrided(N, M, spiral_sampling_curve, V)
     elif subsampling_pattern == "EPI":
         P = R.setup_subsampling_epi(N, M, epi_sampling_rate, V)
+    elif subsampling_pattern == "SpiralExact":                                       # the spiral at its exact positions (NUFFT)
+        if recon_method not in ("PnP_ADMM", "SVD_MRF"):
+            raise ValueError(f"subsampling pattern SpiralExact supports PnP_ADMM and SVD_MRF, not {recon_method}")
+        P = R.setup_subsampling_spiral_exact(N, M, spiral_sampling_curve, V)
     else:
         raise ValueError(f"unknown subsampling pattern {subsampling_pattern}")
     F = R.make_F(P, device=device)

@@ -6,7 +6,15 @@ function F = qmri_make_F(pattern, N, M, rate, V)
 %       F.adjoint = @(x) (ifft2(reshape(P.adj(x),N,M,[]))*sqrt(N*M));
 %   by   F = qmri_make_F('Spiral', N, M, spiral_sampling_curve, V);          (or 'EPI', ..., epi_sampling_rate, V)
 %   N, M in {32 64 96 112 128 160 192 224 256}, chosen independently (EPI); the spiral is square, N == M.
+%   F = qmri_make_F('SpiralExact', N, N, spiral_sampling_curve, V) keeps the spiral's samples at their exact positions (no rounding onto the
+%   grid): a NUFFT operator (DESIGN.md section 14).  For a measured trajectory see qmri_make_F_traj.
 T = size(V, 1);  s = size(V, 2);
+if strcmp(pattern, 'SpiralExact')
+    if N ~= M, error('qmri:pattern', 'the spiral is square (setup_subsampling_spiralgrided.m:28-31): N must equal M'); end
+    [fp, omega] = qmri_mex('build_spiral_traj', N, rate, T);
+    F = qmri_make_F_traj(N, M, V, fp, omega);
+    return
+end
 switch pattern
     case 'Spiral'
         if N ~= M, error('qmri:pattern', 'the spiral mask is square (setup_subsampling_spiralgrided.m:28-31): N must equal M'); end

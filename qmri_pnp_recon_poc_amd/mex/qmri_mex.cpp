@@ -15,6 +15,8 @@
 //   * 'device' selects the GPU of the single-context commands;
 //   * 'recon_batch' hands a whole slice stack to qmri_recon_batch: one worker (host thread + context) per entry of `devs`, slices_per_launch
 //     slices advanced together on each (k_conv6p, batched LSQR), x and the T1 / T2 / PD maps of every slice back.
+//   * 'set_trajectory' plans a non-Cartesian operator (qmri_set_operator_nufft; 'build_spiral_traj' gives the reference's spiral before rounding):
+//     'forward', 'adjoint' and 'pnp_admm' then run on it (a measurement matrix slice by slice; no diagnostics), 'recon_batch*' refuse it.
 //   * 'recon_batch_mc' is the same for multi-coil stacks, every slice with its own coil maps (qmri_recon_batch_mc; an extension, no reference
 //     counterpart); with a coil-compression argument every launch compresses its slices on the device first (qmri_recon_batch_mc_cc).
 //   * 'coil_compress' compresses a multi-coil stack to virtual coils (qmri_coil_compress; extension).
@@ -34,7 +36,8 @@ static qmri_ctx* g_ctx = nullptr;
 static int g_device = 0;
 
 // what the current plans were made from (persistent mxArrays: they survive the call that brought them)
-struct OperatorSpec { mxArray* V = nullptr; mxArray* fp = nullptr; mxArray* kidx = nullptr; int N = 0, M = 0, max_batch = 0; };
+struct OperatorSpec { mxArray* V = nullptr; mxArray* fp = nullptr; mxArray* kidx = nullptr; int N = 0, M = 0, max_batch = 0;
+                     mxArray* omega = nullptr; int width = 0; };      // omega (m x 2) set: a trajectory operator ('set_trajectory'), kidx unset
 struct DenoiserSpec { mxArray* w = nullptr; qmri_net_desc d{}; int H = 0, W = 0, max_batch = 0; };
 struct DictSpec { mxArray* D = nullptr; mxArray* normD = nullptr; mxArray* lut = nullptr; };
 static OperatorSpec g_op;
@@ -47,7 +50,7 @@ static mxArray* keep(const mxArray* a) { mxArray* c = mxDuplicateArray(a); mexMa
 
 static void cleanup() {
     if (g_ctx) { qmri_destroy(g_ctx); g_ctx = nullptr; }
-    drop(g_op.V); drop(g_op.fp); drop(g_op.kidx); g_op = OperatorSpec();
+    drop(g_op.V); drop(g_op.fp); drop(g_op.kidx); drop(g_op.omega); g_op = OperatorSpec();
     drop(g_net.w); g_net = DenoiserSpec();
     drop(g_dict.D); drop(g_dict.normD); drop(g_dict.lut);
 }
@@ -112,6 +115,17 @@ static size_t operator_m() {
 // (re-)make the plans from the kept specifications
 static void plan_operator(int max_batch) {
     const int T = (int)mxGetM(g_op.V), s = (int)mxGetN(g_op.V);
+    if (g_op.omega) {                                               // MATLAB's m x 2 (column-major) -> the ABI's interleaved (omega1, omega2) pairs
+        const size_t m = mxGetM(g_op.omega);
+        const double* om = mxGetDoubles(g_op.omega);
+        std::vector<double> pairs(2 * m);
+        for (size_t i = 0; i < m; ++i) { pairs[2 * i] = om[i]; pairs[2 * i + 1] = om[m + i]; }
+        qmri_nufft_params np{};
+        np.width = g_op.width;
+        check(qmri_set_operator_nufft(ctx(), g_op.N, g_op.M, s, T, mxGetDoubles(g_op.V), (const int32_t*)mxGetData(g_op.fp), pairs.data(), max_batch, &np));
+        g_op.max_batch = max_batch;
+        return;
+    }
     check(qmri_set_operator(ctx(), g_op.N, g_op.M, s, T, mxGetDoubles(g_op.V), (const int32_t*)mxGetData(g_op.fp), (const int32_t*)mxGetData(g_op.kidx), max_batch));
     g_op.max_batch = max_batch;
 }
@@ -205,10 +219,46 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         const int Nn = int_arg(prhs[1], 1, 65536, "qmri:set_operator:size", "N must be a positive integer");
         const int Mm = int_arg(prhs[2], 1, 65536, "qmri:set_operator:size", "M must be a positive integer");
         const int mb = nrhs > 6 ? int_arg(prhs[6], 1, 4096, "qmri:set_operator:size", "max_batch must be a positive integer") : 1;
-        drop(g_op.V); drop(g_op.fp); drop(g_op.kidx);
+        drop(g_op.V); drop(g_op.fp); drop(g_op.kidx); drop(g_op.omega); g_op = OperatorSpec();
         g_op.N = Nn; g_op.M = Mm;
         g_op.V = keep(prhs[3]); g_op.fp = keep(prhs[4]); g_op.kidx = keep(prhs[5]);
         plan_operator(mb);
+    } else if (c == "set_trajectory") {              // qmri_mex('set_trajectory', N, M, V, frame_ptr(int32), omega(m x 2 double) [, max_batch [, width]])
+        need(nrhs, 6, "qmri_mex('set_trajectory', N, M, V, frame_ptr, omega [, max_batch [, width]])");
+        want(mxIsDouble(prhs[3]) && !mxIsComplex(prhs[3]), "qmri:set_trajectory:type", "V must be a real double T x s matrix");
+        want(mxIsInt32(prhs[4]), "qmri:set_trajectory:type", "frame_ptr must be int32 (as 'build_spiral_traj' returns it)");
+        want(mxIsDouble(prhs[5]) && !mxIsComplex(prhs[5]) && mxGetNumberOfDimensions(prhs[5]) == 2 && mxGetN(prhs[5]) == 2, "qmri:set_trajectory:type",
+             "omega must be a real double m x 2 matrix (radians per pixel; column 1 along N, column 2 along M)");
+        {
+            const size_t T = mxGetM(prhs[3]);
+            want(mxGetNumberOfElements(prhs[4]) == T + 1, "qmri:set_trajectory:size", "frame_ptr must have T + 1 entries (T = rows of V)");
+            const int32_t total = ((const int32_t*)mxGetData(prhs[4]))[T];
+            want(total >= 0 && mxGetM(prhs[5]) == (size_t)total, "qmri:set_trajectory:size", "omega must have frame_ptr(end) rows");
+        }
+        const int Nn = int_arg(prhs[1], 1, 65536, "qmri:set_trajectory:size", "N must be a positive integer");
+        const int Mm = int_arg(prhs[2], 1, 65536, "qmri:set_trajectory:size", "M must be a positive integer");
+        const int mb = nrhs > 6 ? int_arg(prhs[6], 1, 4096, "qmri:set_trajectory:size", "max_batch must be a positive integer") : 1;
+        const int wd = nrhs > 7 ? int_arg(prhs[7], 0, 64, "qmri:set_trajectory:size", "width must be a non-negative integer (0: the default)") : 0;
+        drop(g_op.V); drop(g_op.fp); drop(g_op.kidx); drop(g_op.omega); g_op = OperatorSpec();
+        g_op.N = Nn; g_op.M = Mm; g_op.width = wd;
+        g_op.V = keep(prhs[3]); g_op.fp = keep(prhs[4]); g_op.omega = keep(prhs[5]);
+        plan_operator(mb);
+    } else if (c == "build_spiral_traj") {           // [frame_ptr, omega] = qmri_mex('build_spiral_traj', N, S, T)   (host code: no GPU needed)
+        need(nrhs, 4, "[frame_ptr, omega] = qmri_mex('build_spiral_traj', N, S, T)");
+        const int N = int_arg(prhs[1], 1, 65536, "qmri:build_spiral_traj:size", "N must be a positive integer");
+        const int S = int_arg(prhs[2], 2, 1 << 20, "qmri:build_spiral_traj:size", "S must be an integer >= 2");
+        const int T = int_arg(prhs[3], 1, 65535, "qmri:build_spiral_traj:size", "T must be a positive integer");
+        want((double)S * T <= 2147483647.0, "qmri:build_spiral_traj:size", "S * T exceeds the int32 sample index");
+        const size_t m = (size_t)S * T;
+        std::vector<double> pairs(2 * m);
+        int mo = 0;
+        plhs[0] = mxCreateNumericMatrix(T + 1, 1, mxINT32_CLASS, mxREAL);
+        if (qmri_build_spiral_traj(nullptr, N, S, T, (int32_t*)mxGetData(plhs[0]), pairs.data(), (int)m, &mo) != QMRI_OK)
+            mexErrMsgIdAndTxt("qmri:mask", "%s", qmri_last_error(nullptr));
+        mxArray* om = mxCreateDoubleMatrix(m, 2, mxREAL);
+        double* o = mxGetDoubles(om);
+        for (size_t i = 0; i < m; ++i) { o[i] = pairs[2 * i]; o[m + i] = pairs[2 * i + 1]; }
+        if (nlhs > 1) plhs[1] = om; else mxDestroyArray(om);
     } else if (c == "build_spiral" || c == "build_epi") {   // [frame_ptr, kidx] = qmri_mex('build_spiral', N, S, T)   (host integer code: no GPU needed)
         need(nrhs, 4, "[frame_ptr, kidx] = qmri_mex('build_spiral', N, S, T) | qmri_mex('build_epi', N, M, pct, T)");
         const int N = (int)mxGetScalar(prhs[1]);
@@ -296,7 +346,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         // through the batched kernels, slices_per_launch = min(S, 15) at a time, on the current device (X0 / gt: N x M x s x S or empty)
         need(nrhs, 6, "[x, diag, lsqr_iters] = qmri_mex('pnp_admm', y, param, X0, gt, [N M s])");
         want(mxIsStruct(prhs[2]), "qmri:pnp_admm:type", "param must be a struct");
-        const qmri_admm_params p = admm_params(prhs[2], nlhs > 1);
+        const qmri_admm_params p = admm_params(prhs[2], nlhs > 1 && !g_op.omega);   // (a trajectory computes no diagnostics: diag stays NaN)
         const double* d = mxGetDoubles(prhs[5]);
         const size_t S = mxGetN(prhs[1]), m = mxGetM(prhs[1]), n = dims_numel(prhs[5]);
         want(is_cdouble(prhs[1]) && S >= 1 && m == operator_m(), "qmri:pnp_admm:size", "y must be complex double, one column of m samples per slice");
@@ -307,6 +357,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         plhs[0] = mxCreateNumericArray(S > 1 ? 4 : 3, dims, mxDOUBLE_CLASS, mxCOMPLEX);
         const mwSize ddims[3] = {2, (mwSize)it, (mwSize)S};
         mxArray* diag = mxCreateNumericArray(S > 1 ? 3 : 2, ddims, mxDOUBLE_CLASS, mxREAL);
+        if (g_op.omega) std::fill(mxGetDoubles(diag), mxGetDoubles(diag) + mxGetNumberOfElements(diag), NAN);
         mxArray* li = mxCreateNumericMatrix(it, S, mxINT32_CLASS, mxREAL);
         const mxComplexDouble* y = mxGetComplexDoubles(prhs[1]);
         const mxComplexDouble* x0 = mxIsEmpty(prhs[3]) ? nullptr : mxGetComplexDoubles(prhs[3]);
@@ -317,7 +368,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
             check(qmri_pnp_admm(ctx(), y, &p, x0, gt, mxGetComplexDoubles(plhs[0]), p.want_diag ? mxGetDoubles(diag) : nullptr, (int32_t*)mxGetData(li)));
         } else {
             // several slices on this device: the plans grow to the launch size, then qmri_pnp_admm_batch walks the stack
-            const int spl = (int)std::min<size_t>(S, DEFAULT_SLICES_PER_LAUNCH);
+            const int spl = g_op.omega ? 1 : (int)std::min<size_t>(S, DEFAULT_SLICES_PER_LAUNCH);   // (a trajectory: one slice per launch)
             reserve(spl, true, true);
             check(qmri_pnp_admm_batch(ctx(), (int)S, spl, y, &p, x0, gt, mxGetComplexDoubles(plhs[0]), p.want_diag ? mxGetDoubles(diag) : nullptr,
                                       (int32_t*)mxGetData(li)));
@@ -337,6 +388,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         if (mc) need(nrhs, 7, "[X, qmap, pd] = qmri_mex('recon_batch_mc', Y, maps, param, devs, slices_per_launch, [N M s] [, cc, noise_cov])");
         else need(nrhs, 6, "[X, qmap, pd] = qmri_mex('recon_batch', Y, param, devs, slices_per_launch, [N M s])");
         if (!g_op.V || !g_net.w) mexErrMsgIdAndTxt("qmri:recon_batch:state", "set_operator and set_denoiser (or load_onnx) must come first");
+        want(!g_op.omega, "qmri:recon_batch:trajectory", "the batch workers need a gridded mask (set_operator); reconstruct a trajectory with 'pnp_admm'");
         size_t S = mxGetN(prhs[1]), ncoil = 0;
         if (mc) {
             const mwSize nd = mxGetNumberOfDimensions(prhs[1]);

@@ -4,6 +4,7 @@ pipeline, so this Python mirror is the executable counterpart of the `.m` wrappe
 
     P   = setup_subsampling_spiralgrided(N, M, S, V)        # setup_subsampling_spiralgrided.m:1
     P   = setup_subsampling_epi(N, M, percentage, V)        # setup_subsampling_epi.m:1
+    P   = setup_subsampling_spiral_exact(N, M, S, V)        # the same spiral before its rounding (a trajectory)
     F   = make_F(P)                                         # F.forward / F.adjoint, main_recon_tsmis_FFT.m:228-229
     net = make_net(weights, denoiser_type, residual_noise)  # param.net, main_recon_tsmis_FFT.m:164
     x   = PnP_ADMM(y, param)                                # PnP_ADMM.m:1, param = dict with the reference's field names
@@ -50,10 +51,24 @@ def setup_subsampling_epi(N, M, percentage, V):
     return SimpleNamespace(N=int(N), M=int(M), V=V, frame_ptr=fp, kidx=k, pattern="EPI")
 
 
+def setup_subsampling_spiral_exact(N, M, S, V):
+    """The spiral of setup_subsampling_spiralgrided.m:7-27 WITHOUT the rounding onto the grid: every sample at its exact position
+    (qmri_build_spiral_traj); make_F turns it into the NUFFT operator (qmri_set_operator_nufft).  No reference counterpart."""
+    if int(N) != int(M):
+        raise ValueError(f"the spiral is square (setup_subsampling_spiralgrided.m:28-31): N = {N} != M = {M}")
+    V = np.real(np.asarray(V, dtype=np.complex128)).astype(np.float64)
+    fp, om = E.build_spiral_traj(int(N), int(S), V.shape[0])
+    return SimpleNamespace(N=int(N), M=int(M), V=V, frame_ptr=fp, omega=om, pattern="SpiralExact")
+
+
 def make_F(P, device=0):
-    """F.forward = @(x) P.for(reshape(fft2(x),[],1))/sqrt(N*M);  F.adjoint = @(x) ifft2(reshape(P.adj(x),N,M,[]))*sqrt(N*M)."""
+    """F.forward = @(x) P.for(reshape(fft2(x),[],1))/sqrt(N*M);  F.adjoint = @(x) ifft2(reshape(P.adj(x),N,M,[]))*sqrt(N*M).
+    A P with a trajectory (setup_subsampling_spiral_exact) gives the same two maps at the exact sample positions."""
     eng = _engine(device)
-    eng.set_operator(P.N, P.M, P.V, P.frame_ptr, P.kidx)
+    if getattr(P, "omega", None) is not None:
+        eng.set_trajectory(P.N, P.M, P.V, P.frame_ptr, P.omega)
+    else:
+        eng.set_operator(P.N, P.M, P.V, P.frame_ptr, P.kidx)
     return SimpleNamespace(forward=eng.forward, adjoint=eng.adjoint, _engine=eng, _P=P)
 
 
@@ -104,9 +119,11 @@ def PnP_ADMM(y, param):
         raise TypeError("param.F and param.net must come from make_F / make_net of this package (same device)")
     multi = param.get("denoiser_type", net._denoiser_type) == "multi_level"
     noise_std = float(np.asarray(param["noise_map"]).ravel()[0]) if multi else 0.01
+    traj = getattr(F._P, "omega", None) is not None                 # (a trajectory computes no per-iteration diagnostics: last_diagnostics is None)
     x, diag, li = F._engine.pnp_admm(y, gamma=param["gamma"], iters=int(param["iter"]), cg_tol=param["cg_tol"], cg_maxit=100,
                                      solver=param.get("solver", "lsqr"), multi_level=multi, noise_std=noise_std,
-                                     x0=param.get("X0"), gt=param.get("gt_tsmi"), want_diag=param.get("gt_tsmi") is not None)
+                                     x0=param.get("X0"), gt=None if traj else param.get("gt_tsmi"),
+                                     want_diag=param.get("gt_tsmi") is not None and not traj)
     PnP_ADMM.last_diagnostics, PnP_ADMM.last_lsqr_iters = diag, li
     return x
 

@@ -1,0 +1,168 @@
+"""Host (no GPU): the exact spiral builder of the trajectory operator, its rounding back to the gridded mask, the ABI symbols and the refusals that
+need no device."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+
+import nufft_ref as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def E():
+    from qmri_pnp_recon_poc_amd import engine
+    return engine
+
+
+@pytest.mark.parametrize("N,S,T", [(32, 120, 3), (64, 771, 5), (224, 771, 200), (96, 57, 1)])
+def test_spiral_traj_matches_restatement(E, N, S, T):
+    fp, om = E.build_spiral_traj(N, S, T)
+    fr, omr = R.spiral_traj(N, S, T)
+    assert np.array_equal(fp, fr) and om.shape == (S * T, 2)
+    assert np.allclose(om, omr, rtol=0, atol=1e-12)             # (linspace and pow round differently in numpy)
+    assert np.all(np.abs(om) <= np.pi)
+
+
+@pytest.mark.parametrize("N,S,T", [(32, 120, 4), (64, 771, 6), (224, 771, 200)])
+def test_rounding_the_exact_spiral_gives_the_gridded_mask(E, N, S, T):
+    fp, om = E.build_spiral_traj(N, S, T)
+    fg, kg = E.build_spiral(N, S, T)
+    fr, kr = R.grid_mask_from_traj(N, fp, om)
+    assert np.array_equal(fr, fg) and np.array_equal(kr, kg)
+    if (N, S, T) == (224, 771, 200):
+        assert fp[-1] == 154200 and fg[-1] < fp[-1]               # gridding merges samples
+
+
+def test_symbols_are_declared_and_exported():
+    from qmri_pnp_recon_poc_amd import _lib
+    hdr = open(os.path.join(ROOT, "include", "qmri.h")).read()
+    for name in ("qmri_build_spiral_traj", "qmri_set_operator_nufft"):
+        assert name in _lib.SYMBOLS and f"int {name}(" in hdr
+        assert hasattr(_lib.lib(), name)
+    assert "qmri_nufft_params" in hdr
+
+
+def test_capacity_and_argument_refusals_without_a_device():
+    from qmri_pnp_recon_poc_amd import _lib
+    L = _lib.lib()
+    fp = np.zeros(4, np.int32)
+    om = np.zeros(2 * 10, np.float64)
+    m = C.c_int(0)
+    st = L.qmri_build_spiral_traj(None, 32, 120, 3, fp.ctypes.data_as(C.POINTER(C.c_int32)), om.ctypes.data_as(C.POINTER(C.c_double)), 10, C.byref(m))
+    assert st == -1 and m.value == 360 and b"capacity" in L.qmri_last_error(None)
+    st = L.qmri_build_spiral_traj(None, 32, 1, 3, fp.ctypes.data_as(C.POINTER(C.c_int32)), om.ctypes.data_as(C.POINTER(C.c_double)), 10, C.byref(m))
+    assert st == -1
+    st = L.qmri_set_operator_nufft(None, 32, 32, 1, 1, None, None, None, 1, None)
+    assert st == -1
+
+
+def _nufft_args(om, fp, V):
+    return (V.ctypes.data_as(C.POINTER(C.c_double)), fp.ctypes.data_as(C.POINTER(C.c_int32)), om.ctypes.data_as(C.POINTER(C.c_double)))
+
+
+def test_set_operator_nufft_checks_its_arguments_before_the_context():
+    """The trajectory checks are host arithmetic and run before the context is used: with ctx == NULL each one reports itself
+    (qmri_last_error(NULL)); a call that passes them all fails on the NULL context alone."""
+    from qmri_pnp_recon_poc_amd import _lib
+    L = _lib.lib()
+    T, S, s = 3, 40, 2
+    V = np.ones((T * s,), np.float64)
+    fp = (np.arange(T + 1) * S).astype(np.int32)
+    om = np.zeros((S * T, 2), np.float64)
+
+    def call(om_, fp_, N=32, M=32, width=0, reserved=0):
+        p = _lib.NufftParams(width)
+        p.reserved[2] = reserved
+        st = L.qmri_set_operator_nufft(None, N, M, s, T, *_nufft_args(np.ascontiguousarray(om_), np.ascontiguousarray(fp_), V), 1, C.byref(p))
+        return st, L.qmri_last_error(None).decode()
+
+    bad = om.copy(); bad[7, 1] = np.pi * (1 + 1e-12)
+    assert call(bad, fp)[0] == -1 and "[-pi, pi]" in call(bad, fp)[1] and "sample 7" in call(bad, fp)[1]
+    bad[7, 1] = np.nan
+    assert call(bad, fp)[0] == -1 and "[-pi, pi]" in call(bad, fp)[1]
+    bad[7, 1] = -np.inf
+    assert call(bad, fp)[0] == -1
+    fpb = fp.copy(); fpb[1], fpb[2] = fpb[2], fpb[1]
+    assert call(om, fpb) == (-1, "invalid argument: frame_ptr must be non-decreasing")
+    for w in (1, 17, -3):
+        st, msg = call(om, fp, width=w)
+        assert st == -4 and "width" in msg, (w, st, msg)
+    assert call(om, fp, reserved=5) == (-1, "invalid argument: qmri_nufft_params.reserved must be zero")
+    st, msg = call(om, fp, N=48)
+    assert st == -4 and "48" in msg                                    # no FFT plan for that side
+    edge = om.copy(); edge[0] = [np.pi, -np.pi]                       # the closed interval is allowed
+    assert call(edge, fp) == (-1, "invalid argument: ctx must not be NULL")
+
+
+def test_python_argument_checks(E):
+    e = E.Engine.__new__(E.Engine)                                    # (no device: the checks come before the library call)
+    e.L, e.h = None, None
+    V = np.ones((2, 1))
+    with pytest.raises(ValueError):
+        e.set_trajectory(32, 32, V, np.array([0, 1], np.int32), np.zeros((1, 2)))          # frame_ptr must have T + 1 entries
+    with pytest.raises(ValueError):
+        e.set_trajectory(32, 32, V, np.array([0, 1, 2], np.int32), np.zeros((2, 3)))       # omega m x 2
+    with pytest.raises(ValueError):
+        e.set_trajectory(32, 32, V, np.array([0, 1, 3], np.int32), np.zeros((2, 2)))       # m = frame_ptr[-1]
+
+
+def test_mex_trajectory_commands_under_the_mock_gateway(E):
+    """'build_spiral_traj' runs on the host and equals the Python builder (m x 2, MATLAB layout); 'set_trajectory' checks what its arrays must
+    be before the library reads them; the harness refuses SpiralExact for the methods a trajectory does not serve."""
+    from mexmock import MexError, qmri_mex
+    fp, om = qmri_mex("build_spiral_traj", 64.0, 120.0, 5.0, nargout=2)
+    fr, omr = E.build_spiral_traj(64, 120, 5)
+    assert fp.dtype == np.int32 and fp.shape == (6, 1) and np.array_equal(fp.ravel(), fr)
+    assert om.shape == (600, 2) and np.array_equal(om, omr)
+    for args in ((64.0, 1.0, 5.0), (64.0, 120.0, float("nan")), (-1.0, 120.0, 5.0)):
+        with pytest.raises(MexError) as e:
+            qmri_mex("build_spiral_traj", *args, nargout=2)
+        assert e.value.id == "qmri:build_spiral_traj:size"
+    with pytest.raises(MexError) as e:
+        qmri_mex("build_spiral_traj", 64.0, 120.0, nargout=2)
+    assert e.value.id == "qmri:usage"
+    V = np.ones((5, 2))
+    fp32 = fp.ravel().astype(np.int32)
+    cases = [((64.0, 64.0, V, fp32.astype(np.float64), om), "qmri:set_trajectory:type"),     # frame_ptr as doubles
+             ((64.0, 64.0, V, fp32, om.T.copy()), "qmri:set_trajectory:type"),               # 2 x m
+             ((64.0, 64.0, V, fp32, om.astype(np.complex128)), "qmri:set_trajectory:type"),  # complex omega
+             ((64.0, 64.0, V.astype(np.complex128), fp32, om), "qmri:set_trajectory:type"),
+             ((64.0, 64.0, V, fp32[:-1].copy(), om), "qmri:set_trajectory:size"),           # T + 1 entries wanted
+             ((64.0, 64.0, V, fp32, om[:-1].copy()), "qmri:set_trajectory:size"),           # fewer rows than frame_ptr(end)
+             ((64.0, 64.0, V, fp32, om, 0.0), "qmri:set_trajectory:size"),                  # max_batch
+             ((64.0, 64.0, V, fp32, om, 1.0, float("nan")), "qmri:set_trajectory:size"),    # width
+             ((float("nan"), 64.0, V, fp32, om), "qmri:set_trajectory:size")]
+    for args, ident in cases:
+        with pytest.raises(MexError) as e:
+            qmri_mex("set_trajectory", *args)
+        assert e.value.id == ident, (ident, e.value.id, e.value.msg)
+    with pytest.raises(MexError) as e:
+        qmri_mex("set_trajectory", 64.0, 64.0, V, fp32)
+    assert e.value.id == "qmri:usage"
+    from qmri_pnp_recon_poc_amd import harness as H
+    with pytest.raises(ValueError) as e:
+        H.recon_tsmis({"V": np.ones((4, 2))}, np.zeros((32, 32, 2)), np.zeros((32, 32, 3)), recon_method="LRTV", subsampling_pattern="SpiralExact")
+    assert "SpiralExact" in str(e.value)
+
+
+def test_restatement_is_adjoint_and_pins_the_grid():
+    """The numpy restatement itself: <A x, y> = <x, A^H y>, and on-grid points give the unitary DFT of the mask's k."""
+    rng = np.random.default_rng(0)
+    N, M, T, s = 16, 24, 3, 2
+    V = rng.standard_normal((T, s))
+    fp = np.array([0, 5, 9, 14], np.int32)
+    om = rng.uniform(-np.pi, np.pi, (14, 2))
+    x = rng.standard_normal((N, M, s)) + 1j * rng.standard_normal((N, M, s))
+    y = rng.standard_normal(14) + 1j * rng.standard_normal(14)
+    a = np.vdot(y, R.nudft_forward(x, om, V, fp))
+    b = np.vdot(R.nudft_adjoint(y, om, V, fp, N, M), x)
+    assert abs(a - b) < 1e-12 * abs(a)
+    k = rng.integers(0, N * M, 14)
+    yg = R.nudft_forward(x, R.traj_from_kidx(N, M, k), V, fp)
+    X = np.fft.fft2(x, axes=(0, 1)) / np.sqrt(N * M)
+    t = R.frames_of(fp)
+    ref = np.array([np.sum(V[t[i]] * X[k[i] % N, k[i] // N, :]) for i in range(14)])
+    assert np.allclose(yg, ref, rtol=0, atol=1e-12)
