@@ -15,7 +15,12 @@ one GPU and reconstructs its own slice (slices are independent: weak scaling, no
 `value` = ADMM iterations of all ranks / wall time of the slowest rank.  Inputs (y) are resident in HBM when the
 timed region starts.  Data and weights are synthetic (seeded; the reference ships neither).
 
-The JSON line also carries
+A plain run does only what the headline needs: set-up, --warmup iterations, the --steps timed iterations, --dump-outputs, and the line
+(`metric`, `value`, `unit`, `ms_per_step`, `dtype`, ... and the timed call's own `lsqr_iters_mean` and `health`; `roofline`, `cpu_baseline`
+and `parity` are null).  Everything else takes runs of its own and comes with `--full` (off by default; the --no-* options leave parts of it
+out): `cold_start`, `with_diagnostics`, `stage_ms_per_iter`, `denoiser_weights_timing`, `slices` and the objects below.
+
+With --full the JSON line also carries
   roofline     -- the dominant kernel family (the 3x3 convolutions: conv3x3 as implicit GEMM on v_mfma_f32_32x32x16_f16, every fp32
                   operand split into two f16 pieces (hi, scaled residual), three MFMA products per fp32-equivalent product; with
                   QMRI_DEBUG="conv_scheme=3": three bf16 pieces, six products).  Pure measurement, no apportioning: every launch
@@ -132,7 +137,13 @@ def parse_args():
                     "(CPU test of the --gpus N path; the line carries value null)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed call returned (rank 0) as DIR/<name>.npy, "
                     "float32 / float64, at most 64 MB in all; the inputs are seeded, so two builds can be compared output for output")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="everything else the line can carry besides the headline: cold start, the timed region with "
+                    "diagnostics, rooflines and stage split, CPU baseline and parity, the `slices` phase, the other BASELINE configurations (the --no-* "
+                    "options leave parts of it out).  Without it a run sets up, warms up, times the steps, writes --dump-outputs and prints the headline")
+    args = ap.parse_args()
+    if not args.full:                                            # a plain run: only what the headline figure needs
+        args.no_cold_start = args.no_roofline = args.no_cpu_baseline = args.no_slices = args.no_secondary = True
+    return args
 
 
 DUMP_LIMIT_BYTES = 64 << 20
@@ -742,7 +753,7 @@ def worker(args):
             dist.all_reduce(cover, op=dist.ReduceOp.SUM)
         if rank == 0:
             print(json.dumps({"metric": "ADMM iters/sec (224x224x10 TSMI, spiral mask)", "value": None, "unit": "ADMM iters/s", "n_gpus": world,
-                              "steps": args.steps, "warmup": args.warmup, "plumbing_only": True, "max_rank_seconds": round(dt, 4),
+                              "steps": args.steps, "warmup": args.warmup, "plumbing_only": True, "full": args.full, "max_rank_seconds": round(dt, 4),
                               "slices_on_rank0": len(mine), "slices_owned_once": int((cover == 1).sum()), "slices_total": int(cover.numel()),
                               "batches_on_rank0": -(-len(mine) // max(args.batch, 1)), "scaling": "strong" if args.total_slices > 0 else "weak"}), flush=True)
         if world > 1:
@@ -855,18 +866,19 @@ def worker(args):
         # the same K steps with the reference's two per-iteration diagnostics on (PnP_ADMM.m:106-109: |y - A x| / |y| and
         # |x_gt - x| / |x_gt|, which the reference always computes and the CPU baseline below runs): a second timed region,
         # reported beside `value` (the headline keeps the diagnostics off: they are print-outs, not part of the iteration)
-        barrier()
-        t0 = time.perf_counter()
-        run(args.steps, want_diag=1)
-        barrier()
-        dt_diag = time.perf_counter() - t0
-        if world > 1:
-            t = torch.tensor([dt_diag], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            dt_diag = float(t.item())
-        result_extra["with_diagnostics"] = {"value": round(args.steps * world / dt_diag, 4), "unit": "ADMM iters/s",
-                                            "ms_per_step": round(dt_diag / max(args.steps, 1) * 1e3, 4),
-                                            "last_data_fidelity_rel": float(diag[max(args.steps, 1) - 1, 0]), "last_gt_rel_err": float(diag[max(args.steps, 1) - 1, 1])}
+        if args.full:
+            barrier()
+            t0 = time.perf_counter()
+            run(args.steps, want_diag=1)
+            barrier()
+            dt_diag = time.perf_counter() - t0
+            if world > 1:
+                t = torch.tensor([dt_diag], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
+                dist.all_reduce(t, op=dist.ReduceOp.MAX)
+                dt_diag = float(t.item())
+            result_extra["with_diagnostics"] = {"value": round(args.steps * world / dt_diag, 4), "unit": "ADMM iters/s",
+                                                "ms_per_step": round(dt_diag / max(args.steps, 1) * 1e3, 4),
+                                                "last_data_fidelity_rel": float(diag[max(args.steps, 1) - 1, 0]), "last_gt_rel_err": float(diag[max(args.steps, 1) - 1, 1])}
     else:
         from qmri_pnp_recon_poc_amd.batch import shard_slices
         if args.total_slices > 0:
@@ -1125,7 +1137,7 @@ def worker(args):
             ms_per_step = dt / max(unit_count, 1) * 1e3              # per slice on one rank
         out = {"metric": metric, "value": round(total_units / dt, 4), "unit": unit, "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": "f32",
-               "data": "synthetic", "config": cfg, "roofline": roof, "cpu_baseline": cpu, "parity": parity}
+               "data": "synthetic", "full": args.full, "config": cfg, "roofline": roof, "cpu_baseline": cpu, "parity": parity}
         out.update(result_extra)
         if cold is not None:
             out["cold_start"] = cold

@@ -70,3 +70,17 @@ def test_bench_gpus_n_spawns_its_own_ranks():
     import torch
     if not torch.cuda.is_available():
         assert r.returncode != 0                           # no GPU here: the workers refuse (no CPU path), the parent reports it
+
+
+def test_bench_full_adds_the_slices_phase_to_the_rank_plumbing():
+    """A plain `bench.py --gpus N` run times the headline alone: every rank works on slices of its own (--slices-per-gpu each: weak).  With --full
+    the line also carries the fixed 120-slice phase, sharded over the ranks in contiguous blocks (strong); --plumbing-only rehearses both here
+    without a GPU."""
+    import json
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
+    for extra, full, on0, scaling in (([], False, 15, "weak"), (["--full"], True, 60, "strong")):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--plumbing-only", "--steps", "3", "--warmup", "1"] + extra,
+                           env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr
+        out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+        assert out["full"] is full and out["n_gpus"] == 2 and out["slices_on_rank0"] == on0 and out["scaling"] == scaling

@@ -3,6 +3,7 @@ import json
 import os
 import subprocess
 import sys
+import time
 
 import numpy as np
 import pytest
@@ -25,7 +26,7 @@ def _run(args, timeout=900):
 
 def test_bench_two_ranks_without_a_launcher():
     """`bench.py --gpus 2` alone: two worker processes (here both on device 0 over gloo: one-GPU box), one line, n_gpus 2."""
-    out = _run(["--gpus", "2", "--backend", "gloo", "--one-device", "--steps", "4", "--warmup", "1", "--no-roofline", "--no-cpu-baseline", "--no-secondary",
+    out = _run(["--full", "--gpus", "2", "--backend", "gloo", "--one-device", "--steps", "4", "--warmup", "1", "--no-roofline", "--no-cpu-baseline", "--no-secondary",
                 "--slices-total", "5", "--slices-iters", "2", "--slices-batch", "2"])
     assert out["n_gpus"] == 2 and out["steps"] == 4 and out["value"] > 0
     assert out["scaling"] == "weak" and out["config"]["parallelism"].startswith("slice-parallel x2")
@@ -39,7 +40,7 @@ def test_bench_many_ranks_rehearsed_on_one_device():
     over the two-rank test is exercised: a rendezvous of many ranks started by a parent that never touches the GPU, a shard per rank, many contexts
     on one device at once -- both co-residency kernels (k_ks_persist, k_conv6r) must run or fall back cleanly when they do not get the chip to
     themselves -- and the max-over-ranks line.  (N = 8 itself: tests/test_dist_gloo.py, --plumbing-only, on the CPU.)"""
-    out = _run(["--gpus", "5", "--backend", "gloo", "--one-device", "--steps", "3", "--warmup", "1", "--no-roofline", "--no-cpu-baseline", "--no-secondary",
+    out = _run(["--full", "--gpus", "5", "--backend", "gloo", "--one-device", "--steps", "3", "--warmup", "1", "--no-roofline", "--no-cpu-baseline", "--no-secondary",
                 "--slices-total", "10", "--slices-iters", "2", "--slices-batch", "2"], timeout=1200)
     assert out["n_gpus"] == 5 and out["steps"] == 3 and out["value"] > 0 and out["config"]["parallelism"].startswith("slice-parallel x5")
     sl = out["slices"]
@@ -47,7 +48,7 @@ def test_bench_many_ranks_rehearsed_on_one_device():
 
 
 def test_bench_line_has_roofline_cpu_baseline_and_parity():
-    out = _run(["--steps", "6", "--warmup", "2", "--cpu-iters", "6", "--slices-total", "6", "--slices-iters", "3", "--slices-batch", "3", "--secondary-steps", "4"])
+    out = _run(["--full", "--steps", "6", "--warmup", "2", "--cpu-iters", "6", "--slices-total", "6", "--slices-iters", "3", "--slices-batch", "3", "--secondary-steps", "4"])
     assert out["n_gpus"] == 1 and out["unit"] == "ADMM iters/s" and out["dtype"] == "f32"
     # north_star's second metric rides in the same line (default: 120 slices x 100 iterations; here 6 x 3): slices/s, the batched conv
     # kernel's roofline and the dictionary match against the f16 pipe it runs on (a fraction <= 1)
@@ -107,6 +108,22 @@ def test_bench_line_has_roofline_cpu_baseline_and_parity():
     wd = out["with_diagnostics"]                                                                      # PnP_ADMM.m:106-109 on the GPU side too
     # (6 steps each: which of the two short timed regions is faster is noise; a sanity bound)
     assert 0 < wd["value"] <= out["value"] * 1.5 and 0 < wd["last_data_fidelity_rel"] < 1 and 0 < wd["last_gt_rel_err"] < 1
+
+
+def test_bench_plain_run_does_the_headline_alone():
+    """Without --full a run sets up, warms up, times the steps and prints the headline: none of the phases that take runs of their own, and at most
+    30 s of its wall clock (process start to exit) outside the warm-up and timed steps."""
+    t0 = time.perf_counter()
+    out = _run(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    wall = time.perf_counter() - t0
+    assert out["full"] is False and out["n_gpus"] == 1 and out["steps"] == 5 and out["warmup"] == 2
+    assert out["unit"] == "ADMM iters/s" and out["dtype"] == "f32" and out["higher_is_better"] is True and out["value"] > 0
+    assert abs(out["value"] * out["ms_per_step"] - 1e3) < 1.0 and out["lsqr_iters_mean"] >= 1
+    assert out["roofline"] is None and out["cpu_baseline"] is None and out["parity"] is None
+    for key in ("cold_start", "with_diagnostics", "stage_ms_per_iter", "xupdate", "denoiser_weights_timing", "slices", "epi_batch15", "cut0", "cut0_multicoil8"):
+        assert key not in out, key
+    assert out["health"]["repeated_calls"] == 0 and out["health"]["all_ranks"]["repeated_calls"] == 0
+    assert wall - 7 * out["ms_per_step"] * 1e-3 < 30.0, f"{wall:.1f} s in all"
 
 
 def test_bench_slices_fixed_total_sharding():

@@ -6,7 +6,7 @@ R=$PWD; KNOB=$1; STEPS=${2:-50}; shift 2
 [ $# -gt 0 ] || set -- 0 1
 for rep in 1 2; do
   for v in "$@"; do
-    QMRI_DEBUG="$KNOB=$v" timeout -k 10 280 python3 $R/bench.py --gpus 1 --steps $STEPS --warmup 5 --no-slices --no-secondary --no-cpu-baseline > /tmp/abk.json 2>/tmp/abk.err || { echo "bench failed ($KNOB=$v)"; tail -5 /tmp/abk.err; exit 1; }
+    QMRI_DEBUG="$KNOB=$v" timeout -k 10 280 python3 $R/bench.py --full --gpus 1 --steps $STEPS --warmup 5 --no-slices --no-secondary --no-cpu-baseline > /tmp/abk.json 2>/tmp/abk.err || { echo "bench failed ($KNOB=$v)"; tail -5 /tmp/abk.err; exit 1; }
     python3 - "$KNOB" "$v" "$rep" <<'PY'
 import json, sys
 o = json.loads([l for l in open('/tmp/abk.json') if l.startswith('{')][0])

@@ -7,7 +7,7 @@ STEPS=${2:-50}
 for rep in 1 2; do
   for which in other tree; do
     if [ $which = other ]; then export QMRI_LIBQMRI=$R/$OTHER; else unset QMRI_LIBQMRI; fi
-    timeout -k 10 280 python3 $R/bench.py --gpus 1 --steps $STEPS --warmup 5 --no-slices --no-cpu-baseline > /tmp/abl.json 2>/tmp/abl.err || { echo "bench failed ($which)"; tail -5 /tmp/abl.err; exit 1; }
+    timeout -k 10 280 python3 $R/bench.py --full --gpus 1 --steps $STEPS --warmup 5 --no-slices --no-cpu-baseline > /tmp/abl.json 2>/tmp/abl.err || { echo "bench failed ($which)"; tail -5 /tmp/abl.err; exit 1; }
     python3 - "$which" "$rep" <<'PY'
 import json, sys
 o = json.loads([l for l in open('/tmp/abl.json') if l.startswith('{')][0])

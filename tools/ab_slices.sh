@@ -8,7 +8,7 @@ for spec in "$@"; do
   [ "$lib" = "-" ] && libenv="" || libenv="QMRI_LIBQMRI=$lib"
   for rep in 1 2; do
     echo "== $spec (run $rep)" >> $OUT
-    env $envs $libenv python bench.py --workload slices --steps 10 --warmup 1 --no-cpu-baseline --dict-k 64 32 2>>$OUT | python -c "
+    env $envs $libenv python bench.py --full --workload slices --steps 10 --warmup 1 --no-cpu-baseline --dict-k 64 32 2>>$OUT | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -10,7 +10,7 @@ while time.time() - t0 < float(sys.argv[1]):
     for _ in range(20): c = a @ b
     torch.cuda.synchronize()
 """
-BENCH = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-secondary", "--no-cold-start", "--no-slices"]
+BENCH = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-secondary", "--no-cold-start", "--no-slices"]
 for hog in (False, True):
     for dbg in ("", "lsqr_persist=0", "conv_resident=0", "lsqr_persist=0,conv_resident=0"):
         h = None

@@ -7,8 +7,8 @@ TAG=${1:-r06}
 R=$PWD; OUT=$R/gpurun_out/final_$TAG; mkdir -p $OUT; export TMPDIR=/tmp
 timeout -k 10 1000 python3 -m pytest tests -x -q -m gpu > $OUT/pytest_gpu.log 2>&1; echo "pytest rc $?" >> $OUT/pytest_gpu.log
 tail -3 $OUT/pytest_gpu.log
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_command.json 2> $OUT/bench_driver.err || echo "driver bench failed"
-python3 bench.py --no-slices --no-secondary --no-cold-start > $OUT/bench_default_steps100.json 2> $OUT/bench_default.err || echo "default bench failed"
+python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_command.json 2> $OUT/bench_driver.err || echo "driver bench failed"
+python3 bench.py --full --no-slices --no-secondary --no-cold-start > $OUT/bench_default_steps100.json 2> $OUT/bench_default.err || echo "default bench failed"
 python3 -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.txt 2>&1 || echo "smoke failed"
 bash tools/profile_round.sh $TAG > $OUT/profile_round.log 2>&1 || echo "profile round failed"
 bash tools/pmc_xupdate.sh $TAG > $OUT/pmc_xupdate.log 2>&1 || echo "pmc xupdate failed"

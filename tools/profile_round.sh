@@ -1,6 +1,6 @@
 #!/bin/bash
 # One profiling pass on the GPU box (run through gpurun from the repository root):  bash tools/profile_round.sh <tag>
-# kernel-trace statistics of the DRIVER's command (bench.py --steps 20 --warmup 5: ADMM it/s + the slices object + CPU baseline), then the PMC
+# kernel-trace statistics of the DRIVER's command with --full (bench.py --steps 20 --warmup 5: ADMM it/s + the slices object + CPU baseline), then the PMC
 # passes for tools/pmc_traffic.py (one slice and a 15-slice batch) and the matrix-core / clock pass of tools/pmc_conv.sh.
 # rocprofv3 is given the program itself after `--` (python3 ...), never a wrapper; counters and traces are separate runs.
 set -o pipefail
@@ -10,7 +10,7 @@ OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/driver -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_command_under_rocprof.json 2> $OUT/driver.err || echo "driver-command trace failed"
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/driver -- python3 $R/bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_command_under_rocprof.json 2> $OUT/driver.err || echo "driver-command trace failed"
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc_fetch -- python3 $R/tools/prof_net.py 1 3 > $OUT/pmc_fetch.log 2>&1 || echo "pmc fetch failed"
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/pmc_write -- python3 $R/tools/prof_net.py 1 3 > $OUT/pmc_write.log 2>&1 || echo "pmc write failed"
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc_fetch15 -- python3 $R/tools/prof_net.py 15 2 > $OUT/pmc_fetch15.log 2>&1 || echo "pmc fetch (batch) failed"

@@ -35,7 +35,7 @@ while time.time() - t0 < float(sys.argv[1]):
     torch.cuda.synchronize()
     del h
 """
-BENCH = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-secondary", "--no-cold-start", "--no-roofline",
+BENCH = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-secondary", "--no-cold-start", "--no-roofline",
          "--slices-total", "30", "--slices-iters", "100", "--slices-batch", "15"]
 
 

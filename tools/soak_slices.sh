@@ -3,7 +3,7 @@
 # every launch, per-rank seconds, the health counters and the stage split of the slowest launch.  Usage (GPU box):  bash tools/soak_slices.sh [runs] > gpurun_out/soak.txt
 N=${1:-6}
 for i in $(seq 1 $N); do
-  python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-secondary --no-roofline --no-cold-start > /tmp/soak_$i.json 2> /tmp/soak_$i.err || { echo "run $i failed"; tail -3 /tmp/soak_$i.err; continue; }
+  python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-secondary --no-roofline --no-cold-start > /tmp/soak_$i.json 2> /tmp/soak_$i.err || { echo "run $i failed"; tail -3 /tmp/soak_$i.err; continue; }
   python3 - $i <<'PY'
 import json, sys
 o = json.loads([l for l in open('/tmp/soak_%s.json' % sys.argv[1]) if l.startswith('{')][0]); s = o['slices']
