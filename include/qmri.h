@@ -11,6 +11,7 @@
  *   param.net = @(x) denoiseImage_PnP_ADMM(...)   main_recon_tsmis_FFT.m:164, denoiseImage_PnP_ADMM.m:1-117 -> qmri_set_denoiser, qmri_denoise
  *   Net = importONNXNetwork(denoiser_path, ...)   main_recon_tsmis_FFT.m:138 (weights only)      -> qmri_onnx_read_unetres
  *   x = PnP_ADMM(y, param)                        PnP_ADMM.m:1                      -> qmri_pnp_admm
+ *     with complex TSMIs (cat(3, real, imag) denoiser, no reference counterpart) -> denoiser_type | QMRI_DENOISER_COMPLEX
  *   out = mrf_dtm_cpu(dict, data, par)            mrf_dtm_cpu.m:1                   -> qmri_set_dictionary, qmri_dict_match
  *   x = FISTA_deep(data, param) (LRTV option)     FISTA_deep.m:1, main_recon_tsmis_FFT.m:273-282 -> qmri_lrtv, qmri_prox_tv, qmri_norm_tv
  *
@@ -167,14 +168,23 @@ int qmri_denoiser_scheme(const qmri_ctx* ctx, int* scheme_out, int* fallbacks_ou
 
 /* ---- PnP-ADMM: x = PnP_ADMM(y, param), PnP_ADMM.m:1 ----------------------------------------------- */
 enum { QMRI_SOLVER_LSQR = 0, QMRI_SOLVER_DIRECT = 1 };
-enum { QMRI_DENOISER_SINGLE_LEVEL = 0, QMRI_DENOISER_MULTI_LEVEL = 1 };
+/* denoiser_type is a set of bits: 0 single_level, 1 multi_level, 2 complex single_level, 3 complex multi_level; any other value is
+ * QMRI_ERR_INVALID_ARG.  QMRI_DENOISER_COMPLEX (complex TSMIs; the reference's TSMIs are real, PnP_ADMM.m:115-118) changes Step 2 only:
+ *   v = x + uold ; V = cat(3, real(v), imag(v))        N x M x 2s, planes 0..s-1 real, s..2s-1 imaginary
+ *   [V, lo, hi, range] = norm_zero_to_one(V)          one min / max over all 2s*N*M values of the slice
+ *   multi_level: V = cat(3, V, noise_map)             noise plane at channel 2s
+ *   V = net(V) ; V = V*range + lo ; v = complex(V(:,:,1:s), V(:,:,s+1:2s)) ; uold = uold + x - v ; z = v - uold
+ * The denoiser then has in_nc == 2s (+1) and out_nc == 2s (the 2s-channel layout of qmri_synthesize_tsmi_complex); any other network, and a
+ * 2s-channel network in real mode, is QMRI_ERR_STATE with a message naming the channel counts (other misfits in real mode: QMRI_ERR_INVALID_ARG).
+ * Every PnP-ADMM entry point takes the mode through this field (single- and multi-coil, slice batches, qmri_recon_batch(_mc)). */
+enum { QMRI_DENOISER_SINGLE_LEVEL = 0, QMRI_DENOISER_MULTI_LEVEL = 1, QMRI_DENOISER_COMPLEX = 2 };
 typedef struct {
     double gamma;            /* param.gamma = sigma_squared/eta = 0.05   main_recon_tsmis_FFT.m:285-287 */
     int32_t iters;           /* param.iter = 100                          :288 */
     double cg_tol;           /* param.cg_tol = 1e-4                       :289 */
     int32_t cg_maxit;        /* 100 (literal in PnP_ADMM.m:102) */
     int32_t solver;          /* QMRI_SOLVER_LSQR reproduces the reference; DIRECT is the exact minimiser */
-    int32_t denoiser_type;   /* param.denoiser_type                       :167 */
+    int32_t denoiser_type;   /* param.denoiser_type                       :167  (| QMRI_DENOISER_COMPLEX: complex TSMIs, see above) */
     double noise_std;        /* build_noise_map(0.01,...)                 :76,:170 */
     int32_t want_diag;       /* the two per-iteration diagnostics of PnP_ADMM.m:106-109 */
 } qmri_admm_params;

@@ -26,7 +26,7 @@ def shard_slices(nslices: int, world: int, rank: int) -> list:
 
 def recon_batch(devices, Y, N, M, V, frame_ptr, kidx, weights, in_nc=10, out_nc=10, nc=(64, 128, 256, 512), nb=4,
                 dictionary=None, gamma=0.05, iters=100, cg_tol=1e-4, cg_maxit=100, solver="lsqr", multi_level=False,
-                noise_std=0.01, slices_per_launch=1, coil_maps=None, coil_compress=None, noise_cov=None):
+                noise_std=0.01, slices_per_launch=1, coil_maps=None, coil_compress=None, noise_cov=None, tsmi_domain="real"):
     """Reconstruct Y[nslices, m] on the given devices; returns dict(X [nslices,N,M,s], qmap, pd).
 
     coil_maps [nslices, N, M, ncoil] (multi-coil extension, no reference counterpart): Y is then [nslices, m, ncoil], every slice is reconstructed
@@ -34,7 +34,11 @@ def recon_batch(devices, Y, N, M, V, frame_ptr, kidx, weights, in_nc=10, out_nc=
 
     coil_compress (with coil_maps): an int nv, or a dict of qmri_cc_params fields (nv, energy, shared), and noise_cov [ncoil, ncoil] (or None):
     every launch compresses its slices to nv virtual coils on the device, one W per slice (whitened by noise_cov), before the reconstruction
-    (qmri_recon_batch_mc_cc; the library refuses energy and shared there).  Without coil_compress nothing changes."""
+    (qmri_recon_batch_mc_cc; the library refuses energy and shared there).  Without coil_compress nothing changes.
+
+    tsmi_domain "complex": complex TSMIs (engine.denoiser_type); the network then has in_nc = 2s (+1) and out_nc = 2s."""
+    from .engine import denoiser_type
+    dtype = denoiser_type(multi_level, tsmi_domain)
     L = _lib.lib()
     ncoil, Mb = 0, None
     cc = None
@@ -93,7 +97,7 @@ def recon_batch(devices, Y, N, M, V, frame_ptr, kidx, weights, in_nc=10, out_nc=
     else:
         pb.K, pb.Q = 0, 0
     pb.admm = AdmmParams(float(gamma), int(iters), float(cg_tol), int(cg_maxit), 0 if solver == "lsqr" else 1,
-                         int(bool(multi_level)), float(noise_std), 0)
+                         dtype, float(noise_std), 0)
     pb.slices_per_launch = int(slices_per_launch)
     n = N * M * s
     X = np.empty((nsl, n), np.complex128)

@@ -717,7 +717,7 @@ int qmri_prepare_direct(qmri_ctx* ctx, double r) {
 // its work with ctx->ks_persist = 0).  The ADMM loop uses this so that the host never waits inside a reconstruction.
 // fuse (round 4, nullable): what the ADMM loop has already done in neighbouring launches, or wants done in this solve's last one --
 // z_hpass_nblk > 0: o.d_tmp holds the h-pass of z's transform and ls.pz that many partial sums of |z|^2 per slice (k_dual_fwd_h), d_z is not read;
-// mm_u / mm: the final h-pass also leaves the partial min / max of real(x + mm_u) per workgroup in mm (k_adj_h).
+// mm_u / mm: the final h-pass also leaves the partial min / max of real(x + mm_u) per workgroup in mm (k_adj_h; mm_cpx: of both parts).
 int qmri_lsqr_run(qmri_ctx* ctx, int B, const double2* d_z, double r, double tol, int maxit, double2* d_x,
                   int32_t* iters_out, int32_t* flag_out, double* pdiag, LsqrState* hslot, bool* deferred, const LsqrFuse* fuse) {
     OpHost& o = ctx->op;
@@ -731,6 +731,7 @@ int qmri_lsqr_run(qmri_ctx* ctx, int B, const double2* d_z, double r, double tol
     const bool z_fused = fuse && fuse->z_hpass_nblk > 0;
     const double2* const mm_u = fuse ? fuse->mm_u : nullptr;
     double* const mm = fuse ? fuse->mm : nullptr;
+    const bool mm_cpx = fuse && fuse->mm_cpx;
     if (z_fused && !o.xhat_valid) { qmri_set_error(ctx, "qmri_lsqr_run: a transformed z needs the spectrum of x (internal)"); return QMRI_ERR_STATE; }
     if (!o.xhat_valid) QMRI_TRY(dc_launch_fwd(ctx, op, o.ls, DC_SPECTRUM, B, d_x, o.d_tmp, ks.xhat, nullptr));
     if (z_fused) ks.nblk_z = fuse->z_hpass_nblk;
@@ -762,7 +763,7 @@ int qmri_lsqr_run(qmri_ctx* ctx, int B, const double2* d_z, double r, double tol
         if (persisted) {
             ctx->ks_tag += 2u * (unsigned)(maxit + 2);
             QMRI_TRY(ks_launch_final(ctx, op, ks, B, o.d_tmp));
-            QMRI_TRY(dc_launch_adj_h(ctx, op, B, o.d_tmp, d_x, mm_u, mm));
+            QMRI_TRY(dc_launch_adj_h(ctx, op, B, o.d_tmp, d_x, mm_u, mm, mm_cpx));
             if (deferred) {                                        // the caller reads hslot after its own synchronisation
                 *deferred = true;
                 std::swap(o.ks.xhat, o.ks.xhat_out);
@@ -807,7 +808,7 @@ int qmri_lsqr_run(qmri_ctx* ctx, int B, const double2* d_z, double r, double tol
         // (no copy of the state: k_ks_b writes iter / done / flag of every slice to the pinned host array itself, ks.hst)
         QMRI_HIP(ctx, hipEventRecord(ctx->ev_state, ctx->stream));
         QMRI_TRY(ks_launch_final(ctx, op, ks, B, o.d_tmp));              // reads ks.xhat (x0), writes ks.xhat_out
-        QMRI_TRY(dc_launch_adj_h(ctx, op, B, o.d_tmp, d_x, mm_u, mm));
+        QMRI_TRY(dc_launch_adj_h(ctx, op, B, o.d_tmp, d_x, mm_u, mm, mm_cpx));
         QMRI_HIP(ctx, hipEventSynchronize(ctx->ev_state));
         all_done = true;
         for (int b = 0; b < B; ++b) all_done = all_done && hs[b].done;

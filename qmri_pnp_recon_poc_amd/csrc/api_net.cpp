@@ -718,6 +718,29 @@ struct StageTimer {
     }
 };
 
+// The denoiser step's mode (qmri_admm_params.denoiser_type, include/qmri.h) and the network it needs: real TSMIs take s (+1) -> s channels,
+// complex TSMIs (QMRI_DENOISER_COMPLEX) take 2s (+1) -> 2s.  Complex mode refuses any other network as a state error,
+// and so does real mode a network made for complex TSMIs (the wrong denoiser is set for this call); real mode's other misfits stay argument errors.
+static int admm_net_fits(qmri_ctx* ctx, const qmri_admm_params* prm, int* multi_out, bool* cpx_out) {
+    const OpHost& o = ctx->op;
+    const NetPlan& net = ctx->net;
+    QMRI_CHECK_ARG(ctx, prm->denoiser_type >= 0 && prm->denoiser_type <= (QMRI_DENOISER_COMPLEX | QMRI_DENOISER_MULTI_LEVEL),
+                   "denoiser_type must be 0 .. 3 (QMRI_DENOISER_MULTI_LEVEL | QMRI_DENOISER_COMPLEX)");
+    const int multi = (prm->denoiser_type & QMRI_DENOISER_MULTI_LEVEL) ? 1 : 0;
+    const bool cpx = (prm->denoiser_type & QMRI_DENOISER_COMPLEX) != 0;
+    const int planes = cpx ? 2 * o.s : o.s, other = cpx ? o.s : 2 * o.s;
+    if (net.H != o.N || net.W != o.M || net.desc.in_nc != planes + multi || net.desc.out_nc != planes) {
+        const bool other_domain = net.desc.in_nc == other + multi && net.desc.out_nc == other;
+        qmri_set_error(ctx, "denoiser (%d x %d, %d -> %d channels) does not fit the operator (%d x %d x %d, %s, %s TSMIs: %d -> %d channels needed)",
+                       net.H, net.W, net.desc.in_nc, net.desc.out_nc, o.N, o.M, o.s, multi ? "multi_level" : "single_level",
+                       cpx ? "complex" : "real", planes + multi, planes);
+        return (cpx || other_domain) ? QMRI_ERR_STATE : QMRI_ERR_INVALID_ARG;
+    }
+    *multi_out = multi;
+    *cpx_out = cpx;
+    return QMRI_OK;
+}
+
 static int pnp_admm_dev_impl(qmri_ctx* ctx, int nslices, const void* d_y, const qmri_admm_params* prm, const void* d_x0,
                              const void* d_gt, void* d_x_out, double* diag_out, int32_t* lsqr_iters_out);
 
@@ -781,12 +804,9 @@ static int pnp_admm_dev_impl(qmri_ctx* ctx, int nslices, const void* d_y, const 
     const int B = nslices;
     QMRI_CHECK_ARG(ctx, B >= 1 && B <= o.maxB && B <= net.maxB, "nslices exceeds max_batch of the operator or the denoiser");
     QMRI_CHECK_ARG(ctx, prm->iters >= 0 && prm->gamma > 0 && prm->cg_maxit >= 0, "iters >= 0, gamma > 0, cg_maxit >= 0 required");
-    const int multi = prm->denoiser_type == QMRI_DENOISER_MULTI_LEVEL;
-    if (net.H != o.N || net.W != o.M || net.desc.in_nc != o.s + (multi ? 1 : 0) || net.desc.out_nc != o.s) {
-        qmri_set_error(ctx, "denoiser (%d x %d, %d -> %d channels) does not fit the operator (%d x %d x %d, %s)", net.H, net.W,
-                       net.desc.in_nc, net.desc.out_nc, o.N, o.M, o.s, multi ? "multi_level" : "single_level");
-        return QMRI_ERR_INVALID_ARG;
-    }
+    int multi = 0;
+    bool cpx = false;
+    QMRI_TRY(admm_net_fits(ctx, prm, &multi, &cpx));
     const OpDev op = qmri_opdev(ctx);
     const size_t plane = (size_t)o.N * o.M, n = plane * o.s, nb = (size_t)B * n * sizeof(double2);
     const double2* y = (const double2*)d_y;
@@ -840,7 +860,7 @@ static int pnp_admm_dev_impl(qmri_ctx* ctx, int nslices, const void* d_y, const 
         if (prm->solver == QMRI_SOLVER_LSQR) {
             bool deferred = false;
             LsqrFuse lf;
-            if (fused) { lf.z_hpass_nblk = z_in_tmp ? hb : 0; lf.mm_u = o.d_u; lf.mm = o.d_mm; }
+            if (fused) { lf.z_hpass_nblk = z_in_tmp ? hb : 0; lf.mm_u = o.d_u; lf.mm = o.d_mm; lf.mm_cpx = cpx; }
             QMRI_TRY(qmri_lsqr_run(ctx, B, o.d_z, prm->gamma, prm->cg_tol, prm->cg_maxit, o.d_x, it_b.data(), nullptr,
                                    diag ? o.d_pd : nullptr,            // (the data-fidelity partials come with the solve)
                                    o.h_ring + (size_t)it * B, &deferred, &lf));
@@ -861,10 +881,10 @@ static int pnp_admm_dev_impl(qmri_ctx* ctx, int nslices, const void* d_y, const 
             QMRI_TRY(ew_launch_diag(ctx, op, o.ls, B, o.d_x, (const double2*)d_gt, o.d_pd, o.d_diag, prm->iters, it));
             tm.stop(ctx->prof.ms_diag);
         }
-        // Step 2 (PnP_ADMM.m:115-138): v = real(x+uold) -> [0,1] -> net -> undo
+        // Step 2 (PnP_ADMM.m:115-138): v = real(x+uold) -> [0,1] -> net -> undo   (complex TSMIs: cat(3, real, imag) of x+uold)
         tm.start();
         QMRI_TRY(ew_launch_minmax_normalise(ctx, B, n, (int)plane, o.N, o.s, multi, prm->noise_std, o.d_x, o.d_u, o.d_mm, o.d_norm,
-                                            fused ? hb : o.ls.nblk_z, net.in32, fused /* the partial min / max came with the solve's last h-pass */));
+                                            fused ? hb : o.ls.nblk_z, net.in32, fused /* the partial min / max came with the solve's last h-pass */, cpx));
         tm.stop(ctx->prof.ms_elementwise);
         tm.start();
         QMRI_TRY(net_forward(ctx, B));
@@ -877,14 +897,15 @@ static int pnp_admm_dev_impl(qmri_ctx* ctx, int nslices, const void* d_y, const 
         tm.start();
         if (fused) {
             const DualArgs da = {net.out32.base1(), net.in32.base1(), net.out32.hp, (int)net.out32.plane(), net.out32.batch_stride(), net.in32.batch_stride(),
-                                 net.desc.residual_noise, o.d_norm, o.d_x, o.d_u, o.ls.pz};
+                                 net.desc.residual_noise, o.d_norm, o.d_x, o.d_u, o.ls.pz, cpx ? 1 : 0};
             ActCheckArgs ac{};
             if (net.act_pending_valid) { ac = net.act_pending; net.act_pending_valid = false; }
             QMRI_TRY(dc_launch_dual_fwd_h(ctx, op, B, da, ac, o.d_tmp));
             z_in_tmp = true;
         } else {
             QMRI_TRY(ew_launch_unnormalise_dual(ctx, B, n, (int)plane, o.N, net.out32, net.in32, net.desc.residual_noise, o.d_norm, o.d_x, o.d_u,
-                                                nullptr /* v itself is never read again: z = v - u goes to the next x-update */, o.d_z, o.ls.pz, o.ls.nblk_z));
+                                                nullptr /* v itself is never read again: z = v - u goes to the next x-update */, o.d_z, o.ls.pz, o.ls.nblk_z,
+                                                o.s, cpx));
         }
         tm.stop(ctx->prof.ms_elementwise);
         ctx->prof.admm_iters += 1;
@@ -943,17 +964,13 @@ static int mc_require(qmri_ctx* ctx, int nslices, int ncoil, const void* maps, c
     return QMRI_OK;
 }
 static int mc_admm_check(qmri_ctx* ctx, const qmri_admm_params* prm) {
-    const OpHost& o = ctx->op;
     const NetPlan& net = ctx->net;
     if (!net.ready) { qmri_set_error(ctx, "denoiser not set: call qmri_set_denoiser first"); return QMRI_ERR_STATE; }
     QMRI_CHECK_ARG(ctx, prm, "params must not be NULL");
     QMRI_CHECK_ARG(ctx, prm->iters >= 0 && prm->gamma > 0 && prm->cg_maxit >= 0 && prm->solver == QMRI_SOLVER_LSQR, "iters >= 0, gamma > 0, cg_maxit >= 0, LSQR solver required");
-    const int multi = prm->denoiser_type == QMRI_DENOISER_MULTI_LEVEL;
-    if (net.H != o.N || net.W != o.M || net.desc.in_nc != o.s + (multi ? 1 : 0) || net.desc.out_nc != o.s) {
-        qmri_set_error(ctx, "denoiser (%d x %d, %d -> %d channels) does not fit the operator (%d x %d x %d)", net.H, net.W, net.desc.in_nc, net.desc.out_nc, o.N, o.M, o.s);
-        return QMRI_ERR_INVALID_ARG;
-    }
-    return QMRI_OK;
+    int multi = 0;
+    bool cpx = false;
+    return admm_net_fits(ctx, prm, &multi, &cpx);
 }
 
 // PnP_ADMM.m:76-146 for B <= max_batch slices, all on the device (d_x0 NULL: x = A_mc' y as :84; returns x as :148).  When the network's range guard
@@ -962,7 +979,8 @@ static int mc_admm_group(qmri_ctx* ctx, int B, int ncoil, const double2* d_maps,
                          double2* d_x, int32_t* li_out, int li_stride) {
     OpHost& o = ctx->op;
     NetPlan& net = ctx->net;
-    const int multi = prm->denoiser_type == QMRI_DENOISER_MULTI_LEVEL;
+    const int multi = (prm->denoiser_type & QMRI_DENOISER_MULTI_LEVEL) ? 1 : 0;       // (checked by mc_admm_check)
+    const bool cpx = (prm->denoiser_type & QMRI_DENOISER_COMPLEX) != 0;
     const size_t plane = (size_t)o.N * o.M, n = plane * o.s;
     std::vector<int32_t> li((size_t)B);
     for (int attempt = 0;; ++attempt) {
@@ -975,10 +993,10 @@ static int mc_admm_group(qmri_ctx* ctx, int B, int ncoil, const double2* d_maps,
         for (int it = 0; it < prm->iters; ++it) {
             QMRI_TRY(qmri_lsqr_mc_batch_dev(ctx, B, ncoil, d_maps, d_y, o.d_z, prm->gamma, prm->cg_tol, prm->cg_maxit, d_x, li.data(), nullptr));   // :102
             if (li_out) for (int b = 0; b < B; ++b) li_out[(size_t)b * li_stride + it] = li[b];
-            QMRI_TRY(ew_launch_minmax_normalise(ctx, B, n, (int)plane, o.N, o.s, multi, prm->noise_std, d_x, o.d_u, o.d_mm, o.d_norm, o.ls.nblk_z, net.in32, false));
+            QMRI_TRY(ew_launch_minmax_normalise(ctx, B, n, (int)plane, o.N, o.s, multi, prm->noise_std, d_x, o.d_u, o.d_mm, o.d_norm, o.ls.nblk_z, net.in32, false, cpx));
             QMRI_TRY(net_forward(ctx, B));
             QMRI_TRY(ew_launch_unnormalise_dual(ctx, B, n, (int)plane, o.N, net.out32, net.in32, net.desc.residual_noise, o.d_norm, d_x, o.d_u, nullptr, o.d_z,
-                                                o.ls.pz, o.ls.nblk_z));
+                                                o.ls.pz, o.ls.nblk_z, o.s, cpx));
             QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
             QMRI_TRY(net_range_tripped(ctx, again));              // (f16 range / hand-off guards: the network is re-packed or the form switched; start again)
             if (again) break;

@@ -45,7 +45,7 @@ constexpr int R_KEEP = 32;                                  // a layer follows: 
 constexpr int R_DOWN = 128;                                 // the level's strided convolution behind the ResBlocks (2x2 / stride 2, 64 -> 128: k_conv6s DOWN) from the resident tile: no ring needed
 constexpr unsigned R_DOWN_STEPB = 2 * 2 * 2 * 64 * 16;           // ... bytes of one of its weight steps (k_conv6s: 2 planes x 2 row tiles x 2 pieces x 64 lanes x 16 B)
 constexpr int R_LOCAL = 256;                                // with R_KEEP: the next layer needs no ring (R_DOWN follows): pieces in place, no exchange
-constexpr int R_TAIL = 64;                                  // the network's last layer (<= 16 output channels): first 32-row tile of the weights only, PLANAR fp32 output
+constexpr int R_TAIL = 64;                                  // the network's last layer (<= 32 output channels): first 32-row tile of the weights only, PLANAR fp32 output
 constexpr int R_IH = 18, R_IW = 18, R_IHP = 24;             // input tile with ring; LDS row pitch (= 8 mod 16 entries, as in k_conv6)
 constexpr int R_NPX = R_IHP * (R_IW - 1) + R_IH;            // LDS entries per (split, k-half) plane
 constexpr int R_CHUNK = 2 * 2 * R_NPX;                      // ... per 16-channel chunk: [split][k-half][R_NPX]
@@ -59,9 +59,9 @@ struct Conv6rArgs {
     const float* src; const float* skip;                    // fbase of the run's input (BLOCKED 64 channels, or the PLANAR network input: in_planar) and of the skip tensor (or null)
     const float* radd[R_MAXL]; float* sdst[R_MAXL];         // per layer: the operand R_ADD adds, where R_STORE / R_STORE_WT store (BLOCKED fp32 tensors of the level's geometry)
     float* dn_out; int dn_hp, dn_plane;                     // R_DOWN: the BLOCKED output tensor of the next level (fbase), its pitch and plane (elements)
-    float* out; int out_hp, out_plane, out_c;               // R_TAIL: the PLANAR output tensor (fbase), its pitch and plane (elements), its channels (<= 16)
-    int in_planar, in_plane;                                // the run's first layer is the network's head: src = the PLANAR input (16 channels allocated), its plane (elements)
-    int nch[R_MAXL], kind[R_MAXL];                          // 16-channel chunks of the layer's input (1: the head; 4), R_* flags
+    float* out; int out_hp, out_plane, out_c;               // R_TAIL: the PLANAR output tensor (fbase), its pitch and plane (elements), its channels (<= 32)
+    int in_planar, in_plane;                                // the run's first layer is the network's head: src = the PLANAR input (16 x nch[0] channels allocated), its plane (elements)
+    int nch[R_MAXL], kind[R_MAXL];                          // 16-channel chunks of the layer's input (1 or 2: the head; 4), R_* flags
     unsigned char* xbuf; size_t xbuf_half;                  // exchange buffer [2 layer parities][tiles][R_NTRI][64 bytes]; bytes per parity
     const uint4* wp[R_MAXL];
     float dh[R_MAXL], dl[R_MAXL];                           // descale of the layer's packed weights (Conv6Args::descale_hi / _lo)
@@ -175,41 +175,46 @@ __global__ __launch_bounds__(NT6) void k_conv6r(const Conv6rArgs A) {
                     }
                 }
             } else {
-                // the network's head: the tile's first chunk from the PLANAR fp32 input (16 channels allocated, those beyond in_nc zero: PTensor): 2 k-halves x
-                // 324 pixels, an item = 8 channels of a pixel = 8 requests one plane apart -> one hi and one lo' entry; the other three chunks are zeroed --
-                // the head's epilogue writes their interior, the ring fetch their ring, and at the image border the ring must read as zero
+                // the network's head: the tile's first nch[0] chunks (1 or 2: in_nc <= 32) from the PLANAR fp32 input (16 x nch[0] channels allocated, those
+                // beyond in_nc zero: PTensor), one chunk after the other: 2 k-halves x 324 pixels, an item = 8 channels of a pixel = 8 requests one plane apart
+                // -> one hi and one lo' entry; the chunks behind them are zeroed -- the head's epilogue writes their interior, the ring fetch their ring, and
+                // at the image border the ring must read as zero (the input chunks' border ring is the planar input's zero halo)
                 constexpr int NIT = 2 * R_IH * R_IW, NQ = (NIT + NLD6 - 1) / NLD6;
                 static_assert(NQ == 3, "the wait below names 24 registers");
-                float v[NQ][8];
-                unsigned lo[NQ];
+                const int nin = A.nch[0];
                 const unsigned pl4 = (unsigned)A.in_plane * 4u, t0 = (unsigned)((ow0 * A.hp + oh0) * 4);
+#pragma unroll 1
+                for (int ck = 0; ck < nin; ++ck) {
+                    float v[NQ][8];
+                    unsigned lo[NQ];
 #pragma unroll
-                for (int k = 0; k < NQ; ++k) {
-                    const int idx = lt + NLD6 * k;
-                    const bool valid = idx < NIT;
-                    const int idc = valid ? idx : 0, kh = idc / (R_IH * R_IW), px = idc - kh * (R_IH * R_IW), dw = px / R_IH, dh = px - dw * R_IH;
+                    for (int k = 0; k < NQ; ++k) {
+                        const int idx = lt + NLD6 * k;
+                        const bool valid = idx < NIT;
+                        const int idc = valid ? idx : 0, kh = idc / (R_IH * R_IW), px = idc - kh * (R_IH * R_IW), dw = px / R_IH, dh = px - dw * R_IH;
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) gload1(v[k][j], (unsigned)(8 * kh + j) * pl4 + (unsigned)((dw * A.hp + dh) * 4) + t0, A.src);
-                    lo[k] = valid ? (unsigned)((kh * NPX + dw * IHP + dh) * 16) : ~0u;
-                }
-                {                                                   // chunks 1 .. 3 := 0 while the requests are in flight
-                    const uint4 z = make_uint4(0u, 0u, 0u, 0u);
-                    for (int i = lt; i < 3 * R_CHUNK; i += NLD6) Bt[R_CHUNK + i] = z;
-                }
-                asm volatile("s_waitcnt vmcnt(0)"
-                             : "+v"(v[0][0]), "+v"(v[0][1]), "+v"(v[0][2]), "+v"(v[0][3]), "+v"(v[0][4]), "+v"(v[0][5]), "+v"(v[0][6]), "+v"(v[0][7]), "+v"(v[1][0]),
-                               "+v"(v[1][1]), "+v"(v[1][2]), "+v"(v[1][3]), "+v"(v[1][4]), "+v"(v[1][5]), "+v"(v[1][6]), "+v"(v[1][7]), "+v"(v[2][0]), "+v"(v[2][1]),
-                               "+v"(v[2][2]), "+v"(v[2][3]), "+v"(v[2][4]), "+v"(v[2][5]), "+v"(v[2][6]), "+v"(v[2][7])::"memory");
+                        for (int j = 0; j < 8; ++j) gload1(v[k][j], (unsigned)(16 * ck + 8 * kh + j) * pl4 + (unsigned)((dw * A.hp + dh) * 4) + t0, A.src);
+                        lo[k] = valid ? (unsigned)((ck * R_CHUNK + kh * NPX + dw * IHP + dh) * 16) : ~0u;
+                    }
+                    if (ck == 0) {                                  // chunks nin .. 3 := 0 while the requests are in flight
+                        const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+                        for (int i = lt; i < (4 - nin) * R_CHUNK; i += NLD6) Bt[nin * R_CHUNK + i] = z;
+                    }
+                    asm volatile("s_waitcnt vmcnt(0)"
+                                 : "+v"(v[0][0]), "+v"(v[0][1]), "+v"(v[0][2]), "+v"(v[0][3]), "+v"(v[0][4]), "+v"(v[0][5]), "+v"(v[0][6]), "+v"(v[0][7]), "+v"(v[1][0]),
+                                   "+v"(v[1][1]), "+v"(v[1][2]), "+v"(v[1][3]), "+v"(v[1][4]), "+v"(v[1][5]), "+v"(v[1][6]), "+v"(v[1][7]), "+v"(v[2][0]), "+v"(v[2][1]),
+                                   "+v"(v[2][2]), "+v"(v[2][3]), "+v"(v[2][4]), "+v"(v[2][5]), "+v"(v[2][6]), "+v"(v[2][7])::"memory");
 #pragma unroll
-                for (int k = 0; k < NQ; ++k) {
-                    uint4 s0, s1;
-                    split_pair_h(v[k][0], v[k][1], s0.x, s1.x);
-                    split_pair_h(v[k][2], v[k][3], s0.y, s1.y);
-                    split_pair_h(v[k][4], v[k][5], s0.z, s1.z);
-                    split_pair_h(v[k][6], v[k][7], s0.w, s1.w);
-                    if (lo[k] != ~0u) {
-                        *(uint4*)((unsigned char*)Bt + lo[k]) = s0;
-                        *(uint4*)((unsigned char*)Bt + lo[k] + 2 * NPX * 16) = s1;
+                    for (int k = 0; k < NQ; ++k) {
+                        uint4 s0, s1;
+                        split_pair_h(v[k][0], v[k][1], s0.x, s1.x);
+                        split_pair_h(v[k][2], v[k][3], s0.y, s1.y);
+                        split_pair_h(v[k][4], v[k][5], s0.z, s1.z);
+                        split_pair_h(v[k][6], v[k][7], s0.w, s1.w);
+                        if (lo[k] != ~0u) {
+                            *(uint4*)((unsigned char*)Bt + lo[k]) = s0;
+                            *(uint4*)((unsigned char*)Bt + lo[k] + 2 * NPX * 16) = s1;
+                        }
                     }
                 }
             }
@@ -427,19 +432,21 @@ __global__ __launch_bounds__(NT6) void k_conv6r(const Conv6rArgs A) {
         int pxl_l = pxl, h2_l = h2;
         asm volatile("" : "+v"(gpx_l), "+v"(pxl_l), "+v"(h2_l));           // (behind the loop: what is derived from them is then made here, not kept across the loop)
         if (kind & R_TAIL) {
-            // The network's last layer (64 -> out_c <= 16 channels, no ReLU, no operand): channels 0 .. 15 of the first 32-row tile go through LDS
-            // (the tile is dead: [channel][w][h] fp32, 16 KB) to the loader waves, which store the out_c planes of the PLANAR output -- their side of
-            // the kernel has the scalar registers for it, this side has not.
+            // The network's last layer (64 -> out_c <= 32 channels, no ReLU, no operand): channels 0 .. 15 (out_c > 16: 0 .. 31) of the first 32-row tile
+            // go through LDS (the tile is dead: [channel][w][h] fp32, 16 / 32 KB of its 109) to the loader waves, which store the out_c planes of the
+            // PLANAR output -- their side of the kernel has the scalar registers for it, this side has not.
             R_STAMP(0, 1);
             R_STAMP(0, 2);
             float* tl = (float*)Bt;
             const float dh_ = A.dh[l], dl_ = A.dl[l];
             float gmax = 0.f;
             bool bad = false;
+            const int nrg = A.out_c > 16 ? 4 : 2;                   // (uniform)
 #pragma unroll
             for (int n = 0; n < 2; ++n)
 #pragma unroll
-                for (int rg = 0; rg < 2; ++rg)
+                for (int rg = 0; rg < 4; ++rg)
+                    if (rg < nrg)
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         const int ch = 8 * rg + 4 * h2 + j;
@@ -650,16 +657,16 @@ int conv6r_try(qmri_ctx* ctx, const Conv6rRun& run, int B, bool* done) {
         if (!t) continue;
         if (!t->p || !t->blk || t->Cal < 64 || t->H != src.H || t->W != src.W || t->hp != src.hp || t->h0 != src.h0) return QMRI_OK;
     }
-    if (run.head) {                                                 // in_nc -> 64 from the PLANAR network input: one 16-channel chunk
+    if (run.head) {                                                 // in_nc -> 64 from the PLANAR network input: one or two 16-channel chunks
         const ConvLayer& L = *run.head;
         const PTensor& in = *run.head_in;
-        if (!is3(L) || L.Cout != 64 || L.nchunk6 != 1 || L.Cin > 16 || !in.p || in.blk || in.Cal < 16 || in.H != src.H || in.W != src.W || in.hp != src.hp ||
+        if (!is3(L) || L.Cout != 64 || L.nchunk6 < 1 || L.nchunk6 > 2 || L.Cin > 16 * L.nchunk6 || !in.p || in.blk || in.Cal < 16 * L.nchunk6 || in.H != src.H || in.W != src.W || in.hp != src.hp ||
             in.h0 != src.h0 || src.p == cur.p) return QMRI_OK;
     }
-    if (run.tail) {                                                 // 64 -> out_nc <= 16 to the PLANAR network output
+    if (run.tail) {                                                 // 64 -> out_nc <= 32 (one 32-row weight tile) to the PLANAR network output
         const ConvLayer& L = *run.tail;
         const PTensor& out = *run.tail_out;
-        if (!is3(L) || L.Cin != 64 || L.nchunk6 != 4 || L.Cout > 16 || !out.p || out.blk || out.H != src.H || out.W != src.W ||
+        if (!is3(L) || L.Cin != 64 || L.nchunk6 != 4 || L.Cout > 32 || !out.p || out.blk || out.H != src.H || out.W != src.W ||
             (size_t)out.Cal * out.plane() * 4 >= ((size_t)1 << 31)) return QMRI_OK;
     }
     if (run.down) {                                                 // 64 -> 128, 2x2 / stride 2, to the next level's BLOCKED tensor (the packed weights of k_conv6s DOWN: 2 tiles x 9 steps)

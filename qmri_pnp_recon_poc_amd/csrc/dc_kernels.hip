@@ -56,8 +56,9 @@ __global__ __launch_bounds__(NT) void k_fwd_h(OpDev op, const double2* __restric
 // transform (k_fwd_h): a workgroup's 16 lines of z go from registers to LDS instead of to memory and back.  z itself is never stored
 // (only the solve reads it, as a spectrum).  Its first workgroups also finish the per-layer |output| report of the forward pass that
 // has just ended (conv6_act.h) -- the launch of k_act_check saved.
+// CPX (QMRI_DENOISER_COMPLEX): v = complex(plane c, plane c + s), both halves un-normalised with the same min / range.
 // ---------------------------------------------------------------------------------------------------
-template <int R1, int R2>
+template <int R1, int R2, bool CPX>
 __global__ __launch_bounds__(NT) void k_dual_fwd_h(OpDev op, DualArgs d, ActCheckArgs ac, double2* __restrict__ tmp) {
     typedef Plan<R1, R2> P;
     constexpr int N = P::N, L = Cfg<R1, R2>::L;
@@ -71,7 +72,9 @@ __global__ __launch_bounds__(NT) void k_dual_fwd_h(OpDev op, DualArgs d, ActChec
     // every operand of the workgroup's 16 lines is requested before the first one is used (clamped, not predicated): ONE memory latency for
     // the launch -- with a load / compute / write-through store per loop iteration the 14 iterations paid 14 (16.2 us per launch against 9)
     constexpr int NIT = (L * N + NT - 1) / NT;
-    float Iv[NIT], Jv[NIT];
+    constexpr int NII = CPX ? NIT : 1;
+    const size_t simag = (size_t)op.s * d.pplane;
+    float Iv[NIT], Jv[NIT], Iiv[NII], Jiv[NII];
     double2 xv[NIT], uv[NIT];
 #pragma unroll
     for (int q = 0; q < NIT; ++q) {
@@ -82,6 +85,10 @@ __global__ __launch_bounds__(NT) void k_dual_fwd_h(OpDev op, DualArgs d, ActChec
         const size_t pi = (size_t)c * d.pplane + (size_t)(w + 1) * d.php + h + 1;
         Iv[q] = d.out32[(size_t)b * d.out_bs + pi];
         Jv[q] = d.residual_noise ? d.in32[(size_t)b * d.in_bs + pi] : 0.f;
+        if (CPX) {
+            Iiv[q % NII] = d.out32[(size_t)b * d.out_bs + pi + simag];
+            Jiv[q % NII] = d.residual_noise ? d.in32[(size_t)b * d.in_bs + pi + simag] : 0.f;
+        }
         xv[q] = d.x[base + i];
         uv[q] = d.u[base + i];
     }
@@ -94,11 +101,13 @@ __global__ __launch_bounds__(NT) void k_dual_fwd_h(OpDev op, DualArgs d, ActChec
             const int line = i / N, h = i - line * N;
             const float I = d.residual_noise ? Jv[q] - Iv[q] : Iv[q];   // denoiseImage_PnP_ADMM.m:99-104
             const double vv = (double)I * range + lo;                   // undo_norm_zero_to_one  :138,187-192
+            double vi = 0.0;
+            if (CPX) vi = (double)(d.residual_noise ? Jiv[q % NII] - Iiv[q % NII] : Iiv[q % NII]) * range + lo;
             double2 un = uv[q];
             un.x = un.x + xv[q].x - vv;                                 // uold = uold + x - v  :144
-            un.y = un.y + xv[q].y - 0.0;
+            un.y = un.y + xv[q].y - vi;
             st_wt(d.u + base + i, un);
-            const double2 zz = make_double2(vv - un.x, 0.0 - un.y);     // z = v - uold  :102
+            const double2 zz = make_double2(vv - un.x, vi - un.y);      // z = v - uold  :102
             lds[line * P::LINE + h] = zz;
             acc += zz.x * zz.x + zz.y * zz.y;
         }
@@ -311,7 +320,8 @@ __global__ __launch_bounds__(NT) void k_adj_w(OpDev op, const double2* __restric
 // ---------------------------------------------------------------------------------------------------
 // u / mm (nullable): the ADMM loop's next step needs min / max of real(x + uold) over the whole stack (PnP_ADMM.m:115-121,174-184); the
 // workgroup that produces x adds its lines' u and leaves its partial min / max in mm[b][blockIdx.x][2] -- the launch of k_minmax saved.
-template <int R1, int R2>
+// CPX: min / max over real(x + uold) and imag(x + uold) together (complex TSMIs).
+template <int R1, int R2, bool CPX>
 __global__ __launch_bounds__(NT) void k_adj_h(OpDev op, const double2* __restrict__ tmp, double2* __restrict__ dst,
                                                const double2* __restrict__ u, double* __restrict__ mm) {
     typedef Plan<R1, R2> P;
@@ -333,16 +343,23 @@ __global__ __launch_bounds__(NT) void k_adj_h(OpDev op, const double2* __restric
     if (fft_lds<R1, R2, false>(lds, L, op.tw_h, out, line2, k1)) {
         const double sc = 1.0 / sqrt((double)N * (double)M);
         const size_t g0 = (size_t)b * n + (size_t)(l0 + line2) * N;
-        double ur[R2];
+        constexpr int RI = CPX ? R2 : 1;
+        double ur[R2], ui[RI];
         if (u) {
 #pragma unroll
-            for (int k2 = 0; k2 < R2; ++k2) ur[k2] = u[g0 + k1 + R1 * k2].x;
+            for (int k2 = 0; k2 < R2; ++k2) {
+                ur[k2] = u[g0 + k1 + R1 * k2].x;
+                if (CPX) ui[k2 % RI] = u[g0 + k1 + R1 * k2].y;
+            }
         }
 #pragma unroll
         for (int k2 = 0; k2 < R2; ++k2) {
             const double2 xv = make_double2(out[k2].x * sc, -out[k2].y * sc);
             st_wt(dst + g0 + k1 + R1 * k2, xv);
-            if (u) { const double v = xv.x + ur[k2]; lo = fmin(lo, v); hi = fmax(hi, v); }
+            if (u) {
+                const double v = xv.x + ur[k2]; lo = fmin(lo, v); hi = fmax(hi, v);
+                if (CPX) { const double vi = xv.y + ui[k2 % RI]; lo = fmin(lo, vi); hi = fmax(hi, vi); }
+            }
         }
     }
     if (u) {                                                        // (uniform)
@@ -437,10 +454,11 @@ int launch_adj_w_t(qmri_ctx* ctx, const OpDev& op, int B, const double2* y_in, d
 }
 
 template <int R1, int R2>   // the h plan
-int launch_adj_h_t(qmri_ctx* ctx, const OpDev& op, int B, const double2* tmp, double2* dst, const double2* u, double* mm) {
+int launch_adj_h_t(qmri_ctx* ctx, const OpDev& op, int B, const double2* tmp, double2* dst, const double2* u, double* mm, bool mm_cpx) {
     int gx = 0;
     QMRI_TRY((hpass_grid<R1, R2>(ctx, op, &gx)));
-    k_adj_h<R1, R2><<<dim3(gx, B), dim3(NT), 0, ctx->stream>>>(op, tmp, dst, u, mm);
+    if (u && mm_cpx) k_adj_h<R1, R2, true><<<dim3(gx, B), dim3(NT), 0, ctx->stream>>>(op, tmp, dst, u, mm);
+    else k_adj_h<R1, R2, false><<<dim3(gx, B), dim3(NT), 0, ctx->stream>>>(op, tmp, dst, u, mm);
     QMRI_HIP(ctx, hipGetLastError());
     return QMRI_OK;
 }
@@ -456,9 +474,9 @@ int launch_fwd(qmri_ctx* ctx, const OpDev& op, const LsqrDev& ls, int mode, int 
 }
 
 int launch_adj(qmri_ctx* ctx, const OpDev& op, int B, const double2* y_in, double2* tmp, double2* dst, bool skip_w,
-               const double2* u = nullptr, double* mm = nullptr) {
+               const double2* u = nullptr, double* mm = nullptr, bool mm_cpx = false) {
     if (!skip_w) QMRI_TRY(with_plan(ctx, op.M, [&](auto p) { return launch_adj_w_t<decltype(p)::R1, decltype(p)::R2>(ctx, op, B, y_in, tmp); }));
-    return with_plan(ctx, op.N, [&](auto p) { return launch_adj_h_t<decltype(p)::R1, decltype(p)::R2>(ctx, op, B, tmp, dst, u, mm); });
+    return with_plan(ctx, op.N, [&](auto p) { return launch_adj_h_t<decltype(p)::R1, decltype(p)::R2>(ctx, op, B, tmp, dst, u, mm, mm_cpx); });
 }
 
 }  // namespace
@@ -479,8 +497,8 @@ int dc_launch_adj(qmri_ctx* ctx, const OpDev& op, int B, const double2* y_in, do
     return launch_adj(ctx, op, B, y_in, tmp, dst, false);
 }
 
-int dc_launch_adj_h(qmri_ctx* ctx, const OpDev& op, int B, const double2* tmp, double2* dst, const double2* u, double* mm) {
-    return launch_adj(ctx, op, B, nullptr, const_cast<double2*>(tmp), dst, true, u, mm);
+int dc_launch_adj_h(qmri_ctx* ctx, const OpDev& op, int B, const double2* tmp, double2* dst, const double2* u, double* mm, bool mm_cpx) {
+    return launch_adj(ctx, op, B, nullptr, const_cast<double2*>(tmp), dst, true, u, mm, mm_cpx);
 }
 
 // workgroups of the h-pass kernels per slice (= partial sums of |z|^2 of k_dual_fwd_h, partial min / max of k_adj_h); 0 for an unsupported N
@@ -497,7 +515,8 @@ template <int R1, int R2>   // the h plan
 static int launch_dual_t(qmri_ctx* ctx, const OpDev& op, int B, const DualArgs& d, const ActCheckArgs& ac, double2* tmp) {
     int gx = 0;
     QMRI_TRY((hpass_grid<R1, R2>(ctx, op, &gx)));
-    k_dual_fwd_h<R1, R2><<<dim3(gx, B), dim3(NT), 0, ctx->stream>>>(op, d, ac, tmp);
+    if (d.complex_tsmi) k_dual_fwd_h<R1, R2, true><<<dim3(gx, B), dim3(NT), 0, ctx->stream>>>(op, d, ac, tmp);
+    else k_dual_fwd_h<R1, R2, false><<<dim3(gx, B), dim3(NT), 0, ctx->stream>>>(op, d, ac, tmp);
     QMRI_HIP(ctx, hipGetLastError());
     return QMRI_OK;
 }

@@ -2,6 +2,8 @@
 //
 // Reference semantics (PnP_ADMM.m):
 //   :115-118  v = real(x + uold)
+//             (complex TSMIs, QMRI_DENOISER_COMPLEX, DESIGN.md section 15: v = x + uold stacked as cat(3, real(v), imag(v)), 2s planes; the
+//              template flag CPX of the three kernels below, one min / max over both halves, the noise plane at channel 2s)
 //   :121,174-184  norm_zero_to_one: global min / max over the whole N x M x s stack, v = (v - min)/(max - min)
 //   :132      multi_level: cat(3, v, noise_map), noise_map = constant plane (build_noise_map.m:19)
 //   :138,187-192  undo_norm_zero_to_one: v = v*range + min
@@ -52,7 +54,8 @@ __device__ __forceinline__ void block_minmax(double& lo, double& hi, double* sh)
     for (int i = 1; i < NT / 64; ++i) { lo = fmin(lo, sh[2 * i]); hi = fmax(hi, sh[2 * i + 1]); }
 }
 
-// pass 1: per-block min / max of real(x + u)
+// pass 1: per-block min / max of real(x + u)  (CPX: of its real and imaginary parts together)
+template <bool CPX>
 __global__ __launch_bounds__(NT) void k_minmax(size_t n, const double2* __restrict__ x, const double2* __restrict__ u,
                                                 double* __restrict__ mm) {
     __shared__ double sh[2 * NT / 64];
@@ -63,6 +66,10 @@ __global__ __launch_bounds__(NT) void k_minmax(size_t n, const double2* __restri
     for (size_t i = i0 + threadIdx.x; i < i1; i += NT) {
         const double v = x[(size_t)b * n + i].x + u[(size_t)b * n + i].x;
         lo = fmin(lo, v); hi = fmax(hi, v);
+        if (CPX) {
+            const double vi = x[(size_t)b * n + i].y + u[(size_t)b * n + i].y;
+            lo = fmin(lo, vi); hi = fmax(hi, vi);
+        }
     }
     block_minmax(lo, hi, sh);
     if (threadIdx.x == 0) {
@@ -74,7 +81,9 @@ __global__ __launch_bounds__(NT) void k_minmax(size_t n, const double2* __restri
 // pass 2: reduce the partials (min/max are order independent), normalise, cast to single, append noise map.
 // The workgroup's share of x and u is requested BEFORE the partials are reduced (the loads do not depend on min / max): one memory latency
 // for the launch instead of two plus one per loop iteration; shares beyond NRQ * NT elements per workgroup fall back to the plain loop.
+// CPX: element i of channel c writes real(x + u) to plane c and imag(x + u) to plane c + s; the noise plane is `noise_c` (s, or 2s).
 constexpr int NRQ = 16;
+template <bool CPX>
 __global__ __launch_bounds__(NT) void k_normalise(size_t n, int plane, int H, int s, int multi_level, double noise_std,
                                                    const double2* __restrict__ x, const double2* __restrict__ u,
                                                    const double* __restrict__ mm, int nblk, double* __restrict__ norm,
@@ -83,12 +92,14 @@ __global__ __launch_bounds__(NT) void k_normalise(size_t n, int plane, int H, in
     const int b = blockIdx.y;
     const size_t chunk = (n + gridDim.x - 1) / gridDim.x;
     const size_t i0 = (size_t)blockIdx.x * chunk, i1 = (i0 + chunk < n) ? i0 + chunk : n;
-    double xr[NRQ], ur[NRQ];
+    constexpr int NRI = CPX ? NRQ : 1;
+    double xr[NRQ], ur[NRQ], xi[NRI], ui[NRI];
 #pragma unroll
     for (int q = 0; q < NRQ; ++q) {
         const size_t i = i0 + threadIdx.x + (size_t)NT * q;
         const size_t ic = (i < i1) ? i : i0;
         xr[q] = x[(size_t)b * n + ic].x; ur[q] = u[(size_t)b * n + ic].x;
+        if (CPX) { xi[q % NRI] = x[(size_t)b * n + ic].y; ui[q % NRI] = u[(size_t)b * n + ic].y; }
     }
     double lo = INFINITY, hi = -INFINITY;
     for (int i = threadIdx.x; i < nblk; i += NT) {
@@ -99,23 +110,27 @@ __global__ __launch_bounds__(NT) void k_normalise(size_t n, int plane, int H, in
     const double range = hi - lo;                       // no zero-range guard, as PnP_ADMM.m:174-184
     if (blockIdx.x == 0 && threadIdx.x == 0) { norm[2 * b] = lo; norm[2 * b + 1] = range; }
     float* dst = in32 + (size_t)b * pbs;                 // padded planes [c][w+1][h+1], zero halo untouched
-    auto put = [&](size_t i, double v) __attribute__((always_inline)) {
+    auto put = [&](size_t i, double v, double vi) __attribute__((always_inline)) {
         const int c = (int)(i / plane), rem = (int)(i - (size_t)c * plane);
         const int w = rem / H, h = rem - w * H;
-        dst[(size_t)c * pplane + (size_t)(w + 1) * php + h + 1] = (float)((v - lo) / range);
+        const size_t pi = (size_t)c * pplane + (size_t)(w + 1) * php + h + 1;
+        dst[pi] = (float)((v - lo) / range);
+        if (CPX) dst[pi + (size_t)s * pplane] = (float)((vi - lo) / range);
     };
 #pragma unroll
     for (int q = 0; q < NRQ; ++q) {
         const size_t i = i0 + threadIdx.x + (size_t)NT * q;
-        if (i < i1) put(i, xr[q] + ur[q]);
+        if (i < i1) put(i, xr[q] + ur[q], CPX ? xi[q % NRI] + ui[q % NRI] : 0.0);
     }
-    for (size_t i = i0 + threadIdx.x + (size_t)NT * NRQ; i < i1; i += NT) put(i, x[(size_t)b * n + i].x + u[(size_t)b * n + i].x);
+    for (size_t i = i0 + threadIdx.x + (size_t)NT * NRQ; i < i1; i += NT)
+        put(i, x[(size_t)b * n + i].x + u[(size_t)b * n + i].x, CPX ? x[(size_t)b * n + i].y + u[(size_t)b * n + i].y : 0.0);
     if (multi_level) {
+        const int noise_c = CPX ? 2 * s : s;
         const int per = (plane + gridDim.x - 1) / gridDim.x;
         const int c0 = blockIdx.x * per, c1 = (c0 + per < plane) ? c0 + per : plane;
         for (int i = c0 + threadIdx.x; i < c1; i += NT) {
             const int w = i / H, h = i - w * H;
-            dst[(size_t)s * pplane + (size_t)(w + 1) * php + h + 1] = (float)noise_std;
+            dst[(size_t)noise_c * pplane + (size_t)(w + 1) * php + h + 1] = (float)noise_std;
         }
     }
 }
@@ -123,7 +138,9 @@ __global__ __launch_bounds__(NT) void k_normalise(size_t n, int plane, int H, in
 // v = double(I)*range + min ;  uold = uold + x - v     (I = CNN output, or input - CNN output)      PnP_ADMM.m:138,144
 // and, for the next iteration's x-update, z = v - uold with the partial sums of ||z||^2 (PnP_ADMM.m:102) -- the same
 // partition and summation order as k_prepare_z, which only the first iteration still needs.
-__global__ __launch_bounds__(NT) void k_unnormalise_dual(size_t n, int plane, int H, int php, int pplane, size_t out_bs,
+// CPX: v = complex(plane c, plane c + s), both un-normalised with the same min / range.
+template <bool CPX>
+__global__ __launch_bounds__(NT) void k_unnormalise_dual(size_t n, int plane, int H, int s, int php, int pplane, size_t out_bs,
                                                           size_t in_bs, const float* __restrict__ out32,
                                                           const float* __restrict__ in32, int residual_noise,
                                                           const double* __restrict__ norm, const double2* __restrict__ x,
@@ -134,6 +151,7 @@ __global__ __launch_bounds__(NT) void k_unnormalise_dual(size_t n, int plane, in
     const double lo = norm[2 * b], range = norm[2 * b + 1];
     const size_t chunk = (n + gridDim.x - 1) / gridDim.x;
     const size_t i0 = (size_t)blockIdx.x * chunk, i1 = (i0 + chunk < n) ? i0 + chunk : n;
+    const size_t simag = (size_t)s * pplane;
     double acc = 0.0;
     for (size_t i = i0 + threadIdx.x; i < i1; i += NT) {
         const int c = (int)(i / plane), rem = (int)(i - (size_t)c * plane);
@@ -142,13 +160,19 @@ __global__ __launch_bounds__(NT) void k_unnormalise_dual(size_t n, int plane, in
         float I = out32[(size_t)b * out_bs + pi];
         if (residual_noise) I = in32[(size_t)b * in_bs + pi] - I;
         const double vv = (double)I * range + lo;
+        double vi = 0.0;
+        if (CPX) {
+            float Ii = out32[(size_t)b * out_bs + pi + simag];
+            if (residual_noise) Ii = in32[(size_t)b * in_bs + pi + simag] - Ii;
+            vi = (double)Ii * range + lo;
+        }
         const double2 xv = x[(size_t)b * n + i];
         double2 uv = u[(size_t)b * n + i];
         uv.x = uv.x + xv.x - vv;
-        uv.y = uv.y + xv.y - 0.0;
+        uv.y = uv.y + xv.y - vi;
         st_wt(u + (size_t)b * n + i, uv);
-        if (v) v[(size_t)b * n + i] = make_double2(vv, 0.0);      // (the ADMM loop passes no v: nothing reads it after the first iteration's z)
-        const double2 zz = make_double2(vv - uv.x, 0.0 - uv.y);
+        if (v) v[(size_t)b * n + i] = make_double2(vv, vi);      // (the ADMM loop passes no v: nothing reads it after the first iteration's z)
+        const double2 zz = make_double2(vv - uv.x, vi - uv.y);
         st_wt(z + (size_t)b * n + i, zz);
         acc += zz.x * zz.x + zz.y * zz.y;
     }
@@ -243,22 +267,32 @@ __global__ __launch_bounds__(NT) void k_real_to_complex(size_t count, const doub
 }  // namespace
 
 int ew_launch_minmax_normalise(qmri_ctx* ctx, int B, size_t n, int plane, int H, int s, int multi_level, double noise_std,
-                               const double2* x, const double2* u, double* mm, double* norm, int nblk, const PTensor& in32, bool mm_ready) {
-    if (!mm_ready) k_minmax<<<dim3(nblk, B), dim3(NT), 0, ctx->stream>>>(n, x, u, mm);      // (else: nblk partials per slice are in mm already, k_adj_h)
-    // (measured and removed, round 6: 2 x / 4 x as many workgroups with shorter shares -- the grid need not equal the number of min / max partials --
-    //  865 ... 873 against 870 ADMM it/s, profiles/r06_c_ab_normalise_grid_multiplier_not_kept.txt)
-    k_normalise<<<dim3(nblk, B), dim3(NT), 0, ctx->stream>>>(n, plane, H, s, multi_level, noise_std, x, u, mm, nblk, norm, in32.base1(),
-                                                             in32.hp, (int)in32.plane(), in32.batch_stride());
+                               const double2* x, const double2* u, double* mm, double* norm, int nblk, const PTensor& in32, bool mm_ready,
+                               bool complex_tsmi) {
+    auto go = [&](auto cpx) {
+        constexpr bool CPX = decltype(cpx)::value;
+        if (!mm_ready) k_minmax<CPX><<<dim3(nblk, B), dim3(NT), 0, ctx->stream>>>(n, x, u, mm);      // (else: nblk partials per slice are in mm already, k_adj_h)
+        // (measured and removed, round 6: 2 x / 4 x as many workgroups with shorter shares -- the grid need not equal the number of min / max partials --
+        //  865 ... 873 against 870 ADMM it/s, profiles/r06_c_ab_normalise_grid_multiplier_not_kept.txt)
+        k_normalise<CPX><<<dim3(nblk, B), dim3(NT), 0, ctx->stream>>>(n, plane, H, s, multi_level, noise_std, x, u, mm, nblk, norm, in32.base1(),
+                                                                      in32.hp, (int)in32.plane(), in32.batch_stride());
+    };
+    if (complex_tsmi) go(std::true_type{});
+    else go(std::false_type{});
     QMRI_HIP(ctx, hipGetLastError());
     return QMRI_OK;
 }
 
 int ew_launch_unnormalise_dual(qmri_ctx* ctx, int B, size_t n, int plane, int H, const PTensor& out32, const PTensor& in32,
                                int residual_noise, const double* norm, const double2* x, double2* u, double2* v, double2* z,
-                               double* pz, int nblk_z) {
-    k_unnormalise_dual<<<dim3(nblk_z, B), dim3(NT), 0, ctx->stream>>>(
-        n, plane, H, out32.hp, (int)out32.plane(), out32.batch_stride(), in32.batch_stride(), out32.base1(), in32.base1(), residual_noise, norm,
-        x, u, v, z, pz);
+                               double* pz, int nblk_z, int s, bool complex_tsmi) {
+    auto go = [&](auto cpx) {
+        k_unnormalise_dual<decltype(cpx)::value><<<dim3(nblk_z, B), dim3(NT), 0, ctx->stream>>>(
+            n, plane, H, s, out32.hp, (int)out32.plane(), out32.batch_stride(), in32.batch_stride(), out32.base1(), in32.base1(), residual_noise,
+            norm, x, u, v, z, pz);
+    };
+    if (complex_tsmi) go(std::true_type{});
+    else go(std::false_type{});
     QMRI_HIP(ctx, hipGetLastError());
     return QMRI_OK;
 }

@@ -447,15 +447,17 @@ int dc_launch_fwd(qmri_ctx* ctx, const OpDev& op, const LsqrDev& ls, int mode, i
                   double2* y_out, double* pdiag);
 int dc_launch_adj(qmri_ctx* ctx, const OpDev& op, int B, const double2* y_in, double2* tmp, double2* dst);
 int dc_launch_adj_h(qmri_ctx* ctx, const OpDev& op, int B, const double2* tmp, double2* dst, const double2* u = nullptr,
-                    double* mm = nullptr);   // inverse h-pass only (+ partial min / max of real(dst + u) per workgroup)
+                    double* mm = nullptr, bool mm_cpx = false);   // inverse h-pass only (+ partial min / max of real(dst + u) per workgroup;
+                                                                  //  mm_cpx: of its real and imaginary parts)
 // the step between the denoiser and the next x-update in one launch (dc_kernels.hip, k_dual_fwd_h)
 struct DualArgs {
     const float* out32; const float* in32; int php, pplane; size_t out_bs, in_bs; int residual_noise;
     const double* norm; const double2* x; double2* u; double* pz;
+    int complex_tsmi;        // v = complex(plane c, plane c + s) (QMRI_DENOISER_COMPLEX); 0: v = plane c, the reference's real TSMIs
 };
 int dc_hpass_blocks(const OpDev& op);
 // what the ADMM loop fuses into the launches around a solve (qmri_lsqr_run)
-struct LsqrFuse { int z_hpass_nblk = 0; const double2* mm_u = nullptr; double* mm = nullptr; };
+struct LsqrFuse { int z_hpass_nblk = 0; const double2* mm_u = nullptr; double* mm = nullptr; bool mm_cpx = false; };
 int dc_launch_dual_fwd_h(qmri_ctx* ctx, const OpDev& op, int B, const DualArgs& d, const ActCheckArgs& ac, double2* tmp);
 // k-space LSQR (kslsqr_kernels.hip)
 int ks_launch_init(qmri_ctx* ctx, const OpDev& op, const KsDev& ks, int B, const double2* hpass_tmp = nullptr, bool first_step = true);
@@ -474,10 +476,11 @@ int dc_launch_prepare_z(qmri_ctx* ctx, const OpDev& op, const LsqrDev& ls, int B
                         double2* z);
 // elementwise ADMM stages (PnP_ADMM.m:115-121,138,144)
 int ew_launch_minmax_normalise(qmri_ctx* ctx, int B, size_t n, int plane, int H, int s, int multi_level, double noise_std,
-                               const double2* x, const double2* u, double* mm, double* norm, int nblk, const PTensor& in32, bool mm_ready = false);
+                               const double2* x, const double2* u, double* mm, double* norm, int nblk, const PTensor& in32, bool mm_ready = false,
+                               bool complex_tsmi = false);   // complex_tsmi: 2s planes real / imaginary, noise plane 2s
 int ew_launch_unnormalise_dual(qmri_ctx* ctx, int B, size_t n, int plane, int H, const PTensor& out32, const PTensor& in32,
                                int residual_noise, const double* norm, const double2* x, double2* u, double2* v, double2* z,
-                               double* pz, int nblk_z);   // also z = v - u and the partials of ||z||^2 for the next x-update
+                               double* pz, int nblk_z, int s = 0, bool complex_tsmi = false);   // also z = v - u and the partials of ||z||^2 for the next x-update
 int ew_launch_diag(qmri_ctx* ctx, const OpDev& op, const LsqrDev& ls, int B, const double2* x, const double2* gt,
                    double* pd, double* diag_slot, int iters_total, int it);
 int ew_launch_pack(qmri_ctx* ctx, int B, int C, int H, int W, const void* src, int src_is_double, const PTensor& dst, float scale = 1.f);

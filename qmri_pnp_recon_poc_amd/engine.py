@@ -17,6 +17,17 @@ ARCH_UNETRES, ARCH_SEQ_CONV = 0, 1
 SOLVER_LSQR, SOLVER_DIRECT = 0, 1
 
 
+DENOISER_COMPLEX = 2      # include/qmri.h QMRI_DENOISER_COMPLEX
+
+
+def denoiser_type(multi_level=False, tsmi_domain="real"):
+    """qmri_admm_params.denoiser_type: bit 0 multi_level, bit 1 complex TSMIs.  tsmi_domain "real" is the reference's denoiser step
+    (v = real(x + uold)); "complex" feeds the network cat(3, real(x + uold), imag(x + uold)), 2s (+1) -> 2s channels."""
+    if tsmi_domain not in ("real", "complex"):
+        raise ValueError(f'tsmi_domain must be "real" or "complex", not {tsmi_domain!r}')
+    return int(bool(multi_level)) | (DENOISER_COMPLEX if tsmi_domain == "complex" else 0)
+
+
 class QmriError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"libqmri error {code}: {msg}")
@@ -256,9 +267,9 @@ class Engine:
         self._check(self.L.qmri_xupdate_mc(self.h, _vp(yb), _vp(zb), float(r), float(tol), int(maxit), _vp(x0b), _vp(x), C.byref(it), C.byref(fl)))
         return x.reshape((self.N, self.M, self.s), order="F"), it.value, fl.value
 
-    def pnp_admm_mc(self, y_mc, gamma=0.05, iters=100, cg_tol=1e-4, cg_maxit=100, multi_level=False, noise_std=0.01, x0=None):
+    def pnp_admm_mc(self, y_mc, gamma=0.05, iters=100, cg_tol=1e-4, cg_maxit=100, multi_level=False, noise_std=0.01, x0=None, tsmi_domain="real"):
         """Multi-coil extension: PnP_ADMM(y, param) with F replaced by the SENSE operator of set_coils.  Returns (x, lsqr_iters)."""
-        p = AdmmParams(float(gamma), int(iters), float(cg_tol), int(cg_maxit), SOLVER_LSQR, int(bool(multi_level)), float(noise_std), 0)
+        p = AdmmParams(float(gamma), int(iters), float(cg_tol), int(cg_maxit), SOLVER_LSQR, denoiser_type(multi_level, tsmi_domain), float(noise_std), 0)
         yb = _cbuf(y_mc)
         nc = getattr(self, "ncoil", 0)
         if nc and yb.size != self.m * nc:
@@ -303,12 +314,12 @@ class Engine:
         return np.stack([x[b * n:(b + 1) * n].reshape((self.N, self.M, self.s), order="F") for b in range(S)]), it, fl
 
     def pnp_admm_mc_batch(self, maps, y_mc, slices_per_launch=1, gamma=0.05, iters=100, cg_tol=1e-4, cg_maxit=100, multi_level=False, noise_std=0.01,
-                          x0=None):
+                          x0=None, tsmi_domain="real"):
         """Multi-coil PnP-ADMM of a slice stack, slices_per_launch at a time, each slice with its own maps (extension): maps [S, N, M, ncoil],
         y_mc [S, m, ncoil].  Returns (X [S, N, M, s], lsqr_iters [S, iters])."""
         S, nc, mb, yb = self._mc_stack(maps, y_mc)
         x0b = self._image_stack(x0, S)
-        p = AdmmParams(float(gamma), int(iters), float(cg_tol), int(cg_maxit), SOLVER_LSQR, int(bool(multi_level)), float(noise_std), 0)
+        p = AdmmParams(float(gamma), int(iters), float(cg_tol), int(cg_maxit), SOLVER_LSQR, denoiser_type(multi_level, tsmi_domain), float(noise_std), 0)
         n = self.N * self.M * self.s
         x = np.empty(S * n, np.complex128)
         li = np.zeros((S, max(iters, 1)), np.int32)
@@ -433,10 +444,11 @@ class Engine:
 
     # -- PnP-ADMM ------------------------------------------------------------------------------------
     def pnp_admm(self, y, gamma=0.05, iters=100, cg_tol=1e-4, cg_maxit=100, solver="lsqr", multi_level=False,
-                 noise_std=0.01, x0=None, gt=None, want_diag=False):
-        """x = PnP_ADMM(y, param)  (PnP_ADMM.m:1).  Returns (x [N,M,s] complex, diag [iters,2] or None, lsqr_iters)."""
+                 noise_std=0.01, x0=None, gt=None, want_diag=False, tsmi_domain="real"):
+        """x = PnP_ADMM(y, param)  (PnP_ADMM.m:1).  Returns (x [N,M,s] complex, diag [iters,2] or None, lsqr_iters).
+        tsmi_domain="complex": the denoiser step on cat(3, real, imag) of x + uold (a 2s (+1) -> 2s network; see denoiser_type)."""
         p = AdmmParams(float(gamma), int(iters), float(cg_tol), int(cg_maxit), SOLVER_LSQR if solver == "lsqr" else SOLVER_DIRECT,
-                       int(bool(multi_level)), float(noise_std), int(bool(want_diag)))
+                       denoiser_type(multi_level, tsmi_domain), float(noise_std), int(bool(want_diag)))
         yb = _cbuf(y)
         if yb.size != self.m:
             raise ValueError(f"y must have {self.m} elements")
@@ -452,11 +464,11 @@ class Engine:
                 diag[: 2 * iters].reshape(iters, 2) if diag is not None else None, li[:iters])
 
     def pnp_admm_batch(self, ys, slices_per_launch=15, gamma=0.05, iters=100, cg_tol=1e-4, cg_maxit=100, solver="lsqr", multi_level=False,
-                       noise_std=0.01):
+                       noise_std=0.01, tsmi_domain="real"):
         """A slice stack ys [S, m] through this context, slices_per_launch at a time (qmri_pnp_admm_batch; what `PnP_ADMM_hip(Y, param)` calls
         for a measurement matrix).  Returns (X [S,N,M,s] complex, lsqr_iters [S, iters])."""
         p = AdmmParams(float(gamma), int(iters), float(cg_tol), int(cg_maxit), SOLVER_LSQR if solver == "lsqr" else SOLVER_DIRECT,
-                       int(bool(multi_level)), float(noise_std), 0)
+                       denoiser_type(multi_level, tsmi_domain), float(noise_std), 0)
         yb = np.ascontiguousarray(np.asarray(ys, np.complex128))
         if yb.ndim != 2 or yb.shape[1] != self.m:
             raise ValueError(f"ys must be [slices, {self.m}]")

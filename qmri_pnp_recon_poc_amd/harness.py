@@ -177,6 +177,16 @@ def metrics(qmap, qmap0, foreground_mask, X=None, X0=None):
     return out
 
 
+def tsmi_from_stack(X):
+    """The stored TSMIs of the complex synthesis mode, cat(3, real(X), imag(X)) (main_synthesize_tsmis.m:100-103): N x M x 2s real ->
+    N x M x s complex (double).  Also takes a leading slice axis: [..., 2s] -> [..., s]."""
+    X = np.asarray(X)
+    if np.iscomplexobj(X) or X.ndim < 3 or X.shape[-1] % 2:
+        raise ValueError(f"a complex-mode TSMI stack is real with an even channel count (2s) along its last axis, not {X.dtype} {X.shape}")
+    s = X.shape[-1] // 2
+    return X[..., :s].astype(np.float64) + 1j * X[..., s:].astype(np.float64)
+
+
 def synthesize_tsmis(qmap, dictionary, device=0, mode="real"):
     """main_synthesize_tsmis.m:76-103 for one volume: qmap slices x 3 x N x M (the file layout, :180) -> X slices x N x M x C single.
     mode 'real' (:27,91-98): C = s, |PD| folded in, first SVD channel non-negative; mode 'complex' (:100-103): PD may be complex,
@@ -212,17 +222,21 @@ def save_training_pickle(path, X_slices, channels_to_save=None):
 def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", subsampling_pattern="Spiral",
                 spiral_sampling_curve=771, epi_sampling_rate=1 / 65, measurements_type="noisy", measurements_noise=30,
                 denoiser_type="single_level", noise_map_std=0.01, residual_noise=False, iters=100, seed=0, Y=None, device=0,
-                net_arch=None, lrtv_iters=None):
+                net_arch=None, lrtv_iters=None, tsmi_domain="real"):
     """main_recon_tsmis_FFT.m:216-374 on already loaded (and cropped) arrays.
 
     dictionary  dict(V, D, normD, lut) (load_dictionary);  X0  N x M x s ground-truth TSMI;  qmap0  N x M x 3
     weights     flat fp32 UNetRes weights, or the path of a `.pt` / `.onnx` file (weights.load_denoiser_weights); needed for PnP_ADMM
     Y           precomputed measurements (the script's save / load option, :248-262) instead of subsample + noise
     net_arch    dict(nc=..., nb=...) when `weights` is a flat blob of a non-default UNetRes (files carry their architecture)
+    tsmi_domain "complex": X0 may be complex (tsmi_from_stack turns the stored 2s-channel layout into one) and the denoiser takes 2s (+1) ->
+                2s channels, cat(3, real, imag); "real" is the reference's loop
     Returns dict(X, qmap (N x M x 3: T1, T2, PD), Y, metrics, foreground_mask).
     """
     from . import reference_api as R
     net_arch = dict(net_arch or {})
+    from .engine import denoiser_type as _dtype
+    _dtype(denoiser_type == "multi_level", tsmi_domain)            # (checks tsmi_domain)
     X0 = np.asarray(X0)
     N, M, s = X0.shape
     V = np.asarray(dictionary["V"], dtype=np.float64)
@@ -252,12 +266,15 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
         if isinstance(weights, (str, bytes)) or hasattr(weights, "__fspath__"):
             from .weights import load_denoiser_weights
             weights, arch = load_denoiser_weights(weights)
-            want = 10 if denoiser_type == "single_level" else 11
+            want = (2 * s if tsmi_domain == "complex" else 10) + (0 if denoiser_type == "single_level" else 1)
             if arch["in_nc"] != want:
-                raise ValueError(f"the weight file takes {arch['in_nc']} input channels, denoiser type {denoiser_type} needs {want}")
-        net = R.make_net(weights, denoiser_type, residual_noise, H=N, W=M, out_nc=s, device=device, **{**net_arch, **({"nc": arch["nc"], "nb": arch["nb"]} if arch else {})})
+                raise ValueError(f"the weight file takes {arch['in_nc']} input channels, denoiser type {denoiser_type} "
+                                 f"({tsmi_domain} TSMIs) needs {want}")
+        out_nc = 2 * s if tsmi_domain == "complex" else s
+        net = R.make_net(weights, denoiser_type, residual_noise, H=N, W=M, out_nc=out_nc, device=device, tsmi_domain=tsmi_domain,
+                         **{**net_arch, **({"nc": arch["nc"], "nb": arch["nb"]} if arch else {})})
         param = {"eta": 20, "sigma_squared": 1, "gamma": 1 / 20, "iter": iters, "cg_tol": 1e-4, "F": F, "gt_tsmi": X0,
-                 "X0": F.adjoint(Y), "net": net, "denoiser_type": denoiser_type,
+                 "X0": F.adjoint(Y), "net": net, "denoiser_type": denoiser_type, "tsmi_domain": tsmi_domain,
                  "noise_map": R.build_noise_map(noise_map_std, N, M)}                # :166-171
         X = R.PnP_ADMM(np.asarray(Y, dtype=np.complex128), param)
     elif recon_method == "LRTV":                                                     # :273-282

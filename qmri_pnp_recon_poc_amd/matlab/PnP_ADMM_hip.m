@@ -2,7 +2,8 @@ function [x, diag, lsqr_iters] = PnP_ADMM_hip(y, param)
 % PNP_ADMM_HIP  Drop-in for  x = PnP_ADMM(y, param)  (main_files/algorithms/PnP_ADMM/PnP_ADMM.m:1) that runs the whole
 %   loop on the GPU (one boundary crossing per reconstruction).  param.F must come from qmri_make_F and param.net from
 %   qmri_make_net; the fields read are the reference's own: iter, gamma, cg_tol, gt_tsmi, X0, denoiser_type, noise_map
-%   (PnP_ADMM.m:62-76).  Extra outputs: the two per-iteration diagnostics (PnP_ADMM.m:106-109) and the LSQR iteration counts.
+%   (PnP_ADMM.m:62-76), and param.tsmi_domain ('real', the default and the reference's; 'complex': the denoiser sees
+%   cat(3, real(x+u), imag(x+u)) and param.net must take 2s (+1) -> 2s channels).  Extra outputs: the two per-iteration diagnostics (PnP_ADMM.m:106-109) and the LSQR iteration counts.
 %
 %   y is the measurement vector of one slice (m x 1, as in the reference) or a measurement MATRIX m x S, one column per slice:
 %   the S slices then advance together through the batched kernels (15 at a time) on the current device and x is
@@ -12,6 +13,9 @@ if ~isfield(param.F, 'qmri'), error('qmri:F', 'param.F must be created by qmri_m
 p.gamma = param.gamma;  p.iter = param.iter;  p.cg_tol = param.cg_tol;
 p.multi_level = double(strcmp(param.denoiser_type, 'multi_level'));
 if p.multi_level, p.noise_std = param.noise_map(1); else, p.noise_std = 0.01; end
+tsmi_domain = 'real';  if isfield(param, 'tsmi_domain'), tsmi_domain = char(param.tsmi_domain); end
+if ~any(strcmp(tsmi_domain, {'real', 'complex'})), error('qmri:tsmi_domain', 'param.tsmi_domain must be ''real'' or ''complex'''); end
+p.complex_tsmi = double(strcmp(tsmi_domain, 'complex'));   % complex TSMIs: the denoiser sees cat(3, real, imag), 2s (+1) -> 2s channels
 g = param.F.qmri;
 if isvector(y), y = y(:); end
 gt = [];  if isfield(param, 'gt_tsmi'), gt = complex(double(param.gt_tsmi)); end

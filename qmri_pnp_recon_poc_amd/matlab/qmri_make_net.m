@@ -11,6 +11,7 @@ function net = qmri_make_net(weights, denoiser_type, residual_noise, imsize, arc
 %          [H W] = the operator's [N M] (qmri_make_F); H, W multiples of 8, H ~= W allowed.
 %   arch   (optional, only with a weight vector): struct('out_nc', 10, 'nc', [64 128 256 512], 'nb', 4) = UNetRes as trained
 %          (network_unet.py:68); the input has out_nc channels ('single_level') or out_nc + 1 ('multi_level': the noise map).
+%          For complex TSMIs (param.tsmi_domain = 'complex') out_nc is 2s: the real and imaginary planes, cat(3, real(X), imag(X)).
 if nargin < 4 || isempty(imsize), imsize = [224 224]; end
 if nargin < 5 || isempty(arch), arch = struct('out_nc', 10, 'nc', [64 128 256 512], 'nb', 4); end
 switch denoiser_type

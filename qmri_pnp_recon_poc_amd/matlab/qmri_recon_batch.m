@@ -13,6 +13,7 @@ function [X, qmap, pd] = qmri_recon_batch(Y, param, devs, slices_per_launch)
 %   out.qmap / out.pd of every slice; empty when no dictionary is set or they are not asked for).
 %   devs (default 0): device ids, an id may repeat (two workers sharing one GPU); slices_per_launch (default 15).
 %   param: the reference's fields iter, gamma, cg_tol, denoiser_type, noise_map (PnP_ADMM.m:62-76); param.F from qmri_make_F.
+%   param.tsmi_domain (optional): 'real' (default) or 'complex' -- complex TSMIs, the denoiser then takes 2s (+1) -> 2s channels.
 %   param.coils (optional, multi-coil extension with no reference counterpart): N x M x ncoil x S coil maps, one set per slice; Y is then
 %   m x ncoil x S, column (:, j, k) = F.forward(param.coils(:, :, j, k) .* X0_k) + noise.
 %   param.coil_compress (optional, with param.coils): nv, or a struct with field nv -- every launch compresses its slices to nv virtual coils on
@@ -23,6 +24,9 @@ if ~isfield(param.F, 'qmri'), error('qmri:F', 'param.F must be created by qmri_m
 p.gamma = param.gamma;  p.iter = param.iter;  p.cg_tol = param.cg_tol;
 p.multi_level = double(strcmp(param.denoiser_type, 'multi_level'));
 if p.multi_level, p.noise_std = param.noise_map(1); else, p.noise_std = 0.01; end
+tsmi_domain = 'real';  if isfield(param, 'tsmi_domain'), tsmi_domain = char(param.tsmi_domain); end
+if ~any(strcmp(tsmi_domain, {'real', 'complex'})), error('qmri:tsmi_domain', 'param.tsmi_domain must be ''real'' or ''complex'''); end
+p.complex_tsmi = double(strcmp(tsmi_domain, 'complex'));   % complex TSMIs: the denoiser sees cat(3, real, imag), 2s (+1) -> 2s channels
 g = param.F.qmri;
 tail = {};
 if isfield(param, 'coils') && ~isempty(param.coils)

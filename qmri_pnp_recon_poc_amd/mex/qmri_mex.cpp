@@ -151,6 +151,7 @@ static qmri_admm_params admm_params(const mxArray* P, bool want_diag) {
     p.cg_maxit = 100;                                               // literal in PnP_ADMM.m:102
     p.solver = (int)scalar_field(P, "solver", QMRI_SOLVER_LSQR);
     p.denoiser_type = (int)scalar_field(P, "multi_level", 0);
+    if (scalar_field(P, "complex_tsmi", 0) != 0) p.denoiser_type |= QMRI_DENOISER_COMPLEX;   // param.tsmi_domain = 'complex' 
     p.noise_std = scalar_field(P, "noise_std", 0.01);
     p.want_diag = want_diag ? 1 : 0;
     return p;

@@ -90,10 +90,15 @@ def denoiseImage_PnP_ADMM(A, net, onnx_dagnetwork=True, residual_noise=False):
 
 
 def make_net(weights, denoiser_type="single_level", residual_noise=False, H=224, W=224, nc=(64, 128, 256, 512), nb=4,
-             out_nc=10, device=0):
-    """param.net = @(x) denoiseImage_PnP_ADMM(x, Net, true, residual_noise)  (main_recon_tsmis_FFT.m:138-164)."""
+             out_nc=10, device=0, tsmi_domain="real"):
+    """param.net = @(x) denoiseImage_PnP_ADMM(x, Net, true, residual_noise)  (main_recon_tsmis_FFT.m:138-164).
+    out_nc: the network's output channels -- s for real TSMIs; tsmi_domain "complex": 2s, the cat(3, real, imag) layout of complex TSMIs."""
     if denoiser_type not in ("single_level", "multi_level"):
         raise ValueError(f"unknown denoiser_type {denoiser_type}")
+    from .engine import denoiser_type as _dtype
+    _dtype(False, tsmi_domain)                                     # (checks tsmi_domain)
+    if tsmi_domain == "complex" and out_nc % 2:
+        raise ValueError(f"a denoiser of complex TSMIs has an even number of output channels (2s), not {out_nc}")
     eng = _engine(device)
     in_nc = out_nc + (1 if denoiser_type == "multi_level" else 0)
     eng.set_denoiser(weights, H, W, in_nc=in_nc, out_nc=out_nc, nc=nc, nb=nb, residual_noise=residual_noise)
@@ -101,7 +106,7 @@ def make_net(weights, denoiser_type="single_level", residual_noise=False, H=224,
     def net(x):
         return denoiseImage_PnP_ADMM(x, net, True, residual_noise)
 
-    net._engine, net._residual_noise, net._denoiser_type = eng, bool(residual_noise), denoiser_type
+    net._engine, net._residual_noise, net._denoiser_type, net._tsmi_domain = eng, bool(residual_noise), denoiser_type, tsmi_domain
     return net
 
 
@@ -113,7 +118,8 @@ def build_noise_map(noise_std, rows, cols):
 def PnP_ADMM(y, param):
     """x = PnP_ADMM(y, param)  (PnP_ADMM.m:1).  param: dict with iter, gamma, F, cg_tol, gt_tsmi, net, denoiser_type,
     noise_map (multi_level), X0 (PnP_ADMM.m:62-76).  F and net must be the handles made by make_F / make_net on the same
-    device: the whole loop then runs on the GPU with one boundary crossing."""
+    device: the whole loop then runs on the GPU with one boundary crossing.  param["tsmi_domain"] (default: the net's, "real"):
+    "complex" runs the denoiser step on cat(3, real, imag) of x + uold."""
     F, net = param["F"], param["net"]
     if not hasattr(F, "_engine") or not hasattr(net, "_engine") or F._engine is not net._engine:
         raise TypeError("param.F and param.net must come from make_F / make_net of this package (same device)")
@@ -122,6 +128,7 @@ def PnP_ADMM(y, param):
     traj = getattr(F._P, "omega", None) is not None                 # (a trajectory computes no per-iteration diagnostics: last_diagnostics is None)
     x, diag, li = F._engine.pnp_admm(y, gamma=param["gamma"], iters=int(param["iter"]), cg_tol=param["cg_tol"], cg_maxit=100,
                                      solver=param.get("solver", "lsqr"), multi_level=multi, noise_std=noise_std,
+                                     tsmi_domain=param.get("tsmi_domain", getattr(net, "_tsmi_domain", "real")),
                                      x0=param.get("X0"), gt=None if traj else param.get("gt_tsmi"),
                                      want_diag=param.get("gt_tsmi") is not None and not traj)
     PnP_ADMM.last_diagnostics, PnP_ADMM.last_lsqr_iters = diag, li
