@@ -146,9 +146,6 @@ void qmri_free_operator(qmri_ctx* ctx) {
     o = OpHost();
 }
 
-void qmri_free_net(qmri_ctx* ctx);
-void qmri_free_dict(qmri_ctx* ctx);
-
 extern "C" int qmri_destroy(qmri_ctx* ctx) {
     if (!ctx) return QMRI_OK;
     (void)hipSetDevice(ctx->device);
@@ -269,13 +266,6 @@ OpDev qmri_opdev(const qmri_ctx* ctx) {
     d.Vt = o.d_Vt; d.ent = o.d_ent; d.perm = o.d_perm; d.kptr = o.d_kptr; d.tw_h = o.d_tw; d.tw_w = o.d_tw + o.N;
     d.kslot = o.d_kslot; d.ginv = o.d_ginv;
     return d;
-}
-
-template <typename T> static int dev_alloc(qmri_ctx* ctx, T** p, size_t count) {
-    *p = nullptr;
-    hipError_t e = hipMalloc((void**)p, std::max<size_t>(count, 1) * sizeof(T));
-    if (e != hipSuccess) { qmri_set_error(ctx, "hipMalloc of %zu bytes failed: %s", count * sizeof(T), hipGetErrorString(e)); return QMRI_ERR_NOMEM; }
-    return QMRI_OK;
 }
 
 extern "C" int qmri_set_operator(qmri_ctx* ctx, int N, int M, int s, int T, const double* V, const int32_t* frame_ptr,

@@ -62,8 +62,6 @@ template <typename T> int nu_upload(qmri_ctx* ctx, T** p, const std::vector<T>& 
 inline int wrap(int k, int G) { k %= G; return k < 0 ? k + G : k; }
 }  // namespace
 
-void qmri_free_operator(qmri_ctx* ctx);
-
 void nufft_free(NufftHost& h) {
     void* ptrs[] = {h.d_u, h.d_ph, h.d_t, h.d_perm, h.d_list, h.d_seg, h.d_red, h.d_dp, h.d_r, h.d_g, h.d_grid, h.d_part, h.d_ones};
     for (void* p : ptrs) if (p) (void)hipFree(p);

@@ -2,6 +2,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <string>
@@ -37,6 +38,45 @@ void qmri_set_error(qmri_ctx* ctx, const char* fmt, ...);
         int _s = (expr);                                                                          \
         if (_s != QMRI_OK) return _s;                                                             \
     } while (0)
+
+// ---------------------------------------------------------------------------------------------------
+// Scratch resources that live for one call: move-only owners.  The caller creates the resource into the member (hipMalloc((void**)&b.p, bytes),
+// hipEventCreateWithFlags(&e.e, ..)) and checks the status as it likes; the owner releases it on every way out of the scope.  Internal linkage: none of
+// it reaches the library's dynamic symbols.  (The long-lived members of NetPlan / OpHost / DictHost stay plain pointers that qmri_free_* release.)
+// ---------------------------------------------------------------------------------------------------
+namespace {
+template <typename T> struct DevBuf {               // hipMalloc / hipFree
+    T* p = nullptr;
+    DevBuf() = default; DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    operator T*() const { return p; }
+};
+template <typename T> struct PinnedBuf {            // hipHostMalloc / hipHostFree
+    T* p = nullptr;
+    PinnedBuf() = default; PinnedBuf(PinnedBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
+    ~PinnedBuf() { if (p) (void)hipHostFree(p); }
+    operator T*() const { return p; }
+};
+struct Event {                                      // hipEventCreate* / hipEventDestroy
+    hipEvent_t e = nullptr;
+    Event() = default; Event(Event&& o) noexcept : e(o.e) { o.e = nullptr; }
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    operator hipEvent_t() const { return e; }
+};
+struct Stream {                                     // hipStreamCreate* / hipStreamDestroy
+    hipStream_t s = nullptr;
+    Stream() = default; Stream(Stream&& o) noexcept : s(o.s) { o.s = nullptr; }
+    ~Stream() { if (s) (void)hipStreamDestroy(s); }
+    operator hipStream_t() const { return s; }
+};
+// a long-lived device array of `count` elements (at least one), with the library's message when the device is out of memory
+template <typename T> int dev_alloc(qmri_ctx* ctx, T** p, size_t count) {
+    *p = nullptr;
+    hipError_t e = hipMalloc((void**)p, std::max<size_t>(count, 1) * sizeof(T));
+    if (e != hipSuccess) { qmri_set_error(ctx, "hipMalloc of %zu bytes failed: %s", count * sizeof(T), hipGetErrorString(e)); return QMRI_ERR_NOMEM; }
+    return QMRI_OK;
+}
+}  // namespace
 
 // ---------------------------------------------------------------------------------------------------
 // A/B and diagnostic switches ("knobs").  ONE environment variable, QMRI_DEBUG="name=value,name=value" (read once per process), and
@@ -368,7 +408,7 @@ struct OpHost {
     double* d_pd = nullptr;             // diag partials
     int32_t* h_flags = nullptr;         // pinned host mirror of done flags
     LsqrState* h_state = nullptr;       // pinned
-    LsqrState* h_ring = nullptr;        // pinned [ADMM iteration][slice]: LSQR state of a reconstruction whose host never waits (api_net.cpp)
+    LsqrState* h_ring = nullptr;        // pinned [ADMM iteration][slice]: LSQR state of a reconstruction whose host never waits (api_admm.cpp)
     size_t h_ring_cap = 0;
 };
 
@@ -459,6 +499,16 @@ int dc_hpass_blocks(const OpDev& op);
 // what the ADMM loop fuses into the launches around a solve (qmri_lsqr_run)
 struct LsqrFuse { int z_hpass_nblk = 0; const double2* mm_u = nullptr; double* mm = nullptr; bool mm_cpx = false; };
 int dc_launch_dual_fwd_h(qmri_ctx* ctx, const OpDev& op, int B, const DualArgs& d, const ActCheckArgs& ac, double2* tmp);
+// host functions that cross files: api_core.cpp (operator, LSQR), api_net.cpp (denoiser; hidden: file-local until the ADMM drivers left that file), api_dict.cpp
+void qmri_free_operator(qmri_ctx* ctx);
+void qmri_free_net(qmri_ctx* ctx);
+void qmri_free_dict(qmri_ctx* ctx);
+int qmri_prepare_direct(qmri_ctx* ctx, double r);
+int qmri_lsqr_run(qmri_ctx* ctx, int B, const double2* d_z, double r, double tol, int maxit, double2* d_x,
+                  int32_t* iters_out, int32_t* flag_out, double* pdiag, LsqrState* hslot, bool* deferred, const LsqrFuse* fuse);
+__attribute__((visibility("hidden"))) int net_forward(qmri_ctx* ctx, int B);                       // in32 -> out32 on the context's padded tensors
+__attribute__((visibility("hidden"))) int net_range_tripped(qmri_ctx* ctx, bool& tripped);         // after a synchronisation: a guard of the f16 scheme / the resident launch asks for a repeat
+__attribute__((visibility("hidden"))) bool host_range_tripped(const NetPlan& p);                   // ... the same question from the pinned host words, without a copy
 // k-space LSQR (kslsqr_kernels.hip)
 int ks_launch_init(qmri_ctx* ctx, const OpDev& op, const KsDev& ks, int B, const double2* hpass_tmp = nullptr, bool first_step = true);
 int ks_launch_iter(qmri_ctx* ctx, const OpDev& op, const KsDev& ks, int B);
