@@ -124,6 +124,16 @@ typedef struct {
 } qmri_nufft_params;
 int qmri_set_operator_nufft(qmri_ctx* ctx, int N, int M, int s, int T, const double* V, const int32_t* frame_ptr, const double* omega,
                             int max_batch, const qmri_nufft_params* p);
+/* The normal operator A^H A of a trajectory operator as a block-Toeplitz convolution: out = A^H A x without a gather, by a
+ * zero-padded 2N x 2M FFT against the transform of the s x s point-spread function.  qmri_nufft_prepare_normal builds that transform (once per
+ * trajectory, s (s + 1) / 2 * 4 N M complex doubles on the device, with the kernel width of the operator's qmri_nufft_params); it is idempotent, the
+ * first call that needs the transform builds it too, and replacing the operator drops it.  qmri_normal: host buffers, x as qmri_forward takes it,
+ * out N*M*s complex.  qmri_normal_dev: device buffers [batch][N*M*s], batch <= max_batch, out may be x; a slice's result is the same bits alone and at
+ * any position of any batch.  Agrees with qmri_adjoint(qmri_forward(x)) to about twice the NUFFT's own error.  On a gridded operator all three return
+ * QMRI_ERR_UNSUPPORTED (there qmri_adjoint(qmri_forward(x)) is the route). */
+int qmri_nufft_prepare_normal(qmri_ctx* ctx);
+int qmri_normal(qmri_ctx* ctx, const void* x, int x_is_complex, void* out);
+int qmri_normal_dev(qmri_ctx* ctx, const void* d_x, void* d_out, int batch);
 /* On a trajectory operator these work unchanged: qmri_forward / _adjoint (and _f32, _dev), qmri_operator_m, qmri_set_coils, qmri_forward_mc /
  * _adjoint_mc, qmri_xupdate_mc(_batch), qmri_pnp_admm_mc(_batch, _dev), qmri_coil_compress*, and qmri_xupdate / qmri_pnp_admm (one slice, LSQR,
  * no diagnostics) as the image-domain LSQR with one unit coil -- bit for bit the qmri_*_mc call with that coil.  Everything else that needs the
@@ -167,7 +177,14 @@ int qmri_net_forward_dev(qmri_ctx* ctx, const float* d_in, int B, float* d_out);
 int qmri_denoiser_scheme(const qmri_ctx* ctx, int* scheme_out, int* fallbacks_out);
 
 /* ---- PnP-ADMM: x = PnP_ADMM(y, param), PnP_ADMM.m:1 ----------------------------------------------- */
-enum { QMRI_SOLVER_LSQR = 0, QMRI_SOLVER_DIRECT = 1 };
+enum { QMRI_SOLVER_LSQR = 0, QMRI_SOLVER_DIRECT = 1, QMRI_SOLVER_TOEPLITZ = 2 };
+/* QMRI_SOLVER_TOEPLITZ: an EXTENSION for trajectory operators (qmri_set_operator_nufft), parity unpinned.  The x-update is solved by plain conjugate
+ * gradients on the normal equations (A^H A + r I) x = A^H y + r z (with coils: A_mc), A^H A applied as qmri_normal applies it, warm-started from x.
+ * Stop rule: the first k with || b - (A^H A + r I) x_k ||_2 <= cg_tol * || b ||_2, b the right-hand side and the residual that of the CG recurrence:
+ * flag 0 and k iterations reported; flag 1 when cg_maxit is reached first (cg_maxit = 0 returns x0); flag 3 on a breakdown (p^H (A^H A + r I) p not
+ * positive: non-finite data).  The reference's lsqr stops on a different quantity, so the iterates of the two solvers at tol = 1e-4 differ at the 1e-4
+ * level; both converge to the same minimiser.  Accepted by qmri_xupdate, qmri_pnp_admm (one slice), qmri_pnp_admm_mc(_batch, _dev) and
+ * qmri_recon_batch_mc* on a trajectory operator; on a gridded operator QMRI_ERR_UNSUPPORTED (use QMRI_SOLVER_LSQR there).  LSQR stays the default. */
 /* denoiser_type is a set of bits: 0 single_level, 1 multi_level, 2 complex single_level, 3 complex multi_level; any other value is
  * QMRI_ERR_INVALID_ARG.  QMRI_DENOISER_COMPLEX (complex TSMIs; the reference's TSMIs are real, PnP_ADMM.m:115-118) changes Step 2 only:
  *   v = x + uold ; V = cat(3, real(v), imag(v))        N x M x 2s, planes 0..s-1 real, s..2s-1 imaginary
@@ -183,7 +200,7 @@ typedef struct {
     int32_t iters;           /* param.iter = 100                          :288 */
     double cg_tol;           /* param.cg_tol = 1e-4                       :289 */
     int32_t cg_maxit;        /* 100 (literal in PnP_ADMM.m:102) */
-    int32_t solver;          /* QMRI_SOLVER_LSQR reproduces the reference; DIRECT is the exact minimiser */
+    int32_t solver;          /* QMRI_SOLVER_LSQR reproduces the reference; DIRECT is the exact minimiser; TOEPLITZ: trajectories (above) */
     int32_t denoiser_type;   /* param.denoiser_type                       :167  (| QMRI_DENOISER_COMPLEX: complex TSMIs, see above) */
     double noise_std;        /* build_noise_map(0.01,...)                 :76,:170 */
     int32_t want_diag;       /* the two per-iteration diagnostics of PnP_ADMM.m:106-109 */

@@ -17,7 +17,7 @@ CSRC = os.path.join(_PKG, "csrc")
 # every symbol include/qmri.h declares (checked at load time and by tests/test_abi.py)
 SYMBOLS = [
     "qmri_abi_version", "qmri_create", "qmri_destroy", "qmri_last_error", "qmri_set_stream", "qmri_synchronize",
-    "qmri_build_spiral", "qmri_build_epi", "qmri_build_spiral_traj", "qmri_set_operator", "qmri_set_operator_nufft", "qmri_operator_m", "qmri_forward", "qmri_adjoint",
+    "qmri_build_spiral", "qmri_build_epi", "qmri_build_spiral_traj", "qmri_set_operator", "qmri_set_operator_nufft", "qmri_nufft_prepare_normal", "qmri_normal", "qmri_normal_dev", "qmri_operator_m", "qmri_forward", "qmri_adjoint",
     "qmri_forward_f32", "qmri_adjoint_f32", "qmri_forward_dev", "qmri_adjoint_dev", "qmri_set_coils", "qmri_forward_mc", "qmri_adjoint_mc", "qmri_xupdate_mc", "qmri_pnp_admm_mc", "qmri_xupdate_mc_batch", "qmri_pnp_admm_mc_batch", "qmri_pnp_admm_mc_dev", "qmri_xupdate", "qmri_net_nparams", "qmri_set_denoiser", "qmri_denoise",
     "qmri_net_forward_dev", "qmri_denoiser_scheme", "qmri_pnp_admm", "qmri_pnp_admm_dev", "qmri_pnp_admm_batch", "qmri_set_dictionary", "qmri_dict_match",
     "qmri_dict_match_dev", "qmri_dict_match_xfit", "qmri_dict_match_xfit_dev", "qmri_recon_batch", "qmri_recon_batch_mc",
@@ -120,6 +120,9 @@ def lib() -> C.CDLL:
     L.qmri_set_operator.argtypes = [vp, i, i, i, i, dp, ip, ip, i]
     L.qmri_build_spiral_traj.argtypes = [vp, i, i, i, ip, dp, i, C.POINTER(i)]
     L.qmri_set_operator_nufft.argtypes = [vp, i, i, i, i, dp, ip, dp, i, C.POINTER(NufftParams)]
+    L.qmri_nufft_prepare_normal.argtypes = [vp]
+    L.qmri_normal.argtypes = [vp, vp, i, vp]
+    L.qmri_normal_dev.argtypes = [vp, vp, vp, i]
     L.qmri_operator_m.argtypes = [vp, C.POINTER(i)]
     L.qmri_forward.argtypes = [vp, vp, i, vp]
     L.qmri_adjoint.argtypes = [vp, vp, vp]

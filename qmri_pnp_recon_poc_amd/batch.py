@@ -56,7 +56,7 @@ def recon_batch(devices, Y, N, M, V, frame_ptr, kidx, weights, in_nc=10, out_nc=
         cm, Yc = np.asarray(coil_maps), np.asarray(Y)
         if cm.ndim != 4 or cm.shape[1:3] != (N, M) or Yc.ndim != 3 or Yc.shape[0] != cm.shape[0] or Yc.shape[2] != cm.shape[3]:
             raise ValueError("coil_maps must be [nslices, N, M, ncoil] and Y [nslices, m, ncoil]")
-        if solver != "lsqr":
+        if solver != "lsqr":                                           # (the workers plan gridded masks only: no trajectory for "toeplitz" to run on)
             raise ValueError("the multi-coil reconstruction uses the LSQR solver")
         ncoil = int(cm.shape[3])
         Mb = np.ascontiguousarray(np.concatenate([_cbuf(cm[b]) for b in range(cm.shape[0])]))

@@ -147,7 +147,9 @@ static int mc_admm_check(qmri_ctx* ctx, const qmri_admm_params* prm) {
     const NetPlan& net = ctx->net;
     if (!net.ready) { qmri_set_error(ctx, "denoiser not set: call qmri_set_denoiser first"); return QMRI_ERR_STATE; }
     QMRI_CHECK_ARG(ctx, prm, "params must not be NULL");
-    QMRI_CHECK_ARG(ctx, prm->iters >= 0 && prm->gamma > 0 && prm->cg_maxit >= 0 && prm->solver == QMRI_SOLVER_LSQR, "iters >= 0, gamma > 0, cg_maxit >= 0, LSQR solver required");
+    QMRI_TRY(toep_check_solver(ctx, prm->solver));            // (QMRI_SOLVER_TOEPLITZ: a trajectory operator only)
+    QMRI_CHECK_ARG(ctx, prm->iters >= 0 && prm->gamma > 0 && prm->cg_maxit >= 0 && (prm->solver == QMRI_SOLVER_LSQR || prm->solver == QMRI_SOLVER_TOEPLITZ),
+                   "iters >= 0, gamma > 0, cg_maxit >= 0, LSQR solver required");
     int multi = 0;
     bool cpx = false;
     return admm_net_fits(ctx, prm, &multi, &cpx);
@@ -168,7 +170,7 @@ static int mc_admm_group(qmri_ctx* ctx, int B, int ncoil, const double2* d_maps,
         QMRI_TRY(admm_start(ctx, B, d_x, true));                  // v = x, uold = 0, z = v - uold
         bool again = false;
         for (int it = 0; it < prm->iters; ++it) {
-            QMRI_TRY(qmri_lsqr_mc_batch_dev(ctx, B, ncoil, d_maps, d_y, o.d_z, prm->gamma, prm->cg_tol, prm->cg_maxit, d_x, li.data(), nullptr));   // :102
+            QMRI_TRY(mc_xupdate_dev(ctx, prm->solver, B, ncoil, d_maps, d_y, o.d_z, prm->gamma, prm->cg_tol, prm->cg_maxit, d_x, li.data(), nullptr));   // :102
             if (li_out) for (int b = 0; b < B; ++b) li_out[(size_t)b * li_stride + it] = li[b];
             QMRI_TRY(admm_denoiser_step(ctx, {B, prm, multi, cpx, d_x, nullptr}, false));                                                           // :115-144
             QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -219,7 +221,7 @@ static int pnp_admm_nufft(qmri_ctx* ctx, int nslices, const void* d_y, const qmr
                             "one at a time, or as a stack with qmri_pnp_admm_mc_batch and one unit coil per slice", nslices);
         return QMRI_ERR_UNSUPPORTED;
     }
-    if (prm && prm->solver != QMRI_SOLVER_LSQR) {
+    if (prm && prm->solver != QMRI_SOLVER_LSQR && prm->solver != QMRI_SOLVER_TOEPLITZ) {
         qmri_set_error(ctx, "the DIRECT solver is not available on a trajectory operator (qmri_set_operator_nufft): its closed form needs a gridded "
                             "mask; use QMRI_SOLVER_LSQR");
         return QMRI_ERR_UNSUPPORTED;
@@ -269,6 +271,7 @@ static int pnp_admm_dev_impl(qmri_ctx* ctx, int nslices, const void* d_y, const 
         if (d_x0) { QMRI_TRY(dc_launch_adj(ctx, op, B, y, o.d_tmp, o.d_xa)); aty = o.d_xa; }
         QMRI_TRY(dc_launch_fwd(ctx, op, o.ls, DC_SPECTRUM, B, aty, o.d_tmp, o.d_chat, nullptr));
     } else if (prm->solver != QMRI_SOLVER_LSQR) {
+        QMRI_TRY(toep_check_solver(ctx, prm->solver));
         qmri_set_error(ctx, "unknown solver %d", prm->solver);
         return QMRI_ERR_INVALID_ARG;
     }

@@ -826,7 +826,7 @@ extern "C" int qmri_xupdate(qmri_ctx* ctx, const void* y, const void* z, double 
     if (o.kind == OP_NUFFT) {
         // a trajectory: A^H A is not block-diagonal in k-space, so the k-space LSQR does not apply -- the image-domain LSQR with one unit coil,
         // staged as qmri_xupdate_mc stages it (the same bits as that call with the unit map)
-        if (solver != QMRI_SOLVER_LSQR) {
+        if (solver != QMRI_SOLVER_LSQR && solver != QMRI_SOLVER_TOEPLITZ) {
             qmri_set_error(ctx, "the DIRECT solver is not available on a trajectory operator (qmri_set_operator_nufft): its closed form needs a gridded "
                                 "mask; use QMRI_SOLVER_LSQR");
             return QMRI_ERR_UNSUPPORTED;
@@ -837,7 +837,7 @@ extern "C" int qmri_xupdate(qmri_ctx* ctx, const void* y, const void* z, double 
         QMRI_HIP(ctx, hipMemcpyAsync(w.sy, y, (size_t)o.m * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
         QMRI_HIP(ctx, hipMemcpyAsync(w.sz, z, n * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
         QMRI_HIP(ctx, hipMemcpyAsync(w.sx, x, n * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
-        QMRI_TRY(qmri_lsqr_mc_batch_dev(ctx, 1, 1, o.nu.d_ones, w.sy, w.sz, r, tol, maxit, w.sx, iters_out, flag_out));
+        QMRI_TRY(mc_xupdate_dev(ctx, solver, 1, 1, o.nu.d_ones, w.sy, w.sz, r, tol, maxit, w.sx, iters_out, flag_out));
         QMRI_HIP(ctx, hipMemcpyAsync(x, w.sx, n * sizeof(double2), hipMemcpyDeviceToHost, ctx->stream));
         QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
         return QMRI_OK;
@@ -862,6 +862,7 @@ extern "C" int qmri_xupdate(qmri_ctx* ctx, const void* y, const void* z, double 
         if (iters_out) *iters_out = 0;
         if (flag_out) *flag_out = 0;
     } else {
+        QMRI_TRY(toep_check_solver(ctx, solver));
         qmri_set_error(ctx, "unknown solver %d", solver);
         return QMRI_ERR_INVALID_ARG;
     }

@@ -318,6 +318,22 @@ void mc_free_work(McWork& w) {
     w = McWork();
 }
 
+int mc_launch_coil_mul(qmri_ctx* ctx, int ncoil, int g0, int cnt, const double2* x, const double2* maps, const LsqrState* st, double2* out) {
+    const OpHost& o = ctx->op;
+    const size_t n = (size_t)o.N * o.M * o.s, plane = (size_t)o.N * o.M;
+    k_mcl_coil_mul<<<dim3(blocks_of(n), cnt), dim3(NT), 0, ctx->stream>>>(n, plane, ncoil, g0, x, maps, st, out);
+    QMRI_HIP(ctx, hipGetLastError());
+    return QMRI_OK;
+}
+int mc_launch_coil_sum(qmri_ctx* ctx, int ncoil, int g0, int cnt, const double2* xj, const double2* maps, const LsqrState* st, double2* t) {
+    const OpHost& o = ctx->op;
+    const size_t n = (size_t)o.N * o.M * o.s, plane = (size_t)o.N * o.M;
+    const int nb = (g0 + cnt - 1) / ncoil - g0 / ncoil + 1;
+    k_mcl_coil_sum<<<dim3(blocks_of(n), nb), dim3(NT), 0, ctx->stream>>>(n, plane, ncoil, g0, cnt, xj, maps, st, t);
+    QMRI_HIP(ctx, hipGetLastError());
+    return QMRI_OK;
+}
+
 // work buffers of a B-slice, ncoil-coil solve: allocated on first use, grown only when B or B x ncoil grows (qmri_free_operator frees them)
 int mc_ensure_work(qmri_ctx* ctx, int B, int ncoil) {
     OpHost& o = ctx->op;

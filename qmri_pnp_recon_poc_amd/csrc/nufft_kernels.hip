@@ -29,6 +29,8 @@ __device__ __forceinline__ int nu_k0(double u, double hw) { return (int)ceil(u -
 __device__ __forceinline__ int nu_wrap(int k, int G) { k %= G; return k < 0 ? k + G : k; }
 
 // x [B][c][n2][n1] -> g [B][a][c][q2][q1], a = a1 + 2 a2, q = (n + N/2) mod N
+// DEAPOD = false: the ramps alone, without 1 / Phi -- the zero-padded 2N x 2M DFT of the Toeplitz normal operator (toep_kernels.hip, "k_toep_pre")
+template <bool DEAPOD>
 __global__ __launch_bounds__(NT) void k_nu_pre(NufftDev nu, const double2* __restrict__ x, double2* __restrict__ g) {
     const int N = nu.N, M = nu.M, b = blockIdx.y;
     const size_t plane = (size_t)N * M, n = plane * nu.s;
@@ -36,8 +38,8 @@ __global__ __launch_bounds__(NT) void k_nu_pre(NufftDev nu, const double2* __res
     if (i >= n) return;
     const int c = (int)(i / plane), r = (int)(i - (size_t)c * plane), n2 = r / N, n1 = r - n2 * N;
     const double2 v = x[(size_t)b * n + i];
-    const double sc = nu.dp1[n1] * nu.dp2[n2];
-    const double2 x0 = make_double2(v.x * sc, v.y * sc);
+    const double sc = DEAPOD ? nu.dp1[n1] * nu.dp2[n2] : 1.0;
+    const double2 x0 = DEAPOD ? make_double2(v.x * sc, v.y * sc) : v;
     const double2 e1 = nu.r1[n1], e2 = nu.r2[n2];
     const double2 x1 = make_double2(x0.x * e1.x - x0.y * e1.y, x0.x * e1.y + x0.y * e1.x);
     const double2 x2 = make_double2(x0.x * e2.x - x0.y * e2.y, x0.x * e2.y + x0.y * e2.x);
@@ -195,6 +197,8 @@ __global__ __launch_bounds__(NT) void k_nu_adj_w(OpDev op, const double2* __rest
 }
 
 // images of the 4 sub-grids [B][a][c][q2][q1] -> x [B][c][n2][n1]: sum over a = 0..3 in order of conj(ramp_a) * g_a, times 1 / Phi(p)
+// DEAPOD = false: without 1 / Phi -- the crop of the 2N x 2M inverse DFT (toep_kernels.hip, "k_toep_post")
+template <bool DEAPOD>
 __global__ __launch_bounds__(NT) void k_nu_post(NufftDev nu, const double2* __restrict__ g, double2* __restrict__ x) {
     const int N = nu.N, M = nu.M, b = blockIdx.y;
     const size_t plane = (size_t)N * M, n = plane * nu.s;
@@ -210,9 +214,13 @@ __global__ __launch_bounds__(NT) void k_nu_post(NufftDev nu, const double2* __re
     const double2 h2 = make_double2(g2.x * e2.x + g2.y * e2.y, g2.y * e2.x - g2.x * e2.y);
     const double2 t3 = make_double2(g3.x * e1.x + g3.y * e1.y, g3.y * e1.x - g3.x * e1.y);
     const double2 h3 = make_double2(t3.x * e2.x + t3.y * e2.y, t3.y * e2.x - t3.x * e2.y);
-    const double sc = nu.dp1[n1] * nu.dp2[n2];
     const double re = ((g0.x + h1.x) + h2.x) + h3.x, im = ((g0.y + h1.y) + h2.y) + h3.y;
-    x[(size_t)b * n + i] = make_double2(re * sc, im * sc);
+    if (DEAPOD) {
+        const double sc = nu.dp1[n1] * nu.dp2[n2];
+        x[(size_t)b * n + i] = make_double2(re * sc, im * sc);
+    } else {
+        x[(size_t)b * n + i] = make_double2(re, im);
+    }
 }
 
 template <int R1, int R2>
@@ -254,13 +262,31 @@ int launch_interp(qmri_ctx* ctx, const NufftDev& nu, int B, const double2* S, do
 
 bool nufft_kernel_ok(int w) { return w >= 2 && w <= NU_WMAX; }
 
+NufftDev nufft_dev_view(const qmri_ctx* ctx) { return nufft_dev(ctx); }
+
+// the half-bin ramps of k_nu_pre / k_nu_post without the deapodisation: x [B][n] -> g [B][4][n] and back (toep_kernels.hip)
+int nufft_launch_ramps(qmri_ctx* ctx, int B, const double2* x, double2* g) {
+    const OpHost& o = ctx->op;
+    const size_t n = (size_t)o.N * o.M * o.s;
+    k_nu_pre<false><<<dim3((unsigned)((n + NT - 1) / NT), B), dim3(NT), 0, ctx->stream>>>(nufft_dev(ctx), x, g);
+    QMRI_HIP(ctx, hipGetLastError());
+    return QMRI_OK;
+}
+int nufft_launch_unramps(qmri_ctx* ctx, int B, const double2* g, double2* x) {
+    const OpHost& o = ctx->op;
+    const size_t n = (size_t)o.N * o.M * o.s;
+    k_nu_post<false><<<dim3((unsigned)((n + NT - 1) / NT), B), dim3(NT), 0, ctx->stream>>>(nufft_dev(ctx), g, x);
+    QMRI_HIP(ctx, hipGetLastError());
+    return QMRI_OK;
+}
+
 int nufft_launch_fwd(qmri_ctx* ctx, int B, const double2* x, double2* y) {
     OpHost& o = ctx->op;
     if (o.kind != OP_NUFFT || B < 1 || B > o.maxB) { qmri_set_error(ctx, "nufft_launch_fwd: no trajectory operator / batch out of range (internal)"); return QMRI_ERR_STATE; }
     const NufftDev nu = nufft_dev(ctx);
     const OpDev op = qmri_opdev(ctx);
     const size_t n = (size_t)o.N * o.M * o.s;
-    k_nu_pre<<<dim3((unsigned)((n + NT - 1) / NT), B), dim3(NT), 0, ctx->stream>>>(nu, x, o.nu.d_g);
+    k_nu_pre<true><<<dim3((unsigned)((n + NT - 1) / NT), B), dim3(NT), 0, ctx->stream>>>(nu, x, o.nu.d_g);
     QMRI_HIP(ctx, hipGetLastError());
     // the 4 sub-grids of every slice as 4B slices through the dense spectrum passes (d_grid as their workspace, the spectra back into d_g)
     QMRI_TRY(dc_launch_fwd(ctx, op, o.ls, DC_SPECTRUM, 4 * B, o.nu.d_g, o.nu.d_grid, o.nu.d_g, nullptr));
@@ -283,7 +309,7 @@ int nufft_launch_adj(qmri_ctx* ctx, int B, const double2* y, double2* x) {
     }
     QMRI_TRY(with_plan(ctx, op.M, [&](auto p) { return launch_adj_w_t<decltype(p)::R1, decltype(p)::R2>(ctx, op, 4 * B, o.nu.d_grid, o.nu.d_g); }));
     QMRI_TRY(dc_launch_adj_h(ctx, op, 4 * B, o.nu.d_g, o.nu.d_grid));
-    k_nu_post<<<dim3((unsigned)((n + NT - 1) / NT), B), dim3(NT), 0, ctx->stream>>>(nu, o.nu.d_grid, x);
+    k_nu_post<true><<<dim3((unsigned)((n + NT - 1) / NT), B), dim3(NT), 0, ctx->stream>>>(nu, o.nu.d_grid, x);
     QMRI_HIP(ctx, hipGetLastError());
     return QMRI_OK;
 }

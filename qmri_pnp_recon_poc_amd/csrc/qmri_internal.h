@@ -301,6 +301,7 @@ struct McWork {
     LsqrState* hst = nullptr;           // [B] pinned: iter / done / flag written by the kernel that changes them
     size_t cap_sl = 0, cap_img = 0;
     int pred = 8;                       // iterations enqueued before the first event wait after the initial step (the last solve's count + 1)
+    int pred_cg = 8;                    // ... of the Toeplitz CG (toep_kernels.hip)
     // staging of the host-array entry points: maps [B][ncoil][N*M], y [B][ncoil][m], x and z (or x0) [B][n]
     double2 *sm = nullptr, *sy = nullptr, *sx = nullptr, *sz = nullptr;
     size_t stage_sl = 0, stage_img = 0;
@@ -308,6 +309,10 @@ struct McWork {
 void mc_free_work(McWork& w);
 int mc_ensure_staging(qmri_ctx* ctx, int B, int ncoil);
 int mc_adjoint_batch_dev(qmri_ctx* ctx, int B, int ncoil, const double2* d_maps, const double2* d_y, double2* d_x);
+int mc_ensure_work(qmri_ctx* ctx, int B, int ncoil);
+// the coil products of a transform chunk (coil images g0 .. g0 + cnt - 1 of [B][ncoil]); st (nullable): slices whose solve has stopped are skipped
+int mc_launch_coil_mul(qmri_ctx* ctx, int ncoil, int g0, int cnt, const double2* x, const double2* maps, const LsqrState* st, double2* out);
+int mc_launch_coil_sum(qmri_ctx* ctx, int ncoil, int g0, int cnt, const double2* xj, const double2* maps, const LsqrState* st, double2* t);
 int qmri_lsqr_mc_batch_dev(qmri_ctx* ctx, int B, int ncoil, const double2* d_maps, const double2* d_y, const double2* d_z, double r, double tol, int maxit,
                            double2* d_x, int32_t* iters_out, int32_t* flags_out);
 
@@ -364,6 +369,10 @@ struct NufftHost {
     double2* d_ones = nullptr;                   // [N*M] the unit coil of qmri_xupdate / qmri_pnp_admm on a trajectory
     int w = 0, nseg = 0, nred = 0, nslot = 0;
     double beta = 0.0;
+    // Toeplitz normal operator (toep_kernels.hip): the 2N x 2M DFT of the s x s point-spread function of A^H A, times 1/4,
+    // Hermitian-packed: [pair (c <= c') = c' (c' + 1) / 2 + c][a][j1][j2], bin (2 j1 + a1, 2 j2 + a2).  Built by toep_prepare, freed by nufft_free.
+    double2* d_khat = nullptr;
+    bool khat_ready = false;
 };
 // the exponential spiral of setup_subsampling_spiralgrided.m:7-27 before rounding (shared by qmri_build_spiral and qmri_build_spiral_traj): S angles
 // theta_j and radii r_j normalised to [0, 1]; frame f is rotated by f * SPIRAL_DELTA
@@ -374,6 +383,18 @@ int nufft_launch_adj(qmri_ctx* ctx, int B, const double2* y, double2* x);    // 
 int nufft_check_gridded(qmri_ctx* ctx, const char* what, const char* instead);   // QMRI_ERR_UNSUPPORTED on a trajectory operator, else QMRI_OK
 void nufft_free(NufftHost& h);
 bool nufft_kernel_ok(int w);
+NufftDev nufft_dev_view(const qmri_ctx* ctx);
+int nufft_launch_ramps(qmri_ctx* ctx, int B, const double2* x, double2* g);      // k_nu_pre without 1 / Phi:  x [B][n] -> g [B][4][n]
+int nufft_launch_unramps(qmri_ctx* ctx, int B, const double2* g, double2* x);    // k_nu_post without 1 / Phi
+// Toeplitz normal operator of a trajectory (toep_kernels.hip, api_toep.cpp)
+int toep_prepare(qmri_ctx* ctx);                                                  // builds K^ once per trajectory (idempotent)
+int toep_apply(qmri_ctx* ctx, int B, const double2* x, double2* out);             // out [B][n] = A^H A x [B][n], B <= max_batch; out may be x
+int qmri_cg_toep_batch_dev(qmri_ctx* ctx, int B, int ncoil, const double2* d_maps, const double2* d_y, const double2* d_z, double r, double tol, int maxit,
+                           double2* d_x, int32_t* iters_out, int32_t* flags_out);  // the call shape of qmri_lsqr_mc_batch_dev
+// the x-update of the multi-coil loops by the solver of qmri_admm_params (LSQR or TOEPLITZ)
+int mc_xupdate_dev(qmri_ctx* ctx, int solver, int B, int ncoil, const double2* d_maps, const double2* d_y, const double2* d_z, double r, double tol, int maxit,
+                   double2* d_x, int32_t* iters_out, int32_t* flags_out);
+int toep_check_solver(qmri_ctx* ctx, int solver);   // QMRI_SOLVER_TOEPLITZ without an operator: QMRI_ERR_STATE, on a gridded one: QMRI_ERR_UNSUPPORTED; else QMRI_OK
 
 // ---------------------------------------------------------------------------------------------------
 // context

@@ -28,10 +28,25 @@ def denoiser_type(multi_level=False, tsmi_domain="real"):
     return int(bool(multi_level)) | (DENOISER_COMPLEX if tsmi_domain == "complex" else 0)
 
 
+SOLVER_TOEPLITZ = 2       # include/qmri.h QMRI_SOLVER_TOEPLITZ
+
+
+def solver_code(solver):
+    """qmri_admm_params.solver: "lsqr" the reference's, "toeplitz" CG on the Toeplitz normal operator of a trajectory (DESIGN.md section 16);
+    any other string is the DIRECT solver, as before."""
+    return SOLVER_LSQR if solver == "lsqr" else SOLVER_TOEPLITZ if solver == "toeplitz" else SOLVER_DIRECT
+
+
 class QmriError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"libqmri error {code}: {msg}")
         self.code = code
+
+
+def _mc_solver(solver):
+    if solver not in ("lsqr", "toeplitz"):
+        raise ValueError('the multi-coil reconstruction takes solver="lsqr" or "toeplitz"')
+    return solver_code(solver)
 
 
 def _vp(a):
@@ -204,6 +219,24 @@ class Engine:
             self._check(self.L.qmri_forward(self.h, _vp(xb), 0, _vp(y)))
         return y
 
+    def prepare_normal(self):
+        """Build the Toeplitz normal operator of the trajectory now (qmri_nufft_prepare_normal) instead of on the first call that needs it."""
+        self._check(self.L.qmri_nufft_prepare_normal(self.h))
+
+    def normal(self, x):
+        """A^H A x of a trajectory operator without a gather (qmri_normal).  x: [N,M,s] real or complex -> complex128."""
+        x = np.asarray(x)
+        if x.shape != (self.N, self.M, self.s):
+            raise ValueError(f"x must be {self.N}x{self.M}x{self.s}")
+        out = np.empty(self.N * self.M * self.s, np.complex128)
+        if np.iscomplexobj(x):
+            xb = _cbuf(x)
+            self._check(self.L.qmri_normal(self.h, _vp(xb), 1, _vp(out)))
+        else:
+            xb = np.ascontiguousarray(np.asarray(x, dtype=np.float64).ravel(order="F"))
+            self._check(self.L.qmri_normal(self.h, _vp(xb), 0, _vp(out)))
+        return out.reshape((self.N, self.M, self.s), order="F")
+
     def adjoint(self, y):
         """x = F.adjoint(y)  (main_recon_tsmis_FFT.m:229); complex64 in -> complex64 out (the _f32 entry point)."""
         if np.asarray(y).dtype == np.complex64:
@@ -267,9 +300,11 @@ class Engine:
         self._check(self.L.qmri_xupdate_mc(self.h, _vp(yb), _vp(zb), float(r), float(tol), int(maxit), _vp(x0b), _vp(x), C.byref(it), C.byref(fl)))
         return x.reshape((self.N, self.M, self.s), order="F"), it.value, fl.value
 
-    def pnp_admm_mc(self, y_mc, gamma=0.05, iters=100, cg_tol=1e-4, cg_maxit=100, multi_level=False, noise_std=0.01, x0=None, tsmi_domain="real"):
-        """Multi-coil extension: PnP_ADMM(y, param) with F replaced by the SENSE operator of set_coils.  Returns (x, lsqr_iters)."""
-        p = AdmmParams(float(gamma), int(iters), float(cg_tol), int(cg_maxit), SOLVER_LSQR, denoiser_type(multi_level, tsmi_domain), float(noise_std), 0)
+    def pnp_admm_mc(self, y_mc, gamma=0.05, iters=100, cg_tol=1e-4, cg_maxit=100, multi_level=False, noise_std=0.01, x0=None, tsmi_domain="real",
+                    solver="lsqr"):
+        """Multi-coil extension: PnP_ADMM(y, param) with F replaced by the SENSE operator of set_coils.  Returns (x, lsqr_iters).
+        solver: "lsqr", or "toeplitz" on a trajectory operator."""
+        p = AdmmParams(float(gamma), int(iters), float(cg_tol), int(cg_maxit), _mc_solver(solver), denoiser_type(multi_level, tsmi_domain), float(noise_std), 0)
         yb = _cbuf(y_mc)
         nc = getattr(self, "ncoil", 0)
         if nc and yb.size != self.m * nc:
@@ -314,12 +349,12 @@ class Engine:
         return np.stack([x[b * n:(b + 1) * n].reshape((self.N, self.M, self.s), order="F") for b in range(S)]), it, fl
 
     def pnp_admm_mc_batch(self, maps, y_mc, slices_per_launch=1, gamma=0.05, iters=100, cg_tol=1e-4, cg_maxit=100, multi_level=False, noise_std=0.01,
-                          x0=None, tsmi_domain="real"):
+                          x0=None, tsmi_domain="real", solver="lsqr"):
         """Multi-coil PnP-ADMM of a slice stack, slices_per_launch at a time, each slice with its own maps (extension): maps [S, N, M, ncoil],
-        y_mc [S, m, ncoil].  Returns (X [S, N, M, s], lsqr_iters [S, iters])."""
+        y_mc [S, m, ncoil].  Returns (X [S, N, M, s], lsqr_iters [S, iters]).  solver: "lsqr", or "toeplitz" on a trajectory operator."""
         S, nc, mb, yb = self._mc_stack(maps, y_mc)
         x0b = self._image_stack(x0, S)
-        p = AdmmParams(float(gamma), int(iters), float(cg_tol), int(cg_maxit), SOLVER_LSQR, denoiser_type(multi_level, tsmi_domain), float(noise_std), 0)
+        p = AdmmParams(float(gamma), int(iters), float(cg_tol), int(cg_maxit), _mc_solver(solver), denoiser_type(multi_level, tsmi_domain), float(noise_std), 0)
         n = self.N * self.M * self.s
         x = np.empty(S * n, np.complex128)
         li = np.zeros((S, max(iters, 1)), np.int32)
@@ -375,7 +410,7 @@ class Engine:
         x = _cbuf(x0 if x0 is not None else np.zeros((self.N, self.M, self.s))).copy()
         it, fl = C.c_int32(0), C.c_int32(0)
         self._check(self.L.qmri_xupdate(self.h, _vp(yb), _vp(zb), float(r), float(tol), int(maxit),
-                                        SOLVER_LSQR if solver == "lsqr" else SOLVER_DIRECT, _vp(x), C.byref(it), C.byref(fl)))
+                                        solver_code(solver), _vp(x), C.byref(it), C.byref(fl)))
         return x.reshape((self.N, self.M, self.s), order="F"), it.value, fl.value
 
     # -- denoiser ------------------------------------------------------------------------------------
@@ -447,7 +482,7 @@ class Engine:
                  noise_std=0.01, x0=None, gt=None, want_diag=False, tsmi_domain="real"):
         """x = PnP_ADMM(y, param)  (PnP_ADMM.m:1).  Returns (x [N,M,s] complex, diag [iters,2] or None, lsqr_iters).
         tsmi_domain="complex": the denoiser step on cat(3, real, imag) of x + uold (a 2s (+1) -> 2s network; see denoiser_type)."""
-        p = AdmmParams(float(gamma), int(iters), float(cg_tol), int(cg_maxit), SOLVER_LSQR if solver == "lsqr" else SOLVER_DIRECT,
+        p = AdmmParams(float(gamma), int(iters), float(cg_tol), int(cg_maxit), solver_code(solver),
                        denoiser_type(multi_level, tsmi_domain), float(noise_std), int(bool(want_diag)))
         yb = _cbuf(y)
         if yb.size != self.m:
@@ -467,7 +502,7 @@ class Engine:
                        noise_std=0.01, tsmi_domain="real"):
         """A slice stack ys [S, m] through this context, slices_per_launch at a time (qmri_pnp_admm_batch; what `PnP_ADMM_hip(Y, param)` calls
         for a measurement matrix).  Returns (X [S,N,M,s] complex, lsqr_iters [S, iters])."""
-        p = AdmmParams(float(gamma), int(iters), float(cg_tol), int(cg_maxit), SOLVER_LSQR if solver == "lsqr" else SOLVER_DIRECT,
+        p = AdmmParams(float(gamma), int(iters), float(cg_tol), int(cg_maxit), solver_code(solver),
                        denoiser_type(multi_level, tsmi_domain), float(noise_std), 0)
         yb = np.ascontiguousarray(np.asarray(ys, np.complex128))
         if yb.ndim != 2 or yb.shape[1] != self.m:

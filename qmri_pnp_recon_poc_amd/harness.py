@@ -222,7 +222,7 @@ def save_training_pickle(path, X_slices, channels_to_save=None):
 def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", subsampling_pattern="Spiral",
                 spiral_sampling_curve=771, epi_sampling_rate=1 / 65, measurements_type="noisy", measurements_noise=30,
                 denoiser_type="single_level", noise_map_std=0.01, residual_noise=False, iters=100, seed=0, Y=None, device=0,
-                net_arch=None, lrtv_iters=None, tsmi_domain="real"):
+                net_arch=None, lrtv_iters=None, tsmi_domain="real", solver="lsqr"):
     """main_recon_tsmis_FFT.m:216-374 on already loaded (and cropped) arrays.
 
     dictionary  dict(V, D, normD, lut) (load_dictionary);  X0  N x M x s ground-truth TSMI;  qmap0  N x M x 3
@@ -231,6 +231,7 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
     net_arch    dict(nc=..., nb=...) when `weights` is a flat blob of a non-default UNetRes (files carry their architecture)
     tsmi_domain "complex": X0 may be complex (tsmi_from_stack turns the stored 2s-channel layout into one) and the denoiser takes 2s (+1) ->
                 2s channels, cat(3, real, imag); "real" is the reference's loop
+    solver      x-update of PnP_ADMM: "lsqr" (the reference's), "direct", or with SpiralExact "toeplitz" 
     Returns dict(X, qmap (N x M x 3: T1, T2, PD), Y, metrics, foreground_mask).
     """
     from . import reference_api as R
@@ -275,7 +276,7 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
                          **{**net_arch, **({"nc": arch["nc"], "nb": arch["nb"]} if arch else {})})
         param = {"eta": 20, "sigma_squared": 1, "gamma": 1 / 20, "iter": iters, "cg_tol": 1e-4, "F": F, "gt_tsmi": X0,
                  "X0": F.adjoint(Y), "net": net, "denoiser_type": denoiser_type, "tsmi_domain": tsmi_domain,
-                 "noise_map": R.build_noise_map(noise_map_std, N, M)}                # :166-171
+                 "noise_map": R.build_noise_map(noise_map_std, N, M), "solver": solver}   # :166-171
         X = R.PnP_ADMM(np.asarray(Y, dtype=np.complex128), param)
     elif recon_method == "LRTV":                                                     # :273-282
         param = {"K": 4e-5, "iter": 200 if lrtv_iters is None else int(lrtv_iters), "step": X0.size / np.asarray(Y).size, "tol": 1e-4,

@@ -3,7 +3,8 @@ function [x, diag, lsqr_iters] = PnP_ADMM_hip(y, param)
 %   loop on the GPU (one boundary crossing per reconstruction).  param.F must come from qmri_make_F and param.net from
 %   qmri_make_net; the fields read are the reference's own: iter, gamma, cg_tol, gt_tsmi, X0, denoiser_type, noise_map
 %   (PnP_ADMM.m:62-76), and param.tsmi_domain ('real', the default and the reference's; 'complex': the denoiser sees
-%   cat(3, real(x+u), imag(x+u)) and param.net must take 2s (+1) -> 2s channels).  Extra outputs: the two per-iteration diagnostics (PnP_ADMM.m:106-109) and the LSQR iteration counts.
+%   cat(3, real(x+u), imag(x+u)) and param.net must take 2s (+1) -> 2s channels), and param.solver ('lsqr', the default; 'direct'; 'toeplitz' on a
+%   trajectory F: CG on the Toeplitz normal operator, DESIGN.md section 16).  Extra outputs: the two per-iteration diagnostics (PnP_ADMM.m:106-109) and the LSQR iteration counts.
 %
 %   y is the measurement vector of one slice (m x 1, as in the reference) or a measurement MATRIX m x S, one column per slice:
 %   the S slices then advance together through the batched kernels (15 at a time) on the current device and x is
@@ -16,6 +17,16 @@ if p.multi_level, p.noise_std = param.noise_map(1); else, p.noise_std = 0.01; en
 tsmi_domain = 'real';  if isfield(param, 'tsmi_domain'), tsmi_domain = char(param.tsmi_domain); end
 if ~any(strcmp(tsmi_domain, {'real', 'complex'})), error('qmri:tsmi_domain', 'param.tsmi_domain must be ''real'' or ''complex'''); end
 p.complex_tsmi = double(strcmp(tsmi_domain, 'complex'));   % complex TSMIs: the denoiser sees cat(3, real, imag), 2s (+1) -> 2s channels
+if isfield(param, 'solver')                                % 'lsqr' (default, the reference's), 'direct', 'toeplitz' (trajectory operators), or the integer
+    sv = param.solver;
+    if ischar(sv) || isstring(sv)
+        k = find(strcmp(char(sv), {'lsqr', 'direct', 'toeplitz'}), 1);
+        if isempty(k), error('qmri:solver', 'param.solver must be ''lsqr'', ''direct'', ''toeplitz'' or an integer'); end
+        p.solver = k - 1;
+    else
+        p.solver = double(sv);
+    end
+end
 g = param.F.qmri;
 if isvector(y), y = y(:); end
 gt = [];  if isfield(param, 'gt_tsmi'), gt = complex(double(param.gt_tsmi)); end

@@ -17,6 +17,7 @@
 //     slices advanced together on each (k_conv6p, batched LSQR), x and the T1 / T2 / PD maps of every slice back.
 //   * 'set_trajectory' plans a non-Cartesian operator (qmri_set_operator_nufft; 'build_spiral_traj' gives the reference's spiral before rounding):
 //     'forward', 'adjoint' and 'pnp_admm' then run on it (a measurement matrix slice by slice; no diagnostics), 'recon_batch*' refuse it.
+//     'normal' applies A^H A as a Toeplitz convolution (qmri_normal) and param.solver = 2 ('toeplitz' in PnP_ADMM_hip.m) solves the x-update with it.
 //   * 'recon_batch_mc' is the same for multi-coil stacks, every slice with its own coil maps (qmri_recon_batch_mc; an extension, no reference
 //     counterpart); with a coil-compression argument every launch compresses its slices on the device first (qmri_recon_batch_mc_cc).
 //   * 'coil_compress' compresses a multi-coil stack to virtual coils (qmri_coil_compress; extension).
@@ -299,6 +300,13 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         const mwSize dims[3] = {(mwSize)d[0], (mwSize)d[1], (mwSize)d[2]};
         plhs[0] = mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxCOMPLEX);
         check(qmri_adjoint(ctx(), mxGetComplexDoubles(prhs[1]), mxGetComplexDoubles(plhs[0])));
+    } else if (c == "normal") {                      // z = qmri_mex('normal', x): A^H A x on a trajectory operator (qmri_normal)
+        need(nrhs, 2, "z = qmri_mex('normal', x)");
+        want(mxIsDouble(prhs[1]) && mxGetNumberOfElements(prhs[1]) == image_numel(), "qmri:normal:size", "x must be a double N x M x s array");
+        plhs[0] = mxCreateNumericArray(mxGetNumberOfDimensions(prhs[1]), mxGetDimensions(prhs[1]), mxDOUBLE_CLASS, mxCOMPLEX);
+        const bool cx = mxIsComplex(prhs[1]);
+        check(qmri_normal(ctx(), cx ? (const void*)mxGetComplexDoubles(prhs[1]) : (const void*)mxGetDoubles(prhs[1]), cx,
+                          mxGetComplexDoubles(plhs[0])));
     } else if (c == "set_denoiser") {                // qmri_mex('set_denoiser', weights(single), in_nc, out_nc, nc(1x4), nb, residual_noise, H, W [, max_batch])
         need(nrhs, 9, "qmri_mex('set_denoiser', weights, in_nc, out_nc, nc, nb, residual_noise, H, W [, max_batch])");
         qmri_net_desc d;
