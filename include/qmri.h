@@ -348,6 +348,53 @@ int qmri_coil_eig(int n, const void* herm, double* evals, void* evecs);
 int qmri_recon_batch_mc_cc(int ndev, const int* devs, int nslices, const qmri_problem* prob, int ncoil, const void* maps, const void* Y_mc,
                            void* X_out, float* qmap_out, float* pd_out, char* errbuf, size_t errbuf_len, const void* noise_cov, const qmri_cc_params* cc);
 
+/* ---- coil sensitivity maps from calibration data (multi-coil extension, no reference counterpart, parity unpinned) ---- */
+/* The adaptive-combine estimator of Walsh, Gmitro & Marcellin (MRM 2000) on the device, the step between qmri_coil_compress and a qmri_*_mc call.
+ * Needs qmri_set_operator (gridded or trajectory): the inverse transform runs on the operator's dense FFT passes max_batch coil images at a time, so
+ * N and M must be the operator's.
+ * Per slice, ncoil <= 128 coils on the N x M grid:
+ *   kind QMRI_CSM_IMAGES: calib is nslices x ncoil x N*M complex doubles in the layout of `maps`: the calibration images I_j, used as given.
+ *   kind QMRI_CSM_KSPACE: calib is nslices x ncoil x cM x cN (column-major cN x cM per coil, cN along N), a centred block of k-space in the
+ *     operator's convention -- the centre crop of fftshift(fft2(C_j x)) / sqrt(N M), block index (cN/2, cM/2) is k = 0; cN, cM even, 8 <= cN <= N,
+ *     8 <= cM <= M.  I_j = sqrt(N M) ifft2(ifftshift(P(w .* calib_j))): P zero-pads so that block index (cN/2, cM/2) lands on grid index (N/2, M/2),
+ *     w(a1, a2) = h_cN(a1) h_cM(a2), h_c(a) = (1 + cos(2 pi (a - c/2) / c)) / 2 (Hann; window = 0: w = 1).  An untapered full-size block inverts fft2.
+ *   1. R(r) = sum_{d in [-patch, patch]^2} I(r + d) I(r + d)^H, terms outside the grid dropped (ncoil x ncoil Hermitian, never stored)
+ *   2. lambda_1(r), u(r): its largest eigenvalue and unit eigenvector (power iteration from I(r), per pixel until no entry moves by more than
+ *      1e-13, at most 256 iterations)
+ *   3. phase_ref QMRI_CSM_PHASE_OBJECT: C(r) = u(r) e^{i arg(u(r)^H I(r))} -- C^H I is real and non-negative, the object's phase lives in the maps
+ *      (what the real-mode denoiser, real(x + u) of PnP_ADMM.m:115, needs);  QMRI_CSM_PHASE_COIL: C(r) = u(r) e^{-i arg(u_ref(r))}, ref the coil with
+ *      the largest sum_r |I_j(r)|^2 (lowest index on ties) -- the object's phase stays in x (complex TSMIs).  A modulus of exactly 0: phase factor 1.
+ *   4. thresh > 0: C(r) = 0 where lambda_1(r) < thresh^2 max_r lambda_1(r); |C(r)|_2 = 1 on the pixels kept (thresh = 0: everywhere).
+ * A slice's outputs are the same bits alone, at any position of a stack and with any max_batch.  ESPIRiT is not built. */
+enum { QMRI_CSM_KSPACE = 0, QMRI_CSM_IMAGES = 1 };
+enum { QMRI_CSM_PHASE_OBJECT = 0, QMRI_CSM_PHASE_COIL = 1 };
+typedef struct {
+    int kind;            /* QMRI_CSM_KSPACE / QMRI_CSM_IMAGES */
+    int cN, cM;          /* KSPACE: sides of the calibration block (ignored for IMAGES) */
+    int patch;           /* half-width p of the (2p + 1) x (2p + 1) patch, 0..4 */
+    int window;          /* KSPACE: 1 = Hann taper, 0 = none */
+    int phase_ref;       /* QMRI_CSM_PHASE_OBJECT / QMRI_CSM_PHASE_COIL */
+    double thresh;       /* >= 0; 0 keeps every pixel */
+} qmri_csm_params;
+/* kspace input of a cN x cM block, 7 x 7 patch, Hann taper, object phase, no mask */
+#define QMRI_CSM_PARAMS_DEFAULT(cN_, cM_) { QMRI_CSM_KSPACE, (cN_), (cM_), 3, 1, QMRI_CSM_PHASE_OBJECT, 0.0 }
+typedef struct {
+    int32_t max_iters;       /* the largest iteration count any pixel of the call needed */
+    int32_t not_converged;   /* pixels that reached 256 iterations without meeting the stop rule */
+} qmri_csm_info;
+/* Host arrays.  maps_out: nslices x ncoil x N*M (feeds qmri_set_coils / the *_mc_batch calls directly); img_out (nullable): nslices x N*M complex,
+ * C^H I; lambda_out (nullable): nslices x N*M doubles, lambda_1 (unmasked); info (nullable).  Refusals are decided on the host before the device is
+ * selected (ctx == NULL: the message of the first failing check in qmri_last_error(NULL)): NULL arrays or params, nslices < 1, ncoil < 1, an odd or
+ * out-of-range cN / cM, patch outside 0..4, an unknown kind / phase_ref, window outside {0, 1}, a negative or non-finite thresh: QMRI_ERR_INVALID_ARG;
+ * an N or M outside the supported sides of qmri_set_operator: QMRI_ERR_INVALID_ARG; ncoil > 128: QMRI_ERR_UNSUPPORTED; then no operator:
+ * QMRI_ERR_STATE; N, M not the operator's: QMRI_ERR_INVALID_ARG. */
+int qmri_coil_maps(qmri_ctx* ctx, int nslices, int ncoil, int N, int M, const void* calib, const qmri_csm_params* p, void* maps_out, void* img_out,
+                   double* lambda_out, qmri_csm_info* info);
+/* The same on device arrays of ctx's device (calib, maps_out, img_out, lambda_out; info stays a host struct); d_maps_out must not alias d_calib.
+ * Returns after its kernels have finished. */
+int qmri_coil_maps_dev(qmri_ctx* ctx, int nslices, int ncoil, int N, int M, const void* d_calib, const qmri_csm_params* p, void* d_maps_out,
+                       void* d_img_out, double* d_lambda_out, qmri_csm_info* info);
+
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------------ */
 typedef struct {
     double ms_xupdate, ms_denoiser, ms_elementwise, ms_diag, ms_match;   /* hipEvent time per stage */

@@ -337,6 +337,11 @@ int cc_eig_host(qmri_ctx* ctx, int n, const double2* A, double* lam, double2* U)
 int cc_choose_nv(int n, const double* lam, double energy);
 int cc_batch_param_error(int ncoil, const qmri_cc_params* p, std::string* msg);   // qmri_recon_batch_mc_cc's rules: QMRI_OK or the code + *msg
 
+// coil sensitivity maps from calibration data (csm_kernels.hip, api_csm.cpp).  Scratch lives for the call (DevBuf).
+int csm_chunk_coils(int ncoil, int p);   // coils per LDS chunk of k_csm_eig (= ncoil: all resident); a function of its arguments alone
+int csm_maps_dev(qmri_ctx* ctx, int B, int ncoil, const double2* d_calib, const qmri_csm_params& prm, double2* d_maps, double2* d_img, double* d_lam,
+                 qmri_csm_info* info);
+
 // ---------------------------------------------------------------------------------------------------
 // trajectory (NUFFT) operator (nufft_kernels.hip, api_nufft.cpp).  Planned once on the host per qmri_set_operator_nufft:
 // samples sorted by the 16 x 16 tile of the 2N x 2M oversampled grid that holds their position ("bins"), and for the output-driven spreading the

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import AdmmParams, CcParams, LrtvInfo, LrtvParams, NetDesc, NufftParams, Profile
+from ._lib import AdmmParams, CcParams, CsmInfo, CsmParams, LrtvInfo, LrtvParams, NetDesc, NufftParams, Profile
 
 ARCH_UNETRES, ARCH_SEQ_CONV = 0, 1
 SOLVER_LSQR, SOLVER_DIRECT = 0, 1
@@ -403,6 +403,49 @@ class Engine:
         if maps is not None:
             out["maps"] = np.stack([mo[b * k * plane:(b + 1) * k * plane].reshape((self.N, self.M, k), order="F") for b in range(S)])
         return out
+
+    def coil_maps(self, calib, kind="kspace", patch=3, window=True, phase_ref="object", thresh=0.0):
+        """Coil sensitivity maps from calibration data (adaptive combine; extension, no reference counterpart; include/qmri.h qmri_coil_maps).
+        calib: kind "kspace": a centred k-space block [cN, cM, ncoil] (or a stack [S, cN, cM, ncoil]) in the operator's convention, cN and cM even,
+        8 <= cN <= N, 8 <= cM <= M; kind "images": calibration images [N, M, ncoil] (or [S, N, M, ncoil]).  patch: half-width 0..4; window: Hann
+        taper of the block; phase_ref: "object" (C^H I real and non-negative) or "coil" (the strongest coil real and non-negative); thresh: pixels
+        with lambda_1 < thresh^2 max lambda_1 are zeroed.  Returns (maps, img, lambda1, info) shaped as the input (slice or stack):
+        maps [.., N, M, ncoil], img [.., N, M] = C^H I, lambda1 [.., N, M], info = dict(max_iters, not_converged)."""
+        kinds, refs = {"kspace": 0, "images": 1}, {"object": 0, "coil": 1}
+        if kind not in kinds:
+            raise ValueError('kind must be "kspace" or "images"')
+        if phase_ref not in refs:
+            raise ValueError('phase_ref must be "object" or "coil"')
+        if not (0 <= int(patch) <= 4) or int(patch) != patch:
+            raise ValueError("patch must be an integer 0..4")
+        if not (np.isfinite(thresh) and thresh >= 0):
+            raise ValueError("thresh must be finite and >= 0")
+        calib = np.asarray(calib)
+        if calib.ndim not in (3, 4):
+            raise ValueError("calib must be [n1, n2, ncoil] or [slices, n1, n2, ncoil]")
+        one = calib.ndim == 3
+        c4 = calib[None] if one else calib
+        S, c1, c2, nc = c4.shape
+        if S < 1 or nc < 1 or nc > 128:
+            raise ValueError("calib needs at least one slice and 1..128 coils")
+        if kind == "images":
+            if (c1, c2) != (self.N, self.M):
+                raise ValueError(f"calibration images must be [.., {self.N}, {self.M}, ncoil]")
+        elif c1 % 2 or c2 % 2 or not (8 <= c1 <= self.N) or not (8 <= c2 <= self.M):
+            raise ValueError(f"the calibration block must have even sides with 8 <= cN <= {self.N}, 8 <= cM <= {self.M}")
+        cb = np.concatenate([_cbuf(c4[b]) for b in range(S)])
+        p = CsmParams(kinds[kind], int(c1), int(c2), int(patch), int(bool(window)), refs[phase_ref], float(thresh))
+        plane = self.N * self.M
+        mo = np.empty(S * nc * plane, np.complex128)
+        io = np.empty(S * plane, np.complex128)
+        lo = np.empty(S * plane, np.float64)
+        info = CsmInfo(0, 0)
+        self._check(self.L.qmri_coil_maps(self.h, S, nc, self.N, self.M, _vp(cb), C.byref(p), _vp(mo), _vp(io), _vp(lo), C.byref(info)))
+        maps = np.stack([mo[b * nc * plane:(b + 1) * nc * plane].reshape((self.N, self.M, nc), order="F") for b in range(S)])
+        img = np.stack([io[b * plane:(b + 1) * plane].reshape((self.N, self.M), order="F") for b in range(S)])
+        lam = np.stack([lo[b * plane:(b + 1) * plane].reshape((self.N, self.M), order="F") for b in range(S)])
+        inf = {"max_iters": int(info.max_iters), "not_converged": int(info.not_converged)}
+        return (maps[0], img[0], lam[0], inf) if one else (maps, img, lam, inf)
 
     def xupdate(self, y, z, r, tol=1e-4, maxit=100, x0=None, solver="lsqr"):
         """The x-update of PnP_ADMM.m:102 alone.  Returns (x, iters, flag)."""

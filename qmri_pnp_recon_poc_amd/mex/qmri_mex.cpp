@@ -21,6 +21,7 @@
 //   * 'recon_batch_mc' is the same for multi-coil stacks, every slice with its own coil maps (qmri_recon_batch_mc; an extension, no reference
 //     counterpart); with a coil-compression argument every launch compresses its slices on the device first (qmri_recon_batch_mc_cc).
 //   * 'coil_compress' compresses a multi-coil stack to virtual coils (qmri_coil_compress; extension).
+//   * 'coil_maps' estimates coil sensitivity maps from calibration data (qmri_coil_maps; extension).
 // tests/cpp/mex_mock.cpp is a small stand-in for the MATLAB runtime's C API under which this file is compiled, LINKED against libqmri.so and
 // driven command by command on the GPU box (tests/test_gpu_mex.py); with MATLAB's own mex.h nothing here changes.
 #include "mex.h"
@@ -501,6 +502,48 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         if (nlhs > 3) {
             plhs[3] = mxCreateDoubleMatrix(ncoil, nmat, mxREAL);
             std::memcpy(mxGetDoubles(plhs[3]), eo.data(), nmat * ncoil * sizeof(double));
+        }
+    } else if (c == "coil_maps") {                   // [maps, img, lam, info] = qmri_mex('coil_maps', calib, opts)
+        // multi-coil extension (no reference counterpart): coil sensitivity maps from calibration data (qmri_coil_maps).  calib: complex double,
+        // cN x cM x ncoil x S (a centred k-space block, opts.images = 0) or N x M x ncoil x S (calibration images, opts.images = 1); opts: a struct with
+        // the optional fields images (0), patch (3), window (1), phase_coil (0: object phase, 1: strongest coil), thresh (0).
+        // maps N x M x ncoil x S, img N x M x S, lam N x M x S, info a struct (max_iters, not_converged).
+        need(nrhs, 3, "[maps, img, lam, info] = qmri_mex('coil_maps', calib, opts)");
+        want(mxIsStruct(prhs[2]), "qmri:coil_maps:opts", "opts must be a struct (fields images, patch, window, phase_coil, thresh)");
+        want(g_op.V != nullptr, "qmri:state", "no operator: call qmri_mex('set_operator', ...) (qmri_make_F) first");
+        const mxArray* O = prhs[2];
+        const mxArray* f;
+        qmri_csm_params p = QMRI_CSM_PARAMS_DEFAULT(0, 0);
+        if ((f = mxGetField(O, 0, "images"))) p.kind = int_arg(f, 0, 1, "qmri:coil_maps:opts", "opts.images must be 0 or 1") ? QMRI_CSM_IMAGES : QMRI_CSM_KSPACE;
+        if ((f = mxGetField(O, 0, "patch"))) p.patch = int_arg(f, 0, 4, "qmri:coil_maps:opts", "opts.patch must be an integer in [0, 4]");
+        if ((f = mxGetField(O, 0, "window"))) p.window = int_arg(f, 0, 1, "qmri:coil_maps:opts", "opts.window must be 0 or 1");
+        if ((f = mxGetField(O, 0, "phase_coil"))) p.phase_ref = int_arg(f, 0, 1, "qmri:coil_maps:opts", "opts.phase_coil must be 0 or 1") ? QMRI_CSM_PHASE_COIL : QMRI_CSM_PHASE_OBJECT;
+        p.thresh = scalar_field(O, "thresh", 0.0);
+        want(std::isfinite(p.thresh) && p.thresh >= 0.0, "qmri:coil_maps:opts", "opts.thresh must be finite and >= 0");
+        const mwSize nd = mxGetNumberOfDimensions(prhs[1]);
+        const mwSize* cd = mxGetDimensions(prhs[1]);
+        want(is_cdouble(prhs[1]) && nd >= 2 && nd <= 4, "qmri:coil_maps:size", "calib must be complex double, c1 x c2 x ncoil x S");
+        const size_t c1 = cd[0], c2 = cd[1], ncoil = nd >= 3 ? cd[2] : 1, S = nd >= 4 ? cd[3] : 1, plane = (size_t)g_op.N * g_op.M;
+        want(ncoil >= 1 && ncoil <= 128 && S >= 1, "qmri:coil_maps:size", "calib needs 1..128 coils and at least one slice");
+        if (p.kind == QMRI_CSM_IMAGES) want(c1 == (size_t)g_op.N && c2 == (size_t)g_op.M, "qmri:coil_maps:size", "calibration images must be N x M x ncoil x S");
+        else want(c1 % 2 == 0 && c2 % 2 == 0 && c1 >= 8 && c2 >= 8 && c1 <= (size_t)g_op.N && c2 <= (size_t)g_op.M, "qmri:coil_maps:size",
+                  "the calibration block must have even sides with 8 <= cN <= N and 8 <= cM <= M");
+        p.cN = (int)c1; p.cM = (int)c2;
+        const mwSize md[4] = {(mwSize)g_op.N, (mwSize)g_op.M, (mwSize)ncoil, (mwSize)S}, id3[3] = {(mwSize)g_op.N, (mwSize)g_op.M, (mwSize)S};
+        plhs[0] = mxCreateNumericArray(4, md, mxDOUBLE_CLASS, mxCOMPLEX);
+        mxArray* img = mxCreateNumericArray(3, id3, mxDOUBLE_CLASS, mxCOMPLEX);
+        mxArray* lam = mxCreateNumericArray(3, id3, mxDOUBLE_CLASS, mxREAL);
+        (void)plane;
+        qmri_csm_info info{0, 0};
+        check(qmri_coil_maps(ctx(), (int)S, (int)ncoil, g_op.N, g_op.M, mxGetComplexDoubles(prhs[1]), &p, mxGetComplexDoubles(plhs[0]), mxGetComplexDoubles(img),
+                             mxGetDoubles(lam), &info));
+        if (nlhs > 1) plhs[1] = img; else mxDestroyArray(img);
+        if (nlhs > 2) plhs[2] = lam; else mxDestroyArray(lam);
+        if (nlhs > 3) {
+            const char* names[] = {"max_iters", "not_converged"};
+            plhs[3] = mxCreateStructMatrix(1, 1, 2, names);
+            mxSetFieldByNumber(plhs[3], 0, 0, mxCreateDoubleScalar((double)info.max_iters));
+            mxSetFieldByNumber(plhs[3], 0, 1, mxCreateDoubleScalar((double)info.not_converged));
         }
     } else if (c == "lrtv") {                        // [x, info] = qmri_mex('lrtv', y, param_struct, [N M s])   (FISTA_deep, main_recon_tsmis_FFT.m:273-282)
         need(nrhs, 4, "[x, info] = qmri_mex('lrtv', y, param, [N M s])");
