@@ -395,6 +395,47 @@ int qmri_coil_maps(qmri_ctx* ctx, int nslices, int ncoil, int N, int M, const vo
 int qmri_coil_maps_dev(qmri_ctx* ctx, int nslices, int ncoil, int N, int M, const void* d_calib, const qmri_csm_params* p, void* d_maps_out,
                        void* d_img_out, double* d_lambda_out, qmri_csm_info* info);
 
+/* ---- dictionary compression to its SVD subspace (extension, no reference counterpart, parity unpinned) ---------- */
+/* The reference ships its dictionaries already compressed (SVD_dict_FISP_cut*.mat) and never computes the compression.  This call takes what a
+ * Bloch / EPG simulator writes -- F, K fingerprints of T frames, real, column-major K x T (frame t contiguous over the atoms, as D of
+ * qmri_set_dictionary), fp64 (f_is_f64 = 1) or fp32 (0) -- and returns what qmri_set_operator and qmri_set_dictionary take:
+ *   1. G = F^T F in fp64 (fp32 input widened exactly; split over fixed chunks of atoms added in chunk order, no atomics: the same bits from call to
+ *      call).  A non-finite trace is QMRI_ERR_INVALID_ARG.
+ *   2. lambda_1 >= lambda_2 >= ... and orthonormal v_1 .. v_b, the dominant eigenpairs of G (block subspace iteration with Rayleigh-Ritz, block
+ *      b = min(T, s_cap + 8), s_cap = p->s or p->s_max; stopped when every one of the s_cap leading residuals |G v_c - lambda_c v_c|_2 is
+ *      <= tol lambda_1, or after maxit iterations).  Every vector's entry of largest magnitude (lowest index on ties) is positive.
+ *   3. s = p->s (1..16), or with p->s == 0 the smallest s <= p->s_max (1..16, cut to min(T, K)) with sum_{c<s} lambda_c >= p->energy trace(G); if
+ *      s_max does not reach the energy, s = s_max and info->energy_reached = 0.  p->s > min(T, K) is QMRI_ERR_INVALID_ARG.  Note that the operator
+ *      (qmri_set_operator) takes s <= 10.
+ *   4. Dc = F V (fp64, frames ascending), normD_k = |Dc_k|_2, D_k = Dc_k / normD_k, both rounded once to fp32; an atom of zero norm gives D_k = 0 and
+ *      normD_k = 0.
+ * 1 <= T <= 1024, K >= 1.  Needs neither an operator, a denoiser nor a dictionary. */
+typedef struct {
+    int32_t s;           /* 1..16: the rank; 0: choose by energy */
+    int32_t s_max;       /* 1..16, used when s == 0 */
+    double  energy;      /* (0, 1], used when s == 0 */
+    double  tol;         /* residual bound relative to lambda_1, in [0, 1); 0 -> 1e-13 */
+    int32_t maxit;       /* >= 0; 0 -> 200 */
+} qmri_dsvd_params;
+typedef struct {
+    int32_t s;               /* the rank used */
+    int32_t iters;           /* subspace iterations taken */
+    int32_t converged;       /* 0: maxit was reached before the stop rule held */
+    int32_t energy_reached;  /* 0: energy mode, and s_max vectors hold less than the energy asked for */
+    double  max_resid;       /* the largest |G v_c - lambda_c v_c|_2 / lambda_1 over the s_cap leading pairs */
+    double  energy_kept;     /* sum_{c<s} lambda_c / trace(G) */
+} qmri_dsvd_info;
+/* Host arrays.  V_out: T x s fp64 column-major; D_out: K x s fp32 column-major; normD_out: K; eig_out (nullable): the s leading lambda; info
+ * (nullable).  The outputs are written compactly with the chosen s; a caller who lets energy choose sizes them for s = 16.  Refusals are decided on
+ * the host before the device is selected (ctx == NULL: the message of the first failing check in qmri_last_error(NULL)): NULL arrays or params,
+ * K < 1, T outside 1..1024, f_is_f64 outside {0, 1}, s / s_max / energy / tol / maxit out of range: QMRI_ERR_INVALID_ARG. */
+int qmri_dict_compress(qmri_ctx* ctx, int K, int T, const void* F, int f_is_f64, const qmri_dsvd_params* p, int* s_out, double* V_out, float* D_out,
+                       float* normD_out, double* eig_out, qmri_dsvd_info* info);
+/* The same on device arrays of ctx's device (F, V_out, D_out, normD_out); s_out, eig_out and info stay on the host.  Same bits as the host-array
+ * call.  Returns after its kernels have finished. */
+int qmri_dict_compress_dev(qmri_ctx* ctx, int K, int T, const void* d_F, int f_is_f64, const qmri_dsvd_params* p, int* s_out, double* d_V_out,
+                           float* d_D_out, float* d_normD_out, double* eig_out, qmri_dsvd_info* info);
+
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------------ */
 typedef struct {
     double ms_xupdate, ms_denoiser, ms_elementwise, ms_diag, ms_match;   /* hipEvent time per stage */
@@ -461,6 +502,9 @@ int qmri_debug_dict_filter(qmri_ctx* ctx, int on, float margin_scale);
  * makes one tile withhold its hand-off on purpose: its neighbours' waits time out, the library reports it on stderr, repeats the call with one
  * launch per layer and keeps the resident form off (the recovery path, tested).  timeouts_out (or NULL): hand-off time-outs seen so far. */
 int qmri_debug_conv_resident(qmri_ctx* ctx, int on, int* timeouts_out);
+/* Test / timing hook of the dictionary compression: step 1 alone, G = F^T F (T x T fp64 column-major, both triangles) as qmri_dict_compress forms
+ * it.  on_device = 0: F and G_out are host arrays; 1: device arrays of ctx's device.  Returns after its kernels have finished. */
+int qmri_debug_dsvd_gram(qmri_ctx* ctx, int K, int T, const void* F, int f_is_f64, int on_device, double* G_out);
 /* The one entry point of the process-wide A/B and diagnostic switches ("knobs": tile configurations, the fused launches, in-kernel stamps of the
  * diagnostic builds ...; names and defaults: csrc/api_core.cpp g_knob_defs).  The same switches can be set at start-up through the library's
  * only environment variable, QMRI_DEBUG="name=value,name=value".  Every default is the product's behaviour; an unknown name is

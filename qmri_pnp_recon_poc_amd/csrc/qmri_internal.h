@@ -342,6 +342,14 @@ int csm_chunk_coils(int ncoil, int p);   // coils per LDS chunk of k_csm_eig (= 
 int csm_maps_dev(qmri_ctx* ctx, int B, int ncoil, const double2* d_calib, const qmri_csm_params& prm, double2* d_maps, double2* d_img, double* d_lam,
                  qmri_csm_info* info);
 
+// dictionary compression to its SVD subspace (dsvd_kernels.hip, api_dsvd.cpp).  All pointers are device pointers; the launches
+// go to ctx->stream and are not waited for.
+int dsvd_gram_chunk();                   // atoms per split-K partial of the Gram kernel: a constant, so G's bits depend on (K, T) alone
+size_t dsvd_gram_scratch(int K, int T);  // doubles of partial tiles dsvd_gram_dev needs
+int dsvd_gram_dev(qmri_ctx* ctx, int K, int T, const void* d_F, bool f64, double* d_part, double* d_G, double* d_diag);      // G = F^T F, diag = its diagonal
+int dsvd_gq_dev(qmri_ctx* ctx, int T, int b, const double* d_G, const double* d_Q, double* d_Z);                               // Z = G Q (T x b)
+int dsvd_project_dev(qmri_ctx* ctx, int K, int T, int s, const void* d_F, bool f64, const double* d_V, float* d_D, float* d_normD);
+
 // ---------------------------------------------------------------------------------------------------
 // trajectory (NUFFT) operator (nufft_kernels.hip, api_nufft.cpp).  Planned once on the host per qmri_set_operator_nufft:
 // samples sorted by the 16 x 16 tile of the 2N x 2M oversampled grid that holds their position ("bins"), and for the output-driven spreading the

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import AdmmParams, CcParams, CsmInfo, CsmParams, LrtvInfo, LrtvParams, NetDesc, NufftParams, Profile
+from ._lib import AdmmParams, CcParams, CsmInfo, CsmParams, DsvdInfo, DsvdParams, LrtvInfo, LrtvParams, NetDesc, NufftParams, Profile
 
 ARCH_UNETRES, ARCH_SEQ_CONV = 0, 1
 SOLVER_LSQR, SOLVER_DIRECT = 0, 1
@@ -569,6 +569,39 @@ class Engine:
         f = C.POINTER(C.c_float)
         self._check(self.L.qmri_set_dictionary(self.h, K, s, Q, Df.ctypes.data_as(f), nd.ctypes.data_as(f), lf.ctypes.data_as(f)))
         self.dict_shape = (K, s, Q)
+
+    def compress_dictionary(self, F, s=None, energy=None, s_max=16, tol=0.0, maxit=0):
+        """A simulated dictionary compressed to its SVD subspace on the device (extension, no reference counterpart; include/qmri.h
+        qmri_dict_compress).  F [K, T]: K real fingerprints of T <= 1024 frames, float64 or float32 (float32 stays float32 on its way to the
+        device and is widened there); a complex F with a non-zero imaginary part is refused.  Exactly one of s (the rank, 1..16) and energy (the
+        fraction of trace(F^T F) to keep, with at most s_max <= 16 vectors) is given.  tol: residual bound of the eigenpairs relative to lambda_1
+        (0: 1e-13); maxit: cap on the subspace iterations (0: 200).  Returns dict(V [T, s] float64 for set_operator, D [K, s] float32 and normD [K]
+        float32 for set_dictionary, eig [s], info = dict(s, iters, converged, energy_reached, max_resid, energy_kept)).  Needs no operator."""
+        if (s is None) == (energy is None):
+            raise ValueError("give exactly one of s and energy")
+        F = real_dictionary_array(F, "F", np.float32 if np.asarray(F).dtype == np.float32 else np.float64)
+        if F.ndim != 2 or F.shape[0] < 1 or not (1 <= F.shape[1] <= 1024):
+            raise ValueError("F must be [K, T] with K >= 1 and 1 <= T <= 1024")
+        K, T = F.shape
+        if s is not None and (int(s) != s or not (1 <= int(s) <= min(16, K, T))):
+            raise ValueError(f"s must be an integer with 1 <= s <= min(16, K, T) = {min(16, K, T)}")
+        if s is None and (int(s_max) != s_max or not (1 <= int(s_max) <= 16) or not (0.0 < float(energy) <= 1.0)):
+            raise ValueError("energy must be in (0, 1] and s_max an integer in 1..16")
+        if not (0.0 <= float(tol) < 1.0) or int(maxit) != maxit or int(maxit) < 0:
+            raise ValueError("tol must be in [0, 1) and maxit an integer >= 0")
+        Fb = np.ascontiguousarray(F.ravel(order="F"))
+        p = DsvdParams(0 if s is None else int(s), int(s_max), 0.0 if energy is None else float(energy), float(tol), int(maxit))
+        V = np.empty(T * 16, np.float64)
+        D = np.empty(K * 16, np.float32)
+        nd = np.empty(K, np.float32)
+        eig = np.empty(16, np.float64)
+        got, info = C.c_int(0), DsvdInfo()
+        self._check(self.L.qmri_dict_compress(self.h, K, T, _vp(Fb), int(F.dtype == np.float64), C.byref(p), C.byref(got), _vp(V), _vp(D), _vp(nd), _vp(eig),
+                                              C.byref(info)))
+        r = got.value
+        return {"V": V[: T * r].reshape((T, r), order="F"), "D": D[: K * r].reshape((K, r), order="F"), "normD": nd, "eig": eig[:r].copy(),
+                "info": {"s": int(info.s), "iters": int(info.iters), "converged": int(info.converged), "energy_reached": int(info.energy_reached),
+                         "max_resid": float(info.max_resid), "energy_kept": float(info.energy_kept)}}
 
     def synthesize_tsmi(self, qmap, mode="real"):
         """TSMI of a quantitative map (main_synthesize_tsmis.m:82-103): qmap [..., 3] (T1, T2, PD) ->

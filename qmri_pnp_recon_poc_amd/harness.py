@@ -5,6 +5,7 @@ Host logic in numpy/scipy; the reconstruction and the match run on the GPU throu
 
   load_mat(path)                       `load(...)` of a MATLAB file: v5/v7 (scipy.io) or -v7.3 (HDF5; mat73.py, no HDF5 library needed)
   load_dictionary(path)                `load(dict_dir); V = real(dict.V)`                     main_recon_tsmis_FFT.m:121-130
+  compress_dictionary(dic, s | energy) an uncompressed (s = T) dictionary -> the SVD-compressed fields, on the GPU (extension)
   load_tsmi(path) / crop_tsmi(X)       `load(tsmi_dir); X0 = X((4:227),(4:227),:)`            :199-212
   load_qmaps(path, slice)              qmap(slice,:,:,:) -> N x M x 3, cropped the same way   :177-189
   getmask_fromPD(PD, thresh)           foreground mask                                         getmask_fromPD.m:9-15
@@ -25,7 +26,7 @@ from __future__ import annotations
 
 import numpy as np
 
-__all__ = ["load_mat", "load_dictionary", "load_tsmi", "crop_tsmi", "load_qmaps", "getmask_fromPD", "awgn_measured",
+__all__ = ["load_mat", "load_dictionary", "compress_dictionary", "load_tsmi", "crop_tsmi", "load_qmaps", "getmask_fromPD", "awgn_measured",
            "psnr", "ssim", "metrics", "recon_tsmis", "synthesize_tsmis", "training_volume", "save_training_pickle"]
 
 CROP = slice(3, 227)          # MATLAB (4:227): 230 -> 224                                       main_recon_tsmis_FFT.m:189,212
@@ -56,6 +57,24 @@ def load_dictionary(path):
            "lut": np.asarray(s.lut, dtype=np.float32)}
     out["normD"] = np.asarray(s.normD, dtype=np.float32).ravel() if hasattr(s, "normD") else np.linalg.norm(out["D"], axis=1).astype(np.float32)
     return out
+
+
+def compress_dictionary(dic, s=None, energy=None, s_max=16, device=0):
+    """An uncompressed dictionary -- D K x T unit-norm fingerprints with normD and lut, as synth.make_dictionary(uncompressed=True) and the s = T
+    files give it -- compressed to its SVD subspace on the GPU (Engine.compress_dictionary; an extension, the reference only loads compressed
+    files).  The fingerprints are re-scaled to F = normD .* D first.  Give the rank s or the energy to keep.  Returns the fields of
+    load_dictionary (V, D, normD, lut) plus eig and info; recon_tsmis runs on the result unchanged."""
+    from .engine import Engine, real_dictionary_array
+    D = real_dictionary_array(dic["D"], "dict.D", np.float64)
+    nd = np.asarray(dic["normD"], dtype=np.float64).ravel() if dic.get("normD") is not None else np.ones(D.shape[0])
+    if D.ndim != 2 or nd.shape != (D.shape[0],):
+        raise ValueError("the dictionary must hold D [K, T] and normD [K]")
+    eng = Engine(device)
+    try:
+        out = eng.compress_dictionary(D * nd[:, None], s=s, energy=energy, s_max=s_max)
+    finally:
+        eng.close()
+    return {"V": out["V"], "D": out["D"], "normD": out["normD"], "lut": np.asarray(dic["lut"], dtype=np.float32), "eig": out["eig"], "info": out["info"]}
 
 
 def crop_tsmi(X):

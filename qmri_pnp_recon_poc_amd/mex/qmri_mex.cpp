@@ -22,6 +22,7 @@
 //     counterpart); with a coil-compression argument every launch compresses its slices on the device first (qmri_recon_batch_mc_cc).
 //   * 'coil_compress' compresses a multi-coil stack to virtual coils (qmri_coil_compress; extension).
 //   * 'coil_maps' estimates coil sensitivity maps from calibration data (qmri_coil_maps; extension).
+//   * 'dict_compress' compresses a simulated dictionary to its SVD subspace (qmri_dict_compress; extension); it needs no plan.
 // tests/cpp/mex_mock.cpp is a small stand-in for the MATLAB runtime's C API under which this file is compiled, LINKED against libqmri.so and
 // driven command by command on the GPU box (tests/test_gpu_mex.py); with MATLAB's own mex.h nothing here changes.
 #include "mex.h"
@@ -544,6 +545,58 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
             plhs[3] = mxCreateStructMatrix(1, 1, 2, names);
             mxSetFieldByNumber(plhs[3], 0, 0, mxCreateDoubleScalar((double)info.max_iters));
             mxSetFieldByNumber(plhs[3], 0, 1, mxCreateDoubleScalar((double)info.not_converged));
+        }
+    } else if (c == "dict_compress") {               // [V, D, normD, eig, info] = qmri_mex('dict_compress', F, params)
+        // extension (no reference counterpart): a simulated dictionary compressed to its SVD subspace (qmri_dict_compress).  F: K x T real double or
+        // single, K fingerprints of T <= 1024 frames; params: a struct with s (the rank, 1..16) or energy (and s_max, 16), and the optional tol, maxit.
+        // V T x s double, D K x s single, normD K x 1 single, eig s x 1 double, info a struct.  Needs no operator, denoiser or dictionary.
+        need(nrhs, 3, "[V, D, normD, eig, info] = qmri_mex('dict_compress', F, params)");
+        want(mxIsStruct(prhs[2]), "qmri:dict_compress:params", "params must be a struct (fields s or energy, s_max, tol, maxit)");
+        const mxArray* A = prhs[1];
+        want((mxIsDouble(A) || mxIsSingle(A)) && !mxIsComplex(A) && mxGetNumberOfDimensions(A) == 2, "qmri:dict_compress:F",
+             "F must be a real double or single K x T matrix (complex fingerprints are not supported)");
+        const size_t K = mxGetM(A), T = mxGetN(A);
+        want(K >= 1 && K <= ((size_t)1 << 30) && T >= 1 && T <= 1024, "qmri:dict_compress:F", "F must be K x T with K >= 1 and 1 <= T <= 1024");
+        const mxArray* P = prhs[2];
+        const mxArray* f;
+        const char* pid = "qmri:dict_compress:params";
+        qmri_dsvd_params p = {0, 16, 0.0, 0.0, 0};
+        const bool has_s = mxGetField(P, 0, "s") != nullptr, has_e = mxGetField(P, 0, "energy") != nullptr;
+        want(has_s != has_e, pid, "params needs exactly one of the fields s and energy");
+        const double smax_here = (double)std::min<size_t>(16, std::min(K, T));
+        if (has_s) p.s = int_arg(mxGetField(P, 0, "s"), 1, smax_here, pid, "params.s must be an integer with 1 <= s <= min(16, K, T)");
+        else {
+            p.energy = scalar_field(P, "energy", 0.0);
+            want(p.energy > 0.0 && p.energy <= 1.0, pid, "params.energy must be in (0, 1]");
+            if ((f = mxGetField(P, 0, "s_max"))) p.s_max = int_arg(f, 1, 16, pid, "params.s_max must be an integer in [1, 16]");
+        }
+        p.tol = scalar_field(P, "tol", 0.0);
+        want(std::isfinite(p.tol) && p.tol >= 0.0 && p.tol < 1.0, pid, "params.tol must be in [0, 1)");
+        if ((f = mxGetField(P, 0, "maxit"))) p.maxit = int_arg(f, 0, 1e9, pid, "params.maxit must be an integer >= 0");
+        std::vector<double> Vo(T * 16), eo(16);
+        std::vector<float> Do(K * 16);
+        mxArray* nd = mxCreateNumericMatrix(K, 1, mxSINGLE_CLASS, mxREAL);
+        int s = 0;
+        qmri_dsvd_info info{};
+        const int st = qmri_dict_compress(ctx(), (int)K, (int)T, mxGetData(A), mxIsDouble(A) ? 1 : 0, &p, &s, Vo.data(), Do.data(), (float*)mxGetData(nd), eo.data(), &info);
+        if (st != QMRI_OK) mxDestroyArray(nd);
+        check(st);
+        plhs[0] = mxCreateDoubleMatrix(T, s, mxREAL);
+        std::memcpy(mxGetDoubles(plhs[0]), Vo.data(), T * s * sizeof(double));
+        if (nlhs > 1) {
+            plhs[1] = mxCreateNumericMatrix(K, s, mxSINGLE_CLASS, mxREAL);
+            std::memcpy(mxGetData(plhs[1]), Do.data(), K * s * sizeof(float));
+        }
+        if (nlhs > 2) plhs[2] = nd; else mxDestroyArray(nd);
+        if (nlhs > 3) {
+            plhs[3] = mxCreateDoubleMatrix(s, 1, mxREAL);
+            std::memcpy(mxGetDoubles(plhs[3]), eo.data(), s * sizeof(double));
+        }
+        if (nlhs > 4) {
+            const char* names[] = {"s", "iters", "converged", "energy_reached", "max_resid", "energy_kept"};
+            const double vals[] = {(double)info.s, (double)info.iters, (double)info.converged, (double)info.energy_reached, info.max_resid, info.energy_kept};
+            plhs[4] = mxCreateStructMatrix(1, 1, 6, names);
+            for (int k = 0; k < 6; ++k) mxSetFieldByNumber(plhs[4], 0, k, mxCreateDoubleScalar(vals[k]));
         }
     } else if (c == "lrtv") {                        // [x, info] = qmri_mex('lrtv', y, param_struct, [N M s])   (FISTA_deep, main_recon_tsmis_FFT.m:273-282)
         need(nrhs, 4, "[x, info] = qmri_mex('lrtv', y, param, [N M s])");
