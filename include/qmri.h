@@ -436,6 +436,45 @@ int qmri_dict_compress(qmri_ctx* ctx, int K, int T, const void* F, int f_is_f64,
 int qmri_dict_compress_dev(qmri_ctx* ctx, int K, int T, const void* d_F, int f_is_f64, const qmri_dsvd_params* p, int* s_out, double* d_V_out,
                            float* d_D_out, float* d_normD_out, double* eig_out, qmri_dsvd_info* info);
 
+/* ---- FISP dictionary simulation by extended phase graphs (extension, no reference counterpart, parity unpinned) ---- */
+/* The reference ships its dictionaries already simulated and compressed and has no simulator.  This call makes the fingerprints that
+ * qmri_dict_compress takes, from a flip-angle train and a list of atoms, by the extended-phase-graph recursion of the FISP-MRF sequence (Jiang et al.
+ * 2015; Weigel 2015).  Per atom k, with T1_k, T2_k in seconds and a transmit scale b1_k, the state is three REAL vectors of S = nstates entries,
+ * F+_n, F-_n, Z_n for n = 0 .. S-1, all zero at the start except Z_0 = 1 (the pulses rotate about y, which keeps every state real).
+ *   Inversion (inversion = 1): Z_0 <- -inv_eff Z_0, then relaxation over TI: Z_0 <- Z_0 e + (1 - e), e = exp(-TI / T1).
+ *   Then for each frame t = 0 .. T-1, in this order:
+ *   1. RF.  a = alpha_t b1_k, c = cos a, s = sin a, c2 = (1 + c) / 2, s2 = (1 - c) / 2; for every n, all three from the old values:
+ *        F+ <- c2 F+ - s2 F- + s Z,   F- <- -s2 F+ + c2 F- + s Z,   Z <- -(s / 2) (F+ + F-) + c Z.
+ *   2. Relaxation over TE_t: F+- <- F+- exp(-TE_t / T2), Z <- Z exp(-TE_t / T1) for every n, then Z_0 += 1 - exp(-TE_t / T1).
+ *   3. Signal: F[k, t] = F+_0.
+ *   4. Relaxation over TR_t - TE_t, in the same way as step 2.
+ *   5. Spoiler, one dephasing unit: F+_n <- F+_{n-1} for n >= 1 (the old F+_{S-1} is dropped), F+_0 <- old F-_1 (0 when S = 1),
+ *      F-_n <- old F-_{n+1}, F-_{S-1} <- 0, F-_0 <- the new F+_0.
+ * The truncation at S states is part of the result (it moves the fingerprints by 1e-3 at S = 32 when T2 reaches 0.6 s): S is the caller's to
+ * choose.  No slice profile, no diffusion, no off-resonance.  All arithmetic is fp64, sin / cos / exp included; there is no reduction across atoms
+ * and there are no atomics: equal inputs give equal bits.  1 <= T <= 1024 (the limit of qmri_dict_compress), K >= 1.  Needs neither an operator, a
+ * denoiser nor a dictionary. */
+typedef struct {
+    int32_t nstates;      /* S, 1..256 */
+    int32_t inversion;    /* 0 / 1 */
+    double  ti;           /* s, >= 0, used when inversion */
+    double  inv_eff;      /* (0, 1], used when inversion; 1 = ideal */
+    int32_t out_is_f64;   /* 1: F fp64, 0: F rounded once to fp32 */
+} qmri_epg_params;
+/* Host arrays, all fp64: alpha[T] radians, tr[T] and te[T] seconds, t1[K], t2[K], b1[K] (nullable: 1).  F_out: K x T column-major (frame t
+ * contiguous over the atoms: the layout qmri_dict_compress takes), fp64 or fp32 as p->out_is_f64 says.  Refusals are decided on the host before
+ * the device is selected (ctx == NULL: the message of the first failing check in qmri_last_error(NULL)): a NULL array or params, K < 1, T outside
+ * 1..1024, nstates outside 1..256, inversion / out_is_f64 outside {0, 1}, ti or inv_eff out of range when inversion, a non-finite or negative alpha,
+ * TR or TE, TR_t <= 0, TE_t > TR_t, a T1 or T2 that is non-finite or <= 0, a b1 that is non-finite or negative (b1 = 0 is allowed):
+ * QMRI_ERR_INVALID_ARG.  Returns after its kernels have finished. */
+int qmri_dict_simulate(qmri_ctx* ctx, int K, int T, const double* alpha, const double* tr, const double* te, const double* t1, const double* t2,
+                       const double* b1, const qmri_epg_params* p, void* F_out);
+/* The same with t1, t2, b1 and F_out on ctx's device; alpha, tr, te and p stay on the host.  Same bits as the host-array call.  This route cannot
+ * read its atoms on the host: for an atom whose T1 or T2 is non-finite or <= 0, or whose b1 is non-finite or negative, the kernel writes NaN in
+ * every frame of that atom (and of no other).  F_out feeds qmri_dict_compress_dev as it is. */
+int qmri_dict_simulate_dev(qmri_ctx* ctx, int K, int T, const double* alpha, const double* tr, const double* te, const double* d_t1, const double* d_t2,
+                           const double* d_b1, const qmri_epg_params* p, void* d_F_out);
+
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------------ */
 typedef struct {
     double ms_xupdate, ms_denoiser, ms_elementwise, ms_diag, ms_match;   /* hipEvent time per stage */
@@ -505,6 +544,9 @@ int qmri_debug_conv_resident(qmri_ctx* ctx, int on, int* timeouts_out);
 /* Test / timing hook of the dictionary compression: step 1 alone, G = F^T F (T x T fp64 column-major, both triangles) as qmri_dict_compress forms
  * it.  on_device = 0: F and G_out are host arrays; 1: device arrays of ctx's device.  Returns after its kernels have finished. */
 int qmri_debug_dsvd_gram(qmri_ctx* ctx, int K, int T, const void* F, int f_is_f64, int on_device, double* G_out);
+/* Test hook of the dictionary simulation: step 5 (the spoiler) alone, nshift times, on one atom's given state with the lane layout
+ * qmri_dict_simulate uses for S states.  in / out: host arrays of 3 S doubles, F+ [S], F- [S], Z [S] (Z is copied).  1 <= S <= 256, 0 <= nshift <= 4096. */
+int qmri_debug_epg_shift(qmri_ctx* ctx, int S, int nshift, const double* in, double* out);
 /* The one entry point of the process-wide A/B and diagnostic switches ("knobs": tile configurations, the fused launches, in-kernel stamps of the
  * diagnostic builds ...; names and defaults: csrc/api_core.cpp g_knob_defs).  The same switches can be set at start-up through the library's
  * only environment variable, QMRI_DEBUG="name=value,name=value".  Every default is the product's behaviour; an unknown name is

@@ -21,8 +21,8 @@ SYMBOLS = [
     "qmri_forward_f32", "qmri_adjoint_f32", "qmri_forward_dev", "qmri_adjoint_dev", "qmri_set_coils", "qmri_forward_mc", "qmri_adjoint_mc", "qmri_xupdate_mc", "qmri_pnp_admm_mc", "qmri_xupdate_mc_batch", "qmri_pnp_admm_mc_batch", "qmri_pnp_admm_mc_dev", "qmri_xupdate", "qmri_net_nparams", "qmri_set_denoiser", "qmri_denoise",
     "qmri_net_forward_dev", "qmri_denoiser_scheme", "qmri_pnp_admm", "qmri_pnp_admm_dev", "qmri_pnp_admm_batch", "qmri_set_dictionary", "qmri_dict_match",
     "qmri_dict_match_dev", "qmri_dict_match_xfit", "qmri_dict_match_xfit_dev", "qmri_recon_batch", "qmri_recon_batch_mc",
-    "qmri_coil_compress", "qmri_coil_compress_dev", "qmri_coil_eig", "qmri_recon_batch_mc_cc", "qmri_coil_maps", "qmri_coil_maps_dev", "qmri_dict_compress", "qmri_dict_compress_dev", "qmri_profile_enable", "qmri_profile_get", "qmri_get_health",
-    "qmri_debug_lsqr_stamps", "qmri_debug_conv_stamps", "qmri_debug_lsqr_persist", "qmri_debug_dict_filter", "qmri_debug_conv_resident", "qmri_debug_dsvd_gram", "qmri_debug_knob",
+    "qmri_coil_compress", "qmri_coil_compress_dev", "qmri_coil_eig", "qmri_recon_batch_mc_cc", "qmri_coil_maps", "qmri_coil_maps_dev", "qmri_dict_compress", "qmri_dict_compress_dev", "qmri_dict_simulate", "qmri_dict_simulate_dev", "qmri_profile_enable", "qmri_profile_get", "qmri_get_health",
+    "qmri_debug_lsqr_stamps", "qmri_debug_conv_stamps", "qmri_debug_lsqr_persist", "qmri_debug_dict_filter", "qmri_debug_conv_resident", "qmri_debug_dsvd_gram", "qmri_debug_epg_shift", "qmri_debug_knob",
     "qmri_onnx_read_unetres",
     "qmri_lrtv", "qmri_prox_tv", "qmri_norm_tv", "qmri_synthesize_tsmi", "qmri_synthesize_tsmi_complex",
 ]
@@ -65,6 +65,10 @@ class DsvdParams(C.Structure):
 class DsvdInfo(C.Structure):
     _fields_ = [("s", C.c_int32), ("iters", C.c_int32), ("converged", C.c_int32), ("energy_reached", C.c_int32),
                 ("max_resid", C.c_double), ("energy_kept", C.c_double)]
+
+
+class EpgParams(C.Structure):
+    _fields_ = [("nstates", C.c_int32), ("inversion", C.c_int32), ("ti", C.c_double), ("inv_eff", C.c_double), ("out_is_f64", C.c_int32)]
 
 
 class NufftParams(C.Structure):
@@ -188,6 +192,9 @@ def lib() -> C.CDLL:
     L.qmri_dict_compress.argtypes = [vp, i, i, vp, i, C.POINTER(DsvdParams), C.POINTER(i), vp, vp, vp, vp, C.POINTER(DsvdInfo)]
     L.qmri_dict_compress_dev.argtypes = [vp, i, i, vp, i, C.POINTER(DsvdParams), C.POINTER(i), vp, vp, vp, vp, C.POINTER(DsvdInfo)]
     L.qmri_debug_dsvd_gram.argtypes = [vp, i, i, vp, i, i, vp]
+    L.qmri_dict_simulate.argtypes = [vp, i, i, vp, vp, vp, vp, vp, vp, C.POINTER(EpgParams), vp]
+    L.qmri_dict_simulate_dev.argtypes = [vp, i, i, vp, vp, vp, vp, vp, vp, C.POINTER(EpgParams), vp]
+    L.qmri_debug_epg_shift.argtypes = [vp, i, i, vp, vp]
     L.qmri_debug_knob.argtypes = [C.c_char_p, i]
     L.qmri_profile_enable.argtypes = [vp, i]
     L.qmri_profile_get.argtypes = [vp, C.POINTER(Profile), i]

@@ -1,0 +1,101 @@
+// api_epg.cpp -- C ABI of the FISP dictionary simulation by extended phase graphs (include/qmri.h; kernels: epg_kernels.hip).  An EXTENSION with no
+// reference counterpart.  Every refusal is decided here, on the host, before the device is selected; with ctx == NULL the message of the first
+// failing check is left in qmri_last_error(NULL), so the argument rules can be exercised on a machine without a GPU.
+#include <cmath>
+#include <cstdint>
+#include <vector>
+#include "qmri_internal.h"
+
+namespace {
+constexpr int EPG_MAX_T = 1024, EPG_MAX_S = 256;
+
+// QMRI_OK, or the code of the first failing check with its message set on ctx (ctx may be NULL).  host_atoms: t1 / t2 / b1 can be read here
+int epg_checks(qmri_ctx* ctx, int K, int T, const double* alpha, const double* tr, const double* te, const double* t1, const double* t2, const double* b1,
+               const qmri_epg_params* p, const void* F_out, bool host_atoms) {
+    QMRI_CHECK_ARG(ctx, p, "simulation params must not be NULL");
+    QMRI_CHECK_ARG(ctx, alpha && tr && te && t1 && t2 && F_out, "alpha / tr / te / t1 / t2 / F_out must not be NULL");
+    QMRI_CHECK_ARG(ctx, K >= 1 && K <= (1 << 30), "K must satisfy 1 <= K <= 2^30");
+    QMRI_CHECK_ARG(ctx, T >= 1 && T <= EPG_MAX_T, "T must satisfy 1 <= T <= 1024");
+    QMRI_CHECK_ARG(ctx, p->nstates >= 1 && p->nstates <= EPG_MAX_S, "nstates must satisfy 1 <= nstates <= 256");
+    QMRI_CHECK_ARG(ctx, p->inversion == 0 || p->inversion == 1, "inversion must be 0 or 1");
+    QMRI_CHECK_ARG(ctx, p->out_is_f64 == 0 || p->out_is_f64 == 1, "out_is_f64 must be 0 or 1");
+    if (p->inversion) {
+        QMRI_CHECK_ARG(ctx, std::isfinite(p->ti) && p->ti >= 0.0, "ti must be finite and >= 0");
+        QMRI_CHECK_ARG(ctx, p->inv_eff > 0.0 && p->inv_eff <= 1.0, "inv_eff must be in (0, 1]");
+    }
+    for (int t = 0; t < T; ++t) {
+        QMRI_CHECK_ARG(ctx, std::isfinite(alpha[t]) && alpha[t] >= 0.0, "alpha must be finite and >= 0 in every frame");
+        QMRI_CHECK_ARG(ctx, std::isfinite(tr[t]) && tr[t] > 0.0, "tr must be finite and > 0 in every frame");
+        QMRI_CHECK_ARG(ctx, std::isfinite(te[t]) && te[t] >= 0.0, "te must be finite and >= 0 in every frame");
+        QMRI_CHECK_ARG(ctx, te[t] <= tr[t], "te must not exceed tr in any frame");
+    }
+    if (host_atoms)
+        for (int k = 0; k < K; ++k) {
+            QMRI_CHECK_ARG(ctx, std::isfinite(t1[k]) && t1[k] > 0.0, "t1 must be finite and > 0 for every atom");
+            QMRI_CHECK_ARG(ctx, std::isfinite(t2[k]) && t2[k] > 0.0, "t2 must be finite and > 0 for every atom");
+            QMRI_CHECK_ARG(ctx, !b1 || (std::isfinite(b1[k]) && b1[k] >= 0.0), "b1 must be finite and >= 0 for every atom");
+        }
+    if (!ctx) { qmri_set_error(nullptr, "invalid argument: ctx must not be NULL"); return QMRI_ERR_INVALID_ARG; }
+    return QMRI_OK;
+}
+
+// the schedule on the device (alpha, tr, te: 3 T doubles) and the launch; the stream is idle on return
+int epg_run(qmri_ctx* ctx, int K, int T, const double* alpha, const double* tr, const double* te, const double* d_t1, const double* d_t2,
+            const double* d_b1, const qmri_epg_params& p, void* d_F) {
+    std::vector<double> sched((size_t)3 * T);
+    bool const_timing = true;
+    for (int t = 0; t < T; ++t) {
+        sched[t] = alpha[t]; sched[T + t] = tr[t]; sched[2 * T + t] = te[t];
+        const_timing = const_timing && tr[t] == tr[0] && te[t] == te[0];
+    }
+    DevBuf<double> ds;
+    QMRI_TRY(dev_alloc(ctx, &ds.p, sched.size()));
+    QMRI_HIP(ctx, hipMemcpyAsync(ds.p, sched.data(), sched.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    QMRI_TRY(epg_simulate_dev(ctx, K, T, ds, d_t1, d_t2, d_b1, p, const_timing, d_F));
+    QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return QMRI_OK;
+}
+}  // namespace
+
+extern "C" int qmri_dict_simulate_dev(qmri_ctx* ctx, int K, int T, const double* alpha, const double* tr, const double* te, const double* d_t1,
+                                      const double* d_t2, const double* d_b1, const qmri_epg_params* p, void* d_F_out) {
+    QMRI_TRY(epg_checks(ctx, K, T, alpha, tr, te, d_t1, d_t2, d_b1, p, d_F_out, false));
+    QMRI_HIP(ctx, hipSetDevice(ctx->device));
+    return epg_run(ctx, K, T, alpha, tr, te, d_t1, d_t2, d_b1, *p, d_F_out);
+}
+
+extern "C" int qmri_dict_simulate(qmri_ctx* ctx, int K, int T, const double* alpha, const double* tr, const double* te, const double* t1, const double* t2,
+                                  const double* b1, const qmri_epg_params* p, void* F_out) {
+    QMRI_TRY(epg_checks(ctx, K, T, alpha, tr, te, t1, t2, b1, p, F_out, true));
+    QMRI_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t nF = (size_t)K * T * (p->out_is_f64 ? sizeof(double) : sizeof(float));
+    DevBuf<double> d1, d2, db;
+    DevBuf<unsigned char> dF;
+    QMRI_TRY(dev_alloc(ctx, &d1.p, (size_t)K));
+    QMRI_TRY(dev_alloc(ctx, &d2.p, (size_t)K));
+    if (b1) QMRI_TRY(dev_alloc(ctx, &db.p, (size_t)K));
+    QMRI_TRY(dev_alloc(ctx, &dF.p, nF));
+    QMRI_HIP(ctx, hipMemcpyAsync(d1.p, t1, (size_t)K * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    QMRI_HIP(ctx, hipMemcpyAsync(d2.p, t2, (size_t)K * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (b1) QMRI_HIP(ctx, hipMemcpyAsync(db.p, b1, (size_t)K * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    QMRI_TRY(epg_run(ctx, K, T, alpha, tr, te, d1, d2, db, *p, dF.p));
+    QMRI_HIP(ctx, hipMemcpyAsync(F_out, dF.p, nF, hipMemcpyDeviceToHost, ctx->stream));
+    QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return QMRI_OK;
+}
+
+extern "C" int qmri_debug_epg_shift(qmri_ctx* ctx, int S, int nshift, const double* in, double* out) {
+    QMRI_CHECK_ARG(ctx, in && out, "in / out must not be NULL");
+    QMRI_CHECK_ARG(ctx, S >= 1 && S <= EPG_MAX_S, "S must satisfy 1 <= S <= 256");
+    QMRI_CHECK_ARG(ctx, nshift >= 0 && nshift <= 4096, "nshift must satisfy 0 <= nshift <= 4096");
+    if (!ctx) { qmri_set_error(nullptr, "invalid argument: ctx must not be NULL"); return QMRI_ERR_INVALID_ARG; }
+    QMRI_HIP(ctx, hipSetDevice(ctx->device));
+    DevBuf<double> di, dout;
+    QMRI_TRY(dev_alloc(ctx, &di.p, (size_t)3 * S));
+    QMRI_TRY(dev_alloc(ctx, &dout.p, (size_t)3 * S));
+    QMRI_HIP(ctx, hipMemcpyAsync(di.p, in, (size_t)3 * S * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    QMRI_TRY(epg_shift_dev(ctx, S, nshift, di, dout));
+    QMRI_HIP(ctx, hipMemcpyAsync(out, dout.p, (size_t)3 * S * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return QMRI_OK;
+}

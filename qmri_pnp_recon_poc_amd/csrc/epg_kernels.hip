@@ -1,0 +1,191 @@
+// epg_kernels.hip -- extended-phase-graph simulation of a FISP-MRF dictionary in fp64: an EXTENSION with no reference counterpart (the reference
+// loads dictionaries that are already simulated and compressed).  Definition: include/qmri.h, DESIGN.md section 19.
+//
+// States across lanes: a group of G lanes owns one atom, lane j of the group keeps the R consecutive configuration states n = j R .. j R + R - 1
+// of F+, F-, Z in registers (3 R doubles; S <= G R, the states >= S are held at zero).  RF and relaxation are local to a state; the spoiler is a
+// register rename inside a lane plus one double from the lane below (F+) and one from the lane above (F-): DPP row shifts when the group is one
+// 16-lane row (G = 16), __shfl_up / __shfl_down of width G beyond.  A group never spans two waves (G <= 64).
+//   k_epg<G, R>         a workgroup of NT lanes simulates APW = NT / G atoms, FB frames at a time.  Per block of frames lane j < FB of a group
+//                       computes that frame's cos / sin of alpha_t b1 (and, when TR / TE vary from frame to frame, its four exponentials) once and
+//                       leaves them in LDS, so a transcendental costs 1 / FB per lane and frame; lane 0 of each group stages the signal F+_0 in LDS,
+//                       and after the block the workgroup writes FB x APW values, APW atoms contiguous per frame (8 at S = 32: 64 B).
+//   k_epg_shift<G, R>   the spoiler alone, n times on one atom's given state (qmri_debug_epg_shift: exact-integer test of the lane moves).
+// No atomics, no reduction across atoms: equal inputs give equal bits.
+#include <cmath>
+#include <cstdint>
+#include <limits>
+#include <type_traits>
+#include "qmri_internal.h"
+
+namespace {
+constexpr int NT = 256;          // threads per workgroup
+constexpr int FB = 16;           // frames per block (<= the smallest G)
+constexpr int NQ = 6;            // doubles per atom and frame in LDS: cos, sin, E1(TE), E2(TE), E1(TR - TE), E2(TR - TE)
+constexpr int ROW = FB * NQ + 2; // LDS row stride per atom in doubles (784 B: 16-byte aligned, the groups of a wave fall in distinct banks)
+
+// v of the lane `d` below (d = +1) or above (d = -1) within a 16-lane row, zero past the row's ends
+template <int D> __device__ __forceinline__ double row_move(double v) {
+    constexpr int ctrl = D > 0 ? 0x111 : 0x101;              // row_shr:1 / row_shl:1
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), ctrl, 0xf, 0xf, true);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), ctrl, 0xf, 0xf, true);
+    return __hiloint2double(hi, lo);
+}
+
+// one dephasing unit.  j: the lane's index in its group; S: the number of states kept
+template <int G, int R> __device__ __forceinline__ void epg_shift(double (&fp)[R], double (&fm)[R], int j, int S) {
+    double up, dn;                                           // F+ of the state below this lane's first, F- of the state above its last
+    if constexpr (G == 16) {
+        up = row_move<+1>(fp[R - 1]);
+        dn = row_move<-1>(fm[0]);
+    } else {
+        up = __shfl_up(fp[R - 1], 1, G);
+        dn = __shfl_down(fm[0], 1, G);
+        if (j == G - 1) dn = 0.0;
+    }
+#pragma unroll
+    for (int r = R - 1; r >= 1; --r) fp[r] = fp[r - 1];
+#pragma unroll
+    for (int r = 0; r + 1 < R; ++r) fm[r] = fm[r + 1];
+    fm[R - 1] = dn;
+    fp[0] = j == 0 ? fm[0] : up;                             // F+_0 <- old F-_1 (= the new F-_0)
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+        if (j * R + r >= S) fp[r] = 0.0;                     // the old F+_{S-1} is dropped; F- and Z of the padding are never fed
+}
+
+template <int G, int R>
+__global__ void __launch_bounds__(NT) k_epg(const double* __restrict__ sched, int T, int K, int S, const double* __restrict__ t1, const double* __restrict__ t2,
+                                            const double* __restrict__ b1, int inversion, double ti, double inv_eff, int const_timing,
+                                            void* __restrict__ Fout, int out_f64) {
+    constexpr int APW = NT / G;
+    __shared__ __attribute__((aligned(16))) double sc[APW * ROW];
+    __shared__ double sig[FB * APW];
+    const double *alpha = sched, *tr = sched + T, *te = sched + 2 * T;
+    const int tid = threadIdx.x, g = tid / G, j = tid % G;
+    const long long k0 = (long long)blockIdx.x * APW;
+    const long long k = k0 + g < K ? k0 + g : (long long)K - 1;                  // the lanes past K repeat the last atom and store nothing
+    double T1 = t1[k], T2 = t2[k], B1 = b1 ? b1[k] : 1.0;
+    const double inf = std::numeric_limits<double>::infinity();
+    const bool bad = !(T1 > 0.0 && T1 < inf && T2 > 0.0 && T2 < inf && B1 >= 0.0 && B1 < inf);
+    if (bad) { T1 = 1.0; T2 = 1.0; B1 = 1.0; }                                   // its row becomes NaN at the store
+    double fp[R], fm[R], z[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) fp[r] = fm[r] = z[r] = 0.0;
+    if (j == 0) {
+        z[0] = 1.0;
+        if (inversion) {
+            const double e = exp(-ti / T1);
+            z[0] = (-inv_eff * z[0]) * e + (1.0 - e);
+        }
+    }
+    double ea1 = 0.0, ea2 = 0.0, eb1 = 0.0, eb2 = 0.0;
+    if (const_timing) {
+        const double a = te[0], b = tr[0] - te[0];
+        ea1 = exp(-a / T1); ea2 = exp(-a / T2); eb1 = exp(-b / T1); eb2 = exp(-b / T2);
+    }
+    double* my = sc + g * ROW;
+    for (int t0 = 0; t0 < T; t0 += FB) {
+        const int nf = min(FB, T - t0);
+        __syncthreads();                                     // the previous block's sc and sig have been read
+        if (j < nf) {
+            double s, c;
+            sincos(alpha[t0 + j] * B1, &s, &c);
+            my[j * NQ + 0] = c;
+            my[j * NQ + 1] = s;
+            if (!const_timing) {
+                const double a = te[t0 + j], b = tr[t0 + j] - a;
+                my[j * NQ + 2] = exp(-a / T1);
+                my[j * NQ + 3] = exp(-a / T2);
+                my[j * NQ + 4] = exp(-b / T1);
+                my[j * NQ + 5] = exp(-b / T2);
+            }
+        }
+        __syncthreads();
+        for (int tt = 0; tt < nf; ++tt) {
+            const double2 cs = *reinterpret_cast<const double2*>(my + tt * NQ);
+            const double c = cs.x, s = cs.y, c2 = (1.0 + c) * 0.5, s2 = (1.0 - c) * 0.5;
+            if (!const_timing) {
+                const double2 ea = *reinterpret_cast<const double2*>(my + tt * NQ + 2), eb = *reinterpret_cast<const double2*>(my + tt * NQ + 4);
+                ea1 = ea.x; ea2 = ea.y; eb1 = eb.x; eb2 = eb.y;
+            }
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const double p = fp[r], m = fm[r], zz = z[r];
+                fp[r] = (c2 * p - s2 * m + s * zz) * ea2;
+                fm[r] = (-s2 * p + c2 * m + s * zz) * ea2;
+                z[r] = (-0.5 * s * (p + m) + c * zz) * ea1;
+            }
+            if (j == 0) {
+                z[0] += 1.0 - ea1;
+                sig[tt * APW + g] = bad ? std::numeric_limits<double>::quiet_NaN() : fp[0];
+            }
+#pragma unroll
+            for (int r = 0; r < R; ++r) { fp[r] *= eb2; fm[r] *= eb2; z[r] *= eb1; }
+            if (j == 0) z[0] += 1.0 - eb1;
+            epg_shift<G, R>(fp, fm, j, S);
+        }
+        __syncthreads();
+        if (tid < nf * APW) {                                // FB * APW <= NT: one value per lane, the atoms of a frame contiguous
+            const int tt = tid / APW, a = tid % APW;
+            if (k0 + a < K) {
+                const size_t o = (size_t)(t0 + tt) * (size_t)K + (size_t)(k0 + a);
+                if (out_f64) static_cast<double*>(Fout)[o] = sig[tid];
+                else static_cast<float*>(Fout)[o] = (float)sig[tid];
+            }
+        }
+    }
+}
+
+// st: F+ [S], F- [S], Z [S] of one atom; one group of one wave does the work
+template <int G, int R> __global__ void __launch_bounds__(64) k_epg_shift(int S, int nshift, const double* __restrict__ in, double* __restrict__ out) {
+    const int lane = threadIdx.x, j = lane % G;
+    double fp[R], fm[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int n = j * R + r;
+        fp[r] = n < S ? in[n] : 0.0;
+        fm[r] = n < S ? in[S + n] : 0.0;
+    }
+    for (int i = 0; i < nshift; ++i) epg_shift<G, R>(fp, fm, j, S);
+    if (lane >= G) return;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int n = j * R + r;
+        if (n < S) { out[n] = fp[r]; out[S + n] = fm[r]; out[2 * S + n] = in[2 * S + n]; }
+    }
+}
+
+// (G, R) for S states: (16,1), (32,1), (64,1), (64,2), (64,4)
+template <typename Fn> void epg_dispatch(int S, Fn&& fn) {
+    if (S <= 16) fn(std::integral_constant<int, 16>(), std::integral_constant<int, 1>());
+    else if (S <= 32) fn(std::integral_constant<int, 32>(), std::integral_constant<int, 1>());
+    else if (S <= 64) fn(std::integral_constant<int, 64>(), std::integral_constant<int, 1>());
+    else if (S <= 128) fn(std::integral_constant<int, 64>(), std::integral_constant<int, 2>());
+    else fn(std::integral_constant<int, 64>(), std::integral_constant<int, 4>());
+}
+}  // namespace
+
+int epg_atoms_per_workgroup(int S) {
+    int apw = 0;
+    epg_dispatch(S, [&](auto g, auto) { apw = NT / decltype(g)::value; });
+    return apw;
+}
+
+int epg_simulate_dev(qmri_ctx* ctx, int K, int T, const double* d_sched, const double* d_t1, const double* d_t2, const double* d_b1,
+                     const qmri_epg_params& p, bool const_timing, void* d_F) {
+    static_assert(FB * (NT / 16) <= NT && FB <= 16, "one staged value per lane; a frame block fits the smallest group");
+    epg_dispatch(p.nstates, [&](auto g, auto r) {
+        constexpr int G = decltype(g)::value, R = decltype(r)::value, APW = NT / G;
+        const unsigned grid = (unsigned)(((long long)K + APW - 1) / APW);
+        k_epg<G, R><<<grid, NT, 0, ctx->stream>>>(d_sched, T, K, p.nstates, d_t1, d_t2, d_b1, p.inversion, p.ti, p.inv_eff, const_timing ? 1 : 0, d_F,
+                                                  p.out_is_f64);
+    });
+    QMRI_HIP(ctx, hipGetLastError());
+    return QMRI_OK;
+}
+
+int epg_shift_dev(qmri_ctx* ctx, int S, int nshift, const double* d_in, double* d_out) {
+    epg_dispatch(S, [&](auto g, auto r) { k_epg_shift<decltype(g)::value, decltype(r)::value><<<1, 64, 0, ctx->stream>>>(S, nshift, d_in, d_out); });
+    QMRI_HIP(ctx, hipGetLastError());
+    return QMRI_OK;
+}

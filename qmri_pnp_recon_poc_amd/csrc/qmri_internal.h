@@ -350,6 +350,13 @@ int dsvd_gram_dev(qmri_ctx* ctx, int K, int T, const void* d_F, bool f64, double
 int dsvd_gq_dev(qmri_ctx* ctx, int T, int b, const double* d_G, const double* d_Q, double* d_Z);                               // Z = G Q (T x b)
 int dsvd_project_dev(qmri_ctx* ctx, int K, int T, int s, const void* d_F, bool f64, const double* d_V, float* d_D, float* d_normD);
 
+// FISP dictionary simulation by extended phase graphs (epg_kernels.hip, api_epg.cpp).  All d_ pointers are device pointers;
+// d_sched holds alpha, tr, te (3 T doubles); the launches go to ctx->stream and are not waited for.
+int epg_atoms_per_workgroup(int S);      // atoms a workgroup simulates (= the contiguous run of its stores) with S states
+int epg_simulate_dev(qmri_ctx* ctx, int K, int T, const double* d_sched, const double* d_t1, const double* d_t2, const double* d_b1 /* or NULL */,
+                     const qmri_epg_params& p, bool const_timing, void* d_F);
+int epg_shift_dev(qmri_ctx* ctx, int S, int nshift, const double* d_in, double* d_out);      // the spoiler alone on one atom's state (3 S doubles)
+
 // ---------------------------------------------------------------------------------------------------
 // trajectory (NUFFT) operator (nufft_kernels.hip, api_nufft.cpp).  Planned once on the host per qmri_set_operator_nufft:
 // samples sorted by the 16 x 16 tile of the 2N x 2M oversampled grid that holds their position ("bins"), and for the output-driven spreading the

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import AdmmParams, CcParams, CsmInfo, CsmParams, DsvdInfo, DsvdParams, LrtvInfo, LrtvParams, NetDesc, NufftParams, Profile
+from ._lib import AdmmParams, CcParams, CsmInfo, CsmParams, DsvdInfo, DsvdParams, EpgParams, LrtvInfo, LrtvParams, NetDesc, NufftParams, Profile
 
 ARCH_UNETRES, ARCH_SEQ_CONV = 0, 1
 SOLVER_LSQR, SOLVER_DIRECT = 0, 1
@@ -70,6 +70,48 @@ def real_dictionary_array(a, name: str, dtype):
                              f"(dict.D real, as in the reference's real_fisp dictionaries); pass real({name}) if that is what is meant")
         a = a.real
     return np.asarray(a, dtype=dtype)
+
+
+def simulation_arguments(alpha, tr, te, t1, t2, b1, nstates, inversion, ti, inv_eff, dtype):
+    """The arguments of Engine.simulate_dictionary as the library takes them: (alpha [T], tr [T], te [T], t1 [K], t2 [K], b1 [K] or None, EpgParams),
+    contiguous float64.  A scalar tr or te is broadcast to T; t1, t2 and b1 are broadcast against each other and flattened."""
+    a = np.ascontiguousarray(np.asarray(alpha, dtype=np.float64).ravel())
+    T = a.size
+    if not (1 <= T <= 1024):
+        raise ValueError("alpha must hold 1 <= T <= 1024 flip angles")
+    sched = []
+    for name, v in (("tr", tr), ("te", te)):
+        v = np.asarray(v, dtype=np.float64)
+        if v.ndim > 1 or (v.ndim == 1 and v.size != T):
+            raise ValueError(f"{name} must be a scalar or hold one value per frame ({T})")
+        sched.append(np.ascontiguousarray(np.broadcast_to(v, (T,))))
+    if np.iscomplexobj(t1) or np.iscomplexobj(t2) or np.iscomplexobj(b1) or np.iscomplexobj(alpha):
+        raise ValueError("alpha, t1, t2 and b1 must be real")
+    atoms = [np.asarray(t1, dtype=np.float64), np.asarray(t2, dtype=np.float64)] + ([np.asarray(b1, dtype=np.float64)] if b1 is not None else [])
+    atoms = [np.ascontiguousarray(x.ravel()) for x in np.broadcast_arrays(*atoms)]
+    if atoms[0].size < 1:
+        raise ValueError("t1 and t2 must hold at least one atom")
+    if int(nstates) != nstates or not (1 <= int(nstates) <= 256):
+        raise ValueError("nstates must be an integer in 1..256")
+    if np.dtype(dtype) not in (np.dtype(np.float64), np.dtype(np.float32)):
+        raise ValueError("dtype must be float64 or float32")
+    if inversion and (not (float(ti) >= 0.0 and np.isfinite(ti)) or not (0.0 < float(inv_eff) <= 1.0)):
+        raise ValueError("ti must be >= 0 and inv_eff in (0, 1]")
+    p = EpgParams(int(nstates), 1 if inversion else 0, float(ti), float(inv_eff), int(np.dtype(dtype) == np.dtype(np.float64)))
+    return a, sched[0], sched[1], atoms[0], atoms[1], atoms[2] if b1 is not None else None, p
+
+
+def _hip_runtime():
+    """The HIP runtime through ctypes, for the few calls that keep an intermediate result on the device between two library calls."""
+    import os
+    try:
+        hip = C.CDLL("libamdhip64.so")
+    except OSError:
+        hip = C.CDLL(os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "libamdhip64.so"))
+    hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    hip.hipFree.argtypes = [C.c_void_p]
+    return hip
 
 
 def build_spiral(N: int, S: int, T: int):
@@ -600,6 +642,57 @@ class Engine:
                                               C.byref(info)))
         r = got.value
         return {"V": V[: T * r].reshape((T, r), order="F"), "D": D[: K * r].reshape((K, r), order="F"), "normD": nd, "eig": eig[:r].copy(),
+                "info": {"s": int(info.s), "iters": int(info.iters), "converged": int(info.converged), "energy_reached": int(info.energy_reached),
+                         "max_resid": float(info.max_resid), "energy_kept": float(info.energy_kept)}}
+
+    def simulate_dictionary(self, alpha, tr, te, t1, t2, b1=None, nstates=32, inversion=True, ti=0.0, inv_eff=1.0, dtype=np.float64):
+        """The fingerprints of a FISP-MRF sequence by extended phase graphs on the device (extension, no reference counterpart; include/qmri.h
+        qmri_dict_simulate).  alpha [T] flip angles in radians, T <= 1024; tr, te in seconds, scalars (broadcast to T) or [T]; t1, t2 (seconds)
+        and b1 (transmit scale, None: 1) are broadcast against each other and flattened to the K atoms.  nstates: configuration states kept
+        (1..256; the truncation is part of the result).  inversion: an inversion pulse of efficiency inv_eff, TI = ti before the train.
+        Returns F [K, T] in dtype (float64, or float32: the float64 result rounded once).  Needs no operator."""
+        a, trv, tev, T1, T2, B1, p = simulation_arguments(alpha, tr, te, t1, t2, b1, nstates, inversion, ti, inv_eff, dtype)
+        K, T = T1.size, a.size
+        F = np.empty(K * T, np.float64 if p.out_is_f64 else np.float32)
+        self._check(self.L.qmri_dict_simulate(self.h, K, T, _vp(a), _vp(trv), _vp(tev), _vp(T1), _vp(T2), _vp(B1), C.byref(p), _vp(F)))
+        return F.reshape((K, T), order="F")
+
+    def simulate_compress_dictionary(self, alpha, tr, te, t1, t2, b1=None, s=None, energy=None, s_max=16, nstates=32, inversion=True, ti=0.0,
+                                     inv_eff=1.0):
+        """simulate_dictionary followed by compress_dictionary on the same device buffer: the K x T float64 fingerprints never leave the device.
+        Returns what compress_dictionary returns."""
+        if (s is None) == (energy is None):
+            raise ValueError("give exactly one of s and energy")
+        a, trv, tev, T1, T2, B1, p = simulation_arguments(alpha, tr, te, t1, t2, b1, nstates, inversion, ti, inv_eff, np.float64)
+        K, T = T1.size, a.size
+        if s is not None and (int(s) != s or not (1 <= int(s) <= min(16, K, T))):
+            raise ValueError(f"s must be an integer with 1 <= s <= min(16, K, T) = {min(16, K, T)}")
+        if s is None and (int(s_max) != s_max or not (1 <= int(s_max) <= 16) or not (0.0 < float(energy) <= 1.0)):
+            raise ValueError("energy must be in (0, 1] and s_max an integer in 1..16")
+        q = DsvdParams(0 if s is None else int(s), int(s_max), 0.0 if energy is None else float(energy), 0.0, 0)
+        V, D, nd, eig = np.empty(T * 16, np.float64), np.empty(K * 16, np.float32), np.empty(K, np.float32), np.empty(16, np.float64)
+        got, info = C.c_int(0), DsvdInfo()
+        hip = _hip_runtime()
+        bufs = [C.c_void_p() for _ in range(7)]
+        d_t1, d_t2, d_b1, d_F, d_V, d_D, d_n = bufs
+        try:
+            for d, nb in ((d_t1, K * 8), (d_t2, K * 8), (d_b1, K * 8), (d_F, K * T * 8), (d_V, V.nbytes), (d_D, D.nbytes), (d_n, nd.nbytes)):
+                if hip.hipMalloc(C.byref(d), nb) != 0:
+                    raise MemoryError(f"hipMalloc of {nb} bytes failed")
+            for d, h in ((d_t1, T1), (d_t2, T2)) + (((d_b1, B1),) if B1 is not None else ()):
+                if hip.hipMemcpy(d, _vp(h), h.nbytes, 1) != 0:
+                    raise RuntimeError("hipMemcpy to the device failed")
+            self._check(self.L.qmri_dict_simulate_dev(self.h, K, T, _vp(a), _vp(trv), _vp(tev), d_t1, d_t2, d_b1 if B1 is not None else None, C.byref(p), d_F))
+            self._check(self.L.qmri_dict_compress_dev(self.h, K, T, d_F, 1, C.byref(q), C.byref(got), d_V, d_D, d_n, _vp(eig), C.byref(info)))
+            for d, h in ((d_V, V), (d_D, D), (d_n, nd)):
+                if hip.hipMemcpy(_vp(h), d, h.nbytes, 2) != 0:
+                    raise RuntimeError("hipMemcpy from the device failed")
+        finally:
+            for d in bufs:
+                if d.value:
+                    hip.hipFree(d)
+        r = got.value
+        return {"V": V[: T * r].reshape((T, r), order="F").copy(), "D": D[: K * r].reshape((K, r), order="F").copy(), "normD": nd, "eig": eig[:r].copy(),
                 "info": {"s": int(info.s), "iters": int(info.iters), "converged": int(info.converged), "energy_reached": int(info.energy_reached),
                          "max_resid": float(info.max_resid), "energy_kept": float(info.energy_kept)}}
 

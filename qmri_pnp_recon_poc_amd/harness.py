@@ -6,6 +6,8 @@ Host logic in numpy/scipy; the reconstruction and the match run on the GPU throu
   load_mat(path)                       `load(...)` of a MATLAB file: v5/v7 (scipy.io) or -v7.3 (HDF5; mat73.py, no HDF5 library needed)
   load_dictionary(path)                `load(dict_dir); V = real(dict.V)`                     main_recon_tsmis_FFT.m:121-130
   compress_dictionary(dic, s | energy) an uncompressed (s = T) dictionary -> the SVD-compressed fields, on the GPU (extension)
+  simulate_dictionary(alpha, tr, te, t1_grid, t2_grid, s | energy)  a FISP dictionary by extended phase graphs, simulated and compressed on the GPU
+                                       (extension)
   load_tsmi(path) / crop_tsmi(X)       `load(tsmi_dir); X0 = X((4:227),(4:227),:)`            :199-212
   load_qmaps(path, slice)              qmap(slice,:,:,:) -> N x M x 3, cropped the same way   :177-189
   getmask_fromPD(PD, thresh)           foreground mask                                         getmask_fromPD.m:9-15
@@ -26,7 +28,7 @@ from __future__ import annotations
 
 import numpy as np
 
-__all__ = ["load_mat", "load_dictionary", "compress_dictionary", "load_tsmi", "crop_tsmi", "load_qmaps", "getmask_fromPD", "awgn_measured",
+__all__ = ["load_mat", "load_dictionary", "compress_dictionary", "simulate_dictionary", "load_tsmi", "crop_tsmi", "load_qmaps", "getmask_fromPD", "awgn_measured",
            "psnr", "ssim", "metrics", "recon_tsmis", "synthesize_tsmis", "training_volume", "save_training_pickle"]
 
 CROP = slice(3, 227)          # MATLAB (4:227): 230 -> 224                                       main_recon_tsmis_FFT.m:189,212
@@ -75,6 +77,27 @@ def compress_dictionary(dic, s=None, energy=None, s_max=16, device=0):
     finally:
         eng.close()
     return {"V": out["V"], "D": out["D"], "normD": out["normD"], "lut": np.asarray(dic["lut"], dtype=np.float32), "eig": out["eig"], "info": out["info"]}
+
+
+def simulate_dictionary(alpha, tr, te, t1_grid, t2_grid, s=None, energy=None, nstates=32, inversion=True, ti=0.0, inv_eff=1.0, b1=None, s_max=16,
+                        device=0):
+    """A FISP-MRF dictionary from a flip-angle train: the fingerprints of every (T1, T2) of the grid by extended phase graphs
+    (Engine.simulate_dictionary), then their SVD compression (Engine.compress_dictionary) on the same device buffer -- the K x T fingerprints
+    never cross to the host.  An extension; the reference only loads compressed files.  The atoms are the ij-meshgrid of t1_grid and t2_grid as
+    synth.make_dictionary orders it (T2 fastest), lut = (T1, T2).  Atoms with T2 > T1 are kept: a caller who wants only the physical ones filters
+    the grid (or the result) itself.  b1: one transmit scale for all atoms, or None.  Give the rank s or the energy to keep.  Returns the fields
+    of load_dictionary (V, D, normD, lut) plus eig and info; recon_tsmis runs on the result unchanged."""
+    from .engine import Engine
+    t1g, t2g = np.asarray(t1_grid, dtype=np.float64).ravel(), np.asarray(t2_grid, dtype=np.float64).ravel()
+    T1, T2 = (a.ravel() for a in np.meshgrid(t1g, t2g, indexing="ij"))
+    eng = Engine(device)
+    try:
+        out = eng.simulate_compress_dictionary(alpha, tr, te, T1, T2, b1=b1, s=s, energy=energy, s_max=s_max, nstates=nstates, inversion=inversion,
+                                               ti=ti, inv_eff=inv_eff)
+    finally:
+        eng.close()
+    return {"V": out["V"], "D": out["D"], "normD": out["normD"], "lut": np.ascontiguousarray(np.stack([T1, T2], axis=1).astype(np.float32)),
+            "eig": out["eig"], "info": out["info"]}
 
 
 def crop_tsmi(X):

@@ -23,6 +23,7 @@
 //   * 'coil_compress' compresses a multi-coil stack to virtual coils (qmri_coil_compress; extension).
 //   * 'coil_maps' estimates coil sensitivity maps from calibration data (qmri_coil_maps; extension).
 //   * 'dict_compress' compresses a simulated dictionary to its SVD subspace (qmri_dict_compress; extension); it needs no plan.
+//   * 'dict_simulate' simulates the fingerprints of a FISP-MRF sequence by extended phase graphs (qmri_dict_simulate; extension); it needs no plan.
 // tests/cpp/mex_mock.cpp is a small stand-in for the MATLAB runtime's C API under which this file is compiled, LINKED against libqmri.so and
 // driven command by command on the GPU box (tests/test_gpu_mex.py); with MATLAB's own mex.h nothing here changes.
 #include "mex.h"
@@ -598,6 +599,49 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
             plhs[4] = mxCreateStructMatrix(1, 1, 6, names);
             for (int k = 0; k < 6; ++k) mxSetFieldByNumber(plhs[4], 0, k, mxCreateDoubleScalar(vals[k]));
         }
+    } else if (c == "dict_simulate") {               // F = qmri_mex('dict_simulate', alpha, tr, te, t1, t2, b1, params)
+        // extension (no reference counterpart): the fingerprints of a FISP-MRF sequence by extended phase graphs (qmri_dict_simulate).  alpha: T flip
+        // angles in radians, T <= 1024; tr, te: T values or one, seconds; t1, t2: K values each, seconds; b1: K values or [] (1); all real double.
+        // params: a struct with the optional nstates (32), inversion (1), ti (0), inv_eff (1), single (0: F double; 1: F single).  F is K x T.
+        need(nrhs, 8, "F = qmri_mex('dict_simulate', alpha, tr, te, t1, t2, b1, params)");
+        want(mxIsStruct(prhs[7]), "qmri:dict_simulate:params", "params must be a struct (fields nstates, inversion, ti, inv_eff, single)");
+        auto real_vec = [](const mxArray* a, const char* id, const char* msg) {
+            want(mxIsDouble(a) && !mxIsComplex(a), id, msg);
+            return mxGetNumberOfElements(a);
+        };
+        const size_t T = real_vec(prhs[1], "qmri:dict_simulate:alpha", "alpha must be a real double vector (complex flip angles are not supported)");
+        want(T >= 1 && T <= 1024, "qmri:dict_simulate:alpha", "alpha must hold 1 <= T <= 1024 flip angles");
+        std::vector<double> sched[2];
+        const char* sid[2] = {"qmri:dict_simulate:tr", "qmri:dict_simulate:te"};
+        for (int q = 0; q < 2; ++q) {
+            const size_t n = real_vec(prhs[2 + q], sid[q], "tr / te must be real double, one value or one per frame");
+            want(n == 1 || n == T, sid[q], "tr / te must be real double, one value or one per frame");
+            sched[q].resize(T);
+            for (size_t t = 0; t < T; ++t) sched[q][t] = mxGetDoubles(prhs[2 + q])[n == 1 ? 0 : t];
+        }
+        const char* aid = "qmri:dict_simulate:atoms";
+        const size_t K = real_vec(prhs[4], aid, "t1, t2 and b1 must be real double (complex values are not supported)");
+        want(K >= 1 && K <= ((size_t)1 << 30) && real_vec(prhs[5], aid, "t1, t2 and b1 must be real double (complex values are not supported)") == K, aid,
+             "t1 and t2 must hold the same number K >= 1 of atoms");
+        const bool has_b1 = mxGetNumberOfElements(prhs[6]) > 0;
+        if (has_b1) want(real_vec(prhs[6], aid, "t1, t2 and b1 must be real double (complex values are not supported)") == K, aid, "b1 must be [] or hold K values");
+        const mxArray* P = prhs[7];
+        const mxArray* f;
+        const char* pid = "qmri:dict_simulate:params";
+        qmri_epg_params p = {32, 1, 0.0, 1.0, 1};
+        if ((f = mxGetField(P, 0, "nstates"))) p.nstates = int_arg(f, 1, 256, pid, "params.nstates must be an integer in [1, 256]");
+        if ((f = mxGetField(P, 0, "inversion"))) p.inversion = int_arg(f, 0, 1, pid, "params.inversion must be 0 or 1");
+        if ((f = mxGetField(P, 0, "single"))) p.out_is_f64 = 1 - int_arg(f, 0, 1, pid, "params.single must be 0 or 1");
+        p.ti = scalar_field(P, "ti", 0.0);
+        p.inv_eff = scalar_field(P, "inv_eff", 1.0);
+        want(std::isfinite(p.ti) && p.ti >= 0.0, pid, "params.ti must be finite and >= 0");
+        want(p.inv_eff > 0.0 && p.inv_eff <= 1.0, pid, "params.inv_eff must be in (0, 1]");
+        mxArray* Fo = mxCreateNumericMatrix(K, T, p.out_is_f64 ? mxDOUBLE_CLASS : mxSINGLE_CLASS, mxREAL);
+        const int st = qmri_dict_simulate(ctx(), (int)K, (int)T, mxGetDoubles(prhs[1]), sched[0].data(), sched[1].data(), mxGetDoubles(prhs[4]), mxGetDoubles(prhs[5]),
+                                          has_b1 ? mxGetDoubles(prhs[6]) : nullptr, &p, mxGetData(Fo));
+        if (st != QMRI_OK) mxDestroyArray(Fo);
+        check(st);
+        plhs[0] = Fo;
     } else if (c == "lrtv") {                        // [x, info] = qmri_mex('lrtv', y, param_struct, [N M s])   (FISTA_deep, main_recon_tsmis_FFT.m:273-282)
         need(nrhs, 4, "[x, info] = qmri_mex('lrtv', y, param, [N M s])");
         const mxArray* P = prhs[2];
