@@ -282,6 +282,39 @@ int qmri_dict_match_xfit(qmri_ctx* ctx, const void* X, int Npix, float* qmap, fl
 int qmri_dict_match_xfit_dev(qmri_ctx* ctx, const void* d_X, int Npix, float* d_qmap, float* d_pd, float* d_mt,
                              int32_t* d_dm, float* d_xfit);
 
+/* ---- groups of a dictionary and the grouped match (extension, no reference counterpart, parity unpinned) ---------- */
+/* A dictionary simulated over a transmit-field axis (qmri_dict_simulate: atoms carry T1, T2 and b1) is matched per pixel against the atoms of
+ * that pixel's MEASURED B1 only (B1-corrected MRF: Buonincontri & Sawiak 2016; Ma et al. 2017) -- 1/G of the products of a match over all atoms,
+ * and no attempt to estimate B1 from the fingerprint.  The reference's mrf_dtm_cpu.m has one flat list of atoms.
+ *
+ * Groups.  The dictionary of qmri_set_dictionary (narrow form, s <= 16) is given G groups: group g holds atoms group_ptr[g] .. group_ptr[g+1]-1
+ * (0-based) and has the selector value group_val[g] (e.g. its b1).  1 <= G <= 256, group_ptr[0] == 0, group_ptr[G] == K, group_ptr strictly
+ * increasing (no empty group), group_val finite and strictly ascending; anything else, NULL arrays included: QMRI_ERR_INVALID_ARG.  G = 0 clears
+ * the groups (the arrays are not read).  No dictionary set: QMRI_ERR_STATE.  A wide dictionary (s > 16, the channel-blocked match):
+ * QMRI_ERR_UNSUPPORTED -- groups for wide dictionaries are not implemented.  qmri_set_dictionary drops the groups.  Setting groups changes nothing
+ * about qmri_dict_match*: those still match all K atoms, with the same bits.  A call that fails, for whatever reason, leaves the groups as they
+ * were.  (Costs a second device copy of the packed dictionary in which every
+ * group starts on a 32-atom tile.) */
+int qmri_set_dictionary_groups(qmri_ctx* ctx, int G, const int32_t* group_ptr, const double* group_val);
+/* Assignment.  For a selector value b, g(b) is the LOWEST g that minimises fabs(b - group_val[g]), evaluated in fp64: values outside the range of
+ * group_val go to the end groups, an exact midpoint goes to the lower group, and a non-finite b (NaN, +-Inf) means UNMATCHED.  This is that rule
+ * on the host, without a context: grp_out[i] = g(sel[i]) + 1, or 0 for unmatched, i < n.  The grouped match gives the same integers.
+ * 1 <= G <= 256, group_val finite and strictly ascending, n >= 0, no NULL array (sel / grp_out may be NULL when n == 0): else QMRI_ERR_INVALID_ARG. */
+int qmri_dict_group_assign(int G, const double* group_val, int n, const double* sel, int32_t* grp_out);
+/* Grouped match.  X, qmap, pd, mt, dm and xfit exactly as in qmri_dict_match_xfit (every output nullable); sel: Npix doubles, the selector map;
+ * grp (nullable): the 1-based group of each pixel, 0 for unmatched.  Needs qmri_set_dictionary and qmri_set_dictionary_groups (else QMRI_ERR_STATE).
+ * For a pixel p with g = g(sel[p]) the outputs are, BIT FOR BIT, what qmri_dict_match_xfit returns for that pixel on a dictionary holding only rows
+ * group_ptr[g] .. group_ptr[g+1]-1 of D / normD / lut, with dm shifted by group_ptr[g] (so dm indexes the whole dictionary, 1-based): the
+ * single-precision products and magnitudes of mrf_dtm_cpu.m:91-96, ties going to the first index OF THE GROUP, NaN in lut -> 0 (:136-160).
+ * An unmatched pixel gets dm = 0, grp = 0, mt = 0, pd = 0, every qmap column 0 and xfit 0, and costs no atom work: a NaN outside the body in the B1
+ * map is the foreground mask.  A pixel's result depends neither on the other pixels of the call, nor on their order, nor on the filter switch
+ * (qmri_debug_dict_filter). */
+int qmri_dict_match_grouped(qmri_ctx* ctx, const void* X, int Npix, const double* sel, float* qmap, float* pd, float* mt, int32_t* dm, int32_t* grp,
+                            float* xfit);
+/* The same on device arrays, asynchronous on ctx's stream. */
+int qmri_dict_match_grouped_dev(qmri_ctx* ctx, const void* d_X, int Npix, const double* d_sel, float* d_qmap, float* d_pd, float* d_mt, int32_t* d_dm,
+                                int32_t* d_grp, float* d_xfit);
+
 /* ---- TSMI synthesis from quantitative maps: main_synthesize_tsmis.m:54,82-100 (mode 'real') ------------ */
 /* I = knnsearch(KDTreeSearcher(dict.lut), qm(:,1:2)); X = real(dict.D(I,:)) .* dict.normD(I) .* abs(qm(:,3)); X .* sign(X(:,:,1)).
  * qmap: Npix x 3 doubles column-major (T1, T2, PD, in the units of dict.lut); X_out: Npix x s singles column-major;

@@ -1,4 +1,5 @@
-// api_dict.cpp -- dictionary match of libqmri.so: the dictionary's device form (qmri_set_dictionary) and the qmri_dict_match* entry points.
+// api_dict.cpp -- dictionary match of libqmri.so: the dictionary's device form (qmri_set_dictionary), its groups (qmri_set_dictionary_groups) and the
+// qmri_dict_match* entry points.
 //
 // Replaces (reference file:line): mrf_dtm_cpu.m:1-166.
 #include "qmri_internal.h"
@@ -7,6 +8,7 @@
 #include <cmath>
 
 void qmri_free_dict(qmri_ctx* ctx) {
+    dictg_free(ctx);
     DictHost& d = ctx->dict;
     void* ptrs[] = { d.d_pack, d.d_pack16, d.d_gmax, d.d_normD, d.d_lut, d.d_part, d.d_xp, d.d_win };
     for (void* p : ptrs) if (p) (void)hipFree(p);
@@ -141,4 +143,72 @@ extern "C" int qmri_dict_match_xfit(qmri_ctx* ctx, const void* X, int Npix, floa
 
 extern "C" int qmri_dict_match(qmri_ctx* ctx, const void* X, int Npix, float* qmap, float* pd, float* mt, int32_t* dm) {
     return qmri_dict_match_xfit(ctx, X, Npix, qmap, pd, mt, dm, nullptr);
+}
+
+// ---- groups of a dictionary and the grouped match (extension) ----------------------------------------------------------
+extern "C" int qmri_set_dictionary_groups(qmri_ctx* ctx, int G, const int32_t* group_ptr, const double* group_val) {
+    if (!ctx) return QMRI_ERR_INVALID_ARG;
+    if (G == 0) {                                                       // clears
+        QMRI_HIP(ctx, hipSetDevice(ctx->device));
+        QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        dictg_free(ctx);
+        return QMRI_OK;
+    }
+    QMRI_CHECK_ARG(ctx, G >= 1 && G <= 256, "1 <= G <= 256 groups (0 clears)");
+    QMRI_CHECK_ARG(ctx, group_ptr && group_val, "group_ptr / group_val must not be NULL");
+    for (int g = 0; g < G; ++g) {
+        QMRI_CHECK_ARG(ctx, group_ptr[g + 1] > group_ptr[g], "group_ptr must be strictly increasing (no empty group)");
+        QMRI_CHECK_ARG(ctx, std::isfinite(group_val[g]) && (g == 0 || group_val[g] > group_val[g - 1]), "group_val must be finite and strictly ascending");
+    }
+    QMRI_CHECK_ARG(ctx, group_ptr[0] == 0, "group_ptr[0] must be 0");
+    if (!ctx->dict.ready) { qmri_set_error(ctx, "dictionary not set: call qmri_set_dictionary first"); return QMRI_ERR_STATE; }
+    if (ctx->dict.wide) { qmri_set_error(ctx, "groups are supported for dictionaries of s <= 16 channels (got %d)", ctx->dict.s); return QMRI_ERR_UNSUPPORTED; }
+    QMRI_CHECK_ARG(ctx, group_ptr[G] == ctx->dict.K, "group_ptr[G] must be K");
+    QMRI_HIP(ctx, hipSetDevice(ctx->device));
+    return dictg_set_groups(ctx, G, group_ptr, group_val);
+}
+
+static int grouped_ready(qmri_ctx* ctx, const void* X, int Npix, const double* sel) {
+    if (!ctx->dict.ready) { qmri_set_error(ctx, "dictionary not set: call qmri_set_dictionary first"); return QMRI_ERR_STATE; }
+    if (!ctx->dict.G) { qmri_set_error(ctx, "dictionary groups not set: call qmri_set_dictionary_groups first"); return QMRI_ERR_STATE; }
+    QMRI_CHECK_ARG(ctx, X && sel && Npix > 0, "X / sel must not be NULL and Npix > 0");
+    return QMRI_OK;
+}
+
+extern "C" int qmri_dict_match_grouped_dev(qmri_ctx* ctx, const void* d_X, int Npix, const double* d_sel, float* d_qmap, float* d_pd, float* d_mt, int32_t* d_dm,
+                                           int32_t* d_grp, float* d_xfit) {
+    if (!ctx) return QMRI_ERR_INVALID_ARG;
+    QMRI_HIP(ctx, hipSetDevice(ctx->device));
+    QMRI_TRY(grouped_ready(ctx, d_X, Npix, d_sel));
+    return dictg_launch(ctx, (const double2*)d_X, Npix, d_sel, d_qmap, d_pd, d_mt, d_dm, d_grp, (float2*)d_xfit);
+}
+
+extern "C" int qmri_dict_match_grouped(qmri_ctx* ctx, const void* X, int Npix, const double* sel, float* qmap, float* pd, float* mt, int32_t* dm, int32_t* grp,
+                                       float* xfit) {
+    if (!ctx) return QMRI_ERR_INVALID_ARG;
+    QMRI_HIP(ctx, hipSetDevice(ctx->device));
+    QMRI_TRY(grouped_ready(ctx, X, Npix, sel));
+    const DictHost& d = ctx->dict;
+    const size_t nx = (size_t)Npix * d.s;
+    DevBuf<double2> dX; DevBuf<double> dsel; DevBuf<float> dq, dp, dmt; DevBuf<int32_t> ddm, dgrp; DevBuf<float2> dxf;
+    auto fail = [&](const char* what) { qmri_set_error(ctx, "%s failed in qmri_dict_match_grouped", what); return QMRI_ERR_HIP; };
+    if (hipMalloc((void**)&dX.p, nx * sizeof(double2)) != hipSuccess) return fail("hipMalloc");
+    if (hipMalloc((void**)&dsel.p, (size_t)Npix * sizeof(double)) != hipSuccess) return fail("hipMalloc");
+    if (qmap && hipMalloc((void**)&dq.p, (size_t)Npix * d.Q * sizeof(float)) != hipSuccess) return fail("hipMalloc");
+    if (pd && hipMalloc((void**)&dp.p, (size_t)Npix * 2 * sizeof(float)) != hipSuccess) return fail("hipMalloc");
+    if (mt && hipMalloc((void**)&dmt.p, (size_t)Npix * sizeof(float)) != hipSuccess) return fail("hipMalloc");
+    if (dm && hipMalloc((void**)&ddm.p, (size_t)Npix * sizeof(int32_t)) != hipSuccess) return fail("hipMalloc");
+    if (grp && hipMalloc((void**)&dgrp.p, (size_t)Npix * sizeof(int32_t)) != hipSuccess) return fail("hipMalloc");
+    if (xfit && hipMalloc((void**)&dxf.p, nx * sizeof(float2)) != hipSuccess) return fail("hipMalloc");
+    if (hipMemcpyAsync(dX, X, nx * sizeof(double2), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return fail("H2D copy");
+    if (hipMemcpyAsync(dsel, sel, (size_t)Npix * sizeof(double), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return fail("H2D copy");
+    QMRI_TRY(dictg_launch(ctx, dX, Npix, dsel, dq, dp, dmt, ddm, dgrp, dxf));
+    if (qmap && hipMemcpyAsync(qmap, dq, (size_t)Npix * d.Q * sizeof(float), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return fail("D2H copy");
+    if (pd && hipMemcpyAsync(pd, dp, (size_t)Npix * 2 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return fail("D2H copy");
+    if (mt && hipMemcpyAsync(mt, dmt, (size_t)Npix * sizeof(float), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return fail("D2H copy");
+    if (dm && hipMemcpyAsync(dm, ddm, (size_t)Npix * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return fail("D2H copy");
+    if (grp && hipMemcpyAsync(grp, dgrp, (size_t)Npix * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return fail("D2H copy");
+    if (xfit && hipMemcpyAsync(xfit, dxf, nx * sizeof(float2), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return fail("D2H copy");
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return fail("synchronize");
+    return QMRI_OK;
 }

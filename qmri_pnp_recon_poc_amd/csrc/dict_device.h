@@ -105,3 +105,21 @@ __device__ __forceinline__ float dict_atom(const DictView& v, int a, int c) {
     if (v.wide) return v.pack[(((size_t)(a >> 5) * v.G8 + (c >> 3)) * 64 + lane) * 4 + ((c & 7) >> 1)];
     return v.pack[((size_t)(a >> 5) * 64 + lane) * v.npl + (c >> 1)];
 }
+
+// A grouped match (qmri_dict_match_grouped) as the match kernels see it.  Pixels sit in SLOTS, bucketed by group and each
+// group's count padded to the workgroup's pixel width, so that the pixels of a workgroup share a group; the atoms come from a second pack in
+// which every group starts on a 32-atom tile (its last tile padded with all-zero rows, which follow every real atom of the group).  A workgroup
+// of slot tile b walks the tiles [gtile[g], gtile[g + 1]) of that pack, g = tile_grp[b]; an index 32 t + row of it is atom
+// gptr[g] + (32 t + row - 32 gtile[g]) of the dictionary -- monotone within the group, so ties resolve as they do on global indices.
+struct DictGroupView {
+    const int* slot_pix;        // [slot] pixel, -1: padding
+    const int* tile_grp;        // [slot tile] group, 0-based
+    const int* slot_beg;        // [G + 1] first slot of a group; slot_beg[G] = slots in use
+    const int* gtile;           // [G + 1] first tile of a group in the group-padded packs
+    const int* gptr;            // [G + 1] group_ptr
+    int G, slot_cap;            // slot_cap: stride of the per-part candidates
+};
+__device__ __forceinline__ int dict_group_atom(const DictGroupView& gv, int g, int bidx) {
+    const int lo = gv.gptr[g], a = bidx - 32 * gv.gtile[g] + lo;
+    return (a < lo || a >= gv.gptr[g + 1]) ? lo : a;                 // cannot happen: padded atoms are all-zero and never beat a real one
+}

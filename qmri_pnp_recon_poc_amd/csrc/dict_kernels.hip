@@ -54,12 +54,13 @@ __device__ __forceinline__ void exact_tile(int t, int h, const f32x4 (&av)[NV], 
 
 // D packed as MFMA A-fragments, all pairs of a lane together: pack[tile][lane][q] = D[tile*32 + (lane&31)][2q + (lane>>5)]  (0 beyond K or s;
 // NPL = 4 or 8 floats per lane, so a tile is one or two 16-byte requests per lane instead of one 4-byte request per pair)
-template <int NPAIR>
+// GRP (qmri_dict_match_grouped): blockIdx.x is a slot tile of one group, `pack` the group-padded pack and the atom tiles are that group's (DictGroupView)
+template <int NPAIR, bool GRP = false>
 __global__ __launch_bounds__(NT) void k_dict_match(const double2* __restrict__ X, int Npix, int s, const float* __restrict__ pack,
                                                     int ntiles_all, int K, const float* __restrict__ normD,
                                                     const float* __restrict__ lut, int Q, float* __restrict__ qmap,
                                                     float* __restrict__ pd, float* __restrict__ mt, int32_t* __restrict__ dm,
-                                                    float4* __restrict__ part, float4* __restrict__ win) {
+                                                    float4* __restrict__ part, float4* __restrict__ win, DictGroupView gv) {
     __shared__ float s_best[4][32];
     __shared__ int s_idx[4][32];
     __shared__ float s_re[4][32];
@@ -69,14 +70,21 @@ __global__ __launch_bounds__(NT) void k_dict_match(const double2* __restrict__ X
     //  vector instruction of the loop is paid in full; 8 of its ~43 were tile-address arithmetic)
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int j = lane & 31, h = lane >> 5;
-    const int p = blockIdx.x * 32 + j;
+    const int slot = blockIdx.x * 32 + j;
+    int p = slot, grp = 0;
+    if constexpr (GRP) {
+        if ((int)blockIdx.x * 32 >= gv.slot_beg[gv.G]) return;          // (uniform: the grid covers the largest possible slot count)
+        p = gv.slot_pix[slot];
+        grp = gv.tile_grp[blockIdx.x];
+    }
+    const bool valid = GRP ? p >= 0 : p < Npix;
     // B fragments: B[k = 2q + h][j] = x(p, c = 2q + h)  (real chain) and -imag (conjugate) for the imaginary chain
     float bre[NPAIR], bim[NPAIR];
 #pragma unroll
     for (int q = 0; q < NPAIR; ++q) {
         const int c = 2 * q + h;
         double2 v = make_double2(0.0, 0.0);
-        if (p < Npix && c < s) v = X[(size_t)p + (size_t)Npix * c];
+        if (valid && c < s) v = X[(size_t)p + (size_t)Npix * c];
         bre[q] = (float)v.x;                   // single(x)  mrf_dtm_cpu.m:54
         bim[q] = -(float)v.y;                  // conj
     }
@@ -84,8 +92,14 @@ __global__ __launch_bounds__(NT) void k_dict_match(const double2* __restrict__ X
     float &best = I.best, &cre = I.cre, &cim = I.cim;
     int& bidx = I.bidx;
     // this workgroup's part of the atom tiles: [tbeg, ntiles)
-    const int tper = (ntiles_all + (int)gridDim.y - 1) / (int)gridDim.y;
-    const int tbeg = (int)blockIdx.y * tper, ntiles = min(ntiles_all, tbeg + tper);
+    // (GRP: of the group's tiles [t0, tall), in as many parts as keep >= 64 tiles per wave; a part beyond them is empty and leaves best = -1)
+    int t0 = 0, tall = ntiles_all, nparts = (int)gridDim.y;
+    if constexpr (GRP) {
+        t0 = gv.gtile[grp]; tall = gv.gtile[grp + 1];
+        nparts = max(1, min(nparts, (tall - t0) / (4 * 64)));
+    }
+    const int tper = (tall - t0 + nparts - 1) / nparts;
+    const int tbeg = t0 + (int)blockIdx.y * tper, ntiles = min(tall, tbeg + tper);
     // The atom fragments of tile t + 4 are requested before the products of tile t (register double buffer): the loop used to
     // request a tile's fragments and wait for them at once, one L2 latency per tile hidden only by occupancy.
     constexpr int NPL = (NPAIR <= 4) ? 4 : 8, NV = NPL / 4;
@@ -135,7 +149,7 @@ __global__ __launch_bounds__(NT) void k_dict_match(const double2* __restrict__ X
     }
     if (h == 0) { s_best[wave][j] = best; s_idx[wave][j] = bidx; s_re[wave][j] = cre; s_im[wave][j] = cim; }
     __syncthreads();
-    if (tid < 32 && p < Npix) {
+    if (tid < 32 && valid) {
         best = s_best[0][tid]; bidx = s_idx[0][tid]; cre = s_re[0][tid]; cim = s_im[0][tid];
 #pragma unroll
         for (int w = 1; w < 4; ++w) {
@@ -143,9 +157,10 @@ __global__ __launch_bounds__(NT) void k_dict_match(const double2* __restrict__ X
             const int oi = s_idx[w][tid];
             if (ob > best || (ob == best && oi < bidx)) { best = ob; bidx = oi; cre = s_re[w][tid]; cim = s_im[w][tid]; }
         }
+        if constexpr (GRP) bidx = dict_group_atom(gv, grp, bidx);
         if (bidx >= K) bidx = 0;       // cannot happen: padded atoms are all-zero and never beat a real one
         if (part) {                    // atoms split over workgroups: k_dict_merge finishes the pixel
-            part[(size_t)blockIdx.y * Npix + p] = make_float4(best, __int_as_float(bidx), cre, cim);
+            part[GRP ? (size_t)blockIdx.y * gv.slot_cap + slot : (size_t)blockIdx.y * Npix + p] = make_float4(best, __int_as_float(bidx), cre, cim);
             return;
         }
         finish_pixel(p, Npix, K, best, bidx, cre, cim, normD, lut, Q, qmap, pd, mt, dm, win);
@@ -170,18 +185,26 @@ __global__ __launch_bounds__(NT) void k_dict_match(const double2* __restrict__ X
 // bit-reversed order (see k_dict_match).
 constexpr int LCAP = 128;       // tiles a wave collects for the exact products before it works them off
 constexpr int FSTEP = 8;        // tiles per LDS step: 16 KB of f16 pieces, [tile][hi | lo][lane] of 16 bytes
-template <int NPAIR, bool SEED>
+// GRP: as in k_dict_match; gmax is indexed by slot, the seed samples the group's own tiles (skipped for a group of fewer than 48 steps)
+template <int NPAIR, bool SEED, bool GRP = false>
 __global__ __launch_bounds__(NT) void k_dict_match_f(const double2* __restrict__ X, int Npix, int s, const float* __restrict__ pack,
                                                       int ntiles_all, int tper, int K, const float* __restrict__ normD,
                                                       const float* __restrict__ lut, int Q, float* __restrict__ qmap,
                                                       float* __restrict__ pd, float* __restrict__ mt, int32_t* __restrict__ dm,
                                                       float4* __restrict__ part, const uint4* __restrict__ pack16, float marg_coef,
-                                                      int* __restrict__ gmax, int seed_stride, float4* __restrict__ win) {
+                                                      int* __restrict__ gmax, int seed_stride, float4* __restrict__ win, DictGroupView gv) {
     __shared__ uint4 s_a[2][FSTEP * 128];
     __shared__ int s_list[4][LCAP];
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int j = lane & 31, h = lane >> 5;
-    const int p = ((int)blockIdx.x * 4 + wave) * 32 + j;
+    const int slot = ((int)blockIdx.x * 4 + wave) * 32 + j;
+    int p = slot, grp = 0;
+    if constexpr (GRP) {
+        if ((int)blockIdx.x * 128 >= gv.slot_beg[gv.G]) return;         // (uniform: the grid covers the largest possible slot count)
+        p = gv.slot_pix[slot];
+        grp = gv.tile_grp[blockIdx.x];
+    }
+    const bool valid = GRP ? p >= 0 : p < Npix;
     constexpr int NPL = (NPAIR <= 4) ? 4 : 8, NV = NPL / 4;
     // exact products: B[k = 2q + h][j] = x(p, c = 2q + h) (real chain) and -imag (conjugate) for the imaginary chain
     float bre[NPAIR], bim[NPAIR];
@@ -189,7 +212,7 @@ __global__ __launch_bounds__(NT) void k_dict_match_f(const double2* __restrict__
     for (int q = 0; q < NPAIR; ++q) {
         const int c = 2 * q + h;
         double2 v = make_double2(0.0, 0.0);
-        if (p < Npix && c < s) v = X[(size_t)p + (size_t)Npix * c];
+        if (valid && c < s) v = X[(size_t)p + (size_t)Npix * c];
         bre[q] = (float)v.x;                   // single(x)  mrf_dtm_cpu.m:54
         bim[q] = -(float)v.y;                  // conj
     }
@@ -203,7 +226,7 @@ __global__ __launch_bounds__(NT) void k_dict_match_f(const double2* __restrict__
         for (int jj = 0; jj < 8; ++jj) {
             const int c = 8 * h + jj;
             double2 v = make_double2(0.0, 0.0);
-            if (p < Npix && c < s) v = X[(size_t)p + (size_t)Npix * c];
+            if (valid && c < s) v = X[(size_t)p + (size_t)Npix * c];
             xr[jj] = (float)v.x; xi[jj] = -(float)v.y;
             mx = fmaxf(mx, fmaxf(fabsf(xr[jj]), fabsf(xi[jj])));
             n2 = fmaf(xr[jj], xr[jj], fmaf(xi[jj], xi[jj], n2));
@@ -233,14 +256,27 @@ __global__ __launch_bounds__(NT) void k_dict_match_f(const double2* __restrict__
     // when the dictionary is small and that launch is skipped).  Any value found there belongs to an atom of the dictionary, so the
     // argument above holds with it.  What it buys: without it every wave climbs from -1 in each of the P atom parts and 7 % of the tiles
     // went to the exact products (21 parts of 152 tiles on the bench slice); within the margin of the final maximum are ~0.5 %.
-    const bool pub = (marg < __builtin_inff()) && p < Npix;
+    const bool pub = (marg < __builtin_inff()) && valid;
+    const int gi = GRP ? slot : p;                                      // this pixel's entry of gmax
     Inc I = {-1.0f, -1.0f, 0.f, 0.f, 0};
-    float runa = (!SEED && pub) ? __int_as_float(gmax[p]) : -1.f, cut = runa - marg;
+    float runa = (!SEED && pub) ? __int_as_float(gmax[gi]) : -1.f, cut = runa - marg;
     int cnt = 0;                                                        // listed tiles (scalar)
     // this workgroup's part of the atom tiles: [tbeg, tbeg + n), local index i
     // (SEED: the whole dictionary, steps (blockIdx.y + gridDim.y k) seed_stride)
-    const int tbeg = SEED ? 0 : (int)blockIdx.y * tper, n = SEED ? ntiles_all : min(ntiles_all - tbeg, tper);
+    // (GRP: the group's tiles [t0, tall) in place of the dictionary's, in as many parts as keep >= 64 tiles each, whole LDS steps per part; a part
+    //  beyond them is empty, n = 0, and leaves best = -1)
+    int t0 = 0, tall = ntiles_all;
+    if constexpr (GRP) {
+        t0 = gv.gtile[grp]; tall = gv.gtile[grp + 1];
+        const int nparts = max(1, min((int)gridDim.y, (tall - t0) / 64));
+        tper = ((tall - t0 + nparts - 1) / nparts + FSTEP - 1) / FSTEP * FSTEP;
+    }
+    const int tbeg = SEED ? t0 : t0 + (int)blockIdx.y * tper, n = SEED ? tall - t0 : GRP ? max(0, min(tall - tbeg, tper)) : min(tall - tbeg, tper);
     const int nsteps = (n + FSTEP - 1) / FSTEP;
+    if constexpr (SEED && GRP) {
+        if (nsteps < 48) return;
+        seed_stride = max(1, nsteps / 12);
+    }
     int nb = 0;
     while ((1 << nb) < nsteps) ++nb;
     const unsigned kend = 1u << nb;
@@ -258,11 +294,11 @@ __global__ __launch_bounds__(NT) void k_dict_match_f(const double2* __restrict__
         return nsteps;
     };
     auto stage_load = [&](int st, uint4 (&r)[4]) __attribute__((always_inline)) {
-        const int t0 = tbeg + st * FSTEP;
+        const int ts = tbeg + st * FSTEP;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int idx = tid + 256 * q;
-            r[q] = (t0 + idx / 128 < ntiles_all) ? pack16[(size_t)t0 * 128 + idx] : make_uint4(0, 0, 0, 0);
+            r[q] = (ts + idx / 128 < tall) ? pack16[(size_t)ts * 128 + idx] : make_uint4(0, 0, 0, 0);
         }
     };
     auto stage_store = [&](int b, const uint4 (&r)[4]) __attribute__((always_inline)) {
@@ -342,7 +378,7 @@ __global__ __launch_bounds__(NT) void k_dict_match_f(const double2* __restrict__
         }
     }
     if constexpr (SEED) {
-        if (pub && runa >= 0.f) (void)__hip_atomic_fetch_max(gmax + p, __float_as_int(runa), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (pub && runa >= 0.f) (void)__hip_atomic_fetch_max(gmax + gi, __float_as_int(runa), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         return;
     }
     // merge the two lane halves (same pixel, interleaved atom rows): larger value, then lower index
@@ -351,11 +387,12 @@ __global__ __launch_bounds__(NT) void k_dict_match_f(const double2* __restrict__
         const int oi = __shfl(I.bidx, lane ^ 32, 64);
         if (ob > I.best || (ob == I.best && oi < I.bidx)) { I.best = ob; I.bidx = oi; I.cre = ore; I.cim = oim; }
     }
-    if (h == 0 && p < Npix) {
+    if (h == 0 && valid) {
         int bidx = I.bidx;
+        if constexpr (GRP) bidx = dict_group_atom(gv, grp, bidx);
         if (bidx >= K) bidx = 0;       // cannot happen: padded atoms are all-zero and never beat a real one
         if (part) {                    // atoms split over workgroups: k_dict_merge finishes the pixel
-            part[(size_t)blockIdx.y * Npix + p] = make_float4(I.best, __int_as_float(bidx), I.cre, I.cim);
+            part[GRP ? (size_t)blockIdx.y * gv.slot_cap + slot : (size_t)blockIdx.y * Npix + p] = make_float4(I.best, __int_as_float(bidx), I.cre, I.cim);
             return;
         }
         finish_pixel(p, Npix, K, I.best, bidx, I.cre, I.cim, normD, lut, Q, qmap, pd, mt, dm, win);
@@ -363,14 +400,18 @@ __global__ __launch_bounds__(NT) void k_dict_match_f(const double2* __restrict__
 }
 
 // per pixel: the best candidate of the P atom parts (larger magnitude, then lower index), then the outputs as in k_dict_match
-__global__ __launch_bounds__(256) void k_dict_merge(const float4* __restrict__ part, int P, int Npix, int K, const float* __restrict__ normD,
+// (slot_pix, a grouped match: the candidates are n slots per part and slot_pix names a slot's pixel, -1 none; else n = Npix)
+__global__ __launch_bounds__(256) void k_dict_merge(const float4* __restrict__ part, int P, int n, int Npix, int K, const float* __restrict__ normD,
                                                      const float* __restrict__ lut, int Q, float* __restrict__ qmap, float* __restrict__ pd,
-                                                     float* __restrict__ mt, int32_t* __restrict__ dm, float4* __restrict__ win) {
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= Npix) return;
-    float4 b = part[p];
+                                                     float* __restrict__ mt, int32_t* __restrict__ dm, float4* __restrict__ win,
+                                                     const int* __restrict__ slot_pix) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int p = slot_pix ? slot_pix[i] : i;
+    if (p < 0) return;
+    float4 b = part[i];
     for (int k = 1; k < P; ++k) {
-        const float4 o = part[(size_t)k * Npix + p];
+        const float4 o = part[(size_t)k * n + i];
         if (cand_better(o.x, __float_as_int(o.y), b.x, __float_as_int(b.y))) b = o;
     }
     finish_pixel(p, Npix, K, b.x, __float_as_int(b.y), b.z, b.w, normD, lut, Q, qmap, pd, mt, dm, win);
@@ -384,6 +425,7 @@ __global__ __launch_bounds__(256) void k_dict_xfit(const float4* __restrict__ wi
     const float4 w = win[p];
     const int a = __float_as_int(w.z);
     for (int c = blockIdx.y; c < s; c += gridDim.y) {
+        if (a < 0) { xfit[(size_t)p + (size_t)Npix * c] = make_float2(0.f, 0.f); continue; }      // an unmatched pixel of a grouped match
         const float d = dict_atom(dv, a, c);
         xfit[(size_t)p + (size_t)Npix * c] = make_float2(w.x * d, w.y * d);
     }
@@ -402,7 +444,7 @@ int dict_scratch(qmri_ctx* ctx, void** buf, size_t* cap, size_t need_bytes) {
 
 int dict_launch_merge(qmri_ctx* ctx, const float4* part, int P, int Npix, float* d_qmap, float* d_pd, float* d_mt, int32_t* d_dm, float4* win) {
     const DictHost& D = ctx->dict;
-    k_dict_merge<<<dim3((Npix + 255) / 256), dim3(256), 0, ctx->stream>>>(part, P, Npix, D.K, D.d_normD, D.d_lut, D.Q, d_qmap, d_pd, d_mt, d_dm, win);
+    k_dict_merge<<<dim3((Npix + 255) / 256), dim3(256), 0, ctx->stream>>>(part, P, Npix, Npix, D.K, D.d_normD, D.d_lut, D.Q, d_qmap, d_pd, d_mt, d_dm, win, nullptr);
     QMRI_HIP(ctx, hipGetLastError());
     return QMRI_OK;
 }
@@ -420,10 +462,7 @@ int dict_launch(qmri_ctx* ctx, const double2* d_X, int Npix, float* d_qmap, floa
     if (D.wide) QMRI_TRY(dictw_launch(ctx, d_X, Npix, d_qmap, d_pd, d_mt, d_dm, win));
     else QMRI_TRY(dict_launch_narrow(ctx, d_X, Npix, d_qmap, d_pd, d_mt, d_dm, win));
     if (d_xfit) {
-        const int npair = (D.s + 1) / 2;
-        const DictView dv = {D.d_pack, D.wide, (npair <= 4) ? 4 : 8, D.G8};
-        k_dict_xfit<<<dim3((Npix + 255) / 256, std::min(D.s, 64)), dim3(256), 0, ctx->stream>>>(win, Npix, D.s, dv, d_xfit);
-        QMRI_HIP(ctx, hipGetLastError());
+        QMRI_TRY(dict_launch_xfit(ctx, win, Npix, d_xfit));
     }
     return QMRI_OK;
 }
@@ -477,11 +516,11 @@ static int dict_launch_narrow(qmri_ctx* ctx, const double2* d_X, int Npix, float
 #define LAUNCH(NP)                                                                                                              \
     do {                                                                                                                        \
         if (seed) k_dict_match_f<NP, true><<<dim3(ptiles, Ps), blk, 0, ctx->stream>>>(d_X, Npix, D.s, D.d_pack, D.ntiles, tper, D.K, D.d_normD, D.d_lut, \
-                                                                    D.Q, nullptr, nullptr, nullptr, nullptr, nullptr, D.d_pack16, mc, D.d_gmax, seed_stride, nullptr); \
+                                                                    D.Q, nullptr, nullptr, nullptr, nullptr, nullptr, D.d_pack16, mc, D.d_gmax, seed_stride, nullptr, DictGroupView{}); \
         if (filt) k_dict_match_f<NP, false><<<grid, blk, 0, ctx->stream>>>(d_X, Npix, D.s, D.d_pack, D.ntiles, tper, D.K, D.d_normD, D.d_lut, D.Q, \
-                                                                    d_qmap, d_pd, d_mt, d_dm, part, D.d_pack16, mc, D.d_gmax, 0, win); \
+                                                                    d_qmap, d_pd, d_mt, d_dm, part, D.d_pack16, mc, D.d_gmax, 0, win, DictGroupView{}); \
         else k_dict_match<NP><<<grid, blk, 0, ctx->stream>>>(d_X, Npix, D.s, D.d_pack, D.ntiles, D.K, D.d_normD, D.d_lut, D.Q,  \
-                                                             d_qmap, d_pd, d_mt, d_dm, part, win);                              \
+                                                             d_qmap, d_pd, d_mt, d_dm, part, win, DictGroupView{});             \
     } while (0)
     switch (npair) {
         case 1: LAUNCH(1); break;
@@ -496,5 +535,85 @@ static int dict_launch_narrow(qmri_ctx* ctx, const double2* d_X, int Npix, float
 #undef LAUNCH
     QMRI_HIP(ctx, hipGetLastError());
     if (P > 1) QMRI_TRY(dict_launch_merge(ctx, part, P, Npix, d_qmap, d_pd, d_mt, d_dm, win));
+    return QMRI_OK;
+}
+
+// The grouped match (qmri_dict_match_grouped): the same kernels on slot tiles of one group each.  gv comes from
+// the bucketing launches of dictg_launch() (dictg_kernels.hip) with the pixel width this function asks for; nslot_tiles is the largest number of slot tiles the call can
+// have (the kernels leave at once beyond the slots in use, which only the device knows).
+int dict_group_pixel_width(const qmri_ctx* ctx) { return (ctx->dict.d_gpack16 && ctx->dict.filter_on) ? 128 : 32; }
+
+int dict_launch_grouped(qmri_ctx* ctx, const double2* d_X, int Npix, const DictGroupView& gv, int nslot_tiles, float* d_qmap, float* d_pd, float* d_mt,
+                        int32_t* d_dm, float4* win) {
+    DictHost& D = ctx->dict;
+    const int npair = (D.s + 1) / 2;
+    const bool filt = D.d_gpack16 && D.filter_on;
+    if (!D.slots_g) {
+        int per_cu = 0, per_cu_f = 0;
+        hipDeviceProp_t prop;
+        QMRI_HIP(ctx, hipGetDeviceProperties(&prop, ctx->device));
+        QMRI_HIP(ctx, (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_dict_match<5, true>, NT, 0)));
+        QMRI_HIP(ctx, (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_f, k_dict_match_f<5, false, true>, NT, 0)));
+        D.slots_g = std::max(1, per_cu) * prop.multiProcessorCount;
+        D.slots_gf = std::max(1, per_cu_f) * prop.multiProcessorCount;
+    }
+    // atom parts as in dict_launch_narrow, from the largest group's tiles; a smaller group uses fewer of them (the kernels' own arithmetic)
+    const int ptiles = filt ? (Npix + 127) / 128 : (Npix + 31) / 32;
+    const int slots = filt ? D.slots_gf : D.slots_g;
+    int P = 1;
+    if (ptiles < 4 * slots) {
+        P = (8 * slots + ptiles - 1) / ptiles;
+        P = std::max(1, std::min(P, D.gtiles_max / (filt ? 64 : 4 * 64)));
+    }
+    float4* part = nullptr;
+    if (P > 1) {
+        QMRI_TRY(dict_scratch(ctx, (void**)&D.d_part, &D.part_cap, (size_t)P * gv.slot_cap * sizeof(float4)));
+        part = D.d_part;
+    }
+    dim3 grid(nslot_tiles, P), blk(NT);
+    const float mc = D.marg_coef * D.margin_scale;
+    if (filt) {
+        QMRI_TRY(dict_scratch(ctx, (void**)&D.d_gmax, &D.gmax_cap, (size_t)gv.slot_cap * sizeof(int)));
+        QMRI_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)D.d_gmax, (int)0xBF800000u /* -1.0f */, (size_t)gv.slot_cap, ctx->stream));
+    }
+    const int nsteps_max = (D.gtiles_max + FSTEP - 1) / FSTEP;
+    const bool seed = filt && P > 1 && nsteps_max >= 48;
+    const int Ps = seed ? std::max(1, std::min(12, (slots + ptiles - 1) / ptiles)) : 0;
+    const int tall = D.gtile_h.back();
+#define LAUNCH(NP)                                                                                                              \
+    do {                                                                                                                        \
+        if (seed) k_dict_match_f<NP, true, true><<<dim3(nslot_tiles, Ps), blk, 0, ctx->stream>>>(d_X, Npix, D.s, D.d_gpack, tall, 0, D.K, D.d_normD, D.d_lut, \
+                                                                    D.Q, nullptr, nullptr, nullptr, nullptr, nullptr, D.d_gpack16, mc, D.d_gmax, 0, nullptr, gv); \
+        if (filt) k_dict_match_f<NP, false, true><<<grid, blk, 0, ctx->stream>>>(d_X, Npix, D.s, D.d_gpack, tall, 0, D.K, D.d_normD, D.d_lut, D.Q, \
+                                                                    d_qmap, d_pd, d_mt, d_dm, part, D.d_gpack16, mc, D.d_gmax, 0, win, gv); \
+        else k_dict_match<NP, true><<<grid, blk, 0, ctx->stream>>>(d_X, Npix, D.s, D.d_gpack, tall, D.K, D.d_normD, D.d_lut, D.Q,  \
+                                                                   d_qmap, d_pd, d_mt, d_dm, part, win, gv);                    \
+    } while (0)
+    switch (npair) {
+        case 1: LAUNCH(1); break;
+        case 2: LAUNCH(2); break;
+        case 3: LAUNCH(3); break;
+        case 4: LAUNCH(4); break;
+        case 5: LAUNCH(5); break;
+        case 6: LAUNCH(6); break;
+        case 7: LAUNCH(7); break;
+        default: LAUNCH(8); break;
+    }
+#undef LAUNCH
+    QMRI_HIP(ctx, hipGetLastError());
+    if (P > 1) {
+        k_dict_merge<<<dim3((gv.slot_cap + 255) / 256), dim3(256), 0, ctx->stream>>>(part, P, gv.slot_cap, Npix, D.K, D.d_normD, D.d_lut, D.Q, d_qmap, d_pd,
+                                                                                      d_mt, d_dm, win, gv.slot_pix);
+        QMRI_HIP(ctx, hipGetLastError());
+    }
+    return QMRI_OK;
+}
+
+int dict_launch_xfit(qmri_ctx* ctx, const float4* win, int Npix, float2* d_xfit) {
+    const DictHost& D = ctx->dict;
+    const int npair = (D.s + 1) / 2;
+    const DictView dv = {D.d_pack, D.wide, (npair <= 4) ? 4 : 8, D.G8};
+    k_dict_xfit<<<dim3((Npix + 255) / 256, std::min(D.s, 64)), dim3(256), 0, ctx->stream>>>(win, Npix, D.s, dv, d_xfit);
+    QMRI_HIP(ctx, hipGetLastError());
     return QMRI_OK;
 }

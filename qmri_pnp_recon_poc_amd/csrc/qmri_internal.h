@@ -472,6 +472,15 @@ struct DictHost {
     int* d_gmax = nullptr; size_t gmax_cap = 0;           // per pixel: largest filtered |ip|^2 seen by any wave (float bits), -1 at launch (bytes)
     float marg_coef = 0.f;
     int filter_on = 1; float margin_scale = 1.f;          // qmri_debug_dict_filter
+    // groups of a narrow dictionary (qmri_set_dictionary_groups; dictg_kernels.hip): G = 0 none.  d_gpack / d_gpack16 are
+    // d_pack / d_pack16 again with every group starting on a 32-atom tile (gtile_h[g], gtile_h[G] tiles in all); d_gwork is the per-call scratch of
+    // the pixel bucketing (bytes)
+    int G = 0, gtiles_max = 0;
+    std::vector<int> gtile_h;
+    float* d_gpack = nullptr; uint4* d_gpack16 = nullptr;
+    int* d_gptr = nullptr; int* d_gtile = nullptr; double* d_gval = nullptr;
+    int* d_gwork = nullptr; size_t gwork_cap = 0;
+    int slots_g = 0, slots_gf = 0;                        // as slots / slots_f, for the grouped instantiations
 };
 
 struct qmri_ctx {
@@ -622,6 +631,16 @@ void conv_plan_layer(ConvLayer& L, ConvKind kind, int Cin, int Cout);
 // dictionary match (dict_kernels.hip)
 int dict_launch(qmri_ctx* ctx, const double2* d_X, int Npix, float* d_qmap, float* d_pd, float* d_mt, int32_t* d_dm, float2* d_xfit);
 int dict_scratch(qmri_ctx* ctx, void** buf, size_t* cap, size_t need_bytes);
+int dict_launch_xfit(qmri_ctx* ctx, const float4* win, int Npix, float2* d_xfit);
+// grouped match (dictg_kernels.hip: groups, pixel bucketing; dict_kernels.hip: the match on slot tiles)
+struct DictGroupView;
+int dict_group_pixel_width(const qmri_ctx* ctx);
+int dict_launch_grouped(qmri_ctx* ctx, const double2* d_X, int Npix, const DictGroupView& gv, int nslot_tiles, float* d_qmap, float* d_pd, float* d_mt,
+                        int32_t* d_dm, float4* win);
+int dictg_set_groups(qmri_ctx* ctx, int G, const int32_t* group_ptr, const double* group_val);
+void dictg_free(qmri_ctx* ctx);
+int dictg_launch(qmri_ctx* ctx, const double2* d_X, int Npix, const double* d_sel, float* d_qmap, float* d_pd, float* d_mt, int32_t* d_dm, int32_t* d_grp,
+                 float2* d_xfit);
 int dict_launch_merge(qmri_ctx* ctx, const float4* part, int P, int Npix, float* d_qmap, float* d_pd, float* d_mt, int32_t* d_dm, float4* win);
 // wide dictionaries (16 < s <= 1024; dictw_kernels.hip)
 int dictw_pack_dictionary(qmri_ctx* ctx, const float* D_host, int K, int s);    // fills ctx->dict.d_pack / G8 / ntiles

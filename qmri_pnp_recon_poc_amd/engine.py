@@ -101,6 +101,28 @@ def simulation_arguments(alpha, tr, te, t1, t2, b1, nstates, inversion, ti, inv_
     return a, sched[0], sched[1], atoms[0], atoms[1], atoms[2] if b1 is not None else None, p
 
 
+def group_arguments(group_ptr, group_val):
+    """(group_ptr [G + 1] int32, group_val [G] float64) as qmri_set_dictionary_groups takes them; the library checks their contents."""
+    gp, gv = np.asarray(group_ptr), np.asarray(group_val, dtype=np.float64)
+    if gp.ndim != 1 or gv.ndim != 1 or gp.size != gv.size + 1 or gv.size < 1 or not np.issubdtype(gp.dtype, np.integer):
+        raise ValueError("group_ptr must be G + 1 integers and group_val G values, G >= 1")
+    return np.ascontiguousarray(gp, dtype=np.int32), np.ascontiguousarray(gv)
+
+
+def dict_group_assign(group_val, sel):
+    """The group of each selector value as the grouped dictionary match assigns it (qmri_dict_group_assign, host only): the lowest g minimising
+    |sel - group_val[g]| in float64, 1-based; 0 for a non-finite value (unmatched).  Returns int32 in the shape of sel."""
+    from . import _lib
+    gv = np.ascontiguousarray(group_val, dtype=np.float64).ravel()
+    b = np.ascontiguousarray(sel, dtype=np.float64)
+    out = np.zeros(b.size, np.int32)
+    st = _lib.lib().qmri_dict_group_assign(gv.size, gv.ctypes.data_as(C.POINTER(C.c_double)), b.size, b.ravel().ctypes.data_as(C.POINTER(C.c_double)),
+                                           out.ctypes.data_as(C.POINTER(C.c_int32)))
+    if st != 0:
+        raise QmriError(st, _lib.lib().qmri_last_error(None).decode())
+    return out.reshape(b.shape)
+
+
 def _hip_runtime():
     """The HIP runtime through ctypes, for the few calls that keep an intermediate result on the device between two library calls."""
     import os
@@ -612,6 +634,17 @@ class Engine:
         self._check(self.L.qmri_set_dictionary(self.h, K, s, Q, Df.ctypes.data_as(f), nd.ctypes.data_as(f), lf.ctypes.data_as(f)))
         self.dict_shape = (K, s, Q)
 
+    def set_dictionary_groups(self, group_ptr, group_val):
+        """Groups of the set dictionary (extension, no reference counterpart; include/qmri.h qmri_set_dictionary_groups): group g holds atoms
+        group_ptr[g] .. group_ptr[g + 1] - 1 (0-based) and has the selector value group_val[g] (e.g. its b1), ascending.  dict_match(X, sel=...) then
+        matches every pixel against the atoms of its own group.  group_ptr = None clears.  set_dictionary drops the groups."""
+        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        if group_ptr is None:
+            self._check(self.L.qmri_set_dictionary_groups(self.h, 0, None, None))
+            return
+        gp, gv = group_arguments(group_ptr, group_val)
+        self._check(self.L.qmri_set_dictionary_groups(self.h, gv.size, gp.ctypes.data_as(ip), gv.ctypes.data_as(dp)))
+
     def compress_dictionary(self, F, s=None, energy=None, s_max=16, tol=0.0, maxit=0):
         """A simulated dictionary compressed to its SVD subspace on the device (extension, no reference counterpart; include/qmri.h
         qmri_dict_compress).  F [K, T]: K real fingerprints of T <= 1024 frames, float64 or float32 (float32 stays float32 on its way to the
@@ -763,9 +796,11 @@ class Engine:
         self._check(self.L.qmri_norm_tv(self.h, I.ctypes.data_as(C.POINTER(C.c_double)), I.shape[0], I.shape[1], C.byref(out)))
         return float(out.value)
 
-    def dict_match(self, X, want_mt=True, want_dm=True, want_xfit=False):
+    def dict_match(self, X, sel=None, want_mt=True, want_dm=True, want_xfit=False):
         """out = mrf_dtm_cpu(dict, data, par)  (mrf_dtm_cpu.m:1).  X [..., s] complex -> dict of arrays; want_xfit adds Xfit [..., s]
-        complex64 (par.f.Xout, :95,129-134)."""
+        complex64 (par.f.Xout, :95,129-134).  sel (the leading shape of X, e.g. a measured B1 map): the grouped match (extension;
+        set_dictionary_groups) -- every pixel against the atoms of the group nearest its value, "grp" (1-based, 0 = unmatched: a non-finite value,
+        all outputs zero) added to the result."""
         X = np.asarray(X, dtype=np.complex128)
         K, s, Q = self.dict_shape
         if X.shape[-1] != s:
@@ -778,12 +813,22 @@ class Engine:
         mt = np.empty(npix, np.float32) if want_mt else None
         dm = np.empty(npix, np.int32) if want_dm else None
         xfit = np.empty(2 * npix * s, np.float32) if want_xfit else None
-        f = C.POINTER(C.c_float)
-        self._check(self.L.qmri_dict_match_xfit(self.h, _vp(xb), npix, qmap.ctypes.data_as(f), pd.ctypes.data_as(f),
-                                                mt.ctypes.data_as(f) if mt is not None else None,
-                                                dm.ctypes.data_as(C.POINTER(C.c_int32)) if dm is not None else None,
-                                                xfit.ctypes.data_as(f) if xfit is not None else None))
+        f, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+        outs = (qmap.ctypes.data_as(f), pd.ctypes.data_as(f), mt.ctypes.data_as(f) if mt is not None else None, dm.ctypes.data_as(ip) if dm is not None else None)
+        xf = xfit.ctypes.data_as(f) if xfit is not None else None
+        grp = None
+        if sel is None:
+            self._check(self.L.qmri_dict_match_xfit(self.h, _vp(xb), npix, *outs, xf))
+        else:
+            sel = np.asarray(sel, dtype=np.float64)
+            if sel.shape != lead:
+                raise ValueError(f"sel must have the leading shape of X, {lead}, not {sel.shape}")
+            sb = np.ascontiguousarray(sel.ravel(order="F"))
+            grp = np.empty(npix, np.int32)
+            self._check(self.L.qmri_dict_match_grouped(self.h, _vp(xb), npix, sb.ctypes.data_as(C.POINTER(C.c_double)), *outs, grp.ctypes.data_as(ip), xf))
         out = {"qmap": qmap.reshape(lead + (Q,), order="F"), "pd": pd.view(np.complex64).reshape(lead, order="F")}
+        if grp is not None:
+            out["grp"] = grp.reshape(lead, order="F")
         if xfit is not None:
             out["Xfit"] = xfit.view(np.complex64).reshape(lead + (s,), order="F")
         if mt is not None:
@@ -792,9 +837,13 @@ class Engine:
             out["dm"] = dm.reshape(lead, order="F")
         return out
 
-    def dict_match_dev(self, d_X: int, npix: int, d_qmap: int = 0, d_pd: int = 0, d_mt: int = 0, d_dm: int = 0, d_xfit: int = 0):
+    def dict_match_dev(self, d_X: int, npix: int, d_qmap: int = 0, d_pd: int = 0, d_mt: int = 0, d_dm: int = 0, d_xfit: int = 0, d_sel: int = 0, d_grp: int = 0):
         """qmri_dict_match_xfit_dev: device pointers (X Npix x s complex double column-major; outputs as qmri.h lays them out), asynchronous on
-        the engine's stream."""
+        the engine's stream.  d_sel (Npix doubles): the grouped match, qmri_dict_match_grouped_dev, with d_grp (Npix int32) as a further output."""
+        if d_sel:
+            self._check(self.L.qmri_dict_match_grouped_dev(self.h, C.c_void_p(d_X), int(npix), C.c_void_p(d_sel), C.c_void_p(d_qmap or None), C.c_void_p(d_pd or None),
+                                                           C.c_void_p(d_mt or None), C.c_void_p(d_dm or None), C.c_void_p(d_grp or None), C.c_void_p(d_xfit or None)))
+            return
         self._check(self.L.qmri_dict_match_xfit_dev(self.h, C.c_void_p(d_X), int(npix), C.c_void_p(d_qmap or None), C.c_void_p(d_pd or None),
                                                     C.c_void_p(d_mt or None), C.c_void_p(d_dm or None), C.c_void_p(d_xfit or None)))
 

@@ -80,24 +80,38 @@ def compress_dictionary(dic, s=None, energy=None, s_max=16, device=0):
 
 
 def simulate_dictionary(alpha, tr, te, t1_grid, t2_grid, s=None, energy=None, nstates=32, inversion=True, ti=0.0, inv_eff=1.0, b1=None, s_max=16,
-                        device=0):
+                        device=0, b1_grid=None):
     """A FISP-MRF dictionary from a flip-angle train: the fingerprints of every (T1, T2) of the grid by extended phase graphs
     (Engine.simulate_dictionary), then their SVD compression (Engine.compress_dictionary) on the same device buffer -- the K x T fingerprints
     never cross to the host.  An extension; the reference only loads compressed files.  The atoms are the ij-meshgrid of t1_grid and t2_grid as
     synth.make_dictionary orders it (T2 fastest), lut = (T1, T2).  Atoms with T2 > T1 are kept: a caller who wants only the physical ones filters
     the grid (or the result) itself.  b1: one transmit scale for all atoms, or None.  Give the rank s or the energy to keep.  Returns the fields
-    of load_dictionary (V, D, normD, lut) plus eig and info; recon_tsmis runs on the result unchanged."""
+    of load_dictionary (V, D, normD, lut) plus eig and info; recon_tsmis runs on the result unchanged.
+    b1_grid (ascending transmit scales, instead of b1): a B1-resolved dictionary -- the (T1, T2) atoms of b1_grid[0], then
+    those of b1_grid[1], ... in one simulation with one joint SVD; lut = (T1, T2, b1) and the result carries group_ptr and group_val, which
+    recon_tsmis(..., b1_map=...) hands to the grouped match."""
     from .engine import Engine
     t1g, t2g = np.asarray(t1_grid, dtype=np.float64).ravel(), np.asarray(t2_grid, dtype=np.float64).ravel()
     T1, T2 = (a.ravel() for a in np.meshgrid(t1g, t2g, indexing="ij"))
+    groups = {}
+    if b1_grid is not None:
+        if b1 is not None:
+            raise ValueError("give b1 or b1_grid, not both")
+        bg = np.asarray(b1_grid, dtype=np.float64).ravel()
+        if bg.size < 1 or bg.size > 256 or not np.all(np.isfinite(bg)) or np.any(bg < 0) or np.any(np.diff(bg) <= 0):
+            raise ValueError("b1_grid must hold 1..256 finite, non-negative, strictly ascending values")
+        n = T1.size
+        T1, T2, b1 = np.tile(T1, bg.size), np.tile(T2, bg.size), np.repeat(bg, n)                # group-major
+        groups = {"group_ptr": (np.arange(bg.size + 1) * n).astype(np.int32), "group_val": bg.copy()}
     eng = Engine(device)
     try:
         out = eng.simulate_compress_dictionary(alpha, tr, te, T1, T2, b1=b1, s=s, energy=energy, s_max=s_max, nstates=nstates, inversion=inversion,
                                                ti=ti, inv_eff=inv_eff)
     finally:
         eng.close()
-    return {"V": out["V"], "D": out["D"], "normD": out["normD"], "lut": np.ascontiguousarray(np.stack([T1, T2], axis=1).astype(np.float32)),
-            "eig": out["eig"], "info": out["info"]}
+    cols = [T1, T2] + ([b1] if groups else [])
+    return {"V": out["V"], "D": out["D"], "normD": out["normD"], "lut": np.ascontiguousarray(np.stack(cols, axis=1).astype(np.float32)),
+            "eig": out["eig"], "info": out["info"], **groups}
 
 
 def crop_tsmi(X):
@@ -264,7 +278,7 @@ def save_training_pickle(path, X_slices, channels_to_save=None):
 def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", subsampling_pattern="Spiral",
                 spiral_sampling_curve=771, epi_sampling_rate=1 / 65, measurements_type="noisy", measurements_noise=30,
                 denoiser_type="single_level", noise_map_std=0.01, residual_noise=False, iters=100, seed=0, Y=None, device=0,
-                net_arch=None, lrtv_iters=None, tsmi_domain="real", solver="lsqr"):
+                net_arch=None, lrtv_iters=None, tsmi_domain="real", solver="lsqr", b1_map=None):
     """main_recon_tsmis_FFT.m:216-374 on already loaded (and cropped) arrays.
 
     dictionary  dict(V, D, normD, lut) (load_dictionary);  X0  N x M x s ground-truth TSMI;  qmap0  N x M x 3
@@ -274,7 +288,9 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
     tsmi_domain "complex": X0 may be complex (tsmi_from_stack turns the stored 2s-channel layout into one) and the denoiser takes 2s (+1) ->
                 2s channels, cat(3, real, imag); "real" is the reference's loop
     solver      x-update of PnP_ADMM: "lsqr" (the reference's), "direct", or with SpiralExact "toeplitz" 
-    Returns dict(X, qmap (N x M x 3: T1, T2, PD), Y, metrics, foreground_mask).
+    b1_map      N x M measured transmit field for a dictionary that carries group_ptr / group_val (simulate_dictionary(..., b1_grid=...)): every
+                pixel is matched against the atoms of the b1 nearest its value, NaN = background, all outputs zero
+    Returns dict(X, qmap (N x M x 3: T1, T2, PD), Y, metrics, foreground_mask); with b1_map also grp (N x M, the 1-based b1 group, 0 = unmatched).
     """
     from . import reference_api as R
     net_arch = dict(net_arch or {})
@@ -282,6 +298,12 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
     _dtype(denoiser_type == "multi_level", tsmi_domain)            # (checks tsmi_domain)
     X0 = np.asarray(X0)
     N, M, s = X0.shape
+    if b1_map is not None:                                                           # (refused before anything is reconstructed)
+        if dictionary.get("group_ptr") is None or dictionary.get("group_val") is None:
+            raise ValueError("b1_map needs a dictionary with group_ptr and group_val (simulate_dictionary(..., b1_grid=...))")
+        b1_map = np.asarray(b1_map, dtype=np.float64)
+        if b1_map.shape != (N, M):
+            raise ValueError(f"b1_map must be {N} x {M}")
     V = np.asarray(dictionary["V"], dtype=np.float64)
     if subsampling_pattern == "Spiral":
         P = R.setup_subsampling_spiralgrided(N, M, spiral_sampling_curve, V)
@@ -328,7 +350,16 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
     else:
         raise ValueError(f"unknown reconstruction method {recon_method}")
     par = {"f": {"qout": 1, "pdout": 1, "mtout": 0, "Xout": 0, "dmout": 0, "Yout": 0, "verbose": 0}, "fp": {"blockSize": 1e9}}   # :302-309
-    out = R.mrf_dtm_cpu(dictionary, {"X": X}, par, device=device)
+    extra = {}
+    if b1_map is not None:
+        eng = R._engine(device)
+        eng.set_dictionary(dictionary["D"], dictionary["normD"], dictionary["lut"])
+        eng.set_dictionary_groups(dictionary["group_ptr"], dictionary["group_val"])
+        out = eng.dict_match(X, sel=b1_map)
+        out["qmap"] = out["qmap"][:, :, :2]                                          # (T1, T2); column 3 of the lut is the group's b1
+        extra["grp"] = out["grp"]
+    else:
+        out = R.mrf_dtm_cpu(dictionary, {"X": X}, par, device=device)
     qmap = np.concatenate([np.asarray(out["qmap"], dtype=np.complex128), np.asarray(out["pd"]).reshape(N, M, 1)], axis=2)       # :316
     mask = getmask_fromPD(np.asarray(qmap0)[:, :, 2], 0.15)                          # :192
-    return {"X": X, "qmap": qmap, "Y": Y, "foreground_mask": mask, "metrics": metrics(qmap, qmap0, mask, X, X0)}
+    return {"X": X, "qmap": qmap, "Y": Y, "foreground_mask": mask, "metrics": metrics(qmap, qmap0, mask, X, X0), **extra}

@@ -694,6 +694,47 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         if (nlhs > 2) plhs[2] = mt; else mxDestroyArray(mt);
         if (nlhs > 3) plhs[3] = dm; else mxDestroyArray(dm);
         if (nlhs > 4) plhs[4] = xfit;
+    } else if (c == "set_dictionary_groups") {       // qmri_mex('set_dictionary_groups', group_ptr(G+1 doubles, 0-based), group_val(G doubles)); ([], []) clears
+        // groups of the set dictionary for 'dict_match_grouped' (extension; qmri.h qmri_set_dictionary_groups).  'set_dictionary' drops them.
+        need(nrhs, 3, "qmri_mex('set_dictionary_groups', group_ptr, group_val)");
+        for (int a = 1; a <= 2; ++a)
+            want(mxIsDouble(prhs[a]) && !mxIsComplex(prhs[a]), "qmri:set_dictionary_groups:type", "group_ptr and group_val must be real double arrays");
+        const size_t G = mxGetNumberOfElements(prhs[2]);
+        const bool clear = G == 0 && mxGetNumberOfElements(prhs[1]) == 0;
+        want(clear || (G >= 1 && G <= 256 && mxGetNumberOfElements(prhs[1]) == G + 1), "qmri:set_dictionary_groups:size",
+             "group_val must have 1 <= G <= 256 elements and group_ptr G + 1");
+        want(g_dict.D != nullptr, "qmri:state", "no dictionary: call qmri_mex('set_dictionary', ...) first");
+        if (clear) { check(qmri_set_dictionary_groups(ctx(), 0, nullptr, nullptr)); return; }
+        std::vector<int32_t> gp(G + 1);
+        const double* v = mxGetDoubles(prhs[1]);
+        for (size_t g = 0; g <= G; ++g) {
+            want(std::isfinite(v[g]) && v[g] == std::floor(v[g]) && v[g] >= 0 && v[g] <= 2147483647.0, "qmri:set_dictionary_groups:size", "group_ptr must hold 0-based atom offsets");
+            gp[g] = (int32_t)v[g];
+        }
+        check(qmri_set_dictionary_groups(ctx(), (int)G, gp.data(), mxGetDoubles(prhs[2])));
+    } else if (c == "dict_match_grouped") {          // [qmap, pd, mt, dm, grp, xfit] = qmri_mex('dict_match_grouped', X(Npix x s complex double), Q, sel(Npix double))
+        need(nrhs, 4, "[qmap, pd, mt, dm, grp, xfit] = qmri_mex('dict_match_grouped', X, Q, sel)");
+        want(is_cdouble(prhs[1]) && mxGetM(prhs[1]) >= 1 && mxGetM(prhs[1]) <= 2147483647u, "qmri:dict_match_grouped:type", "X must be complex double, Npix x s");
+        want(mxIsDouble(prhs[2]) && !mxIsComplex(prhs[2]) && mxGetNumberOfElements(prhs[2]) == 1, "qmri:dict_match_grouped:type", "Q must be a real double scalar");
+        want(mxIsDouble(prhs[3]) && !mxIsComplex(prhs[3]), "qmri:dict_match_grouped:type", "sel must be a real double array");
+        want(mxGetNumberOfElements(prhs[3]) == mxGetM(prhs[1]), "qmri:dict_match_grouped:size", "sel must have one value per row of X");
+        want(g_dict.D != nullptr, "qmri:state", "no dictionary: call qmri_mex('set_dictionary', ...) (mrf_dtm_b1_hip) first");
+        want(mxGetN(prhs[1]) == mxGetN(g_dict.D), "qmri:dict_match_grouped:size", "X must have s columns (s = columns of dict.D)");
+        want(mxGetScalar(prhs[2]) == (double)mxGetN(g_dict.lut), "qmri:dict_match_grouped:size", "Q must be the number of columns of dict.lut");
+        const int npix = (int)mxGetM(prhs[1]), Q = (int)mxGetScalar(prhs[2]);
+        mxArray* xfit = (nlhs > 5) ? mxCreateNumericMatrix(npix, mxGetN(prhs[1]), mxSINGLE_CLASS, mxCOMPLEX) : nullptr;
+        plhs[0] = mxCreateNumericMatrix(npix, Q, mxSINGLE_CLASS, mxREAL);
+        mxArray* pd = mxCreateNumericMatrix(npix, 1, mxSINGLE_CLASS, mxCOMPLEX);
+        mxArray* mt = mxCreateNumericMatrix(npix, 1, mxSINGLE_CLASS, mxREAL);
+        mxArray* dm = mxCreateNumericMatrix(npix, 1, mxINT32_CLASS, mxREAL);
+        mxArray* grp = mxCreateNumericMatrix(npix, 1, mxINT32_CLASS, mxREAL);
+        check(qmri_dict_match_grouped(ctx(), mxGetComplexDoubles(prhs[1]), npix, mxGetDoubles(prhs[3]), (float*)mxGetData(plhs[0]), (float*)mxGetData(pd),
+                                      (float*)mxGetData(mt), (int32_t*)mxGetData(dm), (int32_t*)mxGetData(grp), xfit ? (float*)mxGetData(xfit) : nullptr));
+        if (nlhs > 1) plhs[1] = pd; else mxDestroyArray(pd);
+        if (nlhs > 2) plhs[2] = mt; else mxDestroyArray(mt);
+        if (nlhs > 3) plhs[3] = dm; else mxDestroyArray(dm);
+        if (nlhs > 4) plhs[4] = grp; else mxDestroyArray(grp);
+        if (nlhs > 5) plhs[5] = xfit;
     } else if (c == "health") {                      // h = qmri_mex('health'): qmri_get_health of the gateway's context as a struct
         qmri_health h;
         check(qmri_get_health(ctx(), &h));
