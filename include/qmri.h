@@ -134,6 +134,31 @@ int qmri_set_operator_nufft(qmri_ctx* ctx, int N, int M, int s, int T, const dou
 int qmri_nufft_prepare_normal(qmri_ctx* ctx);
 int qmri_normal(qmri_ctx* ctx, const void* x, int x_is_complex, void* out);
 int qmri_normal_dev(qmri_ctx* ctx, const void* d_x, void* d_out, int batch);
+/* Density compensation for a trajectory operator (an EXTENSION, no reference counterpart, parity unpinned).  The bare adjoint
+ * of a trajectory that oversamples the centre of k-space (every spiral) is a blurred, mis-scaled image; x = A^H (w .* y) with density weights w is the
+ * gridding reconstruction.  qmri_nufft_dcf computes w by the iteration of Pipe & Menon (MRM 1999) on the operator's own interpolation kernel psi
+ * (width and shape of qmri_nufft_params) and oversampled coordinates u_i, all m samples of all frames as one set on the periodic 2N x 2M grid:
+ *   w_i = 1;  repeat:  g[k] = sum_j w_j psi(u_j1 - k1) psi(u_j2 - k2);  d_i = sum_k g[k] psi(u_i1 - k1) psi(u_i2 - k2);  w_i <- w_i / d_i
+ * for p->niter iterations (1..200; 0 = 20), stopped after the first iteration whose dev = max_i |d_i - 1| is <= p->tol (tol = 0: never), and then
+ * scaled once, w <- kappa w, kappa = (T / 4) I_1^2 I_2^2, I_a = sum_k psi(k) over the window of a sample at zero offset: with orthonormal V and equal
+ * weight per frame A^H W A then has unit transfer where the trajectory has support.  All sums run in a fixed order without floating-point atomics:
+ * the weights are the same bits on every call.  A sample with d_i <= 0 or non-finite (impossible for finite input) gets w_i = 0 and is counted in
+ * info->clamped.  The weights are ATTACHED to the operator and, when w_out != NULL, copied out (m doubles, ABI order).  p == NULL: the defaults;
+ * info nullable (iters: iterations run, dev: that of the last one, split_tiles: tiles of the plan whose samples went through partial tiles and
+ * the reduction).  qmri_set_sample_weights attaches the caller's own weights (m finite doubles
+ * >= 0; NULL clears).  Replacing the operator drops the weights.
+ * Only the three qmri_adjoint_w* calls read the weights -- x = A^H (w .* y), the product formed where the spreading kernel stages y, no pass over y;
+ * the same bits as qmri_adjoint* of the caller's own w .* y.  qmri_adjoint*, every solver and every other _mc call ignore them, bit for bit.
+ * Refusals, all decided on the host before the device is selected: ctx == NULL, a NULL array, niter outside 0..200, tol negative or non-finite,
+ * reserved != 0, batch outside 1..max_batch, a weight that is negative or non-finite: QMRI_ERR_INVALID_ARG; no operator, a qmri_adjoint_w* call
+ * without attached weights, qmri_adjoint_w_mc without coil maps: QMRI_ERR_STATE; a gridded operator: QMRI_ERR_UNSUPPORTED. */
+typedef struct { int32_t niter; double tol; int32_t reserved[6]; } qmri_dcf_params;      /* zeros = defaults */
+typedef struct { int32_t iters; double dev; int32_t clamped; int32_t split_tiles; int32_t reserved[4]; } qmri_dcf_info;
+int qmri_nufft_dcf(qmri_ctx* ctx, const qmri_dcf_params* p, double* w_out, qmri_dcf_info* info);
+int qmri_set_sample_weights(qmri_ctx* ctx, const double* w);
+int qmri_adjoint_w(qmri_ctx* ctx, const void* y, void* x);                 /* x = A^H (w .* y) */
+int qmri_adjoint_w_dev(qmri_ctx* ctx, const void* d_y, void* d_x, int batch);
+int qmri_adjoint_w_mc(qmri_ctx* ctx, const void* y_mc, void* x);           /* sum_j conj(C_j) A^H (w .* y_j) */
 /* On a trajectory operator these work unchanged: qmri_forward / _adjoint (and _f32, _dev), qmri_operator_m, qmri_set_coils, qmri_forward_mc /
  * _adjoint_mc, qmri_xupdate_mc(_batch), qmri_pnp_admm_mc(_batch, _dev), qmri_coil_compress*, and qmri_xupdate / qmri_pnp_admm (one slice, LSQR,
  * no diagnostics) as the image-domain LSQR with one unit coil -- bit for bit the qmri_*_mc call with that coil.  Everything else that needs the

@@ -16,17 +16,12 @@
 // Forward and adjoint evaluate the kernel with the same device function on the same inputs (nu_phi(u - k) with k from nu_k0), so adjointness
 // holds to rounding.  Interpolation and spreading are gathers with w^2 reuse per sample: vector fp64 FMA, no MFMA.
 #include "dc_device.h"
+#include "nufft_device.h"
 
 using namespace dcdev;
+using namespace nudev;
 
 namespace {
-
-__device__ __forceinline__ double nu_phi(double d, double inv_hw, double beta) {
-    const double z = d * inv_hw, t = 1.0 - z * z;
-    return t >= 0.0 ? exp(beta * (sqrt(t) - 1.0)) : 0.0;
-}
-__device__ __forceinline__ int nu_k0(double u, double hw) { return (int)ceil(u - hw); }    // first grid point of the window [k0, k0 + w)
-__device__ __forceinline__ int nu_wrap(int k, int G) { k %= G; return k < 0 ? k + G : k; }
 
 // x [B][c][n2][n1] -> g [B][a][c][q2][q1], a = a1 + 2 a2, q = (n + N/2) mod N
 // DEAPOD = false: the ramps alone, without 1 / Phi -- the zero-padded 2N x 2M DFT of the Toeplitz normal operator (toep_kernels.hip, "k_toep_pre")
@@ -103,6 +98,8 @@ __global__ __launch_bounds__(NT) void k_nu_interp(NufftDev nu, const double2* __
 
 // adjoint spreading: one workgroup per (segment, slice); thread (r1, r2) owns grid point (16 t1 + r1, 16 t2 + r2) of the 2N x 2M grid
 constexpr int NU_CH = 64;        // samples staged in LDS at a time
+// WEIGHTED: y times the attached sample weight (nu.wgt, ABI order) as it is staged -- the weighted adjoint of DESIGN.md section 21, no pass over y
+template <bool WEIGHTED>
 __global__ __launch_bounds__(NT) void k_nu_spread(NufftDev nu, const double2* __restrict__ y, double2* __restrict__ grid, double2* __restrict__ part) {
     __shared__ double2 vy[NU_CH * DC_MAXS];           // V(t, c) * conj(ph) * y of the staged samples
     __shared__ double wl[NU_CH][2 * NU_TB];           // their weights along both axes at the tile's 16 + 16 grid lines (0 outside the window)
@@ -120,7 +117,9 @@ __global__ __launch_bounds__(NT) void k_nu_spread(NufftDev nu, const double2* __
         for (int it = tid; it < cnt * s; it += NT) {
             const int j = it / s, c = it - j * s;
             const int e = nu.list[i0 + j];
-            const double2 yv = y[(size_t)b * nu.m + nu.perm[e]], ph = nu.ph[e];
+            double2 yv = y[(size_t)b * nu.m + nu.perm[e]];
+            const double2 ph = nu.ph[e];
+            if (WEIGHTED) { const double wq = nu.wgt[nu.perm[e]]; yv.x *= wq; yv.y *= wq; }
             const double yr = yv.x * ph.x + yv.y * ph.y, yi = yv.y * ph.x - yv.x * ph.y;      // y * conj(ph)
             const double v = nu.Vt[(size_t)nu.t[e] * s + c];
             vy[j * DC_MAXS + c] = make_double2(v * yr, v * yi);
@@ -239,6 +238,7 @@ NufftDev nufft_dev(const qmri_ctx* ctx) {
     d.ntile2 = 2 * o.M / NU_TB; d.nseg = h.nseg; d.nred = h.nred; d.nslot = h.nslot;
     d.Vt = o.d_Vt; d.u = (const double2*)h.d_u; d.ph = (const double2*)h.d_ph; d.t = h.d_t; d.perm = h.d_perm; d.list = h.d_list;
     d.seg = h.d_seg; d.red = h.d_red; d.dp1 = h.d_dp; d.dp2 = h.d_dp + o.N; d.r1 = h.d_r; d.r2 = h.d_r + o.N;
+    d.wgt = h.w_set ? h.d_w : nullptr;
     return d;
 }
 
@@ -295,13 +295,15 @@ int nufft_launch_fwd(qmri_ctx* ctx, int B, const double2* x, double2* y) {
     return launch_interp(ctx, nu, B, o.nu.d_grid, y);
 }
 
-int nufft_launch_adj(qmri_ctx* ctx, int B, const double2* y, double2* x) {
+static int launch_adj(qmri_ctx* ctx, int B, const double2* y, double2* x, bool weighted) {
     OpHost& o = ctx->op;
     if (o.kind != OP_NUFFT || B < 1 || B > o.maxB) { qmri_set_error(ctx, "nufft_launch_adj: no trajectory operator / batch out of range (internal)"); return QMRI_ERR_STATE; }
     const NufftDev nu = nufft_dev(ctx);
+    if (weighted && !nu.wgt) { qmri_set_error(ctx, "nufft_launch_adj_w: no sample weights attached (internal)"); return QMRI_ERR_STATE; }
     const OpDev op = qmri_opdev(ctx);
     const size_t n = (size_t)o.N * o.M * o.s;
-    k_nu_spread<<<dim3(nu.nseg, B), dim3(NT), 0, ctx->stream>>>(nu, y, o.nu.d_grid, o.nu.d_part);
+    if (weighted) k_nu_spread<true><<<dim3(nu.nseg, B), dim3(NT), 0, ctx->stream>>>(nu, y, o.nu.d_grid, o.nu.d_part);
+    else k_nu_spread<false><<<dim3(nu.nseg, B), dim3(NT), 0, ctx->stream>>>(nu, y, o.nu.d_grid, o.nu.d_part);
     QMRI_HIP(ctx, hipGetLastError());
     if (nu.nred > 0) {
         k_nu_reduce<<<dim3(nu.nred, B, nu.s), dim3(NT), 0, ctx->stream>>>(nu, o.nu.d_part, o.nu.d_grid);
@@ -313,3 +315,6 @@ int nufft_launch_adj(qmri_ctx* ctx, int B, const double2* y, double2* x) {
     QMRI_HIP(ctx, hipGetLastError());
     return QMRI_OK;
 }
+
+int nufft_launch_adj(qmri_ctx* ctx, int B, const double2* y, double2* x) { return launch_adj(ctx, B, y, x, false); }
+int nufft_launch_adj_w(qmri_ctx* ctx, int B, const double2* y, double2* x) { return launch_adj(ctx, B, y, x, true); }

@@ -381,6 +381,7 @@ struct NufftDev {
     const NuRed* red;                            // [nred]
     const double* dp1; const double* dp2;        // [N], [M] deapodisation 1 / Phi at n - N/2
     const double2* r1; const double2* r2;        // [N], [M] exp(-i pi (n - N/2) / N): the half-bin ramps
+    const double* wgt;                           // [m] ABI order: the attached sample weights or null; read by k_nu_spread<true> only
 };
 struct NufftHost {
     double* d_u = nullptr; double* d_ph = nullptr; int32_t* d_t = nullptr; int32_t* d_perm = nullptr; int32_t* d_list = nullptr;
@@ -393,6 +394,10 @@ struct NufftHost {
     // Hermitian-packed: [pair (c <= c') = c' (c' + 1) / 2 + c][a][j1][j2], bin (2 j1 + a1, 2 j2 + a2).  Built by toep_prepare, freed by nufft_free.
     double2* d_khat = nullptr;
     bool khat_ready = false;
+    // sample weights of the weighted adjoint (density compensation): [m] in ABI order, attached by qmri_nufft_dcf or
+    // qmri_set_sample_weights, read by the qmri_adjoint_w* calls alone, freed by nufft_free (replacing the operator drops them)
+    double* d_w = nullptr;
+    bool w_set = false;
 };
 // the exponential spiral of setup_subsampling_spiralgrided.m:7-27 before rounding (shared by qmri_build_spiral and qmri_build_spiral_traj): S angles
 // theta_j and radii r_j normalised to [0, 1]; frame f is rotated by f * SPIRAL_DELTA
@@ -400,6 +405,11 @@ void spiral_points(int S, std::vector<double>& theta, std::vector<double>& rad);
 constexpr double SPIRAL_DELTA = 3.14159265358979323846 / 180.0 * 7.5;
 int nufft_launch_fwd(qmri_ctx* ctx, int B, const double2* x, double2* y);    // x [B][n] -> y [B][m] (ABI order)
 int nufft_launch_adj(qmri_ctx* ctx, int B, const double2* y, double2* x);    // y [B][m] -> x [B][n]
+int nufft_launch_adj_w(qmri_ctx* ctx, int B, const double2* y, double2* x);  // ... of w .* y, w the attached sample weights (multiplied where k_nu_spread stages y)
+// Pipe-Menon density compensation on the plan's own kernel and spreading lists (dcf_kernels.hip, api_dcf.cpp): niter
+// iterations (1..200) from w = 1, stopped early once max |d - 1| <= tol (tol <= 0: never), then d_w_out [m] (ABI order) = kappa * w.  Uses the plan's
+// d_grid / d_part as scratch; waits for its kernels.
+int dcf_weights_dev(qmri_ctx* ctx, int niter, double tol, double kappa, double* d_w_out, qmri_dcf_info* info);
 int nufft_check_gridded(qmri_ctx* ctx, const char* what, const char* instead);   // QMRI_ERR_UNSUPPORTED on a trajectory operator, else QMRI_OK
 void nufft_free(NufftHost& h);
 bool nufft_kernel_ok(int w);

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import AdmmParams, CcParams, CsmInfo, CsmParams, DsvdInfo, DsvdParams, EpgParams, LrtvInfo, LrtvParams, NetDesc, NufftParams, Profile
+from ._lib import AdmmParams, CcParams, CsmInfo, CsmParams, DcfInfo, DcfParams, DsvdInfo, DsvdParams, EpgParams, LrtvInfo, LrtvParams, NetDesc, NufftParams, Profile
 
 ARCH_UNETRES, ARCH_SEQ_CONV = 0, 1
 SOLVER_LSQR, SOLVER_DIRECT = 0, 1
@@ -301,8 +301,45 @@ class Engine:
             self._check(self.L.qmri_normal(self.h, _vp(xb), 0, _vp(out)))
         return out.reshape((self.N, self.M, self.s), order="F")
 
-    def adjoint(self, y):
-        """x = F.adjoint(y)  (main_recon_tsmis_FFT.m:229); complex64 in -> complex64 out (the _f32 entry point)."""
+    # -- density compensation of a trajectory operator (extension, no reference counterpart) ------------------
+    def density_weights(self, niter=0, tol=0.0):
+        """Pipe-Menon density weights of the trajectory on the operator's own kernel (qmri_nufft_dcf): niter iterations (1..200, 0: the default
+        20), stopped after the first one whose max |d - 1| is <= tol (0: never), scaled so that A^H W A has unit transfer for orthonormal V.
+        The weights are attached to the operator (adjoint(y, weighted=True) uses them).  Returns (w [m] float64, dict(iters, dev, clamped, split_tiles:
+        the tiles of the plan that were spread in segments and reduced))."""
+        if int(niter) != niter or not (0 <= int(niter) <= 200):
+            raise ValueError("niter must be an integer in 1..200 (0: the default 20)")
+        if not (np.isfinite(tol) and tol >= 0):
+            raise ValueError("tol must be finite and >= 0")
+        p, info = DcfParams(int(niter), float(tol)), DcfInfo()
+        w = np.empty(max(self.m, 1), np.float64)
+        self._check(self.L.qmri_nufft_dcf(self.h, C.byref(p), w.ctypes.data_as(C.POINTER(C.c_double)), C.byref(info)))
+        return w[: self.m], {"iters": int(info.iters), "dev": float(info.dev), "clamped": int(info.clamped),
+                              "split_tiles": int(info.split_tiles)}
+
+    def set_sample_weights(self, w):
+        """Attach the caller's own sample weights (qmri_set_sample_weights): m finite values >= 0, the order of y; None clears them."""
+        if w is None:
+            self._check(self.L.qmri_set_sample_weights(self.h, None))
+            return
+        w = np.asarray(w)
+        if np.iscomplexobj(w):
+            raise ValueError("the sample weights must be real")
+        wb = np.ascontiguousarray(w, dtype=np.float64).ravel()
+        if wb.size != self.m:
+            raise ValueError(f"w must have {self.m} elements")
+        self._check(self.L.qmri_set_sample_weights(self.h, wb.ctypes.data_as(C.POINTER(C.c_double))))
+
+    def adjoint(self, y, weighted=False):
+        """x = F.adjoint(y)  (main_recon_tsmis_FFT.m:229); complex64 in -> complex64 out (the _f32 entry point).
+        weighted=True: x = A^H (w .* y) with the attached sample weights of a trajectory operator (qmri_adjoint_w; complex128)."""
+        if weighted:
+            yb = _cbuf(y)
+            if yb.size != self.m:
+                raise ValueError(f"y must have {self.m} elements")
+            x = np.empty(self.N * self.M * self.s, np.complex128)
+            self._check(self.L.qmri_adjoint_w(self.h, _vp(yb), _vp(x)))
+            return x.reshape((self.N, self.M, self.s), order="F")
         if np.asarray(y).dtype == np.complex64:
             y32 = np.ascontiguousarray(np.asarray(y).ravel(order="F"))
             if y32.size != self.m:
@@ -342,14 +379,14 @@ class Engine:
         self._check(self.L.qmri_forward_mc(self.h, _vp(xb), 1, _vp(y)))
         return y.reshape((self.m, -1), order="F")
 
-    def adjoint_mc(self, y):
-        """x = sum_j conj(maps[..., j]) * F.adjoint(y[:, j])."""
+    def adjoint_mc(self, y, weighted=False):
+        """x = sum_j conj(maps[..., j]) * F.adjoint(y[:, j]); weighted=True: of w .* y[:, j] with the attached sample weights (qmri_adjoint_w_mc)."""
         yb = _cbuf(y)
         nc = getattr(self, "ncoil", 0)
         if nc and yb.size != self.m * nc:                        # (no maps set: the library says so, QMRI_ERR_STATE)
             raise ValueError(f"y must be {self.m} x {nc}")
         x = np.empty(self.N * self.M * self.s, np.complex128)
-        self._check(self.L.qmri_adjoint_mc(self.h, _vp(yb), _vp(x)))
+        self._check((self.L.qmri_adjoint_w_mc if weighted else self.L.qmri_adjoint_mc)(self.h, _vp(yb), _vp(x)))
         return x.reshape((self.N, self.M, self.s), order="F")
 
     def xupdate_mc(self, y_mc, z, r, tol=1e-4, maxit=100, x0=None):
@@ -367,17 +404,28 @@ class Engine:
     def pnp_admm_mc(self, y_mc, gamma=0.05, iters=100, cg_tol=1e-4, cg_maxit=100, multi_level=False, noise_std=0.01, x0=None, tsmi_domain="real",
                     solver="lsqr"):
         """Multi-coil extension: PnP_ADMM(y, param) with F replaced by the SENSE operator of set_coils.  Returns (x, lsqr_iters).
+        x0 = "dcf": the start image is adjoint_mc(y_mc, weighted=True) (a trajectory operator with attached sample weights).
         solver: "lsqr", or "toeplitz" on a trajectory operator."""
         p = AdmmParams(float(gamma), int(iters), float(cg_tol), int(cg_maxit), _mc_solver(solver), denoiser_type(multi_level, tsmi_domain), float(noise_std), 0)
         yb = _cbuf(y_mc)
         nc = getattr(self, "ncoil", 0)
         if nc and yb.size != self.m * nc:
             raise ValueError(f"y_mc must be {self.m} x {nc}")
+        if isinstance(x0, str):
+            x0 = self._dcf_start(x0, lambda: self.adjoint_mc(y_mc, weighted=True))
         x0b = _cbuf(x0) if x0 is not None else None
         x = np.empty(self.N * self.M * self.s, np.complex128)
         li = np.zeros(max(iters, 1), np.int32)
         self._check(self.L.qmri_pnp_admm_mc(self.h, _vp(yb), C.byref(p), _vp(x0b), _vp(x), li.ctypes.data_as(C.POINTER(C.c_int32))))
         return x.reshape((self.N, self.M, self.s), order="F"), li[:iters]
+
+    @staticmethod
+    def _dcf_start(x0, weighted_adjoint):
+        """x0 = "dcf" of pnp_admm / pnp_admm_mc: the density-compensated adjoint of y as the start image (the attached weights of
+        density_weights / set_sample_weights).  Nothing else is a valid string."""
+        if x0 != "dcf":
+            raise ValueError(f'x0 must be an array, None (the adjoint of y) or "dcf" (the density-compensated adjoint), not {x0!r}')
+        return weighted_adjoint()
 
     def _mc_stack(self, maps, y_mc):
         """maps [S, N, M, ncoil], y_mc [S, m, ncoil] -> slice-major column-major buffers (S, ncoil, maps, y)."""
@@ -588,12 +636,15 @@ class Engine:
     def pnp_admm(self, y, gamma=0.05, iters=100, cg_tol=1e-4, cg_maxit=100, solver="lsqr", multi_level=False,
                  noise_std=0.01, x0=None, gt=None, want_diag=False, tsmi_domain="real"):
         """x = PnP_ADMM(y, param)  (PnP_ADMM.m:1).  Returns (x [N,M,s] complex, diag [iters,2] or None, lsqr_iters).
+        x0: an array, None (F.adjoint(y)) or, on a trajectory operator with attached sample weights, "dcf": adjoint(y, weighted=True).
         tsmi_domain="complex": the denoiser step on cat(3, real, imag) of x + uold (a 2s (+1) -> 2s network; see denoiser_type)."""
         p = AdmmParams(float(gamma), int(iters), float(cg_tol), int(cg_maxit), solver_code(solver),
                        denoiser_type(multi_level, tsmi_domain), float(noise_std), int(bool(want_diag)))
         yb = _cbuf(y)
         if yb.size != self.m:
             raise ValueError(f"y must have {self.m} elements")
+        if isinstance(x0, str):
+            x0 = self._dcf_start(x0, lambda: self.adjoint(y, weighted=True))
         x0b = _cbuf(x0) if x0 is not None else None
         gtb = _cbuf(gt) if gt is not None else None
         x = np.empty(self.N * self.M * self.s, np.complex128)

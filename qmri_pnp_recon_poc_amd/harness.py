@@ -278,7 +278,7 @@ def save_training_pickle(path, X_slices, channels_to_save=None):
 def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", subsampling_pattern="Spiral",
                 spiral_sampling_curve=771, epi_sampling_rate=1 / 65, measurements_type="noisy", measurements_noise=30,
                 denoiser_type="single_level", noise_map_std=0.01, residual_noise=False, iters=100, seed=0, Y=None, device=0,
-                net_arch=None, lrtv_iters=None, tsmi_domain="real", solver="lsqr", b1_map=None):
+                net_arch=None, lrtv_iters=None, tsmi_domain="real", solver="lsqr", b1_map=None, density_compensation=False):
     """main_recon_tsmis_FFT.m:216-374 on already loaded (and cropped) arrays.
 
     dictionary  dict(V, D, normD, lut) (load_dictionary);  X0  N x M x s ground-truth TSMI;  qmap0  N x M x 3
@@ -290,6 +290,8 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
     solver      x-update of PnP_ADMM: "lsqr" (the reference's), "direct", or with SpiralExact "toeplitz" 
     b1_map      N x M measured transmit field for a dictionary that carries group_ptr / group_val (simulate_dictionary(..., b1_grid=...)): every
                 pixel is matched against the atoms of the b1 nearest its value, NaN = background, all outputs zero
+    density_compensation  with SpiralExact: SVD_MRF is the density-compensated adjoint A^H (w .* y) and PnP_ADMM starts from it (Pipe-Menon
+                weights); False (default) is the bare adjoint
     Returns dict(X, qmap (N x M x 3: T1, T2, PD), Y, metrics, foreground_mask); with b1_map also grp (N x M, the 1-based b1 group, 0 = unmatched).
     """
     from . import reference_api as R
@@ -315,7 +317,11 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
         P = R.setup_subsampling_spiral_exact(N, M, spiral_sampling_curve, V)
     else:
         raise ValueError(f"unknown subsampling pattern {subsampling_pattern}")
+    if density_compensation and subsampling_pattern != "SpiralExact":
+        raise ValueError("density_compensation needs the subsampling pattern SpiralExact (a gridded mask has nothing to compensate)")
     F = R.make_F(P, device=device)
+    if density_compensation:
+        F._engine.density_weights()                                                  # (make_F planned the operator afresh: nothing was attached)
     if Y is None:
         Y = F.forward(X0.astype(np.complex128))                                      # :237
         if measurements_type == "noisy":
@@ -323,7 +329,8 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
         elif measurements_type != "clean":
             raise ValueError(f"unknown measurements type {measurements_type}")
     if recon_method == "SVD_MRF":                                                    # :270-271
-        X = F.adjoint(np.asarray(Y, dtype=np.complex128))
+        Yc = np.asarray(Y, dtype=np.complex128)
+        X = F._engine.adjoint(Yc, weighted=True) if density_compensation else F.adjoint(Yc)
     elif recon_method == "PnP_ADMM":                                                 # :284-293
         if weights is None:
             raise ValueError("PnP_ADMM needs the denoiser weights")
@@ -339,8 +346,10 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
         net = R.make_net(weights, denoiser_type, residual_noise, H=N, W=M, out_nc=out_nc, device=device, tsmi_domain=tsmi_domain,
                          **{**net_arch, **({"nc": arch["nc"], "nb": arch["nb"]} if arch else {})})
         param = {"eta": 20, "sigma_squared": 1, "gamma": 1 / 20, "iter": iters, "cg_tol": 1e-4, "F": F, "gt_tsmi": X0,
-                 "X0": F.adjoint(Y), "net": net, "denoiser_type": denoiser_type, "tsmi_domain": tsmi_domain,
+                 "X0": None if density_compensation else F.adjoint(Y), "net": net, "denoiser_type": denoiser_type, "tsmi_domain": tsmi_domain,
                  "noise_map": R.build_noise_map(noise_map_std, N, M), "solver": solver}   # :166-171
+        if density_compensation:
+            param["x0"] = "dcf"
         X = R.PnP_ADMM(np.asarray(Y, dtype=np.complex128), param)
     elif recon_method == "LRTV":                                                     # :273-282
         param = {"K": 4e-5, "iter": 200 if lrtv_iters is None else int(lrtv_iters), "step": X0.size / np.asarray(Y).size, "tol": 1e-4,

@@ -18,6 +18,9 @@
 //   * 'set_trajectory' plans a non-Cartesian operator (qmri_set_operator_nufft; 'build_spiral_traj' gives the reference's spiral before rounding):
 //     'forward', 'adjoint' and 'pnp_admm' then run on it (a measurement matrix slice by slice; no diagnostics), 'recon_batch*' refuse it.
 //     'normal' applies A^H A as a Toeplitz convolution (qmri_normal) and param.solver = 2 ('toeplitz' in PnP_ADMM_hip.m) solves the x-update with it.
+//     'dcf' computes and attaches density weights (qmri_nufft_dcf; extension), 'set_sample_weights' attaches the caller's,
+//     'adjoint_w' is the weighted adjoint A^H (w .* y).  Re-planning the operator drops the weights: 'set_trajectory', 'device', and any
+//     call that brings more slices than the plan's max_batch (it re-plans the operator for them); call 'dcf' / 'set_sample_weights' again after it.
 //   * 'recon_batch_mc' is the same for multi-coil stacks, every slice with its own coil maps (qmri_recon_batch_mc; an extension, no reference
 //     counterpart); with a coil-compression argument every launch compresses its slices on the device first (qmri_recon_batch_mc_cc).
 //   * 'coil_compress' compresses a multi-coil stack to virtual coils (qmri_coil_compress; extension).
@@ -310,6 +313,44 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         const bool cx = mxIsComplex(prhs[1]);
         check(qmri_normal(ctx(), cx ? (const void*)mxGetComplexDoubles(prhs[1]) : (const void*)mxGetDoubles(prhs[1]), cx,
                           mxGetComplexDoubles(plhs[0])));
+    } else if (c == "dcf") {                         // [w, info] = qmri_mex('dcf' [, niter [, tol]]): density weights of the trajectory, attached (qmri_nufft_dcf)
+        qmri_dcf_params dp{};                                       // (the argument checks come first: they need no operator)
+        if (nrhs > 1) dp.niter = int_arg(prhs[1], 0, 200, "qmri:dcf:niter", "niter must be an integer in 1..200 (0: the default 20)");
+        if (nrhs > 2) {
+            want(mxIsDouble(prhs[2]) && !mxIsComplex(prhs[2]) && mxGetNumberOfElements(prhs[2]) == 1, "qmri:dcf:tol", "tol must be a real double scalar");
+            dp.tol = mxGetScalar(prhs[2]);
+            want(std::isfinite(dp.tol) && dp.tol >= 0.0, "qmri:dcf:tol", "tol must be finite and >= 0 (0: never stop early)");
+        }
+        want(g_op.V != nullptr, "qmri:state", "no operator: call qmri_mex('set_trajectory', ...) (qmri_make_F_traj) first");
+        want(g_op.omega != nullptr, "qmri:dcf:trajectory", "density compensation needs a trajectory operator ('set_trajectory'); a gridded mask has nothing to compensate");
+        plhs[0] = mxCreateDoubleMatrix(operator_m(), 1, mxREAL);
+        qmri_dcf_info di{};
+        check(qmri_nufft_dcf(ctx(), &dp, mxGetDoubles(plhs[0]), &di));
+        if (nlhs > 1) {
+            const char* names[] = {"iters", "dev", "clamped", "split_tiles"};
+            plhs[1] = mxCreateStructMatrix(1, 1, 4, names);
+            mxSetFieldByNumber(plhs[1], 0, 0, mxCreateDoubleScalar((double)di.iters));
+            mxSetFieldByNumber(plhs[1], 0, 1, mxCreateDoubleScalar(di.dev));
+            mxSetFieldByNumber(plhs[1], 0, 2, mxCreateDoubleScalar((double)di.clamped));
+            mxSetFieldByNumber(plhs[1], 0, 3, mxCreateDoubleScalar((double)di.split_tiles));
+        }
+    } else if (c == "set_sample_weights") {          // qmri_mex('set_sample_weights', w): the caller's own weights, m x 1 real double, finite and >= 0; [] clears
+        need(nrhs, 2, "qmri_mex('set_sample_weights', w)");
+        want(mxIsDouble(prhs[1]) && !mxIsComplex(prhs[1]), "qmri:set_sample_weights:type", "w must be a real double vector (or [])");
+        want(g_op.V != nullptr, "qmri:state", "no operator: call qmri_mex('set_trajectory', ...) (qmri_make_F_traj) first");
+        want(g_op.omega != nullptr, "qmri:set_sample_weights:trajectory", "sample weights need a trajectory operator ('set_trajectory')");
+        if (mxIsEmpty(prhs[1])) { check(qmri_set_sample_weights(ctx(), nullptr)); return; }
+        want(mxGetNumberOfElements(prhs[1]) == operator_m(), "qmri:set_sample_weights:size", "w must have one entry per sample");
+        check(qmri_set_sample_weights(ctx(), mxGetDoubles(prhs[1])));
+    } else if (c == "adjoint_w") {                   // x = qmri_mex('adjoint_w', y): A^H (w .* y) with the attached weights, N x M x s (qmri_adjoint_w)
+        need(nrhs, 2, "x = qmri_mex('adjoint_w', y)");
+        want(is_cdouble(prhs[1]), "qmri:adjoint_w:type", "y must be a complex double vector");
+        (void)image_numel();
+        want(g_op.omega != nullptr, "qmri:adjoint_w:trajectory", "the weighted adjoint needs a trajectory operator ('set_trajectory')");
+        want(mxGetNumberOfElements(prhs[1]) == operator_m(), "qmri:adjoint_w:size", "y must have one entry per sample");
+        const mwSize dims[3] = {(mwSize)g_op.N, (mwSize)g_op.M, (mwSize)mxGetN(g_op.V)};
+        plhs[0] = mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxCOMPLEX);
+        check(qmri_adjoint_w(ctx(), mxGetComplexDoubles(prhs[1]), mxGetComplexDoubles(plhs[0])));
     } else if (c == "set_denoiser") {                // qmri_mex('set_denoiser', weights(single), in_nc, out_nc, nc(1x4), nb, residual_noise, H, W [, max_batch])
         need(nrhs, 9, "qmri_mex('set_denoiser', weights, in_nc, out_nc, nc, nb, residual_noise, H, W [, max_batch])");
         qmri_net_desc d;

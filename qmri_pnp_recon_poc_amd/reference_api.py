@@ -119,7 +119,9 @@ def PnP_ADMM(y, param):
     """x = PnP_ADMM(y, param)  (PnP_ADMM.m:1).  param: dict with iter, gamma, F, cg_tol, gt_tsmi, net, denoiser_type,
     noise_map (multi_level), X0 (PnP_ADMM.m:62-76).  F and net must be the handles made by make_F / make_net on the same
     device: the whole loop then runs on the GPU with one boundary crossing.  param["tsmi_domain"] (default: the net's, "real"):
-    "complex" runs the denoiser step on cat(3, real, imag) of x + uold."""
+    "complex" runs the denoiser step on cat(3, real, imag) of x + uold.  param["x0"] = "dcf" (an extension for a
+    trajectory F): the start image is the density-compensated adjoint of y instead of param["X0"]; the weights are
+    computed here if none are attached yet."""
     F, net = param["F"], param["net"]
     if not hasattr(F, "_engine") or not hasattr(net, "_engine") or F._engine is not net._engine:
         raise TypeError("param.F and param.net must come from make_F / make_net of this package (same device)")
@@ -129,10 +131,30 @@ def PnP_ADMM(y, param):
     x, diag, li = F._engine.pnp_admm(y, gamma=param["gamma"], iters=int(param["iter"]), cg_tol=param["cg_tol"], cg_maxit=100,
                                      solver=param.get("solver", "lsqr"), multi_level=multi, noise_std=noise_std,
                                      tsmi_domain=param.get("tsmi_domain", getattr(net, "_tsmi_domain", "real")),
-                                     x0=param.get("X0"), gt=None if traj else param.get("gt_tsmi"),
+                                     x0=_dcf_x0(F, param, y), gt=None if traj else param.get("gt_tsmi"),
                                      want_diag=param.get("gt_tsmi") is not None and not traj)
     PnP_ADMM.last_diagnostics, PnP_ADMM.last_lsqr_iters = diag, li
     return x
+
+
+def _dcf_x0(F, param, y):
+    """The start image of PnP_ADMM: param["X0"], or with param["x0"] == "dcf" the engine's density-compensated adjoint of y.  Whether weights
+    are attached is the engine's to say (QMRI_ERR_STATE): weights the caller attached are used as they are, and only an operator without any
+    gets the Pipe-Menon weights of density_weights()."""
+    x0 = param.get("x0")
+    if x0 is None:
+        return param.get("X0")
+    if x0 != "dcf":
+        raise ValueError(f'param["x0"] must be "dcf" or absent, not {x0!r}')
+    if getattr(F._P, "omega", None) is None:
+        raise ValueError('param["x0"] = "dcf" needs a trajectory operator (setup_subsampling_spiral_exact)')
+    try:
+        return F._engine.adjoint(y, weighted=True)
+    except E.QmriError as err:
+        if err.code != -2:                                          # (QMRI_ERR_STATE: no sample weights attached)
+            raise
+    F._engine.density_weights()
+    return F._engine.adjoint(y, weighted=True)
 
 
 def FISTA_deep(data, param):
