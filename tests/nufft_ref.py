@@ -3,9 +3,12 @@
     y_i = (1/sqrt(NM)) sum_c V(t_i, c) a_i^T X_c b_i,   a_i[n1] = exp(-i omega1_i n1),  b_i[n2] = exp(-i omega2_i n2)
 
 computed exactly (a non-uniform DFT, in chunks of samples), its adjoint, and a duck-typed operator whose multi-coil methods, LSQR and the
-PnP-ADMM loop are the oracle's own (oracle.Operator.forward_mc / adjoint_mc / lsqr_mc, oracle.pnp_admm_mc) running on it unchanged."""
+PnP-ADMM loop are the oracle's own (oracle.Operator.forward_mc / adjoint_mc / lsqr_mc, oracle.pnp_admm_mc) running on it unchanged.
+gridded_forward / gridded_adjoint restate the approximation the library computes instead of the exact sum: the 2x oversampled gridding NUFFT at a
+given kernel width, on one 2N x 2M FFT."""
 import numpy as np
 
+import dcf_ref as D
 from oracle import oracle as O
 
 CHUNK = 2048
@@ -49,6 +52,74 @@ def nudft_adjoint(y, omega, V, frame_ptr, N, M):
         A = np.exp(1j * np.outer(om[sl, 0], n1))
         B = np.exp(1j * np.outer(om[sl, 1], n2))
         x += np.einsum("in,ic,im->nmc", A, Vt[sl] * y[sl, None], B)
+    return x / np.sqrt(N * M)
+
+
+def deapodisation(L, width, beta):
+    """1 / Phi(p) at the centred index p = n - L/2, n < L:  Phi(p) = int_{-w/2}^{w/2} phi(u) cos(2 pi u p / (2L)) du by the 200-point
+    Gauss-Legendre quadrature of the host plan (deapodisation() of csrc/api_nufft.cpp)."""
+    gx, gw = np.polynomial.legendre.leggauss(200)
+    hw = 0.5 * width
+    p = np.arange(L) - L // 2
+    Phi = np.sum(gw[None, :] * hw * D.phi(gx * hw, hw, beta)[None, :] * np.cos(2 * np.pi * np.outer(p, gx * hw) / (2 * L)), axis=1)
+    return 1.0 / Phi
+
+
+def _gridding_plan(omega, N, M, width):
+    """-> (w, k1 [m, w] and k2 [m, w] wrapped into the 2N x 2M grid, p1 [m, w] and p2 [m, w] = phi(u - k), the samples' phases [m])."""
+    w = D.plan_width(width)
+    beta, hw = D.plan_beta(w), 0.5 * w
+    om = np.asarray(omega, np.float64)
+    u1, u2 = om[:, 0] * N / np.pi, om[:, 1] * M / np.pi
+    k1 = np.ceil(u1 - hw).astype(np.int64)[:, None] + np.arange(w)[None, :]
+    k2 = np.ceil(u2 - hw).astype(np.int64)[:, None] + np.arange(w)[None, :]
+    p1, p2 = D.phi(u1[:, None] - k1, hw, beta), D.phi(u2[:, None] - k2, hw, beta)
+    ph = np.exp(-1j * (om[:, 0] * (N // 2) + om[:, 1] * (M // 2)))     # the image index is centred: n = p + (N/2, M/2)
+    return w, k1 % (2 * N), k2 % (2 * M), p1, p2, ph
+
+
+def gridded_forward(x, omega, V, frame_ptr, width=0):
+    """The library's gridding NUFFT restated plainly, without the sub-grid trick: x / Phi(p) on the centred index p,
+    zero-padded to 2N x 2M (at p mod 2N, 2M), np.fft.fft2, then y_i = ph_i sum_k phi(u_i1 - k1) phi(u_i2 - k2) sum_c V(t_i, c) G_c[k] / sqrt(NM) over
+    the window k = ceil(u - w/2) ... + w - 1 wrapped into the grid.  x: N x M x s, width 0: the plan's default -> y: m complex."""
+    x = np.asarray(x, np.complex128)
+    if x.ndim == 2:
+        x = x[..., None]
+    N, M, s = x.shape
+    w, k1, k2, p1, p2, ph = _gridding_plan(omega, N, M, width)
+    beta = D.plan_beta(w)
+    pad = np.zeros((2 * N, 2 * M, s), np.complex128)
+    i1, i2 = (np.arange(N) - N // 2) % (2 * N), (np.arange(M) - M // 2) % (2 * M)
+    pad[np.ix_(i1, i2)] = x * (deapodisation(N, w, beta)[:, None] * deapodisation(M, w, beta)[None, :])[:, :, None]
+    G = np.fft.fft2(pad, axes=(0, 1))
+    Vt = np.asarray(V, np.float64)[frames_of(frame_ptr)]               # m x s
+    y = np.empty(k1.shape[0], np.complex128)
+    for i0 in range(0, y.size, CHUNK):
+        sl = slice(i0, min(i0 + CHUNK, y.size))
+        g = G[k1[sl][:, :, None], k2[sl][:, None, :], :]               # chunk x w x w x s
+        y[sl] = np.einsum("ia,ib,iabc,ic->i", p1[sl], p2[sl], g, Vt[sl])
+    return ph * y / np.sqrt(N * M)
+
+
+def gridded_adjoint(y, omega, V, frame_ptr, N, M, width=0):
+    """the exact transpose of gridded_forward, step by step in reverse: spread conj(ph) V y with the same window and kernel values, the conjugate
+    2N x 2M DFT, crop to the centred image, 1 / Phi -> N x M x s complex."""
+    y = np.asarray(y, np.complex128)
+    w, k1, k2, p1, p2, ph = _gridding_plan(omega, N, M, width)
+    beta = D.plan_beta(w)
+    Vt = np.asarray(V, np.float64)[frames_of(frame_ptr)]
+    s = Vt.shape[1]
+    val = (p1[:, :, None] * p2[:, None, :]).reshape(y.size, w * w)
+    idx = (k1[:, :, None] * (2 * M) + k2[:, None, :]).reshape(y.size, w * w)
+    yc = np.conj(ph) * y
+    G = np.empty((2 * N, 2 * M, s), np.complex128)
+    for c in range(s):
+        v = Vt[:, c] * yc
+        G[:, :, c] = (np.bincount(idx.ravel(), weights=(v.real[:, None] * val).ravel(), minlength=4 * N * M)
+                      + 1j * np.bincount(idx.ravel(), weights=(v.imag[:, None] * val).ravel(), minlength=4 * N * M)).reshape(2 * N, 2 * M)
+    pad = np.fft.ifft2(G, axes=(0, 1)) * (4 * N * M)                   # sum_k G[k] exp(+2 pi i k p / (2N, 2M))
+    i1, i2 = (np.arange(N) - N // 2) % (2 * N), (np.arange(M) - M // 2) % (2 * M)
+    x = pad[np.ix_(i1, i2)] * (deapodisation(N, w, beta)[:, None] * deapodisation(M, w, beta)[None, :])[:, :, None]
     return x / np.sqrt(N * M)
 
 

@@ -1,5 +1,7 @@
 """GPU: density compensation of a trajectory operator (qmri_nufft_dcf and the weighted adjoints) against the numpy
-restatement of tests/dcf_ref.py and the exact non-uniform DFT of tests/nufft_ref.py.  32 x 32 and 64 x 96 only."""
+restatement of tests/dcf_ref.py and the exact non-uniform DFT of tests/nufft_ref.py.  This file runs 32 x 32 and 64 x 96 at widths 6 and 12 with
+s = 1 and 3; every width 2 ... 16, the grids 160 x 192, 256 x 112 and 112 x 128 (split tiles) and the weighted adjoint at every s = 1 ... 10 are in
+tests/test_gpu_traj_grids.py, held to this file's WEIGHTS_RTOL."""
 import ctypes as C
 
 import numpy as np

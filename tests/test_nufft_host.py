@@ -166,3 +166,71 @@ def test_restatement_is_adjoint_and_pins_the_grid():
     t = R.frames_of(fp)
     ref = np.array([np.sum(V[t[i]] * X[k[i] % N, k[i] // N, :]) for i in range(14)])
     assert np.allclose(yg, ref, rtol=0, atol=1e-12)
+
+
+# -- the numpy restatement of the library's gridding NUFFT (nufft_ref.gridded_forward / gridded_adjoint), the yardstick of tests/test_gpu_traj_grids.py
+
+WIDTHS = list(range(2, 17))
+
+
+@pytest.fixture(scope="module")
+def gridding_case():
+    """16 x 24, s = 2, 3 frames, 64 random samples with the corners and edges of [-pi, pi]^2; the exact NUDFT of them: computed once, read-only."""
+    rng = np.random.default_rng(14)
+    N, M, T, s = 16, 24, 3, 2
+    V = rng.standard_normal((T, s))
+    fp = np.array([0, 20, 45, 64], np.int32)
+    om = rng.uniform(-np.pi, np.pi, (64, 2))
+    om[:8] = [[np.pi, np.pi], [-np.pi, -np.pi], [np.pi, -np.pi], [-np.pi, np.pi], [0.0, 0.0], [-np.pi, 1e-9], [1e-12, np.pi], [np.pi, 0.3]]
+    x = rng.standard_normal((N, M, s)) + 1j * rng.standard_normal((N, M, s))
+    y = rng.standard_normal(64) + 1j * rng.standard_normal(64)
+    case = dict(N=N, M=M, V=V, fp=fp, om=om, x=x, y=y, ye=R.nudft_forward(x, om, V, fp), xe=R.nudft_adjoint(y, om, V, fp, N, M))
+    for v in case.values():
+        if isinstance(v, np.ndarray):
+            v.setflags(write=False)
+    return case
+
+
+def _rel(a, b):
+    return float(np.linalg.norm(a - b) / np.linalg.norm(b))
+
+
+@pytest.mark.parametrize("width", WIDTHS)
+def test_gridding_restatement_is_adjoint_at_every_width(gridding_case, width):
+    c = gridding_case
+    Ax = R.gridded_forward(c["x"], c["om"], c["V"], c["fp"], width)
+    Ahy = R.gridded_adjoint(c["y"], c["om"], c["V"], c["fp"], c["N"], c["M"], width)
+    assert Ax.shape == c["y"].shape and Ahy.shape == c["x"].shape
+    gap = abs(np.vdot(c["y"], Ax) - np.vdot(Ahy, c["x"])) / (np.linalg.norm(Ax) * np.linalg.norm(c["y"]))
+    assert gap <= 1e-12, (width, gap)
+
+
+def test_gridding_restatement_stays_inside_the_stated_bound(gridding_case):
+    """Against the exact NUDFT: forward and adjoint err at most 10^(2-w) for w = 2 ... 12 (the bound DESIGN.md section 14 states and the GPU tests
+    use) and no more at a width than at the one below it.  Above 12 the error keeps falling until fp64 rounding of the deapodised sum stops it;
+    there it is only asked to stay below the error at 12."""
+    c = gridding_case
+    errs = {}
+    for w in WIDTHS:
+        errs[w] = max(_rel(R.gridded_forward(c["x"], c["om"], c["V"], c["fp"], w), c["ye"]),
+                      _rel(R.gridded_adjoint(c["y"], c["om"], c["V"], c["fp"], c["N"], c["M"], w), c["xe"]))
+    print("restatement against the exact NUDFT by width:", {w: f"{e:.2e}" for w, e in errs.items()})
+    for w in range(2, 13):
+        assert errs[w] <= 10.0 ** (2 - w), (w, errs[w])
+        if w > 2:
+            assert errs[w] <= errs[w - 1], (w, errs[w], errs[w - 1])
+    for w in range(13, 17):
+        assert errs[w] <= errs[12], (w, errs[w])
+
+
+def test_gridding_restatement_default_width_and_on_grid_points(gridding_case):
+    """width 0 is the plan's default (NU_WDEF of api_nufft.cpp); on-grid points reproduce the unitary DFT to that width's error."""
+    import dcf_ref as D
+    c = gridding_case
+    assert np.array_equal(R.gridded_forward(c["x"], c["om"], c["V"], c["fp"], 0), R.gridded_forward(c["x"], c["om"], c["V"], c["fp"], D.plan_width(0)))
+    k = np.random.default_rng(1).integers(0, c["N"] * c["M"], 64)
+    yg = R.gridded_forward(c["x"], R.traj_from_kidx(c["N"], c["M"], k), c["V"], c["fp"], 0)
+    X = np.fft.fft2(c["x"], axes=(0, 1)) / np.sqrt(c["N"] * c["M"])
+    t = R.frames_of(c["fp"])
+    ref = np.array([np.sum(c["V"][t[i]] * X[k[i] % c["N"], k[i] // c["N"], :]) for i in range(64)])
+    assert _rel(yg, ref) <= 1e-9
