@@ -159,6 +159,38 @@ int qmri_set_sample_weights(qmri_ctx* ctx, const double* w);
 int qmri_adjoint_w(qmri_ctx* ctx, const void* y, void* x);                 /* x = A^H (w .* y) */
 int qmri_adjoint_w_dev(qmri_ctx* ctx, const void* d_y, void* d_x, int batch);
 int qmri_adjoint_w_mc(qmri_ctx* ctx, const void* y_mc, void* x);           /* sum_j conj(C_j) A^H (w .* y_j) */
+/* Off-resonance correction for a trajectory operator by time segmentation (an EXTENSION, no reference counterpart, parity unpinned; DESIGN.md
+ * section 22).  A pixel f Hz off resonance accumulates the phase 2 pi f tau over a readout; with a field map attached the operator is
+ *   y_i = (1 / sqrt(N M)) sum_n (sum_c V(t(i), c) x_c[n]) exp(-i omega_i . n) exp(-i 2 pi f[n] tau_i)
+ * f_hz: N*M doubles in the layout of one channel plane of x (n1 + N n2), t_s: the m readout times tau_i in seconds in the order of y.  It is
+ * computed as L NUFFTs (Sutton, Noll & Fessler, IEEE TMI 2003):  exp(-i 2 pi f tau) ~ sum_{l<L} b_l(tau) exp(-i 2 pi f tau^_l)  with
+ *   - the centre frequency f0 = (f_min + f_max) / 2 taken out exactly (every sample carries exp(-i 2 pi f0 tau_i), the segmentation sees f - f0);
+ *   - segment times tau^_l = t_min + l (t_max - t_min) / (L - 1) (L = 1: t_min);
+ *   - per sample the least-squares coefficients over the nbins-bin histogram (p_h, f_h) of f - f0 (equal bins on [f_min - f0, f_max - f0], f_h the
+ *     bin centres, p_h the fraction of pixels):  (G^H P G + eps I) b = G^H P e(tau_i),  G_hl = exp(-i 2 pi f_h tau^_l),  eps = 1e-12 tr(G^H P G) / L.
+ *     The L x L matrix is factored once on the host; the m right-hand sides and substitutions run on the device in a fixed order (same bits on
+ *     every call);
+ *   - a constant map (f_max == f_min) is L = 1 and exact whatever nseg asks for (b = 1, fit 0).
+ * nseg = 0 (auto) tries L = 2, 3, ... 16 and keeps the first whose fit_max <= tol, else keeps 16 with info->tol_reached = 0.  info (nullable):
+ * fit_max / fit_rms are the maximum and the p-weighted rms over occupied bins x samples of |exp(-i 2 pi f_h tau_i) - sum_l b_l G_hl|, computed on
+ * the device.  The adjoint is the exact Hermitian transpose of what the forward computes (conj(b_l) on the samples, the conjugate phase maps on the
+ * images), so adjointness holds to rounding.  The map BELONGS TO THE OPERATOR: every call that runs the operator -- qmri_forward* / _adjoint*, the
+ * _mc calls, the image-domain LSQR of qmri_xupdate* and both PnP-ADMM loops, qmri_adjoint_w* (A_f^H (w .* y)) -- uses it, for every batch entry
+ * (every coil, every slice of a stack: ONE map per operator, per-slice maps are not built); replacing the operator drops it; f_hz == NULL clears it
+ * (t_s and p are then not read) and restores the bits of the operator without a map.  qmri_nufft_dcf is unaffected (the trajectory alone).
+ * Costs: about L times the plain transform per call; tables of L (N M + m) complex doubles on the device.
+ * Refusals, decided on the host before the device is selected: ctx == NULL, t_s == NULL with a map, a non-finite f or t, nseg outside 0..16, nbins
+ * outside {0, 16..1024}, tol negative or non-finite, reserved != 0, nseg = 1 with a non-constant map: QMRI_ERR_INVALID_ARG; no operator:
+ * QMRI_ERR_STATE; a gridded operator: QMRI_ERR_UNSUPPORTED.  While a map is attached qmri_nufft_prepare_normal, qmri_normal(_dev) and
+ * QMRI_SOLVER_TOEPLITZ return QMRI_ERR_UNSUPPORTED (A^H A is then L^2 Toeplitz terms, which are not built): use QMRI_SOLVER_LSQR. */
+typedef struct { int32_t nseg;    /* 1..16; 0 = auto */
+                 int32_t nbins;   /* histogram bins, 16..1024; 0 = 256 */
+                 double  tol;     /* auto: smallest L whose fit_max <= tol; 0 = 1e-4 */
+                 int32_t reserved[4]; } qmri_offres_params;          /* zeros = defaults */
+typedef struct { int32_t nseg; int32_t tol_reached;
+                 double fit_max, fit_rms, f_min, f_max, t_min, t_max;
+                 int32_t reserved[4]; } qmri_offres_info;
+int qmri_set_field_map(qmri_ctx* ctx, const double* f_hz, const double* t_s, const qmri_offres_params* p, qmri_offres_info* info);
 /* On a trajectory operator these work unchanged: qmri_forward / _adjoint (and _f32, _dev), qmri_operator_m, qmri_set_coils, qmri_forward_mc /
  * _adjoint_mc, qmri_xupdate_mc(_batch), qmri_pnp_admm_mc(_batch, _dev), qmri_coil_compress*, and qmri_xupdate / qmri_pnp_admm (one slice, LSQR,
  * no diagnostics) as the image-domain LSQR with one unit coil -- bit for bit the qmri_*_mc call with that coil.  Everything else that needs the

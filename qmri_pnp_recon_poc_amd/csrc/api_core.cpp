@@ -820,6 +820,7 @@ int qmri_lsqr_run(qmri_ctx* ctx, int B, const double2* d_z, double r, double tol
 
 extern "C" int qmri_xupdate(qmri_ctx* ctx, const void* y, const void* z, double r, double tol, int maxit, int solver,
                             void* x, int32_t* iters_out, int32_t* flag_out) {
+    if (solver == QMRI_SOLVER_TOEPLITZ) QMRI_TRY(offres_refuse_toeplitz(ctx, "QMRI_SOLVER_TOEPLITZ"));      // (a field map attached: decided on the host)
     REQUIRE_OP(ctx);
     QMRI_CHECK_ARG(ctx, y && z && x && r > 0 && maxit >= 0, "qmri_xupdate arguments");
     OpHost& o = ctx->op;

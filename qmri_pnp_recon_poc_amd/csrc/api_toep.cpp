@@ -18,6 +18,7 @@ int require_trajectory(qmri_ctx* ctx, const char* what, const char* instead) {
 
 extern "C" int qmri_nufft_prepare_normal(qmri_ctx* ctx) {
     QMRI_TRY(require_trajectory(ctx, "qmri_nufft_prepare_normal", "there is no Toeplitz normal operator to build"));
+    QMRI_TRY(offres_refuse_toeplitz(ctx, "qmri_nufft_prepare_normal"));
     QMRI_HIP(ctx, hipSetDevice(ctx->device));
     return toep_prepare(ctx);
 }
@@ -25,6 +26,7 @@ extern "C" int qmri_nufft_prepare_normal(qmri_ctx* ctx) {
 extern "C" int qmri_normal_dev(qmri_ctx* ctx, const void* d_x, void* d_out, int batch) {
     QMRI_TRY(require_trajectory(ctx, "qmri_normal_dev", "use qmri_adjoint_dev(qmri_forward_dev(x))"));
     QMRI_CHECK_ARG(ctx, d_x && d_out && batch >= 1 && batch <= ctx->op.maxB, "qmri_normal_dev arguments / batch > max_batch");
+    QMRI_TRY(offres_refuse_toeplitz(ctx, "qmri_normal_dev"));
     QMRI_HIP(ctx, hipSetDevice(ctx->device));
     return toep_apply(ctx, batch, (const double2*)d_x, (double2*)d_out);
 }
@@ -32,6 +34,7 @@ extern "C" int qmri_normal_dev(qmri_ctx* ctx, const void* d_x, void* d_out, int 
 extern "C" int qmri_normal(qmri_ctx* ctx, const void* x, int x_is_complex, void* out) {
     QMRI_TRY(require_trajectory(ctx, "qmri_normal", "use qmri_adjoint(qmri_forward(x))"));
     QMRI_CHECK_ARG(ctx, x && out, "x / out must not be NULL");
+    QMRI_TRY(offres_refuse_toeplitz(ctx, "qmri_normal"));
     QMRI_HIP(ctx, hipSetDevice(ctx->device));
     OpHost& o = ctx->op;
     const size_t n = (size_t)o.N * o.M * o.s;
@@ -50,7 +53,7 @@ extern "C" int qmri_normal(qmri_ctx* ctx, const void* x, int x_is_complex, void*
 int toep_check_solver(qmri_ctx* ctx, int solver) {
     if (solver != QMRI_SOLVER_TOEPLITZ) return QMRI_OK;
     if (!ctx->op.ready) { qmri_set_error(ctx, "operator not set: call qmri_set_operator first"); return QMRI_ERR_STATE; }
-    if (ctx->op.kind == OP_NUFFT) return QMRI_OK;
+    if (ctx->op.kind == OP_NUFFT) return offres_refuse_toeplitz(ctx, "QMRI_SOLVER_TOEPLITZ");      // (a field map: the Toeplitz form is not built)
     qmri_set_error(ctx, "QMRI_SOLVER_TOEPLITZ needs a trajectory operator (qmri_set_operator_nufft): on a gridded operator A^H A is already diagonal "
                         "per k-space location; use QMRI_SOLVER_LSQR (the k-space LSQR)");
     return QMRI_ERR_UNSUPPORTED;
@@ -58,6 +61,7 @@ int toep_check_solver(qmri_ctx* ctx, int solver) {
 
 int mc_xupdate_dev(qmri_ctx* ctx, int solver, int B, int ncoil, const double2* d_maps, const double2* d_y, const double2* d_z, double r, double tol, int maxit,
                    double2* d_x, int32_t* iters_out, int32_t* flags_out) {
+    if (solver == QMRI_SOLVER_TOEPLITZ) QMRI_TRY(offres_refuse_toeplitz(ctx, "QMRI_SOLVER_TOEPLITZ"));     // (a transform built before the map is never used with it)
     if (solver == QMRI_SOLVER_TOEPLITZ) return qmri_cg_toep_batch_dev(ctx, B, ncoil, d_maps, d_y, d_z, r, tol, maxit, d_x, iters_out, flags_out);
     return qmri_lsqr_mc_batch_dev(ctx, B, ncoil, d_maps, d_y, d_z, r, tol, maxit, d_x, iters_out, flags_out);
 }

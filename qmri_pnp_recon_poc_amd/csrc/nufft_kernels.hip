@@ -15,6 +15,12 @@
 //             k_nu_post    sum over the 4 sub-grids in a fixed order with the conjugate ramps, times 1 / Phi(p)
 // Forward and adjoint evaluate the kernel with the same device function on the same inputs (nu_phi(u - k) with k from nu_k0), so adjointness
 // holds to rounding.  Interpolation and spreading are gathers with w^2 reuse per sample: vector fp64 FMA, no MFMA.
+//
+// With a field map attached (qmri_set_field_map) nufft_launch_fwd / launch_adj run the chain once per time segment l with the
+// OFFRES instantiations, which fold the segment's factors in where the data already is in registers or LDS: k_nu_pre times the phase map P_l,
+// k_nu_interp times b_l (adding to y for l > 0); k_nu_spread times conj(b_l) as y is staged (after the sample weight), k_nu_post times conj(P_l)
+// (adding to x for l > 0).  Segments run one after the other on the stream, so the sums have a fixed order.  The instantiations without OFFRES are
+// the ones used without a map and compile to what they were before the parameter existed.
 #include "dc_device.h"
 #include "nufft_device.h"
 
@@ -25,14 +31,16 @@ namespace {
 
 // x [B][c][n2][n1] -> g [B][a][c][q2][q1], a = a1 + 2 a2, q = (n + N/2) mod N
 // DEAPOD = false: the ramps alone, without 1 / Phi -- the zero-padded 2N x 2M DFT of the Toeplitz normal operator (toep_kernels.hip, "k_toep_pre")
-template <bool DEAPOD>
+// OFFRES: x times the segment's phase map nu.pm (one table entry per pixel, shared by the channels; no sincos here) first
+template <bool DEAPOD, bool OFFRES = false>
 __global__ __launch_bounds__(NT) void k_nu_pre(NufftDev nu, const double2* __restrict__ x, double2* __restrict__ g) {
     const int N = nu.N, M = nu.M, b = blockIdx.y;
     const size_t plane = (size_t)N * M, n = plane * nu.s;
     const size_t i = (size_t)blockIdx.x * NT + threadIdx.x;
     if (i >= n) return;
     const int c = (int)(i / plane), r = (int)(i - (size_t)c * plane), n2 = r / N, n1 = r - n2 * N;
-    const double2 v = x[(size_t)b * n + i];
+    double2 v = x[(size_t)b * n + i];
+    if (OFFRES) { const double2 p = nu.pm[r]; v = make_double2(v.x * p.x - v.y * p.y, v.x * p.y + v.y * p.x); }
     const double sc = DEAPOD ? nu.dp1[n1] * nu.dp2[n2] : 1.0;
     const double2 x0 = DEAPOD ? make_double2(v.x * sc, v.y * sc) : v;
     const double2 e1 = nu.r1[n1], e2 = nu.r2[n2];
@@ -59,7 +67,8 @@ __global__ __launch_bounds__(NT) void k_nu_interleave(NufftDev nu, const double2
 }
 
 // forward interpolation: one lane per sample, in the plan's bin order, on the interleaved grid G
-template <int W>
+// OFFRES: the sample times the segment's coefficient nu.bl (sorted order, as u and ph), added to y for the segments after the first
+template <int W, bool OFFRES = false>
 __global__ __launch_bounds__(NT) void k_nu_interp(NufftDev nu, const double2* __restrict__ S, double2* __restrict__ y) {
     const int e = blockIdx.x * NT + threadIdx.x, b = blockIdx.y;
     if (e >= nu.m) return;
@@ -93,13 +102,22 @@ __global__ __launch_bounds__(NT) void k_nu_interp(NufftDev nu, const double2* __
     for (int c = 0; c < DC_MAXS; ++c)
         if (c < s) { const double v = vr[c]; re = fma(v, ar[c], re); im = fma(v, ai[c], im); }
     const double2 ph = nu.ph[e];
+    if (OFFRES) {
+        const double2 v = make_double2(re * ph.x - im * ph.y, re * ph.y + im * ph.x), bl = nu.bl[e];
+        double2 o = make_double2(v.x * bl.x - v.y * bl.y, v.x * bl.y + v.y * bl.x);
+        double2* dst = y + (size_t)b * nu.m + nu.perm[e];
+        if (nu.acc) { const double2 p = *dst; o.x += p.x; o.y += p.y; }
+        *dst = o;
+        return;
+    }
     y[(size_t)b * nu.m + nu.perm[e]] = make_double2(re * ph.x - im * ph.y, re * ph.y + im * ph.x);
 }
 
 // adjoint spreading: one workgroup per (segment, slice); thread (r1, r2) owns grid point (16 t1 + r1, 16 t2 + r2) of the 2N x 2M grid
 constexpr int NU_CH = 64;        // samples staged in LDS at a time
 // WEIGHTED: y times the attached sample weight (nu.wgt, ABI order) as it is staged -- the weighted adjoint of DESIGN.md section 21, no pass over y
-template <bool WEIGHTED>
+// OFFRES: then times conj(b_l) of the segment (nu.bl, sorted order) -- it composes with WEIGHTED: A_f^H (w .* y)
+template <bool WEIGHTED, bool OFFRES = false>
 __global__ __launch_bounds__(NT) void k_nu_spread(NufftDev nu, const double2* __restrict__ y, double2* __restrict__ grid, double2* __restrict__ part) {
     __shared__ double2 vy[NU_CH * DC_MAXS];           // V(t, c) * conj(ph) * y of the staged samples
     __shared__ double wl[NU_CH][2 * NU_TB];           // their weights along both axes at the tile's 16 + 16 grid lines (0 outside the window)
@@ -120,6 +138,7 @@ __global__ __launch_bounds__(NT) void k_nu_spread(NufftDev nu, const double2* __
             double2 yv = y[(size_t)b * nu.m + nu.perm[e]];
             const double2 ph = nu.ph[e];
             if (WEIGHTED) { const double wq = nu.wgt[nu.perm[e]]; yv.x *= wq; yv.y *= wq; }
+            if (OFFRES) { const double2 bl = nu.bl[e]; yv = make_double2(yv.x * bl.x + yv.y * bl.y, yv.y * bl.x - yv.x * bl.y); }       // y * conj(b_l)
             const double yr = yv.x * ph.x + yv.y * ph.y, yi = yv.y * ph.x - yv.x * ph.y;      // y * conj(ph)
             const double v = nu.Vt[(size_t)nu.t[e] * s + c];
             vy[j * DC_MAXS + c] = make_double2(v * yr, v * yi);
@@ -197,7 +216,8 @@ __global__ __launch_bounds__(NT) void k_nu_adj_w(OpDev op, const double2* __rest
 
 // images of the 4 sub-grids [B][a][c][q2][q1] -> x [B][c][n2][n1]: sum over a = 0..3 in order of conj(ramp_a) * g_a, times 1 / Phi(p)
 // DEAPOD = false: without 1 / Phi -- the crop of the 2N x 2M inverse DFT (toep_kernels.hip, "k_toep_post")
-template <bool DEAPOD>
+// OFFRES: then times the conjugate of the segment's phase map, added to x for the segments after the first
+template <bool DEAPOD, bool OFFRES = false>
 __global__ __launch_bounds__(NT) void k_nu_post(NufftDev nu, const double2* __restrict__ g, double2* __restrict__ x) {
     const int N = nu.N, M = nu.M, b = blockIdx.y;
     const size_t plane = (size_t)N * M, n = plane * nu.s;
@@ -214,7 +234,14 @@ __global__ __launch_bounds__(NT) void k_nu_post(NufftDev nu, const double2* __re
     const double2 t3 = make_double2(g3.x * e1.x + g3.y * e1.y, g3.y * e1.x - g3.x * e1.y);
     const double2 h3 = make_double2(t3.x * e2.x + t3.y * e2.y, t3.y * e2.x - t3.x * e2.y);
     const double re = ((g0.x + h1.x) + h2.x) + h3.x, im = ((g0.y + h1.y) + h2.y) + h3.y;
-    if (DEAPOD) {
+    if (OFFRES) {
+        const double sc = DEAPOD ? nu.dp1[n1] * nu.dp2[n2] : 1.0;
+        const double vr = re * sc, vi = im * sc;
+        const double2 p = nu.pm[r];
+        double2 o = make_double2(vr * p.x + vi * p.y, vi * p.x - vr * p.y);                 // v * conj(P_l)
+        if (nu.acc) { const double2 q = x[(size_t)b * n + i]; o.x += q.x; o.y += q.y; }
+        x[(size_t)b * n + i] = o;
+    } else if (DEAPOD) {
         const double sc = nu.dp1[n1] * nu.dp2[n2];
         x[(size_t)b * n + i] = make_double2(re * sc, im * sc);
     } else {
@@ -239,11 +266,22 @@ NufftDev nufft_dev(const qmri_ctx* ctx) {
     d.Vt = o.d_Vt; d.u = (const double2*)h.d_u; d.ph = (const double2*)h.d_ph; d.t = h.d_t; d.perm = h.d_perm; d.list = h.d_list;
     d.seg = h.d_seg; d.red = h.d_red; d.dp1 = h.d_dp; d.dp2 = h.d_dp + o.N; d.r1 = h.d_r; d.r2 = h.d_r + o.N;
     d.wgt = h.w_set ? h.d_w : nullptr;
+    d.pm = nullptr; d.bl = nullptr; d.acc = 0;
+    return d;
+}
+// the view of segment l of the attached field map
+NufftDev nufft_dev_seg(const qmri_ctx* ctx, int l) {
+    NufftDev d = nufft_dev(ctx);
+    const NufftHost& h = ctx->op.nu;
+    d.pm = h.d_pm + (size_t)l * ctx->op.N * ctx->op.M;
+    d.bl = h.d_bl + (size_t)l * ctx->op.m;
+    d.acc = l > 0;
     return d;
 }
 
 template <int W> int launch_interp_t(qmri_ctx* ctx, const NufftDev& nu, int B, const double2* S, double2* y) {
-    k_nu_interp<W><<<dim3((nu.m + NT - 1) / NT, B), dim3(NT), 0, ctx->stream>>>(nu, S, y);
+    if (nu.bl) k_nu_interp<W, true><<<dim3((nu.m + NT - 1) / NT, B), dim3(NT), 0, ctx->stream>>>(nu, S, y);
+    else k_nu_interp<W><<<dim3((nu.m + NT - 1) / NT, B), dim3(NT), 0, ctx->stream>>>(nu, S, y);
     QMRI_HIP(ctx, hipGetLastError());
     return QMRI_OK;
 }
@@ -283,9 +321,23 @@ int nufft_launch_unramps(qmri_ctx* ctx, int B, const double2* g, double2* x) {
 int nufft_launch_fwd(qmri_ctx* ctx, int B, const double2* x, double2* y) {
     OpHost& o = ctx->op;
     if (o.kind != OP_NUFFT || B < 1 || B > o.maxB) { qmri_set_error(ctx, "nufft_launch_fwd: no trajectory operator / batch out of range (internal)"); return QMRI_ERR_STATE; }
-    const NufftDev nu = nufft_dev(ctx);
     const OpDev op = qmri_opdev(ctx);
     const size_t n = (size_t)o.N * o.M * o.s;
+    if (o.nu.fm_set) {
+        // a field map: the chain once per segment, the B entries of the call at a time (the work buffers hold max_batch entries, which the callers
+        // fill), y = sum_l b_l .* NUFFT(P_l .* x) in segment order
+        for (int l = 0; l < o.nu.fm_L; ++l) {
+            const NufftDev nl = nufft_dev_seg(ctx, l);
+            k_nu_pre<true, true><<<dim3((unsigned)((n + NT - 1) / NT), B), dim3(NT), 0, ctx->stream>>>(nl, x, o.nu.d_g);
+            QMRI_HIP(ctx, hipGetLastError());
+            QMRI_TRY(dc_launch_fwd(ctx, op, o.ls, DC_SPECTRUM, 4 * B, o.nu.d_g, o.nu.d_grid, o.nu.d_g, nullptr));
+            k_nu_interleave<<<dim3((unsigned)((4 * n + NT - 1) / NT), B), dim3(NT), 0, ctx->stream>>>(nl, o.nu.d_g, o.nu.d_grid);
+            QMRI_HIP(ctx, hipGetLastError());
+            QMRI_TRY(launch_interp(ctx, nl, B, o.nu.d_grid, y));
+        }
+        return QMRI_OK;
+    }
+    const NufftDev nu = nufft_dev(ctx);
     k_nu_pre<true><<<dim3((unsigned)((n + NT - 1) / NT), B), dim3(NT), 0, ctx->stream>>>(nu, x, o.nu.d_g);
     QMRI_HIP(ctx, hipGetLastError());
     // the 4 sub-grids of every slice as 4B slices through the dense spectrum passes (d_grid as their workspace, the spectra back into d_g)
@@ -302,6 +354,24 @@ static int launch_adj(qmri_ctx* ctx, int B, const double2* y, double2* x, bool w
     if (weighted && !nu.wgt) { qmri_set_error(ctx, "nufft_launch_adj_w: no sample weights attached (internal)"); return QMRI_ERR_STATE; }
     const OpDev op = qmri_opdev(ctx);
     const size_t n = (size_t)o.N * o.M * o.s;
+    if (o.nu.fm_set) {
+        // x = sum_l conj(P_l) .* NUFFT^H(conj(b_l) .* (w .*) y) in segment order: the exact transpose of the forward's segments
+        for (int l = 0; l < o.nu.fm_L; ++l) {
+            const NufftDev nl = nufft_dev_seg(ctx, l);
+            if (weighted) k_nu_spread<true, true><<<dim3(nl.nseg, B), dim3(NT), 0, ctx->stream>>>(nl, y, o.nu.d_grid, o.nu.d_part);
+            else k_nu_spread<false, true><<<dim3(nl.nseg, B), dim3(NT), 0, ctx->stream>>>(nl, y, o.nu.d_grid, o.nu.d_part);
+            QMRI_HIP(ctx, hipGetLastError());
+            if (nl.nred > 0) {
+                k_nu_reduce<<<dim3(nl.nred, B, nl.s), dim3(NT), 0, ctx->stream>>>(nl, o.nu.d_part, o.nu.d_grid);
+                QMRI_HIP(ctx, hipGetLastError());
+            }
+            QMRI_TRY(with_plan(ctx, op.M, [&](auto p) { return launch_adj_w_t<decltype(p)::R1, decltype(p)::R2>(ctx, op, 4 * B, o.nu.d_grid, o.nu.d_g); }));
+            QMRI_TRY(dc_launch_adj_h(ctx, op, 4 * B, o.nu.d_g, o.nu.d_grid));
+            k_nu_post<true, true><<<dim3((unsigned)((n + NT - 1) / NT), B), dim3(NT), 0, ctx->stream>>>(nl, o.nu.d_grid, x);
+            QMRI_HIP(ctx, hipGetLastError());
+        }
+        return QMRI_OK;
+    }
     if (weighted) k_nu_spread<true><<<dim3(nu.nseg, B), dim3(NT), 0, ctx->stream>>>(nu, y, o.nu.d_grid, o.nu.d_part);
     else k_nu_spread<false><<<dim3(nu.nseg, B), dim3(NT), 0, ctx->stream>>>(nu, y, o.nu.d_grid, o.nu.d_part);
     QMRI_HIP(ctx, hipGetLastError());

@@ -382,6 +382,10 @@ struct NufftDev {
     const double* dp1; const double* dp2;        // [N], [M] deapodisation 1 / Phi at n - N/2
     const double2* r1; const double2* r2;        // [N], [M] exp(-i pi (n - N/2) / N): the half-bin ramps
     const double* wgt;                           // [m] ABI order: the attached sample weights or null; read by k_nu_spread<true> only
+    // the segment of a field map that a launch works on; read by the OFFRES instantiations only, null / 0 without a map
+    const double2* pm;                           // [N*M] plane order (n1 + N n2): exp(-i 2 pi (f - f0) tau^_l)
+    const double2* bl;                           // [m] sorted: b_l(tau_i) exp(-i 2 pi f0 tau_i)
+    int acc;                                     // 1: add to the output (segments l > 0), 0: overwrite it
 };
 struct NufftHost {
     double* d_u = nullptr; double* d_ph = nullptr; int32_t* d_t = nullptr; int32_t* d_perm = nullptr; int32_t* d_list = nullptr;
@@ -398,6 +402,13 @@ struct NufftHost {
     // qmri_set_sample_weights, read by the qmri_adjoint_w* calls alone, freed by nufft_free (replacing the operator drops them)
     double* d_w = nullptr;
     bool w_set = false;
+    // field map of the off-resonance correction (time segmentation): attached by qmri_set_field_map, read by nufft_launch_fwd /
+    // _adj (every caller of the operator), freed by nufft_free (replacing the operator drops it).  Sized at attach time.
+    double2* d_pm = nullptr;                     // [fm_L][N*M] phase maps of the segments
+    double2* d_bl = nullptr;                     // [fm_L][m] coefficients in the plan's sorted order, the centre-frequency phase folded in
+    size_t pm_cap = 0, bl_cap = 0;               // elements allocated
+    int fm_L = 0;                                // segments
+    bool fm_set = false;
 };
 // the exponential spiral of setup_subsampling_spiralgrided.m:7-27 before rounding (shared by qmri_build_spiral and qmri_build_spiral_traj): S angles
 // theta_j and radii r_j normalised to [0, 1]; frame f is rotated by f * SPIRAL_DELTA
@@ -410,6 +421,16 @@ int nufft_launch_adj_w(qmri_ctx* ctx, int B, const double2* y, double2* x);  // 
 // iterations (1..200) from w = 1, stopped early once max |d - 1| <= tol (tol <= 0: never), then d_w_out [m] (ABI order) = kappa * w.  Uses the plan's
 // d_grid / d_part as scratch; waits for its kernels.
 int dcf_weights_dev(qmri_ctx* ctx, int niter, double tol, double kappa, double* d_w_out, qmri_dcf_info* info);
+// time-segmented off-resonance correction (offres_kernels.hip, api_offres.cpp)
+struct OffresFit { double fit_max, fit_rms; };
+// d_pm [L][N*M] = exp(-i 2 pi (f - f0) tauhat_l) from d_f [N*M]
+int offres_phase_maps_dev(qmri_ctx* ctx, int L, size_t plane, const double* d_f, double f0, const double* d_tauhat, double2* d_pm);
+// d_bl [L][m] (sorted order) from the Cholesky factor d_chol [L][L] (lower, row-major) of G^H P G + eps I, the histogram d_hist [nbins] (x: p_h,
+// y: f_h) and its table d_G [nbins][L]; exact = a constant map (b = 1).  Fills *fit (device reductions in a fixed order) and waits for its kernels.
+int offres_coefficients_dev(qmri_ctx* ctx, int L, int nbins, bool exact, const double2* d_hist, const double2* d_G, const double2* d_chol,
+                            const double* d_ts, double f0, double2* d_bl, OffresFit* fit);
+// QMRI_ERR_UNSUPPORTED with a message naming LSQR while a field map is attached, else QMRI_OK (host check only)
+int offres_refuse_toeplitz(qmri_ctx* ctx, const char* what);
 int nufft_check_gridded(qmri_ctx* ctx, const char* what, const char* instead);   // QMRI_ERR_UNSUPPORTED on a trajectory operator, else QMRI_OK
 void nufft_free(NufftHost& h);
 bool nufft_kernel_ok(int w);

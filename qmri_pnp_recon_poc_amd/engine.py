@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import AdmmParams, CcParams, CsmInfo, CsmParams, DcfInfo, DcfParams, DsvdInfo, DsvdParams, EpgParams, LrtvInfo, LrtvParams, NetDesc, NufftParams, Profile
+from ._lib import AdmmParams, CcParams, CsmInfo, CsmParams, DcfInfo, DcfParams, DsvdInfo, DsvdParams, EpgParams, LrtvInfo, LrtvParams, NetDesc, NufftParams, OffresInfo, OffresParams, Profile
 
 ARCH_UNETRES, ARCH_SEQ_CONV = 0, 1
 SOLVER_LSQR, SOLVER_DIRECT = 0, 1
@@ -176,6 +176,16 @@ def build_spiral_traj(N: int, S: int, T: int):
     return fp, om[: m.value].copy()
 
 
+def spiral_readout_times(S: int, T: int, readout_s: float):
+    """Readout times of build_spiral_traj's samples for set_field_map: sample j of every frame is measured at tau = j * readout_s / S seconds after
+    the frame's excitation -> t_s [S * T] float64, frame-major as y."""
+    if int(S) != S or int(T) != T or S < 1 or T < 1:
+        raise ValueError("S and T must be positive integers")
+    if not (np.isfinite(readout_s) and readout_s >= 0):
+        raise ValueError("readout_s must be finite and >= 0 (seconds)")
+    return np.tile(np.arange(int(S), dtype=np.float64) * (float(readout_s) / int(S)), int(T))
+
+
 def read_onnx_unetres(path):
     """Weights of the ONNX file main_recon_tsmis_FFT.m:138 imports, through the library's own reader
     (qmri_onnx_read_unetres) -> (flat fp32 weights, dict(in_nc, out_nc, nc, nb))."""
@@ -329,6 +339,43 @@ class Engine:
         if wb.size != self.m:
             raise ValueError(f"w must have {self.m} elements")
         self._check(self.L.qmri_set_sample_weights(self.h, wb.ctypes.data_as(C.POINTER(C.c_double))))
+
+    # -- off-resonance correction of a trajectory operator (extension, no reference counterpart) ----------------
+    def set_field_map(self, f_hz, t_s=None, nseg=0, nbins=0, tol=0.0):
+        """Attach a field map to the trajectory operator (qmri_set_field_map): f_hz [N, M] real, Hz; t_s [m] the readout time of every sample in
+        seconds, the order of y (spiral_readout_times makes them for the project's spiral).  The operator then carries exp(-i 2 pi f[n] t_i), by time
+        segmentation with nseg segments (1..16; 0: the smallest whose fit_max <= tol, tol 0: 1e-4) fitted over an nbins-bin histogram (16..1024; 0:
+        256).  forward / adjoint / the _mc methods / xupdate / pnp_admm all run the corrected operator; normal, prepare_normal and solver="toeplitz"
+        are refused while a map is attached.  None clears the map.  One map per operator (every coil, every slice).
+        Returns dict(nseg, tol_reached, fit_max, fit_rms, f_min, f_max, t_min, t_max), or None after clearing."""
+        if f_hz is None:
+            self._check(self.L.qmri_set_field_map(self.h, None, None, None, None))
+            return None
+        f = np.asarray(f_hz)
+        if np.iscomplexobj(f):
+            raise ValueError("the field map must be real (Hz)")
+        if f.shape != (self.N, self.M):
+            raise ValueError(f"f_hz must be {self.N}x{self.M}")
+        if t_s is None:
+            raise ValueError("t_s (the readout time of every sample, seconds) is needed with a field map")
+        t = np.asarray(t_s)
+        if np.iscomplexobj(t):
+            raise ValueError("the readout times must be real (seconds)")
+        tb = np.ascontiguousarray(t, dtype=np.float64).ravel()
+        if tb.size != self.m:
+            raise ValueError(f"t_s must have {self.m} elements")
+        if int(nseg) != nseg or not (0 <= int(nseg) <= 16):
+            raise ValueError("nseg must be an integer in 1..16 (0: automatic)")
+        if int(nbins) != nbins or not (int(nbins) == 0 or 16 <= int(nbins) <= 1024):
+            raise ValueError("nbins must be an integer in 16..1024 (0: the default 256)")
+        if not (np.isfinite(tol) and tol >= 0):
+            raise ValueError("tol must be finite and >= 0")
+        fb = np.ascontiguousarray(np.asarray(f, dtype=np.float64).ravel(order="F"))
+        p, info = OffresParams(int(nseg), int(nbins), float(tol)), OffresInfo()
+        dp = C.POINTER(C.c_double)
+        self._check(self.L.qmri_set_field_map(self.h, fb.ctypes.data_as(dp), tb.ctypes.data_as(dp), C.byref(p), C.byref(info)))
+        return {"nseg": int(info.nseg), "tol_reached": int(info.tol_reached), "fit_max": float(info.fit_max), "fit_rms": float(info.fit_rms),
+                "f_min": float(info.f_min), "f_max": float(info.f_max), "t_min": float(info.t_min), "t_max": float(info.t_max)}
 
     def adjoint(self, y, weighted=False):
         """x = F.adjoint(y)  (main_recon_tsmis_FFT.m:229); complex64 in -> complex64 out (the _f32 entry point).

@@ -278,7 +278,8 @@ def save_training_pickle(path, X_slices, channels_to_save=None):
 def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", subsampling_pattern="Spiral",
                 spiral_sampling_curve=771, epi_sampling_rate=1 / 65, measurements_type="noisy", measurements_noise=30,
                 denoiser_type="single_level", noise_map_std=0.01, residual_noise=False, iters=100, seed=0, Y=None, device=0,
-                net_arch=None, lrtv_iters=None, tsmi_domain="real", solver="lsqr", b1_map=None, density_compensation=False):
+                net_arch=None, lrtv_iters=None, tsmi_domain="real", solver="lsqr", b1_map=None, density_compensation=False,
+                field_map=None, readout_s=None):
     """main_recon_tsmis_FFT.m:216-374 on already loaded (and cropped) arrays.
 
     dictionary  dict(V, D, normD, lut) (load_dictionary);  X0  N x M x s ground-truth TSMI;  qmap0  N x M x 3
@@ -292,6 +293,9 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
                 pixel is matched against the atoms of the b1 nearest its value, NaN = background, all outputs zero
     density_compensation  with SpiralExact: SVD_MRF is the density-compensated adjoint A^H (w .* y) and PnP_ADMM starts from it (Pipe-Menon
                 weights); False (default) is the bare adjoint
+    field_map, readout_s  with SpiralExact, PnP_ADMM or SVD_MRF: an N x M field map in Hz and the length of one spiral readout in seconds (sample j of a
+                frame is measured at j * readout_s / S): the operator carries the off-resonance phase (time segmentation), for
+                the measurements it simulates (when Y is not given) and for the reconstruction.  Absent: the operator without a map, bit for bit.
     Returns dict(X, qmap (N x M x 3: T1, T2, PD), Y, metrics, foreground_mask); with b1_map also grp (N x M, the 1-based b1 group, 0 = unmatched).
     """
     from . import reference_api as R
@@ -319,7 +323,13 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
         raise ValueError(f"unknown subsampling pattern {subsampling_pattern}")
     if density_compensation and subsampling_pattern != "SpiralExact":
         raise ValueError("density_compensation needs the subsampling pattern SpiralExact (a gridded mask has nothing to compensate)")
-    F = R.make_F(P, device=device)
+    if (field_map is None) != (readout_s is None):
+        raise ValueError("field_map and readout_s go together")
+    if field_map is not None and subsampling_pattern != "SpiralExact":
+        raise ValueError("field_map needs the subsampling pattern SpiralExact (a gridded mask has no readout times)")
+    if field_map is not None and solver == "toeplitz":
+        raise ValueError('with a field_map the x-update is solver="lsqr": the Toeplitz normal operator of the corrected operator is not built')
+    F = R.make_F(P, device=device) if field_map is None else R.make_F(P, device=device, field_map=field_map, readout_s=readout_s)
     if density_compensation:
         F._engine.density_weights()                                                  # (make_F planned the operator afresh: nothing was attached)
     if Y is None:

@@ -21,6 +21,8 @@
 //     'dcf' computes and attaches density weights (qmri_nufft_dcf; extension), 'set_sample_weights' attaches the caller's,
 //     'adjoint_w' is the weighted adjoint A^H (w .* y).  Re-planning the operator drops the weights: 'set_trajectory', 'device', and any
 //     call that brings more slices than the plan's max_batch (it re-plans the operator for them); call 'dcf' / 'set_sample_weights' again after it.
+//     'set_field_map' attaches a field map for the off-resonance correction (qmri_set_field_map; extension).  The same
+//     re-plans drop the map with the weights: call 'set_field_map' again after them.
 //   * 'recon_batch_mc' is the same for multi-coil stacks, every slice with its own coil maps (qmri_recon_batch_mc; an extension, no reference
 //     counterpart); with a coil-compression argument every launch compresses its slices on the device first (qmri_recon_batch_mc_cc).
 //   * 'coil_compress' compresses a multi-coil stack to virtual coils (qmri_coil_compress; extension).
@@ -351,6 +353,34 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         const mwSize dims[3] = {(mwSize)g_op.N, (mwSize)g_op.M, (mwSize)mxGetN(g_op.V)};
         plhs[0] = mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxCOMPLEX);
         check(qmri_adjoint_w(ctx(), mxGetComplexDoubles(prhs[1]), mxGetComplexDoubles(plhs[0])));
+    } else if (c == "set_field_map") {               // info = qmri_mex('set_field_map', f, t [, nseg [, nbins [, tol]]]): N x M real Hz, m x 1 seconds; f = [] clears
+        need(nrhs, 2, "info = qmri_mex('set_field_map', f, t [, nseg, nbins, tol])");
+        want(mxIsDouble(prhs[1]) && !mxIsComplex(prhs[1]), "qmri:set_field_map:type", "f must be a real double N x M array in Hz (or [])");
+        qmri_offres_params fp{};                                    // (the argument checks come first: they need no operator)
+        if (nrhs > 3) fp.nseg = int_arg(prhs[3], 0, 16, "qmri:set_field_map:nseg", "nseg must be an integer in 1..16 (0: automatic)");
+        if (nrhs > 4) {
+            fp.nbins = int_arg(prhs[4], 0, 1024, "qmri:set_field_map:nbins", "nbins must be an integer in 16..1024 (0: the default 256)");
+            want(fp.nbins == 0 || fp.nbins >= 16, "qmri:set_field_map:nbins", "nbins must be an integer in 16..1024 (0: the default 256)");
+        }
+        if (nrhs > 5) {
+            want(mxIsDouble(prhs[5]) && !mxIsComplex(prhs[5]) && mxGetNumberOfElements(prhs[5]) == 1, "qmri:set_field_map:tol", "tol must be a real double scalar");
+            fp.tol = mxGetScalar(prhs[5]);
+            want(std::isfinite(fp.tol) && fp.tol >= 0.0, "qmri:set_field_map:tol", "tol must be finite and >= 0 (0: the default 1e-4)");
+        }
+        want(g_op.V != nullptr, "qmri:state", "no operator: call qmri_mex('set_trajectory', ...) (qmri_make_F_traj) first");
+        want(g_op.omega != nullptr, "qmri:set_field_map:trajectory", "a field map needs a trajectory operator ('set_trajectory'): a gridded mask has no readout times");
+        if (mxIsEmpty(prhs[1])) { check(qmri_set_field_map(ctx(), nullptr, nullptr, nullptr, nullptr)); return; }
+        need(nrhs, 3, "info = qmri_mex('set_field_map', f, t [, nseg, nbins, tol])");
+        want(mxGetNumberOfElements(prhs[1]) == (size_t)g_op.N * (size_t)g_op.M && mxGetM(prhs[1]) == (size_t)g_op.N, "qmri:set_field_map:size",
+             "f must be N x M, one entry per pixel");
+        want(mxIsDouble(prhs[2]) && !mxIsComplex(prhs[2]), "qmri:set_field_map:type", "t must be a real double vector of readout times in seconds");
+        want(mxGetNumberOfElements(prhs[2]) == operator_m(), "qmri:set_field_map:size", "t must have one entry per sample");
+        qmri_offres_info fi{};
+        check(qmri_set_field_map(ctx(), mxGetDoubles(prhs[1]), mxGetDoubles(prhs[2]), &fp, &fi));
+        const char* names[] = {"nseg", "tol_reached", "fit_max", "fit_rms", "f_min", "f_max", "t_min", "t_max"};
+        const double vals[] = {(double)fi.nseg, (double)fi.tol_reached, fi.fit_max, fi.fit_rms, fi.f_min, fi.f_max, fi.t_min, fi.t_max};
+        plhs[0] = mxCreateStructMatrix(1, 1, 8, names);
+        for (int k = 0; k < 8; ++k) mxSetFieldByNumber(plhs[0], 0, k, mxCreateDoubleScalar(vals[k]));
     } else if (c == "set_denoiser") {                // qmri_mex('set_denoiser', weights(single), in_nc, out_nc, nc(1x4), nb, residual_noise, H, W [, max_batch])
         need(nrhs, 9, "qmri_mex('set_denoiser', weights, in_nc, out_nc, nc, nb, residual_noise, H, W [, max_batch])");
         qmri_net_desc d;

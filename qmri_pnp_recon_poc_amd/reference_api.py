@@ -58,18 +58,27 @@ def setup_subsampling_spiral_exact(N, M, S, V):
         raise ValueError(f"the spiral is square (setup_subsampling_spiralgrided.m:28-31): N = {N} != M = {M}")
     V = np.real(np.asarray(V, dtype=np.complex128)).astype(np.float64)
     fp, om = E.build_spiral_traj(int(N), int(S), V.shape[0])
-    return SimpleNamespace(N=int(N), M=int(M), V=V, frame_ptr=fp, omega=om, pattern="SpiralExact")
+    return SimpleNamespace(N=int(N), M=int(M), V=V, frame_ptr=fp, omega=om, pattern="SpiralExact", S=int(S))
 
 
-def make_F(P, device=0):
+def make_F(P, device=0, field_map=None, readout_s=None):
     """F.forward = @(x) P.for(reshape(fft2(x),[],1))/sqrt(N*M);  F.adjoint = @(x) ifft2(reshape(P.adj(x),N,M,[]))*sqrt(N*M).
-    A P with a trajectory (setup_subsampling_spiral_exact) gives the same two maps at the exact sample positions."""
+    A P with a trajectory (setup_subsampling_spiral_exact) gives the same two maps at the exact sample positions; field_map (N x M, Hz) with
+    readout_s (the length of one spiral readout, seconds) then attaches the off-resonance correction (an extension):
+    F.forward / F.adjoint and PnP_ADMM carry exp(-i 2 pi f tau).  F.field_info is what Engine.set_field_map reported, or None."""
+    if (field_map is None) != (readout_s is None):
+        raise ValueError("field_map and readout_s go together")
+    if field_map is not None and getattr(P, "omega", None) is None:
+        raise ValueError("field_map needs a trajectory operator (setup_subsampling_spiral_exact): a gridded mask has no readout times")
     eng = _engine(device)
+    info = None
     if getattr(P, "omega", None) is not None:
         eng.set_trajectory(P.N, P.M, P.V, P.frame_ptr, P.omega)
+        if field_map is not None:
+            info = eng.set_field_map(field_map, E.spiral_readout_times(P.S, P.V.shape[0], readout_s))
     else:
         eng.set_operator(P.N, P.M, P.V, P.frame_ptr, P.kidx)
-    return SimpleNamespace(forward=eng.forward, adjoint=eng.adjoint, _engine=eng, _P=P)
+    return SimpleNamespace(forward=eng.forward, adjoint=eng.adjoint, _engine=eng, _P=P, field_info=info)
 
 
 def denoiseImage_PnP_ADMM(A, net, onnx_dagnetwork=True, residual_noise=False):
