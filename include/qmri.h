@@ -182,7 +182,8 @@ int qmri_adjoint_w_mc(qmri_ctx* ctx, const void* y_mc, void* x);           /* su
  * Refusals, decided on the host before the device is selected: ctx == NULL, t_s == NULL with a map, a non-finite f or t, nseg outside 0..16, nbins
  * outside {0, 16..1024}, tol negative or non-finite, reserved != 0, nseg = 1 with a non-constant map: QMRI_ERR_INVALID_ARG; no operator:
  * QMRI_ERR_STATE; a gridded operator: QMRI_ERR_UNSUPPORTED.  While a map is attached qmri_nufft_prepare_normal, qmri_normal(_dev) and
- * QMRI_SOLVER_TOEPLITZ return QMRI_ERR_UNSUPPORTED (A^H A is then L^2 Toeplitz terms, which are not built): use QMRI_SOLVER_LSQR. */
+ * QMRI_SOLVER_TOEPLITZ return QMRI_ERR_UNSUPPORTED unless qmri_nufft_prepare_normal_fm (below) has built the field-aware transform for that map:
+ * use QMRI_SOLVER_LSQR, or that call. */
 typedef struct { int32_t nseg;    /* 1..16; 0 = auto */
                  int32_t nbins;   /* histogram bins, 16..1024; 0 = 256 */
                  double  tol;     /* auto: smallest L whose fit_max <= tol; 0 = 1e-4 */
@@ -191,6 +192,41 @@ typedef struct { int32_t nseg; int32_t tol_reached;
                  double fit_max, fit_rms, f_min, f_max, t_min, t_max;
                  int32_t reserved[4]; } qmri_offres_info;
 int qmri_set_field_map(qmri_ctx* ctx, const double* f_hz, const double* t_s, const qmri_offres_params* p, qmri_offres_info* info);
+/* The Toeplitz normal operator of a trajectory operator WITH a field map (an EXTENSION).  Segmenting the DIFFERENCE phase
+ * (Fessler, Lee, Olafsson, Shi & Noll, IEEE Trans. Signal Process. 2005) needs L' terms, not L^2:
+ *   (A_f^H A_f)_{c,c'}[n, n'] = (1/NM) sum_i V(t_i,c) V(t_i,c') exp(i omega_i . (n - n')) exp(i 2 pi (f[n] - f[n']) tau_i)
+ *   exp(i 2 pi g tau) ~ sum_{l<L'} c_l(tau) exp(i 2 pi g tau^_l),  g = f[n] - f[n'] in [-(f_max - f_min), f_max - f_min],   so that
+ *   A_f^H A_f ~ sum_{l<L'} P_l^H T_l P_l,   P_l = diag(exp(-i 2 pi (f - f0) tau^_l)),
+ * T_l the block-Toeplitz operator of qmri_nufft_prepare_normal built with the sample weights c_l(tau_i).  f0, f_min, f_max, t_min, t_max, nbins and
+ * the histogram (p_h, f_h) are those of the attached map (kept on the host at attach time).  The difference histogram is p~_j = sum_h p_h p_{h-j}
+ * over 2 nbins - 1 bins at g_j = j (f_max - f_min) / nbins; tau^_l = t_min + l (t_max - t_min) / (L' - 1); c(tau_i) solves the REAL system
+ *   (R + eps I) c = rho(tau_i),  R_ll' = sum_j p~_j cos 2 pi g_j (tau^_l - tau^_l'),  rho_l(tau) = sum_j p~_j cos 2 pi g_j (tau - tau^_l),  eps = 1e-12 tr(R) / L'
+ * (p~ is symmetric in g, so the coefficients are real and every T_l is Hermitian).  The system is solved as the least-squares
+ * problem it is the normal equations of: B = [sqrt(p~_j) cos 2 pi g_j tau^_l; sqrt(p~_j) sin 2 pi g_j tau^_l; sqrt(eps) I] = Q U is factored on the host
+ * in fp64 (U is the Cholesky factor of R + eps I, transposed, but formed at B's condition, which is the square root of R's), and c = U^-1 Q^T b(tau_i);
+ * Q^T b, the back substitution and the fit run on the device in a fixed order.  fit_max is the maximum of |exp(i 2 pi g_j tau_i) - sum_l c_l exp(i 2 pi g_j
+ * tau^_l)| over occupied difference bins x samples, fit_rms its p~-weighted rms.  nseg = 0 (auto) tries L' = 2 .. 32 by the fit alone and builds the
+ * transform once, for the first L' whose fit_max <= tol, else for 32 with tol_reached = 0.  Expect L' ~ 2 L - 1 for the accuracy of an L-segment
+ * operator: the range of g is twice that of f.  A constant map is the plain normal operator: nseg = 1, fit_max = 0 whatever nseg asks for, the plain
+ * transform built or reused.  The transform is [L'][s (s + 1) / 2][4 N M] complex doubles on the device (khat_bytes), plus L' N M phase-map entries
+ * and a max_batch image buffer; an allocation failure returns QMRI_ERR_NOMEM and leaves the context as it was before the call.
+ * OPT-IN: without this call for the map in force qmri_nufft_prepare_normal, qmri_normal(_dev) and QMRI_SOLVER_TOEPLITZ refuse as described above.
+ * After it they run the field-aware normal operator (the one-slice qmri_xupdate, both PnP-ADMM loops, every coil chunk); qmri_nufft_prepare_normal
+ * returns QMRI_OK and builds nothing; a slice's bits are the same alone, at any batch position and at any max_batch, and out may be x.
+ * qmri_set_field_map (a new map or NULL) and replacing the operator drop the transform; calling again with other parameters rebuilds it.  The plain
+ * transform of qmri_nufft_prepare_normal is a separate buffer that is never touched: built before the map, it serves again, with the same bits, once
+ * the map is cleared, and it is never used with a (non-constant) map.
+ * Refusals, decided on the host before the device is selected: ctx == NULL, nseg outside {0, 2..32}, tol negative or non-finite, reserved != 0:
+ * QMRI_ERR_INVALID_ARG; no operator, or a trajectory operator without a map (attach one with qmri_set_field_map; without a map the plain
+ * qmri_nufft_prepare_normal is the call): QMRI_ERR_STATE; a gridded operator: QMRI_ERR_UNSUPPORTED.  p == NULL: the defaults; info nullable. */
+typedef struct { int32_t nseg;   /* 2..32; 0 = auto */
+                 double  tol;    /* auto: smallest L' whose fit_max <= tol; 0 = 1e-4 */
+                 int32_t reserved[4]; } qmri_offres_normal_params;     /* zeros / NULL = defaults */
+typedef struct { int32_t nseg; int32_t tol_reached;
+                 double fit_max, fit_rms;
+                 uint64_t khat_bytes;
+                 int32_t reserved[4]; } qmri_offres_normal_info;
+int qmri_nufft_prepare_normal_fm(qmri_ctx* ctx, const qmri_offres_normal_params* p, qmri_offres_normal_info* info);
 /* On a trajectory operator these work unchanged: qmri_forward / _adjoint (and _f32, _dev), qmri_operator_m, qmri_set_coils, qmri_forward_mc /
  * _adjoint_mc, qmri_xupdate_mc(_batch), qmri_pnp_admm_mc(_batch, _dev), qmri_coil_compress*, and qmri_xupdate / qmri_pnp_admm (one slice, LSQR,
  * no diagnostics) as the image-domain LSQR with one unit coil -- bit for bit the qmri_*_mc call with that coil.  Everything else that needs the

@@ -18,7 +18,7 @@ CSRC = os.path.join(_PKG, "csrc")
 SYMBOLS = [
     "qmri_abi_version", "qmri_create", "qmri_destroy", "qmri_last_error", "qmri_set_stream", "qmri_synchronize",
     "qmri_build_spiral", "qmri_build_epi", "qmri_build_spiral_traj", "qmri_set_operator", "qmri_set_operator_nufft", "qmri_nufft_prepare_normal", "qmri_normal", "qmri_normal_dev",
-    "qmri_nufft_dcf", "qmri_set_sample_weights", "qmri_adjoint_w", "qmri_adjoint_w_dev", "qmri_adjoint_w_mc", "qmri_set_field_map", "qmri_operator_m", "qmri_forward", "qmri_adjoint",
+    "qmri_nufft_dcf", "qmri_set_sample_weights", "qmri_adjoint_w", "qmri_adjoint_w_dev", "qmri_adjoint_w_mc", "qmri_set_field_map", "qmri_nufft_prepare_normal_fm", "qmri_operator_m", "qmri_forward", "qmri_adjoint",
     "qmri_forward_f32", "qmri_adjoint_f32", "qmri_forward_dev", "qmri_adjoint_dev", "qmri_set_coils", "qmri_forward_mc", "qmri_adjoint_mc", "qmri_xupdate_mc", "qmri_pnp_admm_mc", "qmri_xupdate_mc_batch", "qmri_pnp_admm_mc_batch", "qmri_pnp_admm_mc_dev", "qmri_xupdate", "qmri_net_nparams", "qmri_set_denoiser", "qmri_denoise",
     "qmri_net_forward_dev", "qmri_denoiser_scheme", "qmri_pnp_admm", "qmri_pnp_admm_dev", "qmri_pnp_admm_batch", "qmri_set_dictionary", "qmri_dict_match",
     "qmri_dict_match_dev", "qmri_dict_match_xfit", "qmri_dict_match_xfit_dev", "qmri_set_dictionary_groups", "qmri_dict_group_assign", "qmri_dict_match_grouped",
@@ -92,6 +92,15 @@ class OffresParams(C.Structure):
 class OffresInfo(C.Structure):
     _fields_ = [("nseg", C.c_int32), ("tol_reached", C.c_int32), ("fit_max", C.c_double), ("fit_rms", C.c_double), ("f_min", C.c_double),
                 ("f_max", C.c_double), ("t_min", C.c_double), ("t_max", C.c_double), ("reserved", C.c_int32 * 4)]
+
+
+class OffresNormalParams(C.Structure):
+    _fields_ = [("nseg", C.c_int32), ("tol", C.c_double), ("reserved", C.c_int32 * 4)]
+
+
+class OffresNormalInfo(C.Structure):
+    _fields_ = [("nseg", C.c_int32), ("tol_reached", C.c_int32), ("fit_max", C.c_double), ("fit_rms", C.c_double), ("khat_bytes", C.c_uint64),
+                ("reserved", C.c_int32 * 4)]
 
 
 class LrtvParams(C.Structure):
@@ -169,6 +178,7 @@ def lib() -> C.CDLL:
     L.qmri_adjoint_w_dev.argtypes = [vp, vp, vp, i]
     L.qmri_adjoint_w_mc.argtypes = [vp, vp, vp]
     L.qmri_set_field_map.argtypes = [vp, dp, dp, C.POINTER(OffresParams), C.POINTER(OffresInfo)]
+    L.qmri_nufft_prepare_normal_fm.argtypes = [vp, C.POINTER(OffresNormalParams), C.POINTER(OffresNormalInfo)]
     L.qmri_operator_m.argtypes = [vp, C.POINTER(i)]
     L.qmri_forward.argtypes = [vp, vp, i, vp]
     L.qmri_adjoint.argtypes = [vp, vp, vp]

@@ -63,7 +63,7 @@ inline int wrap(int k, int G) { k %= G; return k < 0 ? k + G : k; }
 }  // namespace
 
 void nufft_free(NufftHost& h) {
-    void* ptrs[] = {h.d_u, h.d_ph, h.d_t, h.d_perm, h.d_list, h.d_seg, h.d_red, h.d_dp, h.d_r, h.d_g, h.d_grid, h.d_part, h.d_ones, h.d_khat, h.d_w, h.d_pm, h.d_bl};
+    void* ptrs[] = {h.d_u, h.d_ph, h.d_t, h.d_perm, h.d_list, h.d_seg, h.d_red, h.d_dp, h.d_r, h.d_g, h.d_grid, h.d_part, h.d_ones, h.d_khat, h.d_w, h.d_pm, h.d_bl, h.d_khat_fm, h.d_pm_n, h.d_xs};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     h = NufftHost();
 }

@@ -20,7 +20,7 @@ extern "C" int qmri_nufft_prepare_normal(qmri_ctx* ctx) {
     QMRI_TRY(require_trajectory(ctx, "qmri_nufft_prepare_normal", "there is no Toeplitz normal operator to build"));
     QMRI_TRY(offres_refuse_toeplitz(ctx, "qmri_nufft_prepare_normal"));
     QMRI_HIP(ctx, hipSetDevice(ctx->device));
-    return toep_prepare(ctx);
+    return toep_prepare(ctx);           // (with a field map and its own transform in force this builds nothing)
 }
 
 extern "C" int qmri_normal_dev(qmri_ctx* ctx, const void* d_x, void* d_out, int batch) {
@@ -53,7 +53,7 @@ extern "C" int qmri_normal(qmri_ctx* ctx, const void* x, int x_is_complex, void*
 int toep_check_solver(qmri_ctx* ctx, int solver) {
     if (solver != QMRI_SOLVER_TOEPLITZ) return QMRI_OK;
     if (!ctx->op.ready) { qmri_set_error(ctx, "operator not set: call qmri_set_operator first"); return QMRI_ERR_STATE; }
-    if (ctx->op.kind == OP_NUFFT) return offres_refuse_toeplitz(ctx, "QMRI_SOLVER_TOEPLITZ");      // (a field map: the Toeplitz form is not built)
+    if (ctx->op.kind == OP_NUFFT) return offres_refuse_toeplitz(ctx, "QMRI_SOLVER_TOEPLITZ");      // (a field map whose normal operator is not prepared)
     qmri_set_error(ctx, "QMRI_SOLVER_TOEPLITZ needs a trajectory operator (qmri_set_operator_nufft): on a gridded operator A^H A is already diagonal "
                         "per k-space location; use QMRI_SOLVER_LSQR (the k-space LSQR)");
     return QMRI_ERR_UNSUPPORTED;

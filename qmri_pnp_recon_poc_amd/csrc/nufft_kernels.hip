@@ -318,6 +318,27 @@ int nufft_launch_unramps(qmri_ctx* ctx, int B, const double2* g, double2* x) {
     return QMRI_OK;
 }
 
+// ... with a phase plane pm [N*M] of the field-aware normal operator: x .* pm on the way in, conj(pm) on the way out, added
+// to x when acc
+int nufft_launch_ramps_pm(qmri_ctx* ctx, int B, const double2* x, double2* g, const double2* pm) {
+    const OpHost& o = ctx->op;
+    const size_t n = (size_t)o.N * o.M * o.s;
+    NufftDev nu = nufft_dev(ctx);
+    nu.pm = pm;
+    k_nu_pre<false, true><<<dim3((unsigned)((n + NT - 1) / NT), B), dim3(NT), 0, ctx->stream>>>(nu, x, g);
+    QMRI_HIP(ctx, hipGetLastError());
+    return QMRI_OK;
+}
+int nufft_launch_unramps_pm(qmri_ctx* ctx, int B, const double2* g, double2* x, const double2* pm, bool acc) {
+    const OpHost& o = ctx->op;
+    const size_t n = (size_t)o.N * o.M * o.s;
+    NufftDev nu = nufft_dev(ctx);
+    nu.pm = pm; nu.acc = acc ? 1 : 0;
+    k_nu_post<false, true><<<dim3((unsigned)((n + NT - 1) / NT), B), dim3(NT), 0, ctx->stream>>>(nu, g, x);
+    QMRI_HIP(ctx, hipGetLastError());
+    return QMRI_OK;
+}
+
 int nufft_launch_fwd(qmri_ctx* ctx, int B, const double2* x, double2* y) {
     OpHost& o = ctx->op;
     if (o.kind != OP_NUFFT || B < 1 || B > o.maxB) { qmri_set_error(ctx, "nufft_launch_fwd: no trajectory operator / batch out of range (internal)"); return QMRI_ERR_STATE; }
@@ -347,14 +368,15 @@ int nufft_launch_fwd(qmri_ctx* ctx, int B, const double2* x, double2* y) {
     return launch_interp(ctx, nu, B, o.nu.d_grid, y);
 }
 
-static int launch_adj(qmri_ctx* ctx, int B, const double2* y, double2* x, bool weighted) {
+// plain: the uncorrected transform even while a field map is attached (the Toeplitz set-ups build point-spread functions of the trajectory alone)
+static int launch_adj(qmri_ctx* ctx, int B, const double2* y, double2* x, bool weighted, bool plain) {
     OpHost& o = ctx->op;
     if (o.kind != OP_NUFFT || B < 1 || B > o.maxB) { qmri_set_error(ctx, "nufft_launch_adj: no trajectory operator / batch out of range (internal)"); return QMRI_ERR_STATE; }
     const NufftDev nu = nufft_dev(ctx);
     if (weighted && !nu.wgt) { qmri_set_error(ctx, "nufft_launch_adj_w: no sample weights attached (internal)"); return QMRI_ERR_STATE; }
     const OpDev op = qmri_opdev(ctx);
     const size_t n = (size_t)o.N * o.M * o.s;
-    if (o.nu.fm_set) {
+    if (o.nu.fm_set && !plain) {
         // x = sum_l conj(P_l) .* NUFFT^H(conj(b_l) .* (w .*) y) in segment order: the exact transpose of the forward's segments
         for (int l = 0; l < o.nu.fm_L; ++l) {
             const NufftDev nl = nufft_dev_seg(ctx, l);
@@ -386,5 +408,6 @@ static int launch_adj(qmri_ctx* ctx, int B, const double2* y, double2* x, bool w
     return QMRI_OK;
 }
 
-int nufft_launch_adj(qmri_ctx* ctx, int B, const double2* y, double2* x) { return launch_adj(ctx, B, y, x, false); }
-int nufft_launch_adj_w(qmri_ctx* ctx, int B, const double2* y, double2* x) { return launch_adj(ctx, B, y, x, true); }
+int nufft_launch_adj(qmri_ctx* ctx, int B, const double2* y, double2* x) { return launch_adj(ctx, B, y, x, false, false); }
+int nufft_launch_adj_w(qmri_ctx* ctx, int B, const double2* y, double2* x) { return launch_adj(ctx, B, y, x, true, false); }
+int nufft_launch_adj_plain(qmri_ctx* ctx, int B, const double2* y, double2* x) { return launch_adj(ctx, B, y, x, false, true); }

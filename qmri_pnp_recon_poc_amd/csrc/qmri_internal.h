@@ -409,6 +409,18 @@ struct NufftHost {
     size_t pm_cap = 0, bl_cap = 0;               // elements allocated
     int fm_L = 0;                                // segments
     bool fm_set = false;
+    // what the attached map's field-aware normal operator is defined by, kept on the host at attach time
+    std::vector<double> fm_f, fm_ts, fm_p;       // the map [N*M], the readout times [m] (ABI order), the histogram p_h [fm_nbins]
+    double fm_f0 = 0.0, fm_fmin = 0.0, fm_fmax = 0.0, fm_tmin = 0.0, fm_tmax = 0.0;
+    int fm_nbins = 0;
+    // field-aware Toeplitz normal operator (qmri_nufft_prepare_normal_fm): A_f^H A_f ~ sum_l P_l^H T_l P_l over fmn_L segments of
+    // the DIFFERENCE phase.  Belongs to the attached map: qmri_set_field_map and replacing the operator drop it.  d_khat above is never touched by it.
+    double2* d_khat_fm = nullptr;                // [fmn_L][pair][a][j1][j2], T_l built with the sample weights c_l(tau_i)
+    double2* d_pm_n = nullptr;                   // [fmn_L][N*M] phase maps at the fmn_L segment times (d_pm is at the operator's own times)
+    double2* d_xs = nullptr;                     // [maxB][n] x kept while the segments add into out (out may be x)
+    int fmn_L = 0;                               // segments; 1 with fmn_plain: a constant map, the plain d_khat serves
+    bool fmn_plain = false;
+    bool fmn_ready = false;
 };
 // the exponential spiral of setup_subsampling_spiralgrided.m:7-27 before rounding (shared by qmri_build_spiral and qmri_build_spiral_traj): S angles
 // theta_j and radii r_j normalised to [0, 1]; frame f is rotated by f * SPIRAL_DELTA
@@ -416,6 +428,7 @@ void spiral_points(int S, std::vector<double>& theta, std::vector<double>& rad);
 constexpr double SPIRAL_DELTA = 3.14159265358979323846 / 180.0 * 7.5;
 int nufft_launch_fwd(qmri_ctx* ctx, int B, const double2* x, double2* y);    // x [B][n] -> y [B][m] (ABI order)
 int nufft_launch_adj(qmri_ctx* ctx, int B, const double2* y, double2* x);    // y [B][m] -> x [B][n]
+int nufft_launch_adj_plain(qmri_ctx* ctx, int B, const double2* y, double2* x);  // ... uncorrected even while a field map is attached (the Toeplitz set-ups)
 int nufft_launch_adj_w(qmri_ctx* ctx, int B, const double2* y, double2* x);  // ... of w .* y, w the attached sample weights (multiplied where k_nu_spread stages y)
 // Pipe-Menon density compensation on the plan's own kernel and spreading lists (dcf_kernels.hip, api_dcf.cpp): niter
 // iterations (1..200) from w = 1, stopped early once max |d - 1| <= tol (tol <= 0: never), then d_w_out [m] (ABI order) = kappa * w.  Uses the plan's
@@ -429,17 +442,30 @@ int offres_phase_maps_dev(qmri_ctx* ctx, int L, size_t plane, const double* d_f,
 // y: f_h) and its table d_G [nbins][L]; exact = a constant map (b = 1).  Fills *fit (device reductions in a fixed order) and waits for its kernels.
 int offres_coefficients_dev(qmri_ctx* ctx, int L, int nbins, bool exact, const double2* d_hist, const double2* d_G, const double2* d_chol,
                             const double* d_ts, double f0, double2* d_bl, OffresFit* fit);
-// QMRI_ERR_UNSUPPORTED with a message naming LSQR while a field map is attached, else QMRI_OK (host check only)
+// QMRI_ERR_UNSUPPORTED with a message naming LSQR while a field map is attached and qmri_nufft_prepare_normal_fm has not built the field-aware
+// transform for it, else QMRI_OK (host check only)
 int offres_refuse_toeplitz(qmri_ctx* ctx, const char* what);
+// the real coefficients c [L][m] (sorted order) of the difference-phase segmentation (k_offres_ncoef) from the thin QR B = Q U of
+// the stacked table [sqrt(p~) cos; sqrt(p~) sin; sqrt(eps) I]: d_Qw [nb][L] (x / y: sqrt(p~_j) times Q's cos / sin row of bin j), d_U [L][L] (upper,
+// row-major), the difference histogram d_dh [nb] (x: p~_j, y: g_j) and its table d_G [nb][L] = exp(i 2 pi g_j tauhat_l).  Fills *fit (device
+// reductions in a fixed order) and waits for its kernels.
+int offres_ncoefficients_dev(qmri_ctx* ctx, int L, int nb, const double2* d_dh, const double2* d_G, const double2* d_Qw, const double* d_U,
+                             const double* d_ts, double* d_c, OffresFit* fit);
+void offres_drop_normal(NufftHost& h);             // forgets the field-aware transform and frees its device buffers (K^, phase maps, staging)
 int nufft_check_gridded(qmri_ctx* ctx, const char* what, const char* instead);   // QMRI_ERR_UNSUPPORTED on a trajectory operator, else QMRI_OK
 void nufft_free(NufftHost& h);
 bool nufft_kernel_ok(int w);
 NufftDev nufft_dev_view(const qmri_ctx* ctx);
 int nufft_launch_ramps(qmri_ctx* ctx, int B, const double2* x, double2* g);      // k_nu_pre without 1 / Phi:  x [B][n] -> g [B][4][n]
 int nufft_launch_unramps(qmri_ctx* ctx, int B, const double2* g, double2* x);    // k_nu_post without 1 / Phi
+int nufft_launch_ramps_pm(qmri_ctx* ctx, int B, const double2* x, double2* g, const double2* pm);                // ... of x .* pm, pm [N*M]
+int nufft_launch_unramps_pm(qmri_ctx* ctx, int B, const double2* g, double2* x, const double2* pm, bool acc);    // ... times conj(pm); acc: x += 
 // Toeplitz normal operator of a trajectory (toep_kernels.hip, api_toep.cpp)
 int toep_prepare(qmri_ctx* ctx);                                                  // builds K^ once per trajectory (idempotent)
-int toep_apply(qmri_ctx* ctx, int B, const double2* x, double2* out);             // out [B][n] = A^H A x [B][n], B <= max_batch; out may be x
+// K^ of segment l of the field-aware normal into khat [pair][a][j1][j2]: the pipeline of toep_prepare with the per-sample real weights d_c [m] (sorted)
+int toep_build_weighted(qmri_ctx* ctx, const double* d_c, double2* khat);
+// out [B][n] = A^H A x [B][n], B <= max_batch; out may be x.  With a field map attached (and its transform prepared): the segment loop of section 23
+int toep_apply(qmri_ctx* ctx, int B, const double2* x, double2* out);
 int qmri_cg_toep_batch_dev(qmri_ctx* ctx, int B, int ncoil, const double2* d_maps, const double2* d_y, const double2* d_z, double r, double tol, int maxit,
                            double2* d_x, int32_t* iters_out, int32_t* flags_out);  // the call shape of qmri_lsqr_mc_batch_dev
 // the x-update of the multi-coil loops by the solver of qmri_admm_params (LSQR or TOEPLITZ)

@@ -13,6 +13,10 @@
 // and the dense inverse h-pass, the conjugate ramps of k_nu_post without 1 / Phi (nufft_launch_unramps).  No gather, no floating-point atomics;
 // every image of a batch goes through the same instructions in the same order, so a slice's bits do not depend on the batch.
 //
+// With a field map attached and qmri_nufft_prepare_normal_fm called for it toep_apply runs A_f^H A_f ~ sum_l P_l^H T_l P_l: per
+// segment l of the difference phase the same chain on that segment's K^ (built by toep_build_weighted with the real sample weights c_l(tau_i)), the
+// ramps as their OFFRES instantiations (x times the phase plane P_l on the way in, conj(P_l) on the way out, adding for l > 0).
+//
 // Solver (qmri_cg_toep_batch_dev, QMRI_SOLVER_TOEPLITZ): conjugate gradients on (A_mc^H A_mc + r I) x = A_mc^H y + r z with
 // A_mc^H A_mc x = sum_j conj(C_j) . T (C_j . x), the discipline of the multi-coil LSQR (mc_kernels.hip): scalars on the device, norms from PS fixed
 // partials per slice added in one order, per-slice stopping, one event wait per chunk of iterations.
@@ -28,13 +32,16 @@ constexpr int PS = 256;          // partial sums per slice vector
 __device__ __forceinline__ int toep_pair(int c, int cp) { return cp * (cp + 1) / 2 + c; }      // c <= cp
 
 // y[perm[e]] = V(t_e, cp) exp(-i pi (b1 u1 + b2 u2)):  omega . off with off = (-b1 N, -b2 M) and u = omega (N, M) / pi
-__global__ __launch_bounds__(NT) void k_toep_synth(NufftDev nu, int cp, int b1, int b2, double2* __restrict__ y) {
+// WEIGHTED: times the real weight cw[e] (sorted order) -- segment l of the field-aware normal operator, cw = c_l(tau)
+template <bool WEIGHTED>
+__global__ __launch_bounds__(NT) void k_toep_synth(NufftDev nu, int cp, int b1, int b2, const double* __restrict__ cw, double2* __restrict__ y) {
     const int e = blockIdx.x * NT + threadIdx.x;
     if (e >= nu.m) return;
     const double2 u = nu.u[e];
     double sn, cs;
     sincospi(-((double)b1 * u.x + (double)b2 * u.y), &sn, &cs);
-    const double v = nu.Vt[(size_t)nu.t[e] * nu.s + cp];
+    double v = nu.Vt[(size_t)nu.t[e] * nu.s + cp];
+    if (WEIGHTED) v *= cw[e];
     y[nu.perm[e]] = make_double2(v * cs, v * sn);
 }
 
@@ -300,13 +307,13 @@ int tcg_normal_chunks(qmri_ctx* ctx, int B, int ncoil, const double2* maps, cons
 }
 }  // namespace
 
-int toep_prepare(qmri_ctx* ctx) {
+// K^ of one Toeplitz operator into khat [pair][a][j1][j2]; d_c == nullptr: the plain one, else the samples weighted by d_c [m] (sorted order).  The
+// adjoint NUFFTs are the PLAIN transform whether or not a field map is attached: the point-spread function is the trajectory's.
+int toep_build_weighted(qmri_ctx* ctx, const double* d_c, double2* khat) {
     OpHost& o = ctx->op;
     NufftHost& h = o.nu;
     if (o.kind != OP_NUFFT) { qmri_set_error(ctx, "toep_prepare: no trajectory operator (internal)"); return QMRI_ERR_STATE; }
-    if (h.khat_ready) return QMRI_OK;
-    const size_t plane = (size_t)o.N * o.M, n = plane * o.s, npair = (size_t)o.s * (o.s + 1) / 2;
-    if (!h.d_khat) QMRI_TRY(dev_alloc(ctx, &h.d_khat, npair * 4 * plane));
+    const size_t plane = (size_t)o.N * o.M, n = plane * o.s;
     DevBuf<double2> Q, y;
     QMRI_TRY(dev_alloc(ctx, &Q.p, 4 * n));
     QMRI_TRY(dev_alloc(ctx, &y.p, (size_t)o.m));
@@ -314,37 +321,74 @@ int toep_prepare(qmri_ctx* ctx) {
     const OpDev op = qmri_opdev(ctx);
     for (int cp = 0; cp < o.s; ++cp) {
         for (int b = 0; b < 4; ++b) {
-            k_toep_synth<<<dim3((o.m + NT - 1) / NT), dim3(NT), 0, ctx->stream>>>(nu, cp, b & 1, b >> 1, y);
+            if (d_c) k_toep_synth<true><<<dim3((o.m + NT - 1) / NT), dim3(NT), 0, ctx->stream>>>(nu, cp, b & 1, b >> 1, d_c, y);
+            else k_toep_synth<false><<<dim3((o.m + NT - 1) / NT), dim3(NT), 0, ctx->stream>>>(nu, cp, b & 1, b >> 1, nullptr, y);
             QMRI_HIP(ctx, hipGetLastError());
-            QMRI_TRY(nufft_launch_adj(ctx, 1, y, Q + (size_t)b * n));
+            QMRI_TRY(nufft_launch_adj_plain(ctx, 1, y, Q + (size_t)b * n));
         }
         k_toep_combine<<<dim3((unsigned)((n + NT - 1) / NT)), dim3(NT), 0, ctx->stream>>>(nu, Q, h.d_g);
         QMRI_HIP(ctx, hipGetLastError());
         // the four sub-grids as four slices through the dense spectrum passes (unitary: 1 / sqrt(NM), which the adjoint's own 1 / sqrt(NM) left over)
         QMRI_TRY(dc_launch_fwd(ctx, op, o.ls, DC_SPECTRUM, 4, h.d_g, h.d_grid, h.d_g, nullptr));
-        k_toep_pack<<<dim3((unsigned)((4 * plane + NT - 1) / NT), cp + 1), dim3(NT), 0, ctx->stream>>>(o.s, plane, cp, h.d_g, h.d_khat);
+        k_toep_pack<<<dim3((unsigned)((4 * plane + NT - 1) / NT), cp + 1), dim3(NT), 0, ctx->stream>>>(o.s, plane, cp, h.d_g, khat);
         QMRI_HIP(ctx, hipGetLastError());
     }
     QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));           // (Q and y are released on return)
+    return QMRI_OK;
+}
+
+int toep_prepare(qmri_ctx* ctx) {
+    OpHost& o = ctx->op;
+    NufftHost& h = o.nu;
+    if (o.kind != OP_NUFFT) { qmri_set_error(ctx, "toep_prepare: no trajectory operator (internal)"); return QMRI_ERR_STATE; }
+    if (h.fm_set && h.fmn_ready && !h.fmn_plain) return QMRI_OK;      // the field-aware transform is the one in force: the plain one is not needed
+    if (h.khat_ready) return QMRI_OK;
+    const size_t plane = (size_t)o.N * o.M, npair = (size_t)o.s * (o.s + 1) / 2;
+    if (!h.d_khat) QMRI_TRY(dev_alloc(ctx, &h.d_khat, npair * 4 * plane));
+    QMRI_TRY(toep_build_weighted(ctx, nullptr, h.d_khat));
     h.khat_ready = true;
     return QMRI_OK;
 }
 
-int toep_apply(qmri_ctx* ctx, int B, const double2* x, double2* out) {
+// the passes between the ramps: d_g [B][4][n] -> spectra, times khat, back to the sub-grid images in d_g
+static int toep_core(qmri_ctx* ctx, const OpDev& op, int B, const double2* khat) {
     OpHost& o = ctx->op;
-    if (o.kind != OP_NUFFT || B < 1 || B > o.maxB) { qmri_set_error(ctx, "toep_apply: no trajectory operator / batch out of range (internal)"); return QMRI_ERR_STATE; }
-    QMRI_TRY(toep_prepare(ctx));
-    const OpDev op = qmri_opdev(ctx);
     const size_t plane = (size_t)o.N * o.M;
     const unsigned gm = (unsigned)((4 * plane + NT - 1) / NT);
-    QMRI_TRY(nufft_launch_ramps(ctx, B, x, o.nu.d_g));
     QMRI_TRY(dc_launch_fwd(ctx, op, o.ls, DC_SPECTRUM, 4 * B, o.nu.d_g, o.nu.d_grid, o.nu.d_g, nullptr));
-    if (B == 1) k_toep_mul<1><<<dim3(gm), dim3(NT), 0, ctx->stream>>>(o.s, plane, B, o.nu.d_khat, o.nu.d_g);
-    else k_toep_mul<2><<<dim3(gm), dim3(NT), 0, ctx->stream>>>(o.s, plane, B, o.nu.d_khat, o.nu.d_g);
+    if (B == 1) k_toep_mul<1><<<dim3(gm), dim3(NT), 0, ctx->stream>>>(o.s, plane, B, khat, o.nu.d_g);
+    else k_toep_mul<2><<<dim3(gm), dim3(NT), 0, ctx->stream>>>(o.s, plane, B, khat, o.nu.d_g);
     QMRI_HIP(ctx, hipGetLastError());
     QMRI_TRY(with_plan(ctx, op.M, [&](auto p) { return launch_toep_adj_w_t<decltype(p)::R1, decltype(p)::R2>(ctx, op, 4 * B, o.nu.d_g, o.nu.d_grid); }));
-    QMRI_TRY(dc_launch_adj_h(ctx, op, 4 * B, o.nu.d_grid, o.nu.d_g));
-    return nufft_launch_unramps(ctx, B, o.nu.d_g, out);
+    return dc_launch_adj_h(ctx, op, 4 * B, o.nu.d_grid, o.nu.d_g);
+}
+
+int toep_apply(qmri_ctx* ctx, int B, const double2* x, double2* out) {
+    OpHost& o = ctx->op;
+    NufftHost& h = o.nu;
+    if (o.kind != OP_NUFFT || B < 1 || B > o.maxB) { qmri_set_error(ctx, "toep_apply: no trajectory operator / batch out of range (internal)"); return QMRI_ERR_STATE; }
+    if (h.fm_set && !h.fmn_ready) { qmri_set_error(ctx, "toep_apply: a field map without its normal operator (internal)"); return QMRI_ERR_STATE; }
+    const OpDev op = qmri_opdev(ctx);
+    if (h.fm_set && !h.fmn_plain) {
+        // A_f^H A_f x ~ sum_l conj(P_l) .* T_l (P_l .* x), segments one after the other on the stream; every output element is owned by one thread
+        // of k_nu_post, which stores for l = 0 and adds for l > 0.  out == x: the later segments read the copy of x made here.
+        const size_t plane = (size_t)o.N * o.M, n = plane * o.s, kseg = (size_t)o.s * (o.s + 1) / 2 * 4 * plane;
+        if (x == out && h.fmn_L > 1) {
+            QMRI_HIP(ctx, hipMemcpyAsync(h.d_xs, x, (size_t)B * n * sizeof(double2), hipMemcpyDeviceToDevice, ctx->stream));
+            x = h.d_xs;
+        }
+        for (int l = 0; l < h.fmn_L; ++l) {
+            const double2* pm = h.d_pm_n + (size_t)l * plane;
+            QMRI_TRY(nufft_launch_ramps_pm(ctx, B, x, h.d_g, pm));
+            QMRI_TRY(toep_core(ctx, op, B, h.d_khat_fm + (size_t)l * kseg));
+            QMRI_TRY(nufft_launch_unramps_pm(ctx, B, h.d_g, out, pm, l > 0));
+        }
+        return QMRI_OK;
+    }
+    QMRI_TRY(toep_prepare(ctx));
+    QMRI_TRY(nufft_launch_ramps(ctx, B, x, h.d_g));
+    QMRI_TRY(toep_core(ctx, op, B, h.d_khat));
+    return nufft_launch_unramps(ctx, B, h.d_g, out);
 }
 
 // CG on (A_mc^H A_mc + r I) x = A_mc^H y + r z for B slices from x0 = d_x (device, overwritten with the solutions); operands as qmri_lsqr_mc_batch_dev.

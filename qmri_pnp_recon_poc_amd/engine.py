@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import AdmmParams, CcParams, CsmInfo, CsmParams, DcfInfo, DcfParams, DsvdInfo, DsvdParams, EpgParams, LrtvInfo, LrtvParams, NetDesc, NufftParams, OffresInfo, OffresParams, Profile
+from ._lib import AdmmParams, CcParams, CsmInfo, CsmParams, DcfInfo, DcfParams, DsvdInfo, DsvdParams, EpgParams, LrtvInfo, LrtvParams, NetDesc, NufftParams, OffresInfo, OffresNormalInfo, OffresNormalParams, OffresParams, Profile
 
 ARCH_UNETRES, ARCH_SEQ_CONV = 0, 1
 SOLVER_LSQR, SOLVER_DIRECT = 0, 1
@@ -346,7 +346,7 @@ class Engine:
         seconds, the order of y (spiral_readout_times makes them for the project's spiral).  The operator then carries exp(-i 2 pi f[n] t_i), by time
         segmentation with nseg segments (1..16; 0: the smallest whose fit_max <= tol, tol 0: 1e-4) fitted over an nbins-bin histogram (16..1024; 0:
         256).  forward / adjoint / the _mc methods / xupdate / pnp_admm all run the corrected operator; normal, prepare_normal and solver="toeplitz"
-        are refused while a map is attached.  None clears the map.  One map per operator (every coil, every slice).
+        are refused while a map is attached, until prepare_normal_field builds the field-aware normal operator for it.  None clears the map.  One map per operator (every coil, every slice).
         Returns dict(nseg, tol_reached, fit_max, fit_rms, f_min, f_max, t_min, t_max), or None after clearing."""
         if f_hz is None:
             self._check(self.L.qmri_set_field_map(self.h, None, None, None, None))
@@ -376,6 +376,21 @@ class Engine:
         self._check(self.L.qmri_set_field_map(self.h, fb.ctypes.data_as(dp), tb.ctypes.data_as(dp), C.byref(p), C.byref(info)))
         return {"nseg": int(info.nseg), "tol_reached": int(info.tol_reached), "fit_max": float(info.fit_max), "fit_rms": float(info.fit_rms),
                 "f_min": float(info.f_min), "f_max": float(info.f_max), "t_min": float(info.t_min), "t_max": float(info.t_max)}
+
+    def prepare_normal_field(self, nseg=0, tol=0.0):
+        """Build the Toeplitz normal operator of the trajectory operator WITH its attached field map (qmri_nufft_prepare_normal_fm; DESIGN.md section
+        23): A_f^H A_f ~ sum over nseg segments of the difference phase (2..32; 0: the smallest whose fit_max <= tol, tol 0: 1e-4).  After it normal,
+        xupdate(..., solver="toeplitz") and the pnp_admm* methods with that solver run the field-aware normal operator; set_field_map (a new map or
+        None) drops it.  A constant map reports nseg = 1 and is the plain normal operator.
+        Returns dict(nseg, tol_reached, fit_max, fit_rms, khat_bytes)."""
+        if int(nseg) != nseg or not (int(nseg) == 0 or 2 <= int(nseg) <= 32):
+            raise ValueError("nseg must be an integer in 2..32 (0: automatic)")
+        if not (np.isfinite(tol) and tol >= 0):
+            raise ValueError("tol must be finite and >= 0")
+        p, info = OffresNormalParams(int(nseg), float(tol)), OffresNormalInfo()
+        self._check(self.L.qmri_nufft_prepare_normal_fm(self.h, C.byref(p), C.byref(info)))
+        return {"nseg": int(info.nseg), "tol_reached": int(info.tol_reached), "fit_max": float(info.fit_max), "fit_rms": float(info.fit_rms),
+                "khat_bytes": int(info.khat_bytes)}
 
     def adjoint(self, y, weighted=False):
         """x = F.adjoint(y)  (main_recon_tsmis_FFT.m:229); complex64 in -> complex64 out (the _f32 entry point).

@@ -279,7 +279,7 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
                 spiral_sampling_curve=771, epi_sampling_rate=1 / 65, measurements_type="noisy", measurements_noise=30,
                 denoiser_type="single_level", noise_map_std=0.01, residual_noise=False, iters=100, seed=0, Y=None, device=0,
                 net_arch=None, lrtv_iters=None, tsmi_domain="real", solver="lsqr", b1_map=None, density_compensation=False,
-                field_map=None, readout_s=None):
+                field_map=None, readout_s=None, field_normal=None):
     """main_recon_tsmis_FFT.m:216-374 on already loaded (and cropped) arrays.
 
     dictionary  dict(V, D, normD, lut) (load_dictionary);  X0  N x M x s ground-truth TSMI;  qmap0  N x M x 3
@@ -296,7 +296,10 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
     field_map, readout_s  with SpiralExact, PnP_ADMM or SVD_MRF: an N x M field map in Hz and the length of one spiral readout in seconds (sample j of a
                 frame is measured at j * readout_s / S): the operator carries the off-resonance phase (time segmentation), for
                 the measurements it simulates (when Y is not given) and for the reconstruction.  Absent: the operator without a map, bit for bit.
-    Returns dict(X, qmap (N x M x 3: T1, T2, PD), Y, metrics, foreground_mask); with b1_map also grp (N x M, the 1-based b1 group, 0 = unmatched).
+    field_normal  with field_map and solver="toeplitz": True, or a dict with nseg / tol, builds the field-aware Toeplitz normal operator before the
+                loop (Engine.prepare_normal_field); None or False (default): solver="toeplitz" with a field_map is refused
+    Returns dict(X, qmap (N x M x 3: T1, T2, PD), Y, metrics, foreground_mask); with b1_map also grp (N x M, the 1-based b1 group, 0 = unmatched);
+    with field_normal also field_normal_info (what prepare_normal_field reported).
     """
     from . import reference_api as R
     net_arch = dict(net_arch or {})
@@ -327,8 +330,13 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
         raise ValueError("field_map and readout_s go together")
     if field_map is not None and subsampling_pattern != "SpiralExact":
         raise ValueError("field_map needs the subsampling pattern SpiralExact (a gridded mask has no readout times)")
-    if field_map is not None and solver == "toeplitz":
+    if field_normal is False:                                                        # (as None: no field-aware normal operator)
+        field_normal = None
+    if field_normal is not None and (field_map is None or solver != "toeplitz" or recon_method != "PnP_ADMM"):
+        raise ValueError('field_normal goes with a field_map, recon_method="PnP_ADMM" and solver="toeplitz"')
+    if field_map is not None and solver == "toeplitz" and field_normal is None:
         raise ValueError('with a field_map the x-update is solver="lsqr": the Toeplitz normal operator of the corrected operator is not built')
+    extra_fn = {}
     F = R.make_F(P, device=device) if field_map is None else R.make_F(P, device=device, field_map=field_map, readout_s=readout_s)
     if density_compensation:
         F._engine.density_weights()                                                  # (make_F planned the operator afresh: nothing was attached)
@@ -360,7 +368,11 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
                  "noise_map": R.build_noise_map(noise_map_std, N, M), "solver": solver}   # :166-171
         if density_compensation:
             param["x0"] = "dcf"
+        if field_normal is not None:
+            param["field_normal"] = field_normal
         X = R.PnP_ADMM(np.asarray(Y, dtype=np.complex128), param)
+        if field_normal is not None:
+            extra_fn = {"field_normal_info": R.PnP_ADMM.last_field_normal}
     elif recon_method == "LRTV":                                                     # :273-282
         param = {"K": 4e-5, "iter": 200 if lrtv_iters is None else int(lrtv_iters), "step": X0.size / np.asarray(Y).size, "tol": 1e-4,
                  "backtrack": 1, "usegpu": 0}
@@ -369,7 +381,7 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
     else:
         raise ValueError(f"unknown reconstruction method {recon_method}")
     par = {"f": {"qout": 1, "pdout": 1, "mtout": 0, "Xout": 0, "dmout": 0, "Yout": 0, "verbose": 0}, "fp": {"blockSize": 1e9}}   # :302-309
-    extra = {}
+    extra = dict(extra_fn)
     if b1_map is not None:
         eng = R._engine(device)
         eng.set_dictionary(dictionary["D"], dictionary["normD"], dictionary["lut"])

@@ -4,7 +4,8 @@ function [x, diag, lsqr_iters] = PnP_ADMM_hip(y, param)
 %   qmri_make_net; the fields read are the reference's own: iter, gamma, cg_tol, gt_tsmi, X0, denoiser_type, noise_map
 %   (PnP_ADMM.m:62-76), and param.tsmi_domain ('real', the default and the reference's; 'complex': the denoiser sees
 %   cat(3, real(x+u), imag(x+u)) and param.net must take 2s (+1) -> 2s channels), and param.solver ('lsqr', the default; 'direct'; 'toeplitz' on a
-%   trajectory F: CG on the Toeplitz normal operator, DESIGN.md section 16).  Extra outputs: the two per-iteration diagnostics (PnP_ADMM.m:106-109) and the LSQR iteration counts.
+%   trajectory F: CG on the Toeplitz normal operator, DESIGN.md section 16), and param.field_normal (with a field map and solver 'toeplitz': true, or a
+%   struct with nseg and / or tol, builds the field-aware normal operator before the loop, as qmri_prepare_normal_fm does).  Extra outputs: the two per-iteration diagnostics (PnP_ADMM.m:106-109) and the LSQR iteration counts.
 %
 %   y is the measurement vector of one slice (m x 1, as in the reference) or a measurement MATRIX m x S, one column per slice:
 %   the S slices then advance together through the batched kernels (15 at a time) on the current device and x is
@@ -25,6 +26,19 @@ if isfield(param, 'solver')                                % 'lsqr' (default, th
         p.solver = k - 1;
     else
         p.solver = double(sv);
+    end
+end
+if isfield(param, 'field_normal') && ~isempty(param.field_normal)  % true, or a struct with nseg / tol: qmri_prepare_normal_fm before the loop
+    fn = param.field_normal;
+    if isstruct(fn)
+        if ~all(ismember(fieldnames(fn), {'nseg', 'tol'})), error('qmri:field_normal', 'param.field_normal must be true or a struct with nseg and / or tol'); end
+        p.field_normal = 1;
+        if isfield(fn, 'nseg'), p.field_normal_nseg = double(fn.nseg); end
+        if isfield(fn, 'tol'), p.field_normal_tol = double(fn.tol); end
+    elseif (islogical(fn) || isnumeric(fn)) && isscalar(fn)
+        p.field_normal = double(fn ~= 0);
+    else
+        error('qmri:field_normal', 'param.field_normal must be true or a struct with nseg and / or tol');
     end
 end
 g = param.F.qmri;

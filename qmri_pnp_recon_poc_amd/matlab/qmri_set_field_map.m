@@ -12,7 +12,8 @@ function info = qmri_set_field_map(f, t, nseg, nbins, tol)
 %   nseg: segments, 1..16 (default 0: the smallest whose fit_max <= tol); nbins: histogram bins of the fit, 16..1024 (default 0 = 256);
 %   tol: for nseg = 0 (default 0 = 1e-4).  info: struct (nseg, tol_reached, fit_max, fit_rms, f_min, f_max, t_min, t_max).
 %   The cost is about nseg times the plain transform.  One map per operator (every coil and slice).  While a map is attached the Toeplitz normal
-%   operator ('normal', solver 'toeplitz') is refused: use the LSQR.  Making a new operator drops the map, as it drops the sample weights.
+%   operator ('normal', solver 'toeplitz') is refused until qmri_prepare_normal_fm (or param.field_normal in PnP_ADMM_hip) has built its
+%   field-aware form for this map; the LSQR needs no such call.  Making a new operator drops the map, as it drops the sample weights.
 if isempty(f), qmri_mex('set_field_map', []); info = []; return; end
 if nargin < 3 || isempty(nseg), nseg = 0; end
 if nargin < 4 || isempty(nbins), nbins = 0; end

@@ -23,6 +23,9 @@
 //     call that brings more slices than the plan's max_batch (it re-plans the operator for them); call 'dcf' / 'set_sample_weights' again after it.
 //     'set_field_map' attaches a field map for the off-resonance correction (qmri_set_field_map; extension).  The same
 //     re-plans drop the map with the weights: call 'set_field_map' again after them.
+//     'prepare_normal_fm' builds the Toeplitz normal operator of the attached map (qmri_nufft_prepare_normal_fm; extension):
+//     'normal' and param.solver = 2 then run with the map.  param.field_normal = 1 (with field_normal_nseg / field_normal_tol; param.field_normal
+//     in PnP_ADMM_hip.m) has 'pnp_admm' build it before the loop.  A new map, or any re-plan above, drops it.
 //   * 'recon_batch_mc' is the same for multi-coil stacks, every slice with its own coil maps (qmri_recon_batch_mc; an extension, no reference
 //     counterpart); with a coil-compression argument every launch compresses its slices on the device first (qmri_recon_batch_mc_cc).
 //   * 'coil_compress' compresses a multi-coil stack to virtual coils (qmri_coil_compress; extension).
@@ -119,6 +122,21 @@ static size_t operator_m() {
     int m = 0;
     check(qmri_operator_m(ctx(), &m));
     return (size_t)m;
+}
+
+// nseg and tol of the field-aware normal operator ('prepare_normal_fm', param.field_normal): nseg 0 or 2..32, tol finite and >= 0
+static qmri_offres_normal_params normal_fm_params(const mxArray* nseg, const mxArray* tol, const char* id_nseg, const char* id_tol) {
+    qmri_offres_normal_params p{};
+    if (nseg) {
+        p.nseg = int_arg(nseg, 0, 32, id_nseg, "nseg must be an integer in 2..32 (0: automatic)");
+        want(p.nseg != 1, id_nseg, "nseg must be an integer in 2..32 (0: automatic)");
+    }
+    if (tol) {
+        want(mxIsDouble(tol) && !mxIsComplex(tol) && mxGetNumberOfElements(tol) == 1, id_tol, "tol must be a real double scalar");
+        p.tol = mxGetScalar(tol);
+        want(std::isfinite(p.tol) && p.tol >= 0.0, id_tol, "tol must be finite and >= 0 (0: the default 1e-4)");
+    }
+    return p;
 }
 
 // (re-)make the plans from the kept specifications
@@ -381,6 +399,17 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         const double vals[] = {(double)fi.nseg, (double)fi.tol_reached, fi.fit_max, fi.fit_rms, fi.f_min, fi.f_max, fi.t_min, fi.t_max};
         plhs[0] = mxCreateStructMatrix(1, 1, 8, names);
         for (int k = 0; k < 8; ++k) mxSetFieldByNumber(plhs[0], 0, k, mxCreateDoubleScalar(vals[k]));
+    } else if (c == "prepare_normal_fm") {           // info = qmri_mex('prepare_normal_fm' [, nseg [, tol]]): the Toeplitz normal operator of the attached map
+        const qmri_offres_normal_params np = normal_fm_params(nrhs > 1 ? prhs[1] : nullptr, nrhs > 2 ? prhs[2] : nullptr, "qmri:prepare_normal_fm:nseg",
+                                                              "qmri:prepare_normal_fm:tol");     // (the argument checks come first: they need no operator)
+        want(g_op.V != nullptr, "qmri:state", "no operator: call qmri_mex('set_trajectory', ...) (qmri_make_F_traj) first");
+        want(g_op.omega != nullptr, "qmri:prepare_normal_fm:trajectory", "the field-aware normal operator needs a trajectory operator ('set_trajectory') with a field map");
+        qmri_offres_normal_info ni{};
+        check(qmri_nufft_prepare_normal_fm(ctx(), &np, &ni));
+        const char* names[] = {"nseg", "tol_reached", "fit_max", "fit_rms", "khat_bytes"};
+        const double vals[] = {(double)ni.nseg, (double)ni.tol_reached, ni.fit_max, ni.fit_rms, (double)ni.khat_bytes};
+        plhs[0] = mxCreateStructMatrix(1, 1, 5, names);
+        for (int k = 0; k < 5; ++k) mxSetFieldByNumber(plhs[0], 0, k, mxCreateDoubleScalar(vals[k]));
     } else if (c == "set_denoiser") {                // qmri_mex('set_denoiser', weights(single), in_nc, out_nc, nc(1x4), nb, residual_noise, H, W [, max_batch])
         need(nrhs, 9, "qmri_mex('set_denoiser', weights, in_nc, out_nc, nc, nb, residual_noise, H, W [, max_batch])");
         qmri_net_desc d;
@@ -430,6 +459,14 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         need(nrhs, 6, "[x, diag, lsqr_iters] = qmri_mex('pnp_admm', y, param, X0, gt, [N M s])");
         want(mxIsStruct(prhs[2]), "qmri:pnp_admm:type", "param must be a struct");
         const qmri_admm_params p = admm_params(prhs[2], nlhs > 1 && !g_op.omega);   // (a trajectory computes no diagnostics: diag stays NaN)
+        // param.field_normal = 1: build the field-aware Toeplitz normal operator before the loop (field_normal_nseg / field_normal_tol: its parameters)
+        const bool field_normal = scalar_field(prhs[2], "field_normal", 0) != 0;
+        qmri_offres_normal_params fnp{};
+        if (field_normal) {
+            fnp = normal_fm_params(mxGetField(prhs[2], 0, "field_normal_nseg"), mxGetField(prhs[2], 0, "field_normal_tol"), "qmri:pnp_admm:field_normal",
+                                   "qmri:pnp_admm:field_normal");
+            want(g_op.omega != nullptr, "qmri:pnp_admm:field_normal", "param.field_normal needs a trajectory operator ('set_trajectory') with a field map");
+        }
         const double* d = mxGetDoubles(prhs[5]);
         const size_t S = mxGetN(prhs[1]), m = mxGetM(prhs[1]), n = dims_numel(prhs[5]);
         want(is_cdouble(prhs[1]) && S >= 1 && m == operator_m(), "qmri:pnp_admm:size", "y must be complex double, one column of m samples per slice");
@@ -447,6 +484,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         const mxComplexDouble* gt = mxIsEmpty(prhs[4]) ? nullptr : mxGetComplexDoubles(prhs[4]);
         if (x0 && mxGetNumberOfElements(prhs[3]) != n * S) mexErrMsgIdAndTxt("qmri:pnp_admm:size", "X0 must hold N x M x s values per slice");
         if (gt && mxGetNumberOfElements(prhs[4]) != n * S) mexErrMsgIdAndTxt("qmri:pnp_admm:size", "gt_tsmi must hold N x M x s values per slice");
+        if (field_normal) check(qmri_nufft_prepare_normal_fm(ctx(), &fnp, nullptr));    // (a trajectory's launch size is 1: no re-plan follows)
         if (S == 1) {
             check(qmri_pnp_admm(ctx(), y, &p, x0, gt, mxGetComplexDoubles(plhs[0]), p.want_diag ? mxGetDoubles(diag) : nullptr, (int32_t*)mxGetData(li)));
         } else {

@@ -130,10 +130,13 @@ def PnP_ADMM(y, param):
     device: the whole loop then runs on the GPU with one boundary crossing.  param["tsmi_domain"] (default: the net's, "real"):
     "complex" runs the denoiser step on cat(3, real, imag) of x + uold.  param["x0"] = "dcf" (an extension for a
     trajectory F): the start image is the density-compensated adjoint of y instead of param["X0"]; the weights are
-    computed here if none are attached yet."""
+    computed here if none are attached yet.  param["field_normal"] (an extension for a trajectory F with a field map): True,
+    or a dict with nseg / tol, builds the field-aware Toeplitz normal operator before the loop (Engine.prepare_normal_field), which
+    param["solver"] = "toeplitz" then needs; what it reported is PnP_ADMM.last_field_normal."""
     F, net = param["F"], param["net"]
     if not hasattr(F, "_engine") or not hasattr(net, "_engine") or F._engine is not net._engine:
         raise TypeError("param.F and param.net must come from make_F / make_net of this package (same device)")
+    PnP_ADMM.last_field_normal = _field_normal(F, param.get("field_normal"))
     multi = param.get("denoiser_type", net._denoiser_type) == "multi_level"
     noise_std = float(np.asarray(param["noise_map"]).ravel()[0]) if multi else 0.01
     traj = getattr(F._P, "omega", None) is not None                 # (a trajectory computes no per-iteration diagnostics: last_diagnostics is None)
@@ -144,6 +147,17 @@ def PnP_ADMM(y, param):
                                      want_diag=param.get("gt_tsmi") is not None and not traj)
     PnP_ADMM.last_diagnostics, PnP_ADMM.last_lsqr_iters = diag, li
     return x
+
+
+def _field_normal(F, fn):
+    """param["field_normal"]: None / False: nothing; True: the defaults; a dict: its nseg and tol."""
+    if fn is None or fn is False:
+        return None
+    if fn is True:
+        fn = {}
+    if not isinstance(fn, dict) or set(fn) - {"nseg", "tol"}:
+        raise ValueError("field_normal must be True or a dict with nseg and / or tol")
+    return F._engine.prepare_normal_field(nseg=fn.get("nseg", 0), tol=fn.get("tol", 0.0))
 
 
 def _dcf_x0(F, param, y):
