@@ -428,3 +428,34 @@ def test_wide_dict_match_at_bench_size_K_98304_T_1000(engine_mod, oracle, synth)
     i1 = np.searchsorted(t1g, g["qmap"][:, :, 0][fg] * (1 - 1e-6)); i1 = np.clip(i1, 0, t1g.size - 1)
     want1 = np.abs(t1g[None, :] - q[:, :, 0][fg][:, None]).argmin(1)
     assert np.mean(np.abs(i1 - want1) <= 1) > 0.98
+
+
+@pytest.mark.parametrize("s", [1, 6, 8, 16])
+def test_xfit_reads_both_narrow_packs(engine_mod, oracle, s):
+    """k_dict_xfit reads D(dm, :) back through dict_atom (dict_device.h): s = 1, 6, 8 sit in the pack of 4 floats per lane, s = 16 fills the one of
+    8.  Random unit-norm atoms, K below and above the split of the atoms over workgroups and no multiple of the 32-atom tile, 300 noisy scaled
+    atoms as pixels, filter on and off: every output equals the oracle's bits, Xfit included."""
+    e = engine_mod.Engine(0)
+    try:
+        for K in (97, 2049):
+            rng = np.random.default_rng(100 * s + K)
+            D = rng.standard_normal((K, s)).astype(np.float32)
+            D /= np.linalg.norm(D, axis=1, keepdims=True)
+            nd = (0.5 + rng.random(K)).astype(np.float32)
+            lut = rng.random((K, 2)).astype(np.float32)
+            X = D[rng.integers(0, K, 300)] * (0.1 + rng.random((300, 1))) * np.exp(1j * rng.random((300, 1)) * 6.28)
+            X = X + 0.05 * (rng.standard_normal(X.shape) + 1j * rng.standard_normal(X.shape)) / np.sqrt(s)
+            o = oracle.dict_match(X, D, nd, lut, want_xfit=True)
+            assert o["Xfit"].shape == (300, s) and np.all(np.isfinite(o["Xfit"]))
+            e.set_dictionary(D, nd, lut)
+            for filt in (True, False):
+                e.dict_filter(filt)
+                g = e.dict_match(X, want_xfit=True)
+                for k in ("dm", "mt", "pd", "qmap", "Xfit"):
+                    gb, ob = np.ascontiguousarray(g[k]).view(np.uint32 if k != "dm" else np.int32), np.ascontiguousarray(o[k]).view(np.uint32 if k != "dm" else np.int32)
+                    assert np.array_equal(gb, ob), (s, K, filt, k, int(np.sum(gb != ob)))
+            if s > 1:
+                assert len(np.unique(o["dm"])) > 50                 # (the match is not degenerate)
+    finally:
+        e.dict_filter(True)
+        e.close()
