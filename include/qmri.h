@@ -601,6 +601,52 @@ int qmri_dict_simulate(qmri_ctx* ctx, int K, int T, const double* alpha, const d
 int qmri_dict_simulate_dev(qmri_ctx* ctx, int K, int T, const double* alpha, const double* tr, const double* te, const double* d_t1, const double* d_t2,
                            const double* d_b1, const qmri_epg_params* p, void* d_F_out);
 
+/* ---- field map from multi-echo images (extension, no reference counterpart, parity unpinned) ---- */
+/* qmri_set_field_map takes its map f from the caller; this call makes one from L gradient-echo images per slice, by the regularised estimator of
+ * Funai, Fessler, Yeo, Olafsson and Noll (IEEE TMI 2008): a penalised cosine fit over all echo pairs and coils, minimised by separable quadratic
+ * surrogates with a FIXED iteration count (no stopping rule, so the bits do not depend on what else is in the batch).
+ *   Model: y_{l,c}[n] = x_c[n] exp(sigma i 2 pi f[n] t_l); sigma = phase_sign, default -1 = the sign of qmri_set_field_map's operator.
+ *   Pairs (a < b), P = L (L - 1) / 2 of them in the order (0,1), (0,2), ..., (L-2, L-1):
+ *     s_ab[n] = sum_c y_{a,c}[n] conj(y_{b,c}[n]), coils ascending (sigma = +1: conj(y_a) y_b);  phi_ab = atan2(Im s_ab, Re s_ab);
+ *     d_ab = 2 pi (t_b - t_a);  w_ab[n] = |s_ab[n]| / W,  W = max_n sum_ab |s_ab[n]| over the slice (W = 0: every weight 0).
+ *   Cost: Psi(f) = sum_n sum_ab w_ab[n] (1 - cos(phi_ab[n] - d_ab f[n])) + (B / 2) sum_edges (f[n] - f[n'])^2, the edges being the horizontal and
+ *     vertical neighbour pairs inside the grid, each once; B = beta (2 pi (t_{L-1} - t_0))^2.
+ *   Start: f0[n] = phi_01[n] / d_01, or the caller's f_init.
+ *   Iteration, all of f^{k+1} from f^k, per pixel with pairs in their order and the neighbours in the order n1-1, n1+1, n2-1, n2+1:
+ *     u_ab = phi_ab - d_ab f, wrapped by u - 2 pi rint(u / 2 pi);  kappa(u) = sin(u) / u (1 for |u| < 1e-8);
+ *     g = -sum w_ab d_ab sin u_ab;  c = sum w_ab d_ab^2 kappa(u_ab);  lap = nb f - sum of the nb in-grid neighbours;  den = c + 2 B nb;
+ *     f <- f - (g + B lap) / den  (unchanged when den <= 0).
+ * Psi does not increase.  All arithmetic is fp64 with explicit fused multiply-adds in one order, no atomics: a slice has the same bits alone, at
+ * any position of a stack and for any nslices.  N, M >= 2 are free (no FFT is involved; at most 4096 each).  Needs neither an operator, a
+ * denoiser nor a dictionary. */
+typedef struct {
+    int32_t iters;        /* 1..100000; 0: the default 200 */
+    double  beta;         /* dimensionless, finite, >= 0; 0: the default 0.01 (so 0 cannot mean "no regulariser") */
+    int32_t phase_sign;   /* -1 (also 0): y_l = x exp(-i 2 pi f t_l), the operator's sign; +1: the other convention */
+    int32_t reserved[4];  /* must be 0 */
+} qmri_fieldmap_params;
+typedef struct {
+    double  cost0, cost;      /* Psi before the first and after the last iteration (fixed-order sums) */
+    double  f_min, f_max;     /* of the returned map, Hz */
+    int32_t iters;            /* iterations run */
+    int32_t reserved;
+    double  unwrap_limit_hz;  /* 1 / (2 (t_1 - t_0)): the start wraps beyond it */
+} qmri_fieldmap_info;
+/* Host arrays.  Y: complex fp64, [slice][echo][coil][n1 + N n2]; t_s[nechoes] seconds, finite and strictly increasing; f_init (nullable) and f_out:
+ * [slice][n1 + N n2] fp64 Hz, one slice plane being what qmri_set_field_map reads; trust_out (nullable): sum_ab w_ab in the same layout; info
+ * (nullable): nslices entries; p (nullable): the defaults.  Refusals are decided on the host before the device is selected (ctx == NULL: the
+ * message of the first failing check in qmri_last_error(NULL)): a NULL Y / t_s / f_out, nslices outside 1..4096, nechoes outside 2..8, ncoil < 1,
+ * N or M outside 2..4096, a non-finite or non-increasing t_s, a negative or non-finite beta, iters outside 0..100000, phase_sign outside
+ * {0, -1, +1}, reserved != 0, a non-finite value in Y or f_init: QMRI_ERR_INVALID_ARG; ncoil > 128: QMRI_ERR_UNSUPPORTED.  Returns after its
+ * kernels have finished. */
+int qmri_field_map_estimate(qmri_ctx* ctx, int nslices, int nechoes, int ncoil, int N, int M, const void* Y, const double* t_s, const double* f_init,
+                            const qmri_fieldmap_params* p, double* f_out, double* trust_out, qmri_fieldmap_info* info);
+/* The same with Y, f_init, f_out and trust_out on ctx's device; t_s, p and info stay on the host.  Same bits as the host-array call.  Runs on the
+ * context's stream and returns after its kernels have finished.  This route cannot read its images on the host: for a slice whose Y or f_init
+ * holds a non-finite value the whole plane of f_out (and of trust_out) of that slice, and of no other, is NaN. */
+int qmri_field_map_estimate_dev(qmri_ctx* ctx, int nslices, int nechoes, int ncoil, int N, int M, const void* d_Y, const double* t_s,
+                                const double* d_f_init, const qmri_fieldmap_params* p, double* d_f_out, double* d_trust_out, qmri_fieldmap_info* info);
+
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------------ */
 typedef struct {
     double ms_xupdate, ms_denoiser, ms_elementwise, ms_diag, ms_match;   /* hipEvent time per stage */

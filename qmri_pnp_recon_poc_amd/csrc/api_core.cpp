@@ -28,6 +28,7 @@ const KnobDef g_knob_defs[K_COUNT] = {
     {"conv_mt2", 1024}, {"conv_occ", 2},
     {"fuse_ew", 1}, {"lsqr_persist", 1}, {"lsqr_fold", 1}, {"dictw_lsp", 2}, {"verbose", 0},
     {"pack_gpu", 1}, {"nufft_seg", NU_SEG},
+    {"fmap_fuse", 0}, {"fmap_start", 0},
 };
 std::atomic<int> g_knob_val[K_COUNT];
 std::once_flag g_knob_once;

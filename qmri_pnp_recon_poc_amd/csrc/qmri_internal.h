@@ -104,6 +104,8 @@ enum QmriKnob {
     K_VERBOSE,            // calibration / guard decisions on stderr
     K_PACK_GPU,           // qmri_set_denoiser: weights split and ordered on the device (1, default) or on the host (0: the round-1 packers, same bits)
     K_NUFFT_SEG,          // qmri_set_operator_nufft: samples per spreading segment (default NU_SEG = 512, at least 32); results change only in rounding
+    K_FMAP_FUSE,          // qmri_field_map_estimate: 0 (default) one launch per iteration, 1 h iterations per launch on halo tiles in LDS (same bits; slower as measured)
+    K_FMAP_START,         // qmri_field_map_estimate: 1 returns the start f0 (no iteration is run; info.iters = 0): what the tests feed back as f_init
     K_COUNT
 };
 int qmri_knob(QmriKnob k);
@@ -356,6 +358,20 @@ int epg_atoms_per_workgroup(int S);      // atoms a workgroup simulates (= the c
 int epg_simulate_dev(qmri_ctx* ctx, int K, int T, const double* d_sched, const double* d_t1, const double* d_t2, const double* d_b1 /* or NULL */,
                      const qmri_epg_params& p, bool const_timing, void* d_F);
 int epg_shift_dev(qmri_ctx* ctx, int S, int nshift, const double* d_in, double* d_out);      // the spoiler alone on one atom's state (3 S doubles)
+
+// field map from multi-echo images (fmap_kernels.hip, api_fmap.cpp).  All d_ pointers are device pointers; the stream is
+// idle on return (the per-slice results are read back for info).
+constexpr int FMAP_MAX_PAIRS = 28;       // L <= 8 echoes
+struct FmapPlan {
+    int nslices, L, C, N, M, P, iters, sign;
+    double beta;                         // B = beta (2 pi (t_{L-1} - t_0))^2
+    double unwrap_limit_hz;
+    double d[FMAP_MAX_PAIRS];            // 2 pi (t_b - t_a) per pair
+    int pa[FMAP_MAX_PAIRS], pb[FMAP_MAX_PAIRS];
+};
+int fmap_halo();                         // h: iterations per fused launch
+int fmap_estimate_dev(qmri_ctx* ctx, const FmapPlan& pl, const double2* d_Y, const double* d_f_init /* or NULL */, double* d_f_out,
+                      double* d_trust_out /* or NULL */, qmri_fieldmap_info* info /* host, or NULL */);
 
 // ---------------------------------------------------------------------------------------------------
 // trajectory (NUFFT) operator (nufft_kernels.hip, api_nufft.cpp).  Planned once on the host per qmri_set_operator_nufft:

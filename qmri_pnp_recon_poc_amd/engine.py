@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import AdmmParams, CcParams, CsmInfo, CsmParams, DcfInfo, DcfParams, DsvdInfo, DsvdParams, EpgParams, LrtvInfo, LrtvParams, NetDesc, NufftParams, OffresInfo, OffresNormalInfo, OffresNormalParams, OffresParams, Profile
+from ._lib import AdmmParams, CcParams, CsmInfo, CsmParams, DcfInfo, DcfParams, DsvdInfo, DsvdParams, EpgParams, FieldmapInfo, FieldmapParams, LrtvInfo, LrtvParams, NetDesc, NufftParams, OffresInfo, OffresNormalInfo, OffresNormalParams, OffresParams, Profile
 
 ARCH_UNETRES, ARCH_SEQ_CONV = 0, 1
 SOLVER_LSQR, SOLVER_DIRECT = 0, 1
@@ -99,6 +99,51 @@ def simulation_arguments(alpha, tr, te, t1, t2, b1, nstates, inversion, ti, inv_
         raise ValueError("ti must be >= 0 and inv_eff in (0, 1]")
     p = EpgParams(int(nstates), 1 if inversion else 0, float(ti), float(inv_eff), int(np.dtype(dtype) == np.dtype(np.float64)))
     return a, sched[0], sched[1], atoms[0], atoms[1], atoms[2] if b1 is not None else None, p
+
+
+def fieldmap_arguments(Y, echo_times, iters=0, beta=0.0, phase_sign=-1, f_init=None):
+    """The arguments of Engine.estimate_field_map as the library takes them: (Y buffer [S][L][C][n1 + N n2] complex128, t [L] float64, f_init buffer
+    or None, FieldmapParams, (S, L, C, N, M), stacked).  Y is [L, N, M], [L, C, N, M] or [S, L, C, N, M]; stacked says whether it carried a slice axis
+    (the results then keep it).  f_init is [N, M], or [S, N, M] for a stack."""
+    Y = np.asarray(Y)
+    if Y.ndim not in (3, 4, 5):
+        raise ValueError(f"Y must be [L, N, M], [L, C, N, M] or [S, L, C, N, M], not {Y.ndim}-dimensional")
+    stacked = Y.ndim == 5
+    Y5 = Y[None, :, None] if Y.ndim == 3 else Y[None] if Y.ndim == 4 else Y
+    S, L, Cc, N, M = Y5.shape
+    t = np.asarray(echo_times)
+    if np.iscomplexobj(t):
+        raise ValueError("the echo times must be real (seconds)")
+    t = np.ascontiguousarray(t, dtype=np.float64).ravel()
+    if t.size != L:
+        raise ValueError(f"echo_times must hold one time per echo ({L}), not {t.size}")
+    if not (2 <= L <= 8):
+        raise ValueError("the estimate takes 2 <= L <= 8 echoes")
+    if S < 1 or Cc < 1 or N < 2 or M < 2:
+        raise ValueError("Y needs at least one slice and coil and a grid of at least 2 x 2")
+    if not np.all(np.isfinite(t)) or np.any(np.diff(t) <= 0):
+        raise ValueError("echo_times must be finite and strictly increasing")
+    if int(iters) != iters or not (0 <= int(iters) <= 100000):
+        raise ValueError("iters must be an integer in 1..100000 (0: the default 200)")
+    if not (np.isfinite(beta) and beta >= 0):
+        raise ValueError("beta must be finite and >= 0 (0: the default 0.01)")
+    if phase_sign not in (-1, 0, 1):
+        raise ValueError("phase_sign must be -1 or +1")
+    Yb = np.ascontiguousarray(np.swapaxes(np.asarray(Y5, dtype=np.complex128), 3, 4))       # [S][L][C][n2][n1]: n1 fastest
+    fb = None
+    if f_init is not None:
+        f = np.asarray(f_init)
+        if np.iscomplexobj(f):
+            raise ValueError("f_init must be real (Hz)")
+        if f.shape != ((S, N, M) if stacked else (N, M)):
+            raise ValueError(f"f_init must be {'[S, N, M]' if stacked else '[N, M]'} = {(S, N, M) if stacked else (N, M)}, not {f.shape}")
+        fb = np.ascontiguousarray(np.swapaxes(np.asarray(f, dtype=np.float64).reshape(S, N, M), 1, 2))
+    return Yb, t, fb, FieldmapParams(int(iters), float(beta), int(phase_sign)), (S, L, Cc, N, M), stacked
+
+
+def fieldmap_info(info):
+    return {"cost0": float(info.cost0), "cost": float(info.cost), "f_min": float(info.f_min), "f_max": float(info.f_max), "iters": int(info.iters),
+            "unwrap_limit_hz": float(info.unwrap_limit_hz)}
 
 
 def group_arguments(group_ptr, group_val):
@@ -391,6 +436,40 @@ class Engine:
         self._check(self.L.qmri_nufft_prepare_normal_fm(self.h, C.byref(p), C.byref(info)))
         return {"nseg": int(info.nseg), "tol_reached": int(info.tol_reached), "fit_max": float(info.fit_max), "fit_rms": float(info.fit_rms),
                 "khat_bytes": int(info.khat_bytes)}
+
+    # -- field map from multi-echo images (extension, no reference counterpart) ------------------------------
+    def estimate_field_map(self, Y, echo_times, *, iters=0, beta=0.0, phase_sign=-1, f_init=None, return_info=False, return_trust=False):
+        """The field map in Hz of L gradient-echo images per slice, by the regularised estimator of Funai et al. on the device
+        (qmri_field_map_estimate): Y [L, N, M], [L, C, N, M] or [S, L, C, N, M] complex, echo_times [L] seconds, strictly increasing.  iters
+        iterations (0: 200; there is no stopping rule), beta the dimensionless smoothness weight (0: 0.01), phase_sign -1: y_l = x exp(-i 2 pi f
+        t_l), the sign of set_field_map's operator; +1 the other convention.  f_init ([N, M], or [S, N, M] for a stack) replaces the start
+        phi_01 / d_01.  Returns f [N, M] ([S, N, M] for a stack): what set_field_map takes; with return_info also dict(cost0, cost, f_min, f_max,
+        iters, unwrap_limit_hz) (a list of them for a stack), with return_trust also sum_ab w_ab in the shape of f.  Needs no operator."""
+        Yb, t, fb, p, (S, L, Cc, N, M), stacked = fieldmap_arguments(Y, echo_times, iters, beta, phase_sign, f_init)
+        f = np.empty((S, M, N), np.float64)
+        trust = np.empty((S, M, N), np.float64) if return_trust else None
+        info = (FieldmapInfo * S)()
+        self._check(self.L.qmri_field_map_estimate(self.h, S, L, Cc, N, M, _vp(Yb), t.ctypes.data_as(C.POINTER(C.c_double)), _vp(fb), C.byref(p), _vp(f),
+                                                   _vp(trust), info))
+        shape = (lambda a: np.ascontiguousarray(np.swapaxes(a, 1, 2)) if stacked else np.ascontiguousarray(a[0].T))
+        out = [shape(f)]
+        if return_info:
+            out.append([fieldmap_info(i) for i in info] if stacked else fieldmap_info(info[0]))
+        if return_trust:
+            out.append(shape(trust))
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def estimate_field_map_dev(self, d_Y: int, dims, echo_times, d_f_out: int, *, iters=0, beta=0.0, phase_sign=-1, d_f_init: int = 0, d_trust_out: int = 0):
+        """qmri_field_map_estimate_dev: device pointers (Y [S][L][C][n1 + N n2] complex double, f / trust [S][n1 + N n2] double), dims = (S, L, C, N,
+        M); runs on the engine's stream and returns after completion.  Returns the list of S info dicts."""
+        S, L, Cc, N, M = (int(v) for v in dims)
+        t = np.ascontiguousarray(echo_times, dtype=np.float64).ravel()
+        if t.size != L:
+            raise ValueError(f"echo_times must hold one time per echo ({L}), not {t.size}")
+        p, info = FieldmapParams(int(iters), float(beta), int(phase_sign)), (FieldmapInfo * max(S, 1))()
+        self._check(self.L.qmri_field_map_estimate_dev(self.h, S, L, Cc, N, M, C.c_void_p(d_Y), t.ctypes.data_as(C.POINTER(C.c_double)),
+                                                       C.c_void_p(d_f_init or None), C.byref(p), C.c_void_p(d_f_out), C.c_void_p(d_trust_out or None), info))
+        return [fieldmap_info(i) for i in info[:S]]
 
     def adjoint(self, y, weighted=False):
         """x = F.adjoint(y)  (main_recon_tsmis_FFT.m:229); complex64 in -> complex64 out (the _f32 entry point).

@@ -272,6 +272,14 @@ def save_training_pickle(path, X_slices, channels_to_save=None):
         pickle.dump(training_volume(X_slices, channels_to_save), f)
 
 
+def estimate_field_map(Y, echo_times, device=0, **kw):
+    """The field map in Hz of multi-echo gradient-echo images, estimated on the device (Engine.estimate_field_map; an extension, DESIGN.md section
+    24): Y [L, N, M], [L, C, N, M] or [S, L, C, N, M] complex, echo_times [L] seconds.  Keywords: iters, beta, phase_sign, f_init, return_info,
+    return_trust.  The result is what recon_tsmis(field_map=...) and Engine.set_field_map take."""
+    from . import reference_api as R
+    return R._engine(device).estimate_field_map(Y, echo_times, **kw)
+
+
 # ------------------------------------------------------------------------------------------------------------
 # the script's main flow
 # ------------------------------------------------------------------------------------------------------------
@@ -279,7 +287,7 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
                 spiral_sampling_curve=771, epi_sampling_rate=1 / 65, measurements_type="noisy", measurements_noise=30,
                 denoiser_type="single_level", noise_map_std=0.01, residual_noise=False, iters=100, seed=0, Y=None, device=0,
                 net_arch=None, lrtv_iters=None, tsmi_domain="real", solver="lsqr", b1_map=None, density_compensation=False,
-                field_map=None, readout_s=None, field_normal=None):
+                field_map=None, readout_s=None, field_normal=None, field_echoes=None, field_echo_times=None):
     """main_recon_tsmis_FFT.m:216-374 on already loaded (and cropped) arrays.
 
     dictionary  dict(V, D, normD, lut) (load_dictionary);  X0  N x M x s ground-truth TSMI;  qmap0  N x M x 3
@@ -296,6 +304,9 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
     field_map, readout_s  with SpiralExact, PnP_ADMM or SVD_MRF: an N x M field map in Hz and the length of one spiral readout in seconds (sample j of a
                 frame is measured at j * readout_s / S): the operator carries the off-resonance phase (time segmentation), for
                 the measurements it simulates (when Y is not given) and for the reconstruction.  Absent: the operator without a map, bit for bit.
+    field_echoes, field_echo_times  with field_map="estimate": [L, N, M] or [L, C, N, M] gradient-echo images and their L echo times in seconds; the
+                map is estimated from them on the device first (estimate_field_map) and then takes the field_map route
+                unchanged.  The result gains field_map (the estimate) and field_map_info.
     field_normal  with field_map and solver="toeplitz": True, or a dict with nseg / tol, builds the field-aware Toeplitz normal operator before the
                 loop (Engine.prepare_normal_field); None or False (default): solver="toeplitz" with a field_map is refused
     Returns dict(X, qmap (N x M x 3: T1, T2, PD), Y, metrics, foreground_mask); with b1_map also grp (N x M, the 1-based b1 group, 0 = unmatched);
@@ -326,6 +337,18 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
         raise ValueError(f"unknown subsampling pattern {subsampling_pattern}")
     if density_compensation and subsampling_pattern != "SpiralExact":
         raise ValueError("density_compensation needs the subsampling pattern SpiralExact (a gridded mask has nothing to compensate)")
+    extra_fm = {}
+    if isinstance(field_map, str) or field_echoes is not None or field_echo_times is not None:
+        if not (isinstance(field_map, str) and field_map == "estimate") or field_echoes is None or field_echo_times is None:
+            raise ValueError('field_map="estimate", field_echoes and field_echo_times go together')
+        if readout_s is None:
+            raise ValueError("field_map and readout_s go together")
+        if subsampling_pattern != "SpiralExact":
+            raise ValueError("field_map needs the subsampling pattern SpiralExact (a gridded mask has no readout times)")
+        if np.asarray(field_echoes).ndim not in (3, 4) or np.asarray(field_echoes).shape[-2:] != (N, M):
+            raise ValueError(f"field_echoes must be [L, {N}, {M}] or [L, C, {N}, {M}]")
+        field_map, fm_info = estimate_field_map(field_echoes, field_echo_times, device=device, return_info=True)
+        extra_fm = {"field_map": field_map, "field_map_info": fm_info}
     if (field_map is None) != (readout_s is None):
         raise ValueError("field_map and readout_s go together")
     if field_map is not None and subsampling_pattern != "SpiralExact":
@@ -381,7 +404,7 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
     else:
         raise ValueError(f"unknown reconstruction method {recon_method}")
     par = {"f": {"qout": 1, "pdout": 1, "mtout": 0, "Xout": 0, "dmout": 0, "Yout": 0, "verbose": 0}, "fp": {"blockSize": 1e9}}   # :302-309
-    extra = dict(extra_fn)
+    extra = {**extra_fn, **extra_fm}
     if b1_map is not None:
         eng = R._engine(device)
         eng.set_dictionary(dictionary["D"], dictionary["normD"], dictionary["lut"])

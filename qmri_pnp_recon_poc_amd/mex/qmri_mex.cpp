@@ -32,6 +32,8 @@
 //   * 'coil_maps' estimates coil sensitivity maps from calibration data (qmri_coil_maps; extension).
 //   * 'dict_compress' compresses a simulated dictionary to its SVD subspace (qmri_dict_compress; extension); it needs no plan.
 //   * 'dict_simulate' simulates the fingerprints of a FISP-MRF sequence by extended phase graphs (qmri_dict_simulate; extension); it needs no plan.
+//   * 'field_map_estimate' estimates the field map that 'set_field_map' takes from multi-echo images (qmri_field_map_estimate; extension, DESIGN.md
+//     section 24); it needs no plan.
 // tests/cpp/mex_mock.cpp is a small stand-in for the MATLAB runtime's C API under which this file is compiled, LINKED against libqmri.so and
 // driven command by command on the GPU box (tests/test_gpu_mex.py); with MATLAB's own mex.h nothing here changes.
 #include "mex.h"
@@ -399,6 +401,58 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         const double vals[] = {(double)fi.nseg, (double)fi.tol_reached, fi.fit_max, fi.fit_rms, fi.f_min, fi.f_max, fi.t_min, fi.t_max};
         plhs[0] = mxCreateStructMatrix(1, 1, 8, names);
         for (int k = 0; k < 8; ++k) mxSetFieldByNumber(plhs[0], 0, k, mxCreateDoubleScalar(vals[k]));
+    } else if (c == "field_map_estimate") {          // [f, info, trust] = qmri_mex('field_map_estimate', Y, t [, iters [, beta [, phase_sign]]])
+        // extension (no reference counterpart): the field map in Hz of L gradient-echo images per slice (qmri_field_map_estimate).  Y: complex double
+        // N x M x L (one coil), N x M x C x L or N x M x C x L x S; t: the L echo times in seconds.  f: N x M (x S); info: struct of 1 x S rows; trust as f.
+        const char* usage = "[f, info, trust] = qmri_mex('field_map_estimate', Y, t [, iters, beta, phase_sign])";
+        need(nrhs, 3, usage);
+        want(nlhs <= 3, "qmri:usage", usage);
+        want(is_cdouble(prhs[1]), "qmri:field_map_estimate:type", "Y must be a complex double array (N x M x L, N x M x C x L or N x M x C x L x S)");
+        want(mxIsDouble(prhs[2]) && !mxIsComplex(prhs[2]), "qmri:field_map_estimate:t", "t must be a real double vector of echo times in seconds");
+        const size_t L = mxGetNumberOfElements(prhs[2]);
+        want(L >= 2 && L <= 8, "qmri:field_map_estimate:t", "t must hold 2 <= L <= 8 echo times");
+        const double* t = mxGetDoubles(prhs[2]);
+        for (size_t l = 0; l < L; ++l)
+            want(std::isfinite(t[l]) && (l == 0 || t[l] > t[l - 1]), "qmri:field_map_estimate:t", "t must be finite and strictly increasing");
+        const size_t nd = mxGetNumberOfDimensions(prhs[1]);
+        const mwSize* yd = mxGetDimensions(prhs[1]);
+        want(nd >= 3 && nd <= 5, "qmri:field_map_estimate:size", "Y must be N x M x L, N x M x C x L or N x M x C x L x S");
+        const size_t N = yd[0], M = yd[1], Cc = nd == 3 ? 1 : yd[2], Ly = nd == 3 ? yd[2] : yd[3], S = nd == 5 ? yd[4] : 1;
+        want(Ly == L, "qmri:field_map_estimate:size", "the echo dimension of Y must have one image per entry of t");
+        want(N >= 2 && N <= 4096 && M >= 2 && M <= 4096 && Cc >= 1 && Cc <= 128 && S >= 1 && S <= 4096, "qmri:field_map_estimate:size",
+             "Y: 2 <= N, M <= 4096, at most 128 coils and 4096 slices");
+        qmri_fieldmap_params fp{};
+        if (nrhs > 3) fp.iters = int_arg(prhs[3], 0, 100000, "qmri:field_map_estimate:iters", "iters must be an integer in 1..100000 (0: the default 200)");
+        if (nrhs > 4) {
+            want(mxIsDouble(prhs[4]) && !mxIsComplex(prhs[4]) && mxGetNumberOfElements(prhs[4]) == 1, "qmri:field_map_estimate:beta", "beta must be a real double scalar");
+            fp.beta = mxGetScalar(prhs[4]);
+            want(std::isfinite(fp.beta) && fp.beta >= 0.0, "qmri:field_map_estimate:beta", "beta must be finite and >= 0 (0: the default 0.01)");
+        }
+        if (nrhs > 5) {
+            fp.phase_sign = int_arg(prhs[5], -1, 1, "qmri:field_map_estimate:phase_sign", "phase_sign must be -1 or +1");
+            want(fp.phase_sign != 0, "qmri:field_map_estimate:phase_sign", "phase_sign must be -1 or +1");
+        }
+        // MATLAB's N x M x C x L x S is the ABI's [slice][echo][coil][n1 + N n2] as it stands
+        const mwSize fd[3] = {(mwSize)N, (mwSize)M, (mwSize)S};
+        plhs[0] = mxCreateNumericArray(S > 1 ? 3 : 2, fd, mxDOUBLE_CLASS, mxREAL);
+        mxArray* trust = nlhs > 2 ? mxCreateNumericArray(S > 1 ? 3 : 2, fd, mxDOUBLE_CLASS, mxREAL) : nullptr;
+        std::vector<qmri_fieldmap_info> fi(S);
+        check(qmri_field_map_estimate(ctx(), (int)S, (int)L, (int)Cc, (int)N, (int)M, mxGetComplexDoubles(prhs[1]), t, nullptr, &fp, mxGetDoubles(plhs[0]),
+                                      trust ? mxGetDoubles(trust) : nullptr, fi.data()));
+        if (nlhs > 1) {
+            const char* names[] = {"cost0", "cost", "f_min", "f_max", "iters", "unwrap_limit_hz"};
+            plhs[1] = mxCreateStructMatrix(1, 1, 6, names);          // every field a 1 x S row: info.cost(k) is slice k's
+            for (int k = 0; k < 6; ++k) {
+                mxArray* row = mxCreateDoubleMatrix(1, (mwSize)S, mxREAL);
+                double* v = mxGetDoubles(row);
+                for (size_t i = 0; i < S; ++i) {
+                    const double vals[] = {fi[i].cost0, fi[i].cost, fi[i].f_min, fi[i].f_max, (double)fi[i].iters, fi[i].unwrap_limit_hz};
+                    v[i] = vals[k];
+                }
+                mxSetFieldByNumber(plhs[1], 0, k, row);
+            }
+        }
+        if (trust) plhs[2] = trust;
     } else if (c == "prepare_normal_fm") {           // info = qmri_mex('prepare_normal_fm' [, nseg [, tol]]): the Toeplitz normal operator of the attached map
         const qmri_offres_normal_params np = normal_fm_params(nrhs > 1 ? prhs[1] : nullptr, nrhs > 2 ? prhs[2] : nullptr, "qmri:prepare_normal_fm:nseg",
                                                               "qmri:prepare_normal_fm:tol");     // (the argument checks come first: they need no operator)

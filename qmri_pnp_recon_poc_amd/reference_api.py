@@ -61,11 +61,29 @@ def setup_subsampling_spiral_exact(N, M, S, V):
     return SimpleNamespace(N=int(N), M=int(M), V=V, frame_ptr=fp, omega=om, pattern="SpiralExact", S=int(S))
 
 
-def make_F(P, device=0, field_map=None, readout_s=None):
+def make_F(P, device=0, field_map=None, readout_s=None, field_echoes=None, field_echo_times=None):
     """F.forward = @(x) P.for(reshape(fft2(x),[],1))/sqrt(N*M);  F.adjoint = @(x) ifft2(reshape(P.adj(x),N,M,[]))*sqrt(N*M).
     A P with a trajectory (setup_subsampling_spiral_exact) gives the same two maps at the exact sample positions; field_map (N x M, Hz) with
     readout_s (the length of one spiral readout, seconds) then attaches the off-resonance correction (an extension):
-    F.forward / F.adjoint and PnP_ADMM carry exp(-i 2 pi f tau).  F.field_info is what Engine.set_field_map reported, or None."""
+    F.forward / F.adjoint and PnP_ADMM carry exp(-i 2 pi f tau).  F.field_info is what Engine.set_field_map reported, or None.
+    field_echoes ([L, N, M] or [L, C, N, M] gradient-echo images) with field_echo_times ([L] seconds) instead of field_map (or with
+    field_map="estimate"): the map is estimated from them on the device first (Engine.estimate_field_map) and attached in
+    the same way; F.field_map is the map in use and F.field_map_info what the estimate reported (None for a caller's map)."""
+    if (field_echoes is None) != (field_echo_times is None):
+        raise ValueError("field_echoes and field_echo_times go together")
+    if isinstance(field_map, str) and (field_map != "estimate" or field_echoes is None):
+        raise ValueError('field_map is an N x M array, or "estimate" with field_echoes and field_echo_times')
+    if field_echoes is not None and not (field_map is None or isinstance(field_map, str)):
+        raise ValueError("give field_echoes or a field_map, not both")
+    fm_info = None
+    if field_echoes is not None:
+        if readout_s is None:
+            raise ValueError("field_map and readout_s go together")
+        if getattr(P, "omega", None) is None:
+            raise ValueError("field_map needs a trajectory operator (setup_subsampling_spiral_exact): a gridded mask has no readout times")
+        if np.asarray(field_echoes).ndim not in (3, 4):
+            raise ValueError("field_echoes must be [L, N, M] or [L, C, N, M]: one map per operator")
+        field_map, fm_info = _engine(device).estimate_field_map(field_echoes, field_echo_times, return_info=True)
     if (field_map is None) != (readout_s is None):
         raise ValueError("field_map and readout_s go together")
     if field_map is not None and getattr(P, "omega", None) is None:
@@ -78,7 +96,7 @@ def make_F(P, device=0, field_map=None, readout_s=None):
             info = eng.set_field_map(field_map, E.spiral_readout_times(P.S, P.V.shape[0], readout_s))
     else:
         eng.set_operator(P.N, P.M, P.V, P.frame_ptr, P.kidx)
-    return SimpleNamespace(forward=eng.forward, adjoint=eng.adjoint, _engine=eng, _P=P, field_info=info)
+    return SimpleNamespace(forward=eng.forward, adjoint=eng.adjoint, _engine=eng, _P=P, field_info=info, field_map=field_map, field_map_info=fm_info)
 
 
 def denoiseImage_PnP_ADMM(A, net, onnx_dagnetwork=True, residual_noise=False):
