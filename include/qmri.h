@@ -647,6 +647,46 @@ int qmri_field_map_estimate(qmri_ctx* ctx, int nslices, int nechoes, int ncoil, 
 int qmri_field_map_estimate_dev(qmri_ctx* ctx, int nslices, int nechoes, int ncoil, int N, int M, const void* d_Y, const double* t_s,
                                 const double* d_f_init, const qmri_fieldmap_params* p, double* d_f_out, double* d_trust_out, qmri_fieldmap_info* info);
 
+/* ---- locally low-rank regulariser (extension, no reference counterpart, parity unpinned) ---- */
+/* The proximal step of the locally low-rank (LLR) penalty of subspace MR fingerprinting (Zhang et al., Tamir et al., Asslaender et al.): the
+ * singular values of every b x b spatial block of the coefficient images are soft-thresholded.  It needs no trained weights, is defined for
+ * complex images and does not involve the operator.
+ *   X: N x M x s complex fp64, [n1 + N n2 + N M c] per slice, slices outermost.  b = block in {4, 8, 16}, b | N and b | M; 0 <= o1, o2 < b.
+ *   Block (i, j), i < N / b, j < M / b, holds the pixels ((o1 + i b + p) mod N, (o2 + j b + q) mod M), p, q < b (circular wrap: every block is full).
+ *   The b^2 x s Casorati matrix A of a block becomes U max(S - tau, 0) V^H.  tau = 0 is the identity up to rounding; a zero block stays zero.
+ *   sigma_max of a slice = the largest singular value over its blocks before thresholding.
+ *   Real mode works on real(X); its output has an imaginary part that is exactly 0.
+ * The device route: G = A^H A, its eigenpairs by cyclic Jacobi sweeps in a fixed pivot order (at most 24 sweeps), W = V diag(f) V^H with
+ * f_k = max(0, 1 - tau / sigma_k), sigma_k = sqrt(max(lambda_k, 0)), out = A W.  All fp64, every sum in one fixed order, no atomics: a slice has
+ * the same bits alone, at any position of a stack and for any nslices.  A non-finite value makes the output of its block (and of no other) non-finite. */
+typedef struct {
+    double  tau;          /* threshold on the singular values, in the units of the TSMI, >= 0 */
+    int32_t block;        /* 4, 8 or 16; 0 = 8 */
+    int32_t shift;        /* 0: blocks always at offset (0,0); 1: the offsets cycle with the ADMM iteration */
+    int32_t reserved[5];  /* must be zero */
+} qmri_llr_params;
+/* Host arrays.  x: [slice][c][n2][n1], complex fp64 (x_is_complex = 1) or real fp64 (x_is_complex = 0: real mode); out: complex fp64 in the same
+ * layout; sigma_max_out (nullable): nslices doubles.  p->shift is ignored (the offsets are arguments).  Needs neither an operator, a denoiser nor a
+ * dictionary.  Refusals are decided on the host before the device is selected (ctx == NULL: the message of the first failing check in
+ * qmri_last_error(NULL)): a NULL x / p / out, nslices < 1, s outside 1..16, a block outside {0, 4, 8, 16}, N or M not a positive multiple of
+ * the block, an offset outside 0..block-1, a negative or non-finite tau, reserved != 0: QMRI_ERR_INVALID_ARG.  Returns after its kernels have finished. */
+int qmri_llr_prox(qmri_ctx* ctx, int N, int M, int s, int nslices, const void* x, int x_is_complex, const qmri_llr_params* p, int o1, int o2,
+                  void* out, double* sigma_max_out);
+/* The same with d_x and d_out (complex fp64 both) on ctx's device; x_is_complex = 0: real mode, the real part of d_x is taken.  d_out may alias
+ * d_x.  sigma_max_out (nullable) stays a host array.  Same bits as the host-array call.  Runs on the context's stream and returns after its
+ * kernels have finished. */
+int qmri_llr_prox_dev(qmri_ctx* ctx, int N, int M, int s, int nslices, const void* d_x, int x_is_complex, const qmri_llr_params* p, int o1, int o2,
+                      void* d_out, double* sigma_max_out);
+/* Selects the LLR step as Step 2 of the PnP-ADMM loops (p == NULL: back to the network).  While set, qmri_pnp_admm, _dev, _batch, qmri_pnp_admm_mc,
+ * _mc_batch and _mc_dev compute v = LLR_tau(x + uold) -- of the complex x + uold with QMRI_DENOISER_COMPLEX, else of real(x + uold) as the
+ * reference's Step 2 -- and need no denoiser; the multi_level bit and noise_std are ignored (denoiser_type keeps its range 0..3).  ADMM iteration
+ * `it` (0-based) uses the offsets (0, 0) with shift = 0, else q = it mod b^2, o1 = q mod b, o2 = (q div b + q) mod b: every offset once per b^2
+ * iterations, both coordinates moving each iteration.  The gridded loop runs its unfused launch sequence; the solvers, the diagnostics and the
+ * stage timers work as before, the prox time goes to ms_denoiser.  b must divide N and M of the operator in force at the ADMM call, which
+ * otherwise returns QMRI_ERR_INVALID_ARG.  qmri_recon_batch* build their own contexts and are not affected.  Refusals (host only): the checks of
+ * qmri_llr_prox on tau, block and reserved, shift outside {0, 1}. */
+int qmri_set_llr(qmri_ctx* ctx, const qmri_llr_params* p);
+
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------------ */
 typedef struct {
     double ms_xupdate, ms_denoiser, ms_elementwise, ms_diag, ms_match;   /* hipEvent time per stage */

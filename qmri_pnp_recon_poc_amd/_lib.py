@@ -23,7 +23,7 @@ SYMBOLS = [
     "qmri_net_forward_dev", "qmri_denoiser_scheme", "qmri_pnp_admm", "qmri_pnp_admm_dev", "qmri_pnp_admm_batch", "qmri_set_dictionary", "qmri_dict_match",
     "qmri_dict_match_dev", "qmri_dict_match_xfit", "qmri_dict_match_xfit_dev", "qmri_set_dictionary_groups", "qmri_dict_group_assign", "qmri_dict_match_grouped",
     "qmri_dict_match_grouped_dev", "qmri_recon_batch", "qmri_recon_batch_mc",
-    "qmri_coil_compress", "qmri_coil_compress_dev", "qmri_coil_eig", "qmri_recon_batch_mc_cc", "qmri_coil_maps", "qmri_coil_maps_dev", "qmri_dict_compress", "qmri_dict_compress_dev", "qmri_dict_simulate", "qmri_dict_simulate_dev", "qmri_field_map_estimate", "qmri_field_map_estimate_dev", "qmri_profile_enable", "qmri_profile_get", "qmri_get_health",
+    "qmri_coil_compress", "qmri_coil_compress_dev", "qmri_coil_eig", "qmri_recon_batch_mc_cc", "qmri_coil_maps", "qmri_coil_maps_dev", "qmri_dict_compress", "qmri_dict_compress_dev", "qmri_dict_simulate", "qmri_dict_simulate_dev", "qmri_field_map_estimate", "qmri_field_map_estimate_dev", "qmri_llr_prox", "qmri_llr_prox_dev", "qmri_set_llr", "qmri_profile_enable", "qmri_profile_get", "qmri_get_health",
     "qmri_debug_lsqr_stamps", "qmri_debug_conv_stamps", "qmri_debug_lsqr_persist", "qmri_debug_dict_filter", "qmri_debug_conv_resident", "qmri_debug_dsvd_gram", "qmri_debug_epg_shift", "qmri_debug_knob",
     "qmri_onnx_read_unetres",
     "qmri_lrtv", "qmri_prox_tv", "qmri_norm_tv", "qmri_synthesize_tsmi", "qmri_synthesize_tsmi_complex",
@@ -110,6 +110,10 @@ class FieldmapParams(C.Structure):
 class FieldmapInfo(C.Structure):
     _fields_ = [("cost0", C.c_double), ("cost", C.c_double), ("f_min", C.c_double), ("f_max", C.c_double), ("iters", C.c_int32), ("reserved", C.c_int32),
                 ("unwrap_limit_hz", C.c_double)]
+
+
+class LlrParams(C.Structure):
+    _fields_ = [("tau", C.c_double), ("block", C.c_int32), ("shift", C.c_int32), ("reserved", C.c_int32 * 5)]
 
 
 class LrtvParams(C.Structure):
@@ -245,6 +249,9 @@ def lib() -> C.CDLL:
     L.qmri_debug_epg_shift.argtypes = [vp, i, i, vp, vp]
     L.qmri_field_map_estimate.argtypes = [vp, i, i, i, i, i, vp, dp, vp, C.POINTER(FieldmapParams), vp, vp, C.POINTER(FieldmapInfo)]
     L.qmri_field_map_estimate_dev.argtypes = [vp, i, i, i, i, i, vp, dp, vp, C.POINTER(FieldmapParams), vp, vp, C.POINTER(FieldmapInfo)]
+    L.qmri_llr_prox.argtypes = [vp, i, i, i, i, vp, i, C.POINTER(LlrParams), i, i, vp, dp]
+    L.qmri_llr_prox_dev.argtypes = [vp, i, i, i, i, vp, i, C.POINTER(LlrParams), i, i, vp, dp]
+    L.qmri_set_llr.argtypes = [vp, C.POINTER(LlrParams)]
     L.qmri_debug_knob.argtypes = [C.c_char_p, i]
     L.qmri_profile_enable.argtypes = [vp, i]
     L.qmri_profile_get.argtypes = [vp, C.POINTER(Profile), i]

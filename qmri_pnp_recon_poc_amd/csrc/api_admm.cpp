@@ -85,6 +85,23 @@ static int admm_net_fits(qmri_ctx* ctx, const qmri_admm_params* prm, int* multi_
     return QMRI_OK;
 }
 
+// What Step 2 needs before a loop starts.  With the LLR regulariser set (qmri_set_llr) no network is involved: denoiser_type
+// keeps its range, its multi_level bit is ignored, and the block side must divide the grid of the operator in force.
+static int admm_step_fits(qmri_ctx* ctx, const qmri_admm_params* prm, int* multi_out, bool* cpx_out) {
+    if (!ctx->llr.on) return admm_net_fits(ctx, prm, multi_out, cpx_out);
+    const OpHost& o = ctx->op;
+    QMRI_CHECK_ARG(ctx, prm->denoiser_type >= 0 && prm->denoiser_type <= (QMRI_DENOISER_COMPLEX | QMRI_DENOISER_MULTI_LEVEL),
+                   "denoiser_type must be 0 .. 3 (QMRI_DENOISER_MULTI_LEVEL | QMRI_DENOISER_COMPLEX)");
+    if (o.N % ctx->llr.block || o.M % ctx->llr.block || o.s > 16) {
+        qmri_set_error(ctx, "invalid argument: the LLR regulariser (block side %d, at most 16 channels) does not fit the operator (%d x %d x %d): the "
+                            "block side must divide both sides", ctx->llr.block, o.N, o.M, o.s);
+        return QMRI_ERR_INVALID_ARG;
+    }
+    *multi_out = 0;
+    *cpx_out = (prm->denoiser_type & QMRI_DENOISER_COMPLEX) != 0;
+    return QMRI_OK;
+}
+
 // The start of both loops (PnP_ADMM.m:86-90) on the context's v / u / z: v = x, uold = 0 and, with `z_now`, z = v - uold.  The gridded loop passes
 // z_now = false and makes z itself inside iteration 0, under the x-update's stage timer and never when iters = 0.
 static int admm_start(qmri_ctx* ctx, int B, const double2* d_x, bool z_now) {
@@ -119,10 +136,21 @@ static int admm_to_net(qmri_ctx* ctx, const DenoiserStep& d, int mm_nblk, bool m
 
 // The denoiser step as three launches (both loops; the gridded one's fused form folds the third into the next x-update): step 2, then step 3
 // (PnP_ADMM.m:138,144): v = I*range + min ; uold = uold + x - v ; z = v - uold with the partials of ||z||^2
-static int admm_denoiser_step(qmri_ctx* ctx, const DenoiserStep& d, bool copy_range_flag) {
+// With the LLR regulariser set, two launches: v = LLR_tau(x + uold) at the offsets of iteration `it`, then step 3 on v.
+static int admm_denoiser_step(qmri_ctx* ctx, const DenoiserStep& d, bool copy_range_flag, int it) {
     OpHost& o = ctx->op;
     NetPlan& net = ctx->net;
     const size_t plane = (size_t)o.N * o.M;
+    if (ctx->llr.on) {
+        LlrPlan pl = {o.N, o.M, o.s, ctx->llr.block, 0, 0, d.cpx ? 0 : 1, ctx->llr.tau};
+        llr_offsets(it, pl.block, ctx->llr.shift, &pl.o1, &pl.o2);
+        if (d.tm) d.tm->start();
+        QMRI_TRY(llr_prox_dev(ctx, pl, d.B, d.d_x, o.d_u, o.d_vv, nullptr, nullptr));
+        if (d.tm) { d.tm->stop(ctx->prof.ms_denoiser); d.tm->start(); }
+        QMRI_TRY(llr_dual_dev(ctx, d.B, plane * o.s, d.d_x, o.d_vv, o.d_u, o.d_z, o.ls.pz, o.ls.nblk_z));
+        if (d.tm) d.tm->stop(ctx->prof.ms_elementwise);
+        return QMRI_OK;
+    }
     QMRI_TRY(admm_to_net(ctx, d, o.ls.nblk_z, false, copy_range_flag));
     if (d.tm) d.tm->start();
     QMRI_TRY(ew_launch_unnormalise_dual(ctx, d.B, plane * o.s, (int)plane, o.N, net.out32, net.in32, net.desc.residual_noise, o.d_norm, d.d_x, o.d_u,
@@ -145,14 +173,14 @@ static int mc_require(qmri_ctx* ctx, int nslices, int ncoil, const void* maps, c
 }
 static int mc_admm_check(qmri_ctx* ctx, const qmri_admm_params* prm) {
     const NetPlan& net = ctx->net;
-    if (!net.ready) { qmri_set_error(ctx, "denoiser not set: call qmri_set_denoiser first"); return QMRI_ERR_STATE; }
+    if (!net.ready && !ctx->llr.on) { qmri_set_error(ctx, "denoiser not set: call qmri_set_denoiser first"); return QMRI_ERR_STATE; }
     QMRI_CHECK_ARG(ctx, prm, "params must not be NULL");
     QMRI_TRY(toep_check_solver(ctx, prm->solver));            // (QMRI_SOLVER_TOEPLITZ: a trajectory operator only)
     QMRI_CHECK_ARG(ctx, prm->iters >= 0 && prm->gamma > 0 && prm->cg_maxit >= 0 && (prm->solver == QMRI_SOLVER_LSQR || prm->solver == QMRI_SOLVER_TOEPLITZ),
                    "iters >= 0, gamma > 0, cg_maxit >= 0, LSQR solver required");
     int multi = 0;
     bool cpx = false;
-    return admm_net_fits(ctx, prm, &multi, &cpx);
+    return admm_step_fits(ctx, prm, &multi, &cpx);
 }
 
 // PnP_ADMM.m:76-146 for B <= max_batch slices, all on the device (d_x0 NULL: x = A_mc' y as :84; returns x as :148).  When the network's range guard
@@ -160,7 +188,8 @@ static int mc_admm_check(qmri_ctx* ctx, const qmri_admm_params* prm) {
 static int mc_admm_group(qmri_ctx* ctx, int B, int ncoil, const double2* d_maps, const double2* d_y, const qmri_admm_params* prm, const double2* d_x0,
                          double2* d_x, int32_t* li_out, int li_stride) {
     OpHost& o = ctx->op;
-    const int multi = (prm->denoiser_type & QMRI_DENOISER_MULTI_LEVEL) ? 1 : 0;       // (checked by mc_admm_check)
+    const bool llr = ctx->llr.on;                                                      // (no network: nothing can trip, nothing is waited for)
+    const int multi = (!llr && (prm->denoiser_type & QMRI_DENOISER_MULTI_LEVEL)) ? 1 : 0;   // (checked by mc_admm_check)
     const bool cpx = (prm->denoiser_type & QMRI_DENOISER_COMPLEX) != 0;
     const size_t n = (size_t)o.N * o.M * o.s;
     std::vector<int32_t> li((size_t)B);
@@ -172,7 +201,8 @@ static int mc_admm_group(qmri_ctx* ctx, int B, int ncoil, const double2* d_maps,
         for (int it = 0; it < prm->iters; ++it) {
             QMRI_TRY(mc_xupdate_dev(ctx, prm->solver, B, ncoil, d_maps, d_y, o.d_z, prm->gamma, prm->cg_tol, prm->cg_maxit, d_x, li.data(), nullptr));   // :102
             if (li_out) for (int b = 0; b < B; ++b) li_out[(size_t)b * li_stride + it] = li[b];
-            QMRI_TRY(admm_denoiser_step(ctx, {B, prm, multi, cpx, d_x, nullptr}, false));                                                           // :115-144
+            QMRI_TRY(admm_denoiser_step(ctx, {B, prm, multi, cpx, d_x, nullptr}, false, it));                                                       // :115-144
+            if (llr) continue;
             QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
             QMRI_TRY(net_range_tripped(ctx, again));              // (f16 range / hand-off guards: the network is re-packed or the form switched; start again)
             if (again) break;
@@ -248,14 +278,15 @@ static int pnp_admm_dev_impl(qmri_ctx* ctx, int nslices, const void* d_y, const 
     OpHost& o = ctx->op;
     NetPlan& net = ctx->net;
     if (!o.ready) { qmri_set_error(ctx, "operator not set: call qmri_set_operator first"); return QMRI_ERR_STATE; }
-    if (!net.ready) { qmri_set_error(ctx, "denoiser not set: call qmri_set_denoiser first"); return QMRI_ERR_STATE; }
+    const bool llr = ctx->llr.on;                          // Step 2 is the LLR prox: no network, so no fused launches, no range guard and no repeat
+    if (!net.ready && !llr) { qmri_set_error(ctx, "denoiser not set: call qmri_set_denoiser first"); return QMRI_ERR_STATE; }
     QMRI_CHECK_ARG(ctx, d_y && prm && d_x_out, "y / params / x_out must not be NULL");
     const int B = nslices;
-    QMRI_CHECK_ARG(ctx, B >= 1 && B <= o.maxB && B <= net.maxB, "nslices exceeds max_batch of the operator or the denoiser");
+    QMRI_CHECK_ARG(ctx, B >= 1 && B <= o.maxB && (llr || B <= net.maxB), "nslices exceeds max_batch of the operator or the denoiser");
     QMRI_CHECK_ARG(ctx, prm->iters >= 0 && prm->gamma > 0 && prm->cg_maxit >= 0, "iters >= 0, gamma > 0, cg_maxit >= 0 required");
     int multi = 0;
     bool cpx = false;
-    QMRI_TRY(admm_net_fits(ctx, prm, &multi, &cpx));
+    QMRI_TRY(admm_step_fits(ctx, prm, &multi, &cpx));
     const OpDev op = qmri_opdev(ctx);
     const size_t plane = (size_t)o.N * o.M, n = plane * o.s, nb = (size_t)B * n * sizeof(double2);
     const double2* y = (const double2*)d_y;
@@ -296,7 +327,7 @@ static int pnp_admm_dev_impl(qmri_ctx* ctx, int nslices, const void* d_y, const 
     // Round 4: the small launches around the network are folded into their neighbours (LSQR solver; knob fuse_ew = 0 restores the separate kernels
     // for A/Bs): un-normalise + dual update + z + the h-pass of z's transform + the forward pass's |output| report = ONE launch (k_dual_fwd_h);
     // the w-pass of z rides in the solve's first kernel (k_ks_init_a<FWDW>); the min / max of real(x + u) come out of the solve's last h-pass.
-    const bool fused = qmri_knob(K_FUSE_EW) != 0 && prm->solver == QMRI_SOLVER_LSQR;
+    const bool fused = qmri_knob(K_FUSE_EW) != 0 && prm->solver == QMRI_SOLVER_LSQR && !llr;
     const int hb = dc_hpass_blocks(op);
     bool z_in_tmp = false;                                 // o.d_tmp holds the h-pass of z (and ls.pz hb partial sums per slice)
     struct DeferGuard { NetPlan& n; ~DeferGuard() { n.act_defer = false; n.act_pending_valid = false; } } defer_guard{net};
@@ -318,7 +349,7 @@ static int pnp_admm_dev_impl(qmri_ctx* ctx, int nslices, const void* d_y, const 
             // The range guard of earlier forwards is on the host (pinned words written by k_act_check).  After a wait inside qmri_lsqr_run (the
             // two-launch iteration) it is current up to the previous iteration; without one it is whatever has arrived.  A tripped guard ends
             // this attempt at once instead of after all iterations.
-            if (it > 0 && net.sp6 == 2 && host_range_tripped(net)) { range_trip = true; tm.stop(ctx->prof.ms_xupdate); break; }
+            if (it > 0 && !llr && net.sp6 == 2 && host_range_tripped(net)) { range_trip = true; tm.stop(ctx->prof.ms_xupdate); break; }
         } else {
             QMRI_TRY(dc_launch_direct(ctx, op, B, o.d_z, o.d_chat, prm->gamma, o.d_tmp, o.d_x));
             if (lsqr_iters_out) for (int b = 0; b < B; ++b) lsqr_iters_out[(size_t)b * prm->iters + it] = 0;
@@ -331,7 +362,7 @@ static int pnp_admm_dev_impl(qmri_ctx* ctx, int nslices, const void* d_y, const 
             tm.stop(ctx->prof.ms_diag);
         }
         // Steps 2 and 3 (PnP_ADMM.m:115-144): the denoiser on v = real(x+uold), then uold = uold + x - v
-        if (!fused) QMRI_TRY(admm_denoiser_step(ctx, step, true));
+        if (!fused) QMRI_TRY(admm_denoiser_step(ctx, step, !llr, it));
         else {
             QMRI_TRY(admm_to_net(ctx, step, hb, true, true));
             tm.start();
@@ -374,7 +405,7 @@ static int pnp_admm_dev_impl(qmri_ctx* ctx, int nslices, const void* d_y, const 
         }
     }
     // f16 range guard: the network now runs on the bf16 scheme; the inputs are untouched (d_x_out must not alias d_x0), run again
-    if (prm->iters > 0) QMRI_TRY(net_range_tripped(ctx, *repeat));
+    if (prm->iters > 0 && !llr) QMRI_TRY(net_range_tripped(ctx, *repeat));
     return QMRI_OK;
 }
 
@@ -412,7 +443,7 @@ extern "C" int qmri_pnp_admm_mc_dev(qmri_ctx* ctx, int nslices, int ncoil, const
     QMRI_TRY(mc_require(ctx, nslices, ncoil, d_maps, d_y));
     QMRI_TRY(mc_admm_check(ctx, prm));
     QMRI_CHECK_ARG(ctx, d_x_out && d_x_out != d_x0, "x_out must not be NULL and must not alias x0");
-    QMRI_CHECK_ARG(ctx, nslices <= ctx->op.maxB && nslices <= ctx->net.maxB, "nslices exceeds max_batch of the operator or the denoiser");
+    QMRI_CHECK_ARG(ctx, nslices <= ctx->op.maxB && (ctx->llr.on || nslices <= ctx->net.maxB), "nslices exceeds max_batch of the operator or the denoiser");
     QMRI_TRY(mc_admm_group(ctx, nslices, ncoil, (const double2*)d_maps, (const double2*)d_y, prm, (const double2*)d_x0, (double2*)d_x_out,
                            lsqr_iters_out, prm->iters));
     QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -428,7 +459,7 @@ extern "C" int qmri_pnp_admm_mc_batch(qmri_ctx* ctx, int nslices, int slices_per
     QMRI_CHECK_ARG(ctx, x_out && slices_per_launch >= 1, "x_out must not be NULL, slices_per_launch >= 1");
     OpHost& o = ctx->op;
     const int spl = std::min(slices_per_launch, nslices);
-    QMRI_CHECK_ARG(ctx, spl <= o.maxB && spl <= ctx->net.maxB, "slices_per_launch exceeds max_batch of the operator or the denoiser");
+    QMRI_CHECK_ARG(ctx, spl <= o.maxB && (ctx->llr.on || spl <= ctx->net.maxB), "slices_per_launch exceeds max_batch of the operator or the denoiser");
     const size_t plane = (size_t)o.N * o.M, n = plane * o.s;
     for (int b0 = 0; b0 < nslices; b0 += spl) {            // (the first run is the largest: the staging is sized once)
         const int B = std::min(spl, nslices - b0);
@@ -506,13 +537,13 @@ extern "C" int qmri_pnp_admm_batch(qmri_ctx* ctx, int nslices, int slices_per_la
     QMRI_HIP(ctx, hipSetDevice(ctx->device));
     OpHost& o = ctx->op;
     if (!o.ready) { qmri_set_error(ctx, "operator not set: call qmri_set_operator first"); return QMRI_ERR_STATE; }
-    if (!ctx->net.ready) { qmri_set_error(ctx, "denoiser not set: call qmri_set_denoiser first"); return QMRI_ERR_STATE; }
+    if (!ctx->net.ready && !ctx->llr.on) { qmri_set_error(ctx, "denoiser not set: call qmri_set_denoiser first"); return QMRI_ERR_STATE; }
     QMRI_CHECK_ARG(ctx, y && p && x_out && nslices >= 1 && slices_per_launch >= 1, "y / params / x_out must not be NULL, nslices and slices_per_launch >= 1");
     if (std::min(slices_per_launch, nslices) > 1)
         QMRI_TRY(nufft_check_gridded(ctx, "qmri_pnp_admm_batch with more than one slice per launch",
                                      "use slices_per_launch = 1, or qmri_pnp_admm_mc_batch with one unit coil per slice"));
     const int spl = std::min(slices_per_launch, nslices);
-    QMRI_CHECK_ARG(ctx, spl <= o.maxB && spl <= ctx->net.maxB, "slices_per_launch exceeds max_batch of the operator or the denoiser");
+    QMRI_CHECK_ARG(ctx, spl <= o.maxB && (ctx->llr.on || spl <= ctx->net.maxB), "slices_per_launch exceeds max_batch of the operator or the denoiser");
     const size_t n = (size_t)o.N * o.M * o.s, m = (size_t)o.m, it = (size_t)std::max(p->iters, 0);
     DevBuf<double2> dY, dX, dX0, dGT;
     auto fail = [&](const char* what) { qmri_set_error(ctx, "%s failed in qmri_pnp_admm_batch", what); return QMRI_ERR_HIP; };

@@ -373,6 +373,17 @@ int fmap_halo();                         // h: iterations per fused launch
 int fmap_estimate_dev(qmri_ctx* ctx, const FmapPlan& pl, const double2* d_Y, const double* d_f_init /* or NULL */, double* d_f_out,
                       double* d_trust_out /* or NULL */, qmri_fieldmap_info* info /* host, or NULL */);
 
+// locally low-rank proximal step (llr_kernels.hip, api_llr.cpp).  All d_ pointers are device pointers; the launches go to
+// ctx->stream and are not waited for.
+struct LlrPlan { int N, M, s, block, o1, o2, real; double tau; };
+struct LlrState { bool on = false; double tau = 0.0; int block = 8, shift = 0; };    // qmri_set_llr
+void llr_offsets(int it, int block, int shift, int* o1, int* o2);                     // the offsets of ADMM iteration `it` (0-based)
+// d_out [B][s][M][N] = LLR_tau(d_x + d_u) (d_u NULL: of d_x; real: of the real part, imaginary part 0); d_out may be d_x.  d_bsmax (nullable):
+// [B][blocks per slice] sigma_max per block, and with it d_smax (nullable): [B] the slice's maximum (a second small launch)
+int llr_prox_dev(qmri_ctx* ctx, const LlrPlan& pl, int B, const double2* d_x, const double2* d_u, double2* d_out, double* d_bsmax, double* d_smax);
+// uold += x - v; z = v - uold; pz [B][nblk_z] partial sums of ||z||^2 (n elements per slice)
+int llr_dual_dev(qmri_ctx* ctx, int B, size_t n, const double2* d_x, const double2* d_v, double2* d_u, double2* d_z, double* d_pz, int nblk_z);
+
 // ---------------------------------------------------------------------------------------------------
 // trajectory (NUFFT) operator (nufft_kernels.hip, api_nufft.cpp).  Planned once on the host per qmri_set_operator_nufft:
 // samples sorted by the 16 x 16 tile of the 2N x 2M oversampled grid that holds their position ("bins"), and for the output-driven spreading the
@@ -595,6 +606,8 @@ struct qmri_ctx {
     size_t marks_n = 0;
     double last_call_ms[4] = {0, 0, 0, 0};   // stage times of the most recent qmri_pnp_admm_dev call (levels 1 and 3)
     double last_call_wall_ms = 0;            // ... its host wall clock, entry to return (always)
+    LlrState llr;                       // the regulariser of the PnP-ADMM loops' Step 2 while set (qmri_set_llr), else the network
+    bool llr_lds_attr[3] = {false, false, false};   // large dynamic LDS allowed for k_llr_prox<4 | 8 | 16>
     int conv_ncu = 0;                   // f32-MFMA conv kernels (conv_kernels.hip): CU count and resident workgroups per CU by (kind, MT)
     int conv_occ[4][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};
 };

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import AdmmParams, CcParams, CsmInfo, CsmParams, DcfInfo, DcfParams, DsvdInfo, DsvdParams, EpgParams, FieldmapInfo, FieldmapParams, LrtvInfo, LrtvParams, NetDesc, NufftParams, OffresInfo, OffresNormalInfo, OffresNormalParams, OffresParams, Profile
+from ._lib import AdmmParams, CcParams, CsmInfo, CsmParams, DcfInfo, DcfParams, DsvdInfo, DsvdParams, EpgParams, FieldmapInfo, FieldmapParams, LlrParams, LrtvInfo, LrtvParams, NetDesc, NufftParams, OffresInfo, OffresNormalInfo, OffresNormalParams, OffresParams, Profile
 
 ARCH_UNETRES, ARCH_SEQ_CONV = 0, 1
 SOLVER_LSQR, SOLVER_DIRECT = 0, 1
@@ -772,6 +772,48 @@ class Engine:
         self._check(self.L.qmri_denoise(self.h, xb.ctypes.data_as(C.POINTER(C.c_double)), H, W, Cc, B, out.ctypes.data_as(C.POINTER(C.c_double))))
         out = out.reshape((H, W, out_nc, B), order="F")
         return out[..., 0] if squeeze else out
+
+    # -- locally low-rank regulariser ------------------------------------------
+    def llr_prox(self, x, tau, block=8, offset=(0, 0), real=False):
+        """The locally low-rank proximal step (qmri_llr_prox): the singular values of every block x block patch of x are soft-thresholded by
+        tau.  x: [N, M, s] or a stack [S, N, M, s], N and M multiples of block (4, 8 or 16), s <= 16; offset = (o1, o2) shifts the blocks
+        (circular wrap); real: work on real(x).  Needs no operator.  Returns (out complex128 like x, sigma_max: a float, or [S] for a stack)."""
+        x = np.asarray(x)
+        one = x.ndim == 3
+        xs = x[None] if one else x
+        if xs.ndim != 4:
+            raise ValueError("x must be [N, M, s] or [slices, N, M, s]")
+        S, N, M, s = xs.shape
+        p = LlrParams(float(tau), int(block), 0)
+        if real:
+            xb = np.concatenate([np.ascontiguousarray(np.asarray(xs[b].real, np.float64).ravel(order="F")) for b in range(S)])
+        else:
+            xb = np.concatenate([_cbuf(xs[b]) for b in range(S)])
+        out = np.empty(S * N * M * s, np.complex128)
+        sm = np.zeros(S, np.float64)
+        self._check(self.L.qmri_llr_prox(self.h, N, M, s, S, _vp(xb), 0 if real else 1, C.byref(p), int(offset[0]), int(offset[1]), _vp(out),
+                                         sm.ctypes.data_as(C.POINTER(C.c_double))))
+        n = N * M * s
+        out = np.stack([out[b * n:(b + 1) * n].reshape((N, M, s), order="F") for b in range(S)])
+        return (out[0], float(sm[0])) if one else (out, sm)
+
+    def llr_prox_dev(self, d_x: int, dims, tau, d_out: int, block=8, offset=(0, 0), real=False, want_sigma_max=True):
+        """qmri_llr_prox_dev on device arrays (complex fp64, [slice][c][n2][n1]); dims = (N, M, s, slices); d_out may be d_x.  Returns sigma_max [slices]."""
+        N, M, s, S = (int(v) for v in dims)
+        p = LlrParams(float(tau), int(block), 0)
+        sm = np.zeros(S, np.float64)
+        self._check(self.L.qmri_llr_prox_dev(self.h, N, M, s, S, C.c_void_p(d_x), 0 if real else 1, C.byref(p), int(offset[0]), int(offset[1]),
+                                             C.c_void_p(d_out), sm.ctypes.data_as(C.POINTER(C.c_double)) if want_sigma_max else None))
+        return sm
+
+    def set_llr(self, tau, block=8, shift=True):
+        """Step 2 of every pnp_admm* call of this engine becomes v = LLR_tau(x + uold) (qmri_set_llr) until clear_llr: no denoiser is needed.
+        tsmi_domain="complex" thresholds the complex x + uold, "real" its real part.  shift: the block offsets cycle with the iteration."""
+        p = LlrParams(float(tau), int(block), int(bool(shift)))
+        self._check(self.L.qmri_set_llr(self.h, C.byref(p)))
+
+    def clear_llr(self):
+        self._check(self.L.qmri_set_llr(self.h, None))
 
     # -- PnP-ADMM ------------------------------------------------------------------------------------
     def pnp_admm(self, y, gamma=0.05, iters=100, cg_tol=1e-4, cg_maxit=100, solver="lsqr", multi_level=False,

@@ -287,7 +287,8 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
                 spiral_sampling_curve=771, epi_sampling_rate=1 / 65, measurements_type="noisy", measurements_noise=30,
                 denoiser_type="single_level", noise_map_std=0.01, residual_noise=False, iters=100, seed=0, Y=None, device=0,
                 net_arch=None, lrtv_iters=None, tsmi_domain="real", solver="lsqr", b1_map=None, density_compensation=False,
-                field_map=None, readout_s=None, field_normal=None, field_echoes=None, field_echo_times=None):
+                field_map=None, readout_s=None, field_normal=None, field_echoes=None, field_echo_times=None,
+                regulariser="net", llr_tau=None, llr_tau_rel=0.02, llr_block=8):
     """main_recon_tsmis_FFT.m:216-374 on already loaded (and cropped) arrays.
 
     dictionary  dict(V, D, normD, lut) (load_dictionary);  X0  N x M x s ground-truth TSMI;  qmap0  N x M x 3
@@ -309,11 +310,18 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
                 unchanged.  The result gains field_map (the estimate) and field_map_info.
     field_normal  with field_map and solver="toeplitz": True, or a dict with nseg / tol, builds the field-aware Toeplitz normal operator before the
                 loop (Engine.prepare_normal_field); None or False (default): solver="toeplitz" with a field_map is refused
+    regulariser   of PnP_ADMM: "net" (default) is the denoiser of `weights`; "llr" the locally low-rank proximal step, which
+                needs no weights and works on every subsampling pattern: llr_block x llr_block patches (4, 8 or 16, dividing N and M), threshold
+                llr_tau, or with None llr_tau_rel times sigma_max of the start image.  The result gains llr_tau, the threshold used.
     Returns dict(X, qmap (N x M x 3: T1, T2, PD), Y, metrics, foreground_mask); with b1_map also grp (N x M, the 1-based b1 group, 0 = unmatched);
     with field_normal also field_normal_info (what prepare_normal_field reported).
     """
     from . import reference_api as R
     net_arch = dict(net_arch or {})
+    if regulariser not in ("net", "llr"):
+        raise ValueError(f'regulariser must be "net" or "llr", not {regulariser!r}')
+    if regulariser == "llr" and recon_method != "PnP_ADMM":
+        raise ValueError('regulariser="llr" goes with recon_method="PnP_ADMM"')
     from .engine import denoiser_type as _dtype
     _dtype(denoiser_type == "multi_level", tsmi_domain)            # (checks tsmi_domain)
     X0 = np.asarray(X0)
@@ -373,10 +381,12 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
         Yc = np.asarray(Y, dtype=np.complex128)
         X = F._engine.adjoint(Yc, weighted=True) if density_compensation else F.adjoint(Yc)
     elif recon_method == "PnP_ADMM":                                                 # :284-293
-        if weights is None:
+        if weights is None and regulariser != "llr":
             raise ValueError("PnP_ADMM needs the denoiser weights")
         arch = {}
-        if isinstance(weights, (str, bytes)) or hasattr(weights, "__fspath__"):
+        if regulariser == "llr":
+            pass
+        elif isinstance(weights, (str, bytes)) or hasattr(weights, "__fspath__"):
             from .weights import load_denoiser_weights
             weights, arch = load_denoiser_weights(weights)
             want = (2 * s if tsmi_domain == "complex" else 10) + (0 if denoiser_type == "single_level" else 1)
@@ -384,8 +394,11 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
                 raise ValueError(f"the weight file takes {arch['in_nc']} input channels, denoiser type {denoiser_type} "
                                  f"({tsmi_domain} TSMIs) needs {want}")
         out_nc = 2 * s if tsmi_domain == "complex" else s
-        net = R.make_net(weights, denoiser_type, residual_noise, H=N, W=M, out_nc=out_nc, device=device, tsmi_domain=tsmi_domain,
-                         **{**net_arch, **({"nc": arch["nc"], "nb": arch["nb"]} if arch else {})})
+        if regulariser == "llr":
+            net = R.make_llr(F, tau=llr_tau, tau_rel=llr_tau_rel, block=llr_block)
+        else:
+            net = R.make_net(weights, denoiser_type, residual_noise, H=N, W=M, out_nc=out_nc, device=device, tsmi_domain=tsmi_domain,
+                             **{**net_arch, **({"nc": arch["nc"], "nb": arch["nb"]} if arch else {})})
         param = {"eta": 20, "sigma_squared": 1, "gamma": 1 / 20, "iter": iters, "cg_tol": 1e-4, "F": F, "gt_tsmi": X0,
                  "X0": None if density_compensation else F.adjoint(Y), "net": net, "denoiser_type": denoiser_type, "tsmi_domain": tsmi_domain,
                  "noise_map": R.build_noise_map(noise_map_std, N, M), "solver": solver}   # :166-171
@@ -396,6 +409,8 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
         X = R.PnP_ADMM(np.asarray(Y, dtype=np.complex128), param)
         if field_normal is not None:
             extra_fn = {"field_normal_info": R.PnP_ADMM.last_field_normal}
+        if regulariser == "llr":
+            extra_fn["llr_tau"] = net.tau
     elif recon_method == "LRTV":                                                     # :273-282
         param = {"K": 4e-5, "iter": 200 if lrtv_iters is None else int(lrtv_iters), "step": X0.size / np.asarray(Y).size, "tol": 1e-4,
                  "backtrack": 1, "usegpu": 0}

@@ -32,6 +32,8 @@
 //   * 'coil_maps' estimates coil sensitivity maps from calibration data (qmri_coil_maps; extension).
 //   * 'dict_compress' compresses a simulated dictionary to its SVD subspace (qmri_dict_compress; extension); it needs no plan.
 //   * 'dict_simulate' simulates the fingerprints of a FISP-MRF sequence by extended phase graphs (qmri_dict_simulate; extension); it needs no plan.
+//   * 'set_llr' / 'clear_llr' select the locally low-rank proximal step as Step 2 of 'pnp_admm' (qmri_set_llr; extension), which
+//     then needs no denoiser; 'llr_prox' is the step alone (qmri_llr_prox).
 //   * 'field_map_estimate' estimates the field map that 'set_field_map' takes from multi-echo images (qmri_field_map_estimate; extension, DESIGN.md
 //     section 24); it needs no plan.
 // tests/cpp/mex_mock.cpp is a small stand-in for the MATLAB runtime's C API under which this file is compiled, LINKED against libqmri.so and
@@ -57,6 +59,7 @@ struct DictSpec { mxArray* D = nullptr; mxArray* normD = nullptr; mxArray* lut =
 static OperatorSpec g_op;
 static DenoiserSpec g_net;
 static DictSpec g_dict;
+static bool g_llr = false;                             // 'set_llr' is in force: 'pnp_admm' needs no denoiser
 static const int DEFAULT_SLICES_PER_LAUNCH = 15;       // what a measurement matrix grows the plans to (the batched kernels' design point)
 
 static void drop(mxArray*& a) { if (a) { mxDestroyArray(a); a = nullptr; } }
@@ -67,6 +70,7 @@ static void cleanup() {
     drop(g_op.V); drop(g_op.fp); drop(g_op.kidx); drop(g_op.omega); g_op = OperatorSpec();
     drop(g_net.w); g_net = DenoiserSpec();
     drop(g_dict.D); drop(g_dict.normD); drop(g_dict.lut);
+    g_llr = false;
 }
 
 static void check(int st) {
@@ -453,6 +457,50 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
             }
         }
         if (trust) plhs[2] = trust;
+    } else if (c == "set_llr") {                     // qmri_mex('set_llr', tau [, block [, shift]]): Step 2 of 'pnp_admm' becomes the locally low-rank prox
+        // extension (no reference counterpart; qmri_set_llr): tau >= 0 in the units of the TSMI, block 4, 8 (default) or 16,
+        // shift 1 (default): the block offsets cycle with the ADMM iteration.  No denoiser is needed while it is set.
+        need(nrhs, 2, "qmri_mex('set_llr', tau [, block, shift])");
+        want(mxIsDouble(prhs[1]) && !mxIsComplex(prhs[1]) && mxGetNumberOfElements(prhs[1]) == 1, "qmri:set_llr:tau", "tau must be a real double scalar");
+        qmri_llr_params lp{};
+        lp.tau = mxGetScalar(prhs[1]);
+        want(std::isfinite(lp.tau) && lp.tau >= 0.0, "qmri:set_llr:tau", "tau must be finite and >= 0");
+        lp.block = nrhs > 2 ? int_arg(prhs[2], 4, 16, "qmri:set_llr:block", "block must be 4, 8 or 16") : 8;
+        want(lp.block == 4 || lp.block == 8 || lp.block == 16, "qmri:set_llr:block", "block must be 4, 8 or 16");
+        lp.shift = nrhs > 3 ? int_arg(prhs[3], 0, 1, "qmri:set_llr:shift", "shift must be 0 or 1") : 1;
+        check(qmri_set_llr(ctx(), &lp));
+        g_llr = true;
+    } else if (c == "clear_llr") {                   // qmri_mex('clear_llr'): Step 2 of 'pnp_admm' is the network again
+        check(qmri_set_llr(ctx(), nullptr));
+        g_llr = false;
+    } else if (c == "llr_prox") {                    // [out, smax] = qmri_mex('llr_prox', x, tau [, block [, o1, o2]])
+        // the locally low-rank proximal step alone (qmri_llr_prox).  x: double N x M x s (x S), complex, or real (real mode: the output's imaginary
+        // part is exactly 0); N and M multiples of block, s <= 16.  out: complex like x; smax: 1 x S, the largest singular value of each slice's blocks.
+        const char* usage = "[out, smax] = qmri_mex('llr_prox', x, tau [, block, o1, o2])";
+        need(nrhs, 3, usage);
+        want(nlhs <= 2 && nrhs != 5, "qmri:usage", usage);
+        want(mxIsDouble(prhs[1]), "qmri:llr_prox:type", "x must be a double array (complex, or real for real mode)");
+        want(mxIsDouble(prhs[2]) && !mxIsComplex(prhs[2]) && mxGetNumberOfElements(prhs[2]) == 1, "qmri:llr_prox:tau", "tau must be a real double scalar");
+        qmri_llr_params lp{};
+        lp.tau = mxGetScalar(prhs[2]);
+        want(std::isfinite(lp.tau) && lp.tau >= 0.0, "qmri:llr_prox:tau", "tau must be finite and >= 0");
+        lp.block = nrhs > 3 ? int_arg(prhs[3], 4, 16, "qmri:llr_prox:block", "block must be 4, 8 or 16") : 8;
+        want(lp.block == 4 || lp.block == 8 || lp.block == 16, "qmri:llr_prox:block", "block must be 4, 8 or 16");
+        const int o1 = nrhs > 5 ? int_arg(prhs[4], 0, lp.block - 1, "qmri:llr_prox:offset", "o1 and o2 must be integers in 0 .. block - 1") : 0;
+        const int o2 = nrhs > 5 ? int_arg(prhs[5], 0, lp.block - 1, "qmri:llr_prox:offset", "o1 and o2 must be integers in 0 .. block - 1") : 0;
+        const size_t nd = mxGetNumberOfDimensions(prhs[1]);
+        const mwSize* xd = mxGetDimensions(prhs[1]);
+        want(nd >= 2 && nd <= 4, "qmri:llr_prox:size", "x must be N x M x s or N x M x s x S");
+        const size_t N = xd[0], M = xd[1], s = nd > 2 ? xd[2] : 1, S = nd > 3 ? xd[3] : 1;
+        want(N >= 1 && M >= 1 && N <= 16384 && M <= 16384 && N % lp.block == 0 && M % lp.block == 0, "qmri:llr_prox:size", "N and M must be positive multiples of block");
+        want(s >= 1 && s <= 16 && S >= 1 && S <= 65536, "qmri:llr_prox:size", "x must hold 1 <= s <= 16 channels and at least one slice");
+        const mwSize od[4] = {(mwSize)N, (mwSize)M, (mwSize)s, (mwSize)S};
+        plhs[0] = mxCreateNumericArray(S > 1 ? 4 : 3, od, mxDOUBLE_CLASS, mxCOMPLEX);
+        mxArray* sm = mxCreateDoubleMatrix(1, (mwSize)S, mxREAL);
+        const bool cpx = mxIsComplex(prhs[1]);
+        check(qmri_llr_prox(ctx(), (int)N, (int)M, (int)s, (int)S, cpx ? (const void*)mxGetComplexDoubles(prhs[1]) : (const void*)mxGetDoubles(prhs[1]), cpx ? 1 : 0,
+                            &lp, o1, o2, mxGetComplexDoubles(plhs[0]), mxGetDoubles(sm)));
+        if (nlhs > 1) plhs[1] = sm; else mxDestroyArray(sm);
     } else if (c == "prepare_normal_fm") {           // info = qmri_mex('prepare_normal_fm' [, nseg [, tol]]): the Toeplitz normal operator of the attached map
         const qmri_offres_normal_params np = normal_fm_params(nrhs > 1 ? prhs[1] : nullptr, nrhs > 2 ? prhs[2] : nullptr, "qmri:prepare_normal_fm:nseg",
                                                               "qmri:prepare_normal_fm:tol");     // (the argument checks come first: they need no operator)
@@ -524,7 +572,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         const double* d = mxGetDoubles(prhs[5]);
         const size_t S = mxGetN(prhs[1]), m = mxGetM(prhs[1]), n = dims_numel(prhs[5]);
         want(is_cdouble(prhs[1]) && S >= 1 && m == operator_m(), "qmri:pnp_admm:size", "y must be complex double, one column of m samples per slice");
-        want(g_net.w != nullptr, "qmri:state", "no denoiser: call qmri_mex('set_denoiser' | 'load_onnx', ...) (qmri_make_net) first");
+        want(g_net.w != nullptr || g_llr, "qmri:state", "no denoiser: call qmri_mex('set_denoiser' | 'load_onnx', ...) (qmri_make_net) or qmri_mex('set_llr', ...) (qmri_make_llr) first");
         want((mxIsEmpty(prhs[3]) || is_cdouble(prhs[3])) && (mxIsEmpty(prhs[4]) || is_cdouble(prhs[4])), "qmri:pnp_admm:type", "X0 and gt_tsmi must be complex double or empty");
         const int it = p.iters > 0 ? p.iters : 1;
         const mwSize dims[4] = {(mwSize)d[0], (mwSize)d[1], (mwSize)d[2], (mwSize)S};

@@ -7,6 +7,7 @@ pipeline, so this Python mirror is the executable counterpart of the `.m` wrappe
     P   = setup_subsampling_spiral_exact(N, M, S, V)        # the same spiral before its rounding (a trajectory)
     F   = make_F(P)                                         # F.forward / F.adjoint, main_recon_tsmis_FFT.m:228-229
     net = make_net(weights, denoiser_type, residual_noise)  # param.net, main_recon_tsmis_FFT.m:164
+    net = make_llr(F, tau, tau_rel, block, shift)           # param.net without a network: the locally low-rank regulariser
     x   = PnP_ADMM(y, param)                                # PnP_ADMM.m:1, param = dict with the reference's field names
     out = mrf_dtm_cpu(dict, data, par)                      # mrf_dtm_cpu.m:1 (name kept; it runs on the GPU)
     x   = FISTA_deep(data, param)                           # LRTV option, FISTA_deep.m:1 (+ TV_operator, prox_tv, norm_tv)
@@ -137,6 +138,34 @@ def make_net(weights, denoiser_type="single_level", residual_noise=False, H=224,
     return net
 
 
+def make_llr(F, tau=None, tau_rel=0.02, block=8, shift=True):
+    """param.net without a network (an extension): Step 2 of PnP_ADMM becomes the locally low-rank proximal step
+    v = LLR_tau(x + uold) on block x block patches (Engine.set_llr), which needs no trained weights and fits every operator of make_F.
+    tau: the threshold on the singular values in the units of the TSMI; None: tau_rel times sigma_max of the loop's start image (Engine.llr_prox
+    with tau = 0 gives sigma_max).  shift: the block offsets cycle with the iteration.  The threshold a PnP_ADMM call used is .tau afterwards."""
+    if not hasattr(F, "_engine"):
+        raise TypeError("F must come from make_F of this package")
+    if block not in (4, 8, 16):
+        raise ValueError("block must be 4, 8 or 16")
+    if tau is not None and not (float(tau) >= 0 and np.isfinite(tau)):
+        raise ValueError("tau must be finite and >= 0")
+    if tau is None and not (float(tau_rel) >= 0 and np.isfinite(tau_rel)):
+        raise ValueError("tau_rel must be finite and >= 0")
+    return SimpleNamespace(_engine=F._engine, _llr=True, _denoiser_type="single_level", _tsmi_domain="real", _residual_noise=False,
+                           tau=None if tau is None else float(tau), tau_given=None if tau is None else float(tau), tau_rel=float(tau_rel),
+                           block=int(block), shift=bool(shift), sigma_max=None)
+
+
+def _llr_arm(F, net, param, y, x0, tsmi_domain):
+    """Sets the engine's LLR step for one PnP_ADMM call; the threshold comes from the start image unless the caller gave one."""
+    eng = F._engine
+    if net.tau_given is None:
+        start = x0 if x0 is not None else F.adjoint(y)
+        _, net.sigma_max = eng.llr_prox(start, 0.0, block=net.block, real=tsmi_domain != "complex")
+        net.tau = net.tau_rel * net.sigma_max
+    eng.set_llr(net.tau, block=net.block, shift=net.shift)
+
+
 def build_noise_map(noise_std, rows, cols):
     """noise_map = repmat(noise_std, rows, cols)  (build_noise_map.m:19)."""
     return np.full((rows, cols), float(noise_std))
@@ -155,14 +184,23 @@ def PnP_ADMM(y, param):
     if not hasattr(F, "_engine") or not hasattr(net, "_engine") or F._engine is not net._engine:
         raise TypeError("param.F and param.net must come from make_F / make_net of this package (same device)")
     PnP_ADMM.last_field_normal = _field_normal(F, param.get("field_normal"))
-    multi = param.get("denoiser_type", net._denoiser_type) == "multi_level"
+    llr = getattr(net, "_llr", False)                               # (make_llr: Step 2 is the locally low-rank prox)
+    multi = param.get("denoiser_type", net._denoiser_type) == "multi_level" and not llr
     noise_std = float(np.asarray(param["noise_map"]).ravel()[0]) if multi else 0.01
     traj = getattr(F._P, "omega", None) is not None                 # (a trajectory computes no per-iteration diagnostics: last_diagnostics is None)
-    x, diag, li = F._engine.pnp_admm(y, gamma=param["gamma"], iters=int(param["iter"]), cg_tol=param["cg_tol"], cg_maxit=100,
-                                     solver=param.get("solver", "lsqr"), multi_level=multi, noise_std=noise_std,
-                                     tsmi_domain=param.get("tsmi_domain", getattr(net, "_tsmi_domain", "real")),
-                                     x0=_dcf_x0(F, param, y), gt=None if traj else param.get("gt_tsmi"),
-                                     want_diag=param.get("gt_tsmi") is not None and not traj)
+    tsmi_domain = param.get("tsmi_domain", getattr(net, "_tsmi_domain", "real"))
+    x0 = _dcf_x0(F, param, y)
+    if llr:
+        _llr_arm(F, net, param, y, x0, tsmi_domain)
+    try:
+        x, diag, li = F._engine.pnp_admm(y, gamma=param["gamma"], iters=int(param["iter"]), cg_tol=param["cg_tol"], cg_maxit=100,
+                                         solver=param.get("solver", "lsqr"), multi_level=multi, noise_std=noise_std,
+                                         tsmi_domain=tsmi_domain,
+                                         x0=x0, gt=None if traj else param.get("gt_tsmi"),
+                                         want_diag=param.get("gt_tsmi") is not None and not traj)
+    finally:
+        if llr:
+            F._engine.clear_llr()
     PnP_ADMM.last_diagnostics, PnP_ADMM.last_lsqr_iters = diag, li
     return x
 
