@@ -23,7 +23,7 @@ struct KnobDef { const char* name; int dflt; };
 const KnobDef g_knob_defs[K_COUNT] = {
     {"conv_scheme", 2}, {"conv_f32", 0}, {"conv_wt", 1}, {"conv_xcd", 1}, {"conv_persist", 1}, {"conv_splitk", 1},
     {"conv_midcfg", 3}, {"conv_deepcfg", 3}, {"conv_deepks", 4},
-    {"conv_resident", 1}, {"res_head", 1}, {"res_tail", 1}, {"res_down", 1}, {"res_delay", 24}, {"res_rearm", 64},
+    {"conv_resident", 1}, {"res_head", 1}, {"res_tail", 1}, {"res_down", 1}, {"res_delay", 24}, {"res_pipe", 1}, {"res_pipe_delay", 8}, {"res_rearm", 64},
     {"res_stamps", 0}, {"conv_stamps", 0}, {"conv_stamp_launch", -1}, {"lsqr_stamps", 0},
     {"conv_mt2", 1024}, {"conv_occ", 2},
     {"fuse_ew", 1}, {"lsqr_persist", 1}, {"lsqr_fold", 1}, {"dictw_lsp", 2}, {"verbose", 0},

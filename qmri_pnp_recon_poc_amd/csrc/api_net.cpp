@@ -326,7 +326,7 @@ extern "C" int qmri_set_denoiser(qmri_ctx* ctx, const qmri_net_desc* desc, const
             QMRI_TRY(dev_alloc(ctx, &p.d_res_xbuf, conv6r_xbuf_bytes(p.res_tiles)));
             QMRI_HIP(ctx, hipMemset(p.d_res_xbuf, 0, conv6r_xbuf_bytes(p.res_tiles)));
             p.res_epoch = 0; p.res_off = false;
-            if (qmri_knob(K_RES_STAMPS)) { QMRI_HIP(ctx, hipMalloc(&p.d_res_stamps, 1024 * sizeof(unsigned long long))); QMRI_HIP(ctx, hipMemset(p.d_res_stamps, 0, 1024 * sizeof(unsigned long long))); }
+            if (qmri_knob(K_RES_STAMPS)) { QMRI_HIP(ctx, hipMalloc(&p.d_res_stamps, 2048 * sizeof(unsigned long long))); QMRI_HIP(ctx, hipMemset(p.d_res_stamps, 0, 2048 * sizeof(unsigned long long))); }
         }
     } else {
         const int width = desc->nc[0];
@@ -628,9 +628,9 @@ extern "C" int qmri_denoise(qmri_ctx* ctx, const double* in, int H, int W, int C
 
 // diagnostic: copy the per-workgroup stamps of the most recent conv launch (see conv_kernels.hip) to the host
 extern "C" int qmri_debug_conv_stamps(qmri_ctx* ctx, unsigned long long* out, int nwg) {
-    if (ctx && nwg == -6 && ctx->net.d_res_stamps) {                // (the resident-tile launch's stamps: 1024 values, knob res_stamps)
+    if (ctx && nwg == -6 && ctx->net.d_res_stamps) {                // (the resident-tile launch's stamps: 2048 values, knob res_stamps)
         QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        QMRI_HIP(ctx, hipMemcpy(out, ctx->net.d_res_stamps, (size_t)1024 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        QMRI_HIP(ctx, hipMemcpy(out, ctx->net.d_res_stamps, (size_t)2048 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
         return QMRI_OK;
     }
     if (!ctx || !ctx->net.d_stamps) return QMRI_ERR_STATE;

@@ -2,6 +2,7 @@
 // scheme and shared device code: conv6_kernels.hip, conv6_device.h).  Reference semantics: the ResBlocks of UNetRes (basicblock.py:211-223,
 // network_unet.py:106-117) with the head, the tail and the level's down-sampling convolution where they ride in the launch.
 #include "conv6_device.h"
+#include "conv6r_ring.h"
 
 namespace {
 
@@ -19,14 +20,32 @@ namespace {
 //     PLACE into the resident tile (the input is dead once the loop is over); ResBlock outputs also go to memory as fp32 (they are
 //     residual operands -- read back by this workgroup alone -- and the run's result), the ReLU intermediates never leave the chip;
 //   * the one-pixel ring comes from the eight neighbouring workgroups through memory, as TAGGED GRANULES: the loader waves publish the
-//     tile's edges (columns w = 0 / 15, rows h = 0 / 15, four corner pixels: 368 triples of three 16-byte LDS entries) as 8-byte words
-//     {3 x f16, 16-bit tag}, four 16-byte sc1 stores per triple, into the tile's part of the exchange buffer of the layer's parity; the
-//     matrix waves (idle between two layers) pause, request the matching segments of the eight neighbours, check the eight tags of each
-//     triple, write its three entries into the ring and ask again for what was not complete.  No counter, no drain of the stores, no
-//     barrier between publish and fetch: a granule is its own flag (MI355X_MICROARCH.md, valid forms, R2).  Two buffers in turn make it
-//     race-free: a tile overwrites its layer-l edges at layer l + 2, which it reaches only after its neighbours published layer l + 1,
-//     i.e. after they consumed layer l.  The tag is a running count the host never resets.  At the image border nothing is fetched: the
-//     ring there keeps the zeros of the run input's halo.
+//     tile's edges (columns w = 0 / 15, rows h = 0 / 15, four corner pixels; per 16-channel chunk 96 triples of three 16-byte LDS entries,
+//     384 in all: conv6r_ring.h) as 8-byte words {3 x f16, 16-bit tag}, four 16-byte sc1 stores per triple, into the tile's part of the
+//     exchange buffer of the layer's parity; the fetching side requests the matching segments of the eight neighbours, checks the eight
+//     tags of each triple, writes its three entries into the ring and asks again for what was not complete.  No counter, no drain of the
+//     stores, no barrier between publish and fetch: a granule is its own flag (MI355X_MICROARCH.md, valid forms, R2).  The tag is a running
+//     count the host never resets.  At the image border nothing is fetched: the ring there keeps the zeros of the run input's halo.
+//   * the exchange is PIPELINED BY CHUNK (Conv6rArgs::pipe, knob res_pipe; 0 = everything between the barriers E2 and E3 behind the epilogue,
+//     fetched by the matrix waves).  The tile is stored per chunk, the loop walks K chunk by chunk (three steps each) and the epilogue writes
+//     the channel blocks in chunk order, so the next loop needs the ring of chunk 0 at its first step and that of chunk c three steps per
+//     chunk later:
+//       - E1a, one more barrier after the first quarter of the epilogue (channel blocks 0, 1 = chunk 0 are in the tile): the loader waves,
+//         idle there, publish chunk 0 at once and then fetch the neighbours' chunk 0 into the ring of chunk 0 while the matrix waves finish
+//         the epilogue (which writes the interior of chunks 1 - 3; the loop that read those ring positions is over in every wave: all of
+//         them passed E1a);
+//       - E2 (the whole output is in the tile, and the ring of chunk 0): the next loop starts, and under its first step the loader waves
+//         publish chunks 1 - 3 (no E3 in this form: nothing the first chunk's steps read changes after E2);
+//       - under that loop the loader waves request the ring of chunk c in the second step of chunk c - 1 and check it in the third, whose
+//         barrier -- the one in front of chunk c's first step -- is the deadline; a triple that is not complete there is asked for again,
+//         at most R_SPIN_MAX times, before the loader wave enters that barrier.  The requests are counted into the weight stream's waits.
+//     Both roles execute the same barriers in every kind of layer: E1a exists where pipe is set and the layer publishes (R_KEEP without
+//     R_LOCAL), E2 where R_KEEP, E3 where pipe is not set and the layer publishes.
+//     RACE-FREE with two buffers in turn, early publication included: a tile publishes ANY chunk of layer l + 2 (into the buffer that holds
+//     its layer l) only after its own loop l + 2; that loop passed the deadlines of all chunks of its neighbours' layer l + 1; the
+//     neighbours published any chunk of layer l + 1 only after THEIR loop l + 1, under which they had taken every chunk of layer l.
+//     DEADLOCK-FREE: a wait for a chunk of layer l depends only on the neighbours finishing loop l (chunk 0: plus a quarter of an epilogue),
+//     and loop l depends on rings of layer l - 1, all of which were published before their owners entered loop l.  Every wait is bounded.
 // The launch is a small layer program (Conv6rArgs: per layer the chunks of its input, what its epilogue does, the tensors involved).
 // All 196 workgroups must be resident at once (one per CU by LDS size; the host checks tiles <= CUs).  A fetch that is not complete after
 // R_SPIN_MAX attempts raises bit 2 of the range flag and the wave runs on without waiting (its workgroup goes on publishing, so nobody
@@ -46,13 +65,10 @@ constexpr int R_DOWN = 128;                                 // the level's strid
 constexpr unsigned R_DOWN_STEPB = 2 * 2 * 2 * 64 * 16;           // ... bytes of one of its weight steps (k_conv6s: 2 planes x 2 row tiles x 2 pieces x 64 lanes x 16 B)
 constexpr int R_LOCAL = 256;                                // with R_KEEP: the next layer needs no ring (R_DOWN follows): pieces in place, no exchange
 constexpr int R_TAIL = 64;                                  // the network's last layer (<= 32 output channels): first 32-row tile of the weights only, PLANAR fp32 output
-constexpr int R_IH = 18, R_IW = 18, R_IHP = 24;             // input tile with ring; LDS row pitch (= 8 mod 16 entries, as in k_conv6)
-constexpr int R_NPX = R_IHP * (R_IW - 1) + R_IH;            // LDS entries per (split, k-half) plane
-constexpr int R_CHUNK = 2 * 2 * R_NPX;                      // ... per 16-channel chunk: [split][k-half][R_NPX]
+// (tile geometry R_IH .. R_CHUNK and the exchange's index maps R_NTRI, r_*: conv6r_ring.h)
 constexpr int R_AST = ast6(2);
 constexpr int R_SPIN_MAX = 1 << 16;
-constexpr int R_SEGT = 86, R_CORT = 6;                      // triples per edge segment (16 pixels x 16 entries, padded) / per corner pixel
-constexpr int R_NTRI = 4 * R_SEGT + 4 * R_CORT;             // triples (64 bytes each) a tile publishes per layer
+static_assert(R_NTRI <= 2 * NLD6 && R_CHT <= NLD6, "two triples per thread to publish, one per thread and chunk to fetch");
 constexpr size_t conv6r_lds() { return (size_t)(NABUF * R_AST + 4 * R_CHUNK) * 16; }
 
 struct Conv6rArgs {
@@ -68,7 +84,9 @@ struct Conv6rArgs {
     int am_layer[R_MAXL];                                   // row of the |output| report, -1: none
     int nlayers, hp, plane, tiles_h, tiles_w, xcd;
     int drop;                                               // test hook: tile (0, 0) publishes nothing
-    int delay;                                              // s_sleep(1) units (64 clocks) between E2 and the first fetch attempt
+    int pipe;                                               // 1: the exchange pipelined by chunk (chunk 0 published at E1a and fetched under the epilogue, chunks 1 - 3 fetched under the next loop); 0: all of it between E2 and E3
+    int delay;                                              // pipe = 0: s_sleep(1) units (64 clocks) between E2 and the first fetch attempt
+    int pdelay;                                             // pipe = 1: ... between the early publish and the first attempt at chunk 0
     unsigned epoch;                                         // layers published before this launch: layer l of this launch tags its granules (epoch + l + 1) mod 2^16
     unsigned* range_flag; float* am_slots; int* am_count;
     unsigned long long* stamps;                             // diagnostic instantiation only
@@ -82,24 +100,15 @@ template <int IMM> __device__ __forceinline__ void gload4r_sc1(f32x4& dst, unsig
 template <int IMM> __device__ __forceinline__ void gstore4r(unsigned off, f32x4 x, void* base) { asm volatile("global_store_dwordx4 %0, %1, %2 offset:%3\n\ts_nop 1" ::"v"(off), "v"(x), "s"(base), "n"(IMM) : "memory"); }
 template <int IMM> __device__ __forceinline__ void gstore4r_sc1(unsigned off, f32x4 x, void* base) { asm volatile("global_store_dwordx4 %0, %1, %2 offset:%3 sc1\n\ts_nop 1" ::"v"(off), "v"(x), "s"(base), "n"(IMM) : "memory"); }
 
-// triple t of a tile's 368 -> (segment, index inside it); first triple of a segment; LDS byte offset of entry kind k (channel block, piece) at tile position (dw, dh)
-__device__ __forceinline__ void r_tri_decode(int t, int& seg, int& j) {
-    if (t < 4 * R_SEGT) { seg = t / R_SEGT; j = t - seg * R_SEGT; } else { seg = 4 + (t - 4 * R_SEGT) / R_CORT; j = (t - 4 * R_SEGT) - (seg - 4) * R_CORT; }
-}
-__device__ __forceinline__ int r_seg_base(int seg) { return seg < 4 ? seg * R_SEGT : 4 * R_SEGT + (seg - 4) * R_CORT; }
-__device__ __forceinline__ unsigned r_ent_lds(int k, int dw, int dh) {
-    const int cb = k >> 1, sp = k & 1;
-    return (unsigned)(((cb >> 1) * R_CHUNK + sp * 2 * R_NPX + (cb & 1) * R_NPX + dw * R_IHP + dh) * 16);
-}
-
-// (STAMP: diagnostic instantiation, knob res_stamps -- tools/conv6r_stamps.py: 100 MHz phase stamps of four workgroups, [wg][matrix wave 0 / loader wave 0][layer][8])
-#define R_STAMP(role, k)                                                                                         \
+// (STAMP: diagnostic instantiation, knob res_stamps -- tools/conv6r_stamps.py: 100 MHz phase stamps of four workgroups, [wg][matrix wave 0 / loader wave 0][layer][16])
+#define R_STAMPV(role, k, v)                                                                                     \
     do {                                                                                                         \
         if constexpr (STAMP) {                                                                                   \
             if (A.stamps && (threadIdx.x & 255) == 0 && blockIdx.x % 50 == 0 && blockIdx.x / 50 < 4)             \
-                A.stamps[(((blockIdx.x / 50) * 2 + (role)) * R_MAXL + l) * 8 + (k)] = wall_clock64();            \
+                A.stamps[(((blockIdx.x / 50) * 2 + (role)) * R_MAXL + l) * 16 + (k)] = (v);                      \
         }                                                                                                        \
     } while (0)
+#define R_STAMP(role, k) R_STAMPV(role, k, wall_clock64())
 template <bool STAMP>
 __global__ __launch_bounds__(NT6) void k_conv6r(const Conv6rArgs A) {
     constexpr int SP = 2, AST = R_AST, IHP = R_IHP, NPX = R_NPX, NAQ = 3;
@@ -221,28 +230,97 @@ __global__ __launch_bounds__(NT6) void k_conv6r(const Conv6rArgs A) {
             gwait_a<0>(ra0); gwait_a<0>(pa1);
             R_STORE_A(0, ra0) R_STORE_A(1, pa1)
         }
-        // The ring exchange, per thread and layer: <= 2 TRIPLES to publish and <= 2 to fetch.  A triple = three 16-byte LDS entries (an entry = the 8 hi
-        // or the 8 lo' pieces of one channel block at one pixel) = 24 f16 values = eight 8-byte granules {3 x f16, 16-bit tag} = four 16-byte stores.
-        // A tile publishes eight segments -- its columns w = 0 / 15, its rows h = 0 / 15 (16 pixels x 16 entries, padded to 86 triples) and its four
-        // corner pixels (16 entries, 6 triples) -- into its own 368 x 64 bytes of the exchange buffer of the layer's parity; a tile fetches the
-        // matching segments of its eight neighbours (its left ring column = the left neighbour's column w = 15, ...).  Offsets: ~0u = none.
+        // The ring exchange (index maps: conv6r_ring.h), per thread and layer: <= 2 TRIPLES to publish, and with A.pipe one triple per chunk to fetch.
+        // A triple = three 16-byte LDS entries of ONE 16-channel chunk (an entry = the 8 hi or the 8 lo' pieces of one channel block at one pixel)
+        // = 24 f16 values = eight 8-byte granules {3 x f16, 16-bit tag} = four 16-byte stores.  A tile publishes eight segments -- its columns
+        // w = 0 / 15, its rows h = 0 / 15 (per chunk 16 pixels x 4 entries, padded to 22 triples) and its four corner pixels (per chunk 4 entries,
+        // 2 triples) -- into its own 384 x 64 bytes of the exchange buffer of the layer's parity, chunk-major; a tile fetches the matching segments
+        // of its eight neighbours (its left ring column = the left neighbour's column w = 15, ...).  Offsets: R_NONE = none.
         unsigned p_lds[2][3], p_x[2];
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const int t = lt + NLD6 * q;
             const bool valid = t < R_NTRI;
-            int seg, j;
-            r_tri_decode(valid ? t : 0, seg, j);
-            const int npx = seg < 4 ? 16 : 1;
+            const int tc = valid ? t : 0, ck = r_tri_chunk(tc), seg = r_tri_seg(tc), j = r_tri_j(tc);
 #pragma unroll
-            for (int i = 0; i < 3; ++i) {                           // segment `seg` of this tile, pixel pp at interior position (w, h)
-                const int E = 3 * j + i, Ec = (E < npx * 16) ? E : 0, pp = Ec >> 4, k = Ec & 15;
-                const int w = (seg == 0) ? 0 : (seg == 1) ? 15 : (seg == 2 || seg == 3) ? pp : (seg < 6 ? 0 : 15);
-                const int h = (seg == 0 || seg == 1) ? pp : (seg == 2) ? 0 : (seg == 3) ? 15 : ((seg & 1) ? 15 : 0);
-                p_lds[q][i] = r_ent_lds(k, w + 1, h + 1);
-            }
-            p_x[q] = valid ? (unsigned)((tw * A.tiles_h + th) * (R_NTRI * 64) + t * 16) : ~0u;   // (quarter i of a triple: + i * R_NTRI * 16 -- consecutive lanes, consecutive 16 bytes)
+            for (int i = 0; i < 3; ++i) p_lds[q][i] = r_pub_lds_d(ck, seg, j, i);
+            p_x[q] = valid ? r_slot(t, th, tw, A.tiles_h) : R_NONE;
         }
+        // (pipe) thread lt < R_CHT fetches ring triple lt of every chunk: LDS offsets and slot for chunk 0 (chunk c: + c * R_CHUNK * 16, + c * R_CHT * 16).
+        // A lane with nothing to fetch requests its own tile's first slot and drops it: the hand-counted waits below need the same number of
+        // requests in flight in every wave.
+        unsigned f_lds[3], f_x;
+        {
+            const bool fv = lt < R_CHT;
+            const int seg = r_tri_seg(fv ? lt : 0), j = r_tri_j(fv ? lt : 0);
+            const bool have = (int(fv) & int(r_ring_have_d(seg, th, tw, A.tiles_h, A.tiles_w))) != 0;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) f_lds[i] = r_ring_lds_d(0, seg, j, i, have);
+            const unsigned fs = r_ring_slot_d(0, seg, j, th, tw, A.tiles_h, have);
+            f_x = fs != R_NONE ? fs : r_slot(0, th, tw, A.tiles_h);
+        }
+        const unsigned f_idle = r_slot(0, th, tw, A.tiles_h);
+        bool dead = false;                                          // a fetch timed out: no more waiting in this wave
+        auto publish = [&](auto qc, unsigned thi, unsigned char* xb) __attribute__((always_inline)) {
+            constexpr int q = decltype(qc)::value;
+            unsigned d[12];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                const uint4 e = *(const uint4*)((const unsigned char*)Bt + p_lds[q][i]);
+                d[4 * i] = e.x; d[4 * i + 1] = e.y; d[4 * i + 2] = e.z; d[4 * i + 3] = e.w;
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {                           // two granules per store: {F0 F1 | F2 tag} {F3 F4 | F5 tag}
+                u32x4 g;
+                g[0] = d[3 * i];
+                g[1] = (d[3 * i + 1] & 0xFFFFu) | thi;
+                g[2] = (d[3 * i + 1] >> 16) | (d[3 * i + 2] << 16);
+                g[3] = (d[3 * i + 2] >> 16) | thi;
+                const unsigned po = p_x[q] + (unsigned)(i * (R_NTRI * 16));
+                asm volatile("global_store_dwordx4 %0, %1, %2 sc1\n\ts_nop 1" ::"v"(po), "v"(g), "s"(xb) : "memory");
+            }
+        };
+        auto ring_req = [&](u32x4 (&g)[4], unsigned slot, const unsigned char* xb) __attribute__((always_inline)) {      // the four quarters of the triple in `slot`
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const unsigned fo = slot + (unsigned)(i * (R_NTRI * 16));
+                asm volatile("global_load_dwordx4 %0, %1, %2 sc1" : "=v"(g[i]) : "v"(fo), "s"(xb) : "memory");
+            }
+        };
+        auto ring_take = [&](const u32x4 (&g)[4], int c, unsigned thi) __attribute__((always_inline)) -> bool {  // all eight granules carry the tag: the three entries go into the ring
+            unsigned bad = 0;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) bad |= (g[i][1] ^ thi) | (g[i][3] ^ thi);
+            if ((bad >> 16) != 0) return false;
+            unsigned d[12];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                d[3 * i] = g[i][0];
+                d[3 * i + 1] = (g[i][1] & 0xFFFFu) | (g[i][2] << 16);
+                d[3 * i + 2] = (g[i][2] >> 16) | (g[i][3] << 16);
+            }
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+                if (f_lds[i] != R_NONE) *(uint4*)((unsigned char*)Bt + f_lds[i] + (unsigned)(c * (R_CHUNK * 16))) = make_uint4(d[4 * i], d[4 * i + 1], d[4 * i + 2], d[4 * i + 3]);
+            return true;
+        };
+        // asks again, at most R_SPIN_MAX times, for what is not complete (waits for EVERYTHING this wave has in flight: the weight stream's counted
+        // waits behind it then find fewer requests outstanding than they allow for, which only makes them pass at once); returns the attempts
+        auto ring_spin = [&](bool pend, int c, unsigned thi, const unsigned char* xb) __attribute__((always_inline)) -> int {
+            int spin = 0;
+            bool ok = false;
+            for (; spin < R_SPIN_MAX; ++spin) {
+                u32x4 g[4];
+                if (pend) ring_req(g, f_x + (unsigned)(c * (R_CHT * 16)), xb);
+                asm volatile("s_waitcnt vmcnt(0)" : "+v"(g[0]), "+v"(g[1]), "+v"(g[2]), "+v"(g[3])::"memory");
+                if (pend && ring_take(g, c, thi)) pend = false;
+                if (!__any(pend)) { ok = true; break; }
+                __builtin_amdgcn_s_sleep(1);
+            }
+            if (!ok) { dead = true; if ((lt & 63) == 0 && A.range_flag) atomicOr(A.range_flag, 4u); }
+            return spin;
+        };
+        typedef std::integral_constant<int, 0> Q0; typedef std::integral_constant<int, 1> Q1;
         lds_barrier6();                                             // barrier 0: step 0 may start
 #define R_ITER(k_, rs_, rq_)     /* stores step g + k_ + 2 into its buffer, requests step g + k_ + 4 */          \
         {                                                                                                        \
@@ -255,13 +333,52 @@ __global__ __launch_bounds__(NT6) void k_conv6r(const Conv6rArgs A) {
         }
 #pragma unroll 1
         for (int l = 0; l < nl; ++l) {
+            // (pipe) the ring of this layer's input, chunks 1 - 3, arrives UNDER its loop: the ring of chunk c is requested in the second step of
+            // chunk c - 1 and checked in its third, whose barrier -- the one in front of chunk c's first step -- is the deadline.  Requests in flight,
+            // oldest first, at the counted waits (w = three weight requests of a step, r = the four ring requests):
+            //   second step   w(g+3) w(g+4) r w(g+5)   -> vmcnt(10) releases w(g+3)
+            //   third step    w(g+4) r w(g+5) w(g+6)   -> vmcnt(6)  releases w(g+4) AND r: the usual count
+            // (publish stores may still be in flight in front of them: they only make a wait last longer).  There is ONE form of the three steps:
+            // where nothing is to be fetched (pipe = 0, no ring, the last chunk) every lane requests the tile's own first slot -- one cache line
+            // per request and wave -- and drops it.  (Two forms of the loop body, one with and one without the ring requests, made hipcc copy
+            // weight registers that were still in flight where the two paths join.)
+            const bool fin = A.pipe && l > 0 && (A.kind[l - 1] & (R_KEEP | R_LOCAL)) == R_KEEP;
+            const unsigned thip = ((A.epoch + (unsigned)l) & 0xFFFFu) << 16;            // the tag of layer l - 1
+            const unsigned char* xbp = A.xbuf + (size_t)((l + 1) & 1) * A.xbuf_half;   // ... and its parity
+            int nretry = 0;
 #pragma unroll 1
             for (int g = 0; g < 3 * A.nch[l]; g += 3) {
+                const int c = g / 3 + 1;
+                const bool fnow = fin && c < 4;                     // (uniform)
+                u32x4 rg[4];
                 R_ITER(0, ra1, ra0)
-                R_ITER(1, ra2, ra1)
-                R_ITER(2, ra0, ra2)
+                {
+                    __builtin_amdgcn_s_setprio(2);
+                    ring_req(rg, fnow ? f_x + (unsigned)(c * (R_CHT * 16)) : f_idle, xbp);
+                    R_REQ(ra1)
+                    __builtin_amdgcn_s_setprio(0);
+                    gwait_a<2 * NAQ + 4>(ra2);
+                    R_STORE_A(0, ra2)
+                    lds_barrier6();
+                }
+                {
+                    __builtin_amdgcn_s_setprio(2);
+                    R_REQ(ra2)
+                    __builtin_amdgcn_s_setprio(0);
+                    asm volatile("s_waitcnt vmcnt(%7)" : "+v"(ra0[0]), "+v"(ra0[1]), "+v"(ra0[2]), "+v"(rg[0]), "+v"(rg[1]), "+v"(rg[2]), "+v"(rg[3]) : "n"(2 * NAQ) : "memory");
+                    if (fnow) {
+                        bool pend = f_lds[0] != R_NONE && !dead;
+                        if (pend && ring_take(rg, c, thip)) pend = false;
+                        if (__any(pend)) nretry += 1 + ring_spin(pend, c, thip, xbp);
+                        R_STAMP(1, 7 + c);
+                    }
+                    R_STORE_A(1, ra0)
+                    lds_barrier6();                                 // the deadline of chunk c
+                    if (fnow) R_STAMP(1, 10 + c);
+                }
             }
             R_STAMP(1, 0);
+            R_STAMPV(1, 15, (unsigned long long)nretry);
             if (A.kind[l] & R_TAIL) {                               // the network's output: out_c planes of this tile from the matrix waves' LDS copy
                 lds_barrier6();
                 const float* tl = (const float*)Bt;
@@ -273,35 +390,38 @@ __global__ __launch_bounds__(NT6) void k_conv6r(const Conv6rArgs A) {
                 break;
             }
             if (!(A.kind[l] & R_KEEP)) break;                      // (the last layer)
-            lds_barrier6();                                         // E2: the matrix waves have written this layer's output into the tile
-            if (A.kind[l] & R_LOCAL) continue;                      // (the next layer reads no ring)
-            R_STAMP(1, 1);
+            const bool pubs = !(A.kind[l] & R_LOCAL);               // (R_LOCAL: the next layer reads no ring)
+            const bool silent = A.drop && th == 0 && tw == 0;
             const unsigned tag = (A.epoch + (unsigned)l + 1u) & 0xFFFFu, thi = tag << 16;
             unsigned char* xb = A.xbuf + (size_t)(l & 1) * A.xbuf_half;
-            if (!(A.drop && th == 0 && tw == 0)) {
-#pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    if (p_x[q] == ~0u) continue;
-                    unsigned d[12];
-#pragma unroll
-                    for (int i = 0; i < 3; ++i) {
-                        const uint4 e = *(const uint4*)((const unsigned char*)Bt + p_lds[q][i]);
-                        d[4 * i] = e.x; d[4 * i + 1] = e.y; d[4 * i + 2] = e.z; d[4 * i + 3] = e.w;
-                    }
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {                   // two granules per store: {F0 F1 | F2 tag} {F3 F4 | F5 tag}
-                        u32x4 g;
-                        g[0] = d[3 * i];
-                        g[1] = (d[3 * i + 1] & 0xFFFFu) | thi;
-                        g[2] = (d[3 * i + 1] >> 16) | (d[3 * i + 2] << 16);
-                        g[3] = (d[3 * i + 2] >> 16) | thi;
-                        asm volatile("global_store_dwordx4 %0, %1, %2 sc1\n\ts_nop 1" ::"v"(p_x[q] + (unsigned)(i * (R_NTRI * 16))), "v"(g), "s"(xb) : "memory");
-                    }
+            if (A.pipe && pubs) {
+                lds_barrier6();                                     // E1a: the matrix waves have written chunk 0 of this layer's output into the tile
+                R_STAMP(1, 3);
+                if (!silent && lt < R_CHT) publish(Q0{}, thi, xb);  // chunk 0 = triples 0 .. 95, at once: the neighbours' loops need it first
+                R_STAMP(1, 4);
+                // ... and the neighbours' chunk 0 into the ring of chunk 0, under the rest of the epilogue (which writes the interior of chunks 1 - 3;
+                // the loop that read these ring positions is over in every wave: all of them passed E1a)
+                const bool pend = f_lds[0] != R_NONE && !dead;
+                int ns = 0;
+                if (__any(pend)) {
+                    for (int i = 0; i < A.pdelay; ++i) __builtin_amdgcn_s_sleep(1);    // (the neighbours publish about now; knob res_pipe_delay, 8 units by the sweep in profiles/ring_chunks_sweep.txt)
+                    ns = ring_spin(pend, 0, thi, xb);
                 }
+                R_STAMP(1, 7);
+                R_STAMPV(1, 14, (unsigned long long)ns);
+            }
+            lds_barrier6();                                         // E2: the matrix waves have written this layer's output into the tile
+            if (!pubs) continue;
+            R_STAMP(1, 1);
+            if (!silent) {
+                if (!(A.pipe && lt < R_CHT)) publish(Q0{}, thi, xb);        // (every thread has a first triple: R_NTRI >= NLD6)
+                if (p_x[1] != R_NONE) publish(Q1{}, thi, xb);
             }
             R_STAMP(1, 2);
             R_STAMP(1, 5);
-            lds_barrier6();                                         // E3: the tile is the next layer's input
+            // E3: the tile is the next layer's input.  Not with pipe: all the next loop's first chunk needs was in the tile at E2 (the ring of chunk 0
+            // was fetched in front of it), so the matrix waves start at E2 and this publish runs under their first step.
+            if (!A.pipe) lds_barrier6();
             R_STAMP(1, 6);
         }
         gwait_a<0>(ra0); gwait_a<0>(ra1); gwait_a<0>(ra2);          // (clamped requests past the end are still in flight)
@@ -514,6 +634,7 @@ __global__ __launch_bounds__(NT6) void k_conv6r(const Conv6rArgs A) {
         R_STAMP(0, 2);
         float gmax = 0.f;                                           // largest |output| of this lane
         bool bad = false;
+        const bool e1a = A.pipe && (kind & (R_KEEP | R_LOCAL)) == R_KEEP;   // (uniform; the loader waves evaluate the same condition)
         // RELU; STORE 0 none / 1 plain (this workgroup reads it back, sc1) / 2 written through (the run's result); KEEP: the next layer's operand, in place
         auto finish = [&](auto relu_c, auto store_c, auto keep_c) __attribute__((always_inline)) {
             constexpr bool RELU = decltype(relu_c)::value, KEEP = decltype(keep_c)::value;
@@ -545,6 +666,12 @@ __global__ __launch_bounds__(NT6) void k_conv6r(const Conv6rArgs A) {
                         }
                     }
                     go += plane32;
+                    if constexpr (KEEP) {
+                        if (m == 0 && rg == 1 && e1a) {             // E1a: chunk 0 (cb = 0, 1) is in the tile -- the loader waves publish it now
+                            lds_barrier6();
+                            R_STAMP(0, 7);
+                        }
+                    }
                 }
         };
         typedef std::true_type T1; typedef std::false_type T0;
@@ -560,9 +687,10 @@ __global__ __launch_bounds__(NT6) void k_conv6r(const Conv6rArgs A) {
         lds_barrier6();                                             // E2
         if (kind & R_LOCAL) continue;                               // (the next layer reads no ring)
         R_STAMP(0, 4);
-        {
-                // this thread's <= 2 triples of the ring, worked out again for every layer (eight registers less across the loop; fetched by the matrix waves, which have nothing else to do between two layers -- and, unlike the loader
-            // waves, no stores of their own in front of the requests): ring segment `seg` <- neighbour (dtw, dth), its segment ns
+        if (!A.pipe) {
+            // pipe = 0: the whole exchange between E2 and E3, fetched by the matrix waves -- this thread's <= 2 triples of the ring, worked out again
+            // for every layer (eight registers less across the loop).  (pipe = 1: the loader waves have fetched chunk 0 before E2 and fetch
+            // chunks 1 - 3 under the next loop.)
             int tid_l = tid;
             asm volatile("" : "+v"(tid_l));                        // (per layer, on purpose: as loop invariants the eight offsets are spilled)
             unsigned c_lds[2][3], c_x[2];
@@ -570,20 +698,11 @@ __global__ __launch_bounds__(NT6) void k_conv6r(const Conv6rArgs A) {
             for (int q = 0; q < 2; ++q) {
                 const int t = tid_l + 256 * q;
                 const bool valid = t < R_NTRI;
-                int seg, j;
-                r_tri_decode(valid ? t : 0, seg, j);
-                const int npx = seg < 4 ? 16 : 1;
-                const int dtw = (seg == 0 || seg == 4 || seg == 5) ? -1 : (seg == 1 || seg == 6 || seg == 7) ? 1 : 0;
-                const int dth = (seg == 2 || seg == 4 || seg == 6) ? -1 : (seg == 3 || seg == 5 || seg == 7) ? 1 : 0;
-                const int ns = (seg < 4) ? (seg ^ 1) : 11 - seg;
-                const bool have = valid && tw + dtw >= 0 && tw + dtw < A.tiles_w && th + dth >= 0 && th + dth < A.tiles_h;
+                const int tc = valid ? t : 0, ck = r_tri_chunk(tc), seg = r_tri_seg(tc), j = r_tri_j(tc);
+                const bool have = (int(valid) & int(r_ring_have_d(seg, th, tw, A.tiles_h, A.tiles_w))) != 0;
 #pragma unroll
-                for (int i = 0; i < 3; ++i) {
-                    const int E = 3 * j + i, pp = E >> 4, k = E & 15;
-                    const int dw = (dtw < 0) ? 0 : (dtw > 0) ? 17 : pp + 1, dh = (dth < 0) ? 0 : (dth > 0) ? 17 : pp + 1;
-                    c_lds[q][i] = (have && E < npx * 16) ? r_ent_lds(k, dw, dh) : ~0u;
-                }
-                c_x[q] = have ? (unsigned)(((tw + dtw) * A.tiles_h + th + dth) * (R_NTRI * 64) + (r_seg_base(ns) + j) * 16) : ~0u;
+                for (int i = 0; i < 3; ++i) c_lds[q][i] = r_ring_lds_d(ck, seg, j, i, have);
+                c_x[q] = r_ring_slot_d(ck, seg, j, th, tw, A.tiles_h, have);
             }
             const unsigned tag = (A.epoch + (unsigned)l + 1u) & 0xFFFFu, thi = tag << 16;
             const unsigned char* xb = A.xbuf + (size_t)(l & 1) * A.xbuf_half;
@@ -629,7 +748,7 @@ __global__ __launch_bounds__(NT6) void k_conv6r(const Conv6rArgs A) {
             }
         }
         R_STAMP(0, 5);
-        lds_barrier6();                                             // E3
+        if (!A.pipe) lds_barrier6();                                // E3 (pipe: the loop starts at E2, see the loader waves' side)
         R_STAMP(0, 6);
     }
 }
@@ -717,11 +836,14 @@ int conv6r_try(qmri_ctx* ctx, const Conv6rRun& run, int B, bool* done) {
     int pub[2] = {0, 0};
     for (int k = 0; k < l; ++k) if ((A.kind[k] & R_KEEP) && !(A.kind[k] & R_LOCAL)) pub[k & 1] += 1;
     if (!pub[0] || !pub[1]) return QMRI_OK;
+    for (int k = 1; k < l; ++k)                                     // a layer behind a publishing one takes its ring chunk by chunk under its loop: four chunks
+        if ((A.kind[k - 1] & (R_KEEP | R_LOCAL)) == R_KEEP && A.nch[k] != 4) return QMRI_OK;
     A.nlayers = nl; A.hp = src.hp; A.plane = (int)src.plane(); A.tiles_h = tiles_h; A.tiles_w = tiles_w;
     A.xbuf = net.d_res_xbuf; A.xbuf_half = (size_t)tiles * R_NTRI * 64;
     A.xcd = qmri_knob(K_CONV_XCD);
     const int delay = std::max(0, std::min(4096, qmri_knob(K_RES_DELAY)));
     A.epoch = net.res_epoch; A.drop = net.res_drop; A.delay = delay;
+    A.pipe = qmri_knob(K_RES_PIPE) ? 1 : 0; A.pdelay = std::max(0, std::min(4096, qmri_knob(K_RES_PIPE_DELAY)));
     A.range_flag = net.d_range_flag; A.am_slots = net.d_act_slots; A.am_count = net.d_act_count;
     if (!ctx->conv6r_attr) {
         QMRI_HIP(ctx, hipFuncSetAttribute((const void*)k_conv6r<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)conv6r_lds()));

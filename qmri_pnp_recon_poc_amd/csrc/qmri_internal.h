@@ -93,7 +93,9 @@ enum QmriKnob {
     K_CONV_MIDCFG, K_CONV_DEEPCFG, K_CONV_DEEPKS,   // tile configuration of the 56 x 56 / 28 x 28 level, largest K split of the latter
     K_CONV_RESIDENT,      // k_conv6r: the full-resolution level's layers as one launch with resident tiles
     K_RES_HEAD, K_RES_TAIL, K_RES_DOWN,             // ... with the head / tail / down-sampling convolution inside
-    K_RES_DELAY,          // ... pause before the ring fetch, in units of 64 clocks
+    K_RES_DELAY,          // ... pause before the ring fetch, in units of 64 clocks (res_pipe = 0)
+    K_RES_PIPE,           // ... ring exchange pipelined by 16-channel chunk (1, default) or all of it between two layers (0; same bits)
+    K_RES_PIPE_DELAY,     // ... res_pipe = 1: pause between the early publish and the first attempt at the neighbours' chunk 0, in units of 64 clocks
     K_RES_REARM,          // ... clean one-launch-per-layer passes after a hand-off time-out before the resident form is tried again
     K_RES_STAMPS, K_CONV_STAMPS, K_CONV_STAMP_LAUNCH, K_LSQR_STAMPS,   // diagnostic builds' in-kernel stamps
     K_CONV_MT2, K_CONV_OCC,                         // f32-MFMA fallback kernels: tile / occupancy choices
@@ -289,7 +291,7 @@ struct NetPlan {
     int res_clean = 0;               // clean one-launch-per-layer passes since the last one (K_RES_REARM of them re-arm the form)
     int res_drop = 0;                // test hook: bit 0 = tile 0 withholds its hand-off
     double* d_io = nullptr; size_t io_cap = 0;   // qmri_denoise: device staging of the caller's doubles (elements), kept between calls
-    void* d_res_stamps = nullptr;    // diagnostic: phase stamps of the last k_conv6r launch (knob res_stamps), 4 x 2 x R_MAXL (10) x 8 of 1024 values
+    void* d_res_stamps = nullptr;    // diagnostic: phase stamps of the last k_conv6r launch (knob res_stamps), 4 x 2 x R_MAXL (10) x 16 of 2048 values
     bool ready = false;
 };
 
