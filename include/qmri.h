@@ -592,7 +592,8 @@ typedef struct {
  * the device is selected (ctx == NULL: the message of the first failing check in qmri_last_error(NULL)): a NULL array or params, K < 1, T outside
  * 1..1024, nstates outside 1..256, inversion / out_is_f64 outside {0, 1}, ti or inv_eff out of range when inversion, a non-finite or negative alpha,
  * TR or TE, TR_t <= 0, TE_t > TR_t, a T1 or T2 that is non-finite or <= 0, a b1 that is non-finite or negative (b1 = 0 is allowed):
- * QMRI_ERR_INVALID_ARG.  Returns after its kernels have finished. */
+ * QMRI_ERR_INVALID_ARG.  Returns after its kernels have finished.  qmri_dict_simulate_sp / qmri_dict_simulate_sp_dev below are the same simulation
+ * integrated over a slice profile. */
 int qmri_dict_simulate(qmri_ctx* ctx, int K, int T, const double* alpha, const double* tr, const double* te, const double* t1, const double* t2,
                        const double* b1, const qmri_epg_params* p, void* F_out);
 /* The same with t1, t2, b1 and F_out on ctx's device; alpha, tr, te and p stay on the host.  Same bits as the host-array call.  This route cannot
@@ -600,6 +601,34 @@ int qmri_dict_simulate(qmri_ctx* ctx, int K, int T, const double* alpha, const d
  * every frame of that atom (and of no other).  F_out feeds qmri_dict_compress_dev as it is. */
 int qmri_dict_simulate_dev(qmri_ctx* ctx, int K, int T, const double* alpha, const double* tr, const double* te, const double* d_t1, const double* d_t2,
                            const double* d_b1, const qmri_epg_params* p, void* d_F_out);
+
+/* ---- slice-profile-aware FISP dictionary simulation (extension, no reference counterpart, parity unpinned) ---- */
+/* A slice-selective pulse turns the magnetisation by a flip angle that varies through the slice; a voxel's signal is the integral over that
+ * distribution (Ma et al. 2017; Buonincontri and Sawiak 2016).  The slice is cut into Q = nq sub-slices, 1 <= Q <= 64, with weights weight[Q] and
+ * flip-angle scales prof: [Q], the same in every frame (per_frame = 0), or [T][Q] with q fastest (per_frame = 1).  Every entry of weight and prof
+ * is finite and >= 0 and the weights sum to more than 0; they are NOT normalised here.  For atom k and sub-slice q the recursion of
+ * qmri_dict_simulate runs unchanged, except that step 1 uses a = (alpha_t b1_k) prof[t, q], in that product order; with f_q[t] its step-3 signal,
+ *   F[k, t] = sum_q weight[q] f_q[t],
+ * the sum starting from 0 and running in ascending q, all in fp64, stored as fp64 or rounded once to fp32 as p->out_is_f64 says.  So Q = 1,
+ * weight = {1}, prof = {1} gives the bits of qmri_dict_simulate; a zero weight contributes nothing; and with per_frame = 0 the result is
+ * sum_q weight[q] x (qmri_dict_simulate with b1 prof[q]) up to the one-ulp difference in the product order of a.  The sum is taken on the chip: the
+ * only device memory beyond the outputs is the schedule ((3 + Q) T + Q doubles); no atomics, and an atom's bits depend neither on K nor on its
+ * position in the call. */
+typedef struct {
+    int32_t nq;             /* Q, 1..64 */
+    int32_t per_frame;      /* 0: prof[Q]; 1: prof[T][Q], q fastest */
+    const double* prof;     /* host array, flip-angle scales, finite and >= 0 */
+    const double* weight;   /* host array [Q], finite and >= 0, sum > 0 */
+} qmri_epg_profile;
+/* The arguments, layout and refusals of qmri_dict_simulate, plus: a NULL profile struct, nq outside 1..64, per_frame outside {0, 1}, a NULL prof or
+ * weight, a non-finite or negative entry of either, weights that do not sum to more than 0: QMRI_ERR_INVALID_ARG, decided on the host before the
+ * device is selected (ctx == NULL: the message of the first failing check in qmri_last_error(NULL)).  Returns after its kernel has finished. */
+int qmri_dict_simulate_sp(qmri_ctx* ctx, int K, int T, const double* alpha, const double* tr, const double* te, const double* t1, const double* t2,
+                          const double* b1, const qmri_epg_params* p, const qmri_epg_profile* sp, void* F_out);
+/* The same with t1, t2, b1 and F_out on ctx's device; alpha, tr, te, p, sp and the arrays sp points to stay on the host.  Same bits as the
+ * host-array call.  An atom this route cannot refuse (see qmri_dict_simulate_dev) gets NaN in every frame of that atom (and of no other). */
+int qmri_dict_simulate_sp_dev(qmri_ctx* ctx, int K, int T, const double* alpha, const double* tr, const double* te, const double* d_t1, const double* d_t2,
+                              const double* d_b1, const qmri_epg_params* p, const qmri_epg_profile* sp, void* d_F_out);
 
 /* ---- field map from multi-echo images (extension, no reference counterpart, parity unpinned) ---- */
 /* qmri_set_field_map takes its map f from the caller; this call makes one from L gradient-echo images per slice, by the regularised estimator of

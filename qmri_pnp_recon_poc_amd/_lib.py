@@ -23,7 +23,7 @@ SYMBOLS = [
     "qmri_net_forward_dev", "qmri_denoiser_scheme", "qmri_pnp_admm", "qmri_pnp_admm_dev", "qmri_pnp_admm_batch", "qmri_set_dictionary", "qmri_dict_match",
     "qmri_dict_match_dev", "qmri_dict_match_xfit", "qmri_dict_match_xfit_dev", "qmri_set_dictionary_groups", "qmri_dict_group_assign", "qmri_dict_match_grouped",
     "qmri_dict_match_grouped_dev", "qmri_recon_batch", "qmri_recon_batch_mc",
-    "qmri_coil_compress", "qmri_coil_compress_dev", "qmri_coil_eig", "qmri_recon_batch_mc_cc", "qmri_coil_maps", "qmri_coil_maps_dev", "qmri_dict_compress", "qmri_dict_compress_dev", "qmri_dict_simulate", "qmri_dict_simulate_dev", "qmri_field_map_estimate", "qmri_field_map_estimate_dev", "qmri_llr_prox", "qmri_llr_prox_dev", "qmri_set_llr", "qmri_profile_enable", "qmri_profile_get", "qmri_get_health",
+    "qmri_coil_compress", "qmri_coil_compress_dev", "qmri_coil_eig", "qmri_recon_batch_mc_cc", "qmri_coil_maps", "qmri_coil_maps_dev", "qmri_dict_compress", "qmri_dict_compress_dev", "qmri_dict_simulate", "qmri_dict_simulate_dev", "qmri_dict_simulate_sp", "qmri_dict_simulate_sp_dev", "qmri_field_map_estimate", "qmri_field_map_estimate_dev", "qmri_llr_prox", "qmri_llr_prox_dev", "qmri_set_llr", "qmri_profile_enable", "qmri_profile_get", "qmri_get_health",
     "qmri_debug_lsqr_stamps", "qmri_debug_conv_stamps", "qmri_debug_lsqr_persist", "qmri_debug_dict_filter", "qmri_debug_conv_resident", "qmri_debug_dsvd_gram", "qmri_debug_epg_shift", "qmri_debug_knob",
     "qmri_onnx_read_unetres",
     "qmri_lrtv", "qmri_prox_tv", "qmri_norm_tv", "qmri_synthesize_tsmi", "qmri_synthesize_tsmi_complex",
@@ -71,6 +71,10 @@ class DsvdInfo(C.Structure):
 
 class EpgParams(C.Structure):
     _fields_ = [("nstates", C.c_int32), ("inversion", C.c_int32), ("ti", C.c_double), ("inv_eff", C.c_double), ("out_is_f64", C.c_int32)]
+
+
+class EpgProfile(C.Structure):
+    _fields_ = [("nq", C.c_int32), ("per_frame", C.c_int32), ("prof", C.c_void_p), ("weight", C.c_void_p)]
 
 
 class NufftParams(C.Structure):
@@ -246,6 +250,8 @@ def lib() -> C.CDLL:
     L.qmri_debug_dsvd_gram.argtypes = [vp, i, i, vp, i, i, vp]
     L.qmri_dict_simulate.argtypes = [vp, i, i, vp, vp, vp, vp, vp, vp, C.POINTER(EpgParams), vp]
     L.qmri_dict_simulate_dev.argtypes = [vp, i, i, vp, vp, vp, vp, vp, vp, C.POINTER(EpgParams), vp]
+    L.qmri_dict_simulate_sp.argtypes = [vp, i, i, vp, vp, vp, vp, vp, vp, C.POINTER(EpgParams), C.POINTER(EpgProfile), vp]
+    L.qmri_dict_simulate_sp_dev.argtypes = [vp, i, i, vp, vp, vp, vp, vp, vp, C.POINTER(EpgParams), C.POINTER(EpgProfile), vp]
     L.qmri_debug_epg_shift.argtypes = [vp, i, i, vp, vp]
     L.qmri_field_map_estimate.argtypes = [vp, i, i, i, i, i, vp, dp, vp, C.POINTER(FieldmapParams), vp, vp, C.POINTER(FieldmapInfo)]
     L.qmri_field_map_estimate_dev.argtypes = [vp, i, i, i, i, i, vp, dp, vp, C.POINTER(FieldmapParams), vp, vp, C.POINTER(FieldmapInfo)]

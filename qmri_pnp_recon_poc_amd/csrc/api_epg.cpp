@@ -1,15 +1,17 @@
-// api_epg.cpp -- C ABI of the FISP dictionary simulation by extended phase graphs (include/qmri.h; kernels: epg_kernels.hip).  An EXTENSION with no
-// reference counterpart.  Every refusal is decided here, on the host, before the device is selected; with ctx == NULL the message of the first
+// api_epg.cpp -- C ABI of the FISP dictionary simulation by extended phase graphs, plain and over a slice profile (include/qmri.h; kernels:
+// epg_kernels.hip).  An EXTENSION with no reference counterpart.  Every refusal is decided here, on the host, before the device is selected; with ctx == NULL the message of the first
 // failing check is left in qmri_last_error(NULL), so the argument rules can be exercised on a machine without a GPU.
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <vector>
 #include "qmri_internal.h"
 
 namespace {
-constexpr int EPG_MAX_T = 1024, EPG_MAX_S = 256;
+constexpr int EPG_MAX_T = 1024, EPG_MAX_S = 256, EPG_MAX_Q = 64;
 
-// QMRI_OK, or the code of the first failing check with its message set on ctx (ctx may be NULL).  host_atoms: t1 / t2 / b1 can be read here
+// QMRI_OK, or the code of the first failing check with its message set on ctx (ctx may be NULL; ctx_check comes after
+// these).  host_atoms: t1 / t2 / b1 can be read here
 int epg_checks(qmri_ctx* ctx, int K, int T, const double* alpha, const double* tr, const double* te, const double* t1, const double* t2, const double* b1,
                const qmri_epg_params* p, const void* F_out, bool host_atoms) {
     QMRI_CHECK_ARG(ctx, p, "simulation params must not be NULL");
@@ -35,38 +37,71 @@ int epg_checks(qmri_ctx* ctx, int K, int T, const double* alpha, const double* t
             QMRI_CHECK_ARG(ctx, std::isfinite(t2[k]) && t2[k] > 0.0, "t2 must be finite and > 0 for every atom");
             QMRI_CHECK_ARG(ctx, !b1 || (std::isfinite(b1[k]) && b1[k] >= 0.0), "b1 must be finite and >= 0 for every atom");
         }
+    return QMRI_OK;
+}
+
+// the rules of a slice profile (ctx may be NULL)
+int epg_profile_checks(qmri_ctx* ctx, int T, const qmri_epg_profile* sp) {
+    QMRI_CHECK_ARG(ctx, sp, "slice profile must not be NULL");
+    QMRI_CHECK_ARG(ctx, sp->nq >= 1 && sp->nq <= EPG_MAX_Q, "nq must satisfy 1 <= nq <= 64");
+    QMRI_CHECK_ARG(ctx, sp->per_frame == 0 || sp->per_frame == 1, "per_frame must be 0 or 1");
+    QMRI_CHECK_ARG(ctx, sp->prof && sp->weight, "prof / weight must not be NULL");
+    const size_t np = (size_t)sp->nq * (sp->per_frame ? (size_t)T : 1);
+    for (size_t i = 0; i < np; ++i) QMRI_CHECK_ARG(ctx, std::isfinite(sp->prof[i]) && sp->prof[i] >= 0.0, "prof must be finite and >= 0 in every entry");
+    double sum = 0.0;
+    for (int q = 0; q < sp->nq; ++q) {
+        QMRI_CHECK_ARG(ctx, std::isfinite(sp->weight[q]) && sp->weight[q] >= 0.0, "weight must be finite and >= 0 in every entry");
+        sum += sp->weight[q];
+    }
+    QMRI_CHECK_ARG(ctx, sum > 0.0, "the weights must sum to more than 0");
+    return QMRI_OK;
+}
+
+int ctx_check(qmri_ctx* ctx) {
     if (!ctx) { qmri_set_error(nullptr, "invalid argument: ctx must not be NULL"); return QMRI_ERR_INVALID_ARG; }
     return QMRI_OK;
 }
 
-// the schedule on the device (alpha, tr, te: 3 T doubles) and the launch; the stream is idle on return
+// the schedule on the device and the launch; the stream is idle on return.  Without a profile: alpha [T], tr [T], te [T].  With one: T frame
+// records (alpha_t, tr_t, te_t, prof[t, 0 .. Q-1]; a per_frame = 0 profile repeated in every record), then weight [Q]: (3 + Q) T + Q doubles
 int epg_run(qmri_ctx* ctx, int K, int T, const double* alpha, const double* tr, const double* te, const double* d_t1, const double* d_t2,
-            const double* d_b1, const qmri_epg_params& p, void* d_F) {
-    std::vector<double> sched((size_t)3 * T);
+            const double* d_b1, const qmri_epg_params& p, const qmri_epg_profile* sp, void* d_F) {
+    const int Q = sp ? sp->nq : 0, FR = 3 + Q;
+    std::vector<double> sched(sp ? (size_t)FR * T + Q : (size_t)3 * T);
     bool const_timing = true;
     for (int t = 0; t < T; ++t) {
-        sched[t] = alpha[t]; sched[T + t] = tr[t]; sched[2 * T + t] = te[t];
         const_timing = const_timing && tr[t] == tr[0] && te[t] == te[0];
+        if (!sp) { sched[t] = alpha[t]; sched[T + t] = tr[t]; sched[2 * T + t] = te[t]; continue; }
+        double* fr = sched.data() + (size_t)t * FR;
+        fr[0] = alpha[t]; fr[1] = tr[t]; fr[2] = te[t];
+        std::copy_n(sp->prof + (sp->per_frame ? (size_t)t * Q : 0), Q, fr + 3);
     }
+    if (sp) std::copy_n(sp->weight, Q, sched.data() + (size_t)FR * T);
     DevBuf<double> ds;
     QMRI_TRY(dev_alloc(ctx, &ds.p, sched.size()));
     QMRI_HIP(ctx, hipMemcpyAsync(ds.p, sched.data(), sched.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    QMRI_TRY(epg_simulate_dev(ctx, K, T, ds, d_t1, d_t2, d_b1, p, const_timing, d_F));
+    if (sp) QMRI_TRY(epg_simulate_sp_dev(ctx, K, T, Q, ds, d_t1, d_t2, d_b1, p, const_timing, d_F));
+    else QMRI_TRY(epg_simulate_dev(ctx, K, T, ds, d_t1, d_t2, d_b1, p, const_timing, d_F));
     QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return QMRI_OK;
 }
-}  // namespace
 
-extern "C" int qmri_dict_simulate_dev(qmri_ctx* ctx, int K, int T, const double* alpha, const double* tr, const double* te, const double* d_t1,
-                                      const double* d_t2, const double* d_b1, const qmri_epg_params* p, void* d_F_out) {
+// the device-array and the host-array route behind all four entry points.  with_profile: the _sp calls, whose sp is checked (a NULL one is a
+// refusal); the plain calls pass sp == NULL and run k_epg as before
+int simulate_dev(qmri_ctx* ctx, int K, int T, const double* alpha, const double* tr, const double* te, const double* d_t1, const double* d_t2,
+                 const double* d_b1, const qmri_epg_params* p, const qmri_epg_profile* sp, bool with_profile, void* d_F_out) {
     QMRI_TRY(epg_checks(ctx, K, T, alpha, tr, te, d_t1, d_t2, d_b1, p, d_F_out, false));
+    if (with_profile) QMRI_TRY(epg_profile_checks(ctx, T, sp));
+    QMRI_TRY(ctx_check(ctx));
     QMRI_HIP(ctx, hipSetDevice(ctx->device));
-    return epg_run(ctx, K, T, alpha, tr, te, d_t1, d_t2, d_b1, *p, d_F_out);
+    return epg_run(ctx, K, T, alpha, tr, te, d_t1, d_t2, d_b1, *p, sp, d_F_out);
 }
 
-extern "C" int qmri_dict_simulate(qmri_ctx* ctx, int K, int T, const double* alpha, const double* tr, const double* te, const double* t1, const double* t2,
-                                  const double* b1, const qmri_epg_params* p, void* F_out) {
+int simulate_host(qmri_ctx* ctx, int K, int T, const double* alpha, const double* tr, const double* te, const double* t1, const double* t2, const double* b1,
+                  const qmri_epg_params* p, const qmri_epg_profile* sp, bool with_profile, void* F_out) {
     QMRI_TRY(epg_checks(ctx, K, T, alpha, tr, te, t1, t2, b1, p, F_out, true));
+    if (with_profile) QMRI_TRY(epg_profile_checks(ctx, T, sp));
+    QMRI_TRY(ctx_check(ctx));
     QMRI_HIP(ctx, hipSetDevice(ctx->device));
     const size_t nF = (size_t)K * T * (p->out_is_f64 ? sizeof(double) : sizeof(float));
     DevBuf<double> d1, d2, db;
@@ -78,10 +113,31 @@ extern "C" int qmri_dict_simulate(qmri_ctx* ctx, int K, int T, const double* alp
     QMRI_HIP(ctx, hipMemcpyAsync(d1.p, t1, (size_t)K * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     QMRI_HIP(ctx, hipMemcpyAsync(d2.p, t2, (size_t)K * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     if (b1) QMRI_HIP(ctx, hipMemcpyAsync(db.p, b1, (size_t)K * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    QMRI_TRY(epg_run(ctx, K, T, alpha, tr, te, d1, d2, db, *p, dF.p));
+    QMRI_TRY(epg_run(ctx, K, T, alpha, tr, te, d1, d2, db, *p, sp, dF.p));
     QMRI_HIP(ctx, hipMemcpyAsync(F_out, dF.p, nF, hipMemcpyDeviceToHost, ctx->stream));
     QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return QMRI_OK;
+}
+}  // namespace
+
+extern "C" int qmri_dict_simulate_dev(qmri_ctx* ctx, int K, int T, const double* alpha, const double* tr, const double* te, const double* d_t1,
+                                      const double* d_t2, const double* d_b1, const qmri_epg_params* p, void* d_F_out) {
+    return simulate_dev(ctx, K, T, alpha, tr, te, d_t1, d_t2, d_b1, p, nullptr, false, d_F_out);
+}
+
+extern "C" int qmri_dict_simulate(qmri_ctx* ctx, int K, int T, const double* alpha, const double* tr, const double* te, const double* t1, const double* t2,
+                                  const double* b1, const qmri_epg_params* p, void* F_out) {
+    return simulate_host(ctx, K, T, alpha, tr, te, t1, t2, b1, p, nullptr, false, F_out);
+}
+
+extern "C" int qmri_dict_simulate_sp_dev(qmri_ctx* ctx, int K, int T, const double* alpha, const double* tr, const double* te, const double* d_t1,
+                                         const double* d_t2, const double* d_b1, const qmri_epg_params* p, const qmri_epg_profile* sp, void* d_F_out) {
+    return simulate_dev(ctx, K, T, alpha, tr, te, d_t1, d_t2, d_b1, p, sp, true, d_F_out);
+}
+
+extern "C" int qmri_dict_simulate_sp(qmri_ctx* ctx, int K, int T, const double* alpha, const double* tr, const double* te, const double* t1,
+                                     const double* t2, const double* b1, const qmri_epg_params* p, const qmri_epg_profile* sp, void* F_out) {
+    return simulate_host(ctx, K, T, alpha, tr, te, t1, t2, b1, p, sp, true, F_out);
 }
 
 extern "C" int qmri_debug_epg_shift(qmri_ctx* ctx, int S, int nshift, const double* in, double* out) {

@@ -9,6 +9,7 @@
 //                       computes that frame's cos / sin of alpha_t b1 (and, when TR / TE vary from frame to frame, its four exponentials) once and
 //                       leaves them in LDS, so a transcendental costs 1 / FB per lane and frame; lane 0 of each group stages the signal F+_0 in LDS,
 //                       and after the block the workgroup writes FB x APW values, APW atoms contiguous per frame (8 at S = 32: 64 B).
+//   k_epg_sp<G, R>      the same per (atom, sub-slice of a slice profile), the weighted sum over the sub-slices taken in LDS (see its comment).
 //   k_epg_shift<G, R>   the spoiler alone, n times on one atom's given state (qmri_debug_epg_shift: exact-integer test of the lane moves).
 // No atomics, no reduction across atoms: equal inputs give equal bits.
 #include <cmath>
@@ -22,6 +23,7 @@ constexpr int NT = 256;          // threads per workgroup
 constexpr int FB = 16;           // frames per block (<= the smallest G)
 constexpr int NQ = 6;            // doubles per atom and frame in LDS: cos, sin, E1(TE), E2(TE), E1(TR - TE), E2(TR - TE)
 constexpr int ROW = FB * NQ + 2; // LDS row stride per atom in doubles (784 B: 16-byte aligned, the groups of a wave fall in distinct banks)
+constexpr int EPG_SP_MAX_T = 1024; // frames k_epg_sp's pass accumulator holds (the T limit of the entry points)
 
 // v of the lane `d` below (d = +1) or above (d = -1) within a 16-lane row, zero past the row's ends
 template <int D> __device__ __forceinline__ double row_move(double v) {
@@ -136,6 +138,119 @@ __global__ void __launch_bounds__(NT) k_epg(const double* __restrict__ sched, in
     }
 }
 
+// The slice-profile-aware simulation: the work item is the pair (atom, sub-slice q), one group of G lanes per pair with
+// k_epg's scheme unchanged; the RF argument is (alpha_t b1) prof[t, q].  sched: T frame records (alpha_t, tr_t, te_t, prof[t, 0 .. Q-1]), then
+// weight [Q].
+// A workgroup holds GPW = NT / G groups.  Q <= GPW: it simulates A = GPW / Q atoms in one pass, group g = a Q + q (the GPW - A Q groups left
+// over repeat a valid pair and their staged signals are never read).  Q > GPW: it simulates one atom in ceil(Q / GPW) passes of GPW sub-slices,
+// each pass over the whole train, and carries the partial sums of the T frames in the LDS array acc, which it alone reads and writes.  Per frame
+// block one lane per (frame, atom) adds w_q x the staged signals in ascending q (from 0 in the first pass, from acc afterwards) and the last pass
+// stores: every output is written once, without atomics, and an atom's bits depend on Q and S only.
+// Scalar registers are the scarce resource of this loop nest (sincos and exp keep their constants in them): the kernel is compiled once per
+// timing kind (CT), keeps the bad-atom flag and the reducing lanes' addresses in vector registers, and re-reads S from LDS in every frame so that
+// epg_shift's R padding masks are not kept in scalar registers across the loops.  With that no instantiation spills.
+template <int G, int R, bool CT>                           // CT: TR and TE are the same in every frame
+__global__ void __launch_bounds__(NT) k_epg_sp(const double* __restrict__ sched, int T, int K, int S, int Q, const double* __restrict__ t1,
+                                               const double* __restrict__ t2, const double* __restrict__ b1, int inversion, double ti, double inv_eff,
+                                               void* __restrict__ Fout, int out_f64) {
+    constexpr int GPW = NT / G;
+    __shared__ __attribute__((aligned(16))) double sc[GPW * ROW];
+    __shared__ double sig[FB * GPW];
+    __shared__ double acc[EPG_SP_MAX_T];
+    __shared__ double wl[64];
+    __shared__ int nkeep;                                    // S (see above)
+    const int FR = 3 + Q;                                    // doubles per frame record
+    const int QP = min(Q, GPW), A = GPW / QP;                // sub-slices per pass, atoms per workgroup (1 when Q > GPW)
+    const int tid = threadIdx.x, g = tid / G, j = tid % G, ql = g % QP;
+    const int k0 = blockIdx.x * A;                                               // < K <= 2^30
+    const int k = min(k0 + min(g / QP, A - 1), K - 1);                           // the groups past A, K or Q repeat a valid pair and are never read
+    double T1 = t1[k], T2 = t2[k], B1 = b1 ? b1[k] : 1.0;
+    const double inf = std::numeric_limits<double>::infinity();
+    const bool bad = !(T1 > 0.0 && T1 < inf && T2 > 0.0 && T2 < inf && B1 >= 0.0 && B1 < inf);
+    if (bad) { T1 = 1.0; T2 = 1.0; B1 = 1.0; }                                   // its row becomes NaN at the store: w_q NaN is NaN for every w_q
+    const int nanbits = bad ? -1 : 0;                                            // or-ed into the staged signal: all ones is a NaN
+    double ea1 = 0.0, ea2 = 0.0, eb1 = 0.0, eb2 = 0.0;
+    if constexpr (CT) {
+        const double a = sched[2], b = sched[1] - a;
+        ea1 = exp(-a / T1); ea2 = exp(-a / T2); eb1 = exp(-b / T1); eb2 = exp(-b / T2);
+    }
+    double z0 = 0.0;                                         // Z_0 before the first frame (lane 0 of a group), the same in every pass
+    if (j == 0) {
+        z0 = 1.0;
+        if (inversion) {
+            const double e = exp(-ti / T1);
+            z0 = (-inv_eff * z0) * e + (1.0 - e);
+        }
+    }
+    if (tid == 0) nkeep = S;
+    if (tid < Q) wl[tid] = sched[(size_t)T * FR + tid];                         // read after the first __syncthreads()
+    // the reducing lanes: lane tid < FB A sums frame tid / A of atom tid % A of every block (FB A <= NT); the lanes past K never pass rt < nf
+    const int ra = tid % A, rt = k0 + ra < K ? tid / A : FB;
+    const double* sg = sig + min(rt, FB - 1) * GPW + ra * QP;
+    const size_t esz = out_f64 ? sizeof(double) : sizeof(float), ostep = (size_t)FB * (size_t)K * esz;
+    char* const out0 = static_cast<char*>(Fout) + ((size_t)min(rt, FB - 1) * (size_t)K + (size_t)(k0 + ra)) * esz;      // this lane's frame of block 0
+    double* my = sc + g * ROW;
+    for (int q0 = 0; q0 < Q; q0 += QP) {                     // one pass
+        const int nq = min(QP, Q - q0), q = min(q0 + ql, Q - 1);
+        double fp[R], fm[R], z[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) fp[r] = fm[r] = z[r] = 0.0;
+        z[0] = z0;
+        char* out = out0;
+        for (int t0 = 0; t0 < T; t0 += FB) {
+            const int nf = min(FB, T - t0);
+            __syncthreads();                                 // the previous block's sc and sig have been read
+            if (j < nf) {
+                const double* fr = sched + (t0 + j) * FR;
+                double s, c;
+                sincos((fr[0] * B1) * fr[3 + q], &s, &c);
+                my[j * NQ + 0] = c;
+                my[j * NQ + 1] = s;
+                if constexpr (!CT) {
+                    const double a = fr[2], b = fr[1] - a;
+                    my[j * NQ + 2] = exp(-a / T1);
+                    my[j * NQ + 3] = exp(-a / T2);
+                    my[j * NQ + 4] = exp(-b / T1);
+                    my[j * NQ + 5] = exp(-b / T2);
+                }
+            }
+            __syncthreads();
+            for (int tt = 0; tt < nf; ++tt) {
+                const double2 cs = *reinterpret_cast<const double2*>(my + tt * NQ);
+                const double c = cs.x, s = cs.y, c2 = (1.0 + c) * 0.5, s2 = (1.0 - c) * 0.5;
+                if constexpr (!CT) {
+                    const double2 ea = *reinterpret_cast<const double2*>(my + tt * NQ + 2), eb = *reinterpret_cast<const double2*>(my + tt * NQ + 4);
+                    ea1 = ea.x; ea2 = ea.y; eb1 = eb.x; eb2 = eb.y;
+                }
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const double p = fp[r], m = fm[r], zz = z[r];
+                    fp[r] = (c2 * p - s2 * m + s * zz) * ea2;
+                    fm[r] = (-s2 * p + c2 * m + s * zz) * ea2;
+                    z[r] = (-0.5 * s * (p + m) + c * zz) * ea1;
+                }
+                if (j == 0) {
+                    z[0] += 1.0 - ea1;
+                    sig[tt * GPW + g] = __hiloint2double(__double2hiint(fp[0]) | nanbits, __double2loint(fp[0]) | nanbits);
+                }
+#pragma unroll
+                for (int r = 0; r < R; ++r) { fp[r] *= eb2; fm[r] *= eb2; z[r] *= eb1; }
+                if (j == 0) z[0] += 1.0 - eb1;
+                epg_shift<G, R>(fp, fm, j, nkeep);
+            }
+            __syncthreads();
+            if (rt < nf) {                                   // the atoms of a frame contiguous
+                double v = q0 ? acc[t0 + rt] : 0.0;          // written by this lane in the pass before (A = 1: rt = tid)
+                for (int i = 0; i < nq; ++i) v += wl[q0 + i] * sg[i];
+                if (q0 + QP < Q) acc[t0 + rt] = v;
+                else if (out_f64) *reinterpret_cast<double*>(out) = v;
+                else *reinterpret_cast<float*>(out) = (float)v;
+            }
+            out += ostep;
+        }
+    }
+}
+
 // st: F+ [S], F- [S], Z [S] of one atom; one group of one wave does the work
 template <int G, int R> __global__ void __launch_bounds__(64) k_epg_shift(int S, int nshift, const double* __restrict__ in, double* __restrict__ out) {
     const int lane = threadIdx.x, j = lane % G;
@@ -179,6 +294,25 @@ int epg_simulate_dev(qmri_ctx* ctx, int K, int T, const double* d_sched, const d
         const unsigned grid = (unsigned)(((long long)K + APW - 1) / APW);
         k_epg<G, R><<<grid, NT, 0, ctx->stream>>>(d_sched, T, K, p.nstates, d_t1, d_t2, d_b1, p.inversion, p.ti, p.inv_eff, const_timing ? 1 : 0, d_F,
                                                   p.out_is_f64);
+    });
+    QMRI_HIP(ctx, hipGetLastError());
+    return QMRI_OK;
+}
+
+int epg_sp_atoms_per_workgroup(int S, int Q) {
+    int gpw = epg_atoms_per_workgroup(S);
+    return Q >= gpw ? 1 : gpw / Q;
+}
+
+int epg_simulate_sp_dev(qmri_ctx* ctx, int K, int T, int Q, const double* d_sched, const double* d_t1, const double* d_t2, const double* d_b1,
+                        const qmri_epg_params& p, bool const_timing, void* d_F) {
+    if (T < 1 || T > EPG_SP_MAX_T || Q < 1 || Q > 64) { qmri_set_error(ctx, "internal: k_epg_sp takes 1 <= T <= 1024 and 1 <= Q <= 64"); return QMRI_ERR_INVALID_ARG; }
+    epg_dispatch(p.nstates, [&](auto g, auto r) {
+        constexpr int G = decltype(g)::value, R = decltype(r)::value;
+        const int A = epg_sp_atoms_per_workgroup(p.nstates, Q);
+        const unsigned grid = (unsigned)(((long long)K + A - 1) / A);
+        auto* kern = const_timing ? k_epg_sp<G, R, true> : k_epg_sp<G, R, false>;
+        kern<<<grid, NT, 0, ctx->stream>>>(d_sched, T, K, p.nstates, Q, d_t1, d_t2, d_b1, p.inversion, p.ti, p.inv_eff, d_F, p.out_is_f64);
     });
     QMRI_HIP(ctx, hipGetLastError());
     return QMRI_OK;

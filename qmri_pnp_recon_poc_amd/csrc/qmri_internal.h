@@ -359,6 +359,10 @@ int dsvd_project_dev(qmri_ctx* ctx, int K, int T, int s, const void* d_F, bool f
 int epg_atoms_per_workgroup(int S);      // atoms a workgroup simulates (= the contiguous run of its stores) with S states
 int epg_simulate_dev(qmri_ctx* ctx, int K, int T, const double* d_sched, const double* d_t1, const double* d_t2, const double* d_b1 /* or NULL */,
                      const qmri_epg_params& p, bool const_timing, void* d_F);
+// the slice-profile-aware simulation.  d_sched: T frame records (alpha_t, tr_t, te_t, prof[t, 0 .. Q-1]), then weight [Q]
+int epg_sp_atoms_per_workgroup(int S, int Q);      // atoms a workgroup simulates with S states and Q sub-slices (1 when Q fills its groups)
+int epg_simulate_sp_dev(qmri_ctx* ctx, int K, int T, int Q, const double* d_sched, const double* d_t1, const double* d_t2,
+                        const double* d_b1 /* or NULL */, const qmri_epg_params& p, bool const_timing, void* d_F);
 int epg_shift_dev(qmri_ctx* ctx, int S, int nshift, const double* d_in, double* d_out);      // the spoiler alone on one atom's state (3 S doubles)
 
 // field map from multi-echo images (fmap_kernels.hip, api_fmap.cpp).  All d_ pointers are device pointers; the stream is

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import AdmmParams, CcParams, CsmInfo, CsmParams, DcfInfo, DcfParams, DsvdInfo, DsvdParams, EpgParams, FieldmapInfo, FieldmapParams, LlrParams, LrtvInfo, LrtvParams, NetDesc, NufftParams, OffresInfo, OffresNormalInfo, OffresNormalParams, OffresParams, Profile
+from ._lib import AdmmParams, CcParams, CsmInfo, CsmParams, DcfInfo, DcfParams, DsvdInfo, DsvdParams, EpgParams, EpgProfile, FieldmapInfo, FieldmapParams, LlrParams, LrtvInfo, LrtvParams, NetDesc, NufftParams, OffresInfo, OffresNormalInfo, OffresNormalParams, OffresParams, Profile
 
 ARCH_UNETRES, ARCH_SEQ_CONV = 0, 1
 SOLVER_LSQR, SOLVER_DIRECT = 0, 1
@@ -99,6 +99,32 @@ def simulation_arguments(alpha, tr, te, t1, t2, b1, nstates, inversion, ti, inv_
         raise ValueError("ti must be >= 0 and inv_eff in (0, 1]")
     p = EpgParams(int(nstates), 1 if inversion else 0, float(ti), float(inv_eff), int(np.dtype(dtype) == np.dtype(np.float64)))
     return a, sched[0], sched[1], atoms[0], atoms[1], atoms[2] if b1 is not None else None, p
+
+
+def slice_profile_arguments(slice_profile, slice_weights, T):
+    """The slice profile of Engine.simulate_dictionary as the library takes it: (prof buffer, weight buffer, EpgProfile), or None without one.
+    slice_profile is [Q] (the same flip-angle scale in every frame) or [T, Q] (one row per frame), 1 <= Q <= 64; slice_weights is [Q] and
+    defaults to 1 / Q.  Every entry is finite and >= 0 and the weights sum to more than 0; they are not normalised.  The two buffers must outlive
+    the call that takes the EpgProfile."""
+    if slice_profile is None:
+        if slice_weights is not None:
+            raise ValueError("slice_weights needs a slice_profile")
+        return None
+    if np.iscomplexobj(slice_profile) or np.iscomplexobj(slice_weights):
+        raise ValueError("slice_profile and slice_weights must be real")
+    prof = np.asarray(slice_profile, dtype=np.float64)
+    if prof.ndim not in (1, 2) or (prof.ndim == 2 and prof.shape[0] != T):
+        raise ValueError(f"slice_profile must have shape [Q] or [T, Q] with T = {T}")
+    prof = np.ascontiguousarray(prof)
+    Q = prof.shape[-1]
+    if not (1 <= Q <= 64):
+        raise ValueError("slice_profile must hold 1 <= Q <= 64 sub-slices")
+    w = np.full(Q, 1.0 / Q) if slice_weights is None else np.ascontiguousarray(np.asarray(slice_weights, dtype=np.float64))
+    if w.shape != (Q,):
+        raise ValueError(f"slice_weights must have shape [Q] = [{Q}]")
+    if not (np.all(np.isfinite(prof)) and np.all(prof >= 0) and np.all(np.isfinite(w)) and np.all(w >= 0) and w.sum() > 0):
+        raise ValueError("slice_profile and slice_weights must be finite and >= 0, and the weights must sum to more than 0")
+    return prof, w, EpgProfile(Q, int(prof.ndim == 2), prof.ctypes.data, w.ctypes.data)
 
 
 def fieldmap_arguments(Y, echo_times, iters=0, beta=0.0, phase_sign=-1, f_init=None):
@@ -912,26 +938,34 @@ class Engine:
                 "info": {"s": int(info.s), "iters": int(info.iters), "converged": int(info.converged), "energy_reached": int(info.energy_reached),
                          "max_resid": float(info.max_resid), "energy_kept": float(info.energy_kept)}}
 
-    def simulate_dictionary(self, alpha, tr, te, t1, t2, b1=None, nstates=32, inversion=True, ti=0.0, inv_eff=1.0, dtype=np.float64):
+    def simulate_dictionary(self, alpha, tr, te, t1, t2, b1=None, nstates=32, inversion=True, ti=0.0, inv_eff=1.0, dtype=np.float64,
+                            slice_profile=None, slice_weights=None):
         """The fingerprints of a FISP-MRF sequence by extended phase graphs on the device (extension, no reference counterpart; include/qmri.h
         qmri_dict_simulate).  alpha [T] flip angles in radians, T <= 1024; tr, te in seconds, scalars (broadcast to T) or [T]; t1, t2 (seconds)
         and b1 (transmit scale, None: 1) are broadcast against each other and flattened to the K atoms.  nstates: configuration states kept
         (1..256; the truncation is part of the result).  inversion: an inversion pulse of efficiency inv_eff, TI = ti before the train.
+        slice_profile [Q] or [T, Q] (with slice_weights [Q], default 1 / Q): the simulation integrated over a slice profile (qmri_dict_simulate_sp;
+        DESIGN.md section 26) -- F = sum_q w_q x the fingerprint with flip angles alpha_t b1 slice_profile[t, q]; synth.rf_slice_profile makes one.
         Returns F [K, T] in dtype (float64, or float32: the float64 result rounded once).  Needs no operator."""
         a, trv, tev, T1, T2, B1, p = simulation_arguments(alpha, tr, te, t1, t2, b1, nstates, inversion, ti, inv_eff, dtype)
         K, T = T1.size, a.size
+        sp = slice_profile_arguments(slice_profile, slice_weights, T)
         F = np.empty(K * T, np.float64 if p.out_is_f64 else np.float32)
-        self._check(self.L.qmri_dict_simulate(self.h, K, T, _vp(a), _vp(trv), _vp(tev), _vp(T1), _vp(T2), _vp(B1), C.byref(p), _vp(F)))
+        if sp is None:
+            self._check(self.L.qmri_dict_simulate(self.h, K, T, _vp(a), _vp(trv), _vp(tev), _vp(T1), _vp(T2), _vp(B1), C.byref(p), _vp(F)))
+        else:
+            self._check(self.L.qmri_dict_simulate_sp(self.h, K, T, _vp(a), _vp(trv), _vp(tev), _vp(T1), _vp(T2), _vp(B1), C.byref(p), C.byref(sp[2]), _vp(F)))
         return F.reshape((K, T), order="F")
 
     def simulate_compress_dictionary(self, alpha, tr, te, t1, t2, b1=None, s=None, energy=None, s_max=16, nstates=32, inversion=True, ti=0.0,
-                                     inv_eff=1.0):
+                                     inv_eff=1.0, slice_profile=None, slice_weights=None):
         """simulate_dictionary followed by compress_dictionary on the same device buffer: the K x T float64 fingerprints never leave the device.
-        Returns what compress_dictionary returns."""
+        slice_profile / slice_weights: as in simulate_dictionary.  Returns what compress_dictionary returns."""
         if (s is None) == (energy is None):
             raise ValueError("give exactly one of s and energy")
         a, trv, tev, T1, T2, B1, p = simulation_arguments(alpha, tr, te, t1, t2, b1, nstates, inversion, ti, inv_eff, np.float64)
         K, T = T1.size, a.size
+        sp = slice_profile_arguments(slice_profile, slice_weights, T)
         if s is not None and (int(s) != s or not (1 <= int(s) <= min(16, K, T))):
             raise ValueError(f"s must be an integer with 1 <= s <= min(16, K, T) = {min(16, K, T)}")
         if s is None and (int(s_max) != s_max or not (1 <= int(s_max) <= 16) or not (0.0 < float(energy) <= 1.0)):
@@ -949,7 +983,11 @@ class Engine:
             for d, h in ((d_t1, T1), (d_t2, T2)) + (((d_b1, B1),) if B1 is not None else ()):
                 if hip.hipMemcpy(d, _vp(h), h.nbytes, 1) != 0:
                     raise RuntimeError("hipMemcpy to the device failed")
-            self._check(self.L.qmri_dict_simulate_dev(self.h, K, T, _vp(a), _vp(trv), _vp(tev), d_t1, d_t2, d_b1 if B1 is not None else None, C.byref(p), d_F))
+            if sp is None:
+                self._check(self.L.qmri_dict_simulate_dev(self.h, K, T, _vp(a), _vp(trv), _vp(tev), d_t1, d_t2, d_b1 if B1 is not None else None, C.byref(p), d_F))
+            else:
+                self._check(self.L.qmri_dict_simulate_sp_dev(self.h, K, T, _vp(a), _vp(trv), _vp(tev), d_t1, d_t2, d_b1 if B1 is not None else None, C.byref(p),
+                                                             C.byref(sp[2]), d_F))
             self._check(self.L.qmri_dict_compress_dev(self.h, K, T, d_F, 1, C.byref(q), C.byref(got), d_V, d_D, d_n, _vp(eig), C.byref(info)))
             for d, h in ((d_V, V), (d_D, D), (d_n, nd)):
                 if hip.hipMemcpy(_vp(h), d, h.nbytes, 2) != 0:

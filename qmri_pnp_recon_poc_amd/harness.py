@@ -80,7 +80,7 @@ def compress_dictionary(dic, s=None, energy=None, s_max=16, device=0):
 
 
 def simulate_dictionary(alpha, tr, te, t1_grid, t2_grid, s=None, energy=None, nstates=32, inversion=True, ti=0.0, inv_eff=1.0, b1=None, s_max=16,
-                        device=0, b1_grid=None):
+                        device=0, b1_grid=None, slice_profile=None, slice_weights=None):
     """A FISP-MRF dictionary from a flip-angle train: the fingerprints of every (T1, T2) of the grid by extended phase graphs
     (Engine.simulate_dictionary), then their SVD compression (Engine.compress_dictionary) on the same device buffer -- the K x T fingerprints
     never cross to the host.  An extension; the reference only loads compressed files.  The atoms are the ij-meshgrid of t1_grid and t2_grid as
@@ -89,7 +89,10 @@ def simulate_dictionary(alpha, tr, te, t1_grid, t2_grid, s=None, energy=None, ns
     of load_dictionary (V, D, normD, lut) plus eig and info; recon_tsmis runs on the result unchanged.
     b1_grid (ascending transmit scales, instead of b1): a B1-resolved dictionary -- the (T1, T2) atoms of b1_grid[0], then
     those of b1_grid[1], ... in one simulation with one joint SVD; lut = (T1, T2, b1) and the result carries group_ptr and group_val, which
-    recon_tsmis(..., b1_map=...) hands to the grouped match."""
+    recon_tsmis(..., b1_map=...) hands to the grouped match.
+    slice_profile [Q] or [T, Q], slice_weights [Q] (default 1 / Q): every atom is integrated over that slice profile (Engine.simulate_dictionary;
+    DESIGN.md section 26).  It composes with b1 and b1_grid -- the flip angle of sub-slice q is alpha_t b1 slice_profile[t, q] -- and leaves the
+    atom order, lut and groups unchanged."""
     from .engine import Engine
     t1g, t2g = np.asarray(t1_grid, dtype=np.float64).ravel(), np.asarray(t2_grid, dtype=np.float64).ravel()
     T1, T2 = (a.ravel() for a in np.meshgrid(t1g, t2g, indexing="ij"))
@@ -103,10 +106,11 @@ def simulate_dictionary(alpha, tr, te, t1_grid, t2_grid, s=None, energy=None, ns
         n = T1.size
         T1, T2, b1 = np.tile(T1, bg.size), np.tile(T2, bg.size), np.repeat(bg, n)                # group-major
         groups = {"group_ptr": (np.arange(bg.size + 1) * n).astype(np.int32), "group_val": bg.copy()}
+    sp = {} if slice_profile is None and slice_weights is None else {"slice_profile": slice_profile, "slice_weights": slice_weights}
     eng = Engine(device)
     try:
         out = eng.simulate_compress_dictionary(alpha, tr, te, T1, T2, b1=b1, s=s, energy=energy, s_max=s_max, nstates=nstates, inversion=inversion,
-                                               ti=ti, inv_eff=inv_eff)
+                                               ti=ti, inv_eff=inv_eff, **sp)
     finally:
         eng.close()
     cols = [T1, T2] + ([b1] if groups else [])

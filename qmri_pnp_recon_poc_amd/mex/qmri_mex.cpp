@@ -32,6 +32,7 @@
 //   * 'coil_maps' estimates coil sensitivity maps from calibration data (qmri_coil_maps; extension).
 //   * 'dict_compress' compresses a simulated dictionary to its SVD subspace (qmri_dict_compress; extension); it needs no plan.
 //   * 'dict_simulate' simulates the fingerprints of a FISP-MRF sequence by extended phase graphs (qmri_dict_simulate; extension); it needs no plan.
+//   * 'dict_simulate_sp' is 'dict_simulate' integrated over a slice profile (qmri_dict_simulate_sp; extension); it needs no plan.
 //   * 'set_llr' / 'clear_llr' select the locally low-rank proximal step as Step 2 of 'pnp_admm' (qmri_set_llr; extension), which
 //     then needs no denoiser; 'llr_prox' is the step alone (qmri_llr_prox).
 //   * 'field_map_estimate' estimates the field map that 'set_field_map' takes from multi-echo images (qmri_field_map_estimate; extension, DESIGN.md
@@ -850,6 +851,56 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         mxArray* Fo = mxCreateNumericMatrix(K, T, p.out_is_f64 ? mxDOUBLE_CLASS : mxSINGLE_CLASS, mxREAL);
         const int st = qmri_dict_simulate(ctx(), (int)K, (int)T, mxGetDoubles(prhs[1]), sched[0].data(), sched[1].data(), mxGetDoubles(prhs[4]), mxGetDoubles(prhs[5]),
                                           has_b1 ? mxGetDoubles(prhs[6]) : nullptr, &p, mxGetData(Fo));
+        if (st != QMRI_OK) mxDestroyArray(Fo);
+        check(st);
+        plhs[0] = Fo;
+    } else if (c == "dict_simulate_sp") {            // F = qmri_mex('dict_simulate_sp', alpha, tr, te, t1, t2, b1, params, prof, w)
+        // extension (no reference counterpart): 'dict_simulate' integrated over a slice profile (qmri_dict_simulate_sp).  The
+        // first seven arguments are those of 'dict_simulate'.  w: Q weights, 1 <= Q <= 64; prof: the flip-angle scales, Q x 1 (the same in every
+        // frame) or Q x T (column-major: q fastest); both real double.  F is K x T.
+        need(nrhs, 10, "F = qmri_mex('dict_simulate_sp', alpha, tr, te, t1, t2, b1, params, prof, w)");
+        want(mxIsStruct(prhs[7]), "qmri:dict_simulate_sp:params", "params must be a struct (fields nstates, inversion, ti, inv_eff, single)");
+        auto real_vec = [](const mxArray* a, const char* id, const char* msg) {
+            want(mxIsDouble(a) && !mxIsComplex(a), id, msg);
+            return mxGetNumberOfElements(a);
+        };
+        const size_t T = real_vec(prhs[1], "qmri:dict_simulate_sp:alpha", "alpha must be a real double vector (complex flip angles are not supported)");
+        want(T >= 1 && T <= 1024, "qmri:dict_simulate_sp:alpha", "alpha must hold 1 <= T <= 1024 flip angles");
+        std::vector<double> sched[2];
+        const char* sid[2] = {"qmri:dict_simulate_sp:tr", "qmri:dict_simulate_sp:te"};
+        for (int q = 0; q < 2; ++q) {
+            const size_t n = real_vec(prhs[2 + q], sid[q], "tr / te must be real double, one value or one per frame");
+            want(n == 1 || n == T, sid[q], "tr / te must be real double, one value or one per frame");
+            sched[q].resize(T);
+            for (size_t t = 0; t < T; ++t) sched[q][t] = mxGetDoubles(prhs[2 + q])[n == 1 ? 0 : t];
+        }
+        const char* aid = "qmri:dict_simulate_sp:atoms";
+        const size_t K = real_vec(prhs[4], aid, "t1, t2 and b1 must be real double (complex values are not supported)");
+        want(K >= 1 && K <= ((size_t)1 << 30) && real_vec(prhs[5], aid, "t1, t2 and b1 must be real double (complex values are not supported)") == K, aid,
+             "t1 and t2 must hold the same number K >= 1 of atoms");
+        const bool has_b1 = mxGetNumberOfElements(prhs[6]) > 0;
+        if (has_b1) want(real_vec(prhs[6], aid, "t1, t2 and b1 must be real double (complex values are not supported)") == K, aid, "b1 must be [] or hold K values");
+        const mxArray* P = prhs[7];
+        const mxArray* f;
+        const char* pid = "qmri:dict_simulate_sp:params";
+        qmri_epg_params p = {32, 1, 0.0, 1.0, 1};
+        if ((f = mxGetField(P, 0, "nstates"))) p.nstates = int_arg(f, 1, 256, pid, "params.nstates must be an integer in [1, 256]");
+        if ((f = mxGetField(P, 0, "inversion"))) p.inversion = int_arg(f, 0, 1, pid, "params.inversion must be 0 or 1");
+        if ((f = mxGetField(P, 0, "single"))) p.out_is_f64 = 1 - int_arg(f, 0, 1, pid, "params.single must be 0 or 1");
+        p.ti = scalar_field(P, "ti", 0.0);
+        p.inv_eff = scalar_field(P, "inv_eff", 1.0);
+        want(std::isfinite(p.ti) && p.ti >= 0.0, pid, "params.ti must be finite and >= 0");
+        want(p.inv_eff > 0.0 && p.inv_eff <= 1.0, pid, "params.inv_eff must be in (0, 1]");
+        const char* qid = "qmri:dict_simulate_sp:profile";
+        const size_t Q = real_vec(prhs[9], qid, "prof and w must be real double (complex profiles are not supported)");
+        want(Q >= 1 && Q <= 64, qid, "w must hold 1 <= Q <= 64 weights");
+        const size_t np = real_vec(prhs[8], qid, "prof and w must be real double (complex profiles are not supported)");
+        want(np == Q || np == Q * T, qid, "prof must be Q x 1 or Q x T");
+        want(np == Q || mxGetM(prhs[8]) == Q, qid, "prof must be Q x 1 or Q x T");
+        const qmri_epg_profile sp = {(int32_t)Q, np == Q ? 0 : 1, mxGetDoubles(prhs[8]), mxGetDoubles(prhs[9])};
+        mxArray* Fo = mxCreateNumericMatrix(K, T, p.out_is_f64 ? mxDOUBLE_CLASS : mxSINGLE_CLASS, mxREAL);
+        const int st = qmri_dict_simulate_sp(ctx(), (int)K, (int)T, mxGetDoubles(prhs[1]), sched[0].data(), sched[1].data(), mxGetDoubles(prhs[4]),
+                                             mxGetDoubles(prhs[5]), has_b1 ? mxGetDoubles(prhs[6]) : nullptr, &p, &sp, mxGetData(Fo));
         if (st != QMRI_OK) mxDestroyArray(Fo);
         check(st);
         plhs[0] = Fo;

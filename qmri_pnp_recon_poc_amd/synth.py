@@ -56,6 +56,38 @@ def flip_angle_train(T: int, seed: int = 0) -> np.ndarray:
     return np.deg2rad(5.0 + lobes + jitter)
 
 
+def rf_slice_profile(alpha, envelope, tbw: float, nq: int, zmax: float = 1.0):
+    """Flip-angle scales through the slice of a slice-selective pulse, for Engine.simulate_dictionary(..., slice_profile=, slice_weights=)
+    (DESIGN.md section 26): a hard-pulse Bloch simulation without relaxation, on the host.  alpha [T] nominal flip angles in radians; envelope [P]
+    the pulse shape (its sum must not be 0), scaled per frame so that its P sub-pulse rotations about y sum to alpha_t; between two sub-pulses the
+    magnetisation precesses about z by 2 pi tbw z / P (tbw: time-bandwidth product, z in units of the nominal slice thickness).  z_q are the
+    midpoints of nq equal intervals of [0, zmax]: half of a symmetric profile.  From M = (0, 0, 1), prof[t, q] = atan2(|Mxy|, Mz) / alpha_t; a
+    frame with alpha_t = 0 gets its small-tip limit |sum_p b_p exp(i phi_p(z))| / sum_p b_p.  Returns (prof [T, nq], w [nq] = 1 / nq)."""
+    alpha = np.asarray(alpha, dtype=np.float64).ravel()
+    b = np.asarray(envelope, dtype=np.float64).ravel()
+    nq = int(nq)
+    if b.size < 1 or not np.all(np.isfinite(b)) or b.sum() == 0.0:
+        raise ValueError("envelope must hold at least one finite value and must not sum to 0")
+    if nq < 1 or not (zmax > 0.0) or not np.all(np.isfinite(alpha)) or np.any(alpha < 0):
+        raise ValueError("nq >= 1, zmax > 0 and finite alpha >= 0 are required")
+    P = b.size
+    z = (np.arange(nq) + 0.5) * (float(zmax) / nq)
+    phi = 2.0 * np.pi * float(tbw) * z / P                                        # precession between two sub-pulses [nq]
+    theta = alpha[:, None] * (b / b.sum())[None, :]                               # sub-pulse rotations [T, P]
+    mx, my, mz = np.zeros((alpha.size, nq)), np.zeros((alpha.size, nq)), np.ones((alpha.size, nq))
+    cp, sp = np.cos(phi)[None, :], np.sin(phi)[None, :]
+    for p in range(P):
+        c, s = np.cos(theta[:, p])[:, None], np.sin(theta[:, p])[:, None]
+        mx, mz = mx * c + mz * s, -mx * s + mz * c
+        if p + 1 < P:
+            mx, my = mx * cp - my * sp, mx * sp + my * cp
+    small = np.abs(np.exp(1j * np.outer(phi, P - 1 - np.arange(P))) @ b) / abs(b.sum())      # [nq]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        prof = np.arctan2(np.hypot(mx, my), mz) / alpha[:, None]
+    prof[alpha == 0.0] = small
+    return prof, np.full(nq, 1.0 / nq)
+
+
 def make_dictionary(T: int = 200, n_t1: int = 128, n_t2: int = 64, s: int = 10, seed: int = 0, uncompressed: bool = False) -> dict:
     """Synthetic MRF dictionary with K = n_t1*n_t2 atoms.
 
