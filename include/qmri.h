@@ -794,6 +794,14 @@ int qmri_debug_epg_shift(qmri_ctx* ctx, int S, int nshift, const double* in, dou
  * QMRI_ERR_INVALID_ARG (message: qmri_last_error(NULL)).  Knobs are read when a plan is made or a launch is issued: set them before
  * qmri_set_operator / qmri_set_denoiser. */
 int qmri_debug_knob(const char* name, int value);
+/* Diagnostic: the library's device and pinned allocations, counted process-wide where they are made (csrc/dev_mem.h): how many are live, their
+ * bytes, and how many were made since the process started.  Takes no context, so it also reads after qmri_destroy: a process that has destroyed
+ * all its contexts reads zero live allocations.  out == NULL: QMRI_ERR_INVALID_ARG. */
+typedef struct {
+    long long dev_live, dev_bytes, dev_total;           /* hipMalloc */
+    long long pinned_live, pinned_bytes, pinned_total;  /* hipHostMalloc */
+} qmri_mem_stats;
+int qmri_debug_mem_stats(qmri_mem_stats* out);
 
 #ifdef __cplusplus
 }

@@ -24,7 +24,7 @@ SYMBOLS = [
     "qmri_dict_match_dev", "qmri_dict_match_xfit", "qmri_dict_match_xfit_dev", "qmri_set_dictionary_groups", "qmri_dict_group_assign", "qmri_dict_match_grouped",
     "qmri_dict_match_grouped_dev", "qmri_recon_batch", "qmri_recon_batch_mc",
     "qmri_coil_compress", "qmri_coil_compress_dev", "qmri_coil_eig", "qmri_recon_batch_mc_cc", "qmri_coil_maps", "qmri_coil_maps_dev", "qmri_dict_compress", "qmri_dict_compress_dev", "qmri_dict_simulate", "qmri_dict_simulate_dev", "qmri_dict_simulate_sp", "qmri_dict_simulate_sp_dev", "qmri_field_map_estimate", "qmri_field_map_estimate_dev", "qmri_llr_prox", "qmri_llr_prox_dev", "qmri_set_llr", "qmri_profile_enable", "qmri_profile_get", "qmri_get_health",
-    "qmri_debug_lsqr_stamps", "qmri_debug_conv_stamps", "qmri_debug_lsqr_persist", "qmri_debug_dict_filter", "qmri_debug_conv_resident", "qmri_debug_dsvd_gram", "qmri_debug_epg_shift", "qmri_debug_knob",
+    "qmri_debug_lsqr_stamps", "qmri_debug_conv_stamps", "qmri_debug_lsqr_persist", "qmri_debug_dict_filter", "qmri_debug_conv_resident", "qmri_debug_dsvd_gram", "qmri_debug_epg_shift", "qmri_debug_knob", "qmri_debug_mem_stats",
     "qmri_onnx_read_unetres",
     "qmri_lrtv", "qmri_prox_tv", "qmri_norm_tv", "qmri_synthesize_tsmi", "qmri_synthesize_tsmi_complex",
 ]
@@ -145,6 +145,11 @@ class Health(C.Structure):
                 ("last_call_wall_ms", C.c_double), ("last_call_stage_ms", C.c_double * 4), ("set_denoiser_ms", C.c_double * 3)]
 
 
+class MemStats(C.Structure):
+    _fields_ = [("dev_live", C.c_longlong), ("dev_bytes", C.c_longlong), ("dev_total", C.c_longlong),
+                ("pinned_live", C.c_longlong), ("pinned_bytes", C.c_longlong), ("pinned_total", C.c_longlong)]
+
+
 def build(force: bool = False) -> str:
     """Compile libqmri.so for gfx950 with hipcc (in-tree, next to this file)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".cpp", ".h")) or f == "Makefile"]
@@ -259,6 +264,7 @@ def lib() -> C.CDLL:
     L.qmri_llr_prox_dev.argtypes = [vp, i, i, i, i, vp, i, C.POINTER(LlrParams), i, i, vp, dp]
     L.qmri_set_llr.argtypes = [vp, C.POINTER(LlrParams)]
     L.qmri_debug_knob.argtypes = [C.c_char_p, i]
+    L.qmri_debug_mem_stats.argtypes = [C.POINTER(MemStats)]
     L.qmri_profile_enable.argtypes = [vp, i]
     L.qmri_profile_get.argtypes = [vp, C.POINTER(Profile), i]
     if L.qmri_abi_version() != 1:

@@ -306,10 +306,7 @@ static int pnp_admm_dev_impl(qmri_ctx* ctx, int nslices, const void* d_y, const 
         qmri_set_error(ctx, "unknown solver %d", prm->solver);
         return QMRI_ERR_INVALID_ARG;
     }
-    if (prm->want_diag && diag_out) {
-        if (o.d_diag) { (void)hipFree(o.d_diag); o.d_diag = nullptr; }
-        QMRI_HIP(ctx, hipMalloc((void**)&o.d_diag, (size_t)B * std::max(prm->iters, 1) * 2 * sizeof(double)));
-    }
+    if (prm->want_diag && diag_out) QMRI_TRY(o.d_diag.ensure(ctx, (size_t)B * std::max(prm->iters, 1) * 2));
     std::vector<int32_t> it_b(B);
     o.xhat_valid = false;                                  // x was just set: its spectrum is not known yet
     const bool diag = prm->want_diag && diag_out;
@@ -318,12 +315,7 @@ static int pnp_admm_dev_impl(qmri_ctx* ctx, int nslices, const void* d_y, const 
     // (qmri_lsqr_run, "deferred") -- the kernels of all iterations are queued back to back and the counts are read after the final
     // synchronisation; an event or a host round trip per x-update left the GPU idle for ~6 us each
     std::vector<char> deferred_it((size_t)std::max(prm->iters, 1), 0);
-    if (prm->solver == QMRI_SOLVER_LSQR && (size_t)prm->iters * B > o.h_ring_cap) {
-        if (o.h_ring) { QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream)); (void)hipHostFree(o.h_ring); o.h_ring = nullptr; o.h_ring_cap = 0; }
-        const size_t cap = std::max<size_t>((size_t)prm->iters * B, 128);
-        QMRI_HIP(ctx, hipHostMalloc((void**)&o.h_ring, cap * sizeof(LsqrState), hipHostMallocDefault));
-        o.h_ring_cap = cap;
-    }
+    if (prm->solver == QMRI_SOLVER_LSQR) QMRI_TRY(o.h_ring.ensure(ctx, std::max<size_t>((size_t)prm->iters * B, 128)));
     // Round 4: the small launches around the network are folded into their neighbours (LSQR solver; knob fuse_ew = 0 restores the separate kernels
     // for A/Bs): un-normalise + dual update + z + the h-pass of z's transform + the forward pass's |output| report = ONE launch (k_dual_fwd_h);
     // the w-pass of z rides in the solve's first kernel (k_ks_init_a<FWDW>); the min / max of real(x + u) come out of the solve's last h-pass.
@@ -513,7 +505,7 @@ extern "C" int qmri_pnp_admm(qmri_ctx* ctx, const void* y, const qmri_admm_param
     QMRI_HIP(ctx, hipMemcpyAsync(o.d_ya, y, (size_t)o.m * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
     if (x0) { d_x0 = o.d_xb; QMRI_HIP(ctx, hipMemcpyAsync(d_x0, x0, n * sizeof(double2), hipMemcpyHostToDevice, ctx->stream)); }
     if (gt) {
-        QMRI_HIP(ctx, hipMalloc((void**)&d_gt.p, n * sizeof(double2)));
+        QMRI_TRY(d_gt.ensure(ctx, n));
         if (hipMemcpyAsync(d_gt, gt, n * sizeof(double2), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
             qmri_set_error(ctx, "copy of gt_tsmi to the device failed");
             return QMRI_ERR_HIP;
@@ -547,11 +539,10 @@ extern "C" int qmri_pnp_admm_batch(qmri_ctx* ctx, int nslices, int slices_per_la
     const size_t n = (size_t)o.N * o.M * o.s, m = (size_t)o.m, it = (size_t)std::max(p->iters, 0);
     DevBuf<double2> dY, dX, dX0, dGT;
     auto fail = [&](const char* what) { qmri_set_error(ctx, "%s failed in qmri_pnp_admm_batch", what); return QMRI_ERR_HIP; };
-    if (hipMalloc((void**)&dY.p, spl * m * sizeof(double2)) != hipSuccess || hipMalloc((void**)&dX.p, spl * n * sizeof(double2)) != hipSuccess ||
-        (x0 && hipMalloc((void**)&dX0.p, spl * n * sizeof(double2)) != hipSuccess) || (gt && hipMalloc((void**)&dGT.p, spl * n * sizeof(double2)) != hipSuccess)) {
-        qmri_set_error(ctx, "hipMalloc failed in qmri_pnp_admm_batch");
-        return QMRI_ERR_NOMEM;
-    }
+    QMRI_TRY(dY.ensure(ctx, spl * m));
+    QMRI_TRY(dX.ensure(ctx, spl * n));
+    if (x0) QMRI_TRY(dX0.ensure(ctx, spl * n));
+    if (gt) QMRI_TRY(dGT.ensure(ctx, spl * n));
     for (int s0 = 0; s0 < nslices; s0 += spl) {
         const size_t cnt = (size_t)std::min(spl, nslices - s0);
         if (hipMemcpyAsync(dY, (const double2*)y + (size_t)s0 * m, cnt * m * sizeof(double2), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return fail("H2D copy");

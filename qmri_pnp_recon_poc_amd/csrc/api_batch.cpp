@@ -40,8 +40,8 @@ static int recon_worker(int device, bool shared_device, int widx, int nworkers, 
     DevBuf<double2> d_psi;
     Stream cs;
     struct Set { DevBuf<double2> dY, dX, dM, dYc, dMc; DevBuf<float> dq, dp;
-                 PinnedBuf<char> hY, hX, hM;
-                 PinnedBuf<float> hq, hp;
+                 PinnedArr<char> hY, hX, hM;
+                 PinnedArr<float> hq, hp;
                  Event matched, copied; int s0 = -1, cnt = 0; } set[2];
     auto bail = [&](int code) { *err = qmri_last_error(ctx); return code; };
     auto hipfail = [&](const char* what) { *err = std::string(what) + " failed in qmri_recon_batch"; return QMRI_ERR_HIP; };
@@ -67,15 +67,15 @@ static int recon_worker(int device, bool shared_device, int widx, int nworkers, 
         bool ok = hipStreamCreateWithFlags(&cs.s, hipStreamNonBlocking) == hipSuccess;
         for (int j = 0; j < 2 && ok; ++j) {
             Set& S = set[j];
-            ok = hipMalloc((void**)&S.dY.p, by) == hipSuccess && hipMalloc((void**)&S.dX.p, bx) == hipSuccess && hipHostMalloc((void**)&S.hY.p, by, hipHostMallocDefault) == hipSuccess &&
-                 hipHostMalloc((void**)&S.hX.p, bx, hipHostMallocDefault) == hipSuccess && hipEventCreateWithFlags(&S.matched.e, hipEventDisableTiming) == hipSuccess &&
-                 hipEventCreateWithFlags(&S.copied.e, hipEventDisableTiming) == hipSuccess;
-            if (ok && ncoil) ok = hipMalloc((void**)&S.dM.p, bm) == hipSuccess && hipHostMalloc((void**)&S.hM.p, bm, hipHostMallocDefault) == hipSuccess;
-            if (ok && cc) ok = hipMalloc((void**)&S.dYc.p, byc) == hipSuccess && hipMalloc((void**)&S.dMc.p, bmc) == hipSuccess;
-            if (ok && maps) ok = hipMalloc((void**)&S.dq.p, bq) == hipSuccess && hipMalloc((void**)&S.dp.p, bp) == hipSuccess &&
-                                 hipHostMalloc((void**)&S.hq.p, bq, hipHostMallocDefault) == hipSuccess && hipHostMalloc((void**)&S.hp.p, bp, hipHostMallocDefault) == hipSuccess;
+            const auto dev = [&](DevBuf<double2>& d, size_t bytes) { return d.ensure(ctx, bytes / sizeof(double2)) == QMRI_OK; };
+            ok = dev(S.dY, by) && dev(S.dX, bx) && S.hY.ensure(ctx, by) == QMRI_OK && S.hX.ensure(ctx, bx) == QMRI_OK &&
+                 hipEventCreateWithFlags(&S.matched.e, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&S.copied.e, hipEventDisableTiming) == hipSuccess;
+            if (ok && ncoil) ok = dev(S.dM, bm) && S.hM.ensure(ctx, bm) == QMRI_OK;
+            if (ok && cc) ok = dev(S.dYc, byc) && dev(S.dMc, bmc);
+            if (ok && maps) ok = S.dq.ensure(ctx, bq / sizeof(float)) == QMRI_OK && S.dp.ensure(ctx, bp / sizeof(float)) == QMRI_OK &&
+                                 S.hq.ensure(ctx, bq / sizeof(float)) == QMRI_OK && S.hp.ensure(ctx, bp / sizeof(float)) == QMRI_OK;
         }
-        if (ok && cc && psi) ok = hipMalloc((void**)&d_psi.p, (size_t)ncoil * ncoil * sizeof(double2)) == hipSuccess;
+        if (ok && cc && psi) ok = d_psi.ensure(ctx, (size_t)ncoil * ncoil) == QMRI_OK;
         if (!ok) { *err = "allocation failed in qmri_recon_batch"; return QMRI_ERR_NOMEM; }
         if (d_psi && hipMemcpy(d_psi, psi, (size_t)ncoil * ncoil * sizeof(double2), hipMemcpyHostToDevice) != hipSuccess) return hipfail("H2D copy");
         const int nlaunch = (nslices + spl - 1) / spl;

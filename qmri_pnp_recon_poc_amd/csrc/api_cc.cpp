@@ -181,12 +181,7 @@ extern "C" int qmri_coil_compress(qmri_ctx* ctx, int nslices, int ncoil, const v
     if (maps) QMRI_HIP(ctx, hipMemcpyAsync(w.sm, maps, nm * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
     if (noise_cov) {
         const size_t nn = (size_t)ncoil * ncoil;
-        if (!w.psi || w.psi_cap < nn) {
-            if (w.psi) (void)hipFree(w.psi);
-            w.psi = nullptr; w.psi_cap = 0;
-            QMRI_HIP(ctx, hipMalloc((void**)&w.psi, nn * sizeof(double2)));
-            w.psi_cap = nn;
-        }
+        QMRI_TRY(w.psi.ensure(ctx, nn));
         QMRI_HIP(ctx, hipMemcpyAsync(w.psi, noise_cov, nn * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
     }
     QMRI_TRY(cc_compress_dev(ctx, nslices, ncoil, w.sy, maps ? w.sm : nullptr, noise_cov ? w.psi : nullptr, *p, nv_out, w.oy, maps ? w.om : nullptr,

@@ -128,23 +128,24 @@ extern "C" int qmri_create(int device, qmri_ctx** out) {
     return QMRI_OK;
 }
 
-static void free_dev(void* p) { if (p) (void)hipFree(p); }
+int qmri_stream_idle(qmri_ctx* ctx) {
+    if (ctx) QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return QMRI_OK;
+}
+
+static MemCount g_mem_count[2];
+MemCount& qmri_mem_count(bool pinned) { return g_mem_count[pinned ? 1 : 0]; }
+
+extern "C" int qmri_debug_mem_stats(qmri_mem_stats* out) {
+    if (!out) return QMRI_ERR_INVALID_ARG;
+    const MemCount &d = g_mem_count[0], &h = g_mem_count[1];
+    *out = qmri_mem_stats{d.live.load(), d.bytes.load(), d.total.load(), h.live.load(), h.bytes.load(), h.total.load()};
+    return QMRI_OK;
+}
 
 void qmri_free_operator(qmri_ctx* ctx) {
-    OpHost& o = ctx->op;
-    void* ptrs[] = { o.d_Vt, o.d_ent, o.d_perm, o.d_kptr, o.d_tw, o.d_kslot, o.d_ginv, o.d_tmp, o.d_xa, o.d_xb, o.d_ya,
-                     o.ls.st, o.ls.pz, o.ls.yk, o.ls.py,
-                     (void*)o.ks.unit, (void*)o.ks.es, (void*)o.ks.grp, (void*)o.ks.sgrp,
-                     o.ks.pu[0], o.ks.pu[1], o.ks.pv[0], o.ks.pv[1], o.ks.pinit, o.ks.pR, o.ks.cx, o.ks.cv, o.ks.cd, o.ks.cub,
-                     o.ks.ut, o.ks.xhat, o.ks.zhat, o.ks.xhat_out, o.ks.stamps,
-                     o.d_x, o.d_u, o.d_vv, o.d_z, o.d_chat, o.d_mm, o.d_norm, o.d_diag, o.d_pd, o.d_coils };
-    for (void* p : ptrs) free_dev(p);
-    if (o.h_state) (void)hipHostFree(o.h_state);
-    if (o.h_ring) (void)hipHostFree(o.h_ring);
-    free_dev(ctx->d_ks_gran); ctx->d_ks_gran = nullptr; ctx->ks_persist_cap = -1;    // (sized for this operator's work units)
-    mc_free_work(o.mc);
-    nufft_free(o.nu);
-    o = OpHost();
+    ctx->d_ks_gran.reset(); ctx->ks_persist_cap = -1;    // (sized for this operator's work units)
+    ctx->op = OpHost();
 }
 
 extern "C" int qmri_destroy(qmri_ctx* ctx) {
@@ -154,7 +155,7 @@ extern "C" int qmri_destroy(qmri_ctx* ctx) {
     qmri_free_operator(ctx);
     qmri_free_net(ctx);
     qmri_free_dict(ctx);
-    cc_free_work(ctx->cc);
+    ctx->cc = CcWork();
     for (auto& ev : ctx->ev) if (ev) (void)hipEventDestroy(ev);
     if (ctx->ev_state) (void)hipEventDestroy(ctx->ev_state);
     for (hipEvent_t e : ctx->chain) if (e) (void)hipEventDestroy(e);
@@ -326,13 +327,13 @@ extern "C" int qmri_set_operator(qmri_ctx* ctx, int N, int M, int s, int T, cons
     for (int j = 0; j < M; ++j) { const double a = 2.0 * pi * j / M; tw[(size_t)N + j] = make_double2(std::cos(a), -std::sin(a)); }
 
     const size_t n = (size_t)N * M * s, B = (size_t)max_batch;
-    QMRI_TRY(dev_alloc(ctx, &o.d_Vt, Vt.size()));
-    QMRI_TRY(dev_alloc(ctx, &o.d_ent, (size_t)m));
-    QMRI_TRY(dev_alloc(ctx, &o.d_perm, (size_t)m));
-    QMRI_TRY(dev_alloc(ctx, &o.d_kptr, (size_t)NM + 1));
-    QMRI_TRY(dev_alloc(ctx, &o.d_tw, tw.size()));
-    QMRI_TRY(dev_alloc(ctx, &o.d_kslot, (size_t)NM));
-    QMRI_TRY(dev_alloc(ctx, &o.d_ginv, (size_t)o.nsampled * s * s));
+    QMRI_TRY(o.pool.alloc(ctx, &o.d_Vt, Vt.size()));
+    QMRI_TRY(o.pool.alloc(ctx, &o.d_ent, (size_t)m));
+    QMRI_TRY(o.pool.alloc(ctx, &o.d_perm, (size_t)m));
+    QMRI_TRY(o.pool.alloc(ctx, &o.d_kptr, (size_t)NM + 1));
+    QMRI_TRY(o.pool.alloc(ctx, &o.d_tw, tw.size()));
+    QMRI_TRY(o.pool.alloc(ctx, &o.d_kslot, (size_t)NM));
+    QMRI_TRY(o.pool.alloc(ctx, &o.d_ginv, (size_t)o.nsampled * s * s));
     QMRI_HIP(ctx, hipMemcpy(o.d_Vt, Vt.data(), Vt.size() * sizeof(double), hipMemcpyHostToDevice));
     QMRI_HIP(ctx, hipMemcpy(o.d_ent, o.ent_h.data(), (size_t)m * sizeof(KEntry), hipMemcpyHostToDevice));
     QMRI_HIP(ctx, hipMemcpy(o.d_perm, o.perm_h.data(), (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -436,7 +437,7 @@ extern "C" int qmri_set_operator(qmri_ctx* ctx, int N, int M, int s, int T, cons
         for (int g = 0; g < ks.G; ++g) units[g] = KsUnit{bslot[g], bslot[g + 1], sptr[bslot[g]], sptr[bslot[g + 1]], gptr[g], gptr[g + 1], 0, 0};
         int32_t* p32; KSample* pes; KsGroup* pg; KsUnit* pu_;
 #define KS_UPLOAD(ptr, field, vec, T_)                                                                 \
-        QMRI_TRY(dev_alloc(ctx, &ptr, (vec).size()));                                                  \
+        QMRI_TRY(o.pool.alloc(ctx, &ptr, (vec).size()));                                                  \
         QMRI_HIP(ctx, hipMemcpy(ptr, (vec).data(), (vec).size() * sizeof(T_), hipMemcpyHostToDevice)); \
         ks.field = ptr;
         KS_UPLOAD(p32, sgrp, sgrp, int32_t)
@@ -452,40 +453,40 @@ extern "C" int qmri_set_operator(qmri_ctx* ctx, int N, int M, int s, int T, cons
     OpDev dims{};
     dims.N = N; dims.M = M; dims.s = s;
     const size_t npart = (size_t)std::max(ls.nblk_z, dc_hpass_blocks(dims));
-    QMRI_TRY(dev_alloc(ctx, &o.d_tmp, B * n));
-    QMRI_TRY(dev_alloc(ctx, &o.d_xa, B * n));
-    QMRI_TRY(dev_alloc(ctx, &o.d_xb, B * n));
-    QMRI_TRY(dev_alloc(ctx, &o.d_ya, B * (size_t)m));
-    QMRI_TRY(dev_alloc(ctx, &ls.st, B));
-    QMRI_TRY(dev_alloc(ctx, &ls.pz, B * npart));
-    QMRI_TRY(dev_alloc(ctx, &ls.py, B * (size_t)DC_SORT_BLOCKS));
+    QMRI_TRY(o.pool.alloc(ctx, &o.d_tmp, B * n));
+    QMRI_TRY(o.pool.alloc(ctx, &o.d_xa, B * n));
+    QMRI_TRY(o.pool.alloc(ctx, &o.d_xb, B * n));
+    QMRI_TRY(o.pool.alloc(ctx, &o.d_ya, B * (size_t)m));
+    QMRI_TRY(o.pool.alloc(ctx, &ls.st, B));
+    QMRI_TRY(o.pool.alloc(ctx, &ls.pz, B * npart));
+    QMRI_TRY(o.pool.alloc(ctx, &ls.py, B * (size_t)DC_SORT_BLOCKS));
     for (int par = 0; par < 2; ++par) {
-        QMRI_TRY(dev_alloc(ctx, &ks.pu[par], B * 2 * ks.G));
-        QMRI_TRY(dev_alloc(ctx, &ks.pv[par], B * ks.G));
+        QMRI_TRY(o.pool.alloc(ctx, &ks.pu[par], B * 2 * ks.G));
+        QMRI_TRY(o.pool.alloc(ctx, &ks.pv[par], B * ks.G));
     }
-    QMRI_TRY(dev_alloc(ctx, &ks.pinit, B * 2 * N));
-    QMRI_TRY(dev_alloc(ctx, &ks.pR, B * N));
-    QMRI_TRY(dev_alloc(ctx, &ks.cx, B * ks.ns * s));
-    QMRI_TRY(dev_alloc(ctx, &ks.cv, B * ks.ns * s));
-    QMRI_TRY(dev_alloc(ctx, &ks.cd, B * ks.ns * s));
-    QMRI_TRY(dev_alloc(ctx, &ks.cub, B * ks.ns * s));
-    QMRI_TRY(dev_alloc(ctx, &ks.ut, B * (size_t)m));
-    QMRI_TRY(dev_alloc(ctx, &ks.xhat, B * n));
-    QMRI_TRY(dev_alloc(ctx, &ks.zhat, B * n));
-    QMRI_TRY(dev_alloc(ctx, &ks.xhat_out, B * n));
+    QMRI_TRY(o.pool.alloc(ctx, &ks.pinit, B * 2 * N));
+    QMRI_TRY(o.pool.alloc(ctx, &ks.pR, B * N));
+    QMRI_TRY(o.pool.alloc(ctx, &ks.cx, B * ks.ns * s));
+    QMRI_TRY(o.pool.alloc(ctx, &ks.cv, B * ks.ns * s));
+    QMRI_TRY(o.pool.alloc(ctx, &ks.cd, B * ks.ns * s));
+    QMRI_TRY(o.pool.alloc(ctx, &ks.cub, B * ks.ns * s));
+    QMRI_TRY(o.pool.alloc(ctx, &ks.ut, B * (size_t)m));
+    QMRI_TRY(o.pool.alloc(ctx, &ks.xhat, B * n));
+    QMRI_TRY(o.pool.alloc(ctx, &ks.zhat, B * n));
+    QMRI_TRY(o.pool.alloc(ctx, &ks.xhat_out, B * n));
     ks.stamps = nullptr;
-    if (qmri_knob(K_LSQR_STAMPS) > 0) { QMRI_TRY(dev_alloc(ctx, &ks.stamps, (size_t)2 * 512 * 16)); QMRI_HIP(ctx, hipMemset(ks.stamps, 0, 2 * 512 * 16 * 8)); }
-    QMRI_TRY(dev_alloc(ctx, &ls.yk, B * (size_t)m));
-    QMRI_TRY(dev_alloc(ctx, &o.d_x, B * n));
-    QMRI_TRY(dev_alloc(ctx, &o.d_u, B * n));
-    QMRI_TRY(dev_alloc(ctx, &o.d_vv, B * n));
-    QMRI_TRY(dev_alloc(ctx, &o.d_z, B * n));
-    QMRI_TRY(dev_alloc(ctx, &o.d_chat, B * n));
-    QMRI_TRY(dev_alloc(ctx, &o.d_mm, B * npart * 2));
-    QMRI_TRY(dev_alloc(ctx, &o.d_norm, B * 2));
-    QMRI_TRY(dev_alloc(ctx, &o.d_pd, B * ((size_t)N + 2 * ls.nblk_z)));
+    if (qmri_knob(K_LSQR_STAMPS) > 0) { QMRI_TRY(o.pool.alloc(ctx, &ks.stamps, (size_t)2 * 512 * 16)); QMRI_HIP(ctx, hipMemset(ks.stamps, 0, 2 * 512 * 16 * 8)); }
+    QMRI_TRY(o.pool.alloc(ctx, &ls.yk, B * (size_t)m));
+    QMRI_TRY(o.pool.alloc(ctx, &o.d_x, B * n));
+    QMRI_TRY(o.pool.alloc(ctx, &o.d_u, B * n));
+    QMRI_TRY(o.pool.alloc(ctx, &o.d_vv, B * n));
+    QMRI_TRY(o.pool.alloc(ctx, &o.d_z, B * n));
+    QMRI_TRY(o.pool.alloc(ctx, &o.d_chat, B * n));
+    QMRI_TRY(o.pool.alloc(ctx, &o.d_mm, B * npart * 2));
+    QMRI_TRY(o.pool.alloc(ctx, &o.d_norm, B * 2));
+    QMRI_TRY(o.pool.alloc(ctx, &o.d_pd, B * ((size_t)N + 2 * ls.nblk_z)));
     QMRI_HIP(ctx, hipMemset(ls.st, 0, B * sizeof(LsqrState)));
-    QMRI_HIP(ctx, hipHostMalloc((void**)&o.h_state, B * sizeof(LsqrState), hipHostMallocDefault));
+    QMRI_TRY(o.h_state.ensure(ctx, B));
     ks.hst = nullptr; ks.st = ls.st; ks.pz = ls.pz; ks.nblk_z = ls.nblk_z; ks.yk = ls.yk; ks.pdiag = nullptr;
     o.xhat_valid = false;
     o.ginv_r = -1.0;
@@ -568,11 +569,11 @@ extern "C" int qmri_set_coils(qmri_ctx* ctx, int ncoil, const void* maps) {
     OpHost& o = ctx->op;
     QMRI_CHECK_ARG(ctx, ncoil >= 0 && ncoil <= 1024 && (ncoil == 0 || maps), "0 <= ncoil <= 1024, maps must not be NULL");
     QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (o.d_coils) { (void)hipFree(o.d_coils); o.d_coils = nullptr; }
+    o.d_coils.reset();
     o.ncoil = 0;
     if (ncoil == 0) return QMRI_OK;
     const size_t count = (size_t)ncoil * o.N * o.M;
-    QMRI_HIP(ctx, hipMalloc((void**)&o.d_coils, count * sizeof(double2)));
+    QMRI_TRY(o.d_coils.ensure(ctx, count));
     QMRI_HIP(ctx, hipMemcpy(o.d_coils, maps, count * sizeof(double2), hipMemcpyHostToDevice));
     QMRI_HIP(ctx, hipDeviceSynchronize());                        // (as in qmri_set_operator: the copy must have landed before this context's stream reads it)
     o.ncoil = ncoil;
@@ -744,9 +745,9 @@ int qmri_lsqr_run(qmri_ctx* ctx, int B, const double2* d_z, double r, double tol
     // cut0, slice batches) and after a time-out of the persistent kernel (never seen; the inputs are untouched then).
     bool persisted = false;
     if (per_launch > 0) {
-        if (!ctx->d_ks_gran) {
+        if (!ctx->d_ks_gran.p) {
             const size_t nb = ks_gran_bytes(ks.G, o.maxB);
-            QMRI_HIP(ctx, hipMalloc(&ctx->d_ks_gran, nb));
+            QMRI_TRY(ctx->d_ks_gran.ensure(ctx, nb));
             QMRI_HIP(ctx, hipMemsetAsync(ctx->d_ks_gran, 0, nb, ctx->stream));      // (tag 0 is never used)
         }
         const unsigned tag0 = ctx->ks_tag;
@@ -877,9 +878,9 @@ extern "C" int qmri_xupdate(qmri_ctx* ctx, const void* y, const void* z, double 
 extern "C" int qmri_debug_lsqr_persist(qmri_ctx* ctx, int on) {
     if (!ctx) return QMRI_ERR_INVALID_ARG;
     ctx->ks_persist = (on == 2) ? 2 : (on ? 1 : 0);               // (2: test hook -- one partial sum is withheld, the time-out path must take over)
-    if (ctx->d_ks_gran && ctx->op.ready) {                         // a fresh start: forget an earlier time-out (the sticky word behind the granules)
+    if (ctx->d_ks_gran.p && ctx->op.ready) {                         // a fresh start: forget an earlier time-out (the sticky word behind the granules)
         QMRI_HIP(ctx, hipSetDevice(ctx->device));
-        QMRI_HIP(ctx, hipMemsetAsync((char*)ctx->d_ks_gran + ks_gran_bytes(ctx->op.ks.G, ctx->op.maxB) - 64, 0, 64, ctx->stream));
+        QMRI_HIP(ctx, hipMemsetAsync((char*)ctx->d_ks_gran.p + ks_gran_bytes(ctx->op.ks.G, ctx->op.maxB) - 64, 0, 64, ctx->stream));
     }
     return QMRI_OK;
 }

@@ -53,10 +53,10 @@ extern "C" int qmri_coil_maps(qmri_ctx* ctx, int nslices, int ncoil, int N, int 
     const size_t ncal = nimg * (p->kind == QMRI_CSM_KSPACE ? (size_t)p->cN * p->cM : plane);
     DevBuf<double2> cal, maps, img;
     DevBuf<double> lam;
-    QMRI_TRY(dev_alloc(ctx, &cal.p, ncal));
-    QMRI_TRY(dev_alloc(ctx, &maps.p, nimg * plane));
-    if (img_out) QMRI_TRY(dev_alloc(ctx, &img.p, (size_t)nslices * plane));
-    if (lambda_out) QMRI_TRY(dev_alloc(ctx, &lam.p, (size_t)nslices * plane));
+    QMRI_TRY(cal.ensure(ctx, ncal));
+    QMRI_TRY(maps.ensure(ctx, nimg * plane));
+    if (img_out) QMRI_TRY(img.ensure(ctx, (size_t)nslices * plane));
+    if (lambda_out) QMRI_TRY(lam.ensure(ctx, (size_t)nslices * plane));
     QMRI_HIP(ctx, hipMemcpyAsync(cal.p, calib, ncal * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
     QMRI_TRY(csm_maps_dev(ctx, nslices, ncoil, cal, *p, maps, img_out ? img.p : nullptr, lambda_out ? lam.p : nullptr, info));
     QMRI_HIP(ctx, hipMemcpyAsync(maps_out, maps.p, nimg * plane * sizeof(double2), hipMemcpyDeviceToHost, ctx->stream));

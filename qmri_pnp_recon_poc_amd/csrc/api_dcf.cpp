@@ -38,7 +38,7 @@ double kernel_sum(int w, double beta) {
 }
 int ensure_weight_array(qmri_ctx* ctx) {
     NufftHost& h = ctx->op.nu;
-    if (!h.d_w) QMRI_TRY(dev_alloc(ctx, &h.d_w, (size_t)ctx->op.m));
+    QMRI_TRY(h.d_w.ensure(ctx, (size_t)ctx->op.m));
     return QMRI_OK;
 }
 }  // namespace

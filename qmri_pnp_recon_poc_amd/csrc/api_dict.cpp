@@ -8,10 +8,7 @@
 #include <cmath>
 
 void qmri_free_dict(qmri_ctx* ctx) {
-    dictg_free(ctx);
     DictHost& d = ctx->dict;
-    void* ptrs[] = { d.d_pack, d.d_pack16, d.d_gmax, d.d_normD, d.d_lut, d.d_part, d.d_xp, d.d_win };
-    for (void* p : ptrs) if (p) (void)hipFree(p);
     const int filter_on = d.filter_on; const float margin_scale = d.margin_scale;
     d = DictHost();
     d.filter_on = filter_on; d.margin_scale = margin_scale;
@@ -31,8 +28,8 @@ extern "C" int qmri_set_dictionary(qmri_ctx* ctx, int K, int s, int Q, const flo
         // wide dictionaries (uncompressed fingerprints, s = T; mrf_dtm_cpu.m:41-50 is T-generic): channel-blocked GEMM, dictw_kernels.hip
         d.wide = 1;
         int st = dictw_pack_dictionary(ctx, D, K, s);
-        if (st == QMRI_OK) st = dev_alloc(ctx, &d.d_normD, (size_t)K);
-        if (st == QMRI_OK) st = dev_alloc(ctx, &d.d_lut, (size_t)K * Q);
+        if (st == QMRI_OK) st = d.pool.alloc(ctx, &d.d_normD, (size_t)K);
+        if (st == QMRI_OK) st = d.pool.alloc(ctx, &d.d_lut, (size_t)K * Q);
         if (st != QMRI_OK) { qmri_free_dict(ctx); return st; }
         QMRI_HIP(ctx, hipMemcpy(d.d_normD, normD, (size_t)K * sizeof(float), hipMemcpyHostToDevice));
         QMRI_HIP(ctx, hipMemcpy(d.d_lut, lut, (size_t)K * Q * sizeof(float), hipMemcpyHostToDevice));
@@ -52,9 +49,9 @@ extern "C" int qmri_set_dictionary(qmri_ctx* ctx, int K, int s, int Q, const flo
                 const int atom = t * 32 + (lane & 31), c = 2 * q + (lane >> 5);
                 if (atom < K && c < s) pack[((size_t)t * 64 + lane) * npl + q] = D[(size_t)atom + (size_t)K * c];
             }
-    QMRI_TRY(dev_alloc(ctx, &d.d_pack, pack.size()));
-    QMRI_TRY(dev_alloc(ctx, &d.d_normD, (size_t)K));
-    QMRI_TRY(dev_alloc(ctx, &d.d_lut, (size_t)K * Q));
+    QMRI_TRY(d.pool.alloc(ctx, &d.d_pack, pack.size()));
+    QMRI_TRY(d.pool.alloc(ctx, &d.d_normD, (size_t)K));
+    QMRI_TRY(d.pool.alloc(ctx, &d.d_lut, (size_t)K * Q));
     QMRI_HIP(ctx, hipMemcpy(d.d_pack, pack.data(), pack.size() * sizeof(float), hipMemcpyHostToDevice));
     QMRI_HIP(ctx, hipMemcpy(d.d_normD, normD, (size_t)K * sizeof(float), hipMemcpyHostToDevice));
     QMRI_HIP(ctx, hipMemcpy(d.d_lut, lut, (size_t)K * Q * sizeof(float), hipMemcpyHostToDevice));
@@ -85,7 +82,7 @@ extern "C" int qmri_set_dictionary(qmri_ctx* ctx, int K, int s, int Q, const flo
                         hi[jj] = (_Float16)a; lo[jj] = (_Float16)(a - (float)hi[jj]);
                     }
                 }
-            QMRI_HIP(ctx, hipMalloc((void**)&d.d_pack16, p16.size() * sizeof(_Float16)));
+            QMRI_TRY(d.pool.alloc(ctx, &d.d_pack16, p16.size() * sizeof(_Float16) / sizeof(uint4)));
             QMRI_HIP(ctx, hipMemcpy(d.d_pack16, p16.data(), p16.size() * sizeof(_Float16), hipMemcpyHostToDevice));
             d.marg_coef = (float)(std::ldexp(1.0, -14) * r2max * (double)g * (double)g * 1.001);
         }
@@ -124,12 +121,12 @@ extern "C" int qmri_dict_match_xfit(qmri_ctx* ctx, const void* X, int Npix, floa
     const size_t nx = (size_t)Npix * d.s;
     DevBuf<double2> dX; DevBuf<float> dq, dp, dmt; DevBuf<int32_t> ddm; DevBuf<float2> dxf;
     auto fail = [&](const char* what) { qmri_set_error(ctx, "%s failed in qmri_dict_match", what); return QMRI_ERR_HIP; };
-    if (hipMalloc((void**)&dX.p, nx * sizeof(double2)) != hipSuccess) return fail("hipMalloc");
-    if (qmap && hipMalloc((void**)&dq.p, (size_t)Npix * d.Q * sizeof(float)) != hipSuccess) return fail("hipMalloc");
-    if (pd && hipMalloc((void**)&dp.p, (size_t)Npix * 2 * sizeof(float)) != hipSuccess) return fail("hipMalloc");
-    if (mt && hipMalloc((void**)&dmt.p, (size_t)Npix * sizeof(float)) != hipSuccess) return fail("hipMalloc");
-    if (dm && hipMalloc((void**)&ddm.p, (size_t)Npix * sizeof(int32_t)) != hipSuccess) return fail("hipMalloc");
-    if (xfit && hipMalloc((void**)&dxf.p, nx * sizeof(float2)) != hipSuccess) return fail("hipMalloc");
+    QMRI_TRY(dX.ensure(ctx, nx));
+    if (qmap) QMRI_TRY(dq.ensure(ctx, (size_t)Npix * d.Q));
+    if (pd) QMRI_TRY(dp.ensure(ctx, (size_t)Npix * 2));
+    if (mt) QMRI_TRY(dmt.ensure(ctx, (size_t)Npix));
+    if (dm) QMRI_TRY(ddm.ensure(ctx, (size_t)Npix));
+    if (xfit) QMRI_TRY(dxf.ensure(ctx, nx));
     if (hipMemcpyAsync(dX, X, nx * sizeof(double2), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return fail("H2D copy");
     QMRI_TRY(dict_launch(ctx, dX, Npix, dq, dp, dmt, ddm, dxf));
     if (qmap && hipMemcpyAsync(qmap, dq, (size_t)Npix * d.Q * sizeof(float), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return fail("D2H copy");
@@ -192,14 +189,14 @@ extern "C" int qmri_dict_match_grouped(qmri_ctx* ctx, const void* X, int Npix, c
     const size_t nx = (size_t)Npix * d.s;
     DevBuf<double2> dX; DevBuf<double> dsel; DevBuf<float> dq, dp, dmt; DevBuf<int32_t> ddm, dgrp; DevBuf<float2> dxf;
     auto fail = [&](const char* what) { qmri_set_error(ctx, "%s failed in qmri_dict_match_grouped", what); return QMRI_ERR_HIP; };
-    if (hipMalloc((void**)&dX.p, nx * sizeof(double2)) != hipSuccess) return fail("hipMalloc");
-    if (hipMalloc((void**)&dsel.p, (size_t)Npix * sizeof(double)) != hipSuccess) return fail("hipMalloc");
-    if (qmap && hipMalloc((void**)&dq.p, (size_t)Npix * d.Q * sizeof(float)) != hipSuccess) return fail("hipMalloc");
-    if (pd && hipMalloc((void**)&dp.p, (size_t)Npix * 2 * sizeof(float)) != hipSuccess) return fail("hipMalloc");
-    if (mt && hipMalloc((void**)&dmt.p, (size_t)Npix * sizeof(float)) != hipSuccess) return fail("hipMalloc");
-    if (dm && hipMalloc((void**)&ddm.p, (size_t)Npix * sizeof(int32_t)) != hipSuccess) return fail("hipMalloc");
-    if (grp && hipMalloc((void**)&dgrp.p, (size_t)Npix * sizeof(int32_t)) != hipSuccess) return fail("hipMalloc");
-    if (xfit && hipMalloc((void**)&dxf.p, nx * sizeof(float2)) != hipSuccess) return fail("hipMalloc");
+    QMRI_TRY(dX.ensure(ctx, nx));
+    QMRI_TRY(dsel.ensure(ctx, (size_t)Npix));
+    if (qmap) QMRI_TRY(dq.ensure(ctx, (size_t)Npix * d.Q));
+    if (pd) QMRI_TRY(dp.ensure(ctx, (size_t)Npix * 2));
+    if (mt) QMRI_TRY(dmt.ensure(ctx, (size_t)Npix));
+    if (dm) QMRI_TRY(ddm.ensure(ctx, (size_t)Npix));
+    if (grp) QMRI_TRY(dgrp.ensure(ctx, (size_t)Npix));
+    if (xfit) QMRI_TRY(dxf.ensure(ctx, nx));
     if (hipMemcpyAsync(dX, X, nx * sizeof(double2), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return fail("H2D copy");
     if (hipMemcpyAsync(dsel, sel, (size_t)Npix * sizeof(double), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return fail("H2D copy");
     QMRI_TRY(dictg_launch(ctx, dX, Npix, dsel, dq, dp, dmt, ddm, dgrp, dxf));

@@ -142,8 +142,8 @@ void mul_tall(int T, int b, int n, const std::vector<double>& A, const std::vect
 int dsvd_eig(qmri_ctx* ctx, int T, int b, int s_cap, const double* d_G, double tol, int maxit, std::vector<double>& X, std::vector<double>& theta,
              qmri_dsvd_info* info) {
     DevBuf<double> dQ, dZ;
-    QMRI_TRY(dev_alloc(ctx, &dQ.p, (size_t)T * b));
-    QMRI_TRY(dev_alloc(ctx, &dZ.p, (size_t)T * b));
+    QMRI_TRY(dQ.ensure(ctx, (size_t)T * b));
+    QMRI_TRY(dZ.ensure(ctx, (size_t)T * b));
     std::vector<double> Q((size_t)T * b), Z((size_t)T * b), A((size_t)b * b), W, ZW;
     for (size_t e = 0; e < Q.size(); ++e) Q[e] = start_value(e);
     orthonormalise(T, b, Q);
@@ -190,9 +190,9 @@ int dsvd_compress_dev(qmri_ctx* ctx, int K, int T, const void* d_F, bool f64, co
     const double tol = p.tol > 0.0 ? p.tol : 1e-13;
     const int maxit = p.maxit > 0 ? p.maxit : 200;
     DevBuf<double> part, G, diag;
-    QMRI_TRY(dev_alloc(ctx, &part.p, dsvd_gram_scratch(K, T)));
-    QMRI_TRY(dev_alloc(ctx, &G.p, (size_t)T * T));
-    QMRI_TRY(dev_alloc(ctx, &diag.p, (size_t)T));
+    QMRI_TRY(part.ensure(ctx, dsvd_gram_scratch(K, T)));
+    QMRI_TRY(G.ensure(ctx, (size_t)T * T));
+    QMRI_TRY(diag.ensure(ctx, (size_t)T));
     QMRI_TRY(dsvd_gram_dev(ctx, K, T, d_F, f64, part, G, diag));
     std::vector<double> dg(T);
     QMRI_HIP(ctx, hipMemcpyAsync(dg.data(), diag.p, (size_t)T * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -249,10 +249,10 @@ extern "C" int qmri_dict_compress(qmri_ctx* ctx, int K, int T, const void* F, in
     DevBuf<unsigned char> dF;
     DevBuf<double> dV;
     DevBuf<float> dD, dn;
-    QMRI_TRY(dev_alloc(ctx, &dF.p, nF));
-    QMRI_TRY(dev_alloc(ctx, &dV.p, (size_t)T * DSVD_MAX_S));
-    QMRI_TRY(dev_alloc(ctx, &dD.p, (size_t)K * DSVD_MAX_S));
-    QMRI_TRY(dev_alloc(ctx, &dn.p, (size_t)K));
+    QMRI_TRY(dF.ensure(ctx, nF));
+    QMRI_TRY(dV.ensure(ctx, (size_t)T * DSVD_MAX_S));
+    QMRI_TRY(dD.ensure(ctx, (size_t)K * DSVD_MAX_S));
+    QMRI_TRY(dn.ensure(ctx, (size_t)K));
     QMRI_HIP(ctx, hipMemcpyAsync(dF.p, F, nF, hipMemcpyHostToDevice, ctx->stream));
     QMRI_TRY(dsvd_compress_dev(ctx, K, T, dF.p, f_is_f64 != 0, *p, s_out, dV, dD, dn, eig_out, info));
     const int s = *s_out;
@@ -273,11 +273,11 @@ extern "C" int qmri_debug_dsvd_gram(qmri_ctx* ctx, int K, int T, const void* F, 
     const size_t nF = (size_t)K * T * (f_is_f64 ? sizeof(double) : sizeof(float));
     DevBuf<unsigned char> dF;
     DevBuf<double> part, G, diag;
-    QMRI_TRY(dev_alloc(ctx, &part.p, dsvd_gram_scratch(K, T)));
-    QMRI_TRY(dev_alloc(ctx, &diag.p, (size_t)T));
+    QMRI_TRY(part.ensure(ctx, dsvd_gram_scratch(K, T)));
+    QMRI_TRY(diag.ensure(ctx, (size_t)T));
     if (!on_device) {
-        QMRI_TRY(dev_alloc(ctx, &dF.p, nF));
-        QMRI_TRY(dev_alloc(ctx, &G.p, (size_t)T * T));
+        QMRI_TRY(dF.ensure(ctx, nF));
+        QMRI_TRY(G.ensure(ctx, (size_t)T * T));
         QMRI_HIP(ctx, hipMemcpyAsync(dF.p, F, nF, hipMemcpyHostToDevice, ctx->stream));
     }
     QMRI_TRY(dsvd_gram_dev(ctx, K, T, on_device ? F : dF.p, f_is_f64 != 0, part, on_device ? G_out : G.p, diag));

@@ -78,7 +78,7 @@ int epg_run(qmri_ctx* ctx, int K, int T, const double* alpha, const double* tr, 
     }
     if (sp) std::copy_n(sp->weight, Q, sched.data() + (size_t)FR * T);
     DevBuf<double> ds;
-    QMRI_TRY(dev_alloc(ctx, &ds.p, sched.size()));
+    QMRI_TRY(ds.ensure(ctx, sched.size()));
     QMRI_HIP(ctx, hipMemcpyAsync(ds.p, sched.data(), sched.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     if (sp) QMRI_TRY(epg_simulate_sp_dev(ctx, K, T, Q, ds, d_t1, d_t2, d_b1, p, const_timing, d_F));
     else QMRI_TRY(epg_simulate_dev(ctx, K, T, ds, d_t1, d_t2, d_b1, p, const_timing, d_F));
@@ -106,10 +106,10 @@ int simulate_host(qmri_ctx* ctx, int K, int T, const double* alpha, const double
     const size_t nF = (size_t)K * T * (p->out_is_f64 ? sizeof(double) : sizeof(float));
     DevBuf<double> d1, d2, db;
     DevBuf<unsigned char> dF;
-    QMRI_TRY(dev_alloc(ctx, &d1.p, (size_t)K));
-    QMRI_TRY(dev_alloc(ctx, &d2.p, (size_t)K));
-    if (b1) QMRI_TRY(dev_alloc(ctx, &db.p, (size_t)K));
-    QMRI_TRY(dev_alloc(ctx, &dF.p, nF));
+    QMRI_TRY(d1.ensure(ctx, (size_t)K));
+    QMRI_TRY(d2.ensure(ctx, (size_t)K));
+    if (b1) QMRI_TRY(db.ensure(ctx, (size_t)K));
+    QMRI_TRY(dF.ensure(ctx, nF));
     QMRI_HIP(ctx, hipMemcpyAsync(d1.p, t1, (size_t)K * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     QMRI_HIP(ctx, hipMemcpyAsync(d2.p, t2, (size_t)K * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     if (b1) QMRI_HIP(ctx, hipMemcpyAsync(db.p, b1, (size_t)K * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
@@ -147,8 +147,8 @@ extern "C" int qmri_debug_epg_shift(qmri_ctx* ctx, int S, int nshift, const doub
     if (!ctx) { qmri_set_error(nullptr, "invalid argument: ctx must not be NULL"); return QMRI_ERR_INVALID_ARG; }
     QMRI_HIP(ctx, hipSetDevice(ctx->device));
     DevBuf<double> di, dout;
-    QMRI_TRY(dev_alloc(ctx, &di.p, (size_t)3 * S));
-    QMRI_TRY(dev_alloc(ctx, &dout.p, (size_t)3 * S));
+    QMRI_TRY(di.ensure(ctx, (size_t)3 * S));
+    QMRI_TRY(dout.ensure(ctx, (size_t)3 * S));
     QMRI_HIP(ctx, hipMemcpyAsync(di.p, in, (size_t)3 * S * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     QMRI_TRY(epg_shift_dev(ctx, S, nshift, di, dout));
     QMRI_HIP(ctx, hipMemcpyAsync(out, dout.p, (size_t)3 * S * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));

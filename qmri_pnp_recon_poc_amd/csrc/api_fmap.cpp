@@ -72,10 +72,10 @@ extern "C" int qmri_field_map_estimate(qmri_ctx* ctx, int nslices, int nechoes, 
     const size_t nf = (size_t)nslices * N * M, ny = nf * nechoes * ncoil;
     DevBuf<double2> dY;
     DevBuf<double> dinit, df, dtrust;
-    QMRI_TRY(dev_alloc(ctx, &dY.p, ny));
-    QMRI_TRY(dev_alloc(ctx, &df.p, nf));
-    if (f_init) QMRI_TRY(dev_alloc(ctx, &dinit.p, nf));
-    if (trust_out) QMRI_TRY(dev_alloc(ctx, &dtrust.p, nf));
+    QMRI_TRY(dY.ensure(ctx, ny));
+    QMRI_TRY(df.ensure(ctx, nf));
+    if (f_init) QMRI_TRY(dinit.ensure(ctx, nf));
+    if (trust_out) QMRI_TRY(dtrust.ensure(ctx, nf));
     QMRI_HIP(ctx, hipMemcpyAsync(dY.p, Y, ny * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
     if (f_init) QMRI_HIP(ctx, hipMemcpyAsync(dinit.p, f_init, nf * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     QMRI_TRY(fmap_estimate_dev(ctx, fmap_plan(nslices, nechoes, ncoil, N, M, t_s, p), dY.p, dinit.p, df.p, dtrust.p, info));

@@ -38,8 +38,8 @@ int llr_run(qmri_ctx* ctx, int N, int M, int s, int nslices, const double2* d_x,
     const LlrPlan pl = {N, M, s, b, o1, o2, real ? 1 : 0, p->tau};
     DevBuf<double> bs, sm;
     if (sigma_max_out) {
-        QMRI_TRY(dev_alloc(ctx, &bs.p, (size_t)nslices * (N / b) * (M / b)));
-        QMRI_TRY(dev_alloc(ctx, &sm.p, (size_t)nslices));
+        QMRI_TRY(bs.ensure(ctx, (size_t)nslices * (N / b) * (M / b)));
+        QMRI_TRY(sm.ensure(ctx, (size_t)nslices));
     }
     QMRI_TRY(llr_prox_dev(ctx, pl, nslices, d_x, nullptr, d_out, bs.p, sm.p));
     if (sigma_max_out) QMRI_HIP(ctx, hipMemcpyAsync(sigma_max_out, sm.p, (size_t)nslices * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -70,10 +70,10 @@ extern "C" int qmri_llr_prox(qmri_ctx* ctx, int N, int M, int s, int nslices, co
     const size_t n = (size_t)nslices * N * M * s;
     DevBuf<double2> dx;
     DevBuf<double> dr;
-    QMRI_TRY(dev_alloc(ctx, &dx.p, n));
+    QMRI_TRY(dx.ensure(ctx, n));
     if (x_is_complex) QMRI_HIP(ctx, hipMemcpyAsync(dx.p, x, n * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
     else {
-        QMRI_TRY(dev_alloc(ctx, &dr.p, n));
+        QMRI_TRY(dr.ensure(ctx, n));
         QMRI_HIP(ctx, hipMemcpyAsync(dr.p, x, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
         QMRI_TRY(ew_launch_real_to_complex(ctx, n, dr.p, dx.p));
     }

@@ -29,13 +29,7 @@ extern "C" size_t qmri_net_nparams(const qmri_net_desc* d) {
 }
 
 void qmri_free_net(qmri_ctx* ctx) {
-    NetPlan& p = ctx->net;
-    for (ConvLayer& L : p.layers) { if (L.wp) (void)hipFree(L.wp); if (L.d_tab) (void)hipFree(L.d_tab); if (L.wp6) (void)hipFree(L.wp6); }
-    for (float* b : p.allocs) if (b) (void)hipFree(b);
-    void* ptrs[] = { p.d_wflat, p.d_counter, p.d_stamps, p.d_c6part, p.d_res_xbuf, p.d_res_stamps, p.d_io, p.d_range_flag, p.d_act_slots, p.d_act_count, p.d_act_ref };
-    for (void* q : ptrs) if (q) (void)hipFree(q);               // (the plan's long-lived members, as qmri_free_operator releases the operator's)
-    if (p.h_range_flag) (void)hipHostFree(p.h_range_flag);
-    p = NetPlan();
+    ctx->net = NetPlan();
 }
 
 // zero-initialised padded activation tensor; Cal channels are allocated (>= C; the extra ones stay zero forever because
@@ -44,9 +38,7 @@ static int alloc_tensor(qmri_ctx* ctx, PTensor& t, int C, int Cal, int H, int W,
     t.C = C; t.Cal = std::max(C, Cal); t.H = H; t.W = W;
     t.h0 = 32; t.hp = ((t.h0 + H + 1 + 31) / 32) * 32;
     const size_t count = B * t.batch_stride() + 8192;
-    hipError_t e = hipMalloc((void**)&t.p, count * sizeof(float));
-    if (e != hipSuccess) { qmri_set_error(ctx, "hipMalloc of %zu bytes failed: %s", count * sizeof(float), hipGetErrorString(e)); return QMRI_ERR_NOMEM; }
-    ctx->net.allocs.push_back(t.p);
+    QMRI_TRY(ctx->net.pool.alloc(ctx, &t.p, count));
     QMRI_HIP(ctx, hipMemset(t.p, 0, count * sizeof(float)));
     return QMRI_OK;
 }
@@ -55,8 +47,7 @@ static int pack_layer6(qmri_ctx* ctx, ConvLayer& L, const float* w) {
     std::vector<uint16_t> p6;
     if (L.kind == CONV_3X3 || L.kind == CONV_3X3N) conv6_plan_pack(L, w, p6);     // (conv_plan_layer renames narrow 3x3 layers)
     else conv6s_plan_pack(L, w, p6);
-    hipError_t e = hipMalloc(&L.wp6, p6.size() * sizeof(uint16_t));
-    if (e != hipSuccess) { qmri_set_error(ctx, "hipMalloc (weights) failed: %s", hipGetErrorString(e)); return QMRI_ERR_NOMEM; }
+    QMRI_TRY(L.wp6.ensure(ctx, p6.size() * sizeof(uint16_t)));
     QMRI_HIP(ctx, hipMemcpy(L.wp6, p6.data(), p6.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
     return QMRI_OK;
 }
@@ -73,14 +64,13 @@ static int add_layer(qmri_ctx* ctx, ConvKind kind, int Cin, int Cout, const floa
     if (!ctx->net.d_wflat) {
         std::vector<float> packed;
         L.wp_floats = conv_pack_weights(L, w, packed);
-        hipError_t e = hipMalloc((void**)&L.wp, packed.size() * sizeof(float));
-        if (e != hipSuccess) { qmri_set_error(ctx, "hipMalloc (weights) failed: %s", hipGetErrorString(e)); return QMRI_ERR_NOMEM; }
+        QMRI_TRY(L.wp.ensure(ctx, packed.size()));
         QMRI_HIP(ctx, hipMemcpy(L.wp, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
         QMRI_TRY(pack_layer6(ctx, L, w));                      // the same weights, split for the bf16 / f16 matrix-core kernels
     }
     w += layer_weight_count(L);
     L.index = (int)ctx->net.layers.size();
-    ctx->net.layers.push_back(L);
+    ctx->net.layers.push_back(std::move(L));
     return QMRI_OK;
 }
 
@@ -97,7 +87,7 @@ static int net_pack_all_dev(qmri_ctx* ctx) {
     NetPlan& p = ctx->net;
     const size_t nl = p.layers.size();
     DevBuf<unsigned> d_max;
-    QMRI_HIP(ctx, hipMalloc((void**)&d_max.p, std::max<size_t>(nl, 1) * sizeof(unsigned)));
+    QMRI_TRY(d_max.ensure(ctx, nl));
     const int rc = [&]() -> int {
         if (hipMemsetAsync(d_max, 0, nl * sizeof(unsigned), ctx->stream) != hipSuccess) return QMRI_ERR_HIP;
         for (size_t l = 0; l < nl; ++l)
@@ -129,7 +119,7 @@ static int net_set_scheme(qmri_ctx* ctx, int sp) {
     if (p.sp6 == sp) return QMRI_OK;
     QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (ConvLayer& L : p.layers) {
-        if (L.wp6) { (void)hipFree(L.wp6); L.wp6 = nullptr; }
+        L.wp6.reset();
         L.sp6 = sp;
         if (p.d_wflat) QMRI_TRY(pack_layer6_dev(ctx, L));
         else QMRI_TRY(pack_layer6(ctx, L, p.w_host.data() + L.w_off));
@@ -205,8 +195,9 @@ static int net_calibrate_scheme(qmri_ctx* ctx) {
     DevBuf<float> d_tmp, d_ref;
     DevBuf<unsigned> d_m;
     const int rc = [&]() -> int {
-        if (hipMalloc((void**)&d_tmp.p, n * sizeof(float)) != hipSuccess || hipMalloc((void**)&d_ref.p, nout * sizeof(float)) != hipSuccess ||
-            hipMalloc((void**)&d_m.p, 2 * sizeof(unsigned)) != hipSuccess) return QMRI_ERR_NOMEM;
+        QMRI_TRY(d_tmp.ensure(ctx, n));
+        QMRI_TRY(d_ref.ensure(ctx, nout));
+        QMRI_TRY(d_m.ensure(ctx, 2));
         if (hipMemsetAsync(d_m, 0, 2 * sizeof(unsigned), ctx->stream) != hipSuccess ||
             hipMemcpyAsync(d_tmp, h.data(), n * sizeof(float), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return QMRI_ERR_HIP;
         QMRI_TRY(ew_launch_pack(ctx, 1, p.desc.in_nc, p.H, p.W, d_tmp, 0, p.in32));
@@ -242,7 +233,6 @@ static int net_calibrate_scheme(qmri_ctx* ctx) {
         return QMRI_OK;
     }();
     if (rc == QMRI_ERR_HIP && ctx->err.empty()) qmri_set_error(ctx, "HIP failure in the denoiser calibration pass");
-    if (rc == QMRI_ERR_NOMEM && ctx->err.empty()) qmri_set_error(ctx, "hipMalloc failed in the denoiser calibration pass");
     return rc;
 }
 
@@ -275,16 +265,16 @@ extern "C" int qmri_set_denoiser(qmri_ctx* ctx, const qmri_net_desc* desc, const
     const auto t_upload = std::chrono::steady_clock::now();
     if (qmri_knob(K_PACK_GPU)) {
         // the caller's blob goes to the device once, as it is; every packing is a kernel over it (net_pack_all_dev) and a later change of scheme re-packs from it
-        QMRI_HIP(ctx, hipMalloc((void**)&p.d_wflat, nbytes));
+        QMRI_TRY(p.pool.alloc(ctx, &p.d_wflat, nbytes / 4));
         QMRI_HIP(ctx, hipMemcpyAsync(p.d_wflat, weights, nbytes, hipMemcpyHostToDevice, ctx->stream));   // (on the stream the packing kernels run on: ordered with them)
     } else {
         p.w_host.assign(weights, weights + nbytes / 4);
         if (p.sp6 == 2 && !conv6_weights_fit_f16(weights, nbytes / 4)) p.sp6 = 3;     // weights beyond the f16 range: bf16 scheme
     }
-    QMRI_HIP(ctx, hipMalloc((void**)&p.d_range_flag, sizeof(unsigned)));
+    QMRI_TRY(p.pool.alloc(ctx, &p.d_range_flag, 1));
     QMRI_HIP(ctx, hipMemset(p.d_range_flag, 0, sizeof(unsigned)));
     p.h_range_words = 4096;
-    QMRI_HIP(ctx, hipHostMalloc((void**)&p.h_range_flag, (size_t)p.h_range_words * sizeof(unsigned), hipHostMallocDefault));
+    QMRI_TRY(p.h_range_flag.ensure(ctx, (size_t)p.h_range_words));
     std::memset(p.h_range_flag, 0, (size_t)p.h_range_words * sizeof(unsigned));
     const float* w = weights;
     const int nb = desc->nb;
@@ -323,10 +313,10 @@ extern "C" int qmri_set_denoiser(qmri_ctx* ctx, const qmri_net_desc* desc, const
         }
         if (nc[0] == 64 && H % 16 == 0 && W % 16 == 0 && (H / 16) * (W / 16) <= 1024) {                   // k_conv6r's exchange buffer (one slice)
             p.res_tiles = (H / 16) * (W / 16);
-            QMRI_TRY(dev_alloc(ctx, &p.d_res_xbuf, conv6r_xbuf_bytes(p.res_tiles)));
+            QMRI_TRY(p.pool.alloc(ctx, &p.d_res_xbuf, conv6r_xbuf_bytes(p.res_tiles)));
             QMRI_HIP(ctx, hipMemset(p.d_res_xbuf, 0, conv6r_xbuf_bytes(p.res_tiles)));
             p.res_epoch = 0; p.res_off = false;
-            if (qmri_knob(K_RES_STAMPS)) { QMRI_HIP(ctx, hipMalloc(&p.d_res_stamps, 2048 * sizeof(unsigned long long))); QMRI_HIP(ctx, hipMemset(p.d_res_stamps, 0, 2048 * sizeof(unsigned long long))); }
+            if (qmri_knob(K_RES_STAMPS)) { QMRI_TRY(p.pool.alloc(ctx, &p.d_res_stamps, 2048 * sizeof(unsigned long long))); QMRI_HIP(ctx, hipMemset(p.d_res_stamps, 0, 2048 * sizeof(unsigned long long))); }
         }
     } else {
         const int width = desc->nc[0];
@@ -355,9 +345,9 @@ extern "C" int qmri_set_denoiser(qmri_ctx* ctx, const qmri_net_desc* desc, const
     else if (nb > 1 && desc->nc[0] % 8) p.blk_ok = false;
     for (int l = 0; l < 4; ++l) if ((p.x[l].p && p.x[l].Cal % 8) || (p.a[l].p && p.a[l].Cal % 8) || (p.t[l].p && p.t[l].Cal % 8)) p.blk_ok = false;
     p.interior_fmt = -1;
-    QMRI_TRY(dev_alloc(ctx, &p.d_counter, (size_t)1));
+    QMRI_TRY(p.pool.alloc(ctx, &p.d_counter, (size_t)1));
     QMRI_HIP(ctx, hipMemset(p.d_counter, 0, sizeof(unsigned)));
-    if (qmri_knob(K_CONV_STAMPS)) { QMRI_HIP(ctx, hipMalloc(&p.d_stamps, 4096 * 11 * sizeof(unsigned long long))); }
+    if (qmri_knob(K_CONV_STAMPS)) { QMRI_TRY(p.pool.alloc(ctx, &p.d_stamps, 4096 * 11 * sizeof(unsigned long long))); }
     p.counter_base = 0;
     p.ready = true;
     // (device-wide: the host packers' blocking copies travel on the NULL stream, which this context's non-blocking stream is not ordered with -- beside
@@ -598,12 +588,7 @@ extern "C" int qmri_denoise(qmri_ctx* ctx, const double* in, int H, int W, int C
         }
     }
     // staging buffer of the per-call drop-in mode (the reference's own PnP_ADMM.m calling param.net 100 times): kept with the plan, grown on demand
-    if (p.io_cap < std::max(nin, nout)) {
-        QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (p.d_io) { (void)hipFree(p.d_io); p.d_io = nullptr; p.io_cap = 0; }
-        QMRI_HIP(ctx, hipMalloc((void**)&p.d_io, std::max(nin, nout) * sizeof(double)));
-        p.io_cap = std::max(nin, nout);
-    }
+    QMRI_TRY(p.d_io.ensure(ctx, std::max(nin, nout)));
     double* const d_io = p.d_io;
     bool again = false;
     auto pass = [&]() -> int {

@@ -48,25 +48,13 @@ void deapodisation(int L, int w, double beta, double* out) {
     }
 }
 
-template <typename T> int nu_alloc(qmri_ctx* ctx, T** p, size_t count) {
-    *p = nullptr;
-    const hipError_t e = hipMalloc((void**)p, std::max<size_t>(count, 1) * sizeof(T));
-    if (e != hipSuccess) { qmri_set_error(ctx, "hipMalloc of %zu bytes failed: %s", count * sizeof(T), hipGetErrorString(e)); return QMRI_ERR_NOMEM; }
-    return QMRI_OK;
-}
 template <typename T> int nu_upload(qmri_ctx* ctx, T** p, const std::vector<T>& v) {
-    QMRI_TRY(nu_alloc(ctx, p, v.size()));
+    QMRI_TRY(ctx->op.pool.alloc(ctx, p, v.size()));
     if (!v.empty()) QMRI_HIP(ctx, hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     return QMRI_OK;
 }
 inline int wrap(int k, int G) { k %= G; return k < 0 ? k + G : k; }
 }  // namespace
-
-void nufft_free(NufftHost& h) {
-    void* ptrs[] = {h.d_u, h.d_ph, h.d_t, h.d_perm, h.d_list, h.d_seg, h.d_red, h.d_dp, h.d_r, h.d_g, h.d_grid, h.d_part, h.d_ones, h.d_khat, h.d_w, h.d_pm, h.d_bl, h.d_khat_fm, h.d_pm_n, h.d_xs};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    h = NufftHost();
-}
 
 int nufft_check_gridded(qmri_ctx* ctx, const char* what, const char* instead) {
     if (ctx->op.kind != OP_NUFFT) return QMRI_OK;
@@ -216,22 +204,22 @@ extern "C" int qmri_set_operator_nufft(qmri_ctx* ctx, int N, int M, int s, int T
     QMRI_TRY(nu_upload(ctx, &h.d_dp, dp));
     QMRI_TRY(nu_upload(ctx, &h.d_r, ramp));
     QMRI_TRY(nu_upload(ctx, &h.d_ones, std::vector<double2>((size_t)N * M, make_double2(1.0, 0.0))));
-    QMRI_TRY(nu_alloc(ctx, &h.d_g, 4 * B * n));
-    QMRI_TRY(nu_alloc(ctx, &h.d_grid, 4 * B * n));
-    QMRI_TRY(nu_alloc(ctx, &h.d_part, B * std::max(nslot, 1) * (size_t)s * 256));
+    QMRI_TRY(o.pool.alloc(ctx, &h.d_g, 4 * B * n));
+    QMRI_TRY(o.pool.alloc(ctx, &h.d_grid, 4 * B * n));
+    QMRI_TRY(o.pool.alloc(ctx, &h.d_part, B * std::max(nslot, 1) * (size_t)s * 256));
     // what the host-array entry points and the image-domain LSQR / ADMM loop use (as qmri_set_operator allocates them)
     LsqrDev& ls = o.ls;
     ls.nblk_z = 256;
-    QMRI_TRY(nu_alloc(ctx, &o.d_xa, B * n));
-    QMRI_TRY(nu_alloc(ctx, &o.d_xb, B * n));
-    QMRI_TRY(nu_alloc(ctx, &o.d_ya, B * (size_t)m));
-    QMRI_TRY(nu_alloc(ctx, &ls.pz, B * (size_t)ls.nblk_z));
-    QMRI_TRY(nu_alloc(ctx, &o.d_x, B * n));
-    QMRI_TRY(nu_alloc(ctx, &o.d_u, B * n));
-    QMRI_TRY(nu_alloc(ctx, &o.d_vv, B * n));
-    QMRI_TRY(nu_alloc(ctx, &o.d_z, B * n));
-    QMRI_TRY(nu_alloc(ctx, &o.d_mm, B * (size_t)ls.nblk_z * 2));
-    QMRI_TRY(nu_alloc(ctx, &o.d_norm, B * 2));
+    QMRI_TRY(o.pool.alloc(ctx, &o.d_xa, B * n));
+    QMRI_TRY(o.pool.alloc(ctx, &o.d_xb, B * n));
+    QMRI_TRY(o.pool.alloc(ctx, &o.d_ya, B * (size_t)m));
+    QMRI_TRY(o.pool.alloc(ctx, &ls.pz, B * (size_t)ls.nblk_z));
+    QMRI_TRY(o.pool.alloc(ctx, &o.d_x, B * n));
+    QMRI_TRY(o.pool.alloc(ctx, &o.d_u, B * n));
+    QMRI_TRY(o.pool.alloc(ctx, &o.d_vv, B * n));
+    QMRI_TRY(o.pool.alloc(ctx, &o.d_z, B * n));
+    QMRI_TRY(o.pool.alloc(ctx, &o.d_mm, B * (size_t)ls.nblk_z * 2));
+    QMRI_TRY(o.pool.alloc(ctx, &o.d_norm, B * 2));
     QMRI_HIP(ctx, hipDeviceSynchronize());          // (as qmri_set_operator: the blocking copies must have landed before the context's stream reads them)
     o.ready = true;
     return QMRI_OK;

@@ -17,17 +17,12 @@ constexpr int OFFRES_NLMAX = 32;          // segments of the field-aware normal 
 constexpr double OFFRES_TOL_DEF = 1e-4;
 typedef std::complex<double> cplx;
 
-// device buffers that live for one call
-struct Temp {
-    std::vector<void*> ptrs;
-    ~Temp() { for (void* p : ptrs) if (p) (void)hipFree(p); }
-    template <typename T> int upload(qmri_ctx* ctx, T** d, const T* src, size_t count) {
-        QMRI_TRY(dev_alloc(ctx, d, count));
-        ptrs.push_back(*d);
-        QMRI_HIP(ctx, hipMemcpy(*d, src, count * sizeof(T), hipMemcpyHostToDevice));
-        return QMRI_OK;
-    }
-};
+// a host array into a device buffer that lives as long as `pool` (one call)
+template <typename T> int upload(qmri_ctx* ctx, DevPool& pool, T** d, const T* src, size_t count) {
+    QMRI_TRY(pool.alloc(ctx, d, count));
+    QMRI_HIP(ctx, hipMemcpy(*d, src, count * sizeof(T), hipMemcpyHostToDevice));
+    return QMRI_OK;
+}
 
 // lower Cholesky factor (row-major, in place) of the Hermitian positive definite A [L][L]; false on a pivot that is not positive
 bool cholesky(std::vector<cplx>& A, int L) {
@@ -71,13 +66,6 @@ bool qr_mgs2(std::vector<double>& B, size_t rows, int L, std::vector<double>& U)
     return true;
 }
 
-int ensure(qmri_ctx* ctx, double2** p, size_t* cap, size_t count) {
-    if (*p && *cap >= count) return QMRI_OK;
-    if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
-    QMRI_TRY(dev_alloc(ctx, p, count));
-    *cap = count;
-    return QMRI_OK;
-}
 }  // namespace
 
 int offres_refuse_toeplitz(qmri_ctx* ctx, const char* what) {
@@ -91,9 +79,7 @@ int offres_refuse_toeplitz(qmri_ctx* ctx, const char* what) {
 
 void offres_drop_normal(NufftHost& h) {
     h.fmn_ready = false; h.fmn_plain = false; h.fmn_L = 0;
-    void* ptrs[] = {h.d_khat_fm, h.d_pm_n, h.d_xs};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    h.d_khat_fm = nullptr; h.d_pm_n = nullptr; h.d_xs = nullptr;
+    h.d_khat_fm.reset(); h.d_pm_n.reset(); h.d_xs.reset();
 }
 
 extern "C" int qmri_set_field_map(qmri_ctx* ctx, const double* f_hz, const double* t_s, const qmri_offres_params* p, qmri_offres_info* info) {
@@ -155,13 +141,13 @@ extern "C" int qmri_set_field_map(qmri_ctx* ctx, const double* f_hz, const doubl
         }
         for (int b = 0; b < nbins; ++b) hist[b] = make_double2((double)cnt[b] / (double)plane, constant ? 0.0 : lo + (b + 0.5) * width);
     }
-    Temp tmp;
+    DevPool tmp;
     double* d_f = nullptr; double* d_ts = nullptr; double2* d_hist = nullptr;
-    QMRI_TRY(tmp.upload(ctx, &d_f, f_hz, plane));
-    QMRI_TRY(tmp.upload(ctx, &d_ts, t_s, (size_t)o.m));
-    QMRI_TRY(tmp.upload(ctx, &d_hist, hist.data(), hist.size()));
+    QMRI_TRY(upload(ctx, tmp, &d_f, f_hz, plane));
+    QMRI_TRY(upload(ctx, tmp, &d_ts, t_s, (size_t)o.m));
+    QMRI_TRY(upload(ctx, tmp, &d_hist, hist.data(), hist.size()));
     const int L_first = constant ? 1 : (nseg ? nseg : 2), L_last = constant ? 1 : (nseg ? nseg : OFFRES_LMAX);
-    QMRI_TRY(ensure(ctx, &h.d_bl, &h.bl_cap, (size_t)L_last * o.m));           // (sized here, at attach time: auto mode for its largest L)
+    QMRI_TRY(h.d_bl.ensure(ctx, (size_t)L_last * o.m));           // (sized here, at attach time: auto mode for its largest L)
     OffresFit fit{0.0, 0.0};
     std::vector<double> tauhat;
     int L = L_first, reached = 0;
@@ -181,18 +167,18 @@ extern "C" int qmri_set_field_map(qmri_ctx* ctx, const double* f_hz, const doubl
         std::vector<double2> Gd(G.size()), Cd(A.size());
         for (size_t i = 0; i < G.size(); ++i) Gd[i] = make_double2(G[i].real(), G[i].imag());
         for (size_t i = 0; i < A.size(); ++i) Cd[i] = make_double2(A[i].real(), A[i].imag());
-        Temp per;
+        DevPool per;
         double2* d_G = nullptr; double2* d_C = nullptr;
-        QMRI_TRY(per.upload(ctx, &d_G, Gd.data(), Gd.size()));
-        QMRI_TRY(per.upload(ctx, &d_C, Cd.data(), Cd.size()));
+        QMRI_TRY(upload(ctx, per, &d_G, Gd.data(), Gd.size()));
+        QMRI_TRY(upload(ctx, per, &d_C, Cd.data(), Cd.size()));
         QMRI_TRY(offres_coefficients_dev(ctx, L, nbins, constant, d_hist, d_G, d_C, d_ts, f0, h.d_bl, &fit));
         reached = fit.fit_max <= tol;
         if (reached || L == L_last) break;
     }
     // the phase maps of the chosen segments, [L][N*M]
-    QMRI_TRY(ensure(ctx, &h.d_pm, &h.pm_cap, (size_t)L * plane));
+    QMRI_TRY(h.d_pm.ensure(ctx, (size_t)L * plane));
     double* d_tau = nullptr;
-    QMRI_TRY(tmp.upload(ctx, &d_tau, tauhat.data(), tauhat.size()));
+    QMRI_TRY(upload(ctx, tmp, &d_tau, tauhat.data(), tauhat.size()));
     QMRI_TRY(offres_phase_maps_dev(ctx, L, plane, d_f, f0, d_tau, h.d_pm));
     QMRI_HIP(ctx, hipDeviceSynchronize());          // (as qmri_set_operator: everything has landed before the context's stream reads it)
     h.fm_L = L;
@@ -255,18 +241,17 @@ extern "C" int qmri_nufft_prepare_normal_fm(qmri_ctx* ctx, const qmri_offres_nor
         for (int b = std::max(0, j); b < std::min(nbins, nbins + j); ++b) a += h.fm_p[b] * h.fm_p[b - j];
         dh[(size_t)(j + nbins - 1)] = make_double2(a, j * width);
     }
-    Temp tmp;
+    DevPool tmp;
     double* d_ts = nullptr; double2* d_dh = nullptr; double* d_c = nullptr;
     const int L_first = nseg ? nseg : 2, L_last = nseg ? nseg : OFFRES_NLMAX;
-    QMRI_TRY(tmp.upload(ctx, &d_ts, h.fm_ts.data(), h.fm_ts.size()));
-    QMRI_TRY(tmp.upload(ctx, &d_dh, dh.data(), dh.size()));
-    QMRI_TRY(dev_alloc(ctx, &d_c, (size_t)L_last * o.m));
-    tmp.ptrs.push_back(d_c);
+    QMRI_TRY(upload(ctx, tmp, &d_ts, h.fm_ts.data(), h.fm_ts.size()));
+    QMRI_TRY(upload(ctx, tmp, &d_dh, dh.data(), dh.size()));
+    QMRI_TRY(tmp.alloc(ctx, &d_c, (size_t)L_last * o.m));
     // the tables of one tried L', allocated once at the largest L' of the search
     double2* d_G = nullptr; double2* d_Qw = nullptr; double* d_U = nullptr;
-    QMRI_TRY(dev_alloc(ctx, &d_G, (size_t)nb * L_last)); tmp.ptrs.push_back(d_G);
-    QMRI_TRY(dev_alloc(ctx, &d_Qw, (size_t)nb * L_last)); tmp.ptrs.push_back(d_Qw);
-    QMRI_TRY(dev_alloc(ctx, &d_U, (size_t)L_last * L_last)); tmp.ptrs.push_back(d_U);
+    QMRI_TRY(tmp.alloc(ctx, &d_G, (size_t)nb * L_last));
+    QMRI_TRY(tmp.alloc(ctx, &d_Qw, (size_t)nb * L_last));
+    QMRI_TRY(tmp.alloc(ctx, &d_U, (size_t)L_last * L_last));
     OffresFit fit{0.0, 0.0};
     std::vector<double> tauhat;
     int L = L_first, reached = 0;
@@ -309,19 +294,17 @@ extern "C" int qmri_nufft_prepare_normal_fm(qmri_ctx* ctx, const qmri_offres_nor
     }
     // everything the transform needs is allocated before the context changes: on a failure the context is as it was before the call
     DevBuf<double2> khat, pm, xs;
-    QMRI_TRY(dev_alloc(ctx, &khat.p, (size_t)L * kseg));
-    QMRI_TRY(dev_alloc(ctx, &pm.p, (size_t)L * plane));
-    QMRI_TRY(dev_alloc(ctx, &xs.p, (size_t)o.maxB * n));
+    QMRI_TRY(khat.ensure(ctx, (size_t)L * kseg));
+    QMRI_TRY(pm.ensure(ctx, (size_t)L * plane));
+    QMRI_TRY(xs.ensure(ctx, (size_t)o.maxB * n));
     double* d_f = nullptr; double* d_tau = nullptr;
-    QMRI_TRY(tmp.upload(ctx, &d_f, h.fm_f.data(), h.fm_f.size()));
-    QMRI_TRY(tmp.upload(ctx, &d_tau, tauhat.data(), tauhat.size()));
+    QMRI_TRY(upload(ctx, tmp, &d_f, h.fm_f.data(), h.fm_f.size()));
+    QMRI_TRY(upload(ctx, tmp, &d_tau, tauhat.data(), tauhat.size()));
     QMRI_TRY(offres_phase_maps_dev(ctx, L, plane, d_f, h.fm_f0, d_tau, pm.p));
     for (int l = 0; l < L; ++l) QMRI_TRY(toep_build_weighted(ctx, d_c + (size_t)l * o.m, khat.p + (size_t)l * kseg));
     QMRI_HIP(ctx, hipDeviceSynchronize());
     offres_drop_normal(h);
-    h.d_khat_fm = khat.p; khat.p = nullptr;
-    h.d_pm_n = pm.p; pm.p = nullptr;
-    h.d_xs = xs.p; xs.p = nullptr;
+    h.d_khat_fm = std::move(khat); h.d_pm_n = std::move(pm); h.d_xs = std::move(xs);
     h.fmn_L = L; h.fmn_plain = false; h.fmn_ready = true;
     if (info) {
         *info = qmri_offres_normal_info{};

@@ -223,31 +223,19 @@ __global__ void __launch_bounds__(NT) k_cc_proj(const double2* __restrict__ in, 
         if (l0 + l < nv) dst[(size_t)(l0 + l) * len] = acc[l];
 }
 
-template <class T> bool grow(T*& p, size_t& cap, size_t n) {
-    if (p && n <= cap) return true;
-    if (p) (void)hipFree(p);
-    p = nullptr; cap = 0;
-    if (hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) { p = nullptr; return false; }
-    cap = n;
-    return true;
-}
 }  // namespace
-
-void cc_free_work(CcWork& w) {
-    void* ptrs[] = {w.part, w.R, w.X, w.L, w.U, w.W, w.psi, w.sy, w.sm, w.oy, w.om};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    if (w.hK) (void)hipHostFree(w.hK);
-    if (w.hbad) (void)hipHostFree(w.hbad);
-    w = CcWork();
-}
 
 int cc_ensure_staging(qmri_ctx* ctx, size_t ny, size_t nm, size_t nyo, size_t nmo) {
     CcWork& w = ctx->cc;
-    if (!grow(w.sy, w.sy_cap, ny) || (nm && !grow(w.sm, w.sm_cap, nm)) || !grow(w.oy, w.oy_cap, nyo) || (nmo && !grow(w.om, w.om_cap, nmo))) {
-        qmri_set_error(ctx, "out of device memory for the staging of the coil compression");
-        return QMRI_ERR_NOMEM;
-    }
-    return QMRI_OK;
+    const int st = [&]() -> int {
+        QMRI_TRY(w.sy.ensure(ctx, ny));
+        if (nm) QMRI_TRY(w.sm.ensure(ctx, nm));
+        QMRI_TRY(w.oy.ensure(ctx, nyo));
+        if (nmo) QMRI_TRY(w.om.ensure(ctx, nmo));
+        return QMRI_OK;
+    }();
+    if (st == QMRI_ERR_NOMEM) qmri_set_error(ctx, "out of device memory for the staging of the coil compression");
+    return st;
 }
 
 // The whole transform on device arrays (api_cc.cpp checks the arguments).  d_psi: device ncoil x ncoil or nullptr.  Writes *nv_out, y_out [B][nv][m],
@@ -259,18 +247,16 @@ int cc_compress_dev(qmri_ctx* ctx, int B, int ncoil, const double2* d_y, const d
     const int n = ncoil, npairs = n * (n + 1) / 2, chunk = cc_chunk(n), nblk = (o.m + chunk - 1) / chunk;
     const int nmat = prm.shared ? 1 : B;
     const size_t nn = (size_t)n * n, plane = (size_t)o.N * o.M;
-    if (!grow(w.part, w.part_cap, (size_t)B * nblk * npairs) || !grow(w.R, w.R_cap, nmat * nn) || !grow(w.X, w.X_cap, nmat * nn) ||
-        !grow(w.U, w.U_cap, nmat * nn) || !grow(w.W, w.W_cap, nmat * nn) || (d_psi && !grow(w.L, w.L_cap, nn))) {
-        qmri_set_error(ctx, "out of device memory for the coil compression of %d slices x %d coils", B, n);
-        return QMRI_ERR_NOMEM;
-    }
-    if (!w.hK || w.hK_cap < nmat * nn) {
-        if (w.hK) (void)hipHostFree(w.hK);
-        w.hK = nullptr; w.hK_cap = 0;
-        QMRI_HIP(ctx, hipHostMalloc((void**)&w.hK, nmat * nn * sizeof(double2), hipHostMallocDefault));
-        w.hK_cap = nmat * nn;
-    }
-    if (!w.hbad) QMRI_HIP(ctx, hipHostMalloc((void**)&w.hbad, sizeof(int), hipHostMallocDefault));
+    const int got = [&]() -> int {
+        QMRI_TRY(w.part.ensure(ctx, (size_t)B * nblk * npairs));
+        for (DevArr<double2>* a : {&w.R, &w.X, &w.U, &w.W}) QMRI_TRY(a->ensure(ctx, nmat * nn));
+        if (d_psi) QMRI_TRY(w.L.ensure(ctx, nn));
+        return QMRI_OK;
+    }();
+    if (got == QMRI_ERR_NOMEM) qmri_set_error(ctx, "out of device memory for the coil compression of %d slices x %d coils", B, n);
+    QMRI_TRY(got);
+    QMRI_TRY(w.hK.ensure(ctx, nmat * nn));
+    QMRI_TRY(w.hbad.ensure(ctx, 1));
     *w.hbad = 0;
     if (d_psi) {
         k_cc_chol<<<1, NT, 0, ctx->stream>>>(d_psi, n, w.L, w.hbad);

@@ -278,7 +278,7 @@ template <int CFG> constexpr size_t conv6p_lds() {
 static ActMax conv6_act_slot(qmri_ctx* ctx, bool reports, const ConvLayer& L) {
     NetPlan& net = ctx->net;
     ActMax am{net.d_act_slots, net.d_act_count, -1};
-    if (reports && net.act_on && net.d_act_slots && L.index >= 0 && L.index < net.act_cap) am.layer = L.index;
+    if (reports && net.act_on && net.d_act_slots && L.index >= 0 && L.index < net.act_rows) am.layer = L.index;
     return am;
 }
 

@@ -497,7 +497,7 @@ int launch6(qmri_ctx* ctx, const ConvLayer& L, int B, const PTensor& in, const P
             const PTensor* add2, int relu_out, int ksplit = 1, float* partial = nullptr, long out_ks = 0, const ProfSpan* span = nullptr) {
     typedef Cfg6<CFG> C;
     Conv6Args A;
-    A.in = in.fbase(); A.wp = reinterpret_cast<const uint4*>(L.wp6); A.out = out.fbase();
+    A.in = in.fbase(); A.wp = reinterpret_cast<const uint4*>(L.wp6.p); A.out = out.fbase();
     A.add1 = add1 ? add1->fbase() : nullptr; A.add2 = add2 ? add2->fbase() : nullptr;
     A.in_blk = in.blk ? 1 : 0; A.out_blk = (out.blk && !partial) ? 1 : 0;       // (split-K partial sums are planar scratch)
     if ((add1 && add1->blk != out.blk) || (add2 && add2->blk != out.blk) || (out.blk && L.Cout % 8 != 0)) {
@@ -667,12 +667,12 @@ int conv6_act_begin(qmri_ctx* ctx, int nlayers) {
     net.act_on = false;
     if (net.sp6 != 2) return QMRI_OK;
     if (!net.d_act_slots) {
-        net.act_cap = nlayers;
-        QMRI_HIP(ctx, hipMalloc((void**)&net.d_act_slots, (size_t)net.act_cap * ACT_MAXSLOT * sizeof(float)));
-        QMRI_HIP(ctx, hipMalloc((void**)&net.d_act_count, (size_t)net.act_cap * sizeof(int)));
-        QMRI_HIP(ctx, hipMalloc((void**)&net.d_act_ref, (size_t)net.act_cap * sizeof(float)));
-        QMRI_HIP(ctx, hipMemsetAsync(net.d_act_count, 0, (size_t)net.act_cap * sizeof(int), ctx->stream));
-        QMRI_HIP(ctx, hipMemsetAsync(net.d_act_ref, 0, (size_t)net.act_cap * sizeof(float), ctx->stream));   // (0: nothing calibrated, nothing trips)
+        net.act_rows = nlayers;
+        QMRI_TRY(net.pool.alloc(ctx, &net.d_act_slots, (size_t)net.act_rows * ACT_MAXSLOT));
+        QMRI_TRY(net.pool.alloc(ctx, &net.d_act_count, (size_t)net.act_rows));
+        QMRI_TRY(net.pool.alloc(ctx, &net.d_act_ref, (size_t)net.act_rows));
+        QMRI_HIP(ctx, hipMemsetAsync(net.d_act_count, 0, (size_t)net.act_rows * sizeof(int), ctx->stream));
+        QMRI_HIP(ctx, hipMemsetAsync(net.d_act_ref, 0, (size_t)net.act_rows * sizeof(float), ctx->stream));   // (0: nothing calibrated, nothing trips)
     }
     net.act_on = true;
     return QMRI_OK;
@@ -684,10 +684,10 @@ int conv6_act_end(qmri_ctx* ctx) {
     const bool verbose = qmri_knob(K_VERBOSE) != 0;
     if (verbose) {                                                  // diagnostic: the per-layer maxima of this forward pass
         QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        std::vector<int> cnt(net.act_cap);
+        std::vector<int> cnt(net.act_rows);
         QMRI_HIP(ctx, hipMemcpy(cnt.data(), net.d_act_count, cnt.size() * sizeof(int), hipMemcpyDeviceToHost));
         fprintf(stderr, "libqmri: largest |output| per layer%s:", net.act_record ? " (calibration probe)" : "");
-        for (int l = 0; l < net.act_cap; ++l) {
+        for (int l = 0; l < net.act_rows; ++l) {
             std::vector<float> v(std::max(cnt[l], 1), 0.f);
             QMRI_HIP(ctx, hipMemcpy(v.data(), net.d_act_slots + (size_t)l * ACT_MAXSLOT, (size_t)cnt[l] * sizeof(float), hipMemcpyDeviceToHost));
             fprintf(stderr, " %.3g", *std::max_element(v.begin(), v.end()));
@@ -695,13 +695,13 @@ int conv6_act_end(qmri_ctx* ctx) {
         fprintf(stderr, "\n");
     }
     const ActCheckArgs ac = {net.d_act_slots, net.d_act_count, net.d_act_ref, net.act_record ? 1 : 0, net.d_range_flag,
-                             (net.act_cap + 1 <= net.h_range_words) ? net.h_range_flag : nullptr, net.act_cap};
+                             (net.act_rows + 1 <= net.h_range_words) ? net.h_range_flag : nullptr, net.act_rows};
     if (net.act_defer && !net.act_record) {                         // the caller's next kernel finishes the layers (qmri_pnp_admm_dev)
         net.act_pending = ac;
         net.act_pending_valid = true;
         return QMRI_OK;
     }
-    k_act_check<<<dim3(net.act_cap), dim3(256), 0, ctx->stream>>>(ac);
+    k_act_check<<<dim3(net.act_rows), dim3(256), 0, ctx->stream>>>(ac);
     QMRI_HIP(ctx, hipGetLastError());
     return QMRI_OK;
 }
@@ -785,8 +785,8 @@ int conv6_pack_dev(qmri_ctx* ctx, ConvLayer& L, const float* d_w, float wmax) {
     L.n_ct6 = (L.Cout + 63) / 64;
     const float wscale = conv6_scale_from_max(L, wmax);
     const long nent = (long)L.n_ct6 * L.nchunk6 * 9 * 2 * 64;
-    QMRI_HIP(ctx, hipMalloc(&L.wp6, (size_t)nent * L.sp6 * sizeof(uint4)));
-    k_pack6_w<<<dim3((unsigned)((nent + 255) / 256)), dim3(256), 0, ctx->stream>>>(d_w, (uint4*)L.wp6, L.Cin, L.Cout, L.nchunk6, nent, L.sp6, wscale);
+    QMRI_TRY(L.wp6.ensure(ctx, (size_t)nent * L.sp6 * sizeof(uint4)));
+    k_pack6_w<<<dim3((unsigned)((nent + 255) / 256)), dim3(256), 0, ctx->stream>>>(d_w, (uint4*)L.wp6.p, L.Cin, L.Cout, L.nchunk6, nent, L.sp6, wscale);
     QMRI_HIP(ctx, hipGetLastError());
     return QMRI_OK;
 }
@@ -831,11 +831,7 @@ int conv6_launch(qmri_ctx* ctx, const ConvLayer& L, int B, const PTensor& in, co
             const long out_ks = (long)B * out.Cal * out.plane();
             const size_t need = (size_t)ksplit * out_ks + 8192;
             NetPlan& net = ctx->net;
-            if (net.c6part_floats < need) {
-                if (net.d_c6part) { QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream)); QMRI_HIP(ctx, hipFree(net.d_c6part)); net.d_c6part = nullptr; }
-                QMRI_HIP(ctx, hipMalloc((void**)&net.d_c6part, need * sizeof(float)));
-                net.c6part_floats = need;
-            }
+            QMRI_TRY(net.d_c6part.ensure(ctx, need));
             // profile level 2: ONE unit per layer -- from the convolution's start to the end of the reduce kernel that completes it
             ProfSpan span;
             QMRI_TRY(qmri_prof_pair(ctx, &span.start, &span.stop, PROF_CONV3, conv_layer_flop(L, B, in.H, in.W)));

@@ -423,7 +423,7 @@ int launch6p_t(qmri_ctx* ctx, const ConvLayer& L, int B, const PTensor& in, cons
                int relu_out) {
     typedef Cfg6<CFG> C;
     Conv6Args A{};
-    A.in = in.fbase(); A.wp = reinterpret_cast<const uint4*>(L.wp6); A.out = out.fbase();   // (BLOCKED tensors: launch6p checks)
+    A.in = in.fbase(); A.wp = reinterpret_cast<const uint4*>(L.wp6.p); A.out = out.fbase();   // (BLOCKED tensors: launch6p checks)
     A.add1 = add1 ? add1->fbase() : nullptr; A.add2 = add2 ? add2->fbase() : nullptr;
     A.in_blk = 1; A.out_blk = 1;
     A.Cout = L.Cout; A.W = in.W; A.H = in.H;

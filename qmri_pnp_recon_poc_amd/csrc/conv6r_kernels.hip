@@ -811,7 +811,7 @@ int conv6r_try(qmri_ctx* ctx, const Conv6rRun& run, int B, bool* done) {
     if (run.tail) { A.out = run.tail_out->fbase(); A.out_hp = run.tail_out->hp; A.out_plane = (int)run.tail_out->plane(); A.out_c = run.tail->Cout; }
     int l = 0;
     auto put = [&](const ConvLayer& L, int kind, const float* radd, float* sdst) {
-        A.wp[l] = reinterpret_cast<const uint4*>(L.wp6);
+        A.wp[l] = reinterpret_cast<const uint4*>(L.wp6.p);
         A.dh[l] = L.w6_descale; A.dl[l] = L.w6_descale * (1.f / LO_SCALE);
         A.am_layer[l] = conv6_act_slot(ctx, true, L).layer;
         A.nch[l] = L.nchunk6; A.kind[l] = kind; A.radd[l] = radd; A.sdst[l] = sdst;

@@ -376,8 +376,8 @@ int conv6s_pack_dev(qmri_ctx* ctx, ConvLayer& L, const float* d_w, float wmax) {
     L.n_ct6 = up ? 2 * ((L.Cout + 31) / 32) : (L.Cout + 63) / 64;
     const float wscale = conv6_scale_from_max(L, wmax);
     const long nent = (long)L.n_ct6 * L.nchunk6 * 2 * 2 * 64;
-    QMRI_HIP(ctx, hipMalloc(&L.wp6, (size_t)nent * L.sp6 * sizeof(uint4)));
-    k_pack6s_w<<<dim3((unsigned)((nent + 255) / 256)), dim3(256), 0, ctx->stream>>>(d_w, (uint4*)L.wp6, up ? 1 : 0, L.Cin, L.Cout, L.nchunk6, L.nsteps6s, nent, L.sp6, wscale);
+    QMRI_TRY(L.wp6.ensure(ctx, (size_t)nent * L.sp6 * sizeof(uint4)));
+    k_pack6s_w<<<dim3((unsigned)((nent + 255) / 256)), dim3(256), 0, ctx->stream>>>(d_w, (uint4*)L.wp6.p, up ? 1 : 0, L.Cin, L.Cout, L.nchunk6, L.nsteps6s, nent, L.sp6, wscale);
     QMRI_HIP(ctx, hipGetLastError());
     return QMRI_OK;
 }
@@ -403,7 +403,7 @@ int conv6s_launch(qmri_ctx* ctx, const ConvLayer& L, int B, const PTensor& in, c
         qmri_set_error(ctx, "conv layer %d: input and output of a 2x2 layer must share one tensor format", L.index);
         return QMRI_ERR_STATE;
     }
-    A.in = in.fbase(); A.wp = reinterpret_cast<const uint4*>(L.wp6); A.out = out.fbase();
+    A.in = in.fbase(); A.wp = reinterpret_cast<const uint4*>(L.wp6.p); A.out = out.fbase();
     A.Cout = L.Cout;
     A.GH = up ? in.H : in.H / 2; A.GW = up ? in.W : in.W / 2;
     A.in_hp = in.hp; A.in_plane = (int)in.plane(); A.in_bs = (long)in.Cal * in.plane();

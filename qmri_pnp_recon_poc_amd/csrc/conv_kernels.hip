@@ -377,16 +377,15 @@ int launch_kind(qmri_ctx* ctx, ConvLayer& L, int B, const PTensor& in, const PTe
         for (int b = 0; b < B; ++b)
             for (int pt = 0; pt < n_pt; ++pt)
                 for (int ct = 0; ct < n_ctiles; ++ct) tab[i++] = make_int4(ct, (pt / tiles_h) * JW, (pt % tiles_h) * JH, b);
-        if (L.d_tab) QMRI_HIP(ctx, hipFree(L.d_tab));
-        QMRI_HIP(ctx, hipMalloc((void**)&L.d_tab, tab.size() * sizeof(int4)));
+        QMRI_TRY(L.d_tab.ensure(ctx, tab.size() * sizeof(int4)));
         QMRI_HIP(ctx, hipMemcpyAsync(L.d_tab, tab.data(), tab.size() * sizeof(int4), hipMemcpyHostToDevice, ctx->stream));
         QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
         L.tab_B = B; L.tab_MT = MT;
     }
     ConvArgs A;
-    A.in = in.base1(); A.wp = reinterpret_cast<const float4*>(L.wp); A.out = out.base1();
+    A.in = in.base1(); A.wp = reinterpret_cast<const float4*>(L.wp.p); A.out = out.base1();
     A.add1 = add1 ? add1->base1() : nullptr; A.add2 = add2 ? add2->base1() : nullptr;
-    A.tab = reinterpret_cast<const int4*>(L.d_tab);
+    A.tab = reinterpret_cast<const int4*>(L.d_tab.p);
     A.Cout = L.Cout; A.W = W; A.H = H; A.OW = OW; A.OH = OH;
     A.in_hp = in.hp; A.in_plane = (int)in.plane(); A.in_bs = (long)in.Cal * in.plane();
     A.out_hp = out.hp; A.out_plane = (int)out.plane(); A.out_bs = (long)out.Cal * out.plane();
@@ -456,8 +455,8 @@ void conv_plan_layer(ConvLayer& L, ConvKind kind, int Cin, int Cout) {
     const int rows = (kind == CONV_UP) ? 4 * Cout : Cout;       // a tile's first step and its last
     L.n_ct = (rows + 31) / 32;
     L.MT = 1;
-    L.wp = nullptr; L.wp_floats = 0;
-    L.d_tab = nullptr; L.tab_B = 0; L.tab_MT = 0;
+    L.wp_floats = 0;
+    L.tab_B = 0; L.tab_MT = 0;
 }
 
 // Pack PyTorch-layout weights (Conv2d OIHW, ConvTranspose2d IOHW) into MFMA A-fragment order:
@@ -529,8 +528,8 @@ int conv_pack_weights_dev(qmri_ctx* ctx, ConvLayer& L, const float* d_w) {
     const int CC = kind_cc(L.kind), NTAP = TH * TH, G = CC / 32, nch = L.cin_pad / CC;
     const long nent = (long)L.n_ct * nch * 4 * NTAP * G * 64;
     L.wp_floats = (size_t)nent * 4;
-    QMRI_HIP(ctx, hipMalloc((void**)&L.wp, L.wp_floats * sizeof(float)));
-    k_pack_w32<<<dim3((unsigned)((nent + 255) / 256)), dim3(256), 0, ctx->stream>>>(d_w, (float4*)L.wp, (int)L.kind, L.Cin, L.Cout, CC, NTAP, nch, nent);
+    QMRI_TRY(L.wp.ensure(ctx, L.wp_floats));
+    k_pack_w32<<<dim3((unsigned)((nent + 255) / 256)), dim3(256), 0, ctx->stream>>>(d_w, (float4*)L.wp.p, (int)L.kind, L.Cin, L.Cout, CC, NTAP, nch, nent);
     QMRI_HIP(ctx, hipGetLastError());
     return QMRI_OK;
 }

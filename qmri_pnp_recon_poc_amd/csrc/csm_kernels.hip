@@ -353,11 +353,11 @@ int csm_maps_dev(qmri_ctx* ctx, int B, int ncoil, const double2* d_calib, const 
     const double2* d_I = d_calib;
     if (prm.kind == QMRI_CSM_KSPACE) {
         const int cN = prm.cN, cM = prm.cM;
-        QMRI_TRY(dev_alloc(ctx, &I.p, nimg * plane));
-        QMRI_TRY(dev_alloc(ctx, &pad.p, (size_t)o.maxB * plane));
-        QMRI_TRY(dev_alloc(ctx, &tmp.p, (size_t)o.maxB * plane));
-        QMRI_TRY(dev_alloc(ctx, &spec.p, (size_t)o.maxB * plane));
-        QMRI_TRY(dev_alloc(ctx, &taper.p, (size_t)cN + cM));
+        QMRI_TRY(I.ensure(ctx, nimg * plane));
+        QMRI_TRY(pad.ensure(ctx, (size_t)o.maxB * plane));
+        QMRI_TRY(tmp.ensure(ctx, (size_t)o.maxB * plane));
+        QMRI_TRY(spec.ensure(ctx, (size_t)o.maxB * plane));
+        QMRI_TRY(taper.ensure(ctx, (size_t)cN + cM));
         std::vector<double> w((size_t)cN + cM, 1.0);
         if (prm.window) {
             const double pi = 3.14159265358979323846;
@@ -378,12 +378,12 @@ int csm_maps_dev(qmri_ctx* ctx, int B, int ncoil, const double2* d_calib, const 
         }
         d_I = I;
     }
-    if (!d_lam) { QMRI_TRY(dev_alloc(ctx, &lam.p, (size_t)B * plane)); }
+    if (!d_lam) { QMRI_TRY(lam.ensure(ctx, (size_t)B * plane)); }
     double* lamw = d_lam ? d_lam : lam.p;
-    QMRI_TRY(dev_alloc(ctx, &tmax.p, (size_t)B * ntiles));
-    QMRI_TRY(dev_alloc(ctx, &tit.p, (size_t)B * ntiles));
-    QMRI_TRY(dev_alloc(ctx, &tbad.p, (size_t)B * ntiles));
-    QMRI_TRY(dev_alloc(ctx, &sc.p, (size_t)B));
+    QMRI_TRY(tmax.ensure(ctx, (size_t)B * ntiles));
+    QMRI_TRY(tit.ensure(ctx, (size_t)B * ntiles));
+    QMRI_TRY(tbad.ensure(ctx, (size_t)B * ntiles));
+    QMRI_TRY(sc.ensure(ctx, (size_t)B));
     CsmEig a{N, M, ncoil, prm.patch, csm_chunk_coils(ncoil, prm.patch), d_I, d_maps, lamw, tmax, tit, tbad};
     const int P = (2 * prm.patch + 1) * (2 * prm.patch + 1), S = CSM_T + 2 * prm.patch;
     const size_t ldsb = sizeof(double2) * ((size_t)CSM_PX * (ncoil + P) + (size_t)std::min(a.ch, ncoil) * S * S);
@@ -392,7 +392,7 @@ int csm_maps_dev(qmri_ctx* ctx, int B, int ncoil, const double2* d_calib, const 
     QMRI_HIP(ctx, hipGetLastError());
     const bool coil = prm.phase_ref == QMRI_CSM_PHASE_COIL;
     if (coil) {
-        QMRI_TRY(dev_alloc(ctx, &en.p, nimg));
+        QMRI_TRY(en.ensure(ctx, nimg));
         k_csm_energy<<<dim3(ncoil, B), dim3(NT), 0, ctx->stream>>>(d_I, plane, en);
         QMRI_HIP(ctx, hipGetLastError());
     }

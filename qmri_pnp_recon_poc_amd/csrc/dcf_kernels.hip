@@ -190,10 +190,10 @@ int dcf_weights_dev(qmri_ctx* ctx, int niter, double tol, double kappa, double* 
     DevBuf<double> w, pd;
     DevBuf<int32_t> ints;
     DevBuf<DcfRes> res;
-    QMRI_TRY(dev_alloc(ctx, &w.p, (size_t)nu.m));
-    QMRI_TRY(dev_alloc(ctx, &pd.p, (size_t)2 * d.nblk));
-    QMRI_TRY(dev_alloc(ctx, &ints.p, (size_t)d.nblk + niter + 2));
-    QMRI_TRY(dev_alloc(ctx, &res.p, 1));
+    QMRI_TRY(w.ensure(ctx, (size_t)nu.m));
+    QMRI_TRY(pd.ensure(ctx, (size_t)2 * d.nblk));
+    QMRI_TRY(ints.ensure(ctx, (size_t)d.nblk + niter + 2));
+    QMRI_TRY(res.ensure(ctx, 1));
     d.w = w; d.pd[0] = pd; d.pd[1] = pd.p + d.nblk; d.pc = ints; d.stop = ints.p + d.nblk; d.res = res;
     QMRI_HIP(ctx, hipMemsetAsync(ints.p, 0, ((size_t)d.nblk + niter + 2) * sizeof(int32_t), ctx->stream));
     QMRI_HIP(ctx, hipMemsetAsync(res.p, 0, sizeof(DcfRes), ctx->stream));

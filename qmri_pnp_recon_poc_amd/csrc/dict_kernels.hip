@@ -433,15 +433,6 @@ __global__ __launch_bounds__(256) void k_dict_xfit(const float4* __restrict__ wi
 
 }  // namespace
 
-// grow-only device scratch of the dictionary match (the stream is drained before a buffer in use is replaced)
-int dict_scratch(qmri_ctx* ctx, void** buf, size_t* cap, size_t need_bytes) {
-    if (*cap >= need_bytes) return QMRI_OK;
-    if (*buf) { QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream)); QMRI_HIP(ctx, hipFree(*buf)); *buf = nullptr; *cap = 0; }
-    QMRI_HIP(ctx, hipMalloc(buf, need_bytes));
-    *cap = need_bytes;
-    return QMRI_OK;
-}
-
 int dict_launch_merge(qmri_ctx* ctx, const float4* part, int P, int Npix, float* d_qmap, float* d_pd, float* d_mt, int32_t* d_dm, float4* win) {
     const DictHost& D = ctx->dict;
     k_dict_merge<<<dim3((Npix + 255) / 256), dim3(256), 0, ctx->stream>>>(part, P, Npix, Npix, D.K, D.d_normD, D.d_lut, D.Q, d_qmap, d_pd, d_mt, d_dm, win, nullptr);
@@ -456,7 +447,7 @@ int dict_launch(qmri_ctx* ctx, const double2* d_X, int Npix, float* d_qmap, floa
     DictHost& D = ctx->dict;
     float4* win = nullptr;
     if (d_xfit) {
-        QMRI_TRY(dict_scratch(ctx, (void**)&D.d_win, &D.win_cap, (size_t)Npix * sizeof(float4)));
+        QMRI_TRY(D.d_win.ensure(ctx, (size_t)Npix));
         win = D.d_win;
     }
     if (D.wide) QMRI_TRY(dictw_launch(ctx, d_X, Npix, d_qmap, d_pd, d_mt, d_dm, win));
@@ -499,13 +490,13 @@ static int dict_launch_narrow(qmri_ctx* ctx, const double2* d_X, int Npix, float
     }
     float4* part = nullptr;
     if (P > 1) {
-        QMRI_TRY(dict_scratch(ctx, (void**)&D.d_part, &D.part_cap, (size_t)P * Npix * sizeof(float4)));
+        QMRI_TRY(D.d_part.ensure(ctx, (size_t)P * Npix));
         part = D.d_part;
     }
     dim3 grid(ptiles, P), blk(NT);
     const float mc = D.marg_coef * D.margin_scale;
     if (filt) {
-        QMRI_TRY(dict_scratch(ctx, (void**)&D.d_gmax, &D.gmax_cap, (size_t)Npix * sizeof(int)));
+        QMRI_TRY(D.d_gmax.ensure(ctx, (size_t)Npix));
         QMRI_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)D.d_gmax, (int)0xBF800000u /* -1.0f */, (size_t)Npix, ctx->stream));
     }
     // seed launch: ~12 steps of the whole dictionary per pixel, spread over as many workgroups as give one round of the device
@@ -567,13 +558,13 @@ int dict_launch_grouped(qmri_ctx* ctx, const double2* d_X, int Npix, const DictG
     }
     float4* part = nullptr;
     if (P > 1) {
-        QMRI_TRY(dict_scratch(ctx, (void**)&D.d_part, &D.part_cap, (size_t)P * gv.slot_cap * sizeof(float4)));
+        QMRI_TRY(D.d_part.ensure(ctx, (size_t)P * gv.slot_cap));
         part = D.d_part;
     }
     dim3 grid(nslot_tiles, P), blk(NT);
     const float mc = D.marg_coef * D.margin_scale;
     if (filt) {
-        QMRI_TRY(dict_scratch(ctx, (void**)&D.d_gmax, &D.gmax_cap, (size_t)gv.slot_cap * sizeof(int)));
+        QMRI_TRY(D.d_gmax.ensure(ctx, (size_t)gv.slot_cap));
         QMRI_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)D.d_gmax, (int)0xBF800000u /* -1.0f */, (size_t)gv.slot_cap, ctx->stream));
     }
     const int nsteps_max = (D.gtiles_max + FSTEP - 1) / FSTEP;

@@ -134,10 +134,8 @@ extern "C" int qmri_dict_group_assign(int G, const double* group_val, int n, con
 
 void dictg_free(qmri_ctx* ctx) {
     DictHost& d = ctx->dict;
-    void* ptrs[] = { d.d_gpack, d.d_gpack16, d.d_gptr, d.d_gtile, d.d_gval, d.d_gwork };
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    d.d_gpack = nullptr; d.d_gpack16 = nullptr; d.d_gptr = nullptr; d.d_gtile = nullptr; d.d_gval = nullptr; d.d_gwork = nullptr;
-    d.gwork_cap = 0; d.G = 0; d.gtiles_max = 0; d.gtile_h.clear();
+    d.d_gpack.reset(); d.d_gpack16.reset(); d.d_gptr.reset(); d.d_gtile.reset(); d.d_gval.reset(); d.d_gwork.reset();
+    d.G = 0; d.gtiles_max = 0; d.gtile_h.clear();
 }
 
 // the arguments are checked (api_dict.cpp); the dictionary is set and narrow.  The new groups are built beside the current ones and take their
@@ -155,13 +153,13 @@ int dictg_set_groups(qmri_ctx* ctx, int G, const int32_t* group_ptr, const doubl
     const int gtiles = gtile[G], npl = ((d.s + 1) / 2 <= 4) ? 4 : 8;
     DevBuf<int> a0, a1, gptr, gtl;
     DevBuf<float> gpack; DevBuf<uint4> gpack16; DevBuf<double> gval;
-    QMRI_TRY(dev_alloc(ctx, &a0.p, (size_t)gtiles));
-    QMRI_TRY(dev_alloc(ctx, &a1.p, (size_t)gtiles));
-    QMRI_TRY(dev_alloc(ctx, &gpack.p, (size_t)gtiles * 64 * npl));
-    if (d.d_pack16) QMRI_TRY(dev_alloc(ctx, &gpack16.p, (size_t)gtiles * 128));
-    QMRI_TRY(dev_alloc(ctx, &gptr.p, (size_t)G + 1));
-    QMRI_TRY(dev_alloc(ctx, &gtl.p, (size_t)G + 1));
-    QMRI_TRY(dev_alloc(ctx, &gval.p, (size_t)G));
+    QMRI_TRY(a0.ensure(ctx, (size_t)gtiles));
+    QMRI_TRY(a1.ensure(ctx, (size_t)gtiles));
+    QMRI_TRY(gpack.ensure(ctx, (size_t)gtiles * 64 * npl));
+    if (d.d_pack16) QMRI_TRY(gpack16.ensure(ctx, (size_t)gtiles * 128));
+    QMRI_TRY(gptr.ensure(ctx, (size_t)G + 1));
+    QMRI_TRY(gtl.ensure(ctx, (size_t)G + 1));
+    QMRI_TRY(gval.ensure(ctx, (size_t)G));
     QMRI_HIP(ctx, hipMemcpy(a0.p, atom0.data(), (size_t)gtiles * sizeof(int), hipMemcpyHostToDevice));
     QMRI_HIP(ctx, hipMemcpy(a1.p, atom1.data(), (size_t)gtiles * sizeof(int), hipMemcpyHostToDevice));
     QMRI_HIP(ctx, hipMemcpy(gptr.p, group_ptr, ((size_t)G + 1) * sizeof(int), hipMemcpyHostToDevice));
@@ -172,8 +170,8 @@ int dictg_set_groups(qmri_ctx* ctx, int G, const int32_t* group_ptr, const doubl
     QMRI_HIP(ctx, hipGetLastError());
     QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));            // (also drains a grouped match still reading the old groups)
     dictg_free(ctx);
-    d.d_gpack = gpack.p; gpack.p = nullptr; d.d_gpack16 = gpack16.p; gpack16.p = nullptr;
-    d.d_gptr = gptr.p; gptr.p = nullptr; d.d_gtile = gtl.p; gtl.p = nullptr; d.d_gval = gval.p; gval.p = nullptr;
+    d.d_gpack = std::move(gpack); d.d_gpack16 = std::move(gpack16);
+    d.d_gptr = std::move(gptr); d.d_gtile = std::move(gtl); d.d_gval = std::move(gval);
     d.G = G; d.gtiles_max = tmax; d.gtile_h = gtile;
     return QMRI_OK;
 }
@@ -195,10 +193,10 @@ int dictg_launch(qmri_ctx* ctx, const double2* d_X, int Npix, const double* d_se
     DictHost& D = ctx->dict;
     const int padw = dict_group_pixel_width(ctx);
     const DictgWork w = dictg_work(Npix, D.G, padw);
-    QMRI_TRY(dict_scratch(ctx, (void**)&D.d_gwork, &D.gwork_cap, w.total * sizeof(int)));
+    QMRI_TRY(D.d_gwork.ensure(ctx, w.total));
     float4* win = nullptr;
     if (d_xfit) {
-        QMRI_TRY(dict_scratch(ctx, (void**)&D.d_win, &D.win_cap, (size_t)Npix * sizeof(float4)));
+        QMRI_TRY(D.d_win.ensure(ctx, (size_t)Npix));
         win = D.d_win;
     }
     int* base = D.d_gwork;

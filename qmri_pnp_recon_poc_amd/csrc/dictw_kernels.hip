@@ -185,19 +185,15 @@ int dictw_pack_dictionary(qmri_ctx* ctx, const float* D_host, int K, int s) {
     const int spad = (s + 15) / 16 * 16;
     d.G8 = spad / 8;
     d.ntiles = (K + 127) / 128 * 4;                                      // 32-atom tiles
-    float* raw = nullptr;
+    DevBuf<float> raw;
     const size_t nraw = (size_t)K * s, npack = (size_t)d.ntiles * d.G8 * 64 * 4;
-    QMRI_HIP(ctx, hipMalloc((void**)&raw, nraw * sizeof(float)));
-    int st = QMRI_OK;
-    do {
-        if (hipMalloc((void**)&d.d_pack, npack * sizeof(float)) != hipSuccess) { qmri_set_error(ctx, "hipMalloc of the packed dictionary failed"); st = QMRI_ERR_NOMEM; break; }
-        if (hipMemcpyAsync(raw, D_host, nraw * sizeof(float), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) { qmri_set_error(ctx, "H2D copy of D failed"); st = QMRI_ERR_HIP; break; }
-        const size_t n4 = npack / 4;
-        k_dictw_pack_d<<<dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, ctx->stream>>>(raw, K, s, d.G8, d.ntiles, (float4*)d.d_pack);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) { qmri_set_error(ctx, "packing the dictionary failed"); st = QMRI_ERR_HIP; break; }
-    } while (0);
-    (void)hipFree(raw);
-    return st;
+    QMRI_TRY(raw.ensure(ctx, nraw));
+    QMRI_TRY(d.pool.alloc(ctx, &d.d_pack, npack));
+    if (hipMemcpyAsync(raw, D_host, nraw * sizeof(float), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) { qmri_set_error(ctx, "H2D copy of D failed"); return QMRI_ERR_HIP; }
+    const size_t n4 = npack / 4;
+    k_dictw_pack_d<<<dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, ctx->stream>>>(raw, K, s, d.G8, d.ntiles, (float4*)d.d_pack);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) { qmri_set_error(ctx, "packing the dictionary failed"); return QMRI_ERR_HIP; }
+    return QMRI_OK;
 }
 
 int dictw_launch(qmri_ctx* ctx, const double2* d_X, int Npix, float* d_qmap, float* d_pd, float* d_mt, int32_t* d_dm, float4* win) {
@@ -216,8 +212,8 @@ int dictw_launch(qmri_ctx* ctx, const double2* d_X, int Npix, float* d_qmap, flo
     const int tper = (AT + P - 1) / P;
     P = (AT + tper - 1) / tper;                                          // no empty part
     const size_t nxp = (size_t)PT * 4 * D.G8 * 2 * 64;                   // float4
-    QMRI_TRY(dict_scratch(ctx, (void**)&D.d_xp, &D.xp_cap, nxp * sizeof(float4)));
-    QMRI_TRY(dict_scratch(ctx, (void**)&D.d_part, &D.part_cap, (size_t)P * Npix * sizeof(float4)));
+    QMRI_TRY(D.d_xp.ensure(ctx, nxp));
+    QMRI_TRY(D.d_part.ensure(ctx, (size_t)P * Npix));
     const size_t nthr = (size_t)PT * 4 * D.G8 * 64;
     k_dictw_pack_x<<<dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, ctx->stream>>>(d_X, Npix, D.s, D.G8, PT * 4, (float4*)D.d_xp);
     QMRI_HIP(ctx, hipGetLastError());

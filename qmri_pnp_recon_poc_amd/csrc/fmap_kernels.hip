@@ -264,16 +264,16 @@ int fmap_estimate_dev(qmri_ctx* ctx, const FmapPlan& pl, const double2* d_Y, con
     const size_t plane = (size_t)npix;
     DevBuf<double> phi, w, fa, fb, pmax, W, part, res;
     DevBuf<int> pbad, badsl;
-    QMRI_TRY(dev_alloc(ctx, &phi.p, (size_t)S * P * plane));
-    QMRI_TRY(dev_alloc(ctx, &w.p, (size_t)S * P * plane));
-    QMRI_TRY(dev_alloc(ctx, &fa.p, (size_t)S * plane));
-    QMRI_TRY(dev_alloc(ctx, &fb.p, (size_t)S * plane));
-    QMRI_TRY(dev_alloc(ctx, &pmax.p, (size_t)S * nblk));
-    QMRI_TRY(dev_alloc(ctx, &pbad.p, (size_t)S * nblk));
-    QMRI_TRY(dev_alloc(ctx, &W.p, (size_t)S));
-    QMRI_TRY(dev_alloc(ctx, &badsl.p, (size_t)S));
-    QMRI_TRY(dev_alloc(ctx, &part.p, (size_t)S * nblk * 3));
-    QMRI_TRY(dev_alloc(ctx, &res.p, (size_t)S * 6));
+    QMRI_TRY(phi.ensure(ctx, (size_t)S * P * plane));
+    QMRI_TRY(w.ensure(ctx, (size_t)S * P * plane));
+    QMRI_TRY(fa.ensure(ctx, (size_t)S * plane));
+    QMRI_TRY(fb.ensure(ctx, (size_t)S * plane));
+    QMRI_TRY(pmax.ensure(ctx, (size_t)S * nblk));
+    QMRI_TRY(pbad.ensure(ctx, (size_t)S * nblk));
+    QMRI_TRY(W.ensure(ctx, (size_t)S));
+    QMRI_TRY(badsl.ensure(ctx, (size_t)S));
+    QMRI_TRY(part.ensure(ctx, (size_t)S * nblk * 3));
+    QMRI_TRY(res.ensure(ctx, (size_t)S * 6));
 
     FmapPairs q{};
     q.L = pl.L; q.C = pl.C; q.P = P; q.sign = pl.sign; q.d01 = pl.d[0];

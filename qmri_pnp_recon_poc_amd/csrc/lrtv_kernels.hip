@@ -215,6 +215,7 @@ __global__ __launch_bounds__(256) void k_lrtv_momentum(double2* __restrict__ x, 
 }
 
 struct TvWork {                                      // device buffers of one prox_tv call on an R x C image
+    DevPool pool;
     double *r[2] = {nullptr, nullptr}, *s[2] = {nullptr, nullptr}, *pold = nullptr, *qold = nullptr, *partials = nullptr;
     TvState* st = nullptr;
     size_t n = 0; unsigned nblk = 0;
@@ -224,15 +225,9 @@ struct TvWork {                                      // device buffers of one pr
 int tv_alloc(qmri_ctx* ctx, TvWork& w, int R, int C) {
     w.n = (size_t)R * C;
     w.nblk = (unsigned)(((R + TVR - 1) / TVR) * ((C + TVC - 1) / TVC));
-    for (double** p : {&w.r[0], &w.r[1], &w.s[0], &w.s[1], &w.pold, &w.qold}) QMRI_HIP(ctx, hipMalloc((void**)p, w.n * sizeof(double)));
-    QMRI_HIP(ctx, hipMalloc((void**)&w.partials, (size_t)4 * std::max(w.nblk, (unsigned)RED_BLOCKS) * sizeof(double)));   // two sets of (fid, tv) per block
-    QMRI_HIP(ctx, hipMalloc((void**)&w.st, sizeof(TvState)));
-    return QMRI_OK;
-}
-void tv_free(TvWork& w) {
-    for (double* p : {w.r[0], w.r[1], w.s[0], w.s[1], w.pold, w.qold, w.partials}) if (p) (void)hipFree(p);
-    if (w.st) (void)hipFree(w.st);
-    w = TvWork();
+    for (double** p : {&w.r[0], &w.r[1], &w.s[0], &w.s[1], &w.pold, &w.qold}) QMRI_TRY(w.pool.alloc(ctx, p, w.n));
+    QMRI_TRY(w.pool.alloc(ctx, &w.partials, (size_t)4 * std::max(w.nblk, (unsigned)RED_BLOCKS)));   // two sets of (fid, tv) per block
+    return w.pool.alloc(ctx, &w.st, 1);
 }
 
 // sol = prox_{gamma TV}(b) on device buffers; returns the iteration count and the final objective
@@ -291,16 +286,15 @@ extern "C" int qmri_norm_tv(qmri_ctx* ctx, const double* I, int R, int C, double
     QMRI_HIP(ctx, hipSetDevice(ctx->device));
     QMRI_CHECK_ARG(ctx, I && out && R >= 2 && C >= 2, "qmri_norm_tv: I / out NULL or image smaller than 2 x 2");
     const size_t n = (size_t)R * C;
-    double *d_I = nullptr, *d_p = nullptr;
-    QMRI_HIP(ctx, hipMalloc((void**)&d_I, n * sizeof(double)));
-    QMRI_HIP(ctx, hipMalloc((void**)&d_p, RED_BLOCKS * sizeof(double)));
+    DevBuf<double> d_I, d_p;
+    QMRI_TRY(d_I.ensure(ctx, n));
+    QMRI_TRY(d_p.ensure(ctx, RED_BLOCKS));
     std::vector<double> hp(RED_BLOCKS);
-    hipError_t e = hipMemcpyAsync(d_I, I, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) { k_lrtv_normtv<<<dim3(RED_BLOCKS), dim3(256), 0, ctx->stream>>>(d_I, R, C, d_p); e = hipGetLastError(); }
-    if (e == hipSuccess) e = hipMemcpyAsync(hp.data(), d_p, RED_BLOCKS * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_I); (void)hipFree(d_p);
-    QMRI_HIP(ctx, e);
+    QMRI_HIP(ctx, hipMemcpyAsync(d_I, I, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    k_lrtv_normtv<<<dim3(RED_BLOCKS), dim3(256), 0, ctx->stream>>>(d_I, R, C, d_p);
+    QMRI_HIP(ctx, hipGetLastError());
+    QMRI_HIP(ctx, hipMemcpyAsync(hp.data(), d_p, RED_BLOCKS * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     *out = host_sum(hp, RED_BLOCKS);
     return QMRI_OK;
 }
@@ -313,19 +307,18 @@ extern "C" int qmri_prox_tv(qmri_ctx* ctx, const double* b, int R, int C, double
     QMRI_CHECK_ARG(ctx, gamma >= 0.0 && tol > 0.0 && maxit >= 1, "qmri_prox_tv: gamma must be >= 0 (test_gamma), tol > 0, maxit >= 1");
     const size_t n = (size_t)R * C;
     TvWork w;
-    double *d_b = nullptr, *d_sol = nullptr;
-    int st = tv_alloc(ctx, w, R, C);
+    DevBuf<double> d_b, d_sol;
     int it = 0; double obj = 0.0;
-    if (st == QMRI_OK && (hipMalloc((void**)&d_b, n * sizeof(double)) != hipSuccess || hipMalloc((void**)&d_sol, n * sizeof(double)) != hipSuccess)) {
-        qmri_set_error(ctx, "qmri_prox_tv: hipMalloc failed"); st = QMRI_ERR_NOMEM;
-    }
-    if (st == QMRI_OK && hipMemcpyAsync(d_b, b, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) { qmri_set_error(ctx, "qmri_prox_tv: H2D copy failed"); st = QMRI_ERR_HIP; }
-    if (st == QMRI_OK) st = tv_prox_dev(ctx, w, d_b, R, C, gamma, tol, maxit, d_sol, &it, &obj);
-    if (st == QMRI_OK && (hipMemcpyAsync(sol, d_sol, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-                          hipStreamSynchronize(ctx->stream) != hipSuccess)) { qmri_set_error(ctx, "qmri_prox_tv: D2H copy failed"); st = QMRI_ERR_HIP; }
-    tv_free(w);
-    if (d_b) (void)hipFree(d_b);
-    if (d_sol) (void)hipFree(d_sol);
+    const int st = [&]() -> int {
+        QMRI_TRY(tv_alloc(ctx, w, R, C));
+        QMRI_TRY(d_b.ensure(ctx, n));
+        QMRI_TRY(d_sol.ensure(ctx, n));
+        if (hipMemcpyAsync(d_b, b, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) { qmri_set_error(ctx, "qmri_prox_tv: H2D copy failed"); return QMRI_ERR_HIP; }
+        QMRI_TRY(tv_prox_dev(ctx, w, d_b, R, C, gamma, tol, maxit, d_sol, &it, &obj));
+        if (hipMemcpyAsync(sol, d_sol, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+            hipStreamSynchronize(ctx->stream) != hipSuccess) { qmri_set_error(ctx, "qmri_prox_tv: D2H copy failed"); return QMRI_ERR_HIP; }
+        return QMRI_OK;
+    }();
     if (iters_out) *iters_out = it;
     if (obj_out) *obj_out = obj;
     return st;
@@ -347,14 +340,15 @@ extern "C" int qmri_lrtv(qmri_ctx* ctx, const void* y, const qmri_lrtv_params* p
     TvWork w;
     double2 *d_x = nullptr, *d_x2 = nullptr, *d_x2p = nullptr, *d_g = nullptr, *d_y = nullptr, *d_fx = nullptr;
     double *d_b = nullptr, *d_sol = nullptr;
-    std::vector<void*> owned;
-    auto alloc = [&](void** p, size_t bytes) { if (hipMalloc(p, bytes) != hipSuccess) return false; owned.push_back(*p); return true; };
-    int st = tv_alloc(ctx, w, R, C);
-    if (st == QMRI_OK && !(alloc((void**)&d_x, n * sizeof(double2)) && alloc((void**)&d_x2, n * sizeof(double2)) && alloc((void**)&d_x2p, n * sizeof(double2)) &&
-                           alloc((void**)&d_g, n * sizeof(double2)) && alloc((void**)&d_y, m * sizeof(double2)) && alloc((void**)&d_fx, m * sizeof(double2)) &&
-                           alloc((void**)&d_b, 2 * n * sizeof(double)) && alloc((void**)&d_sol, 2 * n * sizeof(double)))) {
-        qmri_set_error(ctx, "qmri_lrtv: hipMalloc failed"); st = QMRI_ERR_NOMEM;
-    }
+    DevPool owned;
+    const auto setup = [&]() -> int {
+        QMRI_TRY(tv_alloc(ctx, w, R, C));
+        for (double2** p : {&d_x, &d_x2, &d_x2p, &d_g}) QMRI_TRY(owned.alloc(ctx, p, n));
+        for (double2** p : {&d_y, &d_fx}) QMRI_TRY(owned.alloc(ctx, p, m));
+        for (double** p : {&d_b, &d_sol}) QMRI_TRY(owned.alloc(ctx, p, 2 * n));
+        return QMRI_OK;
+    };
+    int st = setup();
     std::vector<double> hp(2 * RED_BLOCKS);
     qmri_lrtv_info inf{};
     auto body = [&]() -> int {
@@ -426,8 +420,6 @@ extern "C" int qmri_lrtv(qmri_ctx* ctx, const void* y, const qmri_lrtv_params* p
     };
     if (st == QMRI_OK) st = body();
     if (st != QMRI_OK) (void)hipStreamSynchronize(ctx->stream);
-    tv_free(w);
-    for (void* p : owned) (void)hipFree(p);
     if (info) *info = inf;
     return st;
 }

@@ -311,13 +311,6 @@ int mc_scalar(qmri_ctx* ctx, int stage, int B, const ScalarArgs& a) {
 }
 }  // namespace
 
-void mc_free_work(McWork& w) {
-    void* ptrs[] = {w.ut, w.ub, w.v, w.d, w.t, w.scr, w.part, w.st, w.sy, w.sm, w.sx, w.sz};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    if (w.hst) (void)hipHostFree(w.hst);
-    w = McWork();
-}
-
 int mc_launch_coil_mul(qmri_ctx* ctx, int ncoil, int g0, int cnt, const double2* x, const double2* maps, const LsqrState* st, double2* out) {
     const OpHost& o = ctx->op;
     const size_t n = (size_t)o.N * o.M * o.s, plane = (size_t)o.N * o.M;
@@ -334,60 +327,36 @@ int mc_launch_coil_sum(qmri_ctx* ctx, int ncoil, int g0, int cnt, const double2*
     return QMRI_OK;
 }
 
-// work buffers of a B-slice, ncoil-coil solve: allocated on first use, grown only when B or B x ncoil grows (qmri_free_operator frees them)
+// work buffers of a B-slice, ncoil-coil solve: allocated on first use, each grown only when its own need grows (they go with the operator)
 int mc_ensure_work(qmri_ctx* ctx, int B, int ncoil) {
     OpHost& o = ctx->op;
     McWork& w = o.mc;
-    const size_t img = (size_t)B * ncoil;
-    if (w.ut && (size_t)B <= w.cap_sl && img <= w.cap_img) return QMRI_OK;
-    QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const size_t cap_sl = std::max((size_t)B, w.cap_sl), cap_img = std::max(img, w.cap_img);
-    auto drop = [&]() {                                        // the solve's buffers only (the staging grows on its own: mc_ensure_staging)
-        void* ptrs[] = {w.ut, w.ub, w.v, w.d, w.t, w.scr, w.part, w.st};
-        for (void* p : ptrs) if (p) (void)hipFree(p);
-        if (w.hst) (void)hipHostFree(w.hst);
-        w.ut = w.ub = w.v = w.d = w.t = w.scr = nullptr; w.part = nullptr; w.st = w.hst = nullptr;
-        w.cap_sl = w.cap_img = 0;
-    };
-    drop();
-    const size_t n = (size_t)o.N * o.M * o.s;
-    const size_t parts = 2 * cap_img * PC + 5 * cap_sl * PS;
-    if (hipMalloc((void**)&w.ut, cap_img * o.m * sizeof(double2)) != hipSuccess || hipMalloc((void**)&w.ub, cap_sl * n * sizeof(double2)) != hipSuccess ||
-        hipMalloc((void**)&w.v, cap_sl * n * sizeof(double2)) != hipSuccess || hipMalloc((void**)&w.d, cap_sl * n * sizeof(double2)) != hipSuccess ||
-        hipMalloc((void**)&w.t, cap_sl * n * sizeof(double2)) != hipSuccess || hipMalloc((void**)&w.scr, (size_t)o.maxB * n * sizeof(double2)) != hipSuccess ||
-        hipMalloc((void**)&w.part, parts * sizeof(double)) != hipSuccess || hipMalloc((void**)&w.st, cap_sl * sizeof(LsqrState)) != hipSuccess ||
-        hipHostMalloc((void**)&w.hst, cap_sl * sizeof(LsqrState), hipHostMallocDefault) != hipSuccess) {
-        drop();
-        qmri_set_error(ctx, "out of device memory for the multi-coil LSQR of %d slices x %d coils", B, ncoil);
-        return QMRI_ERR_NOMEM;
-    }
-    w.cap_sl = cap_sl; w.cap_img = cap_img;
-    return QMRI_OK;
+    const size_t sl = (size_t)B, img = sl * ncoil, n = (size_t)o.N * o.M * o.s;
+    const int st = [&]() -> int {
+        QMRI_TRY(w.ut.ensure(ctx, img * o.m));
+        for (DevArr<double2>* a : {&w.ub, &w.v, &w.d, &w.t}) QMRI_TRY(a->ensure(ctx, sl * n));
+        QMRI_TRY(w.scr.ensure(ctx, (size_t)o.maxB * n));
+        QMRI_TRY(w.part.ensure(ctx, 2 * img * PC + 5 * sl * PS));
+        QMRI_TRY(w.st.ensure(ctx, sl));
+        return w.hst.ensure(ctx, sl);
+    }();
+    if (st == QMRI_ERR_NOMEM) qmri_set_error(ctx, "out of device memory for the multi-coil LSQR of %d slices x %d coils", B, ncoil);
+    return st;
 }
 
-// staging of host-array calls: maps, y, x, z (or x0) for B slices of ncoil coils, grown only when B or B x ncoil grows
+// staging of host-array calls: maps, y, x, z (or x0) for B slices of ncoil coils, each grown only when its own need grows
 int mc_ensure_staging(qmri_ctx* ctx, int B, int ncoil) {
     OpHost& o = ctx->op;
     McWork& w = o.mc;
-    const size_t img = (size_t)B * ncoil;
-    if (w.sy && (size_t)B <= w.stage_sl && img <= w.stage_img) return QMRI_OK;
-    QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const size_t sl = std::max((size_t)B, w.stage_sl), im = std::max(img, w.stage_img);
-    void* old[] = {w.sy, w.sm, w.sx, w.sz};
-    for (void* p : old) if (p) (void)hipFree(p);
-    w.sy = w.sm = w.sx = w.sz = nullptr;
-    w.stage_sl = w.stage_img = 0;
-    const size_t n = (size_t)o.N * o.M * o.s, plane = (size_t)o.N * o.M;
-    if (hipMalloc((void**)&w.sy, im * o.m * sizeof(double2)) != hipSuccess || hipMalloc((void**)&w.sm, im * plane * sizeof(double2)) != hipSuccess ||
-        hipMalloc((void**)&w.sx, sl * n * sizeof(double2)) != hipSuccess || hipMalloc((void**)&w.sz, sl * n * sizeof(double2)) != hipSuccess) {
-        void* got[] = {w.sy, w.sm, w.sx, w.sz};
-        for (void* p : got) if (p) (void)hipFree(p);
-        w.sy = w.sm = w.sx = w.sz = nullptr;
-        qmri_set_error(ctx, "out of device memory for the staging of %d slices x %d coils", B, ncoil);
-        return QMRI_ERR_NOMEM;
-    }
-    w.stage_sl = sl; w.stage_img = im;
-    return QMRI_OK;
+    const size_t sl = (size_t)B, img = sl * ncoil, n = (size_t)o.N * o.M * o.s, plane = (size_t)o.N * o.M;
+    const int st = [&]() -> int {
+        QMRI_TRY(w.sy.ensure(ctx, img * o.m));
+        QMRI_TRY(w.sm.ensure(ctx, img * plane));
+        QMRI_TRY(w.sx.ensure(ctx, sl * n));
+        return w.sz.ensure(ctx, sl * n);
+    }();
+    if (st == QMRI_ERR_NOMEM) qmri_set_error(ctx, "out of device memory for the staging of %d slices x %d coils", B, ncoil);
+    return st;
 }
 
 // x = A_mc' y for B slices (the ADMM loop's start, PnP_ADMM.m:84)

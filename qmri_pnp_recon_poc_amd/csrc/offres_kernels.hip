@@ -236,19 +236,15 @@ int offres_coefficients_dev(qmri_ctx* ctx, int L, int nbins, bool exact, const d
     const OpHost& o = ctx->op;
     if (o.kind != OP_NUFFT || L < 1 || L > OF_LMAX || nbins < 1) { qmri_set_error(ctx, "offres_coefficients_dev: bad plan (internal)"); return QMRI_ERR_STATE; }
     const int nblk = (o.m + OF_SB - 1) / OF_SB;
-    double* d_part = nullptr;
-    QMRI_TRY(dev_alloc(ctx, &d_part, 2 * (size_t)nblk + 2));
+    DevBuf<double> d_part;
+    QMRI_TRY(d_part.ensure(ctx, 2 * (size_t)nblk + 2));
     k_offres_coef<<<dim3(nblk), dim3(NT), 0, ctx->stream>>>(L, nbins, o.m, exact ? 1 : 0, d_hist, d_G, d_chol, d_ts, o.nu.d_perm, f0, d_bl, d_part, d_part + nblk);
-    hipError_t err = hipGetLastError();
-    if (err == hipSuccess) {
-        k_offres_fit<<<dim3(1), dim3(NT), 0, ctx->stream>>>(nblk, d_part, d_part + nblk, d_part + 2 * (size_t)nblk);
-        err = hipGetLastError();
-    }
+    QMRI_HIP(ctx, hipGetLastError());
+    k_offres_fit<<<dim3(1), dim3(NT), 0, ctx->stream>>>(nblk, d_part, d_part + nblk, d_part + 2 * (size_t)nblk);
+    QMRI_HIP(ctx, hipGetLastError());
     double out[2] = {0.0, 0.0};
-    if (err == hipSuccess) err = hipMemcpyAsync(out, d_part + 2 * (size_t)nblk, sizeof(out), hipMemcpyDeviceToHost, ctx->stream);
-    if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_part);
-    QMRI_HIP(ctx, err);
+    QMRI_HIP(ctx, hipMemcpyAsync(out, d_part + 2 * (size_t)nblk, sizeof(out), hipMemcpyDeviceToHost, ctx->stream));
+    QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     fit->fit_max = std::sqrt(out[0]);
     fit->fit_rms = std::sqrt(out[1] / (double)o.m);
     return QMRI_OK;
@@ -259,19 +255,15 @@ int offres_ncoefficients_dev(qmri_ctx* ctx, int L, int nb, const double2* d_dh, 
     const OpHost& o = ctx->op;
     if (o.kind != OP_NUFFT || L < 2 || L > ON_LMAX || nb < 1 || nb > ON_BMAX) { qmri_set_error(ctx, "offres_ncoefficients_dev: bad plan (internal)"); return QMRI_ERR_STATE; }
     const int nblk = (o.m + ON_SB - 1) / ON_SB;
-    double* d_part = nullptr;
-    QMRI_TRY(dev_alloc(ctx, &d_part, 2 * (size_t)nblk + 2));
+    DevBuf<double> d_part;
+    QMRI_TRY(d_part.ensure(ctx, 2 * (size_t)nblk + 2));
     k_offres_ncoef<<<dim3(nblk), dim3(NT), 0, ctx->stream>>>(L, nb, o.m, d_dh, d_G, d_Qw, d_U, d_ts, o.nu.d_perm, d_c, d_part, d_part + nblk);
-    hipError_t err = hipGetLastError();
-    if (err == hipSuccess) {
-        k_offres_fit<<<dim3(1), dim3(NT), 0, ctx->stream>>>(nblk, d_part, d_part + nblk, d_part + 2 * (size_t)nblk);
-        err = hipGetLastError();
-    }
+    QMRI_HIP(ctx, hipGetLastError());
+    k_offres_fit<<<dim3(1), dim3(NT), 0, ctx->stream>>>(nblk, d_part, d_part + nblk, d_part + 2 * (size_t)nblk);
+    QMRI_HIP(ctx, hipGetLastError());
     double out[2] = {0.0, 0.0};
-    if (err == hipSuccess) err = hipMemcpyAsync(out, d_part + 2 * (size_t)nblk, sizeof(out), hipMemcpyDeviceToHost, ctx->stream);
-    if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_part);
-    QMRI_HIP(ctx, err);
+    QMRI_HIP(ctx, hipMemcpyAsync(out, d_part + 2 * (size_t)nblk, sizeof(out), hipMemcpyDeviceToHost, ctx->stream));
+    QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     fit->fit_max = std::sqrt(out[0]);
     fit->fit_rms = std::sqrt(out[1] / (double)o.m);
     return QMRI_OK;

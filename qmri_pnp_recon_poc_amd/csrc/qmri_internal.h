@@ -40,43 +40,9 @@ void qmri_set_error(qmri_ctx* ctx, const char* fmt, ...);
     } while (0)
 
 // ---------------------------------------------------------------------------------------------------
-// Scratch resources that live for one call: move-only owners.  The caller creates the resource into the member (hipMalloc((void**)&b.p, bytes),
-// hipEventCreateWithFlags(&e.e, ..)) and checks the status as it likes; the owner releases it on every way out of the scope.  Internal linkage: none of
-// it reaches the library's dynamic symbols.  (The long-lived members of NetPlan / OpHost / DictHost stay plain pointers that qmri_free_* release.)
+// Owners of device and pinned memory, events and streams (dev_mem.h).  Internal linkage: none of it reaches the library's dynamic symbols.
 // ---------------------------------------------------------------------------------------------------
-namespace {
-template <typename T> struct DevBuf {               // hipMalloc / hipFree
-    T* p = nullptr;
-    DevBuf() = default; DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    operator T*() const { return p; }
-};
-template <typename T> struct PinnedBuf {            // hipHostMalloc / hipHostFree
-    T* p = nullptr;
-    PinnedBuf() = default; PinnedBuf(PinnedBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
-    ~PinnedBuf() { if (p) (void)hipHostFree(p); }
-    operator T*() const { return p; }
-};
-struct Event {                                      // hipEventCreate* / hipEventDestroy
-    hipEvent_t e = nullptr;
-    Event() = default; Event(Event&& o) noexcept : e(o.e) { o.e = nullptr; }
-    ~Event() { if (e) (void)hipEventDestroy(e); }
-    operator hipEvent_t() const { return e; }
-};
-struct Stream {                                     // hipStreamCreate* / hipStreamDestroy
-    hipStream_t s = nullptr;
-    Stream() = default; Stream(Stream&& o) noexcept : s(o.s) { o.s = nullptr; }
-    ~Stream() { if (s) (void)hipStreamDestroy(s); }
-    operator hipStream_t() const { return s; }
-};
-// a long-lived device array of `count` elements (at least one), with the library's message when the device is out of memory
-template <typename T> int dev_alloc(qmri_ctx* ctx, T** p, size_t count) {
-    *p = nullptr;
-    hipError_t e = hipMalloc((void**)p, std::max<size_t>(count, 1) * sizeof(T));
-    if (e != hipSuccess) { qmri_set_error(ctx, "hipMalloc of %zu bytes failed: %s", count * sizeof(T), hipGetErrorString(e)); return QMRI_ERR_NOMEM; }
-    return QMRI_OK;
-}
-}  // namespace
+#include "dev_mem.h"
 
 // ---------------------------------------------------------------------------------------------------
 // A/B and diagnostic switches ("knobs").  ONE environment variable, QMRI_DEBUG="name=value,name=value" (read once per process), and
@@ -210,11 +176,11 @@ struct ConvLayer {
     int Cin, Cout;           // logical channels (UP: Cout = real output channels)
     int cin_pad, n_ct;       // padded input channels, number of 32-row output tiles in the packed weights
     int MT;                  // 32-row MFMA tiles per wave
-    float* wp;               // packed weights (device)
+    DevArr<float> wp;        // packed weights (device)
     size_t wp_floats;
-    void* d_tab;             // tile table {cout tile, ow0, oh0, batch} for (tab_B, tab_MT)
+    DevArr<void> d_tab;      // tile table {cout tile, ow0, oh0, batch} for (tab_B, tab_MT)
     int tab_B, tab_MT;
-    void* wp6 = nullptr;     // weights split into f16 pairs (sp6 == 2) or bf16 triples (sp6 == 3), MFMA A-fragment order (conv6_kernels.hip)
+    DevArr<void> wp6;        // weights split into f16 pairs (sp6 == 2) or bf16 triples (sp6 == 3), MFMA A-fragment order (conv6_kernels.hip)
     int sp6 = 2;             // pieces per fp32 operand of the matrix-core path
     float w6_descale = 1.f;  // f16 scheme: 2^-k of the power-of-two the packed weights carry (conv6_kernels.hip)
     int nchunk6 = 0, n_ct6 = 0;   // 16-channel chunks (2x2 layers: K steps), 64-row output tiles of wp6
@@ -252,19 +218,19 @@ struct NetPlan {
     PTensor x[4], a[4], t[4];
     PTensor in32;            // normalised network input (in_nc channels, allocated up to the head's padded Cin)
     PTensor out32;           // network output (out_nc channels)
-    std::vector<float*> allocs;
+    DevPool pool;            // the tensors above and the plan-lifetime arrays below
     unsigned* d_counter = nullptr;   // tile-queue counter of the persistent conv kernels
     unsigned counter_base = 0;       // host mirror of its value after the launches issued so far
     bool counter_by_memset = false;  // a launch under a stream capture: the queue is reset before every launch instead
     bool force_f32 = false;             // calibration (qmri_set_denoiser): run the f32-MFMA kernels whatever the scheme
     unsigned* d_range_flag = nullptr;   // f16 scheme: raised by a conv kernel whose output leaves the f16-splittable range
-    unsigned* h_range_flag = nullptr;   // pinned host words written by k_act_check at the end of every forward pass: [0] overflow bit, [1 + layer] low-magnitude bit
+    PinnedArr<unsigned> h_range_flag;   // pinned host words written by k_act_check at the end of every forward pass: [0] overflow bit, [1 + layer] low-magnitude bit
     int h_range_words = 0;              // ... how many (1 + layers must fit, else the ADMM loop copies the device flag instead)
     int fallbacks = 0;                  // times a run-time guard moved the network from the f16 to the bf16 scheme since qmri_set_denoiser
     float* d_act_slots = nullptr;       // f16 scheme: largest |output| per (reporting launch, wave) of the current forward pass (conv6_kernels.hip, ACT_LOW)
     int* d_act_count = nullptr;         // ... valid slots per reporting launch
     float* d_act_ref = nullptr;         // ... the magnitude of every layer under the set-up probe (calibrated reference)
-    int act_cap = 0;                    // rows of the three arrays (= layers)
+    int act_rows = 0;                    // rows of the three arrays (= layers)
     bool act_on = false, act_record = false;   // a reporting forward pass is under way; it is the calibration probe
     // the PnP-ADMM loop lets the kernel after the forward pass finish the per-layer |output| report (conv6_act.h) instead of launching k_act_check
     bool act_defer = false, act_pending_valid = false;
@@ -276,8 +242,7 @@ struct NetPlan {
     float* d_wflat = nullptr;        // ... on the device, in the caller's order (knob pack_gpu = 1, default: the packers run there)
     const float* w_begin = nullptr;  // (inside qmri_set_denoiser only: start of the caller's blob, for the layers' offsets)
     std::vector<float> w_max;        // ... and every layer's largest |w| (from the device): the f16 scheme's per-layer scale
-    float* d_c6part = nullptr;       // split-K partial outputs of k_conv6 (conv6_kernels.hip), grown on demand
-    size_t c6part_floats = 0;
+    DevArr<float> d_c6part;          // split-K partial outputs of k_conv6 (conv6_kernels.hip), grown on demand
     void* d_stamps = nullptr;        // diagnostic: per-workgroup timing stamps of the last conv launch (knob conv_stamps = 1)
     // resident-tile ResBlock runs (conv6_kernels.hip k_conv6r): the exchange buffer of the tiles' edge pixels (two layer parities x tiles x 23.5 KB), the
     // running tag of its granules (never reset), and the switch a timed-out hand-off turns off for the life of the plan
@@ -290,27 +255,24 @@ struct NetPlan {
     int res_timeouts = 0;            // hand-off time-outs since qmri_set_denoiser (three: the form stays off)
     int res_clean = 0;               // clean one-launch-per-layer passes since the last one (K_RES_REARM of them re-arm the form)
     int res_drop = 0;                // test hook: bit 0 = tile 0 withholds its hand-off
-    double* d_io = nullptr; size_t io_cap = 0;   // qmri_denoise: device staging of the caller's doubles (elements), kept between calls
+    DevArr<double> d_io;             // qmri_denoise: device staging of the caller's doubles (elements), kept between calls
     void* d_res_stamps = nullptr;    // diagnostic: phase stamps of the last k_conv6r launch (knob res_stamps), 4 x 2 x R_MAXL (10) x 16 of 2048 values
     bool ready = false;
 };
 
 // multi-coil LSQR of B slices (mc_kernels.hip): work buffers owned by the context, grown only when B or B x ncoil grows
 struct McWork {
-    double2 *ut = nullptr;              // [B][ncoil][m]  u(1:m) of every coil image, unscaled
-    double2 *ub = nullptr, *v = nullptr, *d = nullptr, *t = nullptr;   // [B][n]  u(m+1:end) unscaled, v, d, A_mc' u
-    double2 *scr = nullptr;             // [max_batch][n] coil images of one transform chunk
-    double* part = nullptr;             // fixed partial sums (mc_kernels.hip McParts)
-    LsqrState* st = nullptr;            // [B] device state; sc[0] only
-    LsqrState* hst = nullptr;           // [B] pinned: iter / done / flag written by the kernel that changes them
-    size_t cap_sl = 0, cap_img = 0;
+    DevArr<double2> ut;                 // [B][ncoil][m]  u(1:m) of every coil image, unscaled
+    DevArr<double2> ub, v, d, t;        // [B][n]  u(m+1:end) unscaled, v, d, A_mc' u
+    DevArr<double2> scr;                // [max_batch][n] coil images of one transform chunk
+    DevArr<double> part;                // fixed partial sums (mc_kernels.hip McParts)
+    DevArr<LsqrState> st;               // [B] device state; sc[0] only
+    PinnedArr<LsqrState> hst;           // [B] pinned: iter / done / flag written by the kernel that changes them
     int pred = 8;                       // iterations enqueued before the first event wait after the initial step (the last solve's count + 1)
     int pred_cg = 8;                    // ... of the Toeplitz CG (toep_kernels.hip)
     // staging of the host-array entry points: maps [B][ncoil][N*M], y [B][ncoil][m], x and z (or x0) [B][n]
-    double2 *sm = nullptr, *sy = nullptr, *sx = nullptr, *sz = nullptr;
-    size_t stage_sl = 0, stage_img = 0;
+    DevArr<double2> sm, sy, sx, sz;
 };
-void mc_free_work(McWork& w);
 int mc_ensure_staging(qmri_ctx* ctx, int B, int ncoil);
 int mc_adjoint_batch_dev(qmri_ctx* ctx, int B, int ncoil, const double2* d_maps, const double2* d_y, double2* d_x);
 int mc_ensure_work(qmri_ctx* ctx, int B, int ncoil);
@@ -322,16 +284,13 @@ int qmri_lsqr_mc_batch_dev(qmri_ctx* ctx, int B, int ncoil, const double2* d_map
 
 // coil compression of multi-coil stacks (cc_kernels.hip, api_cc.cpp): work buffers owned by the context, grown only when a call needs more
 struct CcWork {
-    double2 *part = nullptr, *R = nullptr, *X = nullptr, *L = nullptr, *U = nullptr, *W = nullptr;   // partials, R / K, scratch, chol(Psi), U_nv, W
-    size_t part_cap = 0, R_cap = 0, X_cap = 0, L_cap = 0, U_cap = 0, W_cap = 0;
-    double2* hK = nullptr; size_t hK_cap = 0;   // pinned: K to the host eigensolve, then U_nv back
-    int* hbad = nullptr;                        // pinned: Cholesky of Psi failed
+    DevArr<double2> part, R, X, L, U, W;        // partials, R / K, scratch, chol(Psi), U_nv, W
+    PinnedArr<double2> hK;                      // pinned: K to the host eigensolve, then U_nv back
+    PinnedArr<int> hbad;                        // pinned: Cholesky of Psi failed
     bool lds_attr = false;                      // > 64 KB dynamic LDS allowed for the 128-coil covariance kernel
     // staging of the host-array entry point and of Psi: y / maps in, y / maps out
-    double2 *psi = nullptr, *sy = nullptr, *sm = nullptr, *oy = nullptr, *om = nullptr;
-    size_t psi_cap = 0, sy_cap = 0, sm_cap = 0, oy_cap = 0, om_cap = 0;
+    DevArr<double2> psi, sy, sm, oy, om;
 };
-void cc_free_work(CcWork& w);
 int cc_ensure_staging(qmri_ctx* ctx, size_t ny, size_t nm, size_t nyo, size_t nmo);
 int cc_compress_dev(qmri_ctx* ctx, int B, int ncoil, const double2* d_y, const double2* d_maps, const double2* d_psi, const qmri_cc_params& prm,
                     int* nv_out, double2* d_yout, double2* d_mout, double2* d_Wout, double* eig_out);
@@ -428,18 +387,17 @@ struct NufftHost {
     int w = 0, nseg = 0, nred = 0, nslot = 0;
     double beta = 0.0;
     // Toeplitz normal operator (toep_kernels.hip): the 2N x 2M DFT of the s x s point-spread function of A^H A, times 1/4,
-    // Hermitian-packed: [pair (c <= c') = c' (c' + 1) / 2 + c][a][j1][j2], bin (2 j1 + a1, 2 j2 + a2).  Built by toep_prepare, freed by nufft_free.
+    // Hermitian-packed: [pair (c <= c') = c' (c' + 1) / 2 + c][a][j1][j2], bin (2 j1 + a1, 2 j2 + a2).  Built by toep_prepare, in the operator's pool.
     double2* d_khat = nullptr;
     bool khat_ready = false;
     // sample weights of the weighted adjoint (density compensation): [m] in ABI order, attached by qmri_nufft_dcf or
-    // qmri_set_sample_weights, read by the qmri_adjoint_w* calls alone, freed by nufft_free (replacing the operator drops them)
-    double* d_w = nullptr;
+    // qmri_set_sample_weights, read by the qmri_adjoint_w* calls alone (replacing the operator drops them)
+    DevArr<double> d_w;
     bool w_set = false;
     // field map of the off-resonance correction (time segmentation): attached by qmri_set_field_map, read by nufft_launch_fwd /
-    // _adj (every caller of the operator), freed by nufft_free (replacing the operator drops it).  Sized at attach time.
-    double2* d_pm = nullptr;                     // [fm_L][N*M] phase maps of the segments
-    double2* d_bl = nullptr;                     // [fm_L][m] coefficients in the plan's sorted order, the centre-frequency phase folded in
-    size_t pm_cap = 0, bl_cap = 0;               // elements allocated
+    // _adj (every caller of the operator); replacing the operator drops it.  Sized at attach time.
+    DevArr<double2> d_pm;                        // [fm_L][N*M] phase maps of the segments
+    DevArr<double2> d_bl;                        // [fm_L][m] coefficients in the plan's sorted order, the centre-frequency phase folded in
     int fm_L = 0;                                // segments
     bool fm_set = false;
     // what the attached map's field-aware normal operator is defined by, kept on the host at attach time
@@ -448,9 +406,9 @@ struct NufftHost {
     int fm_nbins = 0;
     // field-aware Toeplitz normal operator (qmri_nufft_prepare_normal_fm): A_f^H A_f ~ sum_l P_l^H T_l P_l over fmn_L segments of
     // the DIFFERENCE phase.  Belongs to the attached map: qmri_set_field_map and replacing the operator drop it.  d_khat above is never touched by it.
-    double2* d_khat_fm = nullptr;                // [fmn_L][pair][a][j1][j2], T_l built with the sample weights c_l(tau_i)
-    double2* d_pm_n = nullptr;                   // [fmn_L][N*M] phase maps at the fmn_L segment times (d_pm is at the operator's own times)
-    double2* d_xs = nullptr;                     // [maxB][n] x kept while the segments add into out (out may be x)
+    DevArr<double2> d_khat_fm;                   // [fmn_L][pair][a][j1][j2], T_l built with the sample weights c_l(tau_i)
+    DevArr<double2> d_pm_n;                      // [fmn_L][N*M] phase maps at the fmn_L segment times (d_pm is at the operator's own times)
+    DevArr<double2> d_xs;                        // [maxB][n] x kept while the segments add into out (out may be x)
     int fmn_L = 0;                               // segments; 1 with fmn_plain: a constant map, the plain d_khat serves
     bool fmn_plain = false;
     bool fmn_ready = false;
@@ -486,7 +444,6 @@ int offres_ncoefficients_dev(qmri_ctx* ctx, int L, int nb, const double2* d_dh, 
                              const double* d_ts, double* d_c, OffresFit* fit);
 void offres_drop_normal(NufftHost& h);             // forgets the field-aware transform and frees its device buffers (K^, phase maps, staging)
 int nufft_check_gridded(qmri_ctx* ctx, const char* what, const char* instead);   // QMRI_ERR_UNSUPPORTED on a trajectory operator, else QMRI_OK
-void nufft_free(NufftHost& h);
 bool nufft_kernel_ok(int w);
 NufftDev nufft_dev_view(const qmri_ctx* ctx);
 int nufft_launch_ramps(qmri_ctx* ctx, int B, const double2* x, double2* g);      // k_nu_pre without 1 / Phi:  x [B][n] -> g [B][4][n]
@@ -513,13 +470,14 @@ enum { OP_GRIDDED = 0, OP_NUFFT = 1 };
 struct OpHost {
     int kind = OP_GRIDDED;              // OP_NUFFT: qmri_set_operator_nufft (nu below; the k-space tables are not allocated)
     NufftHost nu;
+    DevPool pool;                       // every plan-lifetime device array of the operator: the raw pointers below, in ks / ls and in nu
     bool ready = false;
     int N = 0, M = 0, s = 0, T = 0, m = 0, maxB = 0, nsampled = 0;
     double* d_Vt = nullptr; KEntry* d_ent = nullptr; int32_t* d_perm = nullptr; int32_t* d_kptr = nullptr;
     double2* d_tw = nullptr; int32_t* d_kslot = nullptr; double* d_ginv = nullptr;
-    double2* d_coils = nullptr; int ncoil = 0;   // multi-coil extension: [ncoil][N*M] sensitivity maps (qmri_set_coils)
+    DevArr<double2> d_coils; int ncoil = 0;   // multi-coil extension: [ncoil][N*M] sensitivity maps (qmri_set_coils)
     McWork mc;                          // ... and the work buffers of its LSQR
-    KsDev ks{};                         // k-space LSQR plan + state (device pointers owned here)
+    KsDev ks{};                         // k-space LSQR plan + state
     bool xhat_valid = false;            // ks.xhat holds the spectrum of d_x
     double ginv_r = -1.0;
     std::vector<double> V;              // T x s column-major (host copy)
@@ -535,12 +493,10 @@ struct OpHost {
     double2* d_chat = nullptr;          // DIRECT: unitary FFT2 of A'y
     double* d_mm = nullptr;             // [B][nblk_z][2] min/max partials
     double* d_norm = nullptr;           // [B][2] lo, range
-    double* d_diag = nullptr;           // [B][iters][2]
+    DevArr<double> d_diag;              // [B][iters][2], sized by the diagnostic call
     double* d_pd = nullptr;             // diag partials
-    int32_t* h_flags = nullptr;         // pinned host mirror of done flags
-    LsqrState* h_state = nullptr;       // pinned
-    LsqrState* h_ring = nullptr;        // pinned [ADMM iteration][slice]: LSQR state of a reconstruction whose host never waits (api_admm.cpp)
-    size_t h_ring_cap = 0;
+    PinnedArr<LsqrState> h_state;       // pinned
+    PinnedArr<LsqrState> h_ring;        // pinned [ADMM iteration][slice]: LSQR state of a reconstruction whose host never waits (api_admm.cpp)
 };
 
 struct DictHost {
@@ -549,27 +505,28 @@ struct DictHost {
     // s <= 16 (dict_kernels.hip): d_pack = [ntiles][lane][4 | 8] MFMA A-fragments.
     // s  > 16 (wide = 1, dictw_kernels.hip): d_pack = [ntiles (padded to 128-atom tiles)][G8][lane][4], G8 = groups of 8 channels (s padded to 16)
     int wide = 0, G8 = 0;
+    DevPool pool;                                         // the dictionary's own arrays: d_pack, d_normD, d_lut, d_pack16
     float* d_pack = nullptr;
-    float* d_xp = nullptr; size_t xp_cap = 0;             // wide: the pixels as single-precision B-fragments, [tile32][G8][re | -im][lane][4]  (bytes)
-    float4* d_win = nullptr; size_t win_cap = 0;          // per pixel (re ip, im ip, atom, |ip|) of the winner, kept when Xfit is asked for (bytes)
+    DevArr<float4> d_xp;                                  // wide: the pixels as single-precision B-fragments, [tile32][G8][re | -im][lane][4]
+    DevArr<float4> d_win;                                 // per pixel (re ip, im ip, atom, |ip|) of the winner, kept when Xfit is asked for
     int slots_w = 0;                                      // workgroups of k_dictw_match the device holds at once
     float* d_normD = nullptr; float* d_lut = nullptr;
-    float4* d_part = nullptr; size_t part_cap = 0;        // (|ip|, atom index, re, im) per (atom part, pixel) when the atoms are split over workgroups (bytes)
+    DevArr<float4> d_part;                                // (|ip|, atom index, re, im) per (atom part, pixel) when the atoms are split over workgroups
     int slots = 0, slots_f = 0;                           // workgroups of k_dict_match / k_dict_match_f the device holds at once (occupancy query, first launch)
     // f16 filter in front of the exact products (dict_kernels.hip): hi / lo pieces of g D as A-fragments, [ntiles][hi | lo][64 lanes] of 16 bytes;
     // nullptr when D holds a non-finite entry (no filter then).  marg_coef = 2^-14 (g R)^2, R = largest row 2-norm of D.
     uint4* d_pack16 = nullptr;
-    int* d_gmax = nullptr; size_t gmax_cap = 0;           // per pixel: largest filtered |ip|^2 seen by any wave (float bits), -1 at launch (bytes)
+    DevArr<int> d_gmax;                                   // per pixel: largest filtered |ip|^2 seen by any wave (float bits), -1 at launch
     float marg_coef = 0.f;
     int filter_on = 1; float margin_scale = 1.f;          // qmri_debug_dict_filter
     // groups of a narrow dictionary (qmri_set_dictionary_groups; dictg_kernels.hip): G = 0 none.  d_gpack / d_gpack16 are
     // d_pack / d_pack16 again with every group starting on a 32-atom tile (gtile_h[g], gtile_h[G] tiles in all); d_gwork is the per-call scratch of
-    // the pixel bucketing (bytes)
+    // the pixel bucketing
     int G = 0, gtiles_max = 0;
     std::vector<int> gtile_h;
-    float* d_gpack = nullptr; uint4* d_gpack16 = nullptr;
-    int* d_gptr = nullptr; int* d_gtile = nullptr; double* d_gval = nullptr;
-    int* d_gwork = nullptr; size_t gwork_cap = 0;
+    DevArr<float> d_gpack; DevArr<uint4> d_gpack16;
+    DevArr<int> d_gptr, d_gtile; DevArr<double> d_gval;
+    DevArr<int> d_gwork;
     int slots_g = 0, slots_gf = 0;                        // as slots / slots_f, for the grouped instantiations
 };
 
@@ -600,7 +557,7 @@ struct qmri_ctx {
     int lsqr_pred = 20;                 // predicted LSQR iteration count for launch chunking
     int ks_persist = -1;                // k_ks_persist (all LSQR iterations in one launch): -1 = knob lsqr_persist (default on), 0 / 1 set by qmri_debug_lsqr_persist
     int ks_persist_cap = -1;            // ... workgroups of it the device holds at once (occupancy query, first use)
-    void* d_ks_gran = nullptr;          // ... its tagged partial sums (granules)
+    DevArr<void> d_ks_gran;             // ... its tagged partial sums (granules)
     unsigned ks_tag = 16;               // ... tag of the next solve's first granule (tags are unique across solves)
     // round 6 (qmri_get_health): what a slow or repeated reconstruction was doing.  Counters since qmri_create.
     int ks_timeouts = 0;                // one-launch LSQR kernels that gave up waiting for a partial sum (the solve / reconstruction was repeated)
@@ -722,7 +679,6 @@ void conv_plan_layer(ConvLayer& L, ConvKind kind, int Cin, int Cout);
 
 // dictionary match (dict_kernels.hip)
 int dict_launch(qmri_ctx* ctx, const double2* d_X, int Npix, float* d_qmap, float* d_pd, float* d_mt, int32_t* d_dm, float2* d_xfit);
-int dict_scratch(qmri_ctx* ctx, void** buf, size_t* cap, size_t need_bytes);
 int dict_launch_xfit(qmri_ctx* ctx, const float4* win, int Npix, float2* d_xfit);
 // grouped match (dictg_kernels.hip: groups, pixel bucketing; dict_kernels.hip: the match on slot tiles)
 struct DictGroupView;

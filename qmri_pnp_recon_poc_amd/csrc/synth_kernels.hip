@@ -114,37 +114,29 @@ static int synthesize_impl(qmri_ctx* ctx, const double* qmap, const double* pd_i
     if (!d.ready) { qmri_set_error(ctx, "dictionary not set: call qmri_set_dictionary first"); return QMRI_ERR_STATE; }
     QMRI_CHECK_ARG(ctx, qmap && X_out && Npix > 0, "qmri_synthesize_tsmi: qmap / X_out NULL or Npix <= 0");
     if (d.Q < 2) { qmri_set_error(ctx, "the look-up table needs T1 and T2 columns (Q >= 2)"); return QMRI_ERR_UNSUPPORTED; }
-    double* d_q = nullptr; float* d_X = nullptr; int32_t* d_i = nullptr;
-    double* d_pd = nullptr; int32_t* d_pi = nullptr; double* d_im = nullptr;
+    DevBuf<double> d_q, d_pd, d_im; DevBuf<float> d_X; DevBuf<int32_t> d_i, d_pi;
     const int nch = complex_mode ? 2 * d.s : d.s;                   // output channels
     const int nbx = (Npix + NNT * NN_PPT - 1) / (NNT * NN_PPT);
     int nslice = std::max(1, std::min(NN_KSPLIT_TARGET / std::max(nbx, 1), (d.K + NN_TILE - 1) / NN_TILE));
     const int kslice = (((d.K + nslice - 1) / nslice) + NN_TILE - 1) / NN_TILE * NN_TILE;     // whole tiles per slice
     nslice = (d.K + kslice - 1) / kslice;
-    int st = QMRI_OK;
-    auto fail = [&](const char* what) { qmri_set_error(ctx, "qmri_synthesize_tsmi: %s", what); st = QMRI_ERR_HIP; };
-    do {
-        if (hipMalloc((void**)&d_q, (size_t)3 * Npix * sizeof(double)) != hipSuccess || hipMalloc((void**)&d_X, (size_t)nch * Npix * sizeof(float)) != hipSuccess ||
-            (pd_imag && hipMalloc((void**)&d_im, (size_t)Npix * sizeof(double)) != hipSuccess) ||
-            hipMalloc((void**)&d_i, (size_t)Npix * sizeof(int32_t)) != hipSuccess || hipMalloc((void**)&d_pd, (size_t)nslice * Npix * sizeof(double)) != hipSuccess ||
-            hipMalloc((void**)&d_pi, (size_t)nslice * Npix * sizeof(int32_t)) != hipSuccess) { fail("hipMalloc"); st = QMRI_ERR_NOMEM; break; }
-        if (hipMemcpyAsync(d_q, qmap, (size_t)3 * Npix * sizeof(double), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) { fail("H2D copy"); break; }
-        if (pd_imag && hipMemcpyAsync(d_im, pd_imag, (size_t)Npix * sizeof(double), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) { fail("H2D copy"); break; }
-        k_nn_lut<<<dim3(nbx, nslice), dim3(NNT), 0, ctx->stream>>>(d_q, Npix, d.d_lut, d.K, kslice, d_pd, d_pi);
-        k_nn_combine<<<dim3((Npix + 255) / 256), dim3(256), 0, ctx->stream>>>(d_pd, d_pi, Npix, nslice, d_i);
-        const DictView dv = {d.d_pack, d.wide, ((d.s + 1) / 2 <= 4) ? 4 : 8, d.G8};
-        if (complex_mode) k_synth_tsmi_complex<<<dim3((Npix + 255) / 256), dim3(256), 0, ctx->stream>>>(d_q, d_im, Npix, d_i, dv, d.d_normD, d.s, d_X);
-        else k_synth_tsmi<<<dim3((Npix + 255) / 256), dim3(256), 0, ctx->stream>>>(d_q, Npix, d_i, dv, d.d_normD, d.s, d_X);
-        if (hipGetLastError() != hipSuccess) { fail("kernel launch"); break; }
-        if (hipMemcpyAsync(X_out, d_X, (size_t)nch * Npix * sizeof(float), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) { fail("D2H copy"); break; }
-        if (idx_out && hipMemcpyAsync(idx_out, d_i, (size_t)Npix * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) { fail("D2H copy"); break; }
-        if (hipStreamSynchronize(ctx->stream) != hipSuccess) { fail("synchronize"); break; }
-    } while (0);
-    if (d_q) (void)hipFree(d_q);
-    if (d_X) (void)hipFree(d_X);
-    if (d_i) (void)hipFree(d_i);
-    if (d_pd) (void)hipFree(d_pd);
-    if (d_pi) (void)hipFree(d_pi);
-    if (d_im) (void)hipFree(d_im);
-    return st;
+    auto fail = [&](const char* what) { qmri_set_error(ctx, "qmri_synthesize_tsmi: %s", what); return QMRI_ERR_HIP; };
+    QMRI_TRY(d_q.ensure(ctx, (size_t)3 * Npix));
+    QMRI_TRY(d_X.ensure(ctx, (size_t)nch * Npix));
+    if (pd_imag) QMRI_TRY(d_im.ensure(ctx, (size_t)Npix));
+    QMRI_TRY(d_i.ensure(ctx, (size_t)Npix));
+    QMRI_TRY(d_pd.ensure(ctx, (size_t)nslice * Npix));
+    QMRI_TRY(d_pi.ensure(ctx, (size_t)nslice * Npix));
+    if (hipMemcpyAsync(d_q, qmap, (size_t)3 * Npix * sizeof(double), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return fail("H2D copy");
+    if (pd_imag && hipMemcpyAsync(d_im, pd_imag, (size_t)Npix * sizeof(double), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return fail("H2D copy");
+    k_nn_lut<<<dim3(nbx, nslice), dim3(NNT), 0, ctx->stream>>>(d_q, Npix, d.d_lut, d.K, kslice, d_pd, d_pi);
+    k_nn_combine<<<dim3((Npix + 255) / 256), dim3(256), 0, ctx->stream>>>(d_pd, d_pi, Npix, nslice, d_i);
+    const DictView dv = {d.d_pack, d.wide, ((d.s + 1) / 2 <= 4) ? 4 : 8, d.G8};
+    if (complex_mode) k_synth_tsmi_complex<<<dim3((Npix + 255) / 256), dim3(256), 0, ctx->stream>>>(d_q, d_im, Npix, d_i, dv, d.d_normD, d.s, d_X);
+    else k_synth_tsmi<<<dim3((Npix + 255) / 256), dim3(256), 0, ctx->stream>>>(d_q, Npix, d_i, dv, d.d_normD, d.s, d_X);
+    if (hipGetLastError() != hipSuccess) return fail("kernel launch");
+    if (hipMemcpyAsync(X_out, d_X, (size_t)nch * Npix * sizeof(float), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return fail("D2H copy");
+    if (idx_out && hipMemcpyAsync(idx_out, d_i, (size_t)Npix * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return fail("D2H copy");
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return fail("synchronize");
+    return QMRI_OK;
 }

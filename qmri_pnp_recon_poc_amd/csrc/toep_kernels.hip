@@ -315,8 +315,8 @@ int toep_build_weighted(qmri_ctx* ctx, const double* d_c, double2* khat) {
     if (o.kind != OP_NUFFT) { qmri_set_error(ctx, "toep_prepare: no trajectory operator (internal)"); return QMRI_ERR_STATE; }
     const size_t plane = (size_t)o.N * o.M, n = plane * o.s;
     DevBuf<double2> Q, y;
-    QMRI_TRY(dev_alloc(ctx, &Q.p, 4 * n));
-    QMRI_TRY(dev_alloc(ctx, &y.p, (size_t)o.m));
+    QMRI_TRY(Q.ensure(ctx, 4 * n));
+    QMRI_TRY(y.ensure(ctx, (size_t)o.m));
     const NufftDev nu = nufft_dev_view(ctx);
     const OpDev op = qmri_opdev(ctx);
     for (int cp = 0; cp < o.s; ++cp) {
@@ -344,7 +344,7 @@ int toep_prepare(qmri_ctx* ctx) {
     if (h.fm_set && h.fmn_ready && !h.fmn_plain) return QMRI_OK;      // the field-aware transform is the one in force: the plain one is not needed
     if (h.khat_ready) return QMRI_OK;
     const size_t plane = (size_t)o.N * o.M, npair = (size_t)o.s * (o.s + 1) / 2;
-    if (!h.d_khat) QMRI_TRY(dev_alloc(ctx, &h.d_khat, npair * 4 * plane));
+    if (!h.d_khat) QMRI_TRY(ctx->op.pool.alloc(ctx, &h.d_khat, npair * 4 * plane));
     QMRI_TRY(toep_build_weighted(ctx, nullptr, h.d_khat));
     h.khat_ready = true;
     return QMRI_OK;
