@@ -19,17 +19,24 @@ static thread_local std::string g_create_err;
 // knobs (qmri_internal.h QmriKnob): A/B and diagnostic switches behind ONE environment variable and one entry point
 // ---------------------------------------------------------------------------------------------------
 namespace {
-struct KnobDef { const char* name; int dflt; };
-const KnobDef g_knob_defs[K_COUNT] = {
-    {"conv_scheme", 2}, {"conv_f32", 0}, {"conv_wt", 1}, {"conv_xcd", 1}, {"conv_persist", 1}, {"conv_splitk", 1},
-    {"conv_midcfg", 3}, {"conv_deepcfg", 3}, {"conv_deepks", 4},
-    {"conv_resident", 1}, {"res_head", 1}, {"res_tail", 1}, {"res_down", 1}, {"res_delay", 24}, {"res_pipe", 1}, {"res_pipe_delay", 8}, {"res_rearm", 64},
-    {"res_stamps", 0}, {"conv_stamps", 0}, {"conv_stamp_launch", -1}, {"lsqr_stamps", 0},
-    {"conv_mt2", 1024}, {"conv_occ", 2},
-    {"fuse_ew", 1}, {"lsqr_persist", 1}, {"lsqr_fold", 1}, {"dictw_lsp", 2}, {"verbose", 0},
-    {"pack_gpu", 1}, {"nufft_seg", NU_SEG},
-    {"fmap_fuse", 0}, {"fmap_start", 0},
+struct KnobDef { QmriKnob id; const char* name; int dflt; };
+constexpr KnobDef g_knob_defs[] = {
+    {K_CONV_SCHEME, "conv_scheme", 2}, {K_CONV_F32, "conv_f32", 0}, {K_CONV_WT, "conv_wt", 1}, {K_CONV_XCD, "conv_xcd", 1}, {K_CONV_PERSIST, "conv_persist", 1},
+    {K_CONV_SPLITK, "conv_splitk", 1}, {K_CONV_MIDCFG, "conv_midcfg", 3}, {K_CONV_DEEPCFG, "conv_deepcfg", 3}, {K_CONV_DEEPKS, "conv_deepks", 4},
+    {K_CONV_RESIDENT, "conv_resident", 1}, {K_RES_HEAD, "res_head", 1}, {K_RES_TAIL, "res_tail", 1}, {K_RES_DOWN, "res_down", 1}, {K_RES_DELAY, "res_delay", 24},
+    {K_RES_PIPE, "res_pipe", 1}, {K_RES_PIPE_DELAY, "res_pipe_delay", 8}, {K_RES_REARM, "res_rearm", 64},
+    {K_RES_STAMPS, "res_stamps", 0}, {K_CONV_STAMPS, "conv_stamps", 0}, {K_CONV_STAMP_LAUNCH, "conv_stamp_launch", -1}, {K_LSQR_STAMPS, "lsqr_stamps", 0},
+    {K_CONV_MT2, "conv_mt2", 1024}, {K_CONV_OCC, "conv_occ", 2},
+    {K_FUSE_EW, "fuse_ew", 1}, {K_LSQR_PERSIST, "lsqr_persist", 1}, {K_LSQR_FOLD, "lsqr_fold", 1}, {K_DICTW_LSP, "dictw_lsp", 2}, {K_VERBOSE, "verbose", 0},
+    {K_PACK_GPU, "pack_gpu", 1}, {K_NUFFT_SEG, "nufft_seg", NU_SEG},
+    {K_FMAP_FUSE, "fmap_fuse", 0}, {K_FMAP_START, "fmap_start", 0},
 };
+constexpr bool knob_defs_follow_enum() {
+    if (sizeof(g_knob_defs) / sizeof(g_knob_defs[0]) != K_COUNT) return false;
+    for (int k = 0; k < K_COUNT; ++k) if (g_knob_defs[k].id != k) return false;
+    return true;
+}
+static_assert(knob_defs_follow_enum(), "g_knob_defs: one entry per QmriKnob, in the enum's order");
 std::atomic<int> g_knob_val[K_COUNT];
 std::once_flag g_knob_once;
 
@@ -109,6 +116,7 @@ extern "C" int qmri_create(int device, qmri_ctx** out) {
     qmri_ctx* ctx = new (std::nothrow) qmri_ctx();
     if (!ctx) { qmri_set_error(nullptr, "out of host memory"); return QMRI_ERR_NOMEM; }
     ctx->device = device;
+    ctx->conv_ncu = prop.multiProcessorCount;
     if ((e = hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking)) != hipSuccess) {
         qmri_set_error(nullptr, "hipStreamCreate failed: %s", hipGetErrorString(e));
         delete ctx;

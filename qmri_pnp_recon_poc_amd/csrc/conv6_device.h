@@ -9,9 +9,11 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 #include "qmri_internal.h"
 #include "conv6_act.h"
+#include "conv6_form.h"
 #include <hip/hip_ext.h>
 
 extern std::atomic<int> g_conv6_launch_counter;   // diagnostic: running number of conv6 launches (all configurations, all contexts; defined in conv6_kernels.hip)
@@ -84,6 +86,8 @@ template <> struct Cfg6<3> {     // 128 px x 32 cout: the workgroup takes ONE 32
     static constexpr int TH = 16, TW = 8, MW = 1, NCT = 1, MH = 2;
     static __device__ __forceinline__ void wave_map(int wave, int& pbh, int& pbw, int& m0) { pbh = 8 * (wave & 1); pbw = 4 * (wave >> 1); m0 = 0; }
 };
+template <int CFG> constexpr bool cfg6_is_form_tile() { return Cfg6<CFG>::TH == CONV6_TILE[CFG].th && Cfg6<CFG>::TW == CONV6_TILE[CFG].tw && Cfg6<CFG>::MH == CONV6_TILE[CFG].mh; }
+static_assert(cfg6_is_form_tile<0>() && cfg6_is_form_tile<1>() && cfg6_is_form_tile<2>() && cfg6_is_form_tile<3>(), "conv6_form.h CONV6_TILE restates Cfg6");
 // Output tile in LDS for BLOCKED output tensors: PIXEL-major, ot[pixel][OTP] with the tile's 64 output channels of a pixel contiguous (round 3).
 // In the MFMA C/D layout a lane's four consecutive registers are four consecutive output channels of one pixel, and an epilogue thread's
 // half-item is four consecutive channels of one pixel: one 16-byte LDS access on either side instead of four 4-byte ones (channel-major
@@ -290,8 +294,60 @@ static double conv_layer_flop(const ConvLayer& L, int B, int Hin, int Win) {
     return 2.0 * L.Cout * L.Cin * (k3 ? 9.0 : (L.kind == CONV_DOWN ? 4.0 : 1.0)) * hw * B;     // (transposed 2x2: every output pixel has ONE tap)
 }
 
-// split-K layers: the pair's start event rides on the convolution launch, its stop event on the reduce launch (one layer = one profile unit)
-struct ProfSpan { hipEvent_t start = nullptr, stop = nullptr; bool on = false; };
+// ---- what the launchers of k_conv6, k_conv6p and k_conv6s share
+// the tensor, weight and scheme fields that Conv6Args and Conv6sArgs have in common
+template <typename Args> static void conv6_fill_common(Args& A, qmri_ctx* ctx, const ConvLayer& L, const PTensor& in, const PTensor& out) {
+    A.in = in.fbase(); A.wp = reinterpret_cast<const uint4*>(L.wp6.p); A.out = out.fbase();
+    A.Cout = L.Cout; A.n_ct = L.n_ct6;
+    A.in_hp = in.hp; A.in_plane = (int)in.plane(); A.in_bs = (long)in.Cal * in.plane();
+    A.out_hp = out.hp; A.out_plane = (int)out.plane(); A.out_bs = (long)out.Cal * out.plane();
+    A.range_flag = ctx->net.d_range_flag;
+    A.xcd = qmri_knob(K_CONV_XCD);
+    A.descale_hi = L.w6_descale; A.descale_lo = L.w6_descale * (1.f / LO_SCALE);
+}
+
+// The arguments of one 3x3 launch in the form conv6_choose_form gave, for k_conv6 and k_conv6p alike; the caller sets `detail`.
+// Split-K (form.ksplit > 1): raw partial sums go to the planar scratch `partial`, out_ks elements apart; k_conv6_reduce adds the residual
+// operands, applies the ReLU and reports the layer's |output|.
+static Conv6Args conv6_args(qmri_ctx* ctx, const ConvLayer& L, int B, const PTensor& in, const PTensor& out, const PTensor* add1, const PTensor* add2,
+                            int relu_out, const Conv6Form& form, int wt, float* partial = nullptr, long out_ks = 0) {
+    const bool split = form.ksplit > 1;
+    Conv6Args A{};
+    conv6_fill_common(A, ctx, L, in, out);
+    if (split) { A.out = partial + (out.h0 - 1); add1 = add2 = nullptr; relu_out = 0; }
+    A.add1 = add1 ? add1->fbase() : nullptr; A.add2 = add2 ? add2->fbase() : nullptr;
+    A.add1_bs = add1 ? (long)add1->Cal * add1->plane() : 0;
+    A.add2_bs = add2 ? (long)add2->Cal * add2->plane() : 0;
+    A.W = in.W; A.H = in.H;
+    A.in_blk = in.blk ? 1 : 0; A.out_blk = (out.blk && !split) ? 1 : 0;
+    A.nchunk = L.nchunk6 / form.ksplit; A.nchunk_all = L.nchunk6; A.ksplit = form.ksplit; A.out_ks = out_ks;
+    A.tiles_h = form.tiles_h; A.tiles_w = form.tiles_w; A.ntiles = A.n_ct * A.tiles_h * A.tiles_w * B;
+    A.relu_out = relu_out; A.vec4 = form.vec4; A.wt = wt;
+    A.am = conv6_act_slot(ctx, L.sp6 == 2 && !split, L);
+    A.stamps = (unsigned long long*)ctx->net.d_stamps;
+    A.launch_idx = g_conv6_launch_counter.fetch_add(1, std::memory_order_relaxed);
+    return A;
+}
+
+// one launch of NT6 threads per workgroup; e0: the launch carries the profile's event pair (level 2 only: its own dispatch timestamps;
+// split-K: the start event alone -- the layer's pair ends on its reduce launch)
+template <typename Args>
+static int conv6_launch_kernel(qmri_ctx* ctx, void (*kernel)(const Args), int grid, size_t lds, hipEvent_t e0, hipEvent_t e1, const Args& A) {
+    if (e0) hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(NT6), (std::uint32_t)lds, ctx->stream, e0, e1, 0, A);
+    else kernel<<<dim3(grid), dim3(NT6), lds, ctx->stream>>>(A);
+    QMRI_HIP(ctx, hipGetLastError());
+    return QMRI_OK;
+}
+
+// the form's tile configuration as a template argument: f(std::integral_constant<int, CFG>)
+template <typename F> static int conv6_with_cfg(int cfg, F&& f) {
+    switch (cfg) {
+        case 0: return f(std::integral_constant<int, 0>());
+        case 1: return f(std::integral_constant<int, 1>());
+        case 2: return f(std::integral_constant<int, 2>());
+        default: return f(std::integral_constant<int, 3>());
+    }
+}
 
 // ---- host side of the weight packers (conv6_plan_pack, conv6s_plan_pack)
 inline uint16_t host_bf16(float x) {                               // round to nearest even, as v_cvt_pk_bf16_f32
@@ -339,25 +395,13 @@ __device__ __forceinline__ void dev_split(int sp, float v, unsigned short (&h)[3
         h[0] = __builtin_bit_cast(unsigned short, hi); h[1] = __builtin_bit_cast(unsigned short, lo); h[2] = 0;
     }
 }
-// the layer's power-of-two weight scale from its largest |w| (conv6_weight_scale's arithmetic; the maximum itself comes from the device)
-static float conv6_scale_from_max(ConvLayer& L, float mx) {
-    L.w6_descale = 1.f;
-    if (L.sp6 != 2) return 1.f;
-    if (!(mx > 0.f) || !std::isfinite(mx)) return 1.f;
-    int e = 0;
-    (void)std::frexp(mx, &e);
-    const int k = std::min(60, std::max(-60, 1 - e));
-    L.w6_descale = std::ldexp(1.f, -k);
-    return std::ldexp(1.f, k);
-}
 // f16 scheme: the layer's weights are packed times 2^k with the largest |w| in [1, 2), and the epilogue multiplies by 2^-k -- both
 // exact.  An f16 piece below 6.1e-5 is subnormal and carries an absolute, not a relative error; scaling keeps a layer of
 // uniformly small weights (say 1e-5) as accurate as any other.  Returns the factor and records its inverse in the layer.
-static float conv6_weight_scale(ConvLayer& L, const float* w, size_t n) {
+// mx: the layer's largest |w| (the device packers compute it on the device)
+static float conv6_scale_from_max(ConvLayer& L, float mx) {
     L.w6_descale = 1.f;
     if (L.sp6 != 2) return 1.f;
-    float mx = 0.f;
-    for (size_t i = 0; i < n; ++i) mx = std::max(mx, std::fabs(w[i]));
     if (!(mx > 0.f) || !std::isfinite(mx)) return 1.f;
     int e = 0;
     (void)std::frexp(mx, &e);                                      // mx = f * 2^e, f in [0.5, 1)
@@ -365,9 +409,14 @@ static float conv6_weight_scale(ConvLayer& L, const float* w, size_t n) {
     L.w6_descale = std::ldexp(1.f, -k);
     return std::ldexp(1.f, k);
 }
+static float conv6_weight_scale(ConvLayer& L, const float* w, size_t n) {
+    float mx = 0.f;
+    for (size_t i = 0; i < n; ++i) mx = std::max(mx, std::fabs(w[i]));
+    return conv6_scale_from_max(L, mx);
+}
 
 }  // namespace
 
-// the persistent form for slice batches (conv6p_kernels.hip): *done = false when the layer / launch does not qualify (k_conv6 runs then)
-int conv6p_try(qmri_ctx* ctx, int cfg, const ConvLayer& L, int B, const PTensor& in, const PTensor& out, const PTensor* add1, const PTensor* add2,
-               int relu_out, bool* done);
+// k_conv6p, the persistent form for slice batches (conv6p_kernels.hip), for conv6_launch: form.kernel == CONV6_KERNEL_CONV6P
+int conv6p_launch(qmri_ctx* ctx, const ConvLayer& L, int B, const PTensor& in, const PTensor& out, const PTensor* add1, const PTensor* add2,
+                  int relu_out, const Conv6Form& form);

@@ -492,84 +492,23 @@ __device__ __forceinline__ void conv6_body(const Conv6Args& A) {
 
 template <int CFG, int SP, bool INB, bool STAMP = false> __global__ __launch_bounds__(NT6) void k_conv6(const Conv6Args A) { conv6_body<CFG, SP, STAMP, INB>(A); }
 
+// k_conv6 on the form's grid; e0, e1: see conv6_launch_kernel
 template <int CFG, int SP>
-int launch6(qmri_ctx* ctx, const ConvLayer& L, int B, const PTensor& in, const PTensor& out, const PTensor* add1,
-            const PTensor* add2, int relu_out, int ksplit = 1, float* partial = nullptr, long out_ks = 0, const ProfSpan* span = nullptr) {
-    typedef Cfg6<CFG> C;
-    Conv6Args A;
-    A.in = in.fbase(); A.wp = reinterpret_cast<const uint4*>(L.wp6.p); A.out = out.fbase();
-    A.add1 = add1 ? add1->fbase() : nullptr; A.add2 = add2 ? add2->fbase() : nullptr;
-    A.in_blk = in.blk ? 1 : 0; A.out_blk = (out.blk && !partial) ? 1 : 0;       // (split-K partial sums are planar scratch)
-    if ((add1 && add1->blk != out.blk) || (add2 && add2->blk != out.blk) || (out.blk && L.Cout % 8 != 0)) {
-        qmri_set_error(ctx, "conv layer %d: residual operands and output must share one tensor format (blocked needs Cout %% 8 == 0)", L.index);
-        return QMRI_ERR_STATE;
-    }
-    A.Cout = L.Cout; A.W = in.W; A.H = in.H;
-    A.in_hp = in.hp; A.in_plane = (int)in.plane(); A.in_bs = (long)in.Cal * in.plane();
-    A.out_hp = out.hp; A.out_plane = (int)out.plane(); A.out_bs = (long)out.Cal * out.plane();
-    A.add1_bs = add1 ? (long)add1->Cal * add1->plane() : 0;
-    A.add2_bs = add2 ? (long)add2->Cal * add2->plane() : 0;
-    A.nchunk = L.nchunk6 / ksplit; A.nchunk_all = L.nchunk6; A.ksplit = ksplit; A.out_ks = out_ks; A.n_ct = L.n_ct6;
-    if (partial) { A.out = partial + (out.h0 - 1); A.add1 = A.add2 = nullptr; relu_out = 0; }   // raw partial sums; k_conv6_reduce finishes the layer
-    A.tiles_h = (in.H + C::TH - 1) / C::TH; A.tiles_w = (in.W + C::TW - 1) / C::TW;
-    A.relu_out = relu_out;
-    A.vec4 = (in.H % 4 == 0 && out.h0 % 4 == 0 && out.hp % 4 == 0 && (!add1 || (add1->h0 == out.h0 && add1->hp == out.hp)) &&
-              (!add2 || (add2->h0 == out.h0 && add2->hp == out.hp))) ? 1 : 0;
-    A.range_flag = ctx->net.d_range_flag;
-    A.am = conv6_act_slot(ctx, SP == 2 && !partial, L);             // (split-K partial sums are reported by k_conv6_reduce)
-    A.wt = qmri_knob(K_CONV_WT);
-    A.xcd = qmri_knob(K_CONV_XCD);
-    A.descale_hi = L.w6_descale; A.descale_lo = L.w6_descale * (1.f / LO_SCALE);
-    A.stamps = (unsigned long long*)ctx->net.d_stamps;
-    const int stamp_launch = qmri_knob(K_CONV_STAMP_LAUNCH);
-    A.launch_idx = g_conv6_launch_counter.fetch_add(1, std::memory_order_relaxed);
-    A.detail = (stamp_launch < 0 || A.launch_idx == stamp_launch) ? 1 : 0;
+int launch6(qmri_ctx* ctx, const Conv6Args& A, int grid, hipEvent_t e0, hipEvent_t e1) {
     const size_t lds = conv6_lds<CFG>(SP);
     if (!ctx->conv6_attr[CFG][SP - 2]) {
         QMRI_HIP(ctx, hipFuncSetAttribute((const void*)k_conv6<CFG, SP, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         QMRI_HIP(ctx, hipFuncSetAttribute((const void*)k_conv6<CFG, SP, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         ctx->conv6_attr[CFG][SP - 2] = true;
     }
-    const int grid = C::MH * A.n_ct * A.tiles_h * A.tiles_w * ksplit * B;
-    hipEvent_t e0 = nullptr, e1 = nullptr;                          // profile level 2 only: the launch's own dispatch timestamps
-    if (span && span->on) e0 = span->start;                         // (split-K: the layer's pair ends on its reduce launch)
-    else if (!span) QMRI_TRY(qmri_prof_pair(ctx, &e0, &e1, PROF_CONV3, conv_layer_flop(L, B, in.H, in.W)));
     if constexpr (SP == 2 && CFG < 2) {
         if (A.stamps) {                                             // knob conv_stamps: the diagnostic instantiation (tools/conv6_stamps.py)
-            if (in.blk) {
-                QMRI_HIP(ctx, hipFuncSetAttribute((const void*)k_conv6<CFG, SP, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                k_conv6<CFG, SP, true, true><<<dim3(grid), dim3(NT6), lds, ctx->stream>>>(A);
-            } else {
-                QMRI_HIP(ctx, hipFuncSetAttribute((const void*)k_conv6<CFG, SP, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                k_conv6<CFG, SP, false, true><<<dim3(grid), dim3(NT6), lds, ctx->stream>>>(A);
-            }
-            QMRI_HIP(ctx, hipGetLastError());
-            return QMRI_OK;
+            void (*const stamped)(const Conv6Args) = A.in_blk ? k_conv6<CFG, SP, true, true> : k_conv6<CFG, SP, false, true>;
+            QMRI_HIP(ctx, hipFuncSetAttribute((const void*)stamped, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            return conv6_launch_kernel(ctx, stamped, grid, lds, nullptr, nullptr, A);
         }
     }
-    if (in.blk) {
-        if (e0) hipExtLaunchKernelGGL((k_conv6<CFG, SP, true>), dim3(grid), dim3(NT6), (std::uint32_t)lds, ctx->stream, e0, e1, 0, A);
-        else k_conv6<CFG, SP, true><<<dim3(grid), dim3(NT6), lds, ctx->stream>>>(A);
-    } else {
-        if (e0) hipExtLaunchKernelGGL((k_conv6<CFG, SP, false>), dim3(grid), dim3(NT6), (std::uint32_t)lds, ctx->stream, e0, e1, 0, A);
-        else k_conv6<CFG, SP, false><<<dim3(grid), dim3(NT6), lds, ctx->stream>>>(A);
-    }
-    QMRI_HIP(ctx, hipGetLastError());
-    return QMRI_OK;
-}
-
-template <int CFG>
-int launch6(qmri_ctx* ctx, const ConvLayer& L, int B, const PTensor& in, const PTensor& out, const PTensor* add1,
-            const PTensor* add2, int relu_out, int ksplit = 1, float* partial = nullptr, long out_ks = 0, const ProfSpan* span = nullptr) {
-    if constexpr (CFG < 2) {
-        if (ksplit == 1 && !partial) {
-            bool done = false;
-            QMRI_TRY(conv6p_try(ctx, CFG, L, B, in, out, add1, add2, relu_out, &done));
-            if (done) return QMRI_OK;
-        }
-    }
-    return (L.sp6 == 2) ? launch6<CFG, 2>(ctx, L, B, in, out, add1, add2, relu_out, ksplit, partial, out_ks, span)
-                        : launch6<CFG, 3>(ctx, L, B, in, out, add1, add2, relu_out, ksplit, partial, out_ks, span);
+    return conv6_launch_kernel(ctx, A.in_blk ? k_conv6<CFG, SP, true> : k_conv6<CFG, SP, false>, grid, lds, e0, e1, A);
 }
 
 // split-K layers: out = relu(sum_k partial_k + add1 + add2), partial sums added in slice order.  VEC: four consecutive h per thread
@@ -706,16 +645,10 @@ int conv6_act_end(qmri_ctx* ctx) {
     return QMRI_OK;
 }
 
-bool conv6_enabled() {
-    const bool on = qmri_knob(K_CONV_F32) <= 0;
-    return on;
-}
+bool conv6_enabled() { return qmri_knob(K_CONV_F32) <= 0; }
 
 // operand splitting of the matrix-core path: 2 = f16 x 3 products (default), 3 = bf16 x 6 products (knob conv_scheme = 3)
-int conv6_default_sp() {
-    const int sp = (qmri_knob(K_CONV_SCHEME) == 3) ? 3 : 2;
-    return sp;
-}
+int conv6_default_sp() { return (qmri_knob(K_CONV_SCHEME) == 3) ? 3 : 2; }
 
 // The f16 scheme carries |w| up to the f16 maximum; larger weights (or non-finite ones) need the bf16 scheme.
 bool conv6_weights_fit_f16(const float* w, size_t n) {
@@ -791,81 +724,63 @@ int conv6_pack_dev(qmri_ctx* ctx, ConvLayer& L, const float* d_w, float wmax) {
     return QMRI_OK;
 }
 
+namespace {
+Conv6Operand conv6_operand(const PTensor* t) {
+    Conv6Operand o;
+    if (t) { o.on = true; o.blk = t->blk; o.h0 = t->h0; o.hp = t->hp; o.plane = (long)t->plane(); }
+    return o;
+}
+
+// k_conv6 in the form's tile configuration and the layer's scheme
+int conv6_run(qmri_ctx* ctx, const ConvLayer& L, const Conv6Args& A, const Conv6Form& form, hipEvent_t e0, hipEvent_t e1) {
+    return conv6_with_cfg(form.cfg, [&](auto cfg) {
+        constexpr int CFG = decltype(cfg)::value;
+        return (L.sp6 == 2) ? launch6<CFG, 2>(ctx, A, form.grid, e0, e1) : launch6<CFG, 3>(ctx, A, form.grid, e0, e1);
+    });
+}
+
+// split-K layers: the reduce kernel the form names finishes the layer from its partial sums; `stop`: the layer's profile pair ends here
+int conv6_reduce(qmri_ctx* ctx, const ConvLayer& L, int B, const PTensor& in, const PTensor& out, const PTensor* add1, const PTensor* add2, int relu_out,
+                 const Conv6Form& form, const float* partial, long out_ks, hipEvent_t stop) {
+    const long total = (long)B * L.Cout * in.H * in.W;
+    const bool blocked = form.reduce == CONV6_REDUCE_BLOCKED;
+    const auto kernel = blocked ? k_conv6_reduce_blk : (form.reduce == CONV6_REDUCE_FLOAT4) ? k_conv6_reduce<true> : k_conv6_reduce<false>;
+    const long threads = (form.reduce == CONV6_REDUCE_SCALAR) ? total : total / 4;   // one element, one float4 or one half-item each
+    hipExtLaunchKernelGGL(kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream, nullptr, stop, 0,
+                          partial + (out.h0 - 1), form.ksplit, out_ks, out.fbase(), (const float*)(add1 ? add1->fbase() : nullptr),
+                          (const float*)(add2 ? add2->fbase() : nullptr), add1 ? (long)add1->Cal * add1->plane() : 0L, add2 ? (long)add2->Cal * add2->plane() : 0L,
+                          (long)out.Cal * out.plane(), L.Cout, in.H, in.W, out.hp, (int)out.plane(), relu_out, blocked ? threads : total,
+                          (L.sp6 == 2) ? ctx->net.d_range_flag : (unsigned*)nullptr, conv6_act_slot(ctx, L.sp6 == 2, L));
+    QMRI_HIP(ctx, hipGetLastError());
+    return QMRI_OK;
+}
+}  // namespace
+
+// Every 3x3 layer of the matrix-core path: snapshot the knobs, describe the layer, let conv6_choose_form (conv6_form.h) decide, execute.
 int conv6_launch(qmri_ctx* ctx, const ConvLayer& L, int B, const PTensor& in, const PTensor& out, const PTensor* add1,
                  const PTensor* add2, int relu_out) {
-    // the largest pixel tile that still gives most CUs a workgroup (one workgroup per CU is the design point)
-    auto ntiles = [&](int th, int tw) { return (long)L.n_ct6 * ((in.H + th - 1) / th) * ((in.W + tw - 1) / tw) * B; };
-    // (tiles may overhang the image -- the kernel masks its stores -- as long as the padded area stays below 1.35 x the image)
-    auto waste = [&](int th, int tw) { return (double)(((in.H + th - 1) / th) * th) * (((in.W + tw - 1) / tw) * tw) / ((double)in.H * in.W); };
-    if (ntiles(16, 16) >= 160 && waste(16, 16) <= 1.35) return launch6<0>(ctx, L, B, in, out, add1, add2, relu_out);
-    if (ntiles(16, 8) >= 160 && waste(16, 8) <= 1.35) return launch6<1>(ctx, L, B, in, out, add1, add2, relu_out);
-    // Small feature maps with many channels (the 28 x 28 x 512 level): a 64-pixel tile would re-read the layer's weights
-    // once per tile (16 x 14 MB); instead keep the 256-pixel tile and split K over workgroups, then add the partial
-    // outputs in slice order (deterministic) in a second, elementwise kernel.
-    const bool splitk_on = qmri_knob(K_CONV_SPLITK) != 0;
-    // 56 x 56 level: tile config of the split-K variant (0, 1), 2 = no split.  With blocked tensors the unsplit 64-pixel tiles (196
-    // workgroups x 48 steps, no reduce launch) win: 696 vs 672 ADMM it/s on one box (round 2; with planar tensors split-K = 2 on
-    // 128-pixel tiles + a reduce kernel was the faster form)
-    // (3 = 128 pixels x 32 output channels, two workgroups per 64-row weight tile: half the weight bytes through LDS per MFMA of the
-    //  64-pixel tile -- these levels' steps are bound by LDS traffic, 4 fragment reads per 3 MFMAs and a full weight step written per
-    //  9 MFMAs of a wave: 743 -> 756 ADMM it/s with 3 / 3 / K over 4.  Measured and not kept on the way: one barrier per chunk instead
-    //  of per step (six A buffers, whole chunks requested two ahead): 18.3 vs 18.2 us per launch, the barriers are not the bound.)
-    const int mid_cfg = qmri_knob(K_CONV_MIDCFG);
-    const int deep_cfg_g = qmri_knob(K_CONV_DEEPCFG);              // (28 x 28 level, see below)
-    if (splitk_on && L.nchunk6 >= 16) {
-        // candidate: the 256-pixel tile (28 x 28 level) or the 128-pixel tile (56 x 56 level), K split so that about one
-        // workgroup per CU results and every workgroup still walks >= 4 chunks
-        // 28 x 28 level: tile config and largest K split.  Measured with blocked tensors on one box (ADMM it/s, two runs each):
-        // 256-pixel tiles x 8 slices (the round-1 choice) 701.6 | x 4: 695 | 128-pixel x 4: 715 | x 2: 695 | 64-pixel x 2: 717.6 | x 1: 679;
-        // then, on another box: 64-pixel x 2 (and 64-pixel unsplit at 56 x 56) 743 | configuration 3 at both levels, K over 2: 751.6 | over 4: 756
-        const int deep_cfg = deep_cfg_g;
-        const int deep_ks = qmri_knob(K_CONV_DEEPKS);
-        const bool deep = (long)in.H * in.W <= 32 * 32;          // (by pixel count: the same choice at square levels, one rule for H != W)
-        const int cfg = deep ? deep_cfg : mid_cfg;
-        const long nt = (cfg == 0) ? ntiles(16, 16) : (cfg == 1) ? ntiles(16, 8) : (cfg == 2) ? ntiles(8, 8) : 2 * ntiles(16, 8);
-        int ksplit = 1;
-        while ((deep || cfg < 2) && cfg >= 0 && ksplit * 2 * nt <= 256 && ksplit * 2 <= (deep ? deep_ks : 8) && L.nchunk6 % (ksplit * 2) == 0 &&
-               L.nchunk6 / (ksplit * 2) >= 4)
-            ksplit *= 2;
-        if (ksplit > 1 && (long)in.H * in.W <= 64 * 64) {
-            const long out_ks = (long)B * out.Cal * out.plane();
-            const size_t need = (size_t)ksplit * out_ks + 8192;
-            NetPlan& net = ctx->net;
-            QMRI_TRY(net.d_c6part.ensure(ctx, need));
-            // profile level 2: ONE unit per layer -- from the convolution's start to the end of the reduce kernel that completes it
-            ProfSpan span;
-            QMRI_TRY(qmri_prof_pair(ctx, &span.start, &span.stop, PROF_CONV3, conv_layer_flop(L, B, in.H, in.W)));
-            span.on = span.start != nullptr;
-            if (cfg == 0) QMRI_TRY(launch6<0>(ctx, L, B, in, out, nullptr, nullptr, 0, ksplit, net.d_c6part, out_ks, &span));
-            else if (cfg == 1) QMRI_TRY(launch6<1>(ctx, L, B, in, out, nullptr, nullptr, 0, ksplit, net.d_c6part, out_ks, &span));
-            else if (cfg == 2) QMRI_TRY(launch6<2>(ctx, L, B, in, out, nullptr, nullptr, 0, ksplit, net.d_c6part, out_ks, &span));
-            else QMRI_TRY(launch6<3>(ctx, L, B, in, out, nullptr, nullptr, 0, ksplit, net.d_c6part, out_ks, &span));
-            const long total = (long)B * L.Cout * in.H * in.W;
-            const bool vec = in.H % 4 == 0 && out.h0 % 4 == 0 && out.hp % 4 == 0 && (!add1 || (add1->h0 == out.h0 && add1->hp == out.hp)) &&
-                             (!add2 || (add2->h0 == out.h0 && add2->hp == out.hp));
-            if ((add1 && add1->blk != out.blk) || (add2 && add2->blk != out.blk) || (out.blk && L.Cout % 8 != 0)) {
-                qmri_set_error(ctx, "conv layer %d: residual operands and output must share one tensor format", L.index);
-                return QMRI_ERR_STATE;
-            }
-#define REDUCE_ARGS (const float*)(net.d_c6part + (out.h0 - 1)), ksplit, out_ks, out.fbase(), (const float*)(add1 ? add1->fbase() : nullptr),            \
-                (const float*)(add2 ? add2->fbase() : nullptr), add1 ? (long)add1->Cal * add1->plane() : 0L, add2 ? (long)add2->Cal * add2->plane() : 0L,   \
-                (long)out.Cal * out.plane(), L.Cout, in.H, in.W, out.hp, (int)out.plane(), relu_out, total,                                           \
-                (L.sp6 == 2) ? ctx->net.d_range_flag : (unsigned*)nullptr, conv6_act_slot(ctx, L.sp6 == 2, L)
-            hipEvent_t const r1 = span.on ? span.stop : nullptr;
-            if (out.blk) {
-                const long total_items = total / 4;             // half-items
-                hipExtLaunchKernelGGL(k_conv6_reduce_blk, dim3((unsigned)((total_items + 255) / 256)), dim3(256), 0, ctx->stream, nullptr, r1, 0,
-                    (const float*)(net.d_c6part + (out.h0 - 1)), ksplit, out_ks, out.fbase(), (const float*)(add1 ? add1->fbase() : nullptr),
-                    (const float*)(add2 ? add2->fbase() : nullptr), add1 ? (long)add1->Cal * add1->plane() : 0L, add2 ? (long)add2->Cal * add2->plane() : 0L,
-                    (long)out.Cal * out.plane(), L.Cout, in.H, in.W, out.hp, (int)out.plane(), relu_out, total_items,
-                    (L.sp6 == 2) ? ctx->net.d_range_flag : (unsigned*)nullptr, conv6_act_slot(ctx, L.sp6 == 2, L));
-            } else if (vec) hipExtLaunchKernelGGL(k_conv6_reduce<true>, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, ctx->stream, nullptr, r1, 0, REDUCE_ARGS);
-            else hipExtLaunchKernelGGL(k_conv6_reduce<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, nullptr, r1, 0, REDUCE_ARGS);
-#undef REDUCE_ARGS
-            QMRI_HIP(ctx, hipGetLastError());
-            return QMRI_OK;
-        }
+    const Conv6Knobs knobs = {qmri_knob(K_CONV_SPLITK), qmri_knob(K_CONV_PERSIST), qmri_knob(K_CONV_MIDCFG), qmri_knob(K_CONV_DEEPCFG), qmri_knob(K_CONV_DEEPKS)};
+    const Conv6Shape shape = {L.Cin, L.Cout, in.H, in.W, B, L.sp6, in.blk, conv6_operand(&out), conv6_operand(add1), conv6_operand(add2)};
+    const Conv6Form form = conv6_choose_form(shape, knobs, ctx->conv_ncu);
+    if (form.valid != CONV6_FORM_OK) {
+        qmri_set_error(ctx, "conv layer %d: residual operands and output must share one tensor format (blocked needs Cout %% 8 == 0)", L.index);
+        return QMRI_ERR_STATE;
     }
-    if (L.nchunk6 >= 16 && L.Cout % 64 == 0 && (((long)in.H * in.W <= 32 * 32) ? deep_cfg_g : mid_cfg) == 3) return launch6<3>(ctx, L, B, in, out, add1, add2, relu_out);
-    return launch6<2>(ctx, L, B, in, out, add1, add2, relu_out);
+    if (form.kernel == CONV6_KERNEL_CONV6P) return conv6p_launch(ctx, L, B, in, out, add1, add2, relu_out, form);
+    const int stamp_launch = qmri_knob(K_CONV_STAMP_LAUNCH);
+    float* partial = nullptr;
+    long out_ks = 0;
+    if (form.ksplit > 1) {
+        out_ks = (long)B * out.Cal * out.plane();
+        QMRI_TRY(ctx->net.d_c6part.ensure(ctx, (size_t)form.ksplit * out_ks + 8192));
+        partial = ctx->net.d_c6part;
+    }
+    Conv6Args A = conv6_args(ctx, L, B, in, out, add1, add2, relu_out, form, qmri_knob(K_CONV_WT), partial, out_ks);
+    A.detail = (stamp_launch < 0 || A.launch_idx == stamp_launch) ? 1 : 0;
+    // profile level 2: ONE unit per layer -- split-K: from the convolution's start to the end of the reduce kernel that completes it
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    QMRI_TRY(qmri_prof_pair(ctx, &e0, &e1, PROF_CONV3, conv_layer_flop(L, B, in.H, in.W)));
+    if (form.ksplit == 1) return conv6_run(ctx, L, A, form, e0, e1);
+    QMRI_TRY(conv6_run(ctx, L, A, form, e0, nullptr));
+    return conv6_reduce(ctx, L, B, in, out, add1, add2, relu_out, form, partial, out_ks, e1);
 }

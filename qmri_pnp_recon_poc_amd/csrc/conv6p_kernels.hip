@@ -24,7 +24,7 @@ namespace {
 // step, vmcnt(2 * NLOAD), stays exactly as in k_conv6: at that point at least 2 * NLOAD younger operations have been issued
 // (the operand requests of the two steps in between), and any epilogue load / store among them only makes the wait conservative.
 // The last tile of a workgroup is finished by all eight waves as in k_conv6.
-// Requirements (conv6_launch checks them, k_conv6 runs otherwise): f16 scheme, Cout % 64 == 0, nchunk even and >= 4, aligned
+// Requirements (conv6_choose_form, conv6_form.h, checks them; k_conv6 runs otherwise): f16 scheme, Cout % 64 == 0, nchunk even and >= 4, aligned
 // tensors (vec4), no split-K.
 // =====================================================================================================================
 struct Tile6 { int ct, oh0, ow0, b; };
@@ -417,79 +417,37 @@ __global__ __launch_bounds__(NT6) void k_conv6p(const Conv6Args A) {
     }
 }
 
-// persistent form (k_conv6p): one workgroup per CU walks the launch's tiles; returns QMRI_OK and sets *done when it ran
+// persistent form (k_conv6p): one workgroup per CU walks the launch's tiles
 template <int CFG, int NRES>
-int launch6p_t(qmri_ctx* ctx, const ConvLayer& L, int B, const PTensor& in, const PTensor& out, const PTensor* add1, const PTensor* add2,
-               int relu_out) {
-    typedef Cfg6<CFG> C;
-    Conv6Args A{};
-    A.in = in.fbase(); A.wp = reinterpret_cast<const uint4*>(L.wp6.p); A.out = out.fbase();   // (BLOCKED tensors: launch6p checks)
-    A.add1 = add1 ? add1->fbase() : nullptr; A.add2 = add2 ? add2->fbase() : nullptr;
-    A.in_blk = 1; A.out_blk = 1;
-    A.Cout = L.Cout; A.W = in.W; A.H = in.H;
-    A.in_hp = in.hp; A.in_plane = (int)in.plane(); A.in_bs = (long)in.Cal * in.plane();
-    A.out_hp = out.hp; A.out_plane = (int)out.plane(); A.out_bs = (long)out.Cal * out.plane();
-    A.add1_bs = add1 ? (long)add1->Cal * add1->plane() : 0;
-    A.add2_bs = add2 ? (long)add2->Cal * add2->plane() : 0;
-    A.nchunk = L.nchunk6; A.nchunk_all = L.nchunk6; A.ksplit = 1; A.out_ks = 0; A.n_ct = L.n_ct6;
-    A.tiles_h = (in.H + C::TH - 1) / C::TH; A.tiles_w = (in.W + C::TW - 1) / C::TW;
-    A.ntiles = A.n_ct * A.tiles_h * A.tiles_w * B;
-    A.relu_out = relu_out; A.vec4 = 1; A.wt = 1;
-    A.xcd = qmri_knob(K_CONV_XCD);
-    A.range_flag = ctx->net.d_range_flag;
-    A.am = conv6_act_slot(ctx, true, L);
-    A.descale_hi = L.w6_descale; A.descale_lo = L.w6_descale * (1.f / LO_SCALE);
-    const int stamp_launch = qmri_knob(K_CONV_STAMP_LAUNCH);
-    A.stamps = (unsigned long long*)ctx->net.d_stamps; A.launch_idx = g_conv6_launch_counter.fetch_add(1, std::memory_order_relaxed);
-    A.detail = (A.stamps && A.launch_idx == stamp_launch) ? 1 : 0;
+int launch6p(qmri_ctx* ctx, const ConvLayer& L, int B, const Conv6Args& A, int grid) {
+    constexpr size_t lds = conv6p_lds<CFG>();
     if (!ctx->conv6p_attr[CFG][NRES]) {
-        QMRI_HIP(ctx, hipFuncSetAttribute((const void*)k_conv6p<CFG, NRES, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)conv6p_lds<CFG>()));
-        QMRI_HIP(ctx, hipFuncSetAttribute((const void*)k_conv6p<CFG, NRES, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)conv6p_lds<CFG>()));
+        QMRI_HIP(ctx, hipFuncSetAttribute((const void*)k_conv6p<CFG, NRES, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        QMRI_HIP(ctx, hipFuncSetAttribute((const void*)k_conv6p<CFG, NRES, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         ctx->conv6p_attr[CFG][NRES] = true;
     }
-    const int grid = std::min(A.ntiles, ctx->conv_ncu);
-    if (A.detail) {                                                 // diagnostic build of the same kernel (tools/conv6p_stamps.py)
-        k_conv6p<CFG, NRES, true><<<dim3(grid), dim3(NT6), conv6p_lds<CFG>(), ctx->stream>>>(A);
-        QMRI_HIP(ctx, hipGetLastError());
-        return QMRI_OK;
-    }
+    if (A.detail) return conv6_launch_kernel(ctx, k_conv6p<CFG, NRES, true>, grid, lds, nullptr, nullptr, A);   // diagnostic build of the same kernel (tools/conv6p_stamps.py)
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    QMRI_TRY(qmri_prof_pair(ctx, &e0, &e1, PROF_CONV3, conv_layer_flop(L, B, in.H, in.W)));
-    if (e0) hipExtLaunchKernelGGL((k_conv6p<CFG, NRES, false>), dim3(grid), dim3(NT6), (std::uint32_t)conv6p_lds<CFG>(), ctx->stream, e0, e1, 0, A);
-    else k_conv6p<CFG, NRES, false><<<dim3(grid), dim3(NT6), conv6p_lds<CFG>(), ctx->stream>>>(A);
-    QMRI_HIP(ctx, hipGetLastError());
-    return QMRI_OK;
-}
-
-template <int CFG>
-int launch6p(qmri_ctx* ctx, const ConvLayer& L, int B, const PTensor& in, const PTensor& out, const PTensor* add1, const PTensor* add2,
-             int relu_out, bool* done) {
-    typedef Cfg6<CFG> C;
-    *done = false;
-    if (!qmri_knob(K_CONV_PERSIST) || L.sp6 != 2 || L.Cout % 64 != 0 || L.nchunk6 < 4 || L.nchunk6 % 2 != 0 || (add2 && !add1)) return QMRI_OK;
-    if (!in.blk || !out.blk || (add1 && !add1->blk) || (add2 && !add2->blk)) return QMRI_OK;      // k_conv6p is written for BLOCKED tensors
-    const bool same = (!add1 || (add1->h0 == out.h0 && add1->hp == out.hp && add1->plane() == out.plane())) &&
-                      (!add2 || (add2->h0 == out.h0 && add2->hp == out.hp && add2->plane() == out.plane()));
-    if (!same) return QMRI_OK;
-    if (!ctx->conv_ncu) {
-        hipDeviceProp_t prop;
-        QMRI_HIP(ctx, hipGetDeviceProperties(&prop, ctx->device));
-        ctx->conv_ncu = prop.multiProcessorCount;
-    }
-    const long ntiles = (long)L.n_ct6 * ((in.H + C::TH - 1) / C::TH) * ((in.W + C::TW - 1) / C::TW) * B;
-    if (ntiles <= ctx->conv_ncu) return QMRI_OK;                   // at most one tile per CU: nothing to pipeline, k_conv6 is the same work
-    *done = true;
-    if (add2) return launch6p_t<CFG, 2>(ctx, L, B, in, out, add1, add2, relu_out);
-    if (add1) return launch6p_t<CFG, 1>(ctx, L, B, in, out, add1, add2, relu_out);
-    return launch6p_t<CFG, 0>(ctx, L, B, in, out, add1, add2, relu_out);
+    QMRI_TRY(qmri_prof_pair(ctx, &e0, &e1, PROF_CONV3, conv_layer_flop(L, B, A.H, A.W)));
+    return conv6_launch_kernel(ctx, k_conv6p<CFG, NRES, false>, grid, lds, e0, e1, A);
 }
 
 }  // namespace
 
-int conv6p_try(qmri_ctx* ctx, int cfg, const ConvLayer& L, int B, const PTensor& in, const PTensor& out, const PTensor* add1, const PTensor* add2,
-               int relu_out, bool* done) {
-    *done = false;
-    if (cfg == 0) return launch6p<0>(ctx, L, B, in, out, add1, add2, relu_out, done);
-    if (cfg == 1) return launch6p<1>(ctx, L, B, in, out, add1, add2, relu_out, done);
-    return QMRI_OK;
+// conv6_choose_form (conv6_form.h) has checked what the kernel requires: BLOCKED tensors throughout (so vec4), write-through stores always
+int conv6p_launch(qmri_ctx* ctx, const ConvLayer& L, int B, const PTensor& in, const PTensor& out, const PTensor* add1, const PTensor* add2,
+                  int relu_out, const Conv6Form& form) {
+    Conv6Args A = conv6_args(ctx, L, B, in, out, add1, add2, relu_out, form, /* wt */ 1);
+    A.detail = (A.stamps && A.launch_idx == qmri_knob(K_CONV_STAMP_LAUNCH)) ? 1 : 0;
+    return conv6_with_cfg(form.cfg, [&](auto cfg) {
+        constexpr int CFG = decltype(cfg)::value;
+        if constexpr (CFG < 2) {
+            if (form.nres == 2) return launch6p<CFG, 2>(ctx, L, B, A, form.grid);
+            if (form.nres == 1) return launch6p<CFG, 1>(ctx, L, B, A, form.grid);
+            return launch6p<CFG, 0>(ctx, L, B, A, form.grid);
+        } else {
+            qmri_set_error(ctx, "conv layer %d: k_conv6p has no tile configuration %d", L.index, CFG);
+            return (int)QMRI_ERR_STATE;
+        }
+    });
 }

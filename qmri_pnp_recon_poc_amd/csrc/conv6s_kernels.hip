@@ -403,31 +403,17 @@ int conv6s_launch(qmri_ctx* ctx, const ConvLayer& L, int B, const PTensor& in, c
         qmri_set_error(ctx, "conv layer %d: input and output of a 2x2 layer must share one tensor format", L.index);
         return QMRI_ERR_STATE;
     }
-    A.in = in.fbase(); A.wp = reinterpret_cast<const uint4*>(L.wp6.p); A.out = out.fbase();
-    A.Cout = L.Cout;
+    conv6_fill_common(A, ctx, L, in, out);
     A.GH = up ? in.H : in.H / 2; A.GW = up ? in.W : in.W / 2;
-    A.in_hp = in.hp; A.in_plane = (int)in.plane(); A.in_bs = (long)in.Cal * in.plane();
-    A.out_hp = out.hp; A.out_plane = (int)out.plane(); A.out_bs = (long)out.Cal * out.plane();
-    A.nsteps = L.nchunk6; A.nsteps_real = L.nsteps6s; A.n_ct = L.n_ct6;
-    A.range_flag = ctx->net.d_range_flag;
+    A.nsteps = L.nchunk6; A.nsteps_real = L.nsteps6s;
     A.am = conv6_act_slot(ctx, L.sp6 == 2, L);
     A.wt = qmri_knob(K_CONV_WT);
-    A.xcd = qmri_knob(K_CONV_XCD);
-    A.descale_hi = L.w6_descale; A.descale_lo = L.w6_descale * (1.f / LO_SCALE);
     A.tiles_h = (A.GH + STH - 1) / STH; A.tiles_w = (A.GW + STW - 1) / STW;
     const int grid = A.n_ct * A.tiles_h * A.tiles_w * B;
     hipEvent_t e0 = nullptr, e1 = nullptr;                          // (profile level 2 only)
     QMRI_TRY(qmri_prof_pair(ctx, &e0, &e1, PROF_CONV2, conv_layer_flop(L, B, in.H, in.W)));
-#define LAUNCH6S_(KIND_, SP_, BLK_)                                                                              \
-    {                                                                                                            \
-        if (e0) hipExtLaunchKernelGGL((k_conv6s<KIND_, SP_, BLK_>), dim3(grid), dim3(NT6), (std::uint32_t)conv6s_lds(SP_), ctx->stream, e0, e1, 0, A); \
-        else k_conv6s<KIND_, SP_, BLK_><<<dim3(grid), dim3(NT6), conv6s_lds(SP_), ctx->stream>>>(A);             \
-    }
-#define LAUNCH6S(KIND_, SP_) { if (in.blk) LAUNCH6S_(KIND_, SP_, true) else LAUNCH6S_(KIND_, SP_, false) }
-    if (L.sp6 == 2) { if (up) LAUNCH6S(1, 2) else LAUNCH6S(0, 2) }
-    else { if (up) LAUNCH6S(1, 3) else LAUNCH6S(0, 3) }
-#undef LAUNCH6S
-#undef LAUNCH6S_
-    QMRI_HIP(ctx, hipGetLastError());
-    return QMRI_OK;
+#define KERNEL6S(SP_) (up ? (in.blk ? k_conv6s<1, SP_, true> : k_conv6s<1, SP_, false>) : (in.blk ? k_conv6s<0, SP_, true> : k_conv6s<0, SP_, false>))
+    if (L.sp6 == 2) return conv6_launch_kernel(ctx, KERNEL6S(2), grid, conv6s_lds(2), e0, e1, A);
+    return conv6_launch_kernel(ctx, KERNEL6S(3), grid, conv6s_lds(3), e0, e1, A);
+#undef KERNEL6S
 }

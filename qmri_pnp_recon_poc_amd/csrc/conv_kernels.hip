@@ -397,13 +397,8 @@ int launch_kind(qmri_ctx* ctx, ConvLayer& L, int B, const PTensor& in, const PTe
     A.stamps = stamps6 ? nullptr : (unsigned long long*)ctx->net.d_stamps;
     // persistent grid: exactly as many workgroups as are resident at once (measured occupancy x CU count)
     // (per context, not function-local statics: qmri_recon_batch runs one host thread + context per device)
-    int& ncu = ctx->conv_ncu;
+    const int ncu = ctx->conv_ncu;
     int* occ = ctx->conv_occ[(int)KIND];
-    if (!ncu) {
-        hipDeviceProp_t prop;
-        QMRI_HIP(ctx, hipGetDeviceProperties(&prop, ctx->device));
-        ncu = prop.multiProcessorCount;
-    }
     if (!occ[MT - 1]) {
         int nb = 0;
         if (MT == 2) QMRI_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_conv<(KIND == CONV_3X3N ? CONV_3X3N : CONV_3X3), 2>, NT, 0));

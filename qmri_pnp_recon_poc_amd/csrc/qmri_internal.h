@@ -47,7 +47,7 @@ void qmri_set_error(qmri_ctx* ctx, const char* fmt, ...);
 // ---------------------------------------------------------------------------------------------------
 // A/B and diagnostic switches ("knobs").  ONE environment variable, QMRI_DEBUG="name=value,name=value" (read once per process), and
 // one entry point, qmri_debug_knob(name, value) (include/qmri.h), set them; every default is the product's behaviour.  The table of
-// names and defaults is in api_core.cpp (g_knob_defs, same order as this enum).
+// names and defaults is in api_core.cpp (g_knob_defs; a static_assert there keeps it to this enum's entries and order).
 // ---------------------------------------------------------------------------------------------------
 enum QmriKnob {
     K_CONV_SCHEME,        // 2: f16 x 3 products (default), 3: bf16 x 6 products from the start
@@ -571,8 +571,8 @@ struct qmri_ctx {
     double last_call_wall_ms = 0;            // ... its host wall clock, entry to return (always)
     LlrState llr;                       // the regulariser of the PnP-ADMM loops' Step 2 while set (qmri_set_llr), else the network
     bool llr_lds_attr[3] = {false, false, false};   // large dynamic LDS allowed for k_llr_prox<4 | 8 | 16>
-    int conv_ncu = 0;                   // f32-MFMA conv kernels (conv_kernels.hip): CU count and resident workgroups per CU by (kind, MT)
-    int conv_occ[4][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};
+    int conv_ncu = 0;                   // CU count of the device (qmri_create)
+    int conv_occ[4][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};   // f32-MFMA conv kernels (conv_kernels.hip): resident workgroups per CU by (kind, MT)
 };
 
 OpDev qmri_opdev(const qmri_ctx* ctx);
@@ -645,10 +645,11 @@ int ew_launch_coil_sum(qmri_ctx* ctx, size_t n, size_t plane, int cnt, const dou
 int conv_launch(qmri_ctx* ctx, ConvLayer& L, int B, const PTensor& in, const PTensor& out, const PTensor* add1,
                 const PTensor* add2, int relu_out);
 int conv_cin_pad(ConvKind kind, int Cin);
-// bf16 x 6 path of the 3x3 layers (conv6_kernels.hip)
+// profile level 2: what an event pair times
 enum { PROF_CONV3 = 0, PROF_CONV2 = 1, PROF_LSQR = 2, PROF_TV = 3 };
 int qmri_prof_pair(qmri_ctx* ctx, hipEvent_t* start, hipEvent_t* stop, int kind = PROF_CONV3, double flop = 0.0);   // profile level 2: next event pair (else nullptrs)
 int qmri_prof_chain_finish(qmri_ctx* ctx, long count = -1);   // synchronises, adds the pairs' durations to the profile; count >= 0: only the first `count` pairs
+// 16-bit matrix-core path of the convolutions, f16 x 3 or bf16 x 6 products (conv6_kernels.hip; 2x2 / stride-2 layers: conv6s_kernels.hip)
 bool conv6_enabled();
 int conv6_act_begin(qmri_ctx* ctx, int nlayers);           // f16 scheme: start / finish the per-layer |output| report of a forward pass
 int conv6_act_end(qmri_ctx* ctx);
@@ -659,8 +660,8 @@ int conv6_pack_dev(qmri_ctx* ctx, ConvLayer& L, const float* d_w, float wmax);  
 int conv6s_pack_dev(qmri_ctx* ctx, ConvLayer& L, const float* d_w, float wmax);
 int conv_pack_weights_dev(qmri_ctx* ctx, ConvLayer& L, const float* d_w);           // ... the f32 A-fragments of the fallback kernels (allocates L.wp)
 int conv6_launch(qmri_ctx* ctx, const ConvLayer& L, int B, const PTensor& in, const PTensor& out, const PTensor* add1,
-                 const PTensor* add2, int relu_out);
-// a run of 3x3 layers of the full-resolution level as ONE launch with LDS-resident tiles (conv6_kernels.hip k_conv6r): nres = 2 nb ResBlock layers
+                 const PTensor* add2, int relu_out);           // every 3x3 layer; its launch form: conv6_form.h conv6_choose_form
+// a run of 3x3 layers of the full-resolution level as ONE launch with LDS-resident tiles (conv6r_kernels.hip k_conv6r): nres = 2 nb ResBlock layers
 // 64 -> 64 on src -> cur (+ skip at the last one), optionally with the network's head in front (head_in -> src)
 struct Conv6rRun {
     const ConvLayer* head = nullptr; const PTensor* head_in = nullptr;

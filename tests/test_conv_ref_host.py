@@ -1,12 +1,17 @@
 """CPU proofs behind tests/test_gpu_conv_layers.py: the fp64 restatement (tests/conv_ref.py) agrees with the oracle, the table's rows take
-the launch forms they name (by the restated launch rules), and every exact input family satisfies, shape by shape, the conditions under
-which its result does not depend on the order of summation."""
+the launch forms they name (by the restated launch rules, launch_form()), those restated rules give what the library's own decision
+function gives (conv6_choose_form of csrc/conv6_form.h, compiled for the host into tests/cpp/conv6_form_test.cpp), and every exact input
+family satisfies, shape by shape, the conditions under which its result does not depend on the order of summation."""
+import os
+import subprocess
+
 import numpy as np
 import pytest
 
 import conv_ref as R
 import test_gpu_conv_layers as G
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U = 2.0 ** -24
 
 
@@ -82,20 +87,79 @@ def test_rows_reach_the_forms_they_name(name, case, form):
     assert H * W * max(in_nc, out_nc) * B <= 64 * 64 * 64 * 17                                               # the largest input / output
 
 
+# (row, knob setting, the forms of the row's layers under it)
+KNOB_FORMS = [
+    ("splitk_512to128_16x16", "conv_midcfg=0,conv_deepcfg=0,conv_deepks=8", ["cfg0/ks8"]),
+    ("splitk_256to64_16x16", "conv_midcfg=0,conv_deepcfg=0,conv_deepks=8", ["cfg0/ks4"]),
+    ("cfg3_unsplit_256to64_40x40", "conv_midcfg=0,conv_deepcfg=0,conv_deepks=8", ["cfg0/ks4"]),
+    ("cfg3_unsplit_256to64_40x40", "conv_midcfg=1,conv_deepcfg=1", ["cfg1/ks4"]),
+    ("splitk_256to72_24x20", "conv_midcfg=1,conv_deepcfg=1", ["cfg1/ks4"]),
+    ("splitk_256to64_16x16", "conv_midcfg=2,conv_deepcfg=2,conv_deepks=2", ["cfg2/ks2"]),
+    ("cfg3_unsplit_256to64_40x40", "conv_midcfg=2,conv_deepcfg=2,conv_deepks=2", ["cfg2"]),
+    ("splitk_256to64_16x16", "conv_splitk=0", ["cfg3"]),
+    ("splitk_256to72_24x20", "conv_splitk=0", ["cfg2"]),                                  # (configuration 3 unsplit needs Cout % 64 == 0)
+    ("persistent_w64_64x64_B17", "conv_persist=0", ["cfg0", "cfg0", "cfg0"]),
+    ("splitk_blocked_w256_16x16", "", ["cfg2", "cfg3/ks4", "cfg3/ks4"]),
+]
+
+
 def test_knob_settings_select_other_forms():
-    """What the tile knobs do to the deep and mid rows (conv6_launch), so that the subprocess runs are known to run something else."""
-    forms = lambda name, s: [G.fmt_form(f) for f in G.case_forms(dict((c[0], c[1]) for c in G.CASES)[name], G.parse_knobs(s))]
-    assert forms("splitk_512to128_16x16", "conv_midcfg=0,conv_deepcfg=0,conv_deepks=8") == ["cfg0/ks8"]
-    assert forms("splitk_256to64_16x16", "conv_midcfg=0,conv_deepcfg=0,conv_deepks=8") == ["cfg0/ks4"]
-    assert forms("cfg3_unsplit_256to64_40x40", "conv_midcfg=0,conv_deepcfg=0,conv_deepks=8") == ["cfg0/ks4"]
-    assert forms("cfg3_unsplit_256to64_40x40", "conv_midcfg=1,conv_deepcfg=1") == ["cfg1/ks4"]
-    assert forms("splitk_256to72_24x20", "conv_midcfg=1,conv_deepcfg=1") == ["cfg1/ks4"]
-    assert forms("splitk_256to64_16x16", "conv_midcfg=2,conv_deepcfg=2,conv_deepks=2") == ["cfg2/ks2"]
-    assert forms("cfg3_unsplit_256to64_40x40", "conv_midcfg=2,conv_deepcfg=2,conv_deepks=2") == ["cfg2"]
-    assert forms("splitk_256to64_16x16", "conv_splitk=0") == ["cfg3"]
-    assert forms("splitk_256to72_24x20", "conv_splitk=0") == ["cfg2"]                     # (configuration 3 unsplit needs Cout % 64 == 0)
-    assert forms("persistent_w64_64x64_B17", "conv_persist=0") == ["cfg0", "cfg0", "cfg0"]
-    assert forms("splitk_blocked_w256_16x16", "") == ["cfg2", "cfg3/ks4", "cfg3/ks4"]
+    """What the tile knobs do to the deep and mid rows (conv6_choose_form), so that the subprocess runs are known to run something else."""
+    cases = dict((c[0], c[1]) for c in G.CASES)
+    for name, setting, forms in KNOB_FORMS:
+        assert [G.fmt_form(f) for f in G.case_forms(cases[name], G.parse_knobs(setting))] == forms, (name, setting)
+
+
+# ---- the restatement against the function the library calls ------------------------------------------------------------------------------------
+
+# the reduce kernel each split-K row's comment names (test_gpu_conv_layers.CASES); every other row has none
+ROW_REDUCE = {"splitk_256to64_16x16": "float4", "splitk_256to64_16x16_B2": "float4", "splitk_512to128_16x16": "float4", "splitk_512to128_16x16_B2": "float4",
+              "splitk_256to72_24x20": "float4", "splitk_256to72_24x20_B2": "float4", "splitk_256to64_18x14_scalar_reduce": "scalar",
+              "splitk_blocked_w256_16x16": "blocked"}
+REDUCE_KINDS = ["none", "scalar", "float4", "blocked"]
+
+
+def test_launch_form_restatement_follows_the_library(tmp_path):
+    """launch_form() (test_gpu_conv_layers.py) against conv6_choose_form (csrc/conv6_form.h), the function conv6_launch executes, through the
+    stand-alone program tests/cpp/conv6_form_test.cpp: every layer of every table row, under the default knobs and under every setting the
+    tests use, and a sweep of shapes around every threshold of the decision.  The program first checks by itself what launch_form() does
+    not model (residual operands, the format-mismatch code)."""
+    exe = tmp_path / "conv6_form_test"
+    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "qmri_pnp_recon_poc_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "cpp", "conv6_form_test.cpp"), "-o", str(exe)], check=True)
+    settings = [""] + sorted(set(G.LAYER_KNOBS) | set(s for _, s, _ in KNOB_FORMS if s))
+    rows = []                                                       # (cin, cout, H, W, B, blk, setting, table row or None)
+    for setting in settings:
+        for name, case, _ in G.CASES:
+            in_nc, out_nc, width, nb, H, W, B = case
+            shapes = R.seq_shapes(in_nc, out_nc, width, nb)
+            for i, (o, c, _, _) in enumerate(shapes):
+                blk = nb > 1 and width % 8 == 0 and 0 < i < len(shapes) - 1
+                rows.append((c, o, H, W, B, int(blk), setting, name if setting == "" and i == G.case_layer(case) else None))
+        sizes = [(n, n) for n in (9, 16, 17, 24, 28, 32, 40, 56, 64, 112, 224)] + [(17, 9), (24, 20), (18, 14), (40, 24)]
+        for cin in (10, 16, 64, 65, 80, 256, 512):
+            for cout in (10, 64, 72, 128, 256, 512):
+                for H, W in sizes:
+                    for B in (1, 2, 5, 15, 17, 30):
+                        for blk in (0, 1):
+                            if not (blk and cout % 8):              # (a blocked tensor holds whole channel blocks)
+                                rows.append((cin, cout, H, W, B, blk, setting, None))
+    knobs = {s: G.parse_knobs(s) for s in settings}
+    text = "".join("%d %d %d %d %d %d " % r[:6] + "%d %d %d %d %d %d\n" % tuple(
+        knobs[r[6]][k] for k in ("conv_splitk", "conv_persist", "conv_midcfg", "conv_deepcfg", "conv_deepks", "conv_scheme")) for r in rows)
+    r = subprocess.run([str(exe)], input=text, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    got = [tuple(map(int, ln.split())) for ln in r.stdout.splitlines()]
+    assert len(got) == len(rows) >= 40000
+    seen = set()
+    for row, (cfg, ks, persistent, reduce, vec4, grid) in zip(rows, got):
+        want = G.launch_form(*row[:5], bool(row[5]), knobs[row[6]])
+        assert (cfg, ks, bool(persistent)) == want, (row, (cfg, ks, persistent), want)
+        seen.add(want)
+        if row[7] is not None:
+            assert REDUCE_KINDS[reduce] == ROW_REDUCE.get(row[7], "none"), (row, REDUCE_KINDS[reduce])
+    # the sets reach every form there is: each configuration unsplit, both persistent ones, and K over 2, 4 and 8
+    assert {(c, 1, False) for c in range(4)} | {(0, 1, True), (1, 1, True)} <= seen and {f[1] for f in seen} == {1, 2, 4, 8}
 
 
 # ---- the exact families, shape by shape -----------------------------------------------------------------------------------------------------

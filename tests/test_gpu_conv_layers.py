@@ -4,8 +4,10 @@ The end-to-end parity tests (test_gpu_net.py, test_gpu_grids.py) judge a forward
 wrong halo pixel, a lost cross term of the f16 x 3 split in one pixel block or a wrong small-valued channel passes them.  Here
 
 * QMRI_ARCH_SEQ_CONV with nb = 1 is exactly one bias-free 3x3 convolution, with nb = 3 it adds ReLU and blocked interior tensors: the table
-  CASES reaches each branch of conv6_launch / launch6p in isolation at the smallest shape that takes it (launch_form() restates those
-  branches; tests/test_conv_ref_host.py checks the table against it without a GPU);
+  CASES reaches each branch of conv6_choose_form (csrc/conv6_form.h, the function conv6_launch executes) in isolation at the smallest shape
+  that takes it.  launch_form() restates those branches, because the forms are needed here without the library's source at hand and as an
+  independent statement; tests/test_conv_ref_host.py checks, without a GPU, the table against launch_form() and launch_form() against
+  conv6_choose_form itself, compiled for the host, on every row, every knob setting below and a sweep of shapes;
 * the inputs come from families whose exact result does not depend on the order of summation (conv_ref: I small integers, A coarse weights x
   fine activations, B fine weights x coarse activations; the host test proves the premises shape by shape), so the assertion is equality of
   bits -- np.array_equal for I, bits == float32(exact fp64 value) for A and B on forms that round once;
@@ -62,7 +64,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U = 2.0 ** -24
 
-# ---- conv6_launch / launch6p restated (conv6_kernels.hip, conv6p_kernels.hip), so that a row can be checked against the code without a GPU -------
+# ---- conv6_choose_form restated (csrc/conv6_form.h; held against it by tests/test_conv_ref_host.py), so that a row names its form without a GPU ----
 
 KNOB_DEFAULTS = dict(conv_splitk=1, conv_persist=1, conv_midcfg=3, conv_deepcfg=3, conv_deepks=4, conv_f32=0, conv_scheme=2)
 TILE = {0: (16, 16), 1: (16, 8), 2: (8, 8), 3: (16, 8)}
@@ -87,7 +89,7 @@ def launch_form(cin, cout, H, W, B, blk, knobs=KNOB_DEFAULTS):
     def waste(th, tw):
         return (-(-H // th) * th) * (-(-W // tw) * tw) / (H * W)
 
-    def persistent(cfg):                                            # launch6p: f16 scheme, blocked tensors, more tiles than CUs
+    def persistent(cfg):                                            # k_conv6p: f16 scheme, blocked tensors, more tiles than CUs
         return bool(knobs["conv_persist"] and knobs["conv_scheme"] == 2 and cout % 64 == 0 and nchunk >= 4 and nchunk % 2 == 0 and blk and
                     ntiles(*TILE[cfg]) > NCU)
 
@@ -126,11 +128,11 @@ def fmt_form(f):
 # ---- the table: (id, (in_nc, out_nc, width, nb, H, W, B), the form of the layer the row is about under the default knobs) ------------------------
 # n_ct = ceil(Cout / 64) weight tiles, nchunk = ceil(Cin / 16) K chunks; ntiles(th, tw) = n_ct * ceil(H / th) * ceil(W / tw) * B.
 CASES = [
-    # 1 * 4 * 4 * 10 = 160 tiles of 16 x 16, no overhang: the first branch of conv6_launch, launch6<0>; planar in and out so not persistent
+    # 1 * 4 * 4 * 10 = 160 tiles of 16 x 16, no overhang: the first branch of conv6_choose_form, configuration 0; planar in and out so not persistent
     ("cfg0_16to64_64x64_B10", (16, 64, 64, 1, 64, 64, 10), "cfg0"),
-    # B = 5: 80 tiles of 16 x 16 (< 160), 1 * 4 * 8 * 5 = 160 of 16 x 8: second branch, launch6<1>
+    # B = 5: 80 tiles of 16 x 16 (< 160), 1 * 4 * 8 * 5 = 160 of 16 x 8: second branch, configuration 1
     ("cfg1_16to64_64x64_B5", (16, 64, 64, 1, 64, 64, 5), "cfg1"),
-    # few tiles and nchunk = 1 < 16: neither split-K nor configuration 3, the last line, launch6<2>; H % 4 == 0: float4 epilogue, 24 = 3 tiles of 8
+    # few tiles and nchunk = 1 < 16: neither split-K nor configuration 3, the last line, configuration 2; H % 4 == 0: float4 epilogue, 24 = 3 tiles of 8
     ("cfg2_16to16_24x24", (16, 16, 16, 1, 24, 24, 1), "cfg2"),
     # H = 17: vec4 = 0, the scalar epilogue; 17 x 9 leaves ragged 8 x 8 tiles in both directions
     ("cfg2_16to16_17x9_scalar_epilogue", (16, 16, 16, 1, 17, 9, 1), "cfg2"),
@@ -139,7 +141,7 @@ CASES = [
     ("cfg2_10to10_32x32_narrow", (10, 10, 16, 1, 32, 32, 1), "cfg2"),
     ("cfg2_11to10_32x32_narrow", (11, 10, 16, 1, 32, 32, 1), "cfg2"),
     # nchunk = 16, 256 px <= 32 * 32: deep, conv_deepcfg = 3, nt = 2 * ntiles(16, 8) = 4 B; K over 2 and 4 pass (4 <= conv_deepks, 16 / 4 = 4 chunks
-    # each), 8 does not: launch6<3> with ksplit = 4 into planar partials, k_conv6_reduce<true> (H % 4 == 0, planar output)
+    # each), 8 does not: configuration 3 with ksplit = 4 into planar partials, k_conv6_reduce<true> (H % 4 == 0, planar output)
     ("splitk_256to64_16x16", (256, 64, 64, 1, 16, 16, 1), "cfg3/ks4"),
     ("splitk_256to64_16x16_B2", (256, 64, 64, 1, 16, 16, 2), "cfg3/ks4"),
     # nchunk = 32, n_ct = 2: nt = 8 B, K over 4 (conv_deepks)
@@ -151,8 +153,8 @@ CASES = [
     ("splitk_256to72_24x20_B2", (256, 72, 64, 1, 24, 20, 2), "cfg3/ks4"),
     # H = 18: k_conv6_reduce<false>, the scalar reduce, and the scalar epilogue of the partial stores
     ("splitk_256to64_18x14_scalar_reduce", (256, 64, 64, 1, 18, 14, 1), "cfg3/ks4"),
-    # 1600 px > 32 * 32: the mid level, conv_midcfg = 3; the split loop needs deep or cfg < 2, so ksplit stays 1 and the line before last takes
-    # launch6<3> unsplit (nchunk >= 16, Cout % 64 == 0)
+    # 1600 px > 32 * 32: the mid level, conv_midcfg = 3; the split loop needs deep or cfg < 2, so ksplit stays 1 and the unsplit rule takes
+    # configuration 3 (nchunk >= 16, Cout % 64 == 0)
     ("cfg3_unsplit_256to64_40x40", (256, 64, 64, 1, 40, 40, 1), "cfg3"),
     # the narrow / wide boundary (Cin <= 64 renames the layer) and K tails: nchunk = 4, 5, 5, 5 with 1, 8 and 16 channels in the last chunk
     ("cfg2_64to64_32x32", (64, 64, 64, 1, 32, 32, 1), "cfg2"),
@@ -160,13 +162,13 @@ CASES = [
     ("cfg2_72to64_32x32", (72, 64, 64, 1, 32, 32, 1), "cfg2"),
     ("cfg2_80to64_32x32", (80, 64, 64, 1, 32, 32, 1), "cfg2"),
     # nb = 3: planar -> blocked, blocked -> blocked, blocked -> planar.  Middle layer: 1 * 4 * 4 * 17 = 272 tiles of 16 x 16 > 256 CUs, nchunk = 4
-    # (even, >= 4), Cout % 64 == 0, blocked: launch6p<0>, 16 workgroups walk two tiles
+    # (even, >= 4), Cout % 64 == 0, blocked: k_conv6p on configuration 0, 16 workgroups walk two tiles
     ("persistent_w64_64x64_B17", (16, 64, 64, 3, 64, 64, 17), "cfg0/persistent"),
     # width 128: n_ct = 2, 2 * 16 * 9 = 288 tiles, nchunk = 8
     ("persistent_w128_64x64_B9", (16, 64, 128, 3, 64, 64, 9), "cfg0/persistent"),
-    # the one-launch-per-layer kernel with blocked tensors on the same tiles: 160 tiles of 16 x 16 are not more than the CUs, so launch6p declines
+    # the one-launch-per-layer kernel with blocked tensors on the same tiles: 160 tiles of 16 x 16 are not more than the CUs, so k_conv6 runs
     ("cfg0_blocked_w64_64x64_B10", (16, 64, 64, 3, 64, 64, 10), "cfg0"),
-    # ... and 160 tiles of 16 x 8 (80 of 16 x 16): launch6<1>, blocked in and out -- the form of the 112 x 112 level of a one-slice 224 x 224 pass
+    # ... and 160 tiles of 16 x 8 (80 of 16 x 16): configuration 1, blocked in and out -- the form of the 112 x 112 level of a one-slice 224 x 224 pass
     ("cfg1_blocked_w64_64x64_B5", (16, 64, 64, 3, 64, 64, 5), "cfg1"),
     # configuration 3 unsplit with blocked tensors (the 56 x 56 level's form): middle layer 256 -> 256 at 40 x 40, n_ct = 4, two workgroups per weight tile
     ("cfg3_blocked_w256_40x40", (16, 16, 256, 3, 40, 40, 1), "cfg3"),
