@@ -112,7 +112,7 @@ extern "C" int qmri_adjoint_w(qmri_ctx* ctx, const void* y, void* x) {
     return QMRI_OK;
 }
 
-// qmri_adjoint_mc (api_core.cpp) with the weighted spreading
+// qmri_adjoint_mc (api_operator.cpp) with the weighted spreading
 extern "C" int qmri_adjoint_w_mc(qmri_ctx* ctx, const void* y, void* x) {
     QMRI_TRY(require_trajectory(ctx, "qmri_adjoint_w_mc"));
     QMRI_CHECK_ARG(ctx, x && y, "x / y must not be NULL");

@@ -48,11 +48,6 @@ void deapodisation(int L, int w, double beta, double* out) {
     }
 }
 
-template <typename T> int nu_upload(qmri_ctx* ctx, T** p, const std::vector<T>& v) {
-    QMRI_TRY(ctx->op.pool.alloc(ctx, p, v.size()));
-    if (!v.empty()) QMRI_HIP(ctx, hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return QMRI_OK;
-}
 inline int wrap(int k, int G) { k %= G; return k < 0 ? k + G : k; }
 }  // namespace
 
@@ -192,18 +187,19 @@ extern "C" int qmri_set_operator_nufft(qmri_ctx* ctx, int N, int M, int s, int T
     for (int j = 0; j < M; ++j) { const double a = 2.0 * PI * j / M; tw[(size_t)N + j] = make_double2(std::cos(a), -std::sin(a)); }
 
     const size_t n = (size_t)N * M * s, B = (size_t)max_batch;
-    QMRI_TRY(nu_upload(ctx, &o.d_Vt, Vt));
-    QMRI_TRY(nu_upload(ctx, &o.d_tw, tw));
-    QMRI_TRY(nu_upload(ctx, &h.d_u, su));
-    QMRI_TRY(nu_upload(ctx, &h.d_ph, sph));
-    QMRI_TRY(nu_upload(ctx, &h.d_t, st));
-    QMRI_TRY(nu_upload(ctx, &h.d_perm, sperm));
-    QMRI_TRY(nu_upload(ctx, &h.d_list, list));
-    QMRI_TRY(nu_upload(ctx, &h.d_seg, segs));
-    QMRI_TRY(nu_upload(ctx, &h.d_red, reds));
-    QMRI_TRY(nu_upload(ctx, &h.d_dp, dp));
-    QMRI_TRY(nu_upload(ctx, &h.d_r, ramp));
-    QMRI_TRY(nu_upload(ctx, &h.d_ones, std::vector<double2>((size_t)N * M, make_double2(1.0, 0.0))));
+    QMRI_TRY(o.pool.upload(ctx, &o.d_Vt, Vt.data(), Vt.size()));
+    QMRI_TRY(o.pool.upload(ctx, &o.d_tw, tw.data(), tw.size()));
+    QMRI_TRY(o.pool.upload(ctx, &h.d_u, su.data(), su.size()));
+    QMRI_TRY(o.pool.upload(ctx, &h.d_ph, sph.data(), sph.size()));
+    QMRI_TRY(o.pool.upload(ctx, &h.d_t, st.data(), st.size()));
+    QMRI_TRY(o.pool.upload(ctx, &h.d_perm, sperm.data(), sperm.size()));
+    QMRI_TRY(o.pool.upload(ctx, &h.d_list, list.data(), list.size()));
+    QMRI_TRY(o.pool.upload(ctx, &h.d_seg, segs.data(), segs.size()));
+    QMRI_TRY(o.pool.upload(ctx, &h.d_red, reds.data(), reds.size()));
+    QMRI_TRY(o.pool.upload(ctx, &h.d_dp, dp.data(), dp.size()));
+    QMRI_TRY(o.pool.upload(ctx, &h.d_r, ramp.data(), ramp.size()));
+    const std::vector<double2> ones((size_t)N * M, make_double2(1.0, 0.0));
+    QMRI_TRY(o.pool.upload(ctx, &h.d_ones, ones.data(), ones.size()));
     QMRI_TRY(o.pool.alloc(ctx, &h.d_g, 4 * B * n));
     QMRI_TRY(o.pool.alloc(ctx, &h.d_grid, 4 * B * n));
     QMRI_TRY(o.pool.alloc(ctx, &h.d_part, B * std::max(nslot, 1) * (size_t)s * 256));

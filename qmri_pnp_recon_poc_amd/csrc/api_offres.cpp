@@ -17,13 +17,6 @@ constexpr int OFFRES_NLMAX = 32;          // segments of the field-aware normal 
 constexpr double OFFRES_TOL_DEF = 1e-4;
 typedef std::complex<double> cplx;
 
-// a host array into a device buffer that lives as long as `pool` (one call)
-template <typename T> int upload(qmri_ctx* ctx, DevPool& pool, T** d, const T* src, size_t count) {
-    QMRI_TRY(pool.alloc(ctx, d, count));
-    QMRI_HIP(ctx, hipMemcpy(*d, src, count * sizeof(T), hipMemcpyHostToDevice));
-    return QMRI_OK;
-}
-
 // lower Cholesky factor (row-major, in place) of the Hermitian positive definite A [L][L]; false on a pivot that is not positive
 bool cholesky(std::vector<cplx>& A, int L) {
     for (int r = 0; r < L; ++r) {
@@ -143,9 +136,9 @@ extern "C" int qmri_set_field_map(qmri_ctx* ctx, const double* f_hz, const doubl
     }
     DevPool tmp;
     double* d_f = nullptr; double* d_ts = nullptr; double2* d_hist = nullptr;
-    QMRI_TRY(upload(ctx, tmp, &d_f, f_hz, plane));
-    QMRI_TRY(upload(ctx, tmp, &d_ts, t_s, (size_t)o.m));
-    QMRI_TRY(upload(ctx, tmp, &d_hist, hist.data(), hist.size()));
+    QMRI_TRY(tmp.upload(ctx, &d_f, f_hz, plane));
+    QMRI_TRY(tmp.upload(ctx, &d_ts, t_s, (size_t)o.m));
+    QMRI_TRY(tmp.upload(ctx, &d_hist, hist.data(), hist.size()));
     const int L_first = constant ? 1 : (nseg ? nseg : 2), L_last = constant ? 1 : (nseg ? nseg : OFFRES_LMAX);
     QMRI_TRY(h.d_bl.ensure(ctx, (size_t)L_last * o.m));           // (sized here, at attach time: auto mode for its largest L)
     OffresFit fit{0.0, 0.0};
@@ -169,8 +162,8 @@ extern "C" int qmri_set_field_map(qmri_ctx* ctx, const double* f_hz, const doubl
         for (size_t i = 0; i < A.size(); ++i) Cd[i] = make_double2(A[i].real(), A[i].imag());
         DevPool per;
         double2* d_G = nullptr; double2* d_C = nullptr;
-        QMRI_TRY(upload(ctx, per, &d_G, Gd.data(), Gd.size()));
-        QMRI_TRY(upload(ctx, per, &d_C, Cd.data(), Cd.size()));
+        QMRI_TRY(per.upload(ctx, &d_G, Gd.data(), Gd.size()));
+        QMRI_TRY(per.upload(ctx, &d_C, Cd.data(), Cd.size()));
         QMRI_TRY(offres_coefficients_dev(ctx, L, nbins, constant, d_hist, d_G, d_C, d_ts, f0, h.d_bl, &fit));
         reached = fit.fit_max <= tol;
         if (reached || L == L_last) break;
@@ -178,7 +171,7 @@ extern "C" int qmri_set_field_map(qmri_ctx* ctx, const double* f_hz, const doubl
     // the phase maps of the chosen segments, [L][N*M]
     QMRI_TRY(h.d_pm.ensure(ctx, (size_t)L * plane));
     double* d_tau = nullptr;
-    QMRI_TRY(upload(ctx, tmp, &d_tau, tauhat.data(), tauhat.size()));
+    QMRI_TRY(tmp.upload(ctx, &d_tau, tauhat.data(), tauhat.size()));
     QMRI_TRY(offres_phase_maps_dev(ctx, L, plane, d_f, f0, d_tau, h.d_pm));
     QMRI_HIP(ctx, hipDeviceSynchronize());          // (as qmri_set_operator: everything has landed before the context's stream reads it)
     h.fm_L = L;
@@ -244,8 +237,8 @@ extern "C" int qmri_nufft_prepare_normal_fm(qmri_ctx* ctx, const qmri_offres_nor
     DevPool tmp;
     double* d_ts = nullptr; double2* d_dh = nullptr; double* d_c = nullptr;
     const int L_first = nseg ? nseg : 2, L_last = nseg ? nseg : OFFRES_NLMAX;
-    QMRI_TRY(upload(ctx, tmp, &d_ts, h.fm_ts.data(), h.fm_ts.size()));
-    QMRI_TRY(upload(ctx, tmp, &d_dh, dh.data(), dh.size()));
+    QMRI_TRY(tmp.upload(ctx, &d_ts, h.fm_ts.data(), h.fm_ts.size()));
+    QMRI_TRY(tmp.upload(ctx, &d_dh, dh.data(), dh.size()));
     QMRI_TRY(tmp.alloc(ctx, &d_c, (size_t)L_last * o.m));
     // the tables of one tried L', allocated once at the largest L' of the search
     double2* d_G = nullptr; double2* d_Qw = nullptr; double* d_U = nullptr;
@@ -298,8 +291,8 @@ extern "C" int qmri_nufft_prepare_normal_fm(qmri_ctx* ctx, const qmri_offres_nor
     QMRI_TRY(pm.ensure(ctx, (size_t)L * plane));
     QMRI_TRY(xs.ensure(ctx, (size_t)o.maxB * n));
     double* d_f = nullptr; double* d_tau = nullptr;
-    QMRI_TRY(upload(ctx, tmp, &d_f, h.fm_f.data(), h.fm_f.size()));
-    QMRI_TRY(upload(ctx, tmp, &d_tau, tauhat.data(), tauhat.size()));
+    QMRI_TRY(tmp.upload(ctx, &d_f, h.fm_f.data(), h.fm_f.size()));
+    QMRI_TRY(tmp.upload(ctx, &d_tau, tauhat.data(), tauhat.size()));
     QMRI_TRY(offres_phase_maps_dev(ctx, L, plane, d_f, h.fm_f0, d_tau, pm.p));
     for (int l = 0; l < L; ++l) QMRI_TRY(toep_build_weighted(ctx, d_c + (size_t)l * o.m, khat.p + (size_t)l * kseg));
     QMRI_HIP(ctx, hipDeviceSynchronize());

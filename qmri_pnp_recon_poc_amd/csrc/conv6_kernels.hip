@@ -761,7 +761,7 @@ int conv6_launch(qmri_ctx* ctx, const ConvLayer& L, int B, const PTensor& in, co
                  const PTensor* add2, int relu_out) {
     const Conv6Knobs knobs = {qmri_knob(K_CONV_SPLITK), qmri_knob(K_CONV_PERSIST), qmri_knob(K_CONV_MIDCFG), qmri_knob(K_CONV_DEEPCFG), qmri_knob(K_CONV_DEEPKS)};
     const Conv6Shape shape = {L.Cin, L.Cout, in.H, in.W, B, L.sp6, in.blk, conv6_operand(&out), conv6_operand(add1), conv6_operand(add2)};
-    const Conv6Form form = conv6_choose_form(shape, knobs, ctx->conv_ncu);
+    const Conv6Form form = conv6_choose_form(shape, knobs, ctx->ncu);
     if (form.valid != CONV6_FORM_OK) {
         qmri_set_error(ctx, "conv layer %d: residual operands and output must share one tensor format (blocked needs Cout %% 8 == 0)", L.index);
         return QMRI_ERR_STATE;

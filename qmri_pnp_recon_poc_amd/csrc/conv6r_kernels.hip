@@ -797,7 +797,7 @@ int conv6r_try(qmri_ctx* ctx, const Conv6rRun& run, int B, bool* done) {
     if (src.H % 16 || src.W % 16) return QMRI_OK;
     if ((size_t)src.Cal * src.plane() * 4 >= ((size_t)1 << 31)) return QMRI_OK;       // (32-bit byte offsets)
     const int tiles_h = src.H / 16, tiles_w = src.W / 16, tiles = tiles_h * tiles_w;
-    if (tiles > ctx->conv_ncu || tiles != net.res_tiles) return QMRI_OK;               // every workgroup must be resident: one per CU
+    if (tiles > ctx->ncu || tiles != net.res_tiles) return QMRI_OK;               // every workgroup must be resident: one per CU
     Conv6rArgs A{};
     A.src = run.head ? run.head_in->fbase() : src.fbase();
     A.in_planar = run.head ? 1 : 0; A.in_plane = run.head ? (int)run.head_in->plane() : 0;

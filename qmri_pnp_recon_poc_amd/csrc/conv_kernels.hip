@@ -397,7 +397,7 @@ int launch_kind(qmri_ctx* ctx, ConvLayer& L, int B, const PTensor& in, const PTe
     A.stamps = stamps6 ? nullptr : (unsigned long long*)ctx->net.d_stamps;
     // persistent grid: exactly as many workgroups as are resident at once (measured occupancy x CU count)
     // (per context, not function-local statics: qmri_recon_batch runs one host thread + context per device)
-    const int ncu = ctx->conv_ncu;
+    const int ncu = ctx->ncu;
     int* occ = ctx->conv_occ[(int)KIND];
     if (!occ[MT - 1]) {
         int nb = 0;

@@ -83,7 +83,16 @@ struct DevPool {
         if (st == QMRI_OK) recs.push_back({q, std::max<size_t>(count, 1) * mem_esize<T>()});
         return st;
     }
-    void free_one(const void* ptr) {                 // a member that is replaced on its own
+    // alloc(), then a blocking copy of the host array data[count] into it (count == 0: nothing to copy)
+    template <typename T> int upload(qmri_ctx* ctx, T** ptr, const std::remove_const_t<T>* data, size_t count) {     // (T may be const: a plan's read-only view)
+        const int st = alloc(ctx, ptr, count);
+        if (st != QMRI_OK || count == 0) return st;
+        const hipError_t e = hipMemcpy((void*)*ptr, data, count * sizeof(T), hipMemcpyHostToDevice);
+        if (e == hipSuccess) return QMRI_OK;
+        qmri_set_error(ctx, "hipMemcpy of %zu bytes to the device failed: %s (%s:%d)", count * sizeof(T), hipGetErrorString(e), __FILE__, __LINE__);
+        return QMRI_ERR_HIP;
+    }
+    void free_one(const void* ptr) {                // a member that is replaced on its own
         for (size_t i = 0; ptr && i < recs.size(); ++i)
             if (recs[i].p == ptr) { mem_free(false, recs[i].p, recs[i].bytes); recs.erase(recs.begin() + (long)i); return; }
     }

@@ -36,7 +36,7 @@ namespace {
 
 constexpr int KT = 256;          // threads of every kernel in this file
 // Capacities of a work unit (round 5): the iteration kernels are instantiated for three shapes of unit, chosen when the operator is planned
-// (api_core.cpp, KS_CAPS in qmri_internal.h) so that a single slice's units fit the chip at once and the one-launch iteration applies:
+// (ks_plan_units, KS_CAPS in op_plan.h) so that a single slice's units fit the chip at once and the one-launch iteration applies:
 //   0  64 slots x 1024 samples   the spiral masks of cut1 ... cut3 (11 051 sampled k, ~11 samples each at T = 200): ~250 units
 //   1  256 slots x  768 samples  masks that sample EVERY k a few times (EPI: 50 176 k x 2.7 samples): 196 - 250 units instead of 784
 //   2  64 slots x 2560 samples   few k, many samples each (spiral cut0, T = 1000: 56 per k): ~248 units instead of 604
@@ -54,7 +54,7 @@ typedef KsCaps<3, 64, 256, 4, 1> Caps3;
 template <class CP> constexpr bool caps_ok() {
     return CP::SCAP == KS_CAPS[CP::ID].scap && CP::ECAP == KS_CAPS[CP::ID].ecap && CP::GCAP == KS_CAPS[CP::ID].gcap && CP::SL == KS_CAPS[CP::ID].sl && CP::GCAPB == KS_CAPS[CP::ID].gcapb;
 }
-static_assert(caps_ok<Caps0>() && caps_ok<Caps1>() && caps_ok<Caps2>() && caps_ok<Caps3>(), "unit shapes: host table (qmri_internal.h KS_CAPS)");
+static_assert(caps_ok<Caps0>() && caps_ok<Caps1>() && caps_ok<Caps2>() && caps_ok<Caps3>(), "unit shapes: host table (op_plan.h KS_CAPS)");
 // sum over the SL lanes that share a scatter group (SL = 8: fixed DPP tree; SL = 1: the lane's own sum)
 template <int SL> __device__ __forceinline__ double group_sum(double v) { if constexpr (SL == 8) return group8_sum(v); else return v; }
 constexpr int NVQ = 8;                                     // V values per thread requested up front (8 * 256 = 2048)

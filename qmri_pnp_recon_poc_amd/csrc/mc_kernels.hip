@@ -3,7 +3,7 @@
 // The reference simulates a single coil (README.md:63) and has no multi-coil operator, so nothing here has a reference counterpart and nothing can pin
 // it: PARITY UNPINNED, stated in include/qmri.h and in the oracle's restatement.  What it generalises is the one line PnP_ADMM.m:102
 //     x = lsqr(@afun, [y; sqrt(r) z], cg_tol, cg_iter, [], [], x0),   afun: B = [A; sqrt(r) I]  (PnP_ADMM.m:153-171)
-// with A replaced by the SENSE operator of api_core.cpp (qmri_forward_mc / qmri_adjoint_mc):  A_mc x = [A (C_j . x)]_j,  A_mc' y = sum_j conj(C_j) . A' y_j.
+// with A replaced by the SENSE operator of api_operator.cpp (qmri_forward_mc / qmri_adjoint_mc):  A_mc x = [A (C_j . x)]_j,  A_mc' y = sum_j conj(C_j) . A' y_j.
 // Coil maps act in image space, so A_mc'A_mc is no longer block-diagonal in k-space and the k-space iteration of kslsqr_kernels.hip does not apply:
 // this is the image-domain LSQR, the recurrences, stop rules and their order exactly as oracle/orc_lsqr.c restates MATLAB's lsqr.
 //

@@ -43,6 +43,9 @@ void qmri_set_error(qmri_ctx* ctx, const char* fmt, ...);
 // Owners of device and pinned memory, events and streams (dev_mem.h).  Internal linkage: none of it reaches the library's dynamic symbols.
 // ---------------------------------------------------------------------------------------------------
 #include "dev_mem.h"
+// What the host decides about a gridded operator, in plain C++ (op_plan.h): the mask builders, the k-sorted sample list (KEntry), the work units of
+// the k-space LSQR (KSample, KsGroup, KsUnit, KS_CAPS, ks_plan_units) and the DIRECT solver's tables.
+#include "op_plan.h"
 
 // ---------------------------------------------------------------------------------------------------
 // A/B and diagnostic switches ("knobs").  ONE environment variable, QMRI_DEBUG="name=value,name=value" (read once per process), and
@@ -81,12 +84,6 @@ int qmri_knob(QmriKnob k);
 // ---------------------------------------------------------------------------------------------------
 // forward operator (struct F): device-side description
 // ---------------------------------------------------------------------------------------------------
-struct KEntry {          // one sample of the k-sorted measurement list
-    uint16_t kw;         // k-space column (second FFT dimension)
-    uint16_t t;          // frame
-};
-
-
 struct OpDev {
     int N, M, s, T, m;
     const double* Vt;        // [T][s]  V(t,c), frame-major
@@ -100,21 +97,8 @@ struct OpDev {
 };
 
 // ---------------------------------------------------------------------------------------------------
-// k-space LSQR (kslsqr_kernels.hip): work partition over the sampled k locations ("slots", k' order)
+// k-space LSQR (kslsqr_kernels.hip): the plan (op_plan.h ks_plan_units: KSample, KsGroup, KsUnit, KS_CAPS) and the state of a solve on the device
 // ---------------------------------------------------------------------------------------------------
-struct KSample { uint16_t ls, t; };              // slot of a sample relative to its block's first slot; frame
-struct KsGroup { uint16_t ls, b, e, pad; };      // <= gcap samples of one slot; b, e relative to the block's first sample
-// The shape of a work unit: slots, samples, samples per scatter group, lanes that share a group, scatter groups per block (= ecap / gcap + scap).
-// Picked when the operator is planned (api_core.cpp); kslsqr_kernels.hip instantiates its kernels for each (KsCaps):
-//   0  dense masks (a sampled k location carries >= 8 samples on average: the spiral), slice batches and single slices whose units fit the chip
-//   1  sparse masks (EPI: every k location, 2.7 samples each), ONE slice: 256 slots per unit so that <= 250 units result (one-launch iteration)
-//   2  dense, very many samples per k (cut0: 56), ONE slice: 2560 samples per unit, <= 256 units (one-launch iteration)
-//   3  sparse masks, slice batches (and whatever 1 does not fit): small units
-// Sparse shapes give every scatter group (<= 4 samples of one slot) to ONE lane; the dense ones share a group of <= 32 samples among 8 lanes.
-struct KsCapsHost { int scap, ecap, gcap, sl, gcapb; };
-constexpr KsCapsHost KS_CAPS[4] = {{64, 1024, 32, 8, 96}, {256, 768, 4, 1, 448}, {64, 2560, 32, 8, 144}, {64, 256, 4, 1, 128}};
-constexpr int KS_NCAPS = 4;
-struct KsUnit { int32_t s0, s1, e0, e1, g0, g1, pad0, pad1; };   // a work unit: its slots, samples and groups (one 32-byte scalar load)
 struct LsqrState;
 struct KsDev {
     int ns, G;                                   // sampled k locations; blocks of the iteration kernels
@@ -413,10 +397,6 @@ struct NufftHost {
     bool fmn_plain = false;
     bool fmn_ready = false;
 };
-// the exponential spiral of setup_subsampling_spiralgrided.m:7-27 before rounding (shared by qmri_build_spiral and qmri_build_spiral_traj): S angles
-// theta_j and radii r_j normalised to [0, 1]; frame f is rotated by f * SPIRAL_DELTA
-void spiral_points(int S, std::vector<double>& theta, std::vector<double>& rad);
-constexpr double SPIRAL_DELTA = 3.14159265358979323846 / 180.0 * 7.5;
 int nufft_launch_fwd(qmri_ctx* ctx, int B, const double2* x, double2* y);    // x [B][n] -> y [B][m] (ABI order)
 int nufft_launch_adj(qmri_ctx* ctx, int B, const double2* y, double2* x);    // y [B][m] -> x [B][n]
 int nufft_launch_adj_plain(qmri_ctx* ctx, int B, const double2* y, double2* x);  // ... uncorrected even while a field map is attached (the Toeplitz set-ups)
@@ -571,11 +551,17 @@ struct qmri_ctx {
     double last_call_wall_ms = 0;            // ... its host wall clock, entry to return (always)
     LlrState llr;                       // the regulariser of the PnP-ADMM loops' Step 2 while set (qmri_set_llr), else the network
     bool llr_lds_attr[3] = {false, false, false};   // large dynamic LDS allowed for k_llr_prox<4 | 8 | 16>
-    int conv_ncu = 0;                   // CU count of the device (qmri_create)
+    int ncu = 0;                        // CU count of the device (qmri_create)
     int conv_occ[4][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};   // f32-MFMA conv kernels (conv_kernels.hip): resident workgroups per CU by (kind, MT)
 };
 
 OpDev qmri_opdev(const qmri_ctx* ctx);
+#define REQUIRE_OP(ctx)                                                                   \
+    do {                                                                                  \
+        if (!(ctx)) return QMRI_ERR_INVALID_ARG;                                          \
+        QMRI_HIP((ctx), hipSetDevice((ctx)->device));                                     \
+        if (!(ctx)->op.ready) { qmri_set_error((ctx), "operator not set: call qmri_set_operator first"); return QMRI_ERR_STATE; } \
+    } while (0)
 
 // ---------------------------------------------------------------------------------------------------
 // kernel launchers (dc_kernels.hip)
@@ -598,7 +584,7 @@ int dc_hpass_blocks(const OpDev& op);
 // what the ADMM loop fuses into the launches around a solve (qmri_lsqr_run)
 struct LsqrFuse { int z_hpass_nblk = 0; const double2* mm_u = nullptr; double* mm = nullptr; bool mm_cpx = false; };
 int dc_launch_dual_fwd_h(qmri_ctx* ctx, const OpDev& op, int B, const DualArgs& d, const ActCheckArgs& ac, double2* tmp);
-// host functions that cross files: api_core.cpp (operator, LSQR), api_net.cpp (denoiser; hidden: file-local until the ADMM drivers left that file), api_dict.cpp
+// host functions that cross files: api_operator.cpp (operator), api_xupdate.cpp (DIRECT tables, LSQR), api_net.cpp (denoiser; hidden: file-local until the ADMM drivers left that file), api_dict.cpp
 void qmri_free_operator(qmri_ctx* ctx);
 void qmri_free_net(qmri_ctx* ctx);
 void qmri_free_dict(qmri_ctx* ctx);

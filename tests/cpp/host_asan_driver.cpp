@@ -4,7 +4,7 @@
 //
 //   host_asan_driver <valid.onnx> [<mangled.onnx> ...]
 //
-// Covered: the mask builders (setup_subsampling_spiralgrided.m / setup_subsampling_epi.m restated in api_core.cpp) incl. the capacity error,
+// Covered: the mask builders (setup_subsampling_spiralgrided.m / setup_subsampling_epi.m restated in op_plan.h) incl. the capacity error,
 // qmri_net_nparams, the ONNX reader on a well-formed file and on truncated / bit-flipped ones (an untrusted input), the weight packers of all
 // four layer kinds in both operand-splitting schemes (conv_kernels.hip / conv6_kernels.hip host code), and the argument / state checks of the
 // entry points that refuse to run without a context or a device.
