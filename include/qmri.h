@@ -408,6 +408,51 @@ int qmri_dict_match_grouped(qmri_ctx* ctx, const void* X, int Npix, const double
 int qmri_dict_match_grouped_dev(qmri_ctx* ctx, const void* d_X, int Npix, const double* d_sel, float* d_qmap, float* d_pd, float* d_mt, int32_t* d_dm,
                                 int32_t* d_grp, float* d_xfit);
 
+/* ---- tissue-fraction maps: each pixel as a non-negative mix of chosen atoms (an EXTENSION, no reference counterpart, parity unpinned;
+ *      DESIGN.md section 27) --------------------------------------------------------------------------------------------------------------------
+ * The match above gives every pixel ONE atom.  A pixel that holds two or three tissues (a boundary, a thick slice) gets a (T1, T2) that belongs to
+ * none of them; partial-volume MRF (Deshmane et al., 2019) writes the pixel's compressed fingerprint as a non-negative combination of a few chosen
+ * atoms -- white matter, grey matter, CSF -- and reports the weights as tissue-fraction maps.
+ * Components.  The caller names C atoms, 1 <= C <= 8, of the narrow dictionary (s <= 16) set by qmri_set_dictionary, 1-based like dm.  Component c is
+ *   the UNNORMALISED atom a_c = normD[k_c] * D[k_c, :], s real values widened to fp64, so a weight is in the units of PD.  A = [a_1 .. a_C] (s x C),
+ *   G = A^T A in fp64 with the channels summed in ascending order.
+ * Per pixel, x (complex, s channels) = one row of the Npix x s complex-double column-major array qmri_dict_match takes:
+ *   1. the real vector b and the phase phi.  QMRI_PV_REAL: b = Re x, phi = 0 (the project's real-TSMI domain).  QMRI_PV_PHASE: q = sum_j x_j^2 (no
+ *      conjugate), phi0 = atan2(Im q, Re q) / 2 (0 when q = 0), b0 = Re(x e^{-i phi0}); if sum_j b0_j (sum_c a_c)_j < 0 then phi = phi0 + pi and
+ *      b = -b0 (e^{-i phi} is the negated e^{-i phi0}, so b = -b0 exactly), else phi = phi0, b = b0.
+ *   2. w = argmin_{w >= 0} ||b - A w||_2 by Lawson & Hanson's active-set method on the normal equations, h = A^T b (channels ascending):
+ *      start with w = 0 and an empty passive set P.
+ *      Outer step: g = h - G w; stop when no i outside P has g_i > tau_i; otherwise the lowest index attaining the largest such g_i moves into P.
+ *        tau_i = 2^-48 ||a_i|| ||b|| (||a_i|| = sqrt(G_ii)): the size of g_i's own rounding error.  With tau = 0 a pixel that IS a mix of the
+ *        components (every dual exactly 0) would move indices in and out on rounding noise until the cap.
+ *      Inner step: solve G_PP z_P = h_P by Cholesky in ascending index order (z = 0 outside P).  If every z_i, i in P, is > 0: w = z, back to the
+ *        outer step.  Otherwise alpha = min over {i in P, z_i <= 0} of w_i / (w_i - z_i) (0 when w_i = 0), w = w + alpha (z - w); every index that
+ *        attains alpha, and any with w_i <= 0, is set to exactly 0 and leaves P; repeat the inner step.
+ *      At most 3 C inner solves per pixel: a pixel that would need more keeps its current w and gets flag bit 0 (QMRI_PV_FLAG_CAP).
+ *   A pixel with a non-finite x gets all outputs 0 and flag bit 1 (QMRI_PV_FLAG_NONFINITE), like the match's NaN -> 0 rule.
+ * Outputs, column-major, all nullable except w:  w Npix x C fp64;  frac Npix x C = w / sum_c w_c (0 where the sum is 0);  pd Npix complex doubles =
+ *   (sum_c w_c) e^{i phi};  res Npix = ||x e^{-i phi} - A w||_2 / ||x||_2, imaginary part included, from A and not from G (0 for x = 0);  flags Npix
+ *   int32.  A pixel's result depends on no other pixel of the call, nor on Npix or the pixels' order, bit for bit.
+ * Not built: components per B1 group, wide dictionaries, more than 8 components, sparse selection of the components from the whole dictionary,
+ *   unmixing inside the batch workers. */
+enum { QMRI_PV_REAL = 0, QMRI_PV_PHASE = 1 };
+enum { QMRI_PV_FLAG_CAP = 1, QMRI_PV_FLAG_NONFINITE = 2 };
+typedef struct {
+    double min_pivot;        /* smallest pivot of the Cholesky factorisation of G scaled to a unit diagonal, in (0, 1]: 1 = orthogonal components */
+    int32_t C, s;            /* components and channels in force */
+    int32_t reserved[4];
+} qmri_pv_info;
+/* Forms A and G on the host from the dictionary's host copy and uploads them.  atoms: C indices, 1-based; info nullable; C = 0 clears (atoms may be
+ * NULL).  qmri_set_dictionary drops the components.  A failed call leaves earlier components in place.  Refusals: C outside 0..8, a NULL array, an
+ * index outside 1..K, a repeated index, a zero or non-finite atom, C > s, collinear components (a scaled pivot <= 1e-10): QMRI_ERR_INVALID_ARG (the
+ * first two also with ctx == NULL); no dictionary: QMRI_ERR_STATE; a wide dictionary (s > 16): QMRI_ERR_UNSUPPORTED. */
+int qmri_set_components(qmri_ctx* ctx, int C, const int32_t* atoms, qmri_pv_info* info);
+/* The unmixing on host arrays; returns after the kernel has finished.  mode: QMRI_PV_REAL or QMRI_PV_PHASE.  Refusals, decided before the device is
+ * touched: Npix < 1, NULL X, NULL w, mode outside {0, 1}: QMRI_ERR_INVALID_ARG (also with ctx == NULL); no components set: QMRI_ERR_STATE. */
+int qmri_dict_unmix(qmri_ctx* ctx, const void* X, int Npix, int mode, double* w, double* frac, double* pd, double* res, int32_t* flags);
+/* The same on device arrays, asynchronous on ctx's stream.  d_X as for qmri_dict_match_dev. */
+int qmri_dict_unmix_dev(qmri_ctx* ctx, const void* d_X, int Npix, int mode, double* d_w, double* d_frac, double* d_pd, double* d_res, int32_t* d_flags);
+
 /* ---- TSMI synthesis from quantitative maps: main_synthesize_tsmis.m:54,82-100 (mode 'real') ------------ */
 /* I = knnsearch(KDTreeSearcher(dict.lut), qm(:,1:2)); X = real(dict.D(I,:)) .* dict.normD(I) .* abs(qm(:,3)); X .* sign(X(:,:,1)).
  * qmap: Npix x 3 doubles column-major (T1, T2, PD, in the units of dict.lut); X_out: Npix x s singles column-major;

@@ -479,6 +479,15 @@ struct OpHost {
     PinnedArr<LsqrState> h_ring;        // pinned [ADMM iteration][slice]: LSQR state of a reconstruction whose host never waits (api_admm.cpp)
 };
 
+// components of the tissue-fraction unmixing (qmri_set_components; pv_kernels.hip, api_pv.cpp).  The table the kernel reads, PV_TAB
+// doubles: A [16][8] (channel j, component c; zero padded), G [8][8], asum [16] = sum_c a_c, na [8] = sqrt(G_cc)
+constexpr int PV_MAX_C = 8, PV_MAX_S = 16, PV_TAB_A = 0, PV_TAB_G = 128, PV_TAB_ASUM = 192, PV_TAB_NA = 208, PV_TAB = 216;
+struct PvHost { int C = 0, s = 0; double min_pivot = 0.0; DevArr<double> d_tab; };
+// Pure host code: the table of C components (1-based atoms) of the dictionary D [K][s column-major] / normD, and the smallest Cholesky pivot of the
+// unit-diagonal-scaled G.  QMRI_OK, or QMRI_ERR_INVALID_ARG with *msg set (index outside 1..K, repeated, zero or non-finite atom, C > s, collinear).
+int pv_form_components(const float* D, const float* normD, int K, int s, int C, const int32_t* atoms, double* tab, double* min_pivot, std::string* msg);
+int pv_launch(qmri_ctx* ctx, const double2* d_X, int Npix, int mode, double* d_w, double* d_frac, double2* d_pd, double* d_res, int32_t* d_flags);
+
 struct DictHost {
     bool ready = false;
     int K = 0, s = 0, Q = 0, ntiles = 0;
@@ -508,6 +517,8 @@ struct DictHost {
     DevArr<int> d_gptr, d_gtile; DevArr<double> d_gval;
     DevArr<int> d_gwork;
     int slots_g = 0, slots_gf = 0;                        // as slots / slots_f, for the grouped instantiations
+    std::vector<float> D_h, normD_h;                      // narrow dictionaries: the caller's D [K x s column-major] and normD, kept for qmri_set_components
+    PvHost pv;                                            // ... and the components in force (C = 0: none); dropped with the dictionary
 };
 
 struct qmri_ctx {

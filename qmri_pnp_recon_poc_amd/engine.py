@@ -180,6 +180,26 @@ def group_arguments(group_ptr, group_val):
     return np.ascontiguousarray(gp, dtype=np.int32), np.ascontiguousarray(gv)
 
 
+def component_arguments(atoms, K=None):
+    """atoms [C] int32 (1-based) as qmri_set_components takes them: 1 <= C <= 8 integers, distinct, and inside 1..K when K is known; the library
+    checks the atoms themselves."""
+    a = np.asarray(atoms)
+    if a.ndim != 1 or not (1 <= a.size <= 8) or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("atoms must be 1 to 8 integer atom indices (1-based)")
+    if len(set(a.tolist())) != a.size:
+        raise ValueError("atoms must be distinct")
+    if a.min() < 1 or (K is not None and a.max() > K):
+        raise ValueError("atoms are 1-based indices" + ("" if K is None else f" into the dictionary's {K} atoms"))
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def unmix_mode(mode):
+    """"real" / "phase" -> QMRI_PV_REAL / QMRI_PV_PHASE."""
+    if mode not in ("real", "phase"):
+        raise ValueError(f'mode must be "real" or "phase", not {mode!r}')
+    return 0 if mode == "real" else 1
+
+
 def dict_group_assign(group_val, sel):
     """The group of each selector value as the grouped dictionary match assigns it (qmri_dict_group_assign, host only): the lowest g minimising
     |sel - group_val[g]| in float64, 1-based; 0 for a non-finite value (unmatched).  Returns int32 in the shape of sel."""
@@ -192,6 +212,16 @@ def dict_group_assign(group_val, sel):
     if st != 0:
         raise QmriError(st, _lib.lib().qmri_last_error(None).decode())
     return out.reshape(b.shape)
+
+
+def nearest_atoms(lut, points):
+    """The 1-based row of lut [K, >= 2] whose (T1, T2) is nearest each row of points [n, 2]: squared distance in float64, the first minimum wins."""
+    lut = np.asarray(lut, dtype=np.float64)
+    pts = np.asarray(points, dtype=np.float64)
+    if lut.ndim != 2 or lut.shape[1] < 2 or pts.ndim != 2 or pts.shape[1] != 2 or not np.all(np.isfinite(pts)):
+        raise ValueError("points must be [n, 2] finite (T1, T2) pairs and the lut [K, >= 2]")
+    d = (lut[None, :, 0] - pts[:, None, 0]) ** 2 + (lut[None, :, 1] - pts[:, None, 1]) ** 2
+    return (np.argmin(d, axis=1) + 1).astype(np.int32)
 
 
 def _hip_runtime():
@@ -286,6 +316,7 @@ class Engine:
         self.N = self.M = self.s = self.T = self.m = 0
         self.net_desc = None
         self.dict_shape = None
+        self.components = None
 
     def close(self):
         if getattr(self, "h", None):
@@ -893,6 +924,71 @@ class Engine:
         f = C.POINTER(C.c_float)
         self._check(self.L.qmri_set_dictionary(self.h, K, s, Q, Df.ctypes.data_as(f), nd.ctypes.data_as(f), lf.ctypes.data_as(f)))
         self.dict_shape = (K, s, Q)
+        self._lut = np.asarray(lut, dtype=np.float64)
+        self.components = None                                   # (qmri_set_dictionary drops them)
+
+    def set_components(self, atoms):
+        """The components of tissue_fractions (extension, no reference counterpart; include/qmri.h qmri_set_components):
+        1 <= C <= 8 distinct atoms (1-based, like dm) of the set narrow dictionary, e.g. nearest_atoms([(T1, T2) of white matter, grey matter,
+        CSF]).  Returns dict(min_pivot, C, s): min_pivot in (0, 1] is the smallest Cholesky pivot of the unit-diagonal Gram matrix of the
+        components (1: orthogonal; near 0: nearly dependent, fractions ill-determined).  set_dictionary drops the components."""
+        from ._lib import PvInfo
+        if self.dict_shape is None:
+            raise ValueError("set_dictionary first")
+        a = component_arguments(atoms, self.dict_shape[0])
+        info = PvInfo()
+        self._check(self.L.qmri_set_components(self.h, a.size, a.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(info)))
+        self.components = a.copy()
+        return {"min_pivot": float(info.min_pivot), "C": int(info.C), "s": int(info.s)}
+
+    def clear_components(self):
+        self._check(self.L.qmri_set_components(self.h, 0, None, None))
+        self.components = None
+
+    def nearest_atoms(self, points):
+        """The 1-based atom whose first two lut columns are nearest each (T1, T2) of points [n, 2], squared distance in float64, the first minimum
+        winning (the rule of synth.synthesize_tsmi's knnsearch) -> int32 [n]."""
+        if self.dict_shape is None:
+            raise ValueError("set_dictionary first")
+        return nearest_atoms(self._lut, points)
+
+    def tissue_fractions(self, X, mode="real", want_frac=True, want_pd=True, want_res=True):
+        """Every pixel of X [..., s] complex as a non-negative combination of the set components (qmri_dict_unmix): dict(w [..., C] float64 in the
+        units of PD, flags [...] int32 (bit 0: iteration cap, bit 1: non-finite pixel, outputs 0), frac [..., C] = w / sum w, pd [...] complex128 =
+        (sum w) e^{i phi}, res [...] = ||x e^{-i phi} - A w|| / ||x||).  mode "real" fits Re x; "phase" first removes the pixel's own phase."""
+        m = unmix_mode(mode)
+        if self.components is None:
+            raise ValueError("set_components first")
+        X = np.asarray(X, dtype=np.complex128)
+        K, s, Q = self.dict_shape
+        if X.ndim < 1 or X.shape[-1] != s:
+            raise ValueError("last dimension of X must equal the dictionary's channel count")
+        lead = X.shape[:-1]
+        npix, nc = int(np.prod(lead)), int(self.components.size)
+        xb = np.ascontiguousarray(X.reshape((npix, s), order="F").ravel(order="F"))
+        w = np.empty(npix * nc, np.float64)
+        frac = np.empty(npix * nc, np.float64) if want_frac else None
+        pd = np.empty(2 * npix, np.float64) if want_pd else None
+        res = np.empty(npix, np.float64) if want_res else None
+        flags = np.empty(npix, np.int32)
+        dp = C.POINTER(C.c_double)
+        self._check(self.L.qmri_dict_unmix(self.h, _vp(xb), npix, m, w.ctypes.data_as(dp), frac.ctypes.data_as(dp) if want_frac else None,
+                                           pd.ctypes.data_as(dp) if want_pd else None, res.ctypes.data_as(dp) if want_res else None,
+                                           flags.ctypes.data_as(C.POINTER(C.c_int32))))
+        out = {"w": w.reshape(lead + (nc,), order="F"), "flags": flags.reshape(lead, order="F")}
+        if want_frac:
+            out["frac"] = frac.reshape(lead + (nc,), order="F")
+        if want_pd:
+            out["pd"] = pd.view(np.complex128).reshape(lead, order="F")
+        if want_res:
+            out["res"] = res.reshape(lead, order="F")
+        return out
+
+    def tissue_fractions_dev(self, d_X: int, npix: int, mode="real", d_w: int = 0, d_frac: int = 0, d_pd: int = 0, d_res: int = 0, d_flags: int = 0):
+        """qmri_dict_unmix_dev: device pointers (X Npix x s complex double column-major; outputs as qmri.h lays them out), asynchronous on the
+        engine's stream."""
+        self._check(self.L.qmri_dict_unmix_dev(self.h, C.c_void_p(d_X), int(npix), unmix_mode(mode), C.c_void_p(d_w or None), C.c_void_p(d_frac or None),
+                                               C.c_void_p(d_pd or None), C.c_void_p(d_res or None), C.c_void_p(d_flags or None)))
 
     def set_dictionary_groups(self, group_ptr, group_val):
         """Groups of the set dictionary (extension, no reference counterpart; include/qmri.h qmri_set_dictionary_groups): group g holds atoms

@@ -284,6 +284,32 @@ def estimate_field_map(Y, echo_times, device=0, **kw):
     return R._engine(device).estimate_field_map(Y, echo_times, **kw)
 
 
+def resolve_components(dictionary, components):
+    """components of recon_tsmis / unmix_tsmi -> 1-based atom indices int32 [C]: integers are taken as they are, (T1, T2) pairs stand for the atom whose
+    first two lut columns are nearest (engine.nearest_atoms)."""
+    from .engine import component_arguments, nearest_atoms
+    c = np.asarray(components)
+    K = np.asarray(dictionary["D"]).shape[0]
+    if c.ndim == 1 and np.issubdtype(c.dtype, np.integer):
+        return component_arguments(c, K)
+    if c.ndim != 2 or c.shape[1] != 2 or not (1 <= c.shape[0] <= 8):
+        raise ValueError("components must be 1 to 8 atom indices (integers, 1-based) or (T1, T2) pairs")
+    return component_arguments(nearest_atoms(dictionary["lut"], c), K)
+
+
+def unmix_tsmi(dictionary, X, components, mode="real", device=0):
+    """Tissue-fraction maps of a TSMI X [N, M, s]: dict(fractions [N, M, C], component_atoms [C], unmix_res [N, M],
+    unmix_weights [N, M, C], unmix_pd [N, M] complex, unmix_flags [N, M])."""
+    from . import reference_api as R
+    atoms = resolve_components(dictionary, components)
+    eng = R._engine(device)
+    eng.set_dictionary(dictionary["D"], dictionary["normD"], dictionary["lut"])
+    eng.set_components(atoms)
+    out = eng.tissue_fractions(X, mode=mode)
+    return {"fractions": out["frac"], "component_atoms": atoms, "unmix_res": out["res"], "unmix_weights": out["w"], "unmix_pd": out["pd"],
+            "unmix_flags": out["flags"]}
+
+
 # ------------------------------------------------------------------------------------------------------------
 # the script's main flow
 # ------------------------------------------------------------------------------------------------------------
@@ -292,7 +318,7 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
                 denoiser_type="single_level", noise_map_std=0.01, residual_noise=False, iters=100, seed=0, Y=None, device=0,
                 net_arch=None, lrtv_iters=None, tsmi_domain="real", solver="lsqr", b1_map=None, density_compensation=False,
                 field_map=None, readout_s=None, field_normal=None, field_echoes=None, field_echo_times=None,
-                regulariser="net", llr_tau=None, llr_tau_rel=0.02, llr_block=8):
+                regulariser="net", llr_tau=None, llr_tau_rel=0.02, llr_block=8, components=None, unmix_mode="real"):
     """main_recon_tsmis_FFT.m:216-374 on already loaded (and cropped) arrays.
 
     dictionary  dict(V, D, normD, lut) (load_dictionary);  X0  N x M x s ground-truth TSMI;  qmap0  N x M x 3
@@ -317,6 +343,10 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
     regulariser   of PnP_ADMM: "net" (default) is the denoiser of `weights`; "llr" the locally low-rank proximal step, which
                 needs no weights and works on every subsampling pattern: llr_block x llr_block patches (4, 8 or 16, dividing N and M), threshold
                 llr_tau, or with None llr_tau_rel times sigma_max of the start image.  The result gains llr_tau, the threshold used.
+    components  tissue-fraction maps after the match: 1..8 (T1, T2) pairs in the units of dict.lut (each stands for the
+                nearest atom) or 1-based atom indices; every pixel of the reconstructed TSMI is written as a non-negative mix of those atoms
+                (unmix_mode "real": of its real part, "phase": after removing the pixel's phase).  The result gains fractions (N x M x C),
+                component_atoms (C, 1-based) and unmix_res (N x M).  Absent: nothing changes.
     Returns dict(X, qmap (N x M x 3: T1, T2, PD), Y, metrics, foreground_mask); with b1_map also grp (N x M, the 1-based b1 group, 0 = unmatched);
     with field_normal also field_normal_info (what prepare_normal_field reported).
     """
@@ -336,6 +366,10 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
         b1_map = np.asarray(b1_map, dtype=np.float64)
         if b1_map.shape != (N, M):
             raise ValueError(f"b1_map must be {N} x {M}")
+    if components is not None:                                                       # (refused before anything is reconstructed)
+        component_atoms = resolve_components(dictionary, components)
+        from .engine import unmix_mode as _umode
+        _umode(unmix_mode)
     V = np.asarray(dictionary["V"], dtype=np.float64)
     if subsampling_pattern == "Spiral":
         P = R.setup_subsampling_spiralgrided(N, M, spiral_sampling_curve, V)
@@ -434,5 +468,7 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
     else:
         out = R.mrf_dtm_cpu(dictionary, {"X": X}, par, device=device)
     qmap = np.concatenate([np.asarray(out["qmap"], dtype=np.complex128), np.asarray(out["pd"]).reshape(N, M, 1)], axis=2)       # :316
+    if components is not None:
+        extra.update(unmix_tsmi(dictionary, X, component_atoms, mode=unmix_mode, device=device))
     mask = getmask_fromPD(np.asarray(qmap0)[:, :, 2], 0.15)                          # :192
     return {"X": X, "qmap": qmap, "Y": Y, "foreground_mask": mask, "metrics": metrics(qmap, qmap0, mask, X, X0), **extra}

@@ -60,6 +60,7 @@ struct DictSpec { mxArray* D = nullptr; mxArray* normD = nullptr; mxArray* lut =
 static OperatorSpec g_op;
 static DenoiserSpec g_net;
 static DictSpec g_dict;
+static std::vector<int32_t> g_comp;                    // 'set_components' in force (1-based atoms); 'set_dictionary' drops them
 static bool g_llr = false;                             // 'set_llr' is in force: 'pnp_admm' needs no denoiser
 static const int DEFAULT_SLICES_PER_LAUNCH = 15;       // what a measurement matrix grows the plans to (the batched kernels' design point)
 
@@ -71,6 +72,7 @@ static void cleanup() {
     drop(g_op.V); drop(g_op.fp); drop(g_op.kidx); drop(g_op.omega); g_op = OperatorSpec();
     drop(g_net.w); g_net = DenoiserSpec();
     drop(g_dict.D); drop(g_dict.normD); drop(g_dict.lut);
+    g_comp.clear();
     g_llr = false;
 }
 
@@ -239,6 +241,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
             if (g_op.V) plan_operator(std::max(1, g_op.max_batch));
             if (g_net.w) plan_denoiser(std::max(1, g_net.max_batch));
             if (g_dict.D) plan_dictionary();
+            if (g_dict.D && !g_comp.empty()) check(qmri_set_components(ctx(), (int)g_comp.size(), g_comp.data(), nullptr));
         }
         if (nlhs > 0) plhs[0] = mxCreateDoubleScalar((double)g_device);
     } else if (c == "set_operator") {                // qmri_mex('set_operator', N, M, V, frame_ptr(int32), kidx(int32) [, max_batch])
@@ -938,6 +941,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
             mexErrMsgIdAndTxt("qmri:set_dictionary:size", "normD must have K elements and lut K rows (K = rows of D)");
         drop(g_dict.D); drop(g_dict.normD); drop(g_dict.lut);
         g_dict.D = keep(prhs[1]); g_dict.normD = keep(prhs[2]); g_dict.lut = keep(prhs[3]);
+        g_comp.clear();
         plan_dictionary();
     } else if (c == "dict_match") {                  // [qmap, pd, mt, dm, xfit] = qmri_mex('dict_match', X(Npix x s complex double), Q)
         need(nrhs, 3, "[qmap, pd, mt, dm, xfit] = qmri_mex('dict_match', X, Q)");
@@ -997,6 +1001,51 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         if (nlhs > 3) plhs[3] = dm; else mxDestroyArray(dm);
         if (nlhs > 4) plhs[4] = grp; else mxDestroyArray(grp);
         if (nlhs > 5) plhs[5] = xfit;
+    } else if (c == "set_components") {              // info = qmri_mex('set_components', atoms(1..8 doubles, 1-based)); [] clears
+        // the components of 'dict_unmix' (extension; qmri.h qmri_set_components).  'set_dictionary' drops them.
+        need(nrhs, 2, "info = qmri_mex('set_components', atoms)");
+        want(nlhs <= 1, "qmri:usage", "info = qmri_mex('set_components', atoms)");
+        want(mxIsDouble(prhs[1]) && !mxIsComplex(prhs[1]), "qmri:set_components:type", "atoms must be a real double array");
+        const size_t nc = mxGetNumberOfElements(prhs[1]);
+        want(nc <= 8, "qmri:set_components:size", "atoms must hold 1 to 8 atom indices ([] clears)");
+        want(g_dict.D != nullptr, "qmri:state", "no dictionary: call qmri_mex('set_dictionary', ...) first");
+        std::vector<int32_t> atoms(nc);
+        const double* v = mxGetDoubles(prhs[1]);
+        for (size_t k = 0; k < nc; ++k) {
+            want(std::isfinite(v[k]) && v[k] == std::floor(v[k]) && v[k] >= 1 && v[k] <= (double)mxGetM(g_dict.D), "qmri:set_components:size",
+                 "atoms must be 1-based atom indices (1 .. rows of dict.D)");
+            atoms[k] = (int32_t)v[k];
+        }
+        qmri_pv_info info{};
+        check(qmri_set_components(ctx(), (int)nc, nc ? atoms.data() : nullptr, &info));
+        g_comp = atoms;
+        if (nlhs > 0) {
+            const char* names[] = {"min_pivot", "C", "s"};
+            plhs[0] = mxCreateStructMatrix(1, 1, 3, names);
+            const double f[3] = {info.min_pivot, (double)info.C, (double)info.s};
+            for (int k = 0; k < 3; ++k) mxSetFieldByNumber(plhs[0], 0, k, mxCreateDoubleScalar(f[k]));
+        }
+    } else if (c == "dict_unmix") {                  // [w, frac, pd, res, flags] = qmri_mex('dict_unmix', X(Npix x s complex double), mode(0 real | 1 phase))
+        const char* usage = "[w, frac, pd, res, flags] = qmri_mex('dict_unmix', X, mode)";
+        need(nrhs, 3, usage);
+        want(nlhs <= 5, "qmri:usage", usage);
+        want(is_cdouble(prhs[1]) && mxGetM(prhs[1]) >= 1 && mxGetM(prhs[1]) <= 2147483647u, "qmri:dict_unmix:type", "X must be complex double, Npix x s");
+        const int mode = int_arg(prhs[2], 0, 1, "qmri:dict_unmix:mode", "mode must be 0 (real) or 1 (phase)");
+        want(g_dict.D != nullptr, "qmri:state", "no dictionary: call qmri_mex('set_dictionary', ...) first");
+        want(mxGetN(prhs[1]) == mxGetN(g_dict.D), "qmri:dict_unmix:size", "X must have s columns (s = columns of dict.D)");
+        want(!g_comp.empty(), "qmri:state", "no components: call qmri_mex('set_components', atoms) first");
+        const size_t npix = mxGetM(prhs[1]), nc = g_comp.size();
+        plhs[0] = mxCreateDoubleMatrix(npix, nc, mxREAL);
+        mxArray* frac = (nlhs > 1) ? mxCreateDoubleMatrix(npix, nc, mxREAL) : nullptr;
+        mxArray* pd = (nlhs > 2) ? mxCreateDoubleMatrix(npix, 1, mxCOMPLEX) : nullptr;
+        mxArray* res = (nlhs > 3) ? mxCreateDoubleMatrix(npix, 1, mxREAL) : nullptr;
+        mxArray* flags = (nlhs > 4) ? mxCreateNumericMatrix(npix, 1, mxINT32_CLASS, mxREAL) : nullptr;
+        check(qmri_dict_unmix(ctx(), mxGetComplexDoubles(prhs[1]), (int)npix, mode, mxGetDoubles(plhs[0]), frac ? mxGetDoubles(frac) : nullptr,
+                              pd ? (double*)mxGetComplexDoubles(pd) : nullptr, res ? mxGetDoubles(res) : nullptr, flags ? (int32_t*)mxGetData(flags) : nullptr));
+        if (nlhs > 1) plhs[1] = frac;
+        if (nlhs > 2) plhs[2] = pd;
+        if (nlhs > 3) plhs[3] = res;
+        if (nlhs > 4) plhs[4] = flags;
     } else if (c == "health") {                      // h = qmri_mex('health'): qmri_get_health of the gateway's context as a struct
         qmri_health h;
         check(qmri_get_health(ctx(), &h));
