@@ -1,6 +1,6 @@
 // op_plan_test.cpp -- the host planning of a gridded operator (csrc/op_plan.h): the functions qmri_set_operator and qmri_prepare_direct call, on a
 // machine without a GPU and under the address and undefined-behaviour sanitizers.  Built and run by tests/test_op_plan_host.py, which compares
-// the lines printed here with the values the planner gave before it was moved into the header.
+// the lines printed here with the values the planner gave before it was moved into the header (and, for the masks of the GPU sweep, as it stands).
 //   stdout: per case  "<name> status=<KsPlanStatus> caps=<shape> units=<G> n=<n> tried=<tried> digest=<FNV-1a of sgrp, es, grp, units>"
 // For every case the program itself checks what holds whatever the planner's thresholds are (check_plan), and once the mask builders' capacity
 // rule, the sorted sample list and the DIRECT solver's tables (a product check).  Exit status 1: a check failed (named on stderr).
@@ -50,6 +50,13 @@ static Mask full_then_k0(int N, int T, int full) {
     k.fp[T] = (int32_t)k.kidx.size();
     return k;
 }
+// one sample in all: frame t samples k, the other frames are empty
+static Mask single_sample(int N, int T, int t, int k) {
+    Mask q; q.N = q.M = N; q.T = T; q.fp.assign(T + 1, 0);
+    for (int f = t + 1; f <= T; ++f) q.fp[f] = 1;
+    q.kidx.push_back(k);
+    return q;
+}
 
 // ---- cases ---------------------------------------------------------------------------------------------------------------------------------------
 struct Setting { const char* tag = ""; int s = 10, max_batch = 1; bool one_launch = true; int ncu = 256; bool fits[KS_NCAPS] = {true, true, true, true}; };
@@ -92,6 +99,12 @@ template <class F> static void for_each_case(F f) {
     run("busy16_T300", full_then_k0(16, 300, 1), {setting("")});                                              // sparse on average, shape 3 refuses k = 0 (300 > 256)
     run("busy16_T1100", full_then_k0(16, 1100, 1), {setting("B1"), setting("B4_off", 4, false)});             // shapes 3, 0, 1 refuse | refusal with the long tail
     run("k0_T2600", full_then_k0(16, 2600, 0), {setting("B1")});                                              // refusal: no shape holds 2600
+    // the 32-sided masks tests/test_gpu_gridded_sweep.py runs on the device (with spiral32_* and full32_T300 above): the shape each one reaches
+    run("busy32_T300", full_then_k0(32, 300, 1), {setting("")});                                              // as busy16_T300
+    run("busy32_T1100", full_then_k0(32, 1100, 1), {setting("")});                                            // as busy16_T1100: only shape 2 holds k = 0
+    run("full32_T8", full_with_short_last_frame(32, 8, 1024), {setting("")});                                 // 8 samples per k: dense
+    run("full32_T8_last1023", full_with_short_last_frame(32, 8, 1023), {setting("")});                        // 7.999 samples per k: sparse
+    run("single_sample32", single_sample(32, 3, 1, 5 + 32 * 7), {setting("")});                               // m = 1: one slot, one group, one unit
 }
 
 // ---- what holds whatever the thresholds are ----------------------------------------------------------------------------------------------------------

@@ -39,6 +39,14 @@ EXPECTED = {
     "busy16_T1100/B1":              (0, 2, 38, 0, 0, "3a0b317f5e43c505"),       # shapes 3, 0 and 1 refuse
     "busy16_T1100/B4_off":          (1, -1, 0, 1100, 1024, "0000000000000000"),
     "k0_T2600/B1":                  (1, -1, 0, 2600, 2560, "0000000000000000"),
+    # The 32-sided masks that tests/test_gpu_gridded_sweep.py runs on the device (beside spiral32_*, full32_T300/B1 above and the epi masks), so that
+    # the unit shape each of those cases reaches is pinned here: the GPU test cannot read it.  Unlike the lines above, these digests were recorded from
+    # ks_plan_units as it stands in op_plan.h; what they pin is the shape and the unit count.
+    "busy32_T300":                  (0, 0, 148, 0, 0, "bcbef29541514020"),      # sparse on average, k = 0 in 300 frames: shape 3 refuses, shape 0 takes it
+    "busy32_T1100":                 (0, 2, 104, 0, 0, "c5d7a6d5b62bde4d"),      # only shape 2 holds the 1100 samples of k = 0 (35 scatter groups of one slot)
+    "full32_T8":                    (0, 0, 205, 0, 0, "93937807f99cc39f"),      # 8 samples per k: dense
+    "full32_T8_last1023":           (0, 3, 205, 0, 0, "7f9aeaa1e2a28572"),      # 7.999: sparse
+    "single_sample32":              (0, 3, 1, 0, 0, "e35c1f865048853b"),        # m = 1: one unit of one slot
 }
 
 
