@@ -124,7 +124,7 @@ static int admm_to_net(qmri_ctx* ctx, const DenoiserStep& d, int mm_nblk, bool m
     NetPlan& net = ctx->net;
     const size_t plane = (size_t)o.N * o.M;
     if (d.tm) d.tm->start();
-    QMRI_TRY(ew_launch_minmax_normalise(ctx, d.B, plane * o.s, (int)plane, o.N, o.s, d.multi, d.prm->noise_std, d.d_x, o.d_u, o.d_mm, o.d_norm, mm_nblk, net.in32,
+    QMRI_TRY(ew_launch_minmax_normalise(ctx, d.B, plane * o.s, (int)plane, o.N, o.s, d.multi, d.prm->noise_std, d.d_x, o.d_u, o.d_mm, o.d_norm, mm_nblk, net.ten[NT_IN32],
                                         mm_ready, d.cpx));
     if (d.tm) { d.tm->stop(ctx->prof.ms_elementwise); d.tm->start(); }
     QMRI_TRY(net_forward(ctx, d.B));
@@ -153,7 +153,7 @@ static int admm_denoiser_step(qmri_ctx* ctx, const DenoiserStep& d, bool copy_ra
     }
     QMRI_TRY(admm_to_net(ctx, d, o.ls.nblk_z, false, copy_range_flag));
     if (d.tm) d.tm->start();
-    QMRI_TRY(ew_launch_unnormalise_dual(ctx, d.B, plane * o.s, (int)plane, o.N, net.out32, net.in32, net.desc.residual_noise, o.d_norm, d.d_x, o.d_u,
+    QMRI_TRY(ew_launch_unnormalise_dual(ctx, d.B, plane * o.s, (int)plane, o.N, net.ten[NT_OUT32], net.ten[NT_IN32], net.desc.residual_noise, o.d_norm, d.d_x, o.d_u,
                                         nullptr /* v itself is never read again: z = v - u goes to the next x-update */, o.d_z, o.ls.pz, o.ls.nblk_z, o.s, d.cpx));
     if (d.tm) d.tm->stop(ctx->prof.ms_elementwise);
     return QMRI_OK;
@@ -358,7 +358,8 @@ static int pnp_admm_dev_impl(qmri_ctx* ctx, int nslices, const void* d_y, const 
         else {
             QMRI_TRY(admm_to_net(ctx, step, hb, true, true));
             tm.start();
-            const DualArgs da = {net.out32.base1(), net.in32.base1(), net.out32.hp, (int)net.out32.plane(), net.out32.batch_stride(), net.in32.batch_stride(),
+            const PTensor &out32 = net.ten[NT_OUT32], &in32 = net.ten[NT_IN32];
+            const DualArgs da = {out32.base1(), in32.base1(), out32.hp, (int)out32.plane(), out32.batch_stride(), in32.batch_stride(),
                                  net.desc.residual_noise, o.d_norm, o.d_x, o.d_u, o.ls.pz, cpx ? 1 : 0};
             ActCheckArgs ac{};
             if (net.act_pending_valid) { ac = net.act_pending; net.act_pending_valid = false; }

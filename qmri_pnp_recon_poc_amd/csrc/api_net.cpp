@@ -12,31 +12,20 @@
 #include <cstring>
 
 extern "C" size_t qmri_net_nparams(const qmri_net_desc* d) {
-    if (!d) return 0;
-    size_t n = 0;
-    if (d->arch == QMRI_ARCH_UNETRES) {
-        const int32_t* nc = d->nc;
-        n += (size_t)nc[0] * d->in_nc * 9;
-        for (int l = 0; l < 3; ++l) n += (size_t)2 * d->nb * nc[l] * nc[l] * 9 + (size_t)nc[l + 1] * nc[l] * 4;
-        n += (size_t)2 * d->nb * nc[3] * nc[3] * 9;
-        for (int l = 3; l > 0; --l) n += (size_t)nc[l] * nc[l - 1] * 4 + (size_t)2 * d->nb * nc[l - 1] * nc[l - 1] * 9;
-        n += (size_t)d->out_nc * nc[0] * 9;
-    } else if (d->arch == QMRI_ARCH_SEQ_CONV) {
-        if (d->nb == 1) return (size_t)d->out_nc * d->in_nc * 9;
-        n = (size_t)d->nc[0] * d->in_nc * 9 + (size_t)(d->nb - 2) * d->nc[0] * d->nc[0] * 9 + (size_t)d->out_nc * d->nc[0] * 9;
-    }
-    return n;
+    return d ? net_plan_nparams(*d) : 0;
 }
 
 void qmri_free_net(qmri_ctx* ctx) {
     ctx->net = NetPlan();
 }
 
-// zero-initialised padded activation tensor; Cal channels are allocated (>= C; the extra ones stay zero forever because
-// kernels only ever write channels < C and plane interiors), plus slack for tiles that overhang the image
-static int alloc_tensor(qmri_ctx* ctx, PTensor& t, int C, int Cal, int H, int W, size_t B) {
-    t.C = C; t.Cal = std::max(C, Cal); t.H = H; t.W = W;
-    t.h0 = 32; t.hp = ((t.h0 + H + 1 + 31) / 32) * 32;
+// zero-initialised padded activation tensor of the layer program; Cal channels are allocated (>= C, net_plan.h; the extra ones stay zero forever
+// because kernels only ever write channels < C and plane interiors), plus slack for tiles that overhang the image
+static int alloc_tensor(qmri_ctx* ctx, NetTensor id, size_t B) {
+    const NetPlan& p = ctx->net;
+    PTensor& t = ctx->net.ten[id];
+    t.C = p.prog.chan[id]; t.Cal = p.prog.cal[id]; t.H = p.H >> nt_level(id); t.W = p.W >> nt_level(id);
+    t.h0 = 32; t.hp = ((t.h0 + t.H + 1 + 31) / 32) * 32;
     const size_t count = B * t.batch_stride() + 8192;
     QMRI_TRY(ctx->net.pool.alloc(ctx, &t.p, count));
     QMRI_HIP(ctx, hipMemset(t.p, 0, count * sizeof(float)));
@@ -56,19 +45,19 @@ static size_t layer_weight_count(const ConvLayer& L) { return (size_t)L.Cin * L.
 
 // knob pack_gpu = 1 (default, round 6): the layer is only PLANNED here; net_pack_all_dev splits and orders every layer's weights on the device.
 // pack_gpu = 0: the host packers (round 1; kept as the reference of the packing and for the sanitised host build), layer by layer.
-static int add_layer(qmri_ctx* ctx, ConvKind kind, int Cin, int Cout, const float*& w) {
+static int add_layer(qmri_ctx* ctx, const NetStep& s, const float* blob) {
     ConvLayer L;
-    conv_plan_layer(L, kind, Cin, Cout);
-    L.w_off = (size_t)(w - ctx->net.w_begin);
+    conv_plan_layer(L, s.kind, s.Cin, s.Cout);
+    L.w_off = s.w_off;
     L.sp6 = ctx->net.sp6;
     if (!ctx->net.d_wflat) {
+        const float* w = blob + s.w_off;
         std::vector<float> packed;
         L.wp_floats = conv_pack_weights(L, w, packed);
         QMRI_TRY(L.wp.ensure(ctx, packed.size()));
         QMRI_HIP(ctx, hipMemcpy(L.wp, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
         QMRI_TRY(pack_layer6(ctx, L, w));                      // the same weights, split for the bf16 / f16 matrix-core kernels
     }
-    w += layer_weight_count(L);
     L.index = (int)ctx->net.layers.size();
     ctx->net.layers.push_back(std::move(L));
     return QMRI_OK;
@@ -188,7 +177,7 @@ static int net_calibrate_scheme(qmri_ctx* ctx) {
     NetPlan& p = ctx->net;
     struct ResOff { NetPlan& n; bool was; ~ResOff() { n.res_off = was; } } res_guard{p, p.res_off};
     p.res_off = true;                                                // (one launch per layer here: same bits, and a hand-off time-out could not be told from a range problem)
-    const size_t n = (size_t)p.desc.in_nc * p.H * p.W, nout = p.out32.batch_stride();
+    const size_t n = (size_t)p.desc.in_nc * p.H * p.W, nout = p.ten[NT_OUT32].batch_stride();
     std::vector<float> h(n);
     uint32_t st = 0x2545F491u;
     for (size_t i = 0; i < n; ++i) { st = st * 1664525u + 1013904223u; h[i] = (float)(st >> 8) * (1.0f / 16777216.0f); }   // uniform [0, 1)
@@ -200,18 +189,18 @@ static int net_calibrate_scheme(qmri_ctx* ctx) {
         QMRI_TRY(d_m.ensure(ctx, 2));
         if (hipMemsetAsync(d_m, 0, 2 * sizeof(unsigned), ctx->stream) != hipSuccess ||
             hipMemcpyAsync(d_tmp, h.data(), n * sizeof(float), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return QMRI_ERR_HIP;
-        QMRI_TRY(ew_launch_pack(ctx, 1, p.desc.in_nc, p.H, p.W, d_tmp, 0, p.in32));
+        QMRI_TRY(ew_launch_pack(ctx, 1, p.desc.in_nc, p.H, p.W, d_tmp, 0, p.ten[NT_IN32]));
         p.force_f32 = true;                                          // reference: exact fp32 products
         int st = net_forward_padded(ctx, 1);
         p.force_f32 = false;
         QMRI_TRY(st);
-        if (hipMemcpyAsync(d_ref, p.out32.p, nout * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) return QMRI_ERR_HIP;
+        if (hipMemcpyAsync(d_ref, p.ten[NT_OUT32].p, nout * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) return QMRI_ERR_HIP;
         p.act_record = true;                                         // ... which also record every layer's magnitude (ACT_LOW guard)
         st = net_forward_padded(ctx, 1);                             // the f16 kernels
         p.act_record = false;
         QMRI_TRY(st);
         QMRI_TRY(ew_launch_absmax(ctx, d_ref, nullptr, nout, d_m));
-        QMRI_TRY(ew_launch_absmax(ctx, p.out32.p, d_ref, nout, d_m + 1));
+        QMRI_TRY(ew_launch_absmax(ctx, p.ten[NT_OUT32].p, d_ref, nout, d_m + 1));
         unsigned m[2] = {0, 0}, flag = 0;
         if (hipMemcpyAsync(m, d_m, sizeof m, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
             hipMemcpyAsync(&flag, p.d_range_flag, sizeof flag, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
@@ -252,15 +241,16 @@ extern "C" int qmri_set_denoiser(qmri_ctx* ctx, const qmri_net_desc* desc, const
         qmri_set_error(ctx, "UNetRes needs H and W divisible by 8 (got %d x %d)", H, W);
         return QMRI_ERR_UNSUPPORTED;
     }
-    if (nbytes != 4 * qmri_net_nparams(desc)) {
-        qmri_set_error(ctx, "weight blob is %zu bytes, architecture needs %zu", nbytes, 4 * qmri_net_nparams(desc));
+    NetProgram prog = net_plan_build(*desc);                         // the layers, their operands, the tensors' channels: everything below follows it
+    if (nbytes != 4 * prog.nparams) {
+        qmri_set_error(ctx, "weight blob is %zu bytes, architecture needs %zu", nbytes, 4 * prog.nparams);
         return QMRI_ERR_INVALID_ARG;
     }
     QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     qmri_free_net(ctx);
     NetPlan& p = ctx->net;
     p.desc = *desc; p.H = H; p.W = W; p.maxB = max_batch;
-    p.w_begin = weights;
+    p.prog = std::move(prog);
     p.sp6 = conv6_default_sp();
     const auto t_upload = std::chrono::steady_clock::now();
     if (qmri_knob(K_PACK_GPU)) {
@@ -276,58 +266,22 @@ extern "C" int qmri_set_denoiser(qmri_ctx* ctx, const qmri_net_desc* desc, const
     p.h_range_words = 4096;
     QMRI_TRY(p.h_range_flag.ensure(ctx, (size_t)p.h_range_words));
     std::memset(p.h_range_flag, 0, (size_t)p.h_range_words * sizeof(unsigned));
-    const float* w = weights;
-    const int nb = desc->nb;
     const size_t B = (size_t)max_batch;
     // (qmri_get_health: where the set-up time goes -- the layers' weight packing and upload, the tensors, the calibration probe)
     typedef std::chrono::steady_clock Clk;
     const auto t_begin = Clk::now();
     double ms_pack = std::chrono::duration<double, std::milli>(t_begin - t_upload).count();      // (the blob's upload / host copy and range check)
-    auto add_layer_timed = [&](qmri_ctx* c, ConvKind kind, int cin, int cout, const float*& wp) {
-        const auto t0 = Clk::now();
-        const int rc = add_layer(c, kind, cin, cout, wp);
-        ms_pack += std::chrono::duration<double, std::milli>(Clk::now() - t0).count();
-        return rc;
-    };
-    if (desc->arch == QMRI_ARCH_UNETRES) {
-        const int32_t* nc = desc->nc;
-        QMRI_TRY(add_layer_timed(ctx, CONV_3X3, desc->in_nc, nc[0], w));
-        for (int l = 0; l < 3; ++l) {
-            for (int b = 0; b < 2 * nb; ++b) QMRI_TRY(add_layer_timed(ctx, CONV_3X3, nc[l], nc[l], w));
-            QMRI_TRY(add_layer_timed(ctx, CONV_DOWN, nc[l], nc[l + 1], w));
-        }
-        for (int b = 0; b < 2 * nb; ++b) QMRI_TRY(add_layer_timed(ctx, CONV_3X3, nc[3], nc[3], w));
-        for (int l = 3; l > 0; --l) {
-            QMRI_TRY(add_layer_timed(ctx, CONV_UP, nc[l], nc[l - 1], w));
-            for (int b = 0; b < 2 * nb; ++b) QMRI_TRY(add_layer_timed(ctx, CONV_3X3, nc[l - 1], nc[l - 1], w));
-        }
-        QMRI_TRY(add_layer_timed(ctx, CONV_3X3, nc[0], desc->out_nc, w));
-        for (int l = 0; l < 4; ++l) {
-            // channels allocated = the largest padded Cin of any layer that reads a level-l tensor
-            int cal = conv_cin_pad(CONV_3X3, nc[l]);
-            if (l < 3) cal = std::max(cal, conv_cin_pad(CONV_DOWN, nc[l]));
-            if (l > 0) cal = std::max(cal, conv_cin_pad(CONV_UP, nc[l]));
-            QMRI_TRY(alloc_tensor(ctx, p.x[l], nc[l], cal, H >> l, W >> l, B));
-            QMRI_TRY(alloc_tensor(ctx, p.a[l], nc[l], cal, H >> l, W >> l, B));
-            QMRI_TRY(alloc_tensor(ctx, p.t[l], nc[l], cal, H >> l, W >> l, B));
-        }
-        if (nc[0] == 64 && H % 16 == 0 && W % 16 == 0 && (H / 16) * (W / 16) <= 1024) {                   // k_conv6r's exchange buffer (one slice)
-            p.res_tiles = (H / 16) * (W / 16);
-            QMRI_TRY(p.pool.alloc(ctx, &p.d_res_xbuf, conv6r_xbuf_bytes(p.res_tiles)));
-            QMRI_HIP(ctx, hipMemset(p.d_res_xbuf, 0, conv6r_xbuf_bytes(p.res_tiles)));
-            p.res_epoch = 0; p.res_off = false;
-            if (qmri_knob(K_RES_STAMPS)) { QMRI_TRY(p.pool.alloc(ctx, &p.d_res_stamps, 2048 * sizeof(unsigned long long))); QMRI_HIP(ctx, hipMemset(p.d_res_stamps, 0, 2048 * sizeof(unsigned long long))); }
-        }
-    } else {
-        const int width = desc->nc[0];
-        if (nb == 1) QMRI_TRY(add_layer_timed(ctx, CONV_3X3, desc->in_nc, desc->out_nc, w));
-        else {
-            QMRI_TRY(add_layer_timed(ctx, CONV_3X3, desc->in_nc, width, w));
-            for (int l = 1; l < nb - 1; ++l) QMRI_TRY(add_layer_timed(ctx, CONV_3X3, width, width, w));
-            QMRI_TRY(add_layer_timed(ctx, CONV_3X3, width, desc->out_nc, w));
-        }
-        QMRI_TRY(alloc_tensor(ctx, p.a[0], width, conv_cin_pad(CONV_3X3, width), H, W, B));
-        QMRI_TRY(alloc_tensor(ctx, p.t[0], width, conv_cin_pad(CONV_3X3, width), H, W, B));
+    for (const NetStep& s : p.prog.steps) QMRI_TRY(add_layer(ctx, s, weights));
+    ms_pack += std::chrono::duration<double, std::milli>(Clk::now() - t_begin).count();
+    for (int id = 0; id < NT_IN32; ++id)                           // the interior tensors the architecture has, level after level
+        if (p.prog.chan[id]) QMRI_TRY(alloc_tensor(ctx, (NetTensor)id, B));
+    // k_conv6r's exchange buffer (one slice): where the program has runs to offer it (64 channels at full resolution: conv6r_try)
+    if (!p.prog.runs.empty() && desc->nc[0] == 64 && H % 16 == 0 && W % 16 == 0 && (H / 16) * (W / 16) <= 1024) {
+        p.res_tiles = (H / 16) * (W / 16);
+        QMRI_TRY(p.pool.alloc(ctx, &p.d_res_xbuf, conv6r_xbuf_bytes(p.res_tiles)));
+        QMRI_HIP(ctx, hipMemset(p.d_res_xbuf, 0, conv6r_xbuf_bytes(p.res_tiles)));
+        p.res_epoch = 0; p.res_off = false;
+        if (qmri_knob(K_RES_STAMPS)) { QMRI_TRY(p.pool.alloc(ctx, &p.d_res_stamps, 2048 * sizeof(unsigned long long))); QMRI_HIP(ctx, hipMemset(p.d_res_stamps, 0, 2048 * sizeof(unsigned long long))); }
     }
     if (p.d_wflat) {
         const auto t0 = Clk::now();
@@ -335,15 +289,11 @@ extern "C" int qmri_set_denoiser(qmri_ctx* ctx, const qmri_net_desc* desc, const
         QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));          // (the time of the packing kernels belongs to this figure)
         ms_pack += std::chrono::duration<double, std::milli>(Clk::now() - t0).count();
     }
-    p.w_begin = nullptr;                                           // (the caller's pointer is not kept)
-    QMRI_TRY(alloc_tensor(ctx, p.in32, desc->in_nc, conv_cin_pad(CONV_3X3, desc->in_nc), H, W, B));
-    QMRI_TRY(alloc_tensor(ctx, p.out32, desc->out_nc, desc->out_nc, H, W, B));
-    // BLOCKED interior tensors (PTensor::blk): every layer on the conv6 kernels, every interior channel count a multiple of 8
-    p.blk_ok = conv6_enabled();
+    QMRI_TRY(alloc_tensor(ctx, NT_IN32, B));
+    QMRI_TRY(alloc_tensor(ctx, NT_OUT32, B));
+    // BLOCKED interior tensors (PTensor::blk): every layer on the conv6 kernels, every interior channel count a multiple of 8 (net_plan.h)
+    p.blk_ok = conv6_enabled() && p.prog.blk_ok;
     for (const ConvLayer& L : p.layers) if (!L.wp6) p.blk_ok = false;
-    if (desc->arch == QMRI_ARCH_UNETRES) { for (int l = 0; l < 4; ++l) if (desc->nc[l] % 8) p.blk_ok = false; }
-    else if (nb > 1 && desc->nc[0] % 8) p.blk_ok = false;
-    for (int l = 0; l < 4; ++l) if ((p.x[l].p && p.x[l].Cal % 8) || (p.a[l].p && p.a[l].Cal % 8) || (p.t[l].p && p.t[l].Cal % 8)) p.blk_ok = false;
     p.interior_fmt = -1;
     QMRI_TRY(p.pool.alloc(ctx, &p.d_counter, (size_t)1));
     QMRI_HIP(ctx, hipMemset(p.d_counter, 0, sizeof(unsigned)));
@@ -363,28 +313,36 @@ extern "C" int qmri_set_denoiser(qmri_ctx* ctx, const qmri_net_desc* desc, const
     return QMRI_OK;
 }
 
-// nb ResBlocks: cur <- cur + conv(relu(conv(cur)))  (basicblock.py:211-223).  `src` is the block input of the first
-// ResBlock (may be a skip tensor that must stay intact); results land in `cur`; `skip` is added by the last conv.
-static int run_resblocks(qmri_ctx* ctx, size_t& li, int nb, int B, const PTensor& src, const PTensor& cur, const PTensor& tmp,
-                         const PTensor* skip) {
+// The layer program (net_plan.h), step by step: one launch per layer -- but where resident-run candidates start at a step, the first one conv6r_try
+// takes runs all its member layers as ONE launch with resident tiles (the full-resolution level; knobs res_head / res_tail / res_down = 0 keep the
+// head / tail / down-sampling convolution out of such a launch).
+static int net_forward_layers(qmri_ctx* ctx, int B) {
     NetPlan& p = ctx->net;
-    if (p.d_res_xbuf && src.H == p.H && src.W == p.W && !p.force_f32) {            // the full-resolution level: one launch with resident tiles where it applies
-        bool done = false;
-        Conv6rRun r;
-        r.res = &p.layers[li]; r.nres = 2 * nb; r.src = &src; r.cur = &cur; r.skip = skip;
-        QMRI_TRY(conv6r_try(ctx, r, B, &done));
-        if (done) { li += (size_t)(2 * nb); return QMRI_OK; }
-    }
-    const PTensor* in = &src;
-    for (int b = 0; b < nb; ++b) {
-        QMRI_TRY(conv_launch(ctx, p.layers[li++], B, *in, tmp, nullptr, nullptr, 1));
-        QMRI_TRY(conv_launch(ctx, p.layers[li++], B, tmp, cur, in, (b == nb - 1) ? skip : nullptr, 0));
-        in = &cur;
+    const std::vector<NetStep>& steps = p.prog.steps;
+    const std::vector<NetRun>& runs = p.prog.runs;
+    const bool resident = p.d_res_xbuf && !p.force_f32;
+    const bool res_head = qmri_knob(K_RES_HEAD) != 0, res_tail = qmri_knob(K_RES_TAIL) != 0, res_down = qmri_knob(K_RES_DOWN) != 0;
+    auto ten = [&p](NetTensor id) -> const PTensor* { return id == NT_NONE ? nullptr : &p.ten[id]; };
+    auto layer = [&p](int i) -> const ConvLayer* { return i < 0 ? nullptr : &p.layers[i]; };
+    size_t ri = 0;
+    for (size_t i = 0; i < steps.size();) {
+        bool taken = false;
+        for (; !taken && ri < runs.size() && runs[ri].first <= (int)i; ++ri) {
+            const NetRun& c = runs[ri];
+            if (c.first != (int)i || !resident || !net_run_allowed(c, res_head, res_tail, res_down)) continue;
+            Conv6rRun r;
+            r.head = layer(c.head); r.head_in = ten(c.head_in); r.res = layer(c.res); r.nres = c.nres; r.src = ten(c.src); r.cur = ten(c.cur); r.skip = ten(c.skip);
+            r.tail = layer(c.tail); r.tail_out = ten(c.tail_out); r.down = layer(c.down); r.down_out = ten(c.down_out);
+            QMRI_TRY(conv6r_try(ctx, r, B, &taken));
+            if (taken) i += (size_t)c.count;
+        }
+        if (taken) continue;
+        const NetStep& s = steps[i];
+        QMRI_TRY(conv_launch(ctx, p.layers[i], B, p.ten[s.in], p.ten[s.out], ten(s.add1), ten(s.add2), s.relu_out));
+        ++i;
     }
     return QMRI_OK;
 }
-
-static int net_forward_layers(qmri_ctx* ctx, int B);
 
 // network forward on the context's padded tensors: in32 -> out32
 static int net_forward_padded(qmri_ctx* ctx, int B) {
@@ -394,15 +352,13 @@ static int net_forward_padded(qmri_ctx* ctx, int B) {
         // channel counts).  The two formats put the zero halo at different addresses: a change of format re-zeroes the tensors.
         NetPlan& p = ctx->net;
         const bool blk = p.blk_ok && !p.force_f32 && conv6_enabled();
-        if (p.interior_fmt != -1 && p.interior_fmt != (blk ? 1 : 0)) {
-            PTensor* ts[12];
-            int nt = 0;
-            for (int l = 0; l < 4; ++l) { ts[nt++] = &p.x[l]; ts[nt++] = &p.a[l]; ts[nt++] = &p.t[l]; }
-            for (int i = 0; i < nt; ++i)
-                if (ts[i]->p) QMRI_HIP(ctx, hipMemsetAsync(ts[i]->p, 0, ((size_t)p.maxB * ts[i]->batch_stride() + 8192) * sizeof(float), ctx->stream));
+        const bool rezero = p.interior_fmt != -1 && p.interior_fmt != (blk ? 1 : 0);
+        for (int id = 0; id < NT_IN32; ++id) {
+            PTensor& t = p.ten[id];
+            if (rezero && t.p) QMRI_HIP(ctx, hipMemsetAsync(t.p, 0, ((size_t)p.maxB * t.batch_stride() + 8192) * sizeof(float), ctx->stream));
+            t.blk = blk;
         }
         p.interior_fmt = blk ? 1 : 0;
-        for (int l = 0; l < 4; ++l) { p.x[l].blk = blk; p.a[l].blk = blk; p.t[l].blk = blk; }
     }
     const bool report = !ctx->net.force_f32;                        // (the calibration's f32 pass reports nothing)
     const bool timed = ctx->prof_level >= 2;                        // profile level 2: the whole pass between two stream events (besides the per-launch pairs)
@@ -418,60 +374,6 @@ static int net_forward_padded(qmri_ctx* ctx, int B) {
         QMRI_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]));
         ctx->prof.ms_net_forward += ms; ctx->prof.n_net_forward += 1;
     }
-    return QMRI_OK;
-}
-
-static int net_forward_layers(qmri_ctx* ctx, int B) {
-    NetPlan& p = ctx->net;
-    const int nb = p.desc.nb;
-    size_t li = 0;
-    if (p.desc.arch == QMRI_ARCH_SEQ_CONV) {
-        const size_t nl = p.layers.size();
-        const PTensor* in = &p.in32;
-        const PTensor* bufs[2] = { &p.a[0], &p.t[0] };
-        for (size_t l = 0; l < nl; ++l) {
-            const PTensor* out = (l == nl - 1) ? &p.out32 : bufs[l & 1];
-            QMRI_TRY(conv_launch(ctx, p.layers[l], B, *in, *out, nullptr, nullptr, l != nl - 1));
-            in = out;
-        }
-        return QMRI_OK;
-    }
-    // UNetRes.forward, network_unet.py:106-117
-    // (the head belongs to the down path's resident-tile launch of the full-resolution level where that applies: knob res_head = 0 keeps it apart)
-    const bool res_head = qmri_knob(K_RES_HEAD) != 0, res_tail = qmri_knob(K_RES_TAIL) != 0, res_down = qmri_knob(K_RES_DOWN) != 0;
-    bool head_done = false, down_done = false;
-    if (res_head && p.d_res_xbuf && !p.force_f32 && p.layers.size() >= (size_t)(2 + 2 * nb)) {
-        Conv6rRun r;
-        r.head = &p.layers[0]; r.head_in = &p.in32; r.res = &p.layers[1]; r.nres = 2 * nb; r.src = &p.x[0]; r.cur = &p.a[0];
-        if (res_down) {                                             // ... and the level's down-sampling convolution behind them
-            r.down = &p.layers[1 + 2 * nb]; r.down_out = &p.x[1];
-            QMRI_TRY(conv6r_try(ctx, r, B, &down_done));
-            if (down_done) { head_done = true; li = (size_t)(2 + 2 * nb); }
-            r.down = nullptr; r.down_out = nullptr;
-        }
-        if (!down_done) {
-            QMRI_TRY(conv6r_try(ctx, r, B, &head_done));
-            if (head_done) li = (size_t)(1 + 2 * nb);
-        }
-    }
-    if (!head_done) QMRI_TRY(conv_launch(ctx, p.layers[li++], B, p.in32, p.x[0], nullptr, nullptr, 0));      // x1 = m_head(x0)
-    for (int l = 0; l < 3; ++l) {                                                                          // x_{l+2} = m_down_{l+1}(x_{l+1})
-        if (!(l == 0 && head_done)) QMRI_TRY(run_resblocks(ctx, li, nb, B, p.x[l], p.a[l], p.t[l], nullptr));
-        if (!(l == 0 && down_done)) QMRI_TRY(conv_launch(ctx, p.layers[li++], B, p.a[l], p.x[l + 1], nullptr, nullptr, 0));
-    }
-    QMRI_TRY(run_resblocks(ctx, li, nb, B, p.x[3], p.a[3], p.t[3], &p.x[3]));                               // m_body(x4) + x4
-    for (int l = 3; l > 0; --l) {                                                                          // m_up_l(x + x_{l+1})
-        QMRI_TRY(conv_launch(ctx, p.layers[li++], B, p.a[l], p.a[l - 1], nullptr, nullptr, 0));               // transposed conv
-        if (l == 1 && res_tail && p.d_res_xbuf && !p.force_f32 && li + (size_t)(2 * nb) < p.layers.size()) {   // ... the level's ResBlocks and the tail in one launch
-            bool done = false;
-            Conv6rRun r;
-            r.res = &p.layers[li]; r.nres = 2 * nb; r.src = &p.a[0]; r.cur = &p.a[0]; r.skip = &p.x[0]; r.tail = &p.layers[li + 2 * nb]; r.tail_out = &p.out32;
-            QMRI_TRY(conv6r_try(ctx, r, B, &done));
-            if (done) { li += (size_t)(2 * nb + 1); return QMRI_OK; }
-        }
-        QMRI_TRY(run_resblocks(ctx, li, nb, B, p.a[l - 1], p.a[l - 1], p.t[l - 1], &p.x[l - 1]));
-    }
-    QMRI_TRY(conv_launch(ctx, p.layers[li++], B, p.a[0], p.out32, nullptr, nullptr, 0));                      // m_tail(x + x1)
     return QMRI_OK;
 }
 
@@ -503,9 +405,9 @@ extern "C" int qmri_net_forward_dev(qmri_ctx* ctx, const float* d_in, int B, flo
     // (then the bf16 scheme) -- and one may follow the other: up to three passes, and a call that still wants another one is an error, not QMRI_OK.
     bool again = false;
     for (int attempt = 0; attempt < 3; ++attempt) {
-        QMRI_TRY(ew_launch_pack(ctx, B, p.desc.in_nc, p.H, p.W, d_in, 0, p.in32));
+        QMRI_TRY(ew_launch_pack(ctx, B, p.desc.in_nc, p.H, p.W, d_in, 0, p.ten[NT_IN32]));
         QMRI_TRY(net_forward(ctx, B));
-        QMRI_TRY(ew_launch_unpack(ctx, B, p.desc.out_nc, p.H, p.W, p.out32, p.in32, 0, d_out, 0));
+        QMRI_TRY(ew_launch_unpack(ctx, B, p.desc.out_nc, p.H, p.W, p.ten[NT_OUT32], p.ten[NT_IN32], 0, d_out, 0));
         again = false;
         if (p.sp6 != 2) break;                              // (the bf16 scheme has no range to guard: stays asynchronous)
         QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -593,9 +495,9 @@ extern "C" int qmri_denoise(qmri_ctx* ctx, const double* in, int H, int W, int C
     bool again = false;
     auto pass = [&]() -> int {
         if (hipMemcpyAsync(d_io, in, nin * sizeof(double), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return QMRI_ERR_HIP;
-        QMRI_TRY(ew_launch_pack(ctx, B, C, H, W, d_io, 1, p.in32, in_scale));                      // im2single: :72-77
+        QMRI_TRY(ew_launch_pack(ctx, B, C, H, W, d_io, 1, p.ten[NT_IN32], in_scale));                      // im2single: :72-77
         QMRI_TRY(net_forward(ctx, B));                                                            // activations(...): :88
-        QMRI_TRY(ew_launch_unpack(ctx, B, p.desc.out_nc, H, W, p.out32, p.in32, p.desc.residual_noise, d_io, 1, out_scale));
+        QMRI_TRY(ew_launch_unpack(ctx, B, p.desc.out_nc, H, W, p.ten[NT_OUT32], p.ten[NT_IN32], p.desc.residual_noise, d_io, 1, out_scale));
         if (hipMemcpyAsync(out, d_io, nout * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return QMRI_ERR_HIP;
         if (hipStreamSynchronize(ctx->stream) != hipSuccess) return QMRI_ERR_HIP;
         return net_range_tripped(ctx, again);

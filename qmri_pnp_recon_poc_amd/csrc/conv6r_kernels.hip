@@ -756,7 +756,8 @@ __global__ __launch_bounds__(NT6) void k_conv6r(const Conv6rArgs A) {
 }  // namespace
 
 // A run of the full-resolution level's 3x3 layers as ONE launch with resident tiles (k_conv6r, Conv6rRun in qmri_internal.h).  *done = false: not
-// eligible, nothing launched.
+// eligible, nothing launched.  The runs it is offered are the layer program's candidates (net_plan.h NetRun).
+static_assert(NET_RUN_MAXL == R_MAXL, "net_plan.h NET_RUN_MAXL and R_MAXL");
 int conv6r_try(qmri_ctx* ctx, const Conv6rRun& run, int B, bool* done) {
     *done = false;
     NetPlan& net = ctx->net;

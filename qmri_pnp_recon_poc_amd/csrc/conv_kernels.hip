@@ -436,18 +436,15 @@ int launch_kind(qmri_ctx* ctx, ConvLayer& L, int B, const PTensor& in, const PTe
 
 }  // namespace
 
-int conv_cin_pad(ConvKind kind, int Cin) {
-    if (kind == CONV_3X3 && Cin <= 64) kind = CONV_3X3N;
-    const int CC = kind_cc(kind);
-    return std::max(2 * CC, ((Cin + CC - 1) / CC) * CC);
-}
+// (conv_cin_pad, net_plan.h, sizes the tensors from the chunk of each kind)
+static_assert(CONV_CHUNK[CONV_3X3] == Geo<CONV_3X3>::CC && CONV_CHUNK[CONV_3X3N] == Geo<CONV_3X3N>::CC && CONV_CHUNK[CONV_DOWN] == Geo<CONV_DOWN>::CC &&
+              CONV_CHUNK[CONV_UP] == Geo<CONV_UP>::CC, "net_plan.h CONV_CHUNK and Geo<KIND>::CC");
 
 void conv_plan_layer(ConvLayer& L, ConvKind kind, int Cin, int Cout) {
-    if (kind == CONV_3X3 && Cin <= 64) kind = CONV_3X3N;       // narrow layers: 32-channel chunks
+    kind = conv_narrow(kind, Cin);
     L.kind = kind; L.Cin = Cin; L.Cout = Cout;
-    const int CC = kind_cc(kind);
-    L.cin_pad = std::max(2 * CC, ((Cin + CC - 1) / CC) * CC);   // >= 2 chunks: the tile pipeline needs a barrier between
-    const int rows = (kind == CONV_UP) ? 4 * Cout : Cout;       // a tile's first step and its last
+    L.cin_pad = conv_cin_pad(kind, Cin);
+    const int rows = (kind == CONV_UP) ? 4 * Cout : Cout;
     L.n_ct = (rows + 31) / 32;
     L.MT = 1;
     L.wp_floats = 0;

@@ -46,6 +46,8 @@ void qmri_set_error(qmri_ctx* ctx, const char* fmt, ...);
 // What the host decides about a gridded operator, in plain C++ (op_plan.h): the mask builders, the k-sorted sample list (KEntry), the work units of
 // the k-space LSQR (KSample, KsGroup, KsUnit, KS_CAPS, ks_plan_units) and the DIRECT solver's tables.
 #include "op_plan.h"
+// The denoiser's layer program, in plain C++ (net_plan.h): ConvKind, conv_cin_pad, the tensor ids (NetTensor), the steps and the resident-run candidates.
+#include "net_plan.h"
 
 // ---------------------------------------------------------------------------------------------------
 // A/B and diagnostic switches ("knobs").  ONE environment variable, QMRI_DEBUG="name=value,name=value" (read once per process), and
@@ -154,7 +156,6 @@ struct LsqrDev {
 // ---------------------------------------------------------------------------------------------------
 // denoiser: one packed layer of the conv engine
 // ---------------------------------------------------------------------------------------------------
-enum ConvKind { CONV_3X3 = 0, CONV_DOWN = 1, CONV_UP = 2, CONV_3X3N = 3 };   // 3X3N: 3x3 with 32-channel chunks (Cin <= 64)
 struct ConvLayer {
     ConvKind kind;
     int Cin, Cout;           // logical channels (UP: Cout = real output channels)
@@ -197,11 +198,11 @@ struct ActCheckArgs { const float* slots; int* count; float* ref; int record; un
 struct NetPlan {
     qmri_net_desc desc{};
     int H = 0, W = 0, maxB = 0;
-    std::vector<ConvLayer> layers;
-    // activation buffers (device, padded planes): per UNet level the skip tensor x and two work tensors a, t
-    PTensor x[4], a[4], t[4];
-    PTensor in32;            // normalised network input (in_nc channels, allocated up to the head's padded Cin)
-    PTensor out32;           // network output (out_nc channels)
+    NetProgram prog;         // the layer program (net_plan.h): one step per layer, and the runs the resident-tile launch is offered
+    std::vector<ConvLayer> layers;   // ... one per step
+    // activation buffers (device, padded planes), by tensor id (NetTensor): per UNet level the skip tensor x and two work tensors a, t;
+    // NT_IN32 the normalised network input (in_nc channels, allocated up to the first layer's padded Cin), NT_OUT32 the network output (out_nc channels)
+    PTensor ten[NT_COUNT];
     DevPool pool;            // the tensors above and the plan-lifetime arrays below
     unsigned* d_counter = nullptr;   // tile-queue counter of the persistent conv kernels
     unsigned counter_base = 0;       // host mirror of its value after the launches issued so far
@@ -224,7 +225,6 @@ struct NetPlan {
     int interior_fmt = -1;           // format the interior tensors were last written in (-1: untouched zeros, 0 planar, 1 blocked): a change re-zeroes them (halo)
     std::vector<float> w_host;       // the caller's weights (kept to re-pack the layers for the other scheme; knob pack_gpu = 0 only)
     float* d_wflat = nullptr;        // ... on the device, in the caller's order (knob pack_gpu = 1, default: the packers run there)
-    const float* w_begin = nullptr;  // (inside qmri_set_denoiser only: start of the caller's blob, for the layers' offsets)
     std::vector<float> w_max;        // ... and every layer's largest |w| (from the device): the f16 scheme's per-layer scale
     DevArr<float> d_c6part;          // split-K partial outputs of k_conv6 (conv6_kernels.hip), grown on demand
     void* d_stamps = nullptr;        // diagnostic: per-workgroup timing stamps of the last conv launch (knob conv_stamps = 1)
@@ -641,7 +641,6 @@ int ew_launch_coil_sum(qmri_ctx* ctx, size_t n, size_t plane, int cnt, const dou
 // conv engine (conv_kernels.hip)
 int conv_launch(qmri_ctx* ctx, ConvLayer& L, int B, const PTensor& in, const PTensor& out, const PTensor* add1,
                 const PTensor* add2, int relu_out);
-int conv_cin_pad(ConvKind kind, int Cin);
 // profile level 2: what an event pair times
 enum { PROF_CONV3 = 0, PROF_CONV2 = 1, PROF_LSQR = 2, PROF_TV = 3 };
 int qmri_prof_pair(qmri_ctx* ctx, hipEvent_t* start, hipEvent_t* stop, int kind = PROF_CONV3, double flop = 0.0);   // profile level 2: next event pair (else nullptrs)

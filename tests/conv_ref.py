@@ -121,7 +121,8 @@ def seq_conv(x, w, in_nc, out_nc, width, nb, taps=None):
 
 
 def unetres(x, w, in_nc, out_nc, nc, nb, taps=None):
-    """UNetRes in the layer order of net_forward_layers (api_net.cpp): head; per level nb ResBlocks cur + conv(relu(conv(cur))) then the
+    """UNetRes in the layer order of the library's layer program (csrc/net_plan.h net_plan_build; tests/test_net_plan_host.py executes that program
+    against this function): head; per level nb ResBlocks cur + conv(relu(conv(cur))) then the
     strided conv; body plus skip; per level the transposed conv, ResBlocks plus skip; tail.  taps: receives every tensor a kernel writes."""
     it = iter(split_blob(w, [s for _, s in unetres_shapes(in_nc, out_nc, nc, nb)]))
 

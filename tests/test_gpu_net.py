@@ -498,6 +498,40 @@ def test_resident_tile_launch_changes_no_bit(engine_mod, synth):
         e.close()
 
 
+# (B, resident form) -> n_conv3x3, n_conv2x2, flop_conv3x3, flop_conv2x2 of ONE denoise call at profile level 2: 32 x 32, the product's channel counts,
+# in_nc = 11, 64 layers.  Recorded from the library of commit 1e81bb66cf195b07b9d0feeafaae026aa5406ef5, the last one whose forward pass was a hand-written
+# walk (api_net.cpp net_forward_layers / run_resblocks), run beside the library that walks the layer program on one device: both gave these figures.
+# Resident form taken: head + 8 ResBlock layers + down-sampling conv are one 3x3 unit, 8 ResBlock layers + tail another (58 - 9 - 9 + 2, 6 - 1).
+LAUNCH_UNITS_1E81BB6 = {
+    (1, 1): (42, 5, 4269408256.0, 83886080.0),
+    (1, 0): (58, 6, 4252631040.0, 100663296.0),
+    (2, 1): (58, 6, 8505262080.0, 201326592.0),                     # (slice batches: conv6r_try declines, one launch per layer)
+}
+
+
+@pytest.mark.parametrize("B,resident", sorted(LAUNCH_UNITS_1E81BB6))
+def test_forward_pass_launch_units_and_flop_are_unchanged(engine_mod, synth, B, resident):
+    """The layer program (csrc/net_plan.h) regroups nothing: a forward pass has the launch units, and the algorithmic flop inside them, that the
+    hand-written walk had -- with the resident-tile form taken, switched off, and declined."""
+    e = engine_mod.Engine(0)
+    e.set_denoiser(synth.random_weights(seed=1, gain=0.7, in_nc=11), 32, 32, in_nc=11, max_batch=2)
+    assert e.denoiser_scheme() == (2, 0)
+    x = synth.uniform01(5, 32 * 32 * 11 * B).reshape(32, 32, 11, B)
+    x = x if B > 1 else x[..., 0]
+    e.conv_resident(resident)
+    e.denoise(x)
+    e.profile_enable(2)
+    e.profile_get(reset=True)
+    e.denoise(x)
+    p = e.profile_get(reset=True)
+    e.profile_enable(0)
+    got = (p["n_conv3x3"], p["n_conv2x2"], p["flop_conv3x3"], p["flop_conv2x2"])
+    print(f"B = {B}, resident = {resident}: {got}")
+    assert e.denoiser_scheme() == (2, 0) and e.conv_resident(1) == 0
+    e.close()
+    assert got == LAUNCH_UNITS_1E81BB6[(B, resident)]
+
+
 def test_resident_tile_launch_recovers_from_a_lost_hand_off(engine_mod, synth, capfd):
     """The workgroups of k_conv6r wait for each other's edge pixels.  Every wait is bounded: with the hook at 2 one tile publishes nothing, its
     neighbours' fetches time out and raise bit 2 of the range flag, the library says so on stderr, repeats the call with one launch per layer
