@@ -408,6 +408,56 @@ int qmri_dict_match_grouped(qmri_ctx* ctx, const void* X, int Npix, const double
 int qmri_dict_match_grouped_dev(qmri_ctx* ctx, const void* d_X, int Npix, const double* d_sel, float* d_qmap, float* d_pd, float* d_mt, int32_t* d_dm,
                                 int32_t* d_grp, float* d_xfit);
 
+/* ---- the B1 map estimated from the fingerprints by a windowed group match (extension, no reference counterpart, parity unpinned;
+ *      DESIGN.md section 28) --------------------------------------------------------------------------------------------------------------------
+ * The grouped match above needs a measured B1 map.  Without one, B1 can be taken from the fingerprints if it is held constant over a window: for
+ * unit-norm atoms min_rho ||x - rho d_k||^2 = ||x||^2 - |<d_k, x>|^2, so under white noise the maximum-likelihood group of a window maximises the
+ * summed explained energy sum_{p in window} max_{k in g} |<d_k, x_p>|^2, with T1, T2 and PD free per pixel.  Two stages and one composed call.
+ *
+ * Stage 1, group scores.  score: G x Npix float32, the pixel contiguous (score[g * Npix + p]).  score[g][p] is, BIT FOR BIT, the mt that
+ * qmri_dict_match_grouped returns for pixel p when sel[p] = group_val[g]: max over the atoms of group g of sqrtf(fmaf(im, im, re * re)) of the
+ * single-precision fmaf chain over c = 0 .. s-1, whatever that gives for zero and non-finite pixels (-1 for a pixel whose magnitudes are all NaN).
+ * X as in qmri_dict_match.  Refusals: Npix < 1, NULL X or score: QMRI_ERR_INVALID_ARG (also with ctx == NULL); no dictionary or no groups:
+ * QMRI_ERR_STATE; a wide dictionary (s > 16): QMRI_ERR_UNSUPPORTED. */
+int qmri_dict_group_scores(qmri_ctx* ctx, const void* X, int Npix, float* score);
+/* The same on device arrays, asynchronous on ctx's stream. */
+int qmri_dict_group_scores_dev(qmri_ctx* ctx, const void* d_X, int Npix, float* d_score);
+/* Stage 2, pooled argmax; needs no dictionary.  Pixel p = i + N j inside a slice (i < N contiguous, j < M), nslices slices stacked;
+ * score: G x (nslices N M) float32 as above; mask (nullable): one uint8 per pixel, non-zero = foreground; half_window h, 0 <= h <= 32.
+ * Everything in fp64.  E[g][p] = (double)S (double)S where p is foreground and S = score[g][p] is finite and > 0, else 0.
+ *   T[g][i, j] = sum over d = -h .. h, ascending, of E[g][i + d, j];   P[g][i, j] = sum over d ascending of T[g][i, j + d];
+ * terms outside the slice are skipped (a window never crosses a slice), the additions are plain and left to right (direct sums, no running sum).
+ * g^ = the LOWEST g with the largest P.  grp[p] = g^ + 1, b1[p] = group_val[g^], conf[p] = (P_best - P_second) / P_best with P_second the largest P
+ * among the other groups (conf = 1 for G = 1).  A background pixel, or one whose P_best is not > 0: grp 0, b1 NaN, conf 0 -- NaN is what the grouped
+ * match treats as unmatched.  A slice's bits do not depend on the stack.  b1, grp, conf: nslices N M entries each, every one nullable.
+ * group_val: G doubles ON THE HOST in both variants.  QMRI_ERR_INVALID_ARG (also with ctx == NULL): G outside 1 .. 256, group_val NULL, non-finite
+ * or not strictly ascending, h outside 0 .. 32, N, M or nslices < 1, score NULL. */
+int qmri_b1_pool(qmri_ctx* ctx, int G, const double* group_val, int N, int M, int nslices, const float* score, const uint8_t* mask, int half_window,
+                 double* b1, int32_t* grp, double* conf);
+/* The same on device arrays (group_val on the host), asynchronous on ctx's stream. */
+int qmri_b1_pool_dev(qmri_ctx* ctx, int G, const double* group_val, int N, int M, int nslices, const float* d_score, const uint8_t* d_mask,
+                     int half_window, double* d_b1, int32_t* d_grp, double* d_conf);
+/* Composed call: stage 1, then stage 2 with the dictionary's own groups, a run of slices at a time so that the scratch (G N M 12 bytes per slice)
+ * stays under 256 MB (one slice at least).  X: (nslices N M) x s complex doubles, column-major, as in qmri_dict_match.  The outputs are those of
+ * qmri_dict_group_scores followed by qmri_b1_pool, bit for bit.  params NULL: half_window 4.  Refusals: those of the two stages; a non-zero
+ * reserved entry, N M nslices beyond 2^31 - 1: QMRI_ERR_INVALID_ARG.  Not built: interpolation between groups, weights other than a 0/1 mask,
+ * wide dictionaries, the qmri_recon_batch* workers, estimating B1 inside the ADMM loop. */
+typedef struct {
+    int32_t half_window;     /* h: the window is (2h + 1) x (2h + 1) pixels, 0 <= h <= 32 */
+    int32_t reserved[7];     /* must be zero */
+} qmri_b1est_params;
+typedef struct {
+    int32_t n_estimated;     /* pixels with grp > 0 */
+    int32_t n_unmatched;     /* the others: background, or no positive pooled energy */
+    double mean_conf;        /* mean conf over the estimated pixels, summed in pixel order (0 when there is none) */
+    int32_t reserved[4];
+} qmri_b1est_info;
+int qmri_b1_estimate(qmri_ctx* ctx, const void* X, int N, int M, int nslices, const uint8_t* mask, const qmri_b1est_params* params, double* b1,
+                     int32_t* grp, double* conf, qmri_b1est_info* info);
+/* The same on device arrays, asynchronous on ctx's stream; info (nullable) is zeroed: it is filled by the host variant only. */
+int qmri_b1_estimate_dev(qmri_ctx* ctx, const void* d_X, int N, int M, int nslices, const uint8_t* d_mask, const qmri_b1est_params* params,
+                         double* d_b1, int32_t* d_grp, double* d_conf, qmri_b1est_info* info);
+
 /* ---- tissue-fraction maps: each pixel as a non-negative mix of chosen atoms (an EXTENSION, no reference counterpart, parity unpinned;
  *      DESIGN.md section 27) --------------------------------------------------------------------------------------------------------------------
  * The match above gives every pixel ONE atom.  A pixel that holds two or three tissues (a boundary, a thick slice) gets a (T1, T2) that belongs to

@@ -22,7 +22,8 @@ SYMBOLS = [
     "qmri_forward_f32", "qmri_adjoint_f32", "qmri_forward_dev", "qmri_adjoint_dev", "qmri_set_coils", "qmri_forward_mc", "qmri_adjoint_mc", "qmri_xupdate_mc", "qmri_pnp_admm_mc", "qmri_xupdate_mc_batch", "qmri_pnp_admm_mc_batch", "qmri_pnp_admm_mc_dev", "qmri_xupdate", "qmri_net_nparams", "qmri_set_denoiser", "qmri_denoise",
     "qmri_net_forward_dev", "qmri_denoiser_scheme", "qmri_pnp_admm", "qmri_pnp_admm_dev", "qmri_pnp_admm_batch", "qmri_set_dictionary", "qmri_dict_match",
     "qmri_dict_match_dev", "qmri_dict_match_xfit", "qmri_dict_match_xfit_dev", "qmri_set_dictionary_groups", "qmri_dict_group_assign", "qmri_dict_match_grouped",
-    "qmri_dict_match_grouped_dev", "qmri_set_components", "qmri_dict_unmix", "qmri_dict_unmix_dev", "qmri_recon_batch", "qmri_recon_batch_mc",
+    "qmri_dict_match_grouped_dev", "qmri_dict_group_scores", "qmri_dict_group_scores_dev", "qmri_b1_pool", "qmri_b1_pool_dev", "qmri_b1_estimate",
+    "qmri_b1_estimate_dev", "qmri_set_components", "qmri_dict_unmix", "qmri_dict_unmix_dev", "qmri_recon_batch", "qmri_recon_batch_mc",
     "qmri_coil_compress", "qmri_coil_compress_dev", "qmri_coil_eig", "qmri_recon_batch_mc_cc", "qmri_coil_maps", "qmri_coil_maps_dev", "qmri_dict_compress", "qmri_dict_compress_dev", "qmri_dict_simulate", "qmri_dict_simulate_dev", "qmri_dict_simulate_sp", "qmri_dict_simulate_sp_dev", "qmri_field_map_estimate", "qmri_field_map_estimate_dev", "qmri_llr_prox", "qmri_llr_prox_dev", "qmri_set_llr", "qmri_profile_enable", "qmri_profile_get", "qmri_get_health",
     "qmri_debug_lsqr_stamps", "qmri_debug_conv_stamps", "qmri_debug_lsqr_persist", "qmri_debug_dict_filter", "qmri_debug_conv_resident", "qmri_debug_dsvd_gram", "qmri_debug_epg_shift", "qmri_debug_knob", "qmri_debug_mem_stats",
     "qmri_onnx_read_unetres",
@@ -122,6 +123,14 @@ class LlrParams(C.Structure):
 
 class PvInfo(C.Structure):
     _fields_ = [("min_pivot", C.c_double), ("C", C.c_int32), ("s", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class B1estParams(C.Structure):
+    _fields_ = [("half_window", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
+class B1estInfo(C.Structure):
+    _fields_ = [("n_estimated", C.c_int32), ("n_unmatched", C.c_int32), ("mean_conf", C.c_double), ("reserved", C.c_int32 * 4)]
 
 
 class LrtvParams(C.Structure):
@@ -246,6 +255,12 @@ def lib() -> C.CDLL:
     L.qmri_dict_group_assign.argtypes = [i, dp, i, dp, ip]
     L.qmri_dict_match_grouped.argtypes = [vp, vp, i, dp, fp, fp, fp, ip, ip, fp]
     L.qmri_dict_match_grouped_dev.argtypes = [vp, vp, i, vp, vp, vp, vp, vp, vp, vp]
+    L.qmri_dict_group_scores.argtypes = [vp, vp, i, fp]
+    L.qmri_dict_group_scores_dev.argtypes = [vp, vp, i, vp]
+    L.qmri_b1_pool.argtypes = [vp, i, dp, i, i, i, fp, vp, i, dp, ip, dp]
+    L.qmri_b1_pool_dev.argtypes = [vp, i, dp, i, i, i, vp, vp, i, vp, vp, vp]
+    L.qmri_b1_estimate.argtypes = [vp, vp, i, i, i, vp, C.POINTER(B1estParams), dp, ip, dp, C.POINTER(B1estInfo)]
+    L.qmri_b1_estimate_dev.argtypes = [vp, vp, i, i, i, vp, C.POINTER(B1estParams), vp, vp, vp, C.POINTER(B1estInfo)]
     L.qmri_set_components.argtypes = [vp, i, ip, C.POINTER(PvInfo)]
     L.qmri_dict_unmix.argtypes = [vp, vp, i, i, dp, dp, dp, dp, ip]
     L.qmri_dict_unmix_dev.argtypes = [vp, vp, i, i, vp, vp, vp, vp, vp]

@@ -25,7 +25,7 @@ constexpr KnobDef g_knob_defs[] = {
     {K_CONV_MT2, "conv_mt2", 1024}, {K_CONV_OCC, "conv_occ", 2},
     {K_FUSE_EW, "fuse_ew", 1}, {K_LSQR_PERSIST, "lsqr_persist", 1}, {K_LSQR_FOLD, "lsqr_fold", 1}, {K_DICTW_LSP, "dictw_lsp", 2}, {K_VERBOSE, "verbose", 0},
     {K_PACK_GPU, "pack_gpu", 1}, {K_NUFFT_SEG, "nufft_seg", NU_SEG},
-    {K_FMAP_FUSE, "fmap_fuse", 0}, {K_FMAP_START, "fmap_start", 0},
+    {K_FMAP_FUSE, "fmap_fuse", 0}, {K_FMAP_START, "fmap_start", 0}, {K_B1_SCRATCH_MB, "b1_scratch_mb", 256},
 };
 constexpr bool knob_defs_follow_enum() {
     if (sizeof(g_knob_defs) / sizeof(g_knob_defs[0]) != K_COUNT) return false;

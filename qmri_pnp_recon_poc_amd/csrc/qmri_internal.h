@@ -79,6 +79,7 @@ enum QmriKnob {
     K_NUFFT_SEG,          // qmri_set_operator_nufft: samples per spreading segment (default NU_SEG = 512, at least 32); results change only in rounding
     K_FMAP_FUSE,          // qmri_field_map_estimate: 0 (default) one launch per iteration, 1 h iterations per launch on halo tiles in LDS (same bits; slower as measured)
     K_FMAP_START,         // qmri_field_map_estimate: 1 returns the start f0 (no iteration is run; info.iters = 0): what the tests feed back as f_init
+    K_B1_SCRATCH_MB,      // qmri_b1_estimate / qmri_b1_pool: MB of score + box-sum scratch a run of slices may take (default 256; one slice at least; same bits)
     K_COUNT
 };
 int qmri_knob(QmriKnob k);
@@ -517,6 +518,9 @@ struct DictHost {
     DevArr<int> d_gptr, d_gtile; DevArr<double> d_gval;
     DevArr<int> d_gwork;
     int slots_g = 0, slots_gf = 0;                        // as slots / slots_f, for the grouped instantiations
+    // the B1 estimate (dictb_kernels.hip, api_b1.cpp): scores and box sums of a run of slices, the atom parts' maxima, group_val of a pool call
+    DevArr<float> d_bscore, d_bpart; DevArr<double> d_bT, d_bval;
+    int slots_b = 0;                                      // workgroups of k_dictb_scores the device holds at once
     std::vector<float> D_h, normD_h;                      // narrow dictionaries: the caller's D [K x s column-major] and normD, kept for qmri_set_components
     PvHost pv;                                            // ... and the components in force (C = 0: none); dropped with the dictionary
 };
@@ -687,6 +691,11 @@ void dictg_free(qmri_ctx* ctx);
 int dictg_launch(qmri_ctx* ctx, const double2* d_X, int Npix, const double* d_sel, float* d_qmap, float* d_pd, float* d_mt, int32_t* d_dm, int32_t* d_grp,
                  float2* d_xfit);
 int dict_launch_merge(qmri_ctx* ctx, const float4* part, int P, int Npix, float* d_qmap, float* d_pd, float* d_mt, int32_t* d_dm, float4* win);
+// B1 estimate (dictb_kernels.hip): group scores of the pixels p0 .. p0 + n - 1 of X (Npix x s), d_score[g * n + i]; the pooled argmax of the slices
+// sl0 .. sl0 + nsl - 1, d_score[g * sstride + (pixel - soff)], mask and outputs by pixel of the whole stack
+int dictb_launch_scores(qmri_ctx* ctx, const double2* d_X, size_t Npix, size_t p0, int n, float* d_score);
+int b1_launch_pool(qmri_ctx* ctx, int G, const double* d_gval, int N, int M, int sl0, int nsl, const float* d_score, size_t sstride, size_t soff,
+                   const uint8_t* d_mask, int hw, double* d_b1, int32_t* d_grp, double* d_conf);
 // wide dictionaries (16 < s <= 1024; dictw_kernels.hip)
 int dictw_pack_dictionary(qmri_ctx* ctx, const float* D_host, int K, int s);    // fills ctx->dict.d_pack / G8 / ntiles
 int dictw_launch(qmri_ctx* ctx, const double2* d_X, int Npix, float* d_qmap, float* d_pd, float* d_mt, int32_t* d_dm, float4* win);

@@ -200,6 +200,37 @@ def unmix_mode(mode):
     return 0 if mode == "real" else 1
 
 
+def b1_window(window):
+    """The half window h of the B1 estimate as an int, 0 <= h <= 32 (the window is (2h + 1) x (2h + 1) pixels)."""
+    if isinstance(window, bool) or not isinstance(window, (int, float, np.integer, np.floating)) or int(window) != window or not (0 <= int(window) <= 32):
+        raise ValueError(f"window must be an integer half window in 0..32, not {window!r}")
+    return int(window)
+
+
+def b1_pool_arguments(score, group_val, mask=None):
+    """(score [G, npix] float32 C-contiguous, group_val [G] float64, mask [npix] uint8 or None, (N, M, nslices)) as qmri_b1_pool takes them.
+    score is [G, N, M] or [G, N, M, nslices], pixel i + N j of a slice (the first image axis contiguous); mask has the image's shape.  The
+    library checks group_val's contents."""
+    sc = np.asarray(score)
+    gv = np.asarray(group_val, dtype=np.float64)
+    if sc.ndim not in (3, 4) or gv.ndim != 1 or gv.size != sc.shape[0] or gv.size < 1:
+        raise ValueError("score must be [G, N, M] or [G, N, M, nslices] with one group_val per group, G >= 1")
+    if np.iscomplexobj(sc):
+        raise ValueError("score must be real")
+    lead = sc.shape[1:]
+    if min(lead) < 1:
+        raise ValueError("score must have at least one pixel")
+    N, M, nsl = lead[0], lead[1], (lead[2] if len(lead) == 3 else 1)
+    sb = np.ascontiguousarray(np.asarray(sc, dtype=np.float32).reshape((gv.size, -1), order="F"))
+    mb = None
+    if mask is not None:
+        m = np.asarray(mask)
+        if m.shape != lead:
+            raise ValueError(f"mask must have the image's shape {lead}, not {m.shape}")
+        mb = np.ascontiguousarray((m != 0).ravel(order="F").astype(np.uint8))
+    return sb, np.ascontiguousarray(gv), mb, (int(N), int(M), int(nsl))
+
+
 def dict_group_assign(group_val, sel):
     """The group of each selector value as the grouped dictionary match assigns it (qmri_dict_group_assign, host only): the lowest g minimising
     |sel - group_val[g]| in float64, 1-based; 0 for a non-finite value (unmatched).  Returns int32 in the shape of sel."""
@@ -926,6 +957,7 @@ class Engine:
         self.dict_shape = (K, s, Q)
         self._lut = np.asarray(lut, dtype=np.float64)
         self.components = None                                   # (qmri_set_dictionary drops them)
+        self.dict_groups = None                                  # (... and the groups)
 
     def set_components(self, atoms):
         """The components of tissue_fractions (extension, no reference counterpart; include/qmri.h qmri_set_components):
@@ -997,9 +1029,103 @@ class Engine:
         ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
         if group_ptr is None:
             self._check(self.L.qmri_set_dictionary_groups(self.h, 0, None, None))
+            self.dict_groups = None
             return
         gp, gv = group_arguments(group_ptr, group_val)
         self._check(self.L.qmri_set_dictionary_groups(self.h, gv.size, gp.ctypes.data_as(ip), gv.ctypes.data_as(dp)))
+        self.dict_groups = gv.copy()
+
+    # -- the B1 map from the fingerprints (extension, no reference counterpart) --
+    def _group_count(self):
+        gv = getattr(self, "dict_groups", None)
+        if getattr(self, "dict_shape", None) is None or gv is None:
+            raise ValueError("set_dictionary and set_dictionary_groups first")
+        return int(gv.size)
+
+    def group_scores(self, X):
+        """qmri_dict_group_scores: X [..., s] complex -> score [G, ...] float32, score[g] the mt of dict_match(X, sel=group_val[g]) for every
+        group g, bit for bit.  Needs a dictionary of s <= 16 channels with groups."""
+        G = self._group_count()
+        X = np.asarray(X, dtype=np.complex128)
+        s = self.dict_shape[1]
+        if X.ndim < 2 or X.shape[-1] != s:
+            raise ValueError("last dimension of X must equal the dictionary's channel count")
+        lead = X.shape[:-1]
+        npix = int(np.prod(lead))
+        xb = np.ascontiguousarray(X.reshape((npix, s), order="F").ravel(order="F"))
+        score = np.empty((G, npix), np.float32)
+        self._check(self.L.qmri_dict_group_scores(self.h, _vp(xb), npix, score.ctypes.data_as(C.POINTER(C.c_float))))
+        return score.reshape((G,) + lead, order="F")
+
+    def group_scores_dev(self, d_X: int, npix: int, d_score: int):
+        """qmri_dict_group_scores_dev: device pointers (X Npix x s complex double column-major, score G x Npix float32), asynchronous on the
+        engine's stream."""
+        self._check(self.L.qmri_dict_group_scores_dev(self.h, C.c_void_p(d_X), int(npix), C.c_void_p(d_score or None)))
+
+    def b1_pool(self, score, group_val, mask=None, window=4, want_b1=True, want_grp=True, want_conf=True):
+        """qmri_b1_pool: score [G, N, M] or [G, N, M, nslices] -> dict(b1 float64 (NaN where nothing was estimated), grp int32 (1-based, 0 none),
+        conf float64) in the image's shape: per pixel the lowest group with the largest energy score^2 summed over the (2 window + 1)^2 window, in
+        fp64 as include/qmri.h states it.  mask: non-zero = foreground.  Needs no dictionary."""
+        sb, gv, mb, (N, M, nsl) = b1_pool_arguments(score, group_val, mask)
+        h = b1_window(window)
+        lead = np.asarray(score).shape[1:]
+        n = N * M * nsl
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        b1 = np.empty(n, np.float64) if want_b1 else None
+        grp = np.empty(n, np.int32) if want_grp else None
+        conf = np.empty(n, np.float64) if want_conf else None
+        self._check(self.L.qmri_b1_pool(self.h, gv.size, gv.ctypes.data_as(dp), N, M, nsl, sb.ctypes.data_as(C.POINTER(C.c_float)),
+                                        _vp(mb) if mb is not None else None, h, b1.ctypes.data_as(dp) if want_b1 else None,
+                                        grp.ctypes.data_as(ip) if want_grp else None, conf.ctypes.data_as(dp) if want_conf else None))
+        out = {}
+        for k, v in (("b1", b1), ("grp", grp), ("conf", conf)):
+            if v is not None:
+                out[k] = v.reshape(lead, order="F")
+        return out
+
+    def b1_pool_dev(self, group_val, N: int, M: int, nslices: int, d_score: int, d_mask: int = 0, window=4, d_b1: int = 0, d_grp: int = 0, d_conf: int = 0):
+        """qmri_b1_pool_dev: device pointers (group_val stays a host array), asynchronous on the engine's stream."""
+        gv = np.ascontiguousarray(group_val, dtype=np.float64).ravel()
+        self._check(self.L.qmri_b1_pool_dev(self.h, gv.size, gv.ctypes.data_as(C.POINTER(C.c_double)), int(N), int(M), int(nslices), C.c_void_p(d_score or None),
+                                            C.c_void_p(d_mask or None), b1_window(window), C.c_void_p(d_b1 or None), C.c_void_p(d_grp or None),
+                                            C.c_void_p(d_conf or None)))
+
+    def estimate_b1(self, X, mask=None, window=4):
+        """qmri_b1_estimate: X [N, M, s] or [N, M, nslices, s] complex -> dict(b1, grp, conf in the image's shape, info = dict(n_estimated,
+        n_unmatched, mean_conf)): group_scores then b1_pool with the dictionary's own groups, bit for bit, a run of slices at a time."""
+        from ._lib import B1estInfo, B1estParams
+        self._group_count()
+        h = b1_window(window)
+        X = np.asarray(X, dtype=np.complex128)
+        s = self.dict_shape[1]
+        if X.ndim not in (3, 4) or X.shape[-1] != s:
+            raise ValueError("X must be [N, M, s] or [N, M, nslices, s] with the dictionary's channel count")
+        lead = X.shape[:-1]
+        if min(lead) < 1:
+            raise ValueError("X must have at least one pixel")
+        N, M, nsl = lead[0], lead[1], (lead[2] if len(lead) == 3 else 1)
+        n = N * M * nsl
+        mb = None
+        if mask is not None:
+            m = np.asarray(mask)
+            if m.shape != lead:
+                raise ValueError(f"mask must have the image's shape {lead}, not {m.shape}")
+            mb = np.ascontiguousarray((m != 0).ravel(order="F").astype(np.uint8))
+        xb = np.ascontiguousarray(X.reshape((n, s), order="F").ravel(order="F"))
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        b1, grp, conf = np.empty(n, np.float64), np.empty(n, np.int32), np.empty(n, np.float64)
+        p, info = B1estParams(h), B1estInfo()
+        self._check(self.L.qmri_b1_estimate(self.h, _vp(xb), N, M, nsl, _vp(mb) if mb is not None else None, C.byref(p), b1.ctypes.data_as(dp),
+                                            grp.ctypes.data_as(ip), conf.ctypes.data_as(dp), C.byref(info)))
+        return {"b1": b1.reshape(lead, order="F"), "grp": grp.reshape(lead, order="F"), "conf": conf.reshape(lead, order="F"),
+                "info": {"n_estimated": int(info.n_estimated), "n_unmatched": int(info.n_unmatched), "mean_conf": float(info.mean_conf)}}
+
+    def estimate_b1_dev(self, d_X: int, N: int, M: int, nslices: int, d_mask: int = 0, window=4, d_b1: int = 0, d_grp: int = 0, d_conf: int = 0):
+        """qmri_b1_estimate_dev: device pointers, asynchronous on the engine's stream."""
+        from ._lib import B1estParams
+        p = B1estParams(b1_window(window))
+        self._check(self.L.qmri_b1_estimate_dev(self.h, C.c_void_p(d_X), int(N), int(M), int(nslices), C.c_void_p(d_mask or None), C.byref(p),
+                                                C.c_void_p(d_b1 or None), C.c_void_p(d_grp or None), C.c_void_p(d_conf or None), None))
 
     def compress_dictionary(self, F, s=None, energy=None, s_max=16, tol=0.0, maxit=0):
         """A simulated dictionary compressed to its SVD subspace on the device (extension, no reference counterpart; include/qmri.h

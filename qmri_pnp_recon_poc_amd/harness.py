@@ -28,7 +28,7 @@ from __future__ import annotations
 
 import numpy as np
 
-__all__ = ["load_mat", "load_dictionary", "compress_dictionary", "simulate_dictionary", "load_tsmi", "crop_tsmi", "load_qmaps", "getmask_fromPD", "awgn_measured",
+__all__ = ["load_mat", "load_dictionary", "compress_dictionary", "simulate_dictionary", "estimate_b1", "load_tsmi", "crop_tsmi", "load_qmaps", "getmask_fromPD", "awgn_measured",
            "psnr", "ssim", "metrics", "recon_tsmis", "synthesize_tsmis", "training_volume", "save_training_pickle"]
 
 CROP = slice(3, 227)          # MATLAB (4:227): 230 -> 224                                       main_recon_tsmis_FFT.m:189,212
@@ -310,6 +310,27 @@ def unmix_tsmi(dictionary, X, components, mode="real", device=0):
             "unmix_flags": out["flags"]}
 
 
+def estimate_b1(dictionary, X, mask=None, window=4, device=0):
+    """The B1 map of a TSMI X [N, M, s] (or [N, M, nslices, s]) estimated from the fingerprints themselves: per pixel the b1
+    group of the dictionary (simulate_dictionary(..., b1_grid=...)) whose best atoms explain the most energy over the (2 window + 1)^2 window;
+    T1, T2 and PD stay free per pixel.  mask: non-zero = foreground.  Returns dict(b1 (NaN = no estimate: what recon_tsmis(b1_map=...) treats as
+    background), grp (1-based, 0 none), conf, info)."""
+    from .engine import b1_window
+    if dictionary.get("group_ptr") is None or dictionary.get("group_val") is None:
+        raise ValueError("estimate_b1 needs a dictionary with group_ptr and group_val (simulate_dictionary(..., b1_grid=...))")
+    b1_window(window)
+    X = np.asarray(X)
+    if X.ndim not in (3, 4):
+        raise ValueError("X must be [N, M, s] or [N, M, nslices, s]")
+    if mask is not None and np.asarray(mask).shape != X.shape[:-1]:
+        raise ValueError(f"mask must have the image's shape {X.shape[:-1]}")
+    from . import reference_api as R
+    eng = R._engine(device)
+    eng.set_dictionary(dictionary["D"], dictionary["normD"], dictionary["lut"])
+    eng.set_dictionary_groups(dictionary["group_ptr"], dictionary["group_val"])
+    return eng.estimate_b1(X, mask=mask, window=window)
+
+
 # ------------------------------------------------------------------------------------------------------------
 # the script's main flow
 # ------------------------------------------------------------------------------------------------------------
@@ -318,7 +339,7 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
                 denoiser_type="single_level", noise_map_std=0.01, residual_noise=False, iters=100, seed=0, Y=None, device=0,
                 net_arch=None, lrtv_iters=None, tsmi_domain="real", solver="lsqr", b1_map=None, density_compensation=False,
                 field_map=None, readout_s=None, field_normal=None, field_echoes=None, field_echo_times=None,
-                regulariser="net", llr_tau=None, llr_tau_rel=0.02, llr_block=8, components=None, unmix_mode="real"):
+                regulariser="net", llr_tau=None, llr_tau_rel=0.02, llr_block=8, components=None, unmix_mode="real", b1_window=4):
     """main_recon_tsmis_FFT.m:216-374 on already loaded (and cropped) arrays.
 
     dictionary  dict(V, D, normD, lut) (load_dictionary);  X0  N x M x s ground-truth TSMI;  qmap0  N x M x 3
@@ -329,7 +350,10 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
                 2s channels, cat(3, real, imag); "real" is the reference's loop
     solver      x-update of PnP_ADMM: "lsqr" (the reference's), "direct", or with SpiralExact "toeplitz" 
     b1_map      N x M measured transmit field for a dictionary that carries group_ptr / group_val (simulate_dictionary(..., b1_grid=...)): every
-                pixel is matched against the atoms of the b1 nearest its value, NaN = background, all outputs zero
+                pixel is matched against the atoms of the b1 nearest its value, NaN = background, all outputs zero.
+                b1_map="estimate": the map is estimated from the reconstructed TSMI itself inside the foreground mask, over windows of
+                (2 b1_window + 1)^2 pixels (estimate_b1), and then takes the b1_map route unchanged; the result gains
+                b1_est and b1_conf
     density_compensation  with SpiralExact: SVD_MRF is the density-compensated adjoint A^H (w .* y) and PnP_ADMM starts from it (Pipe-Menon
                 weights); False (default) is the bare adjoint
     field_map, readout_s  with SpiralExact, PnP_ADMM or SVD_MRF: an N x M field map in Hz and the length of one spiral readout in seconds (sample j of a
@@ -363,9 +387,15 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
     if b1_map is not None:                                                           # (refused before anything is reconstructed)
         if dictionary.get("group_ptr") is None or dictionary.get("group_val") is None:
             raise ValueError("b1_map needs a dictionary with group_ptr and group_val (simulate_dictionary(..., b1_grid=...))")
-        b1_map = np.asarray(b1_map, dtype=np.float64)
-        if b1_map.shape != (N, M):
-            raise ValueError(f"b1_map must be {N} x {M}")
+        if isinstance(b1_map, str):
+            if b1_map != "estimate":
+                raise ValueError(f'b1_map must be an {N} x {M} map or "estimate", not {b1_map!r}')
+            from .engine import b1_window as _b1w
+            _b1w(b1_window)
+        else:
+            b1_map = np.asarray(b1_map, dtype=np.float64)
+            if b1_map.shape != (N, M):
+                raise ValueError(f"b1_map must be {N} x {M}")
     if components is not None:                                                       # (refused before anything is reconstructed)
         component_atoms = resolve_components(dictionary, components)
         from .engine import unmix_mode as _umode
@@ -458,6 +488,10 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
         raise ValueError(f"unknown reconstruction method {recon_method}")
     par = {"f": {"qout": 1, "pdout": 1, "mtout": 0, "Xout": 0, "dmout": 0, "Yout": 0, "verbose": 0}, "fp": {"blockSize": 1e9}}   # :302-309
     extra = {**extra_fn, **extra_fm}
+    if isinstance(b1_map, str):                                                      # "estimate": from X, inside the foreground mask
+        est = estimate_b1(dictionary, X, mask=getmask_fromPD(np.asarray(qmap0)[:, :, 2], 0.15), window=b1_window, device=device)
+        b1_map = est["b1"]
+        extra["b1_est"], extra["b1_conf"] = est["b1"], est["conf"]
     if b1_map is not None:
         eng = R._engine(device)
         eng.set_dictionary(dictionary["D"], dictionary["normD"], dictionary["lut"])

@@ -61,6 +61,7 @@ static OperatorSpec g_op;
 static DenoiserSpec g_net;
 static DictSpec g_dict;
 static std::vector<int32_t> g_comp;                    // 'set_components' in force (1-based atoms); 'set_dictionary' drops them
+static int g_ngroups = 0;                              // 'set_dictionary_groups' in force (G); 'set_dictionary' and a device switch drop them
 static bool g_llr = false;                             // 'set_llr' is in force: 'pnp_admm' needs no denoiser
 static const int DEFAULT_SLICES_PER_LAUNCH = 15;       // what a measurement matrix grows the plans to (the batched kernels' design point)
 
@@ -73,6 +74,7 @@ static void cleanup() {
     drop(g_net.w); g_net = DenoiserSpec();
     drop(g_dict.D); drop(g_dict.normD); drop(g_dict.lut);
     g_comp.clear();
+    g_ngroups = 0;
     g_llr = false;
 }
 
@@ -237,6 +239,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
             if (qmri_create(d, &fresh) != QMRI_OK) mexErrMsgIdAndTxt("qmri:create", "%s", qmri_last_error(nullptr));
             if (g_ctx) qmri_destroy(g_ctx);
             g_ctx = fresh; g_device = d;
+            g_ngroups = 0;                                          // (the groups lived in the old context)
             (void)ctx();                                            // (registers the exit hook and the lock on first use)
             if (g_op.V) plan_operator(std::max(1, g_op.max_batch));
             if (g_net.w) plan_denoiser(std::max(1, g_net.max_batch));
@@ -942,6 +945,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         drop(g_dict.D); drop(g_dict.normD); drop(g_dict.lut);
         g_dict.D = keep(prhs[1]); g_dict.normD = keep(prhs[2]); g_dict.lut = keep(prhs[3]);
         g_comp.clear();
+        g_ngroups = 0;
         plan_dictionary();
     } else if (c == "dict_match") {                  // [qmap, pd, mt, dm, xfit] = qmri_mex('dict_match', X(Npix x s complex double), Q)
         need(nrhs, 3, "[qmap, pd, mt, dm, xfit] = qmri_mex('dict_match', X, Q)");
@@ -970,7 +974,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         want(clear || (G >= 1 && G <= 256 && mxGetNumberOfElements(prhs[1]) == G + 1), "qmri:set_dictionary_groups:size",
              "group_val must have 1 <= G <= 256 elements and group_ptr G + 1");
         want(g_dict.D != nullptr, "qmri:state", "no dictionary: call qmri_mex('set_dictionary', ...) first");
-        if (clear) { check(qmri_set_dictionary_groups(ctx(), 0, nullptr, nullptr)); return; }
+        if (clear) { check(qmri_set_dictionary_groups(ctx(), 0, nullptr, nullptr)); g_ngroups = 0; return; }
         std::vector<int32_t> gp(G + 1);
         const double* v = mxGetDoubles(prhs[1]);
         for (size_t g = 0; g <= G; ++g) {
@@ -978,6 +982,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
             gp[g] = (int32_t)v[g];
         }
         check(qmri_set_dictionary_groups(ctx(), (int)G, gp.data(), mxGetDoubles(prhs[2])));
+        g_ngroups = (int)G;
     } else if (c == "dict_match_grouped") {          // [qmap, pd, mt, dm, grp, xfit] = qmri_mex('dict_match_grouped', X(Npix x s complex double), Q, sel(Npix double))
         need(nrhs, 4, "[qmap, pd, mt, dm, grp, xfit] = qmri_mex('dict_match_grouped', X, Q, sel)");
         want(is_cdouble(prhs[1]) && mxGetM(prhs[1]) >= 1 && mxGetM(prhs[1]) <= 2147483647u, "qmri:dict_match_grouped:type", "X must be complex double, Npix x s");
@@ -1001,6 +1006,57 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         if (nlhs > 3) plhs[3] = dm; else mxDestroyArray(dm);
         if (nlhs > 4) plhs[4] = grp; else mxDestroyArray(grp);
         if (nlhs > 5) plhs[5] = xfit;
+    } else if (c == "group_scores") {                // score(Npix x G single) = qmri_mex('group_scores', X(Npix x s complex double))
+        // per group the mt of 'dict_match_grouped' with a constant selector (extension; qmri.h qmri_dict_group_scores)
+        const char* usage = "score = qmri_mex('group_scores', X)";
+        need(nrhs, 2, usage);
+        want(nlhs <= 1, "qmri:usage", usage);
+        want(is_cdouble(prhs[1]) && mxGetM(prhs[1]) >= 1 && mxGetM(prhs[1]) <= 2147483647u, "qmri:group_scores:type", "X must be complex double, Npix x s");
+        want(g_dict.D != nullptr, "qmri:state", "no dictionary: call qmri_mex('set_dictionary', ...) first");
+        want(mxGetN(prhs[1]) == mxGetN(g_dict.D), "qmri:group_scores:size", "X must have s columns (s = columns of dict.D)");
+        want(g_ngroups > 0, "qmri:state", "no groups: call qmri_mex('set_dictionary_groups', group_ptr, group_val) first");
+        const size_t npix = mxGetM(prhs[1]);
+        plhs[0] = mxCreateNumericMatrix(npix, (size_t)g_ngroups, mxSINGLE_CLASS, mxREAL);
+        check(qmri_dict_group_scores(ctx(), mxGetComplexDoubles(prhs[1]), (int)npix, (float*)mxGetData(plhs[0])));
+    } else if (c == "b1_estimate") {                 // [b1, grp, conf, info] = qmri_mex('b1_estimate', X(Npix x s complex double), [N M nslices], mask(Npix double | []), half_window)
+        // the B1 map from the fingerprints: group scores, then the pooled argmax over (2h+1)^2 windows (extension; qmri.h qmri_b1_estimate)
+        const char* usage = "[b1, grp, conf, info] = qmri_mex('b1_estimate', X, [N M nslices], mask, half_window)";
+        need(nrhs, 5, usage);
+        want(nlhs <= 4, "qmri:usage", usage);
+        want(is_cdouble(prhs[1]) && mxGetM(prhs[1]) >= 1 && mxGetM(prhs[1]) <= 2147483647u, "qmri:b1_estimate:type", "X must be complex double, Npix x s");
+        want(mxIsDouble(prhs[2]) && !mxIsComplex(prhs[2]) && mxGetNumberOfElements(prhs[2]) == 3, "qmri:b1_estimate:size", "the size argument must be [N M nslices]");
+        const double* dv = mxGetDoubles(prhs[2]);
+        for (int k = 0; k < 3; ++k)
+            want(std::isfinite(dv[k]) && dv[k] == std::floor(dv[k]) && dv[k] >= 1 && dv[k] <= 2147483647.0, "qmri:b1_estimate:size", "[N M nslices] must hold positive integers");
+        const size_t npix = mxGetM(prhs[1]);
+        want(dv[0] * dv[1] * dv[2] == (double)npix, "qmri:b1_estimate:size", "X must have N * M * nslices rows");
+        want(mxIsDouble(prhs[3]) && !mxIsComplex(prhs[3]) && (mxGetNumberOfElements(prhs[3]) == 0 || mxGetNumberOfElements(prhs[3]) == npix),
+             "qmri:b1_estimate:type", "mask must be a real double array with one value per row of X, or []");
+        qmri_b1est_params prm{};
+        prm.half_window = int_arg(prhs[4], 0, 32, "qmri:b1_estimate:window", "half_window must be an integer in 0 .. 32");
+        want(g_dict.D != nullptr, "qmri:state", "no dictionary: call qmri_mex('set_dictionary', ...) first");
+        want(mxGetN(prhs[1]) == mxGetN(g_dict.D), "qmri:b1_estimate:size", "X must have s columns (s = columns of dict.D)");
+        want(g_ngroups > 0, "qmri:state", "no groups: call qmri_mex('set_dictionary_groups', group_ptr, group_val) first");
+        std::vector<uint8_t> mask;
+        if (mxGetNumberOfElements(prhs[3])) {
+            mask.resize(npix);
+            const double* mv = mxGetDoubles(prhs[3]);
+            for (size_t k = 0; k < npix; ++k) mask[k] = mv[k] != 0.0;
+        }
+        plhs[0] = mxCreateDoubleMatrix(npix, 1, mxREAL);
+        mxArray* grp = mxCreateNumericMatrix(npix, 1, mxINT32_CLASS, mxREAL);
+        mxArray* conf = mxCreateDoubleMatrix(npix, 1, mxREAL);
+        qmri_b1est_info info{};
+        check(qmri_b1_estimate(ctx(), mxGetComplexDoubles(prhs[1]), (int)dv[0], (int)dv[1], (int)dv[2], mask.empty() ? nullptr : mask.data(), &prm,
+                               mxGetDoubles(plhs[0]), (int32_t*)mxGetData(grp), mxGetDoubles(conf), &info));
+        if (nlhs > 1) plhs[1] = grp; else mxDestroyArray(grp);
+        if (nlhs > 2) plhs[2] = conf; else mxDestroyArray(conf);
+        if (nlhs > 3) {
+            const char* names[] = {"n_estimated", "n_unmatched", "mean_conf"};
+            plhs[3] = mxCreateStructMatrix(1, 1, 3, names);
+            const double f[3] = {(double)info.n_estimated, (double)info.n_unmatched, info.mean_conf};
+            for (int k = 0; k < 3; ++k) mxSetFieldByNumber(plhs[3], 0, k, mxCreateDoubleScalar(f[k]));
+        }
     } else if (c == "set_components") {              // info = qmri_mex('set_components', atoms(1..8 doubles, 1-based)); [] clears
         // the components of 'dict_unmix' (extension; qmri.h qmri_set_components).  'set_dictionary' drops them.
         need(nrhs, 2, "info = qmri_mex('set_components', atoms)");
