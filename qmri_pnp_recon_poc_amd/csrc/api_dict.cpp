@@ -113,30 +113,42 @@ extern "C" int qmri_dict_match_dev(qmri_ctx* ctx, const void* d_X, int Npix, flo
     return qmri_dict_match_xfit_dev(ctx, d_X, Npix, d_qmap, d_pd, d_mt, d_dm, nullptr);
 }
 
+// The host-array form of a match (`who` for its messages): X, and the selector of a grouped match (sel, else NULL), go to the device, the match
+// runs there, and the outputs the caller asked for come back.  grp is a grouped match's.
+static int dict_match_staged(qmri_ctx* ctx, const char* who, const void* X, int Npix, const double* sel, float* qmap, float* pd, float* mt, int32_t* dm,
+                             int32_t* grp, float* xfit) {
+    const DictHost& d = ctx->dict;
+    const size_t nx = (size_t)Npix * d.s;
+    DevBuf<double2> dX; DevBuf<double> dsel; DevBuf<float> dq, dp, dmt; DevBuf<int32_t> ddm, dgrp; DevBuf<float2> dxf;
+    auto fail = [&](const char* what) { qmri_set_error(ctx, "%s failed in %s", what, who); return QMRI_ERR_HIP; };
+    QMRI_TRY(dX.ensure(ctx, nx));
+    if (sel) QMRI_TRY(dsel.ensure(ctx, (size_t)Npix));
+    if (qmap) QMRI_TRY(dq.ensure(ctx, (size_t)Npix * d.Q));
+    if (pd) QMRI_TRY(dp.ensure(ctx, (size_t)Npix * 2));
+    if (mt) QMRI_TRY(dmt.ensure(ctx, (size_t)Npix));
+    if (dm) QMRI_TRY(ddm.ensure(ctx, (size_t)Npix));
+    if (grp) QMRI_TRY(dgrp.ensure(ctx, (size_t)Npix));
+    if (xfit) QMRI_TRY(dxf.ensure(ctx, nx));
+    if (hipMemcpyAsync(dX, X, nx * sizeof(double2), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return fail("H2D copy");
+    if (sel && hipMemcpyAsync(dsel, sel, (size_t)Npix * sizeof(double), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return fail("H2D copy");
+    if (sel) QMRI_TRY(dictg_launch(ctx, dX, Npix, dsel, dq, dp, dmt, ddm, dgrp, dxf));
+    else QMRI_TRY(dict_launch(ctx, dX, Npix, dq, dp, dmt, ddm, dxf));
+    if (qmap && hipMemcpyAsync(qmap, dq, (size_t)Npix * d.Q * sizeof(float), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return fail("D2H copy");
+    if (pd && hipMemcpyAsync(pd, dp, (size_t)Npix * 2 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return fail("D2H copy");
+    if (mt && hipMemcpyAsync(mt, dmt, (size_t)Npix * sizeof(float), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return fail("D2H copy");
+    if (dm && hipMemcpyAsync(dm, ddm, (size_t)Npix * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return fail("D2H copy");
+    if (grp && hipMemcpyAsync(grp, dgrp, (size_t)Npix * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return fail("D2H copy");
+    if (xfit && hipMemcpyAsync(xfit, dxf, nx * sizeof(float2), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return fail("D2H copy");
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return fail("synchronize");
+    return QMRI_OK;
+}
+
 extern "C" int qmri_dict_match_xfit(qmri_ctx* ctx, const void* X, int Npix, float* qmap, float* pd, float* mt, int32_t* dm, float* xfit) {
     if (!ctx) return QMRI_ERR_INVALID_ARG;
     QMRI_HIP(ctx, hipSetDevice(ctx->device));
     if (!ctx->dict.ready) { qmri_set_error(ctx, "dictionary not set: call qmri_set_dictionary first"); return QMRI_ERR_STATE; }
     QMRI_CHECK_ARG(ctx, X && Npix > 0, "X must not be NULL and Npix > 0");
-    const DictHost& d = ctx->dict;
-    const size_t nx = (size_t)Npix * d.s;
-    DevBuf<double2> dX; DevBuf<float> dq, dp, dmt; DevBuf<int32_t> ddm; DevBuf<float2> dxf;
-    auto fail = [&](const char* what) { qmri_set_error(ctx, "%s failed in qmri_dict_match", what); return QMRI_ERR_HIP; };
-    QMRI_TRY(dX.ensure(ctx, nx));
-    if (qmap) QMRI_TRY(dq.ensure(ctx, (size_t)Npix * d.Q));
-    if (pd) QMRI_TRY(dp.ensure(ctx, (size_t)Npix * 2));
-    if (mt) QMRI_TRY(dmt.ensure(ctx, (size_t)Npix));
-    if (dm) QMRI_TRY(ddm.ensure(ctx, (size_t)Npix));
-    if (xfit) QMRI_TRY(dxf.ensure(ctx, nx));
-    if (hipMemcpyAsync(dX, X, nx * sizeof(double2), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return fail("H2D copy");
-    QMRI_TRY(dict_launch(ctx, dX, Npix, dq, dp, dmt, ddm, dxf));
-    if (qmap && hipMemcpyAsync(qmap, dq, (size_t)Npix * d.Q * sizeof(float), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return fail("D2H copy");
-    if (pd && hipMemcpyAsync(pd, dp, (size_t)Npix * 2 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return fail("D2H copy");
-    if (mt && hipMemcpyAsync(mt, dmt, (size_t)Npix * sizeof(float), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return fail("D2H copy");
-    if (dm && hipMemcpyAsync(dm, ddm, (size_t)Npix * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return fail("D2H copy");
-    if (xfit && hipMemcpyAsync(xfit, dxf, nx * sizeof(float2), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return fail("D2H copy");
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return fail("synchronize");
-    return QMRI_OK;
+    return dict_match_staged(ctx, "qmri_dict_match", X, Npix, nullptr, qmap, pd, mt, dm, nullptr, xfit);
 }
 
 extern "C" int qmri_dict_match(qmri_ctx* ctx, const void* X, int Npix, float* qmap, float* pd, float* mt, int32_t* dm) {
@@ -186,27 +198,5 @@ extern "C" int qmri_dict_match_grouped(qmri_ctx* ctx, const void* X, int Npix, c
     if (!ctx) return QMRI_ERR_INVALID_ARG;
     QMRI_HIP(ctx, hipSetDevice(ctx->device));
     QMRI_TRY(grouped_ready(ctx, X, Npix, sel));
-    const DictHost& d = ctx->dict;
-    const size_t nx = (size_t)Npix * d.s;
-    DevBuf<double2> dX; DevBuf<double> dsel; DevBuf<float> dq, dp, dmt; DevBuf<int32_t> ddm, dgrp; DevBuf<float2> dxf;
-    auto fail = [&](const char* what) { qmri_set_error(ctx, "%s failed in qmri_dict_match_grouped", what); return QMRI_ERR_HIP; };
-    QMRI_TRY(dX.ensure(ctx, nx));
-    QMRI_TRY(dsel.ensure(ctx, (size_t)Npix));
-    if (qmap) QMRI_TRY(dq.ensure(ctx, (size_t)Npix * d.Q));
-    if (pd) QMRI_TRY(dp.ensure(ctx, (size_t)Npix * 2));
-    if (mt) QMRI_TRY(dmt.ensure(ctx, (size_t)Npix));
-    if (dm) QMRI_TRY(ddm.ensure(ctx, (size_t)Npix));
-    if (grp) QMRI_TRY(dgrp.ensure(ctx, (size_t)Npix));
-    if (xfit) QMRI_TRY(dxf.ensure(ctx, nx));
-    if (hipMemcpyAsync(dX, X, nx * sizeof(double2), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return fail("H2D copy");
-    if (hipMemcpyAsync(dsel, sel, (size_t)Npix * sizeof(double), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return fail("H2D copy");
-    QMRI_TRY(dictg_launch(ctx, dX, Npix, dsel, dq, dp, dmt, ddm, dgrp, dxf));
-    if (qmap && hipMemcpyAsync(qmap, dq, (size_t)Npix * d.Q * sizeof(float), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return fail("D2H copy");
-    if (pd && hipMemcpyAsync(pd, dp, (size_t)Npix * 2 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return fail("D2H copy");
-    if (mt && hipMemcpyAsync(mt, dmt, (size_t)Npix * sizeof(float), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return fail("D2H copy");
-    if (dm && hipMemcpyAsync(dm, ddm, (size_t)Npix * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return fail("D2H copy");
-    if (grp && hipMemcpyAsync(grp, dgrp, (size_t)Npix * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return fail("D2H copy");
-    if (xfit && hipMemcpyAsync(xfit, dxf, nx * sizeof(float2), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return fail("D2H copy");
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return fail("synchronize");
-    return QMRI_OK;
+    return dict_match_staged(ctx, "qmri_dict_match_grouped", X, Npix, sel, qmap, pd, mt, dm, grp, xfit);
 }

@@ -1,5 +1,6 @@
 // dict_device.h -- device pieces shared by the dictionary-match kernels (dict_kernels.hip: s <= 16 channels, atoms against register-resident pixels;
-// dictw_kernels.hip: s <= 1024 channels, a channel-blocked GEMM), the Xfit kernel and the TSMI synthesis (synth_kernels.hip).
+// dictw_kernels.hip: s <= 1024 channels, a channel-blocked GEMM; dictb_kernels.hip: the group scores), the Xfit kernel and the TSMI synthesis
+// (synth_kernels.hip).  The work split of those kernels -- plain integers, shared with the host -- is dict_plan.h.
 //
 // Reference semantics: main_files/dictionary_matching/mrf_dtm_cpu.m
 //   :92      [mt,dm] = max(abs(ip),[],1)               single-precision MAGNITUDES compared, first index wins ties
@@ -78,6 +79,57 @@ __device__ __forceinline__ void inc_update(int t, int h, const f32x16& are, cons
 // A candidate o against the incumbent b, both (|ip|, atom index bits, re, im): larger magnitude, then lower index -- max(abs(ip)) with the
 // first index winning ties, whatever the split of the atoms over lanes, waves, workgroups (mrf_dtm_cpu.m:92)
 __device__ __forceinline__ bool cand_better(float ob, int oi, float best, int bidx) { return ob > best || (ob == best && oi < bidx); }
+
+// merge the two lane halves (same pixel, interleaved atom rows): larger value, then lower index
+__device__ __forceinline__ void merge_lane_halves(Inc& I, int lane) {
+    const float ob = __shfl(I.best, lane ^ 32, 64), ore = __shfl(I.cre, lane ^ 32, 64), oim = __shfl(I.cim, lane ^ 32, 64);
+    const int oi = __shfl(I.bidx, lane ^ 32, 64);
+    if (cand_better(ob, oi, I.best, I.bidx)) { I.best = ob; I.bidx = oi; I.cre = ore; I.cim = oim; }
+}
+
+// ---- the narrow kernels' exact products (dict_kernels.hip, dictb_kernels.hip): s <= 16 channels as NPAIR <= 8 channel pairs --------------------
+// B fragments of pixel i of X (column-major, `stride` pixels per channel, an int or a size_t; zeros when !valid):
+// B[k = 2q + h][j] = x(p, c = 2q + h)  (real chain) and -imag (conjugate) for the imaginary chain
+template <int NPAIR, class Stride>
+__device__ __forceinline__ void load_b_frags(const double2* __restrict__ X, int i, Stride stride, int s, bool valid, int h, float (&bre)[NPAIR], float (&bim)[NPAIR]) {
+#pragma unroll
+    for (int q = 0; q < NPAIR; ++q) {
+        const int c = 2 * q + h;
+        double2 v = make_double2(0.0, 0.0);
+        if (valid && c < s) v = X[(size_t)i + (size_t)stride * c];
+        bre[q] = (float)v.x;                   // single(x)  mrf_dtm_cpu.m:54
+        bim[q] = -(float)v.y;                  // conj
+    }
+}
+
+// A lane's A fragments of 32-atom tile t of a pack [tile][lane][NPL = 4 NV floats]: one or two 16-byte requests
+template <int NV>
+__device__ __forceinline__ void request_tile(const float* __restrict__ pack, int t, int lane, f32x4 (&dst)[NV]) {
+    const f32x4* ap = (const f32x4*)(pack + ((size_t)t * 64 + lane) * (4 * NV));
+#pragma unroll
+    for (int v = 0; v < NV; ++v) dst[v] = ap[v];
+}
+
+// ip of one 32-atom x 32-pixel tile: the real and the imaginary chain over the channel pairs in ascending order
+template <int NPAIR, int NV>
+__device__ __forceinline__ void exact_products(const f32x4 (&av)[NV], const float (&bre)[NPAIR], const float (&bim)[NPAIR], f32x16& are, f32x16& aim) {
+    are = f32x16{0}; aim = f32x16{0};
+#pragma unroll
+    for (int q = 0; q < NPAIR; ++q) {
+        are = __builtin_amdgcn_mfma_f32_32x32x2f32(av[q >> 2][q & 3], bre[q], are, 0, 0, 0);
+        aim = __builtin_amdgcn_mfma_f32_32x32x2f32(av[q >> 2][q & 3], bim[q], aim, 0, 0, 0);
+    }
+}
+
+// the largest of a lane's sixteen |ip|^2 = fma(im, im, re * re) of a tile  (v_max3_f32: 8 instead of 10 instructions)
+__device__ __forceinline__ float tile_max2(const f32x16& re, const f32x16& im) {
+    float m2[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) m2[r] = __builtin_fmaf(im[r], im[r], re[r] * re[r]);
+    auto max3 = [](float a, float b, float c) __attribute__((always_inline)) { return fmaxf(fmaxf(a, b), c); };
+    return fmaxf(max3(max3(m2[0], m2[1], m2[2]), max3(m2[3], m2[4], m2[5]), m2[15]),
+                 max3(max3(m2[6], m2[7], m2[8]), max3(m2[9], m2[10], m2[11]), max3(m2[12], m2[13], m2[14])));
+}
 
 // The outputs of one pixel from its winner (mrf_dtm_cpu.m:94-96,136-160).  win (nullable): (re ip, im ip, atom index bits, |ip|) kept for k_dict_xfit.
 __device__ __forceinline__ void finish_pixel(int p, int Npix, int K, float best, int bidx, float cre, float cim, const float* __restrict__ normD,

@@ -27,10 +27,14 @@
 // when the pixel tiles alone do not fill the device evenly: a workgroup walks ALL its atoms (1.1 ms at K = 98 304), so 1568 pixel
 // tiles on 1280 resident workgroups took two rounds, the second at 22 % occupancy -- the matrix pipe idled 40 % of the launch.  The
 // parts' candidates go to a scratch array and k_dict_merge picks per pixel: larger magnitude, then lower index -- the same rule,
-// so max(abs(ip)) with the first index winning ties (mrf_dtm_cpu.m:92) whatever the split.
+// so max(abs(ip)) with the first index winning ties (mrf_dtm_cpu.m:92) whatever the split.  How many parts, which tiles a part and a wave
+// take and in which order: dict_plan.h, for the host and the kernels alike.
 #include <algorithm>
 #include "qmri_internal.h"
 #include "dict_device.h"
+#include "dict_plan.h"
+
+using namespace dplan;
 
 namespace {
 
@@ -43,12 +47,8 @@ constexpr int MAXPAIR = 8;      // s <= 16 here; more channels: dictw_kernels.hi
 // per tile were v_accvgpr_read, and the epilogue's issue slots, not the matrix pipe, set the pace (10 MFMAs per 32 x 32 outputs).
 template <int NPAIR, int NV>
 __device__ __forceinline__ void exact_tile(int t, int h, const f32x4 (&av)[NV], const float (&bre)[NPAIR], const float (&bim)[NPAIR], Inc& I) {
-    f32x16 are = {0}, aim = {0};
-#pragma unroll
-    for (int q = 0; q < NPAIR; ++q) {
-        are = __builtin_amdgcn_mfma_f32_32x32x2f32(av[q >> 2][q & 3], bre[q], are, 0, 0, 0);
-        aim = __builtin_amdgcn_mfma_f32_32x32x2f32(av[q >> 2][q & 3], bim[q], aim, 0, 0, 0);
-    }
+    f32x16 are, aim;
+    exact_products<NPAIR, NV>(av, bre, bim, are, aim);
     inc_update(t, h, are, aim, I);
 }
 
@@ -78,28 +78,16 @@ __global__ __launch_bounds__(NT) void k_dict_match(const double2* __restrict__ X
         grp = gv.tile_grp[blockIdx.x];
     }
     const bool valid = GRP ? p >= 0 : p < Npix;
-    // B fragments: B[k = 2q + h][j] = x(p, c = 2q + h)  (real chain) and -imag (conjugate) for the imaginary chain
     float bre[NPAIR], bim[NPAIR];
-#pragma unroll
-    for (int q = 0; q < NPAIR; ++q) {
-        const int c = 2 * q + h;
-        double2 v = make_double2(0.0, 0.0);
-        if (valid && c < s) v = X[(size_t)p + (size_t)Npix * c];
-        bre[q] = (float)v.x;                   // single(x)  mrf_dtm_cpu.m:54
-        bim[q] = -(float)v.y;                  // conj
-    }
+    load_b_frags<NPAIR>(X, p, Npix, s, valid, h, bre, bim);
     Inc I = {-1.0f, -1.0f, 0.f, 0.f, 0};
     float &best = I.best, &cre = I.cre, &cim = I.cim;
     int& bidx = I.bidx;
-    // this workgroup's part of the atom tiles: [tbeg, ntiles)
-    // (GRP: of the group's tiles [t0, tall), in as many parts as keep >= 64 tiles per wave; a part beyond them is empty and leaves best = -1)
-    int t0 = 0, tall = ntiles_all, nparts = (int)gridDim.y;
-    if constexpr (GRP) {
-        t0 = gv.gtile[grp]; tall = gv.gtile[grp + 1];
-        nparts = max(1, min(nparts, (tall - t0) / (4 * 64)));
-    }
-    const int tper = (tall - t0 + nparts - 1) / nparts;
-    const int tbeg = t0 + (int)blockIdx.y * tper, ntiles = min(tall, tbeg + tper);
+    // this workgroup's part of the atom tiles (dict_plan.h)
+    // (GRP: of the group's tiles; a part beyond the group's own is empty and leaves best = -1)
+    TileRange part_r;
+    if constexpr (GRP) part_r = dict_group_part(gv.gtile[grp], gv.gtile[grp + 1], (int)gridDim.y, (int)blockIdx.y, MIN_TILES_EXACT, 1);
+    else part_r = dict_part(0, ntiles_all, dict_tper(ntiles_all, (int)gridDim.y, 1), (int)blockIdx.y);
     // The atom fragments of tile t + 4 are requested before the products of tile t (register double buffer): the loop used to
     // request a tile's fragments and wait for them at once, one L2 latency per tile hidden only by occupancy.
     constexpr int NPL = (NPAIR <= 4) ? 4 : 8, NV = NPL / 4;
@@ -107,26 +95,13 @@ __global__ __launch_bounds__(NT) void k_dict_match(const double2* __restrict__ X
     auto tile_body = [&](int t, const f32x4 (&av)[NV]) __attribute__((always_inline)) { exact_tile<NPAIR, NV>(t, h, av, bre, bim, I); };
     // Visiting order.  Atoms lie on a (T1, T2) grid and neighbouring pixels have neighbouring matches: in ascending order the scan climbs
     // towards the match row by row and 28 % of the tiles brought a new incumbent for some lane of the wave (measured on the bench slice;
-    // the update path costs three times the plain tile).  A wave therefore walks its tiles i = 0 .. n-1 (tile tbeg + wave + 4 i) in
+    // the update path costs three times the plain tile).  A wave therefore walks its tiles i = 0 .. n-1 (dict_wave_tile) in
     // BIT-REVERSED order of i -- coarse to fine over its whole part: the incumbent is close to the final one after a few tiles and 4.5 %
     // of the tiles reach the update path.  The order is scalar arithmetic (s_brev_b32); the result does not depend on it (see above).
-    const int n = (ntiles - tbeg - wave + 3) / 4;                      // this wave's tiles (<= 0: none)
-    int nb = 0;
-    while ((1 << nb) < n) ++nb;
-    const unsigned kend = 1u << nb;
-    auto next_i = [&](unsigned& k) __attribute__((always_inline)) -> int {          // next valid i at or after counter k (n when exhausted); k moves past it
-        while (k < kend) {
-            const int i = nb ? (int)(__builtin_bitreverse32(k) >> (32 - nb)) : 0;
-            ++k;
-            if (i < n) return i;
-        }
-        return n;
-    };
-    auto request = [&](int i, f32x4 (&dst)[NV]) __attribute__((always_inline)) {
-        const f32x4* ap = (const f32x4*)(pack + ((size_t)(tbeg + wave + 4 * i) * 64 + lane) * NPL);
-#pragma unroll
-        for (int v = 0; v < NV; ++v) dst[v] = ap[v];
-    };
+    const int n = dict_wave_count(part_r, wave);                        // this wave's tiles (<= 0: none)
+    const BrevOrder order = brev_order(n);
+    auto next_i = [&](unsigned& k) __attribute__((always_inline)) -> int { return brev_next(order, k); };
+    auto request = [&](int i, f32x4 (&dst)[NV]) __attribute__((always_inline)) { request_tile<NV>(pack, dict_wave_tile(part_r, wave, i), lane, dst); };
     {
         unsigned k = 0;
         int i0 = (n > 0) ? next_i(k) : n;
@@ -134,19 +109,14 @@ __global__ __launch_bounds__(NT) void k_dict_match(const double2* __restrict__ X
         while (i0 < n) {
             const int i1 = next_i(k);
             if (i1 < n) request(i1, avn);
-            tile_body(tbeg + wave + 4 * i0, av);
+            tile_body(dict_wave_tile(part_r, wave, i0), av);
             if (i1 >= n) break;
             i0 = next_i(k);
             if (i0 < n) request(i0, av);
-            tile_body(tbeg + wave + 4 * i1, avn);
+            tile_body(dict_wave_tile(part_r, wave, i1), avn);
         }
     }
-    // merge the two lane halves (same pixel, interleaved atom rows): larger value, then lower index
-    {
-        const float ob = __shfl(best, lane ^ 32, 64), ore = __shfl(cre, lane ^ 32, 64), oim = __shfl(cim, lane ^ 32, 64);
-        const int oi = __shfl(bidx, lane ^ 32, 64);
-        if (ob > best || (ob == best && oi < bidx)) { best = ob; bidx = oi; cre = ore; cim = oim; }
-    }
+    merge_lane_halves(I, lane);
     if (h == 0) { s_best[wave][j] = best; s_idx[wave][j] = bidx; s_re[wave][j] = cre; s_im[wave][j] = cim; }
     __syncthreads();
     if (tid < 32 && valid) {
@@ -155,6 +125,8 @@ __global__ __launch_bounds__(NT) void k_dict_match(const double2* __restrict__ X
         for (int w = 1; w < 4; ++w) {
             const float ob = s_best[w][tid];
             const int oi = s_idx[w][tid];
+            // (cand_better's rule written out: with the call in its place hipcc read s_re / s_im of a candidate that wins a TIE by its lower index
+            //  from the incumbent's wave -- the right atom with another atom's ip)
             if (ob > best || (ob == best && oi < bidx)) { best = ob; bidx = oi; cre = s_re[w][tid]; cim = s_im[w][tid]; }
         }
         if constexpr (GRP) bidx = dict_group_atom(gv, grp, bidx);
@@ -183,8 +155,6 @@ __global__ __launch_bounds__(NT) void k_dict_match(const double2* __restrict__ X
 // the part.  The f16 fragments pass through LDS in steps of FSTEP tiles, loaded once per workgroup (each wave fetching its own copy, as
 // the exact kernel does, asked the L2 for 94 GB/s per CU at the matrix cores' pace -- more than a CU gets).  Steps are visited in
 // bit-reversed order (see k_dict_match).
-constexpr int LCAP = 128;       // tiles a wave collects for the exact products before it works them off
-constexpr int FSTEP = 8;        // tiles per LDS step: 16 KB of f16 pieces, [tile][hi | lo][lane] of 16 bytes
 // GRP: as in k_dict_match; gmax is indexed by slot, the seed samples the group's own tiles (skipped for a group of fewer than 48 steps)
 template <int NPAIR, bool SEED, bool GRP = false>
 __global__ __launch_bounds__(NT) void k_dict_match_f(const double2* __restrict__ X, int Npix, int s, const float* __restrict__ pack,
@@ -206,16 +176,8 @@ __global__ __launch_bounds__(NT) void k_dict_match_f(const double2* __restrict__
     }
     const bool valid = GRP ? p >= 0 : p < Npix;
     constexpr int NPL = (NPAIR <= 4) ? 4 : 8, NV = NPL / 4;
-    // exact products: B[k = 2q + h][j] = x(p, c = 2q + h) (real chain) and -imag (conjugate) for the imaginary chain
-    float bre[NPAIR], bim[NPAIR];
-#pragma unroll
-    for (int q = 0; q < NPAIR; ++q) {
-        const int c = 2 * q + h;
-        double2 v = make_double2(0.0, 0.0);
-        if (valid && c < s) v = X[(size_t)p + (size_t)Npix * c];
-        bre[q] = (float)v.x;                   // single(x)  mrf_dtm_cpu.m:54
-        bim[q] = -(float)v.y;                  // conj
-    }
+    float bre[NPAIR], bim[NPAIR];                                       // exact products
+    load_b_frags<NPAIR>(X, p, Npix, s, valid, h, bre, bim);
     // filter: B[k = 8 h + jj][j], pieces of the scaled pixel
     typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
     f16x8 brh, brl, bih, bil;
@@ -261,37 +223,23 @@ __global__ __launch_bounds__(NT) void k_dict_match_f(const double2* __restrict__
     Inc I = {-1.0f, -1.0f, 0.f, 0.f, 0};
     float runa = (!SEED && pub) ? __int_as_float(gmax[gi]) : -1.f, cut = runa - marg;
     int cnt = 0;                                                        // listed tiles (scalar)
-    // this workgroup's part of the atom tiles: [tbeg, tbeg + n), local index i
-    // (SEED: the whole dictionary, steps (blockIdx.y + gridDim.y k) seed_stride)
-    // (GRP: the group's tiles [t0, tall) in place of the dictionary's, in as many parts as keep >= 64 tiles each, whole LDS steps per part; a part
-    //  beyond them is empty, n = 0, and leaves best = -1)
+    // this workgroup's part of the atom tiles: [tbeg, tbeg + n), local index i (dict_plan.h)
+    // (SEED: the whole dictionary, sampled by dict_seed_step)
+    // (GRP: the group's tiles [t0, tall) in place of the dictionary's; a part beyond the group's own is empty, n = 0, and leaves best = -1)
     int t0 = 0, tall = ntiles_all;
-    if constexpr (GRP) {
-        t0 = gv.gtile[grp]; tall = gv.gtile[grp + 1];
-        const int nparts = max(1, min((int)gridDim.y, (tall - t0) / 64));
-        tper = ((tall - t0 + nparts - 1) / nparts + FSTEP - 1) / FSTEP * FSTEP;
-    }
-    const int tbeg = SEED ? t0 : t0 + (int)blockIdx.y * tper, n = SEED ? tall - t0 : GRP ? max(0, min(tall - tbeg, tper)) : min(tall - tbeg, tper);
+    if constexpr (GRP) { t0 = gv.gtile[grp]; tall = gv.gtile[grp + 1]; }
+    const TileRange part_r = SEED ? TileRange{t0, tall}
+                             : GRP ? dict_group_part(t0, tall, (int)gridDim.y, (int)blockIdx.y, MIN_TILES, FSTEP) : dict_part(t0, tall, tper, (int)blockIdx.y);
+    const int tbeg = part_r.tbeg, n = part_r.tend - tbeg;
     const int nsteps = (n + FSTEP - 1) / FSTEP;
     if constexpr (SEED && GRP) {
-        if (nsteps < 48) return;
-        seed_stride = max(1, nsteps / 12);
+        if (!dict_seed_on(nsteps)) return;
+        seed_stride = dict_seed_stride(nsteps);
     }
-    int nb = 0;
-    while ((1 << nb) < nsteps) ++nb;
-    const unsigned kend = 1u << nb;
+    const BrevOrder order = brev_order(nsteps);
     auto next_step = [&](unsigned& k) __attribute__((always_inline)) -> int {       // next valid step at or after counter k (nsteps when exhausted)
-        if constexpr (SEED) {
-            const long i = ((long)blockIdx.y + (long)gridDim.y * k) * seed_stride;
-            ++k;
-            return i < nsteps ? (int)i : nsteps;
-        }
-        while (k < kend) {
-            const int i = nb ? (int)(__builtin_bitreverse32(k) >> (32 - nb)) : 0;
-            ++k;
-            if (i < nsteps) return i;
-        }
-        return nsteps;
+        if constexpr (SEED) return dict_seed_step(blockIdx.y, gridDim.y, k++, seed_stride, nsteps);
+        return brev_next(order, k);
     };
     auto stage_load = [&](int st, uint4 (&r)[4]) __attribute__((always_inline)) {
         const int ts = tbeg + st * FSTEP;
@@ -314,12 +262,7 @@ __global__ __launch_bounds__(NT) void k_dict_match_f(const double2* __restrict__
         fi = __builtin_amdgcn_mfma_f32_32x32x16_f16(dh, bil, fi, 0, 0, 0);
         fr = __builtin_amdgcn_mfma_f32_32x32x16_f16(dh, brh, fr, 0, 0, 0);
         fi = __builtin_amdgcn_mfma_f32_32x32x16_f16(dh, bih, fi, 0, 0, 0);
-        float m2[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) m2[r] = __builtin_fmaf(fi[r], fi[r], fr[r] * fr[r]);
-        auto max3 = [](float a, float b, float c) __attribute__((always_inline)) { return fmaxf(fmaxf(a, b), c); };     // (v_max3_f32: 8 instead of 10 instructions)
-        const float tm = fmaxf(max3(max3(m2[0], m2[1], m2[2]), max3(m2[3], m2[4], m2[5]), m2[15]),
-                               max3(max3(m2[6], m2[7], m2[8]), max3(m2[9], m2[10], m2[11]), max3(m2[12], m2[13], m2[14])));
+        const float tm = tile_max2(fr, fi);
         const bool tr = !(tm <= cut);
         if constexpr (SEED) { runa = fmaxf(runa, tm); return; }
         if (__builtin_amdgcn_ballot_w64(tr)) {                          // (uniform)
@@ -329,11 +272,7 @@ __global__ __launch_bounds__(NT) void k_dict_match_f(const double2* __restrict__
         }
     };
     f32x4 av[NV], avn[NV];
-    auto request = [&](int i, f32x4 (&dst)[NV]) __attribute__((always_inline)) {
-        const f32x4* ap = (const f32x4*)(pack + ((size_t)(tbeg + i) * 64 + lane) * NPL);
-#pragma unroll
-        for (int v = 0; v < NV; ++v) dst[v] = ap[v];
-    };
+    auto request = [&](int i, f32x4 (&dst)[NV]) __attribute__((always_inline)) { request_tile<NV>(pack, tbeg + i, lane, dst); };
     auto exact_pass = [&]() __attribute__((always_inline)) {            // the listed tiles through the exact products
         if (cnt == 0) return;
         int i0 = __builtin_amdgcn_readfirstlane(s_list[wave][0]);
@@ -351,7 +290,7 @@ __global__ __launch_bounds__(NT) void k_dict_match_f(const double2* __restrict__
     {
         // Tile 0 of the dictionary is listed whatever the filter says: for a pixel whose products are all zero MATLAB's max keeps atom 1,
         // and exact_tile() gives that answer when the dictionary's first tile is the first one it sees (its note on magnitude 0).
-        if (!SEED && blockIdx.y == 0 && n > 0) { if (lane == 0) s_list[wave][0] = 0; cnt = 1; }
+        if (!SEED && dict_lists_first_tile(part_r, (int)blockIdx.y)) { if (lane == 0) s_list[wave][0] = 0; cnt = 1; }
         unsigned k = 0;
         uint4 r[4];
         int st = (nsteps > 0) ? next_step(k) : nsteps, cur = 0;
@@ -381,12 +320,7 @@ __global__ __launch_bounds__(NT) void k_dict_match_f(const double2* __restrict__
         if (pub && runa >= 0.f) (void)__hip_atomic_fetch_max(gmax + gi, __float_as_int(runa), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         return;
     }
-    // merge the two lane halves (same pixel, interleaved atom rows): larger value, then lower index
-    {
-        const float ob = __shfl(I.best, lane ^ 32, 64), ore = __shfl(I.cre, lane ^ 32, 64), oim = __shfl(I.cim, lane ^ 32, 64);
-        const int oi = __shfl(I.bidx, lane ^ 32, 64);
-        if (ob > I.best || (ob == I.best && oi < I.bidx)) { I.best = ob; I.bidx = oi; I.cre = ore; I.cim = oim; }
-    }
+    merge_lane_halves(I, lane);
     if (h == 0 && valid) {
         int bidx = I.bidx;
         if constexpr (GRP) bidx = dict_group_atom(gv, grp, bidx);
@@ -440,7 +374,60 @@ int dict_launch_merge(qmri_ctx* ctx, const float4* part, int P, int Npix, float*
     return QMRI_OK;
 }
 
-static int dict_launch_narrow(qmri_ctx* ctx, const double2* d_X, int Npix, float* d_qmap, float* d_pd, float* d_mt, int32_t* d_dm, float4* win);
+// The narrow match, and with GRP the grouped one (qmri_dict_match_grouped): the same kernels on slot tiles of one group each.
+// There gv comes from the bucketing launches of dictg_launch() (dictg_kernels.hip) with the pixel width dict_group_pixel_width() asks for; nslot_tiles is
+// the largest number of slot tiles the call can have (the kernels leave at once beyond the slots in use, which only the device knows).
+template <bool GRP>
+static int dict_launch_match(qmri_ctx* ctx, const double2* d_X, int Npix, const DictGroupView& gv, int nslot_tiles, float* d_qmap, float* d_pd, float* d_mt,
+                             int32_t* d_dm, float4* win) {
+    DictHost& D = ctx->dict;
+    const int npair = (D.s + 1) / 2;
+    if (npair < 1 || npair > MAXPAIR) {
+        qmri_set_error(ctx, "dictionary match supports s <= %d channels (got %d)", 2 * MAXPAIR, D.s);
+        return QMRI_ERR_UNSUPPORTED;
+    }
+    const float* pack = GRP ? D.d_gpack.p : D.d_pack;
+    const uint4* pack16 = GRP ? D.d_gpack16.p : D.d_pack16;
+    const int tall = GRP ? D.gtile_h.back() : D.ntiles;
+    const bool filt = pack16 && D.filter_on;
+    int& slots = filt ? (GRP ? D.slots_gf : D.slots_f) : (GRP ? D.slots_g : D.slots);
+    if (filt) QMRI_TRY(dict_resident_slots(ctx, k_dict_match_f<5, false, GRP>, NT, slots));
+    else QMRI_TRY(dict_resident_slots(ctx, k_dict_match<5, GRP>, NT, slots));
+    const MatchPlan pl = GRP ? dict_plan_grouped(Npix, nslot_tiles, gv.slot_cap, D.gtiles_max, filt, slots) : dict_plan_narrow(Npix, D.ntiles, filt, slots);
+    float4* part = nullptr;
+    if (pl.npart) {
+        QMRI_TRY(D.d_part.ensure(ctx, pl.npart));
+        part = D.d_part;
+    }
+    if (pl.ngmax) {
+        QMRI_TRY(D.d_gmax.ensure(ctx, pl.ngmax));
+        QMRI_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)D.d_gmax, (int)0xBF800000u /* -1.0f */, pl.ngmax, ctx->stream));
+    }
+    const dim3 grid(pl.gx, pl.P), blk(NT);
+    const float mc = D.marg_coef * D.margin_scale;
+    dict_dispatch_npair(npair, [&](auto np) {
+        constexpr int NP = decltype(np)::value;
+        if (pl.seed) k_dict_match_f<NP, true, GRP><<<dim3(pl.gx, pl.Ps), blk, 0, ctx->stream>>>(d_X, Npix, D.s, pack, tall, pl.tper, D.K, D.d_normD, D.d_lut, D.Q, nullptr, nullptr,
+                                                                    nullptr, nullptr, nullptr, pack16, mc, D.d_gmax, pl.seed_stride, nullptr, gv);
+        if (filt) k_dict_match_f<NP, false, GRP><<<grid, blk, 0, ctx->stream>>>(d_X, Npix, D.s, pack, tall, pl.tper, D.K, D.d_normD, D.d_lut, D.Q, d_qmap, d_pd, d_mt, d_dm,
+                                                                    part, pack16, mc, D.d_gmax, 0, win, gv);
+        else k_dict_match<NP, GRP><<<grid, blk, 0, ctx->stream>>>(d_X, Npix, D.s, pack, tall, D.K, D.d_normD, D.d_lut, D.Q, d_qmap, d_pd, d_mt, d_dm, part, win, gv);
+    });
+    QMRI_HIP(ctx, hipGetLastError());
+    if (pl.P > 1) {
+        const int n = GRP ? gv.slot_cap : Npix;
+        k_dict_merge<<<dim3((n + 255) / 256), dim3(256), 0, ctx->stream>>>(part, pl.P, n, Npix, D.K, D.d_normD, D.d_lut, D.Q, d_qmap, d_pd, d_mt, d_dm, win, gv.slot_pix);
+        QMRI_HIP(ctx, hipGetLastError());
+    }
+    return QMRI_OK;
+}
+
+int dict_group_pixel_width(const qmri_ctx* ctx) { return (ctx->dict.d_gpack16 && ctx->dict.filter_on) ? 128 : 32; }
+
+int dict_launch_grouped(qmri_ctx* ctx, const double2* d_X, int Npix, const DictGroupView& gv, int nslot_tiles, float* d_qmap, float* d_pd, float* d_mt,
+                        int32_t* d_dm, float4* win) {
+    return dict_launch_match<true>(ctx, d_X, Npix, gv, nslot_tiles, d_qmap, d_pd, d_mt, d_dm, win);
+}
 
 // d_xfit (nullable): Npix x s complex single (mrf_dtm_cpu.m:95,129-134, par.f.Xout)
 int dict_launch(qmri_ctx* ctx, const double2* d_X, int Npix, float* d_qmap, float* d_pd, float* d_mt, int32_t* d_dm, float2* d_xfit) {
@@ -451,151 +438,9 @@ int dict_launch(qmri_ctx* ctx, const double2* d_X, int Npix, float* d_qmap, floa
         win = D.d_win;
     }
     if (D.wide) QMRI_TRY(dictw_launch(ctx, d_X, Npix, d_qmap, d_pd, d_mt, d_dm, win));
-    else QMRI_TRY(dict_launch_narrow(ctx, d_X, Npix, d_qmap, d_pd, d_mt, d_dm, win));
+    else QMRI_TRY(dict_launch_match<false>(ctx, d_X, Npix, DictGroupView{}, 0, d_qmap, d_pd, d_mt, d_dm, win));
     if (d_xfit) {
         QMRI_TRY(dict_launch_xfit(ctx, win, Npix, d_xfit));
-    }
-    return QMRI_OK;
-}
-
-static int dict_launch_narrow(qmri_ctx* ctx, const double2* d_X, int Npix, float* d_qmap, float* d_pd, float* d_mt, int32_t* d_dm, float4* win) {
-    DictHost& D = ctx->dict;
-    const int npair = (D.s + 1) / 2;
-    if (npair < 1 || npair > MAXPAIR) {
-        qmri_set_error(ctx, "dictionary match supports s <= %d channels (got %d)", 2 * MAXPAIR, D.s);
-        return QMRI_ERR_UNSUPPORTED;
-    }
-    const bool filt = D.d_pack16 && D.filter_on;
-    if (!D.slots) {
-        int per_cu = 0, per_cu_f = 0;
-        hipDeviceProp_t prop;
-        QMRI_HIP(ctx, hipGetDeviceProperties(&prop, ctx->device));
-        QMRI_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_dict_match<5>, NT, 0));
-        QMRI_HIP(ctx, (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_f, k_dict_match_f<5, false>, NT, 0)));
-        D.slots = std::max(1, per_cu) * prop.multiProcessorCount;
-        D.slots_f = std::max(1, per_cu_f) * prop.multiProcessorCount;
-    }
-    // atom parts: none if the pixel tiles fill the device's resident workgroups at least four times over (a ragged last round then
-    // costs little), else as many as give ~8 rounds, each part keeping >= 64 atom tiles per wave
-    const int ptiles = filt ? (Npix + 127) / 128 : (Npix + 31) / 32;
-    const int slots = filt ? D.slots_f : D.slots;
-    int P = 1, tper = D.ntiles;
-    if (ptiles < 4 * slots) {
-        P = (8 * slots + ptiles - 1) / ptiles;
-        P = std::max(1, std::min(P, D.ntiles / (filt ? 64 : 4 * 64)));
-    }
-    if (filt) {                                                         // whole LDS steps per part, no empty part
-        tper = ((D.ntiles + P - 1) / P + FSTEP - 1) / FSTEP * FSTEP;
-        P = (D.ntiles + tper - 1) / tper;
-    }
-    float4* part = nullptr;
-    if (P > 1) {
-        QMRI_TRY(D.d_part.ensure(ctx, (size_t)P * Npix));
-        part = D.d_part;
-    }
-    dim3 grid(ptiles, P), blk(NT);
-    const float mc = D.marg_coef * D.margin_scale;
-    if (filt) {
-        QMRI_TRY(D.d_gmax.ensure(ctx, (size_t)Npix));
-        QMRI_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)D.d_gmax, (int)0xBF800000u /* -1.0f */, (size_t)Npix, ctx->stream));
-    }
-    // seed launch: ~12 steps of the whole dictionary per pixel, spread over as many workgroups as give one round of the device
-    const int nsteps_all = (D.ntiles + FSTEP - 1) / FSTEP;
-    const int seed_stride = std::max(1, nsteps_all / 12), nseed = (nsteps_all + seed_stride - 1) / seed_stride;
-    const bool seed = filt && P > 1 && nsteps_all >= 48;
-    const int Ps = seed ? std::max(1, std::min(nseed, (slots + ptiles - 1) / ptiles)) : 0;
-#define LAUNCH(NP)                                                                                                              \
-    do {                                                                                                                        \
-        if (seed) k_dict_match_f<NP, true><<<dim3(ptiles, Ps), blk, 0, ctx->stream>>>(d_X, Npix, D.s, D.d_pack, D.ntiles, tper, D.K, D.d_normD, D.d_lut, \
-                                                                    D.Q, nullptr, nullptr, nullptr, nullptr, nullptr, D.d_pack16, mc, D.d_gmax, seed_stride, nullptr, DictGroupView{}); \
-        if (filt) k_dict_match_f<NP, false><<<grid, blk, 0, ctx->stream>>>(d_X, Npix, D.s, D.d_pack, D.ntiles, tper, D.K, D.d_normD, D.d_lut, D.Q, \
-                                                                    d_qmap, d_pd, d_mt, d_dm, part, D.d_pack16, mc, D.d_gmax, 0, win, DictGroupView{}); \
-        else k_dict_match<NP><<<grid, blk, 0, ctx->stream>>>(d_X, Npix, D.s, D.d_pack, D.ntiles, D.K, D.d_normD, D.d_lut, D.Q,  \
-                                                             d_qmap, d_pd, d_mt, d_dm, part, win, DictGroupView{});             \
-    } while (0)
-    switch (npair) {
-        case 1: LAUNCH(1); break;
-        case 2: LAUNCH(2); break;
-        case 3: LAUNCH(3); break;
-        case 4: LAUNCH(4); break;
-        case 5: LAUNCH(5); break;
-        case 6: LAUNCH(6); break;
-        case 7: LAUNCH(7); break;
-        default: LAUNCH(8); break;
-    }
-#undef LAUNCH
-    QMRI_HIP(ctx, hipGetLastError());
-    if (P > 1) QMRI_TRY(dict_launch_merge(ctx, part, P, Npix, d_qmap, d_pd, d_mt, d_dm, win));
-    return QMRI_OK;
-}
-
-// The grouped match (qmri_dict_match_grouped): the same kernels on slot tiles of one group each.  gv comes from
-// the bucketing launches of dictg_launch() (dictg_kernels.hip) with the pixel width this function asks for; nslot_tiles is the largest number of slot tiles the call can
-// have (the kernels leave at once beyond the slots in use, which only the device knows).
-int dict_group_pixel_width(const qmri_ctx* ctx) { return (ctx->dict.d_gpack16 && ctx->dict.filter_on) ? 128 : 32; }
-
-int dict_launch_grouped(qmri_ctx* ctx, const double2* d_X, int Npix, const DictGroupView& gv, int nslot_tiles, float* d_qmap, float* d_pd, float* d_mt,
-                        int32_t* d_dm, float4* win) {
-    DictHost& D = ctx->dict;
-    const int npair = (D.s + 1) / 2;
-    const bool filt = D.d_gpack16 && D.filter_on;
-    if (!D.slots_g) {
-        int per_cu = 0, per_cu_f = 0;
-        hipDeviceProp_t prop;
-        QMRI_HIP(ctx, hipGetDeviceProperties(&prop, ctx->device));
-        QMRI_HIP(ctx, (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_dict_match<5, true>, NT, 0)));
-        QMRI_HIP(ctx, (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_f, k_dict_match_f<5, false, true>, NT, 0)));
-        D.slots_g = std::max(1, per_cu) * prop.multiProcessorCount;
-        D.slots_gf = std::max(1, per_cu_f) * prop.multiProcessorCount;
-    }
-    // atom parts as in dict_launch_narrow, from the largest group's tiles; a smaller group uses fewer of them (the kernels' own arithmetic)
-    const int ptiles = filt ? (Npix + 127) / 128 : (Npix + 31) / 32;
-    const int slots = filt ? D.slots_gf : D.slots_g;
-    int P = 1;
-    if (ptiles < 4 * slots) {
-        P = (8 * slots + ptiles - 1) / ptiles;
-        P = std::max(1, std::min(P, D.gtiles_max / (filt ? 64 : 4 * 64)));
-    }
-    float4* part = nullptr;
-    if (P > 1) {
-        QMRI_TRY(D.d_part.ensure(ctx, (size_t)P * gv.slot_cap));
-        part = D.d_part;
-    }
-    dim3 grid(nslot_tiles, P), blk(NT);
-    const float mc = D.marg_coef * D.margin_scale;
-    if (filt) {
-        QMRI_TRY(D.d_gmax.ensure(ctx, (size_t)gv.slot_cap));
-        QMRI_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)D.d_gmax, (int)0xBF800000u /* -1.0f */, (size_t)gv.slot_cap, ctx->stream));
-    }
-    const int nsteps_max = (D.gtiles_max + FSTEP - 1) / FSTEP;
-    const bool seed = filt && P > 1 && nsteps_max >= 48;
-    const int Ps = seed ? std::max(1, std::min(12, (slots + ptiles - 1) / ptiles)) : 0;
-    const int tall = D.gtile_h.back();
-#define LAUNCH(NP)                                                                                                              \
-    do {                                                                                                                        \
-        if (seed) k_dict_match_f<NP, true, true><<<dim3(nslot_tiles, Ps), blk, 0, ctx->stream>>>(d_X, Npix, D.s, D.d_gpack, tall, 0, D.K, D.d_normD, D.d_lut, \
-                                                                    D.Q, nullptr, nullptr, nullptr, nullptr, nullptr, D.d_gpack16, mc, D.d_gmax, 0, nullptr, gv); \
-        if (filt) k_dict_match_f<NP, false, true><<<grid, blk, 0, ctx->stream>>>(d_X, Npix, D.s, D.d_gpack, tall, 0, D.K, D.d_normD, D.d_lut, D.Q, \
-                                                                    d_qmap, d_pd, d_mt, d_dm, part, D.d_gpack16, mc, D.d_gmax, 0, win, gv); \
-        else k_dict_match<NP, true><<<grid, blk, 0, ctx->stream>>>(d_X, Npix, D.s, D.d_gpack, tall, D.K, D.d_normD, D.d_lut, D.Q,  \
-                                                                   d_qmap, d_pd, d_mt, d_dm, part, win, gv);                    \
-    } while (0)
-    switch (npair) {
-        case 1: LAUNCH(1); break;
-        case 2: LAUNCH(2); break;
-        case 3: LAUNCH(3); break;
-        case 4: LAUNCH(4); break;
-        case 5: LAUNCH(5); break;
-        case 6: LAUNCH(6); break;
-        case 7: LAUNCH(7); break;
-        default: LAUNCH(8); break;
-    }
-#undef LAUNCH
-    QMRI_HIP(ctx, hipGetLastError());
-    if (P > 1) {
-        k_dict_merge<<<dim3((gv.slot_cap + 255) / 256), dim3(256), 0, ctx->stream>>>(part, P, gv.slot_cap, Npix, D.K, D.d_normD, D.d_lut, D.Q, d_qmap, d_pd,
-                                                                                      d_mt, d_dm, win, gv.slot_pix);
-        QMRI_HIP(ctx, hipGetLastError());
     }
     return QMRI_OK;
 }

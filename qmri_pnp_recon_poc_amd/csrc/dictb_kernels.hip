@@ -7,7 +7,8 @@
 //      correctly rounded and monotone, so sqrtf(max m2) == max sqrtf(m2)).  A NaN magnitude never wins, as in the oracle's `mag > best`; a pixel
 //      whose magnitudes are all NaN scores the oracle's -1.  Zero-padded rows give 0 (or NaN for a non-finite pixel) and change no maximum.
 //      No f16 filter: every product is needed.  A maximum does not depend on the order, so the atoms of a group may be split over workgroups
-//      (parts go to a scratch array and k_dictb_finish takes their maximum; no floating-point atomics).
+//      (parts go to a scratch array and k_dictb_finish takes their maximum; no floating-point atomics).  The runs of groups and the atom parts
+//      of a launch: dict_plan_scores and dict_group_part, dict_plan.h.
 //   2. pooled argmax (fp64): E = score^2 on foreground pixels with a finite positive score, box sums over (2h+1) x (2h+1) windows as two passes
 //      of direct left-to-right sums, the lowest group with the largest pooled energy per pixel.
 #include <algorithm>
@@ -15,6 +16,7 @@
 
 #include "qmri_internal.h"
 #include "dict_device.h"
+#include "dict_plan.h"
 
 namespace {
 
@@ -25,18 +27,9 @@ constexpr int MAXPAIR = 8;      // s <= 16
 // `tm > run` is false for a NaN: a tile whose 16 rows are all NaN leaves the maximum alone (fmaxf drops a NaN beside a number).
 template <int NPAIR, int NV>
 __device__ __forceinline__ void score_tile(const f32x4 (&av)[NV], const float (&bre)[NPAIR], const float (&bim)[NPAIR], float& run) {
-    f32x16 are = {0}, aim = {0};
-#pragma unroll
-    for (int q = 0; q < NPAIR; ++q) {
-        are = __builtin_amdgcn_mfma_f32_32x32x2f32(av[q >> 2][q & 3], bre[q], are, 0, 0, 0);
-        aim = __builtin_amdgcn_mfma_f32_32x32x2f32(av[q >> 2][q & 3], bim[q], aim, 0, 0, 0);
-    }
-    float m2[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) m2[r] = __builtin_fmaf(aim[r], aim[r], are[r] * are[r]);
-    auto max3 = [](float a, float b, float c) __attribute__((always_inline)) { return fmaxf(fmaxf(a, b), c); };
-    const float tm = fmaxf(max3(max3(m2[0], m2[1], m2[2]), max3(m2[3], m2[4], m2[5]), m2[15]),
-                           max3(max3(m2[6], m2[7], m2[8]), max3(m2[9], m2[10], m2[11]), max3(m2[12], m2[13], m2[14])));
+    f32x16 are, aim;
+    exact_products<NPAIR, NV>(av, bre, bim, are, aim);
+    const float tm = tile_max2(are, aim);
     if (tm > run) run = tm;
 }
 
@@ -51,32 +44,18 @@ __global__ __launch_bounds__(NT) void k_dictb_scores(const double2* __restrict__
     const int j = lane & 31, h = lane >> 5;
     const int i = ((int)blockIdx.x * 4 + wave) * 32 + j;
     const bool valid = i < n;
-    // B fragments: B[k = 2q + h][j] = x(p, c = 2q + h)  (real chain) and -imag (conjugate) for the imaginary chain
     float bre[NPAIR], bim[NPAIR];
-#pragma unroll
-    for (int q = 0; q < NPAIR; ++q) {
-        const int c = 2 * q + h;
-        double2 v = make_double2(0.0, 0.0);
-        if (valid && c < s) v = X[(size_t)i + xstride * c];
-        bre[q] = (float)v.x;                   // single(x)  mrf_dtm_cpu.m:54
-        bim[q] = -(float)v.y;                  // conj
-    }
-    constexpr int NPL = (NPAIR <= 4) ? 4 : 8, NV = NPL / 4;
+    load_b_frags<NPAIR>(X, i, xstride, s, valid, h, bre, bim);
+    constexpr int NV = (NPAIR <= 4) ? 1 : 2;
     const int nparts = (int)gridDim.z, z = (int)blockIdx.z;
     const int g0 = (int)blockIdx.y * grun, g1 = min(G, g0 + grun);
     for (int g = g0; g < g1; ++g) {
-        // this workgroup's part of the group's tiles [t0, tall): as many parts as keep >= 64 tiles each; a part beyond them is empty
-        const int t0 = gtile[g], tall = gtile[g + 1];
-        const int np = max(1, min(nparts, (tall - t0) / 64));
-        const int tper = (tall - t0 + np - 1) / np;
-        const int tbeg = min(tall, t0 + z * tper), tend = (z < np) ? min(tall, tbeg + tper) : tbeg;
+        // this workgroup's part of the group's tiles (dict_plan.h); a part beyond the group's own is empty
+        const dplan::TileRange part_r = dplan::dict_group_part(gtile[g], gtile[g + 1], nparts, z, dplan::MIN_TILES, 1);
+        const int tbeg = part_r.tbeg, tend = part_r.tend;
         float run = -1.0f;
         f32x4 av[NV], avn[NV];
-        auto request = [&](int t, f32x4 (&dst)[NV]) __attribute__((always_inline)) {
-            const f32x4* ap = (const f32x4*)(pack + ((size_t)t * 64 + lane) * NPL);
-#pragma unroll
-            for (int v = 0; v < NV; ++v) dst[v] = ap[v];
-        };
+        auto request = [&](int t, f32x4 (&dst)[NV]) __attribute__((always_inline)) { request_tile<NV>(pack, t, lane, dst); };
         // (the fragments of the next tile are requested before the products of this one: register double buffer, as in k_dict_match)
         if (tbeg < tend) request(tbeg, av);
         for (int t = tbeg; t < tend; t += 2) {
@@ -167,47 +146,22 @@ int dictb_launch_scores(qmri_ctx* ctx, const double2* d_X, size_t Npix, size_t p
         qmri_set_error(ctx, "group scores support s <= %d channels (got %d)", 2 * MAXPAIR, D.s);
         return QMRI_ERR_UNSUPPORTED;
     }
-    if (!D.slots_b) {
-        int per_cu = 0;
-        hipDeviceProp_t prop;
-        QMRI_HIP(ctx, hipGetDeviceProperties(&prop, ctx->device));
-        QMRI_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_dictb_scores<5>, NT, 0));
-        D.slots_b = std::max(1, per_cu) * prop.multiProcessorCount;
-    }
-    // Units: pixel tiles x groups fill the device's resident workgroups about eight times over.  More than that: a workgroup takes a run of groups
-    // (its pixels are read once per run); fewer than four times: the atoms of a group are split into parts of >= 64 tiles.
-    const int ptiles = (n + 127) / 128, slots = D.slots_b;
-    const long long units = (long long)ptiles * D.G;
-    int grun = (int)std::max<long long>(1, std::min<long long>(D.G, units / (8LL * slots)));
-    const int nruns = (D.G + grun - 1) / grun;
-    int P = 1;
-    if (grun == 1 && units < 4LL * slots) {
-        P = (int)((8LL * slots + units - 1) / units);
-        P = std::max(1, std::min(std::min(P, D.gtiles_max / 64), 1024));
-    }
+    QMRI_TRY(dict_resident_slots(ctx, k_dictb_scores<5>, NT, D.slots_b));
+    const dplan::ScoresPlan pl = dplan::dict_plan_scores(n, D.G, D.gtiles_max, D.slots_b);
     float* out = d_score;
     const size_t gn = (size_t)D.G * n;
-    if (P > 1) {
-        QMRI_TRY(D.d_bpart.ensure(ctx, (size_t)P * gn));
+    if (pl.P > 1) {
+        QMRI_TRY(D.d_bpart.ensure(ctx, (size_t)pl.P * gn));
         out = D.d_bpart;
     }
-    const dim3 grid(ptiles, nruns, P), blk(NT);
+    const dim3 grid(pl.ptiles, pl.nruns, pl.P), blk(NT);
     const double2* x = d_X + p0;
-#define LAUNCH(NP) k_dictb_scores<NP><<<grid, blk, 0, ctx->stream>>>(x, Npix, n, D.s, D.d_gpack, D.d_gtile, D.G, grun, out)
-    switch (npair) {
-        case 1: LAUNCH(1); break;
-        case 2: LAUNCH(2); break;
-        case 3: LAUNCH(3); break;
-        case 4: LAUNCH(4); break;
-        case 5: LAUNCH(5); break;
-        case 6: LAUNCH(6); break;
-        case 7: LAUNCH(7); break;
-        default: LAUNCH(8); break;
-    }
-#undef LAUNCH
+    dict_dispatch_npair(npair, [&](auto np) {
+        k_dictb_scores<decltype(np)::value><<<grid, blk, 0, ctx->stream>>>(x, Npix, n, D.s, D.d_gpack, D.d_gtile, D.G, pl.grun, out);
+    });
     QMRI_HIP(ctx, hipGetLastError());
-    if (P > 1) {
-        k_dictb_finish<<<dim3((unsigned)((gn + 255) / 256)), dim3(256), 0, ctx->stream>>>(out, P, gn, d_score);
+    if (pl.P > 1) {
+        k_dictb_finish<<<dim3((unsigned)((gn + 255) / 256)), dim3(256), 0, ctx->stream>>>(out, pl.P, gn, d_score);
         QMRI_HIP(ctx, hipGetLastError());
     }
     return QMRI_OK;

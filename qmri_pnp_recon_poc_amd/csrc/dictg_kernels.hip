@@ -9,11 +9,13 @@
 //     slot -> pixel table.  The match reads X and writes its outputs THROUGH that table (a gathered copy of X would cost a pass of 16 s bytes per
 //     pixel each way for nothing: a lane reads its pixel's s values once, at the start of the workgroup).  Slots are handed out by an integer
 //     atomic; no result depends on which slot a pixel got.  Unmatched pixels (non-finite selector) get no slot and their zeros here.
+//     The layout of the bucketing scratch (DictgWork) and the atom parts of the match are dict_plan.h's.
 #include <cfloat>
 #include <cmath>
 
 #include "qmri_internal.h"
 #include "dict_device.h"
+#include "dict_plan.h"
 
 // g(b), 1-based: the lowest g that minimises fabs(b - group_val[g]) in fp64; 0 (unmatched) for a non-finite b.  One subtraction and one fabs per
 // group -- nothing a compiler may contract or reorder -- so the host and the device give the same integers.
@@ -176,23 +178,11 @@ int dictg_set_groups(qmri_ctx* ctx, int G, const int32_t* group_ptr, const doubl
     return QMRI_OK;
 }
 
-// Layout of the bucketing scratch for Npix pixels, G groups, pixel width padw (ints): the most slots a call can use is every pixel plus less than
-// one width of padding per group.
-struct DictgWork { int slot_cap, ntiles; size_t grp, count, cursor, slot_beg, tile_grp, slot_pix, total; };
-static DictgWork dictg_work(int Npix, int G, int padw) {
-    DictgWork w;
-    w.ntiles = (Npix + padw - 1) / padw + G;
-    w.slot_cap = w.ntiles * padw;
-    w.grp = 0; w.count = w.grp + (size_t)Npix; w.cursor = w.count + 256; w.slot_beg = w.cursor + 256; w.tile_grp = w.slot_beg + 257;
-    w.slot_pix = w.tile_grp + (size_t)w.ntiles; w.total = w.slot_pix + (size_t)w.slot_cap;
-    return w;
-}
-
 int dictg_launch(qmri_ctx* ctx, const double2* d_X, int Npix, const double* d_sel, float* d_qmap, float* d_pd, float* d_mt, int32_t* d_dm, int32_t* d_grp,
                  float2* d_xfit) {
     DictHost& D = ctx->dict;
     const int padw = dict_group_pixel_width(ctx);
-    const DictgWork w = dictg_work(Npix, D.G, padw);
+    const dplan::DictgWork w = dplan::dictg_work(Npix, D.G, padw);           // the bucketing scratch (dict_plan.h)
     QMRI_TRY(D.d_gwork.ensure(ctx, w.total));
     float4* win = nullptr;
     if (d_xfit) {

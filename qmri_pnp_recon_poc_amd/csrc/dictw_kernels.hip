@@ -12,7 +12,8 @@
 // stages of 16 and the real and imaginary chains accumulate in v_mfma_f32_32x32x2_f32 in ASCENDING channel order -- an f32 MFMA is a k-ordered
 // chain of fmaf, so ip carries the bits of the oracle's sequential fmaf chain over c = 0 .. s-1 (zero padding adds fma(0, 0, acc) = acc) -- and
 // the finished 32 x 32 tiles go through the same incumbent rule as the narrow kernels (inc_update, dict_device.h).  Atoms are split into P
-// parts over workgroups; k_dict_merge picks per pixel by the same rule (larger magnitude, then lower index).
+// parts over workgroups (dict_plan_wide and the workgroup order dictw_decode, dict_plan.h); k_dict_merge picks per pixel by the same rule
+// (larger magnitude, then lower index).
 //
 // Layouts (fragment order, so that both the global -> LDS copy and the LDS -> register reads are plain 16-byte-per-lane contiguous moves;
 // a wave's ds_read_b128 covers 1 KB in lane order: conflict-free by the lane-group table of MI355X_MICROARCH.md):
@@ -23,6 +24,7 @@
 #include <algorithm>
 #include "qmri_internal.h"
 #include "dict_device.h"
+#include "dict_plan.h"
 
 namespace {
 
@@ -68,16 +70,11 @@ __global__ __launch_bounds__(256) void k_dictw_pack_x(const double2* __restrict_
 __global__ __launch_bounds__(WT, 2) void k_dictw_match(const float4* __restrict__ DP, const float4* __restrict__ XP, int G8, int AT, int PT, int P,
                                                         int tper, int Npix, float4* __restrict__ part, int lsp) {
     __shared__ float4 s_buf[2][STAGE_F4];
-    // workgroup order: blockIdx.x % 8 is the XCD under round-robin placement (speed only); an XCD walks super-tiles of 2^lsp pixel tiles x
-    // 2^(6 - lsp) atom parts (64 workgroups = what it holds at once)
-    const int id = blockIdx.x, xcd = id & 7, kk = id >> 3;
-    const int lsa = 6 - lsp;
-    const int SPT = (PT + (1 << lsp) - 1) >> lsp, SPP = (P + (1 << lsa) - 1) >> lsa;
-    const int sidx = xcd + 8 * (kk >> 6), within = kk & 63;
-    if (sidx >= SPT * SPP) return;
-    const int pt = ((sidx % SPT) << lsp) + (within & ((1 << lsp) - 1)), prt = ((sidx / SPT) << lsa) + (within >> lsp);
-    if (pt >= PT || prt >= P) return;
-    const int t0 = prt * tper, nt = min(tper, AT - t0);
+    // workgroup order: XCD super-tiles (dplan::dictw_decode, dict_plan.h; speed only)
+    int pt, prt;
+    if (!dplan::dictw_decode((int)blockIdx.x, PT, P, lsp, pt, prt)) return;
+    const dplan::TileRange part_r = dplan::dict_part(0, AT, tper, prt);
+    const int t0 = part_r.tbeg, nt = part_r.tend - t0;
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int wa = wave & 1, wp = wave >> 1, h = lane >> 5, j = lane & 31;
     const int nstage = G8 >> 1;
@@ -156,9 +153,7 @@ __global__ __launch_bounds__(WT, 2) void k_dictw_match(const float4* __restrict_
     float4* s_c = s_buf[0];                                               // [wp][nb][j]
 #pragma unroll
     for (int nb = 0; nb < 2; ++nb) {
-        const float ob = __shfl(I[nb].best, lane ^ 32, 64), ore = __shfl(I[nb].cre, lane ^ 32, 64), oim = __shfl(I[nb].cim, lane ^ 32, 64);
-        const int oi = __shfl(I[nb].bidx, lane ^ 32, 64);
-        if (cand_better(ob, oi, I[nb].best, I[nb].bidx)) { I[nb].best = ob; I[nb].bidx = oi; I[nb].cre = ore; I[nb].cim = oim; }
+        merge_lane_halves(I[nb], lane);
         if (wa == 1 && h == 0) s_c[(wp * 2 + nb) * 32 + j] = make_float4(I[nb].best, __int_as_float(I[nb].bidx), I[nb].cre, I[nb].cim);
     }
     __syncthreads();
@@ -198,33 +193,16 @@ int dictw_pack_dictionary(qmri_ctx* ctx, const float* D_host, int K, int s) {
 
 int dictw_launch(qmri_ctx* ctx, const double2* d_X, int Npix, float* d_qmap, float* d_pd, float* d_mt, int32_t* d_dm, float4* win) {
     DictHost& D = ctx->dict;
-    if (!D.slots_w) {
-        int per_cu = 0;
-        hipDeviceProp_t prop;
-        QMRI_HIP(ctx, hipGetDeviceProperties(&prop, ctx->device));
-        QMRI_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_dictw_match, WT, 0));
-        D.slots_w = std::max(1, per_cu) * prop.multiProcessorCount;
-    }
-    const int PT = (Npix + 127) / 128, AT = D.ntiles / 4;
-    // atom parts: ~20 rounds of the device's resident workgroups (a ragged last round then costs < 5 %), whole groups of 16 for the XCD super-tiles
-    int P = std::max(1, std::min(AT, (20 * D.slots_w + PT - 1) / PT));
-    if (P < AT) P = std::min(AT, (P + 15) / 16 * 16);
-    const int tper = (AT + P - 1) / P;
-    P = (AT + tper - 1) / tper;                                          // no empty part
-    const size_t nxp = (size_t)PT * 4 * D.G8 * 2 * 64;                   // float4
-    QMRI_TRY(D.d_xp.ensure(ctx, nxp));
-    QMRI_TRY(D.d_part.ensure(ctx, (size_t)P * Npix));
-    const size_t nthr = (size_t)PT * 4 * D.G8 * 64;
-    k_dictw_pack_x<<<dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, ctx->stream>>>(d_X, Npix, D.s, D.G8, PT * 4, (float4*)D.d_xp);
-    QMRI_HIP(ctx, hipGetLastError());
+    QMRI_TRY(dict_resident_slots(ctx, k_dictw_match, WT, D.slots_w));
     // shape of the XCD super-tile (QMRI_DICTW_LSP for A/Bs): 4 pixel tiles x 16 atom parts.  Measured at s = 1000, K = 98 304 (profiles/r04_i_*): the
     // launch time does not depend on it (144 - 147 ms: the kernel is compute-bound), the bytes leaving the L2s do -- FETCH_SIZE as counted 167 GB (64 x 1),
     // 124 GB (8 x 8), 50 GB (4 x 16), 55 GB (2 x 32): X tiles (8 bytes per pixel and channel) are the larger operand, so more parts per pixel tile pay.
-    const int lsp_env = qmri_knob(K_DICTW_LSP);
-    const int lsp = std::max(0, std::min(6, lsp_env)), lsa = 6 - lsp;
-    const int nsuper = ((PT + (1 << lsp) - 1) >> lsp) * ((P + (1 << lsa) - 1) >> lsa);
-    const unsigned grid = 8u * 64u * (unsigned)((nsuper + 7) / 8);
-    k_dictw_match<<<dim3(grid), dim3(WT), 0, ctx->stream>>>((const float4*)D.d_pack, (const float4*)D.d_xp, D.G8, AT, PT, P, tper, Npix, D.d_part, lsp);
+    const dplan::WidePlan pl = dplan::dict_plan_wide(Npix, D.ntiles, D.G8, D.slots_w, qmri_knob(K_DICTW_LSP));
+    QMRI_TRY(D.d_xp.ensure(ctx, pl.nxp));
+    QMRI_TRY(D.d_part.ensure(ctx, pl.npart));
+    k_dictw_pack_x<<<dim3((unsigned)((pl.nxp / 2 + 255) / 256)), dim3(256), 0, ctx->stream>>>(d_X, Npix, D.s, D.G8, pl.PT * 4, (float4*)D.d_xp);
     QMRI_HIP(ctx, hipGetLastError());
-    return dict_launch_merge(ctx, D.d_part, P, Npix, d_qmap, d_pd, d_mt, d_dm, win);
+    k_dictw_match<<<dim3(pl.grid), dim3(WT), 0, ctx->stream>>>((const float4*)D.d_pack, (const float4*)D.d_xp, D.G8, pl.AT, pl.PT, pl.P, pl.tper, Npix, D.d_part, pl.lsp);
+    QMRI_HIP(ctx, hipGetLastError());
+    return dict_launch_merge(ctx, D.d_part, pl.P, Npix, d_qmap, d_pd, d_mt, d_dm, win);
 }

@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/qmri.h"
@@ -679,6 +680,31 @@ size_t conv_pack_weights(const ConvLayer& L, const float* w_src, std::vector<flo
 void conv_plan_layer(ConvLayer& L, ConvKind kind, int Cin, int Cout);
 
 // dictionary match (dict_kernels.hip)
+// `cache` (a slots_* of DictHost) = workgroups of `kernel` the device holds at once; queried on first use
+template <class Kernel>
+int dict_resident_slots(qmri_ctx* ctx, Kernel kernel, int threads, int& cache) {
+    if (cache) return QMRI_OK;
+    int per_cu = 0;
+    hipDeviceProp_t prop;
+    QMRI_HIP(ctx, hipGetDeviceProperties(&prop, ctx->device));
+    QMRI_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, 0));
+    cache = std::max(1, per_cu) * prop.multiProcessorCount;
+    return QMRI_OK;
+}
+// f(std::integral_constant<int, NPAIR>) for the channel pairs of a narrow dictionary, 1 .. 8: the kernels are instantiated per pair count
+template <class F>
+void dict_dispatch_npair(int npair, F&& f) {
+    switch (npair) {
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 3: f(std::integral_constant<int, 3>{}); break;
+        case 4: f(std::integral_constant<int, 4>{}); break;
+        case 5: f(std::integral_constant<int, 5>{}); break;
+        case 6: f(std::integral_constant<int, 6>{}); break;
+        case 7: f(std::integral_constant<int, 7>{}); break;
+        default: f(std::integral_constant<int, 8>{}); break;
+    }
+}
 int dict_launch(qmri_ctx* ctx, const double2* d_X, int Npix, float* d_qmap, float* d_pd, float* d_mt, int32_t* d_dm, float2* d_xfit);
 int dict_launch_xfit(qmri_ctx* ctx, const float4* win, int Npix, float2* d_xfit);
 // grouped match (dictg_kernels.hip: groups, pixel bucketing; dict_kernels.hip: the match on slot tiles)
