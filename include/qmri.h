@@ -811,6 +811,58 @@ int qmri_llr_prox_dev(qmri_ctx* ctx, int N, int M, int s, int nslices, const voi
  * qmri_llr_prox on tau, block and reserved, shift outside {0, 1}. */
 int qmri_set_llr(qmri_ctx* ctx, const qmri_llr_params* p);
 
+/* ---- joint wavelet soft-thresholding (extension, no reference counterpart, parity unpinned) ---- */
+/* The proximal step of the l1-wavelet penalty on the coefficient images of subspace MR fingerprinting, thresholded jointly over the subspace
+ * channels: an orthogonal, periodic, L-level 2-D wavelet transform of every channel plane, a shrink of the detail coefficients, the inverse.
+ * It needs no trained weights, is defined for complex images and does not involve the operator.
+ *   X: N x M x s complex fp64, [n1 + N n2 + N M c] per slice, slices outermost; 1 <= s <= 16.
+ *   Filters, T taps: Haar, T = 2, h = [1, 1] / sqrt 2; Daubechies-2, T = 4, h = [1 + sqrt 3, 3 + sqrt 3, 3 - sqrt 3, 1 - sqrt 3] / (4 sqrt 2);
+ *   high-pass g[j] = (-1)^j h[T-1-j].  One level on a length-n axis (n even, n >= T): a[k] = sum_j h[j] x[(2k+j) mod n] and
+ *   d[k] = sum_j g[j] x[(2k+j) mod n], k < n / 2; synthesis x[(2k+j) mod n] += h[j] a[k] + g[j] d[k].
+ *   Level l = 1 .. L acts on the top-left (N / 2^(l-1)) x (M / 2^(l-1)) corner, axis 0 (N) first, approximation coefficients in the low half of
+ *   each axis (Mallat layout); synthesis is the exact reverse.  1 <= L <= 4, 2^L | N, 2^L | M, N / 2^(L-1) >= T and M / 2^(L-1) >= T.
+ *   Shift: with P = 2^L and 0 <= o1, o2 < P the transform is taken of Xs[n1, n2] = X[(n1 + o1) mod N, (n2 + o2) mod M] and the result shifted back.
+ *   Shrink, at every coefficient position outside the final (N / 2^L) x (M / 2^L) approximation corner: m = sqrt(sum_c |C_c|^2) over the channels
+ *   (joint = 1) or |C_c| (joint = 0); C <- f C with f = m > tau ? 1 - tau / m : 0.  The approximation corner is never thresholded.
+ *   cmax of a slice = the largest m over its detail positions before thresholding (joint = 0: over the channels as well).
+ *   Real mode works on real(X); its output has an imaginary part that is exactly 0.
+ * tau = 0 is the identity up to rounding; a zero image stays exactly zero.  All fp64, every sum in one fixed order, no atomics: a slice has the
+ * same bits alone, at any position of a stack and for any nslices.  A non-finite m gives a non-finite f: a non-finite value reaches the outputs
+ * its coefficients reach (Haar: its own shifted 2^L x 2^L block) and no other slice. */
+#define QMRI_WAVELET_HAAR 0
+#define QMRI_WAVELET_DB2  1
+typedef struct {
+    double  tau;          /* threshold, in the units of the TSMI, >= 0 and finite */
+    int32_t levels;       /* 1 .. 4; 0 = 3 */
+    int32_t filter;       /* QMRI_WAVELET_HAAR, QMRI_WAVELET_DB2 */
+    int32_t joint;        /* 0: per channel, 1: jointly over the s channels */
+    int32_t shift;        /* 0: always the offsets (0,0); 1: the offsets cycle with the ADMM iteration */
+    int32_t reserved[4];  /* must be zero */
+} qmri_wavelet_params;    /* 40 bytes */
+/* Host arrays.  x: [slice][c][n2][n1], complex fp64 (x_is_complex = 1) or real fp64 (x_is_complex = 0: real mode); out: complex fp64 in the same
+ * layout; cmax_out (nullable): nslices doubles.  p->shift is ignored (the offsets are arguments).  Needs neither an operator, a denoiser nor a
+ * dictionary.  Refusals are decided on the host before the device is selected (ctx == NULL: the message of the first failing check in
+ * qmri_last_error(NULL)): a NULL x / p / out, nslices < 1, s outside 1..16, levels outside 0..4, an unknown filter, joint outside
+ * {0, 1}, a negative or non-finite tau, reserved != 0, a side that breaks the size rule, an offset outside 0..2^L-1: QMRI_ERR_INVALID_ARG.
+ * Returns after its kernels have finished. */
+int qmri_wavelet_prox(qmri_ctx* ctx, int N, int M, int s, int nslices, const void* x, int x_is_complex, const qmri_wavelet_params* p, int o1,
+                      int o2, void* out, double* cmax_out);
+/* The same with d_x and d_out (complex fp64 both) on ctx's device; x_is_complex = 0: real mode, the real part of d_x is taken.  d_out may alias
+ * d_x.  cmax_out (nullable) stays a host array.  Same bits as the host-array call.  Runs on the context's stream and returns after its kernels
+ * have finished. */
+int qmri_wavelet_prox_dev(qmri_ctx* ctx, int N, int M, int s, int nslices, const void* d_x, int x_is_complex, const qmri_wavelet_params* p,
+                          int o1, int o2, void* d_out, double* cmax_out);
+/* Selects the wavelet step as Step 2 of the PnP-ADMM loops (p == NULL: back to the network), with the conventions of qmri_set_llr: while set,
+ * qmri_pnp_admm, _dev, _batch, qmri_pnp_admm_mc, _mc_batch and _mc_dev compute v = Wav_tau(x + uold) -- of the complex x + uold with
+ * QMRI_DENOISER_COMPLEX, else of real(x + uold) -- and need no denoiser; the multi_level bit and noise_std are ignored.  ADMM iteration `it`
+ * (0-based) uses the offsets (0, 0) with shift = 0, else, with P = 2^L, q = it mod P^2, o1 = q mod P, o2 = (q div P + q) mod P.  The gridded loop
+ * runs its unfused launch sequence; the prox time goes to ms_denoiser.  The size rule is tested against the operator in force at the ADMM call,
+ * which otherwise returns QMRI_ERR_INVALID_ARG.  qmri_recon_batch* are not affected.  One regulariser at a time: a non-NULL p while the LLR step
+ * is set returns QMRI_ERR_STATE (clear it with qmri_set_llr(ctx, NULL) first), and qmri_set_llr with a non-NULL p while the wavelet step is set
+ * returns QMRI_ERR_STATE (clear it with qmri_set_wavelet(ctx, NULL) first); a failing call leaves the state as it was.  Refusals (host only): the
+ * checks of qmri_wavelet_prox on tau, levels, filter, joint and reserved, shift outside {0, 1}. */
+int qmri_set_wavelet(qmri_ctx* ctx, const qmri_wavelet_params* p);
+
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------------ */
 typedef struct {
     double ms_xupdate, ms_denoiser, ms_elementwise, ms_diag, ms_match;   /* hipEvent time per stage */

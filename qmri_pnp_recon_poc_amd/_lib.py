@@ -24,7 +24,7 @@ SYMBOLS = [
     "qmri_dict_match_dev", "qmri_dict_match_xfit", "qmri_dict_match_xfit_dev", "qmri_set_dictionary_groups", "qmri_dict_group_assign", "qmri_dict_match_grouped",
     "qmri_dict_match_grouped_dev", "qmri_dict_group_scores", "qmri_dict_group_scores_dev", "qmri_b1_pool", "qmri_b1_pool_dev", "qmri_b1_estimate",
     "qmri_b1_estimate_dev", "qmri_set_components", "qmri_dict_unmix", "qmri_dict_unmix_dev", "qmri_recon_batch", "qmri_recon_batch_mc",
-    "qmri_coil_compress", "qmri_coil_compress_dev", "qmri_coil_eig", "qmri_recon_batch_mc_cc", "qmri_coil_maps", "qmri_coil_maps_dev", "qmri_dict_compress", "qmri_dict_compress_dev", "qmri_dict_simulate", "qmri_dict_simulate_dev", "qmri_dict_simulate_sp", "qmri_dict_simulate_sp_dev", "qmri_field_map_estimate", "qmri_field_map_estimate_dev", "qmri_llr_prox", "qmri_llr_prox_dev", "qmri_set_llr", "qmri_profile_enable", "qmri_profile_get", "qmri_get_health",
+    "qmri_coil_compress", "qmri_coil_compress_dev", "qmri_coil_eig", "qmri_recon_batch_mc_cc", "qmri_coil_maps", "qmri_coil_maps_dev", "qmri_dict_compress", "qmri_dict_compress_dev", "qmri_dict_simulate", "qmri_dict_simulate_dev", "qmri_dict_simulate_sp", "qmri_dict_simulate_sp_dev", "qmri_field_map_estimate", "qmri_field_map_estimate_dev", "qmri_llr_prox", "qmri_llr_prox_dev", "qmri_set_llr", "qmri_wavelet_prox", "qmri_wavelet_prox_dev", "qmri_set_wavelet", "qmri_profile_enable", "qmri_profile_get", "qmri_get_health",
     "qmri_debug_lsqr_stamps", "qmri_debug_conv_stamps", "qmri_debug_lsqr_persist", "qmri_debug_dict_filter", "qmri_debug_conv_resident", "qmri_debug_dsvd_gram", "qmri_debug_epg_shift", "qmri_debug_knob", "qmri_debug_mem_stats",
     "qmri_onnx_read_unetres",
     "qmri_lrtv", "qmri_prox_tv", "qmri_norm_tv", "qmri_synthesize_tsmi", "qmri_synthesize_tsmi_complex",
@@ -119,6 +119,14 @@ class FieldmapInfo(C.Structure):
 
 class LlrParams(C.Structure):
     _fields_ = [("tau", C.c_double), ("block", C.c_int32), ("shift", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
+class WaveletParams(C.Structure):
+    _fields_ = [("tau", C.c_double), ("levels", C.c_int32), ("filter", C.c_int32), ("joint", C.c_int32), ("shift", C.c_int32),
+                ("reserved", C.c_int32 * 4)]
+
+
+WAVELET_FILTERS = {"haar": 0, "db2": 1}
 
 
 class PvInfo(C.Structure):
@@ -285,6 +293,9 @@ def lib() -> C.CDLL:
     L.qmri_llr_prox.argtypes = [vp, i, i, i, i, vp, i, C.POINTER(LlrParams), i, i, vp, dp]
     L.qmri_llr_prox_dev.argtypes = [vp, i, i, i, i, vp, i, C.POINTER(LlrParams), i, i, vp, dp]
     L.qmri_set_llr.argtypes = [vp, C.POINTER(LlrParams)]
+    L.qmri_wavelet_prox.argtypes = [vp, i, i, i, i, vp, i, C.POINTER(WaveletParams), i, i, vp, dp]
+    L.qmri_wavelet_prox_dev.argtypes = [vp, i, i, i, i, vp, i, C.POINTER(WaveletParams), i, i, vp, dp]
+    L.qmri_set_wavelet.argtypes = [vp, C.POINTER(WaveletParams)]
     L.qmri_debug_knob.argtypes = [C.c_char_p, i]
     L.qmri_debug_mem_stats.argtypes = [C.POINTER(MemStats)]
     L.qmri_profile_enable.argtypes = [vp, i]

@@ -87,12 +87,21 @@ static int admm_net_fits(qmri_ctx* ctx, const qmri_admm_params* prm, int* multi_
 
 // What Step 2 needs before a loop starts.  With the LLR regulariser set (qmri_set_llr) no network is involved: denoiser_type
 // keeps its range, its multi_level bit is ignored, and the block side must divide the grid of the operator in force.
+// The joint wavelet soft-thresholding (qmri_set_wavelet) takes the same place: its size rule (wav_plan.h) must hold on that grid.
+static bool admm_regulariser_on(const qmri_ctx* ctx) { return ctx->llr.on || ctx->wav.on; }      // a training-free Step 2: no network is involved
 static int admm_step_fits(qmri_ctx* ctx, const qmri_admm_params* prm, int* multi_out, bool* cpx_out) {
-    if (!ctx->llr.on) return admm_net_fits(ctx, prm, multi_out, cpx_out);
+    if (!admm_regulariser_on(ctx)) return admm_net_fits(ctx, prm, multi_out, cpx_out);
     const OpHost& o = ctx->op;
     QMRI_CHECK_ARG(ctx, prm->denoiser_type >= 0 && prm->denoiser_type <= (QMRI_DENOISER_COMPLEX | QMRI_DENOISER_MULTI_LEVEL),
                    "denoiser_type must be 0 .. 3 (QMRI_DENOISER_MULTI_LEVEL | QMRI_DENOISER_COMPLEX)");
-    if (o.N % ctx->llr.block || o.M % ctx->llr.block || o.s > 16) {
+    if (ctx->wav.on) {
+        if (!wav::sizes_ok(o.N, o.M, ctx->wav.levels, wav::taps(ctx->wav.filter)) || o.s > wav::MAX_S) {
+            qmri_set_error(ctx, "invalid argument: the wavelet regulariser (%d levels, %d taps, at most 16 channels) does not fit the operator (%d x %d x %d): "
+                                "2^levels must divide both sides and the last level's input must be at least the filter length",
+                           ctx->wav.levels, wav::taps(ctx->wav.filter), o.N, o.M, o.s);
+            return QMRI_ERR_INVALID_ARG;
+        }
+    } else if (o.N % ctx->llr.block || o.M % ctx->llr.block || o.s > 16) {
         qmri_set_error(ctx, "invalid argument: the LLR regulariser (block side %d, at most 16 channels) does not fit the operator (%d x %d x %d): the "
                             "block side must divide both sides", ctx->llr.block, o.N, o.M, o.s);
         return QMRI_ERR_INVALID_ARG;
@@ -137,10 +146,22 @@ static int admm_to_net(qmri_ctx* ctx, const DenoiserStep& d, int mm_nblk, bool m
 // The denoiser step as three launches (both loops; the gridded one's fused form folds the third into the next x-update): step 2, then step 3
 // (PnP_ADMM.m:138,144): v = I*range + min ; uold = uold + x - v ; z = v - uold with the partials of ||z||^2
 // With the LLR regulariser set, two launches: v = LLR_tau(x + uold) at the offsets of iteration `it`, then step 3 on v.
+// With the wavelet regulariser set, v = Wav_tau(x + uold) in its 2 L + 1 launches, then the same step 3.
 static int admm_denoiser_step(qmri_ctx* ctx, const DenoiserStep& d, bool copy_range_flag, int it) {
     OpHost& o = ctx->op;
     NetPlan& net = ctx->net;
     const size_t plane = (size_t)o.N * o.M;
+    if (ctx->wav.on) {
+        const WavState& w = ctx->wav;
+        WavPlan pl = {o.N, o.M, o.s, w.levels, w.filter, w.joint, 0, 0, d.cpx ? 0 : 1, w.tau};
+        wav::offsets(it, 1 << w.levels, w.shift, &pl.o1, &pl.o2);
+        if (d.tm) d.tm->start();
+        QMRI_TRY(wav_prox_dev(ctx, pl, d.B, d.d_x, o.d_u, o.d_vv, nullptr));
+        if (d.tm) { d.tm->stop(ctx->prof.ms_denoiser); d.tm->start(); }
+        QMRI_TRY(llr_dual_dev(ctx, d.B, plane * o.s, d.d_x, o.d_vv, o.d_u, o.d_z, o.ls.pz, o.ls.nblk_z));
+        if (d.tm) d.tm->stop(ctx->prof.ms_elementwise);
+        return QMRI_OK;
+    }
     if (ctx->llr.on) {
         LlrPlan pl = {o.N, o.M, o.s, ctx->llr.block, 0, 0, d.cpx ? 0 : 1, ctx->llr.tau};
         llr_offsets(it, pl.block, ctx->llr.shift, &pl.o1, &pl.o2);
@@ -173,7 +194,7 @@ static int mc_require(qmri_ctx* ctx, int nslices, int ncoil, const void* maps, c
 }
 static int mc_admm_check(qmri_ctx* ctx, const qmri_admm_params* prm) {
     const NetPlan& net = ctx->net;
-    if (!net.ready && !ctx->llr.on) { qmri_set_error(ctx, "denoiser not set: call qmri_set_denoiser first"); return QMRI_ERR_STATE; }
+    if (!net.ready && !admm_regulariser_on(ctx)) { qmri_set_error(ctx, "denoiser not set: call qmri_set_denoiser first"); return QMRI_ERR_STATE; }
     QMRI_CHECK_ARG(ctx, prm, "params must not be NULL");
     QMRI_TRY(toep_check_solver(ctx, prm->solver));            // (QMRI_SOLVER_TOEPLITZ: a trajectory operator only)
     QMRI_CHECK_ARG(ctx, prm->iters >= 0 && prm->gamma > 0 && prm->cg_maxit >= 0 && (prm->solver == QMRI_SOLVER_LSQR || prm->solver == QMRI_SOLVER_TOEPLITZ),
@@ -188,8 +209,8 @@ static int mc_admm_check(qmri_ctx* ctx, const qmri_admm_params* prm) {
 static int mc_admm_group(qmri_ctx* ctx, int B, int ncoil, const double2* d_maps, const double2* d_y, const qmri_admm_params* prm, const double2* d_x0,
                          double2* d_x, int32_t* li_out, int li_stride) {
     OpHost& o = ctx->op;
-    const bool llr = ctx->llr.on;                                                      // (no network: nothing can trip, nothing is waited for)
-    const int multi = (!llr && (prm->denoiser_type & QMRI_DENOISER_MULTI_LEVEL)) ? 1 : 0;   // (checked by mc_admm_check)
+    const bool reg = admm_regulariser_on(ctx);                                                      // (no network: nothing can trip, nothing is waited for)
+    const int multi = (!reg && (prm->denoiser_type & QMRI_DENOISER_MULTI_LEVEL)) ? 1 : 0;   // (checked by mc_admm_check)
     const bool cpx = (prm->denoiser_type & QMRI_DENOISER_COMPLEX) != 0;
     const size_t n = (size_t)o.N * o.M * o.s;
     std::vector<int32_t> li((size_t)B);
@@ -202,7 +223,7 @@ static int mc_admm_group(qmri_ctx* ctx, int B, int ncoil, const double2* d_maps,
             QMRI_TRY(mc_xupdate_dev(ctx, prm->solver, B, ncoil, d_maps, d_y, o.d_z, prm->gamma, prm->cg_tol, prm->cg_maxit, d_x, li.data(), nullptr));   // :102
             if (li_out) for (int b = 0; b < B; ++b) li_out[(size_t)b * li_stride + it] = li[b];
             QMRI_TRY(admm_denoiser_step(ctx, {B, prm, multi, cpx, d_x, nullptr}, false, it));                                                       // :115-144
-            if (llr) continue;
+            if (reg) continue;
             QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
             QMRI_TRY(net_range_tripped(ctx, again));              // (f16 range / hand-off guards: the network is re-packed or the form switched; start again)
             if (again) break;
@@ -278,11 +299,11 @@ static int pnp_admm_dev_impl(qmri_ctx* ctx, int nslices, const void* d_y, const 
     OpHost& o = ctx->op;
     NetPlan& net = ctx->net;
     if (!o.ready) { qmri_set_error(ctx, "operator not set: call qmri_set_operator first"); return QMRI_ERR_STATE; }
-    const bool llr = ctx->llr.on;                          // Step 2 is the LLR prox: no network, so no fused launches, no range guard and no repeat
-    if (!net.ready && !llr) { qmri_set_error(ctx, "denoiser not set: call qmri_set_denoiser first"); return QMRI_ERR_STATE; }
+    const bool reg = admm_regulariser_on(ctx);                          // Step 2 is a training-free prox (LLR or wavelet): no network, so no fused launches, no range guard and no repeat
+    if (!net.ready && !reg) { qmri_set_error(ctx, "denoiser not set: call qmri_set_denoiser first"); return QMRI_ERR_STATE; }
     QMRI_CHECK_ARG(ctx, d_y && prm && d_x_out, "y / params / x_out must not be NULL");
     const int B = nslices;
-    QMRI_CHECK_ARG(ctx, B >= 1 && B <= o.maxB && (llr || B <= net.maxB), "nslices exceeds max_batch of the operator or the denoiser");
+    QMRI_CHECK_ARG(ctx, B >= 1 && B <= o.maxB && (reg || B <= net.maxB), "nslices exceeds max_batch of the operator or the denoiser");
     QMRI_CHECK_ARG(ctx, prm->iters >= 0 && prm->gamma > 0 && prm->cg_maxit >= 0, "iters >= 0, gamma > 0, cg_maxit >= 0 required");
     int multi = 0;
     bool cpx = false;
@@ -319,7 +340,7 @@ static int pnp_admm_dev_impl(qmri_ctx* ctx, int nslices, const void* d_y, const 
     // Round 4: the small launches around the network are folded into their neighbours (LSQR solver; knob fuse_ew = 0 restores the separate kernels
     // for A/Bs): un-normalise + dual update + z + the h-pass of z's transform + the forward pass's |output| report = ONE launch (k_dual_fwd_h);
     // the w-pass of z rides in the solve's first kernel (k_ks_init_a<FWDW>); the min / max of real(x + u) come out of the solve's last h-pass.
-    const bool fused = qmri_knob(K_FUSE_EW) != 0 && prm->solver == QMRI_SOLVER_LSQR && !llr;
+    const bool fused = qmri_knob(K_FUSE_EW) != 0 && prm->solver == QMRI_SOLVER_LSQR && !reg;
     const int hb = dc_hpass_blocks(op);
     bool z_in_tmp = false;                                 // o.d_tmp holds the h-pass of z (and ls.pz hb partial sums per slice)
     struct DeferGuard { NetPlan& n; ~DeferGuard() { n.act_defer = false; n.act_pending_valid = false; } } defer_guard{net};
@@ -341,7 +362,7 @@ static int pnp_admm_dev_impl(qmri_ctx* ctx, int nslices, const void* d_y, const 
             // The range guard of earlier forwards is on the host (pinned words written by k_act_check).  After a wait inside qmri_lsqr_run (the
             // two-launch iteration) it is current up to the previous iteration; without one it is whatever has arrived.  A tripped guard ends
             // this attempt at once instead of after all iterations.
-            if (it > 0 && !llr && net.sp6 == 2 && host_range_tripped(net)) { range_trip = true; tm.stop(ctx->prof.ms_xupdate); break; }
+            if (it > 0 && !reg && net.sp6 == 2 && host_range_tripped(net)) { range_trip = true; tm.stop(ctx->prof.ms_xupdate); break; }
         } else {
             QMRI_TRY(dc_launch_direct(ctx, op, B, o.d_z, o.d_chat, prm->gamma, o.d_tmp, o.d_x));
             if (lsqr_iters_out) for (int b = 0; b < B; ++b) lsqr_iters_out[(size_t)b * prm->iters + it] = 0;
@@ -354,7 +375,7 @@ static int pnp_admm_dev_impl(qmri_ctx* ctx, int nslices, const void* d_y, const 
             tm.stop(ctx->prof.ms_diag);
         }
         // Steps 2 and 3 (PnP_ADMM.m:115-144): the denoiser on v = real(x+uold), then uold = uold + x - v
-        if (!fused) QMRI_TRY(admm_denoiser_step(ctx, step, !llr, it));
+        if (!fused) QMRI_TRY(admm_denoiser_step(ctx, step, !reg, it));
         else {
             QMRI_TRY(admm_to_net(ctx, step, hb, true, true));
             tm.start();
@@ -398,7 +419,7 @@ static int pnp_admm_dev_impl(qmri_ctx* ctx, int nslices, const void* d_y, const 
         }
     }
     // f16 range guard: the network now runs on the bf16 scheme; the inputs are untouched (d_x_out must not alias d_x0), run again
-    if (prm->iters > 0 && !llr) QMRI_TRY(net_range_tripped(ctx, *repeat));
+    if (prm->iters > 0 && !reg) QMRI_TRY(net_range_tripped(ctx, *repeat));
     return QMRI_OK;
 }
 
@@ -436,7 +457,7 @@ extern "C" int qmri_pnp_admm_mc_dev(qmri_ctx* ctx, int nslices, int ncoil, const
     QMRI_TRY(mc_require(ctx, nslices, ncoil, d_maps, d_y));
     QMRI_TRY(mc_admm_check(ctx, prm));
     QMRI_CHECK_ARG(ctx, d_x_out && d_x_out != d_x0, "x_out must not be NULL and must not alias x0");
-    QMRI_CHECK_ARG(ctx, nslices <= ctx->op.maxB && (ctx->llr.on || nslices <= ctx->net.maxB), "nslices exceeds max_batch of the operator or the denoiser");
+    QMRI_CHECK_ARG(ctx, nslices <= ctx->op.maxB && (admm_regulariser_on(ctx) || nslices <= ctx->net.maxB), "nslices exceeds max_batch of the operator or the denoiser");
     QMRI_TRY(mc_admm_group(ctx, nslices, ncoil, (const double2*)d_maps, (const double2*)d_y, prm, (const double2*)d_x0, (double2*)d_x_out,
                            lsqr_iters_out, prm->iters));
     QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -452,7 +473,7 @@ extern "C" int qmri_pnp_admm_mc_batch(qmri_ctx* ctx, int nslices, int slices_per
     QMRI_CHECK_ARG(ctx, x_out && slices_per_launch >= 1, "x_out must not be NULL, slices_per_launch >= 1");
     OpHost& o = ctx->op;
     const int spl = std::min(slices_per_launch, nslices);
-    QMRI_CHECK_ARG(ctx, spl <= o.maxB && (ctx->llr.on || spl <= ctx->net.maxB), "slices_per_launch exceeds max_batch of the operator or the denoiser");
+    QMRI_CHECK_ARG(ctx, spl <= o.maxB && (admm_regulariser_on(ctx) || spl <= ctx->net.maxB), "slices_per_launch exceeds max_batch of the operator or the denoiser");
     const size_t plane = (size_t)o.N * o.M, n = plane * o.s;
     for (int b0 = 0; b0 < nslices; b0 += spl) {            // (the first run is the largest: the staging is sized once)
         const int B = std::min(spl, nslices - b0);
@@ -530,13 +551,13 @@ extern "C" int qmri_pnp_admm_batch(qmri_ctx* ctx, int nslices, int slices_per_la
     QMRI_HIP(ctx, hipSetDevice(ctx->device));
     OpHost& o = ctx->op;
     if (!o.ready) { qmri_set_error(ctx, "operator not set: call qmri_set_operator first"); return QMRI_ERR_STATE; }
-    if (!ctx->net.ready && !ctx->llr.on) { qmri_set_error(ctx, "denoiser not set: call qmri_set_denoiser first"); return QMRI_ERR_STATE; }
+    if (!ctx->net.ready && !admm_regulariser_on(ctx)) { qmri_set_error(ctx, "denoiser not set: call qmri_set_denoiser first"); return QMRI_ERR_STATE; }
     QMRI_CHECK_ARG(ctx, y && p && x_out && nslices >= 1 && slices_per_launch >= 1, "y / params / x_out must not be NULL, nslices and slices_per_launch >= 1");
     if (std::min(slices_per_launch, nslices) > 1)
         QMRI_TRY(nufft_check_gridded(ctx, "qmri_pnp_admm_batch with more than one slice per launch",
                                      "use slices_per_launch = 1, or qmri_pnp_admm_mc_batch with one unit coil per slice"));
     const int spl = std::min(slices_per_launch, nslices);
-    QMRI_CHECK_ARG(ctx, spl <= o.maxB && (ctx->llr.on || spl <= ctx->net.maxB), "slices_per_launch exceeds max_batch of the operator or the denoiser");
+    QMRI_CHECK_ARG(ctx, spl <= o.maxB && (admm_regulariser_on(ctx) || spl <= ctx->net.maxB), "slices_per_launch exceeds max_batch of the operator or the denoiser");
     const size_t n = (size_t)o.N * o.M * o.s, m = (size_t)o.m, it = (size_t)std::max(p->iters, 0);
     DevBuf<double2> dY, dX, dX0, dGT;
     auto fail = [&](const char* what) { qmri_set_error(ctx, "%s failed in qmri_pnp_admm_batch", what); return QMRI_ERR_HIP; };

@@ -90,6 +90,10 @@ extern "C" int qmri_set_llr(qmri_ctx* ctx, const qmri_llr_params* p) {
     }
     if (!ctx) { qmri_set_error(nullptr, "invalid argument: ctx must not be NULL"); return QMRI_ERR_INVALID_ARG; }
     if (!p) { ctx->llr = LlrState{}; return QMRI_OK; }
+    if (ctx->wav.on) {
+        qmri_set_error(ctx, "the wavelet regulariser is set: one regulariser at a time, clear it with qmri_set_wavelet(ctx, NULL) first");
+        return QMRI_ERR_STATE;
+    }
     ctx->llr.on = true;
     ctx->llr.tau = p->tau;
     ctx->llr.block = p->block ? p->block : 8;

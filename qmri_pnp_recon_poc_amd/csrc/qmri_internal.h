@@ -49,6 +49,8 @@ void qmri_set_error(qmri_ctx* ctx, const char* fmt, ...);
 #include "op_plan.h"
 // The denoiser's layer program, in plain C++ (net_plan.h): ConvKind, conv_cin_pad, the tensor ids (NetTensor), the steps and the resident-run candidates.
 #include "net_plan.h"
+// The joint wavelet soft-thresholding step's geometry, tiles, buffers and launch list, in plain C++ (wav_plan.h).
+#include "wav_plan.h"
 
 // ---------------------------------------------------------------------------------------------------
 // A/B and diagnostic switches ("knobs").  ONE environment variable, QMRI_DEBUG="name=value,name=value" (read once per process), and
@@ -335,6 +337,14 @@ int llr_prox_dev(qmri_ctx* ctx, const LlrPlan& pl, int B, const double2* d_x, co
 // uold += x - v; z = v - uold; pz [B][nblk_z] partial sums of ||z||^2 (n elements per slice)
 int llr_dual_dev(qmri_ctx* ctx, int B, size_t n, const double2* d_x, const double2* d_v, double2* d_u, double2* d_z, double* d_pz, int nblk_z);
 
+// joint wavelet soft-thresholding (wav_kernels.hip, api_wav.cpp, wav_plan.h).  All d_ pointers are device pointers; the
+// launches go to ctx->stream and are not waited for.  levels is 1 .. 4 here (the ABI's 0 is resolved by the caller).
+struct WavPlan { int N, M, s, levels, filter, joint, o1, o2, real; double tau; };
+struct WavState { bool on = false; double tau = 0.0; int levels = 3, filter = QMRI_WAVELET_DB2, joint = 1, shift = 0; };    // qmri_set_wavelet
+// d_out [B][s][M][N] = Wav_tau(d_x + d_u) (d_u NULL: of d_x; real: of the real part, imaginary part 0); d_out may be d_x.  d_cmax (nullable): [B]
+// the largest m of each slice before thresholding (one more small launch).  The scratch (wav_plan.h) is the context's and grows on first use.
+int wav_prox_dev(qmri_ctx* ctx, const WavPlan& pl, int B, const double2* d_x, const double2* d_u, double2* d_out, double* d_cmax);
+
 // ---------------------------------------------------------------------------------------------------
 // trajectory (NUFFT) operator (nufft_kernels.hip, api_nufft.cpp).  Planned once on the host per qmri_set_operator_nufft:
 // samples sorted by the 16 x 16 tile of the 2N x 2M oversampled grid that holds their position ("bins"), and for the output-driven spreading the
@@ -567,6 +577,9 @@ struct qmri_ctx {
     double last_call_wall_ms = 0;            // ... its host wall clock, entry to return (always)
     LlrState llr;                       // the regulariser of the PnP-ADMM loops' Step 2 while set (qmri_set_llr), else the network
     bool llr_lds_attr[3] = {false, false, false};   // large dynamic LDS allowed for k_llr_prox<4 | 8 | 16>
+    WavState wav;                       // ... or the joint wavelet soft-thresholding (qmri_set_wavelet); at most one of the two is on
+    DevArr<double2> wav_s[2];           // its two coefficient stacks (wav_plan.h scratch_elems), grown on first use
+    DevArr<double> wav_part, wav_cmax;  // the shrink launch's per-workgroup maxima; the slices' maxima when asked for
     int ncu = 0;                        // CU count of the device (qmri_create)
     int conv_occ[4][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};   // f32-MFMA conv kernels (conv_kernels.hip): resident workgroups per CU by (kind, MT)
 };

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import AdmmParams, CcParams, CsmInfo, CsmParams, DcfInfo, DcfParams, DsvdInfo, DsvdParams, EpgParams, EpgProfile, FieldmapInfo, FieldmapParams, LlrParams, LrtvInfo, LrtvParams, NetDesc, NufftParams, OffresInfo, OffresNormalInfo, OffresNormalParams, OffresParams, Profile
+from ._lib import AdmmParams, CcParams, CsmInfo, CsmParams, DcfInfo, DcfParams, DsvdInfo, DsvdParams, EpgParams, EpgProfile, FieldmapInfo, FieldmapParams, LlrParams, LrtvInfo, LrtvParams, NetDesc, NufftParams, OffresInfo, OffresNormalInfo, OffresNormalParams, OffresParams, Profile, WAVELET_FILTERS, WaveletParams
 
 ARCH_UNETRES, ARCH_SEQ_CONV = 0, 1
 SOLVER_LSQR, SOLVER_DIRECT = 0, 1
@@ -902,6 +902,58 @@ class Engine:
 
     def clear_llr(self):
         self._check(self.L.qmri_set_llr(self.h, None))
+
+    # -- joint wavelet soft-thresholding ---------------------------------------
+    @staticmethod
+    def _wavelet_params(tau, levels, filter, joint, shift):
+        if isinstance(filter, str):
+            if filter not in WAVELET_FILTERS:
+                raise ValueError(f'filter must be one of {sorted(WAVELET_FILTERS)}, not {filter!r}')
+            filter = WAVELET_FILTERS[filter]
+        return WaveletParams(float(tau), int(levels), int(filter), int(bool(joint)), int(bool(shift)))
+
+    def wavelet_prox(self, x, tau, levels=3, filter="db2", joint=True, offset=(0, 0), real=False):
+        """Joint wavelet soft-thresholding (qmri_wavelet_prox): the detail coefficients of a `levels`-level periodic orthogonal wavelet transform
+        ("haar" or "db2") of every channel plane are shrunk by tau, jointly over the channels (joint) or each on its own.  x: [N, M, s] or a
+        stack [S, N, M, s], N and M multiples of 2^levels, s <= 16; offset = (o1, o2) < 2^levels shifts the transform (cycle spinning); real:
+        work on real(x).  Needs no operator.  Returns (out complex128 like x, cmax: a float, or [S] for a stack)."""
+        x = np.asarray(x)
+        one = x.ndim == 3
+        xs = x[None] if one else x
+        if xs.ndim != 4:
+            raise ValueError("x must be [N, M, s] or [slices, N, M, s]")
+        S, N, M, s = xs.shape
+        p = self._wavelet_params(tau, levels, filter, joint, False)
+        if real:
+            xb = np.concatenate([np.ascontiguousarray(np.asarray(xs[b].real, np.float64).ravel(order="F")) for b in range(S)])
+        else:
+            xb = np.concatenate([_cbuf(xs[b]) for b in range(S)])
+        out = np.empty(S * N * M * s, np.complex128)
+        cm = np.zeros(S, np.float64)
+        self._check(self.L.qmri_wavelet_prox(self.h, N, M, s, S, _vp(xb), 0 if real else 1, C.byref(p), int(offset[0]), int(offset[1]), _vp(out),
+                                             cm.ctypes.data_as(C.POINTER(C.c_double))))
+        n = N * M * s
+        out = np.stack([out[b * n:(b + 1) * n].reshape((N, M, s), order="F") for b in range(S)])
+        return (out[0], float(cm[0])) if one else (out, cm)
+
+    def wavelet_prox_dev(self, d_x: int, dims, tau, d_out: int, levels=3, filter="db2", joint=True, offset=(0, 0), real=False, want_cmax=True):
+        """qmri_wavelet_prox_dev on device arrays (complex fp64, [slice][c][n2][n1]); dims = (N, M, s, slices); d_out may be d_x.  Returns cmax [slices]."""
+        N, M, s, S = (int(v) for v in dims)
+        p = self._wavelet_params(tau, levels, filter, joint, False)
+        cm = np.zeros(S, np.float64)
+        self._check(self.L.qmri_wavelet_prox_dev(self.h, N, M, s, S, C.c_void_p(d_x), 0 if real else 1, C.byref(p), int(offset[0]), int(offset[1]),
+                                                 C.c_void_p(d_out), cm.ctypes.data_as(C.POINTER(C.c_double)) if want_cmax else None))
+        return cm
+
+    def set_wavelet(self, tau, levels=3, filter="db2", joint=True, shift=True):
+        """Step 2 of every pnp_admm* call of this engine becomes v = Wav_tau(x + uold) (qmri_set_wavelet) until clear_wavelet: no denoiser is
+        needed.  tsmi_domain="complex" thresholds the complex x + uold, "real" its real part.  shift: the offsets cycle with the iteration.
+        Refused while the LLR step is set (one regulariser at a time)."""
+        p = self._wavelet_params(tau, levels, filter, joint, shift)
+        self._check(self.L.qmri_set_wavelet(self.h, C.byref(p)))
+
+    def clear_wavelet(self):
+        self._check(self.L.qmri_set_wavelet(self.h, None))
 
     # -- PnP-ADMM ------------------------------------------------------------------------------------
     def pnp_admm(self, y, gamma=0.05, iters=100, cg_tol=1e-4, cg_maxit=100, solver="lsqr", multi_level=False,

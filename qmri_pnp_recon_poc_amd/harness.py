@@ -339,7 +339,8 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
                 denoiser_type="single_level", noise_map_std=0.01, residual_noise=False, iters=100, seed=0, Y=None, device=0,
                 net_arch=None, lrtv_iters=None, tsmi_domain="real", solver="lsqr", b1_map=None, density_compensation=False,
                 field_map=None, readout_s=None, field_normal=None, field_echoes=None, field_echo_times=None,
-                regulariser="net", llr_tau=None, llr_tau_rel=0.02, llr_block=8, components=None, unmix_mode="real", b1_window=4):
+                regulariser="net", llr_tau=None, llr_tau_rel=0.02, llr_block=8, wavelet_tau=None, wavelet_tau_rel=None,
+                wavelet_levels=3, wavelet_filter="db2", components=None, unmix_mode="real", b1_window=4):
     """main_recon_tsmis_FFT.m:216-374 on already loaded (and cropped) arrays.
 
     dictionary  dict(V, D, normD, lut) (load_dictionary);  X0  N x M x s ground-truth TSMI;  qmap0  N x M x 3
@@ -367,6 +368,9 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
     regulariser   of PnP_ADMM: "net" (default) is the denoiser of `weights`; "llr" the locally low-rank proximal step, which
                 needs no weights and works on every subsampling pattern: llr_block x llr_block patches (4, 8 or 16, dividing N and M), threshold
                 llr_tau, or with None llr_tau_rel times sigma_max of the start image.  The result gains llr_tau, the threshold used.
+                "wavelet": joint wavelet soft-thresholding, which needs no weights either and works on every subsampling
+                pattern: wavelet_levels (1..4, 2^levels dividing N and M) of wavelet_filter ("haar" or "db2"), threshold wavelet_tau, or with
+                None wavelet_tau_rel (None: reference_api.WAVELET_TAU_REL) times cmax of the start image.  The result gains wavelet_tau.
     components  tissue-fraction maps after the match: 1..8 (T1, T2) pairs in the units of dict.lut (each stands for the
                 nearest atom) or 1-based atom indices; every pixel of the reconstructed TSMI is written as a non-negative mix of those atoms
                 (unmix_mode "real": of its real part, "phase": after removing the pixel's phase).  The result gains fractions (N x M x C),
@@ -376,10 +380,10 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
     """
     from . import reference_api as R
     net_arch = dict(net_arch or {})
-    if regulariser not in ("net", "llr"):
-        raise ValueError(f'regulariser must be "net" or "llr", not {regulariser!r}')
-    if regulariser == "llr" and recon_method != "PnP_ADMM":
-        raise ValueError('regulariser="llr" goes with recon_method="PnP_ADMM"')
+    if regulariser not in ("net", "llr", "wavelet"):
+        raise ValueError(f'regulariser must be "net", "llr" or "wavelet", not {regulariser!r}')
+    if regulariser != "net" and recon_method != "PnP_ADMM":
+        raise ValueError(f'regulariser="{regulariser}" goes with recon_method="PnP_ADMM"')
     from .engine import denoiser_type as _dtype
     _dtype(denoiser_type == "multi_level", tsmi_domain)            # (checks tsmi_domain)
     X0 = np.asarray(X0)
@@ -449,10 +453,10 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
         Yc = np.asarray(Y, dtype=np.complex128)
         X = F._engine.adjoint(Yc, weighted=True) if density_compensation else F.adjoint(Yc)
     elif recon_method == "PnP_ADMM":                                                 # :284-293
-        if weights is None and regulariser != "llr":
+        if weights is None and regulariser == "net":
             raise ValueError("PnP_ADMM needs the denoiser weights")
         arch = {}
-        if regulariser == "llr":
+        if regulariser != "net":
             pass
         elif isinstance(weights, (str, bytes)) or hasattr(weights, "__fspath__"):
             from .weights import load_denoiser_weights
@@ -464,6 +468,9 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
         out_nc = 2 * s if tsmi_domain == "complex" else s
         if regulariser == "llr":
             net = R.make_llr(F, tau=llr_tau, tau_rel=llr_tau_rel, block=llr_block)
+        elif regulariser == "wavelet":
+            net = R.make_wavelet(F, tau=wavelet_tau, tau_rel=R.WAVELET_TAU_REL if wavelet_tau_rel is None else wavelet_tau_rel,
+                                 levels=wavelet_levels, filter=wavelet_filter)
         else:
             net = R.make_net(weights, denoiser_type, residual_noise, H=N, W=M, out_nc=out_nc, device=device, tsmi_domain=tsmi_domain,
                              **{**net_arch, **({"nc": arch["nc"], "nb": arch["nb"]} if arch else {})})
@@ -479,6 +486,8 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
             extra_fn = {"field_normal_info": R.PnP_ADMM.last_field_normal}
         if regulariser == "llr":
             extra_fn["llr_tau"] = net.tau
+        if regulariser == "wavelet":
+            extra_fn["wavelet_tau"] = net.tau
     elif recon_method == "LRTV":                                                     # :273-282
         param = {"K": 4e-5, "iter": 200 if lrtv_iters is None else int(lrtv_iters), "step": X0.size / np.asarray(Y).size, "tol": 1e-4,
                  "backtrack": 1, "usegpu": 0}

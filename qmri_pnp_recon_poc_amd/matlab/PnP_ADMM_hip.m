@@ -3,7 +3,8 @@ function [x, diag, lsqr_iters, llr_tau] = PnP_ADMM_hip(y, param)
 %   loop on the GPU (one boundary crossing per reconstruction).  param.F must come from qmri_make_F and param.net from
 %   qmri_make_net; the fields read are the reference's own: iter, gamma, cg_tol, gt_tsmi, X0, denoiser_type, noise_map
 %   (PnP_ADMM.m:62-76); param.net may instead be the struct of qmri_make_llr (the locally low-rank regulariser, DESIGN.md section 25: no network,
-%   denoiser_type and noise_map are not read; the threshold used is the fourth output), and param.tsmi_domain ('real', the default and the reference's; 'complex': the denoiser sees
+%   denoiser_type and noise_map are not read; the threshold used is the fourth output) or of qmri_make_wavelet (joint wavelet soft-thresholding,
+%   DESIGN.md section 29: the same conventions, the same fourth output), and param.tsmi_domain ('real', the default and the reference's; 'complex': the denoiser sees
 %   cat(3, real(x+u), imag(x+u)) and param.net must take 2s (+1) -> 2s channels), and param.solver ('lsqr', the default; 'direct'; 'toeplitz' on a
 %   trajectory F: CG on the Toeplitz normal operator, DESIGN.md section 16), and param.field_normal (with a field map and solver 'toeplitz': true, or a
 %   struct with nseg and / or tol, builds the field-aware normal operator before the loop, as qmri_prepare_normal_fm does).  Extra outputs: the two per-iteration diagnostics (PnP_ADMM.m:106-109) and the LSQR iteration counts.
@@ -15,7 +16,8 @@ function [x, diag, lsqr_iters, llr_tau] = PnP_ADMM_hip(y, param)
 if ~isfield(param.F, 'qmri'), error('qmri:F', 'param.F must be created by qmri_make_F'); end
 p.gamma = param.gamma;  p.iter = param.iter;  p.cg_tol = param.cg_tol;
 llr = isstruct(param.net) && isfield(param.net, 'qmri_llr');
-p.multi_level = double(~llr && strcmp(param.denoiser_type, 'multi_level'));
+wav = isstruct(param.net) && isfield(param.net, 'qmri_wavelet');
+p.multi_level = double(~llr && ~wav && strcmp(param.denoiser_type, 'multi_level'));
 if p.multi_level, p.noise_std = param.noise_map(1); else, p.noise_std = 0.01; end
 tsmi_domain = 'real';  if isfield(param, 'tsmi_domain'), tsmi_domain = char(param.tsmi_domain); end
 if ~any(strcmp(tsmi_domain, {'real', 'complex'})), error('qmri:tsmi_domain', 'param.tsmi_domain must be ''real'' or ''complex'''); end
@@ -58,6 +60,18 @@ if llr                                                     % Step 2 = the locall
     end
     qmri_mex('set_llr', llr_tau, param.net.block, param.net.shift);
     unset = onCleanup(@() qmri_mex('clear_llr'));
+end
+if wav                                                     % Step 2 = joint wavelet soft-thresholding: threshold from the start image unless given
+    w = param.net;
+    llr_tau = w.tau;
+    if isempty(llr_tau)
+        start = X0;  if isempty(start), start = complex(double(param.F.adjoint(y(:, 1)))); end
+        if ~p.complex_tsmi, start = real(start); end
+        [~, cmax] = qmri_mex('wavelet_prox', start, 0, w.levels, w.filter, w.joint);
+        llr_tau = w.tau_rel * max(cmax);
+    end
+    qmri_mex('set_wavelet', llr_tau, w.levels, w.filter, w.joint, w.shift);
+    unset = onCleanup(@() qmri_mex('clear_wavelet'));
 end
 if nargout > 1
     [x, diag, lsqr_iters] = qmri_mex('pnp_admm', complex(double(y)), p, X0, gt, [g.N g.M g.s]);

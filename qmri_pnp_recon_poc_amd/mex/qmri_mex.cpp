@@ -35,6 +35,8 @@
 //   * 'dict_simulate_sp' is 'dict_simulate' integrated over a slice profile (qmri_dict_simulate_sp; extension); it needs no plan.
 //   * 'set_llr' / 'clear_llr' select the locally low-rank proximal step as Step 2 of 'pnp_admm' (qmri_set_llr; extension), which
 //     then needs no denoiser; 'llr_prox' is the step alone (qmri_llr_prox).
+//   * 'set_wavelet' / 'clear_wavelet' select joint wavelet soft-thresholding as Step 2 of 'pnp_admm' the same way (qmri_set_wavelet; extension,
+//     DESIGN.md section 29); 'wavelet_prox' is the step alone (qmri_wavelet_prox).  One of the two regularisers at a time.
 //   * 'field_map_estimate' estimates the field map that 'set_field_map' takes from multi-echo images (qmri_field_map_estimate; extension, DESIGN.md
 //     section 24); it needs no plan.
 // tests/cpp/mex_mock.cpp is a small stand-in for the MATLAB runtime's C API under which this file is compiled, LINKED against libqmri.so and
@@ -63,6 +65,7 @@ static DictSpec g_dict;
 static std::vector<int32_t> g_comp;                    // 'set_components' in force (1-based atoms); 'set_dictionary' drops them
 static int g_ngroups = 0;                              // 'set_dictionary_groups' in force (G); 'set_dictionary' and a device switch drop them
 static bool g_llr = false;                             // 'set_llr' is in force: 'pnp_admm' needs no denoiser
+static bool g_wav = false;                             // 'set_wavelet' is in force: the same
 static const int DEFAULT_SLICES_PER_LAUNCH = 15;       // what a measurement matrix grows the plans to (the batched kernels' design point)
 
 static void drop(mxArray*& a) { if (a) { mxDestroyArray(a); a = nullptr; } }
@@ -76,6 +79,7 @@ static void cleanup() {
     g_comp.clear();
     g_ngroups = 0;
     g_llr = false;
+    g_wav = false;
 }
 
 static void check(int st) {
@@ -508,6 +512,55 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         check(qmri_llr_prox(ctx(), (int)N, (int)M, (int)s, (int)S, cpx ? (const void*)mxGetComplexDoubles(prhs[1]) : (const void*)mxGetDoubles(prhs[1]), cpx ? 1 : 0,
                             &lp, o1, o2, mxGetComplexDoubles(plhs[0]), mxGetDoubles(sm)));
         if (nlhs > 1) plhs[1] = sm; else mxDestroyArray(sm);
+    } else if (c == "set_wavelet") {                 // qmri_mex('set_wavelet', tau [, levels [, filter [, joint [, shift]]]]): Step 2 of 'pnp_admm' becomes the wavelet prox
+        // extension (no reference counterpart; qmri_set_wavelet): tau >= 0 in the units of the TSMI, levels 1 .. 4 (default 3),
+        // filter 0 Haar or 1 Daubechies-2 (default), joint 1 (default): the s channels are thresholded together, shift 1 (default): the offsets cycle
+        // with the ADMM iteration.  No denoiser is needed while it is set; refused (qmri:state) while 'set_llr' is in force.
+        need(nrhs, 2, "qmri_mex('set_wavelet', tau [, levels, filter, joint, shift])");
+        want(mxIsDouble(prhs[1]) && !mxIsComplex(prhs[1]) && mxGetNumberOfElements(prhs[1]) == 1, "qmri:set_wavelet:tau", "tau must be a real double scalar");
+        qmri_wavelet_params wp{};
+        wp.tau = mxGetScalar(prhs[1]);
+        want(std::isfinite(wp.tau) && wp.tau >= 0.0, "qmri:set_wavelet:tau", "tau must be finite and >= 0");
+        wp.levels = nrhs > 2 ? int_arg(prhs[2], 1, 4, "qmri:set_wavelet:levels", "levels must be 1, 2, 3 or 4") : 3;
+        wp.filter = nrhs > 3 ? int_arg(prhs[3], 0, 1, "qmri:set_wavelet:filter", "filter must be 0 (Haar) or 1 (Daubechies-2)") : QMRI_WAVELET_DB2;
+        wp.joint = nrhs > 4 ? int_arg(prhs[4], 0, 1, "qmri:set_wavelet:joint", "joint must be 0 or 1") : 1;
+        wp.shift = nrhs > 5 ? int_arg(prhs[5], 0, 1, "qmri:set_wavelet:shift", "shift must be 0 or 1") : 1;
+        check(qmri_set_wavelet(ctx(), &wp));
+        g_wav = true;
+    } else if (c == "clear_wavelet") {               // qmri_mex('clear_wavelet'): Step 2 of 'pnp_admm' is the network again
+        check(qmri_set_wavelet(ctx(), nullptr));
+        g_wav = false;
+    } else if (c == "wavelet_prox") {                // [out, cmax] = qmri_mex('wavelet_prox', x, tau [, levels [, filter [, joint [, o1, o2]]]])
+        // joint wavelet soft-thresholding alone (qmri_wavelet_prox).  x: double N x M x s (x S), complex, or real (real mode: the output's imaginary
+        // part is exactly 0); N and M multiples of 2^levels, s <= 16.  out: complex like x; cmax: 1 x S, the largest m of each slice's detail positions.
+        const char* usage = "[out, cmax] = qmri_mex('wavelet_prox', x, tau [, levels, filter, joint, o1, o2])";
+        need(nrhs, 3, usage);
+        want(nlhs <= 2 && nrhs != 7 && nrhs <= 8, "qmri:usage", usage);
+        want(mxIsDouble(prhs[1]), "qmri:wavelet_prox:type", "x must be a double array (complex, or real for real mode)");
+        want(mxIsDouble(prhs[2]) && !mxIsComplex(prhs[2]) && mxGetNumberOfElements(prhs[2]) == 1, "qmri:wavelet_prox:tau", "tau must be a real double scalar");
+        qmri_wavelet_params wp{};
+        wp.tau = mxGetScalar(prhs[2]);
+        want(std::isfinite(wp.tau) && wp.tau >= 0.0, "qmri:wavelet_prox:tau", "tau must be finite and >= 0");
+        wp.levels = nrhs > 3 ? int_arg(prhs[3], 1, 4, "qmri:wavelet_prox:levels", "levels must be 1, 2, 3 or 4") : 3;
+        wp.filter = nrhs > 4 ? int_arg(prhs[4], 0, 1, "qmri:wavelet_prox:filter", "filter must be 0 (Haar) or 1 (Daubechies-2)") : QMRI_WAVELET_DB2;
+        wp.joint = nrhs > 5 ? int_arg(prhs[5], 0, 1, "qmri:wavelet_prox:joint", "joint must be 0 or 1") : 1;
+        const int P = 1 << wp.levels, T = wp.filter == QMRI_WAVELET_HAAR ? 2 : 4;
+        const int o1 = nrhs > 7 ? int_arg(prhs[6], 0, P - 1, "qmri:wavelet_prox:offset", "o1 and o2 must be integers in 0 .. 2^levels - 1") : 0;
+        const int o2 = nrhs > 7 ? int_arg(prhs[7], 0, P - 1, "qmri:wavelet_prox:offset", "o1 and o2 must be integers in 0 .. 2^levels - 1") : 0;
+        const size_t nd = mxGetNumberOfDimensions(prhs[1]);
+        const mwSize* xd = mxGetDimensions(prhs[1]);
+        want(nd >= 2 && nd <= 4, "qmri:wavelet_prox:size", "x must be N x M x s or N x M x s x S");
+        const size_t N = xd[0], M = xd[1], s = nd > 2 ? xd[2] : 1, S = nd > 3 ? xd[3] : 1;
+        want(N >= 1 && M >= 1 && N <= 16384 && M <= 16384 && N % P == 0 && M % P == 0 && (N >> (wp.levels - 1)) >= (size_t)T && (M >> (wp.levels - 1)) >= (size_t)T,
+             "qmri:wavelet_prox:size", "N and M must be multiples of 2^levels, and N / 2^(levels-1) and M / 2^(levels-1) at least the filter length");
+        want(s >= 1 && s <= 16 && S >= 1 && S <= 65536, "qmri:wavelet_prox:size", "x must hold 1 <= s <= 16 channels and at least one slice");
+        const mwSize od[4] = {(mwSize)N, (mwSize)M, (mwSize)s, (mwSize)S};
+        plhs[0] = mxCreateNumericArray(S > 1 ? 4 : 3, od, mxDOUBLE_CLASS, mxCOMPLEX);
+        mxArray* cm = mxCreateDoubleMatrix(1, (mwSize)S, mxREAL);
+        const bool cpx = mxIsComplex(prhs[1]);
+        check(qmri_wavelet_prox(ctx(), (int)N, (int)M, (int)s, (int)S, cpx ? (const void*)mxGetComplexDoubles(prhs[1]) : (const void*)mxGetDoubles(prhs[1]),
+                                cpx ? 1 : 0, &wp, o1, o2, mxGetComplexDoubles(plhs[0]), mxGetDoubles(cm)));
+        if (nlhs > 1) plhs[1] = cm; else mxDestroyArray(cm);
     } else if (c == "prepare_normal_fm") {           // info = qmri_mex('prepare_normal_fm' [, nseg [, tol]]): the Toeplitz normal operator of the attached map
         const qmri_offres_normal_params np = normal_fm_params(nrhs > 1 ? prhs[1] : nullptr, nrhs > 2 ? prhs[2] : nullptr, "qmri:prepare_normal_fm:nseg",
                                                               "qmri:prepare_normal_fm:tol");     // (the argument checks come first: they need no operator)
@@ -579,7 +632,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         const double* d = mxGetDoubles(prhs[5]);
         const size_t S = mxGetN(prhs[1]), m = mxGetM(prhs[1]), n = dims_numel(prhs[5]);
         want(is_cdouble(prhs[1]) && S >= 1 && m == operator_m(), "qmri:pnp_admm:size", "y must be complex double, one column of m samples per slice");
-        want(g_net.w != nullptr || g_llr, "qmri:state", "no denoiser: call qmri_mex('set_denoiser' | 'load_onnx', ...) (qmri_make_net) or qmri_mex('set_llr', ...) (qmri_make_llr) first");
+        want(g_net.w != nullptr || g_llr || g_wav, "qmri:state", "no denoiser: call qmri_mex('set_denoiser' | 'load_onnx', ...) (qmri_make_net), qmri_mex('set_llr', ...) (qmri_make_llr) or qmri_mex('set_wavelet', ...) (qmri_make_wavelet) first");
         want((mxIsEmpty(prhs[3]) || is_cdouble(prhs[3])) && (mxIsEmpty(prhs[4]) || is_cdouble(prhs[4])), "qmri:pnp_admm:type", "X0 and gt_tsmi must be complex double or empty");
         const int it = p.iters > 0 ? p.iters : 1;
         const mwSize dims[4] = {(mwSize)d[0], (mwSize)d[1], (mwSize)d[2], (mwSize)S};

@@ -8,6 +8,7 @@ pipeline, so this Python mirror is the executable counterpart of the `.m` wrappe
     F   = make_F(P)                                         # F.forward / F.adjoint, main_recon_tsmis_FFT.m:228-229
     net = make_net(weights, denoiser_type, residual_noise)  # param.net, main_recon_tsmis_FFT.m:164
     net = make_llr(F, tau, tau_rel, block, shift)           # param.net without a network: the locally low-rank regulariser
+    net = make_wavelet(F, tau, tau_rel, levels, filter, joint, shift)   # ... or joint wavelet soft-thresholding
     x   = PnP_ADMM(y, param)                                # PnP_ADMM.m:1, param = dict with the reference's field names
     out = mrf_dtm_cpu(dict, data, par)                      # mrf_dtm_cpu.m:1 (name kept; it runs on the GPU)
     x   = FISTA_deep(data, param)                           # LRTV option, FISTA_deep.m:1 (+ TV_operator, prox_tv, norm_tv)
@@ -166,6 +167,40 @@ def _llr_arm(F, net, param, y, x0, tsmi_domain):
     eng.set_llr(net.tau, block=net.block, shift=net.shift)
 
 
+WAVELET_TAU_REL = 0.05      # of cmax of the start image: the choice of DESIGN.md section 29 (tests/test_gpu_wavelet.py::test_it_regularises)
+
+
+def make_wavelet(F, tau=None, tau_rel=WAVELET_TAU_REL, levels=3, filter="db2", joint=True, shift=True):
+    """param.net without a network (an extension): Step 2 of PnP_ADMM becomes joint wavelet soft-thresholding
+    v = Wav_tau(x + uold) (Engine.set_wavelet), which needs no trained weights and fits every operator of make_F.  tau: the threshold on the
+    detail coefficients in the units of the TSMI; None: tau_rel times cmax of the loop's start image (Engine.wavelet_prox with tau = 0 gives
+    cmax).  levels 1..4, filter "haar" or "db2", joint: the s channels are thresholded together; shift: the offsets cycle with the iteration.
+    The threshold a PnP_ADMM call used is .tau afterwards."""
+    if not hasattr(F, "_engine"):
+        raise TypeError("F must come from make_F of this package")
+    if levels not in (1, 2, 3, 4):
+        raise ValueError("levels must be 1, 2, 3 or 4")
+    if filter not in E.WAVELET_FILTERS:
+        raise ValueError(f'filter must be one of {sorted(E.WAVELET_FILTERS)}, not {filter!r}')
+    if tau is not None and not (float(tau) >= 0 and np.isfinite(tau)):
+        raise ValueError("tau must be finite and >= 0")
+    if tau is None and not (float(tau_rel) >= 0 and np.isfinite(tau_rel)):
+        raise ValueError("tau_rel must be finite and >= 0")
+    return SimpleNamespace(_engine=F._engine, _wavelet=True, _denoiser_type="single_level", _tsmi_domain="real", _residual_noise=False,
+                           tau=None if tau is None else float(tau), tau_given=None if tau is None else float(tau), tau_rel=float(tau_rel),
+                           levels=int(levels), filter=filter, joint=bool(joint), shift=bool(shift), cmax=None)
+
+
+def _wavelet_arm(F, net, param, y, x0, tsmi_domain):
+    """Sets the engine's wavelet step for one PnP_ADMM call; the threshold comes from the start image unless the caller gave one."""
+    eng = F._engine
+    if net.tau_given is None:
+        start = x0 if x0 is not None else F.adjoint(y)
+        _, net.cmax = eng.wavelet_prox(start, 0.0, levels=net.levels, filter=net.filter, joint=net.joint, real=tsmi_domain != "complex")
+        net.tau = net.tau_rel * net.cmax
+    eng.set_wavelet(net.tau, levels=net.levels, filter=net.filter, joint=net.joint, shift=net.shift)
+
+
 def build_noise_map(noise_std, rows, cols):
     """noise_map = repmat(noise_std, rows, cols)  (build_noise_map.m:19)."""
     return np.full((rows, cols), float(noise_std))
@@ -185,13 +220,16 @@ def PnP_ADMM(y, param):
         raise TypeError("param.F and param.net must come from make_F / make_net of this package (same device)")
     PnP_ADMM.last_field_normal = _field_normal(F, param.get("field_normal"))
     llr = getattr(net, "_llr", False)                               # (make_llr: Step 2 is the locally low-rank prox)
-    multi = param.get("denoiser_type", net._denoiser_type) == "multi_level" and not llr
+    wavelet = getattr(net, "_wavelet", False)                       # (make_wavelet: joint wavelet soft-thresholding)
+    multi = param.get("denoiser_type", net._denoiser_type) == "multi_level" and not llr and not wavelet
     noise_std = float(np.asarray(param["noise_map"]).ravel()[0]) if multi else 0.01
     traj = getattr(F._P, "omega", None) is not None                 # (a trajectory computes no per-iteration diagnostics: last_diagnostics is None)
     tsmi_domain = param.get("tsmi_domain", getattr(net, "_tsmi_domain", "real"))
     x0 = _dcf_x0(F, param, y)
     if llr:
         _llr_arm(F, net, param, y, x0, tsmi_domain)
+    if wavelet:
+        _wavelet_arm(F, net, param, y, x0, tsmi_domain)
     try:
         x, diag, li = F._engine.pnp_admm(y, gamma=param["gamma"], iters=int(param["iter"]), cg_tol=param["cg_tol"], cg_maxit=100,
                                          solver=param.get("solver", "lsqr"), multi_level=multi, noise_std=noise_std,
@@ -201,6 +239,8 @@ def PnP_ADMM(y, param):
     finally:
         if llr:
             F._engine.clear_llr()
+        if wavelet:
+            F._engine.clear_wavelet()
     PnP_ADMM.last_diagnostics, PnP_ADMM.last_lsqr_iters = diag, li
     return x
 
