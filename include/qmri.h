@@ -503,6 +503,61 @@ int qmri_dict_unmix(qmri_ctx* ctx, const void* X, int Npix, int mode, double* w,
 /* The same on device arrays, asynchronous on ctx's stream.  d_X as for qmri_dict_match_dev. */
 int qmri_dict_unmix_dev(qmri_ctx* ctx, const void* d_X, int Npix, int mode, double* d_w, double* d_frac, double* d_pd, double* d_res, int32_t* d_flags);
 
+/* ---- sub-grid refinement: matched T1 / T2 moved off the dictionary's grid by a fit through neighbouring atoms (an EXTENSION,
+ *      no reference counterpart, parity unpinned) -------------------------------------------------------------------------
+ * Every match above returns lut[dm]: maps quantised to the dictionary's grid.  The dictionary samples the signal manifold; a quadratic through the
+ * matched atom and its neighbours along each parameter axis is a local model of it, and fitting the pixel to that model is a least-squares problem
+ * in 1 to 3 unknowns per pixel in the compressed space.  It needs no sequence knowledge and works for any gridded narrow dictionary (s <= 16).
+ * tests/refine_ref.py states the fit in numpy, operation for operation, and is the definition; this is its summary.
+ * Lines.  P in 1..3 lut columns cols[q] (0-based, distinct, < Q) are refined.  Atoms a, b are on one line of column c when every OTHER lut column
+ *   compares equal.  nbr [K][P][2] int32, 0-based, -1 = none: nbr[k][q][1] is the atom on k's line with the smallest lut[., c] greater than lut[k, c]
+ *   (the lowest index among equal values), nbr[k][q][0] mirrors it (the largest value smaller than lut[k, c]).  An atom with a non-finite lut entry,
+ *   or a zero or non-finite normD, has no neighbours and is nobody's neighbour.  With lut = (T1, T2, b1) and cols = {0, 1} a line never leaves a b1
+ *   group.  qmri_dict_lines is that rule on the host, without a context or a device: lut K x Q floats column-major and normD as
+ *   qmri_set_dictionary takes them; info [P][3] int32 = atoms with 0, 1 and 2 neighbours per column.  QMRI_ERR_INVALID_ARG: a NULL array, K < 1,
+ *   Q < 1, P outside 1..3, a column repeated or out of range, a column in which no atom has a neighbour ("lut column c has no lines").
+ * Model, all in fp64.  a_k = double(normD[k]) * double(D[k, :]), the unnormalised atom.  Per pixel, centre atom k, per column q with neighbours a+, a-:
+ *   both: g_q = (a+ - a-) / 2, h_q = (a+ + a-) / 2 - a0, box [-1, 1];  only a+: g_q = a+ - a0, h_q = 0, box [0, 1];  only a-: g_q = a0 - a-, h_q = 0,
+ *   box [-1, 0];  none: t_q fixed at 0.  d(t) = a0 + sum_q (t_q g_q + t_q^2 h_q); the parameter theta_q(t_q) is the same polynomial through the lut
+ *   values, so non-uniform (logarithmic) grids need no special case.
+ * Fit.  f(t) = ||x - rho d(t)||^2 with rho = (d . x) / (d . d), evaluated as this residual norm.  Variable-projection Gauss-Newton from t = 0:
+ *   J_q = g_q + 2 t_q h_q, H = |rho|^2 (J^T J - (J^T d)(d^T J) / (d . d)) + 1e-12 trace(H) I, gvec = Re(conj(rho) (P_perp J)^T r), r = x - rho d;
+ *   Cholesky; the step clipped to the box; a coordinate is pinned for a step when it has no neighbour, when J_q is collinear with d
+ *   (|P_perp J_q|^2 <= 1e-12 |J_q|^2) or when it sits on a bound and gvec_q points outside.  Converged when the clipped step is <= 1e-10 in every
+ *   coordinate.  Otherwise backtracking alpha = 1, 1/2 .. 2^-10, the first alpha with f_new <= f taken; none: the fit ends, with the STALLED flag
+ *   when the refused step was larger than 1e-6 (a smaller one is the resolution of f in fp64, not a failure).  More than 30 steps: the CAP flag.
+ * Re-centring.  After a fit, the first column q (ascending) with t_q = +-1 whose neighbour in that direction has a further neighbour in that
+ *   direction: that neighbour becomes the centre and the fit restarts from t = 0; at most 4 moves; the last centre's result is returned.
+ * X: Npix x s complex doubles, column-major, as in qmri_dict_match.  dm: Npix int32, the 1-based start atom from ANY match (plain or grouped); a
+ *   value outside 1..K (0 = unmatched) skips the pixel: every output 0, flag SKIPPED.  Outputs, column-major, every one nullable: qmap Npix x Q fp64
+ *   (refined columns theta_q(t), the others the last centre's lut value, NaN -> 0 as in the match);  pd Npix complex doubles = rho (the match's
+ *   convention: x ~ pd * unnormalised atom);  res Npix = sqrt(f / ||x||^2);  t Npix x P;  centre Npix int32, 1-based;  flags Npix int32.
+ *   DEGENERATE: ||x||^2 or d(0) . d(0) zero or not finite; the pixel gets the centre's grid values, t = 0, pd = 0, res = 0.
+ *   A pixel's bits depend on nothing but that pixel: not on Npix, the other pixels or their order.
+ * Not built: wide dictionaries (s > 16), cross terms t_q t_r in the model, refinement inside the qmri_recon_batch* workers (qmri_problem is frozen),
+ *   a sub-grid B1 inside qmri_b1_estimate, uncertainty maps from H^-1. */
+enum { QMRI_RF_FLAG_SKIPPED = 1, QMRI_RF_FLAG_MOVED = 2, QMRI_RF_FLAG_BOUND = 4, QMRI_RF_FLAG_CAP = 8, QMRI_RF_FLAG_STALLED = 16, QMRI_RF_FLAG_DEGENERATE = 32 };
+typedef struct {
+    int32_t P, K, s;         /* refined columns, atoms and channels in force */
+    int32_t reserved;
+    int32_t count[3][3];     /* per refined column: atoms with 0, 1 and 2 neighbours */
+    int32_t reserved2[3];
+} qmri_refine_info;
+int qmri_dict_lines(int K, int Q, const float* lut, const float* normD, int P, const int32_t* cols, int32_t* nbr_out, int32_t* info);
+/* Builds the lines from the host copy of the dictionary set by qmri_set_dictionary and uploads nbr and the fp64 table of unnormalised atoms
+ * [K][16] (one 128-byte row per atom).  info nullable; P = 0 clears (cols may be NULL).  qmri_set_dictionary drops the state.  A failed call leaves
+ * the earlier state working.  Everything is decided on the host before the device is touched.  Refusals: P outside 0..3, NULL cols, a column repeated or
+ * out of range, a column without lines: QMRI_ERR_INVALID_ARG (the first two also with ctx == NULL); no dictionary: QMRI_ERR_STATE; a wide
+ * dictionary (s > 16): QMRI_ERR_UNSUPPORTED.  Setting the state changes nothing about any match. */
+int qmri_set_refine(qmri_ctx* ctx, int P, const int32_t* cols, qmri_refine_info* info);
+/* The fit on host arrays; returns after the kernel has finished.  Refusals, decided before the device is touched: Npix < 1, NULL X or dm:
+ * QMRI_ERR_INVALID_ARG (also with ctx == NULL); no refinement set: QMRI_ERR_STATE. */
+int qmri_dict_refine(qmri_ctx* ctx, const void* X, int Npix, const int32_t* dm, double* qmap, double* pd, double* res, double* t, int32_t* centre,
+                     int32_t* flags);
+/* The same on device arrays, asynchronous on ctx's stream.  d_X as for qmri_dict_match_dev. */
+int qmri_dict_refine_dev(qmri_ctx* ctx, const void* d_X, int Npix, const int32_t* d_dm, double* d_qmap, double* d_pd, double* d_res, double* d_t,
+                         int32_t* d_centre, int32_t* d_flags);
+
 /* ---- TSMI synthesis from quantitative maps: main_synthesize_tsmis.m:54,82-100 (mode 'real') ------------ */
 /* I = knnsearch(KDTreeSearcher(dict.lut), qm(:,1:2)); X = real(dict.D(I,:)) .* dict.normD(I) .* abs(qm(:,3)); X .* sign(X(:,:,1)).
  * qmap: Npix x 3 doubles column-major (T1, T2, PD, in the units of dict.lut); X_out: Npix x s singles column-major;

@@ -23,7 +23,8 @@ SYMBOLS = [
     "qmri_net_forward_dev", "qmri_denoiser_scheme", "qmri_pnp_admm", "qmri_pnp_admm_dev", "qmri_pnp_admm_batch", "qmri_set_dictionary", "qmri_dict_match",
     "qmri_dict_match_dev", "qmri_dict_match_xfit", "qmri_dict_match_xfit_dev", "qmri_set_dictionary_groups", "qmri_dict_group_assign", "qmri_dict_match_grouped",
     "qmri_dict_match_grouped_dev", "qmri_dict_group_scores", "qmri_dict_group_scores_dev", "qmri_b1_pool", "qmri_b1_pool_dev", "qmri_b1_estimate",
-    "qmri_b1_estimate_dev", "qmri_set_components", "qmri_dict_unmix", "qmri_dict_unmix_dev", "qmri_recon_batch", "qmri_recon_batch_mc",
+    "qmri_b1_estimate_dev", "qmri_set_components", "qmri_dict_unmix", "qmri_dict_unmix_dev", "qmri_dict_lines", "qmri_set_refine", "qmri_dict_refine",
+    "qmri_dict_refine_dev", "qmri_recon_batch", "qmri_recon_batch_mc",
     "qmri_coil_compress", "qmri_coil_compress_dev", "qmri_coil_eig", "qmri_recon_batch_mc_cc", "qmri_coil_maps", "qmri_coil_maps_dev", "qmri_dict_compress", "qmri_dict_compress_dev", "qmri_dict_simulate", "qmri_dict_simulate_dev", "qmri_dict_simulate_sp", "qmri_dict_simulate_sp_dev", "qmri_field_map_estimate", "qmri_field_map_estimate_dev", "qmri_llr_prox", "qmri_llr_prox_dev", "qmri_set_llr", "qmri_wavelet_prox", "qmri_wavelet_prox_dev", "qmri_set_wavelet", "qmri_profile_enable", "qmri_profile_get", "qmri_get_health",
     "qmri_debug_lsqr_stamps", "qmri_debug_conv_stamps", "qmri_debug_lsqr_persist", "qmri_debug_dict_filter", "qmri_debug_conv_resident", "qmri_debug_dsvd_gram", "qmri_debug_epg_shift", "qmri_debug_knob", "qmri_debug_mem_stats",
     "qmri_onnx_read_unetres",
@@ -131,6 +132,10 @@ WAVELET_FILTERS = {"haar": 0, "db2": 1}
 
 class PvInfo(C.Structure):
     _fields_ = [("min_pivot", C.c_double), ("C", C.c_int32), ("s", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class RefineInfo(C.Structure):
+    _fields_ = [("P", C.c_int32), ("K", C.c_int32), ("s", C.c_int32), ("reserved", C.c_int32), ("count", (C.c_int32 * 3) * 3), ("reserved2", C.c_int32 * 3)]
 
 
 class B1estParams(C.Structure):
@@ -272,6 +277,10 @@ def lib() -> C.CDLL:
     L.qmri_set_components.argtypes = [vp, i, ip, C.POINTER(PvInfo)]
     L.qmri_dict_unmix.argtypes = [vp, vp, i, i, dp, dp, dp, dp, ip]
     L.qmri_dict_unmix_dev.argtypes = [vp, vp, i, i, vp, vp, vp, vp, vp]
+    L.qmri_dict_lines.argtypes = [i, i, fp, fp, i, ip, ip, ip]
+    L.qmri_set_refine.argtypes = [vp, i, ip, C.POINTER(RefineInfo)]
+    L.qmri_dict_refine.argtypes = [vp, vp, i, ip, dp, dp, dp, dp, ip, ip]
+    L.qmri_dict_refine_dev.argtypes = [vp, vp, i, vp, vp, vp, vp, vp, vp, vp]
     L.qmri_recon_batch.argtypes = [i, C.POINTER(i), i, C.POINTER(Problem), vp, vp, fp, fp, C.c_char_p, C.c_size_t]
     L.qmri_recon_batch_mc.argtypes = [i, C.POINTER(i), i, C.POINTER(Problem), i, vp, vp, vp, fp, fp, C.c_char_p, C.c_size_t]
     L.qmri_recon_batch_mc_cc.argtypes = [i, C.POINTER(i), i, C.POINTER(Problem), i, vp, vp, vp, fp, fp, C.c_char_p, C.c_size_t, vp, C.POINTER(CcParams)]

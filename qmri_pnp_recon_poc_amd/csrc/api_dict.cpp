@@ -38,6 +38,7 @@ extern "C" int qmri_set_dictionary(qmri_ctx* ctx, int K, int s, int Q, const flo
         return QMRI_OK;
     }
     d.D_h.assign(D, D + (size_t)K * s); d.normD_h.assign(normD, normD + K);     // host copy for qmri_set_components (api_pv.cpp)
+    d.lut_h.assign(lut, lut + (size_t)K * Q);                                   // ... and, with it, for qmri_set_refine (api_refine.cpp)
     d.ntiles = (K + 31) / 32;
     const int npair = (s + 1) / 2;
     // [tile][lane][NPL] with NPL = 4 or 8 floats per lane (its A-fragment value of every channel pair, zero padded): a lane fetches its

@@ -51,6 +51,8 @@ void qmri_set_error(qmri_ctx* ctx, const char* fmt, ...);
 #include "net_plan.h"
 // The joint wavelet soft-thresholding step's geometry, tiles, buffers and launch list, in plain C++ (wav_plan.h).
 #include "wav_plan.h"
+// The lines of a gridded dictionary and the refinement's atom table, in plain C++ (refine_plan.h).
+#include "refine_plan.h"
 
 // ---------------------------------------------------------------------------------------------------
 // A/B and diagnostic switches ("knobs").  ONE environment variable, QMRI_DEBUG="name=value,name=value" (read once per process), and
@@ -500,6 +502,12 @@ struct PvHost { int C = 0, s = 0; double min_pivot = 0.0; DevArr<double> d_tab; 
 int pv_form_components(const float* D, const float* normD, int K, int s, int C, const int32_t* atoms, double* tab, double* min_pivot, std::string* msg);
 int pv_launch(qmri_ctx* ctx, const double2* d_X, int Npix, int mode, double* d_w, double* d_frac, double2* d_pd, double* d_res, int32_t* d_flags);
 
+// sub-grid refinement of a match (qmri_set_refine; refine_kernels.hip, api_refine.cpp): P = 0 none.  d_nbr [K][P][2] the lines
+// (refine_plan.h), d_arow [K][16] the unnormalised atoms in fp64, one 128-byte row each.
+struct RefineHost { int P = 0; int cols[3] = {0, 0, 0}; int32_t count[3][3] = {}; DevArr<int32_t> d_nbr; DevArr<double> d_arow; };
+int refine_launch(qmri_ctx* ctx, const double2* d_X, int Npix, const int32_t* d_dm, double* d_qmap, double2* d_pd, double* d_res, double* d_t,
+                  int32_t* d_centre, int32_t* d_flags);
+
 struct DictHost {
     bool ready = false;
     int K = 0, s = 0, Q = 0, ntiles = 0;
@@ -532,8 +540,9 @@ struct DictHost {
     // the B1 estimate (dictb_kernels.hip, api_b1.cpp): scores and box sums of a run of slices, the atom parts' maxima, group_val of a pool call
     DevArr<float> d_bscore, d_bpart; DevArr<double> d_bT, d_bval;
     int slots_b = 0;                                      // workgroups of k_dictb_scores the device holds at once
-    std::vector<float> D_h, normD_h;                      // narrow dictionaries: the caller's D [K x s column-major] and normD, kept for qmri_set_components
+    std::vector<float> D_h, normD_h, lut_h;               // narrow dictionaries: the caller's D [K x s column-major], normD and lut [K x Q column-major], kept for qmri_set_components and qmri_set_refine
     PvHost pv;                                            // ... and the components in force (C = 0: none); dropped with the dictionary
+    RefineHost rf;                                        // ... and the refinement in force (P = 0: none); dropped with the dictionary
 };
 
 struct qmri_ctx {

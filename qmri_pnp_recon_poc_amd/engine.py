@@ -245,6 +245,43 @@ def dict_group_assign(group_val, sel):
     return out.reshape(b.shape)
 
 
+def refine_columns(cols, Q=None):
+    """cols [P] int32 as qmri_set_refine takes them: 1 <= P <= 3 distinct lut columns (0-based), inside 0..Q-1 when Q is known."""
+    c = np.asarray(cols)
+    if c.ndim != 1 or not (1 <= c.size <= 3) or not np.issubdtype(c.dtype, np.integer):
+        raise ValueError("cols must be 1 to 3 integer lut columns (0-based)")
+    if len(set(c.tolist())) != c.size:
+        raise ValueError("cols must be distinct")
+    if c.min() < 0 or (Q is not None and c.max() >= Q):
+        raise ValueError("cols are 0-based lut columns" + ("" if Q is None else f" of the dictionary's {Q}"))
+    return np.ascontiguousarray(c, dtype=np.int32)
+
+
+def dict_lines(lut, normD, cols=(0, 1)):
+    """The lines of a gridded dictionary (qmri_dict_lines, host only): for every atom and every column of cols its lower and
+    upper neighbour along that column, all other lut columns equal.  lut [K, Q], normD [K] -> (nbr [K, P, 2] int32, 0-based, -1 = none;
+    count [P, 3] = atoms with 0, 1 and 2 neighbours per column)."""
+    from . import _lib
+    lut = np.asarray(lut, dtype=np.float32)
+    nd = np.ascontiguousarray(normD, dtype=np.float32).ravel()
+    if lut.ndim != 2 or lut.shape[0] < 1 or lut.shape[1] < 1 or nd.size != lut.shape[0]:
+        raise ValueError("lut must be [K, Q] with one normD per atom")
+    K, Q = lut.shape
+    c = refine_columns(cols, Q)
+    lf = np.ascontiguousarray(lut.ravel(order="F"))
+    nbr = np.empty((K, c.size, 2), np.int32)
+    count = np.zeros((c.size, 3), np.int32)
+    f, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+    st = _lib.lib().qmri_dict_lines(K, Q, lf.ctypes.data_as(f), nd.ctypes.data_as(f), c.size, c.ctypes.data_as(ip), nbr.ctypes.data_as(ip),
+                                    count.ctypes.data_as(ip))
+    if st != 0:
+        raise QmriError(st, _lib.lib().qmri_last_error(None).decode())
+    return nbr, count
+
+
+REFINE_FLAGS = {"skipped": 1, "moved": 2, "bound": 4, "cap": 8, "stalled": 16, "degenerate": 32}
+
+
 def nearest_atoms(lut, points):
     """The 1-based row of lut [K, >= 2] whose (T1, T2) is nearest each row of points [n, 2]: squared distance in float64, the first minimum wins."""
     lut = np.asarray(lut, dtype=np.float64)
@@ -348,6 +385,7 @@ class Engine:
         self.net_desc = None
         self.dict_shape = None
         self.components = None
+        self.refine_cols = None
 
     def close(self):
         if getattr(self, "h", None):
@@ -1010,6 +1048,70 @@ class Engine:
         self._lut = np.asarray(lut, dtype=np.float64)
         self.components = None                                   # (qmri_set_dictionary drops them)
         self.dict_groups = None                                  # (... and the groups)
+        self.refine_cols = None                                  # (... and the refinement)
+
+    # -- sub-grid refinement of a match (extension, no reference counterpart) --
+    def set_refine(self, cols=(0, 1)):
+        """The lut columns dict_refine moves off the grid (include/qmri.h qmri_set_refine): 1 to 3 distinct 0-based columns of the set narrow
+        dictionary's lut, (0, 1) = (T1, T2).  Builds every atom's neighbours along each column (dict_lines) and uploads them with the fp64 table of
+        unnormalised atoms.  Returns dict(P, K, s, count [P, 3] = atoms with 0, 1, 2 neighbours per column).  set_dictionary drops the state."""
+        from ._lib import RefineInfo
+        if getattr(self, "dict_shape", None) is None:
+            raise ValueError("set_dictionary first")
+        c = refine_columns(cols, self.dict_shape[2])
+        info = RefineInfo()
+        self._check(self.L.qmri_set_refine(self.h, c.size, c.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(info)))
+        self.refine_cols = c.copy()
+        return {"P": int(info.P), "K": int(info.K), "s": int(info.s), "count": np.array([[info.count[q][j] for j in range(3)] for q in range(c.size)], np.int32)}
+
+    def clear_refine(self):
+        self._check(self.L.qmri_set_refine(self.h, 0, None, None))
+        self.refine_cols = None
+
+    def dict_refine(self, X, dm, want_pd=True, want_res=True, want_t=True, want_centre=True):
+        """Every pixel of X [..., s] complex fitted to the quadratic through its start atom dm [...] (1-based, from any match; 0 = skipped) and that
+        atom's neighbours along the set_refine columns (qmri_dict_refine): dict(qmap [..., Q] float64 -- the refined columns off the grid, the
+        others the final centre's lut value --, flags [...] int32 (REFINE_FLAGS), pd [...] complex128, res [...] = ||x - pd d|| / ||x||,
+        t [..., P] the position between the neighbours in [-1, 1], centre [...] the 1-based atom the result is expressed around)."""
+        if getattr(self, "refine_cols", None) is None:
+            raise ValueError("set_refine first")
+        X = np.asarray(X, dtype=np.complex128)
+        K, s, Q = self.dict_shape
+        if X.ndim < 1 or X.shape[-1] != s:
+            raise ValueError("last dimension of X must equal the dictionary's channel count")
+        lead = X.shape[:-1]
+        dm = np.asarray(dm)
+        if dm.shape != lead or not np.issubdtype(dm.dtype, np.integer):
+            raise ValueError(f"dm must be integers in the leading shape of X, {lead}")
+        npix, P = int(np.prod(lead)), int(self.refine_cols.size)
+        xb = np.ascontiguousarray(X.reshape((npix, s), order="F").ravel(order="F"))
+        db = np.ascontiguousarray(dm.ravel(order="F"), dtype=np.int32)
+        qmap = np.empty(npix * Q, np.float64)
+        pd = np.empty(2 * npix, np.float64) if want_pd else None
+        res = np.empty(npix, np.float64) if want_res else None
+        t = np.empty(npix * P, np.float64) if want_t else None
+        centre = np.empty(npix, np.int32) if want_centre else None
+        flags = np.empty(npix, np.int32)
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        self._check(self.L.qmri_dict_refine(self.h, _vp(xb), npix, db.ctypes.data_as(ip), qmap.ctypes.data_as(dp), pd.ctypes.data_as(dp) if want_pd else None,
+                                            res.ctypes.data_as(dp) if want_res else None, t.ctypes.data_as(dp) if want_t else None,
+                                            centre.ctypes.data_as(ip) if want_centre else None, flags.ctypes.data_as(ip)))
+        out = {"qmap": qmap.reshape(lead + (Q,), order="F"), "flags": flags.reshape(lead, order="F")}
+        if want_pd:
+            out["pd"] = pd.view(np.complex128).reshape(lead, order="F")
+        if want_res:
+            out["res"] = res.reshape(lead, order="F")
+        if want_t:
+            out["t"] = t.reshape(lead + (P,), order="F")
+        if want_centre:
+            out["centre"] = centre.reshape(lead, order="F")
+        return out
+
+    def dict_refine_dev(self, d_X: int, npix: int, d_dm: int, d_qmap: int = 0, d_pd: int = 0, d_res: int = 0, d_t: int = 0, d_centre: int = 0, d_flags: int = 0):
+        """qmri_dict_refine_dev: device pointers (X Npix x s complex double column-major, dm Npix int32; outputs as qmri.h lays them out),
+        asynchronous on the engine's stream."""
+        self._check(self.L.qmri_dict_refine_dev(self.h, C.c_void_p(d_X), int(npix), C.c_void_p(d_dm), C.c_void_p(d_qmap or None), C.c_void_p(d_pd or None),
+                                                C.c_void_p(d_res or None), C.c_void_p(d_t or None), C.c_void_p(d_centre or None), C.c_void_p(d_flags or None)))
 
     def set_components(self, atoms):
         """The components of tissue_fractions (extension, no reference counterpart; include/qmri.h qmri_set_components):
@@ -1342,11 +1444,21 @@ class Engine:
         self._check(self.L.qmri_norm_tv(self.h, I.ctypes.data_as(C.POINTER(C.c_double)), I.shape[0], I.shape[1], C.byref(out)))
         return float(out.value)
 
-    def dict_match(self, X, sel=None, want_mt=True, want_dm=True, want_xfit=False):
+    def dict_match(self, X, sel=None, want_mt=True, want_dm=True, want_xfit=False, refine=False):
         """out = mrf_dtm_cpu(dict, data, par)  (mrf_dtm_cpu.m:1).  X [..., s] complex -> dict of arrays; want_xfit adds Xfit [..., s]
         complex64 (par.f.Xout, :95,129-134).  sel (the leading shape of X, e.g. a measured B1 map): the grouped match (extension;
         set_dictionary_groups) -- every pixel against the atoms of the group nearest its value, "grp" (1-based, 0 = unmatched: a non-finite value,
-        all outputs zero) added to the result."""
+        all outputs zero) added to the result.  refine=True (extension; set_refine): the match, then dict_refine started at its dm --
+        "qmap_refined", "pd_refined", "refine_res", "refine_t" and "refine_flags" added, everything else unchanged."""
+        if refine:
+            if getattr(self, "refine_cols", None) is None:
+                raise ValueError("set_refine first")
+            out = self.dict_match(X, sel=sel, want_mt=want_mt, want_dm=True, want_xfit=want_xfit)
+            r = self.dict_refine(X, out["dm"], want_centre=False)
+            out.update(qmap_refined=r["qmap"], pd_refined=r["pd"], refine_res=r["res"], refine_t=r["t"], refine_flags=r["flags"])
+            if not want_dm:
+                del out["dm"]
+            return out
         X = np.asarray(X, dtype=np.complex128)
         K, s, Q = self.dict_shape
         if X.shape[-1] != s:

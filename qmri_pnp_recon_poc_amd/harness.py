@@ -310,6 +310,31 @@ def unmix_tsmi(dictionary, X, components, mode="real", device=0):
             "unmix_flags": out["flags"]}
 
 
+def resolve_refine(dictionary, refine):
+    """refine of recon_tsmis -> None (False / None: no refinement) or the int32 lut columns: True stands for (0, 1) = (T1, T2)."""
+    from .engine import refine_columns
+    if refine is None or refine is False:
+        return None
+    return refine_columns((0, 1) if refine is True else refine, np.asarray(dictionary["lut"]).shape[1])
+
+
+def refine_tsmi(dictionary, X, cols=(0, 1), sel=None, device=0):
+    """Quantitative maps of a TSMI X [N, M, s] below the dictionary's grid: the match, then every pixel fitted to the quadratic
+    through its matched atom and that atom's neighbours along the lut columns cols.  sel: the selector map of a grouped match (a dictionary with
+    group_ptr / group_val).  Returns dict(qmap_refined [N, M, Q] float64, pd_refined [N, M] complex, refine_res, refine_t [N, M, P], refine_flags,
+    dm, qmap, pd: the match's own)."""
+    from . import reference_api as R
+    from .engine import refine_columns
+    c = refine_columns(cols, np.asarray(dictionary["lut"]).shape[1])
+    eng = R._engine(device)
+    eng.set_dictionary(dictionary["D"], dictionary["normD"], dictionary["lut"])
+    if sel is not None:
+        eng.set_dictionary_groups(dictionary["group_ptr"], dictionary["group_val"])
+    eng.set_refine(c)
+    out = eng.dict_match(X, sel=sel, refine=True)
+    return {k: out[k] for k in ("qmap_refined", "pd_refined", "refine_res", "refine_t", "refine_flags", "dm", "qmap", "pd")}
+
+
 def estimate_b1(dictionary, X, mask=None, window=4, device=0):
     """The B1 map of a TSMI X [N, M, s] (or [N, M, nslices, s]) estimated from the fingerprints themselves: per pixel the b1
     group of the dictionary (simulate_dictionary(..., b1_grid=...)) whose best atoms explain the most energy over the (2 window + 1)^2 window;
@@ -340,7 +365,7 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
                 net_arch=None, lrtv_iters=None, tsmi_domain="real", solver="lsqr", b1_map=None, density_compensation=False,
                 field_map=None, readout_s=None, field_normal=None, field_echoes=None, field_echo_times=None,
                 regulariser="net", llr_tau=None, llr_tau_rel=0.02, llr_block=8, wavelet_tau=None, wavelet_tau_rel=None,
-                wavelet_levels=3, wavelet_filter="db2", components=None, unmix_mode="real", b1_window=4):
+                wavelet_levels=3, wavelet_filter="db2", components=None, unmix_mode="real", b1_window=4, refine=False):
     """main_recon_tsmis_FFT.m:216-374 on already loaded (and cropped) arrays.
 
     dictionary  dict(V, D, normD, lut) (load_dictionary);  X0  N x M x s ground-truth TSMI;  qmap0  N x M x 3
@@ -375,6 +400,11 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
                 nearest atom) or 1-based atom indices; every pixel of the reconstructed TSMI is written as a non-negative mix of those atoms
                 (unmix_mode "real": of its real part, "phase": after removing the pixel's phase).  The result gains fractions (N x M x C),
                 component_atoms (C, 1-based) and unmix_res (N x M).  Absent: nothing changes.
+    refine      True, or the lut columns to refine ((0, 1) = T1, T2): after the match every pixel is fitted to the quadratic through its matched atom
+                and that atom's neighbours, started at the match's own dm (Engine.dict_refine).  The result gains
+                qmap_refined (N x M x 3: the first two lut columns after the fit and the fit's PD -- the layout of qmap), metrics_refined (metrics
+                of it, as `metrics` is of qmap), refine_qmap (N x M x Q: every lut column after the fit, so a refined third column such as b1 is
+                there), refine_res and refine_flags.  False (default): nothing changes.
     Returns dict(X, qmap (N x M x 3: T1, T2, PD), Y, metrics, foreground_mask); with b1_map also grp (N x M, the 1-based b1 group, 0 = unmatched);
     with field_normal also field_normal_info (what prepare_normal_field reported).
     """
@@ -404,6 +434,7 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
         component_atoms = resolve_components(dictionary, components)
         from .engine import unmix_mode as _umode
         _umode(unmix_mode)
+    refine_cols = resolve_refine(dictionary, refine)                                 # (refused before anything is reconstructed)
     V = np.asarray(dictionary["V"], dtype=np.float64)
     if subsampling_pattern == "Spiral":
         P = R.setup_subsampling_spiralgrided(N, M, spiral_sampling_curve, V)
@@ -508,10 +539,20 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
         out = eng.dict_match(X, sel=b1_map)
         out["qmap"] = out["qmap"][:, :, :2]                                          # (T1, T2); column 3 of the lut is the group's b1
         extra["grp"] = out["grp"]
+    elif refine_cols is not None:                                                    # what mrf_dtm_cpu does, keeping dm for the refinement
+        eng = R._engine(device)
+        eng.set_dictionary(dictionary["D"], dictionary["normD"], dictionary["lut"])
+        out = eng.dict_match(X)
     else:
         out = R.mrf_dtm_cpu(dictionary, {"X": X}, par, device=device)
     qmap = np.concatenate([np.asarray(out["qmap"], dtype=np.complex128), np.asarray(out["pd"]).reshape(N, M, 1)], axis=2)       # :316
     if components is not None:
         extra.update(unmix_tsmi(dictionary, X, component_atoms, mode=unmix_mode, device=device))
     mask = getmask_fromPD(np.asarray(qmap0)[:, :, 2], 0.15)                          # :192
+    if refine_cols is not None:                                                      # the fit, started at the dm of the match above
+        eng.set_refine(refine_cols)
+        rf = eng.dict_refine(X, out["dm"])
+        qr = np.concatenate([np.asarray(rf["qmap"][:, :, :2], dtype=np.complex128), np.asarray(rf["pd"]).reshape(N, M, 1)], axis=2)
+        extra.update(qmap_refined=qr, metrics_refined=metrics(qr, qmap0, mask, X, X0), refine_qmap=rf["qmap"], refine_res=rf["res"],
+                     refine_flags=rf["flags"])
     return {"X": X, "qmap": qmap, "Y": Y, "foreground_mask": mask, "metrics": metrics(qmap, qmap0, mask, X, X0), **extra}

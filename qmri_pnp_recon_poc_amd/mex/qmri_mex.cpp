@@ -63,6 +63,7 @@ static OperatorSpec g_op;
 static DenoiserSpec g_net;
 static DictSpec g_dict;
 static std::vector<int32_t> g_comp;                    // 'set_components' in force (1-based atoms); 'set_dictionary' drops them
+static std::vector<int32_t> g_refine;                  // 'set_refine' in force (0-based lut columns); 'set_dictionary' drops them
 static int g_ngroups = 0;                              // 'set_dictionary_groups' in force (G); 'set_dictionary' and a device switch drop them
 static bool g_llr = false;                             // 'set_llr' is in force: 'pnp_admm' needs no denoiser
 static bool g_wav = false;                             // 'set_wavelet' is in force: the same
@@ -77,6 +78,7 @@ static void cleanup() {
     drop(g_net.w); g_net = DenoiserSpec();
     drop(g_dict.D); drop(g_dict.normD); drop(g_dict.lut);
     g_comp.clear();
+    g_refine.clear();
     g_ngroups = 0;
     g_llr = false;
     g_wav = false;
@@ -249,6 +251,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
             if (g_net.w) plan_denoiser(std::max(1, g_net.max_batch));
             if (g_dict.D) plan_dictionary();
             if (g_dict.D && !g_comp.empty()) check(qmri_set_components(ctx(), (int)g_comp.size(), g_comp.data(), nullptr));
+            if (g_dict.D && !g_refine.empty()) check(qmri_set_refine(ctx(), (int)g_refine.size(), g_refine.data(), nullptr));
         }
         if (nlhs > 0) plhs[0] = mxCreateDoubleScalar((double)g_device);
     } else if (c == "set_operator") {                // qmri_mex('set_operator', N, M, V, frame_ptr(int32), kidx(int32) [, max_batch])
@@ -998,6 +1001,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         drop(g_dict.D); drop(g_dict.normD); drop(g_dict.lut);
         g_dict.D = keep(prhs[1]); g_dict.normD = keep(prhs[2]); g_dict.lut = keep(prhs[3]);
         g_comp.clear();
+        g_refine.clear();
         g_ngroups = 0;
         plan_dictionary();
     } else if (c == "dict_match") {                  // [qmap, pd, mt, dm, xfit] = qmri_mex('dict_match', X(Npix x s complex double), Q)
@@ -1155,6 +1159,58 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         if (nlhs > 2) plhs[2] = pd;
         if (nlhs > 3) plhs[3] = res;
         if (nlhs > 4) plhs[4] = flags;
+    } else if (c == "set_refine") {                  // info = qmri_mex('set_refine', cols(1..3 doubles, 0-based lut columns)); [] clears
+        // the refined columns of 'dict_refine' (extension; qmri.h qmri_set_refine).  'set_dictionary' drops them.
+        need(nrhs, 2, "info = qmri_mex('set_refine', cols)");
+        want(nlhs <= 1, "qmri:usage", "info = qmri_mex('set_refine', cols)");
+        want(mxIsDouble(prhs[1]) && !mxIsComplex(prhs[1]), "qmri:set_refine:type", "cols must be a real double array");
+        const size_t np_ = mxGetNumberOfElements(prhs[1]);
+        want(np_ <= 3, "qmri:set_refine:size", "cols must hold 1 to 3 lut columns ([] clears)");
+        std::vector<int32_t> cols(np_);
+        const double* v = mxGetDoubles(prhs[1]);
+        for (size_t k = 0; k < np_; ++k) {
+            want(std::isfinite(v[k]) && v[k] == std::floor(v[k]) && v[k] >= 0 && v[k] <= 1023, "qmri:set_refine:value", "cols must be 0-based lut column indices");
+            cols[k] = (int32_t)v[k];
+        }
+        want(g_dict.D != nullptr, "qmri:state", "no dictionary: call qmri_mex('set_dictionary', ...) first");
+        qmri_refine_info info{};
+        check(qmri_set_refine(ctx(), (int)np_, np_ ? cols.data() : nullptr, &info));
+        g_refine = cols;
+        if (nlhs > 0) {
+            const char* names[] = {"P", "K", "s", "count"};
+            plhs[0] = mxCreateStructMatrix(1, 1, 4, names);
+            const double f[3] = {(double)info.P, (double)info.K, (double)info.s};
+            for (int k = 0; k < 3; ++k) mxSetFieldByNumber(plhs[0], 0, k, mxCreateDoubleScalar(f[k]));
+            mxArray* cnt = mxCreateDoubleMatrix(np_, 3, mxREAL);       // row q: atoms with 0, 1, 2 neighbours along cols(q)
+            for (size_t q = 0; q < np_; ++q)
+                for (int j = 0; j < 3; ++j) mxGetDoubles(cnt)[q + np_ * j] = (double)info.count[q][j];
+            mxSetFieldByNumber(plhs[0], 0, 3, cnt);
+        }
+    } else if (c == "dict_refine") {                 // [qmap, pd, res, t, centre, flags] = qmri_mex('dict_refine', X(Npix x s complex double), dm(Npix int32))
+        const char* usage = "[qmap, pd, res, t, centre, flags] = qmri_mex('dict_refine', X, dm)";
+        need(nrhs, 3, usage);
+        want(nlhs <= 6, "qmri:usage", usage);
+        want(is_cdouble(prhs[1]) && mxGetM(prhs[1]) >= 1 && mxGetM(prhs[1]) <= 2147483647u, "qmri:dict_refine:type", "X must be complex double, Npix x s");
+        want(mxIsInt32(prhs[2]) && !mxIsComplex(prhs[2]) && mxGetNumberOfElements(prhs[2]) == mxGetM(prhs[1]), "qmri:dict_refine:dm",
+             "dm must be int32 with one start atom per row of X (as 'dict_match' returns it)");
+        want(g_dict.D != nullptr, "qmri:state", "no dictionary: call qmri_mex('set_dictionary', ...) first");
+        want(mxGetN(prhs[1]) == mxGetN(g_dict.D), "qmri:dict_refine:size", "X must have s columns (s = columns of dict.D)");
+        want(!g_refine.empty(), "qmri:state", "no refinement: call qmri_mex('set_refine', cols) first");
+        const size_t npix = mxGetM(prhs[1]), nq = mxGetN(g_dict.lut), np_ = g_refine.size();
+        plhs[0] = mxCreateDoubleMatrix(npix, nq, mxREAL);
+        mxArray* pd = (nlhs > 1) ? mxCreateDoubleMatrix(npix, 1, mxCOMPLEX) : nullptr;
+        mxArray* res = (nlhs > 2) ? mxCreateDoubleMatrix(npix, 1, mxREAL) : nullptr;
+        mxArray* t = (nlhs > 3) ? mxCreateDoubleMatrix(npix, np_, mxREAL) : nullptr;
+        mxArray* centre = (nlhs > 4) ? mxCreateNumericMatrix(npix, 1, mxINT32_CLASS, mxREAL) : nullptr;
+        mxArray* flags = (nlhs > 5) ? mxCreateNumericMatrix(npix, 1, mxINT32_CLASS, mxREAL) : nullptr;
+        check(qmri_dict_refine(ctx(), mxGetComplexDoubles(prhs[1]), (int)npix, (const int32_t*)mxGetData(prhs[2]), mxGetDoubles(plhs[0]),
+                               pd ? (double*)mxGetComplexDoubles(pd) : nullptr, res ? mxGetDoubles(res) : nullptr, t ? mxGetDoubles(t) : nullptr,
+                               centre ? (int32_t*)mxGetData(centre) : nullptr, flags ? (int32_t*)mxGetData(flags) : nullptr));
+        if (nlhs > 1) plhs[1] = pd;
+        if (nlhs > 2) plhs[2] = res;
+        if (nlhs > 3) plhs[3] = t;
+        if (nlhs > 4) plhs[4] = centre;
+        if (nlhs > 5) plhs[5] = flags;
     } else if (c == "health") {                      // h = qmri_mex('health'): qmri_get_health of the gateway's context as a struct
         qmri_health h;
         check(qmri_get_health(ctx(), &h));

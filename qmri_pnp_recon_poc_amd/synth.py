@@ -106,20 +106,7 @@ def make_dictionary(T: int = 200, n_t1: int = 128, n_t2: int = 64, s: int = 10, 
     T1 = T1.ravel()
     T2 = T2.ravel()
     K = T1.size
-    alpha = flip_angle_train(T, seed)
-    TR, TE, spoil = 0.012, 0.002, 0.6
-    e1 = np.exp(-TR / T1)
-    e2 = np.exp(-TR / T2) * spoil
-    ete = np.exp(-TE / T2)
-    mx = np.zeros(K)
-    mz = -np.ones(K)
-    F = np.empty((K, T), dtype=np.float64)
-    for t in range(T):
-        ca, sa = np.cos(alpha[t]), np.sin(alpha[t])
-        mx, mz = ca * mx + sa * mz, -sa * mx + ca * mz
-        F[:, t] = mx * ete
-        mx = mx * e2
-        mz = 1.0 + (mz - 1.0) * e1
+    F = simulate_fingerprints(T, T1, T2, seed)
     if uncompressed:
         normD = np.linalg.norm(F, axis=1)
         return {"D": np.ascontiguousarray((F / normD[:, None]).astype(np.float32)), "normD": normD.astype(np.float32),
@@ -146,6 +133,24 @@ def make_dictionary(T: int = 200, n_t1: int = 128, n_t2: int = 64, s: int = 10, 
         "t2_grid": t2,
         "K": K,
     }
+
+
+def simulate_fingerprints(T: int, t1, t2, seed: int = 0) -> np.ndarray:
+    """The signal model of make_dictionary at arbitrary (t1, t2) in seconds -> [n, T] float64 (not normalised): off-grid fingerprints, e.g.
+    `simulate_fingerprints(T, t1, t2) @ dic["V"]` for pixels between the atoms of make_dictionary(T, ...)."""
+    t1, t2 = np.atleast_1d(np.asarray(t1, np.float64)), np.atleast_1d(np.asarray(t2, np.float64))
+    alpha = flip_angle_train(T, seed)
+    TR, TE, spoil = 0.012, 0.002, 0.6
+    e1, e2, ete = np.exp(-TR / t1), np.exp(-TR / t2) * spoil, np.exp(-TE / t2)
+    mx, mz = np.zeros(t1.size), -np.ones(t1.size)
+    F = np.empty((t1.size, T), dtype=np.float64)
+    for t in range(T):
+        ca, sa = np.cos(alpha[t]), np.sin(alpha[t])
+        mx, mz = ca * mx + sa * mz, -sa * mx + ca * mz
+        F[:, t] = mx * ete
+        mx = mx * e2
+        mz = 1.0 + (mz - 1.0) * e1
+    return F
 
 
 # ----------------------------------------------------------------------------------------------------
