@@ -918,6 +918,42 @@ int qmri_wavelet_prox_dev(qmri_ctx* ctx, int N, int M, int s, int nslices, const
  * checks of qmri_wavelet_prox on tau, levels, filter, joint and reserved, shift outside {0, 1}. */
 int qmri_set_wavelet(qmri_ctx* ctx, const qmri_wavelet_params* p);
 
+/* ---- simultaneous multi-slice (SMS) groups: an EXTENSION, no reference counterpart, parity unpinned -------------------
+ * Z slices excited together with a known phase per frame and slice (SMS-MRF with RF phase cycling): the receiver sees their sum,
+ *     y_j[i] = sum_{b < Z} E[t(i), b] (A (C_{b,j} . x_b))[i]          i sample, t(i) its frame, j coil, b slice, A the context's operator
+ * and the Z slices of a group are solved jointly.  qmri_set_sms attaches E to the operator in force (gridded or trajectory): T x Z complex
+ * doubles, E[t + T*b], every value finite, any modulus; 1 <= Z <= 8 and T*Z <= 8192.  Z = 0 or E = NULL clears it; replacing the operator drops it,
+ * as the sample weights.  No existing entry point reads it.  Host work only.  Refusals: Z outside 0..8, T*Z > 8192, a non-finite E:
+ * QMRI_ERR_INVALID_ARG; no operator: QMRI_ERR_STATE; an operator with a field map attached (one map cannot serve Z slices): QMRI_ERR_UNSUPPORTED,
+ * as is every _sms call while a map is attached.
+ *
+ * Layouts extend the _mc_batch calls by a group index: maps G x Z x ncoil x N*M, y G x ncoil x m (the ABI's frame-major order, one set of samples
+ * per group), x / z / x0 / x_out G x Z x N*M*s (complex doubles).
+ *     A_sms x   = [ sum_b E[t(i), b] (A (C_{g,b,j} . x_{g,b}))_i ]_{g,j}
+ *     A_sms^H y = [ sum_j conj(C_{g,b,j}) . A^H (conj(E[t(.), b]) . y_{g,j}) ]_{g,b}
+ * slice b added after slice b - 1 and coil j after coil j - 1, in fp64, whatever max_batch is.
+ * qmri_xupdate_sms: x = lsqr(@afun, [y; sqrt(r) z], tol, maxit, [], [], x0), afun = [A_sms; sqrt(r) I], over the Z slices of a group jointly, with
+ * the recurrences, stop rules (flags 0 / 1 / 3) and order of qmri_xupdate_mc_batch; one iteration count and flag per GROUP (iters_out / flags_out:
+ * G entries, nullable).  A group's result is the same bits alone, at any position of any call, at any G and max_batch; with Z = 1 and E = 1 it
+ * is qmri_xupdate_mc_batch's, bit for bit.
+ * qmri_pnp_admm_sms: the loop of qmri_pnp_admm_mc_batch with that x-update, groups_per_launch groups at a time (groups_per_launch * Z <=
+ * max_batch of the operator and the denoiser); x0 = NULL: A_sms^H y; Step 2 runs on the G Z slice images as in every other loop (network in real
+ * or complex mode, qmri_set_llr, qmri_set_wavelet); lsqr_iters_out: G x prm->iters (nullable).  prm->solver must be QMRI_SOLVER_LSQR: TOEPLITZ
+ * (its normal operator would need Z^2 point-spread functions) and DIRECT are QMRI_ERR_UNSUPPORTED.  _dev: device arrays, G * Z <= max_batch,
+ * d_x_out must not alias d_x0.
+ * Refusals, decided on the host before the device is selected (ctx == NULL: QMRI_ERR_INVALID_ARG, message in qmri_last_error(NULL)): a NULL
+ * array, G < 1, ncoil outside 1..1024, r <= 0, maxit < 0, groups_per_launch < 1 or groups_per_launch * Z > max_batch: QMRI_ERR_INVALID_ARG; no
+ * operator, no qmri_set_sms, no Step 2 configured: QMRI_ERR_STATE. */
+int qmri_set_sms(qmri_ctx* ctx, int Z, const void* E);
+int qmri_forward_sms(qmri_ctx* ctx, int G, int ncoil, const void* maps, const void* x, int x_is_complex, void* y);
+int qmri_adjoint_sms(qmri_ctx* ctx, int G, int ncoil, const void* maps, const void* y, void* x);
+int qmri_xupdate_sms(qmri_ctx* ctx, int G, int ncoil, const void* maps, const void* y, const void* z, double r, double tol, int maxit, const void* x0,
+                     void* x_out, int32_t* iters_out, int32_t* flags_out);
+int qmri_pnp_admm_sms(qmri_ctx* ctx, int G, int groups_per_launch, int ncoil, const void* maps, const void* y, const qmri_admm_params* prm,
+                      const void* x0, void* x_out, int32_t* lsqr_iters_out);
+int qmri_pnp_admm_sms_dev(qmri_ctx* ctx, int G, int ncoil, const void* d_maps, const void* d_y, const qmri_admm_params* prm, const void* d_x0,
+                          void* d_x_out, int32_t* lsqr_iters_out);
+
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------------ */
 typedef struct {
     double ms_xupdate, ms_denoiser, ms_elementwise, ms_diag, ms_match;   /* hipEvent time per stage */

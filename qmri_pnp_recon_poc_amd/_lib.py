@@ -25,7 +25,7 @@ SYMBOLS = [
     "qmri_dict_match_grouped_dev", "qmri_dict_group_scores", "qmri_dict_group_scores_dev", "qmri_b1_pool", "qmri_b1_pool_dev", "qmri_b1_estimate",
     "qmri_b1_estimate_dev", "qmri_set_components", "qmri_dict_unmix", "qmri_dict_unmix_dev", "qmri_dict_lines", "qmri_set_refine", "qmri_dict_refine",
     "qmri_dict_refine_dev", "qmri_recon_batch", "qmri_recon_batch_mc",
-    "qmri_coil_compress", "qmri_coil_compress_dev", "qmri_coil_eig", "qmri_recon_batch_mc_cc", "qmri_coil_maps", "qmri_coil_maps_dev", "qmri_dict_compress", "qmri_dict_compress_dev", "qmri_dict_simulate", "qmri_dict_simulate_dev", "qmri_dict_simulate_sp", "qmri_dict_simulate_sp_dev", "qmri_field_map_estimate", "qmri_field_map_estimate_dev", "qmri_llr_prox", "qmri_llr_prox_dev", "qmri_set_llr", "qmri_wavelet_prox", "qmri_wavelet_prox_dev", "qmri_set_wavelet", "qmri_profile_enable", "qmri_profile_get", "qmri_get_health",
+    "qmri_coil_compress", "qmri_coil_compress_dev", "qmri_coil_eig", "qmri_recon_batch_mc_cc", "qmri_coil_maps", "qmri_coil_maps_dev", "qmri_dict_compress", "qmri_dict_compress_dev", "qmri_dict_simulate", "qmri_dict_simulate_dev", "qmri_dict_simulate_sp", "qmri_dict_simulate_sp_dev", "qmri_field_map_estimate", "qmri_field_map_estimate_dev", "qmri_llr_prox", "qmri_llr_prox_dev", "qmri_set_llr", "qmri_wavelet_prox", "qmri_wavelet_prox_dev", "qmri_set_wavelet", "qmri_set_sms", "qmri_forward_sms", "qmri_adjoint_sms", "qmri_xupdate_sms", "qmri_pnp_admm_sms", "qmri_pnp_admm_sms_dev", "qmri_profile_enable", "qmri_profile_get", "qmri_get_health",
     "qmri_debug_lsqr_stamps", "qmri_debug_conv_stamps", "qmri_debug_lsqr_persist", "qmri_debug_dict_filter", "qmri_debug_conv_resident", "qmri_debug_dsvd_gram", "qmri_debug_epg_shift", "qmri_debug_knob", "qmri_debug_mem_stats",
     "qmri_onnx_read_unetres",
     "qmri_lrtv", "qmri_prox_tv", "qmri_norm_tv", "qmri_synthesize_tsmi", "qmri_synthesize_tsmi_complex",
@@ -305,6 +305,12 @@ def lib() -> C.CDLL:
     L.qmri_wavelet_prox.argtypes = [vp, i, i, i, i, vp, i, C.POINTER(WaveletParams), i, i, vp, dp]
     L.qmri_wavelet_prox_dev.argtypes = [vp, i, i, i, i, vp, i, C.POINTER(WaveletParams), i, i, vp, dp]
     L.qmri_set_wavelet.argtypes = [vp, C.POINTER(WaveletParams)]
+    L.qmri_set_sms.argtypes = [vp, i, vp]
+    L.qmri_forward_sms.argtypes = [vp, i, i, vp, vp, i, vp]
+    L.qmri_adjoint_sms.argtypes = [vp, i, i, vp, vp, vp]
+    L.qmri_xupdate_sms.argtypes = [vp, i, i, vp, vp, vp, C.c_double, C.c_double, i, vp, vp, ip, ip]
+    L.qmri_pnp_admm_sms.argtypes = [vp, i, i, i, vp, vp, C.POINTER(AdmmParams), vp, vp, ip]
+    L.qmri_pnp_admm_sms_dev.argtypes = [vp, i, i, vp, vp, C.POINTER(AdmmParams), vp, vp, ip]
     L.qmri_debug_knob.argtypes = [C.c_char_p, i]
     L.qmri_debug_mem_stats.argtypes = [C.POINTER(MemStats)]
     L.qmri_profile_enable.argtypes = [vp, i]

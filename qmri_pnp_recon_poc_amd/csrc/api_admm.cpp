@@ -192,7 +192,7 @@ static int mc_require(qmri_ctx* ctx, int nslices, int ncoil, const void* maps, c
     QMRI_CHECK_ARG(ctx, maps && y, "maps / y_mc must not be NULL");
     return QMRI_OK;
 }
-static int mc_admm_check(qmri_ctx* ctx, const qmri_admm_params* prm) {
+int mc_admm_check(qmri_ctx* ctx, const qmri_admm_params* prm) {
     const NetPlan& net = ctx->net;
     if (!net.ready && !admm_regulariser_on(ctx)) { qmri_set_error(ctx, "denoiser not set: call qmri_set_denoiser first"); return QMRI_ERR_STATE; }
     QMRI_CHECK_ARG(ctx, prm, "params must not be NULL");
@@ -204,24 +204,22 @@ static int mc_admm_check(qmri_ctx* ctx, const qmri_admm_params* prm) {
     return admm_step_fits(ctx, prm, &multi, &cpx);
 }
 
-// PnP_ADMM.m:76-146 for B <= max_batch slices, all on the device (d_x0 NULL: x = A_mc' y as :84; returns x as :148).  When the network's range guard
-// trips, the loop starts again from the inputs (d_x_out must not alias d_x0) with no second allocation.
-static int mc_admm_group(qmri_ctx* ctx, int B, int ncoil, const double2* d_maps, const double2* d_y, const qmri_admm_params* prm, const double2* d_x0,
-                         double2* d_x, int32_t* li_out, int li_stride) {
+// PnP_ADMM.m:76-146 for B <= max_batch slice images, all on the device (returns x as :148).  sv.start makes the start image (:84 or the caller's x0)
+// and sv.solve is the x-update (:102) with its sv.nsolve LSQR counts: B of them in the multi-coil loop, one per group in the simultaneous
+// multi-slice loop (api_sms.cpp).  When the network's range guard trips, the loop starts again from the inputs with no second allocation.
+int mc_admm_loop(qmri_ctx* ctx, int B, const qmri_admm_params* prm, const AdmmSolve& sv, double2* d_x, int32_t* li_out, int li_stride) {
     OpHost& o = ctx->op;
     const bool reg = admm_regulariser_on(ctx);                                                      // (no network: nothing can trip, nothing is waited for)
     const int multi = (!reg && (prm->denoiser_type & QMRI_DENOISER_MULTI_LEVEL)) ? 1 : 0;   // (checked by mc_admm_check)
     const bool cpx = (prm->denoiser_type & QMRI_DENOISER_COMPLEX) != 0;
-    const size_t n = (size_t)o.N * o.M * o.s;
-    std::vector<int32_t> li((size_t)B);
+    std::vector<int32_t> li((size_t)sv.nsolve);
     for (int attempt = 0;; ++attempt) {
-        if (d_x0) QMRI_HIP(ctx, hipMemcpyAsync(d_x, d_x0, (size_t)B * n * sizeof(double2), hipMemcpyDeviceToDevice, ctx->stream));
-        else QMRI_TRY(mc_adjoint_batch_dev(ctx, B, ncoil, d_maps, d_y, d_x));
+        QMRI_TRY(sv.start(d_x));
         QMRI_TRY(admm_start(ctx, B, d_x, true));                  // v = x, uold = 0, z = v - uold
         bool again = false;
         for (int it = 0; it < prm->iters; ++it) {
-            QMRI_TRY(mc_xupdate_dev(ctx, prm->solver, B, ncoil, d_maps, d_y, o.d_z, prm->gamma, prm->cg_tol, prm->cg_maxit, d_x, li.data(), nullptr));   // :102
-            if (li_out) for (int b = 0; b < B; ++b) li_out[(size_t)b * li_stride + it] = li[b];
+            QMRI_TRY(sv.solve(o.d_z, d_x, li.data()));                                                                                              // :102
+            if (li_out) for (int b = 0; b < sv.nsolve; ++b) li_out[(size_t)b * li_stride + it] = li[b];
             QMRI_TRY(admm_denoiser_step(ctx, {B, prm, multi, cpx, d_x, nullptr}, false, it));                                                       // :115-144
             if (reg) continue;
             QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -234,6 +232,23 @@ static int mc_admm_group(qmri_ctx* ctx, int B, int ncoil, const double2* d_maps,
     }
     o.xhat_valid = false;
     return QMRI_OK;
+}
+
+// ... with the SENSE operator: d_x0 NULL: x = A_mc' y as :84 (d_x must not alias d_x0)
+static int mc_admm_group(qmri_ctx* ctx, int B, int ncoil, const double2* d_maps, const double2* d_y, const qmri_admm_params* prm, const double2* d_x0,
+                         double2* d_x, int32_t* li_out, int li_stride) {
+    const size_t n = (size_t)ctx->op.N * ctx->op.M * ctx->op.s;
+    AdmmSolve sv;
+    sv.nsolve = B;
+    sv.start = [&](double2* x) -> int {
+        if (!d_x0) return mc_adjoint_batch_dev(ctx, B, ncoil, d_maps, d_y, x);
+        QMRI_HIP(ctx, hipMemcpyAsync(x, d_x0, (size_t)B * n * sizeof(double2), hipMemcpyDeviceToDevice, ctx->stream));
+        return QMRI_OK;
+    };
+    sv.solve = [&](const double2* z, double2* x, int32_t* li) {
+        return mc_xupdate_dev(ctx, prm->solver, B, ncoil, d_maps, d_y, z, prm->gamma, prm->cg_tol, prm->cg_maxit, x, li, nullptr);
+    };
+    return mc_admm_loop(ctx, B, prm, sv, d_x, li_out, li_stride);
 }
 
 // One staged multi-coil run (the host-array entry points and the NUFFT route): the caller's operands go to the context's staging buffers (McWork), run(w)

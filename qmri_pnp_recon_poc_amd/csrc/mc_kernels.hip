@@ -26,8 +26,8 @@
 
 namespace {
 constexpr int NT = 256;          // threads per workgroup of the streaming kernels
-constexpr int PS = 256;          // partial sums per slice vector (n complex)
-constexpr int PC = 64;           // partial sums per coil image (m complex)
+constexpr int PS = MC_PS;        // partial sums per slice vector (n complex)
+constexpr int PC = MC_PC;        // partial sums per coil image (m complex)
 enum { MCL_INIT = 0, MCL_ITER = 1 };
 enum { SC_BETA0 = 0, SC_BETA = 1, SC_STOP = 2, SC_ALPHA = 3 };
 
@@ -323,6 +323,28 @@ int mc_launch_coil_sum(qmri_ctx* ctx, int ncoil, int g0, int cnt, const double2*
     const size_t n = (size_t)o.N * o.M * o.s, plane = (size_t)o.N * o.M;
     const int nb = (g0 + cnt - 1) / ncoil - g0 / ncoil + 1;
     k_mcl_coil_sum<<<dim3(blocks_of(n), nb), dim3(NT), 0, ctx->stream>>>(n, plane, ncoil, g0, cnt, xj, maps, st, t);
+    QMRI_HIP(ctx, hipGetLastError());
+    return QMRI_OK;
+}
+// the image-side vector kernels on B slice vectors, one state per vector (mode 0: the initial step, 1: an iteration).  sms_kernels.hip runs them on
+// the G Z slice vectors of its groups: the same kernels, so the same bits.
+int mc_launch_ub(qmri_ctx* ctx, int mode, int B, double sr, const double2* z, const double2* x, const LsqrState* st, double2* ub, double2* v, double2* d,
+                 double* pb, double* pz) {
+    const OpHost& o = ctx->op;
+    k_mcl_ub<<<dim3(PS, B), dim3(NT), 0, ctx->stream>>>(mode, (size_t)o.N * o.M * o.s, sr, z, x, st, ub, v, d, pb, pz);
+    QMRI_HIP(ctx, hipGetLastError());
+    return QMRI_OK;
+}
+int mc_launch_dupd(qmri_ctx* ctx, int B, const double2* v, const double2* x, const LsqrState* st, double2* d, double* pd, double* px) {
+    const OpHost& o = ctx->op;
+    k_mcl_dupd<<<dim3(PS, B), dim3(NT), 0, ctx->stream>>>((size_t)o.N * o.M * o.s, v, x, st, d, pd, px);
+    QMRI_HIP(ctx, hipGetLastError());
+    return QMRI_OK;
+}
+int mc_launch_vupd(qmri_ctx* ctx, int mode, int B, double sr, const double2* t, const double2* ub, const double2* d, const LsqrState* st, double2* x,
+                   double2* v, double* pv) {
+    const OpHost& o = ctx->op;
+    k_mcl_vupd<<<dim3(PS, B), dim3(NT), 0, ctx->stream>>>(mode, (size_t)o.N * o.M * o.s, sr, t, ub, d, st, x, v, pv);
     QMRI_HIP(ctx, hipGetLastError());
     return QMRI_OK;
 }

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
+#include <functional>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -53,6 +54,8 @@ void qmri_set_error(qmri_ctx* ctx, const char* fmt, ...);
 #include "wav_plan.h"
 // The lines of a gridded dictionary and the refinement's atom table, in plain C++ (refine_plan.h).
 #include "refine_plan.h"
+// The chunk schedule, frame table and partial-sum layout of a simultaneous multi-slice solve, in plain C++ (sms_plan.h).
+#include "sms_plan.h"
 
 // ---------------------------------------------------------------------------------------------------
 // A/B and diagnostic switches ("knobs").  ONE environment variable, QMRI_DEBUG="name=value,name=value" (read once per process), and
@@ -269,6 +272,13 @@ int mc_ensure_work(qmri_ctx* ctx, int B, int ncoil);
 // the coil products of a transform chunk (coil images g0 .. g0 + cnt - 1 of [B][ncoil]); st (nullable): slices whose solve has stopped are skipped
 int mc_launch_coil_mul(qmri_ctx* ctx, int ncoil, int g0, int cnt, const double2* x, const double2* maps, const LsqrState* st, double2* out);
 int mc_launch_coil_sum(qmri_ctx* ctx, int ncoil, int g0, int cnt, const double2* xj, const double2* maps, const LsqrState* st, double2* t);
+// the image-side vector kernels of the LSQR on B slice vectors with one state each (mode 0: initial step, 1: iteration); partials: MC_PS per vector
+constexpr int MC_PS = 256, MC_PC = 64;   // fixed partial sums per slice vector (n complex) / per coil image (m complex)
+int mc_launch_ub(qmri_ctx* ctx, int mode, int B, double sr, const double2* z, const double2* x, const LsqrState* st, double2* ub, double2* v, double2* d,
+                 double* pb, double* pz);
+int mc_launch_dupd(qmri_ctx* ctx, int B, const double2* v, const double2* x, const LsqrState* st, double2* d, double* pd, double* px);
+int mc_launch_vupd(qmri_ctx* ctx, int mode, int B, double sr, const double2* t, const double2* ub, const double2* d, const LsqrState* st, double2* x,
+                   double2* v, double* pv);
 int qmri_lsqr_mc_batch_dev(qmri_ctx* ctx, int B, int ncoil, const double2* d_maps, const double2* d_y, const double2* d_z, double r, double tol, int maxit,
                            double2* d_x, int32_t* iters_out, int32_t* flags_out);
 
@@ -455,7 +465,38 @@ int qmri_cg_toep_batch_dev(qmri_ctx* ctx, int B, int ncoil, const double2* d_map
 // the x-update of the multi-coil loops by the solver of qmri_admm_params (LSQR or TOEPLITZ)
 int mc_xupdate_dev(qmri_ctx* ctx, int solver, int B, int ncoil, const double2* d_maps, const double2* d_y, const double2* d_z, double r, double tol, int maxit,
                    double2* d_x, int32_t* iters_out, int32_t* flags_out);
+// The multi-coil PnP-ADMM loop around a start image and an x-update (api_admm.cpp): what differs between the SENSE loop and the simultaneous
+// multi-slice loop (api_sms.cpp).  nsolve LSQR counts per x-update; B slice images go through Step 2.
+struct AdmmSolve {
+    int nsolve = 0;
+    std::function<int(double2* d_x)> start;
+    std::function<int(const double2* d_z, double2* d_x, int32_t* iters)> solve;
+};
+int mc_admm_check(qmri_ctx* ctx, const qmri_admm_params* prm);     // a Step 2 is configured and fits the operator; the parameters' ranges; the solver
+int mc_admm_loop(qmri_ctx* ctx, int B, const qmri_admm_params* prm, const AdmmSolve& sv, double2* d_x, int32_t* li_out, int li_stride);
 int toep_check_solver(qmri_ctx* ctx, int solver);   // QMRI_SOLVER_TOEPLITZ without an operator: QMRI_ERR_STATE, on a gridded one: QMRI_ERR_UNSUPPORTED; else QMRI_OK
+
+// ---------------------------------------------------------------------------------------------------
+// simultaneous multi-slice (SMS) groups (sms_kernels.hip, api_sms.cpp, sms_plan.h): the state of qmri_set_sms and the work
+// buffers of its solves.  It lives in the operator (OpHost), so replacing the operator drops it, as the sample weights.  Z = 0: not set.
+// ---------------------------------------------------------------------------------------------------
+struct SmsWork {
+    int Z = 0;
+    std::vector<double2> E;             // [Z][T] the caller's phases, E[t + T b]
+    bool on_device = false;             // d_E / d_frame hold E and the frame table (uploaded at the first call that needs them)
+    DevArr<double2> d_E;                // [Z][T]
+    DevArr<int32_t> d_frame;            // [m] frame of every sample, ABI order
+    DevArr<LsqrState> st;               // [G] the LSQR state of every group (McWork::st holds its copies, one per slice vector)
+    PinnedArr<LsqrState> hst;           // [G] pinned: iter / done / flag
+    DevArr<double2> acc;                // [G][ncoil][m] the sum over slices while chunks add to it
+    DevArr<double2> ex;                 // [max_batch][m] conj(E) u of one adjoint chunk
+    int pred = 8;                       // iterations enqueued before the first wait after the initial step
+};
+int sms_forward_dev(qmri_ctx* ctx, int G, int ncoil, const double2* d_maps, const double2* d_x, double2* d_y);      // y [G][ncoil][m] = A_sms x
+int sms_adjoint_dev(qmri_ctx* ctx, int G, int ncoil, const double2* d_maps, const double2* d_y, double2* d_x);      // x [G][Z][n] = A_sms^H y
+// LSQR on [A_sms; sqrt(r) I] x = [y; sqrt(r) z] for G groups from x0 = d_x (overwritten); the call shape of qmri_lsqr_mc_batch_dev, one count per group
+int sms_lsqr_dev(qmri_ctx* ctx, int G, int ncoil, const double2* d_maps, const double2* d_y, const double2* d_z, double r, double tol, int maxit,
+                 double2* d_x, int32_t* iters_out, int32_t* flags_out);
 
 // ---------------------------------------------------------------------------------------------------
 // context
@@ -471,6 +512,7 @@ struct OpHost {
     double2* d_tw = nullptr; int32_t* d_kslot = nullptr; double* d_ginv = nullptr;
     DevArr<double2> d_coils; int ncoil = 0;   // multi-coil extension: [ncoil][N*M] sensitivity maps (qmri_set_coils)
     McWork mc;                          // ... and the work buffers of its LSQR
+    SmsWork sms;                        // simultaneous multi-slice state (qmri_set_sms) and the buffers of its solves
     KsDev ks{};                         // k-space LSQR plan + state
     bool xhat_valid = false;            // ks.xhat holds the spectrum of d_x
     double ginv_r = -1.0;

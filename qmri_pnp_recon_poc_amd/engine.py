@@ -292,6 +292,15 @@ def nearest_atoms(lut, points):
     return (np.argmin(d, axis=1) + 1).astype(np.int32)
 
 
+def caipi_phases(T: int, Z: int):
+    """E [T, Z] of a simultaneous multi-slice acquisition with a CAIPIRINHA-style RF phase cycle: E[t, b] = exp(2 pi i b (t mod Z) / Z)."""
+    T, Z = int(T), int(Z)
+    if T < 1 or not (1 <= Z <= 8):
+        raise ValueError("T >= 1 and 1 <= Z <= 8 required")
+    t, b = np.meshgrid(np.arange(T) % Z, np.arange(Z), indexing="ij")
+    return np.exp(2j * np.pi * b * t / Z)
+
+
 def _hip_runtime():
     """The HIP runtime through ctypes, for the few calls that keep an intermediate result on the device between two library calls."""
     import os
@@ -421,6 +430,7 @@ class Engine:
         self._check(self.L.qmri_set_operator(self.h, int(N), int(M), int(s), int(T), Vf.ctypes.data_as(C.POINTER(C.c_double)),
                                              fp.ctypes.data_as(C.POINTER(C.c_int32)), k.ctypes.data_as(C.POINTER(C.c_int32)), int(max_batch)))
         self.N, self.M, self.s, self.T, self.m = int(N), int(M), int(s), int(T), int(fp[-1])
+        self.sms_Z = 0                     # (the library drops the simultaneous multi-slice phases with the operator)
 
     def set_trajectory(self, N, M, V, frame_ptr, omega, max_batch=1, width=0):
         """A non-Cartesian operator (qmri_set_operator_nufft): omega is m x 2 radians per pixel in [-pi, pi] (column 0 along N, column 1 along M),
@@ -441,6 +451,7 @@ class Engine:
                                                    fp.ctypes.data_as(C.POINTER(C.c_int32)), om.ctypes.data_as(C.POINTER(C.c_double)), int(max_batch),
                                                    C.byref(p)))
         self.N, self.M, self.s, self.T, self.m = int(N), int(M), int(s), int(T), int(fp[-1])
+        self.sms_Z = 0                     # (the library drops the simultaneous multi-slice phases with the operator)
 
     def forward(self, x):
         """y = F.forward(x)  (main_recon_tsmis_FFT.m:228).  x: [N,M,s] real or complex; single-precision input (float32 /
@@ -740,6 +751,98 @@ class Engine:
         self._check(self.L.qmri_pnp_admm_mc_batch(self.h, S, int(slices_per_launch), nc, _vp(mb), _vp(yb), C.byref(p), _vp(x0b), _vp(x),
                                                   li.ctypes.data_as(C.POINTER(C.c_int32))))
         return np.stack([x[b * n:(b + 1) * n].reshape((self.N, self.M, self.s), order="F") for b in range(S)]), li.reshape(-1)[: S * iters].reshape(S, iters)
+
+    # -- simultaneous multi-slice groups (extension, no reference counterpart) ---------------------------
+    def set_sms(self, E):
+        """E [T, Z] complex: the phase of slice b of a group in frame t (qmri_set_sms; caipi_phases makes the usual cycle).  1 <= Z <= 8, every value
+        finite, any modulus.  Attached to the operator in force and dropped when it is replaced; refused on an operator with a field map."""
+        E = np.asarray(E)
+        if E.ndim != 2 or E.shape[0] != self.T or not (1 <= E.shape[1] <= 8):
+            raise ValueError(f"E must be [{self.T}, Z] with 1 <= Z <= 8")
+        if not np.all(np.isfinite(E)):
+            raise ValueError("every value of E must be finite")
+        eb = _cbuf(E)
+        self._check(self.L.qmri_set_sms(self.h, int(E.shape[1]), _vp(eb)))
+        self.sms_Z = int(E.shape[1])
+
+    def clear_sms(self):
+        self._check(self.L.qmri_set_sms(self.h, 0, None))
+        self.sms_Z = 0
+
+    def _sms_stack(self, maps, y=None):
+        """maps [G, Z, N, M, ncoil], y [G, m, ncoil] -> (G, Z, ncoil, maps buffer, y buffer) in the library's group-major layouts."""
+        maps = np.asarray(maps)
+        if maps.ndim != 5 or maps.shape[2:4] != (self.N, self.M) or maps.shape[0] < 1:
+            raise ValueError(f"maps must be [groups, Z, {self.N}, {self.M}, ncoil]")
+        G, Z, nc = maps.shape[0], maps.shape[1], maps.shape[4]
+        if Z != getattr(self, "sms_Z", 0):
+            raise ValueError(f"maps hold {Z} slices per group, set_sms was given {getattr(self, 'sms_Z', 0)}")
+        mb = np.concatenate([_cbuf(maps[g, b]) for g in range(G) for b in range(Z)])
+        yb = None
+        if y is not None:
+            y = np.asarray(y)
+            if y.shape != (G, self.m, nc):
+                raise ValueError(f"y must be [{G}, {self.m}, {nc}]")
+            yb = np.concatenate([_cbuf(y[g]) for g in range(G)])
+        return G, Z, nc, mb, yb
+
+    def _sms_images(self, a, G, Z, real_ok=False):
+        if a is None:
+            return None
+        a = np.asarray(a)
+        if a.shape != (G, Z, self.N, self.M, self.s):
+            raise ValueError(f"images must be [{G}, {Z}, {self.N}, {self.M}, {self.s}]")
+        if real_ok and not np.iscomplexobj(a):
+            return np.concatenate([np.ascontiguousarray(np.asarray(a[g, b], np.float64).ravel(order="F")) for g in range(G) for b in range(Z)])
+        return np.concatenate([_cbuf(a[g, b]) for g in range(G) for b in range(Z)])
+
+    def _sms_unstack(self, x, G, Z):
+        n = self.N * self.M * self.s
+        return np.stack([np.stack([x[(g * Z + b) * n:(g * Z + b + 1) * n].reshape((self.N, self.M, self.s), order="F") for b in range(Z)])
+                         for g in range(G)])
+
+    def forward_sms(self, maps, x):
+        """y[g, :, j] = sum_b E[t(.), b] F.forward(maps[g, b, ..., j] * x[g, b]): maps [G, Z, N, M, ncoil], x [G, Z, N, M, s] (real or complex)
+        -> [G, m, ncoil] complex (qmri_forward_sms)."""
+        G, Z, nc, mb, _ = self._sms_stack(maps)
+        xb = self._sms_images(x, G, Z, real_ok=True)
+        y = np.empty(G * nc * self.m, np.complex128)
+        self._check(self.L.qmri_forward_sms(self.h, G, nc, _vp(mb), _vp(xb), int(np.iscomplexobj(xb)), _vp(y)))
+        return np.stack([y[g * nc * self.m:(g + 1) * nc * self.m].reshape((self.m, nc), order="F") for g in range(G)])
+
+    def adjoint_sms(self, maps, y):
+        """x[g, b] = sum_j conj(maps[g, b, ..., j]) * F.adjoint(conj(E[t(.), b]) * y[g, :, j]): [G, Z, N, M, s] (qmri_adjoint_sms)."""
+        G, Z, nc, mb, yb = self._sms_stack(maps, y)
+        x = np.empty(G * Z * self.N * self.M * self.s, np.complex128)
+        self._check(self.L.qmri_adjoint_sms(self.h, G, nc, _vp(mb), _vp(yb), _vp(x)))
+        return self._sms_unstack(x, G, Z)
+
+    def xupdate_sms(self, maps, y, z, r, tol=1e-4, maxit=100, x0=None):
+        """The joint x-update of G groups of Z simultaneously excited slices: x = lsqr(afun_sms, [y; sqrt(r) z], tol, maxit, [], [], x0) per group.
+        maps [G, Z, N, M, ncoil], y [G, m, ncoil], z / x0 [G, Z, N, M, s].  Returns (x [G, Z, N, M, s], iters [G], flags [G])."""
+        G, Z, nc, mb, yb = self._sms_stack(maps, y)
+        zb, x0b = self._sms_images(z, G, Z), self._sms_images(x0, G, Z)
+        if zb is None:
+            raise ValueError("z must be given")
+        x = np.empty(G * Z * self.N * self.M * self.s, np.complex128)
+        it, fl = np.zeros(G, np.int32), np.zeros(G, np.int32)
+        ip = C.POINTER(C.c_int32)
+        self._check(self.L.qmri_xupdate_sms(self.h, G, nc, _vp(mb), _vp(yb), _vp(zb), float(r), float(tol), int(maxit), _vp(x0b), _vp(x),
+                                            it.ctypes.data_as(ip), fl.ctypes.data_as(ip)))
+        return self._sms_unstack(x, G, Z), it, fl
+
+    def pnp_admm_sms(self, maps, y, groups_per_launch=1, gamma=0.05, iters=100, cg_tol=1e-4, cg_maxit=100, multi_level=False, noise_std=0.01, x0=None,
+                     tsmi_domain="real", solver="lsqr"):
+        """PnP-ADMM of G groups of Z simultaneously excited slices, groups_per_launch at a time (qmri_pnp_admm_sms): the loop of pnp_admm_mc_batch
+        with the joint x-update.  x0 None: adjoint_sms(maps, y).  Returns (X [G, Z, N, M, s], lsqr_iters [G, iters]).  Only solver="lsqr" is built."""
+        G, Z, nc, mb, yb = self._sms_stack(maps, y)
+        x0b = self._sms_images(x0, G, Z)
+        p = AdmmParams(float(gamma), int(iters), float(cg_tol), int(cg_maxit), solver_code(solver), denoiser_type(multi_level, tsmi_domain), float(noise_std), 0)
+        x = np.empty(G * Z * self.N * self.M * self.s, np.complex128)
+        li = np.zeros((G, max(iters, 1)), np.int32)
+        self._check(self.L.qmri_pnp_admm_sms(self.h, G, int(groups_per_launch), nc, _vp(mb), _vp(yb), C.byref(p), _vp(x0b), _vp(x),
+                                             li.ctypes.data_as(C.POINTER(C.c_int32))))
+        return self._sms_unstack(x, G, Z), li.reshape(-1)[: G * iters].reshape(G, iters)
 
     def coil_compress(self, y_mc, maps=None, noise_cov=None, nv=0, energy=0.99, shared=False):
         """Coil compression of a stack (extension, no reference counterpart; include/qmri.h qmri_coil_compress): y_mc [S, m, ncoil], maps

@@ -67,6 +67,7 @@ static std::vector<int32_t> g_refine;                  // 'set_refine' in force 
 static int g_ngroups = 0;                              // 'set_dictionary_groups' in force (G); 'set_dictionary' and a device switch drop them
 static bool g_llr = false;                             // 'set_llr' is in force: 'pnp_admm' needs no denoiser
 static bool g_wav = false;                             // 'set_wavelet' is in force: the same
+static mxArray* g_sms = nullptr;                       // 'set_sms' in force (E, T x Z complex double): re-attached whenever the operator is re-planned; a new operator drops it
 static const int DEFAULT_SLICES_PER_LAUNCH = 15;       // what a measurement matrix grows the plans to (the batched kernels' design point)
 
 static void drop(mxArray*& a) { if (a) { mxDestroyArray(a); a = nullptr; } }
@@ -77,6 +78,7 @@ static void cleanup() {
     drop(g_op.V); drop(g_op.fp); drop(g_op.kidx); drop(g_op.omega); g_op = OperatorSpec();
     drop(g_net.w); g_net = DenoiserSpec();
     drop(g_dict.D); drop(g_dict.normD); drop(g_dict.lut);
+    drop(g_sms);
     g_comp.clear();
     g_refine.clear();
     g_ngroups = 0;
@@ -167,11 +169,11 @@ static void plan_operator(int max_batch) {
         qmri_nufft_params np{};
         np.width = g_op.width;
         check(qmri_set_operator_nufft(ctx(), g_op.N, g_op.M, s, T, mxGetDoubles(g_op.V), (const int32_t*)mxGetData(g_op.fp), pairs.data(), max_batch, &np));
-        g_op.max_batch = max_batch;
-        return;
+    } else {
+        check(qmri_set_operator(ctx(), g_op.N, g_op.M, s, T, mxGetDoubles(g_op.V), (const int32_t*)mxGetData(g_op.fp), (const int32_t*)mxGetData(g_op.kidx), max_batch));
     }
-    check(qmri_set_operator(ctx(), g_op.N, g_op.M, s, T, mxGetDoubles(g_op.V), (const int32_t*)mxGetData(g_op.fp), (const int32_t*)mxGetData(g_op.kidx), max_batch));
     g_op.max_batch = max_batch;
+    if (g_sms) check(qmri_set_sms(ctx(), (int)mxGetN(g_sms), mxGetComplexDoubles(g_sms)));   // (the library drops the phases with the operator)
 }
 static void plan_denoiser(int max_batch) {
     check(qmri_set_denoiser(ctx(), &g_net.d, (const float*)mxGetData(g_net.w), mxGetNumberOfElements(g_net.w) * 4, g_net.H, g_net.W, max_batch));
@@ -223,6 +225,34 @@ static const void* noise_cov_arg(const mxArray* a, size_t ncoil, const char* id)
     return mxGetComplexDoubles(a);
 }
 
+// Simultaneous multi-slice groups (extension).  MATLAB shapes: maps N x M x ncoil x Z x G, y m x ncoil x G, images
+// N x M x s x Z x G (trailing singleton dimensions may be missing); Z is the column count of the E of 'set_sms'.
+static size_t dim_or_1(const mxArray* a, size_t k) { return k < mxGetNumberOfDimensions(a) ? mxGetDimensions(a)[k] : 1; }
+struct SmsShape { size_t ncoil, Z, G; };
+static SmsShape sms_shape(const mxArray* maps, const char* id) {
+    want(is_cdouble(maps) && mxGetNumberOfDimensions(maps) <= 5, id, "maps must be complex double, N x M x ncoil x Z x G");   // (what needs no plan comes first)
+    (void)image_numel();
+    want(g_sms != nullptr, "qmri:state", "no simultaneous multi-slice phases: call qmri_mex('set_sms', E) (qmri_set_sms) first");
+    SmsShape sh;
+    sh.Z = mxGetN(g_sms);
+    want(dim_or_1(maps, 0) == (size_t)g_op.N && dim_or_1(maps, 1) == (size_t)g_op.M, id, "maps must be complex double, N x M x ncoil x Z x G");
+    sh.ncoil = dim_or_1(maps, 2);
+    sh.G = dim_or_1(maps, 4);
+    want(sh.ncoil >= 1 && sh.ncoil <= 1024 && dim_or_1(maps, 3) == sh.Z && sh.G >= 1, id, "maps must be N x M x ncoil x Z x G with 1 <= ncoil <= 1024 and the Z of 'set_sms'");
+    return sh;
+}
+static void sms_want_y(const mxArray* y, const SmsShape& sh, const char* id) {
+    want(is_cdouble(y) && mxGetNumberOfElements(y) == operator_m() * sh.ncoil * sh.G && dim_or_1(y, 0) == operator_m(), id, "y must be complex double, m x ncoil x G");
+}
+static void sms_want_images(const mxArray* x, const SmsShape& sh, bool real_ok, const char* id) {
+    want(mxIsDouble(x) && (real_ok || mxIsComplex(x)) && mxGetNumberOfElements(x) == image_numel() * sh.Z * sh.G && dim_or_1(x, 0) == (size_t)g_op.N, id,
+         "the images must be complex double, N x M x s x Z x G");
+}
+static mxArray* sms_new_images(const SmsShape& sh) {
+    const mwSize dims[5] = {(mwSize)g_op.N, (mwSize)g_op.M, (mwSize)mxGetN(g_op.V), (mwSize)sh.Z, (mwSize)sh.G};
+    return mxCreateNumericArray(5, dims, mxDOUBLE_CLASS, mxCOMPLEX);
+}
+
 static void set_denoiser_from(const mxArray* w, const qmri_net_desc& d, int H, int W, int max_batch) {
     if (!mxIsSingle(w) || mxIsComplex(w)) mexErrMsgIdAndTxt("qmri:set_denoiser:type", "the weights must be a real single vector");
     drop(g_net.w);
@@ -268,6 +298,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         const int Mm = int_arg(prhs[2], 1, 65536, "qmri:set_operator:size", "M must be a positive integer");
         const int mb = nrhs > 6 ? int_arg(prhs[6], 1, 4096, "qmri:set_operator:size", "max_batch must be a positive integer") : 1;
         drop(g_op.V); drop(g_op.fp); drop(g_op.kidx); drop(g_op.omega); g_op = OperatorSpec();
+        drop(g_sms);
         g_op.N = Nn; g_op.M = Mm;
         g_op.V = keep(prhs[3]); g_op.fp = keep(prhs[4]); g_op.kidx = keep(prhs[5]);
         plan_operator(mb);
@@ -288,6 +319,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         const int mb = nrhs > 6 ? int_arg(prhs[6], 1, 4096, "qmri:set_trajectory:size", "max_batch must be a positive integer") : 1;
         const int wd = nrhs > 7 ? int_arg(prhs[7], 0, 64, "qmri:set_trajectory:size", "width must be a non-negative integer (0: the default)") : 0;
         drop(g_op.V); drop(g_op.fp); drop(g_op.kidx); drop(g_op.omega); g_op = OperatorSpec();
+        drop(g_sms);
         g_op.N = Nn; g_op.M = Mm; g_op.width = wd;
         g_op.V = keep(prhs[3]); g_op.fp = keep(prhs[4]); g_op.omega = keep(prhs[5]);
         plan_operator(mb);
@@ -564,6 +596,79 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         check(qmri_wavelet_prox(ctx(), (int)N, (int)M, (int)s, (int)S, cpx ? (const void*)mxGetComplexDoubles(prhs[1]) : (const void*)mxGetDoubles(prhs[1]),
                                 cpx ? 1 : 0, &wp, o1, o2, mxGetComplexDoubles(plhs[0]), mxGetDoubles(cm)));
         if (nlhs > 1) plhs[1] = cm; else mxDestroyArray(cm);
+    } else if (c == "set_sms") {                     // qmri_mex('set_sms', E): E T x Z complex double, the phase of slice b in frame t; [] clears
+        // extension (no reference counterpart; qmri_set_sms): attached to the operator in force, kept across the gateway's own
+        // re-plans, dropped by 'set_operator' / 'set_trajectory'
+        need(nrhs, 2, "qmri_mex('set_sms', E)");
+        if (mxIsEmpty(prhs[1])) {
+            (void)image_numel();
+            drop(g_sms);
+            check(qmri_set_sms(ctx(), 0, nullptr));
+        } else {
+            want(is_cdouble(prhs[1]) && mxGetNumberOfDimensions(prhs[1]) == 2, "qmri:set_sms:type", "E must be a complex double T x Z matrix (or [] to clear)");
+            want(mxGetN(prhs[1]) >= 1 && mxGetN(prhs[1]) <= 8, "qmri:set_sms:size", "E must be T x Z with T the rows of V and 1 <= Z <= 8");
+            const double* e = (const double*)mxGetComplexDoubles(prhs[1]);
+            for (size_t i = 0; i < 2 * mxGetNumberOfElements(prhs[1]); ++i) want(std::isfinite(e[i]), "qmri:set_sms:value", "every value of E must be finite");
+            (void)image_numel();
+            want(mxGetM(prhs[1]) == mxGetM(g_op.V), "qmri:set_sms:size", "E must be T x Z with T the rows of V and 1 <= Z <= 8");
+            check(qmri_set_sms(ctx(), (int)mxGetN(prhs[1]), mxGetComplexDoubles(prhs[1])));
+            drop(g_sms);
+            g_sms = keep(prhs[1]);
+        }
+    } else if (c == "forward_sms") {                 // y = qmri_mex('forward_sms', maps, x): m x ncoil x G
+        need(nrhs, 3, "y = qmri_mex('forward_sms', maps, x)");
+        const SmsShape sh = sms_shape(prhs[1], "qmri:forward_sms:size");
+        sms_want_images(prhs[2], sh, true, "qmri:forward_sms:size");
+        const mwSize dims[3] = {(mwSize)operator_m(), (mwSize)sh.ncoil, (mwSize)sh.G};
+        plhs[0] = mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxCOMPLEX);
+        const bool cpx = mxIsComplex(prhs[2]);
+        check(qmri_forward_sms(ctx(), (int)sh.G, (int)sh.ncoil, mxGetComplexDoubles(prhs[1]), cpx ? (const void*)mxGetComplexDoubles(prhs[2]) : (const void*)mxGetDoubles(prhs[2]),
+                               cpx ? 1 : 0, mxGetComplexDoubles(plhs[0])));
+    } else if (c == "adjoint_sms") {                 // x = qmri_mex('adjoint_sms', maps, y): N x M x s x Z x G
+        need(nrhs, 3, "x = qmri_mex('adjoint_sms', maps, y)");
+        const SmsShape sh = sms_shape(prhs[1], "qmri:adjoint_sms:size");
+        sms_want_y(prhs[2], sh, "qmri:adjoint_sms:size");
+        plhs[0] = sms_new_images(sh);
+        check(qmri_adjoint_sms(ctx(), (int)sh.G, (int)sh.ncoil, mxGetComplexDoubles(prhs[1]), mxGetComplexDoubles(prhs[2]), mxGetComplexDoubles(plhs[0])));
+    } else if (c == "xupdate_sms") {                 // [x, iters, flags] = qmri_mex('xupdate_sms', maps, y, z, r [, tol [, maxit [, x0]]])
+        need(nrhs, 5, "[x, iters, flags] = qmri_mex('xupdate_sms', maps, y, z, r [, tol [, maxit [, x0]]])");
+        want(mxIsDouble(prhs[4]) && !mxIsComplex(prhs[4]) && mxGetNumberOfElements(prhs[4]) == 1 && std::isfinite(mxGetScalar(prhs[4])) && mxGetScalar(prhs[4]) > 0,
+             "qmri:xupdate_sms:r", "r must be a positive real double scalar");
+        double tol = 1e-4;
+        if (nrhs > 5) {
+            want(mxIsDouble(prhs[5]) && !mxIsComplex(prhs[5]) && mxGetNumberOfElements(prhs[5]) == 1 && mxGetScalar(prhs[5]) >= 0, "qmri:xupdate_sms:tol", "tol must be a real double scalar >= 0");
+            tol = mxGetScalar(prhs[5]);
+        }
+        const int maxit = nrhs > 6 ? int_arg(prhs[6], 0, 1e6, "qmri:xupdate_sms:maxit", "maxit must be a non-negative integer") : 100;
+        const SmsShape sh = sms_shape(prhs[1], "qmri:xupdate_sms:size");
+        sms_want_y(prhs[2], sh, "qmri:xupdate_sms:size");
+        sms_want_images(prhs[3], sh, false, "qmri:xupdate_sms:size");
+        const bool has_x0 = nrhs > 7 && !mxIsEmpty(prhs[7]);
+        if (has_x0) sms_want_images(prhs[7], sh, false, "qmri:xupdate_sms:size");
+        plhs[0] = sms_new_images(sh);
+        mxArray* it = mxCreateNumericMatrix(sh.G, 1, mxINT32_CLASS, mxREAL);
+        mxArray* fl = mxCreateNumericMatrix(sh.G, 1, mxINT32_CLASS, mxREAL);
+        check(qmri_xupdate_sms(ctx(), (int)sh.G, (int)sh.ncoil, mxGetComplexDoubles(prhs[1]), mxGetComplexDoubles(prhs[2]), mxGetComplexDoubles(prhs[3]), mxGetScalar(prhs[4]),
+                               tol, maxit, has_x0 ? mxGetComplexDoubles(prhs[7]) : nullptr, mxGetComplexDoubles(plhs[0]), (int32_t*)mxGetData(it), (int32_t*)mxGetData(fl)));
+        if (nlhs > 1) plhs[1] = it; else mxDestroyArray(it);
+        if (nlhs > 2) plhs[2] = fl; else mxDestroyArray(fl);
+    } else if (c == "pnp_admm_sms") {                // [x, lsqr_iters] = qmri_mex('pnp_admm_sms', maps, y, param_struct [, X0 [, groups_per_launch]])
+        need(nrhs, 4, "[x, lsqr_iters] = qmri_mex('pnp_admm_sms', maps, y, param [, X0 [, groups_per_launch]])");
+        want(mxIsStruct(prhs[3]), "qmri:pnp_admm_sms:type", "param must be a struct");
+        const qmri_admm_params p = admm_params(prhs[3], false);
+        const int gpl = nrhs > 5 ? int_arg(prhs[5], 1, 4096, "qmri:pnp_admm_sms:groups", "groups_per_launch must be a positive integer") : 1;
+        const SmsShape sh = sms_shape(prhs[1], "qmri:pnp_admm_sms:size");
+        sms_want_y(prhs[2], sh, "qmri:pnp_admm_sms:size");
+        const bool has_x0 = nrhs > 4 && !mxIsEmpty(prhs[4]);
+        if (has_x0) sms_want_images(prhs[4], sh, false, "qmri:pnp_admm_sms:size");
+        want(g_net.w != nullptr || g_llr || g_wav, "qmri:state", "no denoiser: call qmri_mex('set_denoiser' | 'load_onnx', ...) (qmri_make_net), qmri_mex('set_llr', ...) (qmri_make_llr) or qmri_mex('set_wavelet', ...) (qmri_make_wavelet) first");
+        const int it = p.iters > 0 ? p.iters : 1;
+        plhs[0] = sms_new_images(sh);
+        mxArray* li = mxCreateNumericMatrix(it, sh.G, mxINT32_CLASS, mxREAL);
+        reserve((int)(std::min<size_t>(gpl, sh.G) * sh.Z), true, true);      // a launch holds groups_per_launch x Z slice images: the plans grow to it
+        check(qmri_pnp_admm_sms(ctx(), (int)sh.G, gpl, (int)sh.ncoil, mxGetComplexDoubles(prhs[1]), mxGetComplexDoubles(prhs[2]), &p,
+                                has_x0 ? mxGetComplexDoubles(prhs[4]) : nullptr, mxGetComplexDoubles(plhs[0]), (int32_t*)mxGetData(li)));
+        if (nlhs > 1) plhs[1] = li; else mxDestroyArray(li);
     } else if (c == "prepare_normal_fm") {           // info = qmri_mex('prepare_normal_fm' [, nseg [, tol]]): the Toeplitz normal operator of the attached map
         const qmri_offres_normal_params np = normal_fm_params(nrhs > 1 ? prhs[1] : nullptr, nrhs > 2 ? prhs[2] : nullptr, "qmri:prepare_normal_fm:nseg",
                                                               "qmri:prepare_normal_fm:tol");     // (the argument checks come first: they need no operator)
