@@ -1,6 +1,7 @@
 // api_dcf.cpp -- density compensation for trajectory operators: qmri_nufft_dcf (Pipe-Menon weights on the plan's own kernel),
 // qmri_set_sample_weights, and the weighted adjoints qmri_adjoint_w(_dev, _mc).  The iteration's kernels are in dcf_kernels.hip; the multiply by w is
-// fused into the staging of k_nu_spread (nufft_kernels.hip).  Every refusal is decided on the host before the device is selected.
+// fused into the staging of k_nu_spread (nufft_kernels.hip).  The kernel sum and the scale kappa of the weights are nufft_plan.h's.  Every refusal is
+// decided on the host before the device is selected.
 #include <cmath>
 
 #include "qmri_internal.h"
@@ -23,19 +24,6 @@ int require_weights(qmri_ctx* ctx, const char* what) {
     qmri_set_error(ctx, "%s: no sample weights attached: call qmri_nufft_dcf or qmri_set_sample_weights first", what);
     return QMRI_ERR_STATE;
 }
-// the host twin of nu_phi (nufft_device.h)
-double phi_host(double d, double hw, double beta) {
-    const double z = d / hw, t = 1.0 - z * z;
-    return t >= 0.0 ? std::exp(beta * (std::sqrt(t) - 1.0)) : 0.0;
-}
-// I = sum_k psi(k) over the window [k0, k0 + w) of a sample at u = 0, k0 = ceil(-w / 2) as nu_k0 gives it
-double kernel_sum(int w, double beta) {
-    const double hw = 0.5 * w;
-    const int k0 = (int)std::ceil(0.0 - hw);
-    double a = 0.0;
-    for (int i = 0; i < w; ++i) a += phi_host(0.0 - (double)(k0 + i), hw, beta);
-    return a;
-}
 int ensure_weight_array(qmri_ctx* ctx) {
     NufftHost& h = ctx->op.nu;
     QMRI_TRY(h.d_w.ensure(ctx, (size_t)ctx->op.m));
@@ -55,9 +43,7 @@ extern "C" int qmri_nufft_dcf(qmri_ctx* ctx, const qmri_dcf_params* p, double* w
         tol = p->tol;
     }
     OpHost& o = ctx->op;
-    // one factor per axis: the kernel is the same along both, the grid sides are not (they enter through T / 4 cells per image cell alone)
-    const double I1 = kernel_sum(o.nu.w, o.nu.beta), I2 = kernel_sum(o.nu.w, o.nu.beta);
-    const double kappa = 0.25 * (double)o.T * (I1 * I1) * (I2 * I2);
+    const double kappa = nuplan::dcf_kappa(o.T, o.nu.w, o.nu.beta);
     QMRI_HIP(ctx, hipSetDevice(ctx->device));
     QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     o.nu.w_set = false;

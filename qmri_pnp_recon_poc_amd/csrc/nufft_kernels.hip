@@ -298,8 +298,6 @@ int launch_interp(qmri_ctx* ctx, const NufftDev& nu, int B, const double2* S, do
 
 }  // namespace
 
-bool nufft_kernel_ok(int w) { return w >= 2 && w <= NU_WMAX; }
-
 NufftDev nufft_dev_view(const qmri_ctx* ctx) { return nufft_dev(ctx); }
 
 // the half-bin ramps of k_nu_pre / k_nu_post without the deapodisation: x [B][n] -> g [B][4][n] and back (toep_kernels.hip)

@@ -56,6 +56,10 @@ void qmri_set_error(qmri_ctx* ctx, const char* fmt, ...);
 #include "refine_plan.h"
 // The chunk schedule, frame table and partial-sum layout of a simultaneous multi-slice solve, in plain C++ (sms_plan.h).
 #include "sms_plan.h"
+// The plan of a trajectory (NUFFT) operator, its kernel constants, the exact spiral and the density compensation's kernel sums, in plain C++ (nufft_plan.h; DESIGN.md sections 14, 21).
+#include "nufft_plan.h"
+// The field-map histogram, segment times, coefficient system and QR tables of the off-resonance correction, in plain C++ (offres_plan.h; DESIGN.md sections 22, 23).
+#include "offres_plan.h"
 
 // ---------------------------------------------------------------------------------------------------
 // A/B and diagnostic switches ("knobs").  ONE environment variable, QMRI_DEBUG="name=value,name=value" (read once per process), and
@@ -358,15 +362,9 @@ struct WavState { bool on = false; double tau = 0.0; int levels = 3, filter = QM
 int wav_prox_dev(qmri_ctx* ctx, const WavPlan& pl, int B, const double2* d_x, const double2* d_u, double2* d_out, double* d_cmax);
 
 // ---------------------------------------------------------------------------------------------------
-// trajectory (NUFFT) operator (nufft_kernels.hip, api_nufft.cpp).  Planned once on the host per qmri_set_operator_nufft:
-// samples sorted by the 16 x 16 tile of the 2N x 2M oversampled grid that holds their position ("bins"), and for the output-driven spreading the
-// list of samples each tile's kernel windows reach, cut into segments of <= NU_SEG samples (knob nufft_seg).
+// trajectory (NUFFT) operator (nufft_kernels.hip, api_nufft.cpp).  Planned once on the host per qmri_set_operator_nufft by
+// nufft_plan.h (nu_plan: NU_TB, NuSeg, NuRed; knob nufft_seg): the device's view of the plan and the arrays the operator owns.
 // ---------------------------------------------------------------------------------------------------
-constexpr int NU_TB = 16;        // tile side (oversampled grid points) of the spreading; 2N and 2M are multiples of it for every supported side
-constexpr int NU_SEG = 512;      // samples per spreading segment by default (a heavier tile is split; its partial tiles are summed in segment order)
-constexpr int NU_WMAX = 16;      // widest kernel
-struct NuSeg { int32_t tile, b, e, slot; };      // tile index (t1 * ntile2 + t2), list range, partial slot (-1: the segment writes the grid itself)
-struct NuRed { int32_t tile, slot0, nslot, pad; };
 struct NufftDev {
     int N, M, s, T, m, w;
     double beta, hw;                             // kernel exp(beta (sqrt(1 - (d / hw)^2) - 1)), hw = w / 2
@@ -448,7 +446,6 @@ int offres_ncoefficients_dev(qmri_ctx* ctx, int L, int nb, const double2* d_dh, 
                              const double* d_ts, double* d_c, OffresFit* fit);
 void offres_drop_normal(NufftHost& h);             // forgets the field-aware transform and frees its device buffers (K^, phase maps, staging)
 int nufft_check_gridded(qmri_ctx* ctx, const char* what, const char* instead);   // QMRI_ERR_UNSUPPORTED on a trajectory operator, else QMRI_OK
-bool nufft_kernel_ok(int w);
 NufftDev nufft_dev_view(const qmri_ctx* ctx);
 int nufft_launch_ramps(qmri_ctx* ctx, int B, const double2* x, double2* g);      // k_nu_pre without 1 / Phi:  x [B][n] -> g [B][4][n]
 int nufft_launch_unramps(qmri_ctx* ctx, int B, const double2* g, double2* x);    // k_nu_post without 1 / Phi

@@ -57,7 +57,7 @@ def nudft_adjoint(y, omega, V, frame_ptr, N, M):
 
 def deapodisation(L, width, beta):
     """1 / Phi(p) at the centred index p = n - L/2, n < L:  Phi(p) = int_{-w/2}^{w/2} phi(u) cos(2 pi u p / (2L)) du by the 200-point
-    Gauss-Legendre quadrature of the host plan (deapodisation() of csrc/api_nufft.cpp)."""
+    Gauss-Legendre quadrature of the host plan (deapodisation() of csrc/nufft_plan.h)."""
     gx, gw = np.polynomial.legendre.leggauss(200)
     hw = 0.5 * width
     p = np.arange(L) - L // 2

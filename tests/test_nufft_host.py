@@ -224,7 +224,7 @@ def test_gridding_restatement_stays_inside_the_stated_bound(gridding_case):
 
 
 def test_gridding_restatement_default_width_and_on_grid_points(gridding_case):
-    """width 0 is the plan's default (NU_WDEF of api_nufft.cpp); on-grid points reproduce the unitary DFT to that width's error."""
+    """width 0 is the plan's default (NU_WDEF of nufft_plan.h); on-grid points reproduce the unitary DFT to that width's error."""
     import dcf_ref as D
     c = gridding_case
     assert np.array_equal(R.gridded_forward(c["x"], c["om"], c["V"], c["fp"], 0), R.gridded_forward(c["x"], c["om"], c["V"], c["fp"], D.plan_width(0)))
