@@ -780,6 +780,48 @@ int qmri_dict_simulate_sp(qmri_ctx* ctx, int K, int T, const double* alpha, cons
 int qmri_dict_simulate_sp_dev(qmri_ctx* ctx, int K, int T, const double* alpha, const double* tr, const double* te, const double* d_t1, const double* d_t2,
                               const double* d_b1, const qmri_epg_params* p, const qmri_epg_profile* sp, void* d_F_out);
 
+/* ---- EPG fingerprint derivatives and their Cramer-Rao bound (extension, no reference counterpart, parity unpinned) ---- */
+/* The fingerprints of qmri_dict_simulate together with their derivatives with respect to theta = (T1, T2) (nparams P = 2) or (T1, T2, b1) (P = 3),
+ * by forward-mode differentiation of that recursion, and the Cramer-Rao bound they give per atom -- in ONE launch, so that no K x T x (1 + P) array
+ * has to exist for the bound.  Next to F+, F-, Z every parameter carries a tangent of the same shape, real and zero at the start:
+ *   Inversion: with e = exp(-TI / T1) and e' = e TI / T1^2 the T1 tangent's Z_0 <- (-inv_eff) e' - e'.
+ *   1. RF.  Every tangent takes the rotation of the state.  The b1 tangent adds, from the state (p, m, z) before the pulse,
+ *        alpha_t (-(s / 2) (p + m) + c z) to F+ and to F-,   alpha_t (-(c / 2) (p + m) - s z) to Z.
+ *   2., 4. Relaxation over D.  With E1 = exp(-D / T1), E2 = exp(-D / T2), E1' = E1 D / T1^2, E2' = E2 D / T2^2 the tangents scale by E2 / E2 / E1
+ *      as the state does; the T2 tangent adds E2' (F+, F-) and the T1 tangent E1' Z of the state before its scaling, and the T1 tangent's Z_0
+ *      subtracts E1'.
+ *   3. Signal: dF[q][k, t] = the F+_0 of tangent q.    5. Spoiler: the lane moves of the state on every tangent.
+ * F has the bits of qmri_dict_simulate.  The bound: per atom J = [F, d_1 F, ..., d_P F], T x (1 + P); with a real subspace V [T x s] (s > 0; the V
+ * of qmri_dict_compress) J <- V^T J, s x (1 + P).  G = J^T J, every sum in ascending row order from 0; d = sqrt(diag G); Gn = G / (d d^T); Cholesky of
+ * Gn.  An atom with a diagonal entry of G that is non-finite or <= 0, or a pivot (the number under a square root) that is not > 1e-10, is SINGULAR:
+ * flag 1 and every bound +inf.  Otherwise flag 0 and crb[k][q] = [Gn^-1]_qq / d_q^2, q = 0 .. P, entry 0 the proton density's.  For a pixel
+ * x = rho a_k + noise of variance sigma^2 per real and imaginary part and channel (a_k the unnormalised, compressed atom; rho the match's pd):
+ *   sigma(theta_q) >= sigma sqrt(crb[k][q]) / |rho|,   sigma(Re rho) >= sigma sqrt(crb[k][0]).
+ * s < 1 + P is not refused: it yields SINGULAR atoms.  All arithmetic is fp64; no atomics; an atom's bits depend neither on K nor on its position
+ * in the call, and the bound's bits do not depend on which of the other outputs are asked for.  Integration over a slice profile
+ * (qmri_dict_simulate_sp) is out of scope: there is no _sp form of this call. */
+typedef struct {
+    int32_t nparams;       /* P: 2 (T1, T2) or 3 (T1, T2, b1) */
+    int32_t s;             /* 0: the bound of the uncompressed fingerprints; 1..16: of their projection on V */
+    const double* V;       /* host array, T x s column-major, finite; used when s > 0 */
+    int32_t reserved[4];   /* zero */
+} qmri_epg_grad_params;
+/* Host arrays.  The inputs of qmri_dict_simulate; F_out (nullable): K x T column-major; dF_out (nullable): P arrays of K x T, parameter q at
+ * q K T; both fp64 or rounded once to fp32 as p->out_is_f64 says; crb_out (nullable): K x (1 + P) fp64, atom k at k (1 + P); flags_out: K.  At
+ * least one output is given; crb_out and flags_out go together.  Refusals: those of qmri_dict_simulate (F_out's replaced by: all outputs NULL,
+ * crb_out without flags_out or the reverse), and a NULL grad-params struct, nparams outside {2, 3}, s outside 0..16, s > 0 with a NULL V, a
+ * non-finite entry of V: QMRI_ERR_INVALID_ARG, decided on the host before the device is selected (ctx == NULL: the message of the first failing
+ * check in qmri_last_error(NULL)).  Returns after its kernel has finished. */
+int qmri_dict_simulate_grad(qmri_ctx* ctx, int K, int T, const double* alpha, const double* tr, const double* te, const double* t1, const double* t2,
+                            const double* b1, const qmri_epg_params* p, const qmri_epg_grad_params* gp, void* F_out, void* dF_out, double* crb_out,
+                            int32_t* flags_out);
+/* The same with t1, t2, b1 and the four outputs on ctx's device; alpha, tr, te, p, gp and gp->V stay on the host.  Same bits as the host-array
+ * call.  For an atom this route cannot refuse (see qmri_dict_simulate_dev) the kernel writes NaN in every frame of F and dF, NaN in its crb, and
+ * flag 2 -- for that atom and no other. */
+int qmri_dict_simulate_grad_dev(qmri_ctx* ctx, int K, int T, const double* alpha, const double* tr, const double* te, const double* d_t1,
+                                const double* d_t2, const double* d_b1, const qmri_epg_params* p, const qmri_epg_grad_params* gp, void* d_F_out,
+                                void* d_dF_out, double* d_crb_out, int32_t* d_flags_out);
+
 /* ---- field map from multi-echo images (extension, no reference counterpart, parity unpinned) ---- */
 /* qmri_set_field_map takes its map f from the caller; this call makes one from L gradient-echo images per slice, by the regularised estimator of
  * Funai, Fessler, Yeo, Olafsson and Noll (IEEE TMI 2008): a penalised cosine fit over all echo pairs and coils, minimised by separable quadratic

@@ -1,4 +1,4 @@
-// api_epg.cpp -- C ABI of the FISP dictionary simulation by extended phase graphs, plain and over a slice profile (include/qmri.h; kernels:
+// api_epg.cpp -- C ABI of the FISP dictionary simulation by extended phase graphs, plain, over a slice profile and with derivatives (include/qmri.h; kernels:
 // epg_kernels.hip).  An EXTENSION with no reference counterpart.  Every refusal is decided here, on the host, before the device is selected; with ctx == NULL the message of the first
 // failing check is left in qmri_last_error(NULL), so the argument rules can be exercised on a machine without a GPU.
 #include <algorithm>
@@ -11,11 +11,11 @@ namespace {
 constexpr int EPG_MAX_T = 1024, EPG_MAX_S = 256, EPG_MAX_Q = 64;
 
 // QMRI_OK, or the code of the first failing check with its message set on ctx (ctx may be NULL; ctx_check comes after
-// these).  host_atoms: t1 / t2 / b1 can be read here
+// these).  host_atoms: t1 / t2 / b1 can be read here; need_F: F_out is the call's one output (the derivative calls have their own output rules)
 int epg_checks(qmri_ctx* ctx, int K, int T, const double* alpha, const double* tr, const double* te, const double* t1, const double* t2, const double* b1,
-               const qmri_epg_params* p, const void* F_out, bool host_atoms) {
+               const qmri_epg_params* p, const void* F_out, bool host_atoms, bool need_F = true) {
     QMRI_CHECK_ARG(ctx, p, "simulation params must not be NULL");
-    QMRI_CHECK_ARG(ctx, alpha && tr && te && t1 && t2 && F_out, "alpha / tr / te / t1 / t2 / F_out must not be NULL");
+    QMRI_CHECK_ARG(ctx, alpha && tr && te && t1 && t2 && (F_out || !need_F), "alpha / tr / te / t1 / t2 / F_out must not be NULL");
     QMRI_CHECK_ARG(ctx, K >= 1 && K <= (1 << 30), "K must satisfy 1 <= K <= 2^30");
     QMRI_CHECK_ARG(ctx, T >= 1 && T <= EPG_MAX_T, "T must satisfy 1 <= T <= 1024");
     QMRI_CHECK_ARG(ctx, p->nstates >= 1 && p->nstates <= EPG_MAX_S, "nstates must satisfy 1 <= nstates <= 256");
@@ -57,6 +57,23 @@ int epg_profile_checks(qmri_ctx* ctx, int T, const qmri_epg_profile* sp) {
     return QMRI_OK;
 }
 
+// the rules of the derivative call's own arguments (ctx may be NULL)
+int epg_grad_checks(qmri_ctx* ctx, int T, const qmri_epg_grad_params* gp, const void* F_out, const void* dF_out, const double* crb_out,
+                    const int32_t* flags_out) {
+    QMRI_CHECK_ARG(ctx, gp, "grad params must not be NULL");
+    QMRI_CHECK_ARG(ctx, F_out || dF_out || crb_out || flags_out, "at least one of F_out / dF_out / crb_out must be given");
+    QMRI_CHECK_ARG(ctx, !crb_out == !flags_out, "crb_out and flags_out go together");
+    QMRI_CHECK_ARG(ctx, gp->nparams == 2 || gp->nparams == 3, "nparams must be 2 or 3");
+    QMRI_CHECK_ARG(ctx, gp->s >= 0 && gp->s <= 16, "s must satisfy 0 <= s <= 16");
+    for (int32_t r : gp->reserved) QMRI_CHECK_ARG(ctx, r == 0, "reserved must be zero");
+    if (gp->s > 0) {
+        QMRI_CHECK_ARG(ctx, gp->V, "V must not be NULL when s > 0");
+        const size_t n = (size_t)T * (size_t)gp->s;
+        for (size_t i = 0; i < n; ++i) QMRI_CHECK_ARG(ctx, std::isfinite(gp->V[i]), "V must be finite in every entry");
+    }
+    return QMRI_OK;
+}
+
 int ctx_check(qmri_ctx* ctx) {
     if (!ctx) { qmri_set_error(nullptr, "invalid argument: ctx must not be NULL"); return QMRI_ERR_INVALID_ARG; }
     return QMRI_OK;
@@ -84,6 +101,34 @@ int epg_run(qmri_ctx* ctx, int K, int T, const double* alpha, const double* tr, 
     else QMRI_TRY(epg_simulate_dev(ctx, K, T, ds, d_t1, d_t2, d_b1, p, const_timing, d_F));
     QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return QMRI_OK;
+}
+
+// the derivative call: the schedule followed by V on the device and the launch; the stream is idle on return
+int epg_grad_run(qmri_ctx* ctx, int K, int T, const double* alpha, const double* tr, const double* te, const double* d_t1, const double* d_t2,
+                 const double* d_b1, const qmri_epg_params& p, const qmri_epg_grad_params& gp, void* d_F, void* d_dF, double* d_crb, int32_t* d_flags) {
+    std::vector<double> sched((size_t)3 * T + (size_t)T * gp.s);
+    bool const_timing = true;
+    for (int t = 0; t < T; ++t) {
+        const_timing = const_timing && tr[t] == tr[0] && te[t] == te[0];
+        sched[t] = alpha[t]; sched[T + t] = tr[t]; sched[2 * T + t] = te[t];
+    }
+    if (gp.s > 0) std::copy_n(gp.V, (size_t)T * gp.s, sched.data() + (size_t)3 * T);
+    DevBuf<double> ds;
+    QMRI_TRY(ds.ensure(ctx, sched.size()));
+    QMRI_HIP(ctx, hipMemcpyAsync(ds.p, sched.data(), sched.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    QMRI_TRY(epg_simulate_grad_dev(ctx, K, T, gp.nparams, gp.s, ds, d_t1, d_t2, d_b1, p, const_timing, d_F, d_dF, d_crb, d_flags));
+    QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return QMRI_OK;
+}
+
+// the checks of both derivative entry points: the derivative arguments first (T bounds the read of V), then the rules of the plain call
+int epg_grad_all_checks(qmri_ctx* ctx, int K, int T, const double* alpha, const double* tr, const double* te, const double* t1, const double* t2,
+                        const double* b1, const qmri_epg_params* p, const qmri_epg_grad_params* gp, const void* F_out, const void* dF_out,
+                        const double* crb_out, const int32_t* flags_out, bool host_atoms) {
+    QMRI_CHECK_ARG(ctx, p, "simulation params must not be NULL");
+    QMRI_CHECK_ARG(ctx, T >= 1 && T <= EPG_MAX_T, "T must satisfy 1 <= T <= 1024");
+    QMRI_TRY(epg_grad_checks(ctx, T, gp, F_out, dF_out, crb_out, flags_out));
+    return epg_checks(ctx, K, T, alpha, tr, te, t1, t2, b1, p, F_out, host_atoms, false);
 }
 
 // the device-array and the host-array route behind all four entry points.  with_profile: the _sp calls, whose sp is checked (a NULL one is a
@@ -138,6 +183,50 @@ extern "C" int qmri_dict_simulate_sp_dev(qmri_ctx* ctx, int K, int T, const doub
 extern "C" int qmri_dict_simulate_sp(qmri_ctx* ctx, int K, int T, const double* alpha, const double* tr, const double* te, const double* t1,
                                      const double* t2, const double* b1, const qmri_epg_params* p, const qmri_epg_profile* sp, void* F_out) {
     return simulate_host(ctx, K, T, alpha, tr, te, t1, t2, b1, p, sp, true, F_out);
+}
+
+extern "C" int qmri_dict_simulate_grad_dev(qmri_ctx* ctx, int K, int T, const double* alpha, const double* tr, const double* te, const double* d_t1,
+                                           const double* d_t2, const double* d_b1, const qmri_epg_params* p, const qmri_epg_grad_params* gp, void* d_F_out,
+                                           void* d_dF_out, double* d_crb_out, int32_t* d_flags_out) {
+    QMRI_TRY(epg_grad_all_checks(ctx, K, T, alpha, tr, te, d_t1, d_t2, d_b1, p, gp, d_F_out, d_dF_out, d_crb_out, d_flags_out, false));
+    QMRI_TRY(ctx_check(ctx));
+    QMRI_HIP(ctx, hipSetDevice(ctx->device));
+    return epg_grad_run(ctx, K, T, alpha, tr, te, d_t1, d_t2, d_b1, *p, *gp, d_F_out, d_dF_out, d_crb_out, d_flags_out);
+}
+
+extern "C" int qmri_dict_simulate_grad(qmri_ctx* ctx, int K, int T, const double* alpha, const double* tr, const double* te, const double* t1,
+                                       const double* t2, const double* b1, const qmri_epg_params* p, const qmri_epg_grad_params* gp, void* F_out,
+                                       void* dF_out, double* crb_out, int32_t* flags_out) {
+    QMRI_TRY(epg_grad_all_checks(ctx, K, T, alpha, tr, te, t1, t2, b1, p, gp, F_out, dF_out, crb_out, flags_out, true));
+    QMRI_TRY(ctx_check(ctx));
+    QMRI_HIP(ctx, hipSetDevice(ctx->device));
+    const int NS = 1 + gp->nparams;
+    const size_t nF = (size_t)K * T * (p->out_is_f64 ? sizeof(double) : sizeof(float)), ndF = nF * (size_t)gp->nparams;
+    DevBuf<double> d1, d2, db, dcrb;
+    DevBuf<unsigned char> dF, ddF;
+    DevBuf<int32_t> dfl;
+    QMRI_TRY(d1.ensure(ctx, (size_t)K));
+    QMRI_TRY(d2.ensure(ctx, (size_t)K));
+    if (b1) QMRI_TRY(db.ensure(ctx, (size_t)K));
+    if (F_out) QMRI_TRY(dF.ensure(ctx, nF));
+    if (dF_out) QMRI_TRY(ddF.ensure(ctx, ndF));
+    if (crb_out) {
+        QMRI_TRY(dcrb.ensure(ctx, (size_t)K * NS));
+        QMRI_TRY(dfl.ensure(ctx, (size_t)K));
+    }
+    QMRI_HIP(ctx, hipMemcpyAsync(d1.p, t1, (size_t)K * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    QMRI_HIP(ctx, hipMemcpyAsync(d2.p, t2, (size_t)K * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (b1) QMRI_HIP(ctx, hipMemcpyAsync(db.p, b1, (size_t)K * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    QMRI_TRY(epg_grad_run(ctx, K, T, alpha, tr, te, d1, d2, db, *p, *gp, F_out ? dF.p : nullptr, dF_out ? ddF.p : nullptr, crb_out ? dcrb.p : nullptr,
+                          crb_out ? dfl.p : nullptr));
+    if (F_out) QMRI_HIP(ctx, hipMemcpyAsync(F_out, dF.p, nF, hipMemcpyDeviceToHost, ctx->stream));
+    if (dF_out) QMRI_HIP(ctx, hipMemcpyAsync(dF_out, ddF.p, ndF, hipMemcpyDeviceToHost, ctx->stream));
+    if (crb_out) {
+        QMRI_HIP(ctx, hipMemcpyAsync(crb_out, dcrb.p, (size_t)K * NS * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        QMRI_HIP(ctx, hipMemcpyAsync(flags_out, dfl.p, (size_t)K * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return QMRI_OK;
 }
 
 extern "C" int qmri_debug_epg_shift(qmri_ctx* ctx, int S, int nshift, const double* in, double* out) {

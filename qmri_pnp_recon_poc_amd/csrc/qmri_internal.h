@@ -322,6 +322,11 @@ int dsvd_project_dev(qmri_ctx* ctx, int K, int T, int s, const void* d_F, bool f
 int epg_atoms_per_workgroup(int S);      // atoms a workgroup simulates (= the contiguous run of its stores) with S states
 int epg_simulate_dev(qmri_ctx* ctx, int K, int T, const double* d_sched, const double* d_t1, const double* d_t2, const double* d_b1 /* or NULL */,
                      const qmri_epg_params& p, bool const_timing, void* d_F);
+// the fingerprints with their derivatives and the Cramer-Rao bound in one launch.  d_sched: alpha, tr, te, then V [T x sv]
+// column-major (sv = 0: none).  d_F, d_dF (nparams arrays of K x T) and the pair d_crb [K x (1 + nparams)] / d_flags [K] are each optional
+int epg_simulate_grad_dev(qmri_ctx* ctx, int K, int T, int nparams, int sv, const double* d_sched, const double* d_t1, const double* d_t2,
+                          const double* d_b1 /* or NULL */, const qmri_epg_params& p, bool const_timing, void* d_F, void* d_dF, double* d_crb,
+                          int32_t* d_flags);
 // the slice-profile-aware simulation.  d_sched: T frame records (alpha_t, tr_t, te_t, prof[t, 0 .. Q-1]), then weight [Q]
 int epg_sp_atoms_per_workgroup(int S, int Q);      // atoms a workgroup simulates with S states and Q sub-slices (1 when Q fills its groups)
 int epg_simulate_sp_dev(qmri_ctx* ctx, int K, int T, int Q, const double* d_sched, const double* d_t1, const double* d_t2,

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import AdmmParams, CcParams, CsmInfo, CsmParams, DcfInfo, DcfParams, DsvdInfo, DsvdParams, EpgParams, EpgProfile, FieldmapInfo, FieldmapParams, LlrParams, LrtvInfo, LrtvParams, NetDesc, NufftParams, OffresInfo, OffresNormalInfo, OffresNormalParams, OffresParams, Profile, WAVELET_FILTERS, WaveletParams
+from ._lib import AdmmParams, CcParams, CsmInfo, CsmParams, DcfInfo, DcfParams, DsvdInfo, DsvdParams, EpgGradParams, EpgParams, EpgProfile, FieldmapInfo, FieldmapParams, LlrParams, LrtvInfo, LrtvParams, NetDesc, NufftParams, OffresInfo, OffresNormalInfo, OffresNormalParams, OffresParams, Profile, WAVELET_FILTERS, WaveletParams
 
 ARCH_UNETRES, ARCH_SEQ_CONV = 0, 1
 SOLVER_LSQR, SOLVER_DIRECT = 0, 1
@@ -125,6 +125,29 @@ def slice_profile_arguments(slice_profile, slice_weights, T):
     if not (np.all(np.isfinite(prof)) and np.all(prof >= 0) and np.all(np.isfinite(w)) and np.all(w >= 0) and w.sum() > 0):
         raise ValueError("slice_profile and slice_weights must be finite and >= 0, and the weights must sum to more than 0")
     return prof, w, EpgProfile(Q, int(prof.ndim == 2), prof.ctypes.data, w.ctypes.data)
+
+
+def grad_arguments(wrt, V, outputs, T):
+    """The derivative arguments of Engine.simulate_dictionary_grad as the library takes them: (V buffer or None, EpgGradParams, outputs as a set).
+    wrt is ("t1", "t2") or ("t1", "t2", "b1"); V is None or a real [T, s] subspace with 1 <= s <= 16 (the V of compress_dictionary), finite;
+    outputs is a non-empty subset of ("F", "dF", "crb").  The buffer must outlive the call that takes the EpgGradParams."""
+    wrt = tuple(wrt)
+    if wrt not in (("t1", "t2"), ("t1", "t2", "b1")):
+        raise ValueError('wrt must be ("t1", "t2") or ("t1", "t2", "b1")')
+    outs = {outputs} if isinstance(outputs, str) else set(outputs)
+    if not outs or not outs <= {"F", "dF", "crb"}:
+        raise ValueError('outputs must be a non-empty subset of ("F", "dF", "crb")')
+    if V is None:
+        return None, EpgGradParams(len(wrt), 0, None), outs
+    if np.iscomplexobj(V):
+        raise ValueError("V must be real")
+    V = np.asarray(V, dtype=np.float64)
+    if V.ndim != 2 or V.shape[0] != T or not (1 <= V.shape[1] <= 16):
+        raise ValueError(f"V must have shape [T, s] with T = {T} and 1 <= s <= 16")
+    if not np.all(np.isfinite(V)):
+        raise ValueError("V must be finite")
+    Vb = np.ascontiguousarray(V.ravel(order="F"))
+    return Vb, EpgGradParams(len(wrt), V.shape[1], Vb.ctypes.data), outs
 
 
 def fieldmap_arguments(Y, echo_times, iters=0, beta=0.0, phase_sign=-1, f_init=None):
@@ -1435,6 +1458,37 @@ class Engine:
         else:
             self._check(self.L.qmri_dict_simulate_sp(self.h, K, T, _vp(a), _vp(trv), _vp(tev), _vp(T1), _vp(T2), _vp(B1), C.byref(p), C.byref(sp[2]), _vp(F)))
         return F.reshape((K, T), order="F")
+
+    def simulate_dictionary_grad(self, alpha, tr, te, t1, t2, b1=None, wrt=("t1", "t2"), V=None, outputs=("F", "dF", "crb"), nstates=32, inversion=True,
+                                 ti=0.0, inv_eff=1.0, dtype=np.float64):
+        """The fingerprints of simulate_dictionary with their derivatives and the Cramer-Rao bound they give, in one launch (extension, no
+        reference counterpart; include/qmri.h qmri_dict_simulate_grad).  The sequence and atom arguments are
+        simulate_dictionary's (no slice profile).  wrt: ("t1", "t2") or ("t1", "t2", "b1"), the P parameters.  V [T, s], s <= 16: the bound is that
+        of the fingerprints projected on V (the V of compress_dictionary); None: of the uncompressed ones.  outputs: which of "F", "dF", "crb" to
+        compute and return.  Returns dict(F [K, T] -- the bits of simulate_dictionary --, dF [P, K, T], both in dtype; crb [K, 1 + P] float64: a
+        pixel rho x atom k + noise of deviation sigma per real and imaginary part and channel has sigma(theta_q) >= sigma sqrt(crb[k, 1 + q]) /
+        |rho| and sigma(Re rho) >= sigma sqrt(crb[k, 0]); flags [K] int32: 0, or 1 for an atom whose Fisher matrix is singular (its crb is +inf)).
+        Entries that were not asked for are None.  Needs no operator."""
+        a, trv, tev, T1, T2, B1, p = simulation_arguments(alpha, tr, te, t1, t2, b1, nstates, inversion, ti, inv_eff, dtype)
+        K, T = T1.size, a.size
+        Vb, gp, outs = grad_arguments(wrt, V, outputs, T)
+        P, dt = gp.nparams, np.float64 if p.out_is_f64 else np.float32
+        F = np.empty(K * T, dt) if "F" in outs else None
+        dF = np.empty(P * K * T, dt) if "dF" in outs else None
+        crb = np.empty(K * (1 + P), np.float64) if "crb" in outs else None
+        flags = np.empty(K, np.int32) if "crb" in outs else None
+        self._check(self.L.qmri_dict_simulate_grad(self.h, K, T, _vp(a), _vp(trv), _vp(tev), _vp(T1), _vp(T2), _vp(B1), C.byref(p), C.byref(gp), _vp(F),
+                                                   _vp(dF), _vp(crb), _vp(flags)))
+        return {"F": None if F is None else F.reshape((K, T), order="F"),
+                "dF": None if dF is None else np.stack([dF[q * K * T:(q + 1) * K * T].reshape((K, T), order="F") for q in range(P)]),
+                "crb": None if crb is None else crb.reshape(K, 1 + P), "flags": flags}
+
+    def dictionary_crb(self, alpha, tr, te, t1, t2, b1=None, wrt=("t1", "t2"), V=None, nstates=32, inversion=True, ti=0.0, inv_eff=1.0):
+        """The Cramer-Rao bound of simulate_dictionary_grad alone: no K x T array is made, on the device or the host.  Returns dict(crb [K, 1 + P],
+        flags [K])."""
+        r = self.simulate_dictionary_grad(alpha, tr, te, t1, t2, b1=b1, wrt=wrt, V=V, outputs=("crb",), nstates=nstates, inversion=inversion, ti=ti,
+                                          inv_eff=inv_eff)
+        return {"crb": r["crb"], "flags": r["flags"]}
 
     def simulate_compress_dictionary(self, alpha, tr, te, t1, t2, b1=None, s=None, energy=None, s_max=16, nstates=32, inversion=True, ti=0.0,
                                      inv_eff=1.0, slice_profile=None, slice_weights=None):

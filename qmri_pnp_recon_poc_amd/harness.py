@@ -28,7 +28,7 @@ from __future__ import annotations
 
 import numpy as np
 
-__all__ = ["load_mat", "load_dictionary", "compress_dictionary", "simulate_dictionary", "estimate_b1", "load_tsmi", "crop_tsmi", "load_qmaps", "getmask_fromPD", "awgn_measured",
+__all__ = ["load_mat", "load_dictionary", "compress_dictionary", "simulate_dictionary", "uncertainty_maps", "estimate_b1", "load_tsmi", "crop_tsmi", "load_qmaps", "getmask_fromPD", "awgn_measured",
            "psnr", "ssim", "metrics", "recon_tsmis", "synthesize_tsmis", "training_volume", "save_training_pickle"]
 
 CROP = slice(3, 227)          # MATLAB (4:227): 230 -> 224                                       main_recon_tsmis_FFT.m:189,212
@@ -80,7 +80,7 @@ def compress_dictionary(dic, s=None, energy=None, s_max=16, device=0):
 
 
 def simulate_dictionary(alpha, tr, te, t1_grid, t2_grid, s=None, energy=None, nstates=32, inversion=True, ti=0.0, inv_eff=1.0, b1=None, s_max=16,
-                        device=0, b1_grid=None, slice_profile=None, slice_weights=None):
+                        device=0, b1_grid=None, slice_profile=None, slice_weights=None, crb=False):
     """A FISP-MRF dictionary from a flip-angle train: the fingerprints of every (T1, T2) of the grid by extended phase graphs
     (Engine.simulate_dictionary), then their SVD compression (Engine.compress_dictionary) on the same device buffer -- the K x T fingerprints
     never cross to the host.  An extension; the reference only loads compressed files.  The atoms are the ij-meshgrid of t1_grid and t2_grid as
@@ -92,8 +92,13 @@ def simulate_dictionary(alpha, tr, te, t1_grid, t2_grid, s=None, energy=None, ns
     recon_tsmis(..., b1_map=...) hands to the grouped match.
     slice_profile [Q] or [T, Q], slice_weights [Q] (default 1 / Q): every atom is integrated over that slice profile (Engine.simulate_dictionary;
     DESIGN.md section 26).  It composes with b1 and b1_grid -- the flip angle of sub-slice q is alpha_t b1 slice_profile[t, q] -- and leaves the
-    atom order, lut and groups unchanged."""
+    atom order, lut and groups unchanged.
+    crb=True: after the compression the Cramer-Rao bound of every atom in the dictionary's own subspace V (Engine.dictionary_crb, DESIGN.md
+    section 32; with respect to (T1, T2), and b1 as well with b1_grid) is added as crb [K, 1 + P] and crb_flags [K]; uncertainty_maps turns them
+    into per-pixel standard deviations.  Not available with a slice profile.  The default returns exactly the dict described above."""
     from .engine import Engine
+    if crb and (slice_profile is not None or slice_weights is not None):
+        raise ValueError("crb=True is not available with a slice profile")
     t1g, t2g = np.asarray(t1_grid, dtype=np.float64).ravel(), np.asarray(t2_grid, dtype=np.float64).ravel()
     T1, T2 = (a.ravel() for a in np.meshgrid(t1g, t2g, indexing="ij"))
     groups = {}
@@ -111,11 +116,39 @@ def simulate_dictionary(alpha, tr, te, t1_grid, t2_grid, s=None, energy=None, ns
     try:
         out = eng.simulate_compress_dictionary(alpha, tr, te, T1, T2, b1=b1, s=s, energy=energy, s_max=s_max, nstates=nstates, inversion=inversion,
                                                ti=ti, inv_eff=inv_eff, **sp)
+        bound = {}
+        if crb:
+            c = eng.dictionary_crb(alpha, tr, te, T1, T2, b1=b1, wrt=("t1", "t2", "b1") if groups else ("t1", "t2"), V=out["V"], nstates=nstates,
+                                   inversion=inversion, ti=ti, inv_eff=inv_eff)
+            bound = {"crb": c["crb"], "crb_flags": c["flags"]}
     finally:
         eng.close()
     cols = [T1, T2] + ([b1] if groups else [])
     return {"V": out["V"], "D": out["D"], "normD": out["normD"], "lut": np.ascontiguousarray(np.stack(cols, axis=1).astype(np.float32)),
-            "eig": out["eig"], "info": out["info"], **groups}
+            "eig": out["eig"], "info": out["info"], **groups, **bound}
+
+
+def uncertainty_maps(dictionary, dm, pd, sigma):
+    """Per-pixel lower bounds on the standard deviation of matched maps, from a dictionary that carries crb and crb_flags
+    (simulate_dictionary(..., crb=True)): dm [N, M] the match's 1-based atom indices (0: no atom), pd [N, M] its proton density (real or complex),
+    sigma the noise's standard deviation per real and per imaginary part and channel of the TSMI that was matched.  Returns dict(std [N, M, P]:
+    sigma sqrt(crb[dm - 1, 1 + q]) / |pd| for q = T1, T2 (, b1); std_pd [N, M]: sigma sqrt(crb[dm - 1, 0])).  A host gather; pixels with dm = 0,
+    pd = 0 or an atom flagged singular are NaN."""
+    if "crb" not in dictionary or "crb_flags" not in dictionary:
+        raise ValueError("uncertainty_maps needs a dictionary with crb and crb_flags (simulate_dictionary(..., crb=True))")
+    c, fl = np.asarray(dictionary["crb"], dtype=np.float64), np.asarray(dictionary["crb_flags"])
+    dm, pd = np.asarray(dm), np.asarray(pd)
+    if c.ndim != 2 or fl.shape != (c.shape[0],) or dm.shape != pd.shape or not (np.isfinite(sigma) and float(sigma) >= 0):
+        raise ValueError("crb must be [K, 1 + P] with crb_flags [K], dm and pd of one shape, sigma finite and >= 0")
+    if dm.size and (dm.min() < 0 or dm.max() > c.shape[0]):
+        raise ValueError("dm must hold 1-based atom indices of the dictionary, or 0")
+    k = np.maximum(dm.astype(np.int64) - 1, 0)
+    ok = (dm > 0) & (pd != 0) & (fl[k] == 0)
+    ck = c[k]
+    with np.errstate(all="ignore"):
+        std = float(sigma) * np.sqrt(ck[..., 1:]) / np.abs(pd)[..., None]
+        std_pd = float(sigma) * np.sqrt(ck[..., 0])
+    return {"std": np.where(ok[..., None], std, np.nan), "std_pd": np.where(ok, std_pd, np.nan)}
 
 
 def crop_tsmi(X):
@@ -365,7 +398,7 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
                 net_arch=None, lrtv_iters=None, tsmi_domain="real", solver="lsqr", b1_map=None, density_compensation=False,
                 field_map=None, readout_s=None, field_normal=None, field_echoes=None, field_echo_times=None,
                 regulariser="net", llr_tau=None, llr_tau_rel=0.02, llr_block=8, wavelet_tau=None, wavelet_tau_rel=None,
-                wavelet_levels=3, wavelet_filter="db2", components=None, unmix_mode="real", b1_window=4, refine=False):
+                wavelet_levels=3, wavelet_filter="db2", components=None, unmix_mode="real", b1_window=4, refine=False, uncertainty=None):
     """main_recon_tsmis_FFT.m:216-374 on already loaded (and cropped) arrays.
 
     dictionary  dict(V, D, normD, lut) (load_dictionary);  X0  N x M x s ground-truth TSMI;  qmap0  N x M x 3
@@ -405,11 +438,17 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
                 qmap_refined (N x M x 3: the first two lut columns after the fit and the fit's PD -- the layout of qmap), metrics_refined (metrics
                 of it, as `metrics` is of qmap), refine_qmap (N x M x Q: every lut column after the fit, so a refined third column such as b1 is
                 there), refine_res and refine_flags.  False (default): nothing changes.
+    uncertainty the standard deviation sigma of the noise per real and imaginary part and channel of the reconstructed TSMI, for a dictionary that
+                carries crb / crb_flags (simulate_dictionary(..., crb=True)): the result gains qmap_std (N x M x P) and pd_std (N x M), the
+                Cramer-Rao lower bounds of uncertainty_maps at every pixel's matched atom and PD.  None (default):
+                nothing changes.
     Returns dict(X, qmap (N x M x 3: T1, T2, PD), Y, metrics, foreground_mask); with b1_map also grp (N x M, the 1-based b1 group, 0 = unmatched);
     with field_normal also field_normal_info (what prepare_normal_field reported).
     """
     from . import reference_api as R
     net_arch = dict(net_arch or {})
+    if uncertainty is not None and ("crb" not in dictionary or "crb_flags" not in dictionary):
+        raise ValueError("uncertainty needs a dictionary with crb and crb_flags (simulate_dictionary(..., crb=True))")
     if regulariser not in ("net", "llr", "wavelet"):
         raise ValueError(f'regulariser must be "net", "llr" or "wavelet", not {regulariser!r}')
     if regulariser != "net" and recon_method != "PnP_ADMM":
@@ -539,7 +578,7 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
         out = eng.dict_match(X, sel=b1_map)
         out["qmap"] = out["qmap"][:, :, :2]                                          # (T1, T2); column 3 of the lut is the group's b1
         extra["grp"] = out["grp"]
-    elif refine_cols is not None:                                                    # what mrf_dtm_cpu does, keeping dm for the refinement
+    elif refine_cols is not None or uncertainty is not None:                         # what mrf_dtm_cpu does, keeping dm for what follows
         eng = R._engine(device)
         eng.set_dictionary(dictionary["D"], dictionary["normD"], dictionary["lut"])
         out = eng.dict_match(X)
@@ -548,6 +587,9 @@ def recon_tsmis(dictionary, X0, qmap0, weights=None, recon_method="PnP_ADMM", su
     qmap = np.concatenate([np.asarray(out["qmap"], dtype=np.complex128), np.asarray(out["pd"]).reshape(N, M, 1)], axis=2)       # :316
     if components is not None:
         extra.update(unmix_tsmi(dictionary, X, component_atoms, mode=unmix_mode, device=device))
+    if uncertainty is not None:                                                      # the bound at the matched atom and proton density
+        um = uncertainty_maps(dictionary, out["dm"], out["pd"], uncertainty)
+        extra.update(qmap_std=um["std"], pd_std=um["std_pd"])
     mask = getmask_fromPD(np.asarray(qmap0)[:, :, 2], 0.15)                          # :192
     if refine_cols is not None:                                                      # the fit, started at the dm of the match above
         eng.set_refine(refine_cols)

@@ -33,6 +33,8 @@
 //   * 'dict_compress' compresses a simulated dictionary to its SVD subspace (qmri_dict_compress; extension); it needs no plan.
 //   * 'dict_simulate' simulates the fingerprints of a FISP-MRF sequence by extended phase graphs (qmri_dict_simulate; extension); it needs no plan.
 //   * 'dict_simulate_sp' is 'dict_simulate' integrated over a slice profile (qmri_dict_simulate_sp; extension); it needs no plan.
+//   * 'dict_simulate_grad' is 'dict_simulate' with the derivatives of the fingerprints and their Cramer-Rao bound (qmri_dict_simulate_grad;
+//     extension); it needs no plan.
 //   * 'set_llr' / 'clear_llr' select the locally low-rank proximal step as Step 2 of 'pnp_admm' (qmri_set_llr; extension), which
 //     then needs no denoiser; 'llr_prox' is the step alone (qmri_llr_prox).
 //   * 'set_wavelet' / 'clear_wavelet' select joint wavelet soft-thresholding as Step 2 of 'pnp_admm' the same way (qmri_set_wavelet; extension,
@@ -1071,6 +1073,71 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         if (st != QMRI_OK) mxDestroyArray(Fo);
         check(st);
         plhs[0] = Fo;
+    } else if (c == "dict_simulate_grad") {          // [F, dF, crb, flags] = qmri_mex('dict_simulate_grad', alpha, tr, te, t1, t2, b1, params, V)
+        // extension (no reference counterpart): the fingerprints of 'dict_simulate' with their derivatives and the Cramer-Rao bound they give
+        // (qmri_dict_simulate_grad).  The first seven arguments are those of 'dict_simulate'; params also takes nparams (2:
+        // T1, T2, the default; 3: T1, T2, b1) and bound_only (0; 1: F and dF are not computed and come back empty).  V: [] or a real double T x s
+        // subspace, 1 <= s <= 16.  F is K x T, dF K x T x P, crb (1 + P) x K (atom k in column k), flags int32 K x 1.  dF is computed from two
+        // outputs on, the bound from three on.
+        need(nrhs, 9, "[F, dF, crb, flags] = qmri_mex('dict_simulate_grad', alpha, tr, te, t1, t2, b1, params, V)");
+        want(mxIsStruct(prhs[7]), "qmri:dict_simulate_grad:params", "params must be a struct (fields nstates, inversion, ti, inv_eff, single, nparams, bound_only)");
+        auto real_vec = [](const mxArray* a, const char* id, const char* msg) {
+            want(mxIsDouble(a) && !mxIsComplex(a), id, msg);
+            return mxGetNumberOfElements(a);
+        };
+        const size_t T = real_vec(prhs[1], "qmri:dict_simulate_grad:alpha", "alpha must be a real double vector (complex flip angles are not supported)");
+        want(T >= 1 && T <= 1024, "qmri:dict_simulate_grad:alpha", "alpha must hold 1 <= T <= 1024 flip angles");
+        std::vector<double> sched[2];
+        const char* sid[2] = {"qmri:dict_simulate_grad:tr", "qmri:dict_simulate_grad:te"};
+        for (int q = 0; q < 2; ++q) {
+            const size_t n = real_vec(prhs[2 + q], sid[q], "tr / te must be real double, one value or one per frame");
+            want(n == 1 || n == T, sid[q], "tr / te must be real double, one value or one per frame");
+            sched[q].resize(T);
+            for (size_t t = 0; t < T; ++t) sched[q][t] = mxGetDoubles(prhs[2 + q])[n == 1 ? 0 : t];
+        }
+        const char* aid = "qmri:dict_simulate_grad:atoms";
+        const size_t K = real_vec(prhs[4], aid, "t1, t2 and b1 must be real double (complex values are not supported)");
+        want(K >= 1 && K <= ((size_t)1 << 30) && real_vec(prhs[5], aid, "t1, t2 and b1 must be real double (complex values are not supported)") == K, aid,
+             "t1 and t2 must hold the same number K >= 1 of atoms");
+        const bool has_b1 = mxGetNumberOfElements(prhs[6]) > 0;
+        if (has_b1) want(real_vec(prhs[6], aid, "t1, t2 and b1 must be real double (complex values are not supported)") == K, aid, "b1 must be [] or hold K values");
+        const mxArray* P = prhs[7];
+        const mxArray* f;
+        const char* pid = "qmri:dict_simulate_grad:params";
+        qmri_epg_params p = {32, 1, 0.0, 1.0, 1};
+        if ((f = mxGetField(P, 0, "nstates"))) p.nstates = int_arg(f, 1, 256, pid, "params.nstates must be an integer in [1, 256]");
+        if ((f = mxGetField(P, 0, "inversion"))) p.inversion = int_arg(f, 0, 1, pid, "params.inversion must be 0 or 1");
+        if ((f = mxGetField(P, 0, "single"))) p.out_is_f64 = 1 - int_arg(f, 0, 1, pid, "params.single must be 0 or 1");
+        p.ti = scalar_field(P, "ti", 0.0);
+        p.inv_eff = scalar_field(P, "inv_eff", 1.0);
+        want(std::isfinite(p.ti) && p.ti >= 0.0, pid, "params.ti must be finite and >= 0");
+        want(p.inv_eff > 0.0 && p.inv_eff <= 1.0, pid, "params.inv_eff must be in (0, 1]");
+        qmri_epg_grad_params gp = {2, 0, nullptr, {0, 0, 0, 0}};
+        int bound_only = 0;
+        if ((f = mxGetField(P, 0, "nparams"))) gp.nparams = int_arg(f, 2, 3, pid, "params.nparams must be 2 or 3");
+        if ((f = mxGetField(P, 0, "bound_only"))) bound_only = int_arg(f, 0, 1, pid, "params.bound_only must be 0 or 1");
+        const char* vid = "qmri:dict_simulate_grad:V";
+        if (mxGetNumberOfElements(prhs[8]) > 0) {
+            const size_t nv = real_vec(prhs[8], vid, "V must be [] or a real double T x s matrix, 1 <= s <= 16");
+            want(mxGetM(prhs[8]) == T && nv / T >= 1 && nv / T <= 16 && nv % T == 0, vid, "V must be [] or a real double T x s matrix, 1 <= s <= 16");
+            gp.s = (int32_t)(nv / T);
+            gp.V = mxGetDoubles(prhs[8]);
+        }
+        const bool want_F = !bound_only, want_dF = !bound_only && nlhs > 1, want_crb = bound_only || nlhs > 2;
+        const mxClassID cls = p.out_is_f64 ? mxDOUBLE_CLASS : mxSINGLE_CLASS;
+        const mwSize d3[3] = {(mwSize)K, (mwSize)T, (mwSize)gp.nparams};
+        mxArray* out[4] = {want_F ? mxCreateNumericMatrix(K, T, cls, mxREAL) : mxCreateNumericMatrix(0, 0, cls, mxREAL),
+                           want_dF ? mxCreateNumericArray(3, d3, cls, mxREAL) : mxCreateNumericMatrix(0, 0, cls, mxREAL),
+                           want_crb ? mxCreateDoubleMatrix(1 + gp.nparams, K, mxREAL) : mxCreateDoubleMatrix(0, 0, mxREAL),
+                           want_crb ? mxCreateNumericMatrix(K, 1, mxINT32_CLASS, mxREAL) : mxCreateNumericMatrix(0, 0, mxINT32_CLASS, mxREAL)};
+        const int st = qmri_dict_simulate_grad(ctx(), (int)K, (int)T, mxGetDoubles(prhs[1]), sched[0].data(), sched[1].data(), mxGetDoubles(prhs[4]),
+                                               mxGetDoubles(prhs[5]), has_b1 ? mxGetDoubles(prhs[6]) : nullptr, &p, &gp, want_F ? mxGetData(out[0]) : nullptr,
+                                               want_dF ? mxGetData(out[1]) : nullptr, want_crb ? mxGetDoubles(out[2]) : nullptr,
+                                               want_crb ? static_cast<int32_t*>(mxGetData(out[3])) : nullptr);
+        for (int k = 0; k < 4; ++k)
+            if (st != QMRI_OK || k >= std::max(nlhs, 1)) mxDestroyArray(out[k]);
+        check(st);
+        for (int k = 0; k < std::max(nlhs, 1) && k < 4; ++k) plhs[k] = out[k];
     } else if (c == "lrtv") {                        // [x, info] = qmri_mex('lrtv', y, param_struct, [N M s])   (FISTA_deep, main_recon_tsmis_FFT.m:273-282)
         need(nrhs, 4, "[x, info] = qmri_mex('lrtv', y, param, [N M s])");
         const mxArray* P = prhs[2];

@@ -88,6 +88,33 @@ def rf_slice_profile(alpha, envelope, tbw: float, nq: int, zmax: float = 1.0):
     return prof, np.full(nq, 1.0 / nq)
 
 
+def crb_score(crb, flags, theta):
+    """The score of train_crb_score from a bound: crb [K, 1 + P], flags [K], theta [P][K] the parameter values.  [P]: the mean over the atoms of
+    sqrt(crb[:, 1 + q]) / theta_q; +inf when any atom is flagged (its Fisher matrix is singular: the train cannot separate the parameters there)."""
+    crb, theta = np.asarray(crb, dtype=np.float64), [np.asarray(t, dtype=np.float64).ravel() for t in theta]
+    if np.any(np.asarray(flags) != 0):
+        return np.full(len(theta), np.inf)
+    return np.array([np.mean(np.sqrt(crb[:, 1 + q]) / theta[q]) for q in range(len(theta))])
+
+
+def train_crb_score(alpha, tr, te, t1, t2, b1=None, wrt=("t1", "t2"), V=None, nstates=32, inversion=True, ti=0.0, inv_eff=1.0, device=0):
+    """The scalar a sequence designer compares flip-angle trains by: for each parameter q of wrt the mean over the atoms
+    (t1, t2, b1 broadcast as in Engine.simulate_dictionary; b1 None: 1) of sqrt(crb[q]) / theta_q, the relative standard deviation per unit noise
+    and unit proton density that no unbiased estimate beats.  Smaller is better.  The bound is computed on the device in one launch
+    (Engine.dictionary_crb); V [T, s] scores the train in a compressed space.  Returns [P] float64."""
+    from .engine import Engine
+    eng = Engine(device)
+    try:
+        r = eng.dictionary_crb(alpha, tr, te, t1, t2, b1=b1, wrt=wrt, V=V, nstates=nstates, inversion=inversion, ti=ti, inv_eff=inv_eff)
+    finally:
+        eng.close()
+    atoms = [np.asarray(t1, dtype=np.float64), np.asarray(t2, dtype=np.float64)] + ([np.asarray(b1, dtype=np.float64)] if b1 is not None else [])
+    atoms = [x.ravel() for x in np.broadcast_arrays(*atoms)]
+    if len(tuple(wrt)) == 3 and b1 is None:
+        atoms.append(np.ones(atoms[0].size))
+    return crb_score(r["crb"], r["flags"], atoms[:len(tuple(wrt))])
+
+
 def make_dictionary(T: int = 200, n_t1: int = 128, n_t2: int = 64, s: int = 10, seed: int = 0, uncompressed: bool = False) -> dict:
     """Synthetic MRF dictionary with K = n_t1*n_t2 atoms.
 
