@@ -822,6 +822,55 @@ int qmri_dict_simulate_grad_dev(qmri_ctx* ctx, int K, int T, const double* alpha
                                 const double* d_t2, const double* d_b1, const qmri_epg_params* p, const qmri_epg_grad_params* gp, void* d_F_out,
                                 void* d_dF_out, double* d_crb_out, int32_t* d_flags_out);
 
+/* ---- EPG simulation of prepared, repeated FISP trains (extension, no reference counterpart, parity unpinned) ---- */
+/* qmri_dict_simulate describes one experiment: equilibrium, at most one inversion, one uninterrupted train.  3-D, interleaved multi-slice and SMS
+ * MRF play the same train many times with a pause in between, so that the first recorded frame meets a driven steady state; cardiac MRF (Hamilton
+ * et al. 2017) plays, heartbeat after heartbeat, an inversion, nothing, a T2 preparation, ... each followed by a wait.  This call simulates such a
+ * schedule: the train is cut into B blocks, block b owning the next nframes_b entries of alpha / tr / te (the nframes sum to T), and the block list
+ * is played C = ncycles times, of which only the last is recorded.  Per atom the state starts at equilibrium as in qmri_dict_simulate (every F+-_n
+ * and Z_n zero except Z_0 = 1); then for cycle = 0 .. C-1 and for each block in order:
+ *   a. Wait (only if wait > 0).  E1 = exp(-wait / T1), E2 = exp(-wait / T2); for every n: F+-_n <- F+-_n E2, Z_n <- Z_n E1; then Z_0 += 1 - E1.
+ *      Free relaxation: no dephasing and no crusher.
+ *   b. Preparation.
+ *      inversion (prep = 1): e = exp(-TI / T1), TI = prep_time, eff = prep_eff.  Z_0 <- (-eff Z_0) e + (1 - e); Z_n <- (-eff Z_n) e for n >= 1;
+ *        every F+-_n <- 0 (a crusher follows the pulse).
+ *      T2 preparation (prep = 2): e2 = exp(-prep_time / T2).  Z_n <- (eff Z_n) e2 for every n; every F+-_n <- 0.  This is the IDEALISED tip-down /
+ *        refocus / tip-up module: T1 relaxation during the module is neglected, the pulses are perfect up to the scale eff, a crusher follows.
+ *      Preparations are NOT scaled by b1 (adiabatic pulses).
+ *   c. Frames: nframes frames, each of them steps 1 to 5 of qmri_dict_simulate verbatim.  In the last cycle step 3 writes F[k, t].
+ * All arithmetic is fp64; no atomics; an atom's bits depend neither on K nor on its position in the call.  One block {T, inversion, wait 0, ti,
+ * inv_eff} (or {T, none, 0, 0, 1}) with C = 1 gives the numbers of qmri_dict_simulate with the corresponding qmri_epg_params -- equal as numbers;
+ * the sign of a zero is not pinned --; and when C T <= 1024, C cycles give the numbers of the last T frames of one cycle on the C-fold tiled train
+ * and block list.  The only device memory beyond the outputs is the schedule (3 T doubles and at most T / 16 + B segment records of 40 bytes).
+ * Out of scope: a slice profile (qmri_dict_simulate_sp), derivatives and a Cramer-Rao bound (qmri_dict_simulate_grad) for this schedule, complex
+ * RF phase, diffusion. */
+typedef struct {
+    int32_t nframes;     /* frames acquired in this block, >= 1 */
+    int32_t prep;        /* 0 none, 1 inversion, 2 T2 preparation */
+    double  wait;        /* s, >= 0: free relaxation in front of the preparation */
+    double  prep_time;   /* s, >= 0: inversion: TI; T2 preparation: its echo time; prep none: must be 0 */
+    double  prep_eff;    /* in (0, 1]: inversion efficiency / T2-preparation scale; prep none: must be 1 */
+} qmri_epg_block;
+typedef struct {
+    int32_t nblocks;     /* B, 1..64 */
+    int32_t ncycles;     /* C, 1..16: the block list is played C times, only the last is recorded */
+    const qmri_epg_block* blocks;   /* host array [B] */
+    int32_t reserved[4]; /* zero */
+} qmri_epg_seq;
+/* The arrays, the layout of F_out, T <= 1024, nstates <= 256 and out_is_f64 of qmri_dict_simulate.  p->inversion must be 0: inversions are stated
+ * in the blocks (p->ti and p->inv_eff are not read).  Refusals, decided on the host before the device is selected (ctx == NULL: the message of the
+ * first failing check in qmri_last_error(NULL)): everything qmri_dict_simulate refuses; then p->inversion != 0; a NULL seq or seq->blocks; nblocks
+ * outside 1..64; ncycles outside 1..16; a non-zero reserved; and per block nframes < 1, prep outside 0..2, a non-finite or negative wait or
+ * prep_time, prep_eff outside (0, 1], prep_time != 0 or prep_eff != 1 on a block with prep none; then nframes that do not sum to T:
+ * QMRI_ERR_INVALID_ARG, and nothing is written to F_out.  Returns after its kernel has finished. */
+int qmri_dict_simulate_seq(qmri_ctx* ctx, int K, int T, const double* alpha, const double* tr, const double* te, const double* t1, const double* t2,
+                           const double* b1, const qmri_epg_params* p, const qmri_epg_seq* seq, void* F_out);
+/* The same with t1, t2, b1 and F_out on ctx's device; alpha, tr, te, p, seq and seq->blocks stay on the host.  Same bits as the host-array call.
+ * For an atom this route cannot refuse (see qmri_dict_simulate_dev) the kernel writes NaN in every frame of that atom (and of no other).  F_out
+ * feeds qmri_dict_compress_dev as it is. */
+int qmri_dict_simulate_seq_dev(qmri_ctx* ctx, int K, int T, const double* alpha, const double* tr, const double* te, const double* d_t1,
+                               const double* d_t2, const double* d_b1, const qmri_epg_params* p, const qmri_epg_seq* seq, void* d_F_out);
+
 /* ---- field map from multi-echo images (extension, no reference counterpart, parity unpinned) ---- */
 /* qmri_set_field_map takes its map f from the caller; this call makes one from L gradient-echo images per slice, by the regularised estimator of
  * Funai, Fessler, Yeo, Olafsson and Noll (IEEE TMI 2008): a penalised cosine fit over all echo pairs and coils, minimised by separable quadratic

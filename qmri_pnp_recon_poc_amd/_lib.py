@@ -25,7 +25,7 @@ SYMBOLS = [
     "qmri_dict_match_grouped_dev", "qmri_dict_group_scores", "qmri_dict_group_scores_dev", "qmri_b1_pool", "qmri_b1_pool_dev", "qmri_b1_estimate",
     "qmri_b1_estimate_dev", "qmri_set_components", "qmri_dict_unmix", "qmri_dict_unmix_dev", "qmri_dict_lines", "qmri_set_refine", "qmri_dict_refine",
     "qmri_dict_refine_dev", "qmri_recon_batch", "qmri_recon_batch_mc",
-    "qmri_coil_compress", "qmri_coil_compress_dev", "qmri_coil_eig", "qmri_recon_batch_mc_cc", "qmri_coil_maps", "qmri_coil_maps_dev", "qmri_dict_compress", "qmri_dict_compress_dev", "qmri_dict_simulate", "qmri_dict_simulate_dev", "qmri_dict_simulate_sp", "qmri_dict_simulate_sp_dev", "qmri_dict_simulate_grad", "qmri_dict_simulate_grad_dev", "qmri_field_map_estimate", "qmri_field_map_estimate_dev", "qmri_llr_prox", "qmri_llr_prox_dev", "qmri_set_llr", "qmri_wavelet_prox", "qmri_wavelet_prox_dev", "qmri_set_wavelet", "qmri_set_sms", "qmri_forward_sms", "qmri_adjoint_sms", "qmri_xupdate_sms", "qmri_pnp_admm_sms", "qmri_pnp_admm_sms_dev", "qmri_profile_enable", "qmri_profile_get", "qmri_get_health",
+    "qmri_coil_compress", "qmri_coil_compress_dev", "qmri_coil_eig", "qmri_recon_batch_mc_cc", "qmri_coil_maps", "qmri_coil_maps_dev", "qmri_dict_compress", "qmri_dict_compress_dev", "qmri_dict_simulate", "qmri_dict_simulate_dev", "qmri_dict_simulate_sp", "qmri_dict_simulate_sp_dev", "qmri_dict_simulate_grad", "qmri_dict_simulate_grad_dev", "qmri_dict_simulate_seq", "qmri_dict_simulate_seq_dev", "qmri_field_map_estimate", "qmri_field_map_estimate_dev", "qmri_llr_prox", "qmri_llr_prox_dev", "qmri_set_llr", "qmri_wavelet_prox", "qmri_wavelet_prox_dev", "qmri_set_wavelet", "qmri_set_sms", "qmri_forward_sms", "qmri_adjoint_sms", "qmri_xupdate_sms", "qmri_pnp_admm_sms", "qmri_pnp_admm_sms_dev", "qmri_profile_enable", "qmri_profile_get", "qmri_get_health",
     "qmri_debug_lsqr_stamps", "qmri_debug_conv_stamps", "qmri_debug_lsqr_persist", "qmri_debug_dict_filter", "qmri_debug_conv_resident", "qmri_debug_dsvd_gram", "qmri_debug_epg_shift", "qmri_debug_knob", "qmri_debug_mem_stats",
     "qmri_onnx_read_unetres",
     "qmri_lrtv", "qmri_prox_tv", "qmri_norm_tv", "qmri_synthesize_tsmi", "qmri_synthesize_tsmi_complex",
@@ -81,6 +81,14 @@ class EpgProfile(C.Structure):
 
 class EpgGradParams(C.Structure):
     _fields_ = [("nparams", C.c_int32), ("s", C.c_int32), ("V", C.c_void_p), ("reserved", C.c_int32 * 4)]
+
+
+class EpgBlock(C.Structure):
+    _fields_ = [("nframes", C.c_int32), ("prep", C.c_int32), ("wait", C.c_double), ("prep_time", C.c_double), ("prep_eff", C.c_double)]
+
+
+class EpgSeq(C.Structure):
+    _fields_ = [("nblocks", C.c_int32), ("ncycles", C.c_int32), ("blocks", C.POINTER(EpgBlock)), ("reserved", C.c_int32 * 4)]
 
 
 class NufftParams(C.Structure):
@@ -302,6 +310,8 @@ def lib() -> C.CDLL:
     L.qmri_dict_simulate_sp_dev.argtypes = [vp, i, i, vp, vp, vp, vp, vp, vp, C.POINTER(EpgParams), C.POINTER(EpgProfile), vp]
     L.qmri_dict_simulate_grad.argtypes = [vp, i, i, vp, vp, vp, vp, vp, vp, C.POINTER(EpgParams), C.POINTER(EpgGradParams), vp, vp, vp, vp]
     L.qmri_dict_simulate_grad_dev.argtypes = [vp, i, i, vp, vp, vp, vp, vp, vp, C.POINTER(EpgParams), C.POINTER(EpgGradParams), vp, vp, vp, vp]
+    L.qmri_dict_simulate_seq.argtypes = [vp, i, i, vp, vp, vp, vp, vp, vp, C.POINTER(EpgParams), C.POINTER(EpgSeq), vp]
+    L.qmri_dict_simulate_seq_dev.argtypes = [vp, i, i, vp, vp, vp, vp, vp, vp, C.POINTER(EpgParams), C.POINTER(EpgSeq), vp]
     L.qmri_debug_epg_shift.argtypes = [vp, i, i, vp, vp]
     L.qmri_field_map_estimate.argtypes = [vp, i, i, i, i, i, vp, dp, vp, C.POINTER(FieldmapParams), vp, vp, C.POINTER(FieldmapInfo)]
     L.qmri_field_map_estimate_dev.argtypes = [vp, i, i, i, i, i, vp, dp, vp, C.POINTER(FieldmapParams), vp, vp, C.POINTER(FieldmapInfo)]

@@ -1,10 +1,13 @@
-// api_epg.cpp -- C ABI of the FISP dictionary simulation by extended phase graphs, plain, over a slice profile and with derivatives (include/qmri.h; kernels:
+// api_epg.cpp -- C ABI of the FISP dictionary simulation by extended phase graphs, plain, over a slice profile, with derivatives and over a schedule of
+// prepared, repeated trains (include/qmri.h; kernels:
 // epg_kernels.hip).  An EXTENSION with no reference counterpart.  Every refusal is decided here, on the host, before the device is selected; with ctx == NULL the message of the first
 // failing check is left in qmri_last_error(NULL), so the argument rules can be exercised on a machine without a GPU.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <vector>
+#include "epg_seq_plan.h"
 #include "qmri_internal.h"
 
 namespace {
@@ -74,6 +77,28 @@ int epg_grad_checks(qmri_ctx* ctx, int T, const qmri_epg_grad_params* gp, const 
     return QMRI_OK;
 }
 
+// the rules of a block schedule (ctx may be NULL); they follow the rules of the plain call, whose T bounds the sum
+int epg_seq_checks(qmri_ctx* ctx, int T, const qmri_epg_params* p, const qmri_epg_seq* seq) {
+    QMRI_CHECK_ARG(ctx, p->inversion == 0, "inversion must be 0 in this call: inversions are stated in the blocks");
+    QMRI_CHECK_ARG(ctx, seq && seq->blocks, "seq / blocks must not be NULL");
+    QMRI_CHECK_ARG(ctx, seq->nblocks >= 1 && seq->nblocks <= epgseq::MAX_BLOCKS, "nblocks must satisfy 1 <= nblocks <= 64");
+    QMRI_CHECK_ARG(ctx, seq->ncycles >= 1 && seq->ncycles <= epgseq::MAX_CYCLES, "ncycles must satisfy 1 <= ncycles <= 16");
+    for (int32_t r : seq->reserved) QMRI_CHECK_ARG(ctx, r == 0, "reserved must be zero");
+    long long sum = 0;
+    for (int b = 0; b < seq->nblocks; ++b) {
+        const qmri_epg_block& bl = seq->blocks[b];
+        QMRI_CHECK_ARG(ctx, bl.nframes >= 1, "nframes must be >= 1 in every block");
+        QMRI_CHECK_ARG(ctx, bl.prep >= 0 && bl.prep <= 2, "prep must be 0 (none), 1 (inversion) or 2 (T2 preparation) in every block");
+        QMRI_CHECK_ARG(ctx, std::isfinite(bl.wait) && bl.wait >= 0.0, "wait must be finite and >= 0 in every block");
+        QMRI_CHECK_ARG(ctx, std::isfinite(bl.prep_time) && bl.prep_time >= 0.0, "prep_time must be finite and >= 0 in every block");
+        QMRI_CHECK_ARG(ctx, bl.prep_eff > 0.0 && bl.prep_eff <= 1.0, "prep_eff must be in (0, 1] in every block");
+        QMRI_CHECK_ARG(ctx, bl.prep != 0 || (bl.prep_time == 0.0 && bl.prep_eff == 1.0), "a block without a preparation must have prep_time 0 and prep_eff 1");
+        sum += bl.nframes;
+    }
+    QMRI_CHECK_ARG(ctx, sum == T, "the nframes of the blocks must sum to T");
+    return QMRI_OK;
+}
+
 int ctx_check(qmri_ctx* ctx) {
     if (!ctx) { qmri_set_error(nullptr, "invalid argument: ctx must not be NULL"); return QMRI_ERR_INVALID_ARG; }
     return QMRI_OK;
@@ -99,6 +124,26 @@ int epg_run(qmri_ctx* ctx, int K, int T, const double* alpha, const double* tr, 
     QMRI_HIP(ctx, hipMemcpyAsync(ds.p, sched.data(), sched.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     if (sp) QMRI_TRY(epg_simulate_sp_dev(ctx, K, T, Q, ds, d_t1, d_t2, d_b1, p, const_timing, d_F));
     else QMRI_TRY(epg_simulate_dev(ctx, K, T, ds, d_t1, d_t2, d_b1, p, const_timing, d_F));
+    QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return QMRI_OK;
+}
+
+// the block schedule: alpha, tr, te followed by the segment records of epg_seq_plan.h on the device, and the launch; the stream is idle on return
+int epg_seq_run(qmri_ctx* ctx, int K, int T, const double* alpha, const double* tr, const double* te, const double* d_t1, const double* d_t2,
+                const double* d_b1, const qmri_epg_params& p, const qmri_epg_seq& seq, void* d_F) {
+    const std::vector<epgseq::Segment> segs = epgseq::plan(seq.nblocks, seq.blocks);
+    constexpr size_t SD = sizeof(epgseq::Segment) / sizeof(double);
+    std::vector<double> sched((size_t)3 * T + segs.size() * SD);
+    bool const_timing = true;
+    for (int t = 0; t < T; ++t) {
+        const_timing = const_timing && tr[t] == tr[0] && te[t] == te[0];
+        sched[t] = alpha[t]; sched[T + t] = tr[t]; sched[2 * T + t] = te[t];
+    }
+    std::memcpy(sched.data() + (size_t)3 * T, segs.data(), segs.size() * sizeof(epgseq::Segment));
+    DevBuf<double> ds;
+    QMRI_TRY(ds.ensure(ctx, sched.size()));
+    QMRI_HIP(ctx, hipMemcpyAsync(ds.p, sched.data(), sched.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    QMRI_TRY(epg_simulate_seq_dev(ctx, K, T, (int)segs.size(), seq.ncycles, ds, ds.p + (size_t)3 * T, d_t1, d_t2, d_b1, p, const_timing, d_F));
     QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return QMRI_OK;
 }
@@ -183,6 +228,37 @@ extern "C" int qmri_dict_simulate_sp_dev(qmri_ctx* ctx, int K, int T, const doub
 extern "C" int qmri_dict_simulate_sp(qmri_ctx* ctx, int K, int T, const double* alpha, const double* tr, const double* te, const double* t1,
                                      const double* t2, const double* b1, const qmri_epg_params* p, const qmri_epg_profile* sp, void* F_out) {
     return simulate_host(ctx, K, T, alpha, tr, te, t1, t2, b1, p, sp, true, F_out);
+}
+
+extern "C" int qmri_dict_simulate_seq_dev(qmri_ctx* ctx, int K, int T, const double* alpha, const double* tr, const double* te, const double* d_t1,
+                                          const double* d_t2, const double* d_b1, const qmri_epg_params* p, const qmri_epg_seq* seq, void* d_F_out) {
+    QMRI_TRY(epg_checks(ctx, K, T, alpha, tr, te, d_t1, d_t2, d_b1, p, d_F_out, false));
+    QMRI_TRY(epg_seq_checks(ctx, T, p, seq));
+    QMRI_TRY(ctx_check(ctx));
+    QMRI_HIP(ctx, hipSetDevice(ctx->device));
+    return epg_seq_run(ctx, K, T, alpha, tr, te, d_t1, d_t2, d_b1, *p, *seq, d_F_out);
+}
+
+extern "C" int qmri_dict_simulate_seq(qmri_ctx* ctx, int K, int T, const double* alpha, const double* tr, const double* te, const double* t1,
+                                      const double* t2, const double* b1, const qmri_epg_params* p, const qmri_epg_seq* seq, void* F_out) {
+    QMRI_TRY(epg_checks(ctx, K, T, alpha, tr, te, t1, t2, b1, p, F_out, true));
+    QMRI_TRY(epg_seq_checks(ctx, T, p, seq));
+    QMRI_TRY(ctx_check(ctx));
+    QMRI_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t nF = (size_t)K * T * (p->out_is_f64 ? sizeof(double) : sizeof(float));
+    DevBuf<double> d1, d2, db;
+    DevBuf<unsigned char> dF;
+    QMRI_TRY(d1.ensure(ctx, (size_t)K));
+    QMRI_TRY(d2.ensure(ctx, (size_t)K));
+    if (b1) QMRI_TRY(db.ensure(ctx, (size_t)K));
+    QMRI_TRY(dF.ensure(ctx, nF));
+    QMRI_HIP(ctx, hipMemcpyAsync(d1.p, t1, (size_t)K * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    QMRI_HIP(ctx, hipMemcpyAsync(d2.p, t2, (size_t)K * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (b1) QMRI_HIP(ctx, hipMemcpyAsync(db.p, b1, (size_t)K * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    QMRI_TRY(epg_seq_run(ctx, K, T, alpha, tr, te, d1, d2, db, *p, *seq, dF.p));
+    QMRI_HIP(ctx, hipMemcpyAsync(F_out, dF.p, nF, hipMemcpyDeviceToHost, ctx->stream));
+    QMRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return QMRI_OK;
 }
 
 extern "C" int qmri_dict_simulate_grad_dev(qmri_ctx* ctx, int K, int T, const double* alpha, const double* tr, const double* te, const double* d_t1,

@@ -11,12 +11,14 @@
 //                       and after the block the workgroup writes FB x APW values, APW atoms contiguous per frame (8 at S = 32: 64 B).
 //   k_epg_sp<G, R>      the same per (atom, sub-slice of a slice profile), the weighted sum over the sub-slices taken in LDS (see its comment).
 //   k_epg_grad<G, R, P> k_epg with P tangents beside the state and the Cramer-Rao bound of the 1 + P signals in the same launch (see its comment).
+//   k_epg_seq<G, R>     k_epg walked over a schedule of blocks (wait, preparation, frames) played several times (see its comment).
 //   k_epg_shift<G, R>   the spoiler alone, n times on one atom's given state (qmri_debug_epg_shift: exact-integer test of the lane moves).
 // No atomics, no reduction across atoms: equal inputs give equal bits.
 #include <cmath>
 #include <cstdint>
 #include <limits>
 #include <type_traits>
+#include "epg_seq_plan.h"
 #include "qmri_internal.h"
 
 namespace {
@@ -508,6 +510,103 @@ __global__ void __launch_bounds__(NT) k_epg_grad(const double* __restrict__ sche
     flags[k0 + g] = bad ? 2 : sing ? 1 : 0;
 }
 
+// Prepared, repeated trains: k_epg's scheme, walked over a schedule.  segs: the nseg segments of epg_seq_plan.h, each at
+// most FB frames of one block with the block's event in front of its first segment; the list is played ncycles times from one equilibrium start
+// and only the last cycle stages and stores.  An event is applied by every lane on its own states from two or three exponentials it computes
+// itself (an event is once per block, a frame's transcendentals are shared through LDS as in k_epg):
+//   wait            F+- <- F+- exp(-wait / T2), Z <- Z exp(-wait / T1), Z_0 += 1 - exp(-wait / T1)
+//   inversion       Z <- (-eff Z) e, Z_0 <- (-eff Z_0) e + (1 - e) with e = exp(-TI / T1) -- the expression of k_epg's inversion --, F+- <- 0
+//   T2 preparation  Z <- (eff Z) exp(-prep_time / T2), F+- <- 0
+// The segment record is read with scalar loads (it is the same for every lane), so the branches on it are uniform.  One block {T, inversion} or
+// {T, none} in one cycle runs the instructions of k_epg on the same numbers: the same bits.
+template <int G, int R>
+__global__ void __launch_bounds__(NT) k_epg_seq(const double* __restrict__ sched, const epgseq::Segment* __restrict__ segs, int nseg, int ncycles, int T,
+                                                int K, int S, const double* __restrict__ t1, const double* __restrict__ t2,
+                                                const double* __restrict__ b1, int const_timing, void* __restrict__ Fout, int out_f64) {
+    constexpr int APW = NT / G;
+    __shared__ __attribute__((aligned(16))) double sc[APW * ROW];
+    __shared__ double sig[FB * APW];
+    const double *alpha = sched, *tr = sched + T, *te = sched + 2 * T;
+    const int tid = threadIdx.x, g = tid / G, j = tid % G;
+    const long long k0 = (long long)blockIdx.x * APW;
+    const long long k = k0 + g < K ? k0 + g : (long long)K - 1;                  // the lanes past K repeat the last atom and store nothing
+    double T1 = t1[k], T2 = t2[k], B1 = b1 ? b1[k] : 1.0;
+    const double inf = std::numeric_limits<double>::infinity();
+    const bool bad = !(T1 > 0.0 && T1 < inf && T2 > 0.0 && T2 < inf && B1 >= 0.0 && B1 < inf);
+    if (bad) { T1 = 1.0; T2 = 1.0; B1 = 1.0; }                                   // its row becomes NaN at the store
+    double fp[R], fm[R], z[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) fp[r] = fm[r] = z[r] = 0.0;
+    if (j == 0) z[0] = 1.0;
+    double ea1 = 0.0, ea2 = 0.0, eb1 = 0.0, eb2 = 0.0;
+    if (const_timing) {
+        const double a = te[0], b = tr[0] - te[0];
+        ea1 = exp(-a / T1); ea2 = exp(-a / T2); eb1 = exp(-b / T1); eb2 = exp(-b / T2);
+    }
+    double* my = sc + g * ROW;
+    for (int cyc = 0; cyc < ncycles; ++cyc) {
+        const bool rec = cyc == ncycles - 1;
+        for (int si = 0; si < nseg; ++si) {
+            const int t0 = segs[si].t0, nf = segs[si].nf, prep = segs[si].prep;
+            const double wait = segs[si].wait;
+            if (wait > 0.0) {
+                const double w1 = exp(-wait / T1), w2 = exp(-wait / T2);
+#pragma unroll
+                for (int r = 0; r < R; ++r) { fp[r] *= w2; fm[r] *= w2; z[r] *= w1; }
+                if (j == 0) z[0] += 1.0 - w1;
+            }
+            if (prep == epgseq::PREP_INVERSION) {
+                const double eff = segs[si].prep_eff, e = exp(-segs[si].prep_time / T1);
+#pragma unroll
+                for (int r = 1; r < R; ++r) z[r] = (-eff * z[r]) * e;
+                if (j == 0) z[0] = (-eff * z[0]) * e + (1.0 - e);
+                else z[0] = (-eff * z[0]) * e;
+#pragma unroll
+                for (int r = 0; r < R; ++r) fp[r] = fm[r] = 0.0;
+            } else if (prep == epgseq::PREP_T2) {
+                const double eff = segs[si].prep_eff, e2 = exp(-segs[si].prep_time / T2);
+#pragma unroll
+                for (int r = 0; r < R; ++r) { z[r] = (eff * z[r]) * e2; fp[r] = fm[r] = 0.0; }
+            }
+            __syncthreads();                                 // the previous segment's sc and sig have been read
+            if (j < nf) {
+                double s, c;
+                sincos(alpha[t0 + j] * B1, &s, &c);
+                my[j * NQ + 0] = c;
+                my[j * NQ + 1] = s;
+                if (!const_timing) {
+                    const double a = te[t0 + j], b = tr[t0 + j] - a;
+                    my[j * NQ + 2] = exp(-a / T1);
+                    my[j * NQ + 3] = exp(-a / T2);
+                    my[j * NQ + 4] = exp(-b / T1);
+                    my[j * NQ + 5] = exp(-b / T2);
+                }
+            }
+            __syncthreads();
+            for (int tt = 0; tt < nf; ++tt) {
+                const double2 cs = *reinterpret_cast<const double2*>(my + tt * NQ);
+                const double c = cs.x, s = cs.y, c2 = (1.0 + c) * 0.5, s2 = (1.0 - c) * 0.5;
+                if (!const_timing) {
+                    const double2 ea = *reinterpret_cast<const double2*>(my + tt * NQ + 2), eb = *reinterpret_cast<const double2*>(my + tt * NQ + 4);
+                    ea1 = ea.x; ea2 = ea.y; eb1 = eb.x; eb2 = eb.y;
+                }
+                epg_frame<G, R>(fp, fm, z, c, s, c2, s2, ea1, ea2, eb1, eb2, j, S,
+                                [&] { sig[tt * APW + g] = bad ? std::numeric_limits<double>::quiet_NaN() : fp[0]; }, [] {});
+            }
+            if (!rec) continue;                              // uniform: the cycles before the last one store nothing
+            __syncthreads();
+            if (tid < nf * APW) {                            // FB * APW <= NT: one value per lane, the atoms of a frame contiguous
+                const int tt = tid / APW, a = tid % APW;
+                if (k0 + a < K) {
+                    const size_t o = (size_t)(t0 + tt) * (size_t)K + (size_t)(k0 + a);
+                    if (out_f64) static_cast<double*>(Fout)[o] = sig[tid];
+                    else static_cast<float*>(Fout)[o] = (float)sig[tid];
+                }
+            }
+        }
+    }
+}
+
 // st: F+ [S], F- [S], Z [S] of one atom; one group of one wave does the work
 template <int G, int R> __global__ void __launch_bounds__(64) k_epg_shift(int S, int nshift, const double* __restrict__ in, double* __restrict__ out) {
     const int lane = threadIdx.x, j = lane % G;
@@ -568,6 +667,23 @@ int epg_simulate_grad_dev(qmri_ctx* ctx, int K, int T, int nparams, int sv, cons
         auto* kern = nparams == 2 ? k_epg_grad<G, R, 2> : k_epg_grad<G, R, 3>;
         kern<<<grid, NT, 0, ctx->stream>>>(d_sched, T, K, p.nstates, sv, d_t1, d_t2, d_b1, p.inversion, p.ti, p.inv_eff, const_timing ? 1 : 0, d_F, d_dF,
                                            p.out_is_f64, d_crb, d_flags);
+    });
+    QMRI_HIP(ctx, hipGetLastError());
+    return QMRI_OK;
+}
+
+int epg_simulate_seq_dev(qmri_ctx* ctx, int K, int T, int nseg, int ncycles, const double* d_sched, const void* d_segs, const double* d_t1,
+                         const double* d_t2, const double* d_b1, const qmri_epg_params& p, bool const_timing, void* d_F) {
+    static_assert(epgseq::FB == FB, "the plan cuts the blocks into the kernel's frame blocks");
+    if (nseg < 1 || ncycles < 1 || ncycles > epgseq::MAX_CYCLES) {
+        qmri_set_error(ctx, "internal: k_epg_seq takes nseg >= 1 and 1 <= ncycles <= 16");
+        return QMRI_ERR_INVALID_ARG;
+    }
+    epg_dispatch(p.nstates, [&](auto g, auto r) {
+        constexpr int G = decltype(g)::value, R = decltype(r)::value, APW = NT / G;
+        const unsigned grid = (unsigned)(((long long)K + APW - 1) / APW);
+        k_epg_seq<G, R><<<grid, NT, 0, ctx->stream>>>(d_sched, static_cast<const epgseq::Segment*>(d_segs), nseg, ncycles, T, K, p.nstates, d_t1, d_t2, d_b1,
+                                                      const_timing ? 1 : 0, d_F, p.out_is_f64);
     });
     QMRI_HIP(ctx, hipGetLastError());
     return QMRI_OK;

@@ -331,6 +331,9 @@ int epg_simulate_grad_dev(qmri_ctx* ctx, int K, int T, int nparams, int sv, cons
 int epg_sp_atoms_per_workgroup(int S, int Q);      // atoms a workgroup simulates with S states and Q sub-slices (1 when Q fills its groups)
 int epg_simulate_sp_dev(qmri_ctx* ctx, int K, int T, int Q, const double* d_sched, const double* d_t1, const double* d_t2,
                         const double* d_b1 /* or NULL */, const qmri_epg_params& p, bool const_timing, void* d_F);
+// prepared, repeated trains.  d_segs: nseg records of epg_seq_plan.h (epgseq::Segment), played ncycles times
+int epg_simulate_seq_dev(qmri_ctx* ctx, int K, int T, int nseg, int ncycles, const double* d_sched, const void* d_segs, const double* d_t1,
+                         const double* d_t2, const double* d_b1 /* or NULL */, const qmri_epg_params& p, bool const_timing, void* d_F);
 int epg_shift_dev(qmri_ctx* ctx, int S, int nshift, const double* d_in, double* d_out);      // the spoiler alone on one atom's state (3 S doubles)
 
 // field map from multi-echo images (fmap_kernels.hip, api_fmap.cpp).  All d_ pointers are device pointers; the stream is

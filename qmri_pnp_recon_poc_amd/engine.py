@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import AdmmParams, CcParams, CsmInfo, CsmParams, DcfInfo, DcfParams, DsvdInfo, DsvdParams, EpgGradParams, EpgParams, EpgProfile, FieldmapInfo, FieldmapParams, LlrParams, LrtvInfo, LrtvParams, NetDesc, NufftParams, OffresInfo, OffresNormalInfo, OffresNormalParams, OffresParams, Profile, WAVELET_FILTERS, WaveletParams
+from ._lib import AdmmParams, CcParams, CsmInfo, CsmParams, DcfInfo, DcfParams, DsvdInfo, DsvdParams, EpgBlock, EpgGradParams, EpgParams, EpgProfile, EpgSeq, FieldmapInfo, FieldmapParams, LlrParams, LrtvInfo, LrtvParams, NetDesc, NufftParams, OffresInfo, OffresNormalInfo, OffresNormalParams, OffresParams, Profile, WAVELET_FILTERS, WaveletParams
 
 ARCH_UNETRES, ARCH_SEQ_CONV = 0, 1
 SOLVER_LSQR, SOLVER_DIRECT = 0, 1
@@ -148,6 +148,35 @@ def grad_arguments(wrt, V, outputs, T):
         raise ValueError("V must be finite")
     Vb = np.ascontiguousarray(V.ravel(order="F"))
     return Vb, EpgGradParams(len(wrt), V.shape[1], Vb.ctypes.data), outs
+
+
+EPG_PREPS = {"none": 0, "inversion": 1, "t2": 2}
+
+
+def sequence_arguments(blocks, ncycles, T):
+    """The schedule of Engine.simulate_dictionary_seq as the library takes it: (EpgBlock array, EpgSeq).  blocks is a sequence of
+    dict(nframes=, prep="none" | "inversion" | "t2", wait=0.0, prep_time=0.0, prep_eff=1.0), 1..64 of them, whose nframes sum to T; ncycles is an
+    integer in 1..16.  The ranges of the numbers are the library's to refuse (include/qmri.h qmri_dict_simulate_seq).  The array must outlive the
+    call that takes the EpgSeq."""
+    blocks = list(blocks)
+    if not (1 <= len(blocks) <= 64):
+        raise ValueError("blocks must hold 1..64 blocks")
+    if int(ncycles) != ncycles or not (1 <= int(ncycles) <= 16):
+        raise ValueError("ncycles must be an integer in 1..16")
+    arr = (EpgBlock * len(blocks))()
+    for i, b in enumerate(blocks):
+        extra = set(b) - {"nframes", "prep", "wait", "prep_time", "prep_eff"}
+        if extra or "nframes" not in b:
+            raise ValueError(f"block {i} must be a dict with nframes and optionally prep, wait, prep_time, prep_eff" + (f", not {sorted(extra)}" if extra else ""))
+        prep = b.get("prep", "none")
+        if prep not in EPG_PREPS:
+            raise ValueError(f'block {i}: prep must be "none", "inversion" or "t2"')
+        if int(b["nframes"]) != b["nframes"] or int(b["nframes"]) < 1:
+            raise ValueError(f"block {i}: nframes must be an integer >= 1")
+        arr[i] = EpgBlock(int(b["nframes"]), EPG_PREPS[prep], float(b.get("wait", 0.0)), float(b.get("prep_time", 0.0)), float(b.get("prep_eff", 1.0)))
+    if sum(a.nframes for a in arr) != T:
+        raise ValueError(f"the nframes of the blocks must sum to the T = {T} frames of alpha")
+    return arr, EpgSeq(len(blocks), int(ncycles), arr)
 
 
 def fieldmap_arguments(Y, echo_times, iters=0, beta=0.0, phase_sign=-1, f_init=None):
@@ -1483,6 +1512,20 @@ class Engine:
                 "dF": None if dF is None else np.stack([dF[q * K * T:(q + 1) * K * T].reshape((K, T), order="F") for q in range(P)]),
                 "crb": None if crb is None else crb.reshape(K, 1 + P), "flags": flags}
 
+    def simulate_dictionary_seq(self, alpha, tr, te, t1, t2, blocks, ncycles=1, b1=None, nstates=32, dtype=np.float64):
+        """The fingerprints of a prepared, repeated FISP train (extension, no reference counterpart; include/qmri.h qmri_dict_simulate_seq;
+        DESIGN.md section 33).  alpha, tr, te, t1, t2, b1, nstates, dtype: as in simulate_dictionary.  blocks: a sequence of dict(nframes=,
+        prep="none" | "inversion" | "t2", wait=0.0, prep_time=0.0, prep_eff=1.0) whose nframes sum to T -- in front of its frames a block waits
+        `wait` seconds (free relaxation), then plays its preparation (inversion: TI = prep_time, efficiency prep_eff; T2 preparation: echo time
+        prep_time, scale prep_eff; idealised, not scaled by b1).  The block list is played ncycles times from equilibrium and the last cycle is
+        recorded.  synth.repeated_train_blocks and synth.cmrf_blocks make block lists.  Returns F [K, T] in dtype.  Needs no operator."""
+        a, trv, tev, T1, T2, B1, p = simulation_arguments(alpha, tr, te, t1, t2, b1, nstates, False, 0.0, 1.0, dtype)
+        K, T = T1.size, a.size
+        arr, seq = sequence_arguments(blocks, ncycles, T)
+        F = np.empty(K * T, np.float64 if p.out_is_f64 else np.float32)
+        self._check(self.L.qmri_dict_simulate_seq(self.h, K, T, _vp(a), _vp(trv), _vp(tev), _vp(T1), _vp(T2), _vp(B1), C.byref(p), C.byref(seq), _vp(F)))
+        return F.reshape((K, T), order="F")
+
     def dictionary_crb(self, alpha, tr, te, t1, t2, b1=None, wrt=("t1", "t2"), V=None, nstates=32, inversion=True, ti=0.0, inv_eff=1.0):
         """The Cramer-Rao bound of simulate_dictionary_grad alone: no K x T array is made, on the device or the host.  Returns dict(crb [K, 1 + P],
         flags [K])."""
@@ -1491,14 +1534,21 @@ class Engine:
         return {"crb": r["crb"], "flags": r["flags"]}
 
     def simulate_compress_dictionary(self, alpha, tr, te, t1, t2, b1=None, s=None, energy=None, s_max=16, nstates=32, inversion=True, ti=0.0,
-                                     inv_eff=1.0, slice_profile=None, slice_weights=None):
+                                     inv_eff=1.0, slice_profile=None, slice_weights=None, blocks=None, ncycles=1):
         """simulate_dictionary followed by compress_dictionary on the same device buffer: the K x T float64 fingerprints never leave the device.
-        slice_profile / slice_weights: as in simulate_dictionary.  Returns what compress_dictionary returns."""
+        slice_profile / slice_weights: as in simulate_dictionary.  blocks / ncycles: the fingerprints are those of simulate_dictionary_seq
+        (qmri_dict_simulate_seq_dev on the same buffer); inversions are then stated in the blocks and inversion / ti / inv_eff are not used; not
+        available with a slice profile.  Returns what compress_dictionary returns."""
         if (s is None) == (energy is None):
             raise ValueError("give exactly one of s and energy")
+        if blocks is not None and (slice_profile is not None or slice_weights is not None):
+            raise ValueError("blocks are not available with a slice profile")
+        if blocks is not None:
+            inversion, ti, inv_eff = False, 0.0, 1.0
         a, trv, tev, T1, T2, B1, p = simulation_arguments(alpha, tr, te, t1, t2, b1, nstates, inversion, ti, inv_eff, np.float64)
         K, T = T1.size, a.size
         sp = slice_profile_arguments(slice_profile, slice_weights, T)
+        sq = None if blocks is None else sequence_arguments(blocks, ncycles, T)
         if s is not None and (int(s) != s or not (1 <= int(s) <= min(16, K, T))):
             raise ValueError(f"s must be an integer with 1 <= s <= min(16, K, T) = {min(16, K, T)}")
         if s is None and (int(s_max) != s_max or not (1 <= int(s_max) <= 16) or not (0.0 < float(energy) <= 1.0)):
@@ -1516,7 +1566,10 @@ class Engine:
             for d, h in ((d_t1, T1), (d_t2, T2)) + (((d_b1, B1),) if B1 is not None else ()):
                 if hip.hipMemcpy(d, _vp(h), h.nbytes, 1) != 0:
                     raise RuntimeError("hipMemcpy to the device failed")
-            if sp is None:
+            if sq is not None:
+                self._check(self.L.qmri_dict_simulate_seq_dev(self.h, K, T, _vp(a), _vp(trv), _vp(tev), d_t1, d_t2, d_b1 if B1 is not None else None, C.byref(p),
+                                                              C.byref(sq[1]), d_F))
+            elif sp is None:
                 self._check(self.L.qmri_dict_simulate_dev(self.h, K, T, _vp(a), _vp(trv), _vp(tev), d_t1, d_t2, d_b1 if B1 is not None else None, C.byref(p), d_F))
             else:
                 self._check(self.L.qmri_dict_simulate_sp_dev(self.h, K, T, _vp(a), _vp(trv), _vp(tev), d_t1, d_t2, d_b1 if B1 is not None else None, C.byref(p),

@@ -80,7 +80,7 @@ def compress_dictionary(dic, s=None, energy=None, s_max=16, device=0):
 
 
 def simulate_dictionary(alpha, tr, te, t1_grid, t2_grid, s=None, energy=None, nstates=32, inversion=True, ti=0.0, inv_eff=1.0, b1=None, s_max=16,
-                        device=0, b1_grid=None, slice_profile=None, slice_weights=None, crb=False):
+                        device=0, b1_grid=None, slice_profile=None, slice_weights=None, crb=False, blocks=None, ncycles=1):
     """A FISP-MRF dictionary from a flip-angle train: the fingerprints of every (T1, T2) of the grid by extended phase graphs
     (Engine.simulate_dictionary), then their SVD compression (Engine.compress_dictionary) on the same device buffer -- the K x T fingerprints
     never cross to the host.  An extension; the reference only loads compressed files.  The atoms are the ij-meshgrid of t1_grid and t2_grid as
@@ -95,8 +95,16 @@ def simulate_dictionary(alpha, tr, te, t1_grid, t2_grid, s=None, energy=None, ns
     atom order, lut and groups unchanged.
     crb=True: after the compression the Cramer-Rao bound of every atom in the dictionary's own subspace V (Engine.dictionary_crb, DESIGN.md
     section 32; with respect to (T1, T2), and b1 as well with b1_grid) is added as crb [K, 1 + P] and crb_flags [K]; uncertainty_maps turns them
-    into per-pixel standard deviations.  Not available with a slice profile.  The default returns exactly the dict described above."""
+    into per-pixel standard deviations.  Not available with a slice profile.  The default returns exactly the dict described above.
+    blocks (with ncycles): the fingerprints are those of a prepared, repeated train (Engine.simulate_dictionary_seq; DESIGN.md section 33;
+    synth.repeated_train_blocks and synth.cmrf_blocks make block lists) -- inversions are then stated in the blocks and inversion / ti / inv_eff
+    are not used; everything after the simulation (compression, b1_grid groups, lut) is unchanged.  The schedule has neither a slice-profile nor a
+    derivative form: blocks together with slice_profile or crb=True is refused."""
     from .engine import Engine
+    if blocks is not None and (slice_profile is not None or slice_weights is not None):
+        raise ValueError("blocks are not available with a slice profile: qmri_dict_simulate_seq has no slice-profile form")
+    if blocks is not None and crb:
+        raise ValueError("blocks are not available with crb=True: qmri_dict_simulate_seq has no derivative form")
     if crb and (slice_profile is not None or slice_weights is not None):
         raise ValueError("crb=True is not available with a slice profile")
     t1g, t2g = np.asarray(t1_grid, dtype=np.float64).ravel(), np.asarray(t2_grid, dtype=np.float64).ravel()
@@ -112,6 +120,8 @@ def simulate_dictionary(alpha, tr, te, t1_grid, t2_grid, s=None, energy=None, ns
         T1, T2, b1 = np.tile(T1, bg.size), np.tile(T2, bg.size), np.repeat(bg, n)                # group-major
         groups = {"group_ptr": (np.arange(bg.size + 1) * n).astype(np.int32), "group_val": bg.copy()}
     sp = {} if slice_profile is None and slice_weights is None else {"slice_profile": slice_profile, "slice_weights": slice_weights}
+    if blocks is not None:
+        sp = {"blocks": blocks, "ncycles": ncycles}
     eng = Engine(device)
     try:
         out = eng.simulate_compress_dictionary(alpha, tr, te, T1, T2, b1=b1, s=s, energy=energy, s_max=s_max, nstates=nstates, inversion=inversion,

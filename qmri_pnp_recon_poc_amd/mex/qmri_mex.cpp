@@ -33,6 +33,7 @@
 //   * 'dict_compress' compresses a simulated dictionary to its SVD subspace (qmri_dict_compress; extension); it needs no plan.
 //   * 'dict_simulate' simulates the fingerprints of a FISP-MRF sequence by extended phase graphs (qmri_dict_simulate; extension); it needs no plan.
 //   * 'dict_simulate_sp' is 'dict_simulate' integrated over a slice profile (qmri_dict_simulate_sp; extension); it needs no plan.
+//   * 'dict_simulate_seq' simulates a prepared, repeated FISP train, block by block (qmri_dict_simulate_seq; extension); it needs no plan.
 //   * 'dict_simulate_grad' is 'dict_simulate' with the derivatives of the fingerprints and their Cramer-Rao bound (qmri_dict_simulate_grad;
 //     extension); it needs no plan.
 //   * 'set_llr' / 'clear_llr' select the locally low-rank proximal step as Step 2 of 'pnp_admm' (qmri_set_llr; extension), which
@@ -1070,6 +1071,59 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         mxArray* Fo = mxCreateNumericMatrix(K, T, p.out_is_f64 ? mxDOUBLE_CLASS : mxSINGLE_CLASS, mxREAL);
         const int st = qmri_dict_simulate_sp(ctx(), (int)K, (int)T, mxGetDoubles(prhs[1]), sched[0].data(), sched[1].data(), mxGetDoubles(prhs[4]),
                                              mxGetDoubles(prhs[5]), has_b1 ? mxGetDoubles(prhs[6]) : nullptr, &p, &sp, mxGetData(Fo));
+        if (st != QMRI_OK) mxDestroyArray(Fo);
+        check(st);
+        plhs[0] = Fo;
+    } else if (c == "dict_simulate_seq") {           // F = qmri_mex('dict_simulate_seq', alpha, tr, te, t1, t2, b1, params, blocks, ncycles)
+        // extension (no reference counterpart): the fingerprints of a prepared, repeated FISP train (qmri_dict_simulate_seq).
+        // The first six arguments are those of 'dict_simulate'; params takes nstates (32) and single (0).  blocks: a real double 5 x B matrix,
+        // 1 <= B <= 64, one column per block: nframes; prep (0 none, 1 inversion, 2 T2 preparation); wait; prep_time; prep_eff -- what
+        // matlab/qmri_dict_simulate_seq.m makes of its struct array.  ncycles: an integer in [1, 16].  F is K x T.
+        need(nrhs, 10, "F = qmri_mex('dict_simulate_seq', alpha, tr, te, t1, t2, b1, params, blocks, ncycles)");
+        want(mxIsStruct(prhs[7]), "qmri:dict_simulate_seq:params", "params must be a struct (fields nstates, single)");
+        auto real_vec = [](const mxArray* a, const char* id, const char* msg) {
+            want(mxIsDouble(a) && !mxIsComplex(a), id, msg);
+            return mxGetNumberOfElements(a);
+        };
+        const size_t T = real_vec(prhs[1], "qmri:dict_simulate_seq:alpha", "alpha must be a real double vector (complex flip angles are not supported)");
+        want(T >= 1 && T <= 1024, "qmri:dict_simulate_seq:alpha", "alpha must hold 1 <= T <= 1024 flip angles");
+        std::vector<double> sched[2];
+        const char* sid[2] = {"qmri:dict_simulate_seq:tr", "qmri:dict_simulate_seq:te"};
+        for (int q = 0; q < 2; ++q) {
+            const size_t n = real_vec(prhs[2 + q], sid[q], "tr / te must be real double, one value or one per frame");
+            want(n == 1 || n == T, sid[q], "tr / te must be real double, one value or one per frame");
+            sched[q].resize(T);
+            for (size_t t = 0; t < T; ++t) sched[q][t] = mxGetDoubles(prhs[2 + q])[n == 1 ? 0 : t];
+        }
+        const char* aid = "qmri:dict_simulate_seq:atoms";
+        const size_t K = real_vec(prhs[4], aid, "t1, t2 and b1 must be real double (complex values are not supported)");
+        want(K >= 1 && K <= ((size_t)1 << 30) && real_vec(prhs[5], aid, "t1, t2 and b1 must be real double (complex values are not supported)") == K, aid,
+             "t1 and t2 must hold the same number K >= 1 of atoms");
+        const bool has_b1 = mxGetNumberOfElements(prhs[6]) > 0;
+        if (has_b1) want(real_vec(prhs[6], aid, "t1, t2 and b1 must be real double (complex values are not supported)") == K, aid, "b1 must be [] or hold K values");
+        const mxArray* P = prhs[7];
+        const mxArray* f;
+        const char* pid = "qmri:dict_simulate_seq:params";
+        qmri_epg_params p = {32, 0, 0.0, 1.0, 1};
+        if ((f = mxGetField(P, 0, "nstates"))) p.nstates = int_arg(f, 1, 256, pid, "params.nstates must be an integer in [1, 256]");
+        if ((f = mxGetField(P, 0, "single"))) p.out_is_f64 = 1 - int_arg(f, 0, 1, pid, "params.single must be 0 or 1");
+        const char* bid = "qmri:dict_simulate_seq:blocks";
+        const size_t nb = real_vec(prhs[8], bid, "blocks must be a real double 5 x B matrix, 1 <= B <= 64");
+        want(mxGetM(prhs[8]) == 5 && nb >= 5 && nb <= 5 * 64, bid, "blocks must be a real double 5 x B matrix, 1 <= B <= 64");
+        const size_t B = nb / 5;
+        std::vector<qmri_epg_block> blocks(B);
+        for (size_t b = 0; b < B; ++b) {
+            const double* col = mxGetDoubles(prhs[8]) + 5 * b;
+            // the two integers are checked before the cast; the three times are the library's to refuse
+            want(std::isfinite(col[0]) && col[0] == std::floor(col[0]) && col[0] >= 1.0 && col[0] <= 1024.0, bid, "blocks(1, :) (nframes) must be integers in [1, 1024]");
+            want(std::isfinite(col[1]) && col[1] == std::floor(col[1]) && col[1] >= 0.0 && col[1] <= 2.0, bid, "blocks(2, :) (prep) must be 0, 1 or 2");
+            blocks[b] = {(int32_t)col[0], (int32_t)col[1], col[2], col[3], col[4]};
+        }
+        const int ncycles = int_arg(prhs[9], 1, 16, "qmri:dict_simulate_seq:ncycles", "ncycles must be an integer in [1, 16]");
+        const qmri_epg_seq seq = {(int32_t)B, ncycles, blocks.data(), {0, 0, 0, 0}};
+        mxArray* Fo = mxCreateNumericMatrix(K, T, p.out_is_f64 ? mxDOUBLE_CLASS : mxSINGLE_CLASS, mxREAL);
+        const int st = qmri_dict_simulate_seq(ctx(), (int)K, (int)T, mxGetDoubles(prhs[1]), sched[0].data(), sched[1].data(), mxGetDoubles(prhs[4]),
+                                              mxGetDoubles(prhs[5]), has_b1 ? mxGetDoubles(prhs[6]) : nullptr, &p, &seq, mxGetData(Fo));
         if (st != QMRI_OK) mxDestroyArray(Fo);
         check(st);
         plhs[0] = Fo;

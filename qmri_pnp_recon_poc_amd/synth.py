@@ -115,6 +115,39 @@ def train_crb_score(alpha, tr, te, t1, t2, b1=None, wrt=("t1", "t2"), V=None, ns
     return crb_score(r["crb"], r["flags"], atoms[:len(tuple(wrt))])
 
 
+def repeated_train_blocks(T: int, pause_s: float):
+    """The block list of one train of T frames that is repeated with a pause of pause_s seconds in between (3-D, interleaved multi-slice and SMS
+    MRF), for Engine.simulate_dictionary_seq / harness.simulate_dictionary(blocks=): one block of T frames without a
+    preparation whose wait is the pause.  The caller picks ncycles: the number of repetitions after which the recorded one is taken as the driven
+    steady state.  Pure host code."""
+    if int(T) != T or int(T) < 1 or not (np.isfinite(pause_s) and float(pause_s) >= 0.0):
+        raise ValueError("T must be an integer >= 1 and pause_s finite and >= 0")
+    return [dict(nframes=int(T), prep="none", wait=float(pause_s), prep_time=0.0, prep_eff=1.0)]
+
+
+def cmrf_blocks(rr_s, frames_per_beat: int, tr_s: float, preps=(("inversion", 0.021), ("none", 0.0), ("t2", 0.040), ("t2", 0.080))):
+    """The block list of a cardiac MRF scan (Hamilton et al. 2017), for Engine.simulate_dictionary_seq / harness.simulate_dictionary(blocks=)
+    (DESIGN.md section 33): one block per heartbeat, each of frames_per_beat frames of tr_s seconds behind a preparation; the preparations cycle
+    through preps, pairs (kind, prep_time in seconds) with kind "inversion", "none" or "t2".  rr_s: the len(rr_s) RR intervals of the scan in
+    seconds, beat b starting rr_s[b - 1] after beat b - 1; there are len(rr_s) beats, and the last interval is not used.  The wait of beat b >= 1
+    is what the interval leaves, rr_s[b - 1] - frames_per_beat tr_s - prep_time_b, and that of beat 0 is 0; a negative wait raises ValueError
+    naming the beat.  Pure host code."""
+    rr = np.asarray(rr_s, dtype=np.float64).ravel()
+    preps = [(str(k), float(t)) for k, t in preps]
+    if rr.size < 1 or not np.all(np.isfinite(rr)) or int(frames_per_beat) != frames_per_beat or int(frames_per_beat) < 1 or not (float(tr_s) > 0.0):
+        raise ValueError("rr_s must hold at least one finite interval, frames_per_beat must be an integer >= 1 and tr_s > 0")
+    if not preps or any(k not in ("inversion", "none", "t2") or not (np.isfinite(t) and t >= 0.0) or (k == "none" and t != 0.0) for k, t in preps):
+        raise ValueError('preps must hold pairs (kind, prep_time >= 0) with kind "inversion", "none" (prep_time 0) or "t2"')
+    blocks = []
+    for b in range(rr.size):
+        kind, pt = preps[b % len(preps)]
+        wait = 0.0 if b == 0 else float(rr[b - 1]) - int(frames_per_beat) * float(tr_s) - pt
+        if wait < 0.0:
+            raise ValueError(f"beat {b}: the RR interval {rr[b - 1]} s is shorter than its {frames_per_beat} frames of {tr_s} s and the {pt} s preparation")
+        blocks.append(dict(nframes=int(frames_per_beat), prep=kind, wait=wait, prep_time=pt, prep_eff=1.0))
+    return blocks
+
+
 def make_dictionary(T: int = 200, n_t1: int = 128, n_t2: int = 64, s: int = 10, seed: int = 0, uncompressed: bool = False) -> dict:
     """Synthetic MRF dictionary with K = n_t1*n_t2 atoms.
 
